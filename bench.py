@@ -1,7 +1,16 @@
 #!/usr/bin/env python3
 """bench.py — Groth16 (BLS12-381) proofs/s + constraints/s on the reference's matrix-mul circuit, MI355X HIP path (libzkg16.so).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline figure needs: setup (synthesis, real key, window tables), W warm-up proofs, K timed
+proofs, the pairing check of the last one, the outputs of the last timed proof if --dump-outputs is given, and one JSON line.
+Everything else the line can carry (the plain-key figure, the other workloads as legs, the end-to-end request legs, callers in
+flight, the CPU baseline, per-stage times, roofline / alu figures) runs only with --full.
+
+--dump-outputs DIR writes what the last timed step returned to its caller: DIR/proof.npy (the 48 proof words A | B | C, affine
+Montgomery limbs, each split into its low and high 32-bit halves: float64, shape (48, 2), exact) and DIR/infinity.npy (the three
+infinity flags, float64).  The key, the witness and every r, s are seeded, so the same arguments give the same proof on every run.
 
 N > 1 without a torch.distributed environment: this process only spawns
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py <same flags>` as a CHILD
@@ -15,7 +24,7 @@ Workload at N = 1 = the LARGEST single-GPU configuration of BASELINE.json: Matri
 constraints, 8,675,313 witness variables, domain 2^24 — synthesized by the C++ mirror of the reference's circuit on the
 reference bench's all-ones inputs (bench/matrix.py:11).  The key is a REAL Groth16 key (zkg16_setup_resident from a seeded
 trapdoor), and the last proof of the timed region is VERIFIED with the pairing verifier (zkg16_verify) after the region:
-`proof_verified`; a failure exits non-zero.  Extra legs in the same JSON line (N = 1): the 46x46 (largest 2^20 domain) and
+`proof_verified`; a failure exits non-zero.  Extra legs in the same JSON line (N = 1, --full): the 46x46 (largest 2^20 domain) and
 32x32 (configs[1]) circuits, each verified; `end_to_end` = what the reference times as `proving_time` (host synthesis + the
 host-pointer entry zkg16_prove); `cpu_baseline` = the CPU oracle (a port, oracle/) timed directly on the 32x32 circuit on all
 host threads — its proof must equal the GPU's 32x32 proof bit for bit (`oracle_match`) — and on one thread at 16x16.
@@ -25,7 +34,7 @@ witness map and share h_query; every rank takes the share of the z-side index ra
 exchange per proof — an all_gather of 77 words of partial sums over RCCL — and the tail on every rank: strong scaling.
 `--parallel replicas`: every rank proves its own proofs on the whole key, no exchange (weak scaling).
 
-Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel (msm_accumulate_g1) from HIP-event pairs recorded on
+Prints ONE JSON line (rank 0).  With --full, `roofline` is for the dominant kernel (msm_accumulate_g1) from HIP-event pairs recorded on
 the library's own stream during the timed region; `traffic` / `alu.peak` are read from the profile summaries committed under
 profiles/ for this configuration (null when there is none).
 """
@@ -55,10 +64,10 @@ def parse():
     ap.add_argument("--workload", default="matrix", choices=["matrix", "prime"],
                     help="matrix = the reference's MatrixCircuit (metric workload); prime = the reference's PrimeCircuit (configs[4])")
     ap.add_argument("--legs", default="46,32,prime,fib1000",
-                    help="N = 1: further workloads measured after the timed region (comma list, '' = none): a number = that matrix size; "
+                    help="N = 1, --full: further workloads measured after the timed region (comma list, '' = none): a number = that matrix size; "
                          "prime = the reference's PrimeCircuit (BASELINE configs[4]); fibN = FibonacciCircuit with N rounds (configs[0])")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the end-to-end (host synthesis + host-pointer prove) leg")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and the oracle comparisons of the legs")
+    ap.add_argument("--no-e2e", action="store_true", help="--full: skip the end-to-end (host synthesis + host-pointer prove) leg")
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL, one GPU per rank) | gloo (rehearsal: several ranks on one GPU)")
     ap.add_argument("--cpu-sample-n", type=int, default=32, help="matrix size the CPU baseline proves on all threads")
     ap.add_argument("--cpu-1t-n", type=int, default=16, help="matrix size the CPU baseline proves on one thread")
@@ -67,16 +76,24 @@ def parse():
                          "replicas = every rank proves its own proofs on the whole key (no exchange; weak scaling)")
     ap.add_argument("--h-ranks", type=int, default=0, help="N > 1, shard: ranks that run the witness map (0 = cost model; N = equal split)")
     ap.add_argument("--in-flight", type=int, default=2,
-                    help="N = 1: after the timed region, also report throughput with this many callers on the one ctx (its lanes share the key; 0 = skip)")
+                    help="N = 1, --full: after the timed region, also report throughput with this many callers on the one ctx (its lanes share the key; 0 = skip)")
     ap.add_argument("--replicas-leg", action="store_true",
                     help="N > 1, shard: after the timed sharded region also time every rank proving its own proofs on the whole key (weak "
                          "scaling; keeps the whole key + its tables on every rank, so off by default: the timed leg must not be lost to it)")
     ap.add_argument("--no-replicas-leg", action="store_true", help="(default since round 3; accepted for older command lines)")
     ap.add_argument("--tables", default="auto", choices=["auto", "on", "off"],
-                    help="auto = window tables for the resident key (zkg16_pk_precompute; the plain key is timed first and reported "
-                         "beside it); on = the same without the plain-key proofs (profiling runs); off = plain key only")
+                    help="auto = window tables for the resident key (zkg16_pk_precompute; with --full the plain key is timed first and "
+                         "reported beside it); on = the same without the plain-key proofs (profiling runs); off = plain key only")
     ap.add_argument("--seed", type=int, default=2026)
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure: the plain-key figure (--tables auto), --legs, "
+                         "the end-to-end legs, --in-flight, the CPU baseline, per-stage times and the roofline / alu figures")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed proof as DIR/proof.npy and DIR/infinity.npy (float64; see the module docstring)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def spawn_ranks(args):
@@ -129,6 +146,14 @@ def synthesize(workload, n, x=None):
         desc = ("matrix-mul %dx%d + Poseidon MatrixCircuit: %d constraints, %d witness vars, domain 2^%d"
                 % (n, n, circ.num_constraints, circ.num_witness, circ.domain.bit_length() - 1))
     return circ, time.perf_counter() - t0, desc
+
+
+def dump_outputs(d, proof, inf):
+    """--dump-outputs: the proof words as exact float64 32-bit halves (low, high) and the infinity flags."""
+    os.makedirs(d, exist_ok=True)
+    w = np.asarray(proof, dtype=np.uint64).reshape(48)
+    np.save(os.path.join(d, "proof.npy"), np.stack([w & np.uint64(0xFFFFFFFF), w >> np.uint64(32)], axis=1).astype(np.float64))
+    np.save(os.path.join(d, "infinity.npy"), np.asarray(inf, dtype=np.float64).reshape(3))
 
 
 def profile_lookup(key):
@@ -252,7 +277,8 @@ def main():
     rs = [(fr_mont(int.from_bytes(rng.bytes(31), "little")), fr_mont(int.from_bytes(rng.bytes(31), "little"))) for _ in range(args.steps + args.warmup + 2)]
 
     def with_tables(d, pk_h, prove_once, plain_steps=0):
-        """Window tables for a key that stays resident; the plain key is timed first (a few proofs) so both appear in the line."""
+        """Window tables for a key that stays resident; with prove_once (--full) the plain key is timed first (a few proofs) so both
+        appear in the line."""
         if args.tables == "off":
             return None
         plain_ms, plain = None, None
@@ -284,7 +310,8 @@ def main():
                 "plain_key": plain,
                 "note": "zkg16_pk_precompute: 2^(c w) multiples of every base kept in HBM, all digits of a scalar in one bucket set per MSM; "
                         "same proofs bit for bit (tests/test_gpu_parity.py::test_window_tables_*); built once per resident key"}
-    tables_info = with_tables(dev, ph, (lambda: dev.prove_resident(ph, rh, wh, *rs[0])) if world == 1 else None, plain_steps=args.steps)
+    tables_info = with_tables(dev, ph, (lambda: dev.prove_resident(ph, rh, wh, *rs[0])) if (world == 1 and args.full) else None,
+                              plain_steps=args.steps)
 
     xdev = "cuda" if on_gpu else "cpu"
     if sharded:
@@ -310,8 +337,9 @@ def main():
     proof = inf = None
     for i in range(args.warmup):
         proof, inf = one_proof(*rs[i])
-    dev.kernel_stats_reset()
-    dev.kernel_timing(2)             # async HIP-event pairs around the bucket accumulations (the roofline kernel) on the
+    if args.full:
+        dev.kernel_stats_reset()
+        dev.kernel_timing(2)         # async HIP-event pairs around the bucket accumulations (the roofline kernel) on the
                                      # library's own streams; resolved after the timed region
     gc.collect()
     gc.disable()                     # no cyclic collection inside the timed region (see with_tables)
@@ -322,7 +350,8 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
     gc.enable()
-    dev.kernel_timing(False)
+    if args.full:
+        dev.kernel_timing(False)
     per_rank = None
     if world > 1:
         # every rank's own time of the timed region, so that the curve can be read against the per-shard predictions
@@ -341,16 +370,20 @@ def main():
         flag = torch.tensor([1 if verified else 0], dtype=torch.int64, device=xdev)
         dist.all_reduce(flag, op=dist.ReduceOp.MIN)
         verified = bool(flag.item())
-    stages = dev.last_timings()
-    term_counts = dev.last_term_counts()          # sorted term-list lengths of the last proof: exact mixed additions per MSM
-    acc = dev.kernel_stats("msm_accumulate_g1")
-    acc2 = dev.kernel_stats("msm_accumulate_g2")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, proof, inf)
+    stages = term_counts = acc = acc2 = acc_waves = None
+    if args.full:
+        stages = dev.last_timings()
+        term_counts = dev.last_term_counts()      # sorted term-list lengths of the last proof: exact mixed additions per MSM
+        acc = dev.kernel_stats("msm_accumulate_g1")
+        acc2 = dev.kernel_stats("msm_accumulate_g2")
+        acc_waves = dev.last_acc_waves()
 
     tabled = bool(tables_info and (tables_info["window_bits_z"] or tables_info["window_bits_h"]))
     cfg_key = ("n%d" % args.matrix_n if args.workload == "matrix" else args.workload) + ("_tables" if tabled else "")
-    acc_waves = dev.last_acc_waves()
     extra_out = {}
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         # ---- stand-alone witness map and one transform of the workload's domain (second kernel family of the path)
         try:
             log_n = shp["domain"].bit_length() - 1
@@ -522,7 +555,7 @@ def main():
                         "contract's timed region" % args.in_flight}
 
     in_flight = None
-    if world == 1 and args.in_flight > 1:
+    if world == 1 and args.in_flight > 1 and args.full:
         try:
             in_flight = callers_on_one_ctx(ph, rh, wh, max(args.steps, 4), args.steps / dt)
         except Exception as e:      # noqa: BLE001
@@ -531,7 +564,7 @@ def main():
     # ---- free the headline workload before the smaller legs
     headline_z = circ.z
     headline_gpu_proof = None
-    if world == 1 and not args.no_cpu_baseline and args.workload == "matrix" and args.cpu_sample_n == args.matrix_n:
+    if world == 1 and args.full and not args.no_cpu_baseline and args.workload == "matrix" and args.cpu_sample_n == args.matrix_n:
         headline_gpu_proof = dev.prove_resident(ph, rh, wh, *rs[-1])      # what the CPU baseline's proof of the headline circuit must equal
     for f, h in ((dev.pk_free, ph), (dev.witness_free, wh), (dev.r1cs_free, rh)):
         f(h)
@@ -541,7 +574,7 @@ def main():
     gpu_proofs = {}                 # matrix size -> the GPU's proof for (key_inputs, rs[-1]): what the CPU baseline's proof must equal
     if headline_gpu_proof is not None:
         gpu_proofs[args.matrix_n] = headline_gpu_proof
-    if rank == 0 and world == 1 and args.workload == "matrix":
+    if rank == 0 and world == 1 and args.full and args.workload == "matrix":
         for leg in [x.strip() for x in args.legs.split(",") if x.strip()]:
             try:
                 wl, n = ("matrix", int(leg)) if leg.isdigit() else (leg, 0)
@@ -600,14 +633,6 @@ def main():
 
     if rank == 0:
         total_proofs = args.steps * (world if (world > 1 and not sharded) else 1)
-        # algorithmic bytes of one G1 bucket-accumulation launch: every (base, scalar) term once = (96 + 32) B per term
-        # (SURVEY.md 8d); terms per launch = what the launches of this rank actually processed (event-pair units)
-        launches = max(acc["launches"], 1)
-        terms_per_launch = acc["units"] / launches
-        alg_bytes = 128.0 * terms_per_launch
-        avg_ms = acc["ms"] / launches
-        achieved = alg_bytes / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
-        traffic = profile_lookup([cfg_key, "msm_accumulate_g1_traffic_bytes"]) if world == 1 else None
         out = {
             "metric": "groth16_proofs_per_sec", "value": total_proofs / dt, "unit": "proofs/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
@@ -623,15 +648,25 @@ def main():
                                        "%d replicas: every GPU proves its own proofs on the whole key, no exchange" % world)},
             "constraints_per_sec": shp["nc"] * total_proofs / dt,
             "setup_resident_s": setup_s, "host_synthesis_s": synth_s,
-            "stage_ms_last_proof": stages,
-            "roofline": {"bound": "hbm", "kernel": "msm_accumulate_g1", "achieved": achieved, "peak": 8000.0, "unit": "GB/s",
-                         "frac": achieved / 8000.0, "traffic": traffic,
-                         "avg_launch_ms": avg_ms, "launches": acc["launches"], "algorithmic_bytes_per_launch": alg_bytes,
-                         "terms_per_launch": terms_per_launch,
-                         "note": "integer-ALU bound by construction: one XYZZ mixed addition = 8 products + 2 squarings in Fq (3,542 "
-                                 "v_mad_u64_u32) per window per 128 algorithmic bytes; traffic = PMC FETCH+WRITE of the same command from "
-                                 "profiles/ (one 96-byte base or table entry gathered per (scalar, window) term); g2 accumulate avg %.3f ms" % (acc2["ms"] / max(acc2["launches"], 1))},
         }
+        if args.full:
+            # algorithmic bytes of one G1 bucket-accumulation launch: every (base, scalar) term once = (96 + 32) B per term
+            # (SURVEY.md 8d); terms per launch = what the launches of this rank actually processed (event-pair units)
+            launches = max(acc["launches"], 1)
+            terms_per_launch = acc["units"] / launches
+            alg_bytes = 128.0 * terms_per_launch
+            avg_ms = acc["ms"] / launches
+            achieved = alg_bytes / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
+            traffic = profile_lookup([cfg_key, "msm_accumulate_g1_traffic_bytes"]) if world == 1 else None
+            out["stage_ms_last_proof"] = stages
+            out["roofline"] = {"bound": "hbm", "kernel": "msm_accumulate_g1", "achieved": achieved, "peak": 8000.0, "unit": "GB/s",
+                               "frac": achieved / 8000.0, "traffic": traffic,
+                               "avg_launch_ms": avg_ms, "launches": acc["launches"], "algorithmic_bytes_per_launch": alg_bytes,
+                               "terms_per_launch": terms_per_launch,
+                               "note": "integer-ALU bound by construction: one XYZZ mixed addition = 8 products + 2 squarings in Fq (3,542 "
+                                       "v_mad_u64_u32) per window per 128 algorithmic bytes; traffic = PMC FETCH+WRITE of the same command from "
+                                       "profiles/ (one 96-byte base or table entry gathered per (scalar, window) term); g2 accumulate avg %.3f ms"
+                                       % (acc2["ms"] / max(acc2["launches"], 1))}
         if plan is not None:
             out["config"]["shard_plan"] = [{"rank": i, "z": [p[0], p[1]], "h": [p[2], p[3]], "blinding": p[4],
                                             "role": ("witness map + h share" if p[3] > p[2] else "") + (" + " if p[3] > p[2] and p[1] > p[0] else "") +
@@ -642,7 +677,7 @@ def main():
             out["slowest_rank"] = int(np.argmax(per_rank))
         # the bound that does apply: mixed additions per second against the same addition in a bare register-resident loop
         nshard = world if sharded else 1
-        if world == 1:
+        if world == 1 and args.full:
             one = fr_mont(1)
             zz = np.asarray(headline_z, dtype=np.uint64).reshape(-1, 4)
             n_one = int(np.all(zz == one, axis=1).sum())
@@ -700,7 +735,7 @@ def main():
             out["legs"] = legs
         if in_flight:
             out["throughput_in_flight"] = in_flight
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(dev, args, gpu_proofs, key_inputs, rs[-1], shp["nc"])
             except Exception as e:      # noqa: BLE001
