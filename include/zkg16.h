@@ -349,7 +349,8 @@ ZKG16_API void zkg16_kernel_stats_reset(zkg16_ctx *ctx);
  *   "acc_pipeline"   bit 0 / 1: G1 / G2 accumulation gathers the next base behind the last (inlined) product; 4 = off, 0 = default (both)
  *   "wm_concurrent"  0 = witness map in order on the main stream (default: own stream)  "fixup_aux"      1 = fix-ups on the reduction stream
  *   "g1_waves"       G1 accumulation waves per SIMD in the resident round (0 = 2)       "min_seg"        shortest per-lane run (0 = adaptive)
- *   "ntt_mode"       0 = saturated-limb butterflies (first version), 1 = unsaturated (default)
+ *   "ntt_mode"       0 = saturated-limb butterflies (first version), 1 = unsaturated (default), 3 = unsaturated, but 2^23 and
+ *                    2^24 by three passes over 2048-point tiles instead of two over 4096-point tiles
  *   "ntt_radix"      1 (default; also 0) = the last seven butterfly stages of a tile by lane exchanges, 3 = the top seven as well,
  *                    2 = every stage through the LDS, 4 = two stages per LDS trip
  *   "fuse_pointwise" 1 (default) = (ab - c)/Z fused into the load of the seventh transform, 0 = its own pass

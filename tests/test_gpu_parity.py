@@ -57,7 +57,8 @@ def test_ntt_full_size(dev, oracle, log_n):
 
 @pytest.mark.parametrize("log_n", [23, 24])
 def test_ntt_three_pass(dev, oracle, log_n):
-    """Domains above 2^22 (the literal 128x128 config needs 2^24) take a third pass: oracle equality + round trip."""
+    """Domains above 2^22 (the literal 128x128 config needs 2^24): by default two passes over 4096-point tiles (the three-pass
+    plan and the other variants are in test_ntt_plans.py): oracle equality + round trip."""
     rng = np.random.default_rng(log_n)
     n = 1 << log_n
     a = oracle.fr_from_canonical(rng.integers(0, 1 << 62, size=(n, 4), dtype=np.uint64))
@@ -396,7 +397,7 @@ def test_full_size_request_verifies(dev, n):
     b = rng.integers(0, 1 << 32, size=(n, n), dtype=np.uint64)
     res = handlers.prove_matrix(dev, n, a, b, seed=n)
     circ = res["_circuit"]
-    assert circ.domain == {32: 1 << 19, 46: 1 << 20, 128: 1 << 24}[n]      # 128: 10.7 M constraints, the three-pass NTT
+    assert circ.domain == {32: 1 << 19, 46: 1 << 20, 128: 1 << 24}[n]      # 128: 10.7 M constraints, the 4096-point-tile NTT
     assert handlers.verify_proof(res["vk"], circ.public_inputs, res["proof"])["valid"] is True
     bad = circ.public_inputs.copy()
     bad[2] = bad[0]                     # claim hash_c = hash_a

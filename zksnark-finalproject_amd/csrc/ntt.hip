@@ -373,7 +373,10 @@ __device__ __forceinline__ void lds_dif_u(uint32_t *s_data, const uint32_t *s_tw
             s = log_m - 8;
             s_first = s;                                         // (<= 6) the rest is the lower chain, no LDS stage in between
         }
-        if (GTW && tid < 64) {          // (log_m >= 11 on this path) the chain's twiddles, read once per block instead of once per butterfly
+        // (log_m >= 11 on this path) the chain's twiddles, read once per block instead of once per butterfly.  After MODE 3's top
+        // seven stages (s == s_first) no barrier separates this staging from the chain's reads below: that is safe only because
+        // MODE 3 staged the same 64 values, from the same formula, before its own barrier — so this write never changes a word.
+        if (GTW && tid < 64) {
             uint32_t *tws = const_cast<uint32_t *>(s_tw);
             const unsigned nmask = (1u << a.log_n) - 1u;
             unsigned idx = ((unsigned)tid << (log_m - 7)) << (a.log_n - log_m);
