@@ -281,6 +281,18 @@ ZKG16_API int zkg16_matrix_r1cs_host(size_t n, uint64_t *const row_ptr[3], uint3
 ZKG16_API int zkg16_r1cs_matrix(zkg16_ctx *ctx, size_t n, uint64_t *r1cs_handle);
 ZKG16_API int zkg16_r1cs_read(zkg16_ctx *ctx, uint64_t r1cs_handle, uint64_t *const row_ptr[3], uint32_t *const col[3], uint64_t *const coeff[3],
                     size_t *num_instance, size_t *num_constraints, size_t *num_variables, size_t nnz[3]);
+/* ---- the PrimeCircuit of candidate (x, j) WITHOUT synthesising it (csrc/prime_program.hpp): a witness program and the R1CS, recorded
+ * once per process from one sequential build.  Every entry refuses the candidates zkg16_circuit_prime refuses (ZKG16_ERR_UNSUPPORTED).
+ * _host: host loops, the references of the device entries (same bytes as zkg16_circuit_prime + zkg16_circuit_export; z: n_assign =
+ * num_instance + num_witness entries x 4 limbs, Montgomery).  _dims: the dimensions depend on j only (C has one non-zero fewer at j = 0).
+ * zkg16_r1cs_prime: an r1cs handle as from zkg16_r1cs_load of those arrays — a device-to-device copy of the template the ctx keeps
+ * resident (uploaded on first use, freed by zkg16_destroy) plus four coefficients.  zkg16_witness_prime: a witness handle with the bytes
+ * of zkg16_witness_load of that z — the host computes the program's inputs (a few hundred field elements), kernels evaluate the bits. */
+ZKG16_API int zkg16_prime_witness_host(uint64_t x, uint64_t j, uint64_t *z, size_t n_assign);
+ZKG16_API int zkg16_prime_r1cs_dims(uint64_t j, size_t *num_instance, size_t *num_witness, size_t *num_constraints, size_t nnz[3]);
+ZKG16_API int zkg16_prime_r1cs_host(uint64_t x, uint64_t j, uint64_t *const row_ptr[3], uint32_t *const col[3], uint64_t *const coeff[3]);
+ZKG16_API int zkg16_r1cs_prime(zkg16_ctx *ctx, uint64_t x, uint64_t j, uint64_t *r1cs_handle);
+ZKG16_API int zkg16_witness_prime(zkg16_ctx *ctx, uint64_t x, uint64_t j, uint64_t *witness_handle);
 /* native Poseidon sponge hash of n Fr elements (Montgomery) — the public inputs hash_a/b/c of the matrix handler */
 ZKG16_API int zkg16_poseidon_hash(const uint64_t *elems, size_t n, uint64_t out[4]);
 

@@ -84,6 +84,11 @@ SIGNATURES = {
     "zkg16_matrix_r1cs_host": (C.c_int, [sz, C.POINTER(vp * 3), C.POINTER(vp * 3), C.POINTER(vp * 3)]),
     "zkg16_witness_matrix": (C.c_int, [ctxp, sz, u64p, u64p, C.POINTER(H), vp, vp]),
     "zkg16_prove_matrix": (C.c_int, [ctxp, H, H, sz, u64p, u64p, u64p, u64p, u64p, u8p, vp, vp]),
+    "zkg16_prime_witness_host": (C.c_int, [C.c_uint64, C.c_uint64, u64p, sz]),
+    "zkg16_prime_r1cs_dims": (C.c_int, [C.c_uint64, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz * 3)]),
+    "zkg16_prime_r1cs_host": (C.c_int, [C.c_uint64, C.c_uint64, C.POINTER(vp * 3), C.POINTER(vp * 3), C.POINTER(vp * 3)]),
+    "zkg16_r1cs_prime": (C.c_int, [ctxp, C.c_uint64, C.c_uint64, C.POINTER(H)]),
+    "zkg16_witness_prime": (C.c_int, [ctxp, C.c_uint64, C.c_uint64, C.POINTER(H)]),
     "zkg16_matrix_sponge_states": (C.c_int, [sz, u64p, u64p, vp, u64p]),
     "zkg16_ntt": (C.c_int, [ctxp, u64p, sz, C.c_int, C.c_int]),
     "zkg16_msm_g1": (C.c_int, [ctxp, vp, vp, vp, sz, u64p, u8p]),

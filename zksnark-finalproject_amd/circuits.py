@@ -90,6 +90,48 @@ def prime_circuit_handle(x, j):
     return c
 
 
+def prime_dims(j):
+    """The PrimeCircuit's dimensions for candidate index j (zkg16_prime_r1cs_dims; the same for every x) ->
+    dict(num_instance, num_witness, num_constraints, nnz)."""
+    ni, nw, nc = C.c_size_t(), C.c_size_t(), C.c_size_t()
+    nnz = (C.c_size_t * 3)()
+    rc = _lib.load().zkg16_prime_r1cs_dims(j, C.byref(ni), C.byref(nw), C.byref(nc), C.byref(nnz))
+    if rc:
+        raise Zkg16Error(rc, "zkg16_prime_r1cs_dims")
+    return dict(num_instance=ni.value, num_witness=nw.value, num_constraints=nc.value, nnz=tuple(nnz))
+
+
+def prime_witness_host(x, j):
+    """The PrimeCircuit's assignment for candidate (x, j) from the recorded witness program, evaluated on the host
+    (zkg16_prime_witness_host): what Device.witness_prime is tested against -> z [num_vars, 4] (Montgomery)."""
+    d = prime_dims(j)
+    z = np.zeros((d["num_instance"] + d["num_witness"], 4), dtype=np.uint64)
+    rc = _lib.load().zkg16_prime_witness_host(x, j, z.reshape(-1), z.shape[0])
+    if rc:
+        raise Zkg16Error(rc, "zkg16_prime_witness_host")
+    return z
+
+
+def prime_r1cs_host(x, j):
+    """The PrimeCircuit's R1CS for candidate (x, j) from the recorded template (zkg16_prime_r1cs_dims / _host) -> (r1cs dict as
+    SynthesizedCircuit.r1cs, num_witness).  What Device.r1cs_prime is tested against."""
+    lib = _lib.load()
+    ni, nw, nc = C.c_size_t(), C.c_size_t(), C.c_size_t()
+    nnz = (C.c_size_t * 3)()
+    rc = lib.zkg16_prime_r1cs_dims(j, C.byref(ni), C.byref(nw), C.byref(nc), C.byref(nnz))
+    if rc:
+        raise Zkg16Error(rc, "zkg16_prime_r1cs_dims")
+    rp = [np.zeros(nc.value + 1, dtype=np.uint64) for _ in range(3)]
+    col = [np.zeros(max(nnz[m], 1), dtype=np.uint32) for m in range(3)]
+    cf = [np.zeros((max(nnz[m], 1), 4), dtype=np.uint64) for m in range(3)]
+    arr = lambda xs: (C.c_void_p * 3)(*[x.ctypes.data for x in xs])
+    rc = lib.zkg16_prime_r1cs_host(x, j, C.byref(arr(rp)), C.byref(arr(col)), C.byref(arr(cf)))
+    if rc:
+        raise Zkg16Error(rc, "zkg16_prime_r1cs_host")
+    return dict(a=(rp[0], col[0][:nnz[0]], cf[0][:nnz[0]]), b=(rp[1], col[1][:nnz[1]], cf[1][:nnz[1]]),
+                c=(rp[2], col[2][:nnz[2]], cf[2][:nnz[2]]), num_inputs=ni.value, num_constraints=nc.value), nw.value
+
+
 def matrix_circuit(a, b):
     """MatrixCircuit for u64 matrices a, b (n x n lists/arrays); public inputs = Poseidon hashes of A, B, C = A*B."""
     a = np.ascontiguousarray(a, dtype=np.uint64)

@@ -862,6 +862,7 @@ void zkg16_destroy(zkg16_ctx *ctx) {
     ctx->pks.clear();
     ctx->r1cs.clear();
     ctx->wits.clear();
+    ctx->prime_dev.reset();
     ctx->ntt_tables.clear();
     delete ctx;
     dev_cache_flush();      // a destroyed ctx really returns its memory (other live contexts simply allocate afresh)
@@ -1377,6 +1378,30 @@ int zkg16_r1cs_matrix(zkg16_ctx *ctx, size_t n, uint64_t *r1cs_handle) {
     if (!r) return st;
     *r1cs_handle = ctx->next_handle++;
     ctx->r1cs.put(*r1cs_handle, std::move(r));
+    ZK_API_END(ctx)
+}
+
+// The PrimeCircuit of candidate (x, j) on the device (prime_device.hip): handles as zkg16_r1cs_load / zkg16_witness_load would return
+// for the arrays of zkg16_circuit_prime + zkg16_circuit_export, without synthesising or uploading them.  The template is uploaded on
+// the first call under ctx->mu (held by every entry here) and stays resident until zkg16_destroy.
+int zkg16_r1cs_prime(zkg16_ctx *ctx, uint64_t x, uint64_t j, uint64_t *r1cs_handle) {
+    if (!r1cs_handle) return ZKG16_ERR_BAD_ARG;
+    ZK_API_BEGIN(ctx)
+    int st = ZKG16_OK;
+    std::shared_ptr<R1csDev> r = prime_r1cs_on_device(ctx, x, j, &st);
+    if (!r) return st;
+    *r1cs_handle = ctx->next_handle++;
+    ctx->r1cs.put(*r1cs_handle, std::move(r));
+    ZK_API_END(ctx)
+}
+int zkg16_witness_prime(zkg16_ctx *ctx, uint64_t x, uint64_t j, uint64_t *witness_handle) {
+    if (!witness_handle) return ZKG16_ERR_BAD_ARG;
+    ZK_API_BEGIN(ctx)
+    int st = ZKG16_OK;
+    std::shared_ptr<WitnessDev> w = prime_witness_on_device(ctx, x, j, &st);
+    if (!w) return st;
+    *witness_handle = ctx->next_handle++;
+    ctx->wits.put(*witness_handle, std::move(w));
     ZK_API_END(ctx)
 }
 

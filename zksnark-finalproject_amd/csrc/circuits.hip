@@ -22,6 +22,7 @@
 #include <mutex>
 #include <new>
 #include <stdexcept>
+#include <string>
 #include <system_error>
 #include <thread>
 #include <vector>
@@ -29,6 +30,7 @@
 #include "../../include/zkg16.h"
 #include "ff.cuh"
 #include "matrix_plan.hpp"
+#include "prime_program.hpp"
 
 using namespace zk;
 
@@ -929,9 +931,7 @@ int zkg16_circuit_prime(uint64_t x, uint64_t j, zkg16_circuit **out) {
     if (!out) return ZKG16_ERR_BAD_ARG;
     *out = nullptr;
     const PrimeCandidate cand = prime_candidate(x, j);
-    if (cand.n < 2) return ZKG16_ERR_UNSUPPORTED;          // the reference's BigUint modpow panics on a modulus below 2
-    for (int k = 0; k < PRIME_K; k++)
-        if (cand.base[k] == 0) return ZKG16_ERR_UNSUPPORTED;  // base.inverse().unwrap() panics upstream
+    if (const int g = prime_guard(cand)) return g;
     try {
         const bool trace = getenv("ZKG16_TRACE_HOST") != nullptr;
         const auto t0 = std::chrono::steady_clock::now();
@@ -995,6 +995,274 @@ int zkg16_circuit_prime(uint64_t x, uint64_t j, zkg16_circuit **out) {
         return ZKG16_ERR_OOM;
     } catch (const std::exception &) {
         return ZKG16_ERR_UNSUPPORTED;
+    }
+    return ZKG16_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------ the PrimeCircuit as a program
+// (prime_program.hpp).  Recorded once per process from a sequential build with the recorder attached, checked against that build
+// (every slot and source equal to the native computation, every operand an earlier bit of the same part, the four patched
+// coefficients where they are expected), then kept in prime_store() for the life of the process.
+namespace {
+
+void prime_instance(uint64_t x, const PrimeCandidate &c, std::vector<Fr> &slot) {      // z[0 .. 258): 1, x, the digest bits
+    slot.push_back(Fr::one());
+    slot.push_back(fr_from_u64(x));
+    for (int k = 0; k < 256; k++) slot.push_back(((c.digest[k >> 3] >> (k & 7)) & 1) ? Fr::one() : Fr::zero());
+}
+
+[[noreturn]] void prime_record_fail(const char *what) { throw std::runtime_error(std::string("prime program: ") + what); }
+
+std::shared_ptr<const PrimeProgram> prime_record(uint64_t x, uint64_t j, const PrimeCandidate &cand) {
+    if (j == 0) prime_record_fail("record with j >= 1 (the template keeps C's -j term)");
+    zkg16_circuit c;
+    Circuit &seg = c.add_segment(0);
+    PrimeRecorder rec;
+    PrimeLayout lay;
+    g_prime_rec = &rec;
+    try {
+        build_prime_circuit(seg, x, j, cand, &lay);
+    } catch (...) {
+        g_prime_rec = nullptr;
+        throw;
+    }
+    g_prime_rec = nullptr;
+    if (rec.bad) prime_record_fail("an operand is not a witness bit");
+    auto P = std::make_shared<PrimeProgram>();
+    const size_t ni = seg.instance.size(), nw = seg.witness.size();
+    P->num_instance = ni;
+    P->num_witness = nw;
+    P->num_constraints = seg.rows[0].size();
+    for (int p = 0; p <= PRIME_PARTS; p++) P->wit_base[p] = (uint32_t)lay.wit_base[p];
+    rec.tag.resize(nw);
+
+    // slots and sources: the recording build's values must be the native ones
+    std::vector<Fr> want, want_src;
+    prime_instance(x, cand, want);
+    prime_native_inputs(x, j, cand, want, want_src);
+    P->code.resize(ni + nw);
+    size_t s = 0;
+    for (size_t v = 0; v < ni; v++) {
+        if (s >= want.size() || seg.instance[v] != want[s]) prime_record_fail("instance");
+        P->code[v] = PRIME_SLOT | (uint32_t)s++;
+    }
+    for (size_t w = 0; w < nw; w++) {
+        if (rec.tag[w].op != 0) { P->code[ni + w] = (uint32_t)w; continue; }
+        if (s >= want.size() || seg.witness[w] != want[s]) prime_record_fail("slot value");
+        P->code[ni + w] = PRIME_SLOT | (uint32_t)s++;
+    }
+    if (s != want.size() || rec.sources.size() != want_src.size()) prime_record_fail("slot / source count");
+    for (size_t k = 0; k < want_src.size(); k++)
+        if (rec.sources[k] != want_src[k]) prime_record_fail("source value");
+    P->n_slots = s;
+    P->n_sources = want_src.size();
+
+    // instructions, part by part, sorted by level (1 + the highest level among the operands; BITS: 0)
+    std::vector<uint32_t> level(nw, 0);
+    P->lvl.clear();
+    for (int p = 0; p < PRIME_PARTS; p++) {
+        const uint32_t lo = P->wit_base[p], hi = P->wit_base[p + 1];
+        if (hi < lo || hi - lo >= (1u << 18) || hi - lo > 156u * 1024) prime_record_fail("part too large");
+        P->max_part = std::max(P->max_part, hi - lo);
+        std::vector<PrimeInstr> mine;
+        std::vector<uint32_t> lv;
+        uint32_t top = 0;
+        for (uint32_t w = lo; w < hi; w++) {
+            const PrimeRecorder::Tag &t = rec.tag[w];
+            if (t.op == 0 || t.op == PrimeRecorder::PRIME_SUM_MORE) continue;
+            uint32_t l = 0;
+            auto opnd = [&](uint64_t id) -> uint32_t {
+                if (id < lo || id >= w || rec.tag[id].op == 0) prime_record_fail("operand");
+                l = std::max(l, level[id] + 1);
+                return (uint32_t)(id - lo);
+            };
+            PrimeInstr in{t.op << 29 | (w - lo), 0, 0, 0};
+            uint32_t width = 1;
+            if (t.op == PRIME_OP_XOR || t.op == PRIME_OP_AND) {
+                in.a = opnd(t.a & ~PRIME_NEG) | (t.a & PRIME_NEG);
+                in.b = opnd(t.b & ~PRIME_NEG) | (t.b & PRIME_NEG);
+            } else if (t.op == PRIME_OP_BITS) {
+                if (t.a >= P->n_sources || t.b >= 255) prime_record_fail("source operand");
+                in.a = t.a;
+                in.b = t.b;
+            } else if (t.op == PRIME_OP_SUM) {
+                const uint32_t nt = t.b & 255u, nb = t.b >> 8;
+                if (nb == 0 || nb > 64 || w + nb > hi || (t.k >> 32) >= (1u << 16) || t.a + (uint64_t)nt > rec.terms.size())
+                    prime_record_fail("sum shape");
+                for (uint32_t i = 1; i < nb; i++)
+                    if (rec.tag[w + i].op != PrimeRecorder::PRIME_SUM_MORE) prime_record_fail("sum bits");
+                in.a = (uint32_t)P->terms.size();
+                for (uint32_t k = 0; k < nt; k++) {
+                    const uint64_t tm = rec.terms[t.a + k];
+                    P->terms.push_back(opnd(tm >> 32) | (uint32_t)(tm & 31u) << 18 | (uint32_t)((tm >> 5) & 1u) << 23);
+                }
+                in.b = nt | nb << 8 | (uint32_t)(t.k >> 32) << 16;
+                in.c = (uint32_t)t.k;
+                width = nb;
+            } else {
+                prime_record_fail("opcode");
+            }
+            for (uint32_t i = 0; i < width; i++) level[w + i] = l;
+            top = std::max(top, l);
+            mine.push_back(in);
+            lv.push_back(l);
+        }
+        // counting sort by level
+        std::vector<uint32_t> start(top + 2, 0);
+        for (uint32_t l : lv) start[l + 1]++;
+        for (uint32_t l = 0; l <= top; l++) start[l + 1] += start[l];
+        const uint32_t base = (uint32_t)P->ins.size();
+        P->lvl_base[p] = (uint32_t)P->lvl.size();
+        for (uint32_t l = 0; l <= top; l++) P->lvl.push_back(base + start[l]);
+        P->ins.resize(base + mine.size());
+        std::vector<uint32_t> fill(start.begin(), start.end() - 1);
+        for (size_t i = 0; i < mine.size(); i++) P->ins[base + fill[lv[i]]++] = mine[i];
+        P->part_ins[p] = (uint32_t)mine.size();
+    }
+    P->lvl_base[PRIME_PARTS] = (uint32_t)P->lvl.size();
+    P->lvl.push_back((uint32_t)P->ins.size());
+
+    // the R1CS template and its four patched coefficients
+    size_t nnz[3];
+    zkg16_circuit_dims(&c, nullptr, nullptr, nullptr, nnz);
+    std::vector<Fr> z(ni + nw);
+    uint64_t *rp[3], *cf[3];
+    uint32_t *col[3];
+    for (int m = 0; m < 3; m++) {
+        P->rp[m].resize(P->num_constraints + 1);
+        P->col[m].resize(nnz[m] ? nnz[m] : 1);
+        P->cf[m].resize(nnz[m] ? nnz[m] : 1);
+        rp[m] = P->rp[m].data();
+        col[m] = P->col[m].data();
+        cf[m] = reinterpret_cast<uint64_t *>(P->cf[m].data());
+    }
+    if (zkg16_circuit_export(&c, rp, col, cf, reinterpret_cast<uint64_t *>(z.data())) != ZKG16_OK) prime_record_fail("export");
+    for (int m = 0; m < 3; m++) { P->col[m].resize(nnz[m]); P->cf[m].resize(nnz[m]); }
+    if (rec.exp_rows.size() != 3 || rec.pack_row >= P->num_constraints) prime_record_fail("patch rows");
+    for (int k = 0; k < 3; k++) {
+        const size_t r = rec.exp_rows[k];
+        P->a_pos[k] = P->rp[0][r];
+        if (P->rp[0][r + 1] <= P->a_pos[k] || P->col[0][P->a_pos[k]] != 0 || P->cf[0][P->a_pos[k]] != fr_from_u64(cand.n)) prime_record_fail("A patch");
+    }
+    P->c_pos = P->rp[2][rec.pack_row];
+    if (P->rp[2][rec.pack_row + 1] <= P->c_pos || P->col[2][P->c_pos] != 0 || P->cf[2][P->c_pos] != fp_neg(fr_from_u64(j))) prime_record_fail("C patch");
+    P->rp_c_j0 = P->rp[2];
+    for (size_t r = rec.pack_row + 1; r <= P->num_constraints; r++) P->rp_c_j0[r]--;
+    return P;
+}
+
+std::shared_ptr<const PrimeProgram> g_prime_program;      // guarded by prime_store().mu
+
+}  // namespace
+
+namespace zk {
+
+int prime_program(std::shared_ptr<const PrimeProgram> &out) {
+    PrimeStore &st = prime_store();
+    std::lock_guard<std::mutex> lk(st.mu);
+    if (!g_prime_program) {
+        try {
+            // any candidate the builder accepts (the structure is the same for all): the first of x = 0 with j >= 1
+            uint64_t j = 1;
+            PrimeCandidate cand = prime_candidate(0, j);
+            while (prime_guard(cand) != ZKG16_OK) cand = prime_candidate(0, ++j);
+            g_prime_program = prime_record(0, j, cand);
+            if (getenv("ZKG16_TRACE_HOST")) {
+                const PrimeProgram &P = *g_prime_program;
+                fprintf(stderr, "zkg16 prime program: %zu slots, %zu sources, %zu terms, largest part %u witnesses\n", P.n_slots, P.n_sources, P.terms.size(), P.max_part);
+                for (int p = 0; p < PRIME_PARTS; p++)
+                    fprintf(stderr, "  part %d: %u witnesses, %u instructions, %u levels\n", p, P.wit_base[p + 1] - P.wit_base[p], P.part_ins[p], P.lvl_base[p + 1] - P.lvl_base[p]);
+            }
+        } catch (const std::bad_alloc &) {
+            return ZKG16_ERR_OOM;
+        } catch (const std::exception &e) {
+            fprintf(stderr, "zkg16: %s\n", e.what());
+            return ZKG16_ERR_UNSUPPORTED;
+        }
+    }
+    out = g_prime_program;
+    return ZKG16_OK;
+}
+
+int prime_inputs(const PrimeProgram &P, uint64_t x, uint64_t j, std::vector<Fr> &slots, std::vector<Fr> &sources, uint32_t *n_out) {
+    const PrimeCandidate cand = prime_candidate(x, j);
+    if (const int g = prime_guard(cand)) return g;
+    slots.clear();
+    sources.clear();
+    prime_instance(x, cand, slots);
+    prime_native_inputs(x, j, cand, slots, sources);
+    if (slots.size() != P.n_slots || sources.size() != P.n_sources) return ZKG16_ERR_UNSUPPORTED;
+    for (Fr &v : sources) v = fp_from_mont(v);
+    if (n_out) *n_out = cand.n;
+    return ZKG16_OK;
+}
+
+}  // namespace zk
+
+extern "C" {
+
+// The PrimeCircuit's assignment for (x, j) by evaluating the recorded program on the host: the reference for zkg16_witness_prime
+// (same bytes as zkg16_circuit_prime + zkg16_circuit_export's z).  z: n_assign x 4 limbs, Montgomery; n_assign = num_instance + num_witness.
+int zkg16_prime_witness_host(uint64_t x, uint64_t j, uint64_t *z, size_t n_assign) {
+    if (!z) return ZKG16_ERR_BAD_ARG;
+    std::shared_ptr<const PrimeProgram> P;
+    if (const int rc = prime_program(P)) return rc;
+    if (n_assign != P->num_instance + P->num_witness) return ZKG16_ERR_BAD_ARG;
+    try {
+        std::vector<Fr> slots, src;
+        if (const int rc = prime_inputs(*P, x, j, slots, src, nullptr)) return rc;
+        std::vector<uint8_t> bits(P->num_witness, 0);
+        for (int p = 0; p < PRIME_PARTS; p++) {
+            uint8_t *b = bits.data() + P->wit_base[p];
+            for (uint32_t i = P->lvl[P->lvl_base[p]]; i < P->lvl[P->lvl_base[p + 1]]; i++) prime_exec(P->ins[i], b, P->terms.data(), src.data());
+        }
+        Fr *out = reinterpret_cast<Fr *>(z);
+        for (size_t v = 0; v < n_assign; v++) {
+            const uint32_t c = P->code[v];
+            out[v] = (c & PRIME_SLOT) ? slots[c & ~PRIME_SLOT] : bits[c] ? Fr::one() : Fr::zero();
+        }
+    } catch (const std::bad_alloc &) {
+        return ZKG16_ERR_OOM;
+    }
+    return ZKG16_OK;
+}
+
+// The PrimeCircuit's R1CS for candidate j: the recorded template with its four coefficients patched (host loops; the reference for
+// zkg16_r1cs_prime).  Only j matters to the dimensions: C has one non-zero fewer when j = 0.
+int zkg16_prime_r1cs_dims(uint64_t j, size_t *num_instance, size_t *num_witness, size_t *num_constraints, size_t nnz[3]) {
+    std::shared_ptr<const PrimeProgram> P;
+    if (const int rc = prime_program(P)) return rc;
+    if (num_instance) *num_instance = P->num_instance;
+    if (num_witness) *num_witness = P->num_witness;
+    if (num_constraints) *num_constraints = P->num_constraints;
+    if (nnz)
+        for (int m = 0; m < 3; m++) nnz[m] = P->col[m].size() - (m == 2 && j == 0 ? 1 : 0);
+    return ZKG16_OK;
+}
+int zkg16_prime_r1cs_host(uint64_t x, uint64_t j, uint64_t *const row_ptr[3], uint32_t *const col[3], uint64_t *const coeff[3]) {
+    if (!row_ptr || !col || !coeff) return ZKG16_ERR_BAD_ARG;
+    std::shared_ptr<const PrimeProgram> P;
+    if (const int rc = prime_program(P)) return rc;
+    const PrimeCandidate cand = prime_candidate(x, j);
+    if (const int g = prime_guard(cand)) return g;
+    for (int m = 0; m < 3; m++) {
+        const std::vector<uint64_t> &rp = (m == 2 && j == 0) ? P->rp_c_j0 : P->rp[m];
+        memcpy(row_ptr[m], rp.data(), rp.size() * sizeof(uint64_t));
+        const size_t n = P->col[m].size(), skip = (m == 2 && j == 0) ? P->c_pos : n;
+        Fr *cf = reinterpret_cast<Fr *>(coeff[m]);
+        for (size_t k = 0, o = 0; k < n; k++) {
+            if (k == skip) continue;
+            col[m][o] = P->col[m][k];
+            cf[o++] = P->cf[m][k];
+        }
+    }
+    const Fr fn = fr_from_u64(cand.n);
+    for (int k = 0; k < 3; k++) memcpy(coeff[0] + 4 * P->a_pos[k], fn.l, 32);
+    if (j != 0) {
+        const Fr mj = fp_neg(fr_from_u64(j));
+        memcpy(coeff[2] + 4 * P->c_pos, mj.l, 32);
     }
     return ZKG16_OK;
 }

@@ -160,6 +160,7 @@ struct R1csDev {
 };
 
 struct WitnessDev { size_t n = 0; DevBuf z; };
+struct PrimeDev;            // prime_device.hip: the recorded PrimeCircuit resident on a ctx
 
 // handle -> resident object.  Objects are shared_ptr: a proof in flight on one lane keeps its key / matrices / assignment alive
 // when another caller frees the handle meanwhile (the memory goes back when that proof ends).
@@ -292,6 +293,7 @@ struct zkg16_ctx {
     bool lds_attr_fixup[2] = {false, false}, lds_attr_ntt = false;      // hipFuncSetAttribute(max dynamic LDS) done on this device
     zk::FixedBaseCache fb_g1, fb_g2;
     zk::DevBuf poseidon_dev;                          // Poseidon MDS + round constants, Montgomery form (witness.hip), uploaded on first use
+    std::shared_ptr<zk::PrimeDev> prime_dev;          // PrimeCircuit template + witness program (prime_device.hip), root only, uploaded on first use
 };
 
 namespace zk {
@@ -383,6 +385,11 @@ void matrix_plan_instantiate_host(const MatrixPlan &plan, uint64_t *const rp[3],
 
 // matrix_r1cs.hip: that R1CS written by kernels into a new R1csDev (status: a zkg16_status when the result is null)
 std::shared_ptr<R1csDev> matrix_r1cs_on_device(zkg16_ctx *ctx, size_t n, int *status);
+
+// prime_device.hip: the PrimeCircuit of candidate (x, j) on the device, from the template the root ctx keeps resident (status: a
+// zkg16_status when the result is null; ZKG16_ERR_UNSUPPORTED for the candidates zkg16_circuit_prime refuses)
+std::shared_ptr<R1csDev> prime_r1cs_on_device(zkg16_ctx *ctx, uint64_t x, uint64_t j, int *status);
+std::shared_ptr<WitnessDev> prime_witness_on_device(zkg16_ctx *ctx, uint64_t x, uint64_t j, int *status);
 
 // witness.hip: the MatrixCircuit's assignment arriving on the device in parts (zkg16_witness_matrix: all at once;
 // zkg16_prove_matrix: while the proof is already running).  slices_wanted gadget slices -> parts = slices + 1.

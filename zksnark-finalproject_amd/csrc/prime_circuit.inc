@@ -169,6 +169,14 @@ PrimeCandidate prime_candidate(uint64_t x, uint64_t j) {
     return c;
 }
 
+// the candidates zkg16_circuit_prime refuses (the reference panics on them) — every entry that takes (x, j) asks this one function
+int prime_guard(const PrimeCandidate &c) {
+    if (c.n < 2) return ZKG16_ERR_UNSUPPORTED;          // the reference's BigUint modpow panics on a modulus below 2
+    for (int k = 0; k < PRIME_K; k++)
+        if (c.base[k] == 0) return ZKG16_ERR_UNSUPPORTED;  // base.inverse().unwrap() panics upstream
+    return ZKG16_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ Boolean gadget
 // ark_r1cs_std::boolean::Boolean: Constant(b) | Is(var) | Not(var)
 struct Bit {
@@ -183,6 +191,32 @@ struct Bit {
         return r;
     }
 };
+// The recorder of the witness program (prime_program.hpp): attached, thread-local, only to the one recording build of a process —
+// every hook below is a no-op otherwise, so ordinary builds are unchanged.  Indices are witness indices of that build's single
+// segment; an operand that is not a witness bit marks the recording bad (the program is then refused, never used).
+struct PrimeRecorder {
+    struct Tag { uint32_t op = 0, a = 0, b = 0; uint64_t k = 0; };     // op 0: a slot; PRIME_SUM_MORE: a later result bit of a SUM
+    static constexpr uint32_t PRIME_SUM_MORE = 5;
+    std::vector<Tag> tag;
+    std::vector<uint64_t> terms;              // SUM terms: witness index << 32 | shift | negated << 5
+    std::vector<Fr> sources;                  // the values to_bits_le decomposed, in call order (Montgomery)
+    std::vector<size_t> exp_rows;             // rows of check_bits_is_exp (A's column 0 holds n)
+    size_t pack_row = SIZE_MAX;               // the packing row of to_bits_le(x + j) (C's column 0 holds -j)
+    int part = 0;
+    bool bad = false;
+    void set(VarId v, uint32_t op, uint32_t a, uint32_t b, uint64_t k = 0) {
+        if (!(v & WIT)) { bad = true; return; }
+        const size_t w = v & ~WIT;
+        if (tag.size() <= w) tag.resize(w + 1);
+        tag[w] = Tag{op, a, b, k};
+    }
+    uint32_t operand(const Bit &b) {
+        if (b.kind == Bit::CONST || !(b.v & WIT)) { bad = true; return 0; }
+        return (b.v & ~WIT) | (b.kind == Bit::NOT ? PRIME_NEG : 0u);
+    }
+};
+static thread_local PrimeRecorder *g_prime_rec = nullptr;
+
 struct PrimeBuilder {
     Circuit &cs;
     const Fr one = Fr::one(), minus_one = fp_neg(Fr::one());
@@ -260,12 +294,16 @@ struct PrimeBuilder {
         row({Term{0, one}, Term{r.v, minus_one}}, {Term{r.v, one}}, {});
         return r;
     }
-    Bit raw(bool v, const Bit &a, const Bit &b) {        // helper: fresh result variable without the booleanity row
-        (void)a; (void)b;
+    Bit raw(bool v, const Bit &a, const Bit &b, uint32_t op) {        // helper: fresh result variable without the booleanity row
         Bit r;
         r.kind = Bit::IS;
         r.val = v;
         r.v = cs.new_witness_id(v ? one : Fr::zero());
+        if (g_prime_rec) {
+            const uint32_t oa = g_prime_rec->operand(a), ob = g_prime_rec->operand(b);
+            if (op == PRIME_OP_XOR && ((oa | ob) & PRIME_NEG)) g_prime_rec->bad = true;
+            g_prime_rec->set(r.v, op, oa, ob);
+        }
         return r;
     }
     Bit bxor(const Bit &a, const Bit &b) {
@@ -275,7 +313,7 @@ struct PrimeBuilder {
         if (a.kind == Bit::NOT) return !bxor(!a, b);
         if (b.kind == Bit::NOT) return !bxor(a, !b);
         // AllocatedBool::xor: (a + a) * b = a + b - c
-        const Bit c = raw(a.val != b.val, a, b);
+        const Bit c = raw(a.val != b.val, a, b, PRIME_OP_XOR);
         row({Term{a.v, fp_add(one, one)}}, {Term{b.v, one}}, {Term{a.v, one}, Term{b.v, one}, Term{c.v, minus_one}});
         return c;
     }
@@ -283,7 +321,7 @@ struct PrimeBuilder {
         if (a.kind == Bit::CONST) return a.val ? b : Bit::constant(false);
         if (b.kind == Bit::CONST) return b.val ? a : Bit::constant(false);
         // AllocatedBool::and / and_not / nor: one product row over the operands' linear forms
-        const Bit c = raw(a.val && b.val, a, b);
+        const Bit c = raw(a.val && b.val, a, b, PRIME_OP_AND);
         row(bit_lc(a), bit_lc(b), {Term{c.v, one}});
         return c;
     }
@@ -320,6 +358,11 @@ struct PrimeBuilder {
         const Fr canon = fp_from_mont(x.val);
         std::vector<Bit> bits(255);
         for (int i = 0; i < 255; i++) bits[i] = alloc((canon.l[i >> 5] >> (i & 31)) & 1u);
+        if (g_prime_rec) {
+            for (int i = 0; i < 255; i++) g_prime_rec->set(bits[i].v, PRIME_OP_BITS, (uint32_t)g_prime_rec->sources.size(), (uint32_t)i);
+            g_prime_rec->sources.push_back(x.val);
+            if (g_prime_rec->part == 0 && g_prime_rec->pack_row == SIZE_MAX) g_prime_rec->pack_row = cs.rows[2].size();
+        }
         std::vector<Term> lc;
         Fr coeff = one;
         for (int i = 0; i < 255; i++) { push_bit(lc, bits[i], coeff); coeff = fp_add(coeff, coeff); }
@@ -410,16 +453,38 @@ struct PrimeBuilder {
             }
         }
         if (all_const) return u32_const((uint32_t)value);
+        uint64_t rec_const = 0;
+        const size_t rec_t0 = g_prime_rec ? g_prime_rec->terms.size() : 0;
+        if (g_prime_rec)          // the sum as constant + (+-) bits << shift: a Not bit is 1 - b
+            for (const U32 &op : ops)
+                for (int s = 0; s < 32; s++) {
+                    const Bit &b = op.b[s];
+                    if (b.kind == Bit::CONST) { rec_const += (uint64_t)b.val << s; continue; }
+                    if (b.kind == Bit::NOT) rec_const += 1ull << s;
+                    g_prime_rec->terms.push_back((uint64_t)(b.v & ~WIT) << 32 | (uint64_t)s | (b.kind == Bit::NOT ? 32u : 0u));
+                    if (!(b.v & WIT)) g_prime_rec->bad = true;
+                }
         U32 res;
         Fr coeff = one;
         int i = 0;
+        VarId first = 0;
         while (max_value != 0) {
             const Bit b = alloc((value >> i) & 1ull);
+            if (g_prime_rec) {
+                if (i == 0) first = b.v;
+                else if (b.v != first + (VarId)i) g_prime_rec->bad = true;          // result bits are consecutive
+                g_prime_rec->set(b.v, PrimeRecorder::PRIME_SUM_MORE, 0, 0);
+            }
             lc.push_back(Term{b.v, fp_neg(coeff)});
             if (i < 32) res.b[i] = b;
             max_value >>= 1;
             i++;
             coeff = fp_add(coeff, coeff);
+        }
+        if (g_prime_rec) {
+            const size_t nt = g_prime_rec->terms.size() - rec_t0;
+            if (nt > 255 || i > 64) g_prime_rec->bad = true;                        // the instruction's 8-bit fields
+            g_prime_rec->set(first, PRIME_OP_SUM, (uint32_t)rec_t0, (uint32_t)nt | (uint32_t)i << 8, rec_const);
         }
         row({}, {}, lc);
         return res;
@@ -605,6 +670,7 @@ static void prime_part_fermat(Circuit &cs, int k, const PrimeCandidate &c, const
             uint64_t e = 0;
             for (int i = 0; i < PRIME_NUM_BITS; i++) e |= (uint64_t)tr.bits[i] << i;
             Circuit::add_const(res, fr_from_u64(e));
+            if (g_prime_rec) g_prime_rec->exp_rows.push_back(cs.rows[0].size());
             cs.enforce_equal(res, n_minus_one);
         }
         for (int i = 0; i < PRIME_NUM_BITS; i++) {
@@ -660,6 +726,7 @@ void build_prime_circuit(Circuit &cs, uint64_t x, uint64_t j, const PrimeCandida
                 for (int m = 0; m < 3; m++) lay->nnz_hint[p - 1][m] = cs.rows[m].t.size();
             }
         }
+        if (g_prime_rec) g_prime_rec->part = p;
         prime_part(cs, p, x, j, c, sh);
     }
     if (lay) {
@@ -672,5 +739,57 @@ void build_prime_circuit(Circuit &cs, uint64_t x, uint64_t j, const PrimeCandida
         }
         lay->sh = sh;
         lay->known = true;
+    }
+}
+
+// The values the witness program takes as inputs (prime_program.hpp), natively, in the order the builders above allocate them:
+// the slots (every witness that is not a Boolean gadget result, in allocation order) and the sources (what to_bits_le decomposes,
+// in call order).  Every step repeats the builders' own field operations on the same values; the recording build compares the
+// result with what it allocated before the program is used (circuits.hip: prime_record).
+static void prime_native_inputs(uint64_t x, uint64_t j, const PrimeCandidate &c, std::vector<Fr> &slot, std::vector<Fr> &src) {
+    const Fr one = Fr::one(), zero = Fr::zero(), minus_one = fp_neg(Fr::one());
+    auto sub = [&](const Fr &a, const Fr &b) { return fp_add(a, fp_mul(b, minus_one)); };          // Circuit::sub
+    auto bit = [&](bool b) { return b ? one : zero; };
+    const Fr fn = fr_from_u64(c.n);
+    // head: to_bits_le(x + j); a_i, div, origin, remainder, quotient, div * quotient, n (twice more), a
+    src.push_back(fp_add(fr_from_u64(x), fr_from_u64(j)));
+    {
+        const Fr a_i = fr_from_u256(c.digest_int), div = fr_from_u64(1ull << PRIME_NUM_BITS), q = fr_from_u256(c.q);
+        for (const Fr &v : {a_i, div, a_i, fn, q, fp_mul(div, q), fn, fn, c.a}) slot.push_back(v);
+    }
+    // bases: to_bits_le(a); a_j, rem, quo, n, quo * n
+    for (int k = 0; k < PRIME_K; k++) {
+        src.push_back(c.a);
+        const Fr quo = fr_from_u256(c.base_q[k]);
+        for (const Fr &v : {fr_from_u256(c.base_int[k]), fr_from_u64(c.base[k]), quo, fn, fp_mul(quo, fn)}) slot.push_back(v);
+    }
+    // Fermat parts (prime_part_fermat)
+    for (int k = 0; k < PRIME_K; k++) {
+        const Fr base = fr_from_u64(c.base[k]);
+        const ModpowTrace tr = modpow_trace(c.base[k], c.n, c.n - 1);
+        const Fr result = fr_from_u64(tr.result);
+        const Fr inv = fp_inv(base), one_v = fp_mul(base, inv);
+        for (const Fr &v : {result, bit(c.is_prime), result, result, inv, one_v, zero}) slot.push_back(v);
+        Fr cur_pow = base, calculated = one_v;
+        for (int i = 0; i < PRIME_NUM_BITS; i++) {
+            const Fr elem = fr_from_u64(tr.bits[i]);
+            const Fr m = fp_mul(elem, sub(cur_pow, one_v));
+            calculated = fp_mul(calculated, fp_add(m, one_v));
+            const Fr q1 = fr_from_u64(tr.res_q[i]), r1 = fr_from_u64(tr.res_rem[i]);
+            for (const Fr &v : {elem, m, calculated, q1, r1, fp_mul(q1, fn)}) slot.push_back(v);
+            const Fr d1 = sub(r1, fn);
+            src.push_back(fp_add(d1, d1));
+            calculated = r1;
+            cur_pow = fp_mul(cur_pow, cur_pow);
+            const Fr q2 = fr_from_u64(tr.pow_q[i]), r2 = fr_from_u64(tr.pow_rem[i]);
+            for (const Fr &v : {cur_pow, q2, r2, fp_mul(q2, fn)}) slot.push_back(v);
+            const Fr d2 = sub(r2, fn);
+            src.push_back(fp_add(d2, d2));
+            cur_pow = r2;
+        }
+        const Fr d = sub(result, one);                                                      // is_eq(result, 1)
+        const bool neq = !d.is_zero();
+        slot.push_back(bit(neq));
+        slot.push_back(neq ? fp_inv(d) : one);
     }
 }

@@ -148,6 +148,18 @@ class Device:
         self._check(self.lib.zkg16_r1cs_matrix(self.ctx, n, C.byref(handle)))
         return handle.value
 
+    def r1cs_prime(self, x, j):
+        """The PrimeCircuit's R1CS for candidate (x, j) from the template resident on the device (zkg16_r1cs_prime) -> r1cs handle."""
+        handle = C.c_uint64()
+        self._check(self.lib.zkg16_r1cs_prime(self.ctx, x, j, C.byref(handle)))
+        return handle.value
+
+    def witness_prime(self, x, j):
+        """The PrimeCircuit's assignment for candidate (x, j) built on the device (zkg16_witness_prime) -> witness handle."""
+        handle = C.c_uint64()
+        self._check(self.lib.zkg16_witness_prime(self.ctx, x, j, C.byref(handle)))
+        return handle.value
+
     def r1cs_read(self, h):
         """-> the r1cs dict (as SynthesizedCircuit.r1cs) + num_variables behind a handle (zkg16_r1cs_read)."""
         ni, nc, nv = C.c_size_t(), C.c_size_t(), C.c_size_t()

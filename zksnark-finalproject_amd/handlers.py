@@ -12,7 +12,7 @@ import time
 import numpy as np
 
 from . import wire
-from .circuits import fibonacci_circuit, fibonacci_circuit_handle, matrix_circuit, prime_circuit, prime_circuit_handle, prime_public_inputs, prime_search
+from .circuits import fibonacci_circuit, fibonacci_circuit_handle, matrix_circuit, prime_circuit, prime_dims, prime_public_inputs, prime_search
 from .workloads import R_MOD, g1_generator, g2_generator
 
 
@@ -130,6 +130,47 @@ def _setup_and_prove(dev, circ, rng, keep_key=False):
     return dict(proof=proof, inf=inf, vk=vk, pk=pk, setup_time=setup_time, proving_time=proving_time, r=r, s=s)
 
 
+class _PrimeShape:
+    """What a prime request needs of a PrimeCircuit whose matrices and assignment are built on the device (zkg16_r1cs_prime /
+    zkg16_witness_prime): its dimensions and public inputs, nothing synthesized on the host."""
+
+    def __init__(self, x, j):
+        dims = prime_dims(j)
+        self.num_instance, self.num_witness, self.num_constraints = dims["num_instance"], dims["num_witness"], dims["num_constraints"]
+        self.num_vars = self.num_instance + self.num_witness
+        self.domain = 1 << max(self.num_constraints + self.num_instance - 1, 0).bit_length()
+        self.public_inputs = prime_public_inputs(x, j)
+        self.satisfied = None
+        self.z = self.r1cs = None
+        self.j = j
+
+
+def _setup_and_prove_prime_device(dev, x, j, circ, rng):
+    """_setup_and_prove for the prime request path: R1CS and assignment written on the device for candidate (x, j), resident key.
+    The same draws from rng in the same order, so a seed gives the same key and proof as the host-synthesized path."""
+    trap = np.stack([_fr_mont(rng.randrange(1, R_MOD)) for _ in range(5)])
+    from .device import scalar_mul
+    k = np.array([rng.getrandbits(62) for _ in range(4)], dtype=np.uint64)
+    g1 = scalar_mul("g1", g1_generator(), k)[0]
+    g2 = scalar_mul("g2", g2_generator(), k)[0]
+    rh = wh = ph = None
+    try:
+        rh = dev.r1cs_prime(x, j)
+        wh = dev.witness_prime(x, j)
+        t0 = time.perf_counter()
+        ph, vk = dev.setup_resident(rh, circ.num_instance, trap, g1, g2)
+        setup_time = time.perf_counter() - t0
+        r, s = _fr_mont(rng.randrange(R_MOD)), _fr_mont(rng.randrange(R_MOD))
+        t0 = time.perf_counter()
+        proof, inf = dev.prove_resident(ph, rh, wh, r, s)
+        proving_time = time.perf_counter() - t0
+    finally:
+        for f, h in ((dev.pk_free, ph), (dev.witness_free, wh), (dev.r1cs_free, rh)):
+            if h is not None:
+                f(h)
+    return dict(proof=proof, inf=inf, vk=vk, pk=None, setup_time=setup_time, proving_time=proving_time, r=r, s=s)
+
+
 def prove_matrix(dev, size, matrix_a, matrix_b, seed=0, keep_key=False):
     """-> the reference's ProveOutput fields (matrix_proof.rs:80-91)."""
     a = np.asarray(matrix_a, dtype=np.uint64).reshape(size, size)
@@ -169,11 +210,12 @@ def prove_prime(dev, x, i, seed=7, keep_key=False, check_satisfied=False):
     found = prime_search(x, i)
     if not found["found"]:
         return dict(proof="", j=0, num_constraints=0, num_variables=0, setup_time=0.0, proving_time=0.0, found_prime=False, prime_num="", vk="")
-    if keep_key or check_satisfied:     # tests want the arrays (and the satisfaction check) on the host
+    if keep_key or check_satisfied:     # tests want the arrays (and the satisfaction check) on the host: host synthesis
         circ = prime_circuit(x, found["j"], search=False, check_satisfied=check_satisfied)
-    else:
-        circ = prime_circuit_handle(x, found["j"])
-    out = _setup_and_prove(dev, circ, random.Random(seed), keep_key)
+        out = _setup_and_prove(dev, circ, random.Random(seed), keep_key)
+    else:                               # the request path: R1CS and assignment built on the device, nothing synthesized on the host
+        circ = _PrimeShape(x, found["j"])
+        out = _setup_and_prove_prime_device(dev, x, found["j"], circ, random.Random(seed))
     return dict(proof=wire.encode_proof(out["proof"], out["inf"]), j=found["j"], num_constraints=circ.num_constraints,
                 num_variables=circ.num_vars, setup_time=out["setup_time"], proving_time=out["proving_time"], found_prime=True,
                 prime_num=str(found["prime"]), pvk=wire.encode_pvk(out["vk"]), vk=wire.encode_vk(out["vk"]), satisfied=circ.satisfied,
