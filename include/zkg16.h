@@ -112,6 +112,46 @@ ZKG16_API int zkg16_shard_plan_tables(int n_ranks, size_t m_total, size_t n_h, d
                             int window_tables, uint64_t *ranges, uint8_t *blinding, int *h_ranks_out);
 ZKG16_API void zkg16_pk_free(zkg16_ctx *ctx, uint64_t pk_handle);
 
+/* ---- device groups: several ctxs of ONE process (one per GPU; several may share a GPU) proving one proof together.
+ * zkg16_group_create: n (1..8) distinct ctxs, kept by pointer (destroy the group before them).  Ranks on different GPUs read each
+ * other's buffers: peer access is enabled here, ZKG16_ERR_UNSUPPORTED where it is unavailable.
+ * zkg16_prove_group: per rank a key shard (zkg16_pk_slice / zkg16_pk_load_range of one zkg16_shard_plan(_tables) plan: the z and h
+ * ranges tile the key, exactly one rank blinds), the R1CS and the assignment on that rank's ctx; every handle and dimension is
+ * checked on every rank before any work.  One host thread per rank, each on a lane of its ctx; the ranks with an h range form
+ * the witness-map set.  With k >= 2 of them and a two-pass domain (2^12 .. 2^24; zkg16_group_layout) they split the seven NTTs
+ * between them — seven exchanges and one redistribution of h, each a gather kernel over the rectangles of zkg16_group_layout /
+ * zkg16_group_h_layout — else each runs the whole witness map (as zkg16_prove_partial).  The partials are combined as
+ * zkg16_prove_finish combines them: the same proof bytes as zkg16_prove_resident with the whole key.  A failing rank makes every
+ * rank stop; the call returns its status (text: zkg16_group_last_error).  Group calls are serialised by the group.
+ * zkg16_witness_map_group: every rank is a witness-map rank; h (N x 4 limbs) gathered to the host, rank i bringing [iN/n, (i+1)N/n).
+ * zkg16_group_last_wm: ranks the last call's witness map was split over, 0 = the replicated map ran.
+ * zkg16_group_rank_stats: per rank of the last call: witness-map device ms (the sum of its steps between exchanges; with option
+ * "group_serial" = 1 the ranks run each step one at a time, so this is the rank's time alone on the device), bytes gathered per
+ * row-pass exchange, bytes of the h redistribution, wall ms of the rank (prove: zkg16_last_timings [9]); returns the rank count. */
+typedef struct zkg16_group zkg16_group;
+ZKG16_API int zkg16_group_create(zkg16_ctx *const *ctxs, int n, zkg16_group **out);
+ZKG16_API void zkg16_group_destroy(zkg16_group *group);
+ZKG16_API const char *zkg16_group_last_error(zkg16_group *group);
+ZKG16_API int zkg16_group_set_option(zkg16_group *group, const char *name, int64_t value);   /* "group_serial" (default 0) */
+ZKG16_API int zkg16_prove_group(zkg16_group *group, const uint64_t *pk_handles, const uint64_t *r1cs_handles, const uint64_t *witness_handles,
+                      const uint64_t r[4], const uint64_t s[4], uint64_t proof_out[48], uint8_t inf_out[3]);
+ZKG16_API int zkg16_witness_map_group(zkg16_group *group, const uint64_t *r1cs_handles, const uint64_t *witness_handles, uint64_t *h_out,
+                            size_t *log_n_out);
+ZKG16_API int zkg16_group_last_wm(zkg16_group *group, int *k_dist);
+ZKG16_API int zkg16_group_rank_stats(zkg16_group *group, double *out /* n x 4 */, int cap_ranks);
+/* The split witness map's layout (host-only, no ctx, no GPU).  The two-pass NTT of 2^log_n (ntt_mode as the option) is the matrix
+ * x[N2 i1 + i2]; with m = min(N1, N2) rank g of k owns the positions n with n mod m in [residues[2g], residues[2g+1]), an even split
+ * in units of the pass kernels' tiles.  *applies = 0 (status OK): the replicated map runs — single-pass (<= 2^11) or three-pass
+ * domains, or k above the number of units.  shape = N1, N2, m, unit.  rects (cap x 7 u64, nullable with cap 0; *n_rects = count
+ * needed, ZKG16_ERR_BAD_ARG if above cap): src rank, dst rank, row lo, row hi, col lo, col hi, row stride — the positions
+ * row * stride + col that dst copies from src before each row pass (dst's rows x src's columns, stride N2).
+ * zkg16_group_h_layout: the same for the redistribution of h, rank g receiving [h_ranges[2g], h_ranges[2g+1]) (stride m;
+ * ZKG16_ERR_UNSUPPORTED where the layout does not apply, ZKG16_ERR_BAD_ARG for ranges beyond N or overlapping). */
+ZKG16_API int zkg16_group_layout(int log_n, int k, int ntt_mode, int *applies, uint64_t shape[4], uint64_t *residues /* k x 2 */,
+                       uint64_t *rects, size_t cap, size_t *n_rects);
+ZKG16_API int zkg16_group_h_layout(int log_n, int k, int ntt_mode, const uint64_t *h_ranges /* k x 2 */, uint64_t *rects, size_t cap,
+                         size_t *n_rects);
+
 /* ---- R1CS residency (ark_relations `ConstraintMatrices<Fr>` as CSR; matrices are per-circuit constants).
  * row_ptr: num_constraints + 1 entries; col: nnz u32; coeff: nnz x 4 limbs (Montgomery). */
 ZKG16_API int zkg16_r1cs_load(zkg16_ctx *ctx,

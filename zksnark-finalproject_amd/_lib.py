@@ -37,6 +37,16 @@ SIGNATURES = {
     "zkg16_last_acc_waves": (C.c_int, [ctxp, C.POINTER(C.c_int)]),
     "zkg16_acc_resident_waves": (C.c_int, [ctxp, C.POINTER(C.c_int)]),
     "zkg16_pk_table_bits": (C.c_int, [ctxp, H, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "zkg16_group_create": (C.c_int, [vp, C.c_int, C.POINTER(vp)]),
+    "zkg16_group_destroy": (None, [vp]),
+    "zkg16_group_last_error": (C.c_char_p, [vp]),
+    "zkg16_group_set_option": (C.c_int, [vp, C.c_char_p, C.c_int64]),
+    "zkg16_prove_group": (C.c_int, [vp, u64p, u64p, u64p, u64p, u64p, u64p, u8p]),
+    "zkg16_witness_map_group": (C.c_int, [vp, u64p, u64p, u64p, C.POINTER(sz)]),
+    "zkg16_group_last_wm": (C.c_int, [vp, C.POINTER(C.c_int)]),
+    "zkg16_group_rank_stats": (C.c_int, [vp, C.POINTER(C.c_double), C.c_int]),
+    "zkg16_group_layout": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), u64p, vp, vp, sz, C.POINTER(sz)]),
+    "zkg16_group_h_layout": (C.c_int, [C.c_int, C.c_int, C.c_int, u64p, vp, sz, C.POINTER(sz)]),
     "zkg16_shard_plan": (C.c_int, [C.c_int, sz, sz, C.c_double, C.c_int, vp, u64p, u8p, C.POINTER(C.c_int)]),
     "zkg16_shard_plan_tables": (C.c_int, [C.c_int, sz, sz, C.c_double, C.c_int, vp, C.c_int, u64p, u8p, C.POINTER(C.c_int)]),
     "zkg16_pk_free": (None, [ctxp, H]),

@@ -5,6 +5,8 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <algorithm>
+#include <array>
 #include <atomic>
 #include <condition_variable>
 #include <functional>
@@ -157,6 +159,10 @@ struct R1csDev {
     DevBuf perm[3];
     bool perm_ok = false;
     std::mutex lazy_mu;             // the dictionary / row order are built once, by whichever lane gets there first
+    // a rank's rows of a split witness map (group.hip): the rows i with i mod m in [lo, hi), in the order above when it existed
+    // (from_perm), else natural; one per share this handle has served (under lazy_mu)
+    struct RowShare { uint64_t m = 0, lo = 0, hi = 0; bool from_perm = false; DevBuf list[3]; size_t n[3] = {0, 0, 0}; };
+    std::vector<std::shared_ptr<RowShare>> row_shares;
 };
 
 struct WitnessDev { size_t n = 0; DevBuf z; };
@@ -319,8 +325,18 @@ void kernel_timer_resolve(zkg16_ctx *ctx);
 struct NttPointwise { const Fr *b, *c; Fr zinv; };
 Fr *ntt_run(zkg16_ctx *ctx, Fr *src, Fr *dst, int log_n, bool inverse, bool coset, const NttPointwise *pw = nullptr);
 NttTables *ntt_get_tables(zkg16_ctx *ctx, int log_n);
+// a rank's share of a two-pass transform (split witness map): tiles {lo0, n0, lo1, n1} of the column and of the row pass, and
+// what runs between the two passes (the exchange); see ntt_run_share in ntt.hip
+struct NttShare {
+    unsigned cols[4], rows[4];
+    std::function<void()> between;
+};
+Fr *ntt_run_share(zkg16_ctx *ctx, Fr *src, Fr *dst, int log_n, bool inverse, bool coset, const NttPointwise *pw, const NttShare &share);
+bool ntt_two_pass_shape(int log_n, int ntt_mode, int *log_n1, int *log_n2, int *tile_log);
 
-void spmv_run(zkg16_ctx *ctx, R1csDev &m, const Fr *z, Fr *a, Fr *b, Fr *c);
+// rows: null = every row of the domain; else lane t of matrix i computes row list[i][t], t < n[i] (a rank's share, group.hip)
+struct SpmvRows { const uint32_t *list[3]; size_t n[3]; };
+void spmv_run(zkg16_ctx *ctx, R1csDev &m, const Fr *z, Fr *a, Fr *b, Fr *c, const SpmvRows *rows = nullptr);
 void pointwise_h_run(zkg16_ctx *ctx, Fr *ab_a, const Fr *b, const Fr *c, const Fr &zinv, size_t n);
 void fr_from_mont_run(zkg16_ctx *ctx, const Fr *in, Fr *out, size_t n);
 void witness_map_run(zkg16_ctx *ctx, R1csDev &m, const Fr *z, Fr **h_out);

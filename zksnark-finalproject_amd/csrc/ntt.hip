@@ -85,7 +85,17 @@ struct NttPassArgs {
     size_t batch_stride;         // elements between consecutive batches in `in` (and in `out` for in-place passes)
     int out_stride_log;          // rows pass: final index = batch + (k << out_stride_log)
     int xcd_order;               // 1: neighbouring tiles go to consecutive blocks of one XCD (xcd_tile); option "ntt_xcd"
+    // a rank's share of a two-pass transform (split witness map, group.hip): blockIdx.x walks the tiles [tile_lo0, + tile_n0)
+    // then [tile_lo1, + tile_n1) (grid = tile_n0 + tile_n1).  tile_n0 == 0: every tile of the pass, blockIdx.x as it is.
+    unsigned tile_lo0, tile_n0, tile_lo1, tile_n1;
 };
+
+// the tile this block works on: the XCD-aware order (group > 1) applies within the tiles the launch covers
+__device__ __forceinline__ unsigned pass_tile(const NttPassArgs &a, unsigned group) {
+    if (!a.tile_n0) return xcd_tile(blockIdx.x, gridDim.x, group);
+    const unsigned t = xcd_tile(blockIdx.x, a.tile_n0 + a.tile_n1, group);
+    return t < a.tile_n0 ? a.tile_lo0 + t : a.tile_lo1 + (t - a.tile_n0);
+}
 
 // DIF over `ncols` independent sub-transforms of size 2^log_m laid out back to back in the LDS tile.
 __device__ __forceinline__ void lds_dif(uint32_t *s_data, const uint32_t *s_tw, int log_m, int tw_stride) {
@@ -136,7 +146,7 @@ __global__ void __launch_bounds__(NTT_THREADS) ntt_pass_cols(NttPassArgs a) {
     const int C = 1 << log_c;
     const unsigned nmask = (1u << a.log_n) - 1u;
     const size_t n2 = (size_t)1 << a.log_n2;
-    const size_t col0 = (size_t)blockIdx.x * C;
+    const size_t col0 = (size_t)pass_tile(a, 1) * C;
     const Fr *in = a.in + (size_t)blockIdx.y * a.batch_stride;
     Fr *out = a.out + (size_t)blockIdx.y * a.batch_stride;
 
@@ -173,7 +183,7 @@ __global__ void __launch_bounds__(NTT_THREADS) ntt_pass_rows(NttPassArgs a) {
     const int R = 1 << log_r;
     const size_t n1 = (size_t)1 << a.log_n1;
     const size_t n2 = (size_t)1 << a.log_n2;
-    const size_t row0 = (size_t)blockIdx.x * R;
+    const size_t row0 = (size_t)pass_tile(a, 1) * R;
     const size_t n1_rows = n1;                        // rows that exist (R may exceed N1 for tiny transforms)
     const Fr *in = a.in + (size_t)blockIdx.y * a.batch_stride;
 
@@ -517,7 +527,7 @@ __global__ void __launch_bounds__(NTT_THREADS_U) ntt_pass_cols_u(NttPassArgs a) 
     const int C = 1 << log_c;
     const unsigned nmask = (1u << a.log_n) - 1u;
     const size_t n2 = (size_t)1 << a.log_n2;
-    const size_t col0 = (size_t)xcd_tile(blockIdx.x, gridDim.x, (C >= 4 || !a.xcd_order) ? 1u : 4u / (unsigned)C) * C;
+    const size_t col0 = (size_t)pass_tile(a, (C >= 4 || !a.xcd_order) ? 1u : 4u / (unsigned)C) * C;
     const Fr *in = a.in + (size_t)blockIdx.y * a.batch_stride;
     Fr *out = a.out + (size_t)blockIdx.y * a.batch_stride;
 
@@ -550,7 +560,7 @@ __global__ void __launch_bounds__(NTT_THREADS_U) ntt_pass_rows_u(NttPassArgs a) 
     const int R = 1 << log_r;
     const size_t n1 = (size_t)1 << a.log_n1;
     const size_t n2 = (size_t)1 << a.log_n2;
-    const size_t row0 = (size_t)xcd_tile(blockIdx.x, gridDim.x, (R >= 4 || !a.xcd_order) ? 1u : 4u / (unsigned)R) * R;
+    const size_t row0 = (size_t)pass_tile(a, (R >= 4 || !a.xcd_order) ? 1u : 4u / (unsigned)R) * R;
     const Fr *in = a.in + (size_t)blockIdx.y * a.batch_stride;
 
     if (!GTW) stage_twiddles_u(s_tw, tw_stride, a.w, a.log_n, a.log_n2, a.inverse);
@@ -651,11 +661,20 @@ NttTables *ntt_get_tables(zkg16_ctx *ctx, int log_n) {
     return raw;
 }
 
+// grid of a share's pass: its tile ranges {lo0, n0, lo1, n1} go into the pass arguments
+static unsigned share_tiles(NttPassArgs &p, const unsigned t[4]) {
+    if (!t[1]) throw HipError{hipErrorInvalidValue, "ntt: a share without tiles", __FILE__, __LINE__};
+    p.tile_lo0 = t[0]; p.tile_n0 = t[1]; p.tile_lo1 = t[2]; p.tile_n1 = t[3];
+    return t[1] + t[3];
+}
+
 // Out of place: the transform of `src` ends in `dst` (N elements each); `src` is scratch afterwards (the column passes
 // run in place on it, the last pass writes `dst`) — callers ping-pong two buffers instead of copying a result back
 // (round 1 ended every transform with a device-to-device copy: 7 x 64 N bytes per proof).
 // pw (optional): the witness map's point-wise stage fused into the first pass's load: src[i] <- (src[i]*b[i] - c[i]) / Z.
-Fr *ntt_run(zkg16_ctx *ctx, Fr *data, Fr *tmp, int log_n, bool inverse, bool coset, const NttPointwise *pw) {
+// share (ntt_run_share): only a rank's tiles of each pass, and share->between() in between.
+static Fr *ntt_run_impl(zkg16_ctx *ctx, Fr *data, Fr *tmp, int log_n, bool inverse, bool coset, const NttPointwise *pw,
+                        const NttShare *share) {
     bool &lds_attr_set = ctx->lds_attr_ntt;          // per ctx (= per device)
     if (!lds_attr_set) {   // 64-72 KiB tile + up to 36 KiB of twiddles, or a 144 KiB tile: above the 64 KiB default dynamic-LDS cap
         for (const void *f : {reinterpret_cast<const void *>(ntt_pass_cols), reinterpret_cast<const void *>(ntt_pass_rows),
@@ -755,19 +774,20 @@ Fr *ntt_run(zkg16_ctx *ctx, Fr *data, Fr *tmp, int log_n, bool inverse, bool cos
             p1.in = data; p1.out = data;
             first(p1);
             p1.batch_stride = 0;
-            const unsigned grid = (unsigned)(((size_t)1 << a.log_n2) >> (12 - a.log_n1));
+            const unsigned grid = share ? share_tiles(p1, share->cols) : (unsigned)(((size_t)1 << a.log_n2) >> (12 - a.log_n1));
             ScopedKernelTimer kt(ctx, "ntt_pass_cols", (double)n);
             if (xch2) hipLaunchKernelGGL((ntt_pass_cols_u<12, true, 3>), dim3(grid), dim3(NTT_THREADS_U), big_lds, ctx->stream, p1);
             else if (xch) hipLaunchKernelGGL((ntt_pass_cols_u<12, true, 2>), dim3(grid), dim3(NTT_THREADS_U), big_lds, ctx->stream, p1);
             else if (r4) hipLaunchKernelGGL((ntt_pass_cols_u<12, true, true>), dim3(grid), dim3(NTT_THREADS_U), big_lds, ctx->stream, p1);
             else hipLaunchKernelGGL((ntt_pass_cols_u<12, true, false>), dim3(grid), dim3(NTT_THREADS_U), big_lds, ctx->stream, p1);
         }
+        if (share) share->between();
         {
             NttPassArgs p2 = a;
             p2.in = data; p2.out = tmp;
             p2.post = post;
             p2.post_const_on = post_const_on;
-            const unsigned grid = (unsigned)((size_t)1 << a.log_n1);
+            const unsigned grid = share ? share_tiles(p2, share->rows) : (unsigned)((size_t)1 << a.log_n1);
             ScopedKernelTimer kt(ctx, "ntt_pass_rows", (double)n);
             if (xch2) hipLaunchKernelGGL((ntt_pass_rows_u<12, true, 3>), dim3(grid), dim3(NTT_THREADS_U), big_lds, ctx->stream, p2);
             else if (xch) hipLaunchKernelGGL((ntt_pass_rows_u<12, true, 2>), dim3(grid), dim3(NTT_THREADS_U), big_lds, ctx->stream, p2);
@@ -775,6 +795,7 @@ Fr *ntt_run(zkg16_ctx *ctx, Fr *data, Fr *tmp, int log_n, bool inverse, bool cos
             else hipLaunchKernelGGL((ntt_pass_rows_u<12, true, false>), dim3(grid), dim3(NTT_THREADS_U), big_lds, ctx->stream, p2);
         }
     } else if (log_n <= NTT_MAX_SUB_LOG) {
+        if (share) throw HipError{hipErrorInvalidValue, "ntt: a share of a single-pass transform", __FILE__, __LINE__};
         a.log_n1 = 0;
         a.log_n2 = log_n;
         a.in = data;
@@ -788,6 +809,7 @@ Fr *ntt_run(zkg16_ctx *ctx, Fr *data, Fr *tmp, int log_n, bool inverse, bool cos
         // N = N0 * M (N0 = 1 for N <= 2^22): [outer column pass over N0] then the two-pass transform of size M, batched over k0 < N0
         const int log_m = log_n <= 2 * NTT_MAX_SUB_LOG ? log_n : 2 * NTT_MAX_SUB_LOG;
         const int log_n0 = log_n - log_m;
+        if (share && log_n0 > 0) throw HipError{hipErrorInvalidValue, "ntt: a share of a three-pass transform", __FILE__, __LINE__};
         if (log_n0 > 0) {
             NttPassArgs p0 = a;
             p0.in = data; p0.out = data;
@@ -806,10 +828,11 @@ Fr *ntt_run(zkg16_ctx *ctx, Fr *data, Fr *tmp, int log_n, bool inverse, bool cos
             if (log_n0 == 0) first(p1);
             p1.tw_shift = log_n0;
             p1.batch_stride = (size_t)1 << log_m;
-            const unsigned grid = (unsigned)(((size_t)1 << a.log_n2) >> (NTT_TILE_LOG - a.log_n1));
+            const unsigned grid = share ? share_tiles(p1, share->cols) : (unsigned)(((size_t)1 << a.log_n2) >> (NTT_TILE_LOG - a.log_n1));
             ScopedKernelTimer kt(ctx, "ntt_pass_cols", (double)n);
             hipLaunchKernelGGL(k_cols, dim3(grid, batches), dim3(nthreads), lds_bytes(a.log_n1), ctx->stream, p1);
         }
+        if (share) share->between();
         {
             NttPassArgs p2 = a;
             p2.in = data; p2.out = tmp;
@@ -817,13 +840,43 @@ Fr *ntt_run(zkg16_ctx *ctx, Fr *data, Fr *tmp, int log_n, bool inverse, bool cos
             p2.post_const_on = post_const_on;
             p2.batch_stride = (size_t)1 << log_m;
             p2.out_stride_log = log_n0;
-            const unsigned grid = (unsigned)(((size_t)1 << a.log_n1) >> (NTT_TILE_LOG - a.log_n2));
+            const unsigned grid = share ? share_tiles(p2, share->rows) : (unsigned)(((size_t)1 << a.log_n1) >> (NTT_TILE_LOG - a.log_n2));
             ScopedKernelTimer kt(ctx, "ntt_pass_rows", (double)n);
             hipLaunchKernelGGL(k_rows, dim3(grid, batches), dim3(nthreads), lds_bytes(a.log_n2), ctx->stream, p2);
         }
     }
     ZK_HIP(hipGetLastError());
     return tmp;
+}
+
+Fr *ntt_run(zkg16_ctx *ctx, Fr *data, Fr *tmp, int log_n, bool inverse, bool coset, const NttPointwise *pw) {
+    return ntt_run_impl(ctx, data, tmp, log_n, inverse, coset, pw, nullptr);
+}
+
+// A rank's share of one two-pass transform (split witness map, group.hip): the column pass over the tiles share->cols, then
+// share->between() (the exchange that completes the rank's rows), then the row pass over the tiles share->rows.  Only the
+// positions the rank owns become valid in `tmp`.  Single- and three-pass sizes have no share (an error).
+Fr *ntt_run_share(zkg16_ctx *ctx, Fr *data, Fr *tmp, int log_n, bool inverse, bool coset, const NttPointwise *pw, const NttShare &share) {
+    if (!ntt_two_pass_shape(log_n, ctx->opt_ntt_mode, nullptr, nullptr, nullptr))
+        throw HipError{hipErrorInvalidValue, "ntt: a share of a transform that is not two-pass", __FILE__, __LINE__};
+    return ntt_run_impl(ctx, data, tmp, log_n, inverse, coset, pw, &share);
+}
+
+// The shape ntt_run gives a 2^log_n transform when it is two passes: N1 = 2^log_n1 columns-first, N2 = 2^log_n2, tiles of
+// 2^tile_log elements (column tiles hold 2^tile_log / N1 columns, row tiles 2^tile_log / N2 rows).  Mirrors ntt_run's plan choice.
+bool ntt_two_pass_shape(int log_n, int ntt_mode, int *log_n1, int *log_n2, int *tile_log) {
+    int l1, l2, tl;
+    if (ntt_mode != 0 && ntt_mode != 3 && log_n > 2 * NTT_MAX_SUB_LOG && log_n <= 24) {
+        l2 = 12; l1 = log_n - 12; tl = 12;
+    } else if (log_n > NTT_MAX_SUB_LOG && log_n <= 2 * NTT_MAX_SUB_LOG) {
+        l2 = log_n / 2; l1 = log_n - l2; tl = NTT_TILE_LOG;
+    } else {
+        return false;
+    }
+    if (log_n1) *log_n1 = l1;
+    if (log_n2) *log_n2 = l2;
+    if (tile_log) *tile_log = tl;
+    return true;
 }
 
 }  // namespace zk

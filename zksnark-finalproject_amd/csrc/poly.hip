@@ -29,7 +29,24 @@ struct SpmvArgs {
     Fr *out[3];
     const Fr *z;
     size_t nc, num_instance, n;   // n = domain size (outputs are zero-padded to n)
+    const uint32_t *rows[3];      // null, or lane t takes row rows[m][t], t < nrows[m] (a rank's rows, split witness map)
+    size_t nrows[3];
 };
+// the row of lane `t` of matrix m: from the rank's row list, else from the length-class order (rows < nc), else t itself
+template <class Args>
+__device__ __forceinline__ bool spmv_row(const Args &a, int m, size_t &row) {
+    if (a.rows[m]) {
+        if (row >= a.nrows[m]) return false;
+        row = a.rows[m][row];
+        return row < a.n;
+    }
+    if (row >= a.n) return false;
+    if (row < a.nc && a.perm[m]) {
+        row = a.perm[m][row];
+        if (row >= a.nc) return false;          // never: the order is a permutation of the rows (row_perm_build)
+    }
+    return true;
+}
 
 // One thread per (matrix, row): the reference's circuits have short rows (matmul rows: 1 nnz per side;
 // Poseidon rows: a few tens), so a row per lane keeps all 64 lanes busy.  Rows >= nc are the padding:
@@ -37,11 +54,7 @@ struct SpmvArgs {
 __global__ void __launch_bounds__(256) spmv_kernel(SpmvArgs a) {
     size_t row = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int m = blockIdx.y;
-    if (row >= a.n) return;
-    if (row < a.nc && a.perm[m]) {
-        row = a.perm[m][row];
-        if (row >= a.nc) return;                // never: the order is a permutation of the rows (row_perm_build)
-    }
+    if (!spmv_row(a, m, row)) return;
     Fr acc = Fr::zero();
     if (row < a.nc) {
         const uint64_t lo = a.rp[m][row], hi = a.rp[m][row + 1];
@@ -193,6 +206,8 @@ struct SpmvDictArgs {
     const Fr *z, *dict;
     uint32_t ndict;
     size_t nc, num_instance, n;
+    const uint32_t *rows[3];
+    size_t nrows[3];
 };
 // the same row-per-lane product with the coefficient taken from the dictionary in LDS ([8][ndict] words: neighbouring lanes
 // reading different entries spread over the banks); a coefficient equal to one (40 % of the MatrixCircuit's, all of its C
@@ -209,11 +224,7 @@ __global__ void __launch_bounds__(256) spmv_dict_kernel(SpmvDictArgs a) {
     __syncthreads();
     size_t row = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int m = blockIdx.y;
-    if (row >= a.n) return;
-    if (row < a.nc && a.perm[m]) {
-        row = a.perm[m][row];
-        if (row >= a.nc) return;                // never: the order is a permutation of the rows (row_perm_build)
-    }
+    if (!spmv_row(a, m, row)) return;
     Fr acc = Fr::zero();
     if (row < a.nc) {
         const uint64_t lo = a.rp[m][row], hi = a.rp[m][row + 1];
@@ -373,7 +384,7 @@ static void coef_dict_build(zkg16_ctx *ctx, R1csDev &m) {
     m.dict_state = 1;
 }
 
-void spmv_run(zkg16_ctx *ctx, R1csDev &m, const Fr *z, Fr *a, Fr *b, Fr *c) {
+void spmv_run(zkg16_ctx *ctx, R1csDev &m, const Fr *z, Fr *a, Fr *b, Fr *c, const SpmvRows *rows) {
     // both structures are built the SECOND time a handle is used: the reference's request flow uses its matrices once (the
     // three passes of the build cost more than they save there: Fermat-prime request 8.1 -> 9.7 ms), a resident system pays once
     {
@@ -381,7 +392,10 @@ void spmv_run(zkg16_ctx *ctx, R1csDev &m, const Fr *z, Fr *a, Fr *b, Fr *c) {
         if (m.dict_state == 0 && ctx->opt_spmv_dict != 2 && ++m.spmv_uses >= 2) coef_dict_build(ctx, m);
     }
     const size_t n = (size_t)1 << m.log_n;
-    const unsigned grid = (unsigned)((n + 255) / 256);
+    size_t lanes = n;
+    if (rows) lanes = std::max(rows->n[0], std::max(rows->n[1], rows->n[2]));
+    if (!lanes) return;
+    const unsigned grid = (unsigned)((lanes + 255) / 256);
     ScopedKernelTimer kt(ctx, "spmv_kernel", (double)(m.nnz[0] + m.nnz[1] + m.nnz[2]));
     if (m.dict_state == 1 && ctx->opt_spmv_dict != 2) {
         SpmvDictArgs s;
@@ -398,6 +412,10 @@ void spmv_run(zkg16_ctx *ctx, R1csDev &m, const Fr *z, Fr *a, Fr *b, Fr *c) {
         s.nc = m.num_constraints;
         s.num_instance = m.num_instance;
         s.n = n;
+        for (int i = 0; i < 3; i++) {
+            s.rows[i] = rows ? rows->list[i] : nullptr;
+            s.nrows[i] = rows ? rows->n[i] : 0;
+        }
         hipLaunchKernelGGL(spmv_dict_kernel, dim3(grid, 3), dim3(256), m.ndict * 33 + 16, ctx->stream, s);
     } else {
         SpmvArgs s;
@@ -412,6 +430,10 @@ void spmv_run(zkg16_ctx *ctx, R1csDev &m, const Fr *z, Fr *a, Fr *b, Fr *c) {
         s.nc = m.num_constraints;
         s.num_instance = m.num_instance;
         s.n = n;
+        for (int i = 0; i < 3; i++) {
+            s.rows[i] = rows ? rows->list[i] : nullptr;
+            s.nrows[i] = rows ? rows->n[i] : 0;
+        }
         hipLaunchKernelGGL(spmv_kernel, dim3(grid, 3), dim3(256), 0, ctx->stream, s);
     }
     ZK_HIP(hipGetLastError());

@@ -529,3 +529,112 @@ def verify_prepared(pvk, public_inputs_mont, proof48, inf3):
     if rc != 0:
         raise Zkg16Error(rc, lib.zkg16_strerror(rc).decode())
     return bool(ok.value)
+
+
+class DeviceGroup:
+    """Several Devices of this process proving one proof together (zkg16_group_create): one per GPU, or several on one GPU.
+    The ranks whose key shard has an h range split the witness map's seven NTTs between them where the layout applies
+    (group_layout); the group keeps its Devices alive and must be closed before them."""
+
+    def __init__(self, devices):
+        self.devices = list(devices)
+        self.lib = _lib.load()
+        self.group = C.c_void_p()
+        arr = (C.c_void_p * len(self.devices))(*[d.ctx.value for d in self.devices])
+        rc = self.lib.zkg16_group_create(arr, len(self.devices), C.byref(self.group))
+        if rc != 0:
+            raise Zkg16Error(rc, self.lib.zkg16_strerror(rc).decode())
+
+    def close(self):
+        if self.group:
+            self.lib.zkg16_group_destroy(self.group)
+            self.group = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc):
+        if rc != 0:
+            detail = self.lib.zkg16_group_last_error(self.group).decode()
+            raise Zkg16Error(rc, self.lib.zkg16_strerror(rc).decode() + (" — " + detail if detail else ""))
+
+    def _handles(self, hs, what):
+        hs = np.ascontiguousarray(hs, dtype=np.uint64)
+        if hs.shape != (len(self.devices),):
+            raise ValueError("%s: one handle per device (%d), got %s" % (what, len(self.devices), hs.shape))
+        return hs
+
+    def set_option(self, name, value):
+        self._check(self.lib.zkg16_group_set_option(self.group, name.encode(), int(value)))
+
+    def witness_map(self, r1cs_handles, witness_handles, n_max):
+        """h of the group's witness map, gathered to the host (zkg16_witness_map_group)."""
+        h = np.zeros((n_max, 4), dtype=np.uint64)
+        log_n = C.c_size_t()
+        self._check(self.lib.zkg16_witness_map_group(self.group, self._handles(r1cs_handles, "r1cs"), self._handles(witness_handles, "witness"),
+                                                     h, C.byref(log_n)))
+        return h[: 1 << log_n.value]
+
+    def prove(self, pk_handles, r1cs_handles, witness_handles, r, s):
+        """One proof over the group's ranks: per rank a key shard of one shard_plan (zkg16_prove_group) -> (proof, inf)."""
+        proof = np.zeros(48, dtype=np.uint64)
+        inf = np.zeros(3, dtype=np.uint8)
+        self._check(self.lib.zkg16_prove_group(self.group, self._handles(pk_handles, "pk"), self._handles(r1cs_handles, "r1cs"),
+                                               self._handles(witness_handles, "witness"), _u64(r), _u64(s), proof, inf))
+        return proof, inf
+
+    def last_wm(self):
+        """Ranks the last call's witness map was split over; 0 = the replicated map ran (zkg16_group_last_wm)."""
+        k = C.c_int(0)
+        self._check(self.lib.zkg16_group_last_wm(self.group, C.byref(k)))
+        return k.value
+
+    def rank_stats(self):
+        """Per rank of the last call: dict(wm_ms, exchange_bytes, h_bytes, wall_ms) (zkg16_group_rank_stats)."""
+        n = len(self.devices)
+        buf = (C.c_double * (4 * n))()
+        got = self.lib.zkg16_group_rank_stats(self.group, buf, n)
+        if got < 0 or got > n:
+            self._check(got)
+        return [dict(wm_ms=buf[4 * i], exchange_bytes=int(buf[4 * i + 1]), h_bytes=int(buf[4 * i + 2]), wall_ms=buf[4 * i + 3])
+                for i in range(got)]
+
+
+def group_layout(log_n, k, ntt_mode=1):
+    """Host-only layout of the split witness map (zkg16_group_layout) -> dict(applies, n1, n2, m, unit, residues [(lo, hi)] per rank,
+    rects [(src, dst, row_lo, row_hi, col_lo, col_hi, stride)] of the row-pass exchange)."""
+    lib = _lib.load()
+    applies = C.c_int(0)
+    shape = np.zeros(4, dtype=np.uint64)
+    res = np.zeros(2 * max(k, 1), dtype=np.uint64)
+    n = C.c_size_t(0)
+    rc = lib.zkg16_group_layout(log_n, k, ntt_mode, C.byref(applies), shape, res.ctypes.data, None, 0, C.byref(n))
+    if rc != 0 and not (rc == 1 and n.value > 0):
+        raise Zkg16Error(rc, lib.zkg16_strerror(rc).decode())
+    rects = np.zeros((max(n.value, 1), 7), dtype=np.uint64)
+    rc = lib.zkg16_group_layout(log_n, k, ntt_mode, C.byref(applies), shape, res.ctypes.data, rects.ctypes.data, rects.shape[0], C.byref(n))
+    if rc != 0:
+        raise Zkg16Error(rc, lib.zkg16_strerror(rc).decode())
+    return dict(applies=bool(applies.value), n1=int(shape[0]), n2=int(shape[1]), m=int(shape[2]), unit=int(shape[3]),
+                residues=[(int(res[2 * g]), int(res[2 * g + 1])) for g in range(k)],
+                rects=[tuple(int(x) for x in r) for r in rects[: n.value]])
+
+
+def group_h_layout(log_n, k, h_ranges, ntt_mode=1):
+    """Rectangles (src, dst, row_lo, row_hi, col_lo, col_hi, stride) of the h redistribution (zkg16_group_h_layout)."""
+    lib = _lib.load()
+    hr = np.ascontiguousarray(h_ranges, dtype=np.uint64).reshape(-1)
+    if hr.shape[0] != 2 * k:
+        raise ValueError("group_h_layout: %d ranges for %d ranks" % (hr.shape[0] // 2, k))
+    n = C.c_size_t(0)
+    rc = lib.zkg16_group_h_layout(log_n, k, ntt_mode, hr, None, 0, C.byref(n))
+    if rc != 0 and not (rc == 1 and n.value > 0):
+        raise Zkg16Error(rc, lib.zkg16_strerror(rc).decode())
+    rects = np.zeros((max(n.value, 1), 7), dtype=np.uint64)
+    rc = lib.zkg16_group_h_layout(log_n, k, ntt_mode, hr, rects.ctypes.data, rects.shape[0], C.byref(n))
+    if rc != 0:
+        raise Zkg16Error(rc, lib.zkg16_strerror(rc).decode())
+    return [tuple(int(x) for x in r) for r in rects[: n.value]]
