@@ -217,6 +217,78 @@ ZK_HD void xyzz_madd_finish(XYZZ<FqU> &acc, const MaddTail<FqU> &t, bool normal)
     if (normal) acc.y = y;
 }
 
+#if defined(__HIP_DEVICE_COMPILE__)
+// ---- the G1 mixed addition with every field product inlined: the default G1 bucket accumulation (msm.hip).  No call on the
+// main path, so no argument moves and no call-entry wait for every outstanding memory operation: the gather of the next base
+// and the stores of a finished bucket stay in flight across the whole addition.  The same formulas, in the same order, as
+// xyzz_madd (bit-identical sums).  A scheduling barrier around every product keeps the products from being interleaved: one
+// product's working set (~44 registers) on top of the addition's live values fits the 256 registers of two waves per SIMD,
+// several interleaved ones spill.  The doubling (P == Q) is inlined too: a single call anywhere in the kernel would pin the
+// values live across it to the callee-saved registers and spill the rest around it.  The gather of the next base, issued
+// before the addition, is not waited for until the next one.
+__device__ __forceinline__ FqU fqu_mul_il(const FqU &a, const FqU &b) {
+    __builtin_amdgcn_sched_barrier(0);
+    const FqU r = fqu_mul_impl<false>(a, b);
+    __builtin_amdgcn_sched_barrier(0);
+    return r;
+}
+__device__ __forceinline__ FqU fqu_sqr_il(const FqU &a) {
+    __builtin_amdgcn_sched_barrier(0);
+    const FqU r = fqu_mul_impl<true>(a, a);
+    __builtin_amdgcn_sched_barrier(0);
+    return r;
+}
+__device__ __forceinline__ FqU fqu_mul2_il(const FqU &a, const FqU &b, const FqU &c, const FqU &d) {
+    __builtin_amdgcn_sched_barrier(0);
+    const FqU r = fqu_mul2(a, b, c, d);
+    __builtin_amdgcn_sched_barrier(0);
+    return r;
+}
+__device__ __forceinline__ XYZZ<FqU> xyzz_dbl_affine_inline(const Affine<FqU> &p) {      // = xyzz_dbl_affine
+    FqU U = f_dbl(p.y);
+    FqU V = fqu_sqr_il(U);
+    FqU W = fqu_mul_il(U, V);
+    FqU S = fqu_mul_il(p.x, V);
+    FqU X2 = fqu_sqr_il(p.x);
+    FqU M = f_add(f_dbl(X2), X2);
+    XYZZ<FqU> r;
+    r.x = f_sub(fqu_sqr_il(M), f_dbl(S));
+    r.y = f_sub(fqu_mul_il(M, f_sub2(S, r.x)), fqu_mul_il(W, p.y));
+    r.zz = V;
+    r.zzz = W;
+    return r;
+}
+__device__ __forceinline__ void xyzz_madd_inline(XYZZ<FqU> &acc, const Affine<FqU> &q_in, bool neg) {
+    if (q_in.is_inf()) return;
+    Affine<FqU> q = q_in;
+    if (neg) q.y = f_neg(q.y);
+    if (acc.is_inf()) {
+        acc = XYZZ<FqU>{q.x, q.y, FqU::one(), FqU::one()};
+        return;
+    }
+    FqU U2 = fqu_mul_il(q.x, acc.zz);
+    FqU S2 = fqu_mul_il(q.y, acc.zzz);
+    FqU Pp = f_sub2(U2, acc.x);
+    FqU R = f_sub2(S2, acc.y);
+    // P == +-Q: the lanes concerned run the general formula as well (on Pp = 0 mod q, harmlessly) and then replace its result.
+    // Doubling after the general formula, not in a branch before it: there the general formula's inputs (bucket, Pp, R) would
+    // be live across the doubling's products as well, 30 registers more than the file holds.
+    const bool same_x = f_is_zero_mod(Pp);
+    const bool same_p = same_x && f_is_zero_mod(R);
+    FqU PP = fqu_sqr_il(Pp);
+    FqU PPP = fqu_mul_il(Pp, PP);
+    acc.zz = fqu_mul_il(acc.zz, PP);
+    acc.zzz = fqu_mul_il(acc.zzz, PPP);
+    FqU Q = fqu_mul_il(acc.x, PP);
+    FqU X3 = f_sub(fqu_sqr_il(R), f_add(PPP, f_dbl(Q)));
+    acc.y = fqu_mul2_il(R, f_sub2(Q, X3), fqu_sub<64>(FqU::zero(), acc.y), PPP);      // = f_mul_sub(R, Q - X3, Y1, PPP)
+    acc.x = X3;
+    if (same_x) acc = same_p ? xyzz_dbl_affine_inline(q) : XYZZ<FqU>::inf();
+}
+#else
+__host__ __device__ inline void xyzz_madd_inline(XYZZ<FqU> &acc, const Affine<FqU> &q, bool neg) { xyzz_madd(acc, q, neg); }      // host pass of the kernel template only
+#endif
+
 ZK_HD bool xyzz_madd_front(XYZZ<Fq2U> &acc, const Affine<Fq2U> &q_in, bool neg, MaddTail<Fq2U> &t) {
     if (q_in.is_inf()) { t.a = t.b = Fq2U::zero(); return false; }
     Affine<Fq2U> q = q_in;

@@ -181,7 +181,8 @@ struct AccArgs {
 
 // G1: 2 waves per SIMD (<= 256 registers) hide the base-gather latency; G2's live state needs the whole file.
 // LAZY (G2 only): the mixed addition's Fq2 products with one reduction per component (ec.cuh: xyzz_madd_lazy)
-template <class F, bool PIPE, bool LAZY = false>
+// CALLS (G1 only, PIPE = false): the round-1 loop whose field products are device-function calls (option "g1_inline" = 2)
+template <class F, bool PIPE, bool LAZY = false, bool CALLS = false>
 __global__ void __launch_bounds__(64, FieldTraits<F>::g2 ? 1 : 2) msm_accumulate_kernel(AccArgs<F> a) {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t total = *a.total_ptr;
@@ -271,8 +272,41 @@ __global__ void __launch_bounds__(64, FieldTraits<F>::g2 ? 1 : 2) msm_accumulate
             asm volatile("" ::: "memory");            // the loads above stay above the inlined product
             xyzz_madd_finish(acc, tail, normal);
         }
+    } else if constexpr (!FieldTraits<F>::g2 && !CALLS) {
+        // G1 default: every field product inlined (ec.cuh: xyzz_madd_inline), so nothing inside an addition waits for memory.  The
+        // base of term p+1 is gathered, and entry p+2 loaded, in front of the addition of term p; a finished bucket is stored
+        // where it ends.  Both are waited for only at the next iteration, one whole addition later.
+        uint2 en1 = a.entries[start + 1 < end ? start + 1 : start];      // (a select between a load and `en` would put `en` on the stack)
+        Affine<F> bq = ldv(a.bases + (en.x >> 1));
+        // wait for the first base and entry here: the registers loaded in front of the loop are the ones copied at its end, and
+        // with a load pending on entry every iteration would wait, right after its gather, for the stores of a finished bucket
+#pragma unroll
+        for (int k = 0; k < 14; k++) asm volatile("" ::"v"(bq.x.l[k]), "v"(bq.y.l[k]));
+        asm volatile("" ::"v"(en1.x), "v"(en1.y));
+        for (uint32_t p = start; p < end; p++) {
+            const uint32_t e = en.x, gb = (a.debug & 8u) ? cur : en.y;      // bit 3: never leave the first bucket
+            if (gb != cur) {
+                XYZZ<F> *dst = nullptr;
+                if (cur == g_first && head_open) {
+                    head_b = (int32_t)cur;
+                    dst = a.seg_head + t;
+                } else if (!acc.is_inf()) {
+                    dst = a.buckets + cur;
+                }
+                if (dst != nullptr && !(a.debug & 1u)) stv(dst, acc);
+                acc = XYZZ<F>::inf();
+                cur = gb;
+            }
+            const Affine<F> b = bq;
+            // unconditional (index clamped to the segment), as in the pipelined form; the last iteration re-reads its own entry / base
+            en = en1;
+            en1 = a.entries[p + 2 < end ? p + 2 : end - 1];
+            bq = ldv(a.bases + ((a.debug & 2u) ? 0u : (a.debug & 4u) ? ((en.x >> 1) & 0xffffu) : (en.x >> 1)));
+            __builtin_amdgcn_sched_barrier(0);       // the loads above stay above the addition
+            xyzz_madd_inline(acc, b, (e & 1u) != 0);
+        }
     } else {
-        // round-1 form: the base is gathered right before its addition (kept selectable: option "acc_pipeline")
+        // round-1 form: the base is gathered right before its addition (kept selectable: option "acc_pipeline"; for G1 "g1_inline")
         uint32_t e = en.x, gb = en.y;
         for (uint32_t p = start; p < end; p++) {
             if (p + 1 < end) en = a.entries[p + 1];
@@ -1023,6 +1057,7 @@ static void msm_enqueue_acc(zkg16_ctx *ctx, MsmWorkspace &ws, const MsmPlan &pla
         const bool pipe = (ctx->opt_acc_pipeline >> (FieldTraits<F>::g2 ? 1 : 0)) & 1;
         if (pipe) hipLaunchKernelGGL((msm_accumulate_kernel<F, true>), dim3(grid), dim3(64), 0, ctx->stream, a);
         else if (FieldTraits<F>::g2 && ctx->opt_g2_lazy) hipLaunchKernelGGL((msm_accumulate_kernel<F, false, true>), dim3(grid), dim3(64), 0, ctx->stream, a);
+        else if (!FieldTraits<F>::g2 && !ctx->opt_g1_inline) hipLaunchKernelGGL((msm_accumulate_kernel<F, false, false, true>), dim3(grid), dim3(64), 0, ctx->stream, a);
         else hipLaunchKernelGGL((msm_accumulate_kernel<F, false>), dim3(grid), dim3(64), 0, ctx->stream, a);
     }
     static_assert(sizeof(AccArgs<F>) <= sizeof(slot.acc_args), "MsmSlot::acc_args too small");
@@ -1229,6 +1264,7 @@ int msm_acc_resident_waves(zkg16_ctx *ctx, bool g2) {
         else e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, msm_accumulate_kernel<Fq2U, false>, 64, 0);
     } else {
         if (pipe) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, msm_accumulate_kernel<FqU, true>, 64, 0);
+        else if (!ctx->opt_g1_inline) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, msm_accumulate_kernel<FqU, false, false, true>, 64, 0);
         else e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, msm_accumulate_kernel<FqU, false>, 64, 0);
     }
     ZK_HIP(e);
