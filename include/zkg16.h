@@ -172,6 +172,20 @@ ZKG16_API int zkg16_witness_read(zkg16_ctx *ctx, uint64_t witness_handle, uint64
 ZKG16_API int zkg16_prove_resident(zkg16_ctx *ctx, uint64_t pk_handle, uint64_t r1cs_handle, uint64_t witness_handle,
                          const uint64_t r[4], const uint64_t s[4], uint64_t proof_out[48], uint8_t inf_out[3]);
 
+/* K proofs of ONE circuit on ONE resident key, in one device pass.  witness_handles[k]: the full assignment of proof k
+ * (num_variables of r1cs_handle); r, s: k x 4 Montgomery limbs; proofs_out: k x 48; inf_out: k x 3.
+ * Proof k is byte-identical to zkg16_prove_resident(ctx, pk_handle, r1cs_handle, witness_handles[k], r + 4k, s + 4k).
+ * One lane, like the other proving calls.  The witness map is one SpMV and seven transforms over the K assignments (every launch
+ * with a vector index), and every MSM sorts, accumulates and reduces the K proofs' terms as ONE list whose bucket sets are the K
+ * proofs' windows.  k is split into sub-batches of at most 65,535 proofs whose term lists stay under 2^31 terms and whose
+ * workspaces fit the free HBM (option "batch_max" caps them).  k == 0, null pointers and lengths that do not match:
+ * ZKG16_ERR_BAD_ARG; an unknown handle: ZKG16_ERR_BAD_HANDLE; a key that is not whole (a shard): ZKG16_ERR_UNSUPPORTED — all
+ * checked before any work.  On any error nothing is written to proofs_out / inf_out (the proofs are staged until every
+ * sub-batch has succeeded).  zkg16_last_timings / zkg16_last_term_counts then describe the whole batch (timings: [3] wait for
+ * H, [7] wait for the z-side MSMs, [8] H's combination and the tails of all proofs, [21] the other MSMs' combination). */
+ZKG16_API int zkg16_prove_batch(zkg16_ctx *ctx, uint64_t pk_handle, uint64_t r1cs_handle, const uint64_t *witness_handles,
+                                size_t k, const uint64_t *r, const uint64_t *s, uint64_t *proofs_out, uint8_t *inf_out);
+
 /* One-shot form mirroring create_proof_with_reduction_and_matrices: host pointers in, proof out
  * (uploads matrices + assignment, proves, frees). */
 ZKG16_API int zkg16_prove(zkg16_ctx *ctx, uint64_t pk_handle, const uint64_t r[4], const uint64_t s[4],
@@ -412,6 +426,7 @@ ZKG16_API void zkg16_kernel_stats_reset(zkg16_ctx *ctx);
  *   "g1_inline"      G1 accumulation (plain loop): 0 / 1 (default) every field product inlined, no call; 2 = products as device-function calls
  *   "lanes"          proofs this ctx runs at a time (1..8, default 2): see the note on re-entrancy at the top
  *   "matrix_parts"   zkg16_prove_matrix: slices of the host sponges the proof is fed in (0 = five growing slices, k = k equal ones; 1 = assignment first, then the proof)
+ *   "batch_max"      zkg16_prove_batch: proofs per device pass (0 = as many as fit, else 1..65535)
  * Unknown names return ZKG16_ERR_UNSUPPORTED. */
 ZKG16_API int zkg16_set_option(zkg16_ctx *ctx, const char *name, int64_t value);
 

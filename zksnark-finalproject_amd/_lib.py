@@ -57,6 +57,7 @@ SIGNATURES = {
     "zkg16_witness_read": (C.c_int, [ctxp, H, u64p, sz]),
     "zkg16_prove_resident": (C.c_int, [ctxp, H, H, H, u64p, u64p, u64p, u8p]),
     "zkg16_prove": (C.c_int, [ctxp, H, u64p, u64p] + [u64p, vp, vp] * 3 + [sz, sz, u64p, sz, u64p, u8p]),
+    "zkg16_prove_batch": (C.c_int, [ctxp, H, H, u64p, sz, u64p, u64p, u64p, u8p]),
     "zkg16_prove_partial": (C.c_int, [ctxp, H, H, H, u64p, u64p, u64p, u8p]),
     "zkg16_prove_finish": (C.c_int, [ctxp, H, u64p, u64p, u64p, u8p, C.c_int, u64p, u8p]),
     "zkg16_combine_partials": (C.c_int, [u64p, u64p, u64p, u64p, u64p, u64p, u8p, C.c_int, u64p, u8p]),

@@ -85,7 +85,7 @@ void copy_options(zkg16_ctx *dst, const zkg16_ctx *src) {
     dst->opt_ntt_radix = src->opt_ntt_radix; dst->opt_ntt_xcd = src->opt_ntt_xcd; dst->opt_acc_debug = src->opt_acc_debug;
     dst->opt_sort_mode = src->opt_sort_mode; dst->opt_acc_pipeline = src->opt_acc_pipeline; dst->opt_fuse_pointwise = src->opt_fuse_pointwise;
     dst->opt_matrix_parts = src->opt_matrix_parts; dst->opt_g2_lazy = src->opt_g2_lazy; dst->opt_g1_inline = src->opt_g1_inline; dst->opt_fixed_base_bits = src->opt_fixed_base_bits;
-    dst->opt_collect_threads = src->opt_collect_threads;
+    dst->opt_collect_threads = src->opt_collect_threads; dst->opt_batch_max = src->opt_batch_max;
     dst->kernel_timing = src->kernel_timing; dst->kernel_timing_accumulate_only = src->kernel_timing_accumulate_only;
 }
 void create_streams(zkg16_ctx *ctx) {
@@ -104,6 +104,9 @@ void teardown(zkg16_ctx *ctx) {
     (void)hipStreamSynchronize(ctx->stream);
     (void)hipStreamSynchronize(ctx->wm_stream);
     if (ctx->extra_host) (void)hipHostFree(ctx->extra_host);
+    if (ctx->batch_host) (void)hipHostFree(ctx->batch_host);
+    ctx->batch_host = nullptr;
+    ctx->batch_host_bytes = 0;
     if (ctx->circuit_stage) (void)hipHostFree(ctx->circuit_stage);
     ctx->circuit_stage = nullptr;
     ctx->circuit_stage_bytes = 0;
@@ -368,6 +371,39 @@ double now_ms() {
     return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
 }
 
+// A throw between the first enqueue and the last collect (e.g. out of memory in a slot's bucket array) must not leave
+// kernels of this proof in flight: the next proof on the ctx rewrites extra_host and reuses the workspaces and slots.
+struct DrainOnError {
+    zkg16_ctx *c;
+    bool ok = false;
+    ~DrainOnError() {
+        if (ok) return;
+        (void)hipStreamSynchronize(c->stream);
+        (void)hipStreamSynchronize(c->wm_stream);
+        for (auto &sl : c->slots) {
+            if (sl.stream) (void)hipStreamSynchronize(sl.stream);
+            sl.active = sl.pending_reduce = sl.fixups_pending = sl.last_of_proof = false;
+        }
+    }
+};
+
+// [10..14] device time of the accumulation (+ fix-ups) of H, L, A, B1, B2, [15..19] of their reductions (zkg16_last_timings),
+// [20] / [21] host time of combining H's / the other four's window sums
+void record_msm_timings(zkg16_ctx *ctx, bool h_ran, bool z_ran) {
+    const int slot_of[5] = {1, 2, 3, 4, 0};     // H, L, A, B1, B2
+    for (int k = 0; k < 5; k++) {
+        MsmSlot &sl = ctx->slots[slot_of[k]];
+        const bool ran = k == 0 ? h_ran : z_ran;
+        float acc_ms = 0, red_ms = 0;
+        if (ran && sl.acc_start && hipEventElapsedTime(&acc_ms, sl.acc_start, sl.acc_done) != hipSuccess) { acc_ms = 0; (void)hipGetLastError(); }
+        if (ran && sl.red_start && hipEventElapsedTime(&red_ms, sl.red_start, sl.red_done) != hipSuccess) { red_ms = 0; (void)hipGetLastError(); }
+        ctx->timings[10 + k] = acc_ms;
+        ctx->timings[15 + k] = red_ms;
+    }
+    ctx->timings[20] = h_ran ? ctx->slots[1].collect_host_ms : 0;
+    ctx->timings[21] = z_ran ? ctx->slots[0].collect_host_ms + ctx->slots[2].collect_host_ms + ctx->slots[3].collect_host_ms + ctx->slots[4].collect_host_ms : 0;
+}
+
 // events of one proof, destroyed on every exit path
 struct EventSet {
     hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -394,21 +430,8 @@ void prove_device(zkg16_ctx *ctx, PkDev &pk, R1csDev &rc, WitnessDev &wit, const
     if (pk.n_h_total != N - 1) throw HipError{hipErrorInvalidValue, "prove: h_query length != N-1", __FILE__, __LINE__};
     EventSet evs;                         // 0-1: z-side sort (main stream), 2-4: witness map / h-side sort (aux stream)
     hipEvent_t *ev = evs.ev;
-    // A throw between the first enqueue and the last collect (e.g. out of memory in a slot's bucket array) must not leave
-    // kernels of this proof in flight: the next proof on the ctx rewrites extra_host and reuses the workspaces and slots.
-    struct DrainOnError {
-        zkg16_ctx *c;
-        bool ok = false;
-        ~DrainOnError() {
-            if (ok) return;
-            (void)hipStreamSynchronize(c->stream);
-            (void)hipStreamSynchronize(c->wm_stream);
-            for (auto &sl : c->slots) {
-                if (sl.stream) (void)hipStreamSynchronize(sl.stream);
-                sl.active = sl.pending_reduce = sl.fixups_pending = sl.last_of_proof = false;
-            }
-        }
-    } drain{ctx};
+    DrainOnError drain{ctx};
+    ctx->batch_terms_set = false;
     const double t0 = now_ms();
 
     // ---- main stream: the z-side scalar vector (z-slice || r, s, -rs), read in place by the digit kernel -> digits -> sort.
@@ -610,21 +633,8 @@ void prove_device(zkg16_ctx *ctx, PkDev &pk, R1csDev &rc, WitnessDev &wit, const
     // event pairs on the streams they ran on — the per-stage times upstream's spans ("Compute C" = H + L, "Compute A",
     // "Compute B in G1", "Compute B in G2": ark-groth16 prover.rs) correspond to.  Kernels of different MSMs overlap, so these
     // sum to more than the proof.
-    {
-        const int slot_of[5] = {1, 2, 3, 4, 0};     // H, L, A, B1, B2
-        for (int k = 0; k < 5; k++) {
-            MsmSlot &sl = ctx->slots[slot_of[k]];
-            const bool ran = k == 0 ? nh > 0 : z_side;
-            float acc_ms = 0, red_ms = 0;
-            if (ran && sl.acc_start && hipEventElapsedTime(&acc_ms, sl.acc_start, sl.acc_done) != hipSuccess) { acc_ms = 0; (void)hipGetLastError(); }
-            if (ran && sl.red_start && hipEventElapsedTime(&red_ms, sl.red_start, sl.red_done) != hipSuccess) { red_ms = 0; (void)hipGetLastError(); }
-            ctx->timings[10 + k] = acc_ms;
-            ctx->timings[15 + k] = red_ms;
-        }
-    }
     // [20] host Horner of H's window sums (after the last device event of the proof: exposed), [21] of the other four (overlap H's device work)
-    ctx->timings[20] = nh ? ctx->slots[1].collect_host_ms : 0;
-    ctx->timings[21] = z_side ? ctx->slots[0].collect_host_ms + ctx->slots[2].collect_host_ms + ctx->slots[3].collect_host_ms + ctx->slots[4].collect_host_ms : 0;
+    record_msm_timings(ctx, nh > 0, z_side);
     ctx->timings[0] = 0;
     ZK_HIP(hipEventElapsedTime(&ms, ev[2], ev[3]));
     ctx->timings[1] = ms;
@@ -667,6 +677,170 @@ void prove_tail(PkDev &pk, const Fr &r, const Fr &s, const Partials &p, uint64_t
 }
 
 void sum_partials(Partials &p, const uint64_t *partials, const uint8_t *partial_inf, int n_ranks);
+
+// ---- zkg16_prove_batch: K proofs of one circuit on one whole resident key in one device pass.  Each MSM has ONE plan over the K
+// scalar vectors (msm_plan_build with ScalarSrc::batch: one digit launch, one scatter; the K proofs' bucket sets are windows of it),
+// one accumulation, its fix-ups and one reduction chain; the witness map is one SpMV and seven transforms over all K assignments
+// (witness_map_run_batch), whose K h vectors the H plan reads in place.  The host then combines each proof's window sums and
+// finishes the proof on up to 8 threads (one with option collect_threads = 2) —
+// the same operations in the same order as prove_device + prove_tail, so proof k is byte-identical to zkg16_prove_resident's.
+void prove_batch_device(zkg16_ctx *ctx, PkDev &pk, R1csDev &rc, WitnessDev *const *wits, size_t K, const Fr *r, const Fr *s,
+                        uint64_t *proofs_out, uint8_t *inf_out) {
+    const size_t N = (size_t)1 << rc.log_n;
+    const size_t nh = N - 1;
+    if (pk.z_lo != 0 || !pk.full) throw HipError{hipErrorInvalidValue, "prove_batch: a shard key", __FILE__, __LINE__};
+    EventSet evs;                         // as prove_device: 0-1 z-side sort, 2-3 the witness map, 3-4 the h-side sort
+    hipEvent_t *ev = evs.ev;
+    DrainOnError drain{ctx};
+    const double t0 = now_ms();
+    // pinned, device-visible: the 3K extra scalars (r, s, -rs of every proof) and the K assignment pointers, read by the digit
+    // kernel in place; rewritten only by the next batch on this lane, which starts after this one has been collected
+    const size_t host_bytes = 3 * K * sizeof(Fr) + K * sizeof(void *);
+    if (ctx->batch_host_bytes < host_bytes) {
+        if (ctx->batch_host) (void)hipHostFree(ctx->batch_host);
+        ctx->batch_host = nullptr;
+        ctx->batch_host_bytes = 0;
+        ZK_HIP(hipHostMalloc(&ctx->batch_host, host_bytes, hipHostMallocDefault));
+        ctx->batch_host_bytes = host_bytes;
+    }
+    Fr *extra = reinterpret_cast<Fr *>(ctx->batch_host);
+    const Fr **vecs = reinterpret_cast<const Fr **>(extra + 3 * K);
+    for (size_t k = 0; k < K; k++) {
+        extra[3 * k] = pk.blinding ? r[k] : Fr::zero();
+        extra[3 * k + 1] = pk.blinding ? s[k] : Fr::zero();
+        extra[3 * k + 2] = pk.blinding ? fp_neg(fp_mul(r[k], s[k])) : Fr::zero();
+        vecs[k] = wits[k]->z.as<Fr>() + pk.z_lo;
+    }
+    const size_t nz = pk.z_hi - pk.z_lo;
+    MsmPlan plan_z, plan_h, plan_zb;
+    const bool b_sparse = pk.b_skipped * 20 > nz + 3;
+    ZK_HIP(hipEventRecord(ev[0], ctx->stream));
+    ctx->ws_z.last_tb = ctx->ws_zb.last_tb = ctx->ws_h.last_tb = 0;
+    MsmWorkspace &wsb = b_sparse ? ctx->ws_zb : ctx->ws_z;
+    const MsmPlan &planb = b_sparse ? plan_zb : plan_z;
+    {
+        ScalarSrc zsrc{nullptr, nz, extra, 3, true, nullptr};
+        zsrc.vecs = vecs;
+        zsrc.batch = (int)K;
+        const int tz = pk.tab_c_z;
+        msm_plan_build(ctx, ctx->ws_z, zsrc, plan_z, tz, tz != 0);
+        if (b_sparse) {
+            if ((ctx->opt_b_filter == 1 || (ctx->opt_b_filter == 0 && tz != 0)) && ctx->opt_sort_mode == 0) {
+                msm_plan_filter(ctx, ctx->ws_z, plan_z, pk.b_mask.as<uint8_t>(), ctx->ws_zb, plan_zb);
+            } else {
+                zsrc.mask = pk.b_mask.as<uint8_t>();
+                msm_plan_build(ctx, ctx->ws_zb, zsrc, plan_zb, tz, tz != 0);
+            }
+        }
+    }
+    ZK_HIP(hipEventRecord(ev[1], ctx->stream));
+    msm_g2_enqueue_acc(ctx, wsb, planb, pk.b2.as<G2AffineU>(), ctx->slots[0]);
+    msm_g1_enqueue_acc(ctx, ctx->ws_z, plan_z, pk.l.as<G1AffineU>(), ctx->slots[2]);
+    msm_g1_enqueue_acc(ctx, ctx->ws_z, plan_z, pk.a.as<G1AffineU>(), ctx->slots[3]);
+    msm_g1_enqueue_acc(ctx, wsb, planb, pk.b1.as<G1AffineU>(), ctx->slots[4]);
+
+    const bool wm_concurrent = ctx->opt_wm_concurrent != 0;
+    if (wm_concurrent) std::swap(ctx->stream, ctx->wm_stream);      // every launch helper targets ctx->stream
+    try {
+        ZK_HIP(hipEventRecord(ev[2], ctx->stream));
+        Fr *hv = nullptr;
+        if (K == 1) witness_map_run(ctx, rc, wits[0]->z.as<Fr>(), &hv);
+        else witness_map_run_batch(ctx, rc, vecs, (unsigned)K, &hv);      // vecs: the K assignments (z_lo = 0)
+        ZK_HIP(hipEventRecord(ev[3], ctx->stream));
+        ScalarSrc hsrc{hv + pk.h_lo, nh, nullptr, 0, true, nullptr};
+        hsrc.vec_stride = N;
+        hsrc.batch = (int)K;
+        msm_plan_build(ctx, ctx->ws_h, hsrc, plan_h, pk.tab_c_h ? pk.tab_c_h : ctx->opt_window_bits_h, pk.tab_c_h != 0);
+        ZK_HIP(hipEventRecord(ev[4], ctx->stream));
+    } catch (...) {
+        if (wm_concurrent) std::swap(ctx->stream, ctx->wm_stream);
+        throw;
+    }
+    if (wm_concurrent) std::swap(ctx->stream, ctx->wm_stream);
+    msm_g2_enqueue_reduce(ctx, ctx->slots[0]);
+    msm_g1_enqueue_reduce(ctx, ctx->slots[2]);
+    msm_g1_enqueue_reduce(ctx, ctx->slots[3]);
+    msm_g1_enqueue_reduce(ctx, ctx->slots[4]);
+    ZK_HIP(hipStreamWaitEvent(ctx->stream, ev[4], 0));
+    ctx->slots[1].last_of_proof = true;
+    msm_g1_enqueue(ctx, ctx->ws_h, plan_h, pk.h.as<G1AffineU>(), ctx->slots[1]);
+
+    // ---- host: the proofs are spread over threads; the z-side combination (+ s (A + alpha), r (B1 + beta)) runs while the
+    // device still works on H, then H's and the tail
+    std::vector<Partials> parts(K);
+    const int nth = ctx->opt_collect_threads == 0 ? 1 : (int)(K < 8 ? K : 8);
+    const int device = ctx->device;
+    auto run_pool = [&](const std::function<void(size_t)> &job) {
+        if (nth == 1) {                   // one proof, or option collect_threads = 2: on this thread
+            for (size_t k = 0; k < K; k++) job(k);
+            return;
+        }
+        std::atomic<size_t> next{0};
+        std::vector<std::exception_ptr> err(nth);
+        {
+            ThreadGroup tg;
+            for (int t = 0; t < nth; t++)
+                tg.run([&, t] {
+                    try {
+                        (void)hipSetDevice(device);
+                        for (size_t k; (k = next++) < K;) job(k);
+                    } catch (...) {
+                        err[t] = std::current_exception();
+                    }
+                });
+        }
+        for (auto &e : err)
+            if (e) std::rethrow_exception(e);
+    };
+    double tprev = now_ms();
+    for (int i : {0, 2, 3, 4}) msm_slot_wait(ctx->slots[i]);
+    ctx->timings[7] = (float)(now_ms() - tprev);
+    tprev = now_ms();
+    float host_z_ms = 0;
+    run_pool([&](size_t k) {
+        Partials &p = parts[k];
+        p.b2 = msm_g2_collect_part(ctx->slots[0], (int)k);
+        p.l = msm_g1_collect_part(ctx->slots[2], (int)k);
+        p.a = msm_g1_collect_part(ctx->slots[3], (int)k);
+        p.b1 = msm_g1_collect_part(ctx->slots[4], (int)k);
+        if (pk.full) {
+            G1XYZZ A = p.a;
+            xyzz_madd(A, pk.alpha_g1, false);
+            p.s_a = xyzz_mul(A, fp_from_mont(s[k]).l);
+            G1XYZZ B1 = p.b1;
+            xyzz_madd(B1, pk.beta_g1, false);
+            p.r_b1 = xyzz_mul(B1, fp_from_mont(r[k]).l);
+            p.have_early = true;
+        }
+    });
+    host_z_ms = (float)(now_ms() - tprev);
+    tprev = now_ms();
+    msm_slot_wait(ctx->slots[1]);
+    ctx->timings[3] = (float)(now_ms() - tprev);
+    tprev = now_ms();
+    run_pool([&](size_t k) {
+        parts[k].h = msm_g1_collect_part(ctx->slots[1], (int)k);
+        prove_tail(pk, r[k], s[k], parts[k], proofs_out + 48 * k, inf_out + 3 * k);
+    });
+    ctx->timings[8] = (float)(now_ms() - tprev);
+    for (auto &sl : ctx->slots) {
+        sl.active = false;
+        sl.collect_host_ms = 0;
+    }
+    float ms;
+    record_msm_timings(ctx, true, true);
+    ctx->timings[20] = 0;                 // H's combination is part of [8] (with the tails)
+    ctx->timings[21] = host_z_ms;         // the other four's, with s (A + alpha) and r (B1 + beta)
+    ctx->timings[0] = ctx->timings[4] = ctx->timings[5] = ctx->timings[6] = 0;
+    ZK_HIP(hipEventElapsedTime(&ms, ev[2], ev[3]));
+    ctx->timings[1] = ms;
+    ZK_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
+    ctx->timings[2] = ms;
+    ZK_HIP(hipEventElapsedTime(&ms, ev[3], ev[4]));
+    ctx->timings[2] += ms;
+    ctx->timings[9] = (float)(now_ms() - t0);
+    drain.ok = true;
+}
 
 Fr fr_from_abi(const uint64_t *l) {
     Fr v;
@@ -982,6 +1156,11 @@ int set_option_one(zkg16_ctx *ctx, const char *name, int64_t value) {
     if (!strcmp(name, "matrix_parts")) {       // zkg16_prove_matrix: slices of the host sponges the proof is fed in (0 = five growing slices; k = k equal ones; 1 = no overlap: assignment first)
         if (value < 0 || value > 8) return ZKG16_ERR_BAD_ARG;
         ctx->opt_matrix_parts = (int)value;
+        return ZKG16_OK;
+    }
+    if (!strcmp(name, "batch_max")) {          // zkg16_prove_batch: proofs per device pass, 0 = as many as fit (free HBM, 2^31 terms per list)
+        if (value < 0 || value > 65535) return ZKG16_ERR_BAD_ARG;
+        ctx->opt_batch_max = (int)value;
         return ZKG16_OK;
     }
     if (!strcmp(name, "reduce_chunk")) {
@@ -1540,6 +1719,82 @@ int zkg16_prove_resident(zkg16_ctx *ctx, uint64_t pk_handle, uint64_t r1cs_handl
     ZK_LANE_END(ctx)
 }
 
+// K proofs of one circuit on one whole resident key (prove_batch_device), in sub-batches that fit: every term list under 2^31
+// terms, at most 65,535 proofs (the grid.z / grid.y of the batched launches), and the workspaces that grow with K within 60 % of
+// the free HBM (option batch_max caps the sub-batch; no result changes).  The proofs are staged on the host and written out only
+// when every sub-batch has succeeded: a call that fails writes nothing.
+int zkg16_prove_batch(zkg16_ctx *ctx, uint64_t pk_handle, uint64_t r1cs_handle, const uint64_t *witness_handles, size_t k,
+                      const uint64_t *r, const uint64_t *s, uint64_t *proofs_out, uint8_t *inf_out) {
+    if (!witness_handles || !r || !s || !proofs_out || !inf_out || k == 0) return ZKG16_ERR_BAD_ARG;
+    ZK_LANE_BEGIN(ctx)
+    auto pk_ref = root->pks.get(pk_handle); PkDev *pk = pk_ref.get();
+    auto rc_ref = root->r1cs.get(r1cs_handle); R1csDev *rc = rc_ref.get();
+    if (!pk || !rc) return ZKG16_ERR_BAD_HANDLE;
+    std::vector<std::shared_ptr<WitnessDev>> wit_refs(k);
+    std::vector<WitnessDev *> wits(k);
+    for (size_t i = 0; i < k; i++) {
+        wit_refs[i] = root->wits.get(witness_handles[i]);
+        wits[i] = wit_refs[i].get();
+        if (!wits[i]) return ZKG16_ERR_BAD_HANDLE;
+    }
+    if (!pk->full) return ZKG16_ERR_UNSUPPORTED;                        // shards: zkg16_prove_partial / _group
+    const size_t N = (size_t)1 << rc->log_n;
+    if (pk->m_total != rc->num_variables || pk->num_instance != rc->num_instance || pk->n_h_total != N - 1) return ZKG16_ERR_BAD_ARG;
+    for (size_t i = 0; i < k; i++)
+        if (wits[i]->n != rc->num_variables) return ZKG16_ERR_BAD_ARG;
+    std::vector<Fr> rr(k), ss(k);
+    for (size_t i = 0; i < k; i++) {
+        rr[i] = fr_from_abi(r + 4 * i);
+        ss[i] = fr_from_abi(s + 4 * i);
+    }
+    // sub-batch size: terms per proof of the z and h lists, and what grows with K on the device — both lists' entries, codes and
+    // scatter intermediates (20 B a term; the B list may be a second z list), the witness map's four vectors, and the bucket arrays
+    // of the five MSMs with their reduction buffers (taken as 2x the G1 / G2 buckets)
+    const size_t m = rc->num_variables;
+    const size_t dz = msm_plan_digits(ctx, m + 3, pk->tab_c_z, pk->tab_c_z != 0), dh = msm_plan_digits(ctx, N - 1, pk->tab_c_h ? pk->tab_c_h : ctx->opt_window_bits_h, pk->tab_c_h != 0);
+    const size_t tz = (m + 3) * dz, th = (N - 1) * dh;
+    const size_t term_cap = ((size_t)1 << 31) - 1;
+    size_t kb = term_cap / (tz > th ? tz : th);
+    {
+        const size_t cz = pk->tab_c_z ? (size_t)pk->tab_c_z : msm_plan_bits(ctx, m + 3, 0, false);
+        const size_t ch = pk->tab_c_h ? (size_t)pk->tab_c_h : msm_plan_bits(ctx, N - 1, ctx->opt_window_bits_h, false);
+        const size_t bz = ((size_t)1 << (cz - 1)) * (pk->tab_c_z ? 1 : dz), bh = ((size_t)1 << (ch - 1)) * (pk->tab_c_h ? 1 : dh);
+        const size_t per_proof = (2 * tz + th) * 20 + 4 * N * sizeof(Fr) + 2 * (bz * (3 * sizeof(G1XYZZ) + sizeof(G2XYZZ)) + bh * sizeof(G1XYZZ));
+        size_t free_b = 0, total_b = 0;
+        ZK_HIP(hipMemGetInfo(&free_b, &total_b));
+        const size_t kmem = (size_t)(0.6 * (double)free_b) / per_proof;
+        if (kmem < kb) kb = kmem;
+    }
+    if (ctx->opt_batch_max > 0 && (size_t)ctx->opt_batch_max < kb) kb = (size_t)ctx->opt_batch_max;
+    if (kb > 65535) kb = 65535;
+    if (kb < 1) kb = 1;
+    std::vector<uint64_t> proofs(48 * k);
+    std::vector<uint8_t> infs(3 * k);
+    const double t0 = now_ms();
+    float acc[22] = {0};
+    uint64_t terms[3] = {0, 0, 0};
+    for (size_t off = 0; off < k; off += kb) {
+        const size_t n = k - off < kb ? k - off : kb;
+        prove_batch_device(ctx, *pk, *rc, wits.data() + off, n, rr.data() + off, ss.data() + off, proofs.data() + 48 * off, infs.data() + 3 * off);
+        for (int i = 0; i < 22; i++) acc[i] += ctx->timings[i];
+        if (kb >= k) break;               // one pass: zkg16_last_term_counts reads its lists as after a single proof
+        MsmWorkspace *w[3] = {&ctx->ws_z, &ctx->ws_zb, &ctx->ws_h};
+        for (int i = 0; i < 3; i++) {
+            uint32_t v = 0;
+            if (w[i]->last_tb && w[i]->offsets.p)
+                ZK_HIP(hipMemcpy(&v, w[i]->offsets.as<uint32_t>() + w[i]->last_tb, sizeof v, hipMemcpyDeviceToHost));
+            terms[i] += v;
+        }
+    }
+    for (int i = 0; i < 22; i++) ctx->timings[i] = acc[i];
+    ctx->timings[9] = (float)(now_ms() - t0);
+    for (int i = 0; i < 3; i++) ctx->batch_terms[i] = terms[i];
+    ctx->batch_terms_set = kb < k;
+    memcpy(proofs_out, proofs.data(), proofs.size() * sizeof(uint64_t));
+    memcpy(inf_out, infs.data(), infs.size());
+    ZK_LANE_END(ctx)
+}
+
 // One MatrixCircuit request on matrices that are already resident: what the reference times as `proving_time`
 // (matrix_proof.rs:138-145: Groth16::prove re-synthesises the circuit, then proves) with the per-request part of the synthesis —
 // the assignment — produced WHILE the proof runs.  The three native sponges run on three host threads (sequential by
@@ -1858,6 +2113,10 @@ int zkg16_last_term_counts(zkg16_ctx *ctx, uint64_t counts[3]) {
     zkg16_ctx *root = ctx;
     ctx = lane_of(root, last);
     ZK_API_BEGIN(ctx)
+    if (ctx->batch_terms_set) {           // a batch: the lists of all its sub-batches
+        for (int i = 0; i < 3; i++) counts[i] = ctx->batch_terms[i];
+        return ZKG16_OK;
+    }
     ZK_HIP(hipDeviceSynchronize());
     MsmWorkspace *w[3] = {&ctx->ws_z, &ctx->ws_zb, &ctx->ws_h};
     for (int i = 0; i < 3; i++) {

@@ -45,7 +45,11 @@ struct SortPass {
     uint32_t nblk;               // workgroups per window = ceil(n / SORT_BCH)
     uint32_t nb;                 // buckets per window (the last pass writes global bucket ids)
     int nwin, shift, bits, pass;
+    const uint32_t *win_base;    // last pass of a list with many windows (a batch): exclusive prefix of win_total, else null
 };
+// windows above which the last pass reads its window bases from one prefix (sort_window_prefix_kernel) instead of summing the
+// totals of the windows before it in every block — a plain-key batch has K x W windows
+static constexpr int SORT_PREFIX_WINDOWS = 32;
 
 // lanes of the wave holding the same `dg` as this lane (only among `valid` lanes): one ballot per digit bit
 __device__ __forceinline__ uint64_t match_digit(uint32_t dg, bool valid, int bits) {
@@ -196,6 +200,21 @@ __global__ void __launch_bounds__(64) sort_window_total_kernel(SortPass a) {
 
 // exclusive scan of one value per thread over the 256 threads of the block (scratch: SORT_WAVES words of LDS); returns the
 // exclusive prefix, *total = block total
+__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t *scratch, uint32_t *total);
+// one block: prefix[w] = sum of tot[x] for x < w, prefix[nwin] = the whole list
+__global__ void __launch_bounds__(64 * SORT_WAVES) sort_window_prefix_kernel(const uint32_t *tot, uint32_t nwin, uint32_t *prefix) {
+    __shared__ uint32_t scratch[SORT_WAVES];
+    uint32_t carry = 0;
+    for (uint32_t w0 = 0; w0 < nwin; w0 += 64 * SORT_WAVES) {
+        const uint32_t w = w0 + threadIdx.x;
+        const uint32_t v = w < nwin ? tot[w] : 0u;
+        uint32_t sum;
+        const uint32_t ex = block_excl_scan(v, scratch, &sum);
+        if (w < nwin) prefix[w] = carry + ex;
+        carry += sum;
+    }
+    if (threadIdx.x == 0) prefix[nwin] = carry;
+}
 __device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t *scratch, uint32_t *total) {
     const uint32_t lane = threadIdx.x & 63u, slot = threadIdx.x >> 6;
     uint32_t inc = v;
@@ -234,7 +253,8 @@ __global__ void __launch_bounds__(64 * SORT_WAVES) sort_scatter_kernel(SortPass 
     __syncthreads();
     // window base: the last pass packs the windows (sum of the totals of the windows before), the others keep them apart (w * n)
     size_t win_base = LAST ? 0 : (size_t)w * a.n;
-    if (LAST)
+    if (LAST && a.win_base) win_base = a.win_base[w];
+    else if (LAST)
         for (uint32_t x = 0; x < w; x++) win_base += a.win_total[x];
     // digits are handled `per` at a time per thread, in digit order, so one block scan gives the local start of every digit
     // (from the block's own counts) and a second one the global start (from the totals of the whole window)
@@ -285,7 +305,8 @@ static size_t sort_lds_bytes(int bits, bool scatter) {
 
 // codes: [window][n] digit codes -> entries sorted by (window, bucket), compact over the windows
 // returns the device array of per-window entry counts (nwin values; their sum is the length of the list)
-const uint32_t *msm_bucket_sort(zkg16_ctx *ctx, MsmWorkspace &ws, const uint32_t *codes, size_t n, int nwin, int c, uint2 *entries) {
+// *sum_windows: how many values at the returned pointer add up to the list's length (nwin, or 1 = the total, for many windows)
+const uint32_t *msm_bucket_sort(zkg16_ctx *ctx, MsmWorkspace &ws, const uint32_t *codes, size_t n, int nwin, int c, uint2 *entries, int *sum_windows) {
     if (n == 0) return nullptr;
     const int bbits = c - 1;                                   // bucket bits per window
     const int npass = bbits <= 2 * SORT_MAX_BITS ? 2 : 3;      // 2 x <= 10 bits; above 20 bucket bits 3 x <= 8
@@ -295,13 +316,15 @@ const uint32_t *msm_bucket_sort(zkg16_ctx *ctx, MsmWorkspace &ws, const uint32_t
     const uint32_t nblk = (uint32_t)((n + SORT_BCH - 1) / SORT_BCH);
     const size_t ndig_max = (size_t)1 << bits[0];
     const size_t counts_words = (size_t)nwin * ndig_max * nblk;
-    const size_t small = (size_t)nwin * ndig_max + 3 * (size_t)nwin + 16;
+    const bool prefix = nwin > SORT_PREFIX_WINDOWS;
+    const size_t small = (size_t)nwin * ndig_max + 3 * (size_t)nwin + 16 + (prefix ? (size_t)nwin + 1 : 0);
     ws.sort_temp.ensure((counts_words + small) * sizeof(uint32_t));
     ws.keys.ensure((size_t)nwin * n * sizeof(uint2));           // intermediate entry list (window w at [w * n, ...))
     if (npass == 3) ws.stage.ensure((size_t)nwin * n * sizeof(uint2));      // second intermediate list
     uint32_t *counts = ws.sort_temp.as<uint32_t>();
     uint32_t *dig_total = counts + counts_words;
     uint32_t *win_tot = dig_total + (size_t)nwin * ndig_max;     // [pass][window]
+    uint32_t *win_pre = win_tot + 3 * (size_t)nwin;              // [window + 1] (prefix)
     SortPass a{};
     a.codes = codes;
     a.counts = counts;
@@ -326,13 +349,18 @@ const uint32_t *msm_bucket_sort(zkg16_ctx *ctx, MsmWorkspace &ws, const uint32_t
         else hipLaunchKernelGGL(sort_count_kernel<false>, grid, block, lds_c, ctx->stream, a);
         hipLaunchKernelGGL(sort_scan_kernel, dim3(1u << bits[p], (unsigned)nwin), dim3(64 * scan_waves), 0, ctx->stream, a);
         hipLaunchKernelGGL(sort_window_total_kernel, dim3((unsigned)nwin), dim3(64), 0, ctx->stream, a);
+        if (last && prefix) {
+            hipLaunchKernelGGL(sort_window_prefix_kernel, dim3(1), dim3(64 * SORT_WAVES), 0, ctx->stream, a.win_total, (uint32_t)nwin, win_pre);
+            a.win_base = win_pre;
+        }
         if (first) hipLaunchKernelGGL((sort_scatter_kernel<true, false>), grid, block, lds_s, ctx->stream, a);
         else if (last) hipLaunchKernelGGL((sort_scatter_kernel<false, true>), grid, block, lds_s, ctx->stream, a);
         else hipLaunchKernelGGL((sort_scatter_kernel<false, false>), grid, block, lds_s, ctx->stream, a);
         shift += bits[p];
     }
     ZK_HIP(hipGetLastError());
-    return win_tot + (size_t)(npass - 1) * nwin;
+    if (sum_windows) *sum_windows = prefix ? 1 : nwin;
+    return prefix ? win_pre + nwin : win_tot + (size_t)(npass - 1) * nwin;
 }
 
 }  // namespace zk

@@ -223,6 +223,7 @@ struct MsmSlot {            // one in-flight MSM: written by the accumulate half
     int bit_sliced = 0;             // > 0: the bit-sliced reduction ran with this many weight bits (two_level_k = its chunk size)
     void *red_buckets = nullptr;
     size_t red_nb = 0;
+    int batch = 1;                  // vectors of a batch plan (zkg16_prove_batch): nwin / batch windows each
 };
 
 struct MsmWorkspace {       // grown on demand, reused across proofs
@@ -266,6 +267,11 @@ struct zkg16_ctx {
     void *stage_host[2] = {nullptr, nullptr};         // pinned staging ring of upload_h2d (api.hip)
     hipEvent_t stage_done[2] = {nullptr, nullptr};
     zk::DevBuf poly[4];                               // a, b, c, tmp vectors of the witness map
+    // zkg16_prove_batch: pinned staging of the 3K extra scalars and the K assignment pointers (the K h vectors live in poly)
+    void *batch_host = nullptr;
+    size_t batch_host_bytes = 0;
+    bool batch_terms_set = false;                     // the last proving call was a batch: its term counts (summed over sub-batches)
+    uint64_t batch_terms[3] = {0, 0, 0};
     float timings[24] = {0};
     bool kernel_timing = false;
     bool kernel_timing_accumulate_only = false;       // zkg16_kernel_timing(ctx, 2): only the bucket-accumulation launches
@@ -296,6 +302,7 @@ struct zkg16_ctx {
     int opt_g1_inline = 1;                            // G1 accumulation (plain loop): every field product inlined (ec.cuh: xyzz_madd_inline); 0: products as calls
     int opt_matrix_parts = 0;                         // zkg16_prove_matrix: gadget slices the assignment arrives in (0 = five growing slices, k = k equal ones, 1 = no overlap)
     int opt_fuse_pointwise = 1;                       // (ab - c)/Z on the load of the seventh transform (0: its own pass)
+    int opt_batch_max = 0;                            // zkg16_prove_batch: proofs per device pass (0 = as many as fit)
     int num_cus = 256;
     bool lds_attr_fixup[2] = {false, false}, lds_attr_ntt = false;      // hipFuncSetAttribute(max dynamic LDS) done on this device
     zk::FixedBaseCache fb_g1, fb_g2;
@@ -325,6 +332,8 @@ void kernel_timer_resolve(zkg16_ctx *ctx);
 // point-wise stage on the input, src[i] <- (src[i] * b[i] - c[i]) * zinv (the witness map's (ab - c)/Z).
 struct NttPointwise { const Fr *b, *c; Fr zinv; };
 Fr *ntt_run(zkg16_ctx *ctx, Fr *src, Fr *dst, int log_n, bool inverse, bool coset, const NttPointwise *pw = nullptr);
+// nvec transforms at once: vector v at src / dst (and pw->b / pw->c) + v * vec_stride, every pass one launch over all of them
+Fr *ntt_run_batch(zkg16_ctx *ctx, Fr *src, Fr *dst, int log_n, bool inverse, bool coset, const NttPointwise *pw, unsigned nvec, size_t vec_stride);
 NttTables *ntt_get_tables(zkg16_ctx *ctx, int log_n);
 // a rank's share of a two-pass transform (split witness map): tiles {lo0, n0, lo1, n1} of the column and of the row pass, and
 // what runs between the two passes (the exchange); see ntt_run_share in ntt.hip
@@ -337,10 +346,12 @@ bool ntt_two_pass_shape(int log_n, int ntt_mode, int *log_n1, int *log_n2, int *
 
 // rows: null = every row of the domain; else lane t of matrix i computes row list[i][t], t < n[i] (a rank's share, group.hip)
 struct SpmvRows { const uint32_t *list[3]; size_t n[3]; };
-void spmv_run(zkg16_ctx *ctx, R1csDev &m, const Fr *z, Fr *a, Fr *b, Fr *c, const SpmvRows *rows = nullptr);
+void spmv_run(zkg16_ctx *ctx, R1csDev &m, const Fr *z, Fr *a, Fr *b, Fr *c, const SpmvRows *rows = nullptr, const Fr *const *zs = nullptr,
+              unsigned nvec = 1);
 void pointwise_h_run(zkg16_ctx *ctx, Fr *ab_a, const Fr *b, const Fr *c, const Fr &zinv, size_t n);
 void fr_from_mont_run(zkg16_ctx *ctx, const Fr *in, Fr *out, size_t n);
 void witness_map_run(zkg16_ctx *ctx, R1csDev &m, const Fr *z, Fr **h_out);
+void witness_map_run_batch(zkg16_ctx *ctx, R1csDev &m, const Fr *const *zs, unsigned nvec, Fr **h_out);
 
 // Scalar-vector side of Pippenger (shared by every MSM over the same scalars).
 struct MsmPlan {
@@ -351,13 +362,19 @@ struct MsmPlan {
     size_t nb = 0;           // buckets per window = 2^(c-1)
     size_t total_entries = 0;            // upper bound n * windows (the exact count lives on the device)
     uint32_t lanes_g1 = 0, lanes_g2 = 0; // lanes of one resident round of accumulation waves (2 / 1 waves per SIMD)
+    int batch = 1;           // scalar vectors (zkg16_prove_batch): nwin = batch x the windows of one
 };
 void msm_plan_build(zkg16_ctx *ctx, MsmWorkspace &ws, const Fr *scalars_canonical, size_t n, MsmPlan &plan, int window_bits = 0);
+int msm_plan_bits(zkg16_ctx *ctx, size_t n, int window_bits, bool tabled);          // the c msm_plan_build picks
+size_t msm_plan_digits(zkg16_ctx *ctx, size_t n, int window_bits, bool tabled);     // and 254 / c + 1
 // The scalar vector where it lives: n_main elements at `main` then n_extra at `extra`; `mont` = arkworks' Montgomery form
 // (converted inside the digit kernel); mask[i] != 0 zeroes scalar i (B-query density filter).  All device pointers.
 // part / want_part (streamed assignments, witness.hip): when part != nullptr only the scalars i with part[i] == want_part take
 // part in this plan (the others count as zero: they may not even be computed yet).
-struct ScalarSrc { const Fr *main; size_t n_main; const Fr *extra; size_t n_extra; bool mont; const uint8_t *mask; const uint8_t *part = nullptr; int want_part = 0; };
+// batch > 1: that many vectors, vector v's main part at vecs[v] (a device-visible pointer table) or, without one, at
+// main + v * vec_stride, its extras at extra + v * n_extra.
+struct ScalarSrc { const Fr *main; size_t n_main; const Fr *extra; size_t n_extra; bool mont; const uint8_t *mask; const uint8_t *part = nullptr; int want_part = 0;
+                   const Fr *const *vecs = nullptr; size_t vec_stride = 0; int batch = 1; };
 void msm_plan_build(zkg16_ctx *ctx, MsmWorkspace &ws, const ScalarSrc &src, MsmPlan &plan, int window_bits = 0, bool tabled = false);
 // window tables of a resident key: bases[n] -> new buffer [254 / c + 1][n], level w = 2^(c w) * base (msm.hip)
 DevBuf msm_tables_build_g1(zkg16_ctx *ctx, const DevBuf &bases, size_t n, int c);
@@ -366,7 +383,9 @@ DevBuf msm_tables_build_g2(zkg16_ctx *ctx, const DevBuf &bases, size_t n, int c)
 void msm_plan_filter(zkg16_ctx *ctx, const MsmWorkspace &ws_src, const MsmPlan &plan_src, const uint8_t *mask, MsmWorkspace &ws_dst, MsmPlan &plan_dst);
 void msm_sort_keys(zkg16_ctx *ctx, MsmWorkspace &ws, size_t count, unsigned key_bits);   // sort.hip (rocPRIM radix sort; option sort_mode 1)
 // bucket_sort.hip: hand-written wave-ballot counting scatter (default); returns the per-window entry counts (device)
-const uint32_t *msm_bucket_sort(zkg16_ctx *ctx, MsmWorkspace &ws, const uint32_t *codes, size_t n, int nwin, int c, uint2 *entries);
+// (*sum_windows, nullable: how many values at the returned pointer add up to the list's length — nwin, or 1 for lists of many windows)
+const uint32_t *msm_bucket_sort(zkg16_ctx *ctx, MsmWorkspace &ws, const uint32_t *codes, size_t n, int nwin, int c, uint2 *entries,
+                                int *sum_windows = nullptr);
 void radix_sort_hi32(zkg16_ctx *ctx, const uint64_t *in, uint64_t *out, size_t count, unsigned key_bits, DevBuf &temp, const char *timer_name);
 // setup.hip: Groth16 key generation from a known trapdoor (discrete logs on device, then fixed-base batches)
 struct SetupOut {
@@ -389,6 +408,10 @@ void msm_g1_enqueue(zkg16_ctx *ctx, MsmWorkspace &ws, const MsmPlan &plan, const
 void msm_g2_enqueue(zkg16_ctx *ctx, MsmWorkspace &ws, const MsmPlan &plan, const G2AffineU *bases, MsmSlot &slot);
 G1XYZZ msm_g1_collect(zkg16_ctx *ctx, MsmSlot &slot);
 G2XYZZ msm_g2_collect(zkg16_ctx *ctx, MsmSlot &slot);
+// a batch plan's slot: msm_slot_wait once, then vector v's value (const: threads may combine different vectors at once)
+void msm_slot_wait(MsmSlot &slot);
+G1XYZZ msm_g1_collect_part(const MsmSlot &slot, int v);
+G2XYZZ msm_g2_collect_part(const MsmSlot &slot, int v);
 G1XYZZ msm_g1_exec(zkg16_ctx *ctx, MsmWorkspace &ws, const MsmPlan &plan, const G1AffineU *bases, const char *tag);
 G2XYZZ msm_g2_exec(zkg16_ctx *ctx, MsmWorkspace &ws, const MsmPlan &plan, const G2AffineU *bases, const char *tag);
 // saturated (arkworks) affine points -> the unsaturated device form, on the ctx stream

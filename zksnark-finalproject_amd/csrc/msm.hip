@@ -57,6 +57,8 @@ __device__ __forceinline__ void stv(T *p, const T &v) {
 // terms of a proof), in arkworks' Montgomery form when `mont` (the conversion `into_bigint()` of prover.rs is done here, in
 // registers — round 1 ran a separate fr_from_mont pass plus a staging copy per scalar vector), zeroed where mask[i] != 0
 // (terms whose base is infinity in both B queries: b_density_mask_kernel).
+// A batch (zkg16_prove_batch): grid.y = vector v of the batch, whose main scalars are at vecs[v] (a device-visible pointer table)
+// or at scalars + v * vec_stride elements, its extras at extra + v * (n - n_main); its digits go to windows v * nwin + w.
 struct DigitSrc {
     const uint32_t *scalars, *extra;
     size_t n_main, n;
@@ -64,14 +66,20 @@ struct DigitSrc {
     int mont;
     const uint8_t *part;       // streamed assignments: only scalars with part[i] == want take part (the others may not exist yet)
     int want;
+    const uint32_t *const *vecs;
+    size_t vec_stride;
 };
 __global__ void __launch_bounds__(256) msm_digits_kernel(DigitSrc src, int c, int nwin, size_t nb, uint64_t *keys, uint32_t *codes, uint32_t invalid_bucket) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const size_t n = src.n;
     if (i >= n) return;
+    const unsigned v = blockIdx.y;
+    const uint32_t *mainv = src.vecs ? src.vecs[v] : src.scalars + (size_t)v * src.vec_stride * 8;
+    const uint32_t *extrav = src.extra + (size_t)v * (n - src.n_main) * 8;
+    const size_t w0 = (size_t)v * nwin;
     uint32_t s[9];
     {
-        const uint4 *q = reinterpret_cast<const uint4 *>(i < src.n_main ? src.scalars + 8 * i : src.extra + 8 * (i - src.n_main));
+        const uint4 *q = reinterpret_cast<const uint4 *>(i < src.n_main ? mainv + 8 * i : extrav + 8 * (i - src.n_main));
         uint4 lo = q[0], hi = q[1];
         if (src.mask && src.mask[i]) lo = hi = make_uint4(0, 0, 0, 0);
         if (src.part && (int)src.part[i] != src.want) lo = hi = make_uint4(0, 0, 0, 0);
@@ -121,10 +129,10 @@ __global__ void __launch_bounds__(256) msm_digits_kernel(DigitSrc src, int c, in
             key = 1u + (((v - 1u) << 1) | flipbit);
         }
         if (codes) {      // hand-written bucket scatter (bucket_sort.hip): (|d| - 1) << 1 | negate per (window, scalar), ~0 for digit 0
-            codes[(size_t)w * n + i] = key - 1u;
+            codes[(w0 + w) * n + i] = key - 1u;
         } else {          // rocPRIM path (sort.hip): 64-bit keys
-            const uint32_t g = key ? (uint32_t)((size_t)w * nb + ((key - 1u) >> 1)) : invalid_bucket;
-            keys[(size_t)w * n + i] = ((uint64_t)g << 32) | (uint64_t)(((uint32_t)i << 1) | ((key - 1u) & 1u));
+            const uint32_t g = key ? (uint32_t)((w0 + w) * nb + ((key - 1u) >> 1)) : invalid_bucket;
+            keys[(w0 + w) * n + i] = ((uint64_t)g << 32) | (uint64_t)(((uint32_t)i << 1) | ((key - 1u) & 1u));
         }
     }
 }
@@ -744,6 +752,12 @@ static int pick_window_bits(zkg16_ctx *ctx, size_t n) {
     return c;
 }
 
+// the window bits and digits per scalar msm_plan_build picks for these arguments
+int msm_plan_bits(zkg16_ctx *ctx, size_t n, int window_bits, bool tabled) {
+    return (window_bits >= 2 && window_bits <= (tabled ? 24 : 20)) ? window_bits : pick_window_bits(ctx, n);
+}
+size_t msm_plan_digits(zkg16_ctx *ctx, size_t n, int window_bits, bool tabled) { return 254 / msm_plan_bits(ctx, n, window_bits, tabled) + 1; }
+
 void msm_plan_build(zkg16_ctx *ctx, MsmWorkspace &ws, const Fr *scalars_canonical, size_t n, MsmPlan &plan, int window_bits) {
     const ScalarSrc src{scalars_canonical, n, nullptr, 0, false, nullptr};
     msm_plan_build(ctx, ws, src, plan, window_bits);
@@ -752,41 +766,49 @@ void msm_plan_build(zkg16_ctx *ctx, MsmWorkspace &ws, const Fr *scalars_canonica
 // is an ordinary term (base w * n + i, digit) of ONE bucket set — the digit codes [w][i] already are that flat term list, and
 // the scatter sees a single window of n * nwin_digits terms.  Fewer additions (larger c at the same bucket count) and one
 // bucket reduction instead of one per window.
+// A batch of src.batch scalar vectors (zkg16_prove_batch) is one plan over batch x the windows: vector v's digits are the windows
+// v * nwin_digits + w of a plain key (term position i, as in window w) or window v of a tabled one (position w * n + i, as in the
+// single set).  The scatter, the accumulation and its fix-ups see nothing but more windows; the reduction leaves one result per
+// window, and the host combines each vector's own (msm_g?_collect_part).
 void msm_plan_build(zkg16_ctx *ctx, MsmWorkspace &ws, const ScalarSrc &src, MsmPlan &plan, int window_bits, bool tabled) {
     const size_t n = src.n_main + src.n_extra;
+    const int nv = src.batch > 1 ? src.batch : 1;
     plan.n = n;
+    plan.batch = nv;
     plan.tabled = tabled;
     plan.c = (window_bits >= 2 && window_bits <= (tabled ? 24 : 20)) ? window_bits : pick_window_bits(ctx, n);
     plan.nwin_digits = 254 / plan.c + 1;      // magnitudes are < 2^254 after the r - s fold (msm_digits_kernel)
-    plan.nwin = tabled ? 1 : plan.nwin_digits;
+    plan.nwin = nv * (tabled ? 1 : plan.nwin_digits);
     plan.nb = (size_t)1 << (plan.c - 1);
     plan.total_entries = 0;
     ws.last_tb = 0;
     if (n == 0) return;
     const size_t tb = plan.nb * plan.nwin;
     ws.last_tb = tb;
-    const size_t tot = n * (size_t)plan.nwin_digits;
+    const size_t tot = (size_t)nv * n * (size_t)plan.nwin_digits;
     if (tot >= ((size_t)1 << 31)) throw HipError{hipErrorInvalidValue, "msm: more than 2^31 (scalar, window) terms", __FILE__, __LINE__};
     ws.entries.ensure(tot * sizeof(uint64_t));
     ws.offsets.ensure((tb + 1) * sizeof(uint32_t));
     const bool own_sort = ctx->opt_sort_mode == 0 || tabled;
     const DigitSrc d{reinterpret_cast<const uint32_t *>(src.main), reinterpret_cast<const uint32_t *>(src.extra), src.n_main, n, src.mask,
-                     src.mont ? 1 : 0, src.part, src.want_part};
+                     src.mont ? 1 : 0, src.part, src.want_part, reinterpret_cast<const uint32_t *const *>(src.vecs), src.vec_stride};
+    const dim3 dgrid((unsigned)((n + 255) / 256), (unsigned)nv);
     const uint32_t *win_total = nullptr;
+    int sum_windows = plan.nwin;
     if (own_sort) {
         ws.codes.ensure(tot * sizeof(uint32_t));
         {
-            ScopedKernelTimer kt(ctx, "msm_digits_kernel", (double)n, ctx->stream);
-            hipLaunchKernelGGL(msm_digits_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d, plan.c, plan.nwin_digits, plan.nb,
+            ScopedKernelTimer kt(ctx, "msm_digits_kernel", (double)n * nv, ctx->stream);
+            hipLaunchKernelGGL(msm_digits_kernel, dgrid, dim3(256), 0, ctx->stream, d, plan.c, plan.nwin_digits, plan.nb,
                                (uint64_t *)nullptr, ws.codes.as<uint32_t>(), (uint32_t)tb);
         }
-        if (tabled) win_total = msm_bucket_sort(ctx, ws, ws.codes.as<uint32_t>(), tot, 1, plan.c, ws.entries.as<uint2>());
-        else win_total = msm_bucket_sort(ctx, ws, ws.codes.as<uint32_t>(), n, plan.nwin, plan.c, ws.entries.as<uint2>());
+        if (tabled) win_total = msm_bucket_sort(ctx, ws, ws.codes.as<uint32_t>(), n * (size_t)plan.nwin_digits, nv, plan.c, ws.entries.as<uint2>(), &sum_windows);
+        else win_total = msm_bucket_sort(ctx, ws, ws.codes.as<uint32_t>(), n, plan.nwin, plan.c, ws.entries.as<uint2>(), &sum_windows);
     } else {
         ws.keys.ensure(tot * sizeof(uint64_t));
         {
-            ScopedKernelTimer kt(ctx, "msm_digits_kernel", (double)n, ctx->stream);
-            hipLaunchKernelGGL(msm_digits_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d, plan.c, plan.nwin, plan.nb,
+            ScopedKernelTimer kt(ctx, "msm_digits_kernel", (double)n * nv, ctx->stream);
+            hipLaunchKernelGGL(msm_digits_kernel, dgrid, dim3(256), 0, ctx->stream, d, plan.c, plan.nwin_digits, plan.nb,
                                ws.keys.as<uint64_t>(), (uint32_t *)nullptr, (uint32_t)tb);
         }
         unsigned key_bits = 1;
@@ -796,7 +818,7 @@ void msm_plan_build(zkg16_ctx *ctx, MsmWorkspace &ws, const ScalarSrc &src, MsmP
     {
         ScopedKernelTimer kt(ctx, "msm_offsets_kernel", (double)tb, ctx->stream);
         hipLaunchKernelGGL(msm_offsets_kernel, dim3((unsigned)((tb + 1 + 255) / 256)), dim3(256), 0, ctx->stream,
-                           ws.entries.as<uint2>(), tot, win_total, plan.nwin, ws.offsets.as<uint32_t>(), tb);
+                           ws.entries.as<uint2>(), tot, win_total, sum_windows, ws.offsets.as<uint32_t>(), tb);
     }
     ZK_HIP(hipGetLastError());
     // the exact entry count stays on the device (offsets[tb]); the accumulation grids are one resident round of waves and
@@ -1014,6 +1036,7 @@ static void msm_enqueue_acc(zkg16_ctx *ctx, MsmWorkspace &ws, const MsmPlan &pla
     }
     slot.nwin = plan.nwin;
     slot.c = plan.c;
+    slot.batch = plan.batch;
     if (plan.n == 0) return;
     const size_t tb = plan.nb * plan.nwin;
     const size_t psz = sizeof(XYZZ<F>);
@@ -1120,7 +1143,12 @@ static void msm_enqueue_reduce(zkg16_ctx *ctx, MsmSlot &slot) {
     const bool pow2 = (plan.nb & (plan.nb - 1)) == 0;
     // (the proof's LAST reduction is an exposed tail whatever its size: bit-sliced up to 2^22 buckets — 128x128's H, 2^21: 3.0 -> 1.6 ms)
     const size_t one_set_max = slot.last_of_proof ? ((size_t)1 << 22) : ((size_t)1 << 19);
-    const bool bs_auto = ctx->opt_reduce_mode == 3 && (plan.nwin == 1 ? plan.nb >= 256 && plan.nb <= one_set_max : plan.nb >= 4096 && tb <= ((size_t)1 << 19));
+    // a batch (slot.batch vectors, nwin / batch windows each): the same rule per vector, whatever the batch holds in all (the chunk
+    // size below grows with the rounds the sets need).  Measured against the work-efficient form at K = 8 .. 64
+    // (profiles/batch_reduce_modes_r7.txt): plain keys 8x8 1.14 vs 1.35 ms/proof and 32x32 9.55 vs 10.43 at K = 64, tabled keys equal
+    const int nw1 = plan.nwin / (slot.batch > 1 ? slot.batch : 1);
+    const size_t tb1 = plan.nb * (size_t)nw1;
+    const bool bs_auto = ctx->opt_reduce_mode == 3 && (nw1 == 1 ? plan.nb >= 256 && plan.nb <= one_set_max : plan.nb >= 4096 && tb1 <= ((size_t)1 << 19));
     if (pow2 && plan.nb >= 8 && (ctx->opt_reduce_mode == 5 || bs_auto)) {
         auto log2z = [](size_t v) { int l = 0; while (((size_t)1 << l) < v) l++; return l; };
         // chunk size by depth in dependent additions: 2K - 1 in chunk_local, the first tree level in rounds of the resident lanes (a G2
@@ -1216,13 +1244,9 @@ static void msm_enqueue(zkg16_ctx *ctx, MsmWorkspace &ws, const MsmPlan &plan, c
     msm_enqueue_reduce<F>(ctx, slot);
 }
 
+// host Horner over the windows [w0, w0 + nw) of a reduced slot: sum_w 2^(c (w - w0)) W_w
 template <class FS>
-static XYZZ<FS> msm_collect(zkg16_ctx *ctx, MsmSlot &slot) {
-    (void)ctx;
-    if (!slot.active) return XYZZ<FS>::inf();
-    ZK_HIP(hipEventSynchronize(slot.red_done));
-    const auto host_t0 = std::chrono::steady_clock::now();
-    struct Lap { const std::chrono::steady_clock::time_point t0; MsmSlot &s; ~Lap() { s.collect_host_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count(); } } lap{host_t0, slot};
+static XYZZ<FS> msm_combine(const MsmSlot &slot, int w0, int nw) {
     const XYZZ<FS> *wsum = reinterpret_cast<const XYZZ<FS> *>(slot.wsums_host);
     auto window = [&](int w) {
         if (slot.bit_sliced) {          // K (2^bits S_top + sum_t 2^t T_t) - M   (msm_bit_pairs_kernel)
@@ -1242,14 +1266,33 @@ static XYZZ<FS> msm_collect(zkg16_ctx *ctx, MsmSlot &slot) {
         xyzz_add(v, xyzz_neg(wsum[slot.nwin + w]));
         return v;
     };
-    // host Horner over windows: sum_w 2^(c*w) W_w
-    XYZZ<FS> total = window(slot.nwin - 1);
-    for (int w = slot.nwin - 2; w >= 0; w--) {
+    XYZZ<FS> total = window(w0 + nw - 1);
+    for (int w = w0 + nw - 2; w >= w0; w--) {
         for (int q = 0; q < slot.c; q++) total = xyzz_dbl(total);
         xyzz_add(total, window(w));
     }
+    return total;
+}
+template <class FS>
+static XYZZ<FS> msm_collect(zkg16_ctx *ctx, MsmSlot &slot) {
+    (void)ctx;
+    if (!slot.active) return XYZZ<FS>::inf();
+    ZK_HIP(hipEventSynchronize(slot.red_done));
+    const auto host_t0 = std::chrono::steady_clock::now();
+    struct Lap { const std::chrono::steady_clock::time_point t0; MsmSlot &s; ~Lap() { s.collect_host_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count(); } } lap{host_t0, slot};
+    const XYZZ<FS> total = msm_combine<FS>(slot, 0, slot.nwin);
     slot.active = false;
     return total;
+}
+// a batch's slot: vector v's value, from its nwin / batch windows (after msm_slot_wait; threads may combine different v at once)
+template <class FS>
+static XYZZ<FS> msm_collect_part(const MsmSlot &slot, int v) {
+    if (!slot.active) return XYZZ<FS>::inf();
+    const int nw = slot.nwin / (slot.batch > 1 ? slot.batch : 1);
+    return msm_combine<FS>(slot, v * nw, nw);
+}
+void msm_slot_wait(MsmSlot &slot) {
+    if (slot.active) ZK_HIP(hipEventSynchronize(slot.red_done));
 }
 
 // Waves of the shipped accumulation kernels one SIMD can hold at once (registers: 255 for G1, 478 for G2 in this build): what the
@@ -1279,6 +1322,8 @@ void msm_g1_enqueue(zkg16_ctx *ctx, MsmWorkspace &ws, const MsmPlan &plan, const
 void msm_g2_enqueue(zkg16_ctx *ctx, MsmWorkspace &ws, const MsmPlan &plan, const G2AffineU *bases, MsmSlot &slot) { msm_enqueue<Fq2U>(ctx, ws, plan, bases, slot); }
 G1XYZZ msm_g1_collect(zkg16_ctx *ctx, MsmSlot &slot) { return msm_collect<Fq>(ctx, slot); }
 G2XYZZ msm_g2_collect(zkg16_ctx *ctx, MsmSlot &slot) { return msm_collect<Fq2>(ctx, slot); }
+G1XYZZ msm_g1_collect_part(const MsmSlot &slot, int v) { return msm_collect_part<Fq>(slot, v); }
+G2XYZZ msm_g2_collect_part(const MsmSlot &slot, int v) { return msm_collect_part<Fq2>(slot, v); }
 
 G1XYZZ msm_g1_exec(zkg16_ctx *ctx, MsmWorkspace &ws, const MsmPlan &plan, const G1AffineU *bases, const char *tag) {
     (void)tag;

@@ -88,7 +88,22 @@ struct NttPassArgs {
     // a rank's share of a two-pass transform (split witness map, group.hip): blockIdx.x walks the tiles [tile_lo0, + tile_n0)
     // then [tile_lo1, + tile_n1) (grid = tile_n0 + tile_n1).  tile_n0 == 0: every tile of the pass, blockIdx.x as it is.
     unsigned tile_lo0, tile_n0, tile_lo1, tile_n1;
+    // a batch of transforms (zkg16_prove_batch): blockIdx.z = vector v, whose in / out / pw_b / pw_c lie vec_stride elements
+    // after vector v - 1's; the twiddle, coset and U-form tables are shared
+    size_t vec_stride;
 };
+
+// a batch of transforms: this block's vector (blockIdx.z) — its input, output and point-wise operands; the tables are shared
+__device__ __forceinline__ void vec_offset(NttPassArgs &a) {
+    if (!blockIdx.z) return;
+    const size_t vo = (size_t)blockIdx.z * a.vec_stride;
+    a.in += vo;
+    a.out += vo;
+    if (a.pw_b) {
+        a.pw_b += vo;
+        a.pw_c += vo;
+    }
+}
 
 // the tile this block works on: the XCD-aware order (group > 1) applies within the tiles the launch covers
 __device__ __forceinline__ unsigned pass_tile(const NttPassArgs &a, unsigned group) {
@@ -147,6 +162,7 @@ __global__ void __launch_bounds__(NTT_THREADS) ntt_pass_cols(NttPassArgs a) {
     const unsigned nmask = (1u << a.log_n) - 1u;
     const size_t n2 = (size_t)1 << a.log_n2;
     const size_t col0 = (size_t)pass_tile(a, 1) * C;
+    vec_offset(a);
     const Fr *in = a.in + (size_t)blockIdx.y * a.batch_stride;
     Fr *out = a.out + (size_t)blockIdx.y * a.batch_stride;
 
@@ -185,6 +201,7 @@ __global__ void __launch_bounds__(NTT_THREADS) ntt_pass_rows(NttPassArgs a) {
     const size_t n2 = (size_t)1 << a.log_n2;
     const size_t row0 = (size_t)pass_tile(a, 1) * R;
     const size_t n1_rows = n1;                        // rows that exist (R may exceed N1 for tiny transforms)
+    vec_offset(a);
     const Fr *in = a.in + (size_t)blockIdx.y * a.batch_stride;
 
     stage_twiddles(s_tw, tw_stride, a.w, a.log_n, a.log_n2, a.inverse);
@@ -528,6 +545,7 @@ __global__ void __launch_bounds__(NTT_THREADS_U) ntt_pass_cols_u(NttPassArgs a) 
     const unsigned nmask = (1u << a.log_n) - 1u;
     const size_t n2 = (size_t)1 << a.log_n2;
     const size_t col0 = (size_t)pass_tile(a, (C >= 4 || !a.xcd_order) ? 1u : 4u / (unsigned)C) * C;
+    vec_offset(a);
     const Fr *in = a.in + (size_t)blockIdx.y * a.batch_stride;
     Fr *out = a.out + (size_t)blockIdx.y * a.batch_stride;
 
@@ -561,6 +579,7 @@ __global__ void __launch_bounds__(NTT_THREADS_U) ntt_pass_rows_u(NttPassArgs a) 
     const size_t n1 = (size_t)1 << a.log_n1;
     const size_t n2 = (size_t)1 << a.log_n2;
     const size_t row0 = (size_t)pass_tile(a, (R >= 4 || !a.xcd_order) ? 1u : 4u / (unsigned)R) * R;
+    vec_offset(a);
     const Fr *in = a.in + (size_t)blockIdx.y * a.batch_stride;
 
     if (!GTW) stage_twiddles_u(s_tw, tw_stride, a.w, a.log_n, a.log_n2, a.inverse);
@@ -673,8 +692,10 @@ static unsigned share_tiles(NttPassArgs &p, const unsigned t[4]) {
 // (round 1 ended every transform with a device-to-device copy: 7 x 64 N bytes per proof).
 // pw (optional): the witness map's point-wise stage fused into the first pass's load: src[i] <- (src[i]*b[i] - c[i]) / Z.
 // share (ntt_run_share): only a rank's tiles of each pass, and share->between() in between.
+// nvec > 1: that many transforms at once, vector v at data / tmp (and pw->b / pw->c) + v * vec_stride — every pass one launch
+// with grid.z = nvec (zkg16_prove_batch's witness map)
 static Fr *ntt_run_impl(zkg16_ctx *ctx, Fr *data, Fr *tmp, int log_n, bool inverse, bool coset, const NttPointwise *pw,
-                        const NttShare *share) {
+                        const NttShare *share, unsigned nvec = 1, size_t vec_stride = 0) {
     bool &lds_attr_set = ctx->lds_attr_ntt;          // per ctx (= per device)
     if (!lds_attr_set) {   // 64-72 KiB tile + up to 36 KiB of twiddles, or a 144 KiB tile: above the 64 KiB default dynamic-LDS cap
         for (const void *f : {reinterpret_cast<const void *>(ntt_pass_cols), reinterpret_cast<const void *>(ntt_pass_rows),
@@ -705,6 +726,8 @@ static Fr *ntt_run_impl(zkg16_ctx *ctx, Fr *data, Fr *tmp, int log_n, bool inver
     a.log_n = log_n;
     a.inverse = inverse ? 1 : 0;
     a.xcd_order = ctx->opt_ntt_xcd;
+    if (nvec < 1 || nvec > 65535 || (nvec > 1 && (share || vec_stride < n))) throw HipError{hipErrorInvalidValue, "ntt: bad batch of transforms", __FILE__, __LINE__};
+    a.vec_stride = nvec > 1 ? vec_stride : 0;
     const Fr *pre = (!inverse && coset) ? t->g.as<Fr>() : nullptr;
     const Fr *post = (inverse && coset) ? t->gi.as<Fr>() : nullptr;
     int post_const_on = (inverse && !coset) ? 1 : 0;
@@ -775,11 +798,12 @@ static Fr *ntt_run_impl(zkg16_ctx *ctx, Fr *data, Fr *tmp, int log_n, bool inver
             first(p1);
             p1.batch_stride = 0;
             const unsigned grid = share ? share_tiles(p1, share->cols) : (unsigned)(((size_t)1 << a.log_n2) >> (12 - a.log_n1));
-            ScopedKernelTimer kt(ctx, "ntt_pass_cols", (double)n);
-            if (xch2) hipLaunchKernelGGL((ntt_pass_cols_u<12, true, 3>), dim3(grid), dim3(NTT_THREADS_U), big_lds, ctx->stream, p1);
-            else if (xch) hipLaunchKernelGGL((ntt_pass_cols_u<12, true, 2>), dim3(grid), dim3(NTT_THREADS_U), big_lds, ctx->stream, p1);
-            else if (r4) hipLaunchKernelGGL((ntt_pass_cols_u<12, true, true>), dim3(grid), dim3(NTT_THREADS_U), big_lds, ctx->stream, p1);
-            else hipLaunchKernelGGL((ntt_pass_cols_u<12, true, false>), dim3(grid), dim3(NTT_THREADS_U), big_lds, ctx->stream, p1);
+            ScopedKernelTimer kt(ctx, "ntt_pass_cols", (double)n * nvec);
+            const dim3 g(grid, 1, nvec);
+            if (xch2) hipLaunchKernelGGL((ntt_pass_cols_u<12, true, 3>), g, dim3(NTT_THREADS_U), big_lds, ctx->stream, p1);
+            else if (xch) hipLaunchKernelGGL((ntt_pass_cols_u<12, true, 2>), g, dim3(NTT_THREADS_U), big_lds, ctx->stream, p1);
+            else if (r4) hipLaunchKernelGGL((ntt_pass_cols_u<12, true, true>), g, dim3(NTT_THREADS_U), big_lds, ctx->stream, p1);
+            else hipLaunchKernelGGL((ntt_pass_cols_u<12, true, false>), g, dim3(NTT_THREADS_U), big_lds, ctx->stream, p1);
         }
         if (share) share->between();
         {
@@ -788,11 +812,12 @@ static Fr *ntt_run_impl(zkg16_ctx *ctx, Fr *data, Fr *tmp, int log_n, bool inver
             p2.post = post;
             p2.post_const_on = post_const_on;
             const unsigned grid = share ? share_tiles(p2, share->rows) : (unsigned)((size_t)1 << a.log_n1);
-            ScopedKernelTimer kt(ctx, "ntt_pass_rows", (double)n);
-            if (xch2) hipLaunchKernelGGL((ntt_pass_rows_u<12, true, 3>), dim3(grid), dim3(NTT_THREADS_U), big_lds, ctx->stream, p2);
-            else if (xch) hipLaunchKernelGGL((ntt_pass_rows_u<12, true, 2>), dim3(grid), dim3(NTT_THREADS_U), big_lds, ctx->stream, p2);
-            else if (r4) hipLaunchKernelGGL((ntt_pass_rows_u<12, true, true>), dim3(grid), dim3(NTT_THREADS_U), big_lds, ctx->stream, p2);
-            else hipLaunchKernelGGL((ntt_pass_rows_u<12, true, false>), dim3(grid), dim3(NTT_THREADS_U), big_lds, ctx->stream, p2);
+            ScopedKernelTimer kt(ctx, "ntt_pass_rows", (double)n * nvec);
+            const dim3 g(grid, 1, nvec);
+            if (xch2) hipLaunchKernelGGL((ntt_pass_rows_u<12, true, 3>), g, dim3(NTT_THREADS_U), big_lds, ctx->stream, p2);
+            else if (xch) hipLaunchKernelGGL((ntt_pass_rows_u<12, true, 2>), g, dim3(NTT_THREADS_U), big_lds, ctx->stream, p2);
+            else if (r4) hipLaunchKernelGGL((ntt_pass_rows_u<12, true, true>), g, dim3(NTT_THREADS_U), big_lds, ctx->stream, p2);
+            else hipLaunchKernelGGL((ntt_pass_rows_u<12, true, false>), g, dim3(NTT_THREADS_U), big_lds, ctx->stream, p2);
         }
     } else if (log_n <= NTT_MAX_SUB_LOG) {
         if (share) throw HipError{hipErrorInvalidValue, "ntt: a share of a single-pass transform", __FILE__, __LINE__};
@@ -803,8 +828,8 @@ static Fr *ntt_run_impl(zkg16_ctx *ctx, Fr *data, Fr *tmp, int log_n, bool inver
         first(a);
         a.post = post;
         a.post_const_on = post_const_on;
-        ScopedKernelTimer kt(ctx, "ntt_pass_rows", (double)n);
-        hipLaunchKernelGGL(k_rows, dim3(1), dim3(nthreads), lds_bytes(log_n), ctx->stream, a);
+        ScopedKernelTimer kt(ctx, "ntt_pass_rows", (double)n * nvec);
+        hipLaunchKernelGGL(k_rows, dim3(1, 1, nvec), dim3(nthreads), lds_bytes(log_n), ctx->stream, a);
     } else {
         // N = N0 * M (N0 = 1 for N <= 2^22): [outer column pass over N0] then the two-pass transform of size M, batched over k0 < N0
         const int log_m = log_n <= 2 * NTT_MAX_SUB_LOG ? log_n : 2 * NTT_MAX_SUB_LOG;
@@ -816,8 +841,8 @@ static Fr *ntt_run_impl(zkg16_ctx *ctx, Fr *data, Fr *tmp, int log_n, bool inver
             first(p0);
             p0.log_n1 = log_n0; p0.log_n2 = log_m;
             const unsigned grid = (unsigned)(((size_t)1 << log_m) >> (NTT_TILE_LOG - log_n0));
-            ScopedKernelTimer kt(ctx, "ntt_pass_cols", (double)n);
-            hipLaunchKernelGGL(k_cols, dim3(grid), dim3(nthreads), lds_bytes(log_n0), ctx->stream, p0);
+            ScopedKernelTimer kt(ctx, "ntt_pass_cols", (double)n * nvec);
+            hipLaunchKernelGGL(k_cols, dim3(grid, 1, nvec), dim3(nthreads), lds_bytes(log_n0), ctx->stream, p0);
         }
         a.log_n2 = log_m / 2;
         a.log_n1 = log_m - a.log_n2;
@@ -829,8 +854,8 @@ static Fr *ntt_run_impl(zkg16_ctx *ctx, Fr *data, Fr *tmp, int log_n, bool inver
             p1.tw_shift = log_n0;
             p1.batch_stride = (size_t)1 << log_m;
             const unsigned grid = share ? share_tiles(p1, share->cols) : (unsigned)(((size_t)1 << a.log_n2) >> (NTT_TILE_LOG - a.log_n1));
-            ScopedKernelTimer kt(ctx, "ntt_pass_cols", (double)n);
-            hipLaunchKernelGGL(k_cols, dim3(grid, batches), dim3(nthreads), lds_bytes(a.log_n1), ctx->stream, p1);
+            ScopedKernelTimer kt(ctx, "ntt_pass_cols", (double)n * nvec);
+            hipLaunchKernelGGL(k_cols, dim3(grid, batches, nvec), dim3(nthreads), lds_bytes(a.log_n1), ctx->stream, p1);
         }
         if (share) share->between();
         {
@@ -841,8 +866,8 @@ static Fr *ntt_run_impl(zkg16_ctx *ctx, Fr *data, Fr *tmp, int log_n, bool inver
             p2.batch_stride = (size_t)1 << log_m;
             p2.out_stride_log = log_n0;
             const unsigned grid = share ? share_tiles(p2, share->rows) : (unsigned)(((size_t)1 << a.log_n1) >> (NTT_TILE_LOG - a.log_n2));
-            ScopedKernelTimer kt(ctx, "ntt_pass_rows", (double)n);
-            hipLaunchKernelGGL(k_rows, dim3(grid, batches), dim3(nthreads), lds_bytes(a.log_n2), ctx->stream, p2);
+            ScopedKernelTimer kt(ctx, "ntt_pass_rows", (double)n * nvec);
+            hipLaunchKernelGGL(k_rows, dim3(grid, batches, nvec), dim3(nthreads), lds_bytes(a.log_n2), ctx->stream, p2);
         }
     }
     ZK_HIP(hipGetLastError());
@@ -851,6 +876,9 @@ static Fr *ntt_run_impl(zkg16_ctx *ctx, Fr *data, Fr *tmp, int log_n, bool inver
 
 Fr *ntt_run(zkg16_ctx *ctx, Fr *data, Fr *tmp, int log_n, bool inverse, bool coset, const NttPointwise *pw) {
     return ntt_run_impl(ctx, data, tmp, log_n, inverse, coset, pw, nullptr);
+}
+Fr *ntt_run_batch(zkg16_ctx *ctx, Fr *data, Fr *tmp, int log_n, bool inverse, bool coset, const NttPointwise *pw, unsigned nvec, size_t vec_stride) {
+    return ntt_run_impl(ctx, data, tmp, log_n, inverse, coset, pw, nullptr, nvec, vec_stride);
 }
 
 // A rank's share of one two-pass transform (split witness map, group.hip): the column pass over the tiles share->cols, then

@@ -31,6 +31,8 @@ struct SpmvArgs {
     size_t nc, num_instance, n;   // n = domain size (outputs are zero-padded to n)
     const uint32_t *rows[3];      // null, or lane t takes row rows[m][t], t < nrows[m] (a rank's rows, split witness map)
     size_t nrows[3];
+    const Fr *const *zs;          // a batch (zkg16_prove_batch): blockIdx.z = vector v reads zs[v] and writes out[m] + v * out_stride
+    size_t out_stride;
 };
 // the row of lane `t` of matrix m: from the rank's row list, else from the length-class order (rows < nc), else t itself
 template <class Args>
@@ -55,18 +57,19 @@ __global__ void __launch_bounds__(256) spmv_kernel(SpmvArgs a) {
     size_t row = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int m = blockIdx.y;
     if (!spmv_row(a, m, row)) return;
+    const Fr *z = a.zs ? a.zs[blockIdx.z] : a.z;
     Fr acc = Fr::zero();
     if (row < a.nc) {
         const uint64_t lo = a.rp[m][row], hi = a.rp[m][row + 1];
         for (uint64_t k = lo; k < hi; k++) {
             Fr c = gld_fr(a.cf[m] + k);
-            Fr v = gld_fr(a.z + a.col[m][k]);
+            Fr v = gld_fr(z + a.col[m][k]);
             acc = fp_add(acc, fp_mul(c, v));
         }
     } else if (m == 0 && row < a.nc + a.num_instance) {
-        acc = gld_fr(a.z + (row - a.nc));
+        acc = gld_fr(z + (row - a.nc));
     }
-    gst_fr(a.out[m] + row, acc);
+    gst_fr(a.out[m] + (size_t)blockIdx.z * a.out_stride + row, acc);
 }
 
 // ab[i] = (a[i]*b[i] - c[i]) * zinv
@@ -208,6 +211,8 @@ struct SpmvDictArgs {
     size_t nc, num_instance, n;
     const uint32_t *rows[3];
     size_t nrows[3];
+    const Fr *const *zs;
+    size_t out_stride;
 };
 // the same row-per-lane product with the coefficient taken from the dictionary in LDS ([8][ndict] words: neighbouring lanes
 // reading different entries spread over the banks); a coefficient equal to one (40 % of the MatrixCircuit's, all of its C
@@ -225,12 +230,13 @@ __global__ void __launch_bounds__(256) spmv_dict_kernel(SpmvDictArgs a) {
     size_t row = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int m = blockIdx.y;
     if (!spmv_row(a, m, row)) return;
+    const Fr *z = a.zs ? a.zs[blockIdx.z] : a.z;
     Fr acc = Fr::zero();
     if (row < a.nc) {
         const uint64_t lo = a.rp[m][row], hi = a.rp[m][row + 1];
         for (uint64_t k = lo; k < hi; k++) {
             const uint32_t e = a.ci[m][k];
-            const Fr v = gld_fr(a.z + a.col[m][k]);
+            const Fr v = gld_fr(z + a.col[m][k]);
             if (s_one[e]) {
                 acc = fp_add(acc, v);
             } else {
@@ -241,9 +247,9 @@ __global__ void __launch_bounds__(256) spmv_dict_kernel(SpmvDictArgs a) {
             }
         }
     } else if (m == 0 && row < a.nc + a.num_instance) {
-        acc = gld_fr(a.z + (row - a.nc));
+        acc = gld_fr(z + (row - a.nc));
     }
-    gst_fr(a.out[m] + row, acc);
+    gst_fr(a.out[m] + (size_t)blockIdx.z * a.out_stride + row, acc);
 }
 
 // ------------------------------------------------------------------------------------------------ rows by length
@@ -384,7 +390,8 @@ static void coef_dict_build(zkg16_ctx *ctx, R1csDev &m) {
     m.dict_state = 1;
 }
 
-void spmv_run(zkg16_ctx *ctx, R1csDev &m, const Fr *z, Fr *a, Fr *b, Fr *c, const SpmvRows *rows) {
+// zs / nvec (a batch): vector v's assignment at zs[v] (device-visible pointer table), its a / b / c at a / b / c + v * N
+void spmv_run(zkg16_ctx *ctx, R1csDev &m, const Fr *z, Fr *a, Fr *b, Fr *c, const SpmvRows *rows, const Fr *const *zs, unsigned nvec) {
     // both structures are built the SECOND time a handle is used: the reference's request flow uses its matrices once (the
     // three passes of the build cost more than they save there: Fermat-prime request 8.1 -> 9.7 ms), a resident system pays once
     {
@@ -396,7 +403,8 @@ void spmv_run(zkg16_ctx *ctx, R1csDev &m, const Fr *z, Fr *a, Fr *b, Fr *c, cons
     if (rows) lanes = std::max(rows->n[0], std::max(rows->n[1], rows->n[2]));
     if (!lanes) return;
     const unsigned grid = (unsigned)((lanes + 255) / 256);
-    ScopedKernelTimer kt(ctx, "spmv_kernel", (double)(m.nnz[0] + m.nnz[1] + m.nnz[2]));
+    if (nvec < 1 || nvec > 65535 || (nvec > 1 && (rows || !zs))) throw HipError{hipErrorInvalidValue, "spmv: bad batch", __FILE__, __LINE__};
+    ScopedKernelTimer kt(ctx, "spmv_kernel", (double)(m.nnz[0] + m.nnz[1] + m.nnz[2]) * nvec);
     if (m.dict_state == 1 && ctx->opt_spmv_dict != 2) {
         SpmvDictArgs s;
         for (int i = 0; i < 3; i++) {
@@ -407,6 +415,8 @@ void spmv_run(zkg16_ctx *ctx, R1csDev &m, const Fr *z, Fr *a, Fr *b, Fr *c, cons
         }
         s.out[0] = a; s.out[1] = b; s.out[2] = c;
         s.z = z;
+        s.zs = nvec > 1 ? zs : nullptr;
+        s.out_stride = nvec > 1 ? n : 0;
         s.dict = m.dict.as<Fr>();
         s.ndict = m.ndict;
         s.nc = m.num_constraints;
@@ -416,7 +426,7 @@ void spmv_run(zkg16_ctx *ctx, R1csDev &m, const Fr *z, Fr *a, Fr *b, Fr *c, cons
             s.rows[i] = rows ? rows->list[i] : nullptr;
             s.nrows[i] = rows ? rows->n[i] : 0;
         }
-        hipLaunchKernelGGL(spmv_dict_kernel, dim3(grid, 3), dim3(256), m.ndict * 33 + 16, ctx->stream, s);
+        hipLaunchKernelGGL(spmv_dict_kernel, dim3(grid, 3, nvec), dim3(256), m.ndict * 33 + 16, ctx->stream, s);
     } else {
         SpmvArgs s;
         for (int i = 0; i < 3; i++) {
@@ -427,6 +437,8 @@ void spmv_run(zkg16_ctx *ctx, R1csDev &m, const Fr *z, Fr *a, Fr *b, Fr *c, cons
         }
         s.out[0] = a; s.out[1] = b; s.out[2] = c;
         s.z = z;
+        s.zs = nvec > 1 ? zs : nullptr;
+        s.out_stride = nvec > 1 ? n : 0;
         s.nc = m.num_constraints;
         s.num_instance = m.num_instance;
         s.n = n;
@@ -434,7 +446,7 @@ void spmv_run(zkg16_ctx *ctx, R1csDev &m, const Fr *z, Fr *a, Fr *b, Fr *c, cons
             s.rows[i] = rows ? rows->list[i] : nullptr;
             s.nrows[i] = rows ? rows->n[i] : 0;
         }
-        hipLaunchKernelGGL(spmv_kernel, dim3(grid, 3), dim3(256), 0, ctx->stream, s);
+        hipLaunchKernelGGL(spmv_kernel, dim3(grid, 3, nvec), dim3(256), 0, ctx->stream, s);
     }
     ZK_HIP(hipGetLastError());
 }
@@ -474,6 +486,30 @@ void witness_map_run(zkg16_ctx *ctx, R1csDev &m, const Fr *z, Fr **h_out) {
     } else {
         pointwise_h_run(ctx, a, b, c, t->zinv, n);
         *h_out = ntt_run(ctx, a, tmp, m.log_n, true, true);
+    }
+}
+
+// The witness map of a batch: the K assignments at zs[0 .. K) (device-visible pointer table), every launch of witness_map_run
+// once over the K vectors — one SpMV, seven transform passes sequences with grid.z = K (shared tables, the fused (ab - c)/Z per
+// vector).  a, b, c and the scratch hold K vectors of N side by side; *h_out = K h vectors of N, vector v at (*h_out) + v * N.
+void witness_map_run_batch(zkg16_ctx *ctx, R1csDev &m, const Fr *const *zs, unsigned nvec, Fr **h_out) {
+    const size_t n = (size_t)1 << m.log_n;
+    for (int i = 0; i < 4; i++) ctx->poly[i].ensure((size_t)nvec * n * sizeof(Fr));
+    Fr *a = ctx->poly[0].as<Fr>(), *b = ctx->poly[1].as<Fr>(), *c = ctx->poly[2].as<Fr>(), *tmp = ctx->poly[3].as<Fr>();
+    spmv_run(ctx, m, nullptr, a, b, c, nullptr, zs, nvec);
+    ntt_run_batch(ctx, a, tmp, m.log_n, true, false, nullptr, nvec, n);
+    ntt_run_batch(ctx, tmp, a, m.log_n, false, true, nullptr, nvec, n);
+    ntt_run_batch(ctx, b, tmp, m.log_n, true, false, nullptr, nvec, n);
+    ntt_run_batch(ctx, tmp, b, m.log_n, false, true, nullptr, nvec, n);
+    ntt_run_batch(ctx, c, tmp, m.log_n, true, false, nullptr, nvec, n);
+    ntt_run_batch(ctx, tmp, c, m.log_n, false, true, nullptr, nvec, n);
+    NttTables *t = ntt_get_tables(ctx, m.log_n);
+    if (ctx->opt_fuse_pointwise) {
+        const NttPointwise pw{b, c, t->zinv};
+        *h_out = ntt_run_batch(ctx, a, tmp, m.log_n, true, true, &pw, nvec, n);
+    } else {
+        pointwise_h_run(ctx, a, b, c, t->zinv, (size_t)nvec * n);      // element-wise: the K vectors are one array
+        *h_out = ntt_run_batch(ctx, a, tmp, m.log_n, true, true, nullptr, nvec, n);
     }
 }
 

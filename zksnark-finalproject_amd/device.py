@@ -212,6 +212,21 @@ class Device:
         self._check(self.lib.zkg16_prove_resident(self.ctx, pk_h, r1cs_h, wit_h, _u64(r), _u64(s), proof, inf))
         return proof, inf
 
+    def prove_batch(self, pk_h, r1cs_h, witness_handles, rs, ss):
+        """K proofs of one circuit on one resident key in one device pass (zkg16_prove_batch): witness_handles [k], rs / ss [k, 4]
+        Montgomery -> (proofs [k, 48], inf [k, 3]); proof k is byte-identical to prove_resident(pk_h, r1cs_h, witness_handles[k],
+        rs[k], ss[k])."""
+        hs = np.ascontiguousarray(witness_handles, dtype=np.uint64).reshape(-1)
+        k = hs.shape[0]
+        rs = _u64(rs).reshape(-1, 4)
+        ss = _u64(ss).reshape(-1, 4)
+        if rs.shape[0] != k or ss.shape[0] != k:
+            raise ValueError("prove_batch: one r and one s per witness handle")
+        proofs = np.zeros((k, 48), dtype=np.uint64)
+        inf = np.zeros((k, 3), dtype=np.uint8)
+        self._check(self.lib.zkg16_prove_batch(self.ctx, pk_h, r1cs_h, hs, k, rs, ss, proofs, inf))
+        return proofs, inf
+
     def prove_matrix(self, pk_h, r1cs_h, a, b, r, s):
         """One matrix-handler request on resident matrices: assignment built on the device while the proof already runs
         (zkg16_prove_matrix) -> (proof, inf, public inputs [3, 4], dict of ms)."""
