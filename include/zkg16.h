@@ -419,7 +419,9 @@ ZKG16_API void zkg16_kernel_stats_reset(zkg16_ctx *ctx);
  *                    2^24 by three passes over 2048-point tiles instead of two over 4096-point tiles
  *   "ntt_radix"      1 (default; also 0) = the last seven butterfly stages of a tile by lane exchanges, 3 = the top seven as well,
  *                    2 = every stage through the LDS, 4 = two stages per LDS trip
- *   "fuse_pointwise" 1 (default) = (ab - c)/Z fused into the load of the seventh transform, 0 = its own pass
+ *   "fuse_pointwise" 1 (default) = the point-wise product fused into the load of the witness map's last transform, 0 = its own pass
+ *   "wm_transforms"  6 (default; also 0) = the witness map's C only inverse-transformed and subtracted on the last transform's store,
+ *                    7 = arkworks' seven transforms (C to the coset and back)
  *   "collect_threads" host combination of the z-side MSMs' window sums: 0 = own threads for plain keys, 1 = always, 2 = never
  *   "fixed_base_bits" window width of the setup's fixed-base multiplications (0 = by batch size; 16 / 18 / 20 = two-level tables)
  *   "g2_lazy"        G2 accumulation's Fq2 products: 0 / 1 (default) two fused two-product reductions with operands parked in LDS, 2 = Karatsuba

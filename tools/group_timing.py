@@ -1,6 +1,6 @@
 """Per-rank timing of a device group (zkg16_group_create / zkg16_prove_group) on the MatrixCircuit, with the witness map split
 over the group's witness-map ranks (csrc/group.hip):
-   python tools/group_timing.py [--devices 0,0,0,0] [--n 128|46|32] [--tables on|off] [--bw 50] [--reps 3]
+   python tools/group_timing.py [--devices 0,0,0,0] [--n 128|46|32] [--tables on|off] [--bw 50] [--reps 3] [--wm-transforms 6|7]
 --devices: one ctx per entry (the default puts four ctxs on GPU 0: every number below is then measured on ONE GPU).
 Reports per rank
   - the witness-map share's device time with option group_serial = 1 (each step of each rank alone on the device), of which the
@@ -32,10 +32,14 @@ def main():
     ap.add_argument("--bw", type=float, default=50.0, help="GB/s per rank for the exchanges (a prediction input, not a measurement)")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--wm-only", action="store_true", help="no keys: the split witness map's share per rank for k = 2 .. len(devices)")
+    ap.add_argument("--wm-transforms", type=int, default=6, choices=[6, 7], help="option wm_transforms: one exchange per transform")
     a = ap.parse_args()
     ids = [int(x) for x in a.devices.split(",")]
     G, tables = len(ids), a.tables == "on"
     devs = [Device(i) for i in ids]
+    for d in devs:
+        d.set_option("wm_transforms", a.wm_transforms)
+    T = a.wm_transforms
     rng = np.random.default_rng(a.n)
     am = rng.integers(0, 1 << 20, size=(a.n, a.n), dtype=np.uint64)
     bm = rng.integers(0, 1 << 20, size=(a.n, a.n), dtype=np.uint64)
@@ -72,9 +76,9 @@ def main():
             g.close()
             wm = [float(np.median([run[j]["wm_ms"] for run in runs])) for j in range(k)]
             ex, hb = runs[0][0]["exchange_bytes"], runs[0][0]["h_bytes"]
-            xfer = (7 * ex + hb) / (a.bw * 1e9) * 1e3
-            print("k = %d: wm share per rank (serial, ms) %s; exchange %.1f MB x 7 + h %.1f MB per rank -> %.2f ms at %.0f GB/s (UNMEASURED)" %
-                  (k, [round(x, 2) for x in wm], ex / 1e6, hb / 1e6, xfer, a.bw))
+            xfer = (T * ex + hb) / (a.bw * 1e9) * 1e3
+            print("k = %d: wm share per rank (serial, ms) %s; exchange %.1f MB x %d + h %.1f MB per rank -> %.2f ms at %.0f GB/s (UNMEASURED)" %
+                  (k, [round(x, 2) for x in wm], ex / 1e6, T, hb / 1e6, xfer, a.bw))
         for d, (_, rh, wh) in zip(devs, hs):
             d.r1cs_free(rh)
             d.witness_free(wh)
@@ -151,11 +155,11 @@ def main():
                 role += "+z"
             if i in wstats:
                 w = wstats[i]
-                xfer = (7 * w["ex"] + w["h"]) / (a.bw * 1e9) * 1e3
+                xfer = (T * w["ex"] + w["h"]) / (a.bw * 1e9) * 1e3
                 pred = w["wm"] - w["gather"] + xfer + share[i]
-                print("  rank %d %-6s wm share %.2f ms (serial; gathers %.2f ms)  exchange %.1f MB x 7 + h %.1f MB  H/z share %.2f ms"
+                print("  rank %d %-6s wm share %.2f ms (serial; gathers %.2f ms)  exchange %.1f MB x %d + h %.1f MB  H/z share %.2f ms"
                       "  -> predicted %.2f ms (exchanges %.2f ms at %.0f GB/s: UNMEASURED)" %
-                      (i, role, w["wm"], w["gather"], w["ex"] / 1e6, w["h"] / 1e6, share[i], pred, xfer, a.bw))
+                      (i, role, w["wm"], w["gather"], w["ex"] / 1e6, T, w["h"] / 1e6, share[i], pred, xfer, a.bw))
             else:
                 pred = share[i] + (wm_full if p[3] > p[2] else 0.0)
                 print("  rank %d %-6s H/z share %.2f ms%s -> predicted %.2f ms" %

@@ -85,7 +85,7 @@ void copy_options(zkg16_ctx *dst, const zkg16_ctx *src) {
     dst->opt_ntt_radix = src->opt_ntt_radix; dst->opt_ntt_xcd = src->opt_ntt_xcd; dst->opt_acc_debug = src->opt_acc_debug;
     dst->opt_sort_mode = src->opt_sort_mode; dst->opt_acc_pipeline = src->opt_acc_pipeline; dst->opt_fuse_pointwise = src->opt_fuse_pointwise;
     dst->opt_matrix_parts = src->opt_matrix_parts; dst->opt_g2_lazy = src->opt_g2_lazy; dst->opt_g1_inline = src->opt_g1_inline; dst->opt_fixed_base_bits = src->opt_fixed_base_bits;
-    dst->opt_collect_threads = src->opt_collect_threads; dst->opt_batch_max = src->opt_batch_max;
+    dst->opt_collect_threads = src->opt_collect_threads; dst->opt_batch_max = src->opt_batch_max; dst->opt_wm_transforms = src->opt_wm_transforms;
     dst->kernel_timing = src->kernel_timing; dst->kernel_timing_accumulate_only = src->kernel_timing_accumulate_only;
 }
 void create_streams(zkg16_ctx *ctx) {
@@ -1114,8 +1114,13 @@ int set_option_one(zkg16_ctx *ctx, const char *name, int64_t value) {
         ctx->opt_acc_pipeline = value == 4 ? 0 : (int)value;
         return ZKG16_OK;
     }
-    if (!strcmp(name, "fuse_pointwise")) {     // 1 (default): (ab - c)/Z on the load of the seventh transform; 0: own pass
+    if (!strcmp(name, "fuse_pointwise")) {     // 1 (default): the point-wise product on the load of the last transform; 0: own pass
         ctx->opt_fuse_pointwise = value ? 1 : 0;
+        return ZKG16_OK;
+    }
+    if (!strcmp(name, "wm_transforms")) {      // 6 (default; also 0): C only inverse-transformed (poly.hip: wm_transforms); 7: arkworks' seven
+        if (value != 0 && value != 6 && value != 7) return ZKG16_ERR_BAD_ARG;
+        ctx->opt_wm_transforms = value == 7 ? 7 : 6;
         return ZKG16_OK;
     }
     if (!strcmp(name, "wm_first")) {           // -1 (default): 1 from 2^23 on for keys with window tables; 0: z-side accumulations start at once; 1: after the witness map; 2: after the h-side sort too
@@ -2305,14 +2310,14 @@ int group_run(zkg16_group *grp, GroupBarrier *bar, const std::function<void(int,
 }
 
 // the split witness map of a group call, or null when the replicated one runs (k < 2, the layout does not apply, or the
-// witness-map ranks do not agree on the NTT plan)
+// witness-map ranks do not agree on the NTT plan or on the number of transforms: their exchanges would not pair up)
 std::unique_ptr<GroupSync> group_sync_for(zkg16_group *grp, const std::vector<int> &wm_ranks, int log_n, const std::vector<uint64_t> &h_lo,
                                           const std::vector<uint64_t> &h_hi) {
     const int k = (int)wm_ranks.size();
     if (k < 2) return nullptr;
-    const int mode = grp->ctxs[wm_ranks[0]]->opt_ntt_mode;
+    const int mode = grp->ctxs[wm_ranks[0]]->opt_ntt_mode, transforms = grp->ctxs[wm_ranks[0]]->opt_wm_transforms;
     for (int r : wm_ranks)
-        if (grp->ctxs[r]->opt_ntt_mode != mode) return nullptr;
+        if (grp->ctxs[r]->opt_ntt_mode != mode || grp->ctxs[r]->opt_wm_transforms != transforms) return nullptr;
     GroupLayout L;
     if (!group_layout(log_n, k, mode, L) || !L.applies) return nullptr;
     auto S = std::make_unique<GroupSync>(k);

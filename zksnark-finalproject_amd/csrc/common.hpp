@@ -301,7 +301,8 @@ struct zkg16_ctx {
     int opt_g2_lazy = 1;                              // G2 accumulation: Fq2 products with one reduction per component, operands parked in LDS (ffu.cuh: fq2u_mul_lazy)
     int opt_g1_inline = 1;                            // G1 accumulation (plain loop): every field product inlined (ec.cuh: xyzz_madd_inline); 0: products as calls
     int opt_matrix_parts = 0;                         // zkg16_prove_matrix: gadget slices the assignment arrives in (0 = five growing slices, k = k equal ones, 1 = no overlap)
-    int opt_fuse_pointwise = 1;                       // (ab - c)/Z on the load of the seventh transform (0: its own pass)
+    int opt_fuse_pointwise = 1;                       // the point-wise product on the load of the last transform (0: its own pass)
+    int opt_wm_transforms = 6;                        // witness map: 6 (default) = C only inverse-transformed, subtracted on the last store; 7 = arkworks' sequence
     int opt_batch_max = 0;                            // zkg16_prove_batch: proofs per device pass (0 = as many as fit)
     int num_cus = 256;
     bool lds_attr_fixup[2] = {false, false}, lds_attr_ntt = false;      // hipFuncSetAttribute(max dynamic LDS) done on this device
@@ -329,11 +330,19 @@ void kernel_timer_resolve(zkg16_ctx *ctx);
 
 // ---- entry points implemented per translation unit
 // Out of place: returns `dst`, which holds the transform of `src`; `src` is scratch afterwards.  pw: optional fused
-// point-wise stage on the input, src[i] <- (src[i] * b[i] - c[i]) * zinv (the witness map's (ab - c)/Z).
+// point-wise stage on the input, src[i] <- (src[i] * b[i] - c[i]) * zinv (the witness map's (ab - c)/Z); with c null,
+// src[i] <- src[i] * b[i], b being the output of a transform whose last store carried NttLast::pw_operand.
 struct NttPointwise { const Fr *b, *c; Fr zinv; };
-Fr *ntt_run(zkg16_ctx *ctx, Fr *src, Fr *dst, int log_n, bool inverse, bool coset, const NttPointwise *pw = nullptr);
+// optional extras on the store of a transform's last pass (the six-transform witness map, poly.hip):
+//   scale       the results are multiplied by *scale as well (not with a coset ifft: its store multiplies by a table);
+//   pw_operand  ... and by the factor the one-product fused load (pw with c null) expects of its operand b (U-form: 2^5);
+//   sub         dst[k] <- result - dst[k]: dst holds the subtrahend, read by the thread that then overwrites it.
+struct NttLast { const Fr *scale; bool pw_operand, sub; };
+Fr *ntt_run(zkg16_ctx *ctx, Fr *src, Fr *dst, int log_n, bool inverse, bool coset, const NttPointwise *pw = nullptr,
+            const NttLast *last = nullptr);
 // nvec transforms at once: vector v at src / dst (and pw->b / pw->c) + v * vec_stride, every pass one launch over all of them
-Fr *ntt_run_batch(zkg16_ctx *ctx, Fr *src, Fr *dst, int log_n, bool inverse, bool coset, const NttPointwise *pw, unsigned nvec, size_t vec_stride);
+Fr *ntt_run_batch(zkg16_ctx *ctx, Fr *src, Fr *dst, int log_n, bool inverse, bool coset, const NttPointwise *pw, unsigned nvec, size_t vec_stride,
+                  const NttLast *last = nullptr);
 NttTables *ntt_get_tables(zkg16_ctx *ctx, int log_n);
 // a rank's share of a two-pass transform (split witness map): tiles {lo0, n0, lo1, n1} of the column and of the row pass, and
 // what runs between the two passes (the exchange); see ntt_run_share in ntt.hip
@@ -341,14 +350,15 @@ struct NttShare {
     unsigned cols[4], rows[4];
     std::function<void()> between;
 };
-Fr *ntt_run_share(zkg16_ctx *ctx, Fr *src, Fr *dst, int log_n, bool inverse, bool coset, const NttPointwise *pw, const NttShare &share);
+Fr *ntt_run_share(zkg16_ctx *ctx, Fr *src, Fr *dst, int log_n, bool inverse, bool coset, const NttPointwise *pw, const NttShare &share,
+                  const NttLast *last = nullptr);
 bool ntt_two_pass_shape(int log_n, int ntt_mode, int *log_n1, int *log_n2, int *tile_log);
 
 // rows: null = every row of the domain; else lane t of matrix i computes row list[i][t], t < n[i] (a rank's share, group.hip)
 struct SpmvRows { const uint32_t *list[3]; size_t n[3]; };
 void spmv_run(zkg16_ctx *ctx, R1csDev &m, const Fr *z, Fr *a, Fr *b, Fr *c, const SpmvRows *rows = nullptr, const Fr *const *zs = nullptr,
               unsigned nvec = 1);
-void pointwise_h_run(zkg16_ctx *ctx, Fr *ab_a, const Fr *b, const Fr *c, const Fr &zinv, size_t n);
+void pointwise_h_run(zkg16_ctx *ctx, Fr *ab_a, const Fr *b, const Fr *c /* null: ab only */, const Fr &zinv, size_t n);
 void fr_from_mont_run(zkg16_ctx *ctx, const Fr *in, Fr *out, size_t n);
 void witness_map_run(zkg16_ctx *ctx, R1csDev &m, const Fr *z, Fr **h_out);
 void witness_map_run_batch(zkg16_ctx *ctx, R1csDev &m, const Fr *const *zs, unsigned nvec, Fr **h_out);

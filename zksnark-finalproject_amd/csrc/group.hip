@@ -1,5 +1,5 @@
-// Split witness map over the ranks of a device group: layout (host), exchange kernel and one rank's share of the seven
-// transforms.  See group.hpp for the layout; the group object and its entry points are in api.hip.
+// Split witness map over the ranks of a device group: layout (host), exchange kernel and one rank's share of the witness
+// map's transforms.  See group.hpp for the layout; the group object and its entry points are in api.hip.
 #include <chrono>
 
 #include "group.hpp"
@@ -135,7 +135,7 @@ __global__ void __launch_bounds__(256) group_gather_kernel(GatherArgs a) {
     }
 }
 
-// (ab - c) / Z on the positions n with n mod m in [lo, hi) only (option fuse_pointwise 0)
+// (ab - c) / Z on the positions n with n mod m in [lo, hi) only (option fuse_pointwise 0); c null (six transforms): ab only
 __global__ void __launch_bounds__(256) group_pointwise_kernel(Fr *a, const Fr *b, const Fr *c, Fr zinv, uint64_t m, uint64_t lo,
                                                               uint64_t w, uint64_t count) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -148,7 +148,8 @@ __global__ void __launch_bounds__(256) group_pointwise_kernel(Fr *a, const Fr *b
         v.l[0] = s.x; v.l[1] = s.y; v.l[2] = s.z; v.l[3] = s.w; v.l[4] = t.x; v.l[5] = t.y; v.l[6] = t.z; v.l[7] = t.w;
         return v;
     };
-    const Fr x = fp_mul(fp_sub(fp_mul(ld(a + p), ld(b + p)), ld(c + p)), zinv);
+    Fr x = fp_mul(ld(a + p), ld(b + p));
+    if (c) x = fp_mul(fp_sub(x, ld(c + p)), zinv);
     uint4 *o = reinterpret_cast<uint4 *>(a + p);
     o[0] = make_uint4(x.l[0], x.l[1], x.l[2], x.l[3]);
     o[1] = make_uint4(x.l[4], x.l[5], x.l[6], x.l[7]);
@@ -220,19 +221,24 @@ static std::shared_ptr<R1csDev::RowShare> group_rows(zkg16_ctx *ctx, R1csDev &m,
     return rs;
 }
 
-// Rank g's share of h = coset_ifft((coset_fft(ifft a) coset_fft(ifft b) - coset_fft(ifft c)) / Z), the same ping-pong between
-// a, b, c and tmp as witness_map_run.  Ordering across ranks, per exchange t (seven in front of the row passes, the eighth = h):
-//   - rank g records ev[g][t] on its stream after the writes the peers will read (its column pass; for t = 7 its last row pass);
+// Rank g's share of h, the same transforms and the same ping-pong between a, b, c and tmp as witness_map_run (poly.hip:
+// wm_transforms): six by default, h = coset_ifft(A_cos B_cos / Z) - ifft(c) / Z with the subtraction on the last row pass's store;
+// seven with option wm_transforms = 7.  T = the number of transforms.  Ordering across ranks, per exchange t (one in front of each
+// row pass, t < T; the redistribution of h is t = T):
+//   - rank g records ev[g][t] on its stream after the writes the peers will read (its column pass; for t = T its last row pass);
 //   - a host barrier across the rank threads follows, so no wait below is enqueued before the event it names was recorded;
 //   - g's gather waits on ev[h][t] of every peer h.
 // The same events cover write after read.  Exchange t reads the peers' buffer src_t (the column pass's); a peer's first later
 // write into src_t is either its row pass of t + 1 (src_t = dst_{t+1}) or a pass of t + 2 or later, and every one of those is
 // queued behind that peer's own gather of t + 1, which waits on ev[g][t + 1], which g records after its gather of t.  The only
 // peer write not behind that wait is its column pass of t + 1, and it runs in place on src_{t+1} != src_t (consecutive
-// transforms use different buffers).  The redistribution (t = 7) reads the peers' tmp; no later write to tmp happens in this
-// call, and the next group call's first write to tmp (its first row pass) again waits on every rank's next column-pass event,
-// queued after that rank's redistribution.  Nothing else here synchronises with the host (the row order of the SpMV is built
-// once per handle and share).
+// transforms use different buffers: sources a tmp b tmp c a with six, a tmp b tmp c tmp a with seven).  With six, the last row
+// pass reads the rank's own tmp at exactly the positions the same rank's row pass of c wrote (a rank's row tiles are the same in
+// every transform): same stream, and gathers write only the gathering rank's own buffers.  No peer reads tmp in between: the
+// exchanges there read the source of the last transform, a, and the redistribution's event follows the last row pass.  The
+// redistribution (t = T) reads the peers' tmp; no later write to tmp happens in this call, and the next group call's first write to
+// tmp (its first row pass) again waits on every rank's next column-pass event, queued after that rank's redistribution.  Nothing
+// else here synchronises with the host (the row order of the SpMV is built once per handle and share).
 void group_witness_map_run(zkg16_ctx *ctx, R1csDev &m, const Fr *z, Fr **h_out, GroupRank &r) {
     GroupSync &S = *r.sync;
     const int g = r.idx;
@@ -276,27 +282,35 @@ void group_witness_map_run(zkg16_ctx *ctx, R1csDev &m, const Fr *z, Fr **h_out, 
         return group_gather(ctx, S, g, role, rects, n);
     };
 
-    struct Step { int src, dst; bool inverse, coset; };
-    static const Step seq[7] = {{0, 3, true, false}, {3, 0, false, true}, {1, 3, true, false}, {3, 1, false, true},
-                                {2, 3, true, false}, {3, 2, false, true}, {0, 3, true, true}};
+    struct Step { int src, dst; bool inverse, coset; const NttLast *last; };
+    const bool six = ctx->opt_wm_transforms != 7;
+    const bool fuse = ctx->opt_fuse_pointwise != 0;
+    const NttLast to_b{&tab->zinv, fuse, false}, to_c{&tab->zinv, false, false}, sub{nullptr, false, true};
+    const Step seq7[7] = {{0, 3, true, false, nullptr}, {3, 0, false, true, nullptr}, {1, 3, true, false, nullptr}, {3, 1, false, true, nullptr},
+                          {2, 3, true, false, nullptr}, {3, 2, false, true, nullptr}, {0, 3, true, true, nullptr}};
+    const Step seq6[6] = {{0, 3, true, false, nullptr}, {3, 0, false, true, nullptr}, {1, 3, true, false, nullptr}, {3, 1, false, true, &to_b},
+                          {2, 3, true, false, &to_c}, {0, 3, true, true, &sub}};
+    const Step *seq = six ? seq6 : seq7;
+    const int T = six ? 6 : 7;
+    static_assert(GroupSync::EXCHANGES >= 8, "an event per exchange of the seven-transform map and the redistribution");
     step_begin();
     spmv_run(ctx, m, z, v[0], v[1], v[2], &sp);
-    for (int t = 0; t < 7; t++) {
+    for (int t = 0; t < T; t++) {
         NttShare sh;
         group_share_tiles(L, g, sh.cols, sh.rows);
         const int role = seq[t].src;
         sh.between = [&, t, role] { S.ex_bytes[g] = exchange(t, role, S.ex_rects); };
-        const NttPointwise pw{v[1], v[2], tab->zinv};
-        const bool fused = t == 6 && ctx->opt_fuse_pointwise;
-        if (t == 6 && !fused) {
+        const NttPointwise pw{v[1], six ? nullptr : v[2], tab->zinv};
+        const bool fused = t == T - 1 && fuse;
+        if (t == T - 1 && !fused) {
             const uint64_t w = L.hi[g] - L.lo[g], count = n / L.m * w;
-            hipLaunchKernelGGL(group_pointwise_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, ctx->stream, v[0], v[1], v[2],
-                               tab->zinv, L.m, L.lo[g], w, count);
+            hipLaunchKernelGGL(group_pointwise_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, ctx->stream, v[0], v[1],
+                               six ? nullptr : v[2], tab->zinv, L.m, L.lo[g], w, count);
             ZK_HIP(hipGetLastError());
         }
-        ntt_run_share(ctx, v[seq[t].src], v[seq[t].dst], m.log_n, seq[t].inverse, seq[t].coset, fused ? &pw : nullptr, sh);
+        ntt_run_share(ctx, v[seq[t].src], v[seq[t].dst], m.log_n, seq[t].inverse, seq[t].coset, fused ? &pw : nullptr, sh, seq[t].last);
     }
-    S.h_bytes[g] = exchange(7, 3, S.h_rects);
+    S.h_bytes[g] = exchange(T, 3, S.h_rects);
     step_end();
     *h_out = v[3];
 }

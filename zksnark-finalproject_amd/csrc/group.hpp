@@ -59,7 +59,7 @@ class GroupBarrier {
 
 // One split witness map across the k witness-map ranks of a group call, shared by their threads.
 struct GroupSync {
-    static constexpr int EXCHANGES = 8;          // seven transforms' exchanges + the redistribution of h
+    static constexpr int EXCHANGES = 8;          // one per transform (six, or seven with wm_transforms = 7) + the redistribution of h
     GroupLayout L;
     std::vector<GroupRect> ex_rects, h_rects;
     std::vector<int> device;                     // per rank

@@ -1,4 +1,4 @@
-// BLS12-381 Fr radix-2 NTT for gfx950 — the seven transforms of the R1CS->QAP witness map
+// BLS12-381 Fr radix-2 NTT for gfx950 — the transforms of the R1CS->QAP witness map
 // (ark-poly 0.4.2 Radix2EvaluationDomain::{fft,ifft,coset_fft,coset_ifft}_in_place as driven by
 // ark-groth16 r1cs_to_qap.rs; reached from /root/reference/src/arkworks/backend/matrix_proof.rs:139-140).
 //
@@ -72,12 +72,14 @@ struct NttPassArgs {
     const Fr *pre;     // optional per-input-index multiplier (coset fft), else null
     // optional fused point-wise stage of the witness map on the FIRST pass's load (pre is null then):
     //   x[i] <- (in[i] * pw_b[i] - pw_c[i]) / Z   — ark-groth16 r1cs_to_qap.rs: ab = (a*b - c) * Z(g)^-1 before the coset ifft
+    //   pw_c null (six transforms, poly.hip): x[i] <- in[i] * pw_b[i], pw_b carrying 1/Z already (and the U-form 2^5: load_u)
     const Fr *pw_b, *pw_c;
     Fr pw_zinv;        // saturated kernels: 1/Z (Montgomery)
     FrU pw_zc;         // unsaturated kernels: 1/Z * 2^271 mod r, repacked (see load_u)
     const Fr *post;    // optional per-output-index multiplier (coset ifft), else null
     Fr post_const;     // used when post_const_on (plain ifft: N^-1)
     int post_const_on;
+    const Fr *sub;     // optional, last pass only: the store writes v - sub[k], canonical (six transforms: sub = out, NttLast::sub)
     int log_n, log_n1, log_n2;   // log_n = size of the w table (whole transform); this pass splits a 2^(log_n1+log_n2) sub-transform
     int inverse;
     // three-pass transforms (N > 2^22): passes 2 and 3 run batched over blockIdx.y = k0 on the rows of the outer split
@@ -101,8 +103,9 @@ __device__ __forceinline__ void vec_offset(NttPassArgs &a) {
     a.out += vo;
     if (a.pw_b) {
         a.pw_b += vo;
-        a.pw_c += vo;
+        if (a.pw_c) a.pw_c += vo;
     }
+    if (a.sub) a.sub += vo;
 }
 
 // the tile this block works on: the XCD-aware order (group > 1) applies within the tiles the launch covers
@@ -172,7 +175,10 @@ __global__ void __launch_bounds__(NTT_THREADS) ntt_pass_cols(NttPassArgs a) {
         const size_t gi = (size_t)i1 * n2 + col0 + c;
         Fr v = gld(in + gi);
         if (a.pre) v = fp_mul(v, gld(a.pre + gi));
-        else if (a.pw_b) v = fp_mul(fp_sub(fp_mul(v, gld(a.pw_b + gi)), gld(a.pw_c + gi)), a.pw_zinv);
+        else if (a.pw_b) {
+            v = fp_mul(v, gld(a.pw_b + gi));
+            if (a.pw_c) v = fp_mul(fp_sub(v, gld(a.pw_c + gi)), a.pw_zinv);
+        }
         lds_st(s_data, NTT_TILE, (c << a.log_n1) + i1, v);
     }
     __syncthreads();
@@ -212,7 +218,10 @@ __global__ void __launch_bounds__(NTT_THREADS) ntt_pass_rows(NttPassArgs a) {
             const size_t gi = (row0 + r) * n2 + i2;
             v = gld(in + gi);
             if (a.pre) v = fp_mul(v, gld(a.pre + gi));
-            else if (a.pw_b) v = fp_mul(fp_sub(fp_mul(v, gld(a.pw_b + gi)), gld(a.pw_c + gi)), a.pw_zinv);
+            else if (a.pw_b) {
+                v = fp_mul(v, gld(a.pw_b + gi));
+                if (a.pw_c) v = fp_mul(fp_sub(v, gld(a.pw_c + gi)), a.pw_zinv);
+            }
         }
         lds_st(s_data, NTT_TILE, t, v);
     }
@@ -225,6 +234,7 @@ __global__ void __launch_bounds__(NTT_THREADS) ntt_pass_rows(NttPassArgs a) {
         const size_t k = (size_t)blockIdx.y + (((row0 + r) + n1 * (size_t)k2) << a.out_stride_log);
         if (a.post) v = fp_mul(v, gld(a.post + k));
         else if (a.post_const_on) v = fp_mul(v, a.post_const);
+        if (a.sub) v = fp_sub(v, gld(a.sub + k));
         gst(a.out + k, v);
     }
 }
@@ -520,13 +530,17 @@ __device__ __forceinline__ void stage_twiddles_u(uint32_t *s_tw, int tw_stride, 
 // element load.  The stored (saturated Montgomery) limbs x 2^256 are used AS the U-form of x 2^-5: no conversion product.
 // The transform is linear, so every pass that loads this way leaves a factor 2^-5 behind, and the multiplier of the LAST
 // store carries 2^(5 * passes) (ntt_run).  The coset pre-multiply uses a table scaled by 2^10, which makes its one product a
-// full conversion (X 2^256 * g 2^10 2^256 * 2^-261 = x g 2^261).  Fused point-wise stage (x * b - c) / Z: X (*) B = xb 2^251,
-// C (*) 2^256 = c 2^251, their difference (+2r) times zc = 2^266 / Z is (xb - c)/Z * 2^256: like a plain load   ((*) = fru_mul).
+// full conversion (X 2^256 * g 2^10 2^256 * 2^-261 = x g 2^261).  Fused point-wise stage, six transforms (pw_c null, the
+// default): B's coset transform stored its output with 1/Z and 2^5 folded into its last-store constant (NttLast::pw_operand), i.e.
+// the integer B' = b/Z 2^261, so X (*) B' = x 2^256 * b/Z 2^261 * 2^-261 = (xb/Z) 2^256: like a plain load, with one product.
+// Seven transforms: X (*) B = xb 2^251, C (*) 2^256 = c 2^251, their difference (+2r) times zc = 2^266 / Z is (xb - c)/Z * 2^256:
+// like a plain load   ((*) = fru_mul).
 __device__ __forceinline__ FrU load_u(const NttPassArgs &a, const Fr *in, size_t gi) {
     const FrU x = fru_repack(gld(in + gi));
     if (a.pre) return fru_mul(x, fru_repack(gld(a.pre + gi)));
     if (a.pw_b) {
         const FrU xb = fru_mul(x, fru_repack(gld(a.pw_b + gi)));
+        if (!a.pw_c) return xb;
         const FrU c = fru_mul(fru_repack(gld(a.pw_c + gi)), fru_one_sat());
         return fru_mul(fru_sub_2r(xb, c), a.pw_zc);
     }
@@ -599,7 +613,9 @@ __global__ void __launch_bounds__(NTT_THREADS_U) ntt_pass_rows_u(NttPassArgs a) 
         if (row0 + r >= n1) continue;
         const FrU v = lds_ld_u(s_data, TILE, (r << a.log_n2) + bitrev(k2, a.log_n2));
         const size_t k = (size_t)blockIdx.y + (((row0 + r) + n1 * (size_t)k2) << a.out_stride_log);
-        gst(a.out + k, fru_mul_to_sat(v, a.post ? fru_repack(gld(a.post + k)) : post_c));
+        Fr res = fru_mul_to_sat(v, a.post ? fru_repack(gld(a.post + k)) : post_c);
+        if (a.sub) res = fp_sub(res, gld(a.sub + k));
+        gst(a.out + k, res);
     }
 }
 
@@ -694,7 +710,8 @@ static unsigned share_tiles(NttPassArgs &p, const unsigned t[4]) {
 // share (ntt_run_share): only a rank's tiles of each pass, and share->between() in between.
 // nvec > 1: that many transforms at once, vector v at data / tmp (and pw->b / pw->c) + v * vec_stride — every pass one launch
 // with grid.z = nvec (zkg16_prove_batch's witness map)
-static Fr *ntt_run_impl(zkg16_ctx *ctx, Fr *data, Fr *tmp, int log_n, bool inverse, bool coset, const NttPointwise *pw,
+// last (optional): a scale folded into the last store's constant, and / or the subtraction of what `tmp` holds (common.hpp).
+static Fr *ntt_run_impl(zkg16_ctx *ctx, Fr *data, Fr *tmp, int log_n, bool inverse, bool coset, const NttPointwise *pw, const NttLast *last,
                         const NttShare *share, unsigned nvec = 1, size_t vec_stride = 0) {
     bool &lds_attr_set = ctx->lds_attr_ntt;          // per ctx (= per device)
     if (!lds_attr_set) {   // 64-72 KiB tile + up to 36 KiB of twiddles, or a 144 KiB tile: above the 64 KiB default dynamic-LDS cap
@@ -762,6 +779,14 @@ static Fr *ntt_run_impl(zkg16_ctx *ctx, Fr *data, Fr *tmp, int log_n, bool inver
         a.post_const = post_const_on ? fp_mul(t->n_inv, back) : back;
         post_const_on = 1;                                  // the last store always multiplies (by 2^(5 deficit) at least)
     }
+    if (last && (last->scale || last->pw_operand)) {
+        if (post) throw HipError{hipErrorInvalidValue, "ntt: a scaled last store of a coset ifft", __FILE__, __LINE__};
+        Fr s = last->scale ? *last->scale : fr_from_u64_host(1);
+        if (last->pw_operand && uform) s = fp_mul(s, fr_from_u64_host(32));        // the 2^5 the one-product load expects (load_u)
+        a.post_const = post_const_on ? fp_mul(a.post_const, s) : s;
+        post_const_on = 1;
+    }
+    Fr *const sub = (last && last->sub) ? tmp : nullptr;
     if (pw) {
         if (pre) throw HipError{hipErrorInvalidValue, "ntt: point-wise fusion needs a transform without a coset pre-multiply", __FILE__, __LINE__};
         a.pw_zinv = pw->zinv;
@@ -811,6 +836,7 @@ static Fr *ntt_run_impl(zkg16_ctx *ctx, Fr *data, Fr *tmp, int log_n, bool inver
             p2.in = data; p2.out = tmp;
             p2.post = post;
             p2.post_const_on = post_const_on;
+            p2.sub = sub;
             const unsigned grid = share ? share_tiles(p2, share->rows) : (unsigned)((size_t)1 << a.log_n1);
             ScopedKernelTimer kt(ctx, "ntt_pass_rows", (double)n * nvec);
             const dim3 g(grid, 1, nvec);
@@ -828,6 +854,7 @@ static Fr *ntt_run_impl(zkg16_ctx *ctx, Fr *data, Fr *tmp, int log_n, bool inver
         first(a);
         a.post = post;
         a.post_const_on = post_const_on;
+        a.sub = sub;
         ScopedKernelTimer kt(ctx, "ntt_pass_rows", (double)n * nvec);
         hipLaunchKernelGGL(k_rows, dim3(1, 1, nvec), dim3(nthreads), lds_bytes(log_n), ctx->stream, a);
     } else {
@@ -863,6 +890,7 @@ static Fr *ntt_run_impl(zkg16_ctx *ctx, Fr *data, Fr *tmp, int log_n, bool inver
             p2.in = data; p2.out = tmp;
             p2.post = post;
             p2.post_const_on = post_const_on;
+            p2.sub = sub;
             p2.batch_stride = (size_t)1 << log_m;
             p2.out_stride_log = log_n0;
             const unsigned grid = share ? share_tiles(p2, share->rows) : (unsigned)(((size_t)1 << a.log_n1) >> (NTT_TILE_LOG - a.log_n2));
@@ -874,20 +902,22 @@ static Fr *ntt_run_impl(zkg16_ctx *ctx, Fr *data, Fr *tmp, int log_n, bool inver
     return tmp;
 }
 
-Fr *ntt_run(zkg16_ctx *ctx, Fr *data, Fr *tmp, int log_n, bool inverse, bool coset, const NttPointwise *pw) {
-    return ntt_run_impl(ctx, data, tmp, log_n, inverse, coset, pw, nullptr);
+Fr *ntt_run(zkg16_ctx *ctx, Fr *data, Fr *tmp, int log_n, bool inverse, bool coset, const NttPointwise *pw, const NttLast *last) {
+    return ntt_run_impl(ctx, data, tmp, log_n, inverse, coset, pw, last, nullptr);
 }
-Fr *ntt_run_batch(zkg16_ctx *ctx, Fr *data, Fr *tmp, int log_n, bool inverse, bool coset, const NttPointwise *pw, unsigned nvec, size_t vec_stride) {
-    return ntt_run_impl(ctx, data, tmp, log_n, inverse, coset, pw, nullptr, nvec, vec_stride);
+Fr *ntt_run_batch(zkg16_ctx *ctx, Fr *data, Fr *tmp, int log_n, bool inverse, bool coset, const NttPointwise *pw, unsigned nvec, size_t vec_stride,
+                  const NttLast *last) {
+    return ntt_run_impl(ctx, data, tmp, log_n, inverse, coset, pw, last, nullptr, nvec, vec_stride);
 }
 
 // A rank's share of one two-pass transform (split witness map, group.hip): the column pass over the tiles share->cols, then
 // share->between() (the exchange that completes the rank's rows), then the row pass over the tiles share->rows.  Only the
 // positions the rank owns become valid in `tmp`.  Single- and three-pass sizes have no share (an error).
-Fr *ntt_run_share(zkg16_ctx *ctx, Fr *data, Fr *tmp, int log_n, bool inverse, bool coset, const NttPointwise *pw, const NttShare &share) {
+Fr *ntt_run_share(zkg16_ctx *ctx, Fr *data, Fr *tmp, int log_n, bool inverse, bool coset, const NttPointwise *pw, const NttShare &share,
+                  const NttLast *last) {
     if (!ntt_two_pass_shape(log_n, ctx->opt_ntt_mode, nullptr, nullptr, nullptr))
         throw HipError{hipErrorInvalidValue, "ntt: a share of a transform that is not two-pass", __FILE__, __LINE__};
-    return ntt_run_impl(ctx, data, tmp, log_n, inverse, coset, pw, &share);
+    return ntt_run_impl(ctx, data, tmp, log_n, inverse, coset, pw, last, &share);
 }
 
 // The shape ntt_run gives a 2^log_n transform when it is two passes: N1 = 2^log_n1 columns-first, N2 = 2^log_n2, tiles of

@@ -72,13 +72,13 @@ __global__ void __launch_bounds__(256) spmv_kernel(SpmvArgs a) {
     gst_fr(a.out[m] + (size_t)blockIdx.z * a.out_stride + row, acc);
 }
 
-// ab[i] = (a[i]*b[i] - c[i]) * zinv
+// ab[i] = (a[i]*b[i] - c[i]) * zinv; c null (six transforms: b carries 1/Z, C is subtracted after the last transform): a[i]*b[i]
 __global__ void __launch_bounds__(256) pointwise_h_kernel(Fr *a, const Fr *b, const Fr *c, Fr zinv, size_t n) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     Fr x = fp_mul(gld_fr(a + i), gld_fr(b + i));
-    x = fp_sub(x, gld_fr(c + i));
-    gst_fr(a + i, fp_mul(x, zinv));
+    if (c) x = fp_mul(fp_sub(x, gld_fr(c + i)), zinv);
+    gst_fr(a + i, x);
 }
 
 __global__ void __launch_bounds__(256) fr_from_mont_kernel(const Fr *in, Fr *out, size_t n) {
@@ -464,53 +464,61 @@ void fr_from_mont_run(zkg16_ctx *ctx, const Fr *in, Fr *out, size_t n) {
     ZK_HIP(hipGetLastError());
 }
 
-// h = coset_ifft( (coset_fft(ifft a) * coset_fft(ifft b) - coset_fft(ifft c)) / Z ), N Montgomery coefficients.
-// The transforms ping-pong between each vector and the one scratch buffer (ifft: x -> tmp, coset fft: tmp -> x), and the
-// point-wise (ab - c)/Z rides on the load of the seventh transform: no device-to-device copy and no separate point-wise
-// pass (round 1 had both: 8 extra passes over N x 32 B per proof).  Result pointer = ctx->poly[3].
+// The transforms of the witness map on the SpMV's a, b, c (nvec vectors of N side by side, tmp the scratch) -> h (= tmp).  They
+// ping-pong between each vector and the one scratch buffer (ifft: x -> tmp, coset fft: tmp -> x), and the point-wise stage rides
+// on the load of the last transform: no device-to-device copy and no separate point-wise pass (round 1 had both).
+//   6 (default): h = coset_ifft(A_cos * B_cos / Z) - ifft(c) / Z, X_cos = coset_fft(ifft x).  coset_ifft is linear and undoes
+//     coset_fft, so this is arkworks' h below exactly, for any assignment: C needs only its inverse transform.  1/Z (and the U-form
+//     2^5) is folded into the last-store constant of B's coset fft, so the fused load is ONE product; 1/Z into that of c's ifft, and
+//     the last transform's store subtracts the ifft(c)/Z it finds in tmp (the thread that overwrites a position read it).
+//   7 (option wm_transforms = 7): ark-groth16's coset_ifft((A_cos * B_cos - C_cos) / Z).
+static Fr *wm_transforms(zkg16_ctx *ctx, int log_n, Fr *a, Fr *b, Fr *c, Fr *tmp, unsigned nvec) {
+    const size_t n = (size_t)1 << log_n;
+    auto run = [&](Fr *src, Fr *dst, bool inverse, bool coset, const NttPointwise *pw = nullptr, const NttLast *last = nullptr) {
+        return ntt_run_batch(ctx, src, dst, log_n, inverse, coset, pw, nvec, n, last);
+    };
+    NttTables *t = ntt_get_tables(ctx, log_n);
+    const bool fuse = ctx->opt_fuse_pointwise != 0;
+    run(a, tmp, true, false);
+    run(tmp, a, false, true);
+    if (ctx->opt_wm_transforms == 7) {
+        run(b, tmp, true, false);
+        run(tmp, b, false, true);
+        run(c, tmp, true, false);
+        run(tmp, c, false, true);
+        const NttPointwise pw{b, c, t->zinv};
+        if (fuse) return run(a, tmp, true, true, &pw);
+        pointwise_h_run(ctx, a, b, c, t->zinv, (size_t)nvec * n);      // element-wise: the K vectors are one array
+        return run(a, tmp, true, true);
+    }
+    const NttLast to_b{&t->zinv, fuse, false}, to_c{&t->zinv, false, false}, sub{nullptr, false, true};
+    run(b, tmp, true, false);
+    run(tmp, b, false, true, nullptr, &to_b);          // b <- B_cos / Z (x 2^5 in U-form when the product rides on a load)
+    run(c, tmp, true, false, nullptr, &to_c);          // tmp <- ifft(c) / Z
+    const NttPointwise pw{b, nullptr, t->zinv};
+    if (fuse) return run(a, tmp, true, true, &pw, &sub);
+    pointwise_h_run(ctx, a, b, nullptr, t->zinv, (size_t)nvec * n);
+    return run(a, tmp, true, true, nullptr, &sub);
+}
+
+// h of one assignment, N Montgomery coefficients.  Result pointer = ctx->poly[3].
 void witness_map_run(zkg16_ctx *ctx, R1csDev &m, const Fr *z, Fr **h_out) {
     const size_t n = (size_t)1 << m.log_n;
     for (int i = 0; i < 4; i++) ctx->poly[i].ensure(n * sizeof(Fr));
     Fr *a = ctx->poly[0].as<Fr>(), *b = ctx->poly[1].as<Fr>(), *c = ctx->poly[2].as<Fr>(), *tmp = ctx->poly[3].as<Fr>();
     spmv_run(ctx, m, z, a, b, c);
-    ntt_run(ctx, a, tmp, m.log_n, true, false);
-    ntt_run(ctx, tmp, a, m.log_n, false, true);
-    ntt_run(ctx, b, tmp, m.log_n, true, false);
-    ntt_run(ctx, tmp, b, m.log_n, false, true);
-    ntt_run(ctx, c, tmp, m.log_n, true, false);
-    ntt_run(ctx, tmp, c, m.log_n, false, true);
-    NttTables *t = ntt_get_tables(ctx, m.log_n);
-    if (ctx->opt_fuse_pointwise) {
-        const NttPointwise pw{b, c, t->zinv};
-        *h_out = ntt_run(ctx, a, tmp, m.log_n, true, true, &pw);
-    } else {
-        pointwise_h_run(ctx, a, b, c, t->zinv, n);
-        *h_out = ntt_run(ctx, a, tmp, m.log_n, true, true);
-    }
+    *h_out = wm_transforms(ctx, m.log_n, a, b, c, tmp, 1);
 }
 
 // The witness map of a batch: the K assignments at zs[0 .. K) (device-visible pointer table), every launch of witness_map_run
-// once over the K vectors — one SpMV, seven transform passes sequences with grid.z = K (shared tables, the fused (ab - c)/Z per
+// once over the K vectors — one SpMV, the transform passes with grid.z = K (shared tables, the fused point-wise stage per
 // vector).  a, b, c and the scratch hold K vectors of N side by side; *h_out = K h vectors of N, vector v at (*h_out) + v * N.
 void witness_map_run_batch(zkg16_ctx *ctx, R1csDev &m, const Fr *const *zs, unsigned nvec, Fr **h_out) {
     const size_t n = (size_t)1 << m.log_n;
     for (int i = 0; i < 4; i++) ctx->poly[i].ensure((size_t)nvec * n * sizeof(Fr));
     Fr *a = ctx->poly[0].as<Fr>(), *b = ctx->poly[1].as<Fr>(), *c = ctx->poly[2].as<Fr>(), *tmp = ctx->poly[3].as<Fr>();
     spmv_run(ctx, m, nullptr, a, b, c, nullptr, zs, nvec);
-    ntt_run_batch(ctx, a, tmp, m.log_n, true, false, nullptr, nvec, n);
-    ntt_run_batch(ctx, tmp, a, m.log_n, false, true, nullptr, nvec, n);
-    ntt_run_batch(ctx, b, tmp, m.log_n, true, false, nullptr, nvec, n);
-    ntt_run_batch(ctx, tmp, b, m.log_n, false, true, nullptr, nvec, n);
-    ntt_run_batch(ctx, c, tmp, m.log_n, true, false, nullptr, nvec, n);
-    ntt_run_batch(ctx, tmp, c, m.log_n, false, true, nullptr, nvec, n);
-    NttTables *t = ntt_get_tables(ctx, m.log_n);
-    if (ctx->opt_fuse_pointwise) {
-        const NttPointwise pw{b, c, t->zinv};
-        *h_out = ntt_run_batch(ctx, a, tmp, m.log_n, true, true, &pw, nvec, n);
-    } else {
-        pointwise_h_run(ctx, a, b, c, t->zinv, (size_t)nvec * n);      // element-wise: the K vectors are one array
-        *h_out = ntt_run_batch(ctx, a, tmp, m.log_n, true, true, nullptr, nvec, n);
-    }
+    *h_out = wm_transforms(ctx, m.log_n, a, b, c, tmp, nvec);
 }
 
 }  // namespace zk

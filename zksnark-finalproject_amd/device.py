@@ -307,7 +307,7 @@ class Device:
         return ms.value
 
     def bench_witness_map(self, r1cs_h, wit_h, iters=3):
-        """ms per stand-alone witness map (3 SpMV + 7 NTT + point-wise) on resident inputs."""
+        """ms per stand-alone witness map (3 SpMV + 6 NTT, 7 with option wm_transforms = 7) on resident inputs."""
         ms = C.c_float()
         self._check(self.lib.zkg16_bench_witness_map(self.ctx, r1cs_h, wit_h, iters, C.byref(ms)))
         return ms.value
