@@ -263,6 +263,45 @@ ZKG16_API int zkg16_fq_to_le_bytes(const uint64_t *limbs, size_t n, uint8_t *out
 ZKG16_API int zkg16_fq_from_le_bytes(const uint8_t *bytes, size_t n, uint64_t *out);
 ZKG16_API int zkg16_point_check(int group, const uint64_t *point, int *ok);
 
+/* ---- batched verification: k proofs under ONE prepared key, checked together.  With multipliers rho_k, all k proofs hold iff
+ *     FE( prod_k ML(rho_k A_k, B_k) * ML(sum_k rho_k X_k, -gamma) * ML(sum_k rho_k C_k, -delta) ) == e(alpha, beta)^(sum_k rho_k)
+ * (X_k = gamma_abc[0] + sum_i z_{k,i} gamma_abc[i]; ML the Miller loop, FE the final exponentiation) up to an error of 2^-128:
+ * one final exponentiation per batch instead of one per proof.  rho: k x 2 u64, 128-bit, plain integers, each non-zero.  THE
+ * CALLER DRAWS THEM (as r and s in the proving calls: this ABI draws nothing), and they must be unpredictable to whoever made the
+ * proofs — fresh output of a cryptographic generator per call; with predictable multipliers forged proofs can be made to cancel.
+ * public_inputs: k x (num_instance - 1) x 4 Montgomery limbs, proofs: k x 48, inf: k x 3, the key as for zkg16_verify_prepared.
+ * *ok = 1 iff every proof verifies.  ok_each (nullable, k bytes): the verdict zkg16_verify_prepared gives each proof alone — when
+ * the batch equation fails the bad proofs are found by bisecting over index ranges (one final exponentiation per range).
+ * k == 0, null pointers, n_coeffs != 68 and any rho_k == 0 (it would wave proof k through): ZKG16_ERR_BAD_ARG before any work,
+ * outputs untouched.
+ * zkg16_verify_batch_host: everything on up to `threads` host threads (0 = 8); no ctx, no GPU.
+ * zkg16_verify_batch: the per-proof work — the 3k membership tests, rho_k A_k, the k Miller loops on the unprepared B_k, their
+ * product — in kernels on a lane of the ctx (one GPU lane per proof), sum_k rho_k C_k by the ctx's G1 MSM; the two Miller loops on
+ * the key's coefficients, the final exponentiation and the bisecting stay on the host.  k above 65,536 runs in passes of that
+ * many.  Batches shorter than option "verify_batch_min" (default 1024: the smallest measured K at which the kernels beat the host
+ * form on eight threads, profiles/verify_batch_timing_r8.txt; 1 = always the kernels) are answered by the host form. */
+ZKG16_API int zkg16_verify_batch_host(const uint64_t *gamma_abc_g1, size_t num_instance, const uint64_t alpha_beta[72],
+                            const uint64_t *gamma_neg_coeffs, const uint64_t *delta_neg_coeffs, size_t n_coeffs,
+                            const uint64_t *public_inputs, const uint64_t *proofs, const uint8_t *inf, const uint64_t *rho, size_t k,
+                            int threads, int *ok, uint8_t *ok_each);
+ZKG16_API int zkg16_verify_batch(zkg16_ctx *ctx, const uint64_t *gamma_abc_g1, size_t num_instance, const uint64_t alpha_beta[72],
+                       const uint64_t *gamma_neg_coeffs, const uint64_t *delta_neg_coeffs, size_t n_coeffs,
+                       const uint64_t *public_inputs, const uint64_t *proofs, const uint8_t *inf, const uint64_t *rho, size_t k,
+                       int *ok, uint8_t *ok_each);
+/* Stage entries (tests / tools).  n Miller loops on the device, one GPU lane per pair: f_out[i] (72 u64, ark's tower order, the
+ * layout of alpha_beta) = the Miller value of (g1[i], g2[i]) with ark's line scaling, one for a pair with a point at infinity (flag
+ * bytes nullable); zkg16_final_exp of it is the pairing.  n membership tests on the device: ok_out[i] = what zkg16_point_check says
+ * of point i (the point at infinity passes).  zkg16_final_exp: the verifier's final exponentiation, host-only. */
+ZKG16_API int zkg16_miller_loop_batch(zkg16_ctx *ctx, const uint64_t *g1, const uint8_t *g1_inf, const uint64_t *g2, const uint8_t *g2_inf, size_t n,
+                            uint64_t *f_out);
+ZKG16_API int zkg16_point_check_batch(zkg16_ctx *ctx, int group, const uint64_t *points, const uint8_t *inf, size_t n, uint8_t *ok_out);
+ZKG16_API int zkg16_final_exp(const uint64_t f[72], uint64_t out[72]);
+/* The last zkg16_verify_batch on this ctx, in ms: [0] membership kernels (host clock: launch to the verdicts on the host, beside
+ * the Miller kernel), [1] scaling + Miller kernel (device events), [2] product tree, [3] the MSM
+ * sum rho_k C_k, [4] host coefficients and the batch equation, [5] bisecting, [6] total wall; [7] = 1 when the host form answered.
+ * Returns the number of entries written (at most cap). */
+ZKG16_API int zkg16_verify_batch_timings(zkg16_ctx *ctx, float *ms, int cap);
+
 /* prod_i e(P_i, Q_i) == 1 ?  Host-only (no ctx, no GPU).  g1: n x 12 limbs, g2: n x 24 limbs, flag bytes nullable.
  * flags: ZKG16_PAIRING_PLAIN_FINAL_EXP = final exponentiation as one plain power by (q^12-1)/r (slow cross-check of the
  * default Frobenius + |z|-chain path).  The building block of zkg16_verify; mirrors ark-ec's `Pairing::multi_pairing`

@@ -69,6 +69,12 @@ SIGNATURES = {
     "zkg16_pvk_prepare": (C.c_int, [u64p, u64p, u64p, u64p, u64p, u64p, u64p, C.POINTER(sz)]),
     "zkg16_verify_prepared": (C.c_int, [u64p, sz, vp, u64p, u64p, u64p, sz, u64p, u8p, C.POINTER(C.c_int)]),
     "zkg16_point_check": (C.c_int, [C.c_int, u64p, C.POINTER(C.c_int)]),
+    "zkg16_verify_batch_host": (C.c_int, [vp, sz, vp, vp, vp, sz, vp, vp, vp, vp, sz, C.c_int, C.POINTER(C.c_int), vp]),
+    "zkg16_verify_batch": (C.c_int, [ctxp, vp, sz, vp, vp, vp, sz, vp, vp, vp, vp, sz, C.POINTER(C.c_int), vp]),
+    "zkg16_miller_loop_batch": (C.c_int, [ctxp, vp, vp, vp, vp, sz, vp]),
+    "zkg16_point_check_batch": (C.c_int, [ctxp, C.c_int, vp, vp, sz, vp]),
+    "zkg16_final_exp": (C.c_int, [u64p, u64p]),
+    "zkg16_verify_batch_timings": (C.c_int, [ctxp, C.POINTER(C.c_float), C.c_int]),
     "zkg16_g1_decompress": (C.c_int, [vp, sz, vp, vp, C.c_int, C.POINTER(C.c_int)]),
     "zkg16_g2_decompress": (C.c_int, [vp, sz, vp, vp, C.c_int, C.POINTER(C.c_int)]),
     "zkg16_points_compress": (C.c_int, [C.c_int, vp, vp, sz, vp]),

@@ -85,7 +85,7 @@ void copy_options(zkg16_ctx *dst, const zkg16_ctx *src) {
     dst->opt_ntt_radix = src->opt_ntt_radix; dst->opt_ntt_xcd = src->opt_ntt_xcd; dst->opt_acc_debug = src->opt_acc_debug;
     dst->opt_sort_mode = src->opt_sort_mode; dst->opt_acc_pipeline = src->opt_acc_pipeline; dst->opt_fuse_pointwise = src->opt_fuse_pointwise;
     dst->opt_matrix_parts = src->opt_matrix_parts; dst->opt_g2_lazy = src->opt_g2_lazy; dst->opt_g1_inline = src->opt_g1_inline; dst->opt_fixed_base_bits = src->opt_fixed_base_bits;
-    dst->opt_collect_threads = src->opt_collect_threads; dst->opt_batch_max = src->opt_batch_max; dst->opt_wm_transforms = src->opt_wm_transforms;
+    dst->opt_collect_threads = src->opt_collect_threads; dst->opt_batch_max = src->opt_batch_max; dst->opt_verify_batch_min = src->opt_verify_batch_min; dst->opt_wm_transforms = src->opt_wm_transforms;
     dst->kernel_timing = src->kernel_timing; dst->kernel_timing_accumulate_only = src->kernel_timing_accumulate_only;
 }
 void create_streams(zkg16_ctx *ctx) {
@@ -1166,6 +1166,11 @@ int set_option_one(zkg16_ctx *ctx, const char *name, int64_t value) {
     if (!strcmp(name, "batch_max")) {          // zkg16_prove_batch: proofs per device pass, 0 = as many as fit (free HBM, 2^31 terms per list)
         if (value < 0 || value > 65535) return ZKG16_ERR_BAD_ARG;
         ctx->opt_batch_max = (int)value;
+        return ZKG16_OK;
+    }
+    if (!strcmp(name, "verify_batch_min")) {   // zkg16_verify_batch: batches shorter than this go to the host form (0 restores the default; 1 = always the device)
+        if (value < 0 || value > (1 << 30)) return ZKG16_ERR_BAD_ARG;
+        ctx->opt_verify_batch_min = value == 0 ? ZKG16_VERIFY_BATCH_MIN_DEFAULT : (int)value;
         return ZKG16_OK;
     }
     if (!strcmp(name, "reduce_chunk")) {
@@ -2546,6 +2551,183 @@ int zkg16_prove_group(zkg16_group *group, const uint64_t *pk_handles, const uint
     sum_partials(sum, rec.data(), rinf.data(), n);
     prove_tail(*pk[blinding], rr, ss, sum, proof_out, inf_out);
     return ZKG16_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------ batched verification
+// (verify_batch.hpp.)  The per-proof work in kernels on a lane of the ctx: the three membership launches and the Miller launch of a
+// pass are independent and run on four of the lane's streams at once; the host needs the membership verdicts first (they decide
+// which C_k enter the MSM), so the MSM of sum rho_k C_k runs on the lane's main stream while the Miller kernel is still busy.
+#include "verify_batch.hpp"
+
+namespace {
+const size_t VB_PASS = 65536;          // pairs / points per launch: one wave per SIMD of a 256-CU device
+struct VbEvents {
+    hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    VbEvents() { for (auto &e : ev) ZK_HIP(hipEventCreate(&e)); }
+    ~VbEvents() { for (auto &e : ev) if (e) (void)hipEventDestroy(e); }
+    VbEvents(const VbEvents &) = delete;
+    VbEvents &operator=(const VbEvents &) = delete;
+};
+float vb_elapsed(hipEvent_t a, hipEvent_t b) {
+    float ms = 0;
+    ZK_HIP(hipEventElapsedTime(&ms, a, b));
+    return ms;
+}
+void vb_publish(zkg16_ctx *root, const float tm[8]) {
+    std::lock_guard<std::mutex> lk(root->lane_mu);
+    memcpy(root->vb_timings, tm, sizeof root->vb_timings);
+}
+}  // namespace
+
+extern "C" {
+
+int zkg16_verify_batch(zkg16_ctx *ctx, const uint64_t *gamma_abc_g1, size_t num_instance, const uint64_t alpha_beta[72], const uint64_t *gamma_neg_coeffs,
+                       const uint64_t *delta_neg_coeffs, size_t n_coeffs, const uint64_t *public_inputs, const uint64_t *proofs, const uint8_t *inf,
+                       const uint64_t *rho, size_t k, int *ok, uint8_t *ok_each) {
+    if (!ctx) return ZKG16_ERR_BAD_ARG;
+    const VbKey key{gamma_abc_g1, num_instance, alpha_beta, gamma_neg_coeffs, delta_neg_coeffs, n_coeffs};
+    const VbBatch b{public_inputs, proofs, inf, rho, k};
+    const int rc = vb_check_args(key, b, ok);
+    if (rc != ZKG16_OK) return rc;
+    const double t_all = now_ms();
+    float tm[8] = {0};
+    if (k < (size_t)ctx->opt_verify_batch_min) {
+        try {
+            vb_host(key, b, 0, ok, ok_each);
+        } catch (const std::bad_alloc &) {
+            return ZKG16_ERR_OOM;
+        }
+        tm[6] = (float)(now_ms() - t_all);
+        tm[7] = 1;
+        vb_publish(ctx, tm);
+        return ZKG16_OK;
+    }
+    ZK_LANE_BEGIN(ctx)
+    hipStream_t s_main = ctx->stream, s_mil = ctx->wm_stream, s_c = ctx->slots[1].stream, s_b = ctx->slots[2].stream;
+    VbEvents evs;
+    hipEvent_t e_up = evs.ev[0], e_a = evs.ev[1], e_c = evs.ev[2], e_b = evs.ev[3], e_mil = evs.ev[4], e_p0 = evs.ev[5], e_p1 = evs.ev[6], e_m0 = evs.ev[7];
+    const size_t half = (k + 1) / 2;
+    DevBuf d_proofs(k * 48 * 8), d_inf(3 * k), d_rho(k * 16), d_mem3(3 * k), d_live(k), d_f(k * 72 * 8), d_tmp(2 * half * 72 * 8);
+    upload_h2d(ctx, d_proofs.p, proofs, k * 48 * 8);
+    ZK_HIP(hipMemcpyAsync(d_inf.p, inf, 3 * k, hipMemcpyHostToDevice, s_main));
+    ZK_HIP(hipMemcpyAsync(d_rho.p, rho, k * 16, hipMemcpyHostToDevice, s_main));
+    ZK_HIP(hipEventRecord(e_up, s_main));
+    for (hipStream_t st : {s_mil, s_c, s_b}) ZK_HIP(hipStreamWaitEvent(st, e_up, 0));
+    ZK_HIP(hipEventRecord(e_m0, s_mil));
+    const VbEndo en = vb_endo();
+    for (size_t off = 0; off < k; off += VB_PASS) {
+        const size_t n = std::min(VB_PASS, k - off);
+        const uint64_t *pts = d_proofs.as<uint64_t>() + 48 * off;
+        const uint8_t *fl = d_inf.as<uint8_t>() + 3 * off;
+        uint8_t *m3 = d_mem3.as<uint8_t>() + 3 * off;
+        // membership first: where two of these streams share a hardware queue, the short kernels must not sit behind the long one
+        vb_membership_launch(s_main, 1, pts, 48, fl, 3, n, en, m3, 3);
+        vb_membership_launch(s_c, 1, pts + 36, 48, fl + 2, 3, n, en, m3 + 2, 3);
+        vb_membership_launch(s_b, 2, pts + 12, 48, fl + 1, 3, n, en, m3 + 1, 3);
+        vb_miller_launch(s_mil, pts, 48, fl, pts + 12, 48, fl + 1, 3, d_rho.as<uint64_t>() + 2 * off, n, d_f.as<uint64_t>() + 72 * off);
+    }
+    const double t_launched = now_ms();
+    ZK_HIP(hipEventRecord(e_a, s_main));
+    ZK_HIP(hipEventRecord(e_c, s_c));
+    ZK_HIP(hipEventRecord(e_b, s_b));
+    ZK_HIP(hipEventRecord(e_mil, s_mil));
+    ZK_HIP(hipStreamWaitEvent(s_main, e_c, 0));
+    ZK_HIP(hipStreamWaitEvent(s_main, e_b, 0));
+    std::vector<uint8_t> mem3(3 * k), member(k);
+    ZK_HIP(hipMemcpyAsync(mem3.data(), d_mem3.p, 3 * k, hipMemcpyDeviceToHost, s_main));
+    ZK_HIP(hipStreamSynchronize(s_main));
+    // host clock, launch to verdicts on the host (what the MSM below waits for), not kernel time: measured, it equals the Miller
+    // kernel's time — the verdicts do not reach the host before that kernel ends
+    tm[0] = (float)(now_ms() - t_launched);
+    size_t n_live = 0;
+    for (size_t i = 0; i < k; i++) n_live += member[i] = mem3[3 * i] && mem3[3 * i + 1] && mem3[3 * i + 2] ? 1 : 0;
+    // sum rho_k C_k over the member proofs: the ctx's G1 MSM, beside the Miller kernel
+    uint64_t sum_c[12] = {0};
+    uint8_t sum_c_inf = 1;
+    if (n_live) {
+        const double t0 = now_ms();
+        std::vector<uint64_t> bases(12 * k), sc(4 * k, 0);
+        std::vector<uint8_t> binf(k);
+        for (size_t i = 0; i < k; i++) {
+            memcpy(&bases[12 * i], proofs + 48 * i + 36, 96);
+            binf[i] = inf[3 * i + 2] || !member[i] ? 1 : 0;
+            if (member[i]) { sc[4 * i] = rho[2 * i]; sc[4 * i + 1] = rho[2 * i + 1]; }
+        }
+        DevBuf d_bases(k * sizeof(G1AffineU)), d_sc(k * sizeof(Fr));
+        upload_points<G1Affine>(ctx, d_bases.as<G1AffineU>(), bases.data(), binf.data(), 0, k);
+        ZK_HIP(hipMemcpyAsync(d_sc.p, sc.data(), k * sizeof(Fr), hipMemcpyHostToDevice, s_main));
+        ZK_HIP(hipStreamSynchronize(s_main));
+        MsmPlan plan;
+        msm_plan_build(ctx, ctx->ws_h, d_sc.as<Fr>(), k, plan);
+        const G1XYZZ total = msm_g1_exec(ctx, ctx->ws_h, plan, d_bases.as<G1AffineU>(), "verify_batch_msm");
+        point_to_abi(xyzz_to_affine(total), sum_c, &sum_c_inf);
+        tm[3] = (float)(now_ms() - t0);
+    }
+    // the product of the member proofs' Miller values
+    ZK_HIP(hipMemcpyAsync(d_live.p, member.data(), k, hipMemcpyHostToDevice, s_main));
+    ZK_HIP(hipStreamWaitEvent(s_main, e_mil, 0));
+    ZK_HIP(hipEventRecord(e_p0, s_main));
+    const uint64_t *d_prod = vb_product_launch(s_main, d_f.as<uint64_t>(), d_live.as<uint8_t>(), k, d_tmp.as<uint64_t>());
+    ZK_HIP(hipEventRecord(e_p1, s_main));
+    uint64_t prod[72];
+    ZK_HIP(hipMemcpyAsync(prod, d_prod, sizeof prod, hipMemcpyDeviceToHost, s_main));
+    ZK_HIP(hipStreamSynchronize(s_main));
+    tm[1] = vb_elapsed(e_m0, e_mil);      // both on the Miller stream
+    tm[2] = vb_elapsed(e_p0, e_p1);
+    // the K Miller values leave the device only when the batch equation failed and the caller wants to know where
+    std::vector<uint64_t> miller;
+    vb_decide(key, b, member.data(), [&]() -> const uint64_t * {
+        miller.resize(72 * k);
+        ZK_HIP(hipMemcpy(miller.data(), d_f.p, k * 72 * 8, hipMemcpyDeviceToHost));
+        return miller.data();
+    }, prod, sum_c, &sum_c_inf, 0, ok, ok_each, tm + 4);
+    tm[6] = (float)(now_ms() - t_all);
+    vb_publish(root, tm);
+    ZK_LANE_END(ctx)
+}
+
+int zkg16_miller_loop_batch(zkg16_ctx *ctx, const uint64_t *g1, const uint8_t *g1_inf, const uint64_t *g2, const uint8_t *g2_inf, size_t n, uint64_t *f_out) {
+    if (!ctx || ((!g1 || !g2 || !f_out) && n)) return ZKG16_ERR_BAD_ARG;
+    if (!n) return ZKG16_OK;
+    ZK_LANE_BEGIN(ctx)
+    DevBuf d_g1(n * 96), d_g2(n * 192), d_i1(n), d_i2(n), d_f(n * 576);
+    upload_h2d(ctx, d_g1.p, g1, n * 96);
+    upload_h2d(ctx, d_g2.p, g2, n * 192);
+    if (g1_inf) ZK_HIP(hipMemcpyAsync(d_i1.p, g1_inf, n, hipMemcpyHostToDevice, ctx->stream));
+    if (g2_inf) ZK_HIP(hipMemcpyAsync(d_i2.p, g2_inf, n, hipMemcpyHostToDevice, ctx->stream));
+    for (size_t off = 0; off < n; off += VB_PASS)
+        vb_miller_launch(ctx->stream, d_g1.as<uint64_t>() + 12 * off, 12, g1_inf ? d_i1.as<uint8_t>() + off : nullptr, d_g2.as<uint64_t>() + 24 * off, 24,
+                         g2_inf ? d_i2.as<uint8_t>() + off : nullptr, 1, nullptr, std::min(VB_PASS, n - off), d_f.as<uint64_t>() + 72 * off);
+    ZK_HIP(hipMemcpyAsync(f_out, d_f.p, n * 576, hipMemcpyDeviceToHost, ctx->stream));
+    ZK_HIP(hipStreamSynchronize(ctx->stream));
+    ZK_LANE_END(ctx)
+}
+
+int zkg16_point_check_batch(zkg16_ctx *ctx, int group, const uint64_t *points, const uint8_t *inf, size_t n, uint8_t *ok_out) {
+    if (!ctx || (group != 1 && group != 2) || ((!points || !ok_out) && n)) return ZKG16_ERR_BAD_ARG;
+    if (!n) return ZKG16_OK;
+    ZK_LANE_BEGIN(ctx)
+    const size_t w = group == 1 ? 12 : 24;
+    DevBuf d_p(n * w * 8), d_i(n), d_ok(n);
+    upload_h2d(ctx, d_p.p, points, n * w * 8);
+    if (inf) ZK_HIP(hipMemcpyAsync(d_i.p, inf, n, hipMemcpyHostToDevice, ctx->stream));
+    const VbEndo en = vb_endo();
+    for (size_t off = 0; off < n; off += VB_PASS)
+        vb_membership_launch(ctx->stream, group, d_p.as<uint64_t>() + w * off, w, inf ? d_i.as<uint8_t>() + off : nullptr, 1, std::min(VB_PASS, n - off), en,
+                             d_ok.as<uint8_t>() + off, 1);
+    ZK_HIP(hipMemcpyAsync(ok_out, d_ok.p, n, hipMemcpyDeviceToHost, ctx->stream));
+    ZK_HIP(hipStreamSynchronize(ctx->stream));
+    ZK_LANE_END(ctx)
+}
+
+int zkg16_verify_batch_timings(zkg16_ctx *ctx, float *ms, int cap) {
+    if (!ctx || !ms || cap < 0) return ZKG16_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lk(ctx->lane_mu);
+    const int n = cap < 8 ? cap : 8;
+    memcpy(ms, ctx->vb_timings, n * sizeof(float));
+    return n;
 }
 
 }  // extern "C"

@@ -234,6 +234,10 @@ struct MsmWorkspace {       // grown on demand, reused across proofs
 
 }  // namespace zk
 
+// zkg16_verify_batch answers batches shorter than this on the host: the smallest measured K at which the device form beat the host
+// form on eight threads (profiles/verify_batch_timing_r8.txt)
+#define ZKG16_VERIFY_BATCH_MIN_DEFAULT 1024
+
 struct zkg16_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -304,6 +308,8 @@ struct zkg16_ctx {
     int opt_fuse_pointwise = 1;                       // the point-wise product on the load of the last transform (0: its own pass)
     int opt_wm_transforms = 6;                        // witness map: 6 (default) = C only inverse-transformed, subtracted on the last store; 7 = arkworks' sequence
     int opt_batch_max = 0;                            // zkg16_prove_batch: proofs per device pass (0 = as many as fit)
+    int opt_verify_batch_min = ZKG16_VERIFY_BATCH_MIN_DEFAULT;                   // zkg16_verify_batch: shorter batches are answered by the host form (the measured crossover)
+    float vb_timings[8] = {0};                        // zkg16_verify_batch_timings (root: the last batch verified on any lane)
     int num_cus = 256;
     bool lds_attr_fixup[2] = {false, false}, lds_attr_ntt = false;      // hipFuncSetAttribute(max dynamic LDS) done on this device
     zk::FixedBaseCache fb_g1, fb_g2;

@@ -851,3 +851,258 @@ int zkg16_point_check(int group, const uint64_t *point, int *ok) {
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------------------------------------ batched verification
+// verify_batch.hpp states the equation.  Here: its host side — the coefficients, the two Miller loops on the key's prepared lines,
+// e(alpha, beta)^(sum rho), the one final exponentiation, the bisecting that names the bad proofs — and the host form of the
+// per-proof part (membership, rho_k A_k, the Miller loop on B_k) on threads.
+#include <chrono>
+
+#include "verify_batch.hpp"
+
+namespace {
+using HPt = pf::Pt<pf::Fq64>;
+
+double vb_now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+// fn(lo, hi) over [0, n) on up to `threads` threads (0 = 8), at least min_per items each; a thread that cannot be started runs inline
+template <class Fn>
+void vb_parallel(size_t n, int threads, size_t min_per, Fn fn) {
+    size_t nt = threads <= 0 ? 8 : (size_t)threads;
+    if (min_per && n / min_per < nt) nt = n / min_per;
+    if (nt <= 1) { if (n) fn((size_t)0, n); return; }
+    struct Joiner {
+        std::vector<std::thread> th;
+        ~Joiner() { for (auto &t : th) if (t.joinable()) t.join(); }
+    } tg;
+    const size_t per = (n + nt - 1) / nt;
+    for (size_t t = 0; t < nt; t++) {
+        const size_t lo = t * per, hi = std::min(n, lo + per);
+        if (lo >= hi) break;
+        auto job = [lo, hi, &fn] { fn(lo, hi); };
+        try {
+            tg.th.emplace_back(job);
+        } catch (const std::system_error &) {
+            job();
+        }
+    }
+}
+Fr vb_rho_mont(const uint64_t *rho) {
+    Fr c = Fr::zero();
+    memcpy(c.l, rho, 16);
+    return fp_to_mont(c);
+}
+bool vb_affine(const HPt &p, pf::Fq64 &x, pf::Fq64 &y) {
+    if (p.inf) return false;
+    const pf::Fq64 inv = zk::h64::inv(zk::h64::mul(p.zz, p.zzz));
+    x = zk::h64::mul(p.x, zk::h64::mul(inv, p.zzz));
+    y = zk::h64::mul(p.y, zk::h64::mul(inv, p.zz));
+    return true;
+}
+HPt vb_g1(const uint64_t *l, int inf) {
+    const G1Affine p = load_pt<G1Affine>(l, inf);
+    return p.is_inf() ? pf::pt_inf<pf::Fq64>() : pf::g1_pt(p);
+}
+pf::F12 vb_f12(const uint64_t *in) { return pf::from_flat(fq12_from_abi(in)); }
+// a^e for a in the cyclotomic subgroup (e(alpha, beta) is), e canonical
+pf::F12 vb_pow(const pf::F12 &a, const Fr &e) {
+    pf::F12 acc = pf::f12_one();
+    bool started = false;
+    for (int i = 255; i >= 0; i--) {
+        if (started) acc = pf::cyclotomic_sqr(acc);
+        if ((e.l[i / 32] >> (i % 32)) & 1) { acc = started ? pf::mul(acc, a) : a; started = true; }
+    }
+    return acc;
+}
+
+struct VbDecider {
+    const zk::VbKey &key;
+    const zk::VbBatch &b;
+    int threads;
+    std::vector<uint32_t> live;             // the proofs that passed membership, ascending
+    const uint64_t *miller = nullptr;       // k x 72, by proof index
+    std::vector<HPt> d;                     // rho_k C_k by position in `live` (made when first needed)
+    pf::Prepared gp, dp;
+    pf::F12 ab;
+    VbDecider(const zk::VbKey &k, const zk::VbBatch &bb, int th) : key(k), b(bb), threads(th) {
+        gp = prepared_from_abi_fast(key.gamma_neg_coeffs, key.n_coeffs);
+        dp = prepared_from_abi_fast(key.delta_neg_coeffs, key.n_coeffs);
+        ab = vb_f12(key.alpha_beta);
+    }
+    void ensure_d() {
+        if (d.size() == live.size()) return;
+        d.resize(live.size());
+        vb_parallel(live.size(), threads, 8, [&](size_t lo, size_t hi) {
+            for (size_t p = lo; p < hi; p++) {
+                const size_t k = live[p];
+                d[p] = pf::pt_mul(vb_g1(b.proofs + 48 * k + 36, b.inf[3 * k + 2]), b.rho + 2 * k, 2);
+            }
+        });
+    }
+    // does the batch equation hold for the proofs live[lo .. hi)?  prod / sum_c: that range's product of Miller values / sum of rho_k C_k
+    // where the caller has them
+    bool range_holds(size_t lo, size_t hi, const pf::F12 *prod, const HPt *sum_c) {
+        const size_t ni = key.num_instance, n = hi - lo;
+        // s_0 = sum rho_k, s_i = sum rho_k z_{k,i}: per-thread partial sums
+        const size_t parts = 8;
+        std::vector<Fr> part(parts * ni, Fr::zero());
+        std::vector<pf::F12> fpart(parts, pf::f12_one());
+        std::vector<HPt> cpart(parts, pf::pt_inf<pf::Fq64>());
+        if (!sum_c) ensure_d();
+        const size_t per = (n + parts - 1) / parts;
+        vb_parallel(parts, n >= 64 ? threads : 1, 1, [&](size_t plo, size_t phi) {
+            for (size_t t = plo; t < phi; t++) {
+                Fr *s = part.data() + t * ni;
+                for (size_t p = lo + t * per; p < std::min(hi, lo + (t + 1) * per); p++) {
+                    const size_t k = live[p];
+                    const Fr r = vb_rho_mont(b.rho + 2 * k);
+                    s[0] = fp_add(s[0], r);
+                    for (size_t i = 1; i < ni; i++) {
+                        Fr z;
+                        memcpy(&z, b.public_inputs + 4 * (k * (ni - 1) + (i - 1)), sizeof z);
+                        s[i] = fp_add(s[i], fp_mul(r, z));
+                    }
+                    if (!prod) fpart[t] = pf::mul(fpart[t], vb_f12(miller + 72 * k));
+                    if (!sum_c) cpart[t] = pf::pt_add(cpart[t], d[p]);
+                }
+            }
+        });
+        std::vector<Fr> s(ni, Fr::zero());
+        pf::F12 f = prod ? *prod : pf::f12_one();
+        HPt c = sum_c ? *sum_c : pf::pt_inf<pf::Fq64>();
+        for (size_t t = 0; t < parts; t++) {
+            for (size_t i = 0; i < ni; i++) s[i] = fp_add(s[i], part[t * ni + i]);
+            if (!prod) f = pf::mul(f, fpart[t]);
+            if (!sum_c) c = pf::pt_add(c, cpart[t]);
+        }
+        // sum_k rho_k X_k = sum_i s_i gamma_abc[i]
+        HPt x = pf::pt_inf<pf::Fq64>();
+        for (size_t i = 0; i < ni; i++) {
+            const Fr sc = fp_from_mont(s[i]);
+            uint64_t e[4];
+            memcpy(e, sc.l, sizeof e);
+            x = pf::pt_add(x, pf::pt_mul(vb_g1(key.gamma_abc_g1 + 12 * i, 0), e, 4));
+        }
+        std::vector<pf::PairIn> in;
+        pf::Fq64 xx, xy, cx, cy;
+        if (vb_affine(x, xx, xy)) in.push_back(pf::PairIn{xx, xy, &gp});
+        if (vb_affine(c, cx, cy)) in.push_back(pf::PairIn{cx, cy, &dp});
+        if (!in.empty()) f = pf::mul(f, pf::miller_loop(in));
+        return pf::eq(pf::final_exp(f), vb_pow(ab, fp_from_mont(s[0])));
+    }
+    // live[lo .. hi) is known to fail: mark the proofs that make it fail
+    void find_bad(size_t lo, size_t hi, uint8_t *ok_each) {
+        if (hi - lo == 1) { ok_each[live[lo]] = 0; return; }
+        const size_t mid = lo + (hi - lo) / 2;
+        const bool left = range_holds(lo, mid, nullptr, nullptr);
+        if (!left) find_bad(lo, mid, ok_each);
+        if (left || !range_holds(mid, hi, nullptr, nullptr)) find_bad(mid, hi, ok_each);
+    }
+};
+}  // namespace
+
+namespace zk {
+
+int vb_check_args(const VbKey &key, const VbBatch &b, const int *ok) {
+    if (!key.gamma_abc_g1 || key.num_instance == 0 || !key.alpha_beta || !key.gamma_neg_coeffs || !key.delta_neg_coeffs || key.n_coeffs != ELL_COUNT)
+        return ZKG16_ERR_BAD_ARG;
+    if (b.k == 0 || !b.proofs || !b.inf || !b.rho || (!b.public_inputs && key.num_instance > 1) || !ok) return ZKG16_ERR_BAD_ARG;
+    for (size_t k = 0; k < b.k; k++)
+        if (!(b.rho[2 * k] | b.rho[2 * k + 1])) return ZKG16_ERR_BAD_ARG;       // a zero multiplier would wave proof k through
+    return ZKG16_OK;
+}
+
+VbEndo vb_endo() {
+    const pf::Endo &en = pf::endo();
+    VbEndo e;
+    e.beta = en.beta.to();
+    e.cx = pf::to_sat(en.cx);
+    e.cy = pf::to_sat(en.cy);
+    e.fast_g1 = en.fast_g1 ? 1 : 0;
+    e.fast_g2 = en.fast_g2 ? 1 : 0;
+    return e;
+}
+
+void vb_decide(const VbKey &key, const VbBatch &b, const uint8_t *member, const std::function<const uint64_t *()> &fetch_miller, const uint64_t *prod,
+               const uint64_t *sum_c, const uint8_t *sum_c_inf, int threads, int *ok, uint8_t *ok_each, float ms[2]) {
+    const double t0 = vb_now_ms();
+    VbDecider dc(key, b, threads);
+    for (size_t k = 0; k < b.k; k++)
+        if (member[k]) dc.live.push_back((uint32_t)k);
+    if (!prod) dc.miller = fetch_miller();
+    const pf::F12 fprod = prod ? vb_f12(prod) : pf::f12_one();
+    const HPt csum = sum_c ? vb_g1(sum_c, sum_c_inf && *sum_c_inf) : pf::pt_inf<pf::Fq64>();
+    const bool holds = dc.range_holds(0, dc.live.size(), prod ? &fprod : nullptr, sum_c ? &csum : nullptr);
+    const double t1 = vb_now_ms();
+    if (ms) ms[0] += (float)(t1 - t0);
+    *ok = holds && dc.live.size() == b.k ? 1 : 0;
+    if (!ok_each) return;
+    for (size_t k = 0; k < b.k; k++) ok_each[k] = member[k] ? 1 : 0;
+    if (!holds) {
+        if (dc.live.size() == 1) ok_each[dc.live[0]] = 0;
+        else {
+            if (!dc.miller) dc.miller = fetch_miller();
+            dc.find_bad(0, dc.live.size(), ok_each);
+        }
+        if (ms) ms[1] += (float)(vb_now_ms() - t1);
+    }
+}
+
+void vb_host(const VbKey &key, const VbBatch &b, int threads, int *ok, uint8_t *ok_each) {
+    (void)pf::endo();                // the function-local statics exist before any helper thread asks for them
+    (void)pf::consts();
+    (void)pf::frob_coeffs();
+    std::vector<uint8_t> member(b.k);
+    std::vector<uint64_t> miller(72 * b.k);
+    std::atomic<int> oom{0};
+    vb_parallel(b.k, threads, 1, [&](size_t lo, size_t hi) {
+        try {
+            for (size_t k = lo; k < hi; k++) {
+                const uint64_t *pr = b.proofs + 48 * k;
+                const G1Affine A = load_pt<G1Affine>(pr, b.inf[3 * k]), C = load_pt<G1Affine>(pr + 36, b.inf[3 * k + 2]);
+                const G2Affine B = load_pt<G2Affine>(pr + 12, b.inf[3 * k + 1]);
+                member[k] = g1_valid(A) && g2_valid(B) && g1_valid(C) ? 1 : 0;
+                pf::F12 f = pf::f12_one();
+                pf::Fq64 ax, ay;
+                if (member[k] && !A.is_inf() && !B.is_inf() && vb_affine(pf::pt_mul(pf::g1_pt(A), b.rho + 2 * k, 2), ax, ay)) {
+                    const pf::Prepared bp = pf::prepare(B);
+                    f = pf::miller_loop({pf::PairIn{ax, ay, &bp}});
+                }
+                fq12_to_abi(pf::to_flat(f), miller.data() + 72 * k);
+            }
+        } catch (const std::bad_alloc &) {
+            oom = 1;
+        }
+    });
+    if (oom.load()) throw std::bad_alloc();
+    vb_decide(key, b, member.data(), [&] { return (const uint64_t *)miller.data(); }, nullptr, nullptr, nullptr, threads, ok, ok_each, nullptr);
+}
+
+}  // namespace zk
+
+extern "C" {
+
+int zkg16_verify_batch_host(const uint64_t *gamma_abc_g1, size_t num_instance, const uint64_t alpha_beta[72], const uint64_t *gamma_neg_coeffs,
+                            const uint64_t *delta_neg_coeffs, size_t n_coeffs, const uint64_t *public_inputs, const uint64_t *proofs, const uint8_t *inf,
+                            const uint64_t *rho, size_t k, int threads, int *ok, uint8_t *ok_each) {
+    const zk::VbKey key{gamma_abc_g1, num_instance, alpha_beta, gamma_neg_coeffs, delta_neg_coeffs, n_coeffs};
+    const zk::VbBatch b{public_inputs, proofs, inf, rho, k};
+    if (threads < 0) return ZKG16_ERR_BAD_ARG;
+    const int rc = zk::vb_check_args(key, b, ok);
+    if (rc != ZKG16_OK) return rc;
+    try {
+        zk::vb_host(key, b, threads, ok, ok_each);
+    } catch (const std::bad_alloc &) {
+        return ZKG16_ERR_OOM;
+    }
+    return ZKG16_OK;
+}
+
+// the final exponentiation of the verifier (f^(3 (q^12 - 1)/r), pairing_fast.inc) of one Fq12 value in the ABI's tower order
+int zkg16_final_exp(const uint64_t f[72], uint64_t out[72]) {
+    if (!f || !out) return ZKG16_ERR_BAD_ARG;
+    fq12_to_abi(pf::to_flat(pf::final_exp(vb_f12(f))), out);
+    return ZKG16_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,116 @@
+// The per-proof part of batched Groth16 verification on the device (verify_batch.hpp; arithmetic: pairing_dev.cuh).  One GPU lane
+// per pair / per point, blocks of one wave: the work is a long chain of dependent Fq products per lane with nothing to share
+// between lanes, so 65,536 pairs are one round with one wave per SIMD.
+//
+//   membership_kernel     curve equation + endomorphism subgroup test of n points of one group
+//   miller_batch_kernel   (rho_i P_i when multipliers are given, back to affine, then) the Miller loop of (P_i, Q_i): 72 u64 each
+//   fq12_product_kernel   one round of the product tree over Fq12 values
+//
+// Registers: a Miller lane's state is f (12 Fq = 168 dwords), T (84), Q and P (84) and the operation at hand; every Fq product is a
+// call (ffu.cuh: fqu_mul_call), so what is live across it sits in the callee-saved registers or in scratch: 4,272 B of scratch
+// per Miller lane at one wave per SIMD (profiles/kernel_resource_usage_r8_verify.txt).  DESIGN 2.7.1 states the figures, what
+// LDS / inlined placement would change, and why the spill was left in.
+#include "verify_batch.hpp"
+
+#include "common.hpp"
+#include "pairing_dev.cuh"
+
+namespace zk {
+namespace {
+
+__global__ __launch_bounds__(64) void membership_kernel(int group, const uint64_t *pts, size_t stride, const uint8_t *inf, size_t inf_stride, size_t n, VbEndo en,
+                                                        uint8_t *ok, size_t ok_stride) {
+    const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    bool good = true;
+    if (!(inf && inf[i * inf_stride])) {
+        if (group == 1) {
+            const G1Affine p = *reinterpret_cast<const G1Affine *>(pts + i * stride);
+            good = pd::g1_valid(p, fqu_from_sat(en.beta), en.fast_g1 != 0);
+        } else {
+            const G2Affine p = *reinterpret_cast<const G2Affine *>(pts + i * stride);
+            good = pd::g2_valid(p, fq2u_from_sat(en.cx), fq2u_from_sat(en.cy), en.fast_g2 != 0);
+        }
+    }
+    ok[i * ok_stride] = good ? 1 : 0;
+}
+
+__global__ __launch_bounds__(64) void miller_batch_kernel(const uint64_t *g1, size_t g1_stride, const uint8_t *g1_inf, const uint64_t *g2, size_t g2_stride,
+                                                          const uint8_t *g2_inf, size_t inf_stride, const uint64_t *rho, size_t n, uint64_t *out) {
+    const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    bool one = (g1_inf && g1_inf[i * inf_stride]) || (g2_inf && g2_inf[i * inf_stride]);
+    pd::F12 f = pd::f12_one();
+    if (!one) {
+        const G1Affine p = *reinterpret_cast<const G1Affine *>(g1 + i * g1_stride);
+        const G2Affine q = *reinterpret_cast<const G2Affine *>(g2 + i * g2_stride);
+        FqU px = fqu_from_sat(p.x), py = fqu_from_sat(p.y);
+        if (rho) {
+            const uint32_t *r = reinterpret_cast<const uint32_t *>(rho + 2 * i);
+            const uint32_t k[4] = {r[0], r[1], r[2], r[3]};
+            one = !pd::g1_scale128(px, py, k, px, py);
+        }
+        if (!one) f = pd::miller_loop(px, py, fq2u_from_sat(q.x), fq2u_from_sat(q.y));
+    }
+    Fq2 s[6];
+    pd::f12_to_sat(f, s);
+    Fq2 *o = reinterpret_cast<Fq2 *>(out + 72 * i);
+#pragma unroll
+    for (int t = 0; t < 6; t++) o[t] = s[t];
+}
+
+// out[j] = in[2j] * in[2j + 1] (the last one alone when n_in is odd); live (nullable): in[k] counts as one where live[k] == 0
+__global__ __launch_bounds__(64) void fq12_product_kernel(const uint64_t *in, const uint8_t *live, size_t n_in, uint64_t *out) {
+    const size_t j = (size_t)blockIdx.x * 64 + threadIdx.x;
+    if (2 * j >= n_in) return;
+    const bool have_a = !live || live[2 * j], have_b = 2 * j + 1 < n_in && (!live || live[2 * j + 1]);
+    pd::F12 f = pd::f12_one();
+    if (have_a) f = pd::f12_from_sat(reinterpret_cast<const Fq2 *>(in + 72 * (2 * j)));
+    if (have_b) {
+        const pd::F12 g = pd::f12_from_sat(reinterpret_cast<const Fq2 *>(in + 72 * (2 * j + 1)));
+        f = have_a ? pd::mul(f, g) : g;
+    }
+    Fq2 s[6];
+    pd::f12_to_sat(f, s);
+    Fq2 *o = reinterpret_cast<Fq2 *>(out + 72 * j);
+#pragma unroll
+    for (int t = 0; t < 6; t++) o[t] = s[t];
+}
+
+unsigned blocks_of(size_t n) { return (unsigned)((n + 63) / 64); }
+
+}  // namespace
+
+void vb_membership_launch(hipStream_t st, int group, const uint64_t *pts, size_t stride, const uint8_t *inf, size_t inf_stride, size_t n, const VbEndo &en,
+                          uint8_t *ok, size_t ok_stride) {
+    if (!n) return;
+    hipLaunchKernelGGL(membership_kernel, dim3(blocks_of(n)), dim3(64), 0, st, group, pts, stride, inf, inf_stride, n, en, ok, ok_stride);
+    ZK_HIP(hipGetLastError());
+}
+
+void vb_miller_launch(hipStream_t st, const uint64_t *g1, size_t g1_stride, const uint8_t *g1_inf, const uint64_t *g2, size_t g2_stride, const uint8_t *g2_inf,
+                      size_t inf_stride, const uint64_t *rho, size_t n, uint64_t *out) {
+    if (!n) return;
+    hipLaunchKernelGGL(miller_batch_kernel, dim3(blocks_of(n)), dim3(64), 0, st, g1, g1_stride, g1_inf, g2, g2_stride, g2_inf, inf_stride, rho, n, out);
+    ZK_HIP(hipGetLastError());
+}
+
+const uint64_t *vb_product_launch(hipStream_t st, const uint64_t *f, const uint8_t *live, size_t n, uint64_t *tmp) {
+    const size_t half = (n + 1) / 2;
+    uint64_t *buf[2] = {tmp, tmp + 72 * half};
+    const uint64_t *in = f;
+    int w = 0;
+    // one round at least, also for n == 1: it is the round that replaces the factors of dead proofs by one
+    do {
+        const size_t n_out = (n + 1) / 2;
+        hipLaunchKernelGGL(fq12_product_kernel, dim3(blocks_of(n_out)), dim3(64), 0, st, in, live, n, buf[w]);
+        ZK_HIP(hipGetLastError());
+        in = buf[w];
+        live = nullptr;
+        w ^= 1;
+        n = n_out;
+    } while (n > 1);
+    return in;
+}
+
+}  // namespace zk

@@ -1,0 +1,69 @@
+// Batched Groth16 verification: what verify.hip (host arithmetic), verify_batch.hip (kernels) and api.hip (entry points on a lane of
+// the ctx) share.  K proofs under one prepared key hold iff, for multipliers rho_k nobody could predict (error 2^-128),
+//
+//     FE( prod_k ML(rho_k A_k, B_k) * ML(sum_k rho_k X_k, -gamma) * ML(sum_k rho_k C_k, -delta) ) == e(alpha, beta)^(sum_k rho_k)
+//
+// with X_k = gamma_abc[0] + sum_i z_{k,i} gamma_abc[i].  Per proof: three membership tests, one scalar multiplication by 128 bits and
+// one Miller loop on an unprepared G2 point (host threads or one GPU lane each).  Per batch: two Miller loops on the key's prepared
+// coefficients, one exponentiation of e(alpha, beta) and ONE final exponentiation (host).
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include <functional>
+
+#include <hip/hip_runtime.h>
+
+#include "ec.cuh"
+
+namespace zk {
+
+struct VbKey {
+    const uint64_t *gamma_abc_g1;
+    size_t num_instance;
+    const uint64_t *alpha_beta, *gamma_neg_coeffs, *delta_neg_coeffs;
+    size_t n_coeffs;
+};
+struct VbBatch {
+    const uint64_t *public_inputs;      // k x (num_instance - 1) x 4, Montgomery
+    const uint64_t *proofs;             // k x 48
+    const uint8_t *inf;                 // k x 3
+    const uint64_t *rho;                // k x 2
+    size_t k;
+};
+// the argument checks every batch entry point makes before any work
+int vb_check_args(const VbKey &key, const VbBatch &b, const int *ok);
+
+// ---- verify.hip
+// The batch's verdicts from its per-proof parts: member[k] != 0 iff A_k, B_k, C_k passed membership; prod (nullable, 72 u64): the
+// product of the member proofs' Miller values ML(rho_k A_k, B_k) in ark's tower order; sum_c: sum over the member proofs of rho_k C_k
+// (12 u64 affine; *sum_c_inf != 0: the point at infinity) or null = computed here.  fetch_miller() returns the K Miller values
+// (k x 72 u64 by proof index; anything for proofs that failed membership: they are left out); it is called at most once, and only
+// when prod is null or when the batch equation fails and ok_each wants the culprits (the device form downloads them then).
+// *ok = 1 iff every proof holds; ok_each (nullable): each proof's own verdict, found by bisecting over index ranges.
+// ms (nullable): ms[0] += coefficients + the batch equation, ms[1] += bisecting (the fetch included).
+void vb_decide(const VbKey &key, const VbBatch &b, const uint8_t *member, const std::function<const uint64_t *()> &fetch_miller, const uint64_t *prod,
+               const uint64_t *sum_c, const uint8_t *sum_c_inf, int threads, int *ok, uint8_t *ok_each, float ms[2]);
+// everything on host threads (zkg16_verify_batch_host)
+void vb_host(const VbKey &key, const VbBatch &b, int threads, int *ok, uint8_t *ok_each);
+// the endomorphism constants the host calibrated at start-up, saturated limbs, for the membership kernel
+struct VbEndo {
+    Fq beta;
+    Fq2 cx, cy;
+    int fast_g1, fast_g2;
+};
+VbEndo vb_endo();
+
+// ---- verify_batch.hip: launches on `st` (a stream of the calling lane); nothing synchronises
+// n points at pts + i * stride (u64 units; 12 / 24 u64 each), flag bytes at inf + i * inf_stride (null: none at infinity):
+// ok[i * ok_stride] = what zkg16_point_check says of point i (infinity passes)
+void vb_membership_launch(hipStream_t st, int group, const uint64_t *pts, size_t stride, const uint8_t *inf, size_t inf_stride, size_t n, const VbEndo &en,
+                          uint8_t *ok, size_t ok_stride);
+// out[i] (72 u64) = ML(rho_i P_i, Q_i); rho (2 u64 per pair) null = no scaling; a pair with P or Q at infinity gives one
+void vb_miller_launch(hipStream_t st, const uint64_t *g1, size_t g1_stride, const uint8_t *g1_inf, const uint64_t *g2, size_t g2_stride, const uint8_t *g2_inf,
+                      size_t inf_stride, const uint64_t *rho, size_t n, uint64_t *out);
+// the product of f[0 .. n) by a tree (log2 n rounds); f is only read, and f[k] counts as one where live[k] == 0 (live nullable).
+// tmp: room for 2 * ((n + 1) / 2) * 72 u64.  Returns where the product (72 u64) will lie, inside tmp
+const uint64_t *vb_product_launch(hipStream_t st, const uint64_t *f, const uint8_t *live, size_t n, uint64_t *tmp);
+
+}  // namespace zk

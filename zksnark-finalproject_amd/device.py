@@ -227,6 +227,45 @@ class Device:
         self._check(self.lib.zkg16_prove_batch(self.ctx, pk_h, r1cs_h, hs, k, rs, ss, proofs, inf))
         return proofs, inf
 
+    # ---- batched verification
+    def verify_batch(self, pvk, public_inputs, proofs, infs, rho=None, each=False):
+        """K proofs under one prepared key checked together, the per-proof work in kernels (zkg16_verify_batch): public_inputs
+        [k, num_instance - 1, 4] Montgomery, proofs [k, 48], infs [k, 3]; rho [k, 2]: 128-bit non-zero multipliers that whoever
+        made the proofs could not predict (None: drawn from `secrets`).  -> all_valid, or (all_valid, per-proof bool array) with
+        each=True.  Batches shorter than the option "verify_batch_min" are answered by the host form."""
+        args, k = _verify_batch_args(pvk, public_inputs, proofs, infs, rho)
+        ok = C.c_int(0)
+        ok_each = np.zeros(k, dtype=np.uint8) if each else None
+        self._check(self.lib.zkg16_verify_batch(self.ctx, *args, C.byref(ok), _ptr(ok_each)))
+        return (bool(ok.value), ok_each.astype(bool)) if each else bool(ok.value)
+
+    def verify_batch_timings(self):
+        """ms of the last verify_batch: membership, scaling + Miller, product tree, MSM, host equation, bisecting, total wall."""
+        ms = (C.c_float * 8)()
+        n = self.lib.zkg16_verify_batch_timings(self.ctx, ms, 8)
+        names = ("membership_ms", "miller_ms", "product_ms", "msm_ms", "host_ms", "bisect_ms", "total_ms", "host_form")
+        return {names[i]: float(ms[i]) for i in range(n)}
+
+    def miller_loop_batch(self, g1, g2, g1_inf=None, g2_inf=None):
+        """n Miller loops on the device, one GPU lane per pair (zkg16_miller_loop_batch): g1 [n, 12], g2 [n, 24] -> [n, 72] (ark's
+        Fq12 tower order); a pair with a point at infinity gives one.  final_exp() of a row is that pair's pairing."""
+        g1 = _u64(g1).reshape(-1, 12)
+        g2 = _u64(g2).reshape(-1, 24)
+        if g1.shape[0] != g2.shape[0]:
+            raise ValueError("miller_loop_batch: one G2 point per G1 point")
+        i1, i2 = _opt_u8(g1_inf), _opt_u8(g2_inf)
+        out = np.zeros((g1.shape[0], 72), dtype=np.uint64)
+        self._check(self.lib.zkg16_miller_loop_batch(self.ctx, _ptr(g1), _ptr(i1), _ptr(g2), _ptr(i2), g1.shape[0], _ptr(out)))
+        return out
+
+    def point_check_batch(self, group, points, inf=None):
+        """What point_check says of each of n affine points, on the device (zkg16_point_check_batch) -> bool array."""
+        pts = _u64(points).reshape(-1, 12 if group == "g1" else 24)
+        fl = _opt_u8(inf)
+        out = np.zeros(pts.shape[0], dtype=np.uint8)
+        self._check(self.lib.zkg16_point_check_batch(self.ctx, 1 if group == "g1" else 2, _ptr(pts), _ptr(fl), pts.shape[0], _ptr(out)))
+        return out.astype(bool)
+
     def prove_matrix(self, pk_h, r1cs_h, a, b, r, s):
         """One matrix-handler request on resident matrices: assignment built on the device while the proof already runs
         (zkg16_prove_matrix) -> (proof, inf, public inputs [3, 4], dict of ms)."""
@@ -544,6 +583,68 @@ def verify_prepared(pvk, public_inputs_mont, proof48, inf3):
     if rc != 0:
         raise Zkg16Error(rc, lib.zkg16_strerror(rc).decode())
     return bool(ok.value)
+
+
+def draw_rho(k):
+    """k non-zero 128-bit multipliers for a batch verification, from the operating system's generator -> [k, 2] u64."""
+    import secrets
+    out = np.zeros((k, 2), dtype=np.uint64)
+    for i in range(k):
+        v = 0
+        while v == 0:
+            v = secrets.randbits(128)
+        out[i, 0], out[i, 1] = v & ((1 << 64) - 1), v >> 64
+    return out
+
+
+def _verify_batch_args(pvk, public_inputs, proofs, infs, rho):
+    gabc = _u64(pvk["gamma_abc_g1"]).reshape(-1, 12)
+    proofs = _u64(proofs).reshape(-1, 48)
+    k = proofs.shape[0]
+    infs = np.ascontiguousarray(infs, dtype=np.uint8).reshape(-1, 3)
+    pub = _u64(public_inputs).reshape(k, -1, 4) if k else _u64(public_inputs).reshape(0, gabc.shape[0] - 1, 4)
+    if pub.shape[1] != gabc.shape[0] - 1:
+        raise ValueError("verify_batch: %d public inputs per proof for a key with %d instance variables" % (pub.shape[1], gabc.shape[0]))
+    if infs.shape[0] != k:
+        raise ValueError("verify_batch: one flag triple per proof")
+    rho = draw_rho(k) if rho is None else _u64(rho).reshape(-1, 2)
+    if rho.shape[0] != k:
+        raise ValueError("verify_batch: one multiplier per proof")
+    g, d = _u64(pvk["gamma_neg_pc"]).reshape(-1, 36), _u64(pvk["delta_neg_pc"]).reshape(-1, 36)
+    ab = _u64(pvk["alpha_beta"])
+    # the arrays must outlive the call: they travel in the tuple
+    keep = (gabc, ab, g, d, pub, proofs, infs, rho)
+    return _KeepAlive((_ptr(gabc), gabc.shape[0], _ptr(ab), _ptr(g), _ptr(d), g.shape[0], _ptr(pub) if pub.size else None, _ptr(proofs), _ptr(infs),
+                       _ptr(rho), k), keep), k
+
+
+class _KeepAlive(tuple):
+    def __new__(cls, items, keep):
+        self = super().__new__(cls, items)
+        self.keep = keep
+        return self
+
+
+def verify_batch_host(pvk, public_inputs, proofs, infs, rho=None, each=False, threads=0):
+    """Device.verify_batch's verdicts on host threads alone (zkg16_verify_batch_host; threads 0 = 8; no GPU)."""
+    lib = _lib.load()
+    args, k = _verify_batch_args(pvk, public_inputs, proofs, infs, rho)
+    ok = C.c_int(0)
+    ok_each = np.zeros(k, dtype=np.uint8) if each else None
+    rc = lib.zkg16_verify_batch_host(*args, threads, C.byref(ok), _ptr(ok_each))
+    if rc != 0:
+        raise Zkg16Error(rc, lib.zkg16_strerror(rc).decode())
+    return (bool(ok.value), ok_each.astype(bool)) if each else bool(ok.value)
+
+
+def final_exp(f):
+    """The verifier's final exponentiation of one Fq12 value (72 u64, ark's tower order; zkg16_final_exp, host-only)."""
+    lib = _lib.load()
+    out = np.zeros(72, dtype=np.uint64)
+    rc = lib.zkg16_final_exp(_u64(f).reshape(-1), out)
+    if rc != 0:
+        raise Zkg16Error(rc, lib.zkg16_strerror(rc).decode())
+    return out
 
 
 class DeviceGroup:

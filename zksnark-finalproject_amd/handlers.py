@@ -252,3 +252,46 @@ def verify_proof(vk, public_inputs_mont, proof_b64):
     # verifying_time = the verification call alone, as the reference's timer (matrix_proof.rs:199-206, prime_snark.rs:191-200: started
     # after decode_pvk / decode_proof); decode_time = base64 + decompression + subgroup checks of key and proof (Python big ints)
     return dict(valid=bool(ok), verifying_time=t2 - t1, decode_time=t1 - t0)
+
+
+def verify_proofs(vk, public_inputs_list, proofs_b64, dev=None):
+    """verify_proof for K proofs under one key, checked together (Device.verify_batch with `dev`, else the host form
+    verify_batch_host): one final exponentiation for the batch instead of one per proof.  -> {valid: [K bools], verifying_time,
+    decode_time}.  A proof that does not decode, or whose public inputs have the wrong shape, is valid=False for that entry only;
+    a key that does not decode makes every entry invalid."""
+    from ._lib import Zkg16Error
+    from .device import pvk_prepare, verify_batch_host
+    t0 = time.perf_counter()
+    k = len(proofs_b64)
+    valid = [False] * k
+    if len(public_inputs_list) != k:
+        raise ValueError("verify_proofs: one public input list per proof")
+    try:
+        if isinstance(vk, str):
+            raw = __import__("base64").standard_b64decode(vk)
+            n = int.from_bytes(raw[336:344], "little") if len(raw) >= 344 else 0
+            vk = wire.pvk_deserialize_compressed(raw) if len(raw) > 344 + 48 * n else wire.vk_deserialize_compressed(raw)
+        pvk = vk if "alpha_beta" in vk else pvk_prepare(vk)
+        ni = np.asarray(pvk["gamma_abc_g1"]).reshape(-1, 12).shape[0]
+    except (ValueError, IndexError, Zkg16Error):
+        return dict(valid=valid, verifying_time=0.0, decode_time=time.perf_counter() - t0)
+    idx, proofs, infs, pubs = [], [], [], []
+    for i, (pub, pb) in enumerate(zip(public_inputs_list, proofs_b64)):
+        try:
+            proof, inf = wire.decode_proof(pb)
+            pub = np.ascontiguousarray(pub, dtype=np.uint64).reshape(-1, 4)
+            if pub.shape[0] != ni - 1:
+                continue
+        except (ValueError, IndexError, TypeError):
+            continue
+        idx.append(i)
+        proofs.append(proof)
+        infs.append(inf)
+        pubs.append(pub)
+    t1 = time.perf_counter()
+    if idx:
+        args = (pvk, np.array(pubs, dtype=np.uint64).reshape(len(idx), ni - 1, 4), np.array(proofs, dtype=np.uint64), np.array(infs, dtype=np.uint8))
+        _, each = dev.verify_batch(*args, each=True) if dev is not None else verify_batch_host(*args, each=True)
+        for i, ok in zip(idx, each):
+            valid[i] = bool(ok)
+    return dict(valid=valid, verifying_time=time.perf_counter() - t1, decode_time=t1 - t0)
