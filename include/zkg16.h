@@ -288,6 +288,27 @@ ZKG16_API int zkg16_verify_batch(zkg16_ctx *ctx, const uint64_t *gamma_abc_g1, s
                        const uint64_t *gamma_neg_coeffs, const uint64_t *delta_neg_coeffs, size_t n_coeffs,
                        const uint64_t *public_inputs, const uint64_t *proofs, const uint8_t *inf, const uint64_t *rho, size_t k,
                        int *ok, uint8_t *ok_each);
+/* zkg16_verify_batch from the proofs as they travel: proof_bytes = k x 192 (A 48 | B 96 | C 48, the compressed encoding of
+ * zkg16_g1_decompress / zkg16_g2_decompress).  The bytes are uploaded and decoded in a kernel, one GPU lane per point (square roots
+ * and byte parsing on the device, no validation: the membership kernels test every point once), into the device proof array that
+ * zkg16_verify_batch's kernels read; the decoded limbs and flags come back once (384 B per proof) for the host's share of the work.
+ * A proof with a point that does not decode (status 1 to 4) is treated exactly like one that fails membership: left out of every
+ * sum and product, ok_each[k] = 0, *ok = 0, the other proofs' verdicts unaffected.  decode_status (nullable, k x 3 bytes: A, B, C):
+ * what the validating host decoder says of each point (5 from the membership verdicts).  When every proof decodes, *ok and ok_each
+ * equal zkg16_verify_batch on the host-decoded limbs with the same rho.  Argument checks as zkg16_verify_batch, and proof_bytes
+ * non-null.  Batches shorter than option "verify_wire_min" (default 256: the smallest measured K at which this call
+ * beat host decoding followed by either the host form on eight threads or zkg16_verify_batch, 0.094 against 0.239 and 0.245 ms per
+ * proof, each far outside the spread of the rounds; at K = 64 it lost, 0.361 against 0.270 — profiles/verify_wire_timing_r9.txt;
+ * 1 = always the device) are decoded on host threads and answered by the host form. */
+ZKG16_API int zkg16_verify_batch_wire(zkg16_ctx *ctx, const uint64_t *gamma_abc_g1, size_t num_instance, const uint64_t alpha_beta[72],
+                            const uint64_t *gamma_neg_coeffs, const uint64_t *delta_neg_coeffs, size_t n_coeffs,
+                            const uint64_t *public_inputs, const uint8_t *proof_bytes, const uint64_t *rho, size_t k,
+                            int *ok, uint8_t *ok_each, uint8_t *decode_status);
+/* Stage entry: zkg16_g1_decompress / zkg16_g2_decompress (group 1 / 2) in a kernel on a lane of the ctx, one GPU lane per point.
+ * Outputs, statuses (nullable) and the return code are the host functions': limbs zero for a point of status 1 to 4,
+ * ZKG16_ERR_BAD_ARG when any point failed; n == 0 is ZKG16_OK. */
+ZKG16_API int zkg16_points_decompress_batch(zkg16_ctx *ctx, int group, const uint8_t *bytes, size_t n, uint64_t *out, uint8_t *inf,
+                                  int validate, int *status);
 /* Stage entries (tests / tools).  n Miller loops on the device, one GPU lane per pair: f_out[i] (72 u64, ark's tower order, the
  * layout of alpha_beta) = the Miller value of (g1[i], g2[i]) with ark's line scaling, one for a pair with a point at infinity (flag
  * bytes nullable); zkg16_final_exp of it is the pairing.  n membership tests on the device: ok_out[i] = what zkg16_point_check says
@@ -296,9 +317,10 @@ ZKG16_API int zkg16_miller_loop_batch(zkg16_ctx *ctx, const uint64_t *g1, const 
                             uint64_t *f_out);
 ZKG16_API int zkg16_point_check_batch(zkg16_ctx *ctx, int group, const uint64_t *points, const uint8_t *inf, size_t n, uint8_t *ok_out);
 ZKG16_API int zkg16_final_exp(const uint64_t f[72], uint64_t out[72]);
-/* The last zkg16_verify_batch on this ctx, in ms: [0] membership kernels (host clock: launch to the verdicts on the host, beside
+/* The last zkg16_verify_batch / zkg16_verify_batch_wire on this ctx, in ms: [0] membership kernels (host clock: launch to the verdicts on the host, beside
  * the Miller kernel), [1] scaling + Miller kernel (device events), [2] product tree, [3] the MSM
- * sum rho_k C_k, [4] host coefficients and the batch equation, [5] bisecting, [6] total wall; [7] = 1 when the host form answered.
+ * sum rho_k C_k, [4] host coefficients and the batch equation, [5] bisecting, [6] total wall; [7] = 1 when the host form answered;
+ * [8] zkg16_verify_batch_wire only: the decompress kernels (device events; the host decode's wall time when the host form answered).
  * Returns the number of entries written (at most cap). */
 ZKG16_API int zkg16_verify_batch_timings(zkg16_ctx *ctx, float *ms, int cap);
 

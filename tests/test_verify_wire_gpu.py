@@ -1,0 +1,322 @@
+"""Compressed proofs decoded on the device: decompress_kernel (csrc/verify_batch.hip, arithmetic csrc/decompress_dev.cuh) against the
+host decoders zkg16_g1_decompress / zkg16_g2_decompress byte for byte, and zkg16_verify_batch_wire against zkg16_verify_batch on the
+host-decoded limbs with the same multipliers."""
+import base64
+import random
+
+import numpy as np
+import pytest
+
+import decompress_cases as DC
+import pyref as P
+import verify_batch_cases as VB
+from helpers import *
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def dev():
+    from zksnark_finalproject_amd import Device
+    d = Device(0)
+    d.set_option("verify_batch_min", 1)         # every batch of this module runs the kernels, K = 1 included
+    d.set_option("verify_wire_min", 1)
+    yield d
+    d.close()
+
+
+@pytest.fixture(scope="module")
+def batch1000(oracle):
+    """1,000 distinct proofs, built as tests/test_verify_batch_gpu.py builds its batch1000: 40 assignments proved by the oracle,
+    then re-randomised — (A, B, C) -> (t A, t^-1 B, C) is again a valid proof of the same statement"""
+    base = VB.make_batch(oracle, 40)
+    rng = random.Random(77)
+    k = 1000
+    proofs = np.zeros((k, 48), dtype=np.uint64)
+    infs = np.zeros((k, 3), dtype=np.uint8)
+    pubs = np.zeros((k,) + base.pubs.shape[1:], dtype=np.uint64)
+    for i in range(k):
+        j = i % base.k
+        proofs[i], infs[i], pubs[i] = base.proofs[j], base.infs[j], base.pubs[j]
+        if i >= base.k:
+            t = rng.randrange(1, P.R_MOD)
+            proofs[i, 0:12] = oracle.point_mul("g1", base.proofs[j, 0:12], fr_canon(t))[0]
+            proofs[i, 12:36] = oracle.point_mul("g2", base.proofs[j, 12:36], fr_canon(pow(t, -1, P.R_MOD)))[0]
+    return VB.Batch(base.pvk, pubs, proofs, infs)
+
+
+@pytest.fixture(scope="module")
+def torsion():
+    return VB.g2_outside_subgroup()
+
+
+def to_wire(b):
+    """a limb batch as it travels: [k, 192] bytes (A 48 | B 96 | C 48)"""
+    from zksnark_finalproject_amd import wire
+    k = b.k
+    a = np.frombuffer(wire.points_compress("g1", b.proofs[:, 0:12], b.infs[:, 0]), dtype=np.uint8).reshape(k, 48)
+    bb = np.frombuffer(wire.points_compress("g2", b.proofs[:, 12:36], b.infs[:, 1]), dtype=np.uint8).reshape(k, 96)
+    c = np.frombuffer(wire.points_compress("g1", b.proofs[:, 36:48], b.infs[:, 2]), dtype=np.uint8).reshape(k, 48)
+    return np.ascontiguousarray(np.concatenate([a, bb, c], axis=1))
+
+
+def host_decoded(raw, validate):
+    """[k, 192] bytes through the host decoders -> (proofs [k, 48], infs [k, 3], statuses [k, 3])"""
+    k = raw.shape[0]
+    a = DC.host_decode("g1", raw[:, 0:48].tobytes(), validate)
+    b = DC.host_decode("g2", raw[:, 48:144].tobytes(), validate)
+    c = DC.host_decode("g1", raw[:, 144:192].tobytes(), validate)
+    proofs = np.concatenate([a[0], b[0], c[0]], axis=1)
+    return np.ascontiguousarray(proofs), np.ascontiguousarray(np.stack([a[1], b[1], c[1]], axis=1)), np.stack([a[2], b[2], c[2]], axis=1).astype(np.uint8)
+
+
+# ------------------------------------------------------------------------------------------------ decompress_batch
+@pytest.fixture(scope="module")
+def points(batch1000):
+    """per group: 1,000 proof points as bytes, the host decoders' answer for them (computed once), and every hostile encoding with the
+    host decoders' answer, for validate on and off"""
+    from zksnark_finalproject_amd import wire
+    out = {}
+    for group, limbs in (("g1", batch1000.proofs[:, 0:12]), ("g2", batch1000.proofs[:, 12:36])):
+        data = wire.points_compress(group, limbs)
+        size = DC.SIZE[group]
+        bad = DC.hostile(group, data[:size])
+        bad_bytes = b"".join(e for e, _ in bad.values())
+        out[group] = dict(data=data, names=list(bad), bad=[e for e, _ in bad.values()],
+                          ref={v: DC.host_decode(group, data, v) for v in (True, False)},
+                          bad_ref={v: DC.host_decode(group, bad_bytes, v) for v in (True, False)})
+        assert np.array_equal(out[group]["ref"][True][0], limbs)
+        assert sorted(set(out[group]["bad_ref"][True][2])) == [1, 2, 3, 4, 5]
+    return out
+
+
+@pytest.mark.parametrize("group", ["g1", "g2"])
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 1000])
+def test_decompress_batch_equals_host_decoders(dev, points, group, n):
+    """limbs, flags and statuses byte for byte: the clean points, then every hostile encoding at the first, last and wave-boundary
+    indices, with and without the subgroup test"""
+    pt = points[group]
+    size = DC.SIZE[group]
+    data = pt["data"][:size * n]
+    where = sorted({i for i in (0, 63, 64, n - 1) if i < n})
+    for validate in (True, False):
+        ref_out, ref_inf, ref_st, _ = pt["ref"][validate]
+        out, inf, st = dev.decompress_batch(group, data, validate)
+        assert out.tobytes() == ref_out[:n].tobytes() and np.array_equal(inf, ref_inf[:n]) and not st.any()
+        h_out, h_inf, h_st, _ = pt["bad_ref"][validate]
+        for j, enc in enumerate(pt["bad"]):
+            planted = bytearray(data)
+            w_out, w_inf, w_st = ref_out[:n].copy(), ref_inf[:n].copy(), ref_st[:n].copy()
+            for i in where:
+                planted[size * i:size * (i + 1)] = enc
+                w_out[i], w_inf[i], w_st[i] = h_out[j], h_inf[j], h_st[j]
+            out, inf, st = dev.decompress_batch(group, bytes(planted), validate)
+            assert np.array_equal(st, w_st), (pt["names"][j], validate, st[where], w_st[where])
+            assert np.array_equal(inf, w_inf), pt["names"][j]
+            assert out.tobytes() == w_out.tobytes(), pt["names"][j]
+
+
+def test_decompress_batch_infinity_return_code_and_empty(dev, points):
+    for group in ("g1", "g2"):
+        size, width = DC.SIZE[group], DC.WIDTH[group]
+        good = points[group]["data"][:size]
+        data = good + bytes([0xC0]) + bytes(size - 1) + good
+        out, inf, st = dev.decompress_batch(group, data)
+        assert list(inf) == [0, 1, 0] and not st.any() and not out[1].any() and np.array_equal(out[0], out[2])
+        # the return code of the host functions: BAD_ARG when a point failed, status nullable, n == 0 fine
+        raw = np.frombuffer(good + points[group]["bad"][0], dtype=np.uint8)
+        o, f = np.zeros((2, width), np.uint64), np.zeros(2, np.uint8)
+        g = 1 if group == "g1" else 2
+        assert dev.lib.zkg16_points_decompress_batch(dev.ctx, g, raw.ctypes.data, 2, o.ctypes.data, f.ctypes.data, 1, None) == 1
+        assert dev.lib.zkg16_points_decompress_batch(dev.ctx, g, raw.ctypes.data, 1, o.ctypes.data, f.ctypes.data, 1, None) == 0
+        assert dev.lib.zkg16_points_decompress_batch(dev.ctx, g, None, 0, None, None, 1, None) == 0
+        assert dev.lib.zkg16_points_decompress_batch(dev.ctx, 3, raw.ctypes.data, 1, o.ctypes.data, f.ctypes.data, 1, None) == 1
+        assert dev.lib.zkg16_points_decompress_batch(dev.ctx, g, None, 1, o.ctypes.data, f.ctypes.data, 1, None) == 1
+
+
+# ------------------------------------------------------------------------------------------------ verify_batch_wire
+def wire_and_limbs(dev, b, raw, rho):
+    """verify_batch_wire on the bytes against verify_batch on what the host decoders make of them (same rho): a proof with a point
+    that does not decode is invalid, everything else equal; the statuses are the validating host decoder's"""
+    limbs, infs, st = host_decoded(raw, False)
+    ok_w, each_w, st_w = dev.verify_batch_wire(b.pvk, b.pubs, raw, rho=rho, each=True, status=True)
+    t = dev.verify_batch_timings()
+    assert t["host_form"] == 0 and t["decode_ms"] > 0
+    ok_l, each_l = dev.verify_batch(b.pvk, b.pubs, limbs, infs, rho=rho, each=True)
+    decoded = ~st.any(axis=1)
+    assert np.array_equal(each_w, each_l & decoded)
+    assert ok_w == (ok_l and bool(decoded.all())) == bool(each_w.all())
+    assert np.array_equal(st_w, host_decoded(raw, True)[2])
+    assert dev.verify_batch_wire(b.pvk, b.pubs, raw, rho=rho) == ok_w
+    return ok_w, each_w, st_w
+
+
+@pytest.mark.parametrize("k", [1, 64, 65, 1000])
+def test_verify_batch_wire_all_valid(dev, batch1000, k):
+    b = batch1000.head(k)
+    raw = to_wire(b)
+    ok, each, st = wire_and_limbs(dev, b, raw, VB.draw_rho(random.Random(k), k))
+    assert ok is True and each.all() and not st.any()
+    assert dev.verify_batch_wire(b.pvk, b.pubs, raw.tobytes()) is True        # plain bytes; multipliers from `secrets`
+
+
+@pytest.mark.parametrize("k", [1, 64, 65, 1000])
+@pytest.mark.parametrize("kind", VB.TAMPERS)
+def test_verify_batch_wire_tampered_sets(dev, oracle, batch1000, torsion, k, kind):
+    b0 = batch1000.head(k)
+    for where in VB.positions(k):
+        b = VB.tamper(oracle, b0, kind, where, torsion)
+        ok, each, st = wire_and_limbs(dev, b, to_wire(b), VB.draw_rho(random.Random(k * 7 + len(where)), k))
+        assert ok is False, (kind, where)
+        want = np.ones(k, dtype=bool)
+        want[list(where)] = False
+        if kind == "swap_a":
+            want[[(i + 1) % k for i in where]] = False
+        assert np.array_equal(each, want), (kind, where)
+        if kind == "b_outside_subgroup":
+            assert (st[list(where), 1] == 5).all() and np.count_nonzero(st) == len(where)
+
+
+def test_verify_batch_wire_undecodable_proofs(dev, batch1000, points):
+    """K = 65: a flipped compression bit, a dirty infinity, an x >= q and an x with no point, in A, B and C"""
+    k = 65
+    b = batch1000.head(k)
+    raw = to_wire(b)
+    g1, g2 = dict(zip(points["g1"]["names"], points["g1"]["bad"])), dict(zip(points["g2"]["names"], points["g2"]["bad"]))
+    plant = {0: (0, 1, None), 7: (48, 2, g2["infinity_stray_byte"]), 63: (144, 3, g1["x_is_q"]), 64: (0, 4, g1["no_point"]),
+             20: (48, 4, g2["no_point"]), 33: (48, 3, g2["c0_is_q"]), 41: (144, 2, g1["infinity_with_sign"])}
+    for i, (off, _, enc) in plant.items():
+        if enc is None:
+            raw[i, off] &= 0x7F                      # the compression bit of A
+        else:
+            raw[i, off:off + len(enc)] = np.frombuffer(enc, dtype=np.uint8)
+    ok, each, st = wire_and_limbs(dev, b, raw, VB.draw_rho(random.Random(65), k))
+    want = np.ones(k, dtype=bool)
+    want[list(plant)] = False
+    assert ok is False and np.array_equal(each, want)
+    want_st = np.zeros((k, 3), dtype=np.uint8)
+    for i, (off, code, _) in plant.items():
+        want_st[i, {0: 0, 48: 1, 144: 2}[off]] = code
+    assert np.array_equal(st, want_st)
+
+
+def test_verify_batch_wire_two_passes(dev, batch1000):
+    """K = 70,000 (the 1,000 proofs' bytes tiled): two passes of the kernels, one corrupted byte string in the second"""
+    k = 70000
+    b = batch1000.tiled(k)
+    raw = np.ascontiguousarray(np.tile(to_wire(batch1000), (70, 1)))
+    rho = VB.draw_rho(random.Random(70), k)
+    assert dev.verify_batch_wire(b.pvk, b.pubs, raw, rho=rho) is True
+    bad = 65536 + 1234
+    raw[bad, 150] ^= 0x10                            # inside C's x
+    ok, each, st = dev.verify_batch_wire(b.pvk, b.pubs, raw, rho=rho, each=True, status=True)
+    want = np.ones(k, dtype=bool)
+    want[bad] = False
+    assert ok is False and np.array_equal(each, want)
+    assert st[bad, 2] in (4, 5) and np.count_nonzero(st) == 1     # another x: no point, or a point outside the subgroup
+
+
+def test_verify_batch_wire_bad_arguments(dev, batch1000):
+    import ctypes as C
+    b = batch1000.head(3)
+    raw = to_wire(b)
+    gabc = np.ascontiguousarray(b.pvk["gamma_abc_g1"], dtype=np.uint64).reshape(-1, 12)
+    ab = np.ascontiguousarray(b.pvk["alpha_beta"], dtype=np.uint64)
+    g = np.ascontiguousarray(b.pvk["gamma_neg_pc"], dtype=np.uint64).reshape(-1, 36)
+    d = np.ascontiguousarray(b.pvk["delta_neg_pc"], dtype=np.uint64).reshape(-1, 36)
+    rho = VB.draw_rho(random.Random(1), 3)
+    zero = rho.copy()
+    zero[2] = 0
+    p = lambda a: a.ctypes.data
+
+    def call(**kw):
+        a = dict(ctx=dev.ctx, gabc=p(gabc), ni=gabc.shape[0], ab=p(ab), g=p(g), d=p(d), nc=68, pub=p(b.pubs), raw=p(raw), rho=p(rho), k=3)
+        a.update(kw)
+        ok = C.c_int(-7)
+        each = np.full(3, 9, dtype=np.uint8)
+        st = np.full((3, 3), 9, dtype=np.uint8)
+        rc = dev.lib.zkg16_verify_batch_wire(a["ctx"], a["gabc"], a["ni"], a["ab"], a["g"], a["d"], a["nc"], a["pub"], a["raw"], a["rho"], a["k"],
+                                             None if kw.get("ok_null") else C.byref(ok), p(each), p(st))
+        return rc, ok.value, each, st
+    rc, ok, each, st = call()
+    assert rc == 0 and ok == 1 and (each == 1).all() and (st == 0).all()
+    for kw in [dict(rho=p(zero)), dict(k=0), dict(nc=67), dict(ctx=None), dict(gabc=None), dict(ab=None), dict(g=None), dict(d=None), dict(pub=None),
+               dict(raw=None), dict(rho=None), dict(ok_null=True)]:
+        rc, ok, each, st = call(**kw)
+        assert rc == 1 and ok == -7 and (each == 9).all() and (st == 9).all(), kw
+
+
+def test_verify_batch_wire_host_form_below_threshold(dev, batch1000, torsion, oracle):
+    """below verify_wire_min the host decodes and answers: the same verdicts and statuses as the kernels give"""
+    k = 12
+    b = VB.tamper(oracle, batch1000.head(k), "b_outside_subgroup", (5,), torsion)
+    raw = to_wire(b)
+    raw[2, 0] &= 0x7F
+    rho = VB.draw_rho(random.Random(12), k)
+    on_device = dev.verify_batch_wire(b.pvk, b.pubs, raw, rho=rho, each=True, status=True)
+    assert dev.verify_batch_timings()["host_form"] == 0
+    dev.set_option("verify_wire_min", 13)
+    try:
+        on_host = dev.verify_batch_wire(b.pvk, b.pubs, raw, rho=rho, each=True, status=True)
+        assert dev.verify_batch_timings()["host_form"] == 1
+        assert dev.verify_batch_wire(b.pvk, b.pubs, raw, rho=rho) is False
+    finally:
+        dev.set_option("verify_wire_min", 1)
+    want = np.ones(k, dtype=bool)
+    want[[2, 5]] = False
+    for ok, each, st in (on_device, on_host):
+        assert ok is False and np.array_equal(each, want)
+        assert st[2, 0] == 1 and st[5, 1] == 5 and np.count_nonzero(st) == 2
+
+
+def test_prove_batch_to_wire_to_verify_batch_wire(dev):
+    """prove_batch -> wire.proof_serialize_compressed -> verify_batch_wire, K = 64 proofs of a 12-step Fibonacci: all valid; one
+    flipped byte in one proof and only that proof is flagged"""
+    from zksnark_finalproject_amd import wire
+    from zksnark_finalproject_amd.circuits import fibonacci_circuit
+    from zksnark_finalproject_amd.device import pvk_prepare
+    import bench
+    k = 64
+    circs = [fibonacci_circuit(3 * i + 1, 5 * i + 2, 12) for i in range(k)]
+    rh = dev.r1cs_load(circs[0].r1cs, circs[0].num_vars)
+    trap, g1, g2 = bench.draw_key_inputs(42)
+    ph, vk = dev.setup_resident(rh, circs[0].num_instance, trap, g1, g2)
+    whs = np.array([dev.witness_load(c.z) for c in circs], dtype=np.uint64)
+    rng = random.Random(5)
+    rs = np.stack([fr_mont(rng.randrange(P.R_MOD)) for _ in range(k)]).reshape(k, 4)
+    ss = np.stack([fr_mont(rng.randrange(P.R_MOD)) for _ in range(k)]).reshape(k, 4)
+    try:
+        proofs, infs = dev.prove_batch(ph, rh, whs, rs, ss)
+    finally:
+        for w in whs:
+            dev.witness_free(int(w))
+        dev.pk_free(ph)
+        dev.r1cs_free(rh)
+    pubs = np.array([c.public_inputs for c in circs], dtype=np.uint64).reshape(k, -1, 4)
+    raw = bytearray(b"".join(wire.proof_serialize_compressed(proofs[i], infs[i]) for i in range(k)))
+    pvk = pvk_prepare(vk)
+    ok, each = dev.verify_batch_wire(pvk, pubs, bytes(raw), each=True)
+    assert ok is True and each.all()
+    raw[192 * 37 + 100] ^= 0x04                      # inside B of proof 37
+    ok, each = dev.verify_batch_wire(pvk, pubs, bytes(raw), each=True)
+    want = np.ones(k, dtype=bool)
+    want[37] = False
+    assert ok is False and np.array_equal(each, want)
+
+
+def test_handler_verify_proofs_same_with_and_without_device(dev, oracle, batch1000):
+    """handlers.verify_proofs through verify_batch_wire (dev) and through host decoding + the host form (dev=None): one `valid` list,
+    for a batch with good, tampered, non-base64 and wrong-length entries and one with the wrong number of public inputs"""
+    from zksnark_finalproject_amd import handlers, wire
+    k = 10
+    b = VB.tamper(oracle, batch1000.head(k), "c_plus_g", (3,))
+    enc = [wire.encode_proof(b.proofs[i], b.infs[i]) for i in range(k)]
+    pubs = [b.pubs[i] for i in range(k)]
+    enc[1] = "!!! not base64 !!!"
+    enc[4] = base64.standard_b64encode(base64.standard_b64decode(enc[4])[:100]).decode()
+    enc[6] = base64.standard_b64encode(bytes([base64.standard_b64decode(enc[6])[0] & 0x7F]) + base64.standard_b64decode(enc[6])[1:]).decode()
+    pubs[8] = np.concatenate([pubs[8], pubs[8]])
+    with_dev = handlers.verify_proofs(b.pvk, pubs, enc, dev=dev)
+    without = handlers.verify_proofs(b.pvk, pubs, enc, dev=None)
+    want = [i not in (1, 3, 4, 6, 8) for i in range(k)]
+    assert with_dev["valid"] == without["valid"] == want

@@ -85,7 +85,7 @@ void copy_options(zkg16_ctx *dst, const zkg16_ctx *src) {
     dst->opt_ntt_radix = src->opt_ntt_radix; dst->opt_ntt_xcd = src->opt_ntt_xcd; dst->opt_acc_debug = src->opt_acc_debug;
     dst->opt_sort_mode = src->opt_sort_mode; dst->opt_acc_pipeline = src->opt_acc_pipeline; dst->opt_fuse_pointwise = src->opt_fuse_pointwise;
     dst->opt_matrix_parts = src->opt_matrix_parts; dst->opt_g2_lazy = src->opt_g2_lazy; dst->opt_g1_inline = src->opt_g1_inline; dst->opt_fixed_base_bits = src->opt_fixed_base_bits;
-    dst->opt_collect_threads = src->opt_collect_threads; dst->opt_batch_max = src->opt_batch_max; dst->opt_verify_batch_min = src->opt_verify_batch_min; dst->opt_wm_transforms = src->opt_wm_transforms;
+    dst->opt_collect_threads = src->opt_collect_threads; dst->opt_batch_max = src->opt_batch_max; dst->opt_verify_batch_min = src->opt_verify_batch_min; dst->opt_verify_wire_min = src->opt_verify_wire_min; dst->opt_wm_transforms = src->opt_wm_transforms;
     dst->kernel_timing = src->kernel_timing; dst->kernel_timing_accumulate_only = src->kernel_timing_accumulate_only;
 }
 void create_streams(zkg16_ctx *ctx) {
@@ -1171,6 +1171,11 @@ int set_option_one(zkg16_ctx *ctx, const char *name, int64_t value) {
     if (!strcmp(name, "verify_batch_min")) {   // zkg16_verify_batch: batches shorter than this go to the host form (0 restores the default; 1 = always the device)
         if (value < 0 || value > (1 << 30)) return ZKG16_ERR_BAD_ARG;
         ctx->opt_verify_batch_min = value == 0 ? ZKG16_VERIFY_BATCH_MIN_DEFAULT : (int)value;
+        return ZKG16_OK;
+    }
+    if (!strcmp(name, "verify_wire_min")) {    // zkg16_verify_batch_wire: batches shorter than this are decoded and answered on the host (0 restores the default; 1 = always the device)
+        if (value < 0 || value > (1 << 30)) return ZKG16_ERR_BAD_ARG;
+        ctx->opt_verify_wire_min = value == 0 ? ZKG16_VERIFY_WIRE_MIN_DEFAULT : (int)value;
         return ZKG16_OK;
     }
     if (!strcmp(name, "reduce_chunk")) {
@@ -2559,12 +2564,14 @@ int zkg16_prove_group(zkg16_group *group, const uint64_t *pk_handles, const uint
 // (verify_batch.hpp.)  The per-proof work in kernels on a lane of the ctx: the three membership launches and the Miller launch of a
 // pass are independent and run on four of the lane's streams at once; the host needs the membership verdicts first (they decide
 // which C_k enter the MSM), so the MSM of sum rho_k C_k runs on the lane's main stream while the Miller kernel is still busy.
+// From wire bytes (zkg16_verify_batch_wire) the three decompress launches of a pass fill the device proof array first, B on the main
+// stream beside A and C on two others; everything after reads that array as if the host had uploaded it.
 #include "verify_batch.hpp"
 
 namespace {
 const size_t VB_PASS = 65536;          // pairs / points per launch: one wave per SIMD of a 256-CU device
 struct VbEvents {
-    hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    hipEvent_t ev[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     VbEvents() { for (auto &e : ev) ZK_HIP(hipEventCreate(&e)); }
     ~VbEvents() { for (auto &e : ev) if (e) (void)hipEventDestroy(e); }
     VbEvents(const VbEvents &) = delete;
@@ -2575,48 +2582,63 @@ float vb_elapsed(hipEvent_t a, hipEvent_t b) {
     ZK_HIP(hipEventElapsedTime(&ms, a, b));
     return ms;
 }
-void vb_publish(zkg16_ctx *root, const float tm[8]) {
+void vb_publish(zkg16_ctx *root, const float tm[9]) {
     std::lock_guard<std::mutex> lk(root->lane_mu);
     memcpy(root->vb_timings, tm, sizeof root->vb_timings);
 }
-}  // namespace
 
-extern "C" {
-
-int zkg16_verify_batch(zkg16_ctx *ctx, const uint64_t *gamma_abc_g1, size_t num_instance, const uint64_t alpha_beta[72], const uint64_t *gamma_neg_coeffs,
-                       const uint64_t *delta_neg_coeffs, size_t n_coeffs, const uint64_t *public_inputs, const uint64_t *proofs, const uint8_t *inf,
-                       const uint64_t *rho, size_t k, int *ok, uint8_t *ok_each) {
-    if (!ctx) return ZKG16_ERR_BAD_ARG;
-    const VbKey key{gamma_abc_g1, num_instance, alpha_beta, gamma_neg_coeffs, delta_neg_coeffs, n_coeffs};
-    const VbBatch b{public_inputs, proofs, inf, rho, k};
-    const int rc = vb_check_args(key, b, ok);
-    if (rc != ZKG16_OK) return rc;
-    const double t_all = now_ms();
-    float tm[8] = {0};
-    if (k < (size_t)ctx->opt_verify_batch_min) {
-        try {
-            vb_host(key, b, 0, ok, ok_each);
-        } catch (const std::bad_alloc &) {
-            return ZKG16_ERR_OOM;
-        }
-        tm[6] = (float)(now_ms() - t_all);
-        tm[7] = 1;
-        vb_publish(ctx, tm);
-        return ZKG16_OK;
-    }
+// The device form of both entry points.  wire == null: b.proofs / b.inf are the caller's limbs and flags.  wire != null (k x 192
+// bytes): b.proofs / b.inf are null; the proofs are decoded on the device, unvalidated, and the decoded limbs and flags come back
+// once for the MSM's bases and vb_decide.  A proof with a point that did not decode is left out like one that fails membership;
+// decode_status (nullable, k x 3): the decode kernel's statuses, 5 where a decoded point failed membership.
+int vb_device(zkg16_ctx *ctx, const VbKey &key, VbBatch b, const uint8_t *wire, int *ok, uint8_t *ok_each, uint8_t *decode_status, double t_all) {
+    const size_t k = b.k;
+    float tm[9] = {0};
     ZK_LANE_BEGIN(ctx)
     hipStream_t s_main = ctx->stream, s_mil = ctx->wm_stream, s_c = ctx->slots[1].stream, s_b = ctx->slots[2].stream;
     VbEvents evs;
-    hipEvent_t e_up = evs.ev[0], e_a = evs.ev[1], e_c = evs.ev[2], e_b = evs.ev[3], e_mil = evs.ev[4], e_p0 = evs.ev[5], e_p1 = evs.ev[6], e_m0 = evs.ev[7];
+    hipEvent_t e_up = evs.ev[0], e_a = evs.ev[1], e_c = evs.ev[2], e_b = evs.ev[3], e_mil = evs.ev[4], e_p0 = evs.ev[5], e_p1 = evs.ev[6], e_m0 = evs.ev[7],
+               e_d0 = evs.ev[8], e_d1 = evs.ev[9];
     const size_t half = (k + 1) / 2;
     DevBuf d_proofs(k * 48 * 8), d_inf(3 * k), d_rho(k * 16), d_mem3(3 * k), d_live(k), d_f(k * 72 * 8), d_tmp(2 * half * 72 * 8);
-    upload_h2d(ctx, d_proofs.p, proofs, k * 48 * 8);
-    ZK_HIP(hipMemcpyAsync(d_inf.p, inf, 3 * k, hipMemcpyHostToDevice, s_main));
-    ZK_HIP(hipMemcpyAsync(d_rho.p, rho, k * 16, hipMemcpyHostToDevice, s_main));
+    DevBuf d_wire(wire ? k * 192 : 0), d_st(wire ? 3 * k : 0);
+    const VbEndo en = vb_endo();
+    std::vector<uint64_t> dec_proofs;
+    std::vector<uint8_t> dec_inf, dec_st;
+    if (wire) {
+        upload_h2d(ctx, d_wire.p, wire, k * 192);
+        ZK_HIP(hipMemcpyAsync(d_rho.p, b.rho, k * 16, hipMemcpyHostToDevice, s_main));
+        ZK_HIP(hipEventRecord(e_d0, s_main));
+        for (hipStream_t st : {s_c, s_b}) ZK_HIP(hipStreamWaitEvent(st, e_d0, 0));
+        for (size_t off = 0; off < k; off += VB_PASS) {
+            const size_t n = std::min(VB_PASS, k - off);
+            const uint8_t *by = d_wire.as<uint8_t>() + 192 * off;
+            uint64_t *pts = d_proofs.as<uint64_t>() + 48 * off;
+            uint8_t *fl = d_inf.as<uint8_t>() + 3 * off, *st3 = d_st.as<uint8_t>() + 3 * off;
+            // B (two powers and an inversion) on the main stream, A and C (one power each) beside it
+            vb_decompress_launch(s_main, 2, by + 48, 192, n, 0, en, pts + 12, 48, fl + 1, 3, st3 + 1, 3);
+            vb_decompress_launch(s_c, 1, by, 192, n, 0, en, pts, 48, fl, 3, st3, 3);
+            vb_decompress_launch(s_b, 1, by + 144, 192, n, 0, en, pts + 36, 48, fl + 2, 3, st3 + 2, 3);
+        }
+        ZK_HIP(hipEventRecord(e_c, s_c));
+        ZK_HIP(hipEventRecord(e_b, s_b));
+        ZK_HIP(hipStreamWaitEvent(s_main, e_c, 0));
+        ZK_HIP(hipStreamWaitEvent(s_main, e_b, 0));
+        ZK_HIP(hipEventRecord(e_d1, s_main));
+        // the decoded proofs travel to the host behind the kernels below; they are first read after the membership verdicts
+        dec_proofs.resize(48 * k);
+        dec_inf.resize(3 * k);
+        dec_st.resize(3 * k);
+        b.proofs = dec_proofs.data();
+        b.inf = dec_inf.data();
+    } else {
+        upload_h2d(ctx, d_proofs.p, b.proofs, k * 48 * 8);
+        ZK_HIP(hipMemcpyAsync(d_inf.p, b.inf, 3 * k, hipMemcpyHostToDevice, s_main));
+        ZK_HIP(hipMemcpyAsync(d_rho.p, b.rho, k * 16, hipMemcpyHostToDevice, s_main));
+    }
     ZK_HIP(hipEventRecord(e_up, s_main));
     for (hipStream_t st : {s_mil, s_c, s_b}) ZK_HIP(hipStreamWaitEvent(st, e_up, 0));
     ZK_HIP(hipEventRecord(e_m0, s_mil));
-    const VbEndo en = vb_endo();
     for (size_t off = 0; off < k; off += VB_PASS) {
         const size_t n = std::min(VB_PASS, k - off);
         const uint64_t *pts = d_proofs.as<uint64_t>() + 48 * off;
@@ -2637,12 +2659,27 @@ int zkg16_verify_batch(zkg16_ctx *ctx, const uint64_t *gamma_abc_g1, size_t num_
     ZK_HIP(hipStreamWaitEvent(s_main, e_b, 0));
     std::vector<uint8_t> mem3(3 * k), member(k);
     ZK_HIP(hipMemcpyAsync(mem3.data(), d_mem3.p, 3 * k, hipMemcpyDeviceToHost, s_main));
+    if (wire) {
+        ZK_HIP(hipMemcpyAsync(dec_proofs.data(), d_proofs.p, k * 48 * 8, hipMemcpyDeviceToHost, s_main));
+        ZK_HIP(hipMemcpyAsync(dec_inf.data(), d_inf.p, 3 * k, hipMemcpyDeviceToHost, s_main));
+        ZK_HIP(hipMemcpyAsync(dec_st.data(), d_st.p, 3 * k, hipMemcpyDeviceToHost, s_main));
+    }
     ZK_HIP(hipStreamSynchronize(s_main));
     // host clock, launch to verdicts on the host (what the MSM below waits for), not kernel time: measured, it equals the Miller
     // kernel's time — the verdicts do not reach the host before that kernel ends
     tm[0] = (float)(now_ms() - t_launched);
+    if (wire) tm[8] = vb_elapsed(e_d0, e_d1);
     size_t n_live = 0;
-    for (size_t i = 0; i < k; i++) n_live += member[i] = mem3[3 * i] && mem3[3 * i + 1] && mem3[3 * i + 2] ? 1 : 0;
+    for (size_t i = 0; i < k; i++) {
+        bool good = mem3[3 * i] && mem3[3 * i + 1] && mem3[3 * i + 2];
+        // an undecodable point left zero limbs behind, which no curve holds; the status decides all the same
+        if (wire) good = good && !dec_st[3 * i] && !dec_st[3 * i + 1] && !dec_st[3 * i + 2];
+        n_live += member[i] = good ? 1 : 0;
+    }
+    if (wire && decode_status)
+        for (size_t j = 0; j < 3 * k; j++) decode_status[j] = dec_st[j] ? dec_st[j] : (mem3[j] ? 0 : 5);
+    const uint64_t *proofs = b.proofs, *rho = b.rho;
+    const uint8_t *inf = b.inf;
     // sum rho_k C_k over the member proofs: the ctx's G1 MSM, beside the Miller kernel
     uint64_t sum_c[12] = {0};
     uint8_t sum_c_inf = 1;
@@ -2687,6 +2724,94 @@ int zkg16_verify_batch(zkg16_ctx *ctx, const uint64_t *gamma_abc_g1, size_t num_
     vb_publish(root, tm);
     ZK_LANE_END(ctx)
 }
+}  // namespace
+
+extern "C" {
+
+int zkg16_verify_batch(zkg16_ctx *ctx, const uint64_t *gamma_abc_g1, size_t num_instance, const uint64_t alpha_beta[72], const uint64_t *gamma_neg_coeffs,
+                       const uint64_t *delta_neg_coeffs, size_t n_coeffs, const uint64_t *public_inputs, const uint64_t *proofs, const uint8_t *inf,
+                       const uint64_t *rho, size_t k, int *ok, uint8_t *ok_each) {
+    if (!ctx) return ZKG16_ERR_BAD_ARG;
+    const VbKey key{gamma_abc_g1, num_instance, alpha_beta, gamma_neg_coeffs, delta_neg_coeffs, n_coeffs};
+    const VbBatch b{public_inputs, proofs, inf, rho, k};
+    const int rc = vb_check_args(key, b, ok);
+    if (rc != ZKG16_OK) return rc;
+    const double t_all = now_ms();
+    if (k < (size_t)ctx->opt_verify_batch_min) {
+        float tm[9] = {0};
+        try {
+            vb_host(key, b, 0, ok, ok_each);
+        } catch (const std::bad_alloc &) {
+            return ZKG16_ERR_OOM;
+        }
+        tm[6] = (float)(now_ms() - t_all);
+        tm[7] = 1;
+        vb_publish(ctx, tm);
+        return ZKG16_OK;
+    }
+    return vb_device(ctx, key, b, nullptr, ok, ok_each, nullptr, t_all);
+}
+
+int zkg16_verify_batch_wire(zkg16_ctx *ctx, const uint64_t *gamma_abc_g1, size_t num_instance, const uint64_t alpha_beta[72], const uint64_t *gamma_neg_coeffs,
+                            const uint64_t *delta_neg_coeffs, size_t n_coeffs, const uint64_t *public_inputs, const uint8_t *proof_bytes,
+                            const uint64_t *rho, size_t k, int *ok, uint8_t *ok_each, uint8_t *decode_status) {
+    if (!ctx || !proof_bytes) return ZKG16_ERR_BAD_ARG;
+    const VbKey key{gamma_abc_g1, num_instance, alpha_beta, gamma_neg_coeffs, delta_neg_coeffs, n_coeffs};
+    {
+        // the checks of zkg16_verify_batch: the bytes stand in for the limbs and flags that do not exist yet
+        const VbBatch probe{public_inputs, reinterpret_cast<const uint64_t *>(proof_bytes), proof_bytes, rho, k};
+        const int rc = vb_check_args(key, probe, ok);
+        if (rc != ZKG16_OK) return rc;
+    }
+    const double t_all = now_ms();
+    if (k < (size_t)ctx->opt_verify_wire_min) {
+        float tm[9] = {0};
+        try {
+            // status 5 costs the subgroup tests a second time (vb_host makes its own): only for a caller who asks for the statuses
+            std::vector<uint64_t> proofs(48 * k);
+            std::vector<uint8_t> inf(3 * k), st(3 * k);
+            vb_wire_decode_host(proof_bytes, k, decode_status ? 1 : 0, 0, proofs.data(), inf.data(), st.data());
+            tm[8] = (float)(now_ms() - t_all);
+            std::vector<uint8_t> dead(k);
+            for (size_t i = 0; i < k; i++) dead[i] = st[3 * i] || st[3 * i + 1] || st[3 * i + 2] ? 1 : 0;
+            const VbBatch b{public_inputs, proofs.data(), inf.data(), rho, k};
+            vb_host(key, b, 0, ok, ok_each, dead.data());
+            if (decode_status) memcpy(decode_status, st.data(), 3 * k);
+        } catch (const std::bad_alloc &) {
+            return ZKG16_ERR_OOM;
+        }
+        tm[6] = (float)(now_ms() - t_all);
+        tm[7] = 1;
+        vb_publish(ctx, tm);
+        return ZKG16_OK;
+    }
+    return vb_device(ctx, key, VbBatch{public_inputs, nullptr, nullptr, rho, k}, proof_bytes, ok, ok_each, decode_status, t_all);
+}
+
+int zkg16_points_decompress_batch(zkg16_ctx *ctx, int group, const uint8_t *bytes, size_t n, uint64_t *out, uint8_t *inf, int validate, int *status) {
+    if (!ctx || (group != 1 && group != 2) || ((!bytes || !out || !inf) && n)) return ZKG16_ERR_BAD_ARG;
+    if (!n) return ZKG16_OK;
+    ZK_LANE_BEGIN(ctx)
+    const size_t w = group == 1 ? 12 : 24, nb = group == 1 ? 48 : 96;
+    DevBuf d_b(n * nb), d_p(n * w * 8), d_i(n), d_s(n);
+    upload_h2d(ctx, d_b.p, bytes, n * nb);
+    const VbEndo en = vb_endo();
+    for (size_t off = 0; off < n; off += VB_PASS)
+        vb_decompress_launch(ctx->stream, group, d_b.as<uint8_t>() + nb * off, nb, std::min(VB_PASS, n - off), validate, en, d_p.as<uint64_t>() + w * off, w,
+                             d_i.as<uint8_t>() + off, 1, d_s.as<uint8_t>() + off, 1);
+    std::vector<uint8_t> st(n);
+    ZK_HIP(hipMemcpyAsync(out, d_p.p, n * w * 8, hipMemcpyDeviceToHost, ctx->stream));
+    ZK_HIP(hipMemcpyAsync(inf, d_i.p, n, hipMemcpyDeviceToHost, ctx->stream));
+    ZK_HIP(hipMemcpyAsync(st.data(), d_s.p, n, hipMemcpyDeviceToHost, ctx->stream));
+    ZK_HIP(hipStreamSynchronize(ctx->stream));
+    bool any_bad = false;
+    for (size_t i = 0; i < n; i++) {
+        if (status) status[i] = st[i];
+        any_bad = any_bad || st[i];
+    }
+    if (any_bad) return ZKG16_ERR_BAD_ARG;
+    ZK_LANE_END(ctx)
+}
 
 int zkg16_miller_loop_batch(zkg16_ctx *ctx, const uint64_t *g1, const uint8_t *g1_inf, const uint64_t *g2, const uint8_t *g2_inf, size_t n, uint64_t *f_out) {
     if (!ctx || ((!g1 || !g2 || !f_out) && n)) return ZKG16_ERR_BAD_ARG;
@@ -2725,7 +2850,7 @@ int zkg16_point_check_batch(zkg16_ctx *ctx, int group, const uint64_t *points, c
 int zkg16_verify_batch_timings(zkg16_ctx *ctx, float *ms, int cap) {
     if (!ctx || !ms || cap < 0) return ZKG16_ERR_BAD_ARG;
     std::lock_guard<std::mutex> lk(ctx->lane_mu);
-    const int n = cap < 8 ? cap : 8;
+    const int n = cap < 9 ? cap : 9;
     memcpy(ms, ctx->vb_timings, n * sizeof(float));
     return n;
 }

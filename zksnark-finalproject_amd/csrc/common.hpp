@@ -237,6 +237,10 @@ struct MsmWorkspace {       // grown on demand, reused across proofs
 // zkg16_verify_batch answers batches shorter than this on the host: the smallest measured K at which the device form beat the host
 // form on eight threads (profiles/verify_batch_timing_r8.txt)
 #define ZKG16_VERIFY_BATCH_MIN_DEFAULT 1024
+// the smallest measured K at which zkg16_verify_batch_wire beat both host-decoding routes in every round: 0.094 ms per proof against
+// 0.239 (host decode + host form on 8 threads) and 0.245 (host decode + kernels); at K = 64 it lost, 0.361 against 0.270
+// (profiles/verify_wire_timing_r9.txt)
+#define ZKG16_VERIFY_WIRE_MIN_DEFAULT 256
 
 struct zkg16_ctx {
     int device = 0;
@@ -309,7 +313,8 @@ struct zkg16_ctx {
     int opt_wm_transforms = 6;                        // witness map: 6 (default) = C only inverse-transformed, subtracted on the last store; 7 = arkworks' sequence
     int opt_batch_max = 0;                            // zkg16_prove_batch: proofs per device pass (0 = as many as fit)
     int opt_verify_batch_min = ZKG16_VERIFY_BATCH_MIN_DEFAULT;                   // zkg16_verify_batch: shorter batches are answered by the host form (the measured crossover)
-    float vb_timings[8] = {0};                        // zkg16_verify_batch_timings (root: the last batch verified on any lane)
+    int opt_verify_wire_min = ZKG16_VERIFY_WIRE_MIN_DEFAULT;                     // zkg16_verify_batch_wire: shorter batches are decoded and answered on the host (the measured crossover)
+    float vb_timings[9] = {0};                        // zkg16_verify_batch_timings (root: the last batch verified on any lane)
     int num_cus = 256;
     bool lds_attr_fixup[2] = {false, false}, lds_attr_ntt = false;      // hipFuncSetAttribute(max dynamic LDS) done on this device
     zk::FixedBaseCache fb_g1, fb_g2;

@@ -1048,7 +1048,7 @@ void vb_decide(const VbKey &key, const VbBatch &b, const uint8_t *member, const 
     }
 }
 
-void vb_host(const VbKey &key, const VbBatch &b, int threads, int *ok, uint8_t *ok_each) {
+void vb_host(const VbKey &key, const VbBatch &b, int threads, int *ok, uint8_t *ok_each, const uint8_t *dead) {
     (void)pf::endo();                // the function-local statics exist before any helper thread asks for them
     (void)pf::consts();
     (void)pf::frob_coeffs();
@@ -1061,7 +1061,7 @@ void vb_host(const VbKey &key, const VbBatch &b, int threads, int *ok, uint8_t *
                 const uint64_t *pr = b.proofs + 48 * k;
                 const G1Affine A = load_pt<G1Affine>(pr, b.inf[3 * k]), C = load_pt<G1Affine>(pr + 36, b.inf[3 * k + 2]);
                 const G2Affine B = load_pt<G2Affine>(pr + 12, b.inf[3 * k + 1]);
-                member[k] = g1_valid(A) && g2_valid(B) && g1_valid(C) ? 1 : 0;
+                member[k] = !(dead && dead[k]) && g1_valid(A) && g2_valid(B) && g1_valid(C) ? 1 : 0;
                 pf::F12 f = pf::f12_one();
                 pf::Fq64 ax, ay;
                 if (member[k] && !A.is_inf() && !B.is_inf() && vb_affine(pf::pt_mul(pf::g1_pt(A), b.rho + 2 * k, 2), ax, ay)) {
@@ -1076,6 +1076,25 @@ void vb_host(const VbKey &key, const VbBatch &b, int threads, int *ok, uint8_t *
     });
     if (oom.load()) throw std::bad_alloc();
     vb_decide(key, b, member.data(), [&] { return (const uint64_t *)miller.data(); }, nullptr, nullptr, nullptr, threads, ok, ok_each, nullptr);
+}
+
+// zkg16_verify_batch_wire below its threshold: the host decoders, one proof at a time, spread over threads (zkg16_g2_decompress
+// itself does not thread over n)
+void vb_wire_decode_host(const uint8_t *proof_bytes, size_t k, int validate, int threads, uint64_t *proofs, uint8_t *inf, uint8_t *status) {
+    (void)fq_consts();               // the function-local statics exist before any helper thread asks for them
+    (void)pf::endo();
+    vb_parallel(k, threads, 1, [&](size_t lo, size_t hi) {
+        for (size_t i = lo; i < hi; i++) {
+            const uint8_t *b = proof_bytes + 192 * i;
+            uint64_t *o = proofs + 48 * i;
+            uint8_t *fl = inf + 3 * i;
+            int st[3] = {0, 0, 0};
+            (void)g1_decompress_range(b, 0, 1, o, fl, validate, st);
+            (void)zkg16_g2_decompress(b + 48, 1, o + 12, fl + 1, validate, st + 1);
+            (void)g1_decompress_range(b + 144, 0, 1, o + 36, fl + 2, validate, st + 2);
+            for (int j = 0; j < 3; j++) status[3 * i + j] = (uint8_t)st[j];
+        }
+    });
 }
 
 }  // namespace zk

@@ -5,6 +5,7 @@
 //   membership_kernel     curve equation + endomorphism subgroup test of n points of one group
 //   miller_batch_kernel   (rho_i P_i when multipliers are given, back to affine, then) the Miller loop of (P_i, Q_i): 72 u64 each
 //   fq12_product_kernel   one round of the product tree over Fq12 values
+//   decompress_kernel     n compressed points of one group (48 / 96 wire bytes each) to affine Montgomery limbs (decompress_dev.cuh)
 //
 // Registers: a Miller lane's state is f (12 Fq = 168 dwords), T (84), Q and P (84) and the operation at hand; every Fq product is a
 // call (ffu.cuh: fqu_mul_call), so what is live across it sits in the callee-saved registers or in scratch: 4,272 B of scratch
@@ -13,6 +14,7 @@
 #include "verify_batch.hpp"
 
 #include "common.hpp"
+#include "decompress_dev.cuh"
 #include "pairing_dev.cuh"
 
 namespace zk {
@@ -77,6 +79,27 @@ __global__ __launch_bounds__(64) void fq12_product_kernel(const uint64_t *in, co
     for (int t = 0; t < 6; t++) o[t] = s[t];
 }
 
+// point i: bytes + i * byte_stride -> out + i * stride (u64 units: 12 / 24 limbs), inf[i * inf_stride], status[i * status_stride]
+__global__ __launch_bounds__(64) void decompress_kernel(int group, const uint8_t *bytes, size_t byte_stride, size_t n, int validate, VbEndo en, uint64_t *out,
+                                                        size_t stride, uint8_t *inf, size_t inf_stride, uint8_t *status, size_t status_stride) {
+    const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    const uint8_t *b = bytes + i * byte_stride;
+    uint8_t fl = 0;
+    int st;
+    if (group == 1) {
+        G1Affine p;
+        st = dc::g1_decompress(b, validate != 0, en.beta, en.fast_g1 != 0, p, fl);
+        *reinterpret_cast<G1Affine *>(out + i * stride) = p;
+    } else {
+        G2Affine p;
+        st = dc::g2_decompress(b, validate != 0, en.cx, en.cy, en.fast_g2 != 0, p, fl);
+        *reinterpret_cast<G2Affine *>(out + i * stride) = p;
+    }
+    inf[i * inf_stride] = fl;
+    status[i * status_stride] = (uint8_t)st;
+}
+
 unsigned blocks_of(size_t n) { return (unsigned)((n + 63) / 64); }
 
 }  // namespace
@@ -92,6 +115,14 @@ void vb_miller_launch(hipStream_t st, const uint64_t *g1, size_t g1_stride, cons
                       size_t inf_stride, const uint64_t *rho, size_t n, uint64_t *out) {
     if (!n) return;
     hipLaunchKernelGGL(miller_batch_kernel, dim3(blocks_of(n)), dim3(64), 0, st, g1, g1_stride, g1_inf, g2, g2_stride, g2_inf, inf_stride, rho, n, out);
+    ZK_HIP(hipGetLastError());
+}
+
+void vb_decompress_launch(hipStream_t st, int group, const uint8_t *bytes, size_t byte_stride, size_t n, int validate, const VbEndo &en, uint64_t *out,
+                          size_t stride, uint8_t *inf, size_t inf_stride, uint8_t *status, size_t status_stride) {
+    if (!n) return;
+    hipLaunchKernelGGL(decompress_kernel, dim3(blocks_of(n)), dim3(64), 0, st, group, bytes, byte_stride, n, validate, en, out, stride, inf, inf_stride, status,
+                       status_stride);
     ZK_HIP(hipGetLastError());
 }
 

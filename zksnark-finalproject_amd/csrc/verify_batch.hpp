@@ -44,8 +44,12 @@ int vb_check_args(const VbKey &key, const VbBatch &b, const int *ok);
 // ms (nullable): ms[0] += coefficients + the batch equation, ms[1] += bisecting (the fetch included).
 void vb_decide(const VbKey &key, const VbBatch &b, const uint8_t *member, const std::function<const uint64_t *()> &fetch_miller, const uint64_t *prod,
                const uint64_t *sum_c, const uint8_t *sum_c_inf, int threads, int *ok, uint8_t *ok_each, float ms[2]);
-// everything on host threads (zkg16_verify_batch_host)
-void vb_host(const VbKey &key, const VbBatch &b, int threads, int *ok, uint8_t *ok_each);
+// everything on host threads (zkg16_verify_batch_host).  dead (nullable, k bytes): proofs counted as failing membership whatever
+// their limbs say (zkg16_verify_batch_wire: a proof with a point that did not decode; its zero limbs would read as infinity)
+void vb_host(const VbKey &key, const VbBatch &b, int threads, int *ok, uint8_t *ok_each, const uint8_t *dead = nullptr);
+// k x 192 proof bytes (A 48 | B 96 | C 48) decoded on up to `threads` host threads (0 = 8) by the host decoders' rules:
+// proofs k x 48, inf k x 3, status k x 3 (A, B, C); validate != 0 adds the subgroup test (status 5)
+void vb_wire_decode_host(const uint8_t *proof_bytes, size_t k, int validate, int threads, uint64_t *proofs, uint8_t *inf, uint8_t *status);
 // the endomorphism constants the host calibrated at start-up, saturated limbs, for the membership kernel
 struct VbEndo {
     Fq beta;
@@ -62,6 +66,12 @@ void vb_membership_launch(hipStream_t st, int group, const uint64_t *pts, size_t
 // out[i] (72 u64) = ML(rho_i P_i, Q_i); rho (2 u64 per pair) null = no scaling; a pair with P or Q at infinity gives one
 void vb_miller_launch(hipStream_t st, const uint64_t *g1, size_t g1_stride, const uint8_t *g1_inf, const uint64_t *g2, size_t g2_stride, const uint8_t *g2_inf,
                       size_t inf_stride, const uint64_t *rho, size_t n, uint64_t *out);
+// n compressed points of one group (1: 48 bytes, 2: 96 bytes) at bytes + i * byte_stride -> affine Montgomery limbs at
+// out + i * stride (u64 units), the infinity flag at inf[i * inf_stride] and the status of zkg16_g1_decompress / zkg16_g2_decompress
+// at status[i * status_stride] (0 ok ... 5 not in the subgroup, only with validate; limbs zero for statuses 1 to 4).  The strides let
+// the three points of k x 192 proof bytes land in the k x 48 limb array the launches above read
+void vb_decompress_launch(hipStream_t st, int group, const uint8_t *bytes, size_t byte_stride, size_t n, int validate, const VbEndo &en, uint64_t *out,
+                          size_t stride, uint8_t *inf, size_t inf_stride, uint8_t *status, size_t status_stride);
 // the product of f[0 .. n) by a tree (log2 n rounds); f is only read, and f[k] counts as one where live[k] == 0 (live nullable).
 // tmp: room for 2 * ((n + 1) / 2) * 72 u64.  Returns where the product (72 u64) will lie, inside tmp
 const uint64_t *vb_product_launch(hipStream_t st, const uint64_t *f, const uint8_t *live, size_t n, uint64_t *tmp);

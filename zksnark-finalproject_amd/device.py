@@ -239,11 +239,50 @@ class Device:
         self._check(self.lib.zkg16_verify_batch(self.ctx, *args, C.byref(ok), _ptr(ok_each)))
         return (bool(ok.value), ok_each.astype(bool)) if each else bool(ok.value)
 
+    def verify_batch_wire(self, pvk, public_inputs, proof_bytes, rho=None, each=False, status=False):
+        """verify_batch from the proofs as they travel (zkg16_verify_batch_wire): proof_bytes = k x 192 compressed bytes (bytes, or
+        a uint8 array), decoded on the device.  A proof that does not decode counts as invalid and leaves the others' verdicts alone.
+        -> all_valid, followed by the per-proof bool array with each=True and by the [k, 3] decode statuses (A, B, C: 0 ok ... 5
+        not in the subgroup, as the validating host decoder reports them) with status=True.  Batches shorter than the option
+        "verify_wire_min" are decoded and answered on the host."""
+        raw = np.ascontiguousarray(np.frombuffer(proof_bytes, dtype=np.uint8) if isinstance(proof_bytes, (bytes, bytearray, memoryview))
+                                   else np.asarray(proof_bytes, dtype=np.uint8)).reshape(-1)
+        if raw.size % 192:
+            raise ValueError("verify_batch_wire: a compressed proof is 192 bytes")
+        k = raw.size // 192
+        args, _ = _verify_batch_args(pvk, public_inputs, None, None, rho, k=k)
+        ok = C.c_int(0)
+        ok_each = np.zeros(k, dtype=np.uint8) if each else None
+        st = np.zeros((k, 3), dtype=np.uint8) if status else None
+        self._check(self.lib.zkg16_verify_batch_wire(self.ctx, *args[:7], _ptr(raw) if k else None, args[9], k, C.byref(ok), _ptr(ok_each), _ptr(st)))
+        out = (bool(ok.value),) + ((ok_each.astype(bool),) if each else ()) + ((st,) if status else ())
+        return out if len(out) > 1 else out[0]
+
+    def decompress_batch(self, group, data, validate=True):
+        """n compressed points of one group back to back, decoded on the device (zkg16_points_decompress_batch) ->
+        (limbs [n, 12 | 24], infinity flags [n], statuses [n]).  Nothing raises for a point that does not decode: its status says why
+        (1 not compressed, 2 non-canonical infinity, 3 x not reduced, 4 not on the curve, 5 not in the subgroup) and its limbs are
+        what the host decoders leave."""
+        size, width = (48, 12) if group == "g1" else (96, 24)
+        raw = np.ascontiguousarray(np.frombuffer(bytes(data), dtype=np.uint8))
+        if raw.size % size:
+            raise ValueError("decompress_batch: a compressed %s point is %d bytes" % (group.upper(), size))
+        n = raw.size // size
+        out = np.zeros((n, width), dtype=np.uint64)
+        inf = np.zeros(n, dtype=np.uint8)
+        status = np.zeros(max(n, 1), dtype=np.int32)
+        rc = self.lib.zkg16_points_decompress_batch(self.ctx, 1 if group == "g1" else 2, _ptr(raw) if n else None, n, _ptr(out) if n else None,
+                                                    _ptr(inf) if n else None, 1 if validate else 0, status.ctypes.data_as(C.POINTER(C.c_int)))
+        if rc != 0 and not status[:n].any():
+            self._check(rc)
+        return out, inf, status[:n].copy()
+
     def verify_batch_timings(self):
-        """ms of the last verify_batch: membership, scaling + Miller, product tree, MSM, host equation, bisecting, total wall."""
-        ms = (C.c_float * 8)()
-        n = self.lib.zkg16_verify_batch_timings(self.ctx, ms, 8)
-        names = ("membership_ms", "miller_ms", "product_ms", "msm_ms", "host_ms", "bisect_ms", "total_ms", "host_form")
+        """ms of the last verify_batch / verify_batch_wire: membership, scaling + Miller, product tree, MSM, host equation, bisecting,
+        total wall, whether the host form answered, and the decode kernels (verify_batch_wire only)."""
+        ms = (C.c_float * 9)()
+        n = self.lib.zkg16_verify_batch_timings(self.ctx, ms, 9)
+        names = ("membership_ms", "miller_ms", "product_ms", "msm_ms", "host_ms", "bisect_ms", "total_ms", "host_form", "decode_ms")
         return {names[i]: float(ms[i]) for i in range(n)}
 
     def miller_loop_batch(self, g1, g2, g1_inf=None, g2_inf=None):
@@ -597,15 +636,16 @@ def draw_rho(k):
     return out
 
 
-def _verify_batch_args(pvk, public_inputs, proofs, infs, rho):
+def _verify_batch_args(pvk, public_inputs, proofs, infs, rho, k=None):
+    """the argument tuple the batch entry points share; proofs = infs = None with k given: the wire form, which has no limbs yet"""
     gabc = _u64(pvk["gamma_abc_g1"]).reshape(-1, 12)
-    proofs = _u64(proofs).reshape(-1, 48)
-    k = proofs.shape[0]
-    infs = np.ascontiguousarray(infs, dtype=np.uint8).reshape(-1, 3)
+    proofs = _u64(proofs).reshape(-1, 48) if proofs is not None else None
+    k = proofs.shape[0] if proofs is not None else k
+    infs = np.ascontiguousarray(infs, dtype=np.uint8).reshape(-1, 3) if proofs is not None else None
     pub = _u64(public_inputs).reshape(k, -1, 4) if k else _u64(public_inputs).reshape(0, gabc.shape[0] - 1, 4)
     if pub.shape[1] != gabc.shape[0] - 1:
         raise ValueError("verify_batch: %d public inputs per proof for a key with %d instance variables" % (pub.shape[1], gabc.shape[0]))
-    if infs.shape[0] != k:
+    if infs is not None and infs.shape[0] != k:
         raise ValueError("verify_batch: one flag triple per proof")
     rho = draw_rho(k) if rho is None else _u64(rho).reshape(-1, 2)
     if rho.shape[0] != k:

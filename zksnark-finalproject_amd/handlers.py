@@ -255,9 +255,9 @@ def verify_proof(vk, public_inputs_mont, proof_b64):
 
 
 def verify_proofs(vk, public_inputs_list, proofs_b64, dev=None):
-    """verify_proof for K proofs under one key, checked together (Device.verify_batch with `dev`, else the host form
-    verify_batch_host): one final exponentiation for the batch instead of one per proof.  -> {valid: [K bools], verifying_time,
-    decode_time}.  A proof that does not decode, or whose public inputs have the wrong shape, is valid=False for that entry only;
+    """verify_proof for K proofs under one key, checked together (Device.verify_batch_wire with `dev`: the compressed proofs are
+    decoded on the device; else host decoding and the host form verify_batch_host): one final exponentiation for the batch instead
+    of one per proof.  -> {valid: [K bools], verifying_time, decode_time}.  A proof that does not decode, or whose public inputs have the wrong shape, is valid=False for that entry only;
     a key that does not decode makes every entry invalid."""
     from ._lib import Zkg16Error
     from .device import pvk_prepare, verify_batch_host
@@ -275,6 +275,26 @@ def verify_proofs(vk, public_inputs_list, proofs_b64, dev=None):
         ni = np.asarray(pvk["gamma_abc_g1"]).reshape(-1, 12).shape[0]
     except (ValueError, IndexError, Zkg16Error):
         return dict(valid=valid, verifying_time=0.0, decode_time=time.perf_counter() - t0)
+    if dev is not None:
+        # the proofs stay bytes: base64 and the shape checks here, the square roots in a kernel (Device.verify_batch_wire)
+        idx, raws, pubs = [], [], []
+        for i, (pub, pb) in enumerate(zip(public_inputs_list, proofs_b64)):
+            try:
+                raw = __import__("base64").standard_b64decode(pb)
+                pub = np.ascontiguousarray(pub, dtype=np.uint64).reshape(-1, 4)
+                if len(raw) != 192 or pub.shape[0] != ni - 1:
+                    continue
+            except (ValueError, IndexError, TypeError):
+                continue
+            idx.append(i)
+            raws.append(raw)
+            pubs.append(pub)
+        t1 = time.perf_counter()
+        if idx:
+            _, each = dev.verify_batch_wire(pvk, np.array(pubs, dtype=np.uint64).reshape(len(idx), ni - 1, 4), b"".join(raws), each=True)
+            for i, ok in zip(idx, each):
+                valid[i] = bool(ok)
+        return dict(valid=valid, verifying_time=time.perf_counter() - t1, decode_time=t1 - t0)
     idx, proofs, infs, pubs = [], [], [], []
     for i, (pub, pb) in enumerate(zip(public_inputs_list, proofs_b64)):
         try:
