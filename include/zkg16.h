@@ -304,6 +304,20 @@ ZKG16_API int zkg16_verify_batch_wire(zkg16_ctx *ctx, const uint64_t *gamma_abc_
                             const uint64_t *gamma_neg_coeffs, const uint64_t *delta_neg_coeffs, size_t n_coeffs,
                             const uint64_t *public_inputs, const uint8_t *proof_bytes, const uint64_t *rho, size_t k,
                             int *ok, uint8_t *ok_each, uint8_t *decode_status);
+/* Each proof's own verdict in one device pass: ok_each[i] (k bytes) = what zkg16_verify_prepared says of proof i alone, for every i,
+ * whatever the others are — no multipliers, the unscaled A_k, so the verdict is exact.  On a lane of the ctx, one GPU lane per proof:
+ * the membership kernels of zkg16_verify_batch, then for the proofs that passed X_k = gamma_abc[0] + sum_i z_{k,i} gamma_abc[i], the
+ * three-pair Miller loop ML(A_k, B_k) ML(X_k, -gamma) ML(C_k, -delta) on the key's coefficients, the final exponentiation and the
+ * comparison with e(alpha, beta): a fixed number of launches per 65,536 proofs however many of them are bad.  Arguments as
+ * zkg16_verify_batch without rho; k == 0, null pointers and n_coeffs != 68: ZKG16_ERR_BAD_ARG before any work, ok_each untouched.
+ * zkg16_verify_batch and zkg16_verify_batch_wire run the same pass on the proofs bisecting has not decided once it has made option
+ * "verify_each_after" range tests (default 32: ceil(T_each / t_range) at K = 1024 = ceil(47.72 ms / 2.156 ms) = 23, the whole
+ * per-proof call against one range test of bisecting, both measured, rounded up to a power of two so that one bad proof — up to
+ * 2 log2 k range tests — never reaches the pass; profiles/verify_each_timing_r10.txt; 1 = after the first range
+ * test; a value above 2k never switches; 0 restores the default).  *ok and ok_each of those calls are what they were; only the time changes. */
+ZKG16_API int zkg16_verify_each(zkg16_ctx *ctx, const uint64_t *gamma_abc_g1, size_t num_instance, const uint64_t alpha_beta[72],
+                      const uint64_t *gamma_neg_coeffs, const uint64_t *delta_neg_coeffs, size_t n_coeffs,
+                      const uint64_t *public_inputs, const uint64_t *proofs, const uint8_t *inf, size_t k, uint8_t *ok_each);
 /* Stage entry: zkg16_g1_decompress / zkg16_g2_decompress (group 1 / 2) in a kernel on a lane of the ctx, one GPU lane per point.
  * Outputs, statuses (nullable) and the return code are the host functions': limbs zero for a point of status 1 to 4,
  * ZKG16_ERR_BAD_ARG when any point failed; n == 0 is ZKG16_OK. */
@@ -312,15 +326,20 @@ ZKG16_API int zkg16_points_decompress_batch(zkg16_ctx *ctx, int group, const uin
 /* Stage entries (tests / tools).  n Miller loops on the device, one GPU lane per pair: f_out[i] (72 u64, ark's tower order, the
  * layout of alpha_beta) = the Miller value of (g1[i], g2[i]) with ark's line scaling, one for a pair with a point at infinity (flag
  * bytes nullable); zkg16_final_exp of it is the pairing.  n membership tests on the device: ok_out[i] = what zkg16_point_check says
- * of point i (the point at infinity passes).  zkg16_final_exp: the verifier's final exponentiation, host-only. */
+ * of point i (the point at infinity passes).  zkg16_final_exp: the verifier's final exponentiation, host-only.
+ * zkg16_final_exp_batch: n of them on the device, one GPU lane each: out[i] (72 u64) is bit-equal to zkg16_final_exp(f[i]);
+ * n == 0 is ZKG16_OK. */
 ZKG16_API int zkg16_miller_loop_batch(zkg16_ctx *ctx, const uint64_t *g1, const uint8_t *g1_inf, const uint64_t *g2, const uint8_t *g2_inf, size_t n,
                             uint64_t *f_out);
 ZKG16_API int zkg16_point_check_batch(zkg16_ctx *ctx, int group, const uint64_t *points, const uint8_t *inf, size_t n, uint8_t *ok_out);
 ZKG16_API int zkg16_final_exp(const uint64_t f[72], uint64_t out[72]);
+ZKG16_API int zkg16_final_exp_batch(zkg16_ctx *ctx, const uint64_t *f /* n x 72 */, size_t n, uint64_t *out /* n x 72 */);
 /* The last zkg16_verify_batch / zkg16_verify_batch_wire on this ctx, in ms: [0] membership kernels (host clock: launch to the verdicts on the host, beside
  * the Miller kernel), [1] scaling + Miller kernel (device events), [2] product tree, [3] the MSM
  * sum rho_k C_k, [4] host coefficients and the batch equation, [5] bisecting, [6] total wall; [7] = 1 when the host form answered;
- * [8] zkg16_verify_batch_wire only: the decompress kernels (device events; the host decode's wall time when the host form answered).
+ * [8] zkg16_verify_batch_wire only: the decompress kernels (device events; the host decode's wall time when the host form answered);
+ * [9] the per-proof pass that took over from bisecting (device events; 0 when it did not run; its time is part of [5] too),
+ * [10] the number of range tests bisecting made.
  * Returns the number of entries written (at most cap). */
 ZKG16_API int zkg16_verify_batch_timings(zkg16_ctx *ctx, float *ms, int cap);
 

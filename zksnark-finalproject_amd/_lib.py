@@ -76,6 +76,8 @@ SIGNATURES = {
     "zkg16_miller_loop_batch": (C.c_int, [ctxp, vp, vp, vp, vp, sz, vp]),
     "zkg16_point_check_batch": (C.c_int, [ctxp, C.c_int, vp, vp, sz, vp]),
     "zkg16_final_exp": (C.c_int, [u64p, u64p]),
+    "zkg16_verify_each": (C.c_int, [ctxp, vp, sz, vp, vp, vp, sz, vp, vp, vp, sz, vp]),
+    "zkg16_final_exp_batch": (C.c_int, [ctxp, vp, sz, vp]),
     "zkg16_verify_batch_timings": (C.c_int, [ctxp, C.POINTER(C.c_float), C.c_int]),
     "zkg16_g1_decompress": (C.c_int, [vp, sz, vp, vp, C.c_int, C.POINTER(C.c_int)]),
     "zkg16_g2_decompress": (C.c_int, [vp, sz, vp, vp, C.c_int, C.POINTER(C.c_int)]),

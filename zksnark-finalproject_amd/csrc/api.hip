@@ -85,7 +85,7 @@ void copy_options(zkg16_ctx *dst, const zkg16_ctx *src) {
     dst->opt_ntt_radix = src->opt_ntt_radix; dst->opt_ntt_xcd = src->opt_ntt_xcd; dst->opt_acc_debug = src->opt_acc_debug;
     dst->opt_sort_mode = src->opt_sort_mode; dst->opt_acc_pipeline = src->opt_acc_pipeline; dst->opt_fuse_pointwise = src->opt_fuse_pointwise;
     dst->opt_matrix_parts = src->opt_matrix_parts; dst->opt_g2_lazy = src->opt_g2_lazy; dst->opt_g1_inline = src->opt_g1_inline; dst->opt_fixed_base_bits = src->opt_fixed_base_bits;
-    dst->opt_collect_threads = src->opt_collect_threads; dst->opt_batch_max = src->opt_batch_max; dst->opt_verify_batch_min = src->opt_verify_batch_min; dst->opt_verify_wire_min = src->opt_verify_wire_min; dst->opt_wm_transforms = src->opt_wm_transforms;
+    dst->opt_collect_threads = src->opt_collect_threads; dst->opt_batch_max = src->opt_batch_max; dst->opt_verify_batch_min = src->opt_verify_batch_min; dst->opt_verify_wire_min = src->opt_verify_wire_min; dst->opt_verify_each_after = src->opt_verify_each_after; dst->opt_wm_transforms = src->opt_wm_transforms;
     dst->kernel_timing = src->kernel_timing; dst->kernel_timing_accumulate_only = src->kernel_timing_accumulate_only;
 }
 void create_streams(zkg16_ctx *ctx) {
@@ -1176,6 +1176,11 @@ int set_option_one(zkg16_ctx *ctx, const char *name, int64_t value) {
     if (!strcmp(name, "verify_wire_min")) {    // zkg16_verify_batch_wire: batches shorter than this are decoded and answered on the host (0 restores the default; 1 = always the device)
         if (value < 0 || value > (1 << 30)) return ZKG16_ERR_BAD_ARG;
         ctx->opt_verify_wire_min = value == 0 ? ZKG16_VERIFY_WIRE_MIN_DEFAULT : (int)value;
+        return ZKG16_OK;
+    }
+    if (!strcmp(name, "verify_each_after")) {  // zkg16_verify_batch[_wire] with ok_each: range tests bisecting may make before the per-proof pass decides what is left (0 restores the default; 1 = after the first; above 2K = never)
+        if (value < 0 || value > (1 << 30)) return ZKG16_ERR_BAD_ARG;
+        ctx->opt_verify_each_after = value == 0 ? ZKG16_VERIFY_EACH_AFTER_DEFAULT : (int)value;
         return ZKG16_OK;
     }
     if (!strcmp(name, "reduce_chunk")) {
@@ -2582,9 +2587,36 @@ float vb_elapsed(hipEvent_t a, hipEvent_t b) {
     ZK_HIP(hipEventElapsedTime(&ms, a, b));
     return ms;
 }
-void vb_publish(zkg16_ctx *root, const float tm[9]) {
+void vb_publish(zkg16_ctx *root, const float tm[11]) {
     std::lock_guard<std::mutex> lk(root->lane_mu);
     memcpy(root->vb_timings, tm, sizeof root->vb_timings);
+}
+
+// The per-proof pass on the lane's main stream: the proofs idx[0 .. n) (null: 0 .. n - 1) of the k x 48 limbs / k x 3 flags already on
+// the device, each with its public inputs (pub(j): the (num_instance - 1) x 4 Montgomery limbs of the proof at position j), in
+// launches of VB_PASS.  The key is converted and uploaded once per call.  Returns the kernels' time in ms (device events)
+float vb_each_pass(zkg16_ctx *ctx, const VbKey &key, const uint64_t *d_proofs, const uint8_t *d_inf, const uint32_t *idx, size_t n,
+                   const std::function<const uint64_t *(size_t)> &pub, uint8_t *verdict) {
+    if (!n) return 0;
+    hipStream_t st = ctx->stream;
+    const size_t ni = key.num_instance, per = 4 * (ni - 1), pass = std::min(n, VB_PASS);
+    std::vector<uint32_t> words(vb_each_key_count(ni));
+    vb_each_key_words(key, words.data());
+    std::vector<uint64_t> z(std::max<size_t>(n * per, 1));
+    for (size_t j = 0; j < n && per; j++) vb_scalars_canonical(pub(j), ni - 1, z.data() + per * j);
+    DevBuf d_key(words.size() * 4), d_z(z.size() * 8), d_idx(idx ? n * 4 : 0), d_scratch(vb_each_scratch_bytes(pass)), d_verdict(n);
+    VbEvents evs;
+    ZK_HIP(hipMemcpyAsync(d_key.p, words.data(), words.size() * 4, hipMemcpyHostToDevice, st));
+    ZK_HIP(hipMemcpyAsync(d_z.p, z.data(), z.size() * 8, hipMemcpyHostToDevice, st));
+    if (idx) ZK_HIP(hipMemcpyAsync(d_idx.p, idx, n * 4, hipMemcpyHostToDevice, st));
+    ZK_HIP(hipEventRecord(evs.ev[0], st));
+    for (size_t off = 0; off < n; off += VB_PASS)
+        vb_each_launch(st, d_key.as<uint32_t>(), ni, idx ? d_idx.as<uint32_t>() + off : nullptr, std::min(VB_PASS, n - off), idx ? d_proofs : d_proofs + 48 * off,
+                       idx ? d_inf : d_inf + 3 * off, d_z.as<uint64_t>() + per * off, d_scratch.p, d_verdict.as<uint8_t>() + off);
+    ZK_HIP(hipEventRecord(evs.ev[1], st));
+    ZK_HIP(hipMemcpyAsync(verdict, d_verdict.p, n, hipMemcpyDeviceToHost, st));
+    ZK_HIP(hipStreamSynchronize(st));
+    return vb_elapsed(evs.ev[0], evs.ev[1]);
 }
 
 // The device form of both entry points.  wire == null: b.proofs / b.inf are the caller's limbs and flags.  wire != null (k x 192
@@ -2593,7 +2625,7 @@ void vb_publish(zkg16_ctx *root, const float tm[9]) {
 // decode_status (nullable, k x 3): the decode kernel's statuses, 5 where a decoded point failed membership.
 int vb_device(zkg16_ctx *ctx, const VbKey &key, VbBatch b, const uint8_t *wire, int *ok, uint8_t *ok_each, uint8_t *decode_status, double t_all) {
     const size_t k = b.k;
-    float tm[9] = {0};
+    float tm[11] = {0};
     ZK_LANE_BEGIN(ctx)
     hipStream_t s_main = ctx->stream, s_mil = ctx->wm_stream, s_c = ctx->slots[1].stream, s_b = ctx->slots[2].stream;
     VbEvents evs;
@@ -2715,11 +2747,19 @@ int vb_device(zkg16_ctx *ctx, const VbKey &key, VbBatch b, const uint8_t *wire, 
     tm[2] = vb_elapsed(e_p0, e_p1);
     // the K Miller values leave the device only when the batch equation failed and the caller wants to know where
     std::vector<uint64_t> miller;
+    // ... and when bisecting has used its budget of range tests, the proofs it left undecided stay here for the per-proof pass
+    VbEach each;
+    each.after = (size_t)ctx->opt_verify_each_after;
+    each.decide = [&](const uint32_t *idx, size_t n, uint8_t *verdict) {
+        const size_t per = 4 * (key.num_instance - 1);
+        tm[9] += vb_each_pass(ctx, key, d_proofs.as<uint64_t>(), d_inf.as<uint8_t>(), idx, n, [&](size_t j) { return b.public_inputs + per * idx[j]; }, verdict);
+    };
     vb_decide(key, b, member.data(), [&]() -> const uint64_t * {
         miller.resize(72 * k);
         ZK_HIP(hipMemcpy(miller.data(), d_f.p, k * 72 * 8, hipMemcpyDeviceToHost));
         return miller.data();
-    }, prod, sum_c, &sum_c_inf, 0, ok, ok_each, tm + 4);
+    }, prod, sum_c, &sum_c_inf, 0, ok, ok_each, tm + 4, &each);
+    tm[10] = (float)each.range_tests;
     tm[6] = (float)(now_ms() - t_all);
     vb_publish(root, tm);
     ZK_LANE_END(ctx)
@@ -2738,7 +2778,7 @@ int zkg16_verify_batch(zkg16_ctx *ctx, const uint64_t *gamma_abc_g1, size_t num_
     if (rc != ZKG16_OK) return rc;
     const double t_all = now_ms();
     if (k < (size_t)ctx->opt_verify_batch_min) {
-        float tm[9] = {0};
+        float tm[11] = {0};
         try {
             vb_host(key, b, 0, ok, ok_each);
         } catch (const std::bad_alloc &) {
@@ -2765,7 +2805,7 @@ int zkg16_verify_batch_wire(zkg16_ctx *ctx, const uint64_t *gamma_abc_g1, size_t
     }
     const double t_all = now_ms();
     if (k < (size_t)ctx->opt_verify_wire_min) {
-        float tm[9] = {0};
+        float tm[11] = {0};
         try {
             // status 5 costs the subgroup tests a second time (vb_host makes its own): only for a caller who asks for the statuses
             std::vector<uint64_t> proofs(48 * k);
@@ -2786,6 +2826,82 @@ int zkg16_verify_batch_wire(zkg16_ctx *ctx, const uint64_t *gamma_abc_g1, size_t
         return ZKG16_OK;
     }
     return vb_device(ctx, key, VbBatch{public_inputs, nullptr, nullptr, rho, k}, proof_bytes, ok, ok_each, decode_status, t_all);
+}
+
+int zkg16_verify_each(zkg16_ctx *ctx, const uint64_t *gamma_abc_g1, size_t num_instance, const uint64_t alpha_beta[72], const uint64_t *gamma_neg_coeffs,
+                      const uint64_t *delta_neg_coeffs, size_t n_coeffs, const uint64_t *public_inputs, const uint64_t *proofs, const uint8_t *inf, size_t k,
+                      uint8_t *ok_each) {
+    if (!ctx || !ok_each) return ZKG16_ERR_BAD_ARG;
+    const VbKey key{gamma_abc_g1, num_instance, alpha_beta, gamma_neg_coeffs, delta_neg_coeffs, n_coeffs};
+    {
+        // the checks of zkg16_verify_batch; there are no multipliers, so one non-zero pair stands in for them
+        const uint64_t some_rho[2] = {1, 0};
+        int ok_probe = 0;
+        const VbBatch probe{public_inputs, proofs, inf, some_rho, 1};
+        if (k == 0) return ZKG16_ERR_BAD_ARG;
+        const int rc = vb_check_args(key, probe, &ok_probe);
+        if (rc != ZKG16_OK) return rc;
+    }
+    ZK_LANE_BEGIN(ctx)
+    hipStream_t s_main = ctx->stream, s_c = ctx->slots[1].stream, s_b = ctx->slots[2].stream;
+    // zkg16_verify_prepared reads all-zero limbs as the point at infinity whatever the flag says: the same here
+    std::vector<uint8_t> fl(3 * k);
+    for (size_t i = 0; i < k; i++) {
+        const uint64_t *pr = proofs + 48 * i;
+        const size_t at[4] = {0, 12, 36, 48};
+        for (int j = 0; j < 3; j++) {
+            uint64_t any = 0;
+            for (size_t t = at[j]; t < at[j + 1]; t++) any |= pr[t];
+            fl[3 * i + j] = inf[3 * i + j] || !any ? 1 : 0;
+        }
+    }
+    VbEvents evs;
+    DevBuf d_proofs(k * 48 * 8), d_inf(3 * k), d_mem3(3 * k);
+    const VbEndo en = vb_endo();
+    upload_h2d(ctx, d_proofs.p, proofs, k * 48 * 8);
+    ZK_HIP(hipMemcpyAsync(d_inf.p, fl.data(), 3 * k, hipMemcpyHostToDevice, s_main));
+    ZK_HIP(hipEventRecord(evs.ev[0], s_main));
+    for (hipStream_t st : {s_c, s_b}) ZK_HIP(hipStreamWaitEvent(st, evs.ev[0], 0));
+    for (size_t off = 0; off < k; off += VB_PASS) {
+        const size_t n = std::min(VB_PASS, k - off);
+        const uint64_t *pts = d_proofs.as<uint64_t>() + 48 * off;
+        const uint8_t *f3 = d_inf.as<uint8_t>() + 3 * off;
+        uint8_t *m3 = d_mem3.as<uint8_t>() + 3 * off;
+        vb_membership_launch(s_main, 1, pts, 48, f3, 3, n, en, m3, 3);
+        vb_membership_launch(s_c, 1, pts + 36, 48, f3 + 2, 3, n, en, m3 + 2, 3);
+        vb_membership_launch(s_b, 2, pts + 12, 48, f3 + 1, 3, n, en, m3 + 1, 3);
+    }
+    ZK_HIP(hipEventRecord(evs.ev[1], s_c));
+    ZK_HIP(hipEventRecord(evs.ev[2], s_b));
+    ZK_HIP(hipStreamWaitEvent(s_main, evs.ev[1], 0));
+    ZK_HIP(hipStreamWaitEvent(s_main, evs.ev[2], 0));
+    std::vector<uint8_t> mem3(3 * k);
+    ZK_HIP(hipMemcpyAsync(mem3.data(), d_mem3.p, 3 * k, hipMemcpyDeviceToHost, s_main));
+    ZK_HIP(hipStreamSynchronize(s_main));
+    // proofs that failed membership are never listed
+    std::vector<uint32_t> idx;
+    for (size_t i = 0; i < k; i++)
+        if (mem3[3 * i] && mem3[3 * i + 1] && mem3[3 * i + 2]) idx.push_back((uint32_t)i);
+    std::vector<uint8_t> verdict(idx.size());
+    const size_t per = 4 * (num_instance - 1);
+    (void)vb_each_pass(ctx, key, d_proofs.as<uint64_t>(), d_inf.as<uint8_t>(), idx.size() == k ? nullptr : idx.data(), idx.size(),
+                       [&](size_t j) { return public_inputs + per * idx[j]; }, verdict.data());
+    memset(ok_each, 0, k);
+    for (size_t j = 0; j < idx.size(); j++) ok_each[idx[j]] = verdict[j] ? 1 : 0;
+    ZK_LANE_END(ctx)
+}
+
+int zkg16_final_exp_batch(zkg16_ctx *ctx, const uint64_t *f, size_t n, uint64_t *out) {
+    if (!ctx || ((!f || !out) && n)) return ZKG16_ERR_BAD_ARG;
+    if (!n) return ZKG16_OK;
+    ZK_LANE_BEGIN(ctx)
+    DevBuf d_f(n * 576);
+    upload_h2d(ctx, d_f.p, f, n * 576);
+    for (size_t off = 0; off < n; off += VB_PASS)
+        vb_final_exp_launch(ctx->stream, d_f.as<uint64_t>() + 72 * off, std::min(VB_PASS, n - off), d_f.as<uint64_t>() + 72 * off);
+    ZK_HIP(hipMemcpyAsync(out, d_f.p, n * 576, hipMemcpyDeviceToHost, ctx->stream));
+    ZK_HIP(hipStreamSynchronize(ctx->stream));
+    ZK_LANE_END(ctx)
 }
 
 int zkg16_points_decompress_batch(zkg16_ctx *ctx, int group, const uint8_t *bytes, size_t n, uint64_t *out, uint8_t *inf, int validate, int *status) {
@@ -2850,7 +2966,7 @@ int zkg16_point_check_batch(zkg16_ctx *ctx, int group, const uint64_t *points, c
 int zkg16_verify_batch_timings(zkg16_ctx *ctx, float *ms, int cap) {
     if (!ctx || !ms || cap < 0) return ZKG16_ERR_BAD_ARG;
     std::lock_guard<std::mutex> lk(ctx->lane_mu);
-    const int n = cap < 9 ? cap : 9;
+    const int n = cap < 11 ? cap : 11;
     memcpy(ms, ctx->vb_timings, n * sizeof(float));
     return n;
 }

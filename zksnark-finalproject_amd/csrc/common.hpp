@@ -241,6 +241,10 @@ struct MsmWorkspace {       // grown on demand, reused across proofs
 // 0.239 (host decode + host form on 8 threads) and 0.245 (host decode + kernels); at K = 64 it lost, 0.361 against 0.270
 // (profiles/verify_wire_timing_r9.txt)
 #define ZKG16_VERIFY_WIRE_MIN_DEFAULT 256
+// the range tests bisecting may make before the proofs still undecided go to the per-proof pass: ceil(T_each / t_range) at
+// K = 1024 = ceil(47.72 ms / 2.156 ms) = 23, rounded UP to a power of two — one bad proof needs up to 2 log2 K range tests
+// (19 to 22 measured at K = 16,384), and 16 would send that case to the pass (profiles/verify_each_timing_r10.txt)
+#define ZKG16_VERIFY_EACH_AFTER_DEFAULT 32
 
 struct zkg16_ctx {
     int device = 0;
@@ -314,7 +318,8 @@ struct zkg16_ctx {
     int opt_batch_max = 0;                            // zkg16_prove_batch: proofs per device pass (0 = as many as fit)
     int opt_verify_batch_min = ZKG16_VERIFY_BATCH_MIN_DEFAULT;                   // zkg16_verify_batch: shorter batches are answered by the host form (the measured crossover)
     int opt_verify_wire_min = ZKG16_VERIFY_WIRE_MIN_DEFAULT;                     // zkg16_verify_batch_wire: shorter batches are decoded and answered on the host (the measured crossover)
-    float vb_timings[9] = {0};                        // zkg16_verify_batch_timings (root: the last batch verified on any lane)
+    int opt_verify_each_after = ZKG16_VERIFY_EACH_AFTER_DEFAULT;                 // zkg16_verify_batch[_wire] with ok_each: range tests before the per-proof pass takes over
+    float vb_timings[11] = {0};                       // zkg16_verify_batch_timings (root: the last batch verified on any lane)
     int num_cus = 256;
     bool lds_attr_fixup[2] = {false, false}, lds_attr_ntt = false;      // hipFuncSetAttribute(max dynamic LDS) done on this device
     zk::FixedBaseCache fb_g1, fb_g2;

@@ -990,13 +990,35 @@ struct VbDecider {
         if (!in.empty()) f = pf::mul(f, pf::miller_loop(in));
         return pf::eq(pf::final_exp(f), vb_pow(ab, fp_from_mont(s[0])));
     }
+    // bisecting's budget (verify_batch.hpp: VbEach): once `range_tests` reaches it, the ranges find_bad would have tested next are
+    // collected in `open` instead, for the per-proof pass
+    zk::VbEach *each = nullptr;
+    std::vector<std::pair<size_t, size_t>> open;
+    bool spent() const { return each && each->decide && each->range_tests >= each->after; }
+    bool range_test(size_t lo, size_t hi) {
+        if (each) each->range_tests++;
+        return range_holds(lo, hi, nullptr, nullptr);
+    }
     // live[lo .. hi) is known to fail: mark the proofs that make it fail
     void find_bad(size_t lo, size_t hi, uint8_t *ok_each) {
         if (hi - lo == 1) { ok_each[live[lo]] = 0; return; }
+        if (spent()) { open.emplace_back(lo, hi); return; }
         const size_t mid = lo + (hi - lo) / 2;
-        const bool left = range_holds(lo, mid, nullptr, nullptr);
+        const bool left = range_test(lo, mid);
         if (!left) find_bad(lo, mid, ok_each);
-        if (left || !range_holds(mid, hi, nullptr, nullptr)) find_bad(mid, hi, ok_each);
+        if (left) find_bad(mid, hi, ok_each);                       // the whole fails and the left half holds: the right half fails
+        else if (spent()) open.emplace_back(mid, hi);               // nothing is known of the right half
+        else if (!range_test(mid, hi)) find_bad(mid, hi, ok_each);
+    }
+    // the proofs of the open ranges, decided one by one in one call
+    void decide_open(uint8_t *ok_each) {
+        std::vector<uint32_t> idx;
+        for (const auto &r : open)
+            for (size_t p = r.first; p < r.second; p++) idx.push_back(live[p]);
+        if (idx.empty()) return;
+        std::vector<uint8_t> verdict(idx.size(), 0);
+        each->decide(idx.data(), idx.size(), verdict.data());
+        for (size_t j = 0; j < idx.size(); j++) ok_each[idx[j]] = verdict[j] ? 1 : 0;
     }
 };
 }  // namespace
@@ -1023,10 +1045,28 @@ VbEndo vb_endo() {
     return e;
 }
 
+VbFrob vb_frob() {
+    const pf::Frob &f = pf::frob_coeffs();
+    VbFrob r;
+    for (int i = 0; i < 5; i++) r.g[i] = pf::to_sat(f.g[i + 1]);
+    return r;
+}
+
+void vb_scalars_canonical(const uint64_t *mont, size_t n, uint64_t *out) {
+    for (size_t i = 0; i < n; i++) {
+        Fr z;
+        memcpy(&z, mont + 4 * i, sizeof z);
+        const Fr c = fp_from_mont(z);
+        memcpy(out + 4 * i, c.l, 32);
+    }
+}
+
 void vb_decide(const VbKey &key, const VbBatch &b, const uint8_t *member, const std::function<const uint64_t *()> &fetch_miller, const uint64_t *prod,
-               const uint64_t *sum_c, const uint8_t *sum_c_inf, int threads, int *ok, uint8_t *ok_each, float ms[2]) {
+               const uint64_t *sum_c, const uint8_t *sum_c_inf, int threads, int *ok, uint8_t *ok_each, float ms[2], VbEach *each) {
     const double t0 = vb_now_ms();
     VbDecider dc(key, b, threads);
+    dc.each = each;
+    if (each) each->range_tests = 0;
     for (size_t k = 0; k < b.k; k++)
         if (member[k]) dc.live.push_back((uint32_t)k);
     if (!prod) dc.miller = fetch_miller();
@@ -1043,6 +1083,7 @@ void vb_decide(const VbKey &key, const VbBatch &b, const uint8_t *member, const 
         else {
             if (!dc.miller) dc.miller = fetch_miller();
             dc.find_bad(0, dc.live.size(), ok_each);
+            dc.decide_open(ok_each);
         }
         if (ms) ms[1] += (float)(vb_now_ms() - t1);
     }

@@ -6,6 +6,9 @@
 //   miller_batch_kernel   (rho_i P_i when multipliers are given, back to affine, then) the Miller loop of (P_i, Q_i): 72 u64 each
 //   fq12_product_kernel   one round of the product tree over Fq12 values
 //   decompress_kernel     n compressed points of one group (48 / 96 wire bytes each) to affine Montgomery limbs (decompress_dev.cuh)
+//   each_x_kernel         the prepared public input X of each listed proof, to affine (pairing_each_dev.cuh, as the two below)
+//   each_miller_kernel    ML(A, B) ML(X, -gamma) ML(C, -delta) of each listed proof: one squaring per bit for the three pairs
+//   final_exp_kernel      the final exponentiation of n Fq12 values, and (for the per-proof pass) the comparison with e(alpha, beta)
 //
 // Registers: a Miller lane's state is f (12 Fq = 168 dwords), T (84), Q and P (84) and the operation at hand; every Fq product is a
 // call (ffu.cuh: fqu_mul_call), so what is live across it sits in the callee-saved registers or in scratch: 4,272 B of scratch
@@ -13,9 +16,12 @@
 // LDS / inlined placement would change, and why the spill was left in.
 #include "verify_batch.hpp"
 
+#include <string.h>
+
 #include "common.hpp"
 #include "decompress_dev.cuh"
 #include "pairing_dev.cuh"
+#include "pairing_each_dev.cuh"
 
 namespace zk {
 namespace {
@@ -100,9 +106,112 @@ __global__ __launch_bounds__(64) void decompress_kernel(int group, const uint8_t
     status[i * status_stride] = (uint8_t)st;
 }
 
+// ---- each proof's own verdict: three kernels (DESIGN 2.7.3 has the resource figures the split was decided from)
+const size_t EACH_AB_WORDS = 144, EACH_ELL_WORDS = 84, EACH_COEFF_WORDS = 2 * 68 * EACH_ELL_WORDS, EACH_POINT_WORDS = 28;
+static_assert(sizeof(pd::Ell) == EACH_ELL_WORDS * 4 && sizeof(Affine<FqU>) == EACH_POINT_WORDS * 4, "the key block's layout");
+
+ZK_HD pd::Frob frob_u(const VbFrob &fr) {
+    pd::Frob r;
+#pragma unroll
+    for (int i = 0; i < 5; i++) r.g[i] = fq2u_from_sat(fr.g[i]);
+    return r;
+}
+
+// X of the proof at list position j: xk[2j], xk[2j + 1] affine in the U-form, have[j] = 0 for the point at infinity
+__global__ __launch_bounds__(64) void each_x_kernel(const Affine<FqU> *gamma_abc, size_t num_instance, const uint64_t *z, size_t n, FqU *xk, uint8_t *have) {
+    const size_t j = (size_t)blockIdx.x * 64 + threadIdx.x;
+    if (j >= n) return;
+    FqU x = FqU::zero(), y = FqU::zero();
+    const bool h = pd::prepared_input(gamma_abc, num_instance, z + 4 * (num_instance - 1) * j, x, y);
+    xk[2 * j] = x;
+    xk[2 * j + 1] = y;
+    have[j] = h ? 1 : 0;
+}
+
+// out[j] (72 u64) = ML(A, B) ML(X, -gamma) ML(C, -delta) of proof idx[j] (idx null: proof j)
+__global__ __launch_bounds__(64) void each_miller_kernel(const uint32_t *idx, size_t n, const uint64_t *proofs, const uint8_t *inf, const FqU *xk, const uint8_t *have,
+                                                         const pd::Ell *gamma_neg, const pd::Ell *delta_neg, uint64_t *out) {
+    const size_t j = (size_t)blockIdx.x * 64 + threadIdx.x;
+    if (j >= n) return;
+    const size_t i = idx ? idx[j] : j;
+    const pd::EachKey key{gamma_neg, delta_neg, nullptr};
+    const pd::F12 f = pd::miller_one(proofs + 48 * i, inf + 3 * i, have[j] != 0, xk[2 * j], xk[2 * j + 1], key);
+    Fq2 s[6];
+    pd::f12_to_sat(f, s);
+    Fq2 *o = reinterpret_cast<Fq2 *>(out + 72 * j);
+#pragma unroll
+    for (int t = 0; t < 6; t++) o[t] = s[t];
+}
+
+// the final exponentiation of f[j]; out (nullable): the value, 72 u64; verdict (nullable): verdict[j] = the value == want (72 u64)
+__global__ __launch_bounds__(64) void final_exp_kernel(const uint64_t *f, size_t n, VbFrob fr, uint64_t *out, const uint64_t *want, uint8_t *verdict) {
+    const size_t j = (size_t)blockIdx.x * 64 + threadIdx.x;
+    if (j >= n) return;
+    const pd::F12 r = pd::final_exp(pd::f12_from_sat(reinterpret_cast<const Fq2 *>(f + 72 * j)), frob_u(fr));
+    Fq2 s[6];
+    pd::f12_to_sat(r, s);
+    if (out) {
+        Fq2 *o = reinterpret_cast<Fq2 *>(out + 72 * j);
+#pragma unroll
+        for (int t = 0; t < 6; t++) o[t] = s[t];
+    }
+    if (verdict) {
+        const uint32_t *w = reinterpret_cast<const uint32_t *>(want), *v = reinterpret_cast<const uint32_t *>(s);
+        uint32_t diff = 0;
+        for (int t = 0; t < 144; t++) diff |= w[t] ^ v[t];
+        verdict[j] = diff == 0 ? 1 : 0;
+    }
+}
+
 unsigned blocks_of(size_t n) { return (unsigned)((n + 63) / 64); }
 
 }  // namespace
+
+void vb_final_exp_launch(hipStream_t st, const uint64_t *f, size_t n, uint64_t *out) {
+    if (!n) return;
+    hipLaunchKernelGGL(final_exp_kernel, dim3(blocks_of(n)), dim3(64), 0, st, f, n, vb_frob(), out, (const uint64_t *)nullptr, (uint8_t *)nullptr);
+    ZK_HIP(hipGetLastError());
+}
+
+size_t vb_each_key_count(size_t num_instance) { return EACH_AB_WORDS + EACH_COEFF_WORDS + EACH_POINT_WORDS * num_instance; }
+
+void vb_each_key_words(const VbKey &key, uint32_t *out) {
+    memcpy(out, key.alpha_beta, EACH_AB_WORDS * 4);
+    pd::Ell *ell = reinterpret_cast<pd::Ell *>(out + EACH_AB_WORDS);
+    for (int which = 0; which < 2; which++) {
+        const uint64_t *src = which ? key.delta_neg_coeffs : key.gamma_neg_coeffs;
+        for (size_t i = 0; i < 68; i++) {
+            Fq2 c[3];
+            memcpy(c, src + 36 * i, sizeof c);
+            ell[68 * which + i] = pd::Ell{fq2u_from_sat(c[0]), fq2u_from_sat(c[1]), fq2u_from_sat(c[2])};
+        }
+    }
+    Affine<FqU> *pts = reinterpret_cast<Affine<FqU> *>(out + EACH_AB_WORDS + EACH_COEFF_WORDS);
+    for (size_t i = 0; i < key.num_instance; i++) {
+        G1Affine p;
+        memcpy(&p, key.gamma_abc_g1 + 12 * i, sizeof p);
+        pts[i] = Affine<FqU>{fqu_from_sat(p.x), fqu_from_sat(p.y)};      // exact zeros stay exact: the point at infinity
+    }
+}
+
+size_t vb_each_scratch_bytes(size_t n) { return n * (576 + 2 * sizeof(FqU) + 1); }
+
+void vb_each_launch(hipStream_t st, const uint32_t *key_words, size_t num_instance, const uint32_t *idx, size_t n, const uint64_t *proofs, const uint8_t *inf,
+                    const uint64_t *z, void *scratch, uint8_t *verdict) {
+    if (!n) return;
+    uint64_t *f = static_cast<uint64_t *>(scratch);
+    FqU *xk = reinterpret_cast<FqU *>(f + 72 * n);
+    uint8_t *have = reinterpret_cast<uint8_t *>(xk + 2 * n);
+    const pd::Ell *ell = reinterpret_cast<const pd::Ell *>(key_words + EACH_AB_WORDS);
+    const Affine<FqU> *gamma_abc = reinterpret_cast<const Affine<FqU> *>(key_words + EACH_AB_WORDS + EACH_COEFF_WORDS);
+    hipLaunchKernelGGL(each_x_kernel, dim3(blocks_of(n)), dim3(64), 0, st, gamma_abc, num_instance, z, n, xk, have);
+    ZK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(each_miller_kernel, dim3(blocks_of(n)), dim3(64), 0, st, idx, n, proofs, inf, (const FqU *)xk, (const uint8_t *)have, ell, ell + 68, f);
+    ZK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(final_exp_kernel, dim3(blocks_of(n)), dim3(64), 0, st, (const uint64_t *)f, n, vb_frob(), (uint64_t *)nullptr,
+                       reinterpret_cast<const uint64_t *>(key_words), verdict);
+    ZK_HIP(hipGetLastError());
+}
 
 void vb_membership_launch(hipStream_t st, int group, const uint64_t *pts, size_t stride, const uint8_t *inf, size_t inf_stride, size_t n, const VbEndo &en,
                           uint8_t *ok, size_t ok_stride) {

@@ -42,8 +42,17 @@ int vb_check_args(const VbKey &key, const VbBatch &b, const int *ok);
 // when prod is null or when the batch equation fails and ok_each wants the culprits (the device form downloads them then).
 // *ok = 1 iff every proof holds; ok_each (nullable): each proof's own verdict, found by bisecting over index ranges.
 // ms (nullable): ms[0] += coefficients + the batch equation, ms[1] += bisecting (the fetch included).
+// each (nullable): where bisecting stops paying.  find_bad counts its range tests; when `after` of them have been made and bad
+// proofs are still not all named, every proof of a range that is still open goes to decide() in ONE call — verdict[j] != 0 iff
+// proof idx[j] holds by itself (what zkg16_verify_prepared says of it) — and no further range test is made.  decide empty: bisect
+// to the end, as the host form does.  range_tests: how many find_bad made (out).
+struct VbEach {
+    std::function<void(const uint32_t *idx, size_t n, uint8_t *verdict)> decide;
+    size_t after = 0;
+    size_t range_tests = 0;
+};
 void vb_decide(const VbKey &key, const VbBatch &b, const uint8_t *member, const std::function<const uint64_t *()> &fetch_miller, const uint64_t *prod,
-               const uint64_t *sum_c, const uint8_t *sum_c_inf, int threads, int *ok, uint8_t *ok_each, float ms[2]);
+               const uint64_t *sum_c, const uint8_t *sum_c_inf, int threads, int *ok, uint8_t *ok_each, float ms[2], VbEach *each = nullptr);
 // everything on host threads (zkg16_verify_batch_host).  dead (nullable, k bytes): proofs counted as failing membership whatever
 // their limbs say (zkg16_verify_batch_wire: a proof with a point that did not decode; its zero limbs would read as infinity)
 void vb_host(const VbKey &key, const VbBatch &b, int threads, int *ok, uint8_t *ok_each, const uint8_t *dead = nullptr);
@@ -57,6 +66,13 @@ struct VbEndo {
     int fast_g1, fast_g2;
 };
 VbEndo vb_endo();
+// the Frobenius constants gamma_i = xi^(i (q-1)/6), i = 1..5, of the final exponentiation (pf::frob_coeffs), saturated limbs
+struct VbFrob {
+    Fq2 g[5];
+};
+VbFrob vb_frob();
+// public inputs as the per-proof kernels read them: n Montgomery Fr (4 u64 each) -> canonical limbs
+void vb_scalars_canonical(const uint64_t *mont, size_t n, uint64_t *out);
 
 // ---- verify_batch.hip: launches on `st` (a stream of the calling lane); nothing synchronises
 // n points at pts + i * stride (u64 units; 12 / 24 u64 each), flag bytes at inf + i * inf_stride (null: none at infinity):
@@ -75,5 +91,22 @@ void vb_decompress_launch(hipStream_t st, int group, const uint8_t *bytes, size_
 // the product of f[0 .. n) by a tree (log2 n rounds); f is only read, and f[k] counts as one where live[k] == 0 (live nullable).
 // tmp: room for 2 * ((n + 1) / 2) * 72 u64.  Returns where the product (72 u64) will lie, inside tmp
 const uint64_t *vb_product_launch(hipStream_t st, const uint64_t *f, const uint8_t *live, size_t n, uint64_t *tmp);
+
+// ---- each proof's own verdict (pairing_each_dev.cuh)
+// out[i] (72 u64) = the verifier's final exponentiation of f[i], bit-equal to zkg16_final_exp; out may be f
+void vb_final_exp_launch(hipStream_t st, const uint64_t *f, size_t n, uint64_t *out);
+// A prepared key as the per-proof kernels read it, one block of u32 words made on the host once per call (vb_each_key_words) and
+// uploaded: e(alpha, beta) as it came (144 words), the 2 x 68 line triples of -gamma and -delta in the U-form (2 x 68 x 84) and
+// gamma_abc as affine U-form points (num_instance x 28)
+size_t vb_each_key_count(size_t num_instance);
+void vb_each_key_words(const VbKey &key, uint32_t *out);
+// room for one launch of n proofs: X_k (affine, U-form) with its flag and the Miller values
+size_t vb_each_scratch_bytes(size_t n);
+// verdict[j] = what zkg16_verify_prepared says of proof idx[j] (idx null: proof j), j < n, for proofs that passed membership:
+// FE( ML(A, B) ML(X, -gamma) ML(C, -delta) ) == e(alpha, beta), a pair with a point at infinity counting as one.  proofs
+// (k x 48 limbs) and inf (k x 3 flags) are indexed by proof; z (n x (num_instance - 1) x 4 canonical limbs) by position j.
+// Three kernels: X_k, the three-pair Miller loop (one squaring per bit), the final exponentiation with the comparison
+void vb_each_launch(hipStream_t st, const uint32_t *key_words, size_t num_instance, const uint32_t *idx, size_t n, const uint64_t *proofs, const uint8_t *inf,
+                    const uint64_t *z, void *scratch, uint8_t *verdict);
 
 }  // namespace zk

@@ -258,6 +258,22 @@ class Device:
         out = (bool(ok.value),) + ((ok_each.astype(bool),) if each else ()) + ((st,) if status else ())
         return out if len(out) > 1 else out[0]
 
+    def verify_each(self, pvk, public_inputs, proofs, infs):
+        """What verify_prepared says of each of K proofs under one prepared key, in one device pass (zkg16_verify_each; arguments as
+        verify_batch, no multipliers) -> bool array [k].  The cost does not depend on how many of the proofs are bad."""
+        args, k = _verify_batch_args(pvk, public_inputs, proofs, infs, np.ones((_u64(proofs).reshape(-1, 48).shape[0], 2), dtype=np.uint64))
+        ok_each = np.zeros(k, dtype=np.uint8)
+        self._check(self.lib.zkg16_verify_each(self.ctx, *args[:9], k, _ptr(ok_each)))
+        return ok_each.astype(bool)
+
+    def final_exp_batch(self, f):
+        """The verifier's final exponentiation of n Fq12 values on the device (zkg16_final_exp_batch): [n, 72] -> [n, 72], each row
+        bit-equal to final_exp() of that row."""
+        f = _u64(f).reshape(-1, 72)
+        out = np.zeros_like(f)
+        self._check(self.lib.zkg16_final_exp_batch(self.ctx, _ptr(f) if f.shape[0] else None, f.shape[0], _ptr(out) if f.shape[0] else None))
+        return out
+
     def decompress_batch(self, group, data, validate=True):
         """n compressed points of one group back to back, decoded on the device (zkg16_points_decompress_batch) ->
         (limbs [n, 12 | 24], infinity flags [n], statuses [n]).  Nothing raises for a point that does not decode: its status says why
@@ -279,10 +295,11 @@ class Device:
 
     def verify_batch_timings(self):
         """ms of the last verify_batch / verify_batch_wire: membership, scaling + Miller, product tree, MSM, host equation, bisecting,
-        total wall, whether the host form answered, and the decode kernels (verify_batch_wire only)."""
-        ms = (C.c_float * 9)()
-        n = self.lib.zkg16_verify_batch_timings(self.ctx, ms, 9)
-        names = ("membership_ms", "miller_ms", "product_ms", "msm_ms", "host_ms", "bisect_ms", "total_ms", "host_form", "decode_ms")
+        total wall, whether the host form answered, the decode kernels (verify_batch_wire only), the per-proof pass that took over
+        from bisecting (0 when it did not run) and the number of range tests bisecting made."""
+        ms = (C.c_float * 11)()
+        n = self.lib.zkg16_verify_batch_timings(self.ctx, ms, 11)
+        names = ("membership_ms", "miller_ms", "product_ms", "msm_ms", "host_ms", "bisect_ms", "total_ms", "host_form", "decode_ms", "each_ms", "range_tests")
         return {names[i]: float(ms[i]) for i in range(n)}
 
     def miller_loop_batch(self, g1, g2, g1_inf=None, g2_inf=None):
