@@ -405,6 +405,34 @@ ZKG16_API int zkg16_prove_matrix(zkg16_ctx *ctx, uint64_t pk_handle, uint64_t r1
 /* Its host-only half (no ctx, no GPU): states (nullable) = 3 hashes x ceil(n^2/2) permutations x 3 Fr, the sponge state in
  * front of each permutation (after its two elements were absorbed); hashes = hash_a | hash_b | hash_c. */
 ZKG16_API int zkg16_matrix_sponge_states(size_t n, const uint64_t *a, const uint64_t *b, uint64_t *states, uint64_t hashes[12]);
+/* The same for k requests of one size on a pool of host threads (no ctx, no GPU).  a, b: k x n^2, request-major.  threads: 0 = 8; the
+ * value is capped at 16 and at 3k (the 3k chains are the tasks: a chain is sequential, the c chains are handed out first).  Request
+ * i's states (nullable: k x 3 x ceil(n^2/2) x 12) and hashes (k x 12) are byte for byte those of zkg16_matrix_sponge_states(n, a_i,
+ * b_i).  n outside 2..1024, k == 0, threads < 0 or a null a / b / hashes: ZKG16_ERR_BAD_ARG, nothing written. */
+ZKG16_API int zkg16_matrix_sponge_states_batch(size_t n, const uint64_t *a, const uint64_t *b, size_t k, int threads, uint64_t *states,
+                                               uint64_t *hashes);
+/* zkg16_witness_matrix for k requests of one size in ONE upload, two launches and one synchronisation: the chains of all requests run
+ * first, before the ctx is locked, on option "matrix_batch_threads" host threads; the device then reads one array of all a | b, one
+ * of all entering states and the k instance triples out of pinned staging the ctx keeps, and writes the k assignments — which share
+ * one allocation, returned when the last of the k handles is freed — through a table of their addresses.  witness_handles[i]: the
+ * bytes of zkg16_witness_matrix(n, a_i, b_i), usable wherever a witness handle is.  public_inputs (nullable): k x 12.  timings_ms
+ * (nullable, 3): host chains (wall), device (uploads + kernels), whole call.  Arguments as zkg16_witness_matrix, and k == 0 or k
+ * assignments beyond a size_t: ZKG16_ERR_BAD_ARG, before any work.  All or nothing: on any error no handle is registered and neither
+ * witness_handles nor public_inputs is written. */
+ZKG16_API int zkg16_witness_matrix_batch(zkg16_ctx *ctx, size_t n, const uint64_t *a, const uint64_t *b, size_t k, uint64_t *witness_handles,
+                                         uint64_t *public_inputs, float *timings_ms);
+/* k requests of the matrix handler on one resident key: a, b (k x n^2) in, k proofs and their public inputs out.  Proof i is byte for
+ * byte zkg16_prove_resident's on zkg16_witness_matrix(n, a_i, b_i) with (r + 4i, s + 4i).  One lane.  The work goes in sub-batches sized
+ * as zkg16_prove_batch's with the assignment itself (32 B per variable) added per proof, capped by option "batch_max"; per sub-batch the
+ * host chains, the batched witness pass, then the batched proof, after which its assignments are released — no witness handle ever
+ * exists.  pk_handle / r1cs_handle must be a whole key and the MatrixCircuit of size n (ZKG16_ERR_BAD_HANDLE, ZKG16_ERR_UNSUPPORTED
+ * for a shard, else ZKG16_ERR_BAD_ARG, as k == 0 and null pointers): all checked before any work.  On any error nothing is written
+ * (proofs and public inputs are staged until every sub-batch has succeeded).  public_inputs (nullable): k x 12.  timings_ms (nullable,
+ * 4): host chains (summed wall), witness passes (device), proving (zkg16_last_timings[9] summed), whole call.  zkg16_last_timings /
+ * zkg16_last_term_counts describe the batch as after zkg16_prove_batch. */
+ZKG16_API int zkg16_prove_matrix_batch(zkg16_ctx *ctx, uint64_t pk_handle, uint64_t r1cs_handle, size_t n, const uint64_t *a,
+                                       const uint64_t *b, size_t k, const uint64_t *r, const uint64_t *s, uint64_t *proofs_out /* k x 48 */,
+                                       uint8_t *inf_out /* k x 3 */, uint64_t *public_inputs, float *timings_ms);
 /* ---- the MatrixCircuit's R1CS of size n WITHOUT synthesising it constraint by constraint (csrc/matrix_plan.hpp): the sponge rows are
  * copies of one template per permutation class with renamed variables, matrix_mul's rows have a closed form.  _dims / _host: host
  * loops (the reference the device kernel is tested against; same arrays as zkg16_circuit_matrix + zkg16_circuit_export);
@@ -508,7 +536,9 @@ ZKG16_API void zkg16_kernel_stats_reset(zkg16_ctx *ctx);
  *   "g1_inline"      G1 accumulation (plain loop): 0 / 1 (default) every field product inlined, no call; 2 = products as device-function calls
  *   "lanes"          proofs this ctx runs at a time (1..8, default 2): see the note on re-entrancy at the top
  *   "matrix_parts"   zkg16_prove_matrix: slices of the host sponges the proof is fed in (0 = five growing slices, k = k equal ones; 1 = assignment first, then the proof)
- *   "batch_max"      zkg16_prove_batch: proofs per device pass (0 = as many as fit, else 1..65535)
+ *   "batch_max"      zkg16_prove_batch / zkg16_prove_matrix_batch: proofs per device pass (0 = as many as fit, else 1..65535)
+ *   "matrix_batch_threads" zkg16_witness_matrix_batch / zkg16_prove_matrix_batch: host threads of the sponge chains (0 = 8, else 1..16)
+ *   "matrix_batch_grid" cap on either grid dimension of the batched witness kernels (0 = 65535, else 1..65535): beyond it they loop
  * Unknown names return ZKG16_ERR_UNSUPPORTED. */
 ZKG16_API int zkg16_set_option(zkg16_ctx *ctx, const char *name, int64_t value);
 

@@ -111,6 +111,9 @@ SIGNATURES = {
     "zkg16_r1cs_prime": (C.c_int, [ctxp, C.c_uint64, C.c_uint64, C.POINTER(H)]),
     "zkg16_witness_prime": (C.c_int, [ctxp, C.c_uint64, C.c_uint64, C.POINTER(H)]),
     "zkg16_matrix_sponge_states": (C.c_int, [sz, u64p, u64p, vp, u64p]),
+    "zkg16_matrix_sponge_states_batch": (C.c_int, [sz, vp, vp, sz, C.c_int, vp, vp]),
+    "zkg16_witness_matrix_batch": (C.c_int, [ctxp, sz, vp, vp, sz, vp, vp, vp]),
+    "zkg16_prove_matrix_batch": (C.c_int, [ctxp, H, H, sz, vp, vp, sz, vp, vp, vp, vp, vp, vp]),
     "zkg16_ntt": (C.c_int, [ctxp, u64p, sz, C.c_int, C.c_int]),
     "zkg16_msm_g1": (C.c_int, [ctxp, vp, vp, vp, sz, u64p, u8p]),
     "zkg16_msm_g2": (C.c_int, [ctxp, vp, vp, vp, sz, u64p, u8p]),

@@ -173,6 +173,24 @@ def matrix_sponge_states(a, b):
     return states, hashes
 
 
+def matrix_sponge_states_batch(a, b, threads=0, want_states=True):
+    """matrix_sponge_states for k requests of one size on a pool of host threads (zkg16_matrix_sponge_states_batch; no GPU):
+    a, b [k, n, n] -> (states [k, 3, ceil(n^2/2), 3, 4] or None, hashes [k, 3, 4]); threads: 0 = 8."""
+    a = np.ascontiguousarray(a, dtype=np.uint64)
+    b = np.ascontiguousarray(b, dtype=np.uint64)
+    if a.ndim != 3 or a.shape[1] != a.shape[2] or b.shape != a.shape:
+        raise ValueError("matrix_sponge_states_batch: a and b must be k x n x n")
+    k, n = a.shape[0], a.shape[1]
+    perms = (n * n + 1) // 2
+    states = np.zeros((k, 3, perms, 3, 4), dtype=np.uint64) if want_states else None
+    hashes = np.zeros((k, 3, 4), dtype=np.uint64)
+    rc = _lib.load().zkg16_matrix_sponge_states_batch(n, a.ctypes.data, b.ctypes.data, k, threads,
+                                                      states.ctypes.data if want_states else None, hashes.ctypes.data)
+    if rc:
+        raise Zkg16Error(rc, "zkg16_matrix_sponge_states_batch")
+    return states, hashes
+
+
 def matrix_r1cs_from_plan(n):
     """The MatrixCircuit's R1CS of size n from its plan (zkg16_matrix_r1cs_dims / _host: templates + closed forms, host loops) ->
     (r1cs dict as SynthesizedCircuit.r1cs, num_witness).  What the device kernel of zkg16_r1cs_matrix is tested against."""

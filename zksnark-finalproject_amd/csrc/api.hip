@@ -85,7 +85,7 @@ void copy_options(zkg16_ctx *dst, const zkg16_ctx *src) {
     dst->opt_ntt_radix = src->opt_ntt_radix; dst->opt_ntt_xcd = src->opt_ntt_xcd; dst->opt_acc_debug = src->opt_acc_debug;
     dst->opt_sort_mode = src->opt_sort_mode; dst->opt_acc_pipeline = src->opt_acc_pipeline; dst->opt_fuse_pointwise = src->opt_fuse_pointwise;
     dst->opt_matrix_parts = src->opt_matrix_parts; dst->opt_g2_lazy = src->opt_g2_lazy; dst->opt_g1_inline = src->opt_g1_inline; dst->opt_fixed_base_bits = src->opt_fixed_base_bits;
-    dst->opt_collect_threads = src->opt_collect_threads; dst->opt_batch_max = src->opt_batch_max; dst->opt_verify_batch_min = src->opt_verify_batch_min; dst->opt_verify_wire_min = src->opt_verify_wire_min; dst->opt_verify_each_after = src->opt_verify_each_after; dst->opt_wm_transforms = src->opt_wm_transforms;
+    dst->opt_collect_threads = src->opt_collect_threads; dst->opt_batch_max = src->opt_batch_max; dst->opt_matrix_batch_threads = src->opt_matrix_batch_threads; dst->opt_matrix_batch_grid = src->opt_matrix_batch_grid; dst->opt_verify_batch_min = src->opt_verify_batch_min; dst->opt_verify_wire_min = src->opt_verify_wire_min; dst->opt_verify_each_after = src->opt_verify_each_after; dst->opt_wm_transforms = src->opt_wm_transforms;
     dst->kernel_timing = src->kernel_timing; dst->kernel_timing_accumulate_only = src->kernel_timing_accumulate_only;
 }
 void create_streams(zkg16_ctx *ctx) {
@@ -107,6 +107,10 @@ void teardown(zkg16_ctx *ctx) {
     if (ctx->batch_host) (void)hipHostFree(ctx->batch_host);
     ctx->batch_host = nullptr;
     ctx->batch_host_bytes = 0;
+    if (ctx->mbatch_host) (void)hipHostFree(ctx->mbatch_host);
+    ctx->mbatch_host = nullptr;
+    ctx->mbatch_host_bytes = 0;
+    ctx->mbatch_dev.release();
     if (ctx->circuit_stage) (void)hipHostFree(ctx->circuit_stage);
     ctx->circuit_stage = nullptr;
     ctx->circuit_stage_bytes = 0;
@@ -842,6 +846,45 @@ void prove_batch_device(zkg16_ctx *ctx, PkDev &pk, R1csDev &rc, WitnessDev *cons
     drain.ok = true;
 }
 
+// Proofs per device pass of a batch on (pk, rc): terms per proof of the z and h lists (every list stays under 2^31 terms), and what
+// grows with K on the device — both lists' entries, codes and scatter intermediates (20 B a term; the B list may be a second z list),
+// the witness map's four vectors, and the bucket arrays of the five MSMs with their reduction buffers (taken as 2x the G1 / G2
+// buckets), plus `extra_per_proof` bytes the caller keeps per proof — within 60 % of the free HBM.  Option batch_max caps it.
+size_t batch_sub_size(zkg16_ctx *ctx, const PkDev *pk, const R1csDev *rc, size_t extra_per_proof) {
+    const size_t N = (size_t)1 << rc->log_n;
+    const size_t m = rc->num_variables;
+    const size_t dz = msm_plan_digits(ctx, m + 3, pk->tab_c_z, pk->tab_c_z != 0), dh = msm_plan_digits(ctx, N - 1, pk->tab_c_h ? pk->tab_c_h : ctx->opt_window_bits_h, pk->tab_c_h != 0);
+    const size_t tz = (m + 3) * dz, th = (N - 1) * dh;
+    const size_t term_cap = ((size_t)1 << 31) - 1;
+    size_t kb = term_cap / (tz > th ? tz : th);
+    {
+        const size_t cz = pk->tab_c_z ? (size_t)pk->tab_c_z : msm_plan_bits(ctx, m + 3, 0, false);
+        const size_t ch = pk->tab_c_h ? (size_t)pk->tab_c_h : msm_plan_bits(ctx, N - 1, ctx->opt_window_bits_h, false);
+        const size_t bz = ((size_t)1 << (cz - 1)) * (pk->tab_c_z ? 1 : dz), bh = ((size_t)1 << (ch - 1)) * (pk->tab_c_h ? 1 : dh);
+        const size_t per_proof = (2 * tz + th) * 20 + 4 * N * sizeof(Fr) + 2 * (bz * (3 * sizeof(G1XYZZ) + sizeof(G2XYZZ)) + bh * sizeof(G1XYZZ)) + extra_per_proof;
+        size_t free_b = 0, total_b = 0;
+        ZK_HIP(hipMemGetInfo(&free_b, &total_b));
+        const size_t kmem = (size_t)(0.6 * (double)free_b) / per_proof;
+        if (kmem < kb) kb = kmem;
+    }
+    if (ctx->opt_batch_max > 0 && (size_t)ctx->opt_batch_max < kb) kb = (size_t)ctx->opt_batch_max;
+    if (kb > 65535) kb = 65535;
+    if (kb < 1) kb = 1;
+    return kb;
+}
+// after a pass of prove_batch_device: its timings into acc and, for a batch of several passes, its lists' lengths into terms
+void batch_pass_account(zkg16_ctx *ctx, float acc[22], uint64_t terms[3], bool one_pass) {
+    for (int i = 0; i < 22; i++) acc[i] += ctx->timings[i];
+    if (one_pass) return;                 // zkg16_last_term_counts reads its lists as after a single proof
+    MsmWorkspace *w[3] = {&ctx->ws_z, &ctx->ws_zb, &ctx->ws_h};
+    for (int i = 0; i < 3; i++) {
+        uint32_t v = 0;
+        if (w[i]->last_tb && w[i]->offsets.p)
+            ZK_HIP(hipMemcpy(&v, w[i]->offsets.as<uint32_t>() + w[i]->last_tb, sizeof v, hipMemcpyDeviceToHost));
+        terms[i] += v;
+    }
+}
+
 Fr fr_from_abi(const uint64_t *l) {
     Fr v;
     memcpy(&v, l, sizeof v);
@@ -1163,9 +1206,19 @@ int set_option_one(zkg16_ctx *ctx, const char *name, int64_t value) {
         ctx->opt_matrix_parts = (int)value;
         return ZKG16_OK;
     }
-    if (!strcmp(name, "batch_max")) {          // zkg16_prove_batch: proofs per device pass, 0 = as many as fit (free HBM, 2^31 terms per list)
+    if (!strcmp(name, "batch_max")) {          // zkg16_prove_batch / zkg16_prove_matrix_batch: proofs per device pass, 0 = as many as fit (free HBM, 2^31 terms per list)
         if (value < 0 || value > 65535) return ZKG16_ERR_BAD_ARG;
         ctx->opt_batch_max = (int)value;
+        return ZKG16_OK;
+    }
+    if (!strcmp(name, "matrix_batch_threads")) {      // zkg16_witness_matrix_batch / zkg16_prove_matrix_batch: host threads of the sponge chains, 0 = 8
+        if (value < 0 || value > 16) return ZKG16_ERR_BAD_ARG;
+        ctx->opt_matrix_batch_threads = (int)value;
+        return ZKG16_OK;
+    }
+    if (!strcmp(name, "matrix_batch_grid")) {  // the batched witness kernels: cap on either grid dimension, 0 = 65535 (tests set 1..3 to run the loops at small K)
+        if (value < 0 || value > 65535) return ZKG16_ERR_BAD_ARG;
+        ctx->opt_matrix_batch_grid = (int)value;
         return ZKG16_OK;
     }
     if (!strcmp(name, "verify_batch_min")) {   // zkg16_verify_batch: batches shorter than this go to the host form (0 restores the default; 1 = always the device)
@@ -1767,27 +1820,7 @@ int zkg16_prove_batch(zkg16_ctx *ctx, uint64_t pk_handle, uint64_t r1cs_handle, 
         rr[i] = fr_from_abi(r + 4 * i);
         ss[i] = fr_from_abi(s + 4 * i);
     }
-    // sub-batch size: terms per proof of the z and h lists, and what grows with K on the device — both lists' entries, codes and
-    // scatter intermediates (20 B a term; the B list may be a second z list), the witness map's four vectors, and the bucket arrays
-    // of the five MSMs with their reduction buffers (taken as 2x the G1 / G2 buckets)
-    const size_t m = rc->num_variables;
-    const size_t dz = msm_plan_digits(ctx, m + 3, pk->tab_c_z, pk->tab_c_z != 0), dh = msm_plan_digits(ctx, N - 1, pk->tab_c_h ? pk->tab_c_h : ctx->opt_window_bits_h, pk->tab_c_h != 0);
-    const size_t tz = (m + 3) * dz, th = (N - 1) * dh;
-    const size_t term_cap = ((size_t)1 << 31) - 1;
-    size_t kb = term_cap / (tz > th ? tz : th);
-    {
-        const size_t cz = pk->tab_c_z ? (size_t)pk->tab_c_z : msm_plan_bits(ctx, m + 3, 0, false);
-        const size_t ch = pk->tab_c_h ? (size_t)pk->tab_c_h : msm_plan_bits(ctx, N - 1, ctx->opt_window_bits_h, false);
-        const size_t bz = ((size_t)1 << (cz - 1)) * (pk->tab_c_z ? 1 : dz), bh = ((size_t)1 << (ch - 1)) * (pk->tab_c_h ? 1 : dh);
-        const size_t per_proof = (2 * tz + th) * 20 + 4 * N * sizeof(Fr) + 2 * (bz * (3 * sizeof(G1XYZZ) + sizeof(G2XYZZ)) + bh * sizeof(G1XYZZ));
-        size_t free_b = 0, total_b = 0;
-        ZK_HIP(hipMemGetInfo(&free_b, &total_b));
-        const size_t kmem = (size_t)(0.6 * (double)free_b) / per_proof;
-        if (kmem < kb) kb = kmem;
-    }
-    if (ctx->opt_batch_max > 0 && (size_t)ctx->opt_batch_max < kb) kb = (size_t)ctx->opt_batch_max;
-    if (kb > 65535) kb = 65535;
-    if (kb < 1) kb = 1;
+    const size_t kb = batch_sub_size(ctx, pk, rc, 0);
     std::vector<uint64_t> proofs(48 * k);
     std::vector<uint8_t> infs(3 * k);
     const double t0 = now_ms();
@@ -1796,15 +1829,7 @@ int zkg16_prove_batch(zkg16_ctx *ctx, uint64_t pk_handle, uint64_t r1cs_handle, 
     for (size_t off = 0; off < k; off += kb) {
         const size_t n = k - off < kb ? k - off : kb;
         prove_batch_device(ctx, *pk, *rc, wits.data() + off, n, rr.data() + off, ss.data() + off, proofs.data() + 48 * off, infs.data() + 3 * off);
-        for (int i = 0; i < 22; i++) acc[i] += ctx->timings[i];
-        if (kb >= k) break;               // one pass: zkg16_last_term_counts reads its lists as after a single proof
-        MsmWorkspace *w[3] = {&ctx->ws_z, &ctx->ws_zb, &ctx->ws_h};
-        for (int i = 0; i < 3; i++) {
-            uint32_t v = 0;
-            if (w[i]->last_tb && w[i]->offsets.p)
-                ZK_HIP(hipMemcpy(&v, w[i]->offsets.as<uint32_t>() + w[i]->last_tb, sizeof v, hipMemcpyDeviceToHost));
-            terms[i] += v;
-        }
+        batch_pass_account(ctx, acc, terms, kb >= k);
     }
     for (int i = 0; i < 22; i++) ctx->timings[i] = acc[i];
     ctx->timings[9] = (float)(now_ms() - t0);
@@ -1865,6 +1890,69 @@ int zkg16_prove_matrix(zkg16_ctx *ctx, uint64_t pk_handle, uint64_t r1cs_handle,
         timings_ms[0] = (float)matrix_stream_chain_ms(ms.get());
         timings_ms[1] = (float)zp.parts;
         timings_ms[2] = (float)(now_ms() - t_call);
+    }
+    ZK_LANE_END(ctx)
+}
+
+// K requests of the matrix handler on one resident key and the MatrixCircuit's resident matrices: per sub-batch (batch_sub_size with
+// the assignment itself added per proof) the host chains, the batched witness pass (witness.hip: matrix_batch_assign) and
+// prove_batch_device, after which the sub-batch's assignments go back.  No witness handle exists at any time; proofs and public inputs
+// are staged and written only when every sub-batch has succeeded.  The chains of sub-batch j + 1 do not run beside the proving of
+// sub-batch j: timings_ms (chains, witness passes, proving, whole call) is there to tell whether that would pay.
+int zkg16_prove_matrix_batch(zkg16_ctx *ctx, uint64_t pk_handle, uint64_t r1cs_handle, size_t n, const uint64_t *a, const uint64_t *b, size_t k,
+                             const uint64_t *r, const uint64_t *s, uint64_t *proofs_out, uint8_t *inf_out, uint64_t *public_inputs,
+                             float *timings_ms) {
+    if (!a || !b || !r || !s || !proofs_out || !inf_out || k == 0 || n < 2 || n > 1024) return ZKG16_ERR_BAD_ARG;
+    const double t_call = now_ms();
+    ZK_LANE_BEGIN(ctx)
+    auto pk_ref = root->pks.get(pk_handle); PkDev *pk = pk_ref.get();
+    auto rc_ref = root->r1cs.get(r1cs_handle); R1csDev *rc = rc_ref.get();
+    if (!pk || !rc) return ZKG16_ERR_BAD_HANDLE;
+    if (!pk->full) return ZKG16_ERR_UNSUPPORTED;                        // shards: zkg16_prove_partial / _group
+    const size_t total = matrix_witness_total(n), nn = n * n;
+    if (total != rc->num_variables || pk->m_total != rc->num_variables || pk->num_instance != 4 || rc->num_instance != 4 ||
+        pk->n_h_total != ((size_t)1 << rc->log_n) - 1)
+        return ZKG16_ERR_BAD_ARG;                   // not the MatrixCircuit of this size
+    if (k > SIZE_MAX / (total * sizeof(Fr))) return ZKG16_ERR_BAD_ARG;
+    std::vector<Fr> rr(k), ss(k);
+    for (size_t i = 0; i < k; i++) {
+        rr[i] = fr_from_abi(r + 4 * i);
+        ss[i] = fr_from_abi(s + 4 * i);
+    }
+    const size_t kb = batch_sub_size(ctx, pk, rc, total * sizeof(Fr));
+    std::vector<uint64_t> proofs(48 * k), pubs(12 * k);
+    std::vector<uint8_t> infs(3 * k);
+    const double t0 = now_ms();
+    float acc[22] = {0};
+    uint64_t terms[3] = {0, 0, 0};
+    double chain_ms = 0, wit_ms = 0;
+    for (size_t off = 0; off < k; off += kb) {
+        const size_t nb = k - off < kb ? k - off : kb;
+        const uint64_t *ao = a + off * nn, *bo = b + off * nn;
+        MatrixBatchChains mc;
+        matrix_batch_chains(mc, n, ao, bo, nb, ctx->opt_matrix_batch_threads, pubs.data() + 12 * off);
+        chain_ms += mc.ms;
+        std::vector<std::shared_ptr<WitnessDev>> wit_refs;
+        float dev_ms = 0;
+        matrix_batch_assign(ctx, mc, ao, bo, wit_refs, &dev_ms);
+        wit_ms += dev_ms;
+        std::vector<WitnessDev *> wits(nb);
+        for (size_t i = 0; i < nb; i++) wits[i] = wit_refs[i].get();
+        prove_batch_device(ctx, *pk, *rc, wits.data(), nb, rr.data() + off, ss.data() + off, proofs.data() + 48 * off, infs.data() + 3 * off);
+        batch_pass_account(ctx, acc, terms, kb >= k);
+    }
+    for (int i = 0; i < 22; i++) ctx->timings[i] = acc[i];
+    ctx->timings[9] = (float)(now_ms() - t0);
+    for (int i = 0; i < 3; i++) ctx->batch_terms[i] = terms[i];
+    ctx->batch_terms_set = kb < k;
+    memcpy(proofs_out, proofs.data(), proofs.size() * sizeof(uint64_t));
+    memcpy(inf_out, infs.data(), infs.size());
+    if (public_inputs) memcpy(public_inputs, pubs.data(), pubs.size() * sizeof(uint64_t));
+    if (timings_ms) {
+        timings_ms[0] = (float)chain_ms;
+        timings_ms[1] = (float)wit_ms;
+        timings_ms[2] = acc[9];
+        timings_ms[3] = (float)(now_ms() - t_call);
     }
     ZK_LANE_END(ctx)
 }

@@ -165,7 +165,19 @@ struct R1csDev {
     std::vector<std::shared_ptr<RowShare>> row_shares;
 };
 
-struct WitnessDev { size_t n = 0; DevBuf z; };
+// backing: set when z is a view into an allocation several assignments share (zkg16_witness_matrix_batch: one per batch); the view is
+// detached, not released, and the allocation goes back when the last assignment holding it is gone.
+struct WitnessDev {
+    size_t n = 0;
+    DevBuf z;
+    std::shared_ptr<DevBuf> backing;
+    WitnessDev() = default;
+    WitnessDev(const WitnessDev &) = delete;
+    WitnessDev &operator=(const WitnessDev &) = delete;
+    ~WitnessDev() {
+        if (backing) { z.p = nullptr; z.bytes = 0; }
+    }
+};
 struct PrimeDev;            // prime_device.hip: the recorded PrimeCircuit resident on a ctx
 
 // handle -> resident object.  Objects are shared_ptr: a proof in flight on one lane keeps its key / matrices / assignment alive
@@ -284,6 +296,10 @@ struct zkg16_ctx {
     size_t batch_host_bytes = 0;
     bool batch_terms_set = false;                     // the last proving call was a batch: its term counts (summed over sub-batches)
     uint64_t batch_terms[3] = {0, 0, 0};
+    // zkg16_witness_matrix_batch: pinned staging of a batch's a | b, entering states, instances and z pointers, and its device copy
+    void *mbatch_host = nullptr;
+    size_t mbatch_host_bytes = 0;
+    zk::DevBuf mbatch_dev;
     float timings[24] = {0};
     bool kernel_timing = false;
     bool kernel_timing_accumulate_only = false;       // zkg16_kernel_timing(ctx, 2): only the bucket-accumulation launches
@@ -315,7 +331,9 @@ struct zkg16_ctx {
     int opt_matrix_parts = 0;                         // zkg16_prove_matrix: gadget slices the assignment arrives in (0 = five growing slices, k = k equal ones, 1 = no overlap)
     int opt_fuse_pointwise = 1;                       // the point-wise product on the load of the last transform (0: its own pass)
     int opt_wm_transforms = 6;                        // witness map: 6 (default) = C only inverse-transformed, subtracted on the last store; 7 = arkworks' sequence
-    int opt_batch_max = 0;                            // zkg16_prove_batch: proofs per device pass (0 = as many as fit)
+    int opt_batch_max = 0;                            // zkg16_prove_batch / zkg16_prove_matrix_batch: proofs per device pass (0 = as many as fit)
+    int opt_matrix_batch_threads = 0;                 // zkg16_witness_matrix_batch / zkg16_prove_matrix_batch: host threads of the sponge chains (0 = 8)
+    int opt_matrix_batch_grid = 0;                    // cap on either grid dimension of the batched witness kernels (0 = 65535): beyond it they loop
     int opt_verify_batch_min = ZKG16_VERIFY_BATCH_MIN_DEFAULT;                   // zkg16_verify_batch: shorter batches are answered by the host form (the measured crossover)
     int opt_verify_wire_min = ZKG16_VERIFY_WIRE_MIN_DEFAULT;                     // zkg16_verify_batch_wire: shorter batches are decoded and answered on the host (the measured crossover)
     int opt_verify_each_after = ZKG16_VERIFY_EACH_AFTER_DEFAULT;                 // zkg16_verify_batch[_wire] with ok_each: range tests before the per-proof pass takes over
@@ -469,6 +487,21 @@ void matrix_stream_produce(MatrixWitnessStream *ms, zkg16_ctx *ctx, int k);  // 
 double matrix_stream_chain_ms(const MatrixWitnessStream *ms);
 void matrix_stream_hashes(const MatrixWitnessStream *ms, uint64_t out[12]);
 void matrix_stream_free(MatrixWitnessStream *ms);
+
+// K requests of one size in one pass (zkg16_witness_matrix_batch, zkg16_prove_matrix_batch).  matrix_batch_chains: the 3k host chains
+// on `threads` threads (0 = 8), no ctx; the 12 k hash limbs go to `hashes`, which must stay valid for matrix_batch_assign.  That
+// one queues the uploads and the two batched launches on ctx->stream (under ctx's mutex) and synchronises it: k assignments in one
+// shared allocation.  Throws HipError (the stream drained) / std::bad_alloc.
+struct MatrixBatchChains {
+    size_t n = 0, k = 0, perms = 0;
+    std::vector<uint64_t> states;           // k x 3 x perms x 12
+    const uint64_t *hashes = nullptr;       // k x 12
+    double ms = 0;                          // wall
+};
+size_t matrix_witness_total(size_t n);
+void matrix_batch_chains(MatrixBatchChains &c, size_t n, const uint64_t *a, const uint64_t *b, size_t k, int threads, uint64_t *hashes);
+void matrix_batch_assign(zkg16_ctx *ctx, const MatrixBatchChains &c, const uint64_t *a, const uint64_t *b,
+                         std::vector<std::shared_ptr<WitnessDev>> &out, float *dev_ms);
 
 // An assignment that becomes valid in parts while its proof is already running (prove_device): produce(k) blocks until part k
 // can be made, then queues on ctx->stream whatever writes it; part_of[i] = the part variable i (and the trailing r, s, -rs slots)

@@ -138,6 +138,44 @@ struct MatrixChains {
     }
 };
 
+// The chains of k requests on a pool of host threads (zkg16_matrix_sponge_states_batch).  A chain is sequential by construction, so
+// the unit of work is a whole chain: 3k independent tasks handed out by one shared counter, the c chains first — they multiply the
+// matrices before they hash, so they are the longest and must not be what the pool waits for at the end.  The caller is one of the
+// `threads` workers; a thread that cannot be started runs its worker on the caller (ThreadGroup), which then takes whatever tasks
+// are left.  states (nullable): k x 3 x perms x 3, request-major, then a, b, c; hashes: k x 3.  Throws std::bad_alloc.
+void matrix_chains_batch(size_t n, const uint64_t *a, const uint64_t *b, size_t k, int threads, Fr64 *states, Fr64 *hashes) {
+    const size_t nn = n * n, perms = (nn + POSEIDON_RATE - 1) / POSEIDON_RATE, tasks = 3 * k;
+    size_t nth = threads <= 0 ? 8 : threads > 16 ? 16 : (size_t)threads;
+    if (nth > tasks) nth = tasks;
+    (void)pparams();
+    std::atomic<size_t> next{0};
+    std::atomic<bool> oom{false};
+    auto worker = [&]() {
+        try {
+            std::vector<Fr64> elems(nn);
+            for (size_t t; (t = next.fetch_add(1)) < tasks;) {
+                const int h = t < k ? 2 : t < 2 * k ? 0 : 1;
+                const size_t i = t < k ? t : t < 2 * k ? t - k : t - 2 * k;
+                const uint64_t *ai = a + i * nn, *bi = b + i * nn;
+                if (h == 2) matmul_u64(n, ai, bi, elems.data());
+                else {
+                    const uint64_t *src = h == 0 ? ai : bi;
+                    for (size_t e = 0; e < nn; e++) elems[e] = fr64_from_u64(src[e]);
+                }
+                hashes[3 * i + h] = sponge_chain(elems.data(), nn, states ? states + (3 * i + h) * 3 * perms : nullptr, nullptr);
+            }
+        } catch (const std::bad_alloc &) {
+            oom.store(true);
+        }
+    };
+    {
+        ThreadGroup tg;
+        for (size_t t = 1; t < nth; t++) tg.run(worker);
+        worker();
+    }
+    if (oom.load()) throw std::bad_alloc();
+}
+
 #ifndef ZKG16_HOST_ONLY        // (tests/test_host_sanitize.py compiles the host chains alone, without kernels, under ASan)
 // ------------------------------------------------------------------------------------------------ device
 struct PoseidonDev { Fr mds[3][3], ark[P_ROUNDS][3]; };
@@ -224,6 +262,91 @@ __global__ void __launch_bounds__(64) wit_sponge_kernel(SpongeArgs g) {
             nst[i] = fp_add(acc, fp_mul(st[2], pp->mds[i][2]));
         }
         for (int i = 0; i < 3; i++) st[i] = nst[i];
+    }
+}
+
+// ---- K requests in one pass (zkg16_witness_matrix_batch).  The same two passes with the request as a grid dimension: one array
+// of all a | b (k x 2 n^2), one of all entering states (k x 3 x perms x 3, the layout of matrix_chains_batch) and one of the K
+// instance triples are read, and every request is written through a device-visible table of the K z pointers — the form the batched
+// SpMV and digit kernels read the assignments in.  Both grids stay within 65,535 per dimension and loop over what is beyond.
+struct FillBatchArgs {
+    const uint64_t *ab;             // k x (a | b)
+    const Fr *inst;                 // k x (hash_a, hash_b, hash_c)
+    Fr *const *z;                   // k
+    size_t k, n, nn, off_a, off_mc, off_mm, total;    // total = 4 (instance) + 2 nn (a, b) + nn (zeros) + nn (n + 1)
+};
+__global__ void __launch_bounds__(256) wit_matrix_fill_batch_kernel(FillBatchArgs g) {
+    for (size_t req = blockIdx.y; req < g.k; req += gridDim.y) {
+        const uint64_t *a = g.ab + req * 2 * g.nn, *b = a + g.nn;
+        Fr *z = g.z[req];
+        for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < g.total; t += (size_t)gridDim.x * blockDim.x) {
+            Fr v = Fr::zero();
+            Fr *dst;
+            if (t < 4) {
+                dst = z + t;
+                v = t == 0 ? Fr::one() : ld32(g.inst + 3 * req + (t - 1));
+            } else if (t < 4 + 2 * g.nn) {
+                const size_t e = t - 4;
+                const uint64_t x = e < g.nn ? a[e] : b[e - g.nn];
+                v.l[0] = (uint32_t)x;
+                v.l[1] = (uint32_t)(x >> 32);
+                v = fp_to_mont(v);
+                dst = z + g.off_a + e;
+            } else if (t < 4 + 3 * g.nn) {
+                dst = z + g.off_mc + (t - 4 - 2 * g.nn);
+            } else {
+                const size_t e = t - 4 - 3 * g.nn, cell = e / (g.n + 1), k1 = e % (g.n + 1);
+                dst = z + g.off_mm + e;
+                if (k1) {
+                    const size_t i = cell / g.n, j = cell % g.n, kk = k1 - 1;
+                    const uint64_t x = a[i * g.n + kk], y = b[kk * g.n + j];
+                    const uint64_t lo = x * y, hi = __umul64hi(x, y);
+                    v.l[0] = (uint32_t)lo; v.l[1] = (uint32_t)(lo >> 32); v.l[2] = (uint32_t)hi; v.l[3] = (uint32_t)(hi >> 32);
+                    v = fp_to_mont(v);
+                }
+            }
+            st32(dst, v);
+        }
+    }
+}
+
+// One lane per permutation of any chain of any request: lane q of the k x 3 x perms entering states, so that a wave is full even
+// where one request has fewer than 64 permutations per chain (8x8: 32).  The values and their order are wit_sponge_kernel's.
+struct SpongeBatchArgs {
+    const Fr *states;               // k x 3 x perms x 3
+    Fr *const *z;                   // k
+    const PoseidonDev *params;
+    size_t off[3];                  // first witness of each hash's gadget within an assignment
+    size_t lanes, perms;            // lanes = k x 3 x perms
+};
+__global__ void __launch_bounds__(64) wit_sponge_batch_kernel(SpongeBatchArgs g) {
+    const PoseidonDev *pp = g.params;
+    for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < g.lanes; q += (size_t)gridDim.x * blockDim.x) {
+        const size_t chain = q / g.perms, p = q % g.perms, req = chain / 3;
+        const int h = (int)(chain % 3);
+        Fr st[3];
+        for (int i = 0; i < 3; i++) st[i] = ld32(g.states + 3 * q + i);
+        Fr *out = g.z[req] + g.off[h] + (p == 0 ? 0 : p * PERM_WITNESSES - FIRST_PERM_SKIPPED);
+        for (int r = 0; r < P_ROUNDS; r++) {
+            const bool full = r < P_HALF || r >= P_HALF + POSEIDON_PARTIAL;
+            for (int i = 0; i < 3; i++) st[i] = fp_add(st[i], pp->ark[r][i]);
+            for (int i = 0; i < (full ? 3 : 1); i++) {
+                const Fr x = st[i];
+                const Fr x2 = fp_sqr(x), x4 = fp_sqr(x2), x8 = fp_sqr(x4), x16 = fp_sqr(x8), x17 = fp_mul(x16, x);
+                if (!(p == 0 && r == 0 && i == 0)) {
+                    st32(out, x2); st32(out + 1, x4); st32(out + 2, x8); st32(out + 3, x16); st32(out + 4, x17);
+                    out += 5;
+                }
+                st[i] = x17;
+            }
+            Fr nst[3];
+            for (int i = 0; i < 3; i++) {
+                Fr acc = fp_mul(st[0], pp->mds[i][0]);
+                acc = fp_add(acc, fp_mul(st[1], pp->mds[i][1]));
+                nst[i] = fp_add(acc, fp_mul(st[2], pp->mds[i][2]));
+            }
+            for (int i = 0; i < 3; i++) st[i] = nst[i];
+        }
     }
 }
 
@@ -324,17 +447,20 @@ void matrix_stream_free(MatrixWitnessStream *ms) { delete ms; }
 
 // device buffers of the request; z: total (+ whatever the caller appends) elements.  n_extra: trailing slots of the z-side scalar
 // vector (r, s, -rs) that part_of must cover too.
+static void poseidon_dev_ensure(zkg16_ctx *ctx) {
+    if (ctx->poseidon_dev.p) return;
+    const PoseidonH &ph = pparams();
+    PoseidonDev pd;
+    static_assert(sizeof(PoseidonDev) == sizeof(Fr64) * (9 + 3 * P_ROUNDS), "layout");
+    memcpy(pd.mds, ph.mds, sizeof pd.mds);
+    memcpy(pd.ark, ph.ark, sizeof pd.ark);
+    ctx->poseidon_dev.alloc(sizeof pd);
+    ZK_HIP(hipMemcpy(ctx->poseidon_dev.p, &pd, sizeof pd, hipMemcpyHostToDevice));
+}
+
 void matrix_stream_attach(MatrixWitnessStream *ms, zkg16_ctx *ctx, Fr *z, size_t n_extra) {
     const MatrixWitnessLayout &L = ms->L;
-    if (!ctx->poseidon_dev.p) {
-        const PoseidonH &ph = pparams();
-        PoseidonDev pd;
-        static_assert(sizeof(PoseidonDev) == sizeof(Fr64) * (9 + 3 * P_ROUNDS), "layout");
-        memcpy(pd.mds, ph.mds, sizeof pd.mds);
-        memcpy(pd.ark, ph.ark, sizeof pd.ark);
-        ctx->poseidon_dev.alloc(sizeof pd);
-        ZK_HIP(hipMemcpy(ctx->poseidon_dev.p, &pd, sizeof pd, hipMemcpyHostToDevice));
-    }
+    poseidon_dev_ensure(ctx);
     ms->z = z;
     ms->d_ab.alloc(2 * L.nn * sizeof(uint64_t));
     ms->d_states.alloc(3 * ms->mc.perms * 3 * sizeof(Fr));
@@ -387,6 +513,106 @@ void matrix_stream_produce(MatrixWitnessStream *ms, zkg16_ctx *ctx, int k) {
     ZK_HIP(hipGetLastError());
 }
 
+// ---- K requests in one pass
+size_t matrix_witness_total(size_t n) { return MatrixWitnessLayout(n).total; }
+
+void matrix_batch_chains(MatrixBatchChains &c, size_t n, const uint64_t *a, const uint64_t *b, size_t k, int threads, uint64_t *hashes) {
+    static_assert(sizeof(Fr64) == 32, "layout");
+    const auto t0 = std::chrono::steady_clock::now();
+    c.n = n; c.k = k;
+    c.perms = (n * n + POSEIDON_RATE - 1) / POSEIDON_RATE;
+    c.states.resize(k * 3 * c.perms * 12);
+    matrix_chains_batch(n, a, b, k, threads, reinterpret_cast<Fr64 *>(c.states.data()), reinterpret_cast<Fr64 *>(hashes));
+    c.hashes = hashes;
+    c.ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+// The k assignments of `c`'s requests on ctx->stream, under ctx's mutex: three copies out of the ctx's pinned staging (a | b, the
+// entering states, the instances with the z pointers), the two batched launches, one synchronisation.  The assignments share one
+// allocation, which goes back when the last of them is gone (WitnessDev::backing).  When this throws the stream has been drained.
+void matrix_batch_assign(zkg16_ctx *ctx, const MatrixBatchChains &c, const uint64_t *a, const uint64_t *b,
+                         std::vector<std::shared_ptr<WitnessDev>> &out, float *dev_ms) {
+    const MatrixWitnessLayout L(c.n);
+    const size_t k = c.k, perms = c.perms;
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t ab_bytes = up(k * 2 * L.nn * sizeof(uint64_t)), st_bytes = up(k * 3 * perms * 3 * sizeof(Fr));
+    const size_t tab_bytes = up(k * (3 * sizeof(Fr) + sizeof(Fr *))), bytes = ab_bytes + st_bytes + tab_bytes;
+    const size_t cap = ctx->opt_matrix_batch_grid > 0 ? (size_t)ctx->opt_matrix_batch_grid : 65535;
+    poseidon_dev_ensure(ctx);
+    if (ctx->mbatch_host_bytes < bytes) {           // nothing reads the old block: every call ends with the stream drained
+        if (ctx->mbatch_host) (void)hipHostFree(ctx->mbatch_host);
+        ctx->mbatch_host = nullptr;
+        ctx->mbatch_host_bytes = 0;
+        ZK_HIP(hipHostMalloc(&ctx->mbatch_host, bytes, hipHostMallocDefault));
+        ctx->mbatch_host_bytes = bytes;
+    }
+    ctx->mbatch_dev.ensure(bytes);
+    auto backing = std::make_shared<DevBuf>(k * L.total * sizeof(Fr));
+    std::vector<std::shared_ptr<WitnessDev>> wits(k);
+    for (size_t i = 0; i < k; i++) {
+        wits[i] = std::make_shared<WitnessDev>();
+        wits[i]->n = L.total;
+        wits[i]->backing = backing;
+        wits[i]->z.p = backing->as<Fr>() + i * L.total;
+        wits[i]->z.bytes = L.total * sizeof(Fr);
+    }
+    uint8_t *hs = static_cast<uint8_t *>(ctx->mbatch_host), *ds = ctx->mbatch_dev.as<uint8_t>();
+    uint64_t *h_ab = reinterpret_cast<uint64_t *>(hs);
+    for (size_t i = 0; i < k; i++) {
+        memcpy(h_ab + i * 2 * L.nn, a + i * L.nn, L.nn * sizeof(uint64_t));
+        memcpy(h_ab + i * 2 * L.nn + L.nn, b + i * L.nn, L.nn * sizeof(uint64_t));
+    }
+    memcpy(hs + ab_bytes, c.states.data(), k * 3 * perms * 3 * sizeof(Fr));
+    memcpy(hs + ab_bytes + st_bytes, c.hashes, k * 3 * sizeof(Fr));
+    Fr **h_tab = reinterpret_cast<Fr **>(hs + ab_bytes + st_bytes + k * 3 * sizeof(Fr));
+    for (size_t i = 0; i < k; i++) h_tab[i] = wits[i]->z.as<Fr>();
+
+    hipEvent_t e0, e1;
+    ZK_HIP(hipEventCreate(&e0));
+    struct EvGuard { hipEvent_t e; ~EvGuard() { (void)hipEventDestroy(e); } } g0{e0};
+    ZK_HIP(hipEventCreate(&e1));
+    EvGuard g1{e1};
+    struct Drain { zkg16_ctx *c; bool ok = false; ~Drain() { if (!ok) (void)hipStreamSynchronize(c->stream); } } drain{ctx};
+    ZK_HIP(hipEventRecord(e0, ctx->stream));
+    ZK_HIP(hipMemcpyAsync(ds, hs, k * 2 * L.nn * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+    ZK_HIP(hipMemcpyAsync(ds + ab_bytes, hs + ab_bytes, k * 3 * perms * 3 * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
+    ZK_HIP(hipMemcpyAsync(ds + ab_bytes + st_bytes, hs + ab_bytes + st_bytes, k * (3 * sizeof(Fr) + sizeof(Fr *)), hipMemcpyHostToDevice, ctx->stream));
+    Fr *const *d_tab = reinterpret_cast<Fr *const *>(ds + ab_bytes + st_bytes + k * 3 * sizeof(Fr));
+    {
+        FillBatchArgs g;
+        g.ab = reinterpret_cast<const uint64_t *>(ds);
+        g.inst = reinterpret_cast<const Fr *>(ds + ab_bytes + st_bytes);
+        g.z = d_tab;
+        g.k = k; g.n = L.n; g.nn = L.nn; g.off_a = L.off_a; g.off_mc = L.off_mc; g.off_mm = L.off_mm;
+        g.total = 4 + 3 * L.nn + L.nn * (L.n + 1);
+        const size_t bx = (g.total + 255) / 256;
+        ScopedKernelTimer kt(ctx, "wit_matrix_fill_batch_kernel", (double)g.total * (double)k);
+        hipLaunchKernelGGL(wit_matrix_fill_batch_kernel, dim3((unsigned)(bx < cap ? bx : cap), (unsigned)(k < cap ? k : cap)), dim3(256), 0,
+                           ctx->stream, g);
+        ZK_HIP(hipGetLastError());
+    }
+    {
+        SpongeBatchArgs g;
+        g.states = reinterpret_cast<const Fr *>(ds + ab_bytes);
+        g.z = d_tab;
+        g.params = ctx->poseidon_dev.as<PoseidonDev>();
+        g.off[0] = L.off_ha; g.off[1] = L.off_hb; g.off[2] = L.off_hc;
+        g.perms = perms;
+        g.lanes = k * 3 * perms;
+        const size_t bx = (g.lanes + 63) / 64;
+        ScopedKernelTimer kt(ctx, "wit_sponge_batch_kernel", (double)g.lanes);
+        hipLaunchKernelGGL(wit_sponge_batch_kernel, dim3((unsigned)(bx < cap ? bx : cap)), dim3(64), 0, ctx->stream, g);
+        ZK_HIP(hipGetLastError());
+    }
+    ZK_HIP(hipEventRecord(e1, ctx->stream));
+    ZK_HIP(hipStreamSynchronize(ctx->stream));      // the staging is free again, and the assignments are whole
+    drain.ok = true;
+    float ms = 0;
+    ZK_HIP(hipEventElapsedTime(&ms, e0, e1));
+    if (dev_ms) *dev_ms = ms;
+    out = std::move(wits);
+}
+
 }  // namespace zk
 #endif  // ZKG16_HOST_ONLY
 
@@ -410,7 +636,74 @@ int zkg16_matrix_sponge_states(size_t n, const uint64_t *a, const uint64_t *b, u
     return ZKG16_OK;
 }
 
+// The same for k requests of one size (a, b: k x n^2, request-major) on a pool of `threads` host threads (0 = 8; at most 16 and 3k):
+// request i's states (nullable: k x 3 x perms x 3 Fr) and hashes (k x 3 Fr) are those of zkg16_matrix_sponge_states(n, a_i, b_i).
+// On ZKG16_ERR_BAD_ARG nothing is written.
+int zkg16_matrix_sponge_states_batch(size_t n, const uint64_t *a, const uint64_t *b, size_t k, int threads, uint64_t *states, uint64_t *hashes) {
+    if (!a || !b || !hashes || k == 0 || n < 2 || n > 1024 || threads < 0) return ZKG16_ERR_BAD_ARG;
+    if (k > SIZE_MAX / (3 * 96 * ((n * n + 1) / 2))) return ZKG16_ERR_BAD_ARG;       // the states of k requests have no size
+    try {
+        std::vector<Fr64> hs(3 * k);        // staged: an allocation failing half way leaves `hashes` alone
+        matrix_chains_batch(n, a, b, k, threads, reinterpret_cast<Fr64 *>(states), hs.data());
+        memcpy(hashes, hs.data(), 3 * k * sizeof(Fr64));
+    } catch (const std::bad_alloc &) {
+        return ZKG16_ERR_OOM;
+    }
+    return ZKG16_OK;
+}
+
 #ifndef ZKG16_HOST_ONLY
+// K MatrixCircuit assignments of one size in one upload, two launches and one synchronisation: handle i carries the bytes of
+// zkg16_witness_matrix(n, a_i, b_i).  The chains run before the ctx is locked (option "matrix_batch_threads"); all or nothing: on
+// any error no handle is registered and nothing is written.  timings_ms (nullable, 3): host chains (wall), device, whole call.
+int zkg16_witness_matrix_batch(zkg16_ctx *ctx, size_t n, const uint64_t *a, const uint64_t *b, size_t k, uint64_t *witness_handles,
+                               uint64_t *public_inputs, float *timings_ms) {
+    if (!ctx || !a || !b || !witness_handles || k == 0 || n < 2 || n > 1024) return ZKG16_ERR_BAD_ARG;
+    const auto t_call = std::chrono::steady_clock::now();
+    const size_t total = MatrixWitnessLayout(n).total;
+    if (total >= ((size_t)1 << 32)) return ZKG16_ERR_DOMAIN_TOO_LARGE;
+    if (k > SIZE_MAX / (total * sizeof(Fr))) return ZKG16_ERR_BAD_ARG;
+    MatrixBatchChains mc;
+    std::vector<uint64_t> hashes;
+    try {
+        hashes.resize(12 * k);
+        matrix_batch_chains(mc, n, a, b, k, ctx->opt_matrix_batch_threads, hashes.data());
+    } catch (const std::bad_alloc &) {
+        return ZKG16_ERR_OOM;
+    }
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    try {
+        ZK_HIP(hipSetDevice(ctx->device));
+        std::vector<std::shared_ptr<WitnessDev>> wits;
+        float dev_ms = 0;
+        matrix_batch_assign(ctx, mc, a, b, wits, &dev_ms);
+        const uint64_t first = ctx->next_handle.fetch_add(k);
+        size_t put = 0;
+        try {
+            for (; put < k; put++) ctx->wits.put(first + put, std::move(wits[put]));
+        } catch (const std::bad_alloc &) {          // all or nothing: what was registered is taken back
+            for (size_t i = 0; i < put; i++) ctx->wits.erase(first + i);
+            return ZKG16_ERR_OOM;
+        }
+        for (size_t i = 0; i < k; i++) witness_handles[i] = first + i;
+        if (public_inputs) memcpy(public_inputs, hashes.data(), 12 * k * sizeof(uint64_t));
+        if (timings_ms) {
+            timings_ms[0] = (float)mc.ms;
+            timings_ms[1] = dev_ms;
+            timings_ms[2] = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
+        }
+    } catch (const HipError &e) {
+        char buf[512];
+        snprintf(buf, sizeof buf, "%s failed: %s (%s:%d)", e.what, hipGetErrorString(e.err), e.file, e.line);
+        ctx->last_error = buf;
+        (void)hipGetLastError();
+        return e.err == hipErrorOutOfMemory ? ZKG16_ERR_OOM : ZKG16_ERR_HIP;
+    } catch (const std::bad_alloc &) {
+        return ZKG16_ERR_OOM;
+    }
+    return ZKG16_OK;
+}
+
 // The MatrixCircuit's full assignment for (a, b), built on the device: a witness handle as zkg16_witness_load would return for
 // zkg16_circuit_matrix_witness's output.  public_inputs (nullable): hash_a, hash_b, hash_c (Montgomery), the handler's
 // public inputs.  timings_ms (nullable, 3): host chains, upload + kernels (device time), whole call.

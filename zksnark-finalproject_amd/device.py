@@ -197,6 +197,25 @@ class Device:
         self._check(self.lib.zkg16_witness_matrix(self.ctx, n, a.reshape(-1), b.reshape(-1), C.byref(handle), pub.ctypes.data, C.addressof(ms)))
         return handle.value, pub, dict(host_sponges_ms=float(ms[0]), device_ms=float(ms[1]), call_ms=float(ms[2]))
 
+    @staticmethod
+    def _matrix_batch(what, a, b):
+        a = np.ascontiguousarray(a, dtype=np.uint64)
+        b = np.ascontiguousarray(b, dtype=np.uint64)
+        if a.ndim != 3 or a.shape[1] != a.shape[2] or b.shape != a.shape:
+            raise ValueError(what + ": a and b must be k x n x n")
+        return a, b, a.shape[0], a.shape[1]
+
+    def witness_matrix_batch(self, a, b):
+        """The MatrixCircuit's assignments of k requests of one size, a and b [k, n, n], built in one device pass
+        (zkg16_witness_matrix_batch) -> (witness handles [k], public inputs [k, 3, 4], dict of ms: host chains / device / whole call).
+        Handle i holds what witness_matrix(a[i], b[i]) would; each is freed on its own."""
+        a, b, k, n = self._matrix_batch("witness_matrix_batch", a, b)
+        handles = np.zeros(k, dtype=np.uint64)
+        pub = np.zeros((k, 3, 4), dtype=np.uint64)
+        ms = (C.c_float * 3)()
+        self._check(self.lib.zkg16_witness_matrix_batch(self.ctx, n, _ptr(a), _ptr(b), k, _ptr(handles), _ptr(pub), C.addressof(ms)))
+        return handles, pub, dict(host_sponges_ms=float(ms[0]), device_ms=float(ms[1]), call_ms=float(ms[2]))
+
     def witness_read(self, h, n_assign):
         z = np.zeros((n_assign, 4), dtype=np.uint64)
         self._check(self.lib.zkg16_witness_read(self.ctx, h, z.reshape(-1), n_assign))
@@ -337,6 +356,23 @@ class Device:
         self._check(self.lib.zkg16_prove_matrix(self.ctx, pk_h, r1cs_h, n, a.reshape(-1), b.reshape(-1), _u64(r), _u64(s), proof, inf,
                                                 pub.ctypes.data, C.addressof(ms)))
         return proof, inf, pub, dict(host_sponges_ms=float(ms[0]), parts=int(ms[1]), call_ms=float(ms[2]))
+
+    def prove_matrix_batch(self, pk_h, r1cs_h, a, b, rs, ss):
+        """k matrix-handler requests of one size on one resident key, a and b [k, n, n], rs / ss [k, 4]: assignments and proofs in
+        batched device passes (zkg16_prove_matrix_batch) -> (proofs [k, 48], inf [k, 3], public inputs [k, 3, 4], dict of ms).  Proof i
+        is byte-identical to prove_resident on witness_matrix(a[i], b[i]) with (rs[i], ss[i])."""
+        a, b, k, n = self._matrix_batch("prove_matrix_batch", a, b)
+        rs = _u64(rs).reshape(-1, 4)
+        ss = _u64(ss).reshape(-1, 4)
+        if rs.shape[0] != k or ss.shape[0] != k:
+            raise ValueError("prove_matrix_batch: one r and one s per request")
+        proofs = np.zeros((k, 48), dtype=np.uint64)
+        inf = np.zeros((k, 3), dtype=np.uint8)
+        pub = np.zeros((k, 3, 4), dtype=np.uint64)
+        ms = (C.c_float * 4)()
+        self._check(self.lib.zkg16_prove_matrix_batch(self.ctx, pk_h, r1cs_h, n, _ptr(a), _ptr(b), k, _ptr(rs), _ptr(ss), _ptr(proofs), _ptr(inf),
+                                                      _ptr(pub), C.addressof(ms)))
+        return proofs, inf, pub, dict(host_sponges_ms=float(ms[0]), witness_ms=float(ms[1]), prove_ms=float(ms[2]), call_ms=float(ms[3]))
 
     def prove(self, pk_h, r, s, r1cs, z):
         args, keep = self._csr(r1cs)

@@ -1,5 +1,6 @@
 """In-process mirrors of the reference's request handlers around the hot path (the callers of `Groth16::prove`):
     prove_matrix     src/arkworks/backend/matrix_proof.rs:94-166   (POST /api/matrix_prove/prove)
+    prove_matrices   K such requests of one size under one key, in batched device passes (no counterpart upstream)
     prove_fibonacci  src/arkworks/backend/fibbonaci_handler.rs:98-145
     prove_prime / verify_prime  src/arkworks/backend/prime_snark.rs:49-146, 165-206
 Same steps, same response fields: synthesize the circuit (host C++ mirror), per-request Groth16 setup (on the device,
@@ -192,6 +193,51 @@ def prove_matrix(dev, size, matrix_a, matrix_b, seed=0, keep_key=False):
                 num_variables=circ.num_instance, proof=wire.encode_proof(out["proof"], out["inf"]),
                 # the reference returns the prepared key (encode_pvk, io.rs:62-68); the plain key is kept beside it
                 pvk=wire.encode_pvk(out["vk"]), vk=wire.encode_vk(out["vk"]), _detail=out, _circuit=circ)
+
+
+def prove_matrices(dev, size, pairs, seed=0, key=None):
+    """K requests of one size under ONE key, assignments and proofs in batched device passes (Device.prove_matrix_batch).  pairs: K
+    (matrix_a, matrix_b).  The key is set up once on the device from `seed` (the draws of prove_matrix, then r, s per request, so
+    request 0 is prove_matrix's proof for that seed), or passed in as key=(pk handle, vk dict), which stays the caller's.  The
+    matrices come from the shape cache.  -> the shared vk / pvk and, per request, prove_matrix's hash_a / hash_b / hash_c / proof."""
+    k = len(pairs)
+    if k == 0:
+        raise ValueError("prove_matrices: no requests")
+    a = np.stack([np.asarray(p[0], dtype=np.uint64).reshape(size, size) for p in pairs])
+    b = np.stack([np.asarray(p[1], dtype=np.uint64).reshape(size, size) for p in pairs])
+    shapes = dev.__dict__.setdefault("_matrix_shapes", {})
+    if size not in shapes:
+        shapes[size] = _CachedShape.on_device(dev, size)
+    shape = shapes[size]
+    rng = random.Random(seed)
+    made = []
+    try:
+        setup_time = 0.0
+        if key is None:
+            from .device import scalar_mul
+            trap = np.stack([_fr_mont(rng.randrange(1, R_MOD)) for _ in range(5)])
+            kk = np.array([rng.getrandbits(62) for _ in range(4)], dtype=np.uint64)
+            g1 = scalar_mul("g1", g1_generator(), kk)[0]
+            g2 = scalar_mul("g2", g2_generator(), kk)[0]
+            t0 = time.perf_counter()
+            ph, vk = dev.setup_resident(shape.rh, shape.num_instance, trap, g1, g2)
+            made.append(ph)
+            setup_time = time.perf_counter() - t0
+        else:
+            ph, vk = key
+        rss = [(_fr_mont(rng.randrange(R_MOD)), _fr_mont(rng.randrange(R_MOD))) for _ in range(k)]
+        rs, ss = np.stack([r for r, _ in rss]), np.stack([s for _, s in rss])
+        t0 = time.perf_counter()
+        proofs, inf, pubs, ms = dev.prove_matrix_batch(ph, shape.rh, a, b, rs, ss)
+        proving_time = time.perf_counter() - t0
+    finally:
+        for h in made:
+            dev.pk_free(h)
+    requests = [dict(hash_a=wire.encode_hash(pubs[i][0]), hash_b=wire.encode_hash(pubs[i][1]), hash_c=wire.encode_hash(pubs[i][2]),
+                     proof=wire.encode_proof(proofs[i], inf[i])) for i in range(k)]
+    return dict(vk=wire.encode_vk(vk), pvk=wire.encode_pvk(vk), setup_time=setup_time, proving_time=proving_time,
+                num_constraints_circuit=shape.num_constraints, num_variables=shape.num_instance, requests=requests,
+                _detail=dict(proofs=proofs, inf=inf, public_inputs=pubs, vk=vk, rs=rs, ss=ss, ms=ms))
 
 
 def prove_fibonacci(dev, a, b, num_of_rounds, seed=42, keep_key=False):
