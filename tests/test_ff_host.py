@@ -57,7 +57,9 @@ def test_field_random_vs_python(shim):
             a, b = rng.randrange(mod), rng.randrange(mod)
             got = from_m(unlimbs(call_field(shim, "ht_%s_op" % field, 2, limbs(to_m(a), nl), limbs(to_m(b), nl))))
             assert got == a * b % mod
-        # values just below the modulus / with all-ones limbs exercise the carry paths
+        # values just below the modulus / with all-ones limbs exercise the carry paths of fp_mul_host64, the 64-bit-limb routine
+        # that fp_mul is in a host compile; fp_mul_inline, the 32-bit-limb CIOS the kernels run, is called directly on every ordered
+        # pair of the edge patterns by tests/test_prim_host.py::test_saturated_field_edges (and on the device by test_prim_gpu.py)
         for a in (mod - 1, mod - 2, (1 << (32 * 2 * nl - 1)) % mod, ((1 << 64 * nl) - 1) % mod):
             for b in (mod - 1, 1, 2, a):
                 got = from_m(unlimbs(call_field(shim, "ht_%s_op" % field, 2, limbs(to_m(a), nl), limbs(to_m(b), nl))))

@@ -25,6 +25,10 @@
 // window-sum vectors a proof returns to the host.
 #pragma once
 #include "ff.cuh"
+#ifdef ZK_FQU_CHECK
+#include <stdio.h>
+#include <stdlib.h>
+#endif
 
 namespace zk {
 
@@ -100,6 +104,43 @@ ZK_HD FqU FqU::one() {
     return r;
 }
 
+// ZK_FQU_CHECK (host passes only, off by default; tests/csrc/prim_shim.hip's host build defines it): the functions below
+// assert their stated operand conditions on the ACTUAL values - limbs 0..12 below 2^29, and the value against k q by an exact
+// comparison - and print file and line and abort when one is broken, so the intermediate subtrahends inside the curve
+// formulas are checked while a test runs them, not only their outputs.
+#if defined(ZK_FQU_CHECK) && defined(__HIP_DEVICE_COMPILE__)
+#error "ZK_FQU_CHECK is a host-only check: compile with --offload-host-only"
+#endif
+#ifdef ZK_FQU_CHECK
+inline int fqu_check_cmp(const FqU &v, uint32_t k) {      // sign of v - k q for normalised v, k <= 2^12
+    uint32_t kq[14];
+    uint64_t c = 0;
+    for (int i = 0; i < 14; i++) {
+        c += (uint64_t)k * FqUP::mod(i);
+        kq[i] = i < 13 ? (uint32_t)c & FqU::MASK : (uint32_t)c;
+        c >>= 29;
+    }
+    for (int i = 13; i >= 0; i--)
+        if (v.l[i] != kq[i]) return v.l[i] < kq[i] ? -1 : 1;
+    return 0;
+}
+inline void fqu_check(const FqU &v, uint32_t k, bool strict, const char *what, int line) {      // v normalised and v <= k q (strict: <)
+    bool ok = true;
+    for (int i = 0; i < 13; i++) ok = ok && v.l[i] <= FqU::MASK;
+    if (ok) ok = strict ? fqu_check_cmp(v, k) < 0 : fqu_check_cmp(v, k) <= 0;
+    if (ok) return;
+    fprintf(stderr, "%s:%d: %s: operand not normalised or not %s %u q:", __FILE__, line, what, strict ? "below" : "at most", k);
+    for (int i = 13; i >= 0; i--) fprintf(stderr, " %08x", v.l[i]);
+    fprintf(stderr, "\n");
+    abort();
+}
+#define ZK_FQU_LE(v, k, what) fqu_check(v, (uint32_t)(k), false, what, __LINE__)
+#define ZK_FQU_LT(v, k, what) fqu_check(v, (uint32_t)(k), true, what, __LINE__)
+#else
+#define ZK_FQU_LE(v, k, what) do { } while (0)
+#define ZK_FQU_LT(v, k, what) do { } while (0)
+#endif
+
 // carry propagation: limbs back below 2^29 (the top limb keeps whatever is left; values stay < 2^406)
 ZK_HD void fqu_normalise(FqU &a) {
     uint32_t c = 0;
@@ -124,6 +165,8 @@ ZK_HD FqU fqu_dbl(const FqU &a) { return fqu_add(a, a); }
 // a - b + M*q ; L = 8 / 32 / 64 / 128 ; requires b normalised and b <= (L-1) q
 template <int L>
 ZK_HD FqU fqu_sub(const FqU &a, const FqU &b) {
+    ZK_FQU_LT(a, 4096, "fqu_sub minuend");
+    ZK_FQU_LE(b, L - 1, "fqu_sub subtrahend");
     FqU r;
 #pragma unroll
     for (int i = 0; i < 14; i++) {
@@ -134,6 +177,7 @@ ZK_HD FqU fqu_sub(const FqU &a, const FqU &b) {
     return r;
 }
 ZK_HD FqU fqu_neg(const FqU &a) {   // 8q - a  (a <= 7q); keeps exact zero as exact zero so flags survive
+    ZK_FQU_LE(a, 7, "fqu_neg");
     if (a.is_zero()) return a;
     return fqu_sub<8>(FqU::zero(), a);
 }
@@ -142,6 +186,8 @@ ZK_HD FqU fqu_neg(const FqU &a) {   // 8q - a  (a <= 7q); keeps exact zero as ex
 // Inputs: normalised, values < 2^12 q.  Output: normalised, value < 2q.
 template <bool SQR>
 ZK_HD FqU fqu_mul_impl(const FqU &a, const FqU &b) {
+    ZK_FQU_LT(a, 4096, "fqu_mul_impl a");
+    ZK_FQU_LT(b, 4096, "fqu_mul_impl b");
     constexpr int N = 14;
     uint32_t m[N];
     uint32_t a2[N];
@@ -188,6 +234,10 @@ ZK_HD FqU fqu_mul_impl(const FqU &a, const FqU &b) {
 // ((2 * 2^24 q^2 + 2^406 q) / 2^406 < 2q).  Always inlined (four operands = 56 registers do not fit the 32 argument VGPRs of
 // a device-function call): used once per mixed addition, for Y3 = R (Q - X3) + (-Y1) PPP.
 ZK_HD FqU fqu_mul2(const FqU &a, const FqU &b, const FqU &c, const FqU &d) {
+    ZK_FQU_LT(a, 4096, "fqu_mul2 a");
+    ZK_FQU_LT(b, 4096, "fqu_mul2 b");
+    ZK_FQU_LT(c, 4096, "fqu_mul2 c");
+    ZK_FQU_LT(d, 4096, "fqu_mul2 d");
     constexpr int N = 14;
     uint32_t m[N];
     FqU r;
@@ -446,6 +496,8 @@ __device__ __forceinline__ Fq2U fq2u_mul_lazy(const Fq2U &a, const Fq2U &b) {
 ZK_HD Fq2U f_sqr(const Fq2U &a) {
     // (c0+c1)(c0-c1) + 2 c0 c1 u ; squared values are differences of stored coordinates (components < 74q, or 84q for
     // 2*Y in a doubling) -> level-128 subtraction
+    ZK_FQU_LE(a.c0, 127, "f_sqr(Fq2U) c0");
+    ZK_FQU_LE(a.c1, 127, "f_sqr(Fq2U) c1");
     const FqU p = fqu_mul(a.c0, a.c1);
     const FqU r0 = fqu_mul(fqu_add(a.c0, a.c1), fqu_sub<128>(a.c0, a.c1));
     return Fq2U{r0, fqu_dbl(p)};
@@ -480,6 +532,8 @@ ZK_HD FqU fqu_inv(const FqU &a) {          // a^(q-2); a < 2^12 q, result < 2q
 }
 ZK_HD FqU f_inv(const FqU &a) { return fqu_inv(a); }
 ZK_HD Fq2U f_inv(const Fq2U &a) {           // conj(a) / (c0^2 + c1^2); components of a <= 31q
+    ZK_FQU_LE(a.c0, 31, "f_inv(Fq2U) c0");
+    ZK_FQU_LE(a.c1, 31, "f_inv(Fq2U) c1");
     const FqU n = fqu_inv(fqu_add(fqu_sqr(a.c0), fqu_sqr(a.c1)));
     return Fq2U{fqu_mul(a.c0, n), fqu_mul(fqu_sub<32>(FqU::zero(), a.c1), n)};
 }
