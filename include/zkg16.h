@@ -534,6 +534,8 @@ ZKG16_API void zkg16_kernel_stats_reset(zkg16_ctx *ctx);
  *   "fixed_base_bits" window width of the setup's fixed-base multiplications (0 = by batch size; 16 / 18 / 20 = two-level tables)
  *   "g2_lazy"        G2 accumulation's Fq2 products: 0 / 1 (default) two fused two-product reductions with operands parked in LDS, 2 = Karatsuba
  *   "g1_inline"      G1 accumulation (plain loop): 0 / 1 (default) every field product inlined, no call; 2 = products as device-function calls
+ *   "acc_lazy"       the default G1 / G2 accumulation loops: 1 (default) = mixed additions without the carry passes their results do not
+ *                    need, 0 = the earlier additions (same sums; for A/B runs)
  *   "lanes"          proofs this ctx runs at a time (1..8, default 2): see the note on re-entrancy at the top
  *   "matrix_parts"   zkg16_prove_matrix: slices of the host sponges the proof is fed in (0 = five growing slices, k = k equal ones; 1 = assignment first, then the proof)
  *   "batch_max"      zkg16_prove_batch / zkg16_prove_matrix_batch: proofs per device pass (0 = as many as fit, else 1..65535)

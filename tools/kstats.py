@@ -1,5 +1,5 @@
 """Per-kernel HIP-event table for one workload (development probe, GPU box):
-   python tools/kstats.py [matrix_n] [opt=value ...]"""
+   python tools/kstats.py [matrix_n] [tables=CZ,CH] [opt=value ...]     (tables=: window tables first, 0 = default widths)"""
 import os
 import sys
 
@@ -10,13 +10,17 @@ from zksnark_finalproject_amd import Device
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 32
 dev = Device(0)
+tables = [a.split("=")[1] for a in sys.argv[2:] if a.startswith("tables=")]
 for a in sys.argv[2:]:
-    dev.set_option(a.split("=")[0], int(a.split("=")[1]))
+    if not a.startswith("tables="):
+        dev.set_option(a.split("=")[0], int(a.split("=")[1]))
 trap, g1, g2 = bench.draw_key_inputs(7)
 c, _, desc = bench.synthesize("matrix", n)
 rh = dev.r1cs_load(c.r1cs, c.num_vars)
 ph, vk = dev.setup_resident(rh, c.num_instance, trap, g1, g2)
 wh = dev.witness_load(c.z)
+if tables:
+    print("window tables: %.2f GB" % (dev.pk_precompute(ph, *[int(x) for x in tables[0].split(",")]) / 1e9), flush=True)
 r, s = bench.fr_mont(12345), bench.fr_mont(67890)
 dev.prove_resident(ph, rh, wh, r, s)
 dev.kernel_stats_reset()

@@ -84,7 +84,7 @@ void copy_options(zkg16_ctx *dst, const zkg16_ctx *src) {
     dst->opt_window_bits_h = src->opt_window_bits_h; dst->opt_reduce_chunk = src->opt_reduce_chunk; dst->opt_wm_concurrent = src->opt_wm_concurrent;
     dst->opt_ntt_radix = src->opt_ntt_radix; dst->opt_ntt_xcd = src->opt_ntt_xcd; dst->opt_acc_debug = src->opt_acc_debug;
     dst->opt_sort_mode = src->opt_sort_mode; dst->opt_acc_pipeline = src->opt_acc_pipeline; dst->opt_fuse_pointwise = src->opt_fuse_pointwise;
-    dst->opt_matrix_parts = src->opt_matrix_parts; dst->opt_g2_lazy = src->opt_g2_lazy; dst->opt_g1_inline = src->opt_g1_inline; dst->opt_fixed_base_bits = src->opt_fixed_base_bits;
+    dst->opt_matrix_parts = src->opt_matrix_parts; dst->opt_g2_lazy = src->opt_g2_lazy; dst->opt_g1_inline = src->opt_g1_inline; dst->opt_acc_lazy = src->opt_acc_lazy; dst->opt_fixed_base_bits = src->opt_fixed_base_bits;
     dst->opt_collect_threads = src->opt_collect_threads; dst->opt_batch_max = src->opt_batch_max; dst->opt_matrix_batch_threads = src->opt_matrix_batch_threads; dst->opt_matrix_batch_grid = src->opt_matrix_batch_grid; dst->opt_verify_batch_min = src->opt_verify_batch_min; dst->opt_verify_wire_min = src->opt_verify_wire_min; dst->opt_verify_each_after = src->opt_verify_each_after; dst->opt_wm_transforms = src->opt_wm_transforms;
     dst->kernel_timing = src->kernel_timing; dst->kernel_timing_accumulate_only = src->kernel_timing_accumulate_only;
 }
@@ -1199,6 +1199,11 @@ int set_option_one(zkg16_ctx *ctx, const char *name, int64_t value) {
     if (!strcmp(name, "g1_inline")) {          // G1 bucket accumulation (plain loop): 0 / 1 (default) = every field product inlined, 2 = products as device-function calls (the earlier loop)
         if (value < 0 || value > 2) return ZKG16_ERR_BAD_ARG;
         ctx->opt_g1_inline = value == 2 ? 0 : 1;
+        return ZKG16_OK;
+    }
+    if (!strcmp(name, "acc_lazy")) {           // default G1 / G2 bucket accumulation loops: 1 (default) = mixed additions without the carry passes their results do not need, 0 = the earlier additions (xyzz_madd_inline, xyzz_madd_lazy)
+        if (value < 0 || value > 1) return ZKG16_ERR_BAD_ARG;
+        ctx->opt_acc_lazy = (int)value;
         return ZKG16_OK;
     }
     if (!strcmp(name, "matrix_parts")) {       // zkg16_prove_matrix: slices of the host sponges the proof is fed in (0 = five growing slices; k = k equal ones; 1 = no overlap: assignment first)

@@ -327,6 +327,7 @@ struct zkg16_ctx {
     int opt_collect_threads = -1;                     // -1: the z-side MSMs' window sums are combined on their own host threads when the key is plain; 1 always; 0 never
     int opt_fixed_base_bits = 0;                      // setup's fixed-base window width (0 = by batch size; even widths >= 16 are built in two levels)
     int opt_g2_lazy = 1;                              // G2 accumulation: Fq2 products with one reduction per component, operands parked in LDS (ffu.cuh: fq2u_mul_lazy)
+    int opt_acc_lazy = 1;                             // default G1 / G2 accumulation loops: the mixed addition without the carry passes its results do not need (ec.cuh: xyzz_madd_inline_lc, xyzz_madd_lazy_lc); 0: xyzz_madd_inline / xyzz_madd_lazy
     int opt_g1_inline = 1;                            // G1 accumulation (plain loop): every field product inlined (ec.cuh: xyzz_madd_inline); 0: products as calls
     int opt_matrix_parts = 0;                         // zkg16_prove_matrix: gadget slices the assignment arrives in (0 = five growing slices, k = k equal ones, 1 = no overlap)
     int opt_fuse_pointwise = 1;                       // the point-wise product on the load of the last transform (0: its own pass)

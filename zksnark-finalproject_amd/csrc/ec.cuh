@@ -289,6 +289,110 @@ __device__ __forceinline__ void xyzz_madd_inline(XYZZ<FqU> &acc, const Affine<Fq
 __host__ __device__ inline void xyzz_madd_inline(XYZZ<FqU> &acc, const Affine<FqU> &q, bool neg) { xyzz_madd(acc, q, neg); }      // host pass of the kernel template only
 #endif
 
+// ---- the default bucket accumulations' mixed additions (msm.hip, option "acc_lazy"): xyzz_madd_inline (G1) and xyzz_madd_lazy (G2)
+// with the carry passes left out that no consumer needs (ffu.cuh, "Skipped carry passes": the limb rule every operand below is held
+// against).  The kernels are bound by VALU issue and a carry pass is ~40 instructions, so what counts is the instruction count:
+//   * the sign of the term is folded into R.  -q is never formed in front of the addition (a negation whose two sides every
+//     iteration of a wave with mixed signs runs): S2 = q.y ZZZ < 2q, and R = (neg ? 8q - S2 : S2) + (64q - Y1) is ONE limb-wise
+//     expression with one pass (limbs before it < 2^31, R < 72q).  The negated y itself is needed only where a bucket's run
+//     starts (acc at infinity) and in the doubling, and is formed there;
+//   * X3 = R^2 - PPP - 2Q is one limb-wise expression on the pre-borrowed 32q and one pass instead of three (fqu_sub_b_2c): the
+//     same value as before, < 34q in G1 (R^2 < 2q) and < 36q per component in G2 (a square's second component < 4q);
+//   * 64q - Y1 enters the fused product Y3 = R (Q - X3) + (64q - Y1) PPP as bare limb differences (G1; limbs < 2^30 beside the
+//     normalised pair: 2^58 + 2^59 < 3.57 2^58).  R and Pp are squared and Q - X3 would put 2^59.58 beside the pair (> 2^59.36),
+//     so these three keep their passes.  In G2, Y3 is two Fq2 products; there the bare negation is the parked 128q - a1 of each
+//     of the eight products (fq2u_mul_lc), and the squarings take the bare sum c0 + c1 (fq2u_sqr_lc).
+// The results are other representatives of the same residues than xyzz_madd's where the term is negated (R = 72q - S2 - Y1 instead
+// of 64q + (8q - y) ZZZ - Y1 reduced), inside the same stored bounds (X, Y < 42q; ZZ, ZZZ < 2q, in G2 < 10q per component).
+// Both compile for the host as well, where a ZK_FQU_CHECK build asserts every operand (tests/csrc/madd_lazy_shim.hip).
+ZK_HD FqU fqu_mul_ilc(const FqU &a, const FqU &b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return fqu_mul_il(a, b);
+#else
+    return fqu_mul_impl<false>(a, b);
+#endif
+}
+ZK_HD FqU fqu_sqr_ilc(const FqU &a) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return fqu_sqr_il(a);
+#else
+    return fqu_mul_impl<true>(a, a);
+#endif
+}
+ZK_HD void xyzz_madd_inline_lc(XYZZ<FqU> &acc, const Affine<FqU> &q, bool neg) {
+    if (q.is_inf()) return;
+    if (acc.is_inf()) {
+        acc = XYZZ<FqU>{q.x, neg ? f_neg(q.y) : q.y, FqU::one(), FqU::one()};
+        return;
+    }
+    const FqU nY1 = fqu_rsub_raw<64>(acc.y);                  // 64q - Y1, limbs < 2^30: an addend of R and an operand of Y3
+    FqU U2 = fqu_mul_ilc(q.x, acc.zz);
+    FqU S2 = fqu_mul_ilc(q.y, acc.zzz);
+    FqU Pp = f_sub2(U2, acc.x);                               // squared: normalised
+    FqU R = fqu_addsub_sel(S2, nY1, neg);                     // squared: normalised
+    // P == +-Q after the general formula, as in xyzz_madd_inline
+    const bool same_x = f_is_zero_mod(Pp);
+    const bool same_p = same_x && f_is_zero_mod(R);
+    FqU PP = fqu_sqr_ilc(Pp);
+    FqU PPP = fqu_mul_ilc(Pp, PP);
+    acc.zz = fqu_mul_ilc(acc.zz, PP);
+    acc.zzz = fqu_mul_ilc(acc.zzz, PPP);
+    FqU Q = fqu_mul_ilc(acc.x, PP);
+    FqU X3 = fqu_sub_b_2c(fqu_sqr_ilc(R), PPP, Q);
+    const FqU QmX3 = f_sub2(Q, X3);                           // normalised: un-normalised it is 2^59.58 beside R's pair, > 2^59.36
+#if defined(__HIP_DEVICE_COMPILE__)
+    __builtin_amdgcn_sched_barrier(0);
+#endif
+    acc.y = fqu_mul2_lc<30>(R, QmX3, nY1, PPP);
+#if defined(__HIP_DEVICE_COMPILE__)
+    __builtin_amdgcn_sched_barrier(0);
+#endif
+    acc.x = X3;
+    if (same_x) {
+        if (same_p) {
+            const Affine<FqU> qs{q.x, neg ? f_neg(q.y) : q.y};
+#if defined(__HIP_DEVICE_COMPILE__)
+            acc = xyzz_dbl_affine_inline(qs);
+#else
+            acc = xyzz_dbl_affine(qs);
+#endif
+        } else {
+            acc = XYZZ<FqU>::inf();
+        }
+    }
+}
+// G2; on the device only for kernels with one wave per block (the LDS operand slots of fqu_mul2_lds).  The start of a run negates y
+// in front of the test for infinity, under `neg && acc.is_inf()`: with the negation inside the start's branch the register allocator
+// spilled 25 registers of the accumulation kernel to scratch; in this form it spills none (profiles/acc_lazy_resource_usage.txt).
+ZK_HD void xyzz_madd_lazy_lc(XYZZ<Fq2U> &acc, const Affine<Fq2U> &q_in, bool neg) {
+    if (q_in.is_inf()) return;
+    Affine<Fq2U> q = q_in;
+    const bool start = acc.is_inf();
+    if (neg && start) q.y = f_neg(q.y);
+    if (start) {
+        acc = XYZZ<Fq2U>{q.x, q.y, Fq2U::one(), Fq2U::one()};
+        return;
+    }
+    Fq2U U2 = fq2u_mul_lc(q.x, acc.zz);
+    Fq2U S2 = fq2u_mul_lc(q.y, acc.zzz);
+    Fq2U Pp = f_sub2(U2, acc.x);
+    Fq2U R{fqu_addsub_sel(S2.c0, fqu_rsub_raw<64>(acc.y.c0), neg), fqu_addsub_sel(S2.c1, fqu_rsub_raw<64>(acc.y.c1), neg)};
+    if (f_is_zero_mod(Pp)) {
+        if (f_is_zero_mod(R)) acc = xyzz_dbl_affine(Affine<Fq2U>{q.x, neg ? f_neg(q.y) : q.y});
+        else acc = XYZZ<Fq2U>::inf();
+        return;
+    }
+    Fq2U PP = fq2u_sqr_lc(Pp);
+    Fq2U PPP = fq2u_mul_lc(Pp, PP);
+    Fq2U Q = fq2u_mul_lc(acc.x, PP);
+    const Fq2U RR = fq2u_sqr_lc(R);
+    Fq2U X3{fqu_sub_b_2c(RR.c0, PPP.c0, Q.c0), fqu_sub_b_2c(RR.c1, PPP.c1, Q.c1)};
+    acc.y = f_sub(fq2u_mul_lc(R, f_sub2(Q, X3)), fq2u_mul_lc(acc.y, PPP));      // Q - X3 normalised: it meets the bare 128q - R1
+    acc.x = X3;
+    acc.zz = fq2u_mul_lc(acc.zz, PP);
+    acc.zzz = fq2u_mul_lc(acc.zzz, PPP);
+}
+
 ZK_HD bool xyzz_madd_front(XYZZ<Fq2U> &acc, const Affine<Fq2U> &q_in, bool neg, MaddTail<Fq2U> &t) {
     if (q_in.is_inf()) { t.a = t.b = Fq2U::zero(); return false; }
     Affine<Fq2U> q = q_in;

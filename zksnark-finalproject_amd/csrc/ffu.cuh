@@ -19,6 +19,27 @@
 // Only exact zero limbs encode the additive identity used as a flag (point at infinity); "is this value 0 mod q"
 // (the P == Q / P == -Q tests of the addition formulas) is fqu_is_zero_mod: value in {0, q, 2q, ...}.
 //
+// Skipped carry passes (the bucket accumulations' mixed additions, ec.cuh: xyzz_madd_inline_lc / xyzz_madd_lazy_lc).  A carry
+// pass (fqu_normalise: add, mask, shift for each of 13 limbs) does not change a VALUE, only how it is spread over the limbs, so
+// it is needed only where the next consumer needs small limbs.  Write "limbs < 2^A" when limbs 0..12 of an operand are below
+// 2^A (limb 13 is bounded by the value: < 2^12 q / 2^377 < 2^16).  What the consumers need:
+//   * a limb-wise sum or difference needs nothing but 32 bits per limb, and ONE pass at the end of a whole expression
+//     normalises it: R = (+-S2) + (64 q - Y1) and X3 = RR + (32 q - PPP - 2 Q) are each one expression and one pass;
+//   * a product (fqu_mul_impl) accumulates a column in 64 bits: 14 operand products < 2^(A+B), 14 reduction products
+//     m q < 2^58 and the carry of the column before (< 2^64 / 2^29 = 2^35): 14 2^(A+B) + 14 2^58 + 2^35 < 2^64 holds iff
+//     2^(A+B) < (2^64 - 2^35) / 14 - 2^58 = 3.57 2^58, i.e. A + B <= 59.84;
+//   * the two-product form (fqu_mul2) holds two rows of operand products: 2^(A+B) + 2^(C+D) < 3.57 2^58; with one pair
+//     normalised (2^58) the other may reach 2.57 2^58 = 2^59.36.
+// What the producers give: a bare "M q - b" (b normalised, M q pre-borrowed into [2^29 - 1, 2^30)) has limbs < 2^30; a sum of
+// two normalised values has limbs < 2^30; a difference "a + (M q - b)" before its pass has limbs < 2^29 + 2^30 = 2^30.58.
+// So: a bare negation or a bare sum may enter a product beside a normalised partner (30 + 29 = 59), and fqu_mul2 beside a
+// normalised pair (2^58 + 2^59 = 3 2^58); an un-normalised DIFFERENCE may NOT enter fqu_mul2 (59.58 > 59.36) and is not offered
+// to a plain product either (59.58 would fit the 64 bits, but the template admits whole bit counts only: LA + LB <= 59, and no
+// caller needs it); two lazy operands may never meet (>= 60), and a lazy value is never squared.  The conditions are template
+// parameters (fqu_mul_impl<SQR, LA, LB>, fqu_mul2_lc<LC>), checked at compile time against the rule and, in a ZK_FQU_CHECK
+// host build, on every operand's actual limbs; that build also accumulates every column a second time in 128 bits and
+// aborts when the 64-bit accumulator would have wrapped.  Value bounds (< 2^12 q) are unchanged by skipping a pass.
+//
 // The arkworks-compatible saturated Montgomery form (x * 2^384 mod q, 12 x u32 — what the proving key and the proof
 // use, include/zkg16.h) is converted at the boundaries: fqu_from_sat (one product by 2^(22+406) mod q) when the
 // proving key is loaded, fqu_to_sat (one product by 2^384 mod q, canonical reduction, repack) on the five
@@ -95,6 +116,13 @@ struct FqUP {
         constexpr uint32_t M[14] = {0x3fd55580u, 0x3bfffffeu, 0x3ffff73eu, 0x3ffeb152u, 0x3120f55eu, 0x283dac3cu, 0x3ece61a4u, 0x2f38512au, 0x323ba5c1u, 0x2d2eb35cu, 0x2374f6c7u, 0x3fe69a4au, 0x288f51cau, 0x0000067fu};
         return M[i];
     }
+    // 32 q with limbs 0..12 pre-borrowed into [3 2^29, 2^31): limb-wise "32 q - b - 2 c" never underflows for normalised b, c
+    // (b_i + 2 c_i <= 3 (2^29 - 1)) with b + 2 c <= 31 q, and a normalised value added on top stays below 2^32 per limb
+    ZK_HD static constexpr uint32_t w32(int i) {
+        constexpr uint32_t M[14] = {0x7ff55560u, 0x7efffffcu, 0x7ffffdccu, 0x7fffac51u, 0x6c483d54u, 0x6a0f6b0cu, 0x7fb39866u,
+                                    0x73ce1447u, 0x6c8ee96du, 0x634bacd4u, 0x78dd3dafu, 0x7ff9a68fu, 0x6223d46fu, 0x0000019du};
+        return M[i];
+    }
 };
 
 ZK_HD FqU FqU::one() {
@@ -134,11 +162,56 @@ inline void fqu_check(const FqU &v, uint32_t k, bool strict, const char *what, i
     fprintf(stderr, "\n");
     abort();
 }
+// a LAZY operand (see "Skipped carry passes" above): limbs 0..12 below 2^bits (bits = 29, 30 or 31), and the VALUE - taken after a
+// carry pass on a copy - at most / below k q
+inline void fqu_check_limbs(const FqU &v, int bits, uint32_t k, bool strict, const char *what, int line) {
+    bool ok = true;
+    for (int i = 0; i < 13; i++) ok = ok && ((uint64_t)v.l[i] >> bits) == 0;
+    if (ok) {
+        FqU n = v;
+        uint32_t c = 0;
+        for (int i = 0; i < 13; i++) {
+            const uint32_t t = n.l[i] + c;
+            n.l[i] = t & FqU::MASK;
+            c = t >> 29;
+        }
+        n.l[13] += c;
+        ok = strict ? fqu_check_cmp(n, k) < 0 : fqu_check_cmp(n, k) <= 0;
+    }
+    if (ok) return;
+    fprintf(stderr, "%s:%d: %s: a limb of the operand is not below 2^%d, or the operand not %s %u q:", __FILE__, line, what, bits, strict ? "below" : "at most", k);
+    for (int i = 13; i >= 0; i--) fprintf(stderr, " %08x", v.l[i]);
+    fprintf(stderr, "\n");
+    abort();
+}
+// a product column, accumulated a second time in 128 bits: the 64-bit accumulator of the kernels must never have wrapped
+struct FqUColumn {
+    unsigned __int128 w = 0;
+    void mac(uint32_t x, uint32_t y) { w += (uint64_t)x * y; }
+    void end(uint64_t acc, const char *what, int k, int line) {
+        if ((uint64_t)(w >> 64) != 0 || (uint64_t)w != acc) {
+            fprintf(stderr, "%s:%d: %s: column %d overflows its 64-bit accumulator (%016llx %016llx)\n", __FILE__, line, what, k,
+                    (unsigned long long)(uint64_t)(w >> 64), (unsigned long long)(uint64_t)w);
+            abort();
+        }
+        w >>= 29;
+    }
+};
 #define ZK_FQU_LE(v, k, what) fqu_check(v, (uint32_t)(k), false, what, __LINE__)
 #define ZK_FQU_LT(v, k, what) fqu_check(v, (uint32_t)(k), true, what, __LINE__)
+#define ZK_FQU_LIMBS_LE(v, bits, k, what) fqu_check_limbs(v, bits, (uint32_t)(k), false, what, __LINE__)
+#define ZK_FQU_LIMBS_LT(v, bits, k, what) fqu_check_limbs(v, bits, (uint32_t)(k), true, what, __LINE__)
+#define ZK_FQU_COL_DECL(col) FqUColumn col
+#define ZK_FQU_COL_MAC(col, x, y) col.mac(x, y)
+#define ZK_FQU_COL_END(col, acc, what, k) col.end(acc, what, k, __LINE__)
 #else
 #define ZK_FQU_LE(v, k, what) do { } while (0)
 #define ZK_FQU_LT(v, k, what) do { } while (0)
+#define ZK_FQU_LIMBS_LE(v, bits, k, what) do { } while (0)
+#define ZK_FQU_LIMBS_LT(v, bits, k, what) do { } while (0)
+#define ZK_FQU_COL_DECL(col) do { } while (0)
+#define ZK_FQU_COL_MAC(col, x, y) do { } while (0)
+#define ZK_FQU_COL_END(col, acc, what, k) do { } while (0)
 #endif
 
 // carry propagation: limbs back below 2^29 (the top limb keeps whatever is left; values stay < 2^406)
@@ -182,12 +255,58 @@ ZK_HD FqU fqu_neg(const FqU &a) {   // 8q - a  (a <= 7q); keeps exact zero as ex
     return fqu_sub<8>(FqU::zero(), a);
 }
 
+// ---- the same sums and differences with the carry pass left to the consumer ("Skipped carry passes" above)
+// M q - b as bare limb differences: limbs < 2^30; b normalised, b <= (L-1) q.  Limb 13 cannot go negative: the value is >= q
+// = 13.002 2^377 and limbs 0..12 hold less than 2^30 2^(29 12) (1 + 2^-28) < 2.01 2^377 of it.
+template <int L>
+ZK_HD FqU fqu_rsub_raw(const FqU &b) {
+    ZK_FQU_LE(b, L - 1, "fqu_rsub_raw");
+    FqU r;
+#pragma unroll
+    for (int i = 0; i < 14; i++) r.l[i] = (L == 8 ? FqUP::m8(i) : (L == 32 ? FqUP::m32(i) : (L == 64 ? FqUP::m64(i) : FqUP::m128(i)))) - b.l[i];
+    return r;
+}
+// a + b as bare limb sums: limbs < 2^30; both normalised
+ZK_HD FqU fqu_add_raw(const FqU &a, const FqU &b) {
+    ZK_FQU_LT(a, 2048, "fqu_add_raw a");
+    ZK_FQU_LT(b, 2048, "fqu_add_raw b");
+    FqU r;
+#pragma unroll
+    for (int i = 0; i < 14; i++) r.l[i] = a.l[i] + b.l[i];
+    return r;
+}
+// (neg ? 8 q - s : s) + n with ONE carry pass: the R of a mixed addition, n = the bare 64 q - Y1 (limbs < 2^30), s = S2 < 2q
+// normalised (level 8 holds: s <= 7 q).  Limbs before the pass < 2^30 + 2^30 = 2^31; value < 8 q + 64 q.
+ZK_HD FqU fqu_addsub_sel(const FqU &s, const FqU &n, bool neg) {
+    ZK_FQU_LE(s, 7, "fqu_addsub_sel s");
+    ZK_FQU_LIMBS_LE(n, 30, 64, "fqu_addsub_sel n");
+    FqU r;
+#pragma unroll
+    for (int i = 0; i < 14; i++) r.l[i] = (neg ? FqUP::m8(i) - s.l[i] : s.l[i]) + n.l[i];
+    fqu_normalise(r);
+    return r;
+}
+// rr + (32 q - b - 2 c) with ONE carry pass: the X3 = R^2 - PPP - 2 Q of a mixed addition (fqu_dbl, fqu_add and fqu_sub<32> take
+// three).  All normalised, b + 2 c <= 31 q; limbs before the pass < 2^29 + 2^31; the same VALUE as f_sub(rr, f_add(b, f_dbl(c))).
+ZK_HD FqU fqu_sub_b_2c(const FqU &rr, const FqU &b, const FqU &c) {
+    ZK_FQU_LT(rr, 4064, "fqu_sub_b_2c rr");
+    ZK_FQU_LE(b, 15, "fqu_sub_b_2c b");
+    ZK_FQU_LE(c, 8, "fqu_sub_b_2c c");
+    FqU r;
+#pragma unroll
+    for (int i = 0; i < 14; i++) r.l[i] = rr.l[i] + (FqUP::w32(i) - b.l[i] - 2u * c.l[i]);
+    fqu_normalise(r);
+    return r;
+}
+
 // Montgomery product a*b*2^-406 mod q, product-scanning: one 64-bit accumulator per column, carries once per column.
-// Inputs: normalised, values < 2^12 q.  Output: normalised, value < 2q.
-template <bool SQR>
+// Inputs: values < 2^12 q, limbs 0..12 of a below 2^LA and of b below 2^LB (29 = normalised; LA + LB <= 59, "Skipped carry passes"
+// above; a squaring takes a normalised operand only: it doubles limbs in 32 bits).  Output: normalised, value < 2q.
+template <bool SQR, int LA = 29, int LB = 29>
 ZK_HD FqU fqu_mul_impl(const FqU &a, const FqU &b) {
-    ZK_FQU_LT(a, 4096, "fqu_mul_impl a");
-    ZK_FQU_LT(b, 4096, "fqu_mul_impl b");
+    static_assert(LA >= 29 && LB >= 29 && LA + LB <= 59 && (!SQR || LA + LB == 58), "14 2^(LA+LB) + 14 2^58 + 2^35 < 2^64");
+    ZK_FQU_LIMBS_LT(a, LA, 4096, "fqu_mul_impl a");
+    ZK_FQU_LIMBS_LT(b, LB, 4096, "fqu_mul_impl b");
     constexpr int N = 14;
     uint32_t m[N];
     uint32_t a2[N];
@@ -197,6 +316,7 @@ ZK_HD FqU fqu_mul_impl(const FqU &a, const FqU &b) {
     }
     FqU r;
     uint64_t acc = 0;
+    ZK_FQU_COL_DECL(col);
 #pragma unroll
     for (int k = 0; k < 2 * N - 1; k++) {
         const int lo = k < N ? 0 : k - N + 1;
@@ -205,22 +325,25 @@ ZK_HD FqU fqu_mul_impl(const FqU &a, const FqU &b) {
 #pragma unroll
             for (int i = lo; i <= hi; i++) {
                 const int j = k - i;
-                if (i < j) acc += (uint64_t)a2[i] * a.l[j];
-                else if (i == j) acc += (uint64_t)a.l[i] * a.l[i];
+                if (i < j) { acc += (uint64_t)a2[i] * a.l[j]; ZK_FQU_COL_MAC(col, a2[i], a.l[j]); }
+                else if (i == j) { acc += (uint64_t)a.l[i] * a.l[i]; ZK_FQU_COL_MAC(col, a.l[i], a.l[i]); }
             }
         } else {
 #pragma unroll
-            for (int i = lo; i <= hi; i++) acc += (uint64_t)a.l[i] * b.l[k - i];
+            for (int i = lo; i <= hi; i++) { acc += (uint64_t)a.l[i] * b.l[k - i]; ZK_FQU_COL_MAC(col, a.l[i], b.l[k - i]); }
         }
         if (k < N) {
 #pragma unroll
-            for (int i = 0; i < k; i++) acc += (uint64_t)m[i] * FqUP::mod(k - i);
+            for (int i = 0; i < k; i++) { acc += (uint64_t)m[i] * FqUP::mod(k - i); ZK_FQU_COL_MAC(col, m[i], FqUP::mod(k - i)); }
             m[k] = ((uint32_t)acc * FqUP::INV) & FqU::MASK;
             acc += (uint64_t)m[k] * FqUP::mod(0);
+            ZK_FQU_COL_MAC(col, m[k], FqUP::mod(0));
+            ZK_FQU_COL_END(col, acc, "fqu_mul_impl", k);
             acc >>= 29;
         } else {
 #pragma unroll
-            for (int i = lo; i <= hi; i++) acc += (uint64_t)m[i] * FqUP::mod(k - i);
+            for (int i = lo; i <= hi; i++) { acc += (uint64_t)m[i] * FqUP::mod(k - i); ZK_FQU_COL_MAC(col, m[i], FqUP::mod(k - i)); }
+            ZK_FQU_COL_END(col, acc, "fqu_mul_impl", k);
             r.l[k - N] = (uint32_t)acc & FqU::MASK;
             acc >>= 29;
         }
@@ -233,32 +356,40 @@ ZK_HD FqU fqu_mul_impl(const FqU &a, const FqU &b) {
 // products, each < 2^58: < 2^63.4, still one 64-bit accumulator.  Inputs normalised, < 2^12 q; output normalised, < 2q
 // ((2 * 2^24 q^2 + 2^406 q) / 2^406 < 2q).  Always inlined (four operands = 56 registers do not fit the 32 argument VGPRs of
 // a device-function call): used once per mixed addition, for Y3 = R (Q - X3) + (-Y1) PPP.
-ZK_HD FqU fqu_mul2(const FqU &a, const FqU &b, const FqU &c, const FqU &d) {
+// fqu_mul2_lc<LC>: the same with limbs 0..12 of c below 2^LC; LC = 30 is a bare "M q - b" that skipped its carry pass.  The other
+// three operands are normalised: 2^58 + 2^(LC+29) < 3.57 2^58 holds up to LC = 30 ("Skipped carry passes" above).
+template <int LC>
+ZK_HD FqU fqu_mul2_lc(const FqU &a, const FqU &b, const FqU &c, const FqU &d) {
+    static_assert(LC == 29 || LC == 30, "14 (2^58 + 2^(LC+29)) + 14 2^58 + 2^35 < 2^64");
     ZK_FQU_LT(a, 4096, "fqu_mul2 a");
     ZK_FQU_LT(b, 4096, "fqu_mul2 b");
-    ZK_FQU_LT(c, 4096, "fqu_mul2 c");
+    ZK_FQU_LIMBS_LT(c, LC, 4096, "fqu_mul2 c");
     ZK_FQU_LT(d, 4096, "fqu_mul2 d");
     constexpr int N = 14;
     uint32_t m[N];
     FqU r;
     uint64_t acc = 0;
+    ZK_FQU_COL_DECL(col);
 #pragma unroll
     for (int k = 0; k < 2 * N - 1; k++) {
         const int lo = k < N ? 0 : k - N + 1;
         const int hi = k < N ? k : N - 1;
 #pragma unroll
-        for (int i = lo; i <= hi; i++) acc += (uint64_t)a.l[i] * b.l[k - i];
+        for (int i = lo; i <= hi; i++) { acc += (uint64_t)a.l[i] * b.l[k - i]; ZK_FQU_COL_MAC(col, a.l[i], b.l[k - i]); }
 #pragma unroll
-        for (int i = lo; i <= hi; i++) acc += (uint64_t)c.l[i] * d.l[k - i];
+        for (int i = lo; i <= hi; i++) { acc += (uint64_t)c.l[i] * d.l[k - i]; ZK_FQU_COL_MAC(col, c.l[i], d.l[k - i]); }
         if (k < N) {
 #pragma unroll
-            for (int i = 0; i < k; i++) acc += (uint64_t)m[i] * FqUP::mod(k - i);
+            for (int i = 0; i < k; i++) { acc += (uint64_t)m[i] * FqUP::mod(k - i); ZK_FQU_COL_MAC(col, m[i], FqUP::mod(k - i)); }
             m[k] = ((uint32_t)acc * FqUP::INV) & FqU::MASK;
             acc += (uint64_t)m[k] * FqUP::mod(0);
+            ZK_FQU_COL_MAC(col, m[k], FqUP::mod(0));
+            ZK_FQU_COL_END(col, acc, "fqu_mul2", k);
             acc >>= 29;
         } else {
 #pragma unroll
-            for (int i = lo; i <= hi; i++) acc += (uint64_t)m[i] * FqUP::mod(k - i);
+            for (int i = lo; i <= hi; i++) { acc += (uint64_t)m[i] * FqUP::mod(k - i); ZK_FQU_COL_MAC(col, m[i], FqUP::mod(k - i)); }
+            ZK_FQU_COL_END(col, acc, "fqu_mul2", k);
             r.l[k - N] = (uint32_t)acc & FqU::MASK;
             acc >>= 29;
         }
@@ -266,6 +397,7 @@ ZK_HD FqU fqu_mul2(const FqU &a, const FqU &b, const FqU &c, const FqU &d) {
     r.l[N - 1] = (uint32_t)acc;
     return r;
 }
+ZK_HD FqU fqu_mul2(const FqU &a, const FqU &b, const FqU &c, const FqU &d) { return fqu_mul2_lc<29>(a, b, c, d); }
 
 #if defined(__HIP_DEVICE_COMPILE__)
 // one copy of each body per code object (see the note on fq_mul_call in ff.cuh); 28 VGPR arguments
@@ -492,6 +624,44 @@ __device__ __forceinline__ Fq2U fq2u_mul_lazy(const Fq2U &a, const Fq2U &b) {
     return r;
 }
 #endif
+
+// ---- the G2 bucket accumulation's products with their operand carry passes skipped (ec.cuh: xyzz_madd_lazy_lc; "Skipped carry
+// passes" above).  Host passes compute the same integers without the LDS parking, so a ZK_FQU_CHECK build checks every operand.
+// fq2u_mul_lazy with 128 q - a1 parked as bare limb differences (limbs < 2^30): it meets the normalised b1 beside the normalised
+// pair a0 b0 (2^58 + 2^59 < 3.57 2^58).  a, b: components normalised, <= 127 q; result components normalised, < 2q.
+// On the device the 30-bit operand goes through the shared two-product body (fqu_mul2_lds -> fqu_mul2_lds_call -> fqu_mul2 =
+// fqu_mul2_lc<29>): the same instructions as fqu_mul2_lc<30>, because LC only selects the static_assert and the host checks, and
+// device code carries no operand checks.  The host branch below names the bound it relies on.
+ZK_HD Fq2U fq2u_mul_lc(const Fq2U &a, const Fq2U &b) {
+    const FqU na1 = fqu_rsub_raw<128>(a.c1);
+    Fq2U r;
+#if defined(__HIP_DEVICE_COMPILE__)
+    g2_park(0, na1);
+    g2_park(1, b.c1);
+    g2_park(2, a.c1);
+    g2_park(3, b.c0);
+    r.c0 = fqu_mul2_lds(a.c0, b.c0, 0);          // a0 b0 + (128 q - a1) b1
+    r.c1 = fqu_mul2_lds(a.c0, b.c1, 1);          // a0 b1 + a1 b0
+#else
+    r.c0 = fqu_mul2_lc<30>(a.c0, b.c0, na1, b.c1);
+    r.c1 = fqu_mul2_lc<29>(a.c0, b.c1, a.c1, b.c0);
+#endif
+    return r;
+}
+// f_sqr(Fq2U) with the sum c0 + c1 as bare limb sums (limbs < 2^30) against the normalised difference (30 + 29 <= 59.84).
+// Components normalised, <= 127 q; result (< 2q, < 4q).  The accumulation's own variant: f_sqr below serves the pairing as well.
+ZK_HD Fq2U fq2u_sqr_lc(const Fq2U &a) {
+    ZK_FQU_LE(a.c0, 127, "fq2u_sqr_lc c0");
+    ZK_FQU_LE(a.c1, 127, "fq2u_sqr_lc c1");
+    const FqU p = fqu_mul(a.c0, a.c1);
+    const FqU s = fqu_add_raw(a.c0, a.c1), d = fqu_sub<128>(a.c0, a.c1);
+#if defined(__HIP_DEVICE_COMPILE__)
+    const FqU r0 = fqu_mul(s, d);                // the shared product body (fqu_mul_call): device code carries no operand checks
+#else
+    const FqU r0 = fqu_mul_impl<false, 30, 29>(s, d);
+#endif
+    return Fq2U{r0, fqu_dbl(p)};
+}
 
 ZK_HD Fq2U f_sqr(const Fq2U &a) {
     // (c0+c1)(c0-c1) + 2 c0 c1 u ; squared values are differences of stored coordinates (components < 74q, or 84q for

@@ -190,7 +190,9 @@ struct AccArgs {
 // G1: 2 waves per SIMD (<= 256 registers) hide the base-gather latency; G2's live state needs the whole file.
 // LAZY (G2 only): the mixed addition's Fq2 products with one reduction per component (ec.cuh: xyzz_madd_lazy)
 // CALLS (G1 only, PIPE = false): the round-1 loop whose field products are device-function calls (option "g1_inline" = 2)
-template <class F, bool PIPE, bool LAZY = false, bool CALLS = false>
+// LC (the default; option "acc_lazy"; G1's inlined loop and G2's LAZY loop only): the mixed addition without the carry passes its
+// results do not need (ec.cuh: xyzz_madd_inline_lc / xyzz_madd_lazy_lc)
+template <class F, bool PIPE, bool LAZY = false, bool CALLS = false, bool LC = false>
 __global__ void __launch_bounds__(64, FieldTraits<F>::g2 ? 1 : 2) msm_accumulate_kernel(AccArgs<F> a) {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t total = *a.total_ptr;
@@ -311,7 +313,8 @@ __global__ void __launch_bounds__(64, FieldTraits<F>::g2 ? 1 : 2) msm_accumulate
             en1 = a.entries[p + 2 < end ? p + 2 : end - 1];
             bq = ldv(a.bases + ((a.debug & 2u) ? 0u : (a.debug & 4u) ? ((en.x >> 1) & 0xffffu) : (en.x >> 1)));
             __builtin_amdgcn_sched_barrier(0);       // the loads above stay above the addition
-            xyzz_madd_inline(acc, b, (e & 1u) != 0);
+            if constexpr (LC) xyzz_madd_inline_lc(acc, b, (e & 1u) != 0);
+            else xyzz_madd_inline(acc, b, (e & 1u) != 0);
         }
     } else {
         // round-1 form: the base is gathered right before its addition (kept selectable: option "acc_pipeline"; for G1 "g1_inline")
@@ -330,7 +333,8 @@ __global__ void __launch_bounds__(64, FieldTraits<F>::g2 ? 1 : 2) msm_accumulate
                 cur = gb;
             }
             const Affine<F> b = ldv(a.bases + (e >> 1));
-            if constexpr (LAZY && FieldTraits<F>::g2) xyzz_madd_lazy(acc, b, (e & 1u) != 0);
+            if constexpr (LAZY && LC && FieldTraits<F>::g2) xyzz_madd_lazy_lc(acc, b, (e & 1u) != 0);
+            else if constexpr (LAZY && FieldTraits<F>::g2) xyzz_madd_lazy(acc, b, (e & 1u) != 0);
             else xyzz_madd(acc, b, (e & 1u) != 0);
             e = e_n;
             gb = g_n;
@@ -1078,10 +1082,18 @@ static void msm_enqueue_acc(zkg16_ctx *ctx, MsmWorkspace &ws, const MsmPlan &pla
     {
         ScopedKernelTimer kt(ctx, FieldTraits<F>::g2 ? "msm_accumulate_g2" : "msm_accumulate_g1", (double)plan.n, ctx->stream);
         const bool pipe = (ctx->opt_acc_pipeline >> (FieldTraits<F>::g2 ? 1 : 0)) & 1;
-        if (pipe) hipLaunchKernelGGL((msm_accumulate_kernel<F, true>), dim3(grid), dim3(64), 0, ctx->stream, a);
-        else if (FieldTraits<F>::g2 && ctx->opt_g2_lazy) hipLaunchKernelGGL((msm_accumulate_kernel<F, false, true>), dim3(grid), dim3(64), 0, ctx->stream, a);
-        else if (!FieldTraits<F>::g2 && !ctx->opt_g1_inline) hipLaunchKernelGGL((msm_accumulate_kernel<F, false, false, true>), dim3(grid), dim3(64), 0, ctx->stream, a);
-        else hipLaunchKernelGGL((msm_accumulate_kernel<F, false>), dim3(grid), dim3(64), 0, ctx->stream, a);
+        const bool lc = ctx->opt_acc_lazy != 0;      // only the default loops have the form without the spare carry passes
+        if (pipe) {
+            hipLaunchKernelGGL((msm_accumulate_kernel<F, true>), dim3(grid), dim3(64), 0, ctx->stream, a);
+        } else if constexpr (FieldTraits<F>::g2) {
+            if (ctx->opt_g2_lazy && lc) hipLaunchKernelGGL((msm_accumulate_kernel<F, false, true, false, true>), dim3(grid), dim3(64), 0, ctx->stream, a);
+            else if (ctx->opt_g2_lazy) hipLaunchKernelGGL((msm_accumulate_kernel<F, false, true>), dim3(grid), dim3(64), 0, ctx->stream, a);
+            else hipLaunchKernelGGL((msm_accumulate_kernel<F, false>), dim3(grid), dim3(64), 0, ctx->stream, a);
+        } else {
+            if (!ctx->opt_g1_inline) hipLaunchKernelGGL((msm_accumulate_kernel<F, false, false, true>), dim3(grid), dim3(64), 0, ctx->stream, a);
+            else if (lc) hipLaunchKernelGGL((msm_accumulate_kernel<F, false, false, false, true>), dim3(grid), dim3(64), 0, ctx->stream, a);
+            else hipLaunchKernelGGL((msm_accumulate_kernel<F, false>), dim3(grid), dim3(64), 0, ctx->stream, a);
+        }
     }
     static_assert(sizeof(AccArgs<F>) <= sizeof(slot.acc_args), "MsmSlot::acc_args too small");
     memcpy(slot.acc_args, &a, sizeof a);
@@ -1303,11 +1315,13 @@ int msm_acc_resident_waves(zkg16_ctx *ctx, bool g2) {
     hipError_t e;
     if (g2) {
         if (pipe) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, msm_accumulate_kernel<Fq2U, true>, 64, 0);
+        else if (ctx->opt_g2_lazy && ctx->opt_acc_lazy) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, msm_accumulate_kernel<Fq2U, false, true, false, true>, 64, 0);
         else if (ctx->opt_g2_lazy) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, msm_accumulate_kernel<Fq2U, false, true>, 64, 0);
         else e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, msm_accumulate_kernel<Fq2U, false>, 64, 0);
     } else {
         if (pipe) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, msm_accumulate_kernel<FqU, true>, 64, 0);
         else if (!ctx->opt_g1_inline) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, msm_accumulate_kernel<FqU, false, false, true>, 64, 0);
+        else if (ctx->opt_acc_lazy) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, msm_accumulate_kernel<FqU, false, false, false, true>, 64, 0);
         else e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, msm_accumulate_kernel<FqU, false>, 64, 0);
     }
     ZK_HIP(e);
