@@ -457,6 +457,17 @@ ZKG16_API int zkg16_r1cs_prime(zkg16_ctx *ctx, uint64_t x, uint64_t j, uint64_t 
 ZKG16_API int zkg16_witness_prime(zkg16_ctx *ctx, uint64_t x, uint64_t j, uint64_t *witness_handle);
 /* native Poseidon sponge hash of n Fr elements (Montgomery) — the public inputs hash_a/b/c of the matrix handler */
 ZKG16_API int zkg16_poseidon_hash(const uint64_t *elems, size_t n, uint64_t out[4]);
+/* k hashes in one call.  elems: k vectors of n Fr each (Montgomery), back to back; out[4 i ..] is byte for byte
+ * zkg16_poseidon_hash(elems + 4 n i, n).  _host (no ctx, no GPU): on the pool of zkg16_matrix_sponge_states_batch (threads: 0 = 8, capped at
+ * 16 and at k).  The ctx form takes a lane; with at least option "sponge_chains_min" chains (k) a kernel walks them, one GPU lane per
+ * chain, else it answers with the host form on "matrix_batch_threads" threads.  zkg16_matrix_hash_batch[_host]: the reference's
+ * hash_matrix endpoint for k matrices m of n^2 u64 each: hashes[4 i ..] = hash_a of zkg16_matrix_sponge_states(n, m_i, .) — the value
+ * a verifier needs as a public input.  k == 0, n == 0, null pointers, threads < 0 and, for the matrix forms, n outside 2..1024:
+ * ZKG16_ERR_BAD_ARG before any work; on any error the output is untouched. */
+ZKG16_API int zkg16_poseidon_hash_batch_host(const uint64_t *elems, size_t n, size_t k, int threads, uint64_t *out);
+ZKG16_API int zkg16_poseidon_hash_batch(zkg16_ctx *ctx, const uint64_t *elems, size_t n, size_t k, uint64_t *out);
+ZKG16_API int zkg16_matrix_hash_batch_host(size_t n, const uint64_t *m, size_t k, int threads, uint64_t *hashes);
+ZKG16_API int zkg16_matrix_hash_batch(zkg16_ctx *ctx, size_t n, const uint64_t *m, size_t k, uint64_t *hashes);
 
 /* ---- stage entry points (tests / bench; host buffers) ----------------------------------------- */
 /* ark-poly Radix2EvaluationDomain<Fr>: in-place, natural order; inverse => ifft (incl. 1/N);
@@ -541,6 +552,16 @@ ZKG16_API void zkg16_kernel_stats_reset(zkg16_ctx *ctx);
  *   "batch_max"      zkg16_prove_batch / zkg16_prove_matrix_batch: proofs per device pass (0 = as many as fit, else 1..65535)
  *   "matrix_batch_threads" zkg16_witness_matrix_batch / zkg16_prove_matrix_batch: host threads of the sponge chains (0 = 8, else 1..16)
  *   "matrix_batch_grid" cap on either grid dimension of the batched witness kernels (0 = 65535, else 1..65535): beyond it they loop
+ *   "sponge_chains_min" zkg16_witness_matrix_batch / zkg16_prove_matrix_batch (3K chains per call or sub-batch) and zkg16_poseidon_hash_batch /
+ *                    zkg16_matrix_hash_batch (k chains): calls with at least this many Poseidon sponge chains walk them on the device, one
+ *                    GPU lane per chain (the S-box values written as it goes, the hashes read back once; timings_ms[0] = 0); fewer run on
+ *                    the host pool.  1 = always the device, any value above 2^32 = never, 0 = the default, which is NEVER:
+ *                    measured (profiles/sponge_chains_timing.txt; t_perm = 0.714 ms per permutation of a lone wave) the device
+ *                    beat 8 host threads in zkg16_witness_matrix_batch from 3072 chains (K = 1024: 3.7x at n = 8, 16 and 32) and in
+ *                    zkg16_matrix_hash_batch from 1024 chains (1.3x; 5.2x at 4096), but in zkg16_prove_matrix_batch, whose chain count is that
+ *                    of a sub-batch, only at n = 8 and by 6 %, and it lost at n = 32 by 1.4x.  The default must win on every entry at
+ *                    every measured size; none does.  Callers of the first two entries with that many chains set 3072
+ *   "sponge_chain_segment" permutations of a chain per launch of the chain kernel (0 = 256, else 1..65535): the state is carried between launches
  * Unknown names return ZKG16_ERR_UNSUPPORTED. */
 ZKG16_API int zkg16_set_option(zkg16_ctx *ctx, const char *name, int64_t value);
 

@@ -99,6 +99,10 @@ SIGNATURES = {
     "zkg16_circuit_public_inputs": (C.c_int, [vp, u64p, sz]),
     "zkg16_circuit_load": (C.c_int, [ctxp, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "zkg16_poseidon_hash": (C.c_int, [u64p, sz, u64p]),
+    "zkg16_poseidon_hash_batch_host": (C.c_int, [vp, sz, sz, C.c_int, vp]),
+    "zkg16_poseidon_hash_batch": (C.c_int, [ctxp, vp, sz, sz, vp]),
+    "zkg16_matrix_hash_batch_host": (C.c_int, [sz, vp, sz, C.c_int, vp]),
+    "zkg16_matrix_hash_batch": (C.c_int, [ctxp, sz, vp, sz, vp]),
     "zkg16_r1cs_matrix": (C.c_int, [ctxp, sz, C.POINTER(H)]),
     "zkg16_r1cs_read": (C.c_int, [ctxp, H, vp, vp, vp, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz * 3)]),
     "zkg16_matrix_r1cs_dims": (C.c_int, [sz, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz * 3)]),

@@ -270,6 +270,31 @@ def prime_circuit(x, i_max_or_j, search=True, check_satisfied=True):
     return c
 
 
+def matrix_hash_batch_host(m, threads=0):
+    """The matrix handler's hash of k matrices of one size on host threads (zkg16_matrix_hash_batch_host; no GPU): m [k, n, n] u64 ->
+    [k, 4] Montgomery Fr, row i = hash_a of matrix_sponge_states(m[i], .)."""
+    m = np.ascontiguousarray(m, dtype=np.uint64)
+    if m.ndim != 3 or m.shape[1] != m.shape[2]:
+        raise ValueError("matrix_hash_batch_host: m must be k x n x n")
+    out = np.zeros((m.shape[0], 4), dtype=np.uint64)
+    rc = _lib.load().zkg16_matrix_hash_batch_host(m.shape[1], m.ctypes.data, m.shape[0], threads, out.ctypes.data)
+    if rc:
+        raise Zkg16Error(rc, "zkg16_matrix_hash_batch_host")
+    return out
+
+
+def poseidon_hash_batch_host(elems, threads=0):
+    """k Poseidon hashes on host threads (zkg16_poseidon_hash_batch_host; no GPU): elems [k, n, 4] Montgomery Fr -> [k, 4]."""
+    elems = np.ascontiguousarray(elems, dtype=np.uint64)
+    if elems.ndim != 3 or elems.shape[2] != 4:
+        raise ValueError("poseidon_hash_batch_host: elems must be k x n x 4")
+    out = np.zeros((elems.shape[0], 4), dtype=np.uint64)
+    rc = _lib.load().zkg16_poseidon_hash_batch_host(elems.ctypes.data, elems.shape[1], elems.shape[0], threads, out.ctypes.data)
+    if rc:
+        raise Zkg16Error(rc, "zkg16_poseidon_hash_batch_host")
+    return out
+
+
 def poseidon_hash(elems_mont):
     e = np.ascontiguousarray(elems_mont, dtype=np.uint64).reshape(-1, 4)
     out = np.zeros(4, dtype=np.uint64)

@@ -85,7 +85,7 @@ void copy_options(zkg16_ctx *dst, const zkg16_ctx *src) {
     dst->opt_ntt_radix = src->opt_ntt_radix; dst->opt_ntt_xcd = src->opt_ntt_xcd; dst->opt_acc_debug = src->opt_acc_debug;
     dst->opt_sort_mode = src->opt_sort_mode; dst->opt_acc_pipeline = src->opt_acc_pipeline; dst->opt_fuse_pointwise = src->opt_fuse_pointwise;
     dst->opt_matrix_parts = src->opt_matrix_parts; dst->opt_g2_lazy = src->opt_g2_lazy; dst->opt_g1_inline = src->opt_g1_inline; dst->opt_acc_lazy = src->opt_acc_lazy; dst->opt_fixed_base_bits = src->opt_fixed_base_bits;
-    dst->opt_collect_threads = src->opt_collect_threads; dst->opt_batch_max = src->opt_batch_max; dst->opt_matrix_batch_threads = src->opt_matrix_batch_threads; dst->opt_matrix_batch_grid = src->opt_matrix_batch_grid; dst->opt_verify_batch_min = src->opt_verify_batch_min; dst->opt_verify_wire_min = src->opt_verify_wire_min; dst->opt_verify_each_after = src->opt_verify_each_after; dst->opt_wm_transforms = src->opt_wm_transforms;
+    dst->opt_collect_threads = src->opt_collect_threads; dst->opt_batch_max = src->opt_batch_max; dst->opt_matrix_batch_threads = src->opt_matrix_batch_threads; dst->opt_matrix_batch_grid = src->opt_matrix_batch_grid; dst->opt_sponge_chains_min = src->opt_sponge_chains_min; dst->opt_sponge_chain_segment = src->opt_sponge_chain_segment; dst->opt_verify_batch_min = src->opt_verify_batch_min; dst->opt_verify_wire_min = src->opt_verify_wire_min; dst->opt_verify_each_after = src->opt_verify_each_after; dst->opt_wm_transforms = src->opt_wm_transforms;
     dst->kernel_timing = src->kernel_timing; dst->kernel_timing_accumulate_only = src->kernel_timing_accumulate_only;
 }
 void create_streams(zkg16_ctx *ctx) {
@@ -1226,6 +1226,16 @@ int set_option_one(zkg16_ctx *ctx, const char *name, int64_t value) {
         ctx->opt_matrix_batch_grid = (int)value;
         return ZKG16_OK;
     }
+    if (!strcmp(name, "sponge_chains_min")) {  // calls with at least this many sponge chains (3K for assignments, k for hashes) walk them on the device (0 restores the default; 1 = always; above 2^32 = never)
+        if (value < 0) return ZKG16_ERR_BAD_ARG;
+        ctx->opt_sponge_chains_min = value == 0 ? ZKG16_SPONGE_CHAINS_MIN_DEFAULT : value;
+        return ZKG16_OK;
+    }
+    if (!strcmp(name, "sponge_chain_segment")) {      // wit_chain_batch_kernel: permutations of a chain per launch, 0 = 256 (tests set 1 and 4 to carry states between launches)
+        if (value < 0 || value > 65535) return ZKG16_ERR_BAD_ARG;
+        ctx->opt_sponge_chain_segment = (int)value;
+        return ZKG16_OK;
+    }
     if (!strcmp(name, "verify_batch_min")) {   // zkg16_verify_batch: batches shorter than this go to the host form (0 restores the default; 1 = always the device)
         if (value < 0 || value > (1 << 30)) return ZKG16_ERR_BAD_ARG;
         ctx->opt_verify_batch_min = value == 0 ? ZKG16_VERIFY_BATCH_MIN_DEFAULT : (int)value;
@@ -1935,7 +1945,8 @@ int zkg16_prove_matrix_batch(zkg16_ctx *ctx, uint64_t pk_handle, uint64_t r1cs_h
         const size_t nb = k - off < kb ? k - off : kb;
         const uint64_t *ao = a + off * nn, *bo = b + off * nn;
         MatrixBatchChains mc;
-        matrix_batch_chains(mc, n, ao, bo, nb, ctx->opt_matrix_batch_threads, pubs.data() + 12 * off);
+        if (sponge_chains_on_device(ctx, 3 * nb)) matrix_batch_chains_device(mc, n, nb, pubs.data() + 12 * off);
+        else matrix_batch_chains(mc, n, ao, bo, nb, ctx->opt_matrix_batch_threads, pubs.data() + 12 * off);
         chain_ms += mc.ms;
         std::vector<std::shared_ptr<WitnessDev>> wit_refs;
         float dev_ms = 0;
@@ -1959,6 +1970,26 @@ int zkg16_prove_matrix_batch(zkg16_ctx *ctx, uint64_t pk_handle, uint64_t r1cs_h
         timings_ms[2] = acc[9];
         timings_ms[3] = (float)(now_ms() - t_call);
     }
+    ZK_LANE_END(ctx)
+}
+
+// k Poseidon hashes in one call on a lane: at least "sponge_chains_min" chains are walked by wit_chain_batch_kernel, fewer by the
+// host form (on "matrix_batch_threads" threads).  elems: k vectors of n Montgomery Fr; out[i] = zkg16_poseidon_hash(elems_i, n).
+int zkg16_poseidon_hash_batch(zkg16_ctx *ctx, const uint64_t *elems, size_t n, size_t k, uint64_t *out) {
+    if (!ctx || !elems || !out || n == 0 || k == 0) return ZKG16_ERR_BAD_ARG;
+    if (k > SIZE_MAX / 32 / n || (n + 1) / 2 > 0xffffffffu) return ZKG16_ERR_BAD_ARG;
+    if (!sponge_chains_on_device(ctx, k)) return zkg16_poseidon_hash_batch_host(elems, n, k, ctx->opt_matrix_batch_threads, out);
+    ZK_LANE_BEGIN(ctx)
+    sponge_hash_batch_device(ctx, 0, elems, n, k, out);
+    ZK_LANE_END(ctx)
+}
+// hash_matrix for k matrices of n^2 u64: hashes[i] = hash_a of zkg16_matrix_sponge_states(n, m_i, .).  Routed as above.
+int zkg16_matrix_hash_batch(zkg16_ctx *ctx, size_t n, const uint64_t *m, size_t k, uint64_t *hashes) {
+    if (!ctx || !m || !hashes || k == 0 || n < 2 || n > 1024) return ZKG16_ERR_BAD_ARG;
+    if (k > SIZE_MAX / 32 / (n * n)) return ZKG16_ERR_BAD_ARG;
+    if (!sponge_chains_on_device(ctx, k)) return zkg16_matrix_hash_batch_host(n, m, k, ctx->opt_matrix_batch_threads, hashes);
+    ZK_LANE_BEGIN(ctx)
+    sponge_hash_batch_device(ctx, 1, m, n * n, k, hashes);
     ZK_LANE_END(ctx)
 }
 

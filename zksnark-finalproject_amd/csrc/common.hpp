@@ -257,6 +257,10 @@ struct MsmWorkspace {       // grown on demand, reused across proofs
 // K = 1024 = ceil(47.72 ms / 2.156 ms) = 23, rounded UP to a power of two — one bad proof needs up to 2 log2 K range tests
 // (19 to 22 measured at K = 16,384), and 16 would send that case to the pass (profiles/verify_each_timing_r10.txt)
 #define ZKG16_VERIFY_EACH_AFTER_DEFAULT 32
+// calls with at least this many sponge chains (3K for assignments, k for hashes) walk them on the device.  INT64_MAX = never: in
+// profiles/sponge_chains_timing.txt the device wins zkg16_witness_matrix_batch from 3072 chains and zkg16_matrix_hash_batch from 1024 at
+// every measured n, but zkg16_prove_matrix_batch (chain count = a sub-batch's) only at n = 8 — no count wins on every entry
+#define ZKG16_SPONGE_CHAINS_MIN_DEFAULT INT64_MAX
 
 struct zkg16_ctx {
     int device = 0;
@@ -335,6 +339,8 @@ struct zkg16_ctx {
     int opt_batch_max = 0;                            // zkg16_prove_batch / zkg16_prove_matrix_batch: proofs per device pass (0 = as many as fit)
     int opt_matrix_batch_threads = 0;                 // zkg16_witness_matrix_batch / zkg16_prove_matrix_batch: host threads of the sponge chains (0 = 8)
     int opt_matrix_batch_grid = 0;                    // cap on either grid dimension of the batched witness kernels (0 = 65535): beyond it they loop
+    int64_t opt_sponge_chains_min = ZKG16_SPONGE_CHAINS_MIN_DEFAULT;             // calls with at least this many sponge chains walk them on the device; above 2^32: never
+    int opt_sponge_chain_segment = 0;                 // permutations of a chain per launch of wit_chain_batch_kernel (0 = 256)
     int opt_verify_batch_min = ZKG16_VERIFY_BATCH_MIN_DEFAULT;                   // zkg16_verify_batch: shorter batches are answered by the host form (the measured crossover)
     int opt_verify_wire_min = ZKG16_VERIFY_WIRE_MIN_DEFAULT;                     // zkg16_verify_batch_wire: shorter batches are decoded and answered on the host (the measured crossover)
     int opt_verify_each_after = ZKG16_VERIFY_EACH_AFTER_DEFAULT;                 // zkg16_verify_batch[_wire] with ok_each: range tests before the per-proof pass takes over
@@ -496,11 +502,19 @@ void matrix_stream_free(MatrixWitnessStream *ms);
 struct MatrixBatchChains {
     size_t n = 0, k = 0, perms = 0;
     std::vector<uint64_t> states;           // k x 3 x perms x 12
-    const uint64_t *hashes = nullptr;       // k x 12
+    uint64_t *hashes = nullptr;             // k x 12
     double ms = 0;                          // wall
+    bool on_device = false;                 // the chains are walked by matrix_batch_assign (wit_chain_batch_kernel), which fills hashes
 };
 size_t matrix_witness_total(size_t n);
 void matrix_batch_chains(MatrixBatchChains &c, size_t n, const uint64_t *a, const uint64_t *b, size_t k, int threads, uint64_t *hashes);
+// The chains of a call on the device instead (option "sponge_chains_min" against the call's chain count): matrix_batch_chains_device
+// only describes the batch — nothing runs on the host, c.ms = 0 — and matrix_batch_assign walks the chains (sponge_chain_dev.cuh) and
+// writes the hashes when it has synchronised.  sponge_hash_batch_device: k hashes of k vectors of `count` Montgomery Fr (form 0) or
+// u64 (form 1) on ctx->stream; `out` is written only on success.
+bool sponge_chains_on_device(const zkg16_ctx *ctx, size_t chains);
+void matrix_batch_chains_device(MatrixBatchChains &c, size_t n, size_t k, uint64_t *hashes);
+void sponge_hash_batch_device(zkg16_ctx *ctx, int form, const uint64_t *data, size_t count, size_t k, uint64_t *out);
 void matrix_batch_assign(zkg16_ctx *ctx, const MatrixBatchChains &c, const uint64_t *a, const uint64_t *b,
                          std::vector<std::shared_ptr<WitnessDev>> &out, float *dev_ms);
 

@@ -176,6 +176,46 @@ void matrix_chains_batch(size_t n, const uint64_t *a, const uint64_t *b, size_t 
     if (oom.load()) throw std::bad_alloc();
 }
 
+// k independent chains of `count` elements each on the same pool (zkg16_poseidon_hash_batch_host, zkg16_matrix_hash_batch_host):
+// data = k x count Montgomery Fr, or with u64_elems k x count u64 taken to Montgomery form first.  out: k hashes.
+void hash_chains_batch(bool u64_elems, const uint64_t *data, size_t count, size_t k, int threads, Fr64 *out) {
+    size_t nth = threads <= 0 ? 8 : threads > 16 ? 16 : (size_t)threads;
+    if (nth > k) nth = k;
+    (void)pparams();
+    std::atomic<size_t> next{0};
+    std::atomic<bool> oom{false};
+    auto worker = [&]() {
+        try {
+            std::vector<Fr64> elems(count);
+            for (size_t t; (t = next.fetch_add(1)) < k;) {
+                if (u64_elems)
+                    for (size_t e = 0; e < count; e++) elems[e] = fr64_from_u64(data[t * count + e]);
+                else memcpy(elems.data(), data + 4 * t * count, count * sizeof(Fr64));
+                out[t] = sponge_chain(elems.data(), count, nullptr, nullptr);
+            }
+        } catch (const std::bad_alloc &) {
+            oom.store(true);
+        }
+    };
+    {
+        ThreadGroup tg;
+        for (size_t t = 1; t < nth; t++) tg.run(worker);
+        worker();
+    }
+    if (oom.load()) throw std::bad_alloc();
+}
+// the host forms behind their argument checks; hashes are staged so that a failure leaves `out` alone
+int hash_batch_host(bool u64_elems, const uint64_t *data, size_t count, size_t k, int threads, uint64_t *out) {
+    try {
+        std::vector<Fr64> hs(k);
+        hash_chains_batch(u64_elems, data, count, k, threads, hs.data());
+        memcpy(out, hs.data(), k * sizeof(Fr64));
+    } catch (const std::bad_alloc &) {
+        return ZKG16_ERR_OOM;
+    }
+    return ZKG16_OK;
+}
+
 #ifndef ZKG16_HOST_ONLY        // (tests/test_host_sanitize.py compiles the host chains alone, without kernels, under ASan)
 // ------------------------------------------------------------------------------------------------ device
 struct PoseidonDev { Fr mds[3][3], ark[P_ROUNDS][3]; };
@@ -271,10 +311,13 @@ __global__ void __launch_bounds__(64) wit_sponge_kernel(SpongeArgs g) {
 // SpMV and digit kernels read the assignments in.  Both grids stay within 65,535 per dimension and loop over what is beyond.
 struct FillBatchArgs {
     const uint64_t *ab;             // k x (a | b)
-    const Fr *inst;                 // k x (hash_a, hash_b, hash_c)
+    const Fr *inst;                 // k x (hash_a, hash_b, hash_c); null with INST = false
     Fr *const *z;                   // k
     size_t k, n, nn, off_a, off_mc, off_mm, total;    // total = 4 (instance) + 2 nn (a, b) + nn (zeros) + nn (n + 1)
 };
+// INST = false (the chains run on the device): slots 1..3 are left to wit_chain_batch_kernel and g.inst is not read.  An instantiation
+// of its own, so that the host route's kernel stays instruction for instruction what it was.
+template <bool INST>
 __global__ void __launch_bounds__(256) wit_matrix_fill_batch_kernel(FillBatchArgs g) {
     for (size_t req = blockIdx.y; req < g.k; req += gridDim.y) {
         const uint64_t *a = g.ab + req * 2 * g.nn, *b = a + g.nn;
@@ -283,6 +326,7 @@ __global__ void __launch_bounds__(256) wit_matrix_fill_batch_kernel(FillBatchArg
             Fr v = Fr::zero();
             Fr *dst;
             if (t < 4) {
+                if (!INST && t) continue;
                 dst = z + t;
                 v = t == 0 ? Fr::one() : ld32(g.inst + 3 * req + (t - 1));
             } else if (t < 4 + 2 * g.nn) {
@@ -346,6 +390,51 @@ __global__ void __launch_bounds__(64) wit_sponge_batch_kernel(SpongeBatchArgs g)
                 nst[i] = fp_add(acc, fp_mul(st[2], pp->mds[i][2]));
             }
             for (int i = 0; i < 3; i++) st[i] = nst[i];
+        }
+    }
+}
+
+// ---- the chains of a large batch walked on the device (option "sponge_chains_min"): one lane per chain, so each permutation is
+// computed once and its S-box values are written by the lane that needs its result anyway (sponge_chain_dev.cuh).  Chains are numbered
+// hash-major — all a chains, then b, then c — so that a wave holds one kind of loader except where k is no multiple of 64.  A chain is
+// walked in launches of at most "sponge_chain_segment" permutations, its state carried in `state` between them: no launch runs for
+// seconds (a 128x128 chain is 8,192 permutations), and other lanes' kernels get in between.
+#include "sponge_chain_dev.cuh"
+struct ChainBatchArgs {
+    const void *data;               // form 2: k x (a | b) u64; form 0: k x count Fr; form 1: k x count u64
+    Fr *state;                      // chains x 3, read when p_lo > 0, written when p_hi < perms
+    Fr *hashes;                     // form 2: k x 3 (request-major: the public inputs); else k.  Written by the chain's last launch
+    Fr *const *z;                   // form 2: k assignments
+    const PoseidonDev *params;
+    size_t off[3];                  // form 2: first witness of each hash's gadget within an assignment
+    size_t k, n, count, chains;     // count = elements per chain (form 2: n^2); chains = 3 k in form 2, else k
+    uint32_t p_lo, p_hi, perms;
+    int form;
+};
+template <bool ASSIGN>
+__global__ void __launch_bounds__(64) wit_chain_batch_kernel(ChainBatchArgs g) {
+    for (size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x; c < g.chains; c += (size_t)gridDim.x * blockDim.x) {
+        const size_t h = ASSIGN ? c / g.k : 0, req = ASSIGN ? c % g.k : c;
+        ChainLoadAny ld;
+        if (ASSIGN) {
+            const uint64_t *a = static_cast<const uint64_t *>(g.data) + req * 2 * g.count;
+            ld = ChainLoadAny{h == 2 ? 2 : 1, h == 0 ? a : a + g.count, a, a + g.count, g.n};
+        } else {
+            ld = ChainLoadAny{g.form, g.form == 0 ? static_cast<const void *>(static_cast<const Fr *>(g.data) + req * g.count)
+                                                  : static_cast<const void *>(static_cast<const uint64_t *>(g.data) + req * g.count),
+                              nullptr, nullptr, 0};
+        }
+        Fr st[3];
+        for (int i = 0; i < 3; i++) st[i] = g.p_lo ? ld32(g.state + 3 * c + i) : Fr::zero();
+        Fr *out = ASSIGN ? g.z[req] + g.off[h] : nullptr;
+        const Fr hash = sponge_chain_walk<ASSIGN>(*g.params, ld, g.count, g.p_lo, g.p_hi, st, out);
+        if (g.p_hi < g.perms) {
+            for (int i = 0; i < 3; i++) st32(g.state + 3 * c + i, st[i]);
+        } else if (ASSIGN) {
+            st32(g.hashes + 3 * req + h, hash);
+            st32(g.z[req] + 1 + h, hash);
+        } else {
+            st32(g.hashes + req, hash);
         }
     }
 }
@@ -527,18 +616,39 @@ void matrix_batch_chains(MatrixBatchChains &c, size_t n, const uint64_t *a, cons
     c.ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
-// The k assignments of `c`'s requests on ctx->stream, under ctx's mutex: three copies out of the ctx's pinned staging (a | b, the
-// entering states, the instances with the z pointers), the two batched launches, one synchronisation.  The assignments share one
-// allocation, which goes back when the last of them is gone (WitnessDev::backing).  When this throws the stream has been drained.
-void matrix_batch_assign(zkg16_ctx *ctx, const MatrixBatchChains &c, const uint64_t *a, const uint64_t *b,
-                         std::vector<std::shared_ptr<WitnessDev>> &out, float *dev_ms) {
-    const MatrixWitnessLayout L(c.n);
-    const size_t k = c.k, perms = c.perms;
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t ab_bytes = up(k * 2 * L.nn * sizeof(uint64_t)), st_bytes = up(k * 3 * perms * 3 * sizeof(Fr));
-    const size_t tab_bytes = up(k * (3 * sizeof(Fr) + sizeof(Fr *))), bytes = ab_bytes + st_bytes + tab_bytes;
+// Whether a call with this many chains walks them on the device (option "sponge_chains_min": 1 = always, above 2^32 = never).
+bool sponge_chains_on_device(const zkg16_ctx *ctx, size_t chains) {
+    const int64_t m = ctx->opt_sponge_chains_min;
+    return m <= ((int64_t)1 << 32) && chains >= (uint64_t)m;
+}
+// the device route's stand-in for matrix_batch_chains: nothing runs here, matrix_batch_assign walks the chains and fills `hashes`
+void matrix_batch_chains_device(MatrixBatchChains &c, size_t n, size_t k, uint64_t *hashes) {
+    c.n = n; c.k = k;
+    c.perms = (n * n + POSEIDON_RATE - 1) / POSEIDON_RATE;
+    c.states.clear();
+    c.hashes = hashes;
+    c.on_device = true;
+    c.ms = 0;
+}
+
+// launches of at most "sponge_chain_segment" permutations until every chain of `g` has ended
+static void chain_batch_launch(zkg16_ctx *ctx, ChainBatchArgs g, bool assign) {
     const size_t cap = ctx->opt_matrix_batch_grid > 0 ? (size_t)ctx->opt_matrix_batch_grid : 65535;
-    poseidon_dev_ensure(ctx);
+    const uint32_t seg = ctx->opt_sponge_chain_segment > 0 ? (uint32_t)ctx->opt_sponge_chain_segment : 256;
+    const size_t bx = (g.chains + 63) / 64;
+    const dim3 grid((unsigned)(bx < cap ? bx : cap));
+    for (uint32_t p = 0; p < g.perms;) {
+        g.p_lo = p;
+        g.p_hi = g.perms - p > seg ? p + seg : g.perms;
+        ScopedKernelTimer kt(ctx, "wit_chain_batch_kernel", (double)g.chains * (double)(g.p_hi - g.p_lo));
+        if (assign) hipLaunchKernelGGL(wit_chain_batch_kernel<true>, grid, dim3(64), 0, ctx->stream, g);
+        else hipLaunchKernelGGL(wit_chain_batch_kernel<false>, grid, dim3(64), 0, ctx->stream, g);
+        ZK_HIP(hipGetLastError());
+        p = g.p_hi;
+    }
+}
+
+static void mbatch_staging_ensure(zkg16_ctx *ctx, size_t bytes) {
     if (ctx->mbatch_host_bytes < bytes) {           // nothing reads the old block: every call ends with the stream drained
         if (ctx->mbatch_host) (void)hipHostFree(ctx->mbatch_host);
         ctx->mbatch_host = nullptr;
@@ -547,6 +657,52 @@ void matrix_batch_assign(zkg16_ctx *ctx, const MatrixBatchChains &c, const uint6
         ctx->mbatch_host_bytes = bytes;
     }
     ctx->mbatch_dev.ensure(bytes);
+}
+
+// k hashes on ctx->stream (a lane's, under its mutex): form 0 = k vectors of `count` Montgomery Fr, form 1 = k vectors of `count` u64.
+// One upload, the chain launches, one read-back through the ctx's pinned staging; `out` is written only when all of it succeeded.
+void sponge_hash_batch_device(zkg16_ctx *ctx, int form, const uint64_t *data, size_t count, size_t k, uint64_t *out) {
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t elem = form == 0 ? sizeof(Fr) : sizeof(uint64_t);
+    const size_t in_bytes = up(k * count * elem), st_bytes = up(k * 3 * sizeof(Fr)), out_bytes = up(k * sizeof(Fr));
+    poseidon_dev_ensure(ctx);
+    mbatch_staging_ensure(ctx, in_bytes + st_bytes + out_bytes);
+    uint8_t *hs = static_cast<uint8_t *>(ctx->mbatch_host), *ds = ctx->mbatch_dev.as<uint8_t>();
+    memcpy(hs, data, k * count * elem);
+    struct Drain { zkg16_ctx *c; bool ok = false; ~Drain() { if (!ok) (void)hipStreamSynchronize(c->stream); } } drain{ctx};
+    ZK_HIP(hipMemcpyAsync(ds, hs, k * count * elem, hipMemcpyHostToDevice, ctx->stream));
+    ChainBatchArgs g = {};
+    g.data = ds;
+    g.state = reinterpret_cast<Fr *>(ds + in_bytes);
+    g.hashes = reinterpret_cast<Fr *>(ds + in_bytes + st_bytes);
+    g.z = nullptr;
+    g.params = ctx->poseidon_dev.as<PoseidonDev>();
+    g.k = k; g.n = 0; g.count = count; g.chains = k;
+    g.perms = (uint32_t)((count + POSEIDON_RATE - 1) / POSEIDON_RATE);
+    g.form = form;
+    chain_batch_launch(ctx, g, false);
+    ZK_HIP(hipMemcpyAsync(hs + in_bytes + st_bytes, ds + in_bytes + st_bytes, k * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
+    ZK_HIP(hipStreamSynchronize(ctx->stream));
+    drain.ok = true;
+    memcpy(out, hs + in_bytes + st_bytes, k * sizeof(Fr));
+}
+
+// The k assignments of `c`'s requests on ctx->stream, under ctx's mutex: three copies out of the ctx's pinned staging (a | b, the
+// entering states, the instances with the z pointers), the two batched launches, one synchronisation.  With the chains on the device
+// (c.on_device): a | b and the z pointers go up, the fill pass leaves slots 1..3 to wit_chain_batch_kernel, which takes the place of
+// the per-permutation pass, and the k x 3 hashes come back once into c.hashes.  The assignments share one
+// allocation, which goes back when the last of them is gone (WitnessDev::backing).  When this throws the stream has been drained.
+void matrix_batch_assign(zkg16_ctx *ctx, const MatrixBatchChains &c, const uint64_t *a, const uint64_t *b,
+                         std::vector<std::shared_ptr<WitnessDev>> &out, float *dev_ms) {
+    const MatrixWitnessLayout L(c.n);
+    const size_t k = c.k, perms = c.perms;
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const bool dev = c.on_device;                   // st: the carried states of the 3k chains instead of every entering state
+    const size_t ab_bytes = up(k * 2 * L.nn * sizeof(uint64_t)), st_bytes = up(k * 3 * (dev ? 1 : perms) * 3 * sizeof(Fr));
+    const size_t tab_bytes = up(k * (3 * sizeof(Fr) + sizeof(Fr *))), bytes = ab_bytes + st_bytes + tab_bytes;
+    const size_t cap = ctx->opt_matrix_batch_grid > 0 ? (size_t)ctx->opt_matrix_batch_grid : 65535;
+    poseidon_dev_ensure(ctx);
+    mbatch_staging_ensure(ctx, bytes);
     auto backing = std::make_shared<DevBuf>(k * L.total * sizeof(Fr));
     std::vector<std::shared_ptr<WitnessDev>> wits(k);
     for (size_t i = 0; i < k; i++) {
@@ -562,8 +718,10 @@ void matrix_batch_assign(zkg16_ctx *ctx, const MatrixBatchChains &c, const uint6
         memcpy(h_ab + i * 2 * L.nn, a + i * L.nn, L.nn * sizeof(uint64_t));
         memcpy(h_ab + i * 2 * L.nn + L.nn, b + i * L.nn, L.nn * sizeof(uint64_t));
     }
-    memcpy(hs + ab_bytes, c.states.data(), k * 3 * perms * 3 * sizeof(Fr));
-    memcpy(hs + ab_bytes + st_bytes, c.hashes, k * 3 * sizeof(Fr));
+    if (!dev) {
+        memcpy(hs + ab_bytes, c.states.data(), k * 3 * perms * 3 * sizeof(Fr));
+        memcpy(hs + ab_bytes + st_bytes, c.hashes, k * 3 * sizeof(Fr));
+    }
     Fr **h_tab = reinterpret_cast<Fr **>(hs + ab_bytes + st_bytes + k * 3 * sizeof(Fr));
     for (size_t i = 0; i < k; i++) h_tab[i] = wits[i]->z.as<Fr>();
 
@@ -575,23 +733,42 @@ void matrix_batch_assign(zkg16_ctx *ctx, const MatrixBatchChains &c, const uint6
     struct Drain { zkg16_ctx *c; bool ok = false; ~Drain() { if (!ok) (void)hipStreamSynchronize(c->stream); } } drain{ctx};
     ZK_HIP(hipEventRecord(e0, ctx->stream));
     ZK_HIP(hipMemcpyAsync(ds, hs, k * 2 * L.nn * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
-    ZK_HIP(hipMemcpyAsync(ds + ab_bytes, hs + ab_bytes, k * 3 * perms * 3 * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
-    ZK_HIP(hipMemcpyAsync(ds + ab_bytes + st_bytes, hs + ab_bytes + st_bytes, k * (3 * sizeof(Fr) + sizeof(Fr *)), hipMemcpyHostToDevice, ctx->stream));
-    Fr *const *d_tab = reinterpret_cast<Fr *const *>(ds + ab_bytes + st_bytes + k * 3 * sizeof(Fr));
+    const size_t tab_off = ab_bytes + st_bytes + k * 3 * sizeof(Fr);
+    if (dev) {
+        ZK_HIP(hipMemcpyAsync(ds + tab_off, hs + tab_off, k * sizeof(Fr *), hipMemcpyHostToDevice, ctx->stream));
+    } else {
+        ZK_HIP(hipMemcpyAsync(ds + ab_bytes, hs + ab_bytes, k * 3 * perms * 3 * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
+        ZK_HIP(hipMemcpyAsync(ds + ab_bytes + st_bytes, hs + ab_bytes + st_bytes, k * (3 * sizeof(Fr) + sizeof(Fr *)), hipMemcpyHostToDevice, ctx->stream));
+    }
+    Fr *const *d_tab = reinterpret_cast<Fr *const *>(ds + tab_off);
     {
         FillBatchArgs g;
         g.ab = reinterpret_cast<const uint64_t *>(ds);
-        g.inst = reinterpret_cast<const Fr *>(ds + ab_bytes + st_bytes);
+        g.inst = dev ? nullptr : reinterpret_cast<const Fr *>(ds + ab_bytes + st_bytes);
         g.z = d_tab;
         g.k = k; g.n = L.n; g.nn = L.nn; g.off_a = L.off_a; g.off_mc = L.off_mc; g.off_mm = L.off_mm;
         g.total = 4 + 3 * L.nn + L.nn * (L.n + 1);
         const size_t bx = (g.total + 255) / 256;
         ScopedKernelTimer kt(ctx, "wit_matrix_fill_batch_kernel", (double)g.total * (double)k);
-        hipLaunchKernelGGL(wit_matrix_fill_batch_kernel, dim3((unsigned)(bx < cap ? bx : cap), (unsigned)(k < cap ? k : cap)), dim3(256), 0,
-                           ctx->stream, g);
+        const dim3 grid((unsigned)(bx < cap ? bx : cap), (unsigned)(k < cap ? k : cap));
+        if (dev) hipLaunchKernelGGL(wit_matrix_fill_batch_kernel<false>, grid, dim3(256), 0, ctx->stream, g);
+        else hipLaunchKernelGGL(wit_matrix_fill_batch_kernel<true>, grid, dim3(256), 0, ctx->stream, g);
         ZK_HIP(hipGetLastError());
     }
-    {
+    if (dev) {
+        ChainBatchArgs g = {};
+        g.data = ds;
+        g.state = reinterpret_cast<Fr *>(ds + ab_bytes);
+        g.hashes = reinterpret_cast<Fr *>(ds + ab_bytes + st_bytes);
+        g.z = d_tab;
+        g.params = ctx->poseidon_dev.as<PoseidonDev>();
+        g.off[0] = L.off_ha; g.off[1] = L.off_hb; g.off[2] = L.off_hc;
+        g.k = k; g.n = L.n; g.count = L.nn; g.chains = 3 * k;
+        g.perms = (uint32_t)perms;
+        g.form = 2;
+        chain_batch_launch(ctx, g, true);
+        ZK_HIP(hipMemcpyAsync(hs + ab_bytes + st_bytes, ds + ab_bytes + st_bytes, k * 3 * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
+    } else {
         SpongeBatchArgs g;
         g.states = reinterpret_cast<const Fr *>(ds + ab_bytes);
         g.z = d_tab;
@@ -610,6 +787,7 @@ void matrix_batch_assign(zkg16_ctx *ctx, const MatrixBatchChains &c, const uint6
     float ms = 0;
     ZK_HIP(hipEventElapsedTime(&ms, e0, e1));
     if (dev_ms) *dev_ms = ms;
+    if (dev) memcpy(c.hashes, hs + ab_bytes + st_bytes, k * 3 * sizeof(Fr));
     out = std::move(wits);
 }
 
@@ -652,6 +830,19 @@ int zkg16_matrix_sponge_states_batch(size_t n, const uint64_t *a, const uint64_t
     return ZKG16_OK;
 }
 
+// k vectors of n Montgomery Fr each on the pool (no ctx, no GPU): out[i] is byte for byte zkg16_poseidon_hash(elems + 4 n i, n).
+int zkg16_poseidon_hash_batch_host(const uint64_t *elems, size_t n, size_t k, int threads, uint64_t *out) {
+    if (!elems || !out || n == 0 || k == 0 || threads < 0) return ZKG16_ERR_BAD_ARG;
+    if (k > SIZE_MAX / 32 / n) return ZKG16_ERR_BAD_ARG;
+    return hash_batch_host(false, elems, n, k, threads, out);
+}
+// k matrices of n^2 u64 (no ctx, no GPU): hashes[i] = hash_a of zkg16_matrix_sponge_states(n, m_i, .), what hash_matrix answers.
+int zkg16_matrix_hash_batch_host(size_t n, const uint64_t *m, size_t k, int threads, uint64_t *hashes) {
+    if (!m || !hashes || k == 0 || n < 2 || n > 1024 || threads < 0) return ZKG16_ERR_BAD_ARG;
+    if (k > SIZE_MAX / 32 / (n * n)) return ZKG16_ERR_BAD_ARG;
+    return hash_batch_host(true, m, n * n, k, threads, hashes);
+}
+
 #ifndef ZKG16_HOST_ONLY
 // K MatrixCircuit assignments of one size in one upload, two launches and one synchronisation: handle i carries the bytes of
 // zkg16_witness_matrix(n, a_i, b_i).  The chains run before the ctx is locked (option "matrix_batch_threads"); all or nothing: on
@@ -667,7 +858,8 @@ int zkg16_witness_matrix_batch(zkg16_ctx *ctx, size_t n, const uint64_t *a, cons
     std::vector<uint64_t> hashes;
     try {
         hashes.resize(12 * k);
-        matrix_batch_chains(mc, n, a, b, k, ctx->opt_matrix_batch_threads, hashes.data());
+        if (sponge_chains_on_device(ctx, 3 * k)) matrix_batch_chains_device(mc, n, k, hashes.data());
+        else matrix_batch_chains(mc, n, a, b, k, ctx->opt_matrix_batch_threads, hashes.data());
     } catch (const std::bad_alloc &) {
         return ZKG16_ERR_OOM;
     }

@@ -216,6 +216,26 @@ class Device:
         self._check(self.lib.zkg16_witness_matrix_batch(self.ctx, n, _ptr(a), _ptr(b), k, _ptr(handles), _ptr(pub), C.addressof(ms)))
         return handles, pub, dict(host_sponges_ms=float(ms[0]), device_ms=float(ms[1]), call_ms=float(ms[2]))
 
+    def poseidon_hash_batch(self, elems):
+        """k Poseidon hashes in one call (zkg16_poseidon_hash_batch): elems [k, n, 4] Montgomery Fr -> [k, 4], row i the bytes of
+        circuits.poseidon_hash(elems[i]).  At least option "sponge_chains_min" vectors are hashed by a kernel, fewer on host threads."""
+        elems = np.ascontiguousarray(elems, dtype=np.uint64)
+        if elems.ndim != 3 or elems.shape[2] != 4:
+            raise ValueError("poseidon_hash_batch: elems must be k x n x 4")
+        out = np.zeros((elems.shape[0], 4), dtype=np.uint64)
+        self._check(self.lib.zkg16_poseidon_hash_batch(self.ctx, _ptr(elems), elems.shape[1], elems.shape[0], _ptr(out)))
+        return out
+
+    def matrix_hash_batch(self, m):
+        """The matrix handler's hash of k matrices of one size, m [k, n, n] u64, in one call (zkg16_matrix_hash_batch) -> [k, 4]
+        Montgomery Fr: row i is hash_a of witness_matrix(m[i], .), the public input a verifier needs."""
+        m = np.ascontiguousarray(m, dtype=np.uint64)
+        if m.ndim != 3 or m.shape[1] != m.shape[2]:
+            raise ValueError("matrix_hash_batch: m must be k x n x n")
+        out = np.zeros((m.shape[0], 4), dtype=np.uint64)
+        self._check(self.lib.zkg16_matrix_hash_batch(self.ctx, m.shape[1], _ptr(m), m.shape[0], _ptr(out)))
+        return out
+
     def witness_read(self, h, n_assign):
         z = np.zeros((n_assign, 4), dtype=np.uint64)
         self._check(self.lib.zkg16_witness_read(self.ctx, h, z.reshape(-1), n_assign))

@@ -13,7 +13,7 @@ import time
 import numpy as np
 
 from . import wire
-from .circuits import fibonacci_circuit, fibonacci_circuit_handle, matrix_circuit, prime_circuit, prime_dims, prime_public_inputs, prime_search
+from .circuits import fibonacci_circuit, fibonacci_circuit_handle, matrix_circuit, matrix_hash_batch_host, prime_circuit, prime_dims, prime_public_inputs, prime_search
 from .workloads import R_MOD, g1_generator, g2_generator
 
 
@@ -170,6 +170,22 @@ def _setup_and_prove_prime_device(dev, x, j, circ, rng):
             if h is not None:
                 f(h)
     return dict(proof=proof, inf=inf, vk=vk, pk=None, setup_time=setup_time, proving_time=proving_time, r=r, s=s)
+
+
+def hash_matrix(size, matrix):
+    """The reference's hash_matrix endpoint (matrix_proof.rs:44-71) -> its OutputData: {"hash": the 32 little-endian bytes of the
+    canonical value}.  This is where a client obtains the hashes that become a proof's public inputs.  Host only."""
+    return hash_matrices(size, [matrix])[0]
+
+
+def hash_matrices(size, matrices, dev=None):
+    """hash_matrix for K requests of one size in one call -> K OutputData dicts.  With dev the batch goes through
+    Device.matrix_hash_batch (a kernel from option "sponge_chains_min" matrices on), else through host threads."""
+    if len(matrices) == 0:
+        raise ValueError("hash_matrices: no requests")
+    m = np.stack([np.asarray(x, dtype=np.uint64).reshape(size, size) for x in matrices])
+    hashes = dev.matrix_hash_batch(m) if dev is not None else matrix_hash_batch_host(m)
+    return [dict(hash=list(wire.hash_bytes(h))) for h in hashes]   # OutputData.hash: a Vec<u8> (matrix_proof.rs:66-70)
 
 
 def prove_matrix(dev, size, matrix_a, matrix_b, seed=0, keep_key=False):

@@ -231,10 +231,14 @@ def decode_proof(s):
     return proof_deserialize_compressed(base64.standard_b64decode(s))
 
 
+def hash_bytes(fr_mont_limbs):
+    """Fr (Montgomery limbs) -> into_bigint().to_bytes_le(): the 32 little-endian bytes of the canonical value"""
+    return (_int(fr_mont_limbs) * _RR_INV % R).to_bytes(32, "little")
+
+
 def encode_hash(fr_mont_limbs):
     """Fr (Montgomery limbs) -> into_bigint().to_bytes_le() -> base64 (matrix_proof.rs:116-120)."""
-    v = _int(fr_mont_limbs) * _RR_INV % R
-    return base64.standard_b64encode(v.to_bytes(32, "little")).decode()
+    return base64.standard_b64encode(hash_bytes(fr_mont_limbs)).decode()
 
 
 def decode_hash(s):
