@@ -596,6 +596,117 @@ def test_error_paths(dev):
                     ("fixed_base_bits", 22)):
         with pytest.raises(Zkg16Error):
             dev.set_option(name, v)
+    # every option name zkg16_set_option accepts: one accepted value, the nearest rejected value on each bounded side
+    try:
+        for name, accepted, rejected, _ in OPTION_BOUNDS:
+            for v in accepted:
+                dev.set_option(name, v)
+            for v in rejected:
+                with pytest.raises(Zkg16Error) as e:
+                    dev.set_option(name, v)
+                assert e.value.status == 1, (name, v)        # ZKG16_ERR_BAD_ARG
+        with pytest.raises(Zkg16Error) as e:
+            dev.set_option("no_such_option", 1)
+        assert e.value.status == 7                           # ZKG16_ERR_UNSUPPORTED
+    finally:
+        for name, _, _, default in OPTION_BOUNDS:
+            dev.set_option(name, default)
+
+
+# (name, accepted values, rejected values, the value that restores the default).  The bounds are those of zkg16_set_option; fixup_aux,
+# wm_concurrent and fuse_pointwise take any value.  0 restores the default of sponge_chains_min and of the three verify thresholds.
+OPTION_BOUNDS = (
+    ("lanes", (1, 8), (0, 9), 2),
+    ("window_bits", (2, 20), (-1, 1, 21), 0),
+    ("min_seg", (4096,), (-1, 4097), 0),
+    ("ntt_mode", (0, 3), (-1, 2, 4), 1),
+    ("reduce_mode", (6,), (-1, 7), 0),
+    ("g1_waves", (4,), (-1, 5), 0),
+    ("fixup_aux", (1,), (), 0),
+    ("window_bits_h", (2, 20), (-1, 1, 21), 0),
+    ("wm_concurrent", (0,), (), -1),
+    ("ntt_radix", (4,), (-1, 5), 0),
+    ("ntt_xcd", (2,), (-1, 3), 0),
+    ("acc_debug", (15,), (-1, 16), 0),
+    ("sort_mode", (1,), (-1, 2), 0),
+    ("acc_pipeline", (4,), (-1, 5), 0),
+    ("fuse_pointwise", (0,), (), 1),
+    ("wm_transforms", (6, 7), (-1, 1, 5, 8), 0),
+    ("wm_first", (-1, 2), (-2, 3), -1),
+    ("spmv_dict", (2,), (-1, 3), 0),
+    ("b_filter", (2,), (-1, 3), 0),
+    ("collect_threads", (2,), (-1, 3), 0),
+    ("fixed_base_bits", (4, 14, 16, 20), (-1, 3, 15, 21), 0),
+    ("g2_lazy", (2,), (-1, 3), 0),
+    ("g1_inline", (2,), (-1, 3), 0),
+    ("acc_lazy", (0,), (-1, 2), 1),
+    ("matrix_parts", (8,), (-1, 9), 0),
+    ("batch_max", (65535,), (-1, 65536), 0),
+    ("matrix_batch_threads", (16,), (-1, 17), 0),
+    ("matrix_batch_grid", (65535,), (-1, 65536), 0),
+    ("sponge_chains_min", (1, 1 << 40), (-1,), 0),
+    ("sponge_chain_segment", (65535,), (-1, 65536), 0),
+    ("verify_batch_min", (1 << 30,), (-1, (1 << 30) + 1), 0),
+    ("verify_wire_min", (1 << 30,), (-1, (1 << 30) + 1), 0),
+    ("verify_each_after", (1 << 30,), (-1, (1 << 30) + 1), 0),
+    ("reduce_chunk", (1, 64), (-1, 3, 65), 0),
+)
+
+
+def test_prove_entry_status_codes(dev, oracle):
+    """The status codes of zkg16_prove_resident / _partial / _batch on the smallest system the synth helper makes (50 constraints,
+    domain 2^6): an unknown handle is reported before any shape check, a key shard is a bad argument to prove_resident and
+    unsupported by prove_batch, a witness of the wrong length is a bad argument everywhere; the ctx still proves afterwards."""
+    from zksnark_finalproject_amd import Zkg16Error
+    BAD_ARG, BAD_HANDLE, UNSUPPORTED = 1, 6, 7
+    rng = random.Random(77)
+    nc, ni, nv = 50, 3, 40
+    A, B, C, z = synth.random_r1cs(rng, nc, ni, nv)
+    r1cs = synth.r1cs_arrays(A, B, C, ni)
+    pk, _ = synth.make_pk(oracle, r1cs, nv, rng, point_gen=dev.fixed_base)
+    zm = fr_mont_vec(z)
+    r, s = fr_mont(P.rand_fr(rng)), fr_mont(P.rand_fr(rng))
+    ph, rh, wh = dev.pk_load(pk, ni), dev.r1cs_load(r1cs, nv), dev.witness_load(zm)
+    shard = dev.pk_slice(ph, 0, nv // 2, 0, 30, True)
+    long_w = dev.witness_load(np.concatenate([zm, zm[:1]]))
+    none = 987654321
+
+    def status(call):
+        with pytest.raises(Zkg16Error) as e:
+            call()
+        return e.value.status
+
+    def resident(p, c, w): return lambda: dev.prove_resident(p, c, w, r, s)
+    def partial(p, c, w): return lambda: dev.prove_partial(p, c, w, r, s)
+    def batch(p, c, ws): return lambda: dev.prove_batch(p, c, ws, np.stack([r] * len(ws)), np.stack([s] * len(ws)))
+
+    try:
+        for entry in (resident, partial):
+            assert status(entry(none, rh, wh)) == BAD_HANDLE
+            assert status(entry(ph, none, wh)) == BAD_HANDLE
+            assert status(entry(ph, rh, none)) == BAD_HANDLE
+            assert status(entry(ph, rh, long_w)) == BAD_ARG
+            assert status(entry(none, rh, long_w)) == BAD_HANDLE      # the handles are looked up before any shape is compared
+        assert status(batch(none, rh, [wh])) == BAD_HANDLE
+        assert status(batch(ph, none, [wh])) == BAD_HANDLE
+        assert status(batch(ph, rh, [wh, none])) == BAD_HANDLE
+        assert status(batch(ph, rh, [wh, long_w])) == BAD_ARG
+        assert status(batch(ph, rh, [long_w, none])) == BAD_HANDLE
+        assert status(resident(shard, rh, wh)) == BAD_ARG
+        assert status(batch(shard, rh, [wh])) == UNSUPPORTED
+        assert status(batch(shard, rh, [long_w])) == UNSUPPORTED          # the shard is refused before the lengths are compared
+        assert status(batch(shard, rh, [none])) == BAD_HANDLE
+        part, pinf = dev.prove_partial(shard, rh, wh, r, s)               # prove_partial takes shards
+        assert part.shape == (72,) and pinf.shape == (5,)
+        proof, inf = dev.prove_resident(ph, rh, wh, r, s)
+        eproof, einf = oracle.prove(pk, r, s, r1cs, zm)
+        assert np.array_equal(proof, eproof) and np.array_equal(inf, einf)
+    finally:
+        for w in (wh, long_w):
+            dev.witness_free(w)
+        for p in (shard, ph):
+            dev.pk_free(p)
+        dev.r1cs_free(rh)
 
 
 @pytest.mark.parametrize("kind", ["fib0", "fib10", "fib186", "fib1000", "matrix3", "matrix8", "matrix32", "prime"])

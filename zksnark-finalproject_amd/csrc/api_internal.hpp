@@ -1,0 +1,174 @@
+// What the files behind the C ABI (include/zkg16.h) share: api.hip (ctx, lanes, options, instrumentation), api_keys.hip (key /
+// R1CS / assignment residency), api_prove.hip (the prove pipeline and its host tail), api_stages.hip (setup and the stage entry
+// points), api_group.hip (device groups) and api_verify.hip (batched verification).  None of them holds a kernel.
+#pragma once
+#include <chrono>
+#include <exception>
+
+#include "common.hpp"
+
+namespace zk {
+
+// ---- zkg16_ctx::timings (zkg16_last_timings; device.py names them).  The layout is ABI: it does not move.  The array keeps its
+// declared size, PROOF_TIMING_SLOTS = 24; the 22 slots below are the ones in use.
+enum ProofTiming : int {
+    T_SPMV = 0,            // always 0 (the SpMV is part of the witness map)
+    T_WITNESS_MAP = 1,     // device time of the witness map
+    T_SORT = 2,            // device time of digits + sort of both scalar vectors
+    // host-observed completion gaps of H, L, A, B1, B2 (collected in the order B2, L, A, B1, H — the first gap contains most of the
+    // device time: NOT a breakdown)
+    T_GAP_H = 3, T_GAP_L = 4, T_GAP_A = 5, T_GAP_B1 = 6, T_GAP_B2 = 7,
+    T_HOST_TAIL = 8,       // the O(1) host tail (a batch: H's combination and the tails of all its proofs)
+    T_TOTAL = 9,           // wall time of the proving call
+    // device time of the bucket accumulation (+ fix-ups) of H, L, A, B1, B2 and of their bucket reductions, from event pairs on the
+    // streams they ran on — the per-stage times upstream's spans ("Compute C" = H + L, "Compute A", "Compute B in G1", "Compute B in
+    // G2": ark-groth16 prover.rs) correspond to.  Kernels of different MSMs overlap, so these sum to more than the proof.
+    T_ACC_H = 10, T_ACC_L = 11, T_ACC_A = 12, T_ACC_B1 = 13, T_ACC_B2 = 14,
+    T_RED_H = 15, T_RED_L = 16, T_RED_A = 17, T_RED_B1 = 18, T_RED_B2 = 19,
+    T_HORNER_H = 20,       // host Horner of H's window sums (after the last device event of the proof: exposed)
+    T_HORNER_Z = 21,       // ... of the other four (they overlap H's device work)
+    T_COUNT = 22
+};
+// ---- zkg16_ctx::vb_timings (zkg16_verify_batch_timings), ABI as well
+enum VerifyTiming : int {
+    V_MEMBERSHIP = 0,      // launch to membership verdicts on the host (host clock)
+    V_MILLER = 1,          // scaling + Miller kernel
+    V_PRODUCT = 2,         // product tree
+    V_MSM = 3,             // sum rho_k C_k
+    V_HOST = 4,            // host equation (vb_decide writes this slot and the next)
+    V_BISECT = 5,          // bisecting
+    V_TOTAL = 6,           // wall time of the call
+    V_HOST_FORM = 7,       // 1 when the host form answered
+    V_DECODE = 8,          // decoding the wire bytes (zkg16_verify_batch_wire)
+    V_EACH = 9,            // the per-proof pass that took over from bisecting (0: it did not run)
+    V_RANGE_TESTS = 10,    // range tests bisecting made
+    V_COUNT = 11
+};
+static_assert(T_COUNT <= PROOF_TIMING_SLOTS && V_COUNT == VERIFY_TIMING_SLOTS, "timing slots");
+
+int fail(zkg16_ctx *ctx, const HipError &e);      // api.hip: the error's text into ctx->last_error -> its status
+
+#define ZK_API_BEGIN(ctx)                         \
+    if (!(ctx)) return ZKG16_ERR_BAD_ARG;         \
+    std::lock_guard<std::mutex> _lk((ctx)->mu);   \
+    try {                                         \
+        ZK_HIP(hipSetDevice((ctx)->device));
+#define ZK_API_END(ctx)                           \
+    }                                             \
+    catch (const HipError &e) { return fail((ctx), e); } \
+    catch (const std::bad_alloc &) { return ZKG16_ERR_OOM; } \
+    return ZKG16_OK;
+
+inline double now_ms() {
+    using namespace std::chrono;
+    return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
+}
+
+// ---- lanes (common.hpp: zkg16_ctx::lanes).  Proving entry points take a free lane for the duration of the call; everything
+// else (key / matrix / assignment residency, setup, the stage entry points) runs on the root under its mutex.
+// A free lane of `root` for one proof: the lowest free one (a single caller always gets lane 0 = the root itself, so nothing
+// changes for it); callers beyond opt_lanes wait.  The lane's mutex is held for the lease.  (api.hip)
+struct LaneLease {
+    zkg16_ctx *root, *lane = nullptr;
+    int idx = -1;
+    double t0 = 0;
+    std::unique_lock<std::mutex> held;
+    std::shared_lock<std::shared_mutex> keys;
+    explicit LaneLease(zkg16_ctx *r);
+    ~LaneLease();
+    LaneLease(const LaneLease &) = delete;
+    LaneLease &operator=(const LaneLease &) = delete;
+};
+inline zkg16_ctx *lane_of(zkg16_ctx *root, int idx) { return idx <= 0 || idx > 7 || !root->lanes[idx - 1] ? root : root->lanes[idx - 1].get(); }
+// the proving entry points: `ctx` is rebound to the leased lane for the body, `root` keeps the handle maps
+#define ZK_LANE_BEGIN(ctx)                        \
+    if (!(ctx)) return ZKG16_ERR_BAD_ARG;         \
+    zkg16_ctx *const root = (ctx);                \
+    try {                                         \
+        LaneLease _lease(root);                   \
+        (ctx) = _lease.lane;                      \
+        try {                                     \
+            ZK_HIP(hipSetDevice((ctx)->device));
+#define ZK_LANE_END(ctx)                          \
+        } catch (const HipError &e) {             \
+            const int _rc = fail((ctx), e);       \
+            if ((ctx) != root) { std::lock_guard<std::mutex> _l(root->lane_mu); root->last_error = (ctx)->last_error; } \
+            return _rc;                           \
+        }                                         \
+    } catch (const HipError &e) { return fail(root, e); } \
+    catch (const std::bad_alloc &) { return ZKG16_ERR_OOM; } \
+    return ZKG16_OK;
+
+// ---- host <-> ABI conversions (u64 limbs and u32 limbs share the little-endian byte layout)
+inline Fr fr_from_abi(const uint64_t *l) {
+    Fr v;
+    memcpy(&v, l, sizeof v);
+    return v;
+}
+inline G1Affine g1_from_abi(const uint64_t *l, int inf) {
+    G1Affine p;
+    if (inf) return G1Affine::inf();
+    memcpy(&p, l, sizeof p);
+    return p;
+}
+inline G2Affine g2_from_abi(const uint64_t *l, int inf) {
+    G2Affine p;
+    if (inf) return G2Affine::inf();
+    memcpy(&p, l, sizeof p);
+    return p;
+}
+template <class A>
+void point_to_abi(const A &p, uint64_t *out, uint8_t *inf) {
+    if (p.is_inf()) {
+        memset(out, 0, sizeof p);
+        if (inf) *inf = 1;
+    } else {
+        memcpy(out, &p, sizeof p);
+        if (inf) *inf = 0;
+    }
+}
+
+// ---- uploads (api_keys.hip)
+template <class A> struct UOf;
+template <> struct UOf<G1Affine> { using T = G1AffineU; };
+template <> struct UOf<G2Affine> { using T = G2AffineU; };
+// Upload a slice [lo, hi) of a saturated affine query vector and convert it into the unsaturated device form at
+// dst[0 .. hi-lo); flagged-infinity points become (0,0).  A = G1Affine or G2Affine.
+template <class A>
+void upload_points(zkg16_ctx *ctx, typename UOf<A>::T *dst, const uint64_t *src, const uint8_t *inf, size_t lo, size_t hi);
+template <class A>
+void upload_one(zkg16_ctx *ctx, typename UOf<A>::T *dst, const A &p);
+// host -> device copy of a large pageable buffer through the ctx's pinned ring, queued on ctx->stream
+void upload_h2d(zkg16_ctx *ctx, void *dst, const void *src, size_t bytes);
+// validate + allocate an R1CS (nothing is copied yet) / queue the copies of its three matrices on ctx->stream
+int r1cs_create(const uint64_t *const rp[3], const uint32_t *const col[3], const uint64_t *const cf[3], size_t num_instance,
+                size_t num_constraints, size_t num_variables, std::unique_ptr<R1csDev> &out);
+void r1cs_copy(zkg16_ctx *ctx, R1csDev &r, const uint64_t *const rp[3], const uint32_t *const col[3], const uint64_t *const cf[3]);
+
+// events of one proof, destroyed on every exit path
+struct EventSet {
+    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    EventSet() { for (auto &e : ev) ZK_HIP(hipEventCreate(&e)); }
+    ~EventSet() { for (auto &e : ev) if (e) (void)hipEventDestroy(e); }
+    EventSet(const EventSet &) = delete;
+    EventSet &operator=(const EventSet &) = delete;
+};
+
+// ---- the prove pipeline (api_prove.hip), as far as the device groups need it
+struct GroupRank;      // group.hpp
+struct Partials {
+    G1XYZZ h, l, a, b1;
+    G2XYZZ b2;
+    // un-sharded proofs: s*(a + alpha) and r*(b1 + beta) are formed on the host as soon as A and B1 are collected, while the
+    // device still works on the remaining MSMs (they are ~0.35 ms of the 0.4 ms host tail)
+    bool have_early = false;
+    G1XYZZ s_a, r_b1;
+};
+void prove_device(zkg16_ctx *ctx, PkDev &pk, R1csDev &rc, WitnessDev &wit, const Fr &r, const Fr &s, Partials &out,
+                  const std::function<void()> *before_witness_map = nullptr, const ZParts *zp = nullptr, GroupRank *grp = nullptr);
+void prove_tail(PkDev &pk, const Fr &r, const Fr &s, const Partials &p, uint64_t *proof_out, uint8_t *inf_out);
+// the record of zkg16_prove_partial (h, l, a, b1 | b2 as affine limbs, one infinity flag each), and the sum of n_ranks of them
+void partials_to_abi(const Partials &p, uint64_t out[72], uint8_t inf[5]);
+void sum_partials(Partials &p, const uint64_t *partials, const uint8_t *partial_inf, int n_ranks);
+
+}  // namespace zk

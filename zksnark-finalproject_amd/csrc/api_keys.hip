@@ -1,0 +1,605 @@
+// libzkg16 C ABI, part 2 of 6 (api.hip): residency — proving keys and their shards (load, slice, shard plans, window tables), R1CS
+// matrices, synthesized circuits and assignments; the host -> device upload helpers the other parts share.
+#include "api_internal.hpp"
+
+using namespace zk;
+
+namespace {
+inline void convert_bases(zkg16_ctx *ctx, const G1Affine *in, G1AffineU *out, size_t n) { convert_g1_bases(ctx, in, out, n); }
+inline void convert_bases(zkg16_ctx *ctx, const G2Affine *in, G2AffineU *out, size_t n) { convert_g2_bases(ctx, in, out, n); }
+
+}  // namespace
+
+namespace zk {
+template <class A>
+void upload_points(zkg16_ctx *ctx, typename UOf<A>::T *dst, const uint64_t *src, const uint8_t *inf, size_t lo, size_t hi) {
+    if (hi <= lo) return;
+    const size_t n = hi - lo;
+    const A *s = reinterpret_cast<const A *>(src) + lo;
+    DevBuf stage(n * sizeof(A));
+    if (!inf) {
+        ZK_HIP(hipMemcpyAsync(stage.p, s, n * sizeof(A), hipMemcpyHostToDevice, ctx->stream));
+    } else {
+        std::vector<A> tmp(s, s + n);
+        for (size_t i = 0; i < n; i++)
+            if (inf[lo + i]) tmp[i] = A::inf();
+        ZK_HIP(hipMemcpyAsync(stage.p, tmp.data(), n * sizeof(A), hipMemcpyHostToDevice, ctx->stream));
+        ZK_HIP(hipStreamSynchronize(ctx->stream));      // tmp is freed at scope exit
+    }
+    convert_bases(ctx, stage.as<A>(), dst, n);
+    ZK_HIP(hipStreamSynchronize(ctx->stream));
+}
+
+template <class A>
+void upload_one(zkg16_ctx *ctx, typename UOf<A>::T *dst, const A &p) {
+    const typename UOf<A>::T u{to_u(p.x), to_u(p.y)};     // host-side conversion (same templates)
+    ZK_HIP(hipMemcpyAsync(dst, &u, sizeof(u), hipMemcpyHostToDevice, ctx->stream));
+    ZK_HIP(hipStreamSynchronize(ctx->stream));
+}
+template void upload_points<G1Affine>(zkg16_ctx *, G1AffineU *, const uint64_t *, const uint8_t *, size_t, size_t);
+template void upload_points<G2Affine>(zkg16_ctx *, G2AffineU *, const uint64_t *, const uint8_t *, size_t, size_t);
+template void upload_one<G1Affine>(zkg16_ctx *, G1AffineU *, const G1Affine &);
+template void upload_one<G2Affine>(zkg16_ctx *, G2AffineU *, const G2Affine &);
+
+// validate + allocate (nothing is copied yet)
+int r1cs_create(const uint64_t *const rp[3], const uint32_t *const col[3], const uint64_t *const cf[3], size_t num_instance,
+                size_t num_constraints, size_t num_variables, std::unique_ptr<R1csDev> &out) {
+    if (num_instance == 0) return ZKG16_ERR_BAD_ARG;
+    for (int i = 0; i < 3; i++)
+        if (!rp[i] || (rp[i][num_constraints] && (!col[i] || !cf[i]))) return ZKG16_ERR_BAD_ARG;
+    const size_t dom = num_constraints + num_instance;
+    int log_n = 0;
+    while (((size_t)1 << log_n) < dom) log_n++;
+    if (log_n > 32) return ZKG16_ERR_DOMAIN_TOO_LARGE;      // ark: SynthesisError::PolynomialDegreeTooLarge
+    if (log_n > 28) return ZKG16_ERR_DOMAIN_TOO_LARGE;      // build limit (three-pass NTT covers 2^31; 32-bit entry indices cap the MSMs)
+    auto r = std::make_unique<R1csDev>();
+    r->num_instance = num_instance;
+    r->num_constraints = num_constraints;
+    r->num_variables = num_variables;
+    r->log_n = log_n;
+    for (int i = 0; i < 3; i++) {
+        const size_t nnz = rp[i][num_constraints];
+        // row pointers: start at 0, never decrease, end at nnz — spmv_kernel walks [rp[row], rp[row+1]) unchecked on the device
+        if (rp[i][0] != 0) return ZKG16_ERR_BAD_ARG;
+        // both scans in slices on a few host threads (86.6 M column indices in the 128x128 circuit: ~0.1 s on one)
+        const int T = (nnz + num_constraints) >= ((size_t)1 << 22) ? 8 : 1;
+        std::vector<int> bad(T, 0);
+        auto scan = [&](int t) {
+            const size_t r0 = num_constraints * t / T, r1 = num_constraints * (t + 1) / T;
+            for (size_t row = r0; row < r1; row++)
+                if (rp[i][row] > rp[i][row + 1]) { bad[t] = 1; return; }
+            const size_t k0 = nnz * t / T, k1 = nnz * (t + 1) / T;
+            uint32_t top = 0;
+            for (size_t k = k0; k < k1; k++) top = col[i][k] > top ? col[i][k] : top;
+            if (k1 > k0 && top >= num_variables) bad[t] = 1;
+        };
+        {
+            ThreadGroup tg;
+            for (int t = 1; t < T; t++) tg.run([&scan, t]() { scan(t); });
+            scan(0);
+        }
+        for (int t = 0; t < T; t++)
+            if (bad[t]) return ZKG16_ERR_BAD_ARG;
+        r->nnz[i] = nnz;
+        r->rp[i].alloc((num_constraints + 1) * sizeof(uint64_t));
+        r->col[i].alloc(nnz * sizeof(uint32_t));
+        r->cf[i].alloc(nnz * sizeof(Fr));
+    }
+    out = std::move(r);
+    return ZKG16_OK;
+}
+// Host -> device copy of a large pageable buffer, queued on ctx->stream.  hipMemcpyAsync from pageable memory goes through
+// the runtime's own single-threaded staging (~9 GB/s measured: the 3.5 GB of a 128x128 R1CS took 0.38 s of the 0.55 s
+// host-pointer proof); here four host threads fill one half of a pinned ring while the DMA engine drains the other.
+static constexpr size_t STAGE_BYTES = (size_t)64 << 20;
+void upload_h2d(zkg16_ctx *ctx, void *dst, const void *src, size_t bytes) {
+    if (bytes < ((size_t)8 << 20)) {
+        ZK_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ctx->stream));
+        return;
+    }
+    for (int i = 0; i < 2; i++)
+        if (!ctx->stage_host[i]) {
+            ZK_HIP(hipHostMalloc(&ctx->stage_host[i], STAGE_BYTES, hipHostMallocDefault));
+            ZK_HIP(hipEventCreateWithFlags(&ctx->stage_done[i], hipEventDisableTiming));
+        }
+    const unsigned char *s = static_cast<const unsigned char *>(src);
+    unsigned char *d = static_cast<unsigned char *>(dst);
+    int slot = 0;
+    for (size_t off = 0; off < bytes; off += STAGE_BYTES, slot ^= 1) {
+        const size_t len = bytes - off < STAGE_BYTES ? bytes - off : STAGE_BYTES;
+        ZK_HIP(hipEventSynchronize(ctx->stage_done[slot]));         // the copy that last used this half has left it (a fresh event is complete)
+        unsigned char *stage = static_cast<unsigned char *>(ctx->stage_host[slot]);
+        constexpr int T = 4;
+        const size_t part = (len / T + 4095) & ~(size_t)4095;
+        {
+            ThreadGroup tg;
+            for (int t = 1; t < T; t++) {
+                const size_t lo = part * t < len ? part * t : len, hi = part * (t + 1) < len ? part * (t + 1) : len;
+                tg.run([=]() { if (hi > lo) memcpy(stage + lo, s + off + lo, hi - lo); });
+            }
+            memcpy(stage, s + off, part < len ? part : len);
+        }
+        ZK_HIP(hipMemcpyAsync(d + off, stage, len, hipMemcpyHostToDevice, ctx->stream));
+        ZK_HIP(hipEventRecord(ctx->stage_done[slot], ctx->stream));
+    }
+}
+// host -> device copies of the three matrices, queued on ctx->stream (the call returns when the last piece is staged)
+void r1cs_copy(zkg16_ctx *ctx, R1csDev &r, const uint64_t *const rp[3], const uint32_t *const col[3], const uint64_t *const cf[3]) {
+    for (int i = 0; i < 3; i++) {
+        upload_h2d(ctx, r.rp[i].p, rp[i], (r.num_constraints + 1) * sizeof(uint64_t));
+        if (r.nnz[i]) {
+            upload_h2d(ctx, r.col[i].p, col[i], r.nnz[i] * sizeof(uint32_t));
+            upload_h2d(ctx, r.cf[i].p, cf[i], r.nnz[i] * sizeof(Fr));
+        }
+    }
+}
+}  // namespace zk
+
+namespace {
+int load_r1cs(zkg16_ctx *ctx, const uint64_t *const rp[3], const uint32_t *const col[3], const uint64_t *const cf[3],
+              size_t num_instance, size_t num_constraints, size_t num_variables, uint64_t *handle) {
+    if (!handle) return ZKG16_ERR_BAD_ARG;
+    std::unique_ptr<R1csDev> r;
+    const int rc = r1cs_create(rp, col, cf, num_instance, num_constraints, num_variables, r);
+    if (rc) return rc;
+    r1cs_copy(ctx, *r, rp, col, cf);
+    ZK_HIP(hipStreamSynchronize(ctx->stream));
+    *handle = ctx->next_handle++;
+    ctx->r1cs.put(*handle, std::move(r));
+    return ZKG16_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int zkg16_pk_load_range(zkg16_ctx *ctx,
+                        const uint64_t *a_query, const uint8_t *a_inf, size_t n_a,
+                        const uint64_t *b_g1_query, const uint8_t *b_g1_inf, size_t n_b1,
+                        const uint64_t *b_g2_query, const uint8_t *b_g2_inf, size_t n_b2,
+                        const uint64_t *h_query, const uint8_t *h_inf, size_t n_h,
+                        const uint64_t *l_query, const uint8_t *l_inf, size_t n_l,
+                        const uint64_t alpha_g1[12], const uint64_t beta_g1[12], const uint64_t beta_g2[24],
+                        const uint64_t delta_g1[12], const uint64_t delta_g2[24],
+                        size_t num_instance, size_t z_lo, size_t z_hi, size_t h_lo, size_t h_hi, int blinding, uint64_t *pk_handle) {
+    if (!pk_handle || !a_query || !b_g1_query || !b_g2_query || (!h_query && n_h) || (!l_query && n_l) || !alpha_g1 || !beta_g1 ||
+        !beta_g2 || !delta_g1 || !delta_g2)
+        return ZKG16_ERR_BAD_ARG;
+    if (n_a == 0 || n_a != n_b1 || n_a != n_b2 || num_instance == 0 || num_instance > n_a || n_l != n_a - num_instance) return ZKG16_ERR_BAD_ARG;
+    if (z_lo > z_hi || z_hi > n_a || h_lo > h_hi || h_hi > n_h) return ZKG16_ERR_BAD_ARG;
+    ZK_API_BEGIN(ctx)
+    auto pk = std::make_unique<PkDev>();
+    pk->num_instance = num_instance;
+    pk->m_total = n_a;
+    pk->n_h_total = n_h;
+    pk->z_lo = z_lo; pk->z_hi = z_hi; pk->h_lo = h_lo; pk->h_hi = h_hi;
+    pk->blinding = blinding != 0;
+    pk->full = z_lo == 0 && z_hi == n_a && h_lo == 0 && h_hi == n_h && pk->blinding;
+    const size_t nz = pk->z_hi - pk->z_lo, nh = pk->h_hi - pk->h_lo;
+    pk->a.alloc((nz + 3) * sizeof(G1AffineU));
+    pk->b1.alloc((nz + 3) * sizeof(G1AffineU));
+    pk->l.alloc((nz + 3) * sizeof(G1AffineU));
+    pk->b2.alloc((nz + 3) * sizeof(G2AffineU));
+    pk->h.alloc((nh ? nh : 1) * sizeof(G1AffineU));
+    ZK_HIP(hipMemsetAsync(pk->a.p, 0, pk->a.bytes, ctx->stream));      // (0,0) = infinity everywhere by default
+    ZK_HIP(hipMemsetAsync(pk->b1.p, 0, pk->b1.bytes, ctx->stream));
+    ZK_HIP(hipMemsetAsync(pk->l.p, 0, pk->l.bytes, ctx->stream));
+    ZK_HIP(hipMemsetAsync(pk->b2.p, 0, pk->b2.bytes, ctx->stream));
+    ZK_HIP(hipStreamSynchronize(ctx->stream));
+    upload_points<G1Affine>(ctx, pk->a.as<G1AffineU>(), a_query, a_inf, pk->z_lo, pk->z_hi);
+    upload_points<G1Affine>(ctx, pk->b1.as<G1AffineU>(), b_g1_query, b_g1_inf, pk->z_lo, pk->z_hi);
+    upload_points<G2Affine>(ctx, pk->b2.as<G2AffineU>(), b_g2_query, b_g2_inf, pk->z_lo, pk->z_hi);
+    upload_points<G1Affine>(ctx, pk->h.as<G1AffineU>(), h_query, h_inf, pk->h_lo, pk->h_hi);
+    // l_query[j] pairs with z[num_instance + j]: place it at the same index as its scalar in this shard's z slice
+    {
+        const size_t lo = pk->z_lo > num_instance ? pk->z_lo : num_instance, hi = pk->z_hi;
+        if (hi > lo)
+            upload_points<G1Affine>(ctx, pk->l.as<G1AffineU>() + (lo - pk->z_lo), l_query, l_inf, lo - num_instance, hi - num_instance);
+    }
+    pk->alpha_g1 = g1_from_abi(alpha_g1, 0);
+    pk->beta_g1 = g1_from_abi(beta_g1, 0);
+    pk->delta_g1 = g1_from_abi(delta_g1, 0);
+    pk->beta_g2 = g2_from_abi(beta_g2, 0);
+    pk->delta_g2 = g2_from_abi(delta_g2, 0);
+    // extra slots (scalars r, s, -rs):  a += r*delta1 ; b1 += s*delta1 ; b2 += s*delta2 ; l += (-rs)*delta1
+    upload_one<G1Affine>(ctx, pk->a.as<G1AffineU>() + nz + 0, pk->delta_g1);
+    upload_one<G1Affine>(ctx, pk->b1.as<G1AffineU>() + nz + 1, pk->delta_g1);
+    upload_one<G2Affine>(ctx, pk->b2.as<G2AffineU>() + nz + 1, pk->delta_g2);
+    upload_one<G1Affine>(ctx, pk->l.as<G1AffineU>() + nz + 2, pk->delta_g1);
+    pk->b_mask.alloc(nz + 3);
+    pk->b_skipped = b_density_mask_run(ctx, pk->b1.as<G1AffineU>(), pk->b2.as<G2AffineU>(), nz + 3, pk->b_mask.as<uint8_t>());
+    *pk_handle = ctx->next_handle++;
+    ctx->pks.put(*pk_handle, std::move(pk));
+    ZK_API_END(ctx)
+}
+
+int zkg16_pk_load(zkg16_ctx *ctx,
+                  const uint64_t *a_query, const uint8_t *a_inf, size_t n_a,
+                  const uint64_t *b_g1_query, const uint8_t *b_g1_inf, size_t n_b1,
+                  const uint64_t *b_g2_query, const uint8_t *b_g2_inf, size_t n_b2,
+                  const uint64_t *h_query, const uint8_t *h_inf, size_t n_h,
+                  const uint64_t *l_query, const uint8_t *l_inf, size_t n_l,
+                  const uint64_t alpha_g1[12], const uint64_t beta_g1[12], const uint64_t beta_g2[24],
+                  const uint64_t delta_g1[12], const uint64_t delta_g2[24],
+                  size_t num_instance, int shard_index, int shard_count, uint64_t *pk_handle) {
+    if (shard_count < 1 || shard_index < 0 || shard_index >= shard_count) return ZKG16_ERR_BAD_ARG;
+    return zkg16_pk_load_range(ctx, a_query, a_inf, n_a, b_g1_query, b_g1_inf, n_b1, b_g2_query, b_g2_inf, n_b2, h_query, h_inf, n_h, l_query,
+                               l_inf, n_l, alpha_g1, beta_g1, beta_g2, delta_g1, delta_g2, num_instance,
+                               n_a * (size_t)shard_index / shard_count, n_a * (size_t)(shard_index + 1) / shard_count,
+                               n_h * (size_t)shard_index / shard_count, n_h * (size_t)(shard_index + 1) / shard_count, shard_index == 0,
+                               pk_handle);
+}
+
+// A shard of a key that is already resident (zkg16_setup_resident / an un-sharded zkg16_pk_load): device-to-device copies of
+// the index ranges, nothing crosses PCIe.
+int zkg16_pk_slice(zkg16_ctx *ctx, uint64_t src_handle, size_t z_lo, size_t z_hi, size_t h_lo, size_t h_hi, int blinding,
+                   uint64_t *pk_handle) {
+    if (!pk_handle) return ZKG16_ERR_BAD_ARG;
+    ZK_API_BEGIN(ctx)
+    auto src_ref = ctx->pks.get(src_handle); PkDev *src = src_ref.get();
+    if (!src) return ZKG16_ERR_BAD_HANDLE;
+    if (!src->full) return ZKG16_ERR_BAD_ARG;
+    if (z_lo > z_hi || z_hi > src->m_total || h_lo > h_hi || h_hi > src->n_h_total) return ZKG16_ERR_BAD_ARG;
+    auto pk = std::make_unique<PkDev>();
+    pk->num_instance = src->num_instance;
+    pk->m_total = src->m_total;
+    pk->n_h_total = src->n_h_total;
+    pk->z_lo = z_lo; pk->z_hi = z_hi; pk->h_lo = h_lo; pk->h_hi = h_hi;
+    pk->blinding = blinding != 0;
+    pk->full = z_lo == 0 && z_hi == src->m_total && h_lo == 0 && h_hi == src->n_h_total && pk->blinding;
+    const size_t nz = z_hi - z_lo, nh = h_hi - h_lo, sm = src->m_total;
+    pk->a.alloc((nz + 3) * sizeof(G1AffineU));
+    pk->b1.alloc((nz + 3) * sizeof(G1AffineU));
+    pk->l.alloc((nz + 3) * sizeof(G1AffineU));
+    pk->b2.alloc((nz + 3) * sizeof(G2AffineU));
+    pk->h.alloc((nh ? nh : 1) * sizeof(G1AffineU));
+    auto cp = [&](DevBuf &dst, const DevBuf &from, size_t elem) {
+        if (nz) ZK_HIP(hipMemcpyAsync(dst.p, static_cast<const unsigned char *>(from.p) + z_lo * elem, nz * elem, hipMemcpyDeviceToDevice, ctx->stream));
+        ZK_HIP(hipMemcpyAsync(static_cast<unsigned char *>(dst.p) + nz * elem, static_cast<const unsigned char *>(from.p) + sm * elem, 3 * elem,
+                              hipMemcpyDeviceToDevice, ctx->stream));      // the three trailing delta slots
+    };
+    cp(pk->a, src->a, sizeof(G1AffineU));
+    cp(pk->b1, src->b1, sizeof(G1AffineU));
+    cp(pk->l, src->l, sizeof(G1AffineU));
+    cp(pk->b2, src->b2, sizeof(G2AffineU));
+    if (nh) ZK_HIP(hipMemcpyAsync(pk->h.p, src->h.as<G1AffineU>() + h_lo, nh * sizeof(G1AffineU), hipMemcpyDeviceToDevice, ctx->stream));
+    pk->alpha_g1 = src->alpha_g1; pk->beta_g1 = src->beta_g1; pk->delta_g1 = src->delta_g1;
+    pk->beta_g2 = src->beta_g2; pk->delta_g2 = src->delta_g2;
+    pk->b_mask.alloc(nz + 3);
+    pk->b_skipped = b_density_mask_run(ctx, pk->b1.as<G1AffineU>(), pk->b2.as<G2AffineU>(), nz + 3, pk->b_mask.as<uint8_t>());
+    *pk_handle = ctx->next_handle++;
+    ctx->pks.put(*pk_handle, std::move(pk));
+    ZK_API_END(ctx)
+}
+
+// Rank roles for one proof over n_ranks GPUs (host-only, no ctx).  Work is counted in G1 mixed additions: a z-side term
+// costs W_z * (2 + density * (1 + kappa)) (L, A, and the B1 / B2 terms that are not infinity; kappa = G2 : G1 addition cost),
+// an h term W_h, the witness map omega per domain element.  The first k ranks run the witness map and share h_query; every
+// rank takes a share of the z ranges proportional to the time it has left, so that all finish together at
+//   T(k) = max( (Z + H + k * WM) / n_ranks,  WM + H / k ),
+// and k is the one that minimises T (k = n_ranks is the homogeneous split of round 1: every rank repeats the witness map).
+static int default_window_bits(size_t n) {
+    if (n >= ((size_t)1 << 23)) return 17;
+    if (n >= ((size_t)1 << 20)) return 16;
+    if (n >= ((size_t)1 << 17)) return 15;
+    if (n >= ((size_t)1 << 14)) return 13;
+    int lg = 0;
+    while (((size_t)2 << lg) <= n) lg++;
+    return lg - 3 < 4 ? 4 : lg - 3;
+}
+int zkg16_shard_plan(int n_ranks, size_t m_total, size_t n_h, double b_density, int h_ranks, const float *z_cost, uint64_t *ranges,
+                     uint8_t *blinding, int *h_ranks_out) {
+    return zkg16_shard_plan_tables(n_ranks, m_total, n_h, b_density, h_ranks, z_cost, 0, ranges, blinding, h_ranks_out);
+}
+int zkg16_shard_plan_tables(int n_ranks, size_t m_total, size_t n_h, double b_density, int h_ranks, const float *z_cost, int window_tables,
+                            uint64_t *ranges, uint8_t *blinding, int *h_ranks_out) {
+    if (n_ranks < 1 || m_total == 0 || !ranges || !blinding || h_ranks < 0 || h_ranks > n_ranks) return ZKG16_ERR_BAD_ARG;
+    if (!(b_density > 0.0) || b_density > 1.0) b_density = 0.8;
+    // calibrated on one MI355X playing every rank in turn (tools/shard_calibrate.py, profiles/shard_calibration_r2.txt, 128x128):
+    // a z-only shard takes 3.6 ms + 108 ms x its fraction of the z cost (97 ms with window tables on the shard), an h-only shard
+    // 23.8 ms (the witness map) + 1.2 ms + 46.0 ms x its fraction of h_query (41.2 ms with tables).  In additions at 6.2 G/s:
+    // z side 1.33x (1.19x) its additions, h side 1.13x (1.015x), witness map 8.8 per domain element.
+    constexpr double KAPPA = 2.8, OMEGA = 8.8;
+    const double Z_OVERHEAD = window_tables ? 1.19 : 1.33, H_OVERHEAD = window_tables ? 0.965 : 1.13;
+    const int G = n_ranks;
+    const double Wz = 254 / default_window_bits(m_total + 3) + 1, Wh = n_h ? 254 / default_window_bits(n_h) + 1 : 0;
+    // z-side work: uniform model, or the caller's per-index costs (in G1 mixed additions: entries of the scalar times the
+    // queries in which its base is not the point at infinity, the G2 one counted KAPPA times) — the witness of a real circuit
+    // is not uniform (runs of 0 / 1 values, variables absent from B), so equal index ranges are not equal work
+    double Z = (double)m_total * Wz * (2.0 + b_density * (1.0 + KAPPA));
+    if (z_cost) {
+        Z = 0;
+        for (size_t i = 0; i < m_total; i++) Z += z_cost[i] > 0 ? (double)z_cost[i] : 0.0;
+        if (!(Z > 0)) Z = 1.0;
+    }
+    Z *= Z_OVERHEAD;
+    const double H = H_OVERHEAD * (double)n_h * Wh, WM = n_h ? OMEGA * (double)(n_h + 1) : 0.0;
+    // fixed cost of taking part at all (latency chains that do not shrink with the share: the scatter passes and the four / one
+    // bucket reductions): ~1.9 ms for the z side, ~0.5 ms for the h side, in additions at 6.2 G/s.  With them a rank whose time
+    // is used up by the witness map and its h share takes no z work at all, and small circuits use fewer witness-map ranks.
+    // (round 3, profiles/shard_calibration_r3.txt: with the bit-sliced reductions a z-only shard takes 1.9 ms + 96.8 ms x its fraction,
+    // an h-only one 24.26 ms (the witness map + 0.46 ms) + 39.1 ms x its fraction: round 2's 3.5 / 1.15 ms became 1.9 / 0.46, and the
+    // h-side factor with tables 0.965 — with 1.5 ms / 1.015 the model preferred five witness-map ranks of eight, measured 36.0 against 34.5 ms)
+    constexpr double F_Z = 11.8e6, F_H = 2.9e6;
+    // time of the plan with k witness-map ranks: smallest T with  sum_i max(0, T - busy_i - F_Z) >= Z,  busy_i = WM + F_H + H/k (i < k)
+    auto busy_of = [&](int k, int i) { return i < k ? WM + (n_h ? F_H : 0.0) + H / k : 0.0; };
+    auto T_of = [&](int k) {
+        double lo = busy_of(k, 0), hi = lo + F_Z + Z + 1.0;
+        for (int it = 0; it < 80; it++) {
+            const double T = 0.5 * (lo + hi);
+            double c = 0;
+            for (int i = 0; i < G; i++) { const double x = T - busy_of(k, i) - F_Z; if (x > 0) c += x; }
+            if (c >= Z) hi = T; else lo = T;
+        }
+        return hi;
+    };
+    int k = h_ranks;
+    if (k == 0) {
+        k = 1;
+        for (int c = 2; c <= G; c++)
+            if (T_of(c) < T_of(k) * (1.0 - 1e-9)) k = c;
+    }
+    const double T = T_of(k);
+    std::vector<double> cap(G);
+    double cap_sum = 0;
+    for (int i = 0; i < G; i++) {
+        cap[i] = T - busy_of(k, i) - F_Z;
+        if (cap[i] < 0) cap[i] = 0;
+        cap_sum += cap[i];
+    }
+    if (!(cap_sum > 0)) { cap.assign(G, 1.0); cap_sum = G; }
+    double acc = 0, run = 0;
+    size_t prev = 0, pos = 0;
+    bool blind_given = false;
+    for (int i = 0; i < G; i++) {
+        acc += cap[i];
+        size_t hi;
+        if (i == G - 1) {
+            hi = m_total;
+        } else if (!z_cost) {
+            hi = (size_t)((double)m_total * (acc / cap_sum) + 0.5);
+        } else {                                              // advance until this rank's share of the total cost is reached
+            const double target = Z * (acc / cap_sum);
+            while (pos < m_total && run < target) { run += Z_OVERHEAD * (z_cost[pos] > 0 ? (double)z_cost[pos] : 0.0); pos++; }
+            hi = pos;
+        }
+        if (hi < prev) hi = prev;
+        if (hi > m_total) hi = m_total;
+        ranges[4 * i + 0] = prev;
+        ranges[4 * i + 1] = hi;
+        ranges[4 * i + 2] = i < k ? n_h * (size_t)i / k : 0;
+        ranges[4 * i + 3] = i < k ? n_h * (size_t)(i + 1) / k : 0;
+        blinding[i] = (!blind_given && hi > prev) ? 1 : 0;
+        blind_given = blind_given || blinding[i];
+        prev = hi;
+    }
+    if (h_ranks_out) *h_ranks_out = k;
+    return ZKG16_OK;
+}
+
+// Window tables for a resident key or shard (msm.hip, "window tables").  window_bits_* = 0: chosen from the query length;
+// < 0: leave that side as it is.  All four z-side queries share one width (A and L share a sorted term list, so do B1 and B2).
+// Width chosen by a cost model in mixed additions: one per (scalar, window) term plus ~7 per bucket (its two additions of
+// the reduction, the lost first slot of its run, its share of the fix-ups), over the widths that end on a window boundary
+// (15, 14, 13, 12 windows).  Measured (ms per proof, plain key -> table): 32x32 13.4 -> 12.05 at 17 bits (13.15 at 19, 14.0 at
+// 20); 46x46 22.6 -> 19.65 at 17 (21.7 at 19); 128x128 181 -> 171.0 at 20 / 22 for z / h (172.0 at 20 / 20, 172.4 at 22 / 22,
+// 176.4 at 19 / 22).  Below 17 bits a bucket run spans more than the four lanes the short fix-up path handles (one resident round
+// of accumulation waves is 2^17 lanes) and everything goes through the long path: 46x46 at 16 bits 27.8 ms, at 15 bits 40 ms.
+// Every query gets a table by default: with the bit-sliced bucket reduction one bucket set of 2^15 / 2^16 buckets is reduced in ~20
+// dependent additions, so even small keys gain (profiles/table_sweep_r3.txt: 4x4 3.5 -> 2.45 ms and 8x8 3.9 -> 3.1 ms at 16 bits, 16x16
+// 5.6 -> 4.7 ms and the PrimeCircuit 5.9 -> 4.9 ms at 17; narrower tables lose: few buckets, each a long dependent chain).  Round 2
+// left queries under 3 * 2^17 terms plain because the reduction of 2^16 buckets then cost a G2 MSM 6 ms.
+static int default_table_bits(size_t n) {
+    if (n < ((size_t)1 << 16)) return 16;
+    int best = 17;
+    double best_cost = 0;
+    for (int c : {17, 19, 20, 22}) {
+        const double cost = (double)n * (254 / c + 1) + 7.0 * (double)((size_t)1 << (c - 1));
+        if (c == 17 || cost < best_cost) { best = c; best_cost = cost; }
+    }
+    return best;
+}
+int zkg16_pk_precompute(zkg16_ctx *ctx, uint64_t pk_handle, int window_bits_z, int window_bits_h, uint64_t *table_bytes) {
+    if (window_bits_z > 24 || window_bits_h > 24 || (window_bits_z > 0 && window_bits_z < 4) || (window_bits_h > 0 && window_bits_h < 4))
+        return ZKG16_ERR_BAD_ARG;
+    ZK_API_BEGIN(ctx)
+    std::unique_lock<std::shared_mutex> keys(ctx->key_rw);      // the key's buffers are replaced: no proof on any lane meanwhile
+    auto pk_ref = ctx->pks.get(pk_handle); PkDev *pk = pk_ref.get();
+    if (!pk) return ZKG16_ERR_BAD_HANDLE;
+    if ((window_bits_z >= 0 && pk->tab_c_z) || (window_bits_h >= 0 && pk->tab_c_h)) return ZKG16_ERR_BAD_ARG;      // already built
+    const size_t nz = pk->z_hi - pk->z_lo, nzs = nz + 3, nh = pk->h_hi - pk->h_lo;
+    const int cz = window_bits_z < 0 || (nz == 0 && !pk->blinding) ? 0 : window_bits_z ? window_bits_z : default_table_bits(nzs);
+    const int ch = window_bits_h < 0 || nh == 0 ? 0 : window_bits_h ? window_bits_h : default_table_bits(nh);
+    if ((cz && nzs * (size_t)(254 / cz + 1) >= ((size_t)1 << 31)) || (ch && nh * (size_t)(254 / ch + 1) >= ((size_t)1 << 31))) return ZKG16_ERR_BAD_ARG;
+    uint64_t added = 0;
+    if (cz) {
+        DevBuf a = msm_tables_build_g1(ctx, pk->a, nzs, cz);
+        DevBuf l = msm_tables_build_g1(ctx, pk->l, nzs, cz);
+        DevBuf b1 = msm_tables_build_g1(ctx, pk->b1, nzs, cz);
+        DevBuf b2 = msm_tables_build_g2(ctx, pk->b2, nzs, cz);
+        pk->a = std::move(a); pk->l = std::move(l); pk->b1 = std::move(b1); pk->b2 = std::move(b2);      // all four or none
+        pk->tab_c_z = cz;
+        added += (uint64_t)(254 / cz) * nzs * (3 * sizeof(G1AffineU) + sizeof(G2AffineU));
+    }
+    if (ch) {
+        pk->h = msm_tables_build_g1(ctx, pk->h, nh, ch);
+        pk->tab_c_h = ch;
+        added += (uint64_t)(254 / ch) * nh * sizeof(G1AffineU);
+    }
+    if (table_bytes) *table_bytes = added;
+    ZK_API_END(ctx)
+}
+
+int zkg16_pk_table_bits(zkg16_ctx *ctx, uint64_t pk_handle, int *window_bits_z, int *window_bits_h) {
+    ZK_API_BEGIN(ctx)
+    auto pk_ref = ctx->pks.get(pk_handle); PkDev *pk = pk_ref.get();
+    if (!pk) return ZKG16_ERR_BAD_HANDLE;
+    if (window_bits_z) *window_bits_z = pk->tab_c_z;
+    if (window_bits_h) *window_bits_h = pk->tab_c_h;
+    ZK_API_END(ctx)
+}
+
+void zkg16_pk_free(zkg16_ctx *ctx, uint64_t h) {
+    if (!ctx) return;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    (void)hipSetDevice(ctx->device);
+    ctx->pks.erase(h);
+}
+
+int zkg16_r1cs_load(zkg16_ctx *ctx,
+                    const uint64_t *a_row_ptr, const uint32_t *a_col, const uint64_t *a_coeff,
+                    const uint64_t *b_row_ptr, const uint32_t *b_col, const uint64_t *b_coeff,
+                    const uint64_t *c_row_ptr, const uint32_t *c_col, const uint64_t *c_coeff,
+                    size_t num_instance, size_t num_constraints, size_t num_variables, uint64_t *r1cs_handle) {
+    ZK_API_BEGIN(ctx)
+    const uint64_t *rp[3] = {a_row_ptr, b_row_ptr, c_row_ptr};
+    const uint32_t *col[3] = {a_col, b_col, c_col};
+    const uint64_t *cf[3] = {a_coeff, b_coeff, c_coeff};
+    int rc = load_r1cs(ctx, rp, col, cf, num_instance, num_constraints, num_variables, r1cs_handle);
+    if (rc) return rc;
+    ZK_API_END(ctx)
+}
+
+// A synthesized circuit (zkg16_circuit_*) loaded straight onto the device: the handles zkg16_r1cs_load / zkg16_witness_load would
+// return for zkg16_circuit_export's arrays, without those arrays crossing the ABI.  The arrays are written into pinned staging memory
+// the ctx keeps (grown on demand): a caller that exported into fresh buffers per request paid for 65 MB of allocation, page faults
+// and unmapping around every PrimeCircuit request — and the unmapping slowed the NEXT synthesis from 18 to 45-60 ms on the GPU box.
+int zkg16_circuit_load(zkg16_ctx *ctx, const zkg16_circuit *c, uint64_t *r1cs_handle, uint64_t *witness_handle) {
+    if (!c || !r1cs_handle || !witness_handle) return ZKG16_ERR_BAD_ARG;
+    size_t ni = 0, nw = 0, nc = 0, nnz[3] = {0, 0, 0};
+    if (zkg16_circuit_dims(c, &ni, &nw, &nc, nnz) != ZKG16_OK) return ZKG16_ERR_BAD_ARG;
+    ZK_API_BEGIN(ctx)
+    zkg16_ctx *root = ctx->root ? ctx->root : ctx;
+    // layout of the staging block: 3 row-pointer arrays, 3 column arrays, 3 coefficient arrays, the assignment; 64-byte aligned
+    size_t off[10], total = 0;
+    auto place = [&](int i, size_t bytes) { off[i] = total; total += (bytes + 63) & ~(size_t)63; };
+    for (int m = 0; m < 3; m++) place(m, (nc + 1) * sizeof(uint64_t));
+    for (int m = 0; m < 3; m++) place(3 + m, (nnz[m] ? nnz[m] : 1) * sizeof(uint32_t));
+    for (int m = 0; m < 3; m++) place(6 + m, (nnz[m] ? nnz[m] : 1) * sizeof(Fr));
+    place(9, (ni + nw) * sizeof(Fr));
+    if (root->circuit_stage_bytes < total) {
+        if (root->circuit_stage) (void)hipHostFree(root->circuit_stage);
+        root->circuit_stage = nullptr;
+        root->circuit_stage_bytes = 0;
+        ZK_HIP(hipHostMalloc(&root->circuit_stage, total + total / 8, hipHostMallocDefault));
+        root->circuit_stage_bytes = total + total / 8;
+    }
+    uint8_t *base = static_cast<uint8_t *>(root->circuit_stage);
+    uint64_t *rp[3], *cf[3], *z = reinterpret_cast<uint64_t *>(base + off[9]);
+    uint32_t *col[3];
+    for (int m = 0; m < 3; m++) {
+        rp[m] = reinterpret_cast<uint64_t *>(base + off[m]);
+        col[m] = reinterpret_cast<uint32_t *>(base + off[3 + m]);
+        cf[m] = reinterpret_cast<uint64_t *>(base + off[6 + m]);
+    }
+    if (zkg16_circuit_export(c, rp, col, cf, z) != ZKG16_OK) return ZKG16_ERR_BAD_ARG;
+    const uint64_t *crp[3] = {rp[0], rp[1], rp[2]}, *ccf[3] = {cf[0], cf[1], cf[2]};
+    const uint32_t *ccol[3] = {col[0], col[1], col[2]};
+    auto w = std::make_unique<WitnessDev>();
+    w->n = ni + nw;
+    w->z.alloc(w->n * sizeof(Fr));
+    ZK_HIP(hipMemcpyAsync(w->z.p, z, w->n * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
+    const int rc = load_r1cs(ctx, crp, ccol, ccf, ni, nc, ni + nw, r1cs_handle);      // synchronises the stream: the staging block is free again
+    if (rc) return rc;
+    *witness_handle = ctx->next_handle++;
+    ctx->wits.put(*witness_handle, std::move(w));
+    ZK_API_END(ctx)
+}
+
+// The MatrixCircuit's R1CS of size n written on the device (matrix_r1cs.hip): a handle as zkg16_r1cs_load would return for the
+// arrays of zkg16_circuit_matrix + zkg16_circuit_export, without synthesising or uploading them.
+int zkg16_r1cs_matrix(zkg16_ctx *ctx, size_t n, uint64_t *r1cs_handle) {
+    if (!r1cs_handle || n < 2 || n > 1024) return ZKG16_ERR_BAD_ARG;
+    ZK_API_BEGIN(ctx)
+    int st = ZKG16_OK;
+    std::shared_ptr<R1csDev> r = matrix_r1cs_on_device(ctx, n, &st);
+    if (!r) return st;
+    *r1cs_handle = ctx->next_handle++;
+    ctx->r1cs.put(*r1cs_handle, std::move(r));
+    ZK_API_END(ctx)
+}
+
+// The PrimeCircuit of candidate (x, j) on the device (prime_device.hip): handles as zkg16_r1cs_load / zkg16_witness_load would return
+// for the arrays of zkg16_circuit_prime + zkg16_circuit_export, without synthesising or uploading them.  The template is uploaded on
+// the first call under ctx->mu (held by every entry here) and stays resident until zkg16_destroy.
+int zkg16_r1cs_prime(zkg16_ctx *ctx, uint64_t x, uint64_t j, uint64_t *r1cs_handle) {
+    if (!r1cs_handle) return ZKG16_ERR_BAD_ARG;
+    ZK_API_BEGIN(ctx)
+    int st = ZKG16_OK;
+    std::shared_ptr<R1csDev> r = prime_r1cs_on_device(ctx, x, j, &st);
+    if (!r) return st;
+    *r1cs_handle = ctx->next_handle++;
+    ctx->r1cs.put(*r1cs_handle, std::move(r));
+    ZK_API_END(ctx)
+}
+int zkg16_witness_prime(zkg16_ctx *ctx, uint64_t x, uint64_t j, uint64_t *witness_handle) {
+    if (!witness_handle) return ZKG16_ERR_BAD_ARG;
+    ZK_API_BEGIN(ctx)
+    int st = ZKG16_OK;
+    std::shared_ptr<WitnessDev> w = prime_witness_on_device(ctx, x, j, &st);
+    if (!w) return st;
+    *witness_handle = ctx->next_handle++;
+    ctx->wits.put(*witness_handle, std::move(w));
+    ZK_API_END(ctx)
+}
+
+// The arrays behind an r1cs handle, copied back (tests compare the device-written MatrixCircuit with the host synthesis).  Each
+// pointer may be null; sizes as at load (num_constraints + 1 row pointers, nnz columns / coefficients per matrix).
+int zkg16_r1cs_read(zkg16_ctx *ctx, uint64_t r1cs_handle, uint64_t *const row_ptr[3], uint32_t *const col[3], uint64_t *const coeff[3],
+                    size_t *num_instance, size_t *num_constraints, size_t *num_variables, size_t nnz[3]) {
+    ZK_API_BEGIN(ctx)
+    auto rc_ref = ctx->r1cs.get(r1cs_handle); R1csDev *rc = rc_ref.get();
+    if (!rc) return ZKG16_ERR_BAD_HANDLE;
+    if (num_instance) *num_instance = rc->num_instance;
+    if (num_constraints) *num_constraints = rc->num_constraints;
+    if (num_variables) *num_variables = rc->num_variables;
+    for (int m = 0; m < 3; m++) {
+        if (nnz) nnz[m] = rc->nnz[m];
+        if (row_ptr && row_ptr[m]) ZK_HIP(hipMemcpyAsync(row_ptr[m], rc->rp[m].p, (rc->num_constraints + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+        if (col && col[m] && rc->nnz[m]) ZK_HIP(hipMemcpyAsync(col[m], rc->col[m].p, rc->nnz[m] * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        if (coeff && coeff[m] && rc->nnz[m]) ZK_HIP(hipMemcpyAsync(coeff[m], rc->cf[m].p, rc->nnz[m] * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    ZK_HIP(hipStreamSynchronize(ctx->stream));
+    ZK_API_END(ctx)
+}
+
+void zkg16_r1cs_free(zkg16_ctx *ctx, uint64_t h) {
+    if (!ctx) return;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    (void)hipSetDevice(ctx->device);
+    ctx->r1cs.erase(h);
+}
+
+int zkg16_witness_load(zkg16_ctx *ctx, const uint64_t *full_assignment, size_t n_assign, uint64_t *witness_handle) {
+    if (!full_assignment || !witness_handle || n_assign == 0) return ZKG16_ERR_BAD_ARG;
+    ZK_API_BEGIN(ctx)
+    auto w = std::make_unique<WitnessDev>();
+    w->n = n_assign;
+    w->z.alloc(n_assign * sizeof(Fr));
+    ZK_HIP(hipMemcpyAsync(w->z.p, full_assignment, n_assign * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
+    ZK_HIP(hipStreamSynchronize(ctx->stream));
+    *witness_handle = ctx->next_handle++;
+    ctx->wits.put(*witness_handle, std::move(w));
+    ZK_API_END(ctx)
+}
+
+// The assignment behind a witness handle, copied back to the host (tests compare the device-built MatrixCircuit assignment of
+// zkg16_witness_matrix with the host builder's byte for byte).
+int zkg16_witness_read(zkg16_ctx *ctx, uint64_t witness_handle, uint64_t *out, size_t n_assign) {
+    if (!out) return ZKG16_ERR_BAD_ARG;
+    ZK_API_BEGIN(ctx)
+    auto w_ref = ctx->wits.get(witness_handle); WitnessDev *w = w_ref.get();
+    if (!w) return ZKG16_ERR_BAD_HANDLE;
+    if (w->n != n_assign) return ZKG16_ERR_BAD_ARG;
+    ZK_HIP(hipMemcpyAsync(out, w->z.p, n_assign * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
+    ZK_HIP(hipStreamSynchronize(ctx->stream));
+    ZK_API_END(ctx)
+}
+
+void zkg16_witness_free(zkg16_ctx *ctx, uint64_t h) {
+    if (!ctx) return;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    (void)hipSetDevice(ctx->device);
+    ctx->wits.erase(h);
+}
+
+}  // extern "C"

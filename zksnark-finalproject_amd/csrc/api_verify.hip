@@ -1,0 +1,411 @@
+// libzkg16 C ABI, part 6 of 6 (api.hip): batched verification.
+#include "api_internal.hpp"
+#include "verify_batch.hpp"
+
+using namespace zk;
+
+// ------------------------------------------------------------------------------------------------ batched verification
+// (verify_batch.hpp.)  The per-proof work in kernels on a lane of the ctx: the three membership launches and the Miller launch of a
+// pass are independent and run on four of the lane's streams at once; the host needs the membership verdicts first (they decide
+// which C_k enter the MSM), so the MSM of sum rho_k C_k runs on the lane's main stream while the Miller kernel is still busy.
+// From wire bytes (zkg16_verify_batch_wire) the three decompress launches of a pass fill the device proof array first, B on the main
+// stream beside A and C on two others; everything after reads that array as if the host had uploaded it.
+namespace {
+const size_t VB_PASS = 65536;          // pairs / points per launch: one wave per SIMD of a 256-CU device
+struct VbEvents {
+    hipEvent_t ev[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    VbEvents() { for (auto &e : ev) ZK_HIP(hipEventCreate(&e)); }
+    ~VbEvents() { for (auto &e : ev) if (e) (void)hipEventDestroy(e); }
+    VbEvents(const VbEvents &) = delete;
+    VbEvents &operator=(const VbEvents &) = delete;
+};
+float vb_elapsed(hipEvent_t a, hipEvent_t b) {
+    float ms = 0;
+    ZK_HIP(hipEventElapsedTime(&ms, a, b));
+    return ms;
+}
+void vb_publish(zkg16_ctx *root, const float tm[V_COUNT]) {
+    std::lock_guard<std::mutex> lk(root->lane_mu);
+    memcpy(root->vb_timings, tm, sizeof root->vb_timings);
+}
+// A batch below the entry point's threshold: form(tm) answers it on the host (vb_host, after decoding if need be); its wall time
+// since t_all and the host-form mark are published with whatever slots form filled in.
+template <class Form>
+int vb_answer_on_host(zkg16_ctx *ctx, double t_all, Form &&form) {
+    float tm[V_COUNT] = {0};
+    try {
+        form(tm);
+    } catch (const std::bad_alloc &) {
+        return ZKG16_ERR_OOM;
+    }
+    tm[V_TOTAL] = (float)(now_ms() - t_all);
+    tm[V_HOST_FORM] = 1;
+    vb_publish(ctx, tm);
+    return ZKG16_OK;
+}
+// The three membership launches of one chunk of n proofs (48 limbs and 3 flags each; verdicts m3, 3 a proof): A on the main
+// stream, C and B beside it.
+void vb_membership_chunk(hipStream_t s_main, hipStream_t s_c, hipStream_t s_b, const uint64_t *pts, const uint8_t *fl, size_t n, const VbEndo &en,
+                         uint8_t *m3) {
+    vb_membership_launch(s_main, 1, pts, 48, fl, 3, n, en, m3, 3);
+    vb_membership_launch(s_c, 1, pts + 36, 48, fl + 2, 3, n, en, m3 + 2, 3);
+    vb_membership_launch(s_b, 2, pts + 12, 48, fl + 1, 3, n, en, m3 + 1, 3);
+}
+
+// The per-proof pass on the lane's main stream: the proofs idx[0 .. n) (null: 0 .. n - 1) of the k x 48 limbs / k x 3 flags already on
+// the device, each with its public inputs (pub(j): the (num_instance - 1) x 4 Montgomery limbs of the proof at position j), in
+// launches of VB_PASS.  The key is converted and uploaded once per call.  Returns the kernels' time in ms (device events)
+float vb_each_pass(zkg16_ctx *ctx, const VbKey &key, const uint64_t *d_proofs, const uint8_t *d_inf, const uint32_t *idx, size_t n,
+                   const std::function<const uint64_t *(size_t)> &pub, uint8_t *verdict) {
+    if (!n) return 0;
+    hipStream_t st = ctx->stream;
+    const size_t ni = key.num_instance, per = 4 * (ni - 1), pass = std::min(n, VB_PASS);
+    std::vector<uint32_t> words(vb_each_key_count(ni));
+    vb_each_key_words(key, words.data());
+    std::vector<uint64_t> z(std::max<size_t>(n * per, 1));
+    for (size_t j = 0; j < n && per; j++) vb_scalars_canonical(pub(j), ni - 1, z.data() + per * j);
+    DevBuf d_key(words.size() * 4), d_z(z.size() * 8), d_idx(idx ? n * 4 : 0), d_scratch(vb_each_scratch_bytes(pass)), d_verdict(n);
+    VbEvents evs;
+    ZK_HIP(hipMemcpyAsync(d_key.p, words.data(), words.size() * 4, hipMemcpyHostToDevice, st));
+    ZK_HIP(hipMemcpyAsync(d_z.p, z.data(), z.size() * 8, hipMemcpyHostToDevice, st));
+    if (idx) ZK_HIP(hipMemcpyAsync(d_idx.p, idx, n * 4, hipMemcpyHostToDevice, st));
+    ZK_HIP(hipEventRecord(evs.ev[0], st));
+    for (size_t off = 0; off < n; off += VB_PASS)
+        vb_each_launch(st, d_key.as<uint32_t>(), ni, idx ? d_idx.as<uint32_t>() + off : nullptr, std::min(VB_PASS, n - off), idx ? d_proofs : d_proofs + 48 * off,
+                       idx ? d_inf : d_inf + 3 * off, d_z.as<uint64_t>() + per * off, d_scratch.p, d_verdict.as<uint8_t>() + off);
+    ZK_HIP(hipEventRecord(evs.ev[1], st));
+    ZK_HIP(hipMemcpyAsync(verdict, d_verdict.p, n, hipMemcpyDeviceToHost, st));
+    ZK_HIP(hipStreamSynchronize(st));
+    return vb_elapsed(evs.ev[0], evs.ev[1]);
+}
+
+// The device form of both entry points.  wire == null: b.proofs / b.inf are the caller's limbs and flags.  wire != null (k x 192
+// bytes): b.proofs / b.inf are null; the proofs are decoded on the device, unvalidated, and the decoded limbs and flags come back
+// once for the MSM's bases and vb_decide.  A proof with a point that did not decode is left out like one that fails membership;
+// decode_status (nullable, k x 3): the decode kernel's statuses, 5 where a decoded point failed membership.
+int vb_device(zkg16_ctx *ctx, const VbKey &key, VbBatch b, const uint8_t *wire, int *ok, uint8_t *ok_each, uint8_t *decode_status, double t_all) {
+    const size_t k = b.k;
+    float tm[V_COUNT] = {0};
+    ZK_LANE_BEGIN(ctx)
+    hipStream_t s_main = ctx->stream, s_mil = ctx->wm_stream, s_c = ctx->slots[1].stream, s_b = ctx->slots[2].stream;
+    VbEvents evs;
+    hipEvent_t e_up = evs.ev[0], e_a = evs.ev[1], e_c = evs.ev[2], e_b = evs.ev[3], e_mil = evs.ev[4], e_p0 = evs.ev[5], e_p1 = evs.ev[6], e_m0 = evs.ev[7],
+               e_d0 = evs.ev[8], e_d1 = evs.ev[9];
+    const size_t half = (k + 1) / 2;
+    DevBuf d_proofs(k * 48 * 8), d_inf(3 * k), d_rho(k * 16), d_mem3(3 * k), d_live(k), d_f(k * 72 * 8), d_tmp(2 * half * 72 * 8);
+    DevBuf d_wire(wire ? k * 192 : 0), d_st(wire ? 3 * k : 0);
+    const VbEndo en = vb_endo();
+    std::vector<uint64_t> dec_proofs;
+    std::vector<uint8_t> dec_inf, dec_st;
+    if (wire) {
+        upload_h2d(ctx, d_wire.p, wire, k * 192);
+        ZK_HIP(hipMemcpyAsync(d_rho.p, b.rho, k * 16, hipMemcpyHostToDevice, s_main));
+        ZK_HIP(hipEventRecord(e_d0, s_main));
+        for (hipStream_t st : {s_c, s_b}) ZK_HIP(hipStreamWaitEvent(st, e_d0, 0));
+        for (size_t off = 0; off < k; off += VB_PASS) {
+            const size_t n = std::min(VB_PASS, k - off);
+            const uint8_t *by = d_wire.as<uint8_t>() + 192 * off;
+            uint64_t *pts = d_proofs.as<uint64_t>() + 48 * off;
+            uint8_t *fl = d_inf.as<uint8_t>() + 3 * off, *st3 = d_st.as<uint8_t>() + 3 * off;
+            // B (two powers and an inversion) on the main stream, A and C (one power each) beside it
+            vb_decompress_launch(s_main, 2, by + 48, 192, n, 0, en, pts + 12, 48, fl + 1, 3, st3 + 1, 3);
+            vb_decompress_launch(s_c, 1, by, 192, n, 0, en, pts, 48, fl, 3, st3, 3);
+            vb_decompress_launch(s_b, 1, by + 144, 192, n, 0, en, pts + 36, 48, fl + 2, 3, st3 + 2, 3);
+        }
+        ZK_HIP(hipEventRecord(e_c, s_c));
+        ZK_HIP(hipEventRecord(e_b, s_b));
+        ZK_HIP(hipStreamWaitEvent(s_main, e_c, 0));
+        ZK_HIP(hipStreamWaitEvent(s_main, e_b, 0));
+        ZK_HIP(hipEventRecord(e_d1, s_main));
+        // the decoded proofs travel to the host behind the kernels below; they are first read after the membership verdicts
+        dec_proofs.resize(48 * k);
+        dec_inf.resize(3 * k);
+        dec_st.resize(3 * k);
+        b.proofs = dec_proofs.data();
+        b.inf = dec_inf.data();
+    } else {
+        upload_h2d(ctx, d_proofs.p, b.proofs, k * 48 * 8);
+        ZK_HIP(hipMemcpyAsync(d_inf.p, b.inf, 3 * k, hipMemcpyHostToDevice, s_main));
+        ZK_HIP(hipMemcpyAsync(d_rho.p, b.rho, k * 16, hipMemcpyHostToDevice, s_main));
+    }
+    ZK_HIP(hipEventRecord(e_up, s_main));
+    for (hipStream_t st : {s_mil, s_c, s_b}) ZK_HIP(hipStreamWaitEvent(st, e_up, 0));
+    ZK_HIP(hipEventRecord(e_m0, s_mil));
+    for (size_t off = 0; off < k; off += VB_PASS) {
+        const size_t n = std::min(VB_PASS, k - off);
+        const uint64_t *pts = d_proofs.as<uint64_t>() + 48 * off;
+        const uint8_t *fl = d_inf.as<uint8_t>() + 3 * off;
+        uint8_t *m3 = d_mem3.as<uint8_t>() + 3 * off;
+        // membership first: where two of these streams share a hardware queue, the short kernels must not sit behind the long one
+        vb_membership_chunk(s_main, s_c, s_b, pts, fl, n, en, m3);
+        vb_miller_launch(s_mil, pts, 48, fl, pts + 12, 48, fl + 1, 3, d_rho.as<uint64_t>() + 2 * off, n, d_f.as<uint64_t>() + 72 * off);
+    }
+    const double t_launched = now_ms();
+    ZK_HIP(hipEventRecord(e_a, s_main));
+    ZK_HIP(hipEventRecord(e_c, s_c));
+    ZK_HIP(hipEventRecord(e_b, s_b));
+    ZK_HIP(hipEventRecord(e_mil, s_mil));
+    ZK_HIP(hipStreamWaitEvent(s_main, e_c, 0));
+    ZK_HIP(hipStreamWaitEvent(s_main, e_b, 0));
+    std::vector<uint8_t> mem3(3 * k), member(k);
+    ZK_HIP(hipMemcpyAsync(mem3.data(), d_mem3.p, 3 * k, hipMemcpyDeviceToHost, s_main));
+    if (wire) {
+        ZK_HIP(hipMemcpyAsync(dec_proofs.data(), d_proofs.p, k * 48 * 8, hipMemcpyDeviceToHost, s_main));
+        ZK_HIP(hipMemcpyAsync(dec_inf.data(), d_inf.p, 3 * k, hipMemcpyDeviceToHost, s_main));
+        ZK_HIP(hipMemcpyAsync(dec_st.data(), d_st.p, 3 * k, hipMemcpyDeviceToHost, s_main));
+    }
+    ZK_HIP(hipStreamSynchronize(s_main));
+    // host clock, launch to verdicts on the host (what the MSM below waits for), not kernel time: measured, it equals the Miller
+    // kernel's time — the verdicts do not reach the host before that kernel ends
+    tm[V_MEMBERSHIP] = (float)(now_ms() - t_launched);
+    if (wire) tm[V_DECODE] = vb_elapsed(e_d0, e_d1);
+    size_t n_live = 0;
+    for (size_t i = 0; i < k; i++) {
+        bool good = mem3[3 * i] && mem3[3 * i + 1] && mem3[3 * i + 2];
+        // an undecodable point left zero limbs behind, which no curve holds; the status decides all the same
+        if (wire) good = good && !dec_st[3 * i] && !dec_st[3 * i + 1] && !dec_st[3 * i + 2];
+        n_live += member[i] = good ? 1 : 0;
+    }
+    if (wire && decode_status)
+        for (size_t j = 0; j < 3 * k; j++) decode_status[j] = dec_st[j] ? dec_st[j] : (mem3[j] ? 0 : 5);
+    const uint64_t *proofs = b.proofs, *rho = b.rho;
+    const uint8_t *inf = b.inf;
+    // sum rho_k C_k over the member proofs: the ctx's G1 MSM, beside the Miller kernel
+    uint64_t sum_c[12] = {0};
+    uint8_t sum_c_inf = 1;
+    if (n_live) {
+        const double t0 = now_ms();
+        std::vector<uint64_t> bases(12 * k), sc(4 * k, 0);
+        std::vector<uint8_t> binf(k);
+        for (size_t i = 0; i < k; i++) {
+            memcpy(&bases[12 * i], proofs + 48 * i + 36, 96);
+            binf[i] = inf[3 * i + 2] || !member[i] ? 1 : 0;
+            if (member[i]) { sc[4 * i] = rho[2 * i]; sc[4 * i + 1] = rho[2 * i + 1]; }
+        }
+        DevBuf d_bases(k * sizeof(G1AffineU)), d_sc(k * sizeof(Fr));
+        upload_points<G1Affine>(ctx, d_bases.as<G1AffineU>(), bases.data(), binf.data(), 0, k);
+        ZK_HIP(hipMemcpyAsync(d_sc.p, sc.data(), k * sizeof(Fr), hipMemcpyHostToDevice, s_main));
+        ZK_HIP(hipStreamSynchronize(s_main));
+        MsmPlan plan;
+        msm_plan_build(ctx, ctx->ws_h, d_sc.as<Fr>(), k, plan);
+        const G1XYZZ total = msm_g1_exec(ctx, ctx->ws_h, plan, d_bases.as<G1AffineU>(), "verify_batch_msm");
+        point_to_abi(xyzz_to_affine(total), sum_c, &sum_c_inf);
+        tm[V_MSM] = (float)(now_ms() - t0);
+    }
+    // the product of the member proofs' Miller values
+    ZK_HIP(hipMemcpyAsync(d_live.p, member.data(), k, hipMemcpyHostToDevice, s_main));
+    ZK_HIP(hipStreamWaitEvent(s_main, e_mil, 0));
+    ZK_HIP(hipEventRecord(e_p0, s_main));
+    const uint64_t *d_prod = vb_product_launch(s_main, d_f.as<uint64_t>(), d_live.as<uint8_t>(), k, d_tmp.as<uint64_t>());
+    ZK_HIP(hipEventRecord(e_p1, s_main));
+    uint64_t prod[72];
+    ZK_HIP(hipMemcpyAsync(prod, d_prod, sizeof prod, hipMemcpyDeviceToHost, s_main));
+    ZK_HIP(hipStreamSynchronize(s_main));
+    tm[V_MILLER] = vb_elapsed(e_m0, e_mil);      // both on the Miller stream
+    tm[V_PRODUCT] = vb_elapsed(e_p0, e_p1);
+    // the K Miller values leave the device only when the batch equation failed and the caller wants to know where
+    std::vector<uint64_t> miller;
+    // ... and when bisecting has used its budget of range tests, the proofs it left undecided stay here for the per-proof pass
+    VbEach each;
+    each.after = (size_t)ctx->opt.verify_each_after;
+    each.decide = [&](const uint32_t *idx, size_t n, uint8_t *verdict) {
+        const size_t per = 4 * (key.num_instance - 1);
+        tm[V_EACH] += vb_each_pass(ctx, key, d_proofs.as<uint64_t>(), d_inf.as<uint8_t>(), idx, n, [&](size_t j) { return b.public_inputs + per * idx[j]; }, verdict);
+    };
+    vb_decide(key, b, member.data(), [&]() -> const uint64_t * {
+        miller.resize(72 * k);
+        ZK_HIP(hipMemcpy(miller.data(), d_f.p, k * 72 * 8, hipMemcpyDeviceToHost));
+        return miller.data();
+    }, prod, sum_c, &sum_c_inf, 0, ok, ok_each, tm + V_HOST, &each);
+    tm[V_RANGE_TESTS] = (float)each.range_tests;
+    tm[V_TOTAL] = (float)(now_ms() - t_all);
+    vb_publish(root, tm);
+    ZK_LANE_END(ctx)
+}
+}  // namespace
+
+extern "C" {
+
+int zkg16_verify_batch(zkg16_ctx *ctx, const uint64_t *gamma_abc_g1, size_t num_instance, const uint64_t alpha_beta[72], const uint64_t *gamma_neg_coeffs,
+                       const uint64_t *delta_neg_coeffs, size_t n_coeffs, const uint64_t *public_inputs, const uint64_t *proofs, const uint8_t *inf,
+                       const uint64_t *rho, size_t k, int *ok, uint8_t *ok_each) {
+    if (!ctx) return ZKG16_ERR_BAD_ARG;
+    const VbKey key{gamma_abc_g1, num_instance, alpha_beta, gamma_neg_coeffs, delta_neg_coeffs, n_coeffs};
+    const VbBatch b{public_inputs, proofs, inf, rho, k};
+    const int rc = vb_check_args(key, b, ok);
+    if (rc != ZKG16_OK) return rc;
+    const double t_all = now_ms();
+    if (k < (size_t)ctx->opt.verify_batch_min) return vb_answer_on_host(ctx, t_all, [&](float *) { vb_host(key, b, 0, ok, ok_each); });
+    return vb_device(ctx, key, b, nullptr, ok, ok_each, nullptr, t_all);
+}
+
+int zkg16_verify_batch_wire(zkg16_ctx *ctx, const uint64_t *gamma_abc_g1, size_t num_instance, const uint64_t alpha_beta[72], const uint64_t *gamma_neg_coeffs,
+                            const uint64_t *delta_neg_coeffs, size_t n_coeffs, const uint64_t *public_inputs, const uint8_t *proof_bytes,
+                            const uint64_t *rho, size_t k, int *ok, uint8_t *ok_each, uint8_t *decode_status) {
+    if (!ctx || !proof_bytes) return ZKG16_ERR_BAD_ARG;
+    const VbKey key{gamma_abc_g1, num_instance, alpha_beta, gamma_neg_coeffs, delta_neg_coeffs, n_coeffs};
+    {
+        // the checks of zkg16_verify_batch: the bytes stand in for the limbs and flags that do not exist yet
+        const VbBatch probe{public_inputs, reinterpret_cast<const uint64_t *>(proof_bytes), proof_bytes, rho, k};
+        const int rc = vb_check_args(key, probe, ok);
+        if (rc != ZKG16_OK) return rc;
+    }
+    const double t_all = now_ms();
+    if (k < (size_t)ctx->opt.verify_wire_min)
+        return vb_answer_on_host(ctx, t_all, [&](float *tm) {
+            // status 5 costs the subgroup tests a second time (vb_host makes its own): only for a caller who asks for the statuses
+            std::vector<uint64_t> proofs(48 * k);
+            std::vector<uint8_t> inf(3 * k), st(3 * k);
+            vb_wire_decode_host(proof_bytes, k, decode_status ? 1 : 0, 0, proofs.data(), inf.data(), st.data());
+            tm[V_DECODE] = (float)(now_ms() - t_all);
+            std::vector<uint8_t> dead(k);
+            for (size_t i = 0; i < k; i++) dead[i] = st[3 * i] || st[3 * i + 1] || st[3 * i + 2] ? 1 : 0;
+            const VbBatch b{public_inputs, proofs.data(), inf.data(), rho, k};
+            vb_host(key, b, 0, ok, ok_each, dead.data());
+            if (decode_status) memcpy(decode_status, st.data(), 3 * k);
+        });
+    return vb_device(ctx, key, VbBatch{public_inputs, nullptr, nullptr, rho, k}, proof_bytes, ok, ok_each, decode_status, t_all);
+}
+
+int zkg16_verify_each(zkg16_ctx *ctx, const uint64_t *gamma_abc_g1, size_t num_instance, const uint64_t alpha_beta[72], const uint64_t *gamma_neg_coeffs,
+                      const uint64_t *delta_neg_coeffs, size_t n_coeffs, const uint64_t *public_inputs, const uint64_t *proofs, const uint8_t *inf, size_t k,
+                      uint8_t *ok_each) {
+    if (!ctx || !ok_each) return ZKG16_ERR_BAD_ARG;
+    const VbKey key{gamma_abc_g1, num_instance, alpha_beta, gamma_neg_coeffs, delta_neg_coeffs, n_coeffs};
+    {
+        // the checks of zkg16_verify_batch; there are no multipliers, so one non-zero pair stands in for them
+        const uint64_t some_rho[2] = {1, 0};
+        int ok_probe = 0;
+        const VbBatch probe{public_inputs, proofs, inf, some_rho, 1};
+        if (k == 0) return ZKG16_ERR_BAD_ARG;
+        const int rc = vb_check_args(key, probe, &ok_probe);
+        if (rc != ZKG16_OK) return rc;
+    }
+    ZK_LANE_BEGIN(ctx)
+    hipStream_t s_main = ctx->stream, s_c = ctx->slots[1].stream, s_b = ctx->slots[2].stream;
+    // zkg16_verify_prepared reads all-zero limbs as the point at infinity whatever the flag says: the same here
+    std::vector<uint8_t> fl(3 * k);
+    for (size_t i = 0; i < k; i++) {
+        const uint64_t *pr = proofs + 48 * i;
+        const size_t at[4] = {0, 12, 36, 48};
+        for (int j = 0; j < 3; j++) {
+            uint64_t any = 0;
+            for (size_t t = at[j]; t < at[j + 1]; t++) any |= pr[t];
+            fl[3 * i + j] = inf[3 * i + j] || !any ? 1 : 0;
+        }
+    }
+    VbEvents evs;
+    DevBuf d_proofs(k * 48 * 8), d_inf(3 * k), d_mem3(3 * k);
+    const VbEndo en = vb_endo();
+    upload_h2d(ctx, d_proofs.p, proofs, k * 48 * 8);
+    ZK_HIP(hipMemcpyAsync(d_inf.p, fl.data(), 3 * k, hipMemcpyHostToDevice, s_main));
+    ZK_HIP(hipEventRecord(evs.ev[0], s_main));
+    for (hipStream_t st : {s_c, s_b}) ZK_HIP(hipStreamWaitEvent(st, evs.ev[0], 0));
+    for (size_t off = 0; off < k; off += VB_PASS) {
+        const size_t n = std::min(VB_PASS, k - off);
+        const uint64_t *pts = d_proofs.as<uint64_t>() + 48 * off;
+        const uint8_t *f3 = d_inf.as<uint8_t>() + 3 * off;
+        uint8_t *m3 = d_mem3.as<uint8_t>() + 3 * off;
+        vb_membership_chunk(s_main, s_c, s_b, pts, f3, n, en, m3);
+    }
+    ZK_HIP(hipEventRecord(evs.ev[1], s_c));
+    ZK_HIP(hipEventRecord(evs.ev[2], s_b));
+    ZK_HIP(hipStreamWaitEvent(s_main, evs.ev[1], 0));
+    ZK_HIP(hipStreamWaitEvent(s_main, evs.ev[2], 0));
+    std::vector<uint8_t> mem3(3 * k);
+    ZK_HIP(hipMemcpyAsync(mem3.data(), d_mem3.p, 3 * k, hipMemcpyDeviceToHost, s_main));
+    ZK_HIP(hipStreamSynchronize(s_main));
+    // proofs that failed membership are never listed
+    std::vector<uint32_t> idx;
+    for (size_t i = 0; i < k; i++)
+        if (mem3[3 * i] && mem3[3 * i + 1] && mem3[3 * i + 2]) idx.push_back((uint32_t)i);
+    std::vector<uint8_t> verdict(idx.size());
+    const size_t per = 4 * (num_instance - 1);
+    (void)vb_each_pass(ctx, key, d_proofs.as<uint64_t>(), d_inf.as<uint8_t>(), idx.size() == k ? nullptr : idx.data(), idx.size(),
+                       [&](size_t j) { return public_inputs + per * idx[j]; }, verdict.data());
+    memset(ok_each, 0, k);
+    for (size_t j = 0; j < idx.size(); j++) ok_each[idx[j]] = verdict[j] ? 1 : 0;
+    ZK_LANE_END(ctx)
+}
+
+int zkg16_final_exp_batch(zkg16_ctx *ctx, const uint64_t *f, size_t n, uint64_t *out) {
+    if (!ctx || ((!f || !out) && n)) return ZKG16_ERR_BAD_ARG;
+    if (!n) return ZKG16_OK;
+    ZK_LANE_BEGIN(ctx)
+    DevBuf d_f(n * 576);
+    upload_h2d(ctx, d_f.p, f, n * 576);
+    for (size_t off = 0; off < n; off += VB_PASS)
+        vb_final_exp_launch(ctx->stream, d_f.as<uint64_t>() + 72 * off, std::min(VB_PASS, n - off), d_f.as<uint64_t>() + 72 * off);
+    ZK_HIP(hipMemcpyAsync(out, d_f.p, n * 576, hipMemcpyDeviceToHost, ctx->stream));
+    ZK_HIP(hipStreamSynchronize(ctx->stream));
+    ZK_LANE_END(ctx)
+}
+
+int zkg16_points_decompress_batch(zkg16_ctx *ctx, int group, const uint8_t *bytes, size_t n, uint64_t *out, uint8_t *inf, int validate, int *status) {
+    if (!ctx || (group != 1 && group != 2) || ((!bytes || !out || !inf) && n)) return ZKG16_ERR_BAD_ARG;
+    if (!n) return ZKG16_OK;
+    ZK_LANE_BEGIN(ctx)
+    const size_t w = group == 1 ? 12 : 24, nb = group == 1 ? 48 : 96;
+    DevBuf d_b(n * nb), d_p(n * w * 8), d_i(n), d_s(n);
+    upload_h2d(ctx, d_b.p, bytes, n * nb);
+    const VbEndo en = vb_endo();
+    for (size_t off = 0; off < n; off += VB_PASS)
+        vb_decompress_launch(ctx->stream, group, d_b.as<uint8_t>() + nb * off, nb, std::min(VB_PASS, n - off), validate, en, d_p.as<uint64_t>() + w * off, w,
+                             d_i.as<uint8_t>() + off, 1, d_s.as<uint8_t>() + off, 1);
+    std::vector<uint8_t> st(n);
+    ZK_HIP(hipMemcpyAsync(out, d_p.p, n * w * 8, hipMemcpyDeviceToHost, ctx->stream));
+    ZK_HIP(hipMemcpyAsync(inf, d_i.p, n, hipMemcpyDeviceToHost, ctx->stream));
+    ZK_HIP(hipMemcpyAsync(st.data(), d_s.p, n, hipMemcpyDeviceToHost, ctx->stream));
+    ZK_HIP(hipStreamSynchronize(ctx->stream));
+    bool any_bad = false;
+    for (size_t i = 0; i < n; i++) {
+        if (status) status[i] = st[i];
+        any_bad = any_bad || st[i];
+    }
+    if (any_bad) return ZKG16_ERR_BAD_ARG;
+    ZK_LANE_END(ctx)
+}
+
+int zkg16_miller_loop_batch(zkg16_ctx *ctx, const uint64_t *g1, const uint8_t *g1_inf, const uint64_t *g2, const uint8_t *g2_inf, size_t n, uint64_t *f_out) {
+    if (!ctx || ((!g1 || !g2 || !f_out) && n)) return ZKG16_ERR_BAD_ARG;
+    if (!n) return ZKG16_OK;
+    ZK_LANE_BEGIN(ctx)
+    DevBuf d_g1(n * 96), d_g2(n * 192), d_i1(n), d_i2(n), d_f(n * 576);
+    upload_h2d(ctx, d_g1.p, g1, n * 96);
+    upload_h2d(ctx, d_g2.p, g2, n * 192);
+    if (g1_inf) ZK_HIP(hipMemcpyAsync(d_i1.p, g1_inf, n, hipMemcpyHostToDevice, ctx->stream));
+    if (g2_inf) ZK_HIP(hipMemcpyAsync(d_i2.p, g2_inf, n, hipMemcpyHostToDevice, ctx->stream));
+    for (size_t off = 0; off < n; off += VB_PASS)
+        vb_miller_launch(ctx->stream, d_g1.as<uint64_t>() + 12 * off, 12, g1_inf ? d_i1.as<uint8_t>() + off : nullptr, d_g2.as<uint64_t>() + 24 * off, 24,
+                         g2_inf ? d_i2.as<uint8_t>() + off : nullptr, 1, nullptr, std::min(VB_PASS, n - off), d_f.as<uint64_t>() + 72 * off);
+    ZK_HIP(hipMemcpyAsync(f_out, d_f.p, n * 576, hipMemcpyDeviceToHost, ctx->stream));
+    ZK_HIP(hipStreamSynchronize(ctx->stream));
+    ZK_LANE_END(ctx)
+}
+
+int zkg16_point_check_batch(zkg16_ctx *ctx, int group, const uint64_t *points, const uint8_t *inf, size_t n, uint8_t *ok_out) {
+    if (!ctx || (group != 1 && group != 2) || ((!points || !ok_out) && n)) return ZKG16_ERR_BAD_ARG;
+    if (!n) return ZKG16_OK;
+    ZK_LANE_BEGIN(ctx)
+    const size_t w = group == 1 ? 12 : 24;
+    DevBuf d_p(n * w * 8), d_i(n), d_ok(n);
+    upload_h2d(ctx, d_p.p, points, n * w * 8);
+    if (inf) ZK_HIP(hipMemcpyAsync(d_i.p, inf, n, hipMemcpyHostToDevice, ctx->stream));
+    const VbEndo en = vb_endo();
+    for (size_t off = 0; off < n; off += VB_PASS)
+        vb_membership_launch(ctx->stream, group, d_p.as<uint64_t>() + w * off, w, inf ? d_i.as<uint8_t>() + off : nullptr, 1, std::min(VB_PASS, n - off), en,
+                             d_ok.as<uint8_t>() + off, 1);
+    ZK_HIP(hipMemcpyAsync(ok_out, d_ok.p, n, hipMemcpyDeviceToHost, ctx->stream));
+    ZK_HIP(hipStreamSynchronize(ctx->stream));
+    ZK_LANE_END(ctx)
+}
+
+int zkg16_verify_batch_timings(zkg16_ctx *ctx, float *ms, int cap) {
+    if (!ctx || !ms || cap < 0) return ZKG16_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lk(ctx->lane_mu);
+    const int n = cap < V_COUNT ? cap : V_COUNT;
+    memcpy(ms, ctx->vb_timings, n * sizeof(float));
+    return n;
+}
+
+}  // extern "C"

@@ -244,6 +244,9 @@ struct MsmWorkspace {       // grown on demand, reused across proofs
     uint32_t last_lanes_g1 = 0; // lanes of the G1 accumulation grid the last plan on this workspace asked for (zkg16_last_acc_waves)
 };
 
+// sizes of zkg16_ctx::timings (22 slots in use, declared with two to spare) and ::vb_timings
+constexpr int PROOF_TIMING_SLOTS = 24, VERIFY_TIMING_SLOTS = 11;
+
 }  // namespace zk
 
 // zkg16_verify_batch answers batches shorter than this on the host: the smallest measured K at which the device form beat the host
@@ -292,7 +295,7 @@ struct zkg16_ctx {
     hipStream_t wm_stream = nullptr;                  // witness map + h-side sort of a proof, concurrent with the z-side MSMs
     zk::MsmSlot slots[5];                             // B2, H, L, A, B1 of one proof
     void *extra_host = nullptr;                       // pinned staging for the r, s, -rs scalars
-    void *stage_host[2] = {nullptr, nullptr};         // pinned staging ring of upload_h2d (api.hip)
+    void *stage_host[2] = {nullptr, nullptr};         // pinned staging ring of upload_h2d (api_keys.hip)
     hipEvent_t stage_done[2] = {nullptr, nullptr};
     zk::DevBuf poly[4];                               // a, b, c, tmp vectors of the witness map
     // zkg16_prove_batch: pinned staging of the 3K extra scalars and the K assignment pointers (the K h vectors live in poly)
@@ -304,47 +307,51 @@ struct zkg16_ctx {
     void *mbatch_host = nullptr;
     size_t mbatch_host_bytes = 0;
     zk::DevBuf mbatch_dev;
-    float timings[24] = {0};
-    bool kernel_timing = false;
-    bool kernel_timing_accumulate_only = false;       // zkg16_kernel_timing(ctx, 2): only the bucket-accumulation launches
+    float timings[zk::PROOF_TIMING_SLOTS] = {0};      // zkg16_last_timings; the slots are named in api_internal.hpp (ProofTiming)
+    // ---- zkg16_set_option / zkg16_kernel_timing: everything a lane copies from its root in one assignment (api.hip: copy_options).
+    // opt_lanes is not here: it lives on the root alone, under lane_mu.
+    struct Options {
+        bool kernel_timing = false;
+        bool kernel_timing_accumulate_only = false;       // zkg16_kernel_timing(ctx, 2): only the bucket-accumulation launches
+        int window_bits = 0;
+        int min_seg = 0;                              // shortest per-lane run of sorted entries in an accumulation (0 = default)
+        int ntt_mode = 1;                             // 1: unsaturated (29-bit limb) butterflies, 0: saturated
+        int reduce_mode = 3;                          // 0 classic (log-depth scan over all chunks), 1 work-efficient two-level, 2 = 1 except the proof's last MSM, 3 (default) = 2 from 16-bit windows on and bit-sliced for single bucket sets <= 2^19, 5 = bit-sliced wherever it applies
+        int b_filter = 0;                             // B-side term list filtered out of the full one: 0 = with window tables (default), 1 = always, 2 = never (second sort)
+        int spmv_dict = 0;                            // 0/1: coefficient dictionary in the SpMV (default); 2: plain kernel
+        int wm_first = -1;                            // see zkg16_set_option "wm_first"
+        int g1_waves = 0;                             // G1 accumulation waves per SIMD in the one resident round (0 = 2)
+        int fixup_aux = 0;                            // 1: fix-up kernels on the MSM's reduction stream
+        int window_bits_h = 0;                        // the H MSM's own plan (it is the last one: its reduction is not hidden)
+        int reduce_chunk = 0;
+        int wm_concurrent = -1;
+        int ntt_radix = 1;                            // 1 (default): the last seven butterfly stages by lane exchanges (ds_bpermute / DPP), 2: every stage through the LDS, 4: two stages per LDS trip
+        int ntt_xcd = 1;                              // NTT tiles in XCD-aware order (ntt.hip: xcd_tile)
+        int acc_debug = 0;                            // timing probes (wrong results): see AccArgs::debug
+        int sort_mode = 0;                            // 0: hand-written bucket scatter (bucket_sort.hip), 1: rocPRIM radix sort
+        int acc_pipeline = 0;                         // bit 0 / 1: G1 / G2 accumulation gathers the next base behind the last (inlined) product (default: neither)
+        int collect_threads = -1;                     // -1: the z-side MSMs' window sums are combined on their own host threads when the key is plain; 1 always; 0 never
+        int fixed_base_bits = 0;                      // setup's fixed-base window width (0 = by batch size; even widths >= 16 are built in two levels)
+        int g2_lazy = 1;                              // G2 accumulation: Fq2 products with one reduction per component, operands parked in LDS (ffu.cuh: fq2u_mul_lazy)
+        int acc_lazy = 1;                             // default G1 / G2 accumulation loops: the mixed addition without the carry passes its results do not need (ec.cuh: xyzz_madd_inline_lc, xyzz_madd_lazy_lc); 0: xyzz_madd_inline / xyzz_madd_lazy
+        int g1_inline = 1;                            // G1 accumulation (plain loop): every field product inlined (ec.cuh: xyzz_madd_inline); 0: products as calls
+        int matrix_parts = 0;                         // zkg16_prove_matrix: gadget slices the assignment arrives in (0 = five growing slices, k = k equal ones, 1 = no overlap)
+        int fuse_pointwise = 1;                       // the point-wise product on the load of the last transform (0: its own pass)
+        int wm_transforms = 6;                        // witness map: 6 (default) = C only inverse-transformed, subtracted on the last store; 7 = arkworks' sequence
+        int batch_max = 0;                            // zkg16_prove_batch / zkg16_prove_matrix_batch: proofs per device pass (0 = as many as fit)
+        int matrix_batch_threads = 0;                 // zkg16_witness_matrix_batch / zkg16_prove_matrix_batch: host threads of the sponge chains (0 = 8)
+        int matrix_batch_grid = 0;                    // cap on either grid dimension of the batched witness kernels (0 = 65535): beyond it they loop
+        int64_t sponge_chains_min = ZKG16_SPONGE_CHAINS_MIN_DEFAULT;             // calls with at least this many sponge chains walk them on the device; above 2^32: never
+        int sponge_chain_segment = 0;                 // permutations of a chain per launch of wit_chain_batch_kernel (0 = 256)
+        int verify_batch_min = ZKG16_VERIFY_BATCH_MIN_DEFAULT;                   // zkg16_verify_batch: shorter batches are answered by the host form (the measured crossover)
+        int verify_wire_min = ZKG16_VERIFY_WIRE_MIN_DEFAULT;                     // zkg16_verify_batch_wire: shorter batches are decoded and answered on the host (the measured crossover)
+        int verify_each_after = ZKG16_VERIFY_EACH_AFTER_DEFAULT;                 // zkg16_verify_batch[_wire] with ok_each: range tests before the per-proof pass takes over
+    } opt;
     std::map<std::string, zk::KernelStat> kstats;
     std::vector<zk::PendingEvent> pending_events;
-    int opt_window_bits = 0;
-    int opt_min_seg = 0;                              // shortest per-lane run of sorted entries in an accumulation (0 = default)
-    int opt_ntt_mode = 1;                             // 1: unsaturated (29-bit limb) butterflies, 0: saturated
-    int opt_reduce_mode = 3;                          // 0 classic (log-depth scan over all chunks), 1 work-efficient two-level, 2 = 1 except the proof's last MSM, 3 (default) = 2 from 16-bit windows on and bit-sliced for single bucket sets <= 2^19, 5 = bit-sliced wherever it applies
-    int opt_b_filter = 0;                             // B-side term list filtered out of the full one: 0 = with window tables (default), 1 = always, 2 = never (second sort)
-    int opt_spmv_dict = 0;                            // 0/1: coefficient dictionary in the SpMV (default); 2: plain kernel
-    int opt_wm_first = -1;                            // see zkg16_set_option "wm_first"
-    int opt_g1_waves = 0;                             // G1 accumulation waves per SIMD in the one resident round (0 = 2)
-    int opt_fixup_aux = 0;                            // 1: fix-up kernels on the MSM's reduction stream
-    int opt_window_bits_h = 0;                        // the H MSM's own plan (it is the last one: its reduction is not hidden)
-    int opt_reduce_chunk = 0;
-    int opt_wm_concurrent = -1;
-    int opt_ntt_radix = 1;                            // 1 (default): the last seven butterfly stages by lane exchanges (ds_bpermute / DPP), 2: every stage through the LDS, 4: two stages per LDS trip
-    int opt_ntt_xcd = 1;                              // NTT tiles in XCD-aware order (ntt.hip: xcd_tile)
-    int opt_acc_debug = 0;                            // timing probes (wrong results): see AccArgs::debug
-    int opt_sort_mode = 0;                            // 0: hand-written bucket scatter (bucket_sort.hip), 1: rocPRIM radix sort
-    int opt_acc_pipeline = 0;                         // bit 0 / 1: G1 / G2 accumulation gathers the next base behind the last (inlined) product (default: neither)
     void *circuit_stage = nullptr;                    // pinned staging block of zkg16_circuit_load (root ctx; grown on demand)
     size_t circuit_stage_bytes = 0;
-    int opt_collect_threads = -1;                     // -1: the z-side MSMs' window sums are combined on their own host threads when the key is plain; 1 always; 0 never
-    int opt_fixed_base_bits = 0;                      // setup's fixed-base window width (0 = by batch size; even widths >= 16 are built in two levels)
-    int opt_g2_lazy = 1;                              // G2 accumulation: Fq2 products with one reduction per component, operands parked in LDS (ffu.cuh: fq2u_mul_lazy)
-    int opt_acc_lazy = 1;                             // default G1 / G2 accumulation loops: the mixed addition without the carry passes its results do not need (ec.cuh: xyzz_madd_inline_lc, xyzz_madd_lazy_lc); 0: xyzz_madd_inline / xyzz_madd_lazy
-    int opt_g1_inline = 1;                            // G1 accumulation (plain loop): every field product inlined (ec.cuh: xyzz_madd_inline); 0: products as calls
-    int opt_matrix_parts = 0;                         // zkg16_prove_matrix: gadget slices the assignment arrives in (0 = five growing slices, k = k equal ones, 1 = no overlap)
-    int opt_fuse_pointwise = 1;                       // the point-wise product on the load of the last transform (0: its own pass)
-    int opt_wm_transforms = 6;                        // witness map: 6 (default) = C only inverse-transformed, subtracted on the last store; 7 = arkworks' sequence
-    int opt_batch_max = 0;                            // zkg16_prove_batch / zkg16_prove_matrix_batch: proofs per device pass (0 = as many as fit)
-    int opt_matrix_batch_threads = 0;                 // zkg16_witness_matrix_batch / zkg16_prove_matrix_batch: host threads of the sponge chains (0 = 8)
-    int opt_matrix_batch_grid = 0;                    // cap on either grid dimension of the batched witness kernels (0 = 65535): beyond it they loop
-    int64_t opt_sponge_chains_min = ZKG16_SPONGE_CHAINS_MIN_DEFAULT;             // calls with at least this many sponge chains walk them on the device; above 2^32: never
-    int opt_sponge_chain_segment = 0;                 // permutations of a chain per launch of wit_chain_batch_kernel (0 = 256)
-    int opt_verify_batch_min = ZKG16_VERIFY_BATCH_MIN_DEFAULT;                   // zkg16_verify_batch: shorter batches are answered by the host form (the measured crossover)
-    int opt_verify_wire_min = ZKG16_VERIFY_WIRE_MIN_DEFAULT;                     // zkg16_verify_batch_wire: shorter batches are decoded and answered on the host (the measured crossover)
-    int opt_verify_each_after = ZKG16_VERIFY_EACH_AFTER_DEFAULT;                 // zkg16_verify_batch[_wire] with ok_each: range tests before the per-proof pass takes over
-    float vb_timings[11] = {0};                       // zkg16_verify_batch_timings (root: the last batch verified on any lane)
+    float vb_timings[zk::VERIFY_TIMING_SLOTS] = {0};                    // zkg16_verify_batch_timings (root: the last batch verified on any lane)
     int num_cus = 256;
     bool lds_attr_fixup[2] = {false, false}, lds_attr_ntt = false;      // hipFuncSetAttribute(max dynamic LDS) done on this device
     zk::FixedBaseCache fb_g1, fb_g2;
@@ -354,7 +361,7 @@ struct zkg16_ctx {
 
 namespace zk {
 
-// Brackets one kernel launch with a HIP-event pair on the ctx stream when ctx->kernel_timing is on.
+// Brackets one kernel launch with a HIP-event pair on the ctx stream when ctx->opt.kernel_timing is on.
 // Recording is asynchronous (no host sync inside the timed region); pairs are resolved when stats are read.
 struct PendingEvent { std::string name; double units; hipEvent_t e0, e1; };
 

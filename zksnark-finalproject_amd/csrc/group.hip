@@ -1,5 +1,5 @@
 // Split witness map over the ranks of a device group: layout (host), exchange kernel and one rank's share of the witness
-// map's transforms.  See group.hpp for the layout; the group object and its entry points are in api.hip.
+// map's transforms.  See group.hpp for the layout; the group object and its entry points are in api_group.hip.
 #include <chrono>
 
 #include "group.hpp"
@@ -283,8 +283,8 @@ void group_witness_map_run(zkg16_ctx *ctx, R1csDev &m, const Fr *z, Fr **h_out, 
     };
 
     struct Step { int src, dst; bool inverse, coset; const NttLast *last; };
-    const bool six = ctx->opt_wm_transforms != 7;
-    const bool fuse = ctx->opt_fuse_pointwise != 0;
+    const bool six = ctx->opt.wm_transforms != 7;
+    const bool fuse = ctx->opt.fuse_pointwise != 0;
     const NttLast to_b{&tab->zinv, fuse, false}, to_c{&tab->zinv, false, false}, sub{nullptr, false, true};
     const Step seq7[7] = {{0, 3, true, false, nullptr}, {3, 0, false, true, nullptr}, {1, 3, true, false, nullptr}, {3, 1, false, true, nullptr},
                           {2, 3, true, false, nullptr}, {3, 2, false, true, nullptr}, {0, 3, true, true, nullptr}};

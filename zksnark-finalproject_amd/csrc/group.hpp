@@ -1,4 +1,4 @@
-// Split witness map over the ranks of a device group (group.hip; entry points in api.hip).
+// Split witness map over the ranks of a device group (group.hip; entry points in api_group.hip).
 //
 // The two-pass NTT plans view N = N1 * N2 as a matrix x[N2 * i1 + i2]: the column pass transforms the columns i2 in place,
 // the row pass reads the rows k1 and writes X[k1 + N1 * k2].  With m = min(N1, N2), rank g of k owns the residues

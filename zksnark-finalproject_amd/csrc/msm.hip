@@ -743,7 +743,7 @@ batch_affine_kernel(const XYZZ<FU> *pts, size_t n, FU *pref, AffineSegs<FU> segs
 
 // ------------------------------------------------------------------------------------------------ host drivers
 static int pick_window_bits(zkg16_ctx *ctx, size_t n) {
-    if (ctx->opt_window_bits >= 2 && ctx->opt_window_bits <= 20) return ctx->opt_window_bits;
+    if (ctx->opt.window_bits >= 2 && ctx->opt.window_bits <= 20) return ctx->opt.window_bits;
     // 254-bit magnitudes: c = 16 and 15 leave a 14-bit top window, 13 a 7-bit one (c = 14 would leave 2 bits = 4 giant buckets)
     if (n >= ((size_t)1 << 23)) return 17;         // 128x128 circuit (8.7 M / 16.8 M terms): 15 windows instead of 16; measured 191.3 -> 185.7 ms
     if (n >= ((size_t)1 << 20)) return 16;
@@ -793,7 +793,7 @@ void msm_plan_build(zkg16_ctx *ctx, MsmWorkspace &ws, const ScalarSrc &src, MsmP
     if (tot >= ((size_t)1 << 31)) throw HipError{hipErrorInvalidValue, "msm: more than 2^31 (scalar, window) terms", __FILE__, __LINE__};
     ws.entries.ensure(tot * sizeof(uint64_t));
     ws.offsets.ensure((tb + 1) * sizeof(uint32_t));
-    const bool own_sort = ctx->opt_sort_mode == 0 || tabled;
+    const bool own_sort = ctx->opt.sort_mode == 0 || tabled;
     const DigitSrc d{reinterpret_cast<const uint32_t *>(src.main), reinterpret_cast<const uint32_t *>(src.extra), src.n_main, n, src.mask,
                      src.mont ? 1 : 0, src.part, src.want_part, reinterpret_cast<const uint32_t *const *>(src.vecs), src.vec_stride};
     const dim3 dgrid((unsigned)((n + 255) / 256), (unsigned)nv);
@@ -830,12 +830,12 @@ void msm_plan_build(zkg16_ctx *ctx, MsmWorkspace &ws, const ScalarSrc &src, MsmP
     plan.total_entries = tot;
     // G1: two waves per SIMD, four from 2^25 terms on (124 registers: four fit; the extra waves hide what is left of the gather
     // latency — 128x128: 163.0 -> 160.8 ms; no change at 32x32, where a lane would get ~25 terms)
-    plan.lanes_g1 = (uint32_t)ctx->num_cus * 4u * (uint32_t)(ctx->opt_g1_waves > 0 ? ctx->opt_g1_waves : tot >= ((size_t)1 << 25) ? 4 : 2) * 64u;
+    plan.lanes_g1 = (uint32_t)ctx->num_cus * 4u * (uint32_t)(ctx->opt.g1_waves > 0 ? ctx->opt.g1_waves : tot >= ((size_t)1 << 25) ? 4 : 2) * 64u;
     plan.lanes_g2 = (uint32_t)ctx->num_cus * 4u * 1u * 64u;
     ws.last_lanes_g1 = plan.lanes_g1;
     ws.seg_params.ensure(2 * sizeof(uint32_t));
     hipLaunchKernelGGL(msm_seg_params_kernel, dim3(1), dim3(64), 0, ctx->stream, ws.offsets.as<uint32_t>() + tb, (uint32_t)tb, plan.lanes_g1,
-                       plan.lanes_g2, (uint32_t)(ctx->opt_min_seg > 0 ? ctx->opt_min_seg : 0), ws.seg_params.as<uint32_t>());
+                       plan.lanes_g2, (uint32_t)(ctx->opt.min_seg > 0 ? ctx->opt.min_seg : 0), ws.seg_params.as<uint32_t>());
     ZK_HIP(hipGetLastError());
 }
 
@@ -965,7 +965,7 @@ void msm_plan_filter(zkg16_ctx *ctx, const MsmWorkspace &ws_src, const MsmPlan &
                            counts + nblk, 1, ws_dst.offsets.as<uint32_t>(), tb);
     }
     hipLaunchKernelGGL(msm_seg_params_kernel, dim3(1), dim3(64), 0, ctx->stream, ws_dst.offsets.as<uint32_t>() + tb, (uint32_t)tb, plan_dst.lanes_g1,
-                       plan_dst.lanes_g2, (uint32_t)(ctx->opt_min_seg > 0 ? ctx->opt_min_seg : 0), ws_dst.seg_params.as<uint32_t>());
+                       plan_dst.lanes_g2, (uint32_t)(ctx->opt.min_seg > 0 ? ctx->opt.min_seg : 0), ws_dst.seg_params.as<uint32_t>());
     ZK_HIP(hipGetLastError());
 }
 
@@ -1077,20 +1077,20 @@ static void msm_enqueue_acc(zkg16_ctx *ctx, MsmWorkspace &ws, const MsmPlan &pla
     a.total_ptr = ws.offsets.as<uint32_t>() + tb;
     a.total_buckets = tb;
     a.seg_len_ptr = ws.seg_params.as<uint32_t>() + (FieldTraits<F>::g2 ? 1 : 0);
-    a.debug = (uint32_t)ctx->opt_acc_debug;
+    a.debug = (uint32_t)ctx->opt.acc_debug;
     const unsigned grid = (unsigned)((nseg + 63) / 64);
     {
         ScopedKernelTimer kt(ctx, FieldTraits<F>::g2 ? "msm_accumulate_g2" : "msm_accumulate_g1", (double)plan.n, ctx->stream);
-        const bool pipe = (ctx->opt_acc_pipeline >> (FieldTraits<F>::g2 ? 1 : 0)) & 1;
-        const bool lc = ctx->opt_acc_lazy != 0;      // only the default loops have the form without the spare carry passes
+        const bool pipe = (ctx->opt.acc_pipeline >> (FieldTraits<F>::g2 ? 1 : 0)) & 1;
+        const bool lc = ctx->opt.acc_lazy != 0;      // only the default loops have the form without the spare carry passes
         if (pipe) {
             hipLaunchKernelGGL((msm_accumulate_kernel<F, true>), dim3(grid), dim3(64), 0, ctx->stream, a);
         } else if constexpr (FieldTraits<F>::g2) {
-            if (ctx->opt_g2_lazy && lc) hipLaunchKernelGGL((msm_accumulate_kernel<F, false, true, false, true>), dim3(grid), dim3(64), 0, ctx->stream, a);
-            else if (ctx->opt_g2_lazy) hipLaunchKernelGGL((msm_accumulate_kernel<F, false, true>), dim3(grid), dim3(64), 0, ctx->stream, a);
+            if (ctx->opt.g2_lazy && lc) hipLaunchKernelGGL((msm_accumulate_kernel<F, false, true, false, true>), dim3(grid), dim3(64), 0, ctx->stream, a);
+            else if (ctx->opt.g2_lazy) hipLaunchKernelGGL((msm_accumulate_kernel<F, false, true>), dim3(grid), dim3(64), 0, ctx->stream, a);
             else hipLaunchKernelGGL((msm_accumulate_kernel<F, false>), dim3(grid), dim3(64), 0, ctx->stream, a);
         } else {
-            if (!ctx->opt_g1_inline) hipLaunchKernelGGL((msm_accumulate_kernel<F, false, false, true>), dim3(grid), dim3(64), 0, ctx->stream, a);
+            if (!ctx->opt.g1_inline) hipLaunchKernelGGL((msm_accumulate_kernel<F, false, false, true>), dim3(grid), dim3(64), 0, ctx->stream, a);
             else if (lc) hipLaunchKernelGGL((msm_accumulate_kernel<F, false, false, false, true>), dim3(grid), dim3(64), 0, ctx->stream, a);
             else hipLaunchKernelGGL((msm_accumulate_kernel<F, false>), dim3(grid), dim3(64), 0, ctx->stream, a);
         }
@@ -1098,7 +1098,7 @@ static void msm_enqueue_acc(zkg16_ctx *ctx, MsmWorkspace &ws, const MsmPlan &pla
     static_assert(sizeof(AccArgs<F>) <= sizeof(slot.acc_args), "MsmSlot::acc_args too small");
     memcpy(slot.acc_args, &a, sizeof a);
     slot.acc_grid = grid;
-    slot.fixups_pending = ctx->opt_fixup_aux != 0 && round < 0;      // rounds are merged right away: their fix-ups come first
+    slot.fixups_pending = ctx->opt.fixup_aux != 0 && round < 0;      // rounds are merged right away: their fix-ups come first
     if (!slot.fixups_pending) msm_launch_fixups<F>(ctx, slot, ctx->stream);
     if (round > 0) {
         ScopedKernelTimer kt(ctx, FieldTraits<F>::g2 ? "msm_bucket_merge_g2" : "msm_bucket_merge_g1", (double)tb, ctx->stream);
@@ -1136,7 +1136,7 @@ static void msm_enqueue_reduce(zkg16_ctx *ctx, MsmSlot &slot) {
     const char *rname = FieldTraits<F>::g2 ? "msm_reduce_g2" : "msm_reduce_g1";
     // buckets per lane: 8 when the reduction has enough lanes to matter as work; fewer when it is a short, purely
     // latency-bound chain (small circuits, 1/8 shards): measured 4.4 -> 3.7 ms at 6,476 constraints, 5.6 -> 5.1 ms at 60,684
-    int kk = ctx->opt_reduce_chunk > 0 ? ctx->opt_reduce_chunk : (tb <= 16384 ? 2 : tb <= 131072 ? 4 : 8);
+    int kk = ctx->opt.reduce_chunk > 0 ? ctx->opt.reduce_chunk : (tb <= 16384 ? 2 : tb <= 131072 ? 4 : 8);
     while ((size_t)kk > plan.nb) kk >>= 1;
     const size_t nchunks = plan.nb / kk;
     const size_t tot = nchunks * plan.nwin;
@@ -1145,7 +1145,7 @@ static void msm_enqueue_reduce(zkg16_ctx *ctx, MsmSlot &slot) {
     // (slot.last_of_proof, set by the caller): the others overlap the next accumulation, where work, not depth, is what costs
     // default (3): mode 2 from 16-bit windows on (measured 128x128: 184.1 -> 182.5 ms; 32x32: no change; a 6,476-constraint proof
     // 3.6 -> 4.8 ms with it, so small windows keep the short chain)
-    const int rmode = ctx->opt_reduce_mode >= 5 ? 3 : ctx->opt_reduce_mode;          // 5 / 6: the default with / without the bit-sliced form
+    const int rmode = ctx->opt.reduce_mode >= 5 ? 3 : ctx->opt.reduce_mode;          // 5 / 6: the default with / without the bit-sliced form
     const bool efficient = rmode == 1 || (rmode == 2 && !slot.last_of_proof) || (rmode == 3 && !slot.last_of_proof && slot.c >= 16);
     slot.two_level_k = (efficient && kk >= 2 && nchunks >= 2 * (size_t)kk2) ? kk : 0;
     // bit-sliced: bucket sets of a size where depth, not work, is what the reduction costs — one set of up to 2^19 buckets (window
@@ -1160,8 +1160,8 @@ static void msm_enqueue_reduce(zkg16_ctx *ctx, MsmSlot &slot) {
     // (profiles/batch_reduce_modes_r7.txt): plain keys 8x8 1.14 vs 1.35 ms/proof and 32x32 9.55 vs 10.43 at K = 64, tabled keys equal
     const int nw1 = plan.nwin / (slot.batch > 1 ? slot.batch : 1);
     const size_t tb1 = plan.nb * (size_t)nw1;
-    const bool bs_auto = ctx->opt_reduce_mode == 3 && (nw1 == 1 ? plan.nb >= 256 && plan.nb <= one_set_max : plan.nb >= 4096 && tb1 <= ((size_t)1 << 19));
-    if (pow2 && plan.nb >= 8 && (ctx->opt_reduce_mode == 5 || bs_auto)) {
+    const bool bs_auto = ctx->opt.reduce_mode == 3 && (nw1 == 1 ? plan.nb >= 256 && plan.nb <= one_set_max : plan.nb >= 4096 && tb1 <= ((size_t)1 << 19));
+    if (pow2 && plan.nb >= 8 && (ctx->opt.reduce_mode == 5 || bs_auto)) {
         auto log2z = [](size_t v) { int l = 0; while (((size_t)1 << l) < v) l++; return l; };
         // chunk size by depth in dependent additions: 2K - 1 in chunk_local, the first tree level in rounds of the resident lanes (a G2
         // wave fills a SIMD, two G1 waves do; the following levels add about as much again), then one per halving
@@ -1174,7 +1174,7 @@ static void msm_enqueue_reduce(zkg16_ctx *ctx, MsmSlot &slot) {
             const double depth = 2 * k - 1 + 2 * (rounds > 1 ? rounds : 1) + log2z(ns) - 1;
             if (depth < best) { best = depth; kb = k; }
         }
-        if (ctx->opt_reduce_chunk > 1 && (ctx->opt_reduce_chunk & (ctx->opt_reduce_chunk - 1)) == 0) kb = ctx->opt_reduce_chunk;
+        if (ctx->opt.reduce_chunk > 1 && (ctx->opt.reduce_chunk & (ctx->opt.reduce_chunk - 1)) == 0) kb = ctx->opt.reduce_chunk;
         while (kb > 2 && (size_t)kb * 4 > plan.nb) kb >>= 1;
         slot.two_level_k = kb;
         slot.bit_sliced = log2z(plan.nb / kb);
@@ -1311,17 +1311,17 @@ void msm_slot_wait(MsmSlot &slot) {
 // bare-loop comparison of bench.py has to be read against, beside the waves per SIMD the grid is sized for (zkg16_last_acc_waves).
 int msm_acc_resident_waves(zkg16_ctx *ctx, bool g2) {
     int blocks = 0;
-    const bool pipe = (ctx->opt_acc_pipeline >> (g2 ? 1 : 0)) & 1;
+    const bool pipe = (ctx->opt.acc_pipeline >> (g2 ? 1 : 0)) & 1;
     hipError_t e;
     if (g2) {
         if (pipe) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, msm_accumulate_kernel<Fq2U, true>, 64, 0);
-        else if (ctx->opt_g2_lazy && ctx->opt_acc_lazy) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, msm_accumulate_kernel<Fq2U, false, true, false, true>, 64, 0);
-        else if (ctx->opt_g2_lazy) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, msm_accumulate_kernel<Fq2U, false, true>, 64, 0);
+        else if (ctx->opt.g2_lazy && ctx->opt.acc_lazy) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, msm_accumulate_kernel<Fq2U, false, true, false, true>, 64, 0);
+        else if (ctx->opt.g2_lazy) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, msm_accumulate_kernel<Fq2U, false, true>, 64, 0);
         else e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, msm_accumulate_kernel<Fq2U, false>, 64, 0);
     } else {
         if (pipe) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, msm_accumulate_kernel<FqU, true>, 64, 0);
-        else if (!ctx->opt_g1_inline) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, msm_accumulate_kernel<FqU, false, false, true>, 64, 0);
-        else if (ctx->opt_acc_lazy) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, msm_accumulate_kernel<FqU, false, false, false, true>, 64, 0);
+        else if (!ctx->opt.g1_inline) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, msm_accumulate_kernel<FqU, false, false, true>, 64, 0);
+        else if (ctx->opt.acc_lazy) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, msm_accumulate_kernel<FqU, false, false, false, true>, 64, 0);
         else e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, msm_accumulate_kernel<FqU, false>, 64, 0);
     }
     ZK_HIP(e);
@@ -1425,7 +1425,7 @@ static void fixed_base_run(zkg16_ctx *ctx, FixedBaseCache &cache, const Affine<t
     int wbits = n >= ((size_t)1 << 17) ? 12 : 8;
     if (!g2) { if (n >= ((size_t)1 << 25)) wbits = 20; else if (n >= ((size_t)1 << 24)) wbits = 18; else if (n >= ((size_t)1 << 21)) wbits = 16; }
     else { if (n >= ((size_t)1 << 23)) wbits = 18; else if (n >= ((size_t)1 << 20)) wbits = 16; }      // (64x64: setup 59.6 -> 54.3 ms with 16 / 16 instead of 18 / 12)
-    if (ctx->opt_fixed_base_bits) wbits = ctx->opt_fixed_base_bits;
+    if (ctx->opt.fixed_base_bits) wbits = ctx->opt.fixed_base_bits;
     const bool two_level = wbits >= 16;             // even widths only (checked by the option)
     const int nwin = (256 + wbits - 1) / wbits;
     const size_t tab_n = (size_t)nwin * (((size_t)1 << wbits) - 1);

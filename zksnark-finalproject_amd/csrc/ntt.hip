@@ -727,10 +727,10 @@ static Fr *ntt_run_impl(zkg16_ctx *ctx, Fr *data, Fr *tmp, int log_n, bool inver
             ZK_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         lds_attr_set = true;
     }
-    const bool uform = ctx->opt_ntt_mode != 0;          // 1 (default): unsaturated butterflies; 0: saturated (the first version)
-    const bool r4 = ctx->opt_ntt_radix == 4;
-    const bool xch = ctx->opt_ntt_radix == 1;       // lane exchanges for the last stages
-    const bool xch2 = ctx->opt_ntt_radix == 3;      // ... and for the top seven stages
+    const bool uform = ctx->opt.ntt_mode != 0;          // 1 (default): unsaturated butterflies; 0: saturated (the first version)
+    const bool r4 = ctx->opt.ntt_radix == 4;
+    const bool xch = ctx->opt.ntt_radix == 1;       // lane exchanges for the last stages
+    const bool xch2 = ctx->opt.ntt_radix == 3;      // ... and for the top seven stages
     auto *k_cols = uform ? (xch2 ? ntt_pass_cols_u<11, false, 3> : xch ? ntt_pass_cols_u<11, false, 2> : r4 ? ntt_pass_cols_u<11, false, true> : ntt_pass_cols_u<11, false, false>) : ntt_pass_cols;
     auto *k_rows = uform ? (xch2 ? ntt_pass_rows_u<11, false, 3> : xch ? ntt_pass_rows_u<11, false, 2> : r4 ? ntt_pass_rows_u<11, false, true> : ntt_pass_rows_u<11, false, false>) : ntt_pass_rows;
     const unsigned nthreads = uform ? NTT_THREADS_U : NTT_THREADS;
@@ -742,7 +742,7 @@ static Fr *ntt_run_impl(zkg16_ctx *ctx, Fr *data, Fr *tmp, int log_n, bool inver
     a.w = t->w.as<Fr>();
     a.log_n = log_n;
     a.inverse = inverse ? 1 : 0;
-    a.xcd_order = ctx->opt_ntt_xcd;
+    a.xcd_order = ctx->opt.ntt_xcd;
     if (nvec < 1 || nvec > 65535 || (nvec > 1 && (share || vec_stride < n))) throw HipError{hipErrorInvalidValue, "ntt: bad batch of transforms", __FILE__, __LINE__};
     a.vec_stride = nvec > 1 ? vec_stride : 0;
     const Fr *pre = (!inverse && coset) ? t->g.as<Fr>() : nullptr;
@@ -752,7 +752,7 @@ static Fr *ntt_run_impl(zkg16_ctx *ctx, Fr *data, Fr *tmp, int log_n, bool inver
     if (uform) {
         // passes that load without a conversion product (load_u): all of them, except the first when it carries the coset
         // pre-multiply (a full conversion) or the fused point-wise stage (likewise)
-        const bool two_big = ctx->opt_ntt_mode != 3 && log_n > 2 * NTT_MAX_SUB_LOG && log_n <= 24;
+        const bool two_big = ctx->opt.ntt_mode != 3 && log_n > 2 * NTT_MAX_SUB_LOG && log_n <= 24;
         const int passes = log_n <= NTT_MAX_SUB_LOG ? 1 : (two_big || log_n <= 2 * NTT_MAX_SUB_LOG) ? 2 : 3;
         std::unique_lock<std::mutex> lazy(t->mu);           // lanes share the table object: one of them builds, the others wait
         if (t->u_passes != passes || !t->g_u.p) {
@@ -801,7 +801,7 @@ static Fr *ntt_run_impl(zkg16_ctx *ctx, Fr *data, Fr *tmp, int log_n, bool inver
     };
     auto lds_bytes = [uform](int log_m) { return (size_t)(uform ? 9 : 8) * 4 * (NTT_TILE + (log_m > 0 ? (1 << (log_m - 1)) : 1)); };
 
-    if (uform && ctx->opt_ntt_mode != 3 && log_n > 2 * NTT_MAX_SUB_LOG && log_n <= 24) {
+    if (uform && ctx->opt.ntt_mode != 3 && log_n > 2 * NTT_MAX_SUB_LOG && log_n <= 24) {
         // 2^23, 2^24: two passes over 4096-point tiles (N1 = 2^(log_n - 12) columns-first, N2 = 2^12) with the sub-transform
         // twiddles read from a U-form table in global memory, instead of three passes over 2048-point tiles
         std::unique_lock<std::mutex> lazy(t->mu);
@@ -915,7 +915,7 @@ Fr *ntt_run_batch(zkg16_ctx *ctx, Fr *data, Fr *tmp, int log_n, bool inverse, bo
 // positions the rank owns become valid in `tmp`.  Single- and three-pass sizes have no share (an error).
 Fr *ntt_run_share(zkg16_ctx *ctx, Fr *data, Fr *tmp, int log_n, bool inverse, bool coset, const NttPointwise *pw, const NttShare &share,
                   const NttLast *last) {
-    if (!ntt_two_pass_shape(log_n, ctx->opt_ntt_mode, nullptr, nullptr, nullptr))
+    if (!ntt_two_pass_shape(log_n, ctx->opt.ntt_mode, nullptr, nullptr, nullptr))
         throw HipError{hipErrorInvalidValue, "ntt: a share of a transform that is not two-pass", __FILE__, __LINE__};
     return ntt_run_impl(ctx, data, tmp, log_n, inverse, coset, pw, last, &share);
 }

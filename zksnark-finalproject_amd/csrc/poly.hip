@@ -396,7 +396,7 @@ void spmv_run(zkg16_ctx *ctx, R1csDev &m, const Fr *z, Fr *a, Fr *b, Fr *c, cons
     // three passes of the build cost more than they save there: Fermat-prime request 8.1 -> 9.7 ms), a resident system pays once
     {
         std::lock_guard<std::mutex> lazy(m.lazy_mu);       // lanes share the handle: one of them builds (and synchronises its stream), the others wait
-        if (m.dict_state == 0 && ctx->opt_spmv_dict != 2 && ++m.spmv_uses >= 2) coef_dict_build(ctx, m);
+        if (m.dict_state == 0 && ctx->opt.spmv_dict != 2 && ++m.spmv_uses >= 2) coef_dict_build(ctx, m);
     }
     const size_t n = (size_t)1 << m.log_n;
     size_t lanes = n;
@@ -405,7 +405,7 @@ void spmv_run(zkg16_ctx *ctx, R1csDev &m, const Fr *z, Fr *a, Fr *b, Fr *c, cons
     const unsigned grid = (unsigned)((lanes + 255) / 256);
     if (nvec < 1 || nvec > 65535 || (nvec > 1 && (rows || !zs))) throw HipError{hipErrorInvalidValue, "spmv: bad batch", __FILE__, __LINE__};
     ScopedKernelTimer kt(ctx, "spmv_kernel", (double)(m.nnz[0] + m.nnz[1] + m.nnz[2]) * nvec);
-    if (m.dict_state == 1 && ctx->opt_spmv_dict != 2) {
+    if (m.dict_state == 1 && ctx->opt.spmv_dict != 2) {
         SpmvDictArgs s;
         for (int i = 0; i < 3; i++) {
             s.rp[i] = m.rp[i].as<uint64_t>();
@@ -433,7 +433,7 @@ void spmv_run(zkg16_ctx *ctx, R1csDev &m, const Fr *z, Fr *a, Fr *b, Fr *c, cons
             s.rp[i] = m.rp[i].as<uint64_t>();
             s.col[i] = m.col[i].as<uint32_t>();
             s.cf[i] = m.cf[i].as<Fr>();
-            s.perm[i] = (m.perm_ok && ctx->opt_spmv_dict != 2) ? m.perm[i].as<uint32_t>() : nullptr;
+            s.perm[i] = (m.perm_ok && ctx->opt.spmv_dict != 2) ? m.perm[i].as<uint32_t>() : nullptr;
         }
         s.out[0] = a; s.out[1] = b; s.out[2] = c;
         s.z = z;
@@ -478,10 +478,10 @@ static Fr *wm_transforms(zkg16_ctx *ctx, int log_n, Fr *a, Fr *b, Fr *c, Fr *tmp
         return ntt_run_batch(ctx, src, dst, log_n, inverse, coset, pw, nvec, n, last);
     };
     NttTables *t = ntt_get_tables(ctx, log_n);
-    const bool fuse = ctx->opt_fuse_pointwise != 0;
+    const bool fuse = ctx->opt.fuse_pointwise != 0;
     run(a, tmp, true, false);
     run(tmp, a, false, true);
-    if (ctx->opt_wm_transforms == 7) {
+    if (ctx->opt.wm_transforms == 7) {
         run(b, tmp, true, false);
         run(tmp, b, false, true);
         run(c, tmp, true, false);

@@ -1,4 +1,4 @@
-// Batched Groth16 verification: what verify.hip (host arithmetic), verify_batch.hip (kernels) and api.hip (entry points on a lane of
+// Batched Groth16 verification: what verify.hip (host arithmetic), verify_batch.hip (kernels) and api_verify.hip (entry points on a lane of
 // the ctx) share.  K proofs under one prepared key hold iff, for multipliers rho_k nobody could predict (error 2^-128),
 //
 //     FE( prod_k ML(rho_k A_k, B_k) * ML(sum_k rho_k X_k, -gamma) * ML(sum_k rho_k C_k, -delta) ) == e(alpha, beta)^(sum_k rho_k)

@@ -485,7 +485,7 @@ struct MatrixWitnessLayout {
 };
 
 // The assignment of one MatrixCircuit request arriving on the device in parts: part 0 needs only a and b, part 1 + s the
-// entering states of slice s of the three host chains (common.hpp: MatrixWitnessStream is opaque to api.hip).
+// entering states of slice s of the three host chains (common.hpp: MatrixWitnessStream is opaque to api_prove.hip).
 struct MatrixWitnessStream {
     MatrixWitnessLayout L;
     MatrixChains mc;
@@ -618,7 +618,7 @@ void matrix_batch_chains(MatrixBatchChains &c, size_t n, const uint64_t *a, cons
 
 // Whether a call with this many chains walks them on the device (option "sponge_chains_min": 1 = always, above 2^32 = never).
 bool sponge_chains_on_device(const zkg16_ctx *ctx, size_t chains) {
-    const int64_t m = ctx->opt_sponge_chains_min;
+    const int64_t m = ctx->opt.sponge_chains_min;
     return m <= ((int64_t)1 << 32) && chains >= (uint64_t)m;
 }
 // the device route's stand-in for matrix_batch_chains: nothing runs here, matrix_batch_assign walks the chains and fills `hashes`
@@ -633,8 +633,8 @@ void matrix_batch_chains_device(MatrixBatchChains &c, size_t n, size_t k, uint64
 
 // launches of at most "sponge_chain_segment" permutations until every chain of `g` has ended
 static void chain_batch_launch(zkg16_ctx *ctx, ChainBatchArgs g, bool assign) {
-    const size_t cap = ctx->opt_matrix_batch_grid > 0 ? (size_t)ctx->opt_matrix_batch_grid : 65535;
-    const uint32_t seg = ctx->opt_sponge_chain_segment > 0 ? (uint32_t)ctx->opt_sponge_chain_segment : 256;
+    const size_t cap = ctx->opt.matrix_batch_grid > 0 ? (size_t)ctx->opt.matrix_batch_grid : 65535;
+    const uint32_t seg = ctx->opt.sponge_chain_segment > 0 ? (uint32_t)ctx->opt.sponge_chain_segment : 256;
     const size_t bx = (g.chains + 63) / 64;
     const dim3 grid((unsigned)(bx < cap ? bx : cap));
     for (uint32_t p = 0; p < g.perms;) {
@@ -700,7 +700,7 @@ void matrix_batch_assign(zkg16_ctx *ctx, const MatrixBatchChains &c, const uint6
     const bool dev = c.on_device;                   // st: the carried states of the 3k chains instead of every entering state
     const size_t ab_bytes = up(k * 2 * L.nn * sizeof(uint64_t)), st_bytes = up(k * 3 * (dev ? 1 : perms) * 3 * sizeof(Fr));
     const size_t tab_bytes = up(k * (3 * sizeof(Fr) + sizeof(Fr *))), bytes = ab_bytes + st_bytes + tab_bytes;
-    const size_t cap = ctx->opt_matrix_batch_grid > 0 ? (size_t)ctx->opt_matrix_batch_grid : 65535;
+    const size_t cap = ctx->opt.matrix_batch_grid > 0 ? (size_t)ctx->opt.matrix_batch_grid : 65535;
     poseidon_dev_ensure(ctx);
     mbatch_staging_ensure(ctx, bytes);
     auto backing = std::make_shared<DevBuf>(k * L.total * sizeof(Fr));
@@ -859,7 +859,7 @@ int zkg16_witness_matrix_batch(zkg16_ctx *ctx, size_t n, const uint64_t *a, cons
     try {
         hashes.resize(12 * k);
         if (sponge_chains_on_device(ctx, 3 * k)) matrix_batch_chains_device(mc, n, k, hashes.data());
-        else matrix_batch_chains(mc, n, a, b, k, ctx->opt_matrix_batch_threads, hashes.data());
+        else matrix_batch_chains(mc, n, a, b, k, ctx->opt.matrix_batch_threads, hashes.data());
     } catch (const std::bad_alloc &) {
         return ZKG16_ERR_OOM;
     }
