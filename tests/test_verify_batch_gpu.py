@@ -28,22 +28,7 @@ def batch1000(oracle):
     distinct proofs"""
     base = VB.make_batch(oracle, 40)
     rng = random.Random(77)
-    return rerandomised(oracle, base, 1000, rng)
-
-
-def rerandomised(oracle, base, k, rng):
-    """k valid proofs from a few: (A, B, C) -> (t A, t^-1 B, C) is again a valid proof of the same statement for every t != 0"""
-    proofs = np.zeros((k, 48), dtype=np.uint64)
-    infs = np.zeros((k, 3), dtype=np.uint8)
-    pubs = np.zeros((k,) + base.pubs.shape[1:], dtype=np.uint64)
-    for i in range(k):
-        j = i % base.k
-        proofs[i], infs[i], pubs[i] = base.proofs[j], base.infs[j], base.pubs[j]
-        if i >= base.k:
-            t = rng.randrange(1, P.R_MOD)
-            proofs[i, 0:12] = oracle.point_mul("g1", base.proofs[j, 0:12], fr_canon(t))[0]
-            proofs[i, 12:36] = oracle.point_mul("g2", base.proofs[j, 12:36], fr_canon(pow(t, -1, P.R_MOD)))[0]
-    return VB.Batch(base.pvk, pubs, proofs, infs)
+    return VB.rerandomised(oracle, base, 1000, rng)
 
 
 @pytest.fixture(scope="module")

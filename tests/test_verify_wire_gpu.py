@@ -29,20 +29,7 @@ def dev():
 def batch1000(oracle):
     """1,000 distinct proofs, built as tests/test_verify_batch_gpu.py builds its batch1000: 40 assignments proved by the oracle,
     then re-randomised — (A, B, C) -> (t A, t^-1 B, C) is again a valid proof of the same statement"""
-    base = VB.make_batch(oracle, 40)
-    rng = random.Random(77)
-    k = 1000
-    proofs = np.zeros((k, 48), dtype=np.uint64)
-    infs = np.zeros((k, 3), dtype=np.uint8)
-    pubs = np.zeros((k,) + base.pubs.shape[1:], dtype=np.uint64)
-    for i in range(k):
-        j = i % base.k
-        proofs[i], infs[i], pubs[i] = base.proofs[j], base.infs[j], base.pubs[j]
-        if i >= base.k:
-            t = rng.randrange(1, P.R_MOD)
-            proofs[i, 0:12] = oracle.point_mul("g1", base.proofs[j, 0:12], fr_canon(t))[0]
-            proofs[i, 12:36] = oracle.point_mul("g2", base.proofs[j, 12:36], fr_canon(pow(t, -1, P.R_MOD)))[0]
-    return VB.Batch(base.pvk, pubs, proofs, infs)
+    return VB.rerandomised(oracle, VB.make_batch(oracle, 40), 1000, random.Random(77))
 
 
 @pytest.fixture(scope="module")
@@ -50,14 +37,7 @@ def torsion():
     return VB.g2_outside_subgroup()
 
 
-def to_wire(b):
-    """a limb batch as it travels: [k, 192] bytes (A 48 | B 96 | C 48)"""
-    from zksnark_finalproject_amd import wire
-    k = b.k
-    a = np.frombuffer(wire.points_compress("g1", b.proofs[:, 0:12], b.infs[:, 0]), dtype=np.uint8).reshape(k, 48)
-    bb = np.frombuffer(wire.points_compress("g2", b.proofs[:, 12:36], b.infs[:, 1]), dtype=np.uint8).reshape(k, 96)
-    c = np.frombuffer(wire.points_compress("g1", b.proofs[:, 36:48], b.infs[:, 2]), dtype=np.uint8).reshape(k, 48)
-    return np.ascontiguousarray(np.concatenate([a, bb, c], axis=1))
+to_wire = VB.to_wire
 
 
 def host_decoded(raw, validate):

@@ -76,7 +76,8 @@ class Batch:
 
 def make_batch(oracle, k, steps=12, seed=2024):
     """The host Fibonacci synthesis (one circuit, every (a, b) another assignment) under a known-trapdoor key from the oracle,
-    proved k times by the oracle with k different assignments and (r, s)."""
+    proved k times by the oracle with k different assignments and (r, s).  a, b < 2^30 and 12 steps: every public input is below
+    2^40 and num_instance is 4.  Full-width inputs, other key shapes and statements with a point at infinity: tests/sim_proofs.py."""
     from zksnark_finalproject_amd.circuits import fibonacci_circuit
     from zksnark_finalproject_amd.device import pvk_prepare
     rng = random.Random(seed)
@@ -95,6 +96,33 @@ def make_batch(oracle, k, steps=12, seed=2024):
         infs.append(f)
     pubs = np.array([c.public_inputs for c in circs], dtype=np.uint64).reshape(k, c0.num_instance - 1, 4)
     return Batch(pvk, pubs, np.array(proofs, dtype=np.uint64).reshape(k, 48), np.array(infs, dtype=np.uint8).reshape(k, 3))
+
+
+def rerandomised(oracle, base, k, rng):
+    """k valid proofs from a few: (A, B, C) -> (t A, t^-1 B, C) is again a valid proof of the same statement for every t != 0"""
+    proofs = np.zeros((k, 48), dtype=np.uint64)
+    infs = np.zeros((k, 3), dtype=np.uint8)
+    pubs = np.zeros((k,) + base.pubs.shape[1:], dtype=np.uint64)
+    for i in range(k):
+        j = i % base.k
+        proofs[i], infs[i], pubs[i] = base.proofs[j], base.infs[j], base.pubs[j]
+        if i >= base.k:
+            t = rng.randrange(1, P.R_MOD)
+            proofs[i, 0:12] = oracle.point_mul("g1", base.proofs[j, 0:12], fr_canon(t))[0]
+            proofs[i, 12:36] = oracle.point_mul("g2", base.proofs[j, 12:36], fr_canon(pow(t, -1, P.R_MOD)))[0]
+    return Batch(base.pvk, pubs, proofs, infs)
+
+
+def to_wire(b):
+    """a limb batch as it travels: [k, 192] bytes (A 48 | B 96 | C 48).  The wire form has one encoding of the point at infinity,
+    so all-zero limbs without a flag (which the limb entry points read as infinity) travel as infinity too."""
+    from zksnark_finalproject_amd import wire
+    k = b.k
+    inf = lambda lo, hi, j: (b.infs[:, j].astype(bool) | ~b.proofs[:, lo:hi].any(axis=1)).astype(np.uint8)
+    a = np.frombuffer(wire.points_compress("g1", b.proofs[:, 0:12], inf(0, 12, 0)), dtype=np.uint8).reshape(k, 48)
+    bb = np.frombuffer(wire.points_compress("g2", b.proofs[:, 12:36], inf(12, 36, 1)), dtype=np.uint8).reshape(k, 96)
+    c = np.frombuffer(wire.points_compress("g1", b.proofs[:, 36:48], inf(36, 48, 2)), dtype=np.uint8).reshape(k, 48)
+    return np.ascontiguousarray(np.concatenate([a, bb, c], axis=1))
 
 
 def g2_outside_subgroup():

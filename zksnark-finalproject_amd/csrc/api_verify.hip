@@ -43,6 +43,21 @@ int vb_answer_on_host(zkg16_ctx *ctx, double t_all, Form &&form) {
     vb_publish(ctx, tm);
     return ZKG16_OK;
 }
+// The flags the kernels read: zkg16_verify_prepared and the host form read all-zero limbs as the point at infinity whatever the flag
+// says, the kernels go by the flag alone (all-zero limbs are on no curve and would fail membership), so the flag is set for them
+std::vector<uint8_t> vb_flags(const uint64_t *proofs, const uint8_t *inf, size_t k) {
+    std::vector<uint8_t> fl(3 * k);
+    for (size_t i = 0; i < k; i++) {
+        const uint64_t *pr = proofs + 48 * i;
+        const size_t at[4] = {0, 12, 36, 48};
+        for (int j = 0; j < 3; j++) {
+            uint64_t any = 0;
+            for (size_t t = at[j]; t < at[j + 1]; t++) any |= pr[t];
+            fl[3 * i + j] = inf[3 * i + j] || !any ? 1 : 0;
+        }
+    }
+    return fl;
+}
 // The three membership launches of one chunk of n proofs (48 limbs and 3 flags each; verdicts m3, 3 a proof): A on the main
 // stream, C and B beside it.
 void vb_membership_chunk(hipStream_t s_main, hipStream_t s_c, hipStream_t s_b, const uint64_t *pts, const uint8_t *fl, size_t n, const VbEndo &en,
@@ -96,7 +111,7 @@ int vb_device(zkg16_ctx *ctx, const VbKey &key, VbBatch b, const uint8_t *wire, 
     DevBuf d_wire(wire ? k * 192 : 0), d_st(wire ? 3 * k : 0);
     const VbEndo en = vb_endo();
     std::vector<uint64_t> dec_proofs;
-    std::vector<uint8_t> dec_inf, dec_st;
+    std::vector<uint8_t> dec_inf, dec_st, flags;
     if (wire) {
         upload_h2d(ctx, d_wire.p, wire, k * 192);
         ZK_HIP(hipMemcpyAsync(d_rho.p, b.rho, k * 16, hipMemcpyHostToDevice, s_main));
@@ -124,6 +139,9 @@ int vb_device(zkg16_ctx *ctx, const VbKey &key, VbBatch b, const uint8_t *wire, 
         b.proofs = dec_proofs.data();
         b.inf = dec_inf.data();
     } else {
+        // as zkg16_verify_batch_host reads them (a valid proof whose C = O came as zero limbs without its flag is valid here too)
+        flags = vb_flags(b.proofs, b.inf, k);
+        b.inf = flags.data();
         upload_h2d(ctx, d_proofs.p, b.proofs, k * 48 * 8);
         ZK_HIP(hipMemcpyAsync(d_inf.p, b.inf, 3 * k, hipMemcpyHostToDevice, s_main));
         ZK_HIP(hipMemcpyAsync(d_rho.p, b.rho, k * 16, hipMemcpyHostToDevice, s_main));
@@ -284,16 +302,7 @@ int zkg16_verify_each(zkg16_ctx *ctx, const uint64_t *gamma_abc_g1, size_t num_i
     ZK_LANE_BEGIN(ctx)
     hipStream_t s_main = ctx->stream, s_c = ctx->slots[1].stream, s_b = ctx->slots[2].stream;
     // zkg16_verify_prepared reads all-zero limbs as the point at infinity whatever the flag says: the same here
-    std::vector<uint8_t> fl(3 * k);
-    for (size_t i = 0; i < k; i++) {
-        const uint64_t *pr = proofs + 48 * i;
-        const size_t at[4] = {0, 12, 36, 48};
-        for (int j = 0; j < 3; j++) {
-            uint64_t any = 0;
-            for (size_t t = at[j]; t < at[j + 1]; t++) any |= pr[t];
-            fl[3 * i + j] = inf[3 * i + j] || !any ? 1 : 0;
-        }
-    }
+    const std::vector<uint8_t> fl = vb_flags(proofs, inf, k);
     VbEvents evs;
     DevBuf d_proofs(k * 48 * 8), d_inf(3 * k), d_mem3(3 * k);
     const VbEndo en = vb_endo();

@@ -715,7 +715,9 @@ def _verify_batch_args(pvk, public_inputs, proofs, infs, rho, k=None):
     proofs = _u64(proofs).reshape(-1, 48) if proofs is not None else None
     k = proofs.shape[0] if proofs is not None else k
     infs = np.ascontiguousarray(infs, dtype=np.uint8).reshape(-1, 3) if proofs is not None else None
-    pub = _u64(public_inputs).reshape(k, -1, 4) if k else _u64(public_inputs).reshape(0, gabc.shape[0] - 1, 4)
+    pub = _u64(public_inputs)
+    # (k, -1, 4) cannot be inferred for an empty array: no proofs, or a key with one instance variable and so no inputs
+    pub = pub.reshape(k, -1, 4) if pub.size else pub.reshape(k, 0 if k else gabc.shape[0] - 1, 4)
     if pub.shape[1] != gabc.shape[0] - 1:
         raise ValueError("verify_batch: %d public inputs per proof for a key with %d instance variables" % (pub.shape[1], gabc.shape[0]))
     if infs is not None and infs.shape[0] != k:
