@@ -515,6 +515,14 @@ ZKG16_API int zkg16_last_acc_waves(zkg16_ctx *ctx, int waves[3]);
 /* Waves of the bucket-accumulation kernels one SIMD holds at once (their register use decides): [0] G1, [1] G2.  The grid of an
  * accumulation may be sized for more waves per SIMD than that (zkg16_last_acc_waves): the extra ones run as a second round. */
 ZKG16_API int zkg16_acc_resident_waves(zkg16_ctx *ctx, int waves[2]);
+/* Which sparse product an r1cs handle's witness maps run (diagnostics; takes the handle's own lock, launches nothing):
+ * out = { dict_state, ndict, perm_ok, spmv_uses }.  dict_state: 0 = the coefficient dictionary has not been tried yet (the handle
+ * has run fewer than two witness maps: plain kernel, rows in natural order), 1 = the dictionary is in use (ndict distinct
+ * coefficients, 1..1024; 16-bit indices), 2 = this handle keeps the plain kernel (more than 1024 distinct coefficients, or fewer
+ * than 4096 non-zeros; ndict = 0).  perm_ok: 1 = the rows are walked in length-class order (built with the dictionary, from 4096
+ * constraints on; either kernel uses it).  spmv_uses: witness maps counted on the handle until the structures were built.  A null
+ * out or an unknown handle: ZKG16_ERR_BAD_ARG, out untouched. */
+ZKG16_API int zkg16_r1cs_spmv_state(zkg16_ctx *ctx, uint64_t r1cs_handle, uint32_t out[4]);
 /* The lanes of the most recent proofs: rows of (lane, start ms, end ms) on the host's steady clock, oldest first; returns the number of
  * rows written (<= cap_rows).  Two rows with different lanes and intersecting intervals = two proofs in flight at once. */
 ZKG16_API int zkg16_lane_log(zkg16_ctx *ctx, double *rows, int cap_rows);

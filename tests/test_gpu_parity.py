@@ -259,9 +259,10 @@ def test_witness_map_vs_oracle(dev, oracle):
 
 
 def test_witness_map_row_order_and_coefficient_dictionary(dev, oracle):
-    """The SpMV's two per-handle structures (csrc/poly.hip): rows ordered by length class (0 .. 254 non-zeros, and one class for
-    everything longer) and the 16-bit coefficient dictionary (here 37 distinct values, among them 1, -1 and 0; the random systems
-    of the other tests overflow it and exercise the fall-back).  Witness map == oracle, and == the plain kernel (option spmv_dict 2)."""
+    """The SpMV's two per-handle structures (csrc/poly.hip): rows ordered by length class (the bit length of the row's non-zero
+    count: 0, 1, 2-3, 4-7, ..., longest class first; here classes 0 .. 3, 6 and 9) and the 16-bit coefficient dictionary (here 37
+    distinct values, among them 1, -1 and 0; the random systems of the other tests overflow it and exercise the fall-back).
+    Witness map == oracle, and == the plain kernel (option spmv_dict 2).  Their limits: tests/test_sparse_limits_gpu.py."""
     rng = random.Random(77)
     nc, ni, nv = 9000, 3, 7000
     pool = [1, P.R_MOD - 1, 0, 2, 3] + [P.rand_fr(rng) for _ in range(32)]
@@ -286,6 +287,7 @@ def test_witness_map_row_order_and_coefficient_dictionary(dev, oracle):
     finally:
         dev.set_option("spmv_dict", 0)
     assert np.array_equal(dev.witness_map(rh, wh, 1 << 14), want)
+    assert dev.r1cs_spmv_state(rh)[:2] == (1, 37)          # the dictionary is in use, with every value of the pool
     dev.r1cs_free(rh)
     dev.witness_free(wh)
 

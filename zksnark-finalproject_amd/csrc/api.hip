@@ -487,6 +487,21 @@ int zkg16_acc_resident_waves(zkg16_ctx *ctx, int waves[2]) {
     ZK_API_END(ctx)
 }
 
+// Which SpMV path an r1cs handle is on (poly.hip builds both structures the second time the witness map runs on the handle):
+// out = dict_state (0 not tried, 1 dictionary in use, 2 plain kernel for good), ndict, perm_ok, spmv_uses.  Launches nothing.
+int zkg16_r1cs_spmv_state(zkg16_ctx *ctx, uint64_t r1cs_handle, uint32_t out[4]) {
+    if (!ctx || !out) return ZKG16_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    auto rc_ref = ctx->r1cs.get(r1cs_handle); R1csDev *rc = rc_ref.get();
+    if (!rc) return ZKG16_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lazy(rc->lazy_mu);
+    out[0] = (uint32_t)rc->dict_state;
+    out[1] = rc->ndict;
+    out[2] = rc->perm_ok ? 1u : 0u;
+    out[3] = (uint32_t)rc->spmv_uses;
+    return ZKG16_OK;
+}
+
 // the lanes (host intervals, steady-clock ms) of the most recent proofs on this ctx: rows of (lane, start, end); returns the
 // number of rows written.  Two proofs whose intervals intersect on different lanes ran at the same time.
 int zkg16_lane_log(zkg16_ctx *ctx, double *rows, int cap_rows) {

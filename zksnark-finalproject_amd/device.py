@@ -174,6 +174,13 @@ class Device:
         return dict(a=(rp[0], col[0][:nnz[0]], cf[0][:nnz[0]]), b=(rp[1], col[1][:nnz[1]], cf[1][:nnz[1]]),
                     c=(rp[2], col[2][:nnz[2]], cf[2][:nnz[2]]), num_inputs=ni.value, num_constraints=nc.value), nv.value
 
+    def r1cs_spmv_state(self, h):
+        """-> (dict_state, ndict, perm_ok, spmv_uses) of an r1cs handle (zkg16_r1cs_spmv_state): dict_state 0 = not tried yet,
+        1 = coefficient dictionary in use with ndict values, 2 = plain kernel for good; perm_ok 1 = rows in length-class order."""
+        out = (C.c_uint32 * 4)()
+        self._check(self.lib.zkg16_r1cs_spmv_state(self.ctx, h, out))
+        return int(out[0]), int(out[1]), int(out[2]), int(out[3])
+
     def r1cs_free(self, h):
         self.lib.zkg16_r1cs_free(self.ctx, h)
 
