@@ -455,6 +455,39 @@ ZKG16_API int zkg16_prime_r1cs_dims(uint64_t j, size_t *num_instance, size_t *nu
 ZKG16_API int zkg16_prime_r1cs_host(uint64_t x, uint64_t j, uint64_t *const row_ptr[3], uint32_t *const col[3], uint64_t *const coeff[3]);
 ZKG16_API int zkg16_r1cs_prime(zkg16_ctx *ctx, uint64_t x, uint64_t j, uint64_t *r1cs_handle);
 ZKG16_API int zkg16_witness_prime(zkg16_ctx *ctx, uint64_t x, uint64_t j, uint64_t *witness_handle);
+/* ---- K prime requests on ONE key.  Two candidates' R1CS differ in four coefficients of column 0 (the constant-one variable): n three
+ * times in A, -j once in C.  The TEMPLATE is the j >= 1 form with those four set to zero; for one trapdoor a candidate's key differs
+ * from the template's in a_query[0] and gamma_abc_g1[0] only:
+ *     a_query[0] = template's + n U,    gamma_abc_g1[0] = template's + n V_n - j V_j,
+ *     U = [u] g1, V_n = [beta u / gamma] g1, V_j = [w / gamma] g1,  u = L_r1(tau) + L_r2(tau) + L_r3(tau), w = L_r4(tau),
+ * r1..r3 the rows of A's patched coefficients, r4 the row of C's, L_i the Lagrange polynomials of the domain.
+ * zkg16_prime_r1cs_template_host (no ctx): the template arrays, with the dimensions of zkg16_prime_r1cs_dims(1, ...), and r1..r4.
+ * zkg16_r1cs_prime_template: an r1cs handle holding those bytes (a device-to-device copy of the resident template), marked as the
+ * template — the only handle zkg16_prove_prime_batch takes.  zkg16_prime_key_corrections (host only; the trapdoor is not kept):
+ * corr_out = U | V_n | V_j as affine Montgomery limbs, inf_out their infinity flags.
+ * zkg16_witness_prime_batch: zkg16_witness_prime for k candidates in one upload, two launches and one synchronisation; handle i holds
+ * the bytes of zkg16_witness_prime(xs[i], js[i]); the k assignments share one allocation, returned when the last handle is freed.  All
+ * or nothing: a refused candidate gives ZKG16_ERR_UNSUPPORTED, no handle is registered and nothing is written. */
+ZKG16_API int zkg16_prime_r1cs_template_host(uint64_t *const row_ptr[3], uint32_t *const col[3], uint64_t *const coeff[3], uint64_t patch_rows[4]);
+ZKG16_API int zkg16_r1cs_prime_template(zkg16_ctx *ctx, uint64_t *r1cs_handle);
+ZKG16_API int zkg16_prime_key_corrections(const uint64_t trapdoor[20], const uint64_t g1_gen[12], uint64_t corr_out[36], uint8_t inf_out[3]);
+ZKG16_API int zkg16_witness_prime_batch(zkg16_ctx *ctx, const uint64_t *xs, const uint64_t *js, size_t k, uint64_t *witness_handles);
+/* k prime requests on the template key (zkg16_setup_resident of the template handle) in batched device passes: per sub-batch (sized
+ * as zkg16_prove_batch's with the assignment added per proof; option "batch_max") the batched assignment, then the batched proof
+ * with request i's n added to A z in rows r1..r3 and -j to C z in row r4 before the transforms, and n U added to its A on the host.
+ * Proof i is byte for byte zkg16_prove_resident's on zkg16_r1cs_prime / zkg16_witness_prime(xs[i], js[i]) under the key
+ * zkg16_setup_resident gives that R1CS for the same trapdoor and generators, with (r + 4i, s + 4i); gamma_abc0_out[12 i ..] is that
+ * key's gamma_abc_g1[0] (every other verifying-key element is the template's).  corr: zkg16_prime_key_corrections' output (no
+ * infinity among them); gamma_abc0_template: the template key's gamma_abc_g1[0].  public_inputs (nullable): k x 257 x 4
+ * (zkg16_prime_public_inputs).  timings_ms (nullable, 4): host inputs (prime_inputs, summed wall), assignment passes (device),
+ * proving (zkg16_last_timings[9] summed), whole call.  One lane.  Checked before any work: unknown handles (ZKG16_ERR_BAD_HANDLE), a
+ * shard key (ZKG16_ERR_UNSUPPORTED), an r1cs handle that is not the template, a key that does not fit it, k == 0 or null pointers
+ * (ZKG16_ERR_BAD_ARG), a refused candidate anywhere in the batch (ZKG16_ERR_UNSUPPORTED).  On any error nothing is written. */
+ZKG16_API int zkg16_prove_prime_batch(zkg16_ctx *ctx, uint64_t pk_handle, uint64_t r1cs_handle, const uint64_t corr[36],
+                                      const uint64_t gamma_abc0_template[12], const uint64_t *xs, const uint64_t *js, size_t k,
+                                      const uint64_t *r, const uint64_t *s, uint64_t *proofs_out /* k x 48 */, uint8_t *inf_out /* k x 3 */,
+                                      uint64_t *gamma_abc0_out /* k x 12 */, uint64_t *public_inputs /* nullable, k x 257 x 4 */,
+                                      float *timings_ms /* nullable, 4 */);
 /* native Poseidon sponge hash of n Fr elements (Montgomery) — the public inputs hash_a/b/c of the matrix handler */
 ZKG16_API int zkg16_poseidon_hash(const uint64_t *elems, size_t n, uint64_t out[4]);
 /* k hashes in one call.  elems: k vectors of n Fr each (Montgomery), back to back; out[4 i ..] is byte for byte

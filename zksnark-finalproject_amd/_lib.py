@@ -115,6 +115,11 @@ SIGNATURES = {
     "zkg16_prime_r1cs_host": (C.c_int, [C.c_uint64, C.c_uint64, C.POINTER(vp * 3), C.POINTER(vp * 3), C.POINTER(vp * 3)]),
     "zkg16_r1cs_prime": (C.c_int, [ctxp, C.c_uint64, C.c_uint64, C.POINTER(H)]),
     "zkg16_witness_prime": (C.c_int, [ctxp, C.c_uint64, C.c_uint64, C.POINTER(H)]),
+    "zkg16_prime_r1cs_template_host": (C.c_int, [C.POINTER(vp * 3), C.POINTER(vp * 3), C.POINTER(vp * 3), vp]),
+    "zkg16_r1cs_prime_template": (C.c_int, [ctxp, C.POINTER(H)]),
+    "zkg16_prime_key_corrections": (C.c_int, [vp, vp, vp, vp]),
+    "zkg16_witness_prime_batch": (C.c_int, [ctxp, vp, vp, sz, vp]),
+    "zkg16_prove_prime_batch": (C.c_int, [ctxp, H, H, vp, vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp]),
     "zkg16_matrix_sponge_states": (C.c_int, [sz, u64p, u64p, vp, u64p]),
     "zkg16_matrix_sponge_states_batch": (C.c_int, [sz, vp, vp, sz, C.c_int, vp, vp]),
     "zkg16_witness_matrix_batch": (C.c_int, [ctxp, sz, vp, vp, sz, vp, vp, vp]),

@@ -132,6 +132,41 @@ def prime_r1cs_host(x, j):
                 c=(rp[2], col[2][:nnz[2]], cf[2][:nnz[2]]), num_inputs=ni.value, num_constraints=nc.value), nw.value
 
 
+def prime_r1cs_template_host():
+    """The template every candidate's R1CS is a patch of (zkg16_prime_r1cs_template_host): the j >= 1 form with the four
+    candidate-dependent column-0 coefficients zero -> (r1cs dict as SynthesizedCircuit.r1cs, num_witness, patch_rows [4]: the
+    constraint rows of the three A coefficients (n) and of the C coefficient (-j))."""
+    lib = _lib.load()
+    d = prime_dims(1)
+    nnz, nc = d["nnz"], d["num_constraints"]
+    rp = [np.zeros(nc + 1, dtype=np.uint64) for _ in range(3)]
+    col = [np.zeros(max(nnz[m], 1), dtype=np.uint32) for m in range(3)]
+    cf = [np.zeros((max(nnz[m], 1), 4), dtype=np.uint64) for m in range(3)]
+    rows = np.zeros(4, dtype=np.uint64)
+    arr = lambda xs: (C.c_void_p * 3)(*[x.ctypes.data for x in xs])
+    rc = lib.zkg16_prime_r1cs_template_host(C.byref(arr(rp)), C.byref(arr(col)), C.byref(arr(cf)), rows.ctypes.data)
+    if rc:
+        raise Zkg16Error(rc, "zkg16_prime_r1cs_template_host")
+    return dict(a=(rp[0], col[0][:nnz[0]], cf[0][:nnz[0]]), b=(rp[1], col[1][:nnz[1]], cf[1][:nnz[1]]),
+                c=(rp[2], col[2][:nnz[2]], cf[2][:nnz[2]]), num_inputs=d["num_instance"], num_constraints=nc), d["num_witness"], rows
+
+
+def prime_key_corrections(trapdoor_mont, g1_gen):
+    """What a candidate's key has over the template's for one trapdoor [5, 4] and generator g1 [12] (zkg16_prime_key_corrections,
+    host only) -> (corr [3, 12] = U | V_n | V_j affine Montgomery limbs, inf [3]): a_query[0] = template's + n U,
+    gamma_abc_g1[0] = template's + n V_n - j V_j."""
+    trap = np.ascontiguousarray(trapdoor_mont, dtype=np.uint64).reshape(-1)
+    g1 = np.ascontiguousarray(g1_gen, dtype=np.uint64).reshape(-1)
+    if trap.size != 20 or g1.size != 12:
+        raise ValueError("prime_key_corrections: trapdoor 5 x 4 limbs, g1 12 limbs")
+    corr = np.zeros((3, 12), dtype=np.uint64)
+    inf = np.zeros(3, dtype=np.uint8)
+    rc = _lib.load().zkg16_prime_key_corrections(trap.ctypes.data, g1.ctypes.data, corr.ctypes.data, inf.ctypes.data)
+    if rc:
+        raise Zkg16Error(rc, "zkg16_prime_key_corrections")
+    return corr, inf
+
+
 def matrix_circuit(a, b):
     """MatrixCircuit for u64 matrices a, b (n x n lists/arrays); public inputs = Poseidon hashes of A, B, C = A*B."""
     a = np.ascontiguousarray(a, dtype=np.uint64)

@@ -542,6 +542,41 @@ int zkg16_witness_prime(zkg16_ctx *ctx, uint64_t x, uint64_t j, uint64_t *witnes
     ZK_API_END(ctx)
 }
 
+// The template of every candidate's R1CS as a handle (marked: zkg16_prove_prime_batch takes no other), and k assignments in one pass —
+// all or nothing, as zkg16_witness_matrix_batch.
+int zkg16_r1cs_prime_template(zkg16_ctx *ctx, uint64_t *r1cs_handle) {
+    if (!r1cs_handle) return ZKG16_ERR_BAD_ARG;
+    ZK_API_BEGIN(ctx)
+    int st = ZKG16_OK;
+    std::shared_ptr<R1csDev> r = prime_r1cs_template_on_device(ctx, &st);
+    if (!r) return st;
+    *r1cs_handle = ctx->next_handle++;
+    ctx->r1cs.put(*r1cs_handle, std::move(r));
+    ZK_API_END(ctx)
+}
+int zkg16_witness_prime_batch(zkg16_ctx *ctx, const uint64_t *xs, const uint64_t *js, size_t k, uint64_t *witness_handles) {
+    if (!ctx || !xs || !js || !witness_handles || k == 0) return ZKG16_ERR_BAD_ARG;
+    std::vector<Fr> in;      // the host inputs need neither the ctx nor the device
+    try {
+        if (const int st = prime_batch_inputs(xs, js, k, in, nullptr, nullptr)) return st;
+    } catch (const std::bad_alloc &) {
+        return ZKG16_ERR_OOM;
+    }
+    ZK_API_BEGIN(ctx)
+    std::vector<std::shared_ptr<WitnessDev>> wits;
+    prime_witness_batch_assign(ctx, in.data(), k, wits, nullptr);
+    const uint64_t first = ctx->next_handle.fetch_add(k);
+    size_t put = 0;
+    try {
+        for (; put < k; put++) ctx->wits.put(first + put, std::move(wits[put]));
+    } catch (const std::bad_alloc &) {          // all or nothing: what was registered is taken back
+        for (size_t i = 0; i < put; i++) ctx->wits.erase(first + i);
+        return ZKG16_ERR_OOM;
+    }
+    for (size_t i = 0; i < k; i++) witness_handles[i] = first + i;
+    ZK_API_END(ctx)
+}
+
 // The arrays behind an r1cs handle, copied back (tests compare the device-written MatrixCircuit with the host synthesis).  Each
 // pointer may be null; sizes as at load (num_constraints + 1 row pointers, nnz columns / coefficients per matrix).
 int zkg16_r1cs_read(zkg16_ctx *ctx, uint64_t r1cs_handle, uint64_t *const row_ptr[3], uint32_t *const col[3], uint64_t *const coeff[3],

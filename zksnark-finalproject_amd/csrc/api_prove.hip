@@ -350,14 +350,34 @@ void sum_partials(Partials &p, const uint64_t *partials, const uint8_t *partial_
 
 namespace {
 
+// [k] p for a small scalar: as many doublings as k has bits (a prime candidate's n is below 2^20)
+G1XYZZ g1_mul_u64(const G1Affine &p, uint64_t k) {
+    G1XYZZ acc = G1XYZZ::inf();
+    for (int i = 63; i >= 0; i--) {
+        acc = xyzz_dbl(acc);
+        if ((k >> i) & 1) xyzz_madd(acc, p, false);
+    }
+    return acc;
+}
+// What turns a proof on the PrimeCircuit's template key into request k's (zkg16_prove_prime_batch): n[k] and -j[k] go into A z and
+// C z at the template's patch rows before the transforms (WmPatch), and n[k] U — what the request's a_query[0] has over the
+// template's, times z[0] = 1 — into the A partial before s (A + alpha) is taken.
+struct PrimeCorr {
+    const uint32_t *n;
+    const uint64_t *j;
+    G1Affine U;
+    uint32_t rows[4];
+};
+
 // ---- zkg16_prove_batch: K proofs of one circuit on one whole resident key in one device pass.  Each MSM has ONE plan over the K
 // scalar vectors (msm_plan_build with ScalarSrc::batch: one digit launch, one scatter; the K proofs' bucket sets are windows of it),
 // one accumulation, its fix-ups and one reduction chain; the witness map is one SpMV and seven transforms over all K assignments
 // (witness_map_run_batch), whose K h vectors the H plan reads in place.  The host then combines each proof's window sums and
 // finishes the proof on up to 8 threads (one with option collect_threads = 2) —
 // the same operations in the same order as prove_device + prove_tail, so proof k is byte-identical to zkg16_prove_resident's.
+// pc: the per-proof corrections of proofs on the PrimeCircuit's template key (PrimeCorr).
 void prove_batch_device(zkg16_ctx *ctx, PkDev &pk, R1csDev &rc, WitnessDev *const *wits, size_t K, const Fr *r, const Fr *s,
-                        uint64_t *proofs_out, uint8_t *inf_out) {
+                        uint64_t *proofs_out, uint8_t *inf_out, const PrimeCorr *pc = nullptr) {
     const size_t N = (size_t)1 << rc.log_n;
     const size_t nh = N - 1;
     if (pk.z_lo != 0 || !pk.full) throw HipError{hipErrorInvalidValue, "prove_batch: a shard key", __FILE__, __LINE__};
@@ -365,9 +385,10 @@ void prove_batch_device(zkg16_ctx *ctx, PkDev &pk, R1csDev &rc, WitnessDev *cons
     hipEvent_t *ev = evs.ev;
     DrainOnError drain{ctx};
     const double t0 = now_ms();
-    // pinned, device-visible: the 3K extra scalars (r, s, -rs of every proof) and the K assignment pointers, read by the digit
-    // kernel in place; rewritten only by the next batch on this lane, which starts after this one has been collected
-    const size_t host_bytes = 3 * K * sizeof(Fr) + K * sizeof(void *);
+    // pinned, device-visible: the 3K extra scalars (r, s, -rs of every proof), the K x 2 patch values (n, -j: template proofs only) and
+    // the K assignment pointers, read by the kernels in place; rewritten only by the next batch on this lane, which starts after this
+    // one has been collected
+    const size_t host_bytes = (3 + 2) * K * sizeof(Fr) + K * sizeof(void *);
     if (ctx->batch_host_bytes < host_bytes) {
         if (ctx->batch_host) (void)hipHostFree(ctx->batch_host);
         ctx->batch_host = nullptr;
@@ -376,7 +397,18 @@ void prove_batch_device(zkg16_ctx *ctx, PkDev &pk, R1csDev &rc, WitnessDev *cons
         ctx->batch_host_bytes = host_bytes;
     }
     Fr *extra = reinterpret_cast<Fr *>(ctx->batch_host);
-    const Fr **vecs = reinterpret_cast<const Fr **>(extra + 3 * K);
+    Fr *patch_tab = extra + 3 * K;
+    const Fr **vecs = reinterpret_cast<const Fr **>(extra + 5 * K);
+    WmPatch patch{{0, 0, 0, 0}, patch_tab};
+    for (size_t k = 0; pc && k < K; k++) {
+        Fr c = Fr::zero();
+        c.l[0] = pc->n[k];
+        patch_tab[2 * k] = fp_to_mont(c);
+        c.l[0] = (uint32_t)pc->j[k];
+        c.l[1] = (uint32_t)(pc->j[k] >> 32);
+        patch_tab[2 * k + 1] = fp_neg(fp_to_mont(c));
+    }
+    if (pc) memcpy(patch.rows, pc->rows, sizeof patch.rows);
     for (size_t k = 0; k < K; k++) {
         extra[3 * k] = pk.blinding ? r[k] : Fr::zero();
         extra[3 * k + 1] = pk.blinding ? s[k] : Fr::zero();
@@ -399,8 +431,8 @@ void prove_batch_device(zkg16_ctx *ctx, PkDev &pk, R1csDev &rc, WitnessDev *cons
         WmStreamSwap on_wm_stream(ctx);
         ZK_HIP(hipEventRecord(ev[2], ctx->stream));
         Fr *hv = nullptr;
-        if (K == 1) witness_map_run(ctx, rc, wits[0]->z.as<Fr>(), &hv);
-        else witness_map_run_batch(ctx, rc, vecs, (unsigned)K, &hv);      // vecs: the K assignments (z_lo = 0)
+        if (K == 1) witness_map_run(ctx, rc, wits[0]->z.as<Fr>(), &hv, pc ? &patch : nullptr);
+        else witness_map_run_batch(ctx, rc, vecs, (unsigned)K, &hv, pc ? &patch : nullptr);      // vecs: the K assignments (z_lo = 0)
         ZK_HIP(hipEventRecord(ev[3], ctx->stream));
         ScalarSrc hsrc{hv + pk.h_lo, nh, nullptr, 0, true, nullptr};
         hsrc.vec_stride = N;
@@ -450,6 +482,7 @@ void prove_batch_device(zkg16_ctx *ctx, PkDev &pk, R1csDev &rc, WitnessDev *cons
         p.b2 = msm_g2_collect_part(ctx->slots[0], (int)k);
         p.l = msm_g1_collect_part(ctx->slots[2], (int)k);
         p.a = msm_g1_collect_part(ctx->slots[3], (int)k);
+        if (pc) xyzz_add(p.a, g1_mul_u64(pc->U, pc->n[k]));
         p.b1 = msm_g1_collect_part(ctx->slots[4], (int)k);
         if (pk.full) {
             p.s_a = early_s_a(pk, p.a, s[k]);
@@ -747,6 +780,63 @@ int zkg16_prove_matrix_batch(zkg16_ctx *ctx, uint64_t pk_handle, uint64_t r1cs_h
     if (public_inputs) memcpy(public_inputs, pubs.data(), pubs.size() * sizeof(uint64_t));
     if (timings_ms) {
         timings_ms[0] = (float)chain_ms;
+        timings_ms[1] = (float)wit_ms;
+        timings_ms[2] = prove_ms;
+        timings_ms[3] = (float)(now_ms() - t_call);
+    }
+    ZK_LANE_END(ctx)
+}
+
+// K prime requests on the template key: every request's inputs first (a refused candidate ends the call before any device work),
+// then per sub-batch the batched assignment (prime_device.hip) and prove_batch_device with the per-proof corrections; the
+// assignments go back after each sub-batch.  Each request's gamma_abc_g1[0] is formed on the host.  Everything is staged and
+// written only when every sub-batch has succeeded.
+int zkg16_prove_prime_batch(zkg16_ctx *ctx, uint64_t pk_handle, uint64_t r1cs_handle, const uint64_t corr[36], const uint64_t gamma_abc0_template[12],
+                            const uint64_t *xs, const uint64_t *js, size_t k, const uint64_t *r, const uint64_t *s, uint64_t *proofs_out,
+                            uint8_t *inf_out, uint64_t *gamma_abc0_out, uint64_t *public_inputs, float *timings_ms) {
+    if (!corr || !gamma_abc0_template || !xs || !js || !r || !s || !proofs_out || !inf_out || !gamma_abc0_out || k == 0) return ZKG16_ERR_BAD_ARG;
+    const double t_call = now_ms();
+    ZK_LANE_BEGIN(ctx)
+    ProveHandles h;
+    if (const int st = lookup_handles(root, pk_handle, r1cs_handle, nullptr, 0, Shard::unsupported, 0, h)) return st;
+    if (!h.rc->prime_template) return ZKG16_ERR_BAD_ARG;
+    if (k > SIZE_MAX / (257 * 4 * sizeof(uint64_t))) return ZKG16_ERR_BAD_ARG;
+    std::vector<Fr> in;
+    std::vector<uint32_t> ns(k);
+    size_t stride = 0;
+    const double t_in = now_ms();
+    if (const int st = prime_batch_inputs(xs, js, k, in, ns.data(), &stride)) return st;
+    const double in_ms = now_ms() - t_in;
+    PrimeCorr pc;
+    pc.U = g1_from_abi(corr, 0);
+    memcpy(pc.rows, h.rc->patch_rows, sizeof pc.rows);
+    const G1Affine v_n = g1_from_abi(corr + 12, 0), v_j = g1_from_abi(corr + 24, 0), g0 = g1_from_abi(gamma_abc0_template, 0);
+    const std::vector<Fr> rr = frs_from_abi(r, k), ss = frs_from_abi(s, k);
+    std::vector<uint64_t> gammas(12 * k), pubs(public_inputs ? 257 * 4 * k : 0);
+    double wit_ms = 0;
+    const float prove_ms = prove_in_passes(ctx, h.pk.get(), h.rc.get(), k, h.rc->num_variables * sizeof(Fr), proofs_out, inf_out,
+                                           [&](size_t off, size_t nb, uint64_t *proofs, uint8_t *infs) {
+        std::vector<std::shared_ptr<WitnessDev>> wit_refs;
+        float dev_ms = 0;
+        prime_witness_batch_assign(ctx, in.data() + off * stride, nb, wit_refs, &dev_ms);
+        wit_ms += dev_ms;
+        std::vector<WitnessDev *> wits(nb);
+        for (size_t i = 0; i < nb; i++) wits[i] = wit_refs[i].get();
+        pc.n = ns.data() + off;
+        pc.j = js + off;
+        prove_batch_device(ctx, *h.pk, *h.rc, wits.data(), nb, rr.data() + off, ss.data() + off, proofs, infs, &pc);
+    });
+    for (size_t i = 0; i < k; i++) {      // gamma_abc_g1[0] = the template's + n V_n - j V_j
+        G1XYZZ g = G1XYZZ::from_affine(g0);
+        xyzz_add(g, g1_mul_u64(v_n, ns[i]));
+        xyzz_add(g, xyzz_neg(g1_mul_u64(v_j, js[i])));
+        point_to_abi(xyzz_to_affine(g), gammas.data() + 12 * i, nullptr);
+        if (public_inputs) (void)zkg16_prime_public_inputs(xs[i], js[i], pubs.data() + 257 * 4 * i);      // fails on a null pointer only
+    }
+    memcpy(gamma_abc0_out, gammas.data(), gammas.size() * sizeof(uint64_t));
+    if (public_inputs) memcpy(public_inputs, pubs.data(), pubs.size() * sizeof(uint64_t));
+    if (timings_ms) {
+        timings_ms[0] = (float)in_ms;
         timings_ms[1] = (float)wit_ms;
         timings_ms[2] = prove_ms;
         timings_ms[3] = (float)(now_ms() - t_call);

@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "../../include/zkg16.h"
+#include "ec.cuh"
 #include "ff.cuh"
 #include "matrix_plan.hpp"
 #include "prime_program.hpp"
@@ -1144,9 +1145,11 @@ std::shared_ptr<const PrimeProgram> prime_record(uint64_t x, uint64_t j, const P
     for (int k = 0; k < 3; k++) {
         const size_t r = rec.exp_rows[k];
         P->a_pos[k] = P->rp[0][r];
+        P->patch_rows[k] = (uint32_t)r;
         if (P->rp[0][r + 1] <= P->a_pos[k] || P->col[0][P->a_pos[k]] != 0 || P->cf[0][P->a_pos[k]] != fr_from_u64(cand.n)) prime_record_fail("A patch");
     }
     P->c_pos = P->rp[2][rec.pack_row];
+    P->patch_rows[3] = (uint32_t)rec.pack_row;
     if (P->rp[2][rec.pack_row + 1] <= P->c_pos || P->col[2][P->c_pos] != 0 || P->cf[2][P->c_pos] != fp_neg(fr_from_u64(j))) prime_record_fail("C patch");
     P->rp_c_j0 = P->rp[2];
     for (size_t r = rec.pack_row + 1; r <= P->num_constraints; r++) P->rp_c_j0[r]--;
@@ -1263,6 +1266,63 @@ int zkg16_prime_r1cs_host(uint64_t x, uint64_t j, uint64_t *const row_ptr[3], ui
     if (j != 0) {
         const Fr mj = fp_neg(fr_from_u64(j));
         memcpy(coeff[2] + 4 * P->c_pos, mj.l, 32);
+    }
+    return ZKG16_OK;
+}
+
+// The template every candidate's R1CS is a patch of: the j >= 1 form (dimensions of zkg16_prime_r1cs_dims(1, ...)) with the four
+// candidate-dependent coefficients — column 0 of rows patch_rows[0..2] in A (n), of row patch_rows[3] in C (-j) — set to zero.
+int zkg16_prime_r1cs_template_host(uint64_t *const row_ptr[3], uint32_t *const col[3], uint64_t *const coeff[3], uint64_t patch_rows[4]) {
+    if (!row_ptr || !col || !coeff || !patch_rows) return ZKG16_ERR_BAD_ARG;
+    for (int m = 0; m < 3; m++)
+        if (!row_ptr[m] || !col[m] || !coeff[m]) return ZKG16_ERR_BAD_ARG;
+    std::shared_ptr<const PrimeProgram> P;
+    if (const int rc = prime_program(P)) return rc;
+    for (int m = 0; m < 3; m++) {
+        memcpy(row_ptr[m], P->rp[m].data(), P->rp[m].size() * sizeof(uint64_t));
+        memcpy(col[m], P->col[m].data(), P->col[m].size() * sizeof(uint32_t));
+        memcpy(coeff[m], P->cf[m].data(), P->cf[m].size() * sizeof(Fr));
+    }
+    for (int k = 0; k < 3; k++) memset(coeff[0] + 4 * P->a_pos[k], 0, 32);
+    memset(coeff[2] + 4 * P->c_pos, 0, 32);
+    for (int k = 0; k < 4; k++) patch_rows[k] = P->patch_rows[k];
+    return ZKG16_OK;
+}
+
+// What a candidate's key adds to the template's for one trapdoor (tau | alpha | beta | gamma | delta) and generator g1:
+// a_query[0] += n U, gamma_abc_g1[0] += n V_n - j V_j with U = [u] g1, V_n = [beta u / gamma] g1, V_j = [w / gamma] g1,
+// u = L_r1(tau) + L_r2(tau) + L_r3(tau), w = L_r4(tau), L_i(tau) = (tau^N - 1) omega^i / (N (tau - omega^i)) — the column-0 sums the
+// setup forms over the four patched rows.  Host field and curve code (ff.cuh / ec.cuh); nothing of the trapdoor is kept.
+int zkg16_prime_key_corrections(const uint64_t trapdoor[20], const uint64_t g1_gen[12], uint64_t corr_out[36], uint8_t inf_out[3]) {
+    if (!trapdoor || !g1_gen || !corr_out || !inf_out) return ZKG16_ERR_BAD_ARG;
+    std::shared_ptr<const PrimeProgram> P;
+    if (const int rc = prime_program(P)) return rc;
+    Fr trap[5];
+    memcpy(trap, trapdoor, sizeof trap);
+    G1Affine g1;
+    memcpy(&g1, g1_gen, sizeof g1);
+    const Fr &tau = trap[0], &beta = trap[2], &gamma = trap[3];
+    if (gamma.is_zero() || g1.is_inf()) return ZKG16_ERR_BAD_ARG;
+    int log_n = 0;
+    while (((size_t)1 << log_n) < P->num_constraints + P->num_instance) log_n++;
+    Fr zt = tau;
+    for (int i = 0; i < log_n; i++) zt = fp_sqr(zt);
+    zt = fp_sub(zt, Fr::one());                                  // Z(tau) = tau^N - 1
+    if (zt.is_zero()) return ZKG16_ERR_BAD_ARG;                  // tau in the domain: the setup refuses it too
+    const Fr omega = fr_root_of_unity(log_n), scale = fp_mul(zt, fp_inv(fr_from_u64((uint64_t)1 << log_n)));
+    Fr lag[4];
+    for (int k = 0; k < 4; k++) {
+        const Fr wi = fp_pow_u64(omega, P->patch_rows[k]);
+        lag[k] = fp_mul(fp_mul(scale, wi), fp_inv(fp_sub(tau, wi)));
+    }
+    const Fr ginv = fp_inv(gamma);
+    const Fr u = fp_add(fp_add(lag[0], lag[1]), lag[2]);
+    const Fr sc[3] = {u, fp_mul(fp_mul(beta, u), ginv), fp_mul(lag[3], ginv)};
+    for (int k = 0; k < 3; k++) {
+        const G1Affine pt = xyzz_to_affine(xyzz_mul(G1XYZZ::from_affine(g1), fp_from_mont(sc[k]).l));
+        if (pt.is_inf()) memset(corr_out + 12 * k, 0, sizeof pt);
+        else memcpy(corr_out + 12 * k, &pt, sizeof pt);
+        inf_out[k] = pt.is_inf() ? 1 : 0;
     }
     return ZKG16_OK;
 }

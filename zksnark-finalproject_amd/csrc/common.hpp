@@ -163,6 +163,10 @@ struct R1csDev {
     // (from_perm), else natural; one per share this handle has served (under lazy_mu)
     struct RowShare { uint64_t m = 0, lo = 0, hi = 0; bool from_perm = false; DevBuf list[3]; size_t n[3] = {0, 0, 0}; };
     std::vector<std::shared_ptr<RowShare>> row_shares;
+    // the PrimeCircuit's template (zkg16_r1cs_prime_template): the four column-0 coefficients that differ between candidates are
+    // zero, and a request's n / -j go into A z (rows patch_rows[0..2]) and C z (row patch_rows[3]) after the SpMV (WmPatch)
+    bool prime_template = false;
+    uint32_t patch_rows[4] = {0, 0, 0, 0};
 };
 
 // backing: set when z is a view into an allocation several assignments share (zkg16_witness_matrix_batch: one per batch); the view is
@@ -408,8 +412,11 @@ void spmv_run(zkg16_ctx *ctx, R1csDev &m, const Fr *z, Fr *a, Fr *b, Fr *c, cons
               unsigned nvec = 1);
 void pointwise_h_run(zkg16_ctx *ctx, Fr *ab_a, const Fr *b, const Fr *c /* null: ab only */, const Fr &zinv, size_t n);
 void fr_from_mont_run(zkg16_ctx *ctx, const Fr *in, Fr *out, size_t n);
-void witness_map_run(zkg16_ctx *ctx, R1csDev &m, const Fr *z, Fr **h_out);
-void witness_map_run_batch(zkg16_ctx *ctx, R1csDev &m, const Fr *const *zs, unsigned nvec, Fr **h_out);
+// patch (proofs on the PrimeCircuit's template): between the SpMV and the transforms vector v gets add[2 v] added to a[rows[0..2]] and
+// add[2 v + 1] to c[rows[3]] (wm_patch_kernel); add is a device-visible table of nvec x 2 Montgomery values
+struct WmPatch { uint32_t rows[4]; const Fr *add; };
+void witness_map_run(zkg16_ctx *ctx, R1csDev &m, const Fr *z, Fr **h_out, const WmPatch *patch = nullptr);
+void witness_map_run_batch(zkg16_ctx *ctx, R1csDev &m, const Fr *const *zs, unsigned nvec, Fr **h_out, const WmPatch *patch = nullptr);
 
 // Scalar-vector side of Pippenger (shared by every MSM over the same scalars).
 struct MsmPlan {
@@ -488,6 +495,15 @@ std::shared_ptr<R1csDev> matrix_r1cs_on_device(zkg16_ctx *ctx, size_t n, int *st
 // zkg16_status when the result is null; ZKG16_ERR_UNSUPPORTED for the candidates zkg16_circuit_prime refuses)
 std::shared_ptr<R1csDev> prime_r1cs_on_device(zkg16_ctx *ctx, uint64_t x, uint64_t j, int *status);
 std::shared_ptr<WitnessDev> prime_witness_on_device(zkg16_ctx *ctx, uint64_t x, uint64_t j, int *status);
+// the template (the j >= 1 form with the four candidate-dependent coefficients zero) as an R1csDev marked prime_template
+std::shared_ptr<R1csDev> prime_r1cs_template_on_device(zkg16_ctx *ctx, int *status);
+// k assignments in one pass.  prime_batch_inputs (host only): request i's slots | sources at in[i * stride ..) and its n in ns
+// (nullable) — or the status of the first refused candidate, nothing written.  prime_witness_batch_assign: on ctx->stream (a
+// lane's, or the root's under its mutex) one upload of those inputs and the z addresses out of the ctx's pinned staging, the two
+// batched launches, one synchronisation; the assignments share one allocation (WitnessDev::backing).  Throws HipError (the stream
+// drained) / std::bad_alloc.
+int prime_batch_inputs(const uint64_t *xs, const uint64_t *js, size_t k, std::vector<Fr> &in, uint32_t *ns, size_t *stride);
+void prime_witness_batch_assign(zkg16_ctx *ctx, const Fr *in, size_t k, std::vector<std::shared_ptr<WitnessDev>> &out, float *dev_ms);
 
 // witness.hip: the MatrixCircuit's assignment arriving on the device in parts (zkg16_witness_matrix: all at once;
 // zkg16_prove_matrix: while the proof is already running).  slices_wanted gadget slices -> parts = slices + 1.

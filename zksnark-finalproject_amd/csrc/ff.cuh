@@ -353,6 +353,15 @@ ZK_HD Fp<P> fp_inv(const Fp<P> &a) {
 using Fr = Fp<FrP>;
 using Fq = Fp<FqP>;
 
+// the 2^32-th root of unity 7^((r-1)/2^32) (Montgomery) squared down to order 2^log_n: omega_N of the NTT domain (host)
+inline Fr fr_root_of_unity(int log_n) {
+    const uint32_t R32[8] = {0x5f0e466au, 0xb9b58d8cu, 0x1819d7ecu, 0x5b1b4c80u, 0x52a31e64u, 0x0af53ae3u, 0x19e9b27bu, 0x5bf3addau};
+    Fr root;
+    for (int i = 0; i < 8; i++) root.l[i] = R32[i];
+    for (int i = log_n; i < 32; i++) root = fp_sqr(root);
+    return root;
+}
+
 #if defined(__HIP_DEVICE_COMPILE__)
 // Every translation unit that multiplies in Fq on the device gets its own (internal-linkage-free, weak)
 // copy of the callee: HIP code objects are linked per TU (no -fgpu-rdc).

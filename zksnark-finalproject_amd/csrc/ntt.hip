@@ -666,13 +666,7 @@ NttTables *ntt_get_tables(zkg16_ctx *ctx, int log_n) {
     auto t = std::make_unique<NttTables>();
     t->log_n = log_n;
     const size_t n = (size_t)1 << log_n;
-    // 2^32-th root of unity 7^((r-1)/2^32) (Montgomery), squared down to order N
-    Fr root;
-    {
-        const uint32_t R32[8] = {0x5f0e466au, 0xb9b58d8cu, 0x1819d7ecu, 0x5b1b4c80u, 0x52a31e64u, 0x0af53ae3u, 0x19e9b27bu, 0x5bf3addau};
-        for (int i = 0; i < 8; i++) root.l[i] = R32[i];
-        for (int i = log_n; i < 32; i++) root = fp_sqr(root);
-    }
+    const Fr root = fr_root_of_unity(log_n);
     const Fr g = fr_from_u64_host(7);
     const Fr g_inv = fp_inv(g);
     t->n_inv = fp_inv(fr_from_u64_host((uint64_t)n));

@@ -464,6 +464,27 @@ void fr_from_mont_run(zkg16_ctx *ctx, const Fr *in, Fr *out, size_t n) {
     ZK_HIP(hipGetLastError());
 }
 
+// Proofs on the PrimeCircuit's template (WmPatch): the request's four column-0 coefficients are not in the matrices, and z[0] = 1, so
+// their products are added to the SpMV's results here — add[2 v] to a[rows[0..2]], add[2 v + 1] to c[rows[3]] of vector v.  Four
+// lanes per vector, one element each (distinct constraint rows, checked at the launch); before any transform, so
+// both sequences of wm_transforms see the request's A z and C z.
+__global__ void __launch_bounds__(256) wm_patch_kernel(Fr *a, Fr *c, size_t stride, WmPatch p, unsigned nvec) {
+    const unsigned t = blockIdx.x * blockDim.x + threadIdx.x;
+    const unsigned v = t >> 2, k = t & 3u;
+    if (v >= nvec) return;
+    Fr *dst = (k < 3 ? a : c) + (size_t)v * stride + p.rows[k];
+    gst_fr(dst, fp_add(gld_fr(dst), gld_fr(p.add + 2 * (size_t)v + (k < 3 ? 0 : 1))));
+}
+static void wm_patch_run(zkg16_ctx *ctx, const R1csDev &m, Fr *a, Fr *c, const WmPatch &p, unsigned nvec) {
+    const size_t n = (size_t)1 << m.log_n;
+    for (int k = 0; k < 4; k++)
+        if (p.rows[k] >= m.num_constraints) throw HipError{hipErrorInvalidValue, "witness map: patch row outside the constraints", __FILE__, __LINE__};
+    if (p.rows[0] == p.rows[1] || p.rows[0] == p.rows[2] || p.rows[1] == p.rows[2]) throw HipError{hipErrorInvalidValue, "witness map: patch rows repeat", __FILE__, __LINE__};
+    ScopedKernelTimer kt(ctx, "wm_patch_kernel", 4.0 * nvec);
+    hipLaunchKernelGGL(wm_patch_kernel, dim3((4 * nvec + 255) / 256), dim3(256), 0, ctx->stream, a, c, n, p, nvec);
+    ZK_HIP(hipGetLastError());
+}
+
 // The transforms of the witness map on the SpMV's a, b, c (nvec vectors of N side by side, tmp the scratch) -> h (= tmp).  They
 // ping-pong between each vector and the one scratch buffer (ifft: x -> tmp, coset fft: tmp -> x), and the point-wise stage rides
 // on the load of the last transform: no device-to-device copy and no separate point-wise pass (round 1 had both).
@@ -502,22 +523,24 @@ static Fr *wm_transforms(zkg16_ctx *ctx, int log_n, Fr *a, Fr *b, Fr *c, Fr *tmp
 }
 
 // h of one assignment, N Montgomery coefficients.  Result pointer = ctx->poly[3].
-void witness_map_run(zkg16_ctx *ctx, R1csDev &m, const Fr *z, Fr **h_out) {
+void witness_map_run(zkg16_ctx *ctx, R1csDev &m, const Fr *z, Fr **h_out, const WmPatch *patch) {
     const size_t n = (size_t)1 << m.log_n;
     for (int i = 0; i < 4; i++) ctx->poly[i].ensure(n * sizeof(Fr));
     Fr *a = ctx->poly[0].as<Fr>(), *b = ctx->poly[1].as<Fr>(), *c = ctx->poly[2].as<Fr>(), *tmp = ctx->poly[3].as<Fr>();
     spmv_run(ctx, m, z, a, b, c);
+    if (patch) wm_patch_run(ctx, m, a, c, *patch, 1);
     *h_out = wm_transforms(ctx, m.log_n, a, b, c, tmp, 1);
 }
 
 // The witness map of a batch: the K assignments at zs[0 .. K) (device-visible pointer table), every launch of witness_map_run
 // once over the K vectors — one SpMV, the transform passes with grid.z = K (shared tables, the fused point-wise stage per
 // vector).  a, b, c and the scratch hold K vectors of N side by side; *h_out = K h vectors of N, vector v at (*h_out) + v * N.
-void witness_map_run_batch(zkg16_ctx *ctx, R1csDev &m, const Fr *const *zs, unsigned nvec, Fr **h_out) {
+void witness_map_run_batch(zkg16_ctx *ctx, R1csDev &m, const Fr *const *zs, unsigned nvec, Fr **h_out, const WmPatch *patch) {
     const size_t n = (size_t)1 << m.log_n;
     for (int i = 0; i < 4; i++) ctx->poly[i].ensure((size_t)nvec * n * sizeof(Fr));
     Fr *a = ctx->poly[0].as<Fr>(), *b = ctx->poly[1].as<Fr>(), *c = ctx->poly[2].as<Fr>(), *tmp = ctx->poly[3].as<Fr>();
     spmv_run(ctx, m, nullptr, a, b, c, nullptr, zs, nvec);
+    if (patch) wm_patch_run(ctx, m, a, c, *patch, nvec);
     *h_out = wm_transforms(ctx, m.log_n, a, b, c, tmp, nvec);
 }
 

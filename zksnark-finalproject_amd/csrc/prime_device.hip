@@ -14,12 +14,18 @@
 //   base k         73,098         54,389      639     (x 3; two compressions each: the largest LDS footprint, 73 KB)
 //   Fermat k       20,569         20,360       49     (x 3; 40 unchecked comparisons = 40 x to_bits_le)
 // (an addmany is ONE instruction for all its result bits, so a part has fewer instructions than witnesses; its slots have none)
+// K requests in one pass (prime_witness_batch_on_device): the K x (slots | sources) go up in ONE copy out of pinned staging,
+// prime_witness_eval_batch_kernel runs the program on a (part, request) grid — the 639 barrier levels of a base part are latency, not
+// work, and K requests fill the device where one fills seven CUs — and prime_witness_expand_batch_kernel writes the K assignments,
+// which share one allocation, through a table of their addresses.
 #include "common.hpp"
 #include "prime_program.hpp"
 
 using namespace zk;
 
 namespace zk {
+
+void mbatch_staging_ensure(zkg16_ctx *ctx, size_t bytes);      // witness.hip: the ctx's pinned staging block and its device copy
 
 struct PrimeDev {
     std::shared_ptr<const PrimeProgram> prog;
@@ -70,6 +76,51 @@ __global__ void __launch_bounds__(256) prime_witness_expand_kernel(const uint32_
     z[t] = v;
 }
 
+// The same on a (part, request) grid: request r reads its sources at in + r * in_stride + n_slots and writes its bits at
+// bits + r * num_witness.  grid.y is capped (option "matrix_batch_grid", else 65,535): a workgroup then takes requests blockIdx.y,
+// blockIdx.y + gridDim.y, ... one after another — every lane of it the same number, so the barriers stay uniform.
+struct EvalBatchArgs {
+    EvalArgs e;                                // src / bits: request 0's
+    size_t in_stride, num_witness, k;
+};
+__global__ void __launch_bounds__(1024) prime_witness_eval_batch_kernel(EvalBatchArgs g) {
+    extern __shared__ uint8_t sb[];
+    const int p = blockIdx.x;
+    const uint32_t lo = g.e.wit_base[p], n = g.e.wit_base[p + 1] - lo;
+    for (size_t r = blockIdx.y; r < g.k; r += gridDim.y) {
+        const Fr *src = g.e.src + r * g.in_stride;
+        uint8_t *bits = g.e.bits + r * g.num_witness;
+        for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) sb[i] = 0;
+        __syncthreads();
+        for (uint32_t L = g.e.lvl_base[p]; L < g.e.lvl_base[p + 1]; L++) {
+            const uint32_t e = g.e.lvl[L + 1];
+            for (uint32_t i = g.e.lvl[L] + threadIdx.x; i < e; i += blockDim.x) prime_exec(g.e.ins[i], sb, g.e.terms, src);
+            __syncthreads();
+        }
+        for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) bits[lo + i] = sb[i];
+        __syncthreads();                       // the next request clears the bits this one is still writing out
+    }
+}
+
+// prime_witness_expand_kernel for K requests: z[r] is request r's assignment (a table of addresses into one allocation); both grid
+// dimensions are capped as above and loop beyond
+__global__ void __launch_bounds__(256) prime_witness_expand_batch_kernel(const uint32_t *code, const uint8_t *bits, const Fr *in, Fr *const *z,
+                                                                         uint64_t halves, size_t k, size_t in_stride, size_t num_witness) {
+    const Fr one = Fr::one();
+    for (size_t r = blockIdx.y; r < k; r += gridDim.y) {
+        const uint8_t *rb = bits + r * num_witness;
+        const Fr *slots = in + r * in_stride;
+        uint4 *zr = reinterpret_cast<uint4 *>(z[r]);
+        for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < halves; t += (uint64_t)gridDim.x * blockDim.x) {
+            const uint32_t c = code[t >> 1], h = (uint32_t)t & 1u;
+            uint4 v = make_uint4(0, 0, 0, 0);
+            if (c & PRIME_SLOT) v = reinterpret_cast<const uint4 *>(slots + (c & ~PRIME_SLOT))[h];
+            else if (rb[c]) v = make_uint4(one.l[4 * h], one.l[4 * h + 1], one.l[4 * h + 2], one.l[4 * h + 3]);
+            zr[t] = v;
+        }
+    }
+}
+
 template <class T>
 void upload(zkg16_ctx *ctx, DevBuf &b, const std::vector<T> &v) {
     b.alloc(v.size() * sizeof(T));
@@ -95,6 +146,7 @@ std::shared_ptr<PrimeDev> prime_dev_get(zkg16_ctx *ctx, int *status) {
     upload(ctx, d->terms, P->terms);
     upload(ctx, d->code, P->code);
     ZK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(prime_witness_eval_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)P->max_part));
+    ZK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(prime_witness_eval_batch_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)P->max_part));
     ZK_HIP(hipStreamSynchronize(ctx->stream));
     root->prime_dev = d;
     return d;
@@ -153,6 +205,127 @@ std::shared_ptr<R1csDev> prime_r1cs_on_device(zkg16_ctx *ctx, uint64_t x, uint64
     if (j != 0) ZK_HIP(hipMemcpyAsync(r->cf[2].as<Fr>() + P.c_pos, &mj, sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
     ZK_HIP(hipStreamSynchronize(ctx->stream));      // fn / mj are read by the copies above
     return r;
+}
+
+std::shared_ptr<R1csDev> prime_r1cs_template_on_device(zkg16_ctx *ctx, int *status) {
+    *status = ZKG16_OK;
+    std::shared_ptr<PrimeDev> D = prime_dev_get(ctx, status);
+    if (!D) return nullptr;
+    const PrimeProgram &P = *D->prog;
+    const size_t nc = P.num_constraints;
+    int log_n = 0;
+    while (((size_t)1 << log_n) < nc + P.num_instance) log_n++;
+    auto r = std::make_shared<R1csDev>();
+    r->num_instance = P.num_instance;
+    r->num_constraints = nc;
+    r->num_variables = P.num_instance + P.num_witness;
+    r->log_n = log_n;
+    r->prime_template = true;
+    for (int k = 0; k < 4; k++) r->patch_rows[k] = P.patch_rows[k];
+    for (int m = 0; m < 3; m++) {
+        const size_t nnz = P.col[m].size();
+        r->nnz[m] = nnz;
+        r->rp[m].alloc((nc + 1) * sizeof(uint64_t));
+        r->col[m].alloc(nnz * sizeof(uint32_t));
+        r->cf[m].alloc(nnz * sizeof(Fr));
+        ZK_HIP(hipMemcpyAsync(r->rp[m].p, D->rp[m].p, (nc + 1) * sizeof(uint64_t), hipMemcpyDeviceToDevice, ctx->stream));
+        ZK_HIP(hipMemcpyAsync(r->col[m].p, D->col[m].p, nnz * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
+        ZK_HIP(hipMemcpyAsync(r->cf[m].p, D->cf[m].p, nnz * sizeof(Fr), hipMemcpyDeviceToDevice, ctx->stream));
+    }
+    for (int k = 0; k < 3; k++) ZK_HIP(hipMemsetAsync(r->cf[0].as<Fr>() + P.a_pos[k], 0, sizeof(Fr), ctx->stream));
+    ZK_HIP(hipMemsetAsync(r->cf[2].as<Fr>() + P.c_pos, 0, sizeof(Fr), ctx->stream));
+    ZK_HIP(hipStreamSynchronize(ctx->stream));
+    return r;
+}
+
+int prime_batch_inputs(const uint64_t *xs, const uint64_t *js, size_t k, std::vector<Fr> &in, uint32_t *ns, size_t *stride) {
+    std::shared_ptr<const PrimeProgram> Pp;
+    if (const int st = prime_program(Pp)) return st;
+    const PrimeProgram &P = *Pp;
+    const size_t in_stride = P.n_slots + P.n_sources;
+    if (k == 0 || k > SIZE_MAX / ((P.num_instance + P.num_witness) * sizeof(Fr))) return ZKG16_ERR_BAD_ARG;
+    std::vector<Fr> all(k * in_stride), slots, src;
+    std::vector<uint32_t> n(k);
+    for (size_t i = 0; i < k; i++) {
+        if (const int st = prime_inputs(P, xs[i], js[i], slots, src, &n[i])) return st;
+        memcpy(all.data() + i * in_stride, slots.data(), P.n_slots * sizeof(Fr));
+        memcpy(all.data() + i * in_stride + P.n_slots, src.data(), P.n_sources * sizeof(Fr));
+    }
+    in.swap(all);
+    if (ns) memcpy(ns, n.data(), k * sizeof(uint32_t));
+    if (stride) *stride = in_stride;
+    return ZKG16_OK;
+}
+
+void prime_witness_batch_assign(zkg16_ctx *ctx, const Fr *in, size_t k, std::vector<std::shared_ptr<WitnessDev>> &out, float *dev_ms) {
+    zkg16_ctx *root = ctx->root ? ctx->root : ctx;
+    int status = ZKG16_OK;
+    // a lane gets here only with the template's handle in hand, which was made from the resident copy: it exists
+    std::shared_ptr<PrimeDev> D = ctx == root ? prime_dev_get(ctx, &status) : root->prime_dev;
+    if (!D) throw HipError{hipErrorInvalidValue, "prime batch: no resident program", __FILE__, __LINE__};
+    const PrimeProgram &P = *D->prog;
+    const size_t in_stride = P.n_slots + P.n_sources, total = P.num_instance + P.num_witness;
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t in_bytes = up(k * in_stride * sizeof(Fr)), bytes = in_bytes + up(k * sizeof(Fr *));
+    const size_t cap = ctx->opt.matrix_batch_grid > 0 ? (size_t)ctx->opt.matrix_batch_grid : 65535;
+    mbatch_staging_ensure(ctx, bytes);
+    auto backing = std::make_shared<DevBuf>(k * total * sizeof(Fr));
+    std::vector<std::shared_ptr<WitnessDev>> wits(k);
+    for (size_t i = 0; i < k; i++) {
+        wits[i] = std::make_shared<WitnessDev>();
+        wits[i]->n = total;
+        wits[i]->backing = backing;
+        wits[i]->z.p = backing->as<Fr>() + i * total;
+        wits[i]->z.bytes = total * sizeof(Fr);
+    }
+    DevBuf d_bits(k * P.num_witness);
+    uint8_t *hs = static_cast<uint8_t *>(ctx->mbatch_host), *ds = ctx->mbatch_dev.as<uint8_t>();
+    memcpy(hs, in, k * in_stride * sizeof(Fr));
+    Fr **h_tab = reinterpret_cast<Fr **>(hs + in_bytes);
+    for (size_t i = 0; i < k; i++) h_tab[i] = wits[i]->z.as<Fr>();
+
+    hipEvent_t e0, e1;
+    ZK_HIP(hipEventCreate(&e0));
+    struct EvGuard { hipEvent_t e; ~EvGuard() { (void)hipEventDestroy(e); } } g0{e0};
+    ZK_HIP(hipEventCreate(&e1));
+    EvGuard g1{e1};
+    struct Drain { zkg16_ctx *c; bool ok = false; ~Drain() { if (!ok) (void)hipStreamSynchronize(c->stream); } } drain{ctx};
+    ZK_HIP(hipEventRecord(e0, ctx->stream));
+    ZK_HIP(hipMemcpyAsync(ds, hs, in_bytes + k * sizeof(Fr *), hipMemcpyHostToDevice, ctx->stream));      // the one upload: inputs | z table
+    const Fr *d_in = reinterpret_cast<const Fr *>(ds);
+    {
+        EvalBatchArgs g;
+        memset(&g, 0, sizeof g);
+        g.e.ins = D->ins.as<PrimeInstr>();
+        g.e.lvl = D->lvl.as<uint32_t>();
+        g.e.terms = D->terms.as<uint32_t>();
+        g.e.src = d_in + P.n_slots;
+        g.e.bits = d_bits.as<uint8_t>();
+        for (int p = 0; p <= PRIME_PROGRAM_PARTS; p++) {
+            g.e.lvl_base[p] = P.lvl_base[p];
+            g.e.wit_base[p] = P.wit_base[p];
+        }
+        g.in_stride = in_stride;
+        g.num_witness = P.num_witness;
+        g.k = k;
+        ScopedKernelTimer kt(ctx, "prime_witness_eval_batch_kernel", (double)P.ins.size() * (double)k);
+        hipLaunchKernelGGL(prime_witness_eval_batch_kernel, dim3(PRIME_PROGRAM_PARTS, (unsigned)(k < cap ? k : cap)), dim3(1024), P.max_part, ctx->stream, g);
+        ZK_HIP(hipGetLastError());
+    }
+    {
+        const uint64_t halves = 2 * (uint64_t)total;
+        const size_t bx = (size_t)((halves + 255) / 256);
+        ScopedKernelTimer kt(ctx, "prime_witness_expand_batch_kernel", (double)total * (double)k);
+        hipLaunchKernelGGL(prime_witness_expand_batch_kernel, dim3((unsigned)(bx < cap ? bx : cap), (unsigned)(k < cap ? k : cap)), dim3(256), 0, ctx->stream,
+                           D->code.as<uint32_t>(), d_bits.as<uint8_t>(), d_in, reinterpret_cast<Fr *const *>(ds + in_bytes), halves, k, in_stride,
+                           (size_t)P.num_witness);
+        ZK_HIP(hipGetLastError());
+    }
+    ZK_HIP(hipEventRecord(e1, ctx->stream));
+    ZK_HIP(hipStreamSynchronize(ctx->stream));      // the staging is free again, and the assignments are whole
+    drain.ok = true;
+    if (dev_ms) ZK_HIP(hipEventElapsedTime(dev_ms, e0, e1));
+    out = std::move(wits);
 }
 
 std::shared_ptr<WitnessDev> prime_witness_on_device(zkg16_ctx *ctx, uint64_t x, uint64_t j, int *status) {

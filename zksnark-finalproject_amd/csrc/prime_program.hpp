@@ -49,6 +49,7 @@ struct PrimeProgram {
     std::vector<Fr> cf[3];
     std::vector<uint64_t> rp_c_j0;                     // C's row pointers when j = 0
     uint64_t a_pos[3] = {0, 0, 0}, c_pos = 0;          // the patched non-zeros
+    uint32_t patch_rows[4] = {0, 0, 0, 0};             // ... and the constraint rows that hold them (A, A, A, C)
 };
 
 // one instruction on the bits of its part (LDS on the device, a host array in zkg16_prime_witness_host); src: canonical sources

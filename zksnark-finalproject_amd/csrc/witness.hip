@@ -648,7 +648,7 @@ static void chain_batch_launch(zkg16_ctx *ctx, ChainBatchArgs g, bool assign) {
     }
 }
 
-static void mbatch_staging_ensure(zkg16_ctx *ctx, size_t bytes) {
+void mbatch_staging_ensure(zkg16_ctx *ctx, size_t bytes) {
     if (ctx->mbatch_host_bytes < bytes) {           // nothing reads the old block: every call ends with the stream drained
         if (ctx->mbatch_host) (void)hipHostFree(ctx->mbatch_host);
         ctx->mbatch_host = nullptr;

@@ -160,6 +160,24 @@ class Device:
         self._check(self.lib.zkg16_witness_prime(self.ctx, x, j, C.byref(handle)))
         return handle.value
 
+    def r1cs_prime_template(self):
+        """The template every candidate's R1CS is a patch of, as an r1cs handle (zkg16_r1cs_prime_template): what the key of
+        prove_prime_batch is set up on, and the only r1cs handle it takes."""
+        handle = C.c_uint64()
+        self._check(self.lib.zkg16_r1cs_prime_template(self.ctx, C.byref(handle)))
+        return handle.value
+
+    def witness_prime_batch(self, xs, js):
+        """The PrimeCircuit's assignments of k candidates (xs[i], js[i]) built in one device pass (zkg16_witness_prime_batch) ->
+        witness handles [k]; handle i holds what witness_prime(xs[i], js[i]) would, each is freed on its own.  A refused candidate
+        fails the whole call and registers nothing."""
+        xs, js = _u64(xs).reshape(-1), _u64(js).reshape(-1)
+        if xs.shape != js.shape:
+            raise ValueError("witness_prime_batch: one j per x")
+        handles = np.zeros(xs.shape[0], dtype=np.uint64)
+        self._check(self.lib.zkg16_witness_prime_batch(self.ctx, _ptr(xs), _ptr(js), xs.shape[0], _ptr(handles)))
+        return handles
+
     def r1cs_read(self, h):
         """-> the r1cs dict (as SynthesizedCircuit.r1cs) + num_variables behind a handle (zkg16_r1cs_read)."""
         ni, nc, nv = C.c_size_t(), C.c_size_t(), C.c_size_t()
@@ -400,6 +418,28 @@ class Device:
         self._check(self.lib.zkg16_prove_matrix_batch(self.ctx, pk_h, r1cs_h, n, _ptr(a), _ptr(b), k, _ptr(rs), _ptr(ss), _ptr(proofs), _ptr(inf),
                                                       _ptr(pub), C.addressof(ms)))
         return proofs, inf, pub, dict(host_sponges_ms=float(ms[0]), witness_ms=float(ms[1]), prove_ms=float(ms[2]), call_ms=float(ms[3]))
+
+    def prove_prime_batch(self, pk_h, r1cs_h, corr, gamma_abc0, xs, js, rs, ss, public_inputs=True):
+        """k prime requests (xs[i], js[i]) on the template key in batched device passes (zkg16_prove_prime_batch).  pk_h: the key
+        set up on r1cs_prime_template() = r1cs_h; corr: circuits.prime_key_corrections of its trapdoor; gamma_abc0: its
+        gamma_abc_g1[0]; rs / ss [k, 4] -> (proofs [k, 48], inf [k, 3], gamma_abc0 [k, 12]: request i's gamma_abc_g1[0], public
+        inputs [k, 257, 4] or None, dict of ms).  Proof and key are byte for byte those of the per-request path."""
+        xs, js = _u64(xs).reshape(-1), _u64(js).reshape(-1)
+        k = xs.shape[0]
+        rs, ss = _u64(rs).reshape(-1, 4), _u64(ss).reshape(-1, 4)
+        if js.shape[0] != k or rs.shape[0] != k or ss.shape[0] != k:
+            raise ValueError("prove_prime_batch: one j, r and s per request")
+        corr, gamma_abc0 = _u64(corr).reshape(-1), _u64(gamma_abc0).reshape(-1)
+        if corr.size != 36 or gamma_abc0.size != 12:
+            raise ValueError("prove_prime_batch: corr 3 x 12 limbs, gamma_abc0 12 limbs")
+        proofs = np.zeros((k, 48), dtype=np.uint64)
+        inf = np.zeros((k, 3), dtype=np.uint8)
+        g0 = np.zeros((k, 12), dtype=np.uint64)
+        pub = np.zeros((k, 257, 4), dtype=np.uint64) if public_inputs else None
+        ms = (C.c_float * 4)()
+        self._check(self.lib.zkg16_prove_prime_batch(self.ctx, pk_h, r1cs_h, _ptr(corr), _ptr(gamma_abc0), _ptr(xs), _ptr(js), k, _ptr(rs), _ptr(ss),
+                                                     _ptr(proofs), _ptr(inf), _ptr(g0), _ptr(pub), C.addressof(ms)))
+        return proofs, inf, g0, pub, dict(host_inputs_ms=float(ms[0]), witness_ms=float(ms[1]), prove_ms=float(ms[2]), call_ms=float(ms[3]))
 
     def prove(self, pk_h, r, s, r1cs, z):
         args, keep = self._csr(r1cs)

@@ -3,6 +3,7 @@
     prove_matrices   K such requests of one size under one key, in batched device passes (no counterpart upstream)
     prove_fibonacci  src/arkworks/backend/fibbonaci_handler.rs:98-145
     prove_prime / verify_prime  src/arkworks/backend/prime_snark.rs:49-146, 165-206
+    prove_primes     K prime requests under one trapdoor on ONE template key, in batched device passes (no counterpart upstream)
 Same steps, same response fields: synthesize the circuit (host C++ mirror), per-request Groth16 setup (on the device,
 zkg16_setup), prove (zkg16_prove_resident), encode (wire.py).  The reference's HTTP layer (actix-web) is out of scope; the
 trapdoor and r, s come from Python's PRNG rather than arkworks' StdRng stream, so proofs are valid Groth16 proofs for the
@@ -13,7 +14,8 @@ import time
 import numpy as np
 
 from . import wire
-from .circuits import fibonacci_circuit, fibonacci_circuit_handle, matrix_circuit, matrix_hash_batch_host, prime_circuit, prime_dims, prime_public_inputs, prime_search
+from .circuits import (fibonacci_circuit, fibonacci_circuit_handle, matrix_circuit, matrix_hash_batch_host, prime_circuit, prime_dims, prime_key_corrections,
+                       prime_public_inputs, prime_search)
 from .workloads import R_MOD, g1_generator, g2_generator
 
 
@@ -271,7 +273,7 @@ def prove_prime(dev, x, i, seed=7, keep_key=False, check_satisfied=False):
     hash(x + j) mod 2^20 that passes the Fermat test, build PrimeCircuit for it, circuit-specific setup, prove."""
     found = prime_search(x, i)
     if not found["found"]:
-        return dict(proof="", j=0, num_constraints=0, num_variables=0, setup_time=0.0, proving_time=0.0, found_prime=False, prime_num="", vk="")
+        return dict(_PRIME_NOT_FOUND)
     if keep_key or check_satisfied:     # tests want the arrays (and the satisfaction check) on the host: host synthesis
         circ = prime_circuit(x, found["j"], search=False, check_satisfied=check_satisfied)
         out = _setup_and_prove(dev, circ, random.Random(seed), keep_key)
@@ -282,6 +284,81 @@ def prove_prime(dev, x, i, seed=7, keep_key=False, check_satisfied=False):
                 num_variables=circ.num_vars, setup_time=out["setup_time"], proving_time=out["proving_time"], found_prime=True,
                 prime_num=str(found["prime"]), pvk=wire.encode_pvk(out["vk"]), vk=wire.encode_vk(out["vk"]), satisfied=circ.satisfied,
                 _detail=out, _circuit=circ)
+
+
+_PRIME_NOT_FOUND = dict(proof="", j=0, num_constraints=0, num_variables=0, setup_time=0.0, proving_time=0.0, found_prime=False, prime_num="", vk="")
+
+
+def prime_template_key(dev, rng):
+    """The key every prime request of one trapdoor shares: prove_prime's draws from rng in its order (trapdoor, generators), one
+    setup on the template (Device.r1cs_prime_template) -> dict(ph, rh, vk, corr, setup_time).  The trapdoor itself is not kept:
+    corr (circuits.prime_key_corrections) is all a request needs of it.  The caller frees ph and rh."""
+    from .device import scalar_mul
+    trap = np.stack([_fr_mont(rng.randrange(1, R_MOD)) for _ in range(5)])
+    k = np.array([rng.getrandbits(62) for _ in range(4)], dtype=np.uint64)
+    g1 = scalar_mul("g1", g1_generator(), k)[0]
+    g2 = scalar_mul("g2", g2_generator(), k)[0]
+    corr, inf = prime_key_corrections(trap, g1)
+    if inf.any():
+        raise ValueError("prime_template_key: a key correction is the point at infinity")
+    rh = dev.r1cs_prime_template()
+    try:
+        t0 = time.perf_counter()
+        ph, vk = dev.setup_resident(rh, prime_dims(1)["num_instance"], trap, g1, g2)
+        setup_time = time.perf_counter() - t0
+    except Exception:
+        dev.r1cs_free(rh)
+        raise
+    return dict(ph=ph, rh=rh, vk=vk, corr=corr, setup_time=setup_time)
+
+
+def prove_primes(dev, requests, seed=7, key=None):
+    """K requests of the prime handler, requests = [(x, i), ...], under ONE trapdoor: the search runs per request, the requests
+    that found a prime are proved on one template key in batched device passes (Device.prove_prime_batch).  The key is set up
+    once from `seed` with prove_prime's draws (then r, s per proved request), so request 0 is prove_prime's proof and key for that
+    seed, byte for byte; or it is passed in as key= (prime_template_key's dict), which stays the caller's.  A request's key is the
+    template's with gamma_abc_g1[0] replaced, so the prepared key is made once and only that element changes per request.
+    -> a list of prove_prime's fields per request (a request without a prime: its not-found record)."""
+    if len(requests) == 0:
+        raise ValueError("prove_primes: no requests")
+    found = [prime_search(x, i) for x, i in requests]
+    hits = [q for q, f in enumerate(found) if f["found"]]
+    out = [dict(_PRIME_NOT_FOUND) for _ in requests]
+    if not hits:
+        return out
+    rng = random.Random(seed)
+    own = key is None
+    if own:
+        key = prime_template_key(dev, rng)
+    try:
+        rss = [(_fr_mont(rng.randrange(R_MOD)), _fr_mont(rng.randrange(R_MOD))) for _ in hits]
+        rs, ss = np.stack([r for r, _ in rss]), np.stack([s for _, s in rss])
+        xs = np.array([requests[q][0] for q in hits], dtype=np.uint64)
+        js = np.array([found[q]["j"] for q in hits], dtype=np.uint64)
+        t0 = time.perf_counter()
+        proofs, inf, g0, pubs, ms = dev.prove_prime_batch(key["ph"], key["rh"], key["corr"], key["vk"]["gamma_abc_g1"][0], xs, js, rs, ss)
+        proving_time = time.perf_counter() - t0
+    finally:
+        if own:
+            dev.pk_free(key["ph"])
+            dev.r1cs_free(key["rh"])
+    vk = key["vk"]
+    dims = prime_dims(1)
+    # one prepared key and one encoding for the batch: a request's key is the template's with gamma_abc_g1[0] replaced, and both
+    # byte strings begin alpha_g1 (48) | beta_g2, gamma_g2, delta_g2 (96 each) | count (8), so that point is bytes 344 .. 392
+    from .device import pvk_prepare
+    import base64
+    vk_bytes, pvk_bytes = wire.vk_serialize_compressed(vk), wire.pvk_serialize_compressed(pvk_prepare(vk))
+    for n, q in enumerate(hits):
+        point = wire.points_compress("g1", g0[n])
+        vk_q = dict(vk, gamma_abc_g1=np.concatenate([g0[n:n + 1], vk["gamma_abc_g1"][1:]]))
+        out[q] = dict(proof=wire.encode_proof(proofs[n], inf[n]), j=found[q]["j"], num_constraints=dims["num_constraints"],
+                      num_variables=dims["num_instance"] + dims["num_witness"], setup_time=key["setup_time"] if own else 0.0,
+                      proving_time=proving_time / len(hits), found_prime=True, prime_num=str(found[q]["prime"]),
+                      pvk=base64.standard_b64encode(pvk_bytes[:344] + point + pvk_bytes[392:]).decode(),
+                      vk=base64.standard_b64encode(vk_bytes[:344] + point + vk_bytes[392:]).decode(), satisfied=None,
+                      _detail=dict(proof=proofs[n], inf=inf[n], vk=vk_q, r=rs[n], s=ss[n], public_inputs=pubs[n], ms=ms))
+    return out
 
 
 def verify_prime(vk, x, j, proof_b64):
