@@ -1,5 +1,6 @@
 """Thin object layer over the C ABI: one `Device` == one zkg16_ctx == one MI355X."""
 import ctypes as C
+import threading
 
 import numpy as np
 
@@ -19,14 +20,28 @@ def _opt_u8(a):
     return None if a is None else np.ascontiguousarray(a, dtype=np.uint8)
 
 
+def _check_host(rc):
+    """The status of a host-only entry point (no ctx, so no zkg16_last_error)."""
+    if rc != 0:
+        raise Zkg16Error(rc, _lib.load().zkg16_strerror(rc).decode())
+
+
 class Device:
     def __init__(self, device_id=0):
+        # MatrixCircuit shapes resident on this device, by size (handlers._matrix_shape); entries have .rh
+        self._matrix_shapes = {}
+        self._matrix_shapes_lock = threading.Lock()
         self.lib = _lib.load()
         self.ctx = C.c_void_p()
         ids = (C.c_int * 1)(device_id)
-        rc = self.lib.zkg16_init(ids, 1, C.byref(self.ctx))
-        if rc != 0:
-            raise Zkg16Error(rc, self.lib.zkg16_strerror(rc).decode())
+        _check_host(self.lib.zkg16_init(ids, 1, C.byref(self.ctx)))
+
+    def __getattr__(self, name):
+        # reached only when the attribute is missing: callers drop the whole shape cache by deleting it, the next look starts an empty one
+        if name == "_matrix_shapes":
+            self._matrix_shapes = {}
+            return self._matrix_shapes
+        raise AttributeError(name)
 
     def close(self):
         if self.ctx:
@@ -598,9 +613,7 @@ def shard_plan(n_ranks, m_total, n_h, b_density=0.0, h_ranks=0, z_cost=None, win
     zc = None if z_cost is None else np.ascontiguousarray(z_cost, dtype=np.float32)
     if zc is not None and zc.shape[0] != m_total:
         raise ValueError("shard_plan: z_cost has %d entries, m_total is %d" % (zc.shape[0], m_total))
-    rc = lib.zkg16_shard_plan_tables(n_ranks, m_total, n_h, float(b_density), h_ranks, _ptr(zc), int(bool(window_tables)), ranges, blind, C.byref(k))
-    if rc != 0:
-        raise Zkg16Error(rc, lib.zkg16_strerror(rc).decode())
+    _check_host(lib.zkg16_shard_plan_tables(n_ranks, m_total, n_h, float(b_density), h_ranks, _ptr(zc), int(bool(window_tables)), ranges, blind, C.byref(k)))
     r = ranges.reshape(n_ranks, 4)
     return [(int(r[i, 0]), int(r[i, 1]), int(r[i, 2]), int(r[i, 3]), bool(blind[i])) for i in range(n_ranks)], k.value
 
@@ -614,8 +627,7 @@ def combine_partials(alpha_g1, beta_g1, beta_g2, r, s, partials, partial_inf):
     inf = np.zeros(3, dtype=np.uint8)
     rc = lib.zkg16_combine_partials(_u64(alpha_g1), _u64(beta_g1), _u64(beta_g2), _u64(r), _u64(s), partials, partial_inf,
                                     partials.shape[0], proof, inf)
-    if rc != 0:
-        raise Zkg16Error(rc, lib.zkg16_strerror(rc).decode())
+    _check_host(rc)
     return proof, inf
 
 
@@ -654,8 +666,7 @@ def verify(vk, public_inputs_mont, proof48, inf3):
     ok = C.c_int(0)
     rc = lib.zkg16_verify(_u64(vk["alpha_g1"]), _u64(vk["beta_g2"]), _u64(vk["gamma_g2"]), _u64(vk["delta_g2"]), gabc, gabc.shape[0],
                           _ptr(pub) if pub.size else None, _u64(proof48), np.ascontiguousarray(inf3, dtype=np.uint8), C.byref(ok))
-    if rc != 0:
-        raise Zkg16Error(rc, lib.zkg16_strerror(rc).decode())
+    _check_host(rc)
     return bool(ok.value)
 
 
@@ -683,9 +694,7 @@ def pairing_check(g1_points, g2_points, g1_inf=None, g2_inf=None, plain_final_ex
     i1 = np.ascontiguousarray(g1_inf if g1_inf is not None else np.zeros(n), dtype=np.uint8)
     i2 = np.ascontiguousarray(g2_inf if g2_inf is not None else np.zeros(n), dtype=np.uint8)
     ok = C.c_int(0)
-    rc = lib.zkg16_pairing_check(g1, i1, g2, i2, n, 1 if plain_final_exp else 0, C.byref(ok))
-    if rc != 0:
-        raise Zkg16Error(rc, lib.zkg16_strerror(rc).decode())
+    _check_host(lib.zkg16_pairing_check(g1, i1, g2, i2, n, 1 if plain_final_exp else 0, C.byref(ok)))
     return bool(ok.value)
 
 
@@ -697,8 +706,7 @@ def scalar_mul(group, base, k_canonical):
     inf = C.c_uint8(0)
     fn = lib.zkg16_scalar_mul_g1 if group == "g1" else lib.zkg16_scalar_mul_g2
     rc = fn(_u64(base).reshape(-1), _u64(k_canonical).reshape(-1), out, C.byref(inf))
-    if rc != 0:
-        raise Zkg16Error(rc, lib.zkg16_strerror(rc).decode())
+    _check_host(rc)
     return out, int(inf.value)
 
 
@@ -706,9 +714,7 @@ def point_check(group, point):
     """Curve + prime-order-subgroup membership of one affine point (zkg16_point_check; host-only)."""
     lib = _lib.load()
     ok = C.c_int(0)
-    rc = lib.zkg16_point_check(1 if group == "g1" else 2, _u64(point).reshape(-1), C.byref(ok))
-    if rc != 0:
-        raise Zkg16Error(rc, lib.zkg16_strerror(rc).decode())
+    _check_host(lib.zkg16_point_check(1 if group == "g1" else 2, _u64(point).reshape(-1), C.byref(ok)))
     return bool(ok.value)
 
 
@@ -720,9 +726,7 @@ def pvk_prepare(vk):
     g = np.zeros(68 * 36, dtype=np.uint64)
     d = np.zeros(68 * 36, dtype=np.uint64)
     n = C.c_size_t(0)
-    rc = lib.zkg16_pvk_prepare(_u64(vk["alpha_g1"]), _u64(vk["beta_g2"]), _u64(vk["gamma_g2"]), _u64(vk["delta_g2"]), ab, g, d, C.byref(n))
-    if rc != 0:
-        raise Zkg16Error(rc, lib.zkg16_strerror(rc).decode())
+    _check_host(lib.zkg16_pvk_prepare(_u64(vk["alpha_g1"]), _u64(vk["beta_g2"]), _u64(vk["gamma_g2"]), _u64(vk["delta_g2"]), ab, g, d, C.byref(n)))
     out = dict(vk)
     out.update(alpha_beta=ab, gamma_neg_pc=g.reshape(n.value, 36), delta_neg_pc=d.reshape(n.value, 36))
     return out
@@ -739,8 +743,7 @@ def verify_prepared(pvk, public_inputs_mont, proof48, inf3):
     ok = C.c_int(0)
     rc = lib.zkg16_verify_prepared(gabc, gabc.shape[0], _ptr(pub) if pub.size else None, _u64(pvk["alpha_beta"]), g, d, g.shape[0],
                                    _u64(proof48), np.ascontiguousarray(inf3, dtype=np.uint8), C.byref(ok))
-    if rc != 0:
-        raise Zkg16Error(rc, lib.zkg16_strerror(rc).decode())
+    _check_host(rc)
     return bool(ok.value)
 
 
@@ -793,9 +796,7 @@ def verify_batch_host(pvk, public_inputs, proofs, infs, rho=None, each=False, th
     args, k = _verify_batch_args(pvk, public_inputs, proofs, infs, rho)
     ok = C.c_int(0)
     ok_each = np.zeros(k, dtype=np.uint8) if each else None
-    rc = lib.zkg16_verify_batch_host(*args, threads, C.byref(ok), _ptr(ok_each))
-    if rc != 0:
-        raise Zkg16Error(rc, lib.zkg16_strerror(rc).decode())
+    _check_host(lib.zkg16_verify_batch_host(*args, threads, C.byref(ok), _ptr(ok_each)))
     return (bool(ok.value), ok_each.astype(bool)) if each else bool(ok.value)
 
 
@@ -803,9 +804,7 @@ def final_exp(f):
     """The verifier's final exponentiation of one Fq12 value (72 u64, ark's tower order; zkg16_final_exp, host-only)."""
     lib = _lib.load()
     out = np.zeros(72, dtype=np.uint64)
-    rc = lib.zkg16_final_exp(_u64(f).reshape(-1), out)
-    if rc != 0:
-        raise Zkg16Error(rc, lib.zkg16_strerror(rc).decode())
+    _check_host(lib.zkg16_final_exp(_u64(f).reshape(-1), out))
     return out
 
 
@@ -819,9 +818,7 @@ class DeviceGroup:
         self.lib = _lib.load()
         self.group = C.c_void_p()
         arr = (C.c_void_p * len(self.devices))(*[d.ctx.value for d in self.devices])
-        rc = self.lib.zkg16_group_create(arr, len(self.devices), C.byref(self.group))
-        if rc != 0:
-            raise Zkg16Error(rc, self.lib.zkg16_strerror(rc).decode())
+        _check_host(self.lib.zkg16_group_create(arr, len(self.devices), C.byref(self.group)))
 
     def close(self):
         if self.group:
@@ -890,12 +887,10 @@ def group_layout(log_n, k, ntt_mode=1):
     res = np.zeros(2 * max(k, 1), dtype=np.uint64)
     n = C.c_size_t(0)
     rc = lib.zkg16_group_layout(log_n, k, ntt_mode, C.byref(applies), shape, res.ctypes.data, None, 0, C.byref(n))
-    if rc != 0 and not (rc == 1 and n.value > 0):
-        raise Zkg16Error(rc, lib.zkg16_strerror(rc).decode())
+    if not (rc == 1 and n.value > 0):      # the count query: BAD_ARG for "more than cap 0", with the count needed
+        _check_host(rc)
     rects = np.zeros((max(n.value, 1), 7), dtype=np.uint64)
-    rc = lib.zkg16_group_layout(log_n, k, ntt_mode, C.byref(applies), shape, res.ctypes.data, rects.ctypes.data, rects.shape[0], C.byref(n))
-    if rc != 0:
-        raise Zkg16Error(rc, lib.zkg16_strerror(rc).decode())
+    _check_host(lib.zkg16_group_layout(log_n, k, ntt_mode, C.byref(applies), shape, res.ctypes.data, rects.ctypes.data, rects.shape[0], C.byref(n)))
     return dict(applies=bool(applies.value), n1=int(shape[0]), n2=int(shape[1]), m=int(shape[2]), unit=int(shape[3]),
                 residues=[(int(res[2 * g]), int(res[2 * g + 1])) for g in range(k)],
                 rects=[tuple(int(x) for x in r) for r in rects[: n.value]])
@@ -909,10 +904,8 @@ def group_h_layout(log_n, k, h_ranges, ntt_mode=1):
         raise ValueError("group_h_layout: %d ranges for %d ranks" % (hr.shape[0] // 2, k))
     n = C.c_size_t(0)
     rc = lib.zkg16_group_h_layout(log_n, k, ntt_mode, hr, None, 0, C.byref(n))
-    if rc != 0 and not (rc == 1 and n.value > 0):
-        raise Zkg16Error(rc, lib.zkg16_strerror(rc).decode())
+    if not (rc == 1 and n.value > 0):      # the count query: BAD_ARG for "more than cap 0", with the count needed
+        _check_host(rc)
     rects = np.zeros((max(n.value, 1), 7), dtype=np.uint64)
-    rc = lib.zkg16_group_h_layout(log_n, k, ntt_mode, hr, rects.ctypes.data, rects.shape[0], C.byref(n))
-    if rc != 0:
-        raise Zkg16Error(rc, lib.zkg16_strerror(rc).decode())
+    _check_host(lib.zkg16_group_h_layout(log_n, k, ntt_mode, hr, rects.ctypes.data, rects.shape[0], C.byref(n)))
     return [tuple(int(x) for x in r) for r in rects[: n.value]]
