@@ -334,14 +334,57 @@ ZKG16_API int zkg16_miller_loop_batch(zkg16_ctx *ctx, const uint64_t *g1, const 
 ZKG16_API int zkg16_point_check_batch(zkg16_ctx *ctx, int group, const uint64_t *points, const uint8_t *inf, size_t n, uint8_t *ok_out);
 ZKG16_API int zkg16_final_exp(const uint64_t f[72], uint64_t out[72]);
 ZKG16_API int zkg16_final_exp_batch(zkg16_ctx *ctx, const uint64_t *f /* n x 72 */, size_t n, uint64_t *out /* n x 72 */);
-/* The last zkg16_verify_batch / zkg16_verify_batch_wire on this ctx, in ms: [0] membership kernels (host clock: launch to the verdicts on the host, beside
+/* The last zkg16_verify_batch / zkg16_verify_batch_wire / zkg16_verify_prime_batch[_wire] on this ctx, in ms: [0] membership kernels (host clock: launch to the verdicts on the host, beside
  * the Miller kernel), [1] scaling + Miller kernel (device events), [2] product tree, [3] the MSM
  * sum rho_k C_k, [4] host coefficients and the batch equation, [5] bisecting, [6] total wall; [7] = 1 when the host form answered;
  * [8] zkg16_verify_batch_wire only: the decompress kernels (device events; the host decode's wall time when the host form answered);
  * [9] the per-proof pass that took over from bisecting (device events; 0 when it did not run; its time is part of [5] too),
- * [10] the number of range tests bisecting made.
+ * [10] the number of range tests bisecting made; [11] zkg16_verify_prime_batch[_wire] only: the inputs kernel, [12] the sums
+ * kernels (device events; both 0 when the host form answered or the call was not a prime call).
  * Returns the number of entries written (at most cap). */
 ZKG16_API int zkg16_verify_batch_timings(zkg16_ctx *ctx, float *ms, int cap);
+
+/* ---- the prime form: K proofs of the prime handler made under ONE trapdoor (zkg16_prove_prime_batch), verified together.
+ * Request i's own key is the template's with gamma_abc_g1[0] + n_i V_n - j_i V_j in front, so no two requests share a key — but
+ * everything that differs is a function of (x, j).  Under the EXTENDED key — the template's 258 gamma_abc_g1 points, then V_n, then
+ * -V_j (num_instance = 260) — request i has the 259 short public inputs x_i, bit_0 .. bit_255 of SHA-256(x_i + j_i), n_i = that
+ * digest mod 2^20, j_i, and X_i = gamma_abc_ext[0] + sum z_i gamma_abc_ext[i] is exactly the X of its own key: one key, no key
+ * data per proof, and the Miller, membership, product, per-proof and decompress kernels of zkg16_verify_batch unchanged.
+ * zkg16_prime_vk_extend (host only): out (260 x 12) = gamma_abc_g1 (258 x 12) | V_n | -V_j from corr = U | V_n | V_j
+ * (zkg16_prime_key_corrections); nulls or a correction at infinity (zero limbs): ZKG16_ERR_BAD_ARG.
+ * zkg16_prime_ext_inputs (host only): out (259 x 4, Montgomery) = zkg16_prime_public_inputs(x, j) followed by n and j.
+ * zkg16_verify_prime_batch_host: zkg16_verify_batch_host on those inputs; no ctx, no GPU.
+ * zkg16_verify_prime_batch / zkg16_verify_prime_batch_wire: zkg16_verify_batch / _wire with the inputs made on the device from
+ * xs, js (k u64 each; 16 bytes per proof instead of 8.3 KB of limbs): a SHA-256 kernel (one GPU lane per request), the 260
+ * multiplier sums sum_k rho_k z_{k,i} of the member proofs as plain integers in a second kernel (no reduction on the device: every
+ * sum stays below 2^224; the host reduces once and cross-checks s_0 against its own sum), and, when the per-proof pass takes over
+ * from bisecting, each listed proof's 259 scalars written on the device.  The host expands inputs (from the 32-byte digests it then
+ * downloads) only when bisecting runs.  num_instance must be 260 and k below 2^32, else ZKG16_ERR_BAD_ARG before any work; argument
+ * checks, undecodable proofs, membership failures, ok_each, decode_status and the options "verify_batch_min" / "verify_wire_min" /
+ * "verify_each_after" are exactly those of zkg16_verify_batch / _wire (below the thresholds the host form answers).  A candidate
+ * the prover would refuse (n < 2, a zero base) is not an error here: its verdict is the equation's. */
+ZKG16_API int zkg16_prime_vk_extend(const uint64_t *gamma_abc_g1 /* 258 x 12 */, const uint64_t corr[36], uint64_t *out /* 260 x 12 */);
+ZKG16_API int zkg16_prime_ext_inputs(uint64_t x, uint64_t j, uint64_t *out /* 259 x 4 */);
+ZKG16_API int zkg16_verify_prime_batch_host(const uint64_t *gamma_abc_g1, size_t num_instance, const uint64_t alpha_beta[72],
+                                  const uint64_t *gamma_neg_coeffs, const uint64_t *delta_neg_coeffs, size_t n_coeffs,
+                                  const uint64_t *xs, const uint64_t *js, const uint64_t *proofs, const uint8_t *inf, const uint64_t *rho,
+                                  size_t k, int threads, int *ok, uint8_t *ok_each);
+ZKG16_API int zkg16_verify_prime_batch(zkg16_ctx *ctx, const uint64_t *gamma_abc_g1, size_t num_instance, const uint64_t alpha_beta[72],
+                             const uint64_t *gamma_neg_coeffs, const uint64_t *delta_neg_coeffs, size_t n_coeffs,
+                             const uint64_t *xs, const uint64_t *js, const uint64_t *proofs, const uint8_t *inf, const uint64_t *rho,
+                             size_t k, int *ok, uint8_t *ok_each);
+ZKG16_API int zkg16_verify_prime_batch_wire(zkg16_ctx *ctx, const uint64_t *gamma_abc_g1, size_t num_instance, const uint64_t alpha_beta[72],
+                                  const uint64_t *gamma_neg_coeffs, const uint64_t *delta_neg_coeffs, size_t n_coeffs,
+                                  const uint64_t *xs, const uint64_t *js, const uint8_t *proof_bytes /* k x 192 */, const uint64_t *rho,
+                                  size_t k, int *ok, uint8_t *ok_each, uint8_t *decode_status);
+/* Stage entries (tests / tools).  zkg16_prime_inputs_batch: digests (k x 32) and n_out (k) = zkg16_prime_candidate's digest and n
+ * of each (x, j), byte for byte; public_inputs (nullable, k x 257 x 4) = zkg16_prime_public_inputs.  zkg16_prime_rho_sums: sums
+ * (260 x 4 u64, plain integers, unreduced) = sum_k rho_k (1, x_k, bit_0 .. bit_255, n_k, j_k) over the proofs with live[k] != 0
+ * (live null: all).  k == 0: ZKG16_OK, nothing written. */
+ZKG16_API int zkg16_prime_inputs_batch(zkg16_ctx *ctx, const uint64_t *xs, const uint64_t *js, size_t k, uint8_t *digests, uint32_t *n_out,
+                             uint64_t *public_inputs);
+ZKG16_API int zkg16_prime_rho_sums(zkg16_ctx *ctx, const uint64_t *xs, const uint64_t *js, const uint64_t *rho, const uint8_t *live, size_t k,
+                         uint64_t *sums);
 
 /* prod_i e(P_i, Q_i) == 1 ?  Host-only (no ctx, no GPU).  g1: n x 12 limbs, g2: n x 24 limbs, flag bytes nullable.
  * flags: ZKG16_PAIRING_PLAIN_FINAL_EXP = final exponentiation as one plain power by (q^12-1)/r (slow cross-check of the

@@ -73,6 +73,13 @@ SIGNATURES = {
     "zkg16_verify_batch_host": (C.c_int, [vp, sz, vp, vp, vp, sz, vp, vp, vp, vp, sz, C.c_int, C.POINTER(C.c_int), vp]),
     "zkg16_verify_batch": (C.c_int, [ctxp, vp, sz, vp, vp, vp, sz, vp, vp, vp, vp, sz, C.POINTER(C.c_int), vp]),
     "zkg16_verify_batch_wire": (C.c_int, [ctxp, vp, sz, vp, vp, vp, sz, vp, vp, vp, sz, C.POINTER(C.c_int), vp, vp]),
+    "zkg16_prime_vk_extend": (C.c_int, [vp, vp, vp]),
+    "zkg16_prime_ext_inputs": (C.c_int, [C.c_uint64, C.c_uint64, u64p]),
+    "zkg16_verify_prime_batch_host": (C.c_int, [vp, sz, vp, vp, vp, sz, vp, vp, vp, vp, vp, sz, C.c_int, C.POINTER(C.c_int), vp]),
+    "zkg16_verify_prime_batch": (C.c_int, [ctxp, vp, sz, vp, vp, vp, sz, vp, vp, vp, vp, vp, sz, C.POINTER(C.c_int), vp]),
+    "zkg16_verify_prime_batch_wire": (C.c_int, [ctxp, vp, sz, vp, vp, vp, sz, vp, vp, vp, vp, sz, C.POINTER(C.c_int), vp, vp]),
+    "zkg16_prime_inputs_batch": (C.c_int, [ctxp, vp, vp, sz, vp, vp, vp]),
+    "zkg16_prime_rho_sums": (C.c_int, [ctxp, vp, vp, vp, vp, sz, vp]),
     "zkg16_points_decompress_batch": (C.c_int, [ctxp, C.c_int, vp, sz, vp, vp, C.c_int, C.POINTER(C.c_int)]),
     "zkg16_miller_loop_batch": (C.c_int, [ctxp, vp, vp, vp, vp, sz, vp]),
     "zkg16_point_check_batch": (C.c_int, [ctxp, C.c_int, vp, vp, sz, vp]),

@@ -167,6 +167,30 @@ def prime_key_corrections(trapdoor_mont, g1_gen):
     return corr, inf
 
 
+def prime_vk_extend(gamma_abc_g1, corr):
+    """The extended key's points (zkg16_prime_vk_extend, host only): the template's gamma_abc_g1 [258, 12] followed by V_n and -V_j
+    of corr (prime_key_corrections) -> [260, 12].  Under it every request of the trapdoor has the inputs prime_ext_inputs(x, j)."""
+    gabc = np.ascontiguousarray(gamma_abc_g1, dtype=np.uint64).reshape(-1, 12)
+    corr = np.ascontiguousarray(corr, dtype=np.uint64).reshape(-1)
+    if gabc.shape[0] != 258 or corr.size != 36:
+        raise ValueError("prime_vk_extend: gamma_abc_g1 258 x 12 limbs, corr 3 x 12 limbs")
+    out = np.zeros((260, 12), dtype=np.uint64)
+    rc = _lib.load().zkg16_prime_vk_extend(gabc.ctypes.data, corr.ctypes.data, out.ctypes.data)
+    if rc:
+        raise Zkg16Error(rc, "zkg16_prime_vk_extend")
+    return out
+
+
+def prime_ext_inputs(x, j):
+    """A request's 259 public inputs under the extended key (zkg16_prime_ext_inputs): prime_public_inputs(x, j), then n = the digest
+    mod 2^20, then j -> [259, 4] Montgomery."""
+    out = np.zeros((259, 4), dtype=np.uint64)
+    rc = _lib.load().zkg16_prime_ext_inputs(x, j, out.reshape(-1))
+    if rc:
+        raise Zkg16Error(rc, "zkg16_prime_ext_inputs")
+    return out
+
+
 def matrix_circuit(a, b):
     """MatrixCircuit for u64 matrices a, b (n x n lists/arrays); public inputs = Poseidon hashes of A, B, C = A*B."""
     a = np.ascontiguousarray(a, dtype=np.uint64)

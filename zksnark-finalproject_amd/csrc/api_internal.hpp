@@ -42,7 +42,9 @@ enum VerifyTiming : int {
     V_DECODE = 8,          // decoding the wire bytes (zkg16_verify_batch_wire)
     V_EACH = 9,            // the per-proof pass that took over from bisecting (0: it did not run)
     V_RANGE_TESTS = 10,    // range tests bisecting made
-    V_COUNT = 11
+    V_PRIME_INPUTS = 11,   // the prime form: the inputs kernel (device events; 0 when the host form answered or the call was not a prime call)
+    V_PRIME_SUMS = 12,     // ... and the sums kernels
+    V_COUNT = 13
 };
 static_assert(T_COUNT <= PROOF_TIMING_SLOTS && V_COUNT == VERIFY_TIMING_SLOTS, "timing slots");
 

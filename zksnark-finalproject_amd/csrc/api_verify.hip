@@ -10,10 +10,12 @@ using namespace zk;
 // which C_k enter the MSM), so the MSM of sum rho_k C_k runs on the lane's main stream while the Miller kernel is still busy.
 // From wire bytes (zkg16_verify_batch_wire) the three decompress launches of a pass fill the device proof array first, B on the main
 // stream beside A and C on two others; everything after reads that array as if the host had uploaded it.
+// The prime form (zkg16_verify_prime_batch[_wire]) has no public inputs on the host: (x, j) go up, the inputs kernel runs in front
+// of the membership kernels of the main stream, and the 260 multiplier sums are taken there once the member mask is known.
 namespace {
 const size_t VB_PASS = 65536;          // pairs / points per launch: one wave per SIMD of a 256-CU device
 struct VbEvents {
-    hipEvent_t ev[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    hipEvent_t ev[14] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     VbEvents() { for (auto &e : ev) ZK_HIP(hipEventCreate(&e)); }
     ~VbEvents() { for (auto &e : ev) if (e) (void)hipEventDestroy(e); }
     VbEvents(const VbEvents &) = delete;
@@ -67,24 +69,37 @@ void vb_membership_chunk(hipStream_t s_main, hipStream_t s_c, hipStream_t s_b, c
     vb_membership_launch(s_b, 2, pts + 12, 48, fl + 1, 3, n, en, m3 + 1, 3);
 }
 
+// The prime form (verify_batch.hpp): the batch's (x, j) on the host, and once vb_device has run the inputs kernel, the device
+// copies and digests the later stages read
+struct VbPrime {
+    const uint64_t *xs, *js;
+    const uint64_t *d_xs = nullptr, *d_js = nullptr;
+    const uint32_t *d_dig = nullptr;
+};
+
 // The per-proof pass on the lane's main stream: the proofs idx[0 .. n) (null: 0 .. n - 1) of the k x 48 limbs / k x 3 flags already on
 // the device, each with its public inputs (pub(j): the (num_instance - 1) x 4 Montgomery limbs of the proof at position j), in
-// launches of VB_PASS.  The key is converted and uploaded once per call.  Returns the kernels' time in ms (device events)
+// launches of VB_PASS.  The key is converted and uploaded once per call.  prime (nullable): the prime form — pub is not asked; the
+// inputs of the listed proofs are written on the device from its (x, j) and digests, so nothing travels per proof but its index.
+// Returns the kernels' time in ms (device events)
 float vb_each_pass(zkg16_ctx *ctx, const VbKey &key, const uint64_t *d_proofs, const uint8_t *d_inf, const uint32_t *idx, size_t n,
-                   const std::function<const uint64_t *(size_t)> &pub, uint8_t *verdict) {
+                   const std::function<const uint64_t *(size_t)> &pub, uint8_t *verdict, const VbPrime *prime = nullptr) {
     if (!n) return 0;
     hipStream_t st = ctx->stream;
     const size_t ni = key.num_instance, per = 4 * (ni - 1), pass = std::min(n, VB_PASS);
     std::vector<uint32_t> words(vb_each_key_count(ni));
     vb_each_key_words(key, words.data());
-    std::vector<uint64_t> z(std::max<size_t>(n * per, 1));
-    for (size_t j = 0; j < n && per; j++) vb_scalars_canonical(pub(j), ni - 1, z.data() + per * j);
-    DevBuf d_key(words.size() * 4), d_z(z.size() * 8), d_idx(idx ? n * 4 : 0), d_scratch(vb_each_scratch_bytes(pass)), d_verdict(n);
+    std::vector<uint64_t> z(prime ? 1 : std::max<size_t>(n * per, 1));
+    for (size_t j = 0; j < n && per && !prime; j++) vb_scalars_canonical(pub(j), ni - 1, z.data() + per * j);
+    DevBuf d_key(words.size() * 4), d_z(prime ? n * per * 8 : z.size() * 8), d_idx(idx ? n * 4 : 0), d_scratch(vb_each_scratch_bytes(pass)), d_verdict(n);
     VbEvents evs;
     ZK_HIP(hipMemcpyAsync(d_key.p, words.data(), words.size() * 4, hipMemcpyHostToDevice, st));
-    ZK_HIP(hipMemcpyAsync(d_z.p, z.data(), z.size() * 8, hipMemcpyHostToDevice, st));
+    if (!prime) ZK_HIP(hipMemcpyAsync(d_z.p, z.data(), z.size() * 8, hipMemcpyHostToDevice, st));
     if (idx) ZK_HIP(hipMemcpyAsync(d_idx.p, idx, n * 4, hipMemcpyHostToDevice, st));
     ZK_HIP(hipEventRecord(evs.ev[0], st));
+    for (size_t off = 0; off < n && prime; off += VB_PASS)
+        vb_prime_z_launch(st, idx ? d_idx.as<uint32_t>() + off : nullptr, std::min(VB_PASS, n - off), idx ? prime->d_xs : prime->d_xs + off,
+                          idx ? prime->d_js : prime->d_js + off, idx ? prime->d_dig : prime->d_dig + 8 * off, d_z.as<uint64_t>() + per * off);
     for (size_t off = 0; off < n; off += VB_PASS)
         vb_each_launch(st, d_key.as<uint32_t>(), ni, idx ? d_idx.as<uint32_t>() + off : nullptr, std::min(VB_PASS, n - off), idx ? d_proofs : d_proofs + 48 * off,
                        idx ? d_inf : d_inf + 3 * off, d_z.as<uint64_t>() + per * off, d_scratch.p, d_verdict.as<uint8_t>() + off);
@@ -98,17 +113,25 @@ float vb_each_pass(zkg16_ctx *ctx, const VbKey &key, const uint64_t *d_proofs, c
 // bytes): b.proofs / b.inf are null; the proofs are decoded on the device, unvalidated, and the decoded limbs and flags come back
 // once for the MSM's bases and vb_decide.  A proof with a point that did not decode is left out like one that fails membership;
 // decode_status (nullable, k x 3): the decode kernel's statuses, 5 where a decoded point failed membership.
-int vb_device(zkg16_ctx *ctx, const VbKey &key, VbBatch b, const uint8_t *wire, int *ok, uint8_t *ok_each, uint8_t *decode_status, double t_all) {
+// prime (nullable): the prime form — b.public_inputs is null; the inputs kernel runs beside the membership kernels, the 260 sums of
+// the member proofs are taken on the device once the membership verdicts are back, and the host expands inputs (from the 32-byte
+// digests it then downloads) only when bisecting asks for them.
+int vb_device(zkg16_ctx *ctx, const VbKey &key, VbBatch b, const uint8_t *wire, int *ok, uint8_t *ok_each, uint8_t *decode_status, double t_all,
+              VbPrime *prime = nullptr) {
     const size_t k = b.k;
     float tm[V_COUNT] = {0};
     ZK_LANE_BEGIN(ctx)
     hipStream_t s_main = ctx->stream, s_mil = ctx->wm_stream, s_c = ctx->slots[1].stream, s_b = ctx->slots[2].stream;
     VbEvents evs;
     hipEvent_t e_up = evs.ev[0], e_a = evs.ev[1], e_c = evs.ev[2], e_b = evs.ev[3], e_mil = evs.ev[4], e_p0 = evs.ev[5], e_p1 = evs.ev[6], e_m0 = evs.ev[7],
-               e_d0 = evs.ev[8], e_d1 = evs.ev[9];
+               e_d0 = evs.ev[8], e_d1 = evs.ev[9], e_i0 = evs.ev[10], e_i1 = evs.ev[11], e_s0 = evs.ev[12], e_s1 = evs.ev[13];
     const size_t half = (k + 1) / 2;
     DevBuf d_proofs(k * 48 * 8), d_inf(3 * k), d_rho(k * 16), d_mem3(3 * k), d_live(k), d_f(k * 72 * 8), d_tmp(2 * half * 72 * 8);
     DevBuf d_wire(wire ? k * 192 : 0), d_st(wire ? 3 * k : 0);
+    const size_t sum_blocks = prime ? vb_prime_sums_blocks(k) : 0;
+    DevBuf d_xs(prime ? k * 8 : 0), d_js(prime ? k * 8 : 0), d_dig(prime ? k * 32 : 0), d_part(sum_blocks * 260 * 32), d_sums(prime ? 260 * 32 : 0);
+    std::vector<uint64_t> sums(prime ? 260 * 4 : 0), expanded;
+    std::vector<uint32_t> digests;
     const VbEndo en = vb_endo();
     std::vector<uint64_t> dec_proofs;
     std::vector<uint8_t> dec_inf, dec_st, flags;
@@ -149,6 +172,19 @@ int vb_device(zkg16_ctx *ctx, const VbKey &key, VbBatch b, const uint8_t *wire, 
     ZK_HIP(hipEventRecord(e_up, s_main));
     for (hipStream_t st : {s_mil, s_c, s_b}) ZK_HIP(hipStreamWaitEvent(st, e_up, 0));
     ZK_HIP(hipEventRecord(e_m0, s_mil));
+    if (prime) {
+        // 16 bytes per proof up, one SHA-256 block per lane: in front of the membership kernels of the main stream
+        ZK_HIP(hipMemcpyAsync(d_xs.p, prime->xs, k * 8, hipMemcpyHostToDevice, s_main));
+        ZK_HIP(hipMemcpyAsync(d_js.p, prime->js, k * 8, hipMemcpyHostToDevice, s_main));
+        ZK_HIP(hipEventRecord(e_i0, s_main));
+        for (size_t off = 0; off < k; off += VB_PASS)
+            vb_prime_inputs_launch(s_main, d_xs.as<uint64_t>() + off, d_js.as<uint64_t>() + off, std::min(VB_PASS, k - off), d_dig.as<uint32_t>() + 8 * off, nullptr,
+                                   nullptr);
+        ZK_HIP(hipEventRecord(e_i1, s_main));
+        prime->d_xs = d_xs.as<uint64_t>();
+        prime->d_js = d_js.as<uint64_t>();
+        prime->d_dig = d_dig.as<uint32_t>();
+    }
     for (size_t off = 0; off < k; off += VB_PASS) {
         const size_t n = std::min(VB_PASS, k - off);
         const uint64_t *pts = d_proofs.as<uint64_t>() + 48 * off;
@@ -212,6 +248,14 @@ int vb_device(zkg16_ctx *ctx, const VbKey &key, VbBatch b, const uint8_t *wire, 
     }
     // the product of the member proofs' Miller values
     ZK_HIP(hipMemcpyAsync(d_live.p, member.data(), k, hipMemcpyHostToDevice, s_main));
+    if (prime) {
+        // s_i = sum rho_k z_{k,i} over the member proofs, while the Miller kernel is still busy
+        ZK_HIP(hipEventRecord(e_s0, s_main));
+        vb_prime_sums_launch(s_main, prime->d_xs, prime->d_js, prime->d_dig, d_rho.as<uint64_t>(), d_live.as<uint8_t>(), k, d_part.as<uint64_t>(),
+                             d_sums.as<uint64_t>());
+        ZK_HIP(hipEventRecord(e_s1, s_main));
+        ZK_HIP(hipMemcpyAsync(sums.data(), d_sums.p, 260 * 32, hipMemcpyDeviceToHost, s_main));
+    }
     ZK_HIP(hipStreamWaitEvent(s_main, e_mil, 0));
     ZK_HIP(hipEventRecord(e_p0, s_main));
     const uint64_t *d_prod = vb_product_launch(s_main, d_f.as<uint64_t>(), d_live.as<uint8_t>(), k, d_tmp.as<uint64_t>());
@@ -221,6 +265,10 @@ int vb_device(zkg16_ctx *ctx, const VbKey &key, VbBatch b, const uint8_t *wire, 
     ZK_HIP(hipStreamSynchronize(s_main));
     tm[V_MILLER] = vb_elapsed(e_m0, e_mil);      // both on the Miller stream
     tm[V_PRODUCT] = vb_elapsed(e_p0, e_p1);
+    if (prime) {
+        tm[V_PRIME_INPUTS] = vb_elapsed(e_i0, e_i1);
+        tm[V_PRIME_SUMS] = vb_elapsed(e_s0, e_s1);
+    }
     // the K Miller values leave the device only when the batch equation failed and the caller wants to know where
     std::vector<uint64_t> miller;
     // ... and when bisecting has used its budget of range tests, the proofs it left undecided stay here for the per-proof pass
@@ -228,13 +276,27 @@ int vb_device(zkg16_ctx *ctx, const VbKey &key, VbBatch b, const uint8_t *wire, 
     each.after = (size_t)ctx->opt.verify_each_after;
     each.decide = [&](const uint32_t *idx, size_t n, uint8_t *verdict) {
         const size_t per = 4 * (key.num_instance - 1);
-        tm[V_EACH] += vb_each_pass(ctx, key, d_proofs.as<uint64_t>(), d_inf.as<uint8_t>(), idx, n, [&](size_t j) { return b.public_inputs + per * idx[j]; }, verdict);
+        tm[V_EACH] += vb_each_pass(ctx, key, d_proofs.as<uint64_t>(), d_inf.as<uint8_t>(), idx, n, [&](size_t j) { return b.public_inputs + per * idx[j]; }, verdict,
+                                   prime);
     };
+    VbInputs inputs;
+    if (prime) {
+        inputs.sums = sums.data();
+        inputs.expand = [&]() -> const uint64_t * {
+            digests.resize(8 * k);
+            ZK_HIP(hipMemcpy(digests.data(), d_dig.p, k * 32, hipMemcpyDeviceToHost));
+            expanded.resize(4 * 259 * k);
+            vb_prime_expand(prime->xs, prime->js, digests.data(), k, expanded.data());
+            return expanded.data();
+        };
+    }
     vb_decide(key, b, member.data(), [&]() -> const uint64_t * {
         miller.resize(72 * k);
         ZK_HIP(hipMemcpy(miller.data(), d_f.p, k * 72 * 8, hipMemcpyDeviceToHost));
         return miller.data();
-    }, prod, sum_c, &sum_c_inf, 0, ok, ok_each, tm + V_HOST, &each);
+    }, prod, sum_c, &sum_c_inf, 0, ok, ok_each, tm + V_HOST, &each, prime ? &inputs : nullptr);
+    // the verdicts above came from host-expanded inputs then, and are right; a device whose sums are wrong is reported all the same
+    if (inputs.sums_refused) throw HipError{hipErrorUnknown, "prime_rho_sums_kernel: s_0 differs from the host's sum of the multipliers", __FILE__, __LINE__};
     tm[V_RANGE_TESTS] = (float)each.range_tests;
     tm[V_TOTAL] = (float)(now_ms() - t_all);
     vb_publish(root, tm);
@@ -334,6 +396,97 @@ int zkg16_verify_each(zkg16_ctx *ctx, const uint64_t *gamma_abc_g1, size_t num_i
                        [&](size_t j) { return public_inputs + per * idx[j]; }, verdict.data());
     memset(ok_each, 0, k);
     for (size_t j = 0; j < idx.size(); j++) ok_each[idx[j]] = verdict[j] ? 1 : 0;
+    ZK_LANE_END(ctx)
+}
+
+// ---- the prime form: K requests of one trapdoor under the extended key (zkg16_prime_vk_extend), their inputs made on the device
+static int vp_check(zkg16_ctx *ctx, const VbKey &key, const uint64_t *xs, const uint64_t *js, const void *proofs, const uint8_t *inf, const uint64_t *rho, size_t k,
+                    const int *ok) {
+    if (!ctx || key.num_instance != 260 || !xs || !js || k >> 32) return ZKG16_ERR_BAD_ARG;
+    // the checks of zkg16_verify_batch: xs stands in for the inputs that do not exist yet
+    return vb_check_args(key, VbBatch{xs, static_cast<const uint64_t *>(proofs), inf, rho, k}, ok);
+}
+static std::vector<uint64_t> vp_inputs_host(const uint64_t *xs, const uint64_t *js, size_t k) {
+    std::vector<uint64_t> pub(4 * 259 * k);
+    for (size_t i = 0; i < k; i++) (void)zkg16_prime_ext_inputs(xs[i], js[i], pub.data() + 4 * 259 * i);      // fails on a null pointer only
+    return pub;
+}
+
+int zkg16_verify_prime_batch(zkg16_ctx *ctx, const uint64_t *gamma_abc_g1, size_t num_instance, const uint64_t alpha_beta[72], const uint64_t *gamma_neg_coeffs,
+                             const uint64_t *delta_neg_coeffs, size_t n_coeffs, const uint64_t *xs, const uint64_t *js, const uint64_t *proofs, const uint8_t *inf,
+                             const uint64_t *rho, size_t k, int *ok, uint8_t *ok_each) {
+    const VbKey key{gamma_abc_g1, num_instance, alpha_beta, gamma_neg_coeffs, delta_neg_coeffs, n_coeffs};
+    const int rc = vp_check(ctx, key, xs, js, proofs, inf, rho, k, ok);
+    if (rc != ZKG16_OK) return rc;
+    const double t_all = now_ms();
+    if (k < (size_t)ctx->opt.verify_batch_min)
+        return vb_answer_on_host(ctx, t_all, [&](float *) {
+            const std::vector<uint64_t> pub = vp_inputs_host(xs, js, k);
+            vb_host(key, VbBatch{pub.data(), proofs, inf, rho, k}, 0, ok, ok_each);
+        });
+    VbPrime prime{xs, js};
+    return vb_device(ctx, key, VbBatch{nullptr, proofs, inf, rho, k}, nullptr, ok, ok_each, nullptr, t_all, &prime);
+}
+
+int zkg16_verify_prime_batch_wire(zkg16_ctx *ctx, const uint64_t *gamma_abc_g1, size_t num_instance, const uint64_t alpha_beta[72], const uint64_t *gamma_neg_coeffs,
+                                  const uint64_t *delta_neg_coeffs, size_t n_coeffs, const uint64_t *xs, const uint64_t *js, const uint8_t *proof_bytes,
+                                  const uint64_t *rho, size_t k, int *ok, uint8_t *ok_each, uint8_t *decode_status) {
+    const VbKey key{gamma_abc_g1, num_instance, alpha_beta, gamma_neg_coeffs, delta_neg_coeffs, n_coeffs};
+    if (!proof_bytes) return ZKG16_ERR_BAD_ARG;
+    const int rc = vp_check(ctx, key, xs, js, proof_bytes, proof_bytes, rho, k, ok);
+    if (rc != ZKG16_OK) return rc;
+    const double t_all = now_ms();
+    if (k < (size_t)ctx->opt.verify_wire_min)
+        return vb_answer_on_host(ctx, t_all, [&](float *tm) {
+            std::vector<uint64_t> proofs(48 * k);
+            std::vector<uint8_t> inf(3 * k), st(3 * k);
+            vb_wire_decode_host(proof_bytes, k, decode_status ? 1 : 0, 0, proofs.data(), inf.data(), st.data());
+            tm[V_DECODE] = (float)(now_ms() - t_all);
+            std::vector<uint8_t> dead(k);
+            for (size_t i = 0; i < k; i++) dead[i] = st[3 * i] || st[3 * i + 1] || st[3 * i + 2] ? 1 : 0;
+            const std::vector<uint64_t> pub = vp_inputs_host(xs, js, k);
+            vb_host(key, VbBatch{pub.data(), proofs.data(), inf.data(), rho, k}, 0, ok, ok_each, dead.data());
+            if (decode_status) memcpy(decode_status, st.data(), 3 * k);
+        });
+    VbPrime prime{xs, js};
+    return vb_device(ctx, key, VbBatch{nullptr, nullptr, nullptr, rho, k}, proof_bytes, ok, ok_each, decode_status, t_all, &prime);
+}
+
+// Stage entries: the inputs kernel and the sums kernels by themselves
+int zkg16_prime_inputs_batch(zkg16_ctx *ctx, const uint64_t *xs, const uint64_t *js, size_t k, uint8_t *digests, uint32_t *n_out, uint64_t *public_inputs) {
+    if (!ctx || ((!xs || !js || !digests || !n_out) && k)) return ZKG16_ERR_BAD_ARG;
+    if (!k) return ZKG16_OK;
+    ZK_LANE_BEGIN(ctx)
+    hipStream_t st = ctx->stream;
+    DevBuf d_xs(k * 8), d_js(k * 8), d_dig(k * 32), d_n(k * 4), d_pub(public_inputs ? k * 257 * 32 : 0);
+    ZK_HIP(hipMemcpyAsync(d_xs.p, xs, k * 8, hipMemcpyHostToDevice, st));
+    ZK_HIP(hipMemcpyAsync(d_js.p, js, k * 8, hipMemcpyHostToDevice, st));
+    for (size_t off = 0; off < k; off += VB_PASS)
+        vb_prime_inputs_launch(st, d_xs.as<uint64_t>() + off, d_js.as<uint64_t>() + off, std::min(VB_PASS, k - off), d_dig.as<uint32_t>() + 8 * off,
+                               d_n.as<uint32_t>() + off, public_inputs ? d_pub.as<uint64_t>() + 4 * 257 * off : nullptr);
+    ZK_HIP(hipMemcpyAsync(digests, d_dig.p, k * 32, hipMemcpyDeviceToHost, st));
+    ZK_HIP(hipMemcpyAsync(n_out, d_n.p, k * 4, hipMemcpyDeviceToHost, st));
+    if (public_inputs) ZK_HIP(hipMemcpyAsync(public_inputs, d_pub.p, k * 257 * 32, hipMemcpyDeviceToHost, st));
+    ZK_HIP(hipStreamSynchronize(st));
+    ZK_LANE_END(ctx)
+}
+
+int zkg16_prime_rho_sums(zkg16_ctx *ctx, const uint64_t *xs, const uint64_t *js, const uint64_t *rho, const uint8_t *live, size_t k, uint64_t *sums) {
+    if (!ctx || ((!xs || !js || !rho || !sums) && k) || k >> 32) return ZKG16_ERR_BAD_ARG;
+    if (!k) return ZKG16_OK;
+    ZK_LANE_BEGIN(ctx)
+    hipStream_t st = ctx->stream;
+    DevBuf d_xs(k * 8), d_js(k * 8), d_dig(k * 32), d_rho(k * 16), d_live(live ? k : 0), d_part(vb_prime_sums_blocks(k) * 260 * 32), d_sums(260 * 32);
+    ZK_HIP(hipMemcpyAsync(d_xs.p, xs, k * 8, hipMemcpyHostToDevice, st));
+    ZK_HIP(hipMemcpyAsync(d_js.p, js, k * 8, hipMemcpyHostToDevice, st));
+    ZK_HIP(hipMemcpyAsync(d_rho.p, rho, k * 16, hipMemcpyHostToDevice, st));
+    if (live) ZK_HIP(hipMemcpyAsync(d_live.p, live, k, hipMemcpyHostToDevice, st));
+    for (size_t off = 0; off < k; off += VB_PASS)
+        vb_prime_inputs_launch(st, d_xs.as<uint64_t>() + off, d_js.as<uint64_t>() + off, std::min(VB_PASS, k - off), d_dig.as<uint32_t>() + 8 * off, nullptr, nullptr);
+    vb_prime_sums_launch(st, d_xs.as<uint64_t>(), d_js.as<uint64_t>(), d_dig.as<uint32_t>(), d_rho.as<uint64_t>(), live ? d_live.as<uint8_t>() : nullptr, k,
+                         d_part.as<uint64_t>(), d_sums.as<uint64_t>());
+    ZK_HIP(hipMemcpyAsync(sums, d_sums.p, 260 * 32, hipMemcpyDeviceToHost, st));
+    ZK_HIP(hipStreamSynchronize(st));
     ZK_LANE_END(ctx)
 }
 

@@ -249,7 +249,7 @@ struct MsmWorkspace {       // grown on demand, reused across proofs
 };
 
 // sizes of zkg16_ctx::timings (22 slots in use, declared with two to spare) and ::vb_timings
-constexpr int PROOF_TIMING_SLOTS = 24, VERIFY_TIMING_SLOTS = 11;
+constexpr int PROOF_TIMING_SLOTS = 24, VERIFY_TIMING_SLOTS = 13;
 
 }  // namespace zk
 

@@ -941,8 +941,10 @@ struct VbDecider {
     }
     // does the batch equation hold for the proofs live[lo .. hi)?  prod / sum_c: that range's product of Miller values / sum of rho_k C_k
     // where the caller has them
-    bool range_holds(size_t lo, size_t hi, const pf::F12 *prod, const HPt *sum_c) {
+    bool range_holds(size_t lo, size_t hi, const pf::F12 *prod, const HPt *sum_c, const uint64_t *sums = nullptr) {
         const size_t ni = key.num_instance, n = hi - lo;
+        // with the sums of this range at hand only s_0 is taken here (it is cross-checked below)
+        const uint64_t *pub = sums ? nullptr : public_inputs();
         // s_0 = sum rho_k, s_i = sum rho_k z_{k,i}: per-thread partial sums
         const size_t parts = 8;
         std::vector<Fr> part(parts * ni, Fr::zero());
@@ -957,9 +959,9 @@ struct VbDecider {
                     const size_t k = live[p];
                     const Fr r = vb_rho_mont(b.rho + 2 * k);
                     s[0] = fp_add(s[0], r);
-                    for (size_t i = 1; i < ni; i++) {
+                    for (size_t i = 1; pub && i < ni; i++) {
                         Fr z;
-                        memcpy(&z, b.public_inputs + 4 * (k * (ni - 1) + (i - 1)), sizeof z);
+                        memcpy(&z, pub + 4 * (k * (ni - 1) + (i - 1)), sizeof z);
                         s[i] = fp_add(s[i], fp_mul(r, z));
                     }
                     if (!prod) fpart[t] = pf::mul(fpart[t], vb_f12(miller + 72 * k));
@@ -975,6 +977,19 @@ struct VbDecider {
             if (!prod) f = pf::mul(f, fpart[t]);
             if (!sum_c) c = pf::pt_add(c, cpart[t]);
         }
+        if (sums) {
+            // plain integers below r (verify_batch.hpp: VbInputs): to Montgomery, nothing to reduce
+            for (size_t i = 0; i < ni; i++) {
+                Fr c;
+                memcpy(c.l, sums + 4 * i, sizeof c.l);
+                const Fr m = fp_to_mont(c);
+                if (i == 0 && !(m == s[0])) {
+                    inputs->sums_refused = true;
+                    return range_holds(lo, hi, prod, sum_c, nullptr);
+                }
+                s[i] = m;
+            }
+        }
         // sum_k rho_k X_k = sum_i s_i gamma_abc[i]
         HPt x = pf::pt_inf<pf::Fq64>();
         for (size_t i = 0; i < ni; i++) {
@@ -989,6 +1004,14 @@ struct VbDecider {
         if (vb_affine(c, cx, cy)) in.push_back(pf::PairIn{cx, cy, &dp});
         if (!in.empty()) f = pf::mul(f, pf::miller_loop(in));
         return pf::eq(pf::final_exp(f), vb_pow(ab, fp_from_mont(s[0])));
+    }
+    // the K proofs' public inputs: the caller's, or (the prime form) expanded when first asked for
+    zk::VbInputs *inputs = nullptr;
+    const uint64_t *expanded = nullptr;
+    const uint64_t *public_inputs() {
+        if (b.public_inputs || !inputs || !inputs->expand) return b.public_inputs;
+        if (!expanded) expanded = inputs->expand();
+        return expanded;
     }
     // bisecting's budget (verify_batch.hpp: VbEach): once `range_tests` reaches it, the ranges find_bad would have tested next are
     // collected in `open` instead, for the per-proof pass
@@ -1062,17 +1085,18 @@ void vb_scalars_canonical(const uint64_t *mont, size_t n, uint64_t *out) {
 }
 
 void vb_decide(const VbKey &key, const VbBatch &b, const uint8_t *member, const std::function<const uint64_t *()> &fetch_miller, const uint64_t *prod,
-               const uint64_t *sum_c, const uint8_t *sum_c_inf, int threads, int *ok, uint8_t *ok_each, float ms[2], VbEach *each) {
+               const uint64_t *sum_c, const uint8_t *sum_c_inf, int threads, int *ok, uint8_t *ok_each, float ms[2], VbEach *each, VbInputs *inputs) {
     const double t0 = vb_now_ms();
     VbDecider dc(key, b, threads);
     dc.each = each;
+    dc.inputs = inputs;
     if (each) each->range_tests = 0;
     for (size_t k = 0; k < b.k; k++)
         if (member[k]) dc.live.push_back((uint32_t)k);
     if (!prod) dc.miller = fetch_miller();
     const pf::F12 fprod = prod ? vb_f12(prod) : pf::f12_one();
     const HPt csum = sum_c ? vb_g1(sum_c, sum_c_inf && *sum_c_inf) : pf::pt_inf<pf::Fq64>();
-    const bool holds = dc.range_holds(0, dc.live.size(), prod ? &fprod : nullptr, sum_c ? &csum : nullptr);
+    const bool holds = dc.range_holds(0, dc.live.size(), prod ? &fprod : nullptr, sum_c ? &csum : nullptr, inputs ? inputs->sums : nullptr);
     const double t1 = vb_now_ms();
     if (ms) ms[0] += (float)(t1 - t0);
     *ok = holds && dc.live.size() == b.k ? 1 : 0;
@@ -1086,6 +1110,24 @@ void vb_decide(const VbKey &key, const VbBatch &b, const uint8_t *member, const 
             dc.decide_open(ok_each);
         }
         if (ms) ms[1] += (float)(vb_now_ms() - t1);
+    }
+}
+
+void vb_prime_expand(const uint64_t *xs, const uint64_t *js, const uint32_t *digests, size_t k, uint64_t *out) {
+    const auto mont = [](uint64_t v) {
+        Fr c = Fr::zero();
+        c.l[0] = (uint32_t)v;
+        c.l[1] = (uint32_t)(v >> 32);
+        return fp_to_mont(c);
+    };
+    const Fr one = Fr::one(), zero = Fr::zero();
+    for (size_t i = 0; i < k; i++) {
+        const uint32_t *d = digests + 8 * i;
+        Fr *o = reinterpret_cast<Fr *>(out + 4 * 259 * i);
+        o[0] = mont(xs[i]);
+        for (unsigned t = 0; t < 256; t++) o[1 + t] = ((d[t >> 5] >> (t & 31)) & 1) ? one : zero;
+        o[257] = mont(d[0] & 0xFFFFFu);
+        o[258] = mont(js[i]);
     }
 }
 
@@ -1152,6 +1194,56 @@ int zkg16_verify_batch_host(const uint64_t *gamma_abc_g1, size_t num_instance, c
     if (rc != ZKG16_OK) return rc;
     try {
         zk::vb_host(key, b, threads, ok, ok_each);
+    } catch (const std::bad_alloc &) {
+        return ZKG16_ERR_OOM;
+    }
+    return ZKG16_OK;
+}
+
+// ---- the prime form (verify_batch.hpp): one extended key for every request of a trapdoor
+// gamma_abc_g1 of the template (258 x 12) followed by V_n and -V_j of the key corrections (zkg16_prime_key_corrections: U | V_n | V_j)
+int zkg16_prime_vk_extend(const uint64_t *gamma_abc_g1, const uint64_t corr[36], uint64_t *out) {
+    if (!gamma_abc_g1 || !corr || !out) return ZKG16_ERR_BAD_ARG;
+    for (int c = 0; c < 3; c++) {
+        uint64_t any = 0;
+        for (int t = 0; t < 12; t++) any |= corr[12 * c + t];
+        if (!any) return ZKG16_ERR_BAD_ARG;                 // zero limbs: the point at infinity
+    }
+    memcpy(out, gamma_abc_g1, 258 * 12 * sizeof(uint64_t));
+    memcpy(out + 258 * 12, corr + 12, 12 * sizeof(uint64_t));
+    zk::h64::Fq64 y;
+    memcpy(y.l, corr + 24 + 6, 48);
+    y = zk::h64::neg(y);
+    memcpy(out + 259 * 12, corr + 24, 48);
+    memcpy(out + 259 * 12 + 6, y.l, 48);
+    return ZKG16_OK;
+}
+
+// a request's 259 public inputs under the extended key: zkg16_prime_public_inputs, then n and j.  Montgomery
+int zkg16_prime_ext_inputs(uint64_t x, uint64_t j, uint64_t *out) {
+    if (!out) return ZKG16_ERR_BAD_ARG;
+    uint8_t digest[32];
+    uint32_t d[8];
+    const int rc = zkg16_prime_candidate(x, j, digest, nullptr, nullptr, nullptr, nullptr);
+    if (rc != ZKG16_OK) return rc;
+    memcpy(d, digest, 32);          // little-endian host: the words of the inputs kernel
+    zk::vb_prime_expand(&x, &j, d, 1, out);
+    return ZKG16_OK;
+}
+
+int zkg16_verify_prime_batch_host(const uint64_t *gamma_abc_g1, size_t num_instance, const uint64_t alpha_beta[72], const uint64_t *gamma_neg_coeffs,
+                                  const uint64_t *delta_neg_coeffs, size_t n_coeffs, const uint64_t *xs, const uint64_t *js, const uint64_t *proofs,
+                                  const uint8_t *inf, const uint64_t *rho, size_t k, int threads, int *ok, uint8_t *ok_each) {
+    if (num_instance != 260 || !xs || !js || threads < 0 || k >> 32) return ZKG16_ERR_BAD_ARG;
+    const zk::VbKey key{gamma_abc_g1, num_instance, alpha_beta, gamma_neg_coeffs, delta_neg_coeffs, n_coeffs};
+    {
+        const int rc = zk::vb_check_args(key, zk::VbBatch{xs, proofs, inf, rho, k}, ok);      // xs stands in for the inputs made below
+        if (rc != ZKG16_OK) return rc;
+    }
+    try {
+        std::vector<uint64_t> pub(4 * 259 * k);
+        for (size_t i = 0; i < k; i++) (void)zkg16_prime_ext_inputs(xs[i], js[i], pub.data() + 4 * 259 * i);      // fails on a null pointer only
+        zk::vb_host(key, zk::VbBatch{pub.data(), proofs, inf, rho, k}, threads, ok, ok_each);
     } catch (const std::bad_alloc &) {
         return ZKG16_ERR_OOM;
     }

@@ -9,6 +9,11 @@
 //   each_x_kernel         the prepared public input X of each listed proof, to affine (pairing_each_dev.cuh, as the two below)
 //   each_miller_kernel    ML(A, B) ML(X, -gamma) ML(C, -delta) of each listed proof: one squaring per bit for the three pairs
 //   final_exp_kernel      the final exponentiation of n Fq12 values, and (for the per-proof pass) the comparison with e(alpha, beta)
+//   prime_inputs_kernel   the prime form's front (prime_inputs_dev.cuh): SHA-256(x + j) of each request, one GPU lane each
+//   prime_rho_sums_kernel the 260 multiplier sums of the batch equation under the extended key: one 256-lane block per 128 proofs,
+//                         lane t owning digest bit t (rho and the digest word are the same address for a whole wave), then
+//   prime_sums_reduce_kernel  the blocks' partial sums added up, one lane per column — integer sums, so any order gives the same
+//   prime_z_expand_kernel the 259 canonical scalars of each listed request, for each_x_kernel
 //
 // Registers: a Miller lane's state is f (12 Fq = 168 dwords), T (84), Q and P (84) and the operation at hand; every Fq product is a
 // call (ffu.cuh: fqu_mul_call), so what is live across it sits in the callee-saved registers or in scratch: 4,272 B of scratch
@@ -22,6 +27,7 @@
 #include "decompress_dev.cuh"
 #include "pairing_dev.cuh"
 #include "pairing_each_dev.cuh"
+#include "prime_inputs_dev.cuh"
 
 namespace zk {
 namespace {
@@ -163,6 +169,58 @@ __global__ __launch_bounds__(64) void final_exp_kernel(const uint64_t *f, size_t
     }
 }
 
+// ---- the prime form's front (prime_inputs_dev.cuh)
+// request i: dig[8 i ..] = its digest words, n_out[i] (nullable) = the digest mod 2^20, pub (nullable) + 257 * 4 * i = its 257
+// Montgomery public inputs (zkg16_prime_public_inputs)
+__global__ __launch_bounds__(64) void prime_inputs_kernel(const uint64_t *xs, const uint64_t *js, size_t n, uint32_t *dig, uint32_t *n_out, uint64_t *pub) {
+    const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    uint32_t d[8];
+    pi::prime_digest(xs[i], js[i], d);
+    uint4 *o = reinterpret_cast<uint4 *>(dig + 8 * i);
+    o[0] = make_uint4(d[0], d[1], d[2], d[3]);
+    o[1] = make_uint4(d[4], d[5], d[6], d[7]);
+    if (n_out) n_out[i] = pi::digest_n(d);
+    if (pub) pi::public_inputs_mont(xs[i], d, reinterpret_cast<Fr *>(pub + 4 * 257 * i));
+}
+
+// block b: the sums of the proofs [b * SUM_SLICE, min(k, (b + 1) * SUM_SLICE)) -> partial + b * 260 * 4 (every column written)
+__global__ __launch_bounds__(256) void prime_rho_sums_kernel(const uint64_t *xs, const uint64_t *js, const uint32_t *dig, const uint64_t *rho, const uint8_t *live,
+                                                             size_t k, uint64_t *partial) {
+    const size_t lo = (size_t)blockIdx.x * pi::SUM_SLICE, hi = lo + pi::SUM_SLICE < k ? lo + pi::SUM_SLICE : k;
+    const unsigned t = threadIdx.x;
+    uint64_t bit[4], extra[4];
+    pi::column_sums(t, xs, js, dig, rho, live, lo, hi, bit, extra);
+    uint64_t *o = partial + (size_t)blockIdx.x * pi::EXT_INSTANCE * 4;
+#pragma unroll
+    for (int i = 0; i < 4; i++) o[4 * (2 + t) + i] = bit[i];
+    if (t < 4) {
+        const unsigned c = pi::extra_column(t);
+#pragma unroll
+        for (int i = 0; i < 4; i++) o[4 * c + i] = extra[i];
+    }
+}
+
+// sums[c] = sum over the blocks of partial[b][c], c < 260
+__global__ __launch_bounds__(64) void prime_sums_reduce_kernel(const uint64_t *partial, size_t blocks, uint64_t *sums) {
+    const size_t c = (size_t)blockIdx.x * 64 + threadIdx.x;
+    if (c >= pi::EXT_INSTANCE) return;
+    uint64_t acc[4] = {0, 0, 0, 0};
+    for (size_t b = 0; b < blocks; b++) pi::add256(acc, partial + (b * pi::EXT_INSTANCE + c) * 4);
+#pragma unroll
+    for (int i = 0; i < 4; i++) sums[4 * c + i] = acc[i];
+}
+
+// z + 4 * (259 * j + c) = scalar c of request idx[j] (idx null: request j), j < n: one lane per scalar
+__global__ __launch_bounds__(256) void prime_z_expand_kernel(const uint32_t *idx, size_t n, const uint64_t *xs, const uint64_t *js, const uint32_t *dig, uint64_t *z) {
+    const size_t g = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (g >= n * pi::EXT_INPUTS) return;
+    const size_t j = g / pi::EXT_INPUTS, i = idx ? idx[j] : j;
+    const unsigned c = (unsigned)(g % pi::EXT_INPUTS);
+    ulonglong4 *o = reinterpret_cast<ulonglong4 *>(z + 4 * g);
+    *o = make_ulonglong4(pi::ext_scalar(c, xs[i], js[i], dig + 8 * i), 0, 0, 0);
+}
+
 unsigned blocks_of(size_t n) { return (unsigned)((n + 63) / 64); }
 
 }  // namespace
@@ -210,6 +268,31 @@ void vb_each_launch(hipStream_t st, const uint32_t *key_words, size_t num_instan
     ZK_HIP(hipGetLastError());
     hipLaunchKernelGGL(final_exp_kernel, dim3(blocks_of(n)), dim3(64), 0, st, (const uint64_t *)f, n, vb_frob(), (uint64_t *)nullptr,
                        reinterpret_cast<const uint64_t *>(key_words), verdict);
+    ZK_HIP(hipGetLastError());
+}
+
+void vb_prime_inputs_launch(hipStream_t st, const uint64_t *xs, const uint64_t *js, size_t n, uint32_t *dig, uint32_t *n_out, uint64_t *pub) {
+    if (!n) return;
+    hipLaunchKernelGGL(prime_inputs_kernel, dim3(blocks_of(n)), dim3(64), 0, st, xs, js, n, dig, n_out, pub);
+    ZK_HIP(hipGetLastError());
+}
+
+size_t vb_prime_sums_blocks(size_t k) { return (k + pi::SUM_SLICE - 1) / pi::SUM_SLICE; }
+
+void vb_prime_sums_launch(hipStream_t st, const uint64_t *xs, const uint64_t *js, const uint32_t *dig, const uint64_t *rho, const uint8_t *live, size_t k,
+                          uint64_t *partial, uint64_t *sums) {
+    const size_t blocks = vb_prime_sums_blocks(k);
+    if (blocks) {
+        hipLaunchKernelGGL(prime_rho_sums_kernel, dim3((unsigned)blocks), dim3(pi::SUM_LANES), 0, st, xs, js, dig, rho, live, k, partial);
+        ZK_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(prime_sums_reduce_kernel, dim3(blocks_of(pi::EXT_INSTANCE)), dim3(64), 0, st, (const uint64_t *)partial, blocks, sums);
+    ZK_HIP(hipGetLastError());
+}
+
+void vb_prime_z_launch(hipStream_t st, const uint32_t *idx, size_t n, const uint64_t *xs, const uint64_t *js, const uint32_t *dig, uint64_t *z) {
+    if (!n) return;
+    hipLaunchKernelGGL(prime_z_expand_kernel, dim3((unsigned)((n * pi::EXT_INPUTS + 255) / 256)), dim3(256), 0, st, idx, n, xs, js, dig, z);
     ZK_HIP(hipGetLastError());
 }
 

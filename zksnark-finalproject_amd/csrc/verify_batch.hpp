@@ -51,8 +51,22 @@ struct VbEach {
     size_t after = 0;
     size_t range_tests = 0;
 };
+// Where the public inputs come from when b.public_inputs is null (the prime form; num_instance = 260).  sums (nullable): the
+// num_instance multiplier sums s_i = sum_k rho_k z_{k,i} (z_{k,0} = 1) over the member proofs as plain integers below r, 4 u64 each
+// (vb_prime_sums_launch): the whole-batch test takes them instead of walking K x 259 inputs; s_0 is also summed here, and when the
+// two differ the sums are not used and sums_refused is set (out).  expand(): the k x (num_instance - 1) x 4 Montgomery inputs,
+// called at most once and only when a range test needs them (bisecting, or no sums).
+struct VbInputs {
+    const uint64_t *sums = nullptr;
+    std::function<const uint64_t *()> expand;
+    bool sums_refused = false;
+};
 void vb_decide(const VbKey &key, const VbBatch &b, const uint8_t *member, const std::function<const uint64_t *()> &fetch_miller, const uint64_t *prod,
-               const uint64_t *sum_c, const uint8_t *sum_c_inf, int threads, int *ok, uint8_t *ok_each, float ms[2], VbEach *each = nullptr);
+               const uint64_t *sum_c, const uint8_t *sum_c_inf, int threads, int *ok, uint8_t *ok_each, float ms[2], VbEach *each = nullptr,
+               VbInputs *inputs = nullptr);
+// the prime form's inputs on the host: digests (k x 8 words as the inputs kernel writes them = k x 32 digest bytes) ->
+// out (k x 259 x 4, Montgomery): x, the 256 digest bits, n = the digest mod 2^20, j
+void vb_prime_expand(const uint64_t *xs, const uint64_t *js, const uint32_t *digests, size_t k, uint64_t *out);
 // everything on host threads (zkg16_verify_batch_host).  dead (nullable, k bytes): proofs counted as failing membership whatever
 // their limbs say (zkg16_verify_batch_wire: a proof with a point that did not decode; its zero limbs would read as infinity)
 void vb_host(const VbKey &key, const VbBatch &b, int threads, int *ok, uint8_t *ok_each, const uint8_t *dead = nullptr);
@@ -108,5 +122,18 @@ size_t vb_each_scratch_bytes(size_t n);
 // Three kernels: X_k, the three-pair Miller loop (one squaring per bit), the final exponentiation with the comparison
 void vb_each_launch(hipStream_t st, const uint32_t *key_words, size_t num_instance, const uint32_t *idx, size_t n, const uint64_t *proofs, const uint8_t *inf,
                     const uint64_t *z, void *scratch, uint8_t *verdict);
+
+// ---- the prime form's front (prime_inputs_dev.cuh): K prime requests of one trapdoor under the extended key of 260 points
+// (zkg16_prime_vk_extend), whose 259 public inputs x, bit_0 .. bit_255, n, j all follow from the 16 bytes (x, j).  Device pointers
+// request i < n: dig[8 i .. 8 i + 7] = SHA-256(le32(x_i + j_i)) as little-endian words, n_out[i] (nullable) = the digest mod 2^20,
+// pub (nullable) + 257 * 4 * i = zkg16_prime_public_inputs(x_i, j_i)
+void vb_prime_inputs_launch(hipStream_t st, const uint64_t *xs, const uint64_t *js, size_t n, uint32_t *dig, uint32_t *n_out, uint64_t *pub);
+// sums (260 x 4 u64, plain integers, unreduced) = sum_k rho_k (1, x_k, bit_0 .. bit_255, n_k, j_k) over the proofs with live[k] != 0
+// (live null: all k of them); dig from the launch above; partial: room for vb_prime_sums_blocks(k) x 260 x 4 u64.  k < 2^32
+size_t vb_prime_sums_blocks(size_t k);
+void vb_prime_sums_launch(hipStream_t st, const uint64_t *xs, const uint64_t *js, const uint32_t *dig, const uint64_t *rho, const uint8_t *live, size_t k,
+                          uint64_t *partial, uint64_t *sums);
+// z (n x 259 x 4 canonical limbs, what vb_each_launch reads) of the requests idx[0 .. n) (idx null: requests 0 .. n - 1)
+void vb_prime_z_launch(hipStream_t st, const uint32_t *idx, size_t n, const uint64_t *xs, const uint64_t *js, const uint32_t *dig, uint64_t *z);
 
 }  // namespace zk

@@ -345,6 +345,62 @@ class Device:
         self._check(self.lib.zkg16_verify_each(self.ctx, *args[:9], k, _ptr(ok_each)))
         return ok_each.astype(bool)
 
+    # ---- the prime form: K prime requests of one trapdoor under the extended key (circuits.prime_vk_extend)
+    def verify_prime_batch(self, pvk, xs, js, proofs, infs, rho=None, each=False):
+        """verify_batch for K proofs of the prime handler made under one trapdoor (zkg16_verify_prime_batch): pvk = the prepared
+        extended key (260 gamma_abc_g1 points), xs / js [k] u64; the 259 public inputs of each proof and the multiplier sums of the
+        batch equation are made on the device from those 16 bytes.  Everything else as verify_batch."""
+        xs, js = _u64(xs).reshape(-1), _u64(js).reshape(-1)
+        args, k = _verify_prime_args(pvk, xs, js, proofs, infs, rho)
+        ok = C.c_int(0)
+        ok_each = np.zeros(k, dtype=np.uint8) if each else None
+        self._check(self.lib.zkg16_verify_prime_batch(self.ctx, *args, C.byref(ok), _ptr(ok_each)))
+        return (bool(ok.value), ok_each.astype(bool)) if each else bool(ok.value)
+
+    def verify_prime_batch_wire(self, pvk, xs, js, proof_bytes, rho=None, each=False, status=False):
+        """verify_batch_wire for the prime form (zkg16_verify_prime_batch_wire): proof_bytes = k x 192 compressed bytes; rho is
+        drawn from `secrets` when None.  Returns as verify_batch_wire."""
+        raw = np.ascontiguousarray(np.frombuffer(proof_bytes, dtype=np.uint8) if isinstance(proof_bytes, (bytes, bytearray, memoryview))
+                                   else np.asarray(proof_bytes, dtype=np.uint8)).reshape(-1)
+        if raw.size % 192:
+            raise ValueError("verify_prime_batch_wire: a compressed proof is 192 bytes")
+        k = raw.size // 192
+        xs, js = _u64(xs).reshape(-1), _u64(js).reshape(-1)
+        args, _ = _verify_prime_args(pvk, xs, js, None, None, rho, k=k)
+        ok = C.c_int(0)
+        ok_each = np.zeros(k, dtype=np.uint8) if each else None
+        st = np.zeros((k, 3), dtype=np.uint8) if status else None
+        self._check(self.lib.zkg16_verify_prime_batch_wire(self.ctx, *args[:8], _ptr(raw) if k else None, args[10], k, C.byref(ok), _ptr(ok_each), _ptr(st)))
+        out = (bool(ok.value),) + ((ok_each.astype(bool),) if each else ()) + ((st,) if status else ())
+        return out if len(out) > 1 else out[0]
+
+    def prime_inputs_batch(self, xs, js, public_inputs=False):
+        """The inputs kernel by itself (zkg16_prime_inputs_batch) -> (digests [k, 32] u8, n [k] u32), followed by the
+        [k, 257, 4] Montgomery public inputs with public_inputs=True: circuits.prime_candidate / prime_public_inputs of each (x, j)."""
+        xs, js = _u64(xs).reshape(-1), _u64(js).reshape(-1)
+        k = xs.shape[0]
+        if js.shape[0] != k:
+            raise ValueError("prime_inputs_batch: one j per x")
+        dig = np.zeros((k, 32), dtype=np.uint8)
+        n = np.zeros(k, dtype=np.uint32)
+        pub = np.zeros((k, 257, 4), dtype=np.uint64) if public_inputs else None
+        self._check(self.lib.zkg16_prime_inputs_batch(self.ctx, _ptr(xs) if k else None, _ptr(js) if k else None, k, _ptr(dig) if k else None,
+                                                      _ptr(n) if k else None, _ptr(pub) if k else None))
+        return (dig, n, pub) if public_inputs else (dig, n)
+
+    def prime_rho_sums(self, xs, js, rho, live=None):
+        """The sums kernels by themselves (zkg16_prime_rho_sums): rho [k, 2], live [k] bytes or None (all) -> the 260 sums
+        sum_k rho_k (1, x_k, bit_0 .. bit_255, n_k, j_k) as Python integers (unreduced)."""
+        xs, js, rho = _u64(xs).reshape(-1), _u64(js).reshape(-1), _u64(rho).reshape(-1, 2)
+        k = xs.shape[0]
+        live = None if live is None else np.ascontiguousarray(live, dtype=np.uint8).reshape(-1)
+        if js.shape[0] != k or rho.shape[0] != k or (live is not None and live.shape[0] != k):
+            raise ValueError("prime_rho_sums: one j, one multiplier and one live byte per x")
+        sums = np.zeros((260, 4), dtype=np.uint64)
+        self._check(self.lib.zkg16_prime_rho_sums(self.ctx, _ptr(xs) if k else None, _ptr(js) if k else None, _ptr(rho) if k else None,
+                                                  _ptr(live) if k else None, k, _ptr(sums)))
+        return [sum(int(v) << (64 * i) for i, v in enumerate(row)) for row in sums]
+
     def final_exp_batch(self, f):
         """The verifier's final exponentiation of n Fq12 values on the device (zkg16_final_exp_batch): [n, 72] -> [n, 72], each row
         bit-equal to final_exp() of that row."""
@@ -372,13 +428,17 @@ class Device:
             self._check(rc)
         return out, inf, status[:n].copy()
 
-    def verify_batch_timings(self):
+    def verify_batch_timings(self, prime=False):
         """ms of the last verify_batch / verify_batch_wire: membership, scaling + Miller, product tree, MSM, host equation, bisecting,
         total wall, whether the host form answered, the decode kernels (verify_batch_wire only), the per-proof pass that took over
-        from bisecting (0 when it did not run) and the number of range tests bisecting made."""
-        ms = (C.c_float * 11)()
-        n = self.lib.zkg16_verify_batch_timings(self.ctx, ms, 11)
-        names = ("membership_ms", "miller_ms", "product_ms", "msm_ms", "host_ms", "bisect_ms", "total_ms", "host_form", "decode_ms", "each_ms", "range_tests")
+        from bisecting (0 when it did not run) and the number of range tests bisecting made.  prime=True (after verify_prime_batch /
+        verify_prime_batch_wire) adds prime_inputs_ms and prime_sums_ms, the two kernels of the prime form's front (0 when the host
+        form answered or the last call was not a prime call)."""
+        names = ("membership_ms", "miller_ms", "product_ms", "msm_ms", "host_ms", "bisect_ms", "total_ms", "host_form", "decode_ms", "each_ms", "range_tests",
+                 "prime_inputs_ms", "prime_sums_ms")
+        cap = 13 if prime else 11
+        ms = (C.c_float * cap)()
+        n = self.lib.zkg16_verify_batch_timings(self.ctx, ms, cap)
         return {names[i]: float(ms[i]) for i in range(n)}
 
     def miller_loop_batch(self, g1, g2, g1_inf=None, g2_inf=None):
@@ -781,6 +841,37 @@ def _verify_batch_args(pvk, public_inputs, proofs, infs, rho, k=None):
     keep = (gabc, ab, g, d, pub, proofs, infs, rho)
     return _KeepAlive((_ptr(gabc), gabc.shape[0], _ptr(ab), _ptr(g), _ptr(d), g.shape[0], _ptr(pub) if pub.size else None, _ptr(proofs), _ptr(infs),
                        _ptr(rho), k), keep), k
+
+
+def _verify_prime_args(pvk, xs, js, proofs, infs, rho, k=None):
+    """_verify_batch_args for the prime form: xs, js [k] in the place of the public inputs"""
+    gabc = _u64(pvk["gamma_abc_g1"]).reshape(-1, 12)
+    proofs = _u64(proofs).reshape(-1, 48) if proofs is not None else None
+    k = proofs.shape[0] if proofs is not None else k
+    infs = np.ascontiguousarray(infs, dtype=np.uint8).reshape(-1, 3) if proofs is not None else None
+    if xs.shape[0] != k or js.shape[0] != k:
+        raise ValueError("verify_prime_batch: one x and one j per proof")
+    if infs is not None and infs.shape[0] != k:
+        raise ValueError("verify_prime_batch: one flag triple per proof")
+    rho = draw_rho(k) if rho is None else _u64(rho).reshape(-1, 2)
+    if rho.shape[0] != k:
+        raise ValueError("verify_prime_batch: one multiplier per proof")
+    g, d = _u64(pvk["gamma_neg_pc"]).reshape(-1, 36), _u64(pvk["delta_neg_pc"]).reshape(-1, 36)
+    ab = _u64(pvk["alpha_beta"])
+    keep = (gabc, ab, g, d, xs, js, proofs, infs, rho)
+    return _KeepAlive((_ptr(gabc), gabc.shape[0], _ptr(ab), _ptr(g), _ptr(d), g.shape[0], _ptr(xs) if k else None, _ptr(js) if k else None, _ptr(proofs),
+                       _ptr(infs), _ptr(rho), k), keep), k
+
+
+def verify_prime_batch_host(pvk, xs, js, proofs, infs, rho=None, each=False, threads=0):
+    """Device.verify_prime_batch's verdicts on host threads alone (zkg16_verify_prime_batch_host; threads 0 = 8; no GPU)."""
+    lib = _lib.load()
+    xs, js = _u64(xs).reshape(-1), _u64(js).reshape(-1)
+    args, k = _verify_prime_args(pvk, xs, js, proofs, infs, rho)
+    ok = C.c_int(0)
+    ok_each = np.zeros(k, dtype=np.uint8) if each else None
+    _check_host(lib.zkg16_verify_prime_batch_host(*args, threads, C.byref(ok), _ptr(ok_each)))
+    return (bool(ok.value), ok_each.astype(bool)) if each else bool(ok.value)
 
 
 class _KeepAlive(tuple):

@@ -4,6 +4,7 @@
     prove_fibonacci  src/arkworks/backend/fibbonaci_handler.rs:98-145
     prove_prime / verify_prime  src/arkworks/backend/prime_snark.rs:49-146, 165-206
     prove_primes     K prime requests under one trapdoor on ONE template key, in batched device passes (no counterpart upstream)
+    verify_primes    K such proofs checked together under the ONE extended key of their trapdoor (no counterpart upstream)
 Same steps, same response fields: the circuit's R1CS and assignment (built on the device for matrix and prime requests,
 synthesized inside the library and loaded unexported for Fibonacci; the host C++ mirror's arrays only where a test wants them),
 per-request Groth16 setup (on the device, zkg16_setup_resident), prove (zkg16_prove_resident), encode (wire.py): one sequence for
@@ -25,7 +26,7 @@ import numpy as np
 from . import _lib, device, wire
 from ._lib import Zkg16Error
 from .circuits import (fibonacci_circuit, fibonacci_circuit_handle, matrix_circuit, matrix_hash_batch_host, prime_circuit, prime_dims, prime_key_corrections,
-                       prime_public_inputs, prime_search)
+                       prime_public_inputs, prime_search, prime_vk_extend)
 from .workloads import R_MOD, g1_generator, g2_generator
 
 ZKG16_ERR_BAD_ARG = 1      # include/zkg16.h
@@ -278,8 +279,10 @@ _PRIME_NOT_FOUND = dict(proof="", j=0, num_constraints=0, num_variables=0, setup
 
 def prime_template_key(dev, rng):
     """The key every prime request of one trapdoor shares: prove_prime's draws from rng in its order (trapdoor, generators), one
-    setup on the template (Device.r1cs_prime_template) -> dict(ph, rh, vk, corr, setup_time).  The trapdoor itself is not kept:
-    corr (circuits.prime_key_corrections) is all a request needs of it.  The caller frees ph and rh."""
+    setup on the template (Device.r1cs_prime_template) -> dict(ph, rh, vk, corr, ext_vk, setup_time).  The trapdoor itself is not
+    kept: corr (circuits.prime_key_corrections) is all a request needs of it.  ext_vk: the template vk with the 260 gamma_abc_g1
+    points of circuits.prime_vk_extend, the ONE key verify_primes checks every request of this trapdoor under (it serialises
+    through wire.vk_serialize_compressed like any vk).  The caller frees ph and rh."""
     trap, g1, g2 = _draw_key(rng)
     corr, inf = prime_key_corrections(trap, g1)
     if inf.any():
@@ -291,7 +294,8 @@ def prime_template_key(dev, rng):
         ph, vk = dev.setup_resident(rh, prime_dims(1)["num_instance"], trap, g1, g2)
         setup_time = time.perf_counter() - t0
         stack.pop_all()                 # both handles are the caller's from here
-    return dict(ph=ph, rh=rh, vk=vk, corr=corr, setup_time=setup_time)
+    ext_vk = dict(vk, gamma_abc_g1=prime_vk_extend(vk["gamma_abc_g1"], corr))
+    return dict(ph=ph, rh=rh, vk=vk, corr=corr, ext_vk=ext_vk, setup_time=setup_time)
 
 
 def prove_primes(dev, requests, seed=7, key=None):
@@ -422,6 +426,52 @@ def verify_proofs(vk, public_inputs_list, proofs_b64, dev=None):
         else:
             _, each = device.verify_batch_host(pvk, pubs, np.array([p for p, _ in proofs], dtype=np.uint64),
                                                np.array([f for _, f in proofs], dtype=np.uint8), each=True)
+        for i, ok in zip(idx, each):
+            valid[i] = bool(ok)
+    return dict(valid=valid, verifying_time=time.perf_counter() - t1, decode_time=t1 - t0)
+
+
+def verify_primes(ext_vk, requests, dev=None):
+    """verify_prime for K proofs made under one trapdoor (prove_primes), checked together under its ONE extended key
+    (prime_template_key's ext_vk: a dict, or the base64 of its compressed bytes; prepared or not).  requests = [(x, j, proof_b64), ...]
+    -> {valid: [K bools], verifying_time, decode_time}.  With dev the proofs stay bytes and the public inputs are never made on
+    the host (Device.verify_prime_batch_wire); without, host decoding and device.verify_prime_batch_host.  A proof that does not
+    decode, or whose x or j is no u64, is valid=False for that entry only; a key that does not decode, or whose point count is
+    not 260, makes every entry invalid — verify_proofs' rules."""
+    t0 = time.perf_counter()
+    k = len(requests)
+    valid = [False] * k
+    try:
+        vk = _decode_key(ext_vk)
+        pvk = vk if "alpha_beta" in vk else device.pvk_prepare(vk)
+        if np.asarray(pvk["gamma_abc_g1"]).reshape(-1, 12).shape[0] != 260:
+            raise ValueError("verify_primes: an extended key has 260 gamma_abc_g1 points")
+    except (ValueError, IndexError, Zkg16Error) as e:
+        if not _answers_invalid(e):
+            raise
+        return dict(valid=valid, verifying_time=0.0, decode_time=time.perf_counter() - t0)
+    keep_bytes = dev is not None
+    idx, proofs, xs, js = [], [], [], []
+    for i, (x, j, pb) in enumerate(requests):
+        try:
+            proof = base64.standard_b64decode(pb) if keep_bytes else wire.decode_proof(pb)
+            x, j = int(x), int(j)
+            if not (0 <= x < 1 << 64 and 0 <= j < 1 << 64) or (keep_bytes and len(proof) != 192):
+                continue
+        except (ValueError, IndexError, TypeError):
+            continue
+        idx.append(i)
+        proofs.append(proof)
+        xs.append(x)
+        js.append(j)
+    t1 = time.perf_counter()
+    if idx:
+        xs, js = np.array(xs, dtype=np.uint64), np.array(js, dtype=np.uint64)
+        if keep_bytes:
+            _, each = dev.verify_prime_batch_wire(pvk, xs, js, b"".join(proofs), each=True)
+        else:
+            _, each = device.verify_prime_batch_host(pvk, xs, js, np.array([p for p, _ in proofs], dtype=np.uint64),
+                                                     np.array([f for _, f in proofs], dtype=np.uint8), each=True)
         for i, ok in zip(idx, each):
             valid[i] = bool(ok)
     return dict(valid=valid, verifying_time=time.perf_counter() - t1, decode_time=t1 - t0)
