@@ -93,9 +93,27 @@ ZKG16_API int zkg16_pk_slice(zkg16_ctx *ctx, uint64_t pk_handle, size_t z_lo, si
  * proof (128x128: 181 -> 171 ms, 46x46: 22.6 -> 19.7 ms), for (254/c) x the key's HBM and c * (254/c) doublings per base once.  window_bits_z covers a / b_g1 / b_g2 / l,
  * window_bits_h h_query: 0 = chosen from the query length (none under 393,216 terms), 4..24 = as given, < 0 = leave that side
  * without a table.
- * table_bytes (nullable): HBM added.  Not part of the reference's flow (its key is rebuilt per request): for servers that keep a
+ * table_bytes (nullable): HBM added (the tables, zkg16_table_layout, minus the plain queries they replace).  Not part of the reference's flow (its key is rebuilt per request): for servers that keep a
  * circuit's key resident.  A second call for a side that already has its table is ZKG16_ERR_BAD_ARG. */
 ZKG16_API int zkg16_pk_precompute(zkg16_ctx *ctx, uint64_t pk_handle, int window_bits_z, int window_bits_h, uint64_t *table_bytes);
+/* Entry layout of a window table (host-only, no ctx, no GPU).  kind: 1 = G1, 2 = G2; n bases, digits levels (= 254 / c + 1, level 0 is
+ * a copy of the query).  stride_mode as option "table_stride": 1 = packed (an entry is the two coordinates, 112 / 224 bytes, and
+ * straddles 128-byte cache lines 7 times out of 8), 2 = padded to whole lines (128 / 256 bytes; one seventh more HBM), 0 = the
+ * library's choice: ZKG16_TABLE_STRIDE_DEFAULT_G1 / _G2 for a table of at least ZKG16_TABLE_STRIDE_PAD_MIN_BYTES packed bytes — one
+ * that cannot stay in the 256 MiB last-level cache, so its gathers are HBM requests, where whole lines were measured to pay — and
+ * packed below that.
+ * -> *entry_stride bytes between entries, *bytes = n x digits x stride of the whole table (either nullable).
+ * zkg16_pk_precompute lays each table out by this rule with the option's value at that call (a table keeps its layout afterwards) and
+ * falls back from padded to packed when only the packed tables fit the free HBM.  ZKG16_ERR_BAD_ARG: unknown kind or mode, digits < 1,
+ * or a size beyond 64 bits. */
+#define ZKG16_TABLE_STRIDE_PACKED_G1 112
+#define ZKG16_TABLE_STRIDE_PACKED_G2 224
+#define ZKG16_TABLE_STRIDE_PADDED_G1 128
+#define ZKG16_TABLE_STRIDE_PADDED_G2 256
+#define ZKG16_TABLE_STRIDE_DEFAULT_G1 2      /* what mode 0 means for a large table, per kind (measured: DESIGN.md 2.4) */
+#define ZKG16_TABLE_STRIDE_DEFAULT_G2 2
+#define ZKG16_TABLE_STRIDE_PAD_MIN_BYTES 268435456      /* 256 MiB */
+ZKG16_API int zkg16_table_layout(int kind, size_t n, int digits, int stride_mode, size_t *entry_stride, uint64_t *bytes);
 /* The widths of a handle's window tables (0 = that side has none). */
 ZKG16_API int zkg16_pk_table_bits(zkg16_ctx *ctx, uint64_t pk_handle, int *window_bits_z, int *window_bits_h);
 /* Rank roles for one proof over n_ranks GPUs (host-only, no ctx, no GPU).  ranges: n_ranks x 4 = z_lo, z_hi, h_lo, h_hi per rank;
@@ -631,6 +649,8 @@ ZKG16_API void zkg16_kernel_stats_reset(zkg16_ctx *ctx);
  *   "g1_inline"      G1 accumulation (plain loop): 0 / 1 (default) every field product inlined, no call; 2 = products as device-function calls
  *   "acc_lazy"       the default G1 / G2 accumulation loops: 1 (default) = mixed additions without the carry passes their results do not
  *                    need, 0 = the earlier additions (same sums; for A/B runs)
+ *   "table_stride"   entry layout of the window tables zkg16_pk_precompute builds from now on (zkg16_table_layout): 0 (default) = padded to
+ *                    whole cache lines for tables of at least 256 MiB, packed below; 1 = packed; 2 = padded.  An existing table keeps its layout
  *   "lanes"          proofs this ctx runs at a time (1..8, default 2): see the note on re-entrancy at the top
  *   "matrix_parts"   zkg16_prove_matrix: slices of the host sponges the proof is fed in (0 = five growing slices, k = k equal ones; 1 = assignment first, then the proof)
  *   "batch_max"      zkg16_prove_batch / zkg16_prove_matrix_batch: proofs per device pass (0 = as many as fit, else 1..65535)

@@ -36,6 +36,7 @@ SIGNATURES = {
     "zkg16_lane_log": (C.c_int, [ctxp, C.POINTER(C.c_double), C.c_int]),
     "zkg16_last_acc_waves": (C.c_int, [ctxp, C.POINTER(C.c_int)]),
     "zkg16_acc_resident_waves": (C.c_int, [ctxp, C.POINTER(C.c_int)]),
+    "zkg16_table_layout": (C.c_int, [C.c_int, sz, C.c_int, C.c_int, C.POINTER(sz), C.POINTER(C.c_uint64)]),
     "zkg16_pk_table_bits": (C.c_int, [ctxp, H, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "zkg16_r1cs_spmv_state": (C.c_int, [ctxp, H, C.POINTER(C.c_uint32)]),
     "zkg16_group_create": (C.c_int, [vp, C.c_int, C.POINTER(vp)]),

@@ -231,6 +231,16 @@ void dev_release(void *p, size_t bytes) noexcept {
         if (ms > 1.0) fprintf(stderr, "dev_release: hipFree of %.1f MB took %.2f ms\n", bytes / 1048576.0, ms);
     }
 }
+uint64_t dev_cached_bytes() {
+    DevCache &c = dev_cache();
+    int cur = 0;
+    (void)hipGetDevice(&cur);
+    std::lock_guard<std::mutex> lk(c.mu);
+    uint64_t sum = 0;
+    for (auto &kv : c.free_blocks)
+        if (kv.first.first == cur) sum += kv.first.second;
+    return sum;
+}
 void dev_cache_flush() noexcept {
     DevCache &c = dev_cache();
     std::lock_guard<std::mutex> lk(c.mu);
@@ -345,6 +355,8 @@ int set_option_one(zkg16_ctx *ctx, const char *name, int64_t v) {
     // 3: the top seven stages by lane exchanges too; 4: two per trip (radix 4)
     if (is("ntt_radix")) return set(o.ntt_radix, 0, 4, v == 0 ? 1 : v);
     if (is("ntt_xcd")) return set(o.ntt_xcd, 0, 2, v == 2 ? 0 : 1);          // 1 (default): XCD-aware tile order in the NTT passes; 2 = off (0 restores the default)
+    // entry stride of window tables built after this call (zkg16_pk_precompute; an existing table keeps its layout): 0 = by table size (default), 1 = packed, 2 = padded
+    if (is("table_stride")) return set(o.table_stride, 0, 2, v);
     if (is("acc_debug")) return set(o.acc_debug, 0, 15, v);                  // timing probes of the accumulation kernels; results are WRONG while set
     if (is("sort_mode")) return set(o.sort_mode, 0, 1, v);                   // 0 (default): hand-written wave-ballot bucket scatter; 1: rocPRIM device radix sort
     // bit 0: G1, bit 1: G2 software-pipelined gather; 0 (default) and 4: neither.  With four G1 waves per SIMD and window tables the

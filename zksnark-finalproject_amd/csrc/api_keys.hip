@@ -252,16 +252,23 @@ int zkg16_pk_slice(zkg16_ctx *ctx, uint64_t src_handle, size_t z_lo, size_t z_hi
     pk->l.alloc((nz + 3) * sizeof(G1AffineU));
     pk->b2.alloc((nz + 3) * sizeof(G2AffineU));
     pk->h.alloc((nh ? nh : 1) * sizeof(G1AffineU));
-    auto cp = [&](DevBuf &dst, const DevBuf &from, size_t elem) {
-        if (nz) ZK_HIP(hipMemcpyAsync(dst.p, static_cast<const unsigned char *>(from.p) + z_lo * elem, nz * elem, hipMemcpyDeviceToDevice, ctx->stream));
-        ZK_HIP(hipMemcpyAsync(static_cast<unsigned char *>(dst.p) + nz * elem, static_cast<const unsigned char *>(from.p) + sm * elem, 3 * elem,
-                              hipMemcpyDeviceToDevice, ctx->stream));      // the three trailing delta slots
+    // the shard is a plain key: level 0 of the source (the query itself), packed again when the source's table holds padded entries
+    auto cp_range = [&](void *dst, const DevBuf &from, size_t lo, size_t cnt, size_t elem, bool padded) {
+        if (!cnt) return;
+        const size_t stride = padded ? (elem == sizeof(G2AffineU) ? (size_t)ZKG16_TABLE_STRIDE_PADDED_G2 : (size_t)ZKG16_TABLE_STRIDE_PADDED_G1) : elem;
+        const unsigned char *s = static_cast<const unsigned char *>(from.p) + lo * stride;
+        if (padded) msm_bases_restride(ctx, s, stride, dst, elem, elem, cnt);
+        else ZK_HIP(hipMemcpyAsync(dst, s, cnt * elem, hipMemcpyDeviceToDevice, ctx->stream));
     };
-    cp(pk->a, src->a, sizeof(G1AffineU));
-    cp(pk->b1, src->b1, sizeof(G1AffineU));
-    cp(pk->l, src->l, sizeof(G1AffineU));
-    cp(pk->b2, src->b2, sizeof(G2AffineU));
-    if (nh) ZK_HIP(hipMemcpyAsync(pk->h.p, src->h.as<G1AffineU>() + h_lo, nh * sizeof(G1AffineU), hipMemcpyDeviceToDevice, ctx->stream));
+    auto cp = [&](DevBuf &dst, const DevBuf &from, size_t elem, bool padded) {
+        cp_range(dst.p, from, z_lo, nz, elem, padded);
+        cp_range(static_cast<unsigned char *>(dst.p) + nz * elem, from, sm, 3, elem, padded);      // the three trailing delta slots
+    };
+    cp(pk->a, src->a, sizeof(G1AffineU), src->pad_z_g1);
+    cp(pk->b1, src->b1, sizeof(G1AffineU), src->pad_z_g1);
+    cp(pk->l, src->l, sizeof(G1AffineU), src->pad_z_g1);
+    cp(pk->b2, src->b2, sizeof(G2AffineU), src->pad_z_g2);
+    cp_range(pk->h.p, src->h, h_lo, nh, sizeof(G1AffineU), src->pad_h);
     pk->alpha_g1 = src->alpha_g1; pk->beta_g1 = src->beta_g1; pk->delta_g1 = src->delta_g1;
     pk->beta_g2 = src->beta_g2; pk->delta_g2 = src->delta_g2;
     pk->b_mask.alloc(nz + 3);
@@ -398,6 +405,21 @@ static int default_table_bits(size_t n) {
     }
     return best;
 }
+// Entry layout of a window table; the one rule zkg16_pk_precompute and its fit check go by (host-only)
+int zkg16_table_layout(int kind, size_t n, int digits, int stride_mode, size_t *entry_stride, uint64_t *bytes) {
+    if ((kind != 1 && kind != 2) || digits < 1 || stride_mode < 0 || stride_mode > 2) return ZKG16_ERR_BAD_ARG;
+    const uint64_t packed = kind == 1 ? ZKG16_TABLE_STRIDE_PACKED_G1 : ZKG16_TABLE_STRIDE_PACKED_G2;
+    const uint64_t padded = kind == 1 ? ZKG16_TABLE_STRIDE_PADDED_G1 : ZKG16_TABLE_STRIDE_PADDED_G2;
+    if (n && padded * (uint64_t)digits > UINT64_MAX / (uint64_t)n) return ZKG16_ERR_BAD_ARG;      // (stride x digits < 2^40)
+    if (stride_mode == 0) {
+        const bool large = packed * (uint64_t)digits * (uint64_t)n >= (uint64_t)ZKG16_TABLE_STRIDE_PAD_MIN_BYTES;
+        stride_mode = !large ? 1 : kind == 1 ? ZKG16_TABLE_STRIDE_DEFAULT_G1 : ZKG16_TABLE_STRIDE_DEFAULT_G2;
+    }
+    const uint64_t stride = stride_mode == 2 ? padded : packed;
+    if (entry_stride) *entry_stride = (size_t)stride;
+    if (bytes) *bytes = stride * (uint64_t)digits * (uint64_t)n;
+    return ZKG16_OK;
+}
 int zkg16_pk_precompute(zkg16_ctx *ctx, uint64_t pk_handle, int window_bits_z, int window_bits_h, uint64_t *table_bytes) {
     if (window_bits_z > 24 || window_bits_h > 24 || (window_bits_z > 0 && window_bits_z < 4) || (window_bits_h > 0 && window_bits_h < 4))
         return ZKG16_ERR_BAD_ARG;
@@ -410,20 +432,46 @@ int zkg16_pk_precompute(zkg16_ctx *ctx, uint64_t pk_handle, int window_bits_z, i
     const int cz = window_bits_z < 0 || (nz == 0 && !pk->blinding) ? 0 : window_bits_z ? window_bits_z : default_table_bits(nzs);
     const int ch = window_bits_h < 0 || nh == 0 ? 0 : window_bits_h ? window_bits_h : default_table_bits(nh);
     if ((cz && nzs * (size_t)(254 / cz + 1) >= ((size_t)1 << 31)) || (ch && nh * (size_t)(254 / ch + 1) >= ((size_t)1 << 31))) return ZKG16_ERR_BAD_ARG;
+    // the three kinds of table this call may build (z side: three G1 and one G2; h side: one G1), each laid out by zkg16_table_layout
+    struct Lay { size_t stride = 0; uint64_t bytes = 0; bool padded = false; } g1z, g2z, g1h;
+    auto lay_all = [&](int mode) {
+        auto one = [mode](int kind, size_t n, int c) {
+            Lay l;
+            if (c) (void)zkg16_table_layout(kind, n, 254 / c + 1, mode, &l.stride, &l.bytes);
+            l.padded = l.stride == (kind == 1 ? (size_t)ZKG16_TABLE_STRIDE_PADDED_G1 : (size_t)ZKG16_TABLE_STRIDE_PADDED_G2);
+            return l;
+        };
+        g1z = one(1, nzs, cz); g2z = one(2, nzs, cz); g1h = one(1, nh, ch);
+        return 3 * g1z.bytes + g2z.bytes + g1h.bytes;
+    };
+    const uint64_t packed = lay_all(1), want = lay_all(ctx->opt.table_stride);
+    if (want > packed) {
+        // Padded entries add one seventh.  Where only the packed tables fit what is free now (several ranks rehearsed on one GPU, a
+        // key next to other tenants), build those: same proofs.  Free = what the driver reports + the allocation cache's parked
+        // blocks (given back on demand); needed on top of the tables: the largest level's XYZZ points and prefix products, while the
+        // plain queries are still resident.
+        size_t free_b = 0, total_b = 0;
+        ZK_HIP(hipMemGetInfo(&free_b, &total_b));
+        const uint64_t avail = (uint64_t)free_b + dev_cached_bytes();
+        const uint64_t scratch = (uint64_t)std::max(cz ? nzs : (size_t)0, ch ? nh : (size_t)0) * (sizeof(XYZZ<Fq2U>) + sizeof(Fq2U)) + ((uint64_t)64 << 20);
+        if (want + scratch > avail) (void)lay_all(1);
+    }
     uint64_t added = 0;
     if (cz) {
-        DevBuf a = msm_tables_build_g1(ctx, pk->a, nzs, cz);
-        DevBuf l = msm_tables_build_g1(ctx, pk->l, nzs, cz);
-        DevBuf b1 = msm_tables_build_g1(ctx, pk->b1, nzs, cz);
-        DevBuf b2 = msm_tables_build_g2(ctx, pk->b2, nzs, cz);
+        DevBuf a = msm_tables_build_g1(ctx, pk->a, nzs, cz, g1z.padded);
+        DevBuf l = msm_tables_build_g1(ctx, pk->l, nzs, cz, g1z.padded);
+        DevBuf b1 = msm_tables_build_g1(ctx, pk->b1, nzs, cz, g1z.padded);
+        DevBuf b2 = msm_tables_build_g2(ctx, pk->b2, nzs, cz, g2z.padded);
         pk->a = std::move(a); pk->l = std::move(l); pk->b1 = std::move(b1); pk->b2 = std::move(b2);      // all four or none
         pk->tab_c_z = cz;
-        added += (uint64_t)(254 / cz) * nzs * (3 * sizeof(G1AffineU) + sizeof(G2AffineU));
+        pk->pad_z_g1 = g1z.padded; pk->pad_z_g2 = g2z.padded;
+        added += 3 * g1z.bytes + g2z.bytes - (uint64_t)nzs * (3 * sizeof(G1AffineU) + sizeof(G2AffineU));      // the plain queries are released
     }
     if (ch) {
-        pk->h = msm_tables_build_g1(ctx, pk->h, nh, ch);
+        pk->h = msm_tables_build_g1(ctx, pk->h, nh, ch, g1h.padded);
         pk->tab_c_h = ch;
-        added += (uint64_t)(254 / ch) * nh * sizeof(G1AffineU);
+        pk->pad_h = g1h.padded;
+        added += g1h.bytes - (uint64_t)nh * sizeof(G1AffineU);
     }
     if (table_bytes) *table_bytes = added;
     ZK_API_END(ctx)

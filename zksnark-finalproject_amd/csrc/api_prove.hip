@@ -65,10 +65,10 @@ void build_z_plans(zkg16_ctx *ctx, ScalarSrc zsrc, const PkDev &pk, MsmWorkspace
 // The four z-side accumulations on the main stream, G2 first: its long reduction then hides behind the G1 accumulations.
 void enqueue_z_accs(zkg16_ctx *ctx, PkDev &pk, const ZPlans &p, int round) {
     MsmWorkspace &wsb = p.b_sparse ? ctx->ws_zb : ctx->ws_z;
-    msm_g2_enqueue_acc(ctx, wsb, p.b(), pk.b2.as<G2AffineU>(), ctx->slots[0], round);
-    msm_g1_enqueue_acc(ctx, ctx->ws_z, p.z, pk.l.as<G1AffineU>(), ctx->slots[2], round);
-    msm_g1_enqueue_acc(ctx, ctx->ws_z, p.z, pk.a.as<G1AffineU>(), ctx->slots[3], round);
-    msm_g1_enqueue_acc(ctx, wsb, p.b(), pk.b1.as<G1AffineU>(), ctx->slots[4], round);
+    msm_g2_enqueue_acc(ctx, wsb, p.b(), pk.b2.as<G2AffineU>(), ctx->slots[0], round, pk.pad_z_g2);
+    msm_g1_enqueue_acc(ctx, ctx->ws_z, p.z, pk.l.as<G1AffineU>(), ctx->slots[2], round, pk.pad_z_g1);
+    msm_g1_enqueue_acc(ctx, ctx->ws_z, p.z, pk.a.as<G1AffineU>(), ctx->slots[3], round, pk.pad_z_g1);
+    msm_g1_enqueue_acc(ctx, wsb, p.b(), pk.b1.as<G1AffineU>(), ctx->slots[4], round, pk.pad_z_g1);
 }
 // ... and their reductions (B2, L, A, B1), whose first packet is a wait
 void enqueue_z_reduces(zkg16_ctx *ctx) {
@@ -248,7 +248,7 @@ void prove_device(zkg16_ctx *ctx, PkDev &pk, R1csDev &rc, WitnessDev &wit, const
     // 153.65 ms, the shorter tail does not pay for the earlier scatter.)
     ZK_HIP(hipStreamWaitEvent(ctx->stream, ev[4], 0));
     ctx->slots[1].last_of_proof = true;
-    if (nh) msm_g1_enqueue(ctx, ctx->ws_h, plan_h, pk.h.as<G1AffineU>(), ctx->slots[1]);
+    if (nh) msm_g1_enqueue(ctx, ctx->ws_h, plan_h, pk.h.as<G1AffineU>(), ctx->slots[1], pk.pad_h);
     if (trace) fprintf(stderr, "host: h queued at %.3f ms\n", now_ms() - t0);
     double tprev = now_ms();
     auto lap = [&](ProofTiming slot) { const double t = now_ms(); ctx->timings[slot] = (float)(t - tprev); tprev = t; };
@@ -443,7 +443,7 @@ void prove_batch_device(zkg16_ctx *ctx, PkDev &pk, R1csDev &rc, WitnessDev *cons
     enqueue_z_reduces(ctx);
     ZK_HIP(hipStreamWaitEvent(ctx->stream, ev[4], 0));
     ctx->slots[1].last_of_proof = true;
-    msm_g1_enqueue(ctx, ctx->ws_h, plan_h, pk.h.as<G1AffineU>(), ctx->slots[1]);
+    msm_g1_enqueue(ctx, ctx->ws_h, plan_h, pk.h.as<G1AffineU>(), ctx->slots[1], pk.pad_h);
 
     // ---- host: the proofs are spread over threads; the z-side combination (+ s (A + alpha), r (B1 + beta)) runs while the
     // device still works on H, then H's and the tail

@@ -45,6 +45,7 @@ struct HipError {
 void *dev_acquire(size_t bytes, size_t *got);      // api.hip; throws HipError
 void dev_release(void *p, size_t bytes) noexcept;
 void dev_cache_flush() noexcept;
+uint64_t dev_cached_bytes();                       // parked in the cache for the current device: free to the next large request
 
 // Helper threads of one host-side job.  A std::thread that goes out of scope while joinable calls std::terminate, and the
 // constructor itself can throw (EAGAIN): behind a C ABI neither may take the process down.  run() starts fn on a new thread,
@@ -138,8 +139,12 @@ struct PkDev {              // proving key shard resident in HBM (affine AoS; (0
     bool blinding = true;                            // this shard's MSMs carry the r*delta, s*delta, -rs*delta terms
     bool full = true;                                // whole key (all ranges + blinding terms): zkg16_prove / _resident
     // window tables (zkg16_pk_precompute): a / b1 / l / b2 hold [254 / tab_c_z + 1][z_hi - z_lo + 3] points, h [254 / tab_c_h + 1][n_h];
-    // level 0 is the query itself, so everything that reads the plain query keeps working.  0 = no table.
+    // level 0 is the query itself.  0 = no table.
     int tab_c_z = 0, tab_c_h = 0;
+    // entry stride of those tables (zkg16_table_layout; option "table_stride" when they were built): false = packed, 112 / 224 bytes, so
+    // level 0 reads as the plain query; true = 128 / 256 bytes in every level (PadAffine in msm.hip).  Per table kind: the three G1
+    // z-side tables, the G2 one, the h-side one.  Always false without a table.
+    bool pad_z_g1 = false, pad_z_g2 = false, pad_h = false;
 };
 
 struct R1csDev {
@@ -331,6 +336,7 @@ struct zkg16_ctx {
         int wm_concurrent = -1;
         int ntt_radix = 1;                            // 1 (default): the last seven butterfly stages by lane exchanges (ds_bpermute / DPP), 2: every stage through the LDS, 4: two stages per LDS trip
         int ntt_xcd = 1;                              // NTT tiles in XCD-aware order (ntt.hip: xcd_tile)
+        int table_stride = 0;                         // window tables built from now on: 0 = by table size (padded from ZKG16_TABLE_STRIDE_PAD_MIN_BYTES on), 1 = packed entries, 2 = padded to whole cache lines (zkg16_table_layout)
         int acc_debug = 0;                            // timing probes (wrong results): see AccArgs::debug
         int sort_mode = 0;                            // 0: hand-written bucket scatter (bucket_sort.hip), 1: rocPRIM radix sort
         int acc_pipeline = 0;                         // bit 0 / 1: G1 / G2 accumulation gathers the next base behind the last (inlined) product (default: neither)
@@ -442,8 +448,11 @@ struct ScalarSrc { const Fr *main; size_t n_main; const Fr *extra; size_t n_extr
                    const Fr *const *vecs = nullptr; size_t vec_stride = 0; int batch = 1; };
 void msm_plan_build(zkg16_ctx *ctx, MsmWorkspace &ws, const ScalarSrc &src, MsmPlan &plan, int window_bits = 0, bool tabled = false);
 // window tables of a resident key: bases[n] -> new buffer [254 / c + 1][n], level w = 2^(c w) * base (msm.hip)
-DevBuf msm_tables_build_g1(zkg16_ctx *ctx, const DevBuf &bases, size_t n, int c);
-DevBuf msm_tables_build_g2(zkg16_ctx *ctx, const DevBuf &bases, size_t n, int c);
+// padded: entries at the whole-cache-line stride 128 (G1) / 256 (G2) bytes instead of 112 / 224, level 0 included (zkg16_table_layout)
+DevBuf msm_tables_build_g1(zkg16_ctx *ctx, const DevBuf &bases, size_t n, int c, bool padded);
+DevBuf msm_tables_build_g2(zkg16_ctx *ctx, const DevBuf &bases, size_t n, int c, bool padded);
+// n points of entry_bytes each copied from one entry stride to another (bytes, multiples of 16), queued on ctx->stream
+void msm_bases_restride(zkg16_ctx *ctx, const void *src, size_t src_stride, void *dst, size_t dst_stride, size_t entry_bytes, size_t n);
 // the term list of `plan_src` without the terms whose scalar index i has mask[i] != 0 (stable compaction; msm.hip)
 void msm_plan_filter(zkg16_ctx *ctx, const MsmWorkspace &ws_src, const MsmPlan &plan_src, const uint8_t *mask, MsmWorkspace &ws_dst, MsmPlan &plan_dst);
 void msm_sort_keys(zkg16_ctx *ctx, MsmWorkspace &ws, size_t count, unsigned key_bits);   // sort.hip (rocPRIM radix sort; option sort_mode 1)
@@ -465,12 +474,13 @@ void fr_powers_run(zkg16_ctx *ctx, Fr *out, const Fr &base, const Fr &scale, siz
 // round: -1 = the whole MSM in one accumulation (default); k >= 0 = round k of an MSM whose terms arrive in several rounds
 // (same plan geometry every round): the rounds' bucket arrays are summed and ONE reduction follows (msm_*_enqueue_reduce)
 int msm_acc_resident_waves(zkg16_ctx *ctx, bool g2);
-void msm_g1_enqueue_acc(zkg16_ctx *ctx, MsmWorkspace &ws, const MsmPlan &plan, const G1AffineU *bases, MsmSlot &slot, int round = -1);
-void msm_g2_enqueue_acc(zkg16_ctx *ctx, MsmWorkspace &ws, const MsmPlan &plan, const G2AffineU *bases, MsmSlot &slot, int round = -1);
+// padded: `bases` is a window table built with padded entries (PkDev::pad_*), read at its own compile-time stride
+void msm_g1_enqueue_acc(zkg16_ctx *ctx, MsmWorkspace &ws, const MsmPlan &plan, const G1AffineU *bases, MsmSlot &slot, int round = -1, bool padded = false);
+void msm_g2_enqueue_acc(zkg16_ctx *ctx, MsmWorkspace &ws, const MsmPlan &plan, const G2AffineU *bases, MsmSlot &slot, int round = -1, bool padded = false);
 void msm_g1_enqueue_reduce(zkg16_ctx *ctx, MsmSlot &slot);
 void msm_g2_enqueue_reduce(zkg16_ctx *ctx, MsmSlot &slot);
-void msm_g1_enqueue(zkg16_ctx *ctx, MsmWorkspace &ws, const MsmPlan &plan, const G1AffineU *bases, MsmSlot &slot);
-void msm_g2_enqueue(zkg16_ctx *ctx, MsmWorkspace &ws, const MsmPlan &plan, const G2AffineU *bases, MsmSlot &slot);
+void msm_g1_enqueue(zkg16_ctx *ctx, MsmWorkspace &ws, const MsmPlan &plan, const G1AffineU *bases, MsmSlot &slot, bool padded = false);
+void msm_g2_enqueue(zkg16_ctx *ctx, MsmWorkspace &ws, const MsmPlan &plan, const G2AffineU *bases, MsmSlot &slot, bool padded = false);
 G1XYZZ msm_g1_collect(zkg16_ctx *ctx, MsmSlot &slot);
 G2XYZZ msm_g2_collect(zkg16_ctx *ctx, MsmSlot &slot);
 // a batch plan's slot: msm_slot_wait once, then vector v's value (const: threads may combine different vectors at once)

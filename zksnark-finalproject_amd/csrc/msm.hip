@@ -174,9 +174,21 @@ __global__ void msm_seg_params_kernel(const uint32_t *total_ptr, uint32_t total_
 }
 
 // ------------------------------------------------------------------------------------------------ base side
+// A window-table entry at a whole-cache-line stride (option "table_stride" = 2): Affine<F> at the front of a 128-byte (G1) /
+// 256-byte (G2) slot, so a gather touches exactly one / two 128-byte lines instead of 1.87 / 2.75 at the packed stride 112 / 224.
+// ldv of the point member reads its 7 / 14 16-byte words; the pad is never loaded.
+template <class F>
+struct alignas(FieldTraits<F>::g2 ? 256 : 128) PadAffine {
+    Affine<F> p;
+};
+static_assert(sizeof(PadAffine<FqU>) == ZKG16_TABLE_STRIDE_PADDED_G1 && sizeof(PadAffine<Fq2U>) == ZKG16_TABLE_STRIDE_PADDED_G2, "padded entry strides");
+static_assert(sizeof(Affine<FqU>) == ZKG16_TABLE_STRIDE_PACKED_G1 && sizeof(Affine<Fq2U>) == ZKG16_TABLE_STRIDE_PACKED_G2, "packed entry strides");
+template <class F> __device__ __forceinline__ Affine<F> ld_base(const Affine<F> *b, uint32_t i) { return ldv(b + i); }
+template <class F> __device__ __forceinline__ Affine<F> ld_base(const PadAffine<F> *b, uint32_t i) { return ldv(&b[i].p); }
+
 template <class F>
 struct AccArgs {
-    const Affine<F> *bases;
+    const void *bases;           // Affine<F>[] (plain keys, packed tables) or PadAffine<F>[] (padded tables): the kernel's BASE type, one stride per launch
     const uint2 *entries;        // .x = base index << 1 | negate, .y = global bucket id (window * 2^(c-1) + bucket)
     const uint32_t *offsets;
     XYZZ<F> *buckets, *seg_head, *seg_tail;
@@ -192,8 +204,10 @@ struct AccArgs {
 // CALLS (G1 only, PIPE = false): the round-1 loop whose field products are device-function calls (option "g1_inline" = 2)
 // LC (the default; option "acc_lazy"; G1's inlined loop and G2's LAZY loop only): the mixed addition without the carry passes its
 // results do not need (ec.cuh: xyzz_madd_inline_lc / xyzz_madd_lazy_lc)
-template <class F, bool PIPE, bool LAZY = false, bool CALLS = false, bool LC = false>
+// BASE: the entry type of a.bases (Affine<F> or PadAffine<F>): the entry stride is a compile-time shift or multiply of the gather's address
+template <class F, class BASE, bool PIPE, bool LAZY = false, bool CALLS = false, bool LC = false>
 __global__ void __launch_bounds__(64, FieldTraits<F>::g2 ? 1 : 2) msm_accumulate_kernel(AccArgs<F> a) {
+    const BASE *const bases = static_cast<const BASE *>(a.bases);
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t total = *a.total_ptr;
     const uint32_t seg_len = *a.seg_len_ptr;
@@ -222,7 +236,7 @@ __global__ void __launch_bounds__(64, FieldTraits<F>::g2 ? 1 : 2) msm_accumulate
         XYZZ<F> *pend_dst = nullptr;
         uint32_t pend_slot = 0;
         uint2 en1 = start + 1 < end ? a.entries[start + 1] : en;
-        Affine<F> bq = ldv(a.bases + (en.x >> 1));
+        Affine<F> bq = ld_base<F>(bases, en.x >> 1);
         for (uint32_t p = start; p < end; p++) {
             const uint32_t e = en.x, gb = (a.debug & 8u) ? cur : en.y;      // bit 3: never leave the first bucket (no flush code runs)
             if (gb != cur) {
@@ -264,7 +278,7 @@ __global__ void __launch_bounds__(64, FieldTraits<F>::g2 ? 1 : 2) msm_accumulate
             // result with the old value, and those wait for it at once.  The last iteration re-reads its own entry / base.
             en = en1;
             en1 = a.entries[p + 2 < end ? p + 2 : end - 1];
-            bq = ldv(a.bases + ((a.debug & 2u) ? 0u : (a.debug & 4u) ? ((en.x >> 1) & 0xffffu) : (en.x >> 1)));      // bit 2: gathers confined to 64 K bases (cache-resident)
+            bq = ld_base<F>(bases, (a.debug & 2u) ? 0u : (a.debug & 4u) ? ((en.x >> 1) & 0xffffu) : (en.x >> 1));      // bit 2: gathers confined to 64 K bases (cache-resident)
             if constexpr (DEFER) {
                 if (pend_dst != nullptr) {
                     XYZZ<F> v;
@@ -287,7 +301,7 @@ __global__ void __launch_bounds__(64, FieldTraits<F>::g2 ? 1 : 2) msm_accumulate
         // base of term p+1 is gathered, and entry p+2 loaded, in front of the addition of term p; a finished bucket is stored
         // where it ends.  Both are waited for only at the next iteration, one whole addition later.
         uint2 en1 = a.entries[start + 1 < end ? start + 1 : start];      // (a select between a load and `en` would put `en` on the stack)
-        Affine<F> bq = ldv(a.bases + (en.x >> 1));
+        Affine<F> bq = ld_base<F>(bases, en.x >> 1);
         // wait for the first base and entry here: the registers loaded in front of the loop are the ones copied at its end, and
         // with a load pending on entry every iteration would wait, right after its gather, for the stores of a finished bucket
 #pragma unroll
@@ -311,7 +325,7 @@ __global__ void __launch_bounds__(64, FieldTraits<F>::g2 ? 1 : 2) msm_accumulate
             // unconditional (index clamped to the segment), as in the pipelined form; the last iteration re-reads its own entry / base
             en = en1;
             en1 = a.entries[p + 2 < end ? p + 2 : end - 1];
-            bq = ldv(a.bases + ((a.debug & 2u) ? 0u : (a.debug & 4u) ? ((en.x >> 1) & 0xffffu) : (en.x >> 1)));
+            bq = ld_base<F>(bases, (a.debug & 2u) ? 0u : (a.debug & 4u) ? ((en.x >> 1) & 0xffffu) : (en.x >> 1));
             __builtin_amdgcn_sched_barrier(0);       // the loads above stay above the addition
             if constexpr (LC) xyzz_madd_inline_lc(acc, b, (e & 1u) != 0);
             else xyzz_madd_inline(acc, b, (e & 1u) != 0);
@@ -332,7 +346,7 @@ __global__ void __launch_bounds__(64, FieldTraits<F>::g2 ? 1 : 2) msm_accumulate
                 acc = XYZZ<F>::inf();
                 cur = gb;
             }
-            const Affine<F> b = ldv(a.bases + (e >> 1));
+            const Affine<F> b = ld_base<F>(bases, e >> 1);
             if constexpr (LAZY && LC && FieldTraits<F>::g2) xyzz_madd_lazy_lc(acc, b, (e & 1u) != 0);
             else if constexpr (LAZY && FieldTraits<F>::g2) xyzz_madd_lazy(acc, b, (e & 1u) != 0);
             else xyzz_madd(acc, b, (e & 1u) != 0);
@@ -698,6 +712,7 @@ struct AffineSegs {
     size_t start[8];
     Affine<FU> *out_u[8];
     Affine<typename FieldTraits<FU>::Sat> *out_sat[8];
+    size_t u_stride;      // bytes between consecutive out_u points; 0 = sizeof(Affine<FU>) (a padded window-table level: sizeof(PadAffine<FU>))
 };
 
 // XYZZ -> affine for n points; thread t owns points t, t + T, t + 2T, ... (T = threads launched) so that a wave touches
@@ -731,7 +746,7 @@ batch_affine_kernel(const XYZZ<FU> *pts, size_t n, FU *pref, AffineSegs<FU> segs
         int sg = 0;
         while (sg + 1 < segs.n && i >= segs.start[sg + 1]) sg++;
         const size_t j = i - segs.start[sg];
-        if (segs.out_u[sg]) stv(segs.out_u[sg] + j, o);
+        if (segs.out_u[sg]) stv(reinterpret_cast<Affine<FU> *>(reinterpret_cast<unsigned char *>(segs.out_u[sg]) + j * (segs.u_stride ? segs.u_stride : sizeof(Affine<FU>))), o);
         if (segs.out_sat[sg]) {
             Affine<FS> os = Affine<FS>::inf();
             if (!p.is_inf()) os = Affine<FS>{to_sat(o.x), to_sat(o.y)};
@@ -1032,8 +1047,27 @@ __global__ void __launch_bounds__(64, FieldTraits<F>::g2 ? 1 : 2) msm_bucket_mer
     stv(sum + i, a);
 }
 
+// the accumulation variant the options select, for entries of type BASE
+template <class F, class BASE>
+static void msm_launch_accumulate(zkg16_ctx *ctx, unsigned grid, const AccArgs<F> &a) {
+    const bool pipe = (ctx->opt.acc_pipeline >> (FieldTraits<F>::g2 ? 1 : 0)) & 1;
+    const bool lc = ctx->opt.acc_lazy != 0;      // only the default loops have the form without the spare carry passes
+    if (pipe) {
+        hipLaunchKernelGGL((msm_accumulate_kernel<F, BASE, true>), dim3(grid), dim3(64), 0, ctx->stream, a);
+    } else if constexpr (FieldTraits<F>::g2) {
+        if (ctx->opt.g2_lazy && lc) hipLaunchKernelGGL((msm_accumulate_kernel<F, BASE, false, true, false, true>), dim3(grid), dim3(64), 0, ctx->stream, a);
+        else if (ctx->opt.g2_lazy) hipLaunchKernelGGL((msm_accumulate_kernel<F, BASE, false, true>), dim3(grid), dim3(64), 0, ctx->stream, a);
+        else hipLaunchKernelGGL((msm_accumulate_kernel<F, BASE, false>), dim3(grid), dim3(64), 0, ctx->stream, a);
+    } else {
+        if (!ctx->opt.g1_inline) hipLaunchKernelGGL((msm_accumulate_kernel<F, BASE, false, false, true>), dim3(grid), dim3(64), 0, ctx->stream, a);
+        else if (lc) hipLaunchKernelGGL((msm_accumulate_kernel<F, BASE, false, false, false, true>), dim3(grid), dim3(64), 0, ctx->stream, a);
+        else hipLaunchKernelGGL((msm_accumulate_kernel<F, BASE, false>), dim3(grid), dim3(64), 0, ctx->stream, a);
+    }
+}
+
+// padded: `bases` is a window table of PadAffine<F> entries (PkDev::pad_*), not Affine<F>
 template <class F>
-static void msm_enqueue_acc(zkg16_ctx *ctx, MsmWorkspace &ws, const MsmPlan &plan, const Affine<F> *bases, MsmSlot &slot, int round = -1) {
+static void msm_enqueue_acc(zkg16_ctx *ctx, MsmWorkspace &ws, const MsmPlan &plan, const Affine<F> *bases, MsmSlot &slot, int round = -1, bool padded = false) {
     if (round <= 0) {
         slot.active = false;
         slot.pending_reduce = false;
@@ -1081,19 +1115,8 @@ static void msm_enqueue_acc(zkg16_ctx *ctx, MsmWorkspace &ws, const MsmPlan &pla
     const unsigned grid = (unsigned)((nseg + 63) / 64);
     {
         ScopedKernelTimer kt(ctx, FieldTraits<F>::g2 ? "msm_accumulate_g2" : "msm_accumulate_g1", (double)plan.n, ctx->stream);
-        const bool pipe = (ctx->opt.acc_pipeline >> (FieldTraits<F>::g2 ? 1 : 0)) & 1;
-        const bool lc = ctx->opt.acc_lazy != 0;      // only the default loops have the form without the spare carry passes
-        if (pipe) {
-            hipLaunchKernelGGL((msm_accumulate_kernel<F, true>), dim3(grid), dim3(64), 0, ctx->stream, a);
-        } else if constexpr (FieldTraits<F>::g2) {
-            if (ctx->opt.g2_lazy && lc) hipLaunchKernelGGL((msm_accumulate_kernel<F, false, true, false, true>), dim3(grid), dim3(64), 0, ctx->stream, a);
-            else if (ctx->opt.g2_lazy) hipLaunchKernelGGL((msm_accumulate_kernel<F, false, true>), dim3(grid), dim3(64), 0, ctx->stream, a);
-            else hipLaunchKernelGGL((msm_accumulate_kernel<F, false>), dim3(grid), dim3(64), 0, ctx->stream, a);
-        } else {
-            if (!ctx->opt.g1_inline) hipLaunchKernelGGL((msm_accumulate_kernel<F, false, false, true>), dim3(grid), dim3(64), 0, ctx->stream, a);
-            else if (lc) hipLaunchKernelGGL((msm_accumulate_kernel<F, false, false, false, true>), dim3(grid), dim3(64), 0, ctx->stream, a);
-            else hipLaunchKernelGGL((msm_accumulate_kernel<F, false>), dim3(grid), dim3(64), 0, ctx->stream, a);
-        }
+        if (padded) msm_launch_accumulate<F, PadAffine<F>>(ctx, grid, a);
+        else msm_launch_accumulate<F, Affine<F>>(ctx, grid, a);
     }
     static_assert(sizeof(AccArgs<F>) <= sizeof(slot.acc_args), "MsmSlot::acc_args too small");
     memcpy(slot.acc_args, &a, sizeof a);
@@ -1251,8 +1274,8 @@ static void msm_enqueue_reduce(zkg16_ctx *ctx, MsmSlot &slot) {
     slot.active = true;
 }
 template <class F>
-static void msm_enqueue(zkg16_ctx *ctx, MsmWorkspace &ws, const MsmPlan &plan, const Affine<F> *bases, MsmSlot &slot) {
-    msm_enqueue_acc<F>(ctx, ws, plan, bases, slot);
+static void msm_enqueue(zkg16_ctx *ctx, MsmWorkspace &ws, const MsmPlan &plan, const Affine<F> *bases, MsmSlot &slot, bool padded = false) {
+    msm_enqueue_acc<F>(ctx, ws, plan, bases, slot, -1, padded);
     msm_enqueue_reduce<F>(ctx, slot);
 }
 
@@ -1314,26 +1337,26 @@ int msm_acc_resident_waves(zkg16_ctx *ctx, bool g2) {
     const bool pipe = (ctx->opt.acc_pipeline >> (g2 ? 1 : 0)) & 1;
     hipError_t e;
     if (g2) {
-        if (pipe) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, msm_accumulate_kernel<Fq2U, true>, 64, 0);
-        else if (ctx->opt.g2_lazy && ctx->opt.acc_lazy) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, msm_accumulate_kernel<Fq2U, false, true, false, true>, 64, 0);
-        else if (ctx->opt.g2_lazy) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, msm_accumulate_kernel<Fq2U, false, true>, 64, 0);
-        else e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, msm_accumulate_kernel<Fq2U, false>, 64, 0);
+        if (pipe) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, msm_accumulate_kernel<Fq2U, Affine<Fq2U>, true>, 64, 0);
+        else if (ctx->opt.g2_lazy && ctx->opt.acc_lazy) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, msm_accumulate_kernel<Fq2U, Affine<Fq2U>, false, true, false, true>, 64, 0);
+        else if (ctx->opt.g2_lazy) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, msm_accumulate_kernel<Fq2U, Affine<Fq2U>, false, true>, 64, 0);
+        else e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, msm_accumulate_kernel<Fq2U, Affine<Fq2U>, false>, 64, 0);
     } else {
-        if (pipe) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, msm_accumulate_kernel<FqU, true>, 64, 0);
-        else if (!ctx->opt.g1_inline) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, msm_accumulate_kernel<FqU, false, false, true>, 64, 0);
-        else if (ctx->opt.acc_lazy) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, msm_accumulate_kernel<FqU, false, false, false, true>, 64, 0);
-        else e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, msm_accumulate_kernel<FqU, false>, 64, 0);
+        if (pipe) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, msm_accumulate_kernel<FqU, Affine<FqU>, true>, 64, 0);
+        else if (!ctx->opt.g1_inline) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, msm_accumulate_kernel<FqU, Affine<FqU>, false, false, true>, 64, 0);
+        else if (ctx->opt.acc_lazy) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, msm_accumulate_kernel<FqU, Affine<FqU>, false, false, false, true>, 64, 0);
+        else e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, msm_accumulate_kernel<FqU, Affine<FqU>, false>, 64, 0);
     }
     ZK_HIP(e);
     return blocks / 4;      // one-wave blocks per CU -> waves per SIMD
 }
 
-void msm_g1_enqueue_acc(zkg16_ctx *ctx, MsmWorkspace &ws, const MsmPlan &plan, const G1AffineU *bases, MsmSlot &slot, int round) { msm_enqueue_acc<FqU>(ctx, ws, plan, bases, slot, round); }
-void msm_g2_enqueue_acc(zkg16_ctx *ctx, MsmWorkspace &ws, const MsmPlan &plan, const G2AffineU *bases, MsmSlot &slot, int round) { msm_enqueue_acc<Fq2U>(ctx, ws, plan, bases, slot, round); }
+void msm_g1_enqueue_acc(zkg16_ctx *ctx, MsmWorkspace &ws, const MsmPlan &plan, const G1AffineU *bases, MsmSlot &slot, int round, bool padded) { msm_enqueue_acc<FqU>(ctx, ws, plan, bases, slot, round, padded); }
+void msm_g2_enqueue_acc(zkg16_ctx *ctx, MsmWorkspace &ws, const MsmPlan &plan, const G2AffineU *bases, MsmSlot &slot, int round, bool padded) { msm_enqueue_acc<Fq2U>(ctx, ws, plan, bases, slot, round, padded); }
 void msm_g1_enqueue_reduce(zkg16_ctx *ctx, MsmSlot &slot) { msm_enqueue_reduce<FqU>(ctx, slot); }
 void msm_g2_enqueue_reduce(zkg16_ctx *ctx, MsmSlot &slot) { msm_enqueue_reduce<Fq2U>(ctx, slot); }
-void msm_g1_enqueue(zkg16_ctx *ctx, MsmWorkspace &ws, const MsmPlan &plan, const G1AffineU *bases, MsmSlot &slot) { msm_enqueue<FqU>(ctx, ws, plan, bases, slot); }
-void msm_g2_enqueue(zkg16_ctx *ctx, MsmWorkspace &ws, const MsmPlan &plan, const G2AffineU *bases, MsmSlot &slot) { msm_enqueue<Fq2U>(ctx, ws, plan, bases, slot); }
+void msm_g1_enqueue(zkg16_ctx *ctx, MsmWorkspace &ws, const MsmPlan &plan, const G1AffineU *bases, MsmSlot &slot, bool padded) { msm_enqueue<FqU>(ctx, ws, plan, bases, slot, padded); }
+void msm_g2_enqueue(zkg16_ctx *ctx, MsmWorkspace &ws, const MsmPlan &plan, const G2AffineU *bases, MsmSlot &slot, bool padded) { msm_enqueue<Fq2U>(ctx, ws, plan, bases, slot, padded); }
 G1XYZZ msm_g1_collect(zkg16_ctx *ctx, MsmSlot &slot) { return msm_collect<Fq>(ctx, slot); }
 G2XYZZ msm_g2_collect(zkg16_ctx *ctx, MsmSlot &slot) { return msm_collect<Fq2>(ctx, slot); }
 G1XYZZ msm_g1_collect_part(const MsmSlot &slot, int v) { return msm_collect_part<Fq>(slot, v); }
@@ -1377,11 +1400,14 @@ static void batch_affine_run(zkg16_ctx *ctx, const XYZZ<FU> *pts, size_t n, DevB
 // table[w][i] of ONE set of 2^(c-1) buckets — so c can grow (22 bits, 12 digits per scalar instead of 15 at 17 bits) at an
 // unchanged bucket count, and the five reductions of a proof shrink to one window each.  Cost: nwin x the key in HBM
 // (128x128 circuit: 69 GB of the 288 GB) and c * (nwin - 1) doublings per base once, at key-load time (zkg16_pk_precompute).
+// Entry layout (zkg16_table_layout): packed = Affine<FU> at stride 112 / 224 bytes, padded = PadAffine<FU> at 128 / 256, every level
+// (level 0, a copy of the query, included) at the one stride, so the accumulation gathers with one base pointer and one shift.  The
+// allocation is 256-byte aligned and a level is n whole entries, so every padded level starts on a line boundary.
 template <class FU>
-__global__ void __launch_bounds__(64, FieldTraits<FU>::g2 ? 1 : 2) table_level_kernel(const Affine<FU> *prev, XYZZ<FU> *out, size_t n, int c) {
+__global__ void __launch_bounds__(64, FieldTraits<FU>::g2 ? 1 : 2) table_level_kernel(const unsigned char *prev, size_t stride, XYZZ<FU> *out, size_t n, int c) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const Affine<FU> p = ldv(prev + i);
+    const Affine<FU> p = ldv(reinterpret_cast<const Affine<FU> *>(prev + i * stride));
     XYZZ<FU> acc = XYZZ<FU>::inf();
     if (!p.is_inf()) {
         acc = xyzz_dbl_affine(p);
@@ -1389,27 +1415,51 @@ __global__ void __launch_bounds__(64, FieldTraits<FU>::g2 ? 1 : 2) table_level_k
     }
     stv(out + i, acc);
 }
+// n entries of `words` 16-byte words each from one stride to another (strides in 16-byte words): a query into level 0 of a padded
+// table, level 0 of a padded table back into a plain query (zkg16_pk_slice)
+__global__ void __launch_bounds__(256) restride_kernel(const uint4 *src, size_t src_stride, uint4 *dst, size_t dst_stride, unsigned words, size_t n) {
+    const size_t id = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t i = id / words, k = id % words;
+    if (i >= n) return;
+    dst[i * dst_stride + k] = src[i * src_stride + k];
+}
+void msm_bases_restride(zkg16_ctx *ctx, const void *src, size_t src_stride, void *dst, size_t dst_stride, size_t entry_bytes, size_t n) {
+    if (n == 0) return;
+    const unsigned words = (unsigned)(entry_bytes / 16);
+    const size_t total = n * words;
+    hipLaunchKernelGGL(restride_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, static_cast<const uint4 *>(src), src_stride / 16,
+                       static_cast<uint4 *>(dst), dst_stride / 16, words, n);
+    ZK_HIP(hipGetLastError());
+}
 template <class FU>
-static DevBuf tables_build(zkg16_ctx *ctx, const DevBuf &bases, size_t n, int c) {
+static DevBuf tables_build(zkg16_ctx *ctx, const DevBuf &bases, size_t n, int c, bool padded) {
     const int nwin = 254 / c + 1;
-    const size_t lvl = n * sizeof(Affine<FU>);
+    const size_t stride = padded ? sizeof(PadAffine<FU>) : sizeof(Affine<FU>);
+    const size_t lvl = n * stride;
     DevBuf tab((size_t)nwin * lvl), xyzz(n * sizeof(XYZZ<FU>)), pref;
-    ZK_HIP(hipMemcpyAsync(tab.p, bases.p, lvl, hipMemcpyDeviceToDevice, ctx->stream));
-    Affine<FU> *t = tab.as<Affine<FU>>();
+    unsigned char *t = tab.as<unsigned char>();
+    if (padded) {
+        if (reinterpret_cast<uintptr_t>(tab.p) % 256) throw HipError{hipErrorInvalidValue, "window table not 256-byte aligned", __FILE__, __LINE__};
+        ZK_HIP(hipMemsetAsync(tab.p, 0, (size_t)nwin * lvl, ctx->stream));      // the pad bytes: never read by a proof, but defined
+        msm_bases_restride(ctx, bases.p, sizeof(Affine<FU>), t, stride, sizeof(Affine<FU>), n);
+    } else {
+        ZK_HIP(hipMemcpyAsync(tab.p, bases.p, lvl, hipMemcpyDeviceToDevice, ctx->stream));
+    }
     for (int w = 1; w < nwin; w++) {
-        hipLaunchKernelGGL(table_level_kernel<FU>, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, t + (size_t)(w - 1) * n,
+        hipLaunchKernelGGL(table_level_kernel<FU>, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, t + (size_t)(w - 1) * lvl, stride,
                            xyzz.as<XYZZ<FU>>(), n, c);
         ZK_HIP(hipGetLastError());
         AffineSegs<FU> seg{};
         seg.n = 1;
-        seg.out_u[0] = t + (size_t)w * n;
+        seg.out_u[0] = reinterpret_cast<Affine<FU> *>(t + (size_t)w * lvl);
+        seg.u_stride = stride;
         batch_affine_run<FU>(ctx, xyzz.as<XYZZ<FU>>(), n, pref, seg);
     }
     ZK_HIP(hipStreamSynchronize(ctx->stream));
     return tab;
 }
-DevBuf msm_tables_build_g1(zkg16_ctx *ctx, const DevBuf &bases, size_t n, int c) { return tables_build<FqU>(ctx, bases, n, c); }
-DevBuf msm_tables_build_g2(zkg16_ctx *ctx, const DevBuf &bases, size_t n, int c) { return tables_build<Fq2U>(ctx, bases, n, c); }
+DevBuf msm_tables_build_g1(zkg16_ctx *ctx, const DevBuf &bases, size_t n, int c, bool padded) { return tables_build<FqU>(ctx, bases, n, c, padded); }
+DevBuf msm_tables_build_g2(zkg16_ctx *ctx, const DevBuf &bases, size_t n, int c, bool padded) { return tables_build<Fq2U>(ctx, bases, n, c, padded); }
 
 // [s_i] base for the n concatenated scalars; results split over `segs`
 template <class FU>

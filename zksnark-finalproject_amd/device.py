@@ -88,7 +88,8 @@ class Device:
 
     def pk_precompute(self, pk_h, window_bits_z=0, window_bits_h=0):
         """Window tables for a key that stays resident (zkg16_pk_precompute): same proofs, fewer bucket additions.
-        0 = width chosen from the query length, < 0 = leave that side without a table.  -> HBM bytes added."""
+        0 = width chosen from the query length, < 0 = leave that side without a table.  The entries are laid out as option
+        "table_stride" says at this call (table_layout).  -> HBM bytes added."""
         added = C.c_uint64(0)
         self._check(self.lib.zkg16_pk_precompute(self.ctx, pk_h, int(window_bits_z), int(window_bits_h), C.byref(added)))
         return added.value
@@ -659,6 +660,14 @@ def z_costs(r1cs, z_mont, num_instance):
     in_b[np.asarray(r1cs["b"][1], dtype=np.int64)] = True
     mult = in_a.astype(np.float32) + (np.arange(m) >= num_instance) + in_b * 3.8
     return (entries * mult).astype(np.float32)
+
+
+def table_layout(kind, n, digits, stride_mode=0):
+    """Entry layout of a window table (host-only zkg16_table_layout): kind "g1" / "g2", n bases, digits levels; stride_mode as option
+    "table_stride" (0 = the library's choice by table size, 1 = packed 112 / 224 bytes, 2 = padded 128 / 256) -> (entry stride, bytes of the table)."""
+    stride, size = C.c_size_t(0), C.c_uint64(0)
+    _check_host(_lib.load().zkg16_table_layout({"g1": 1, "g2": 2}.get(kind, 0), n, digits, stride_mode, C.byref(stride), C.byref(size)))
+    return stride.value, size.value
 
 
 def shard_plan(n_ranks, m_total, n_h, b_density=0.0, h_ranks=0, z_cost=None, window_tables=False):
