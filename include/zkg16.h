@@ -609,6 +609,16 @@ ZKG16_API int zkg16_last_acc_waves(zkg16_ctx *ctx, int waves[3]);
 /* Waves of the bucket-accumulation kernels one SIMD holds at once (their register use decides): [0] G1, [1] G2.  The grid of an
  * accumulation may be sized for more waves per SIMD than that (zkg16_last_acc_waves): the extra ones run as a second round. */
 ZKG16_API int zkg16_acc_resident_waves(zkg16_ctx *ctx, int waves[2]);
+/* What the last zkg16_msm_g1 / zkg16_msm_g2 / zkg16_bench_msm call on this ctx ran as (diagnostics for tests):
+ * out = { c, nwin, entries, seg_len, fixup_items, fixup_chains, bit_sliced, two_level_k }.  c: window bits; nwin: windows;
+ * entries: length of the sorted (scalar, window) term list; seg_len: entries per lane the accumulation kernel read; fixup_items /
+ * fixup_chains: work items queued for spilled buckets longer than four segments (one per 1024 segments), and how many of those
+ * buckets needed more than one item; bit_sliced: weight bits of the bit-sliced bucket reduction, 0 = another form ran;
+ * two_level_k: chunk size of the bit-sliced or the work-efficient reduction, 0 = the classic form ran.  Copies four words from the
+ * device when called; the MSM and prove paths record nothing for it.  All zero before the first such call and again after a proof
+ * that ran on the ctx's first lane (it takes over the workspace and slot the words live in); entries and what follows are zero
+ * after a call with n = 0.  A null out: ZKG16_ERR_BAD_ARG. */
+ZKG16_API int zkg16_last_msm_state(zkg16_ctx *ctx, uint32_t out[8]);
 /* Which sparse product an r1cs handle's witness maps run (diagnostics; takes the handle's own lock, launches nothing):
  * out = { dict_state, ndict, perm_ok, spmv_uses }.  dict_state: 0 = the coefficient dictionary has not been tried yet (the handle
  * has run fewer than two witness maps: plain kernel, rows in natural order), 1 = the dictionary is in use (ndict distinct

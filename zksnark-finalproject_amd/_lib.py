@@ -39,6 +39,7 @@ SIGNATURES = {
     "zkg16_table_layout": (C.c_int, [C.c_int, sz, C.c_int, C.c_int, C.POINTER(sz), C.POINTER(C.c_uint64)]),
     "zkg16_pk_table_bits": (C.c_int, [ctxp, H, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "zkg16_r1cs_spmv_state": (C.c_int, [ctxp, H, C.POINTER(C.c_uint32)]),
+    "zkg16_last_msm_state": (C.c_int, [ctxp, C.POINTER(C.c_uint32)]),
     "zkg16_group_create": (C.c_int, [vp, C.c_int, C.POINTER(vp)]),
     "zkg16_group_destroy": (None, [vp]),
     "zkg16_group_last_error": (C.c_char_p, [vp]),

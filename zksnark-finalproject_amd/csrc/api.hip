@@ -490,6 +490,33 @@ int zkg16_last_acc_waves(zkg16_ctx *ctx, int waves[3]) {
     return ZKG16_OK;
 }
 
+// What the last zkg16_msm_g1 / zkg16_msm_g2 / zkg16_bench_msm on this ctx ran as (it used ws_h and slots[0] of the root; a later proof
+// on lane 0 takes them over and clears last_msm_group): out = { c, nwin, entries, seg_len, fixup_items, fixup_chains, bit_sliced, two_level_k }.  The four device words are
+// copied here, after the call has returned; the MSM itself records nothing for this.  All zero before the first such call and after such a proof.
+int zkg16_last_msm_state(zkg16_ctx *ctx, uint32_t out[8]) {
+    if (!ctx || !out) return ZKG16_ERR_BAD_ARG;
+    ZK_API_BEGIN(ctx)
+    uint32_t v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    const MsmSlot &s = ctx->slots[0];
+    const MsmWorkspace &w = ctx->ws_h;
+    if (ctx->last_msm_group) {
+        v[0] = (uint32_t)s.c;
+        v[1] = (uint32_t)s.nwin;
+        if (w.last_tb && w.offsets.p && w.seg_params.p && s.long_list.p) {
+            uint32_t q[2] = {0, 0};
+            ZK_HIP(hipMemcpy(&v[2], w.offsets.as<uint32_t>() + w.last_tb, sizeof(uint32_t), hipMemcpyDeviceToHost));
+            ZK_HIP(hipMemcpy(&v[3], w.seg_params.as<uint32_t>() + (ctx->last_msm_group == 2 ? 1 : 0), sizeof(uint32_t), hipMemcpyDeviceToHost));
+            ZK_HIP(hipMemcpy(q, s.long_list.p, sizeof q, hipMemcpyDeviceToHost));
+            v[4] = q[0];
+            v[5] = q[1];
+            v[6] = (uint32_t)s.bit_sliced;
+            v[7] = (uint32_t)s.two_level_k;
+        }
+    }
+    for (int i = 0; i < 8; i++) out[i] = v[i];
+    ZK_API_END(ctx)
+}
+
 // waves of the accumulation kernels (as launched with the ctx's current options) that fit one SIMD at once: [0] G1, [1] G2
 int zkg16_acc_resident_waves(zkg16_ctx *ctx, int waves[2]) {
     if (!waves) return ZKG16_ERR_BAD_ARG;

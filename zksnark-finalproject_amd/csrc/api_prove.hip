@@ -179,6 +179,7 @@ void prove_device(zkg16_ctx *ctx, PkDev &pk, R1csDev &rc, WitnessDev &wit, const
     out.b2 = G2XYZZ::inf();
     ZK_HIP(hipEventRecord(ev[0], ctx->stream));
     ctx->ws_z.last_tb = ctx->ws_zb.last_tb = ctx->ws_h.last_tb = 0;
+    ctx->last_msm_group = 0;              // ws_h and slots[0] are the proof's from here on: zkg16_last_msm_state reports zeros
     const bool trace = getenv("ZKG16_TRACE_HOST") != nullptr;
     const int parts = zp ? zp->parts : 1;
     const bool rounds = parts > 1 && z_side && zp->part_of != nullptr;
@@ -419,6 +420,7 @@ void prove_batch_device(zkg16_ctx *ctx, PkDev &pk, R1csDev &rc, WitnessDev *cons
     MsmPlan plan_h;
     ZK_HIP(hipEventRecord(ev[0], ctx->stream));
     ctx->ws_z.last_tb = ctx->ws_zb.last_tb = ctx->ws_h.last_tb = 0;
+    ctx->last_msm_group = 0;              // ws_h and slots[0] are the proof's from here on: zkg16_last_msm_state reports zeros
     {
         ScalarSrc zsrc{nullptr, pk.z_hi - pk.z_lo, extra, 3, true, nullptr};
         zsrc.vecs = vecs;

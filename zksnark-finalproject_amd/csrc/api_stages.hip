@@ -137,8 +137,8 @@ int msm_host_entry(zkg16_ctx *ctx, const uint64_t *bases, const uint8_t *inf, co
         ms_sum += now_ms() - t0;
     }
     if (ms_per_iter) *ms_per_iter = (float)(ms_sum / (iters < 1 ? 1 : iters));
+    ctx->last_msm_group = g2 ? 2 : 1;
     point_to_abi(xyzz_to_affine(total), out_affine, out_inf);
-    (void)g2;
     ZK_API_END(ctx)
 }
 

@@ -303,6 +303,7 @@ struct zkg16_ctx {
     zk::MsmWorkspace ws_z, ws_h, ws_zb;               // one workspace per scalar vector (z, h, and z masked by the B-query density)
     hipStream_t wm_stream = nullptr;                  // witness map + h-side sort of a proof, concurrent with the z-side MSMs
     zk::MsmSlot slots[5];                             // B2, H, L, A, B1 of one proof
+    int last_msm_group = 0;                           // the last zkg16_msm_g1 / _g2 / zkg16_bench_msm on this ctx: 1 = G1, 2 = G2 (ws_h and slots[0]: zkg16_last_msm_state)
     void *extra_host = nullptr;                       // pinned staging for the r, s, -rs scalars
     void *stage_host[2] = {nullptr, nullptr};         // pinned staging ring of upload_h2d (api_keys.hip)
     hipEvent_t stage_done[2] = {nullptr, nullptr};

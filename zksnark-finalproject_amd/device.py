@@ -112,6 +112,13 @@ class Device:
         self._check(self.lib.zkg16_last_acc_waves(self.ctx, out))
         return int(out[0]), int(out[1]), int(out[2])
 
+    def last_msm_state(self):
+        """-> (c, nwin, entries, seg_len, fixup_items, fixup_chains, bit_sliced, two_level_k) of the last msm() on this device
+        (zkg16_last_msm_state): the path that MSM took, for tests that pin a boundary."""
+        out = (C.c_uint32 * 8)()
+        self._check(self.lib.zkg16_last_msm_state(self.ctx, out))
+        return tuple(int(x) for x in out)
+
     def circuit_load(self, circuit):
         """circuit: a circuits.CircuitHandle (a synthesized circuit still held by the library) -> (r1cs_handle, witness_handle), loaded
         without exporting its arrays to Python (zkg16_circuit_load)."""
