@@ -45,7 +45,8 @@ typedef enum {
     ZKG16_ERR_OOM = 4,
     ZKG16_ERR_NO_DEVICE = 5,        /* no gfx950 device visible: the product has NO CPU fallback */
     ZKG16_ERR_BAD_HANDLE = 6,
-    ZKG16_ERR_UNSUPPORTED = 7
+    ZKG16_ERR_UNSUPPORTED = 7,
+    ZKG16_ERR_UNSATISFIED = 8       /* option "check_satisfied": an assignment of the call does not satisfy its R1CS; nothing was written */
 } zkg16_status;
 
 typedef struct zkg16_ctx zkg16_ctx;
@@ -549,6 +550,47 @@ ZKG16_API int zkg16_prove_prime_batch(zkg16_ctx *ctx, uint64_t pk_handle, uint64
                                       const uint64_t *r, const uint64_t *s, uint64_t *proofs_out /* k x 48 */, uint8_t *inf_out /* k x 3 */,
                                       uint64_t *gamma_abc0_out /* k x 12 */, uint64_t *public_inputs /* nullable, k x 257 x 4 */,
                                       float *timings_ms /* nullable, 4 */);
+/* ---- does an assignment satisfy its R1CS?  (A z)_i * (B z)_i == (C z)_i for every constraint row i < num_constraints, compared as fully
+ * reduced residues.  The proving calls prove whatever they are handed: an unsatisfied assignment gives a well-formed proof that no
+ * verifier accepts (arkworks' prover debug_asserts cs.is_satisfied(); prime_snark.rs:123-128 asserts it on every request).  The witness
+ * map begins with the three sparse products written side by side, so the check is ONE kernel over rows a proof computes anyway
+ * (csrc/r1cs_check_dev.cuh; r1cs_check_kernel in csrc/poly.hip): a lane per row forms the Montgomery product and compares, a block
+ * folds its verdicts by ballot, and a block with a failing row makes one atomic add and one atomic min on two 64-bit words per
+ * assignment, which are read back once per call.  Rows at or beyond num_constraints (the instance rows, the padding) are no rows of the
+ * system and are not looked at; the verdict does not depend on the coefficient dictionary or the row order of the sparse product.
+ * Every entry: *n_bad (required) = failing rows, *first_bad (nullable) = the smallest failing row, UINT64_MAX when none.  Null
+ * pointers, k == 0 and lengths that do not match: ZKG16_ERR_BAD_ARG; unknown handles: ZKG16_ERR_BAD_HANDLE; all checked before any
+ * work, and the outputs are then untouched.
+ * zkg16_r1cs_check_host: no ctx, no GPU — the reference of the device entries and the check for callers without a device.  Arrays as
+ * for zkg16_r1cs_load (col / coeff of a matrix without non-zeros may be null), z: num_variables x 4 limbs.  A decreasing row pointer or
+ * a column >= num_variables: ZKG16_ERR_BAD_ARG.
+ * zkg16_r1cs_check: one sparse product and the kernel, on the witness map's own vectors.  It counts as a use of the r1cs handle exactly
+ * as a witness map does (zkg16_r1cs_spmv_state's spmv_uses: the dictionary and the row order are built on the second use).
+ * zkg16_r1cs_check_batch: k assignments of one system; per sub-batch one batched sparse product and one launch.  A sub-batch is what
+ * fits the witness map's four vectors per assignment into 60 % of the free HBM — never more than zkg16_prove_batch would take — at
+ * most 65,535, capped by option "batch_max".
+ * zkg16_prime_check_batch: k prime requests on the TEMPLATE handle (zkg16_r1cs_prime_template; any other handle: ZKG16_ERR_BAD_ARG).
+ * The assignments are built as zkg16_prove_prime_batch builds them, then the batched sparse product, then each request's n and -j
+ * added at the template's four patch rows, then the kernel: request i's verdict is zkg16_r1cs_check's on zkg16_r1cs_prime /
+ * zkg16_witness_prime(xs[i], js[i]).  A refused candidate anywhere: ZKG16_ERR_UNSUPPORTED before any device work.
+ * zkg16_r1cs_check[_batch] on a template handle is ZKG16_ERR_UNSUPPORTED: the template is no request's system.
+ * Inside the proving calls: option "check_satisfied" (zkg16_set_option) launches the same kernel right after the sparse product (and
+ * the patch) of the proof's own witness map, on the same stream, before the first transform — no second sparse product.  The verdict
+ * is read where the proof's results are collected; if any assignment of the call failed, the call returns ZKG16_ERR_UNSATISFIED and
+ * writes nothing.  It applies to zkg16_prove_resident, zkg16_prove, zkg16_prove_partial (ranks with an h range), zkg16_prove_matrix,
+ * zkg16_prove_batch, zkg16_prove_matrix_batch and zkg16_prove_prime_batch.  Group calls (zkg16_prove_group, zkg16_witness_map_group)
+ * never check, whatever the option says.  Off (the default) nothing changes: no launch, no allocation, the same bytes.
+ * zkg16_last_check: the per-proof verdicts of the last proving call that checked, attributed to the ctx as zkg16_last_timings
+ * attributes its times (the lane of the proof that finished last): *k_out (nullable) = proofs of that call (0: it did not check), up
+ * to cap of them written to n_bad / first_bad (either nullable).  Returns the number written. */
+ZKG16_API int zkg16_r1cs_check_host(const uint64_t *const row_ptr[3], const uint32_t *const col[3], const uint64_t *const coeff[3],
+                          size_t num_constraints, size_t num_variables, const uint64_t *z, uint64_t *n_bad, uint64_t *first_bad);
+ZKG16_API int zkg16_r1cs_check(zkg16_ctx *ctx, uint64_t r1cs_handle, uint64_t witness_handle, uint64_t *n_bad, uint64_t *first_bad);
+ZKG16_API int zkg16_r1cs_check_batch(zkg16_ctx *ctx, uint64_t r1cs_handle, const uint64_t *witness_handles, size_t k,
+                           uint64_t *n_bad /* k */, uint64_t *first_bad /* nullable, k */);
+ZKG16_API int zkg16_prime_check_batch(zkg16_ctx *ctx, uint64_t r1cs_template_handle, const uint64_t *xs, const uint64_t *js, size_t k,
+                            uint64_t *n_bad /* k */, uint64_t *first_bad /* nullable, k */);
+ZKG16_API int zkg16_last_check(zkg16_ctx *ctx, uint64_t *n_bad, uint64_t *first_bad, size_t cap, size_t *k_out);
 /* native Poseidon sponge hash of n Fr elements (Montgomery) — the public inputs hash_a/b/c of the matrix handler */
 ZKG16_API int zkg16_poseidon_hash(const uint64_t *elems, size_t n, uint64_t out[4]);
 /* k hashes in one call.  elems: k vectors of n Fr each (Montgomery), back to back; out[4 i ..] is byte for byte
@@ -675,6 +717,9 @@ ZKG16_API void zkg16_kernel_stats_reset(zkg16_ctx *ctx);
  *                    zkg16_matrix_hash_batch from 1024 chains (1.3x; 5.2x at 4096), but in zkg16_prove_matrix_batch, whose chain count is that
  *                    of a sub-batch, only at n = 8 and by 6 %, and it lost at n = 32 by 1.4x.  The default must win on every entry at
  *                    every measured size; none does.  Callers of the first two entries with that many chains set 3072
+ *   "check_satisfied" 0 (default) = the proving calls prove whatever they are handed; 1 = they check their assignments on the device
+ *                    and return ZKG16_ERR_UNSATISFIED, writing nothing, when one fails (zkg16_r1cs_check above; zkg16_last_check); any
+ *                    other value: ZKG16_ERR_BAD_ARG.  The one option that can change what a call returns — for assignments no verifier accepts
  *   "sponge_chain_segment" permutations of a chain per launch of the chain kernel (0 = 256, else 1..65535): the state is carried between launches
  * Unknown names return ZKG16_ERR_UNSUPPORTED. */
 ZKG16_API int zkg16_set_option(zkg16_ctx *ctx, const char *name, int64_t value);

@@ -191,6 +191,26 @@ def prime_ext_inputs(x, j):
     return out
 
 
+def r1cs_check_host(r1cs, z, num_variables):
+    """Does the assignment z [num_variables, 4] (Montgomery) satisfy the system r1cs (a dict as SynthesizedCircuit.r1cs)?  Host only
+    (zkg16_r1cs_check_host): the reference of Device.r1cs_check -> (n_bad, first_bad): failing constraint rows and the smallest of
+    them, 2^64 - 1 when there is none."""
+    keep, tabs = [], []
+    for k, dt in ((0, np.uint64), (1, np.uint32), (2, np.uint64)):
+        arrs = [np.ascontiguousarray(r1cs[m][k], dtype=dt) for m in "abc"]
+        keep += arrs
+        tabs.append((C.c_void_p * 3)(*[x.ctypes.data if x.size else None for x in arrs]))
+    z = np.ascontiguousarray(z, dtype=np.uint64).reshape(-1, 4)
+    if z.shape[0] != num_variables or any(x.shape[0] != r1cs["num_constraints"] + 1 for x in keep[:3]):
+        raise ValueError("r1cs_check_host: z has num_variables rows, every row pointer num_constraints + 1 entries")
+    nb, fb = C.c_uint64(0), C.c_uint64(0)
+    rc = _lib.load().zkg16_r1cs_check_host(C.byref(tabs[0]), C.byref(tabs[1]), C.byref(tabs[2]), r1cs["num_constraints"], num_variables,
+                                           z.ctypes.data, C.byref(nb), C.byref(fb))
+    if rc:
+        raise Zkg16Error(rc, "zkg16_r1cs_check_host")
+    return int(nb.value), int(fb.value)
+
+
 def matrix_circuit(a, b):
     """MatrixCircuit for u64 matrices a, b (n x n lists/arrays); public inputs = Poseidon hashes of A, B, C = A*B."""
     a = np.ascontiguousarray(a, dtype=np.uint64)
@@ -312,8 +332,10 @@ def prime_candidate(x, j):
 def prime_circuit(x, i_max_or_j, search=True, check_satisfied=True):
     """The reference's PrimeCircuit (C++ mirror).  search=True: as prove_prime — find the first prime candidate j <= i_max and
     build its circuit (raises if none); search=False: the circuit of candidate j itself, as verify_prime rebuilds it.
-    check_satisfied: evaluate all 338 k constraints on the assignment (a test convenience — neither `Groth16::prove` nor the
-    reference's handlers do it; it costs about as much as the synthesis itself, so timed paths pass False)."""
+    check_satisfied: evaluate all 338 k constraints on the assignment on the host.  The reference's prime handler does assert
+    cs.is_satisfied() on every request (prime_snark.rs:123-128), and ark-groth16's prover debug_asserts it; the matrix and Fibonacci
+    handlers do not.  Here it costs about as much as the synthesis itself, so timed paths pass False — the device check
+    (Device.r1cs_check, handlers' check_on_device=True) answers the same question on assignments that were never synthesized."""
     j = i_max_or_j
     if search:
         res = prime_search(x, i_max_or_j)

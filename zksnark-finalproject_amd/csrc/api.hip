@@ -269,6 +269,7 @@ const char *zkg16_strerror(int status) {
         case ZKG16_ERR_NO_DEVICE: return "no HIP device (this library has no CPU fallback)";
         case ZKG16_ERR_BAD_HANDLE: return "unknown handle";
         case ZKG16_ERR_UNSUPPORTED: return "unsupported";
+        case ZKG16_ERR_UNSATISFIED: return "an assignment does not satisfy its R1CS (option check_satisfied)";
         default: return "unknown status";
     }
 }
@@ -406,6 +407,8 @@ int set_option_one(zkg16_ctx *ctx, const char *name, int64_t v) {
     // zkg16_verify_batch[_wire] with ok_each: range tests bisecting may make before the per-proof pass decides what is left
     // (0 restores the default; 1 = after the first; above 2K = never)
     if (is("verify_each_after")) return set(o.verify_each_after, 0, 1 << 30, v == 0 ? ZKG16_VERIFY_EACH_AFTER_DEFAULT : v);
+    // 0 (default): the proving calls prove whatever they are handed; 1: they check (A z)(B z) == C z after the SpMV and refuse with ZKG16_ERR_UNSATISFIED
+    if (is("check_satisfied")) return set(o.check_satisfied, 0, 1, v);
     if (is("reduce_chunk")) return set(o.reduce_chunk, 0, 64, v, (v & (v - 1)) == 0);      // 0 = default, else a power of two up to 64
     return ZKG16_ERR_UNSUPPORTED;
 }
@@ -451,6 +454,23 @@ int zkg16_last_timings(zkg16_ctx *ctx, float *ms, int cap) {
     const int n = cap < T_COUNT ? cap : T_COUNT;
     for (int i = 0; i < n; i++) ms[i] = l->timings[i];
     return n;
+}
+
+// The verdicts of the last proving call that ran with option "check_satisfied", from the lane of the proof that finished last (as
+// zkg16_last_timings): *k_out = its proofs (0: that call did not check), min(cap, k) of them written.  Returns the number written.
+int zkg16_last_check(zkg16_ctx *ctx, uint64_t *n_bad, uint64_t *first_bad, size_t cap, size_t *k_out) {
+    if (!ctx) return 0;
+    int last;
+    { std::lock_guard<std::mutex> lk(ctx->lane_mu); last = ctx->last_lane; }
+    zkg16_ctx *l = lane_of(ctx, last);
+    std::lock_guard<std::mutex> lk(l->mu);
+    const size_t k = l->check_n_bad.size(), n = cap < k ? cap : k;
+    if (k_out) *k_out = k;
+    for (size_t i = 0; i < n; i++) {
+        if (n_bad) n_bad[i] = l->check_n_bad[i];
+        if (first_bad) first_bad[i] = l->check_first_bad[i];
+    }
+    return (int)n;
 }
 
 // Lengths of the sorted (scalar, window) term lists of the last proof on this ctx = mixed additions per MSM that uses the list:

@@ -295,7 +295,7 @@ int zkg16_prove_group(zkg16_group *group, const uint64_t *pk_handles, const uint
     std::vector<double> wall(n, 0);
     const int st = group_run(group, S ? &S->bar : nullptr, [&](int i, zkg16_ctx *ctx) {
         GroupRank gr{S.get(), wm_of[i]};
-        prove_device(ctx, *pk[i], *rc[i], *wit[i], rr, ss, parts[i], nullptr, nullptr, (S && wm_of[i] >= 0) ? &gr : nullptr);
+        prove_device(ctx, *pk[i], *rc[i], *wit[i], rr, ss, parts[i], nullptr, nullptr, (S && wm_of[i] >= 0) ? &gr : nullptr, false);
         wall[i] = ctx->timings[T_TOTAL];
     });
     group->last_k_dist = st == ZKG16_OK && S ? S->L.k : 0;

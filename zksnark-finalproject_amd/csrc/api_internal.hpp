@@ -167,7 +167,8 @@ struct Partials {
     G1XYZZ s_a, r_b1;
 };
 void prove_device(zkg16_ctx *ctx, PkDev &pk, R1csDev &rc, WitnessDev &wit, const Fr &r, const Fr &s, Partials &out,
-                  const std::function<void()> *before_witness_map = nullptr, const ZParts *zp = nullptr, GroupRank *grp = nullptr);
+                  const std::function<void()> *before_witness_map = nullptr, const ZParts *zp = nullptr, GroupRank *grp = nullptr,
+                  bool may_check = true);      // false (group calls): option "check_satisfied" is not looked at
 void prove_tail(PkDev &pk, const Fr &r, const Fr &s, const Partials &p, uint64_t *proof_out, uint8_t *inf_out);
 // the record of zkg16_prove_partial (h, l, a, b1 | b2 as affine limbs, one infinity flag each), and the sum of n_ranks of them
 void partials_to_abi(const Partials &p, uint64_t out[72], uint8_t inf[5]);

@@ -40,6 +40,31 @@ struct WmStreamSwap {
     WmStreamSwap &operator=(const WmStreamSwap &) = delete;
 };
 
+// ---- option "check_satisfied": the pass's witness map fills 2 K device words (n_bad | first_bad: r1cs_check_run) right after its
+// SpMV; they are read when the pass's results have been collected — all its device work is over by then — and appended to the
+// lane's verdicts, which the entry point consults before it writes anything.  Off: a null pointer, no allocation, no launch.
+uint64_t *check_begin(zkg16_ctx *ctx, size_t K) {
+    if (!ctx->opt.check_satisfied) return nullptr;
+    ctx->check_dev.ensure(2 * K * sizeof(uint64_t));
+    return ctx->check_dev.as<uint64_t>();
+}
+void check_collect(zkg16_ctx *ctx, const uint64_t *words, size_t K) {
+    if (!words) return;
+    std::vector<uint64_t> w(2 * K);
+    ZK_HIP(hipMemcpy(w.data(), words, w.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    ctx->check_n_bad.insert(ctx->check_n_bad.end(), w.begin(), w.begin() + K);
+    ctx->check_first_bad.insert(ctx->check_first_bad.end(), w.begin() + K, w.end());
+}
+void check_reset(zkg16_ctx *ctx) {
+    ctx->check_n_bad.clear();
+    ctx->check_first_bad.clear();
+}
+bool check_failed(const zkg16_ctx *ctx) {
+    for (const uint64_t n : ctx->check_n_bad)
+        if (n) return true;
+    return false;
+}
+
 // The z-side term lists: `z` (A and L) and, when more than 5 % of the terms (the z slice + the r, s, -rs slots) have the point at
 // infinity as their B base, `zb` without those terms (B1 and B2) — worth a second (0.3 ms) list.
 struct ZPlans {
@@ -157,7 +182,7 @@ namespace zk {
 // the witness map waits for the last part.
 // grp (zkg16_prove_group): this rank's share of a split witness map instead of the whole one.
 void prove_device(zkg16_ctx *ctx, PkDev &pk, R1csDev &rc, WitnessDev &wit, const Fr &r, const Fr &s, Partials &out,
-                  const std::function<void()> *before_witness_map, const ZParts *zp, GroupRank *grp) {
+                  const std::function<void()> *before_witness_map, const ZParts *zp, GroupRank *grp, bool may_check) {
     const size_t m_total = rc.num_variables;
     if (wit.n != m_total || pk.m_total != m_total) throw HipError{hipErrorInvalidValue, "prove: assignment / key length mismatch", __FILE__, __LINE__};
     const size_t N = (size_t)1 << rc.log_n;
@@ -166,6 +191,9 @@ void prove_device(zkg16_ctx *ctx, PkDev &pk, R1csDev &rc, WitnessDev &wit, const
     hipEvent_t *ev = evs.ev;
     DrainOnError drain{ctx};
     ctx->batch_terms_set = false;
+    check_reset(ctx);
+    // group calls never check (may_check false: with a split witness map no rank sees every row); a rank without an h range runs no SpMV
+    uint64_t *const chk = (may_check && pk.h_hi > pk.h_lo && !grp) ? check_begin(ctx, 1) : nullptr;
     const double t0 = now_ms();
 
     // ---- main stream: the z-side scalar vector (z-slice || r, s, -rs), read in place by the digit kernel -> digits -> sort.
@@ -228,7 +256,7 @@ void prove_device(zkg16_ctx *ctx, PkDev &pk, R1csDev &rc, WitnessDev &wit, const
         ZK_HIP(hipEventRecord(ev[2], ctx->stream));
         Fr *h = nullptr;
         if (nh && grp) group_witness_map_run(ctx, rc, wit.z.as<Fr>(), &h, *grp);
-        else if (nh) witness_map_run(ctx, rc, wit.z.as<Fr>(), &h);
+        else if (nh) witness_map_run(ctx, rc, wit.z.as<Fr>(), &h, nullptr, chk);
         ZK_HIP(hipEventRecord(ev[3], ctx->stream));
         if (nh) {
             const ScalarSrc hsrc{h + pk.h_lo, nh, nullptr, 0, true, nullptr};
@@ -319,6 +347,7 @@ void prove_device(zkg16_ctx *ctx, PkDev &pk, R1csDev &rc, WitnessDev &wit, const
     }
     record_msm_timings(ctx, nh > 0, z_side);
     record_pass_timings(ctx, ev, t0);
+    check_collect(ctx, chk, 1);
     drain.ok = true;
 }
 
@@ -401,6 +430,7 @@ void prove_batch_device(zkg16_ctx *ctx, PkDev &pk, R1csDev &rc, WitnessDev *cons
     Fr *patch_tab = extra + 3 * K;
     const Fr **vecs = reinterpret_cast<const Fr **>(extra + 5 * K);
     WmPatch patch{{0, 0, 0, 0}, patch_tab};
+    uint64_t *const chk = check_begin(ctx, K);
     for (size_t k = 0; pc && k < K; k++) {
         Fr c = Fr::zero();
         c.l[0] = pc->n[k];
@@ -433,8 +463,8 @@ void prove_batch_device(zkg16_ctx *ctx, PkDev &pk, R1csDev &rc, WitnessDev *cons
         WmStreamSwap on_wm_stream(ctx);
         ZK_HIP(hipEventRecord(ev[2], ctx->stream));
         Fr *hv = nullptr;
-        if (K == 1) witness_map_run(ctx, rc, wits[0]->z.as<Fr>(), &hv, pc ? &patch : nullptr);
-        else witness_map_run_batch(ctx, rc, vecs, (unsigned)K, &hv, pc ? &patch : nullptr);      // vecs: the K assignments (z_lo = 0)
+        if (K == 1) witness_map_run(ctx, rc, wits[0]->z.as<Fr>(), &hv, pc ? &patch : nullptr, chk);
+        else witness_map_run_batch(ctx, rc, vecs, (unsigned)K, &hv, pc ? &patch : nullptr, chk);      // vecs: the K assignments (z_lo = 0)
         ZK_HIP(hipEventRecord(ev[3], ctx->stream));
         ScalarSrc hsrc{hv + pk.h_lo, nh, nullptr, 0, true, nullptr};
         hsrc.vec_stride = N;
@@ -511,6 +541,7 @@ void prove_batch_device(zkg16_ctx *ctx, PkDev &pk, R1csDev &rc, WitnessDev *cons
     ctx->timings[T_HORNER_Z] = host_z_ms;       // the other four's, with s (A + alpha) and r (B1 + beta)
     ctx->timings[T_GAP_L] = ctx->timings[T_GAP_A] = ctx->timings[T_GAP_B1] = 0;
     record_pass_timings(ctx, ev, t0);
+    check_collect(ctx, chk, K);
     drain.ok = true;
 }
 
@@ -555,7 +586,8 @@ void batch_pass_account(zkg16_ctx *ctx, float acc[T_COUNT], uint64_t terms[3], b
 // A batch of k proofs on (pk, rc) in sub-batches that fit (batch_sub_size): pass(off, n, proofs, infs) proves requests
 // [off, off + n) — through prove_batch_device — into staged outputs, which reach proofs_out / inf_out only when every pass has
 // succeeded: a call that fails (pass throws) writes nothing.  Publishes the summed timings and term counts of the passes;
-// -> the passes' summed T_TOTAL.
+// -> the passes' summed T_TOTAL, or a negative value — nothing written — when option "check_satisfied" found an unsatisfied
+// assignment in any pass (every pass still runs: zkg16_last_check names all of them).
 template <class Pass>
 float prove_in_passes(zkg16_ctx *ctx, const PkDev *pk, const R1csDev *rc, size_t k, size_t extra_per_proof, uint64_t *proofs_out,
                       uint8_t *inf_out, Pass &&pass) {
@@ -565,6 +597,7 @@ float prove_in_passes(zkg16_ctx *ctx, const PkDev *pk, const R1csDev *rc, size_t
     const double t0 = now_ms();
     float acc[T_COUNT] = {0};
     uint64_t terms[3] = {0, 0, 0};
+    check_reset(ctx);
     for (size_t off = 0; off < k; off += kb) {
         pass(off, k - off < kb ? k - off : kb, proofs.data() + 48 * off, infs.data() + 3 * off);
         batch_pass_account(ctx, acc, terms, kb >= k);
@@ -573,6 +606,7 @@ float prove_in_passes(zkg16_ctx *ctx, const PkDev *pk, const R1csDev *rc, size_t
     ctx->timings[T_TOTAL] = (float)(now_ms() - t0);
     for (int i = 0; i < 3; i++) ctx->batch_terms[i] = terms[i];
     ctx->batch_terms_set = kb < k;
+    if (check_failed(ctx)) return -1.0f;
     memcpy(proofs_out, proofs.data(), proofs.size() * sizeof(uint64_t));
     memcpy(inf_out, infs.data(), infs.size());
     return acc[T_TOTAL];
@@ -641,6 +675,7 @@ int zkg16_prove_partial(zkg16_ctx *ctx, uint64_t pk_handle, uint64_t r1cs_handle
     if (const int st = lookup_handles(root, pk_handle, r1cs_handle, &witness_handle, 1, Shard::accepted, 0, h)) return st;
     Partials p;
     prove_device(ctx, *h.pk, *h.rc, *h.wits[0], fr_from_abi(r), fr_from_abi(s), p);
+    if (check_failed(ctx)) return ZKG16_ERR_UNSATISFIED;
     partials_to_abi(p, partial_out, partial_inf);
     ZK_LANE_END(ctx)
 }
@@ -678,6 +713,7 @@ int zkg16_prove_resident(zkg16_ctx *ctx, uint64_t pk_handle, uint64_t r1cs_handl
     Partials p;
     const Fr rr = fr_from_abi(r), ss = fr_from_abi(s);
     prove_device(ctx, *h.pk, *h.rc, *h.wits[0], rr, ss, p);
+    if (check_failed(ctx)) return ZKG16_ERR_UNSATISFIED;
     finish_proof(ctx, *h.pk, rr, ss, p, proof_out, inf_out);
     ZK_LANE_END(ctx)
 }
@@ -693,9 +729,10 @@ int zkg16_prove_batch(zkg16_ctx *ctx, uint64_t pk_handle, uint64_t r1cs_handle, 
     ProveHandles h;
     if (const int st = lookup_handles(root, pk_handle, r1cs_handle, witness_handles, k, Shard::unsupported, 0, h)) return st;
     const std::vector<Fr> rr = frs_from_abi(r, k), ss = frs_from_abi(s, k);
-    prove_in_passes(ctx, h.pk.get(), h.rc.get(), k, 0, proofs_out, inf_out, [&](size_t off, size_t n, uint64_t *proofs, uint8_t *infs) {
+    const float ms = prove_in_passes(ctx, h.pk.get(), h.rc.get(), k, 0, proofs_out, inf_out, [&](size_t off, size_t n, uint64_t *proofs, uint8_t *infs) {
         prove_batch_device(ctx, *h.pk, *h.rc, h.wits.data() + off, n, rr.data() + off, ss.data() + off, proofs, infs);
     });
+    if (ms < 0) return ZKG16_ERR_UNSATISFIED;
     ZK_LANE_END(ctx)
 }
 
@@ -736,6 +773,7 @@ int zkg16_prove_matrix(zkg16_ctx *ctx, uint64_t pk_handle, uint64_t r1cs_handle,
     Partials p;
     const Fr rr = fr_from_abi(r), ss = fr_from_abi(s);
     prove_device(ctx, *h.pk, *h.rc, wit, rr, ss, p, nullptr, &zp);      // without part_of (matrix_parts = 1): the assignment first, then the proof
+    if (check_failed(ctx)) return ZKG16_ERR_UNSATISFIED;
     finish_proof(ctx, *h.pk, rr, ss, p, proof_out, inf_out);
     if (public_inputs) matrix_stream_hashes(ms.get(), public_inputs);
     if (timings_ms) {
@@ -779,6 +817,7 @@ int zkg16_prove_matrix_batch(zkg16_ctx *ctx, uint64_t pk_handle, uint64_t r1cs_h
         for (size_t i = 0; i < nb; i++) wits[i] = wit_refs[i].get();
         prove_batch_device(ctx, *h.pk, *h.rc, wits.data(), nb, rr.data() + off, ss.data() + off, proofs, infs);
     });
+    if (prove_ms < 0) return ZKG16_ERR_UNSATISFIED;
     if (public_inputs) memcpy(public_inputs, pubs.data(), pubs.size() * sizeof(uint64_t));
     if (timings_ms) {
         timings_ms[0] = (float)chain_ms;
@@ -828,6 +867,7 @@ int zkg16_prove_prime_batch(zkg16_ctx *ctx, uint64_t pk_handle, uint64_t r1cs_ha
         pc.j = js + off;
         prove_batch_device(ctx, *h.pk, *h.rc, wits.data(), nb, rr.data() + off, ss.data() + off, proofs, infs, &pc);
     });
+    if (prove_ms < 0) return ZKG16_ERR_UNSATISFIED;
     for (size_t i = 0; i < k; i++) {      // gamma_abc_g1[0] = the template's + n V_n - j V_j
         G1XYZZ g = G1XYZZ::from_affine(g0);
         xyzz_add(g, g1_mul_u64(v_n, ns[i]));
@@ -895,6 +935,7 @@ int zkg16_prove(zkg16_ctx *ctx, uint64_t pk_handle, const uint64_t r[4], const u
     Partials p;
     const Fr rr = fr_from_abi(r), ss = fr_from_abi(s);
     prove_device(ctx, *pk, *rc, wit, rr, ss, p, &upload);
+    if (check_failed(ctx)) return ZKG16_ERR_UNSATISFIED;
     finish_proof(ctx, *pk, rr, ss, p, proof_out, inf_out);
     ZK_LANE_END(ctx)
 }

@@ -1,6 +1,7 @@
 // libzkg16 C ABI, part 4 of 6 (api.hip): key generation from a known trapdoor and the stage entry points (NTT, MSM, witness map,
 // fixed-base batches) with their stand-alone benchmarks.
 #include "api_internal.hpp"
+#include "r1cs_check_dev.cuh"
 
 using namespace zk;
 extern "C" {
@@ -210,6 +211,167 @@ int zkg16_fixed_base_g2(zkg16_ctx *ctx, const uint64_t base[24], const uint64_t 
             for (size_t i = 0; i < n; i++) out_inf[i] = o[i].is_inf() ? 1 : 0;
         }
     }
+    ZK_API_END(ctx)
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------ satisfaction (r1cs_check_dev.cuh)
+namespace {
+
+// Assignments per device pass of a stand-alone batched check: the witness map's four vectors per assignment (what zkg16_prove_batch
+// reserves for them; the check itself touches three) plus `extra_per` bytes the caller keeps per assignment, within 60 % of the free
+// HBM — zkg16_prove_batch's sub-batch adds its term lists and bucket arrays to the same sum, so it is never larger — at most 65,535
+// (grid.z), capped by option batch_max.
+size_t check_sub_size(zkg16_ctx *ctx, const R1csDev &rc, size_t extra_per) {
+    const size_t per = 4 * ((size_t)1 << rc.log_n) * sizeof(Fr) + extra_per;
+    size_t free_b = 0, total_b = 0;
+    ZK_HIP(hipMemGetInfo(&free_b, &total_b));
+    size_t kb = (size_t)(0.6 * (double)free_b) / per;
+    if (ctx->opt.batch_max > 0 && (size_t)ctx->opt.batch_max < kb) kb = (size_t)ctx->opt.batch_max;
+    if (kb > 65535) kb = 65535;
+    return kb < 1 ? 1 : kb;
+}
+// pinned, device-visible block of the ctx (shared with zkg16_prove_batch, which runs on a lane under the same mutex)
+void *batch_host_ensure(zkg16_ctx *ctx, size_t bytes) {
+    if (ctx->batch_host_bytes < bytes) {
+        if (ctx->batch_host) (void)hipHostFree(ctx->batch_host);
+        ctx->batch_host = nullptr;
+        ctx->batch_host_bytes = 0;
+        ZK_HIP(hipHostMalloc(&ctx->batch_host, bytes, hipHostMallocDefault));
+        ctx->batch_host_bytes = bytes;
+    }
+    return ctx->batch_host;
+}
+// One pass: the (batched) SpMV of `n` assignments, the patch, the kernel, and the 2 n result words read back into out_n / out_first
+void check_pass(zkg16_ctx *ctx, R1csDev &rc, WitnessDev *const *wits, size_t n, const WmPatch *patch, const Fr **table, uint64_t *out_n,
+                uint64_t *out_first) {
+    ctx->check_dev.ensure(2 * n * sizeof(uint64_t));
+    uint64_t *res = ctx->check_dev.as<uint64_t>();
+    struct Drain { zkg16_ctx *c; bool ok = false; ~Drain() { if (!ok) (void)hipStreamSynchronize(c->stream); } } drain{ctx};
+    if (n == 1 && !patch) {
+        r1cs_check_spmv_run(ctx, rc, wits[0]->z.as<Fr>(), nullptr, 1, nullptr, res);
+    } else {
+        for (size_t i = 0; i < n; i++) table[i] = wits[i]->z.as<Fr>();
+        if (n == 1) r1cs_check_spmv_run(ctx, rc, table[0], nullptr, 1, patch, res);
+        else r1cs_check_spmv_run(ctx, rc, nullptr, table, (unsigned)n, patch, res);
+    }
+    std::vector<uint64_t> w(2 * n);
+    ZK_HIP(hipMemcpyAsync(w.data(), res, w.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));      // the one read-back
+    ZK_HIP(hipStreamSynchronize(ctx->stream));
+    drain.ok = true;
+    memcpy(out_n, w.data(), n * sizeof(uint64_t));
+    memcpy(out_first, w.data() + n, n * sizeof(uint64_t));
+}
+
+}  // namespace
+
+extern "C" {
+
+int zkg16_r1cs_check_host(const uint64_t *const row_ptr[3], const uint32_t *const col[3], const uint64_t *const coeff[3], size_t num_constraints,
+                          size_t num_variables, const uint64_t *z, uint64_t *n_bad, uint64_t *first_bad) {
+    if (!row_ptr || !col || !coeff || !z || !n_bad || num_variables == 0) return ZKG16_ERR_BAD_ARG;
+    for (int m = 0; m < 3; m++) {
+        const uint64_t *rp = row_ptr[m];
+        if (!rp || rp[0] != 0) return ZKG16_ERR_BAD_ARG;
+        for (size_t i = 0; i < num_constraints; i++)
+            if (rp[i] > rp[i + 1]) return ZKG16_ERR_BAD_ARG;
+        const uint64_t nnz = rp[num_constraints];
+        if (nnz && (!col[m] || !coeff[m])) return ZKG16_ERR_BAD_ARG;
+        for (uint64_t k = 0; k < nnz; k++)
+            if (col[m][k] >= num_variables) return ZKG16_ERR_BAD_ARG;
+    }
+    try {
+        // the block walk of r1cs_check_kernel on the host: the SpMV's row sums (spmv_kernel's order of operations), rck::row_fails per
+        // lane, rck::block_fold per block, rck::result_merge where the kernel's atomics are
+        uint64_t bad = rck::result_init(0, 1), first = rck::result_init(1, 1);
+        for (size_t row0 = 0; row0 < num_constraints; row0 += rck::BLOCK) {
+            uint64_t ballots[rck::WAVES] = {0, 0, 0, 0};
+            for (unsigned t = 0; t < rck::BLOCK && row0 + t < num_constraints; t++) {
+                Fr v[3];
+                for (int m = 0; m < 3; m++) {
+                    Fr acc = Fr::zero();
+                    for (uint64_t k = row_ptr[m][row0 + t]; k < row_ptr[m][row0 + t + 1]; k++)
+                        acc = fp_add(acc, fp_mul(fr_from_abi(coeff[m] + 4 * k), fr_from_abi(z + 4 * (size_t)col[m][k])));
+                    v[m] = acc;
+                }
+                if (rck::row_fails(v[0], v[1], v[2])) ballots[t >> 6] |= (uint64_t)1 << (t & 63u);
+            }
+            uint64_t count, f;
+            if (rck::block_fold(ballots, row0, count, f)) rck::result_merge(bad, first, count, f);
+        }
+        *n_bad = bad;
+        if (first_bad) *first_bad = first;
+    } catch (const std::bad_alloc &) {
+        return ZKG16_ERR_OOM;
+    }
+    return ZKG16_OK;
+}
+
+int zkg16_r1cs_check(zkg16_ctx *ctx, uint64_t r1cs_handle, uint64_t witness_handle, uint64_t *n_bad, uint64_t *first_bad) {
+    return zkg16_r1cs_check_batch(ctx, r1cs_handle, &witness_handle, 1, n_bad, first_bad);
+}
+
+int zkg16_r1cs_check_batch(zkg16_ctx *ctx, uint64_t r1cs_handle, const uint64_t *witness_handles, size_t k, uint64_t *n_bad, uint64_t *first_bad) {
+    if (!witness_handles || !n_bad || k == 0) return ZKG16_ERR_BAD_ARG;
+    ZK_API_BEGIN(ctx)
+    auto rc = ctx->r1cs.get(r1cs_handle);
+    if (!rc) return ZKG16_ERR_BAD_HANDLE;
+    std::vector<std::shared_ptr<WitnessDev>> refs(k);
+    std::vector<WitnessDev *> wits(k);
+    for (size_t i = 0; i < k; i++) {
+        refs[i] = ctx->wits.get(witness_handles[i]);
+        if (!(wits[i] = refs[i].get())) return ZKG16_ERR_BAD_HANDLE;
+    }
+    if (rc->prime_template) return ZKG16_ERR_UNSUPPORTED;      // no request's system: its four candidate-dependent coefficients are zero
+    for (size_t i = 0; i < k; i++)
+        if (wits[i]->n != rc->num_variables) return ZKG16_ERR_BAD_ARG;
+    const size_t kb = std::min(k, check_sub_size(ctx, *rc, 0));
+    std::vector<uint64_t> nb(k), fb(k);
+    const Fr **table = kb > 1 ? static_cast<const Fr **>(batch_host_ensure(ctx, kb * sizeof(Fr *))) : nullptr;
+    for (size_t off = 0; off < k; off += kb)
+        check_pass(ctx, *rc, wits.data() + off, std::min(kb, k - off), nullptr, table, nb.data() + off, fb.data() + off);
+    memcpy(n_bad, nb.data(), k * sizeof(uint64_t));
+    if (first_bad) memcpy(first_bad, fb.data(), k * sizeof(uint64_t));
+    ZK_API_END(ctx)
+}
+
+int zkg16_prime_check_batch(zkg16_ctx *ctx, uint64_t r1cs_template_handle, const uint64_t *xs, const uint64_t *js, size_t k, uint64_t *n_bad,
+                            uint64_t *first_bad) {
+    if (!xs || !js || !n_bad || k == 0) return ZKG16_ERR_BAD_ARG;
+    ZK_API_BEGIN(ctx)
+    auto rc = ctx->r1cs.get(r1cs_template_handle);
+    if (!rc) return ZKG16_ERR_BAD_HANDLE;
+    if (!rc->prime_template) return ZKG16_ERR_BAD_ARG;
+    std::vector<Fr> in;
+    std::vector<uint32_t> ns(k);
+    size_t stride = 0;
+    if (const int st = prime_batch_inputs(xs, js, k, in, ns.data(), &stride)) return st;      // a refused candidate: before any device work
+    const size_t kb = std::min(k, check_sub_size(ctx, *rc, rc->num_variables * sizeof(Fr)));
+    std::vector<uint64_t> nb(k), fb(k);
+    for (size_t off = 0; off < k; off += kb) {
+        const size_t n = std::min(kb, k - off);
+        std::vector<std::shared_ptr<WitnessDev>> refs;
+        prime_witness_batch_assign(ctx, in.data() + off * stride, n, refs, nullptr);
+        if (refs.size() != n) throw HipError{hipErrorInvalidValue, "prime check: assignments missing", __FILE__, __LINE__};
+        std::vector<WitnessDev *> wits(n);
+        for (size_t i = 0; i < n; i++) wits[i] = refs[i].get();
+        // request i's n and -j, as prove_batch_device lays them out for wm_patch_kernel, then the assignment table
+        Fr *patch_tab = static_cast<Fr *>(batch_host_ensure(ctx, n * (2 * sizeof(Fr) + sizeof(Fr *))));
+        for (size_t i = 0; i < n; i++) {
+            Fr c = Fr::zero();
+            c.l[0] = ns[off + i];
+            patch_tab[2 * i] = fp_to_mont(c);
+            c.l[0] = (uint32_t)js[off + i];
+            c.l[1] = (uint32_t)(js[off + i] >> 32);
+            patch_tab[2 * i + 1] = fp_neg(fp_to_mont(c));
+        }
+        WmPatch patch{{0, 0, 0, 0}, patch_tab};
+        memcpy(patch.rows, rc->patch_rows, sizeof patch.rows);
+        check_pass(ctx, *rc, wits.data(), n, &patch, reinterpret_cast<const Fr **>(patch_tab + 2 * n), nb.data() + off, fb.data() + off);
+    }
+    memcpy(n_bad, nb.data(), k * sizeof(uint64_t));
+    if (first_bad) memcpy(first_bad, fb.data(), k * sizeof(uint64_t));
     ZK_API_END(ctx)
 }
 

@@ -317,6 +317,10 @@ struct zkg16_ctx {
     void *mbatch_host = nullptr;
     size_t mbatch_host_bytes = 0;
     zk::DevBuf mbatch_dev;
+    // option "check_satisfied": the device words of the pass in flight (n_bad[K] | first_bad[K]) and the verdicts of the last proving
+    // call on this lane (zkg16_last_check); neither exists while the option is off
+    zk::DevBuf check_dev;
+    std::vector<uint64_t> check_n_bad, check_first_bad;
     float timings[zk::PROOF_TIMING_SLOTS] = {0};      // zkg16_last_timings; the slots are named in api_internal.hpp (ProofTiming)
     // ---- zkg16_set_option / zkg16_kernel_timing: everything a lane copies from its root in one assignment (api.hip: copy_options).
     // opt_lanes is not here: it lives on the root alone, under lane_mu.
@@ -356,6 +360,7 @@ struct zkg16_ctx {
         int sponge_chain_segment = 0;                 // permutations of a chain per launch of wit_chain_batch_kernel (0 = 256)
         int verify_batch_min = ZKG16_VERIFY_BATCH_MIN_DEFAULT;                   // zkg16_verify_batch: shorter batches are answered by the host form (the measured crossover)
         int verify_wire_min = ZKG16_VERIFY_WIRE_MIN_DEFAULT;                     // zkg16_verify_batch_wire: shorter batches are decoded and answered on the host (the measured crossover)
+        int check_satisfied = 0;                      // 1: the proving calls check their assignments after the SpMV (r1cs_check_kernel) and refuse unsatisfied ones
         int verify_each_after = ZKG16_VERIFY_EACH_AFTER_DEFAULT;                 // zkg16_verify_batch[_wire] with ok_each: range tests before the per-proof pass takes over
     } opt;
     std::map<std::string, zk::KernelStat> kstats;
@@ -422,8 +427,17 @@ void fr_from_mont_run(zkg16_ctx *ctx, const Fr *in, Fr *out, size_t n);
 // patch (proofs on the PrimeCircuit's template): between the SpMV and the transforms vector v gets add[2 v] added to a[rows[0..2]] and
 // add[2 v + 1] to c[rows[3]] (wm_patch_kernel); add is a device-visible table of nvec x 2 Montgomery values
 struct WmPatch { uint32_t rows[4]; const Fr *add; };
-void witness_map_run(zkg16_ctx *ctx, R1csDev &m, const Fr *z, Fr **h_out, const WmPatch *patch = nullptr);
-void witness_map_run_batch(zkg16_ctx *ctx, R1csDev &m, const Fr *const *zs, unsigned nvec, Fr **h_out, const WmPatch *patch = nullptr);
+// check (nullable; option "check_satisfied"): device words n_bad[nvec] | first_bad[nvec] that r1cs_check_run fills from a, b, c right
+// after the SpMV and the patch, on the same stream, before the first transform
+void witness_map_run(zkg16_ctx *ctx, R1csDev &m, const Fr *z, Fr **h_out, const WmPatch *patch = nullptr, uint64_t *check = nullptr);
+void witness_map_run_batch(zkg16_ctx *ctx, R1csDev &m, const Fr *const *zs, unsigned nvec, Fr **h_out, const WmPatch *patch = nullptr,
+                           uint64_t *check = nullptr);
+// (A z)_i (B z)_i == (C z)_i for i < nc on nvec vectors of a / b / c, vector v at + v * stride (r1cs_check_dev.cuh): res (device, 2 nvec
+// words) <- n_bad[v] at res[v], first_bad[v] at res[nvec + v].  Two launches on ctx->stream, no synchronisation.
+void r1cs_check_run(zkg16_ctx *ctx, size_t nc, const Fr *a, const Fr *b, const Fr *c, size_t stride, unsigned nvec, uint64_t *res);
+// the SpMV of nvec assignments into ctx->poly[0..2] (grown as needed), the patch, and the check into res: what the stand-alone check
+// entries run (zs null with nvec == 1: z)
+void r1cs_check_spmv_run(zkg16_ctx *ctx, R1csDev &m, const Fr *z, const Fr *const *zs, unsigned nvec, const WmPatch *patch, uint64_t *res);
 
 // Scalar-vector side of Pippenger (shared by every MSM over the same scalars).
 struct MsmPlan {

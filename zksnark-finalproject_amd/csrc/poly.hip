@@ -4,6 +4,7 @@
 // Called from /root/reference/src/arkworks/backend/matrix_proof.rs:139-140 via Groth16::prove.
 // All kernels are HBM-streaming (32 B per Fr, 16-B vector loads); SpMV gathers z through L2/MALL.
 #include "common.hpp"
+#include "r1cs_check_dev.cuh"
 
 namespace zk {
 
@@ -522,25 +523,81 @@ static Fr *wm_transforms(zkg16_ctx *ctx, int log_n, Fr *a, Fr *b, Fr *c, Fr *tmp
     return run(a, tmp, true, true, nullptr, &sub);
 }
 
+// ------------------------------------------------------------------------------------------------ satisfaction
+// (A z)_i (B z)_i == (C z)_i on the rows the SpMV (and the patch) has just written, in natural order whatever order its lanes took:
+// lane i < nc of vector blockIdx.z reads a, b, c at v * stride + i (r1cs_check_dev.cuh: row_fails), a wave's verdicts are one ballot,
+// lane 0 of the block folds the four and — only when a row failed — adds to n_bad[v] and lowers first_bad[v].  Rows from nc on (the
+// instance rows, the padding) are not rows of the system.  12 KB read per block, one product per lane: bound by the three streams.
+struct R1csCheckArgs {
+    const Fr *a, *b, *c;
+    size_t stride, nc;
+    uint64_t *res;                // n_bad[nvec] | first_bad[nvec], filled by r1cs_check_init_kernel
+    unsigned nvec;
+};
+__global__ void __launch_bounds__(256) r1cs_check_init_kernel(uint64_t *res, unsigned nvec) {
+    const unsigned t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < 2 * nvec) res[t] = rck::result_init(t, nvec);
+}
+__global__ void __launch_bounds__(256) r1cs_check_kernel(R1csCheckArgs k) {
+    __shared__ uint64_t s_ballot[rck::WAVES];
+    const size_t row0 = (size_t)blockIdx.x * rck::BLOCK, i = row0 + threadIdx.x;
+    const unsigned v = blockIdx.z;
+    bool bad = false;
+    if (i < k.nc) {
+        const size_t at = (size_t)v * k.stride + i;
+        bad = rck::row_fails(gld_fr(k.a + at), gld_fr(k.b + at), gld_fr(k.c + at));
+    }
+    const uint64_t m = __ballot(bad);
+    if ((threadIdx.x & 63u) == 0) s_ballot[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    uint64_t ballots[rck::WAVES], count, first;
+    for (unsigned w = 0; w < rck::WAVES; w++) ballots[w] = s_ballot[w];
+    if (!rck::block_fold(ballots, row0, count, first)) return;
+    atomicAdd(reinterpret_cast<unsigned long long *>(k.res + v), (unsigned long long)count);
+    atomicMin(reinterpret_cast<unsigned long long *>(k.res + k.nvec + v), (unsigned long long)first);
+}
+void r1cs_check_run(zkg16_ctx *ctx, size_t nc, const Fr *a, const Fr *b, const Fr *c, size_t stride, unsigned nvec, uint64_t *res) {
+    if (nvec < 1 || nvec > 65535 || nc > stride || nc >= ((size_t)1 << 32)) throw HipError{hipErrorInvalidValue, "r1cs check: bad shape", __FILE__, __LINE__};
+    ScopedKernelTimer kt(ctx, "r1cs_check_kernel", (double)nc * nvec);
+    hipLaunchKernelGGL(r1cs_check_init_kernel, dim3((2 * nvec + 255) / 256), dim3(256), 0, ctx->stream, res, nvec);
+    if (nc) {
+        const R1csCheckArgs k{a, b, c, stride, nc, res, nvec};
+        hipLaunchKernelGGL(r1cs_check_kernel, dim3((unsigned)((nc + rck::BLOCK - 1) / rck::BLOCK), 1, nvec), dim3(rck::BLOCK), 0, ctx->stream, k);
+    }
+    ZK_HIP(hipGetLastError());
+}
+void r1cs_check_spmv_run(zkg16_ctx *ctx, R1csDev &m, const Fr *z, const Fr *const *zs, unsigned nvec, const WmPatch *patch, uint64_t *res) {
+    const size_t n = (size_t)1 << m.log_n;
+    for (int i = 0; i < 3; i++) ctx->poly[i].ensure((size_t)nvec * n * sizeof(Fr));
+    Fr *a = ctx->poly[0].as<Fr>(), *b = ctx->poly[1].as<Fr>(), *c = ctx->poly[2].as<Fr>();
+    if (nvec == 1 && !zs) spmv_run(ctx, m, z, a, b, c);
+    else spmv_run(ctx, m, nullptr, a, b, c, nullptr, zs, nvec);
+    if (patch) wm_patch_run(ctx, m, a, c, *patch, nvec);
+    r1cs_check_run(ctx, m.num_constraints, a, b, c, n, nvec, res);
+}
+
 // h of one assignment, N Montgomery coefficients.  Result pointer = ctx->poly[3].
-void witness_map_run(zkg16_ctx *ctx, R1csDev &m, const Fr *z, Fr **h_out, const WmPatch *patch) {
+void witness_map_run(zkg16_ctx *ctx, R1csDev &m, const Fr *z, Fr **h_out, const WmPatch *patch, uint64_t *check) {
     const size_t n = (size_t)1 << m.log_n;
     for (int i = 0; i < 4; i++) ctx->poly[i].ensure(n * sizeof(Fr));
     Fr *a = ctx->poly[0].as<Fr>(), *b = ctx->poly[1].as<Fr>(), *c = ctx->poly[2].as<Fr>(), *tmp = ctx->poly[3].as<Fr>();
     spmv_run(ctx, m, z, a, b, c);
     if (patch) wm_patch_run(ctx, m, a, c, *patch, 1);
+    if (check) r1cs_check_run(ctx, m.num_constraints, a, b, c, n, 1, check);
     *h_out = wm_transforms(ctx, m.log_n, a, b, c, tmp, 1);
 }
 
 // The witness map of a batch: the K assignments at zs[0 .. K) (device-visible pointer table), every launch of witness_map_run
 // once over the K vectors — one SpMV, the transform passes with grid.z = K (shared tables, the fused point-wise stage per
 // vector).  a, b, c and the scratch hold K vectors of N side by side; *h_out = K h vectors of N, vector v at (*h_out) + v * N.
-void witness_map_run_batch(zkg16_ctx *ctx, R1csDev &m, const Fr *const *zs, unsigned nvec, Fr **h_out, const WmPatch *patch) {
+void witness_map_run_batch(zkg16_ctx *ctx, R1csDev &m, const Fr *const *zs, unsigned nvec, Fr **h_out, const WmPatch *patch, uint64_t *check) {
     const size_t n = (size_t)1 << m.log_n;
     for (int i = 0; i < 4; i++) ctx->poly[i].ensure((size_t)nvec * n * sizeof(Fr));
     Fr *a = ctx->poly[0].as<Fr>(), *b = ctx->poly[1].as<Fr>(), *c = ctx->poly[2].as<Fr>(), *tmp = ctx->poly[3].as<Fr>();
     spmv_run(ctx, m, nullptr, a, b, c, nullptr, zs, nvec);
     if (patch) wm_patch_run(ctx, m, a, c, *patch, nvec);
+    if (check) r1cs_check_run(ctx, m.num_constraints, a, b, c, n, nvec, check);
     *h_out = wm_transforms(ctx, m.log_n, a, b, c, tmp, nvec);
 }
 

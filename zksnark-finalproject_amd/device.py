@@ -225,6 +225,46 @@ class Device:
     def r1cs_free(self, h):
         self.lib.zkg16_r1cs_free(self.ctx, h)
 
+    # ---- satisfaction: (A z)_i (B z)_i == (C z)_i on the device
+    def r1cs_check(self, r1cs_h, wit_h):
+        """Does the assignment satisfy the system (zkg16_r1cs_check)? -> (n_bad, first_bad): failing constraint rows and the smallest
+        of them, 2^64 - 1 when there is none.  One sparse product and one kernel; counts as a use of the r1cs handle."""
+        nb, fb = C.c_uint64(0), C.c_uint64(0)
+        self._check(self.lib.zkg16_r1cs_check(self.ctx, r1cs_h, wit_h, C.byref(nb), C.byref(fb)))
+        return int(nb.value), int(fb.value)
+
+    @staticmethod
+    def _verdicts(nb, fb):
+        return [(int(n), int(f)) for n, f in zip(nb, fb)]
+
+    def r1cs_check_batch(self, r1cs_h, witness_handles):
+        """k assignments of one system in batched device passes (zkg16_r1cs_check_batch) -> [(n_bad, first_bad)] * k, entry i what
+        r1cs_check(r1cs_h, witness_handles[i]) gives."""
+        hs = np.ascontiguousarray(witness_handles, dtype=np.uint64).reshape(-1)
+        nb, fb = np.zeros(hs.shape[0], dtype=np.uint64), np.zeros(hs.shape[0], dtype=np.uint64)
+        self._check(self.lib.zkg16_r1cs_check_batch(self.ctx, r1cs_h, _ptr(hs), hs.shape[0], _ptr(nb), _ptr(fb)))
+        return self._verdicts(nb, fb)
+
+    def prime_check_batch(self, r1cs_h, xs, js):
+        """k prime requests on the template handle (zkg16_prime_check_batch): the assignments built, multiplied and checked on the
+        device -> [(n_bad, first_bad)] * k, entry i what r1cs_check gives on r1cs_prime / witness_prime(xs[i], js[i]).  A candidate
+        the circuit refuses fails the whole call (status 7) before any device work."""
+        xs, js = _u64(xs).reshape(-1), _u64(js).reshape(-1)
+        if xs.shape != js.shape:
+            raise ValueError("prime_check_batch: one j per x")
+        nb, fb = np.zeros(xs.shape[0], dtype=np.uint64), np.zeros(xs.shape[0], dtype=np.uint64)
+        self._check(self.lib.zkg16_prime_check_batch(self.ctx, r1cs_h, _ptr(xs), _ptr(js), xs.shape[0], _ptr(nb), _ptr(fb)))
+        return self._verdicts(nb, fb)
+
+    def last_check(self):
+        """-> [(n_bad, first_bad)] per proof of the last proving call, when it ran with option "check_satisfied" = 1 (zkg16_last_check);
+        [] when it did not check."""
+        k = C.c_size_t(0)
+        self.lib.zkg16_last_check(self.ctx, None, None, 0, C.byref(k))
+        nb, fb = np.zeros(max(k.value, 1), dtype=np.uint64), np.zeros(max(k.value, 1), dtype=np.uint64)
+        n = self.lib.zkg16_last_check(self.ctx, _ptr(nb), _ptr(fb), k.value, None)
+        return self._verdicts(nb[:n], fb[:n])
+
     def witness_load(self, z):
         z = _u64(z).reshape(-1, 4)
         handle = C.c_uint64()

@@ -87,7 +87,7 @@ class _DeviceCircuit:
         self.public_inputs = public_inputs
 
 
-def _request(dev, rng, circ, r1cs, assignment, keep_key=False, overlap=False):
+def _request(dev, rng, circ, r1cs, assignment, keep_key=False, overlap=False, check_on_device=False):
     """One request of any handler: draw the key, obtain the R1CS and the assignment, set the key up, draw r and s, prove, release.
     circ gives the dimensions.  r1cs(own) -> R1CS handle and assignment(own) -> (witness handle, public inputs or None) say how
     this kind of circuit reaches the device; each passes a handle the request owns through own(free, handle) the moment it has it,
@@ -96,7 +96,9 @@ def _request(dev, rng, circ, r1cs, assignment, keep_key=False, overlap=False):
     keep_key: the key goes through the host (zkg16_setup -> zkg16_pk_load) and is returned as "pk"; else it never leaves the device.
     overlap: the assignment needs neither the key nor (for its host half, the three Poseidon chains) the device, so it is obtained
     on a thread beside the setup's kernels (zkg16_witness_matrix takes the ctx only for its ~1 ms of kernels): at 128x128 the 61 ms
-    of chains disappear under the 0.2 s setup."""
+    of chains disappear under the 0.2 s setup.
+    check_on_device: before proving, Device.r1cs_check on the two handles the request holds -> "satisfied" (else None) and
+    "check_time", which is not part of proving_time; the proof is made either way."""
     trap, g1, g2 = _draw_key(rng)
     with contextlib.ExitStack() as stack:
         def own(free, h):
@@ -138,11 +140,17 @@ def _request(dev, rng, circ, r1cs, assignment, keep_key=False, overlap=False):
             if "err" in early:
                 raise early["err"]
             wh, pub = early["out"]
+        satisfied, check_time = None, 0.0
+        if check_on_device:
+            tc = time.perf_counter()
+            satisfied = dev.r1cs_check(rh, wh)[0] == 0
+            check_time = time.perf_counter() - tc
         proof, inf = dev.prove_resident(ph, rh, wh, r, s)
-        proving_time = time.perf_counter() - t0
+        proving_time = time.perf_counter() - t0 - check_time
     if pub is not None:
         circ.public_inputs = pub
-    return dict(proof=proof, inf=inf, vk=vk, pk=pk, setup_time=setup_time, proving_time=proving_time, r=r, s=s)
+    return dict(proof=proof, inf=inf, vk=vk, pk=pk, setup_time=setup_time, proving_time=proving_time, r=r, s=s, satisfied=satisfied,
+                check_time=check_time)
 
 
 def _from_host(dev, circ):
@@ -180,13 +188,21 @@ def hash_matrices(size, matrices, dev=None):
     return [dict(hash=list(wire.hash_bytes(h))) for h in hashes]   # OutputData.hash: a Vec<u8> (matrix_proof.rs:66-70)
 
 
-def prove_matrix(dev, size, matrix_a, matrix_b, seed=0, keep_key=False):
-    """-> the reference's ProveOutput fields (matrix_proof.rs:80-91)."""
+def _with_verdict(record, out, check_on_device):
+    """The record of a handler whose response has no "satisfied" field: it gets one only when the device check was asked for."""
+    if check_on_device:
+        record["satisfied"] = out["satisfied"]
+    return record
+
+
+def prove_matrix(dev, size, matrix_a, matrix_b, seed=0, keep_key=False, check_on_device=False):
+    """-> the reference's ProveOutput fields (matrix_proof.rs:80-91).  check_on_device: "satisfied" is added, the verdict of
+    Device.r1cs_check on the request's handles (the reference's matrix handler does not check)."""
     a = np.asarray(matrix_a, dtype=np.uint64).reshape(size, size)
     b = np.asarray(matrix_b, dtype=np.uint64).reshape(size, size)
     if keep_key or size < 2:            # tests want the host copy of everything
         circ = matrix_circuit(a, b)
-        out = _request(dev, random.Random(seed), circ, *_from_host(dev, circ), keep_key=keep_key)
+        out = _request(dev, random.Random(seed), circ, *_from_host(dev, circ), keep_key=keep_key, check_on_device=check_on_device)
     else:                               # the request path: resident matrices, the assignment built on the device beside the setup
         shape = _matrix_shape(dev, size)
         circ = _DeviceCircuit(shape.num_instance, shape.num_witness, shape.num_constraints)      # hash_a, hash_b, hash_c come with the assignment
@@ -194,22 +210,24 @@ def prove_matrix(dev, size, matrix_a, matrix_b, seed=0, keep_key=False):
         def assignment(own):
             wh, pub, _ = dev.witness_matrix(a, b)
             return own(dev.witness_free, wh), pub
-        out = _request(dev, random.Random(seed), circ, lambda own: shape.rh, assignment, overlap=True)
+        out = _request(dev, random.Random(seed), circ, lambda own: shape.rh, assignment, overlap=True, check_on_device=check_on_device)
     ha, hb, hc = circ.public_inputs
-    return dict(hash_a=wire.encode_hash(ha), hash_b=wire.encode_hash(hb), hash_c=wire.encode_hash(hc),
+    return _with_verdict(dict(hash_a=wire.encode_hash(ha), hash_b=wire.encode_hash(hb), hash_c=wire.encode_hash(hc),
                 setup_time=out["setup_time"], proving_time=out["proving_time"],
                 # the reference counts matrix_mul twice (outer cs + circuit: matrix_proof.rs:108,150,160)
                 num_constraints=circ.num_constraints + 2 * size ** 3, num_constraints_circuit=circ.num_constraints,
                 num_variables=circ.num_instance, proof=wire.encode_proof(out["proof"], out["inf"]),
                 # the reference returns the prepared key (encode_pvk, io.rs:62-68); the plain key is kept beside it
-                pvk=wire.encode_pvk(out["vk"]), vk=wire.encode_vk(out["vk"]), _detail=out, _circuit=circ)
+                pvk=wire.encode_pvk(out["vk"]), vk=wire.encode_vk(out["vk"]), _detail=out, _circuit=circ), out, check_on_device)
 
 
-def prove_matrices(dev, size, pairs, seed=0, key=None):
+def prove_matrices(dev, size, pairs, seed=0, key=None, check_on_device=False):
     """K requests of one size under ONE key, assignments and proofs in batched device passes (Device.prove_matrix_batch).  pairs: K
     (matrix_a, matrix_b).  The key is set up once on the device from `seed` (the draws of prove_matrix, then r, s per request, so
     request 0 is prove_matrix's proof for that seed), or passed in as key=(pk handle, vk dict), which stays the caller's.  The
-    matrices come from the shape cache.  -> the shared vk / pvk and, per request, prove_matrix's hash_a / hash_b / hash_c / proof."""
+    matrices come from the shape cache.  -> the shared vk / pvk and, per request, prove_matrix's hash_a / hash_b / hash_c / proof.
+    check_on_device: the assignments are built as handles (Device.witness_matrix_batch), checked together (Device.r1cs_check_batch)
+    and proved with Device.prove_batch — the same proof bytes — and every request's record gets "satisfied"."""
     k = len(pairs)
     if k == 0:
         raise ValueError("prove_matrices: no requests")
@@ -229,33 +247,48 @@ def prove_matrices(dev, size, pairs, seed=0, key=None):
             ph, vk = key
         rs, ss = _draw_rs_batch(rng, k)
         t0 = time.perf_counter()
-        proofs, inf, pubs, ms = dev.prove_matrix_batch(ph, shape.rh, a, b, rs, ss)
+        verdicts = None
+        if check_on_device:
+            whs, pubs, ms = dev.witness_matrix_batch(a, b)
+            for wh in whs:
+                stack.callback(dev.witness_free, int(wh))
+            verdicts = dev.r1cs_check_batch(shape.rh, whs)
+            proofs, inf = dev.prove_batch(ph, shape.rh, whs, rs, ss)
+        else:
+            proofs, inf, pubs, ms = dev.prove_matrix_batch(ph, shape.rh, a, b, rs, ss)
         proving_time = time.perf_counter() - t0
     requests = [dict(hash_a=wire.encode_hash(pubs[i][0]), hash_b=wire.encode_hash(pubs[i][1]), hash_c=wire.encode_hash(pubs[i][2]),
                      proof=wire.encode_proof(proofs[i], inf[i])) for i in range(k)]
+    if verdicts is not None:
+        for q, (n_bad, _) in zip(requests, verdicts):
+            q["satisfied"] = n_bad == 0
     return dict(vk=wire.encode_vk(vk), pvk=wire.encode_pvk(vk), setup_time=setup_time, proving_time=proving_time,
                 num_constraints_circuit=shape.num_constraints, num_variables=shape.num_instance, requests=requests,
                 _detail=dict(proofs=proofs, inf=inf, public_inputs=pubs, vk=vk, rs=rs, ss=ss, ms=ms))
 
 
-def prove_fibonacci(dev, a, b, num_of_rounds, seed=42, keep_key=False):
-    """-> the reference's OutputDataFib-like fields (fibbonaci_handler.rs:84-90)."""
+def prove_fibonacci(dev, a, b, num_of_rounds, seed=42, keep_key=False, check_on_device=False):
+    """-> the reference's OutputDataFib-like fields (fibbonaci_handler.rs:84-90).  check_on_device: "satisfied" is added, the verdict
+    of Device.r1cs_check on the request's handles."""
     if keep_key:
         circ = fibonacci_circuit(a, b, num_of_rounds)
         sources = _from_host(dev, circ)
     else:
         circ = fibonacci_circuit_handle(a, b, num_of_rounds)
         sources = _from_handle(dev, circ)
-    out = _request(dev, random.Random(seed), circ, *sources, keep_key=keep_key)
-    return dict(proof=wire.encode_proof(out["proof"], out["inf"]), proving_time=out["proving_time"], setup_time=out["setup_time"],
+    out = _request(dev, random.Random(seed), circ, *sources, keep_key=keep_key, check_on_device=check_on_device)
+    return _with_verdict(dict(proof=wire.encode_proof(out["proof"], out["inf"]), proving_time=out["proving_time"], setup_time=out["setup_time"],
                 num_constraints=circ.num_constraints, num_variables=circ.num_instance,
                 fib_number=[wire.encode_hash(x) for x in circ.public_inputs][-1], pvk=wire.encode_pvk(out["vk"]), vk=wire.encode_vk(out["vk"]),
-                _detail=out, _circuit=circ)
+                _detail=out, _circuit=circ), out, check_on_device)
 
 
-def prove_prime(dev, x, i, seed=7, keep_key=False, check_satisfied=False):
+def prove_prime(dev, x, i, seed=7, keep_key=False, check_satisfied=False, check_on_device=False):
     """-> the reference's ProveOutput fields of the prime handler (prime_snark.rs:36-47): search j in 0..=i for the first
-    hash(x + j) mod 2^20 that passes the Fermat test, build PrimeCircuit for it, circuit-specific setup, prove."""
+    hash(x + j) mod 2^20 that passes the Fermat test, build PrimeCircuit for it, circuit-specific setup, prove.
+    "satisfied": None, or with check_satisfied the host synthesis' verdict (which leaves the device path for the host synthesis),
+    or with check_on_device Device.r1cs_check's on the handles of whichever path the request took — what the reference's
+    assert!(cs.is_satisfied()) (prime_snark.rs:123-128) looks at.  The proof is returned either way."""
     found = prime_search(x, i)
     if not found["found"]:
         return dict(_PRIME_NOT_FOUND)
@@ -267,11 +300,11 @@ def prove_prime(dev, x, i, seed=7, keep_key=False, check_satisfied=False):
         circ = _DeviceCircuit(dims["num_instance"], dims["num_witness"], dims["num_constraints"], prime_public_inputs(x, j))
         circ.j = j
         sources = (lambda own: own(dev.r1cs_free, dev.r1cs_prime(x, j)), lambda own: (own(dev.witness_free, dev.witness_prime(x, j)), None))
-    out = _request(dev, random.Random(seed), circ, *sources, keep_key=keep_key)
+    out = _request(dev, random.Random(seed), circ, *sources, keep_key=keep_key, check_on_device=check_on_device)
     return dict(proof=wire.encode_proof(out["proof"], out["inf"]), j=found["j"], num_constraints=circ.num_constraints,
                 num_variables=circ.num_vars, setup_time=out["setup_time"], proving_time=out["proving_time"], found_prime=True,
-                prime_num=str(found["prime"]), pvk=wire.encode_pvk(out["vk"]), vk=wire.encode_vk(out["vk"]), satisfied=circ.satisfied,
-                _detail=out, _circuit=circ)
+                prime_num=str(found["prime"]), pvk=wire.encode_pvk(out["vk"]), vk=wire.encode_vk(out["vk"]),
+                satisfied=out["satisfied"] if check_on_device else circ.satisfied, _detail=out, _circuit=circ)
 
 
 _PRIME_NOT_FOUND = dict(proof="", j=0, num_constraints=0, num_variables=0, setup_time=0.0, proving_time=0.0, found_prime=False, prime_num="", vk="")
@@ -298,13 +331,15 @@ def prime_template_key(dev, rng):
     return dict(ph=ph, rh=rh, vk=vk, corr=corr, ext_vk=ext_vk, setup_time=setup_time)
 
 
-def prove_primes(dev, requests, seed=7, key=None):
+def prove_primes(dev, requests, seed=7, key=None, check_on_device=False):
     """K requests of the prime handler, requests = [(x, i), ...], under ONE trapdoor: the search runs per request, the requests
     that found a prime are proved on one template key in batched device passes (Device.prove_prime_batch).  The key is set up
     once from `seed` with prove_prime's draws (then r, s per proved request), so request 0 is prove_prime's proof and key for that
     seed, byte for byte; or it is passed in as key= (prime_template_key's dict), which stays the caller's.  A request's key is the
     template's with gamma_abc_g1[0] replaced, so the prepared key is made once and only that element changes per request.
-    -> a list of prove_prime's fields per request (a request without a prime: its not-found record)."""
+    -> a list of prove_prime's fields per request (a request without a prime: its not-found record).
+    check_on_device: every proved request's "satisfied" is its verdict from Device.prime_check_batch on the template (else None);
+    the proofs are returned either way."""
     if len(requests) == 0:
         raise ValueError("prove_primes: no requests")
     found = [prime_search(x, i) for x, i in requests]
@@ -322,6 +357,7 @@ def prove_primes(dev, requests, seed=7, key=None):
         rs, ss = _draw_rs_batch(rng, len(hits))
         xs = np.array([requests[q][0] for q in hits], dtype=np.uint64)
         js = np.array([found[q]["j"] for q in hits], dtype=np.uint64)
+        verdicts = dev.prime_check_batch(key["rh"], xs, js) if check_on_device else None
         t0 = time.perf_counter()
         proofs, inf, g0, pubs, ms = dev.prove_prime_batch(key["ph"], key["rh"], key["corr"], key["vk"]["gamma_abc_g1"][0], xs, js, rs, ss)
         proving_time = time.perf_counter() - t0
@@ -337,7 +373,8 @@ def prove_primes(dev, requests, seed=7, key=None):
                       num_variables=dims["num_instance"] + dims["num_witness"], setup_time=key["setup_time"] if own else 0.0,
                       proving_time=proving_time / len(hits), found_prime=True, prime_num=str(found[q]["prime"]),
                       pvk=base64.standard_b64encode(pvk_bytes[:344] + point + pvk_bytes[392:]).decode(),
-                      vk=base64.standard_b64encode(vk_bytes[:344] + point + vk_bytes[392:]).decode(), satisfied=None,
+                      vk=base64.standard_b64encode(vk_bytes[:344] + point + vk_bytes[392:]).decode(),
+                      satisfied=None if verdicts is None else verdicts[n][0] == 0,
                       _detail=dict(proof=proofs[n], inf=inf[n], vk=vk_q, r=rs[n], s=ss[n], public_inputs=pubs[n], ms=ms))
     return out
 
