@@ -661,6 +661,29 @@ ZKG16_API int zkg16_acc_resident_waves(zkg16_ctx *ctx, int waves[2]);
  * that ran on the ctx's first lane (it takes over the workspace and slot the words live in); entries and what follows are zero
  * after a call with n = 0.  A null out: ZKG16_ERR_BAD_ARG. */
 ZKG16_API int zkg16_last_msm_state(zkg16_ctx *ctx, uint32_t out[8]);
+/* The bucket scatter alone on raw digit codes (diagnostics for tests): codes[nwin][n] in the digit kernel's format, (|d| - 1) << 1 |
+ * negate with |d| - 1 < 2^(c-1), or ~0 for digit 0.  Runs the scatter the MSM plans run, in a workspace of its own (the ctx's term
+ * lists, slots and zkg16_last_msm_state are left as they were), and copies out: entries_xy = the sorted list as (x, y) pairs of 32-bit
+ * words, x = position << 1 | negate, y = window * 2^(c-1) + bucket (room for nwin * n pairs; *length are written); win_totals[nwin] =
+ * entries per window — for more than 32 windows the differences of the scatter's own window prefix; *length = the list's length as
+ * the device summed it.  n == 0: *length = 0, win_totals zero, ZKG16_OK.  c - 1 > 24 or n >= 2^31: the scatter refuses
+ * (ZKG16_ERR_HIP, zkg16_last_error names the limit).  nwin < 1, c < 2, nwin * n >= 2^31 or a null pointer: ZKG16_ERR_BAD_ARG.
+ * Synchronises the ctx's stream; on any error no output is written. */
+ZKG16_API int zkg16_diag_bucket_sort(zkg16_ctx *ctx, const uint32_t *codes, size_t n, int nwin, int c, uint32_t *entries_xy,
+                                     uint32_t *win_totals, uint64_t *length);
+/* The sorted term list of batch vectors of n canonical scalars (scalars[batch][n][4]) as the proofs build it (diagnostics for tests):
+ * digits, scatter (or the rocPRIM sort under option "sort_mode" 1) and bucket offsets, in workspaces of its own.  window_bits and
+ * tabled go to the plan as they are (a tabled plan takes up to 24 bits; a width the plan does not take = chosen by size).  mask_mode
+ * 0: no mask; 1: scalars i with mask[i] != 0 count as zero in the digit kernel; 2: the full list, then the stable compaction that
+ * drops their terms (what B1 / B2 of a key with window tables use).  plan_out = { c, windows of the list, digits per scalar,
+ * total buckets tb }; entries_xy = the first offsets[tb] entries (x = position << 1 | negate, position = i on a plain key and
+ * digit * n + i with tables; y = global bucket id), at most entries_cap pairs; offsets = the tb + 1 bucket boundaries, at most
+ * offsets_cap words; *length = offsets[tb].  n == 0: plan_out only, *length = 0.  A buffer too small for the plan, batch < 1, a
+ * mask_mode outside 0..2, mask_mode != 0 without a mask or a null pointer: ZKG16_ERR_BAD_ARG.  Synchronises the ctx's stream; on any
+ * error no output is written. */
+ZKG16_API int zkg16_diag_term_list(zkg16_ctx *ctx, const uint64_t *scalars_canonical, size_t n, int batch, int window_bits, int tabled,
+                                   const uint8_t *mask, int mask_mode, uint32_t plan_out[4], uint32_t *entries_xy, size_t entries_cap,
+                                   uint32_t *offsets, size_t offsets_cap, uint64_t *length);
 /* Which sparse product an r1cs handle's witness maps run (diagnostics; takes the handle's own lock, launches nothing):
  * out = { dict_state, ndict, perm_ok, spmv_uses }.  dict_state: 0 = the coefficient dictionary has not been tried yet (the handle
  * has run fewer than two witness maps: plain kernel, rows in natural order), 1 = the dictionary is in use (ndict distinct

@@ -162,6 +162,108 @@ int zkg16_bench_msm(zkg16_ctx *ctx, int group, const uint64_t *bases, const uint
     return ZKG16_ERR_BAD_ARG;
 }
 
+}  // extern "C"
+
+namespace {
+// a failed diagnostic call leaves no launch behind that still reads the workspace it is about to release
+struct StreamDrain { zkg16_ctx *c; bool ok = false; ~StreamDrain() { if (!ok) (void)hipStreamSynchronize(c->stream); } };
+}  // namespace
+
+extern "C" {
+
+// The bucket scatter alone (msm_bucket_sort as the plans call it) on caller-made digit codes, in a workspace of its own: ws_h, the
+// slots and last_msm_group are not touched.  The results reach the caller's buffers only after everything has succeeded.
+int zkg16_diag_bucket_sort(zkg16_ctx *ctx, const uint32_t *codes, size_t n, int nwin, int c, uint32_t *entries_xy, uint32_t *win_totals,
+                           uint64_t *length) {
+    if (!ctx || (!codes && n) || (!entries_xy && n) || !win_totals || !length || nwin < 1 || c < 2) return ZKG16_ERR_BAD_ARG;
+    if (n && (uint64_t)nwin >= ((uint64_t)1 << 31) / n) return ZKG16_ERR_BAD_ARG;      // positions are 32-bit words
+    ZK_API_BEGIN(ctx)
+    std::vector<uint32_t> tot((size_t)nwin, 0u);
+    std::vector<uint2> list;
+    uint64_t len = 0;
+    if (n) {
+        const size_t cells = (size_t)nwin * n;
+        MsmWorkspace ws;
+        DevBuf d_codes(cells * sizeof(uint32_t)), d_entries(cells * sizeof(uint2));
+        std::vector<uint32_t> raw((size_t)nwin + 1, 0u);
+        StreamDrain drain{ctx};
+        ZK_HIP(hipMemcpyAsync(d_codes.p, codes, cells * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+        int sum_windows = 0;
+        const uint32_t *wt = msm_bucket_sort(ctx, ws, d_codes.as<uint32_t>(), n, nwin, c, d_entries.as<uint2>(), &sum_windows);
+        // nwin totals, or (many windows) the last word of the scatter's window prefix [nwin + 1]: the totals are its differences
+        const bool prefix = sum_windows == 1 && nwin > 1;
+        if (prefix) ZK_HIP(hipMemcpyAsync(raw.data(), wt - nwin, ((size_t)nwin + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        else ZK_HIP(hipMemcpyAsync(raw.data(), wt, (size_t)nwin * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        ZK_HIP(hipStreamSynchronize(ctx->stream));
+        for (int w = 0; w < nwin; w++) tot[w] = prefix ? raw[w + 1] - raw[w] : raw[w];
+        if (prefix) len = raw[nwin];
+        else for (int w = 0; w < nwin; w++) len += raw[w];
+        if (len > cells) throw HipError{hipErrorInvalidValue, "bucket sort: list longer than its input", __FILE__, __LINE__};
+        list.resize((size_t)len);
+        if (len) ZK_HIP(hipMemcpyAsync(list.data(), d_entries.p, (size_t)len * sizeof(uint2), hipMemcpyDeviceToHost, ctx->stream));
+        ZK_HIP(hipStreamSynchronize(ctx->stream));
+        drain.ok = true;
+    }
+    if (len) memcpy(entries_xy, list.data(), (size_t)len * sizeof(uint2));
+    memcpy(win_totals, tot.data(), (size_t)nwin * sizeof(uint32_t));
+    *length = len;
+    ZK_API_END(ctx)
+}
+
+// A term list as build_z_plans makes it — msm_plan_build, and for mask_mode 2 msm_plan_filter of the full list — in workspaces of
+// its own; only the valid part (offsets[tb] entries: under sort_mode 1 the digit-0 keys sort behind it) and the offsets are copied out.
+int zkg16_diag_term_list(zkg16_ctx *ctx, const uint64_t *scalars_canonical, size_t n, int batch, int window_bits, int tabled, const uint8_t *mask,
+                         int mask_mode, uint32_t plan_out[4], uint32_t *entries_xy, size_t entries_cap, uint32_t *offsets, size_t offsets_cap,
+                         uint64_t *length) {
+    if (!ctx || (!scalars_canonical && n) || !plan_out || !length || batch < 1 || mask_mode < 0 || mask_mode > 2 || (mask_mode && !mask && n))
+        return ZKG16_ERR_BAD_ARG;
+    if (n && (!entries_xy || !offsets)) return ZKG16_ERR_BAD_ARG;
+    ZK_API_BEGIN(ctx)
+    const int c = msm_plan_bits(ctx, n, window_bits, tabled != 0);
+    const size_t digits = (size_t)(254 / c + 1), tb = ((size_t)1 << (c - 1)) * (size_t)batch * (tabled ? 1 : digits);
+    if (tb >= ((size_t)1 << 32)) return ZKG16_ERR_BAD_ARG;
+    if (n && (offsets_cap < tb + 1 || entries_cap / digits / (size_t)batch < n)) return ZKG16_ERR_BAD_ARG;
+    std::vector<uint32_t> offs;
+    std::vector<uint2> list;
+    uint32_t len = 0;
+    MsmPlan plan;
+    if (n) {
+        MsmWorkspace ws, ws_f;
+        DevBuf d_sc((size_t)batch * n * sizeof(Fr)), d_mask(mask_mode ? n : 1);
+        StreamDrain drain{ctx};
+        ZK_HIP(hipMemcpyAsync(d_sc.p, scalars_canonical, (size_t)batch * n * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
+        if (mask_mode) ZK_HIP(hipMemcpyAsync(d_mask.p, mask, n, hipMemcpyHostToDevice, ctx->stream));
+        ScalarSrc src{d_sc.as<Fr>(), n, nullptr, 0, false, mask_mode == 1 ? d_mask.as<uint8_t>() : nullptr};
+        src.vec_stride = n;
+        src.batch = batch;
+        msm_plan_build(ctx, ws, src, plan, window_bits, tabled != 0);
+        const MsmWorkspace *res = &ws;
+        if (mask_mode == 2) {
+            MsmPlan kept;
+            msm_plan_filter(ctx, ws, plan, d_mask.as<uint8_t>(), ws_f, kept);
+            res = &ws_f;
+        }
+        if (plan.c != c || plan.nb * (size_t)plan.nwin != tb) throw HipError{hipErrorInvalidValue, "term list: plan differs from its forecast", __FILE__, __LINE__};
+        offs.resize(tb + 1);
+        ZK_HIP(hipMemcpyAsync(offs.data(), res->offsets.p, (tb + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        ZK_HIP(hipStreamSynchronize(ctx->stream));
+        len = offs[tb];
+        if ((size_t)len > plan.total_entries) throw HipError{hipErrorInvalidValue, "term list: longer than its input", __FILE__, __LINE__};
+        list.resize(len);
+        if (len) ZK_HIP(hipMemcpyAsync(list.data(), res->entries.p, (size_t)len * sizeof(uint2), hipMemcpyDeviceToHost, ctx->stream));
+        ZK_HIP(hipStreamSynchronize(ctx->stream));
+        drain.ok = true;
+    }
+    plan_out[0] = (uint32_t)c;
+    plan_out[1] = (uint32_t)((size_t)batch * (tabled ? 1 : digits));
+    plan_out[2] = (uint32_t)digits;
+    plan_out[3] = (uint32_t)tb;
+    if (len) memcpy(entries_xy, list.data(), (size_t)len * sizeof(uint2));
+    if (n) memcpy(offsets, offs.data(), (tb + 1) * sizeof(uint32_t));
+    *length = len;
+    ZK_API_END(ctx)
+}
+
 int zkg16_witness_map(zkg16_ctx *ctx, uint64_t r1cs_handle, uint64_t witness_handle, uint64_t *h_out, size_t *log_n_out) {
     if (!h_out) return ZKG16_ERR_BAD_ARG;
     ZK_API_BEGIN(ctx)

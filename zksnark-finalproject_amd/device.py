@@ -119,6 +119,42 @@ class Device:
         self._check(self.lib.zkg16_last_msm_state(self.ctx, out))
         return tuple(int(x) for x in out)
 
+    def diag_bucket_sort(self, codes, c):
+        """codes: (nwin, n) uint32 digit codes ((|d| - 1) << 1 | negate, ~0 for digit 0) -> (entries (length, 2) uint32 of (x, y),
+        win_totals (nwin,) uint32, length): the bucket scatter alone, in a workspace of its own (zkg16_diag_bucket_sort)."""
+        codes = np.ascontiguousarray(codes, dtype=np.uint32)
+        nwin, n = codes.shape
+        entries = np.zeros((nwin * n, 2), dtype=np.uint32)
+        totals = np.zeros(nwin, dtype=np.uint32)
+        length = C.c_uint64(0)
+        self._check(self.lib.zkg16_diag_bucket_sort(self.ctx, _ptr(codes) if n else None, n, nwin, int(c), _ptr(entries) if n else None,
+                                                    totals.ctypes.data, C.byref(length)))
+        return entries[:length.value], totals, int(length.value)
+
+    def diag_term_list(self, scalars, window_bits, tabled=False, mask=None, mask_mode=0):
+        """scalars: (batch, n, 4) or (n, 4) canonical u64 limbs -> (plan (c, windows, digits, total buckets), entries (length, 2) uint32
+        of (x, y), offsets (total buckets + 1,) uint32): the sorted term list a proof would build (zkg16_diag_term_list).  mask_mode
+        1 = mask in the digit kernel, 2 = the full list filtered."""
+        sc = _u64(scalars)
+        if sc.ndim == 2:
+            sc = sc[None]
+        batch, n = sc.shape[0], sc.shape[1]
+        if not 2 <= int(window_bits) <= (24 if tabled else 20):
+            raise ValueError("diag_term_list: name the window bits (the buffers are sized from them)")
+        digits = 254 // int(window_bits) + 1
+        tb = (1 << (int(window_bits) - 1)) * batch * (1 if tabled else digits)
+        entries = np.zeros((batch * n * digits, 2), dtype=np.uint32)
+        offsets = np.zeros(tb + 1, dtype=np.uint32)
+        mask = _opt_u8(mask)
+        if mask is not None and mask.shape != (n,):
+            raise ValueError("diag_term_list: one mask byte per scalar")
+        plan = (C.c_uint32 * 4)()
+        length = C.c_uint64(0)
+        self._check(self.lib.zkg16_diag_term_list(self.ctx, _ptr(sc) if n else None, n, batch, int(window_bits), int(bool(tabled)), _ptr(mask),
+                                                  int(mask_mode), plan, _ptr(entries) if n else None, entries.shape[0],
+                                                  _ptr(offsets) if n else None, offsets.shape[0], C.byref(length)))
+        return tuple(int(x) for x in plan), entries[:length.value], offsets
+
     def circuit_load(self, circuit):
         """circuit: a circuits.CircuitHandle (a synthesized circuit still held by the library) -> (r1cs_handle, witness_handle), loaded
         without exporting its arrays to Python (zkg16_circuit_load)."""
