@@ -550,6 +550,37 @@ ZKG16_API int zkg16_prove_prime_batch(zkg16_ctx *ctx, uint64_t pk_handle, uint64
                                       const uint64_t *r, const uint64_t *s, uint64_t *proofs_out /* k x 48 */, uint8_t *inf_out /* k x 3 */,
                                       uint64_t *gamma_abc0_out /* k x 12 */, uint64_t *public_inputs /* nullable, k x 257 x 4 */,
                                       float *timings_ms /* nullable, 4 */);
+/* ---- K Fibonacci requests on ONE key.  The FibonacciCircuit's matrices depend on `steps` alone (fibbonaci.rs:22-48: a, b and result
+ * occur only in the assignment), so one key per round count serves every request of that count, with no template and no corrections.
+ * A request's assignment is five elements: 1, a, b, result, 0; result = c_a a + c_b b with two coefficients that depend on `steps`
+ * alone.  steps above ZKG16_FIBONACCI_STEPS_MAX: ZKG16_ERR_BAD_ARG in every entry below.
+ * zkg16_fibonacci_results_host (no ctx, no GPU): a, b = k u64; out[4 i ..] = the `result` input of zkg16_circuit_fibonacci(a[i], b[i],
+ * steps) as Montgomery limbs — the value in Fr, by the additive chain, request by request: the reference the kernel is tested against.
+ * k == 0 or a null pointer: ZKG16_ERR_BAD_ARG, nothing written.
+ * zkg16_r1cs_fibonacci: the circuit's matrices as an r1cs handle with no request in hand — the arrays of zkg16_circuit_fibonacci +
+ * zkg16_circuit_export for any (a, b), built by the host mirror and uploaded (steps + 1 rows: a kernel would not pay).
+ * zkg16_witness_fibonacci_batch: k assignments in ONE upload (16 bytes of input and one address per request), one launch and one
+ * synchronisation; handle i holds byte for byte the assignment zkg16_circuit_export gives for (a[i], b[i], steps) and is usable
+ * wherever a witness handle is.  The assignments share one allocation, returned when the last handle is freed.  public_inputs
+ * (nullable): k x 12 limbs, a | b | result.  timings_ms (nullable, 3): host coefficients, device (upload + kernel + read-back), whole
+ * call.  All or nothing: on any error no handle is registered and nothing is written. */
+#define ZKG16_FIBONACCI_STEPS_MAX ((size_t)0x0FFFFFFF) /* 2^28 - 1 */
+ZKG16_API int zkg16_fibonacci_results_host(size_t steps, const uint64_t *a, const uint64_t *b, size_t k, uint64_t *out /* k x 4 */);
+ZKG16_API int zkg16_r1cs_fibonacci(zkg16_ctx *ctx, size_t steps, uint64_t *r1cs_handle);
+ZKG16_API int zkg16_witness_fibonacci_batch(zkg16_ctx *ctx, size_t steps, const uint64_t *a, const uint64_t *b, size_t k,
+                                            uint64_t *witness_handles, uint64_t *public_inputs, float *timings_ms);
+/* k requests of the Fibonacci handler on one resident key: a, b (k u64 each) in, k proofs and their public inputs out.  Proof i is byte
+ * for byte zkg16_prove_resident's on the assignment above with (r + 4i, s + 4i).  One lane.  The work goes in sub-batches sized as
+ * zkg16_prove_batch's, capped by option "batch_max"; per sub-batch the batched assignment pass, then the batched proof, after which its
+ * assignments are released — no witness handle ever exists.  Checked before any work, in this order: k == 0 or a null pointer
+ * (ZKG16_ERR_BAD_ARG), an unknown handle (ZKG16_ERR_BAD_HANDLE), a shard key (ZKG16_ERR_UNSUPPORTED), a key that does not fit the
+ * r1cs handle or an r1cs handle whose dimensions are not those of the FibonacciCircuit of `steps` (ZKG16_ERR_BAD_ARG).  On any error
+ * nothing is written (proofs and public inputs are staged until every sub-batch has succeeded).  public_inputs (nullable): k x 12,
+ * a | b | result.  timings_ms (nullable, 4): host coefficients, assignment passes (device), proving (zkg16_last_timings[9] summed),
+ * whole call.  zkg16_last_timings / zkg16_last_term_counts describe the batch as after zkg16_prove_batch. */
+ZKG16_API int zkg16_prove_fibonacci_batch(zkg16_ctx *ctx, uint64_t pk_handle, uint64_t r1cs_handle, size_t steps, const uint64_t *a,
+                                          const uint64_t *b, size_t k, const uint64_t *r, const uint64_t *s, uint64_t *proofs_out /* k x 48 */,
+                                          uint8_t *inf_out /* k x 3 */, uint64_t *public_inputs, float *timings_ms);
 /* ---- does an assignment satisfy its R1CS?  (A z)_i * (B z)_i == (C z)_i for every constraint row i < num_constraints, compared as fully
  * reduced residues.  The proving calls prove whatever they are handed: an unsatisfied assignment gives a well-formed proof that no
  * verifier accepts (arkworks' prover debug_asserts cs.is_satisfied(); prime_snark.rs:123-128 asserts it on every request).  The witness

@@ -141,6 +141,10 @@ SIGNATURES = {
     "zkg16_matrix_sponge_states_batch": (C.c_int, [sz, vp, vp, sz, C.c_int, vp, vp]),
     "zkg16_witness_matrix_batch": (C.c_int, [ctxp, sz, vp, vp, sz, vp, vp, vp]),
     "zkg16_prove_matrix_batch": (C.c_int, [ctxp, H, H, sz, vp, vp, sz, vp, vp, vp, vp, vp, vp]),
+    "zkg16_fibonacci_results_host": (C.c_int, [sz, vp, vp, sz, vp]),
+    "zkg16_r1cs_fibonacci": (C.c_int, [ctxp, sz, C.POINTER(H)]),
+    "zkg16_witness_fibonacci_batch": (C.c_int, [ctxp, sz, vp, vp, sz, vp, vp, vp]),
+    "zkg16_prove_fibonacci_batch": (C.c_int, [ctxp, H, H, sz, vp, vp, sz, vp, vp, vp, vp, vp, vp]),
     "zkg16_ntt": (C.c_int, [ctxp, u64p, sz, C.c_int, C.c_int]),
     "zkg16_msm_g1": (C.c_int, [ctxp, vp, vp, vp, sz, u64p, u8p]),
     "zkg16_msm_g2": (C.c_int, [ctxp, vp, vp, vp, sz, u64p, u8p]),

@@ -307,6 +307,21 @@ def fibonacci_circuit_handle(a, b, steps):
     return CircuitHandle(h)
 
 
+def fibonacci_results_host(steps, a, b):
+    """The `result` public input of fibonacci_circuit(a[i], b[i], steps) for k requests of one round count, by the mirror's additive
+    chain in Fr (zkg16_fibonacci_results_host; no GPU): a, b [k] u64 -> [k, 4] Montgomery.  What the batched assignment kernel of
+    Device.witness_fibonacci_batch is tested against."""
+    a = np.ascontiguousarray(a, dtype=np.uint64).reshape(-1)
+    b = np.ascontiguousarray(b, dtype=np.uint64).reshape(-1)
+    if a.shape != b.shape:
+        raise ValueError("fibonacci_results_host: one b per a")
+    out = np.zeros((a.shape[0], 4), dtype=np.uint64)
+    rc = _lib.load().zkg16_fibonacci_results_host(steps, a.ctypes.data, b.ctypes.data, a.shape[0], out.ctypes.data)
+    if rc:
+        raise Zkg16Error(rc, "zkg16_fibonacci_results_host")
+    return out
+
+
 def prime_search(x, i_max):
     """The prime handler's native search (backend/prime_snark.rs:57-70): first j <= i_max whose hash(x + j) mod 2^20 passes the
     Fermat test -> dict(found, j, prime, digest) (zkg16_prime_search)."""

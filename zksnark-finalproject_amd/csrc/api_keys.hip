@@ -566,6 +566,39 @@ int zkg16_r1cs_matrix(zkg16_ctx *ctx, size_t n, uint64_t *r1cs_handle) {
     ZK_API_END(ctx)
 }
 
+// The FibonacciCircuit's R1CS of `steps` rounds with no request in hand: the matrices do not depend on (a, b), so the host mirror is
+// synthesized for (0, 0) and its arrays loaded as zkg16_r1cs_load would — steps + 1 rows of at most three terms, a few hundred KB at
+// the largest round counts in use, written once per round count: nothing a kernel would be faster at.
+int zkg16_r1cs_fibonacci(zkg16_ctx *ctx, size_t steps, uint64_t *r1cs_handle) {
+    if (!ctx || !r1cs_handle || steps > ZKG16_FIBONACCI_STEPS_MAX) return ZKG16_ERR_BAD_ARG;
+    zkg16_circuit *raw = nullptr;
+    try {                               // the synthesis needs neither the ctx nor the device
+        if (const int st = zkg16_circuit_fibonacci(0, 0, steps, &raw)) return st;
+    } catch (const std::bad_alloc &) {
+        return ZKG16_ERR_OOM;
+    }
+    std::unique_ptr<zkg16_circuit, void (*)(zkg16_circuit *)> c(raw, zkg16_circuit_free);
+    size_t ni = 0, nw = 0, nc = 0, nnz[3] = {0, 0, 0};
+    if (zkg16_circuit_dims(c.get(), &ni, &nw, &nc, nnz) != ZKG16_OK) return ZKG16_ERR_BAD_ARG;
+    ZK_API_BEGIN(ctx)
+    std::vector<uint64_t> rp[3], cf[3], z((ni + nw) * 4);
+    std::vector<uint32_t> col[3];
+    uint64_t *prp[3], *pcf[3];
+    uint32_t *pcol[3];
+    for (int m = 0; m < 3; m++) {
+        rp[m].resize(nc + 1);
+        col[m].resize(nnz[m] ? nnz[m] : 1);
+        cf[m].resize(4 * (nnz[m] ? nnz[m] : 1));
+        prp[m] = rp[m].data(); pcol[m] = col[m].data(); pcf[m] = cf[m].data();
+    }
+    if (zkg16_circuit_export(c.get(), prp, pcol, pcf, z.data()) != ZKG16_OK) return ZKG16_ERR_BAD_ARG;
+    const uint64_t *crp[3] = {prp[0], prp[1], prp[2]}, *ccf[3] = {pcf[0], pcf[1], pcf[2]};
+    const uint32_t *ccol[3] = {pcol[0], pcol[1], pcol[2]};
+    const int rc = load_r1cs(ctx, crp, ccol, ccf, ni, nc, ni + nw, r1cs_handle);      // synchronises the stream: the vectors may go
+    if (rc) return rc;
+    ZK_API_END(ctx)
+}
+
 // The PrimeCircuit of candidate (x, j) on the device (prime_device.hip): handles as zkg16_r1cs_load / zkg16_witness_load would return
 // for the arrays of zkg16_circuit_prime + zkg16_circuit_export, without synthesising or uploading them.  The template is uploaded on
 // the first call under ctx->mu (held by every entry here) and stays resident until zkg16_destroy.

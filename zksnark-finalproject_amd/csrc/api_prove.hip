@@ -828,6 +828,49 @@ int zkg16_prove_matrix_batch(zkg16_ctx *ctx, uint64_t pk_handle, uint64_t r1cs_h
     ZK_LANE_END(ctx)
 }
 
+// K requests of the Fibonacci handler on one resident key and the FibonacciCircuit's resident matrices of `steps` rounds: the two
+// coefficients of the result once per call (circuits.hip: fibonacci_coeffs), then per sub-batch the one-launch assignment pass
+// (witness.hip: fibonacci_batch_assign) and prove_batch_device, after which the sub-batch's assignments go back.  No witness handle
+// exists at any time; proofs and public inputs are staged and written only when every sub-batch has succeeded.
+int zkg16_prove_fibonacci_batch(zkg16_ctx *ctx, uint64_t pk_handle, uint64_t r1cs_handle, size_t steps, const uint64_t *a, const uint64_t *b,
+                                size_t k, const uint64_t *r, const uint64_t *s, uint64_t *proofs_out, uint8_t *inf_out, uint64_t *public_inputs,
+                                float *timings_ms) {
+    if (!a || !b || !r || !s || !proofs_out || !inf_out || k == 0 || steps > ZKG16_FIBONACCI_STEPS_MAX) return ZKG16_ERR_BAD_ARG;
+    const double t_call = now_ms();
+    ZK_LANE_BEGIN(ctx)
+    ProveHandles h;
+    if (const int st = lookup_handles(root, pk_handle, r1cs_handle, nullptr, 0, Shard::unsupported, 0, h)) return st;
+    if (h.rc->num_variables != FIBONACCI_VARS || h.rc->num_instance != FIBONACCI_INSTANCE || h.rc->num_constraints != steps + 1)
+        return ZKG16_ERR_BAD_ARG;       // not the FibonacciCircuit of this round count
+    if (k > SIZE_MAX / (48 * sizeof(uint64_t))) return ZKG16_ERR_BAD_ARG;
+    const double t_coeff = now_ms();
+    Fr ca, cb;
+    fibonacci_coeffs(steps, ca, cb);
+    const double coeff_ms = now_ms() - t_coeff;
+    const std::vector<Fr> rr = frs_from_abi(r, k), ss = frs_from_abi(s, k);
+    std::vector<uint64_t> pubs(12 * k);
+    double wit_ms = 0;
+    const float prove_ms = prove_in_passes(ctx, h.pk.get(), h.rc.get(), k, FIBONACCI_VARS * sizeof(Fr), proofs_out, inf_out,
+                                           [&](size_t off, size_t nb, uint64_t *proofs, uint8_t *infs) {
+        std::vector<std::shared_ptr<WitnessDev>> wit_refs;
+        float dev_ms = 0;
+        fibonacci_batch_assign(ctx, ca, cb, a + off, b + off, nb, wit_refs, pubs.data() + 12 * off, &dev_ms);
+        wit_ms += dev_ms;
+        std::vector<WitnessDev *> wits(nb);
+        for (size_t i = 0; i < nb; i++) wits[i] = wit_refs[i].get();
+        prove_batch_device(ctx, *h.pk, *h.rc, wits.data(), nb, rr.data() + off, ss.data() + off, proofs, infs);
+    });
+    if (prove_ms < 0) return ZKG16_ERR_UNSATISFIED;
+    if (public_inputs) memcpy(public_inputs, pubs.data(), pubs.size() * sizeof(uint64_t));
+    if (timings_ms) {
+        timings_ms[0] = (float)coeff_ms;
+        timings_ms[1] = (float)wit_ms;
+        timings_ms[2] = prove_ms;
+        timings_ms[3] = (float)(now_ms() - t_call);
+    }
+    ZK_LANE_END(ctx)
+}
+
 // K prime requests on the template key: every request's inputs first (a refused candidate ends the call before any device work),
 // then per sub-batch the batched assignment (prime_device.hip) and prove_batch_device with the per-proof corrections; the
 // assignments go back after each sub-batch.  Each request's gamma_abc_g1[0] is formed on the host.  Everything is staged and

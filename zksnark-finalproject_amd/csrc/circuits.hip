@@ -773,6 +773,20 @@ void matrix_plan_instantiate_host(const MatrixPlan &P, uint64_t *const rp[3], ui
     }
 }
 
+// fibbonaci_handler.rs:13-27 semantics: after `steps` rounds the result is f_{steps} of the (a, b) sequence, taken in Fr (the
+// reference's u128 helper overflows above 186 rounds: SURVEY.md F8)
+static Fr fibonacci_result(const Fr &fa, const Fr &fb, size_t steps) {
+    Fr x = fa, y = fb, res = steps == 0 ? Fr::zero() : fb;
+    for (size_t i = 0; i < steps; i++) { res = fp_add(x, y); x = y; y = res; }
+    return res;
+}
+// The chain is linear in (a, b): result = ca a + cb b, with ca, cb its results on (1, 0) and (0, 1) — steps = 0 gives (0, 0) and
+// steps = 1 gives (1, 1), as the chain itself does.
+void fibonacci_coeffs(size_t steps, Fr &ca, Fr &cb) {
+    ca = fibonacci_result(Fr::one(), Fr::zero(), steps);
+    cb = fibonacci_result(Fr::zero(), Fr::one(), steps);
+}
+
 }  // namespace zk
 
 extern "C" {
@@ -816,10 +830,7 @@ int zkg16_circuit_fibonacci(uint64_t a, uint64_t b, size_t steps, zkg16_circuit 
     auto c = new (std::nothrow) zkg16_circuit();
     if (!c) return ZKG16_ERR_OOM;
     Circuit &cs = c->add_segment(0);
-    const Fr fa = fr_from_u64(a), fb = fr_from_u64(b);
-    // fibbonaci_handler.rs:13-27 semantics: after `steps` rounds the result is f_{steps} of the (a, b) sequence
-    Fr x = fa, y = fb, res = steps == 0 ? Fr::zero() : fb;
-    for (size_t i = 0; i < steps; i++) { res = fp_add(x, y); x = y; y = res; }
+    const Fr fa = fr_from_u64(a), fb = fr_from_u64(b), res = fibonacci_result(fa, fb, steps);
     Lc f2 = cs.new_input(fa), f1 = cs.new_input(fb), saved = cs.new_input(res);
     Lc fi = cs.new_witness(Fr::zero());
     for (size_t i = 0; i < steps; i++) {
@@ -830,6 +841,20 @@ int zkg16_circuit_fibonacci(uint64_t a, uint64_t b, size_t steps, zkg16_circuit 
     }
     cs.enforce_equal(fi, saved);
     *out = c;
+    return ZKG16_OK;
+}
+
+// The `result` inputs of k requests of one round count, each by the chain above: what the batched assignment kernel (witness.hip),
+// which forms ca a + cb b instead, is tested against.  Staged: a failing allocation leaves `out` alone.
+int zkg16_fibonacci_results_host(size_t steps, const uint64_t *a, const uint64_t *b, size_t k, uint64_t *out) {
+    if (!a || !b || !out || k == 0 || steps > ZKG16_FIBONACCI_STEPS_MAX || k > SIZE_MAX / sizeof(Fr)) return ZKG16_ERR_BAD_ARG;
+    try {
+        std::vector<Fr> res(k);
+        for (size_t i = 0; i < k; i++) res[i] = fibonacci_result(fr_from_u64(a[i]), fr_from_u64(b[i]), steps);
+        memcpy(out, res.data(), k * sizeof(Fr));
+    } catch (const std::bad_alloc &) {
+        return ZKG16_ERR_OOM;
+    }
     return ZKG16_OK;
 }
 

@@ -566,6 +566,18 @@ void sponge_hash_batch_device(zkg16_ctx *ctx, int form, const uint64_t *data, si
 void matrix_batch_assign(zkg16_ctx *ctx, const MatrixBatchChains &c, const uint64_t *a, const uint64_t *b,
                          std::vector<std::shared_ptr<WitnessDev>> &out, float *dev_ms);
 
+// K Fibonacci requests of one round count in one pass (zkg16_witness_fibonacci_batch, zkg16_prove_fibonacci_batch).  The
+// FibonacciCircuit of `steps` has 4 instance variables, 1 witness and steps + 1 rows; its result is linear in the inputs,
+// result = ca a + cb b.  fibonacci_coeffs (circuits.hip, host): ca, cb by the mirror's additive chain on (1, 0) and (0, 1).
+// fibonacci_batch_assign (witness.hip): on ctx->stream (a lane's, or the root's under its mutex) one upload of a | b and the z addresses
+// out of the ctx's pinned staging, one launch, the public inputs read back, one synchronisation; the assignments share one allocation
+// (WitnessDev::backing).  pubs: k x 12 limbs (a | b | result), written after the synchronisation.  Throws HipError (the stream
+// drained) / std::bad_alloc.
+constexpr size_t FIBONACCI_VARS = 5, FIBONACCI_INSTANCE = 4;
+void fibonacci_coeffs(size_t steps, Fr &ca, Fr &cb);
+void fibonacci_batch_assign(zkg16_ctx *ctx, const Fr &ca, const Fr &cb, const uint64_t *a, const uint64_t *b, size_t k,
+                            std::vector<std::shared_ptr<WitnessDev>> &out, uint64_t *pubs, float *dev_ms);
+
 // An assignment that becomes valid in parts while its proof is already running (prove_device): produce(k) blocks until part k
 // can be made, then queues on ctx->stream whatever writes it; part_of[i] = the part variable i (and the trailing r, s, -rs slots)
 // belongs to.

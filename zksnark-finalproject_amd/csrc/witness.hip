@@ -439,6 +439,36 @@ __global__ void __launch_bounds__(64) wit_chain_batch_kernel(ChainBatchArgs g) {
     }
 }
 
+// ---- K Fibonacci requests of one round count (zkg16_witness_fibonacci_batch): one lane per request.  The assignment is 1 | a | b |
+// result | 0, and result = ca a + cb b with the two coefficients the host took from the mirror's chain (fibonacci_coeffs), so a lane
+// costs four field products and one addition whatever `steps` is.  Every operation reduces fully, so the sum is the canonical value
+// the host chain ends on.  The lane writes through the table of the K z pointers and leaves a | b | result in `pub` as well.
+struct FibBatchArgs {
+    const uint64_t *ab;             // k x (a, b)
+    Fr *const *z;                   // k
+    Fr *pub;                        // k x 3
+    Fr ca, cb;
+    size_t k;
+};
+__global__ void __launch_bounds__(64) wit_fibonacci_batch_kernel(FibBatchArgs g) {
+    for (size_t req = (size_t)blockIdx.x * blockDim.x + threadIdx.x; req < g.k; req += (size_t)gridDim.x * blockDim.x) {
+        Fr v[2];
+        for (int i = 0; i < 2; i++) {
+            const uint64_t x = g.ab[2 * req + i];
+            v[i] = Fr::zero();
+            v[i].l[0] = (uint32_t)x;
+            v[i].l[1] = (uint32_t)(x >> 32);
+            v[i] = fp_to_mont(v[i]);
+        }
+        const Fr res = fp_add(fp_mul(g.ca, v[0]), fp_mul(g.cb, v[1]));
+        Fr *z = g.z[req], *pub = g.pub + 3 * req;
+        st32(z, Fr::one());
+        st32(z + 1, v[0]); st32(z + 2, v[1]); st32(z + 3, res);
+        st32(z + 4, Fr::zero());
+        st32(pub, v[0]); st32(pub + 1, v[1]); st32(pub + 2, res);
+    }
+}
+
 // part_of[i] = the part of a streamed assignment in which variable i becomes valid: 0 = what needs only a and b (the constant,
 // a, b, the zeros, the products; also the three trailing r / s / -rs slots of the z-side scalar vector), 1 + s = the S-box
 // values of the permutations of slice s of every sponge, the last part also the three hashes.
@@ -791,6 +821,63 @@ void matrix_batch_assign(zkg16_ctx *ctx, const MatrixBatchChains &c, const uint6
     out = std::move(wits);
 }
 
+// The k assignments of one round count on ctx->stream, under ctx's mutex: a | b and the z addresses go up in one copy out of the
+// ctx's pinned staging, one launch, the k x 3 public inputs come back, one synchronisation.  The assignments share one allocation
+// (WitnessDev::backing).  `pubs` (nullable) is written only when all of it succeeded; when this throws the stream has been drained.
+void fibonacci_batch_assign(zkg16_ctx *ctx, const Fr &ca, const Fr &cb, const uint64_t *a, const uint64_t *b, size_t k,
+                            std::vector<std::shared_ptr<WitnessDev>> &out, uint64_t *pubs, float *dev_ms) {
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t ab_bytes = up(k * 2 * sizeof(uint64_t)), tab_bytes = up(k * sizeof(Fr *)), pub_bytes = k * 3 * sizeof(Fr);
+    const size_t cap = ctx->opt.matrix_batch_grid > 0 ? (size_t)ctx->opt.matrix_batch_grid : 65535;
+    mbatch_staging_ensure(ctx, ab_bytes + tab_bytes + pub_bytes);
+    auto backing = std::make_shared<DevBuf>(k * FIBONACCI_VARS * sizeof(Fr));
+    std::vector<std::shared_ptr<WitnessDev>> wits(k);
+    for (size_t i = 0; i < k; i++) {
+        wits[i] = std::make_shared<WitnessDev>();
+        wits[i]->n = FIBONACCI_VARS;
+        wits[i]->backing = backing;
+        wits[i]->z.p = backing->as<Fr>() + i * FIBONACCI_VARS;
+        wits[i]->z.bytes = FIBONACCI_VARS * sizeof(Fr);
+    }
+    uint8_t *hs = static_cast<uint8_t *>(ctx->mbatch_host), *ds = ctx->mbatch_dev.as<uint8_t>();
+    uint64_t *h_ab = reinterpret_cast<uint64_t *>(hs);
+    Fr **h_tab = reinterpret_cast<Fr **>(hs + ab_bytes);
+    for (size_t i = 0; i < k; i++) {
+        h_ab[2 * i] = a[i];
+        h_ab[2 * i + 1] = b[i];
+        h_tab[i] = wits[i]->z.as<Fr>();
+    }
+    hipEvent_t e0, e1;
+    ZK_HIP(hipEventCreate(&e0));
+    struct EvGuard { hipEvent_t e; ~EvGuard() { (void)hipEventDestroy(e); } } g0{e0};
+    ZK_HIP(hipEventCreate(&e1));
+    EvGuard g1{e1};
+    struct Drain { zkg16_ctx *c; bool ok = false; ~Drain() { if (!ok) (void)hipStreamSynchronize(c->stream); } } drain{ctx};
+    ZK_HIP(hipEventRecord(e0, ctx->stream));
+    ZK_HIP(hipMemcpyAsync(ds, hs, ab_bytes + k * sizeof(Fr *), hipMemcpyHostToDevice, ctx->stream));
+    {
+        FibBatchArgs g;
+        g.ab = reinterpret_cast<const uint64_t *>(ds);
+        g.z = reinterpret_cast<Fr *const *>(ds + ab_bytes);
+        g.pub = reinterpret_cast<Fr *>(ds + ab_bytes + tab_bytes);
+        g.ca = ca; g.cb = cb;
+        g.k = k;
+        const size_t bx = (k + 63) / 64;
+        ScopedKernelTimer kt(ctx, "wit_fibonacci_batch_kernel", (double)k);
+        hipLaunchKernelGGL(wit_fibonacci_batch_kernel, dim3((unsigned)(bx < cap ? bx : cap)), dim3(64), 0, ctx->stream, g);
+        ZK_HIP(hipGetLastError());
+    }
+    ZK_HIP(hipMemcpyAsync(hs + ab_bytes + tab_bytes, ds + ab_bytes + tab_bytes, pub_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    ZK_HIP(hipEventRecord(e1, ctx->stream));
+    ZK_HIP(hipStreamSynchronize(ctx->stream));      // the staging is free again, and the assignments are whole
+    drain.ok = true;
+    float ms = 0;
+    ZK_HIP(hipEventElapsedTime(&ms, e0, e1));
+    if (dev_ms) *dev_ms = ms;
+    if (pubs) memcpy(pubs, hs + ab_bytes + tab_bytes, pub_bytes);
+    out = std::move(wits);
+}
+
 }  // namespace zk
 #endif  // ZKG16_HOST_ONLY
 
@@ -881,6 +968,51 @@ int zkg16_witness_matrix_batch(zkg16_ctx *ctx, size_t n, const uint64_t *a, cons
         if (public_inputs) memcpy(public_inputs, hashes.data(), 12 * k * sizeof(uint64_t));
         if (timings_ms) {
             timings_ms[0] = (float)mc.ms;
+            timings_ms[1] = dev_ms;
+            timings_ms[2] = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
+        }
+    } catch (const HipError &e) {
+        char buf[512];
+        snprintf(buf, sizeof buf, "%s failed: %s (%s:%d)", e.what, hipGetErrorString(e.err), e.file, e.line);
+        ctx->last_error = buf;
+        (void)hipGetLastError();
+        return e.err == hipErrorOutOfMemory ? ZKG16_ERR_OOM : ZKG16_ERR_HIP;
+    } catch (const std::bad_alloc &) {
+        return ZKG16_ERR_OOM;
+    }
+    return ZKG16_OK;
+}
+
+// K FibonacciCircuit assignments of one round count in one upload, one launch and one synchronisation: handle i carries the bytes
+// zkg16_circuit_export gives for (a[i], b[i], steps).  The two coefficients are formed before the ctx is locked; all or nothing: on
+// any error no handle is registered and nothing is written.  timings_ms (nullable, 3): host coefficients, device, whole call.
+int zkg16_witness_fibonacci_batch(zkg16_ctx *ctx, size_t steps, const uint64_t *a, const uint64_t *b, size_t k, uint64_t *witness_handles,
+                                  uint64_t *public_inputs, float *timings_ms) {
+    if (!ctx || !a || !b || !witness_handles || k == 0 || steps > ZKG16_FIBONACCI_STEPS_MAX) return ZKG16_ERR_BAD_ARG;
+    if (k > SIZE_MAX / (FIBONACCI_VARS * sizeof(Fr))) return ZKG16_ERR_BAD_ARG;
+    const auto t_call = std::chrono::steady_clock::now();
+    Fr ca, cb;
+    fibonacci_coeffs(steps, ca, cb);
+    const double coeff_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    try {
+        ZK_HIP(hipSetDevice(ctx->device));
+        std::vector<std::shared_ptr<WitnessDev>> wits;
+        std::vector<uint64_t> pubs(12 * k);
+        float dev_ms = 0;
+        fibonacci_batch_assign(ctx, ca, cb, a, b, k, wits, pubs.data(), &dev_ms);
+        const uint64_t first = ctx->next_handle.fetch_add(k);
+        size_t put = 0;
+        try {
+            for (; put < k; put++) ctx->wits.put(first + put, std::move(wits[put]));
+        } catch (const std::bad_alloc &) {          // all or nothing: what was registered is taken back
+            for (size_t i = 0; i < put; i++) ctx->wits.erase(first + i);
+            return ZKG16_ERR_OOM;
+        }
+        for (size_t i = 0; i < k; i++) witness_handles[i] = first + i;
+        if (public_inputs) memcpy(public_inputs, pubs.data(), 12 * k * sizeof(uint64_t));
+        if (timings_ms) {
+            timings_ms[0] = (float)coeff_ms;
             timings_ms[1] = dev_ms;
             timings_ms[2] = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
         }

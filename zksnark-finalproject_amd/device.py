@@ -207,6 +207,13 @@ class Device:
         self._check(self.lib.zkg16_r1cs_matrix(self.ctx, n, C.byref(handle)))
         return handle.value
 
+    def r1cs_fibonacci(self, steps):
+        """The FibonacciCircuit's R1CS of `steps` rounds, which no request's (a, b) enters (zkg16_r1cs_fibonacci) -> r1cs handle: what
+        the key of prove_fibonacci_batch is set up on."""
+        handle = C.c_uint64()
+        self._check(self.lib.zkg16_r1cs_fibonacci(self.ctx, steps, C.byref(handle)))
+        return handle.value
+
     def r1cs_prime(self, x, j):
         """The PrimeCircuit's R1CS for candidate (x, j) from the template resident on the device (zkg16_r1cs_prime) -> r1cs handle."""
         handle = C.c_uint64()
@@ -339,6 +346,24 @@ class Device:
         ms = (C.c_float * 3)()
         self._check(self.lib.zkg16_witness_matrix_batch(self.ctx, n, _ptr(a), _ptr(b), k, _ptr(handles), _ptr(pub), C.addressof(ms)))
         return handles, pub, dict(host_sponges_ms=float(ms[0]), device_ms=float(ms[1]), call_ms=float(ms[2]))
+
+    @staticmethod
+    def _fibonacci_batch(what, a, b):
+        a, b = _u64(a).reshape(-1), _u64(b).reshape(-1)
+        if a.shape != b.shape:
+            raise ValueError(what + ": one b per a")
+        return a, b, a.shape[0]
+
+    def witness_fibonacci_batch(self, steps, a, b):
+        """The FibonacciCircuit's assignments of k requests of one round count, a and b [k] u64, built in one device pass
+        (zkg16_witness_fibonacci_batch) -> (witness handles [k], public inputs [k, 3, 4] = a, b, result, dict of ms: host coefficients
+        / device / whole call).  Handle i holds what circuit_load of fibonacci_circuit(a[i], b[i], steps) would; each is freed on its own."""
+        a, b, k = self._fibonacci_batch("witness_fibonacci_batch", a, b)
+        handles = np.zeros(k, dtype=np.uint64)
+        pub = np.zeros((k, 3, 4), dtype=np.uint64)
+        ms = (C.c_float * 3)()
+        self._check(self.lib.zkg16_witness_fibonacci_batch(self.ctx, steps, _ptr(a), _ptr(b), k, _ptr(handles), _ptr(pub), C.addressof(ms)))
+        return handles, pub, dict(host_coeffs_ms=float(ms[0]), device_ms=float(ms[1]), call_ms=float(ms[2]))
 
     def poseidon_hash_batch(self, elems):
         """k Poseidon hashes in one call (zkg16_poseidon_hash_batch): elems [k, n, 4] Montgomery Fr -> [k, 4], row i the bytes of
@@ -577,6 +602,24 @@ class Device:
         self._check(self.lib.zkg16_prove_matrix_batch(self.ctx, pk_h, r1cs_h, n, _ptr(a), _ptr(b), k, _ptr(rs), _ptr(ss), _ptr(proofs), _ptr(inf),
                                                       _ptr(pub), C.addressof(ms)))
         return proofs, inf, pub, dict(host_sponges_ms=float(ms[0]), witness_ms=float(ms[1]), prove_ms=float(ms[2]), call_ms=float(ms[3]))
+
+    def prove_fibonacci_batch(self, pk_h, r1cs_h, steps, a, b, rs, ss):
+        """k Fibonacci-handler requests of one round count on one resident key, a and b [k] u64, rs / ss [k, 4]: assignments and proofs
+        in batched device passes (zkg16_prove_fibonacci_batch) -> (proofs [k, 48], inf [k, 3], public inputs [k, 3, 4] = a, b, result,
+        dict of ms).  pk_h: a key set up on r1cs_fibonacci(steps) = r1cs_h.  Proof i is byte-identical to prove_resident on the
+        circuit_load handles of fibonacci_circuit(a[i], b[i], steps) with (rs[i], ss[i])."""
+        a, b, k = self._fibonacci_batch("prove_fibonacci_batch", a, b)
+        rs = _u64(rs).reshape(-1, 4)
+        ss = _u64(ss).reshape(-1, 4)
+        if rs.shape[0] != k or ss.shape[0] != k:
+            raise ValueError("prove_fibonacci_batch: one r and one s per request")
+        proofs = np.zeros((k, 48), dtype=np.uint64)
+        inf = np.zeros((k, 3), dtype=np.uint8)
+        pub = np.zeros((k, 3, 4), dtype=np.uint64)
+        ms = (C.c_float * 4)()
+        self._check(self.lib.zkg16_prove_fibonacci_batch(self.ctx, pk_h, r1cs_h, steps, _ptr(a), _ptr(b), k, _ptr(rs), _ptr(ss), _ptr(proofs),
+                                                         _ptr(inf), _ptr(pub), C.addressof(ms)))
+        return proofs, inf, pub, dict(host_coeffs_ms=float(ms[0]), witness_ms=float(ms[1]), prove_ms=float(ms[2]), call_ms=float(ms[3]))
 
     def prove_prime_batch(self, pk_h, r1cs_h, corr, gamma_abc0, xs, js, rs, ss, public_inputs=True):
         """k prime requests (xs[i], js[i]) on the template key in batched device passes (zkg16_prove_prime_batch).  pk_h: the key

@@ -2,6 +2,8 @@
     prove_matrix     src/arkworks/backend/matrix_proof.rs:94-166   (POST /api/matrix_prove/prove)
     prove_matrices   K such requests of one size under one key, in batched device passes (no counterpart upstream)
     prove_fibonacci  src/arkworks/backend/fibbonaci_handler.rs:98-145
+    prove_fibonaccis / verify_fibonaccis  K Fibonacci requests of one round count under ONE key, in batched device passes (no
+                     counterpart upstream)
     prove_prime / verify_prime  src/arkworks/backend/prime_snark.rs:49-146, 165-206
     prove_primes     K prime requests under one trapdoor on ONE template key, in batched device passes (no counterpart upstream)
     verify_primes    K such proofs checked together under the ONE extended key of their trapdoor (no counterpart upstream)
@@ -281,6 +283,90 @@ def prove_fibonacci(dev, a, b, num_of_rounds, seed=42, keep_key=False, check_on_
                 num_constraints=circ.num_constraints, num_variables=circ.num_instance,
                 fib_number=[wire.encode_hash(x) for x in circ.public_inputs][-1], pvk=wire.encode_pvk(out["vk"]), vk=wire.encode_vk(out["vk"]),
                 _detail=out, _circuit=circ), out, check_on_device)
+
+
+def fibonacci_key(dev, num_of_rounds, rng):
+    """The key every Fibonacci request of one round count shares: the circuit's matrices depend on the round count alone
+    (Device.r1cs_fibonacci), so prove_fibonacci's draws from rng in its order (trapdoor, generators) and one setup give the key
+    prove_fibonacci makes for any (a, b) -> dict(ph, rh, vk, setup_time).  The caller frees ph and rh."""
+    trap, g1, g2 = _draw_key(rng)
+    with contextlib.ExitStack() as stack:
+        rh = dev.r1cs_fibonacci(num_of_rounds)
+        stack.callback(dev.r1cs_free, rh)
+        t0 = time.perf_counter()
+        ph, vk = dev.setup_resident(rh, 4, trap, g1, g2)
+        setup_time = time.perf_counter() - t0
+        stack.pop_all()                 # both handles are the caller's from here
+    return dict(ph=ph, rh=rh, vk=vk, setup_time=setup_time)
+
+
+def prove_fibonaccis(dev, requests, num_of_rounds, seed=42, key=None, check_on_device=False):
+    """K requests of the Fibonacci handler of one round count, requests = [(a, b), ...], under ONE key, assignments and proofs in
+    batched device passes (Device.prove_fibonacci_batch).  The key is set up once from `seed` with prove_fibonacci's draws (then r,
+    s per request), so request 0 is prove_fibonacci's proof and key for that seed, byte for byte; or it is passed in as key=
+    (fibonacci_key's dict), which stays the caller's.  The key's two encodings are made once.
+    -> a list of prove_fibonacci's fields per request; proving_time is the batch's divided by K.
+    check_on_device: the assignments are built as handles (Device.witness_fibonacci_batch), checked together
+    (Device.r1cs_check_batch) and proved with Device.prove_batch — the same proof bytes — and every record gets "satisfied"."""
+    k = len(requests)
+    if k == 0:
+        raise ValueError("prove_fibonaccis: no requests")
+    a = np.array([int(q[0]) for q in requests], dtype=np.uint64)
+    b = np.array([int(q[1]) for q in requests], dtype=np.uint64)
+    rng = random.Random(seed)
+    own = key is None
+    with contextlib.ExitStack() as stack:
+        if own:
+            key = fibonacci_key(dev, num_of_rounds, rng)
+            stack.callback(dev.r1cs_free, key["rh"])
+            stack.callback(dev.pk_free, key["ph"])
+        rs, ss = _draw_rs_batch(rng, k)
+        t0 = time.perf_counter()
+        verdicts, check_time = None, 0.0
+        if check_on_device:
+            whs, pubs, ms = dev.witness_fibonacci_batch(num_of_rounds, a, b)
+            for wh in whs:
+                stack.callback(dev.witness_free, int(wh))
+            tc = time.perf_counter()
+            verdicts = dev.r1cs_check_batch(key["rh"], whs)
+            check_time = time.perf_counter() - tc
+            proofs, inf = dev.prove_batch(key["ph"], key["rh"], whs, rs, ss)
+        else:
+            proofs, inf, pubs, ms = dev.prove_fibonacci_batch(key["ph"], key["rh"], num_of_rounds, a, b, rs, ss)
+        proving_time = time.perf_counter() - t0 - check_time
+    vk = key["vk"]
+    vk_b64, pvk_b64 = wire.encode_vk(vk), wire.encode_pvk(vk)
+    out = []
+    for i in range(k):
+        circ = _DeviceCircuit(4, 1, num_of_rounds + 1, pubs[i])
+        rec = dict(proof=wire.encode_proof(proofs[i], inf[i]), proving_time=proving_time / k, setup_time=key["setup_time"] if own else 0.0,
+                   num_constraints=circ.num_constraints, num_variables=circ.num_instance, fib_number=wire.encode_hash(pubs[i][2]),
+                   pvk=pvk_b64, vk=vk_b64, _circuit=circ,
+                   _detail=dict(proof=proofs[i], inf=inf[i], vk=vk, r=rs[i], s=ss[i], public_inputs=pubs[i], ms=ms))
+        if verdicts is not None:
+            rec["satisfied"] = verdicts[i][0] == 0
+        out.append(rec)
+    return out
+
+
+def verify_fibonaccis(vk, claims, proofs_b64, dev=None):
+    """The Fibonacci verify handler (fibbonaci_handler.rs:118-145) for K proofs under one key, checked together: claims = [(a, b,
+    fib_number), ...] with fib_number the base64 string the prove mirrors return.  The three public inputs a, b, fib_number are built
+    per proof and the batch is answered by verify_proofs (with dev: Device.verify_batch_wire and its thresholds)
+    -> {valid: [K bools], verifying_time, decode_time}.  A claim whose a or b is no u64, or whose fib_number does not decode to 32
+    bytes, is valid=False for that entry only."""
+    if len(claims) != len(proofs_b64):
+        raise ValueError("verify_fibonaccis: one claim per proof")
+    pubs = []
+    for a, b, fib in claims:
+        try:
+            a, b = int(a), int(b)
+            if not (0 <= a < 1 << 64 and 0 <= b < 1 << 64) or len(base64.standard_b64decode(fib)) != 32:
+                raise ValueError("verify_fibonaccis: not a claim")
+            pubs.append(np.stack([_fr_mont(a), _fr_mont(b), np.asarray(wire.decode_hash(fib), dtype=np.uint64)]))
+        except (ValueError, TypeError):
+            pubs.append(np.zeros((0, 4), dtype=np.uint64))       # the wrong shape: verify_proofs answers invalid for this entry
+    return verify_proofs(vk, pubs, proofs_b64, dev=dev)
 
 
 def prove_prime(dev, x, i, seed=7, keep_key=False, check_satisfied=False, check_on_device=False):
