@@ -682,7 +682,7 @@ ZKG16_API int zkg16_last_acc_waves(zkg16_ctx *ctx, int waves[3]);
 /* Waves of the bucket-accumulation kernels one SIMD holds at once (their register use decides): [0] G1, [1] G2.  The grid of an
  * accumulation may be sized for more waves per SIMD than that (zkg16_last_acc_waves): the extra ones run as a second round. */
 ZKG16_API int zkg16_acc_resident_waves(zkg16_ctx *ctx, int waves[2]);
-/* What the last zkg16_msm_g1 / zkg16_msm_g2 / zkg16_bench_msm call on this ctx ran as (diagnostics for tests):
+/* What the last zkg16_msm_g1 / zkg16_msm_g2 / zkg16_bench_msm / zkg16_diag_msm_tabled call on this ctx ran as (diagnostics for tests):
  * out = { c, nwin, entries, seg_len, fixup_items, fixup_chains, bit_sliced, two_level_k }.  c: window bits; nwin: windows;
  * entries: length of the sorted (scalar, window) term list; seg_len: entries per lane the accumulation kernel read; fixup_items /
  * fixup_chains: work items queued for spilled buckets longer than four segments (one per 1024 segments), and how many of those
@@ -715,6 +715,21 @@ ZKG16_API int zkg16_diag_bucket_sort(zkg16_ctx *ctx, const uint32_t *codes, size
 ZKG16_API int zkg16_diag_term_list(zkg16_ctx *ctx, const uint64_t *scalars_canonical, size_t n, int batch, int window_bits, int tabled,
                                    const uint8_t *mask, int mask_mode, uint32_t plan_out[4], uint32_t *entries_xy, size_t entries_cap,
                                    uint32_t *offsets, size_t offsets_cap, uint64_t *length);
+/* One MSM on window tables, run as a proof runs one query of a key that carries them (diagnostics for tests).  group: 1 = G1, 2 = G2;
+ * bases[n] with their infinity mask (nullable) as zkg16_msm_g1 takes them; scalars[batch][n][4] canonical; window_bits 2..24, taken as
+ * they are; stride_mode 1 = packed table entries, 2 = padded to whole cache lines (zkg16_table_layout); last_of_proof 0 | 1 = what the
+ * proof sets for the MSM whose reduction is its tail.  Builds the table [254 / c + 1][n] with the routine zkg16_pk_precompute calls,
+ * the tabled term list of the batch (vector v = window v of one plan) in the workspace of zkg16_msm_g1, accumulates and reduces on
+ * that entry's slot and combines every vector's window on the host: out_affine[batch][12 | 24], out_inf[batch].  table_out /
+ * table_inf (both or neither): the table, read at its stride and converted to the ABI's form, table_out[levels][n][12 | 24] and
+ * table_inf[levels][n].  zkg16_last_msm_state reports this call, nwin reading as batch.  n == 0: every output is the point at
+ * infinity, no table is written, the state is { c, batch, 0, ... }.  A null pointer (inf excepted), one table pointer without the
+ * other, a group outside 1..2, batch < 1, window_bits outside 2..24, a stride_mode outside 1..2, last_of_proof outside 0..1 or
+ * batch * 2^(c-1) >= 2^32: ZKG16_ERR_BAD_ARG.  batch * n * (254 / c + 1) >= 2^31: refused as the plan refuses it (ZKG16_ERR_HIP), before
+ * anything is read.  Synchronises the ctx's stream; on any error no output is written. */
+ZKG16_API int zkg16_diag_msm_tabled(zkg16_ctx *ctx, int group, const uint64_t *bases, const uint8_t *inf, const uint64_t *scalars_canonical,
+                                    size_t n, int batch, int window_bits, int stride_mode, int last_of_proof, uint64_t *out_affine,
+                                    uint8_t *out_inf, uint64_t *table_out, uint8_t *table_inf);
 /* Which sparse product an r1cs handle's witness maps run (diagnostics; takes the handle's own lock, launches nothing):
  * out = { dict_state, ndict, perm_ok, spmv_uses }.  dict_state: 0 = the coefficient dictionary has not been tried yet (the handle
  * has run fewer than two witness maps: plain kernel, rows in natural order), 1 = the dictionary is in use (ndict distinct

@@ -43,6 +43,7 @@ SIGNATURES = {
     "zkg16_diag_bucket_sort": (C.c_int, [ctxp, vp, sz, C.c_int, C.c_int, vp, vp, C.POINTER(C.c_uint64)]),
     "zkg16_diag_term_list": (C.c_int, [ctxp, vp, sz, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.POINTER(C.c_uint32), vp, sz, vp, sz,
                                        C.POINTER(C.c_uint64)]),
+    "zkg16_diag_msm_tabled": (C.c_int, [ctxp, C.c_int, vp, vp, vp, sz, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]),
     "zkg16_r1cs_check_host": (C.c_int, [C.POINTER(vp * 3), C.POINTER(vp * 3), C.POINTER(vp * 3), sz, sz, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "zkg16_r1cs_check": (C.c_int, [ctxp, H, H, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "zkg16_r1cs_check_batch": (C.c_int, [ctxp, H, vp, sz, vp, vp]),

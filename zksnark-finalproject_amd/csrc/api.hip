@@ -510,7 +510,7 @@ int zkg16_last_acc_waves(zkg16_ctx *ctx, int waves[3]) {
     return ZKG16_OK;
 }
 
-// What the last zkg16_msm_g1 / zkg16_msm_g2 / zkg16_bench_msm on this ctx ran as (it used ws_h and slots[0] of the root; a later proof
+// What the last zkg16_msm_g1 / zkg16_msm_g2 / zkg16_bench_msm / zkg16_diag_msm_tabled on this ctx ran as (it used ws_h and slots[0] of the root; a later proof
 // on lane 0 takes them over and clears last_msm_group): out = { c, nwin, entries, seg_len, fixup_items, fixup_chains, bit_sliced, two_level_k }.  The four device words are
 // copied here, after the call has returned; the MSM itself records nothing for this.  All zero before the first such call and after such a proof.
 int zkg16_last_msm_state(zkg16_ctx *ctx, uint32_t out[8]) {

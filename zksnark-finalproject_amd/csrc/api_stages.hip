@@ -264,6 +264,106 @@ int zkg16_diag_term_list(zkg16_ctx *ctx, const uint64_t *scalars_canonical, size
     ZK_API_END(ctx)
 }
 
+}  // extern "C"
+
+namespace {
+
+// zkg16_diag_msm_tabled for one group: A = the ABI's affine point, X = the XYZZ form the collection returns
+template <class A, class X>
+int diag_msm_tabled(zkg16_ctx *ctx, const uint64_t *bases, const uint8_t *inf, const uint64_t *scalars, size_t n, int batch, int c, bool padded,
+                    bool last_of_proof, uint64_t *out_affine, uint8_t *out_inf, uint64_t *table_out, uint8_t *table_inf) {
+    using U = typename UOf<A>::T;
+    constexpr bool g2 = sizeof(A) == sizeof(G2Affine);
+    constexpr size_t words = sizeof(A) / sizeof(uint64_t);
+    ZK_API_BEGIN(ctx)
+    const size_t digits = (size_t)(254 / c + 1), nb = (size_t)1 << (c - 1);
+    if (nb * (size_t)batch >= ((size_t)1 << 32)) return ZKG16_ERR_BAD_ARG;
+    // msm_plan_build's own refusal, before anything is uploaded for it
+    if (n >= ((size_t)1 << 31) || (size_t)batch * n >= ((size_t)1 << 31) || (size_t)batch * n * digits >= ((size_t)1 << 31))
+        throw HipError{hipErrorInvalidValue, "msm: more than 2^31 (scalar, window) terms", __FILE__, __LINE__};
+    std::vector<X> totals((size_t)batch, X::inf());
+    std::vector<uint64_t> tab_h;
+    std::vector<uint8_t> tab_inf;
+    MsmSlot &slot = ctx->slots[0];
+    struct Restore { bool &ref; const bool old; ~Restore() { ref = old; } } restore{slot.last_of_proof, slot.last_of_proof};
+    DevBuf d_bases, d_sc, tab;
+    StreamDrain drain{ctx};
+    ctx->last_msm_group = 0;      // ws_h and slots[0] are this call's from here on; the state reads as its own once it has succeeded
+    if (n) {
+        d_bases.alloc(n * sizeof(U));
+        d_sc.alloc((size_t)batch * n * sizeof(Fr));
+        upload_points<A>(ctx, d_bases.as<U>(), bases, inf, 0, n);
+        ZK_HIP(hipMemcpyAsync(d_sc.p, scalars, (size_t)batch * n * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
+        ZK_HIP(hipStreamSynchronize(ctx->stream));
+        if constexpr (g2) tab = msm_tables_build_g2(ctx, d_bases, n, c, padded);
+        else tab = msm_tables_build_g1(ctx, d_bases, n, c, padded);
+    }
+    ScalarSrc src{d_sc.as<Fr>(), n, nullptr, 0, false, nullptr};
+    src.vec_stride = n;
+    src.batch = batch;
+    MsmPlan plan;
+    msm_plan_build(ctx, ctx->ws_h, src, plan, c, /*tabled*/ true);
+    if (plan.c != c || plan.nwin != batch) throw HipError{hipErrorInvalidValue, "tabled msm: plan differs from its forecast", __FILE__, __LINE__};
+    slot.last_of_proof = last_of_proof;
+    if constexpr (g2) msm_g2_enqueue(ctx, ctx->ws_h, plan, tab.as<U>(), slot, padded);
+    else msm_g1_enqueue(ctx, ctx->ws_h, plan, tab.as<U>(), slot, padded);
+    if (batch == 1) {
+        if constexpr (g2) totals[0] = msm_g2_collect(ctx, slot);
+        else totals[0] = msm_g1_collect(ctx, slot);
+    } else {
+        msm_slot_wait(slot);
+        for (int v = 0; v < batch; v++) {
+            if constexpr (g2) totals[(size_t)v] = msm_g2_collect_part(slot, v);
+            else totals[(size_t)v] = msm_g1_collect_part(slot, v);
+        }
+        slot.active = false;
+    }
+    if (table_out && n) {
+        const size_t stride = padded ? (g2 ? ZKG16_TABLE_STRIDE_PADDED_G2 : ZKG16_TABLE_STRIDE_PADDED_G1) : sizeof(U), cells = digits * n;
+        std::vector<unsigned char> raw(cells * stride);
+        ZK_HIP(hipMemcpyAsync(raw.data(), tab.p, raw.size(), hipMemcpyDeviceToHost, ctx->stream));
+        ZK_HIP(hipStreamSynchronize(ctx->stream));
+        tab_h.assign(cells * words, 0);
+        tab_inf.assign(cells, 0);
+        for (size_t k = 0; k < cells; k++) {
+            U u;
+            memcpy(&u, raw.data() + k * stride, sizeof u);
+            const A a = u.is_inf() ? A::inf() : A{to_sat(u.x), to_sat(u.y)};
+            point_to_abi(a, tab_h.data() + k * words, &tab_inf[k]);
+        }
+    }
+    ZK_HIP(hipStreamSynchronize(ctx->stream));
+    drain.ok = true;
+    ctx->last_msm_group = g2 ? 2 : 1;
+    for (int v = 0; v < batch; v++) point_to_abi(xyzz_to_affine(totals[(size_t)v]), out_affine + (size_t)v * words, out_inf + v);
+    if (table_out && n) {
+        memcpy(table_out, tab_h.data(), tab_h.size() * sizeof(uint64_t));
+        memcpy(table_inf, tab_inf.data(), tab_inf.size());
+    }
+    ZK_API_END(ctx)
+}
+
+}  // namespace
+
+extern "C" {
+
+// One MSM on window tables, as a proof runs one query of a key with tables: msm_tables_build_g?, a tabled msm_plan_build into ws_h, the
+// enqueue on slots[0] (whose last_of_proof it sets for the call) and the collection, one value per vector of a batch; optionally the
+// table itself, read at its stride and converted on the host.  zkg16_last_msm_state reports the call (nwin = batch).
+int zkg16_diag_msm_tabled(zkg16_ctx *ctx, int group, const uint64_t *bases, const uint8_t *inf, const uint64_t *scalars_canonical, size_t n,
+                          int batch, int window_bits, int stride_mode, int last_of_proof, uint64_t *out_affine, uint8_t *out_inf,
+                          uint64_t *table_out, uint8_t *table_inf) {
+    if (!ctx || ((!bases || !scalars_canonical) && n) || !out_affine || !out_inf || (table_out == nullptr) != (table_inf == nullptr)) return ZKG16_ERR_BAD_ARG;
+    if (group < 1 || group > 2 || batch < 1 || window_bits < 2 || window_bits > 24 || stride_mode < 1 || stride_mode > 2 || last_of_proof < 0 ||
+        last_of_proof > 1)
+        return ZKG16_ERR_BAD_ARG;
+    if (group == 1)
+        return diag_msm_tabled<G1Affine, G1XYZZ>(ctx, bases, inf, scalars_canonical, n, batch, window_bits, stride_mode == 2, last_of_proof != 0,
+                                                 out_affine, out_inf, table_out, table_inf);
+    return diag_msm_tabled<G2Affine, G2XYZZ>(ctx, bases, inf, scalars_canonical, n, batch, window_bits, stride_mode == 2, last_of_proof != 0,
+                                             out_affine, out_inf, table_out, table_inf);
+}
+
 int zkg16_witness_map(zkg16_ctx *ctx, uint64_t r1cs_handle, uint64_t witness_handle, uint64_t *h_out, size_t *log_n_out) {
     if (!h_out) return ZKG16_ERR_BAD_ARG;
     ZK_API_BEGIN(ctx)

@@ -155,6 +155,33 @@ class Device:
                                                   _ptr(offsets) if n else None, offsets.shape[0], C.byref(length)))
         return tuple(int(x) for x in plan), entries[:length.value], offsets
 
+    def diag_msm_tabled(self, group, bases, scalars, window_bits, stride_mode=1, last_of_proof=False, inf=None, want_table=False):
+        """One MSM on window tables, as a proof runs one query of a key that carries them (zkg16_diag_msm_tabled).  group "g1" | "g2";
+        bases (n, 12 | 24) with an optional infinity mask; scalars (batch, n, 4) or (n, 4) canonical u64 limbs; stride_mode 1 packed,
+        2 padded.  -> (points (batch, 12 | 24), inf (batch,)), and with want_table also (table (levels, n, 12 | 24), table_inf
+        (levels, n)).  last_msm_state() reports the call, nwin reading as the batch."""
+        w = 12 if group == "g1" else 24
+        bases = _u64(bases).reshape(-1, w)
+        sc = _u64(scalars)
+        if sc.ndim == 2:
+            sc = sc[None]
+        batch, n = sc.shape[0], sc.shape[1]
+        if bases.shape[0] != n or sc.shape[2] != 4:
+            raise ValueError("diag_msm_tabled: one base per scalar of a vector")
+        inf = _opt_u8(inf)
+        if inf is not None and inf.shape != (n,):
+            raise ValueError("diag_msm_tabled: one mask byte per base")
+        c = int(window_bits)
+        levels = 254 // c + 1 if 2 <= c <= 24 else 0      # a width the library refuses: it says so itself
+        out = np.zeros((max(batch, 1), w), dtype=np.uint64)
+        oinf = np.zeros(max(batch, 1), dtype=np.uint8)
+        table = np.zeros((levels, n, w), dtype=np.uint64) if want_table else None
+        tinf = np.zeros((levels, n), dtype=np.uint8) if want_table else None
+        self._check(self.lib.zkg16_diag_msm_tabled(self.ctx, 1 if group == "g1" else 2, _ptr(bases) if n else None, _ptr(inf), _ptr(sc) if n else None, n,
+                                                   batch, c, int(stride_mode), int(bool(last_of_proof)), out.ctypes.data, oinf.ctypes.data,
+                                                   table.ctypes.data if want_table else None, tinf.ctypes.data if want_table else None))
+        return (out, oinf, table, tinf) if want_table else (out, oinf)
+
     def circuit_load(self, circuit):
         """circuit: a circuits.CircuitHandle (a synthesized circuit still held by the library) -> (r1cs_handle, witness_handle), loaded
         without exporting its arrays to Python (zkg16_circuit_load)."""
