@@ -464,6 +464,23 @@ ZKG16_API int zkg16_witness_matrix(zkg16_ctx *ctx, size_t n, const uint64_t *a, 
 ZKG16_API int zkg16_prove_matrix(zkg16_ctx *ctx, uint64_t pk_handle, uint64_t r1cs_handle, size_t n, const uint64_t *a, const uint64_t *b,
                        const uint64_t r[4], const uint64_t s[4], uint64_t proof_out[48], uint8_t inf_out[3], uint64_t public_inputs[12],
                        float *timings_ms);
+/* The slices zkg16_prove_matrix would feed a proof of size n in under option values "matrix_parts" = parts_wanted (0..8) and
+ * "matrix_slice_min" = slice_min (0 = the default, 512; else 1..2^20), host only (no ctx, no GPU; the one function the proof itself
+ * calls): *slices_out = the slice count, bounds_out[0 .. slices] = the first permutation of every slice, then ceil(n^2/2); the words
+ * behind them are zero.  The proof has slices + 1 parts: part 0 is what needs a and b alone, part 1 + s the S-box values of slice s of
+ * every sponge, the last part also the three hashes.  parts_wanted 1 describes the one slice of a proof that does not overlap.  n
+ * outside 2..1024, an option value out of range or a null pointer: ZKG16_ERR_BAD_ARG, nothing written. */
+ZKG16_API int zkg16_matrix_stream_bounds(size_t n, int parts_wanted, int slice_min, uint32_t bounds_out[9], int *slices_out);
+/* The streamed assignment of zkg16_prove_matrix alone, part by part (diagnostics for tests): the stream object, its attachment and its
+ * produce(k) calls are the proof's own, under the ctx's "matrix_parts" and "matrix_slice_min"; no MSM and no witness map runs.  The
+ * assignment buffer is filled with 0xFF bytes first (an all-ones word is at least r: no stored Fr equals it); after every part the
+ * ctx's stream is drained and the buffer read back.  part_of_out[n_assign + 3]: the device's part map (the three trailing entries are
+ * the r, s, -rs slots); all 255 under "matrix_parts" 1, which builds none.  first_valid_out[n_assign]: the first part after which entry
+ * i differs from the fill, 255 = never written.  z_out[n_assign][4]: the finished assignment, the bytes of
+ * zkg16_circuit_matrix_witness.  *parts_out: the parts produced.  n_assign must be the circuit's variable count (num_witness + 4 of
+ * zkg16_matrix_r1cs_dims); that, n outside 2..1024 or a null pointer: ZKG16_ERR_BAD_ARG.  On any error no output is written. */
+ZKG16_API int zkg16_diag_matrix_stream(zkg16_ctx *ctx, size_t n, const uint64_t *a, const uint64_t *b, uint8_t *part_of_out,
+                                       uint8_t *first_valid_out, uint64_t *z_out, size_t n_assign, int *parts_out);
 /* Its host-only half (no ctx, no GPU): states (nullable) = 3 hashes x ceil(n^2/2) permutations x 3 Fr, the sponge state in
  * front of each permutation (after its two elements were absorbed); hashes = hash_a | hash_b | hash_c. */
 ZKG16_API int zkg16_matrix_sponge_states(size_t n, const uint64_t *a, const uint64_t *b, uint64_t *states, uint64_t hashes[12]);
@@ -682,7 +699,7 @@ ZKG16_API int zkg16_last_acc_waves(zkg16_ctx *ctx, int waves[3]);
 /* Waves of the bucket-accumulation kernels one SIMD holds at once (their register use decides): [0] G1, [1] G2.  The grid of an
  * accumulation may be sized for more waves per SIMD than that (zkg16_last_acc_waves): the extra ones run as a second round. */
 ZKG16_API int zkg16_acc_resident_waves(zkg16_ctx *ctx, int waves[2]);
-/* What the last zkg16_msm_g1 / zkg16_msm_g2 / zkg16_bench_msm / zkg16_diag_msm_tabled call on this ctx ran as (diagnostics for tests):
+/* What the last zkg16_msm_g1 / zkg16_msm_g2 / zkg16_bench_msm / zkg16_diag_msm_tabled / zkg16_diag_msm_rounds call on this ctx ran as (diagnostics for tests):
  * out = { c, nwin, entries, seg_len, fixup_items, fixup_chains, bit_sliced, two_level_k }.  c: window bits; nwin: windows;
  * entries: length of the sorted (scalar, window) term list; seg_len: entries per lane the accumulation kernel read; fixup_items /
  * fixup_chains: work items queued for spilled buckets longer than four segments (one per 1024 segments), and how many of those
@@ -730,6 +747,19 @@ ZKG16_API int zkg16_diag_term_list(zkg16_ctx *ctx, const uint64_t *scalars_canon
 ZKG16_API int zkg16_diag_msm_tabled(zkg16_ctx *ctx, int group, const uint64_t *bases, const uint8_t *inf, const uint64_t *scalars_canonical,
                                     size_t n, int batch, int window_bits, int stride_mode, int last_of_proof, uint64_t *out_affine,
                                     uint8_t *out_inf, uint64_t *table_out, uint8_t *table_inf);
+/* One MSM on a plain key fed in rounds, run as a proof on a streamed assignment (zkg16_prove_matrix) runs one z-side query (diagnostics
+ * for tests).  group, bases, inf and scalars[n][4] as zkg16_diag_msm_tabled takes them, one vector; part_of[n]: the part each scalar
+ * belongs to; parts 1..255; window_bits 2..20, taken as they are.  For k = 0 .. parts - 1: the term list of the scalars with part_of[i]
+ * == k (the others count as zero) in the workspace of zkg16_msm_g1, accumulated as round k on that entry's slot — round 0 into the
+ * MSM's bucket array, every later round into a second one, its fix-ups, then the bucket-wise sum of the two — and round_entries_out[k]
+ * = the length of that round's list.  Then one reduction and one collection: out_affine[12 | 24], *out_inf.  A scalar whose label is
+ * parts or more takes part in no round.  zkg16_last_msm_state reports the last round.  n == 0: the point at infinity, every count
+ * zero.  A null pointer (inf excepted), a group outside 1..2, parts outside 1..255 or window_bits outside 2..20: ZKG16_ERR_BAD_ARG.
+ * n * (254 / c + 1) >= 2^31: refused as the plan refuses it (ZKG16_ERR_HIP), before anything is read.  Synchronises the ctx's stream;
+ * on any error no output is written. */
+ZKG16_API int zkg16_diag_msm_rounds(zkg16_ctx *ctx, int group, const uint64_t *bases, const uint8_t *inf, const uint64_t *scalars_canonical,
+                                    size_t n, const uint8_t *part_of, int parts, int window_bits, uint64_t *out_affine, uint8_t *out_inf,
+                                    uint32_t *round_entries_out /* parts */);
 /* Which sparse product an r1cs handle's witness maps run (diagnostics; takes the handle's own lock, launches nothing):
  * out = { dict_state, ndict, perm_ok, spmv_uses }.  dict_state: 0 = the coefficient dictionary has not been tried yet (the handle
  * has run fewer than two witness maps: plain kernel, rows in natural order), 1 = the dictionary is in use (ndict distinct
@@ -774,6 +804,8 @@ ZKG16_API void zkg16_kernel_stats_reset(zkg16_ctx *ctx);
  *                    whole cache lines for tables of at least 256 MiB, packed below; 1 = packed; 2 = padded.  An existing table keeps its layout
  *   "lanes"          proofs this ctx runs at a time (1..8, default 2): see the note on re-entrancy at the top
  *   "matrix_parts"   zkg16_prove_matrix: slices of the host sponges the proof is fed in (0 = five growing slices, k = k equal ones; 1 = assignment first, then the proof)
+ *   "matrix_slice_min" zkg16_prove_matrix: the slice count is lowered until a slice holds at least this many permutations (0 = the default,
+ *                    512; else 1..2^20; at least 1 keeps every slice non-empty).  zkg16_matrix_stream_bounds gives the slices of a size
  *   "batch_max"      zkg16_prove_batch / zkg16_prove_matrix_batch: proofs per device pass (0 = as many as fit, else 1..65535)
  *   "matrix_batch_threads" zkg16_witness_matrix_batch / zkg16_prove_matrix_batch: host threads of the sponge chains (0 = 8, else 1..16)
  *   "matrix_batch_grid" cap on either grid dimension of the batched witness kernels (0 = 65535, else 1..65535): beyond it they loop

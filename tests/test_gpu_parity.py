@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import pyref as P
+import stream_cases
 import synth
 from helpers import *
 
@@ -643,6 +644,7 @@ OPTION_BOUNDS = (
     ("g1_inline", (2,), (-1, 3), 0),
     ("acc_lazy", (0,), (-1, 2), 1),
     ("matrix_parts", (8,), (-1, 9), 0),
+    ("matrix_slice_min", (1, 1 << 20), (-1, (1 << 20) + 1), 0),
     ("batch_max", (65535,), (-1, 65536), 0),
     ("matrix_batch_threads", (16,), (-1, 17), 0),
     ("matrix_batch_grid", (65535,), (-1, 65536), 0),
@@ -1144,6 +1146,9 @@ def test_prove_matrix_streamed_equals_two_step(dev, n, tables, parts):
             proof, inf, pub2, ms = dev.prove_matrix(ph, rh, a, b, r, s)
             assert np.array_equal(pub2, circ.public_inputs) and np.array_equal(pub, pub2)
             assert np.array_equal(proof, want[0]) and np.array_equal(inf, want[1]), "streamed proof differs (parts used: %d)" % ms["parts"]
+            # the slices that really ran (tests/stream_cases.py): 46x46 runs two whether 0 or 8 are asked for, 8x8 and 33x33 one,
+            # 128x128 five; parts = 1 is one slice by definition
+            assert ms["parts"] == len(stream_cases.slice_bounds((n * n + 1) // 2, parts)) == (2 if parts == 1 else {8: 2, 33: 2, 46: 3, 128: 6}[n])
     finally:
         dev.set_option("matrix_parts", 0)
     assert verify(vk, circ.public_inputs, proof, inf) is True

@@ -44,6 +44,9 @@ SIGNATURES = {
     "zkg16_diag_term_list": (C.c_int, [ctxp, vp, sz, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.POINTER(C.c_uint32), vp, sz, vp, sz,
                                        C.POINTER(C.c_uint64)]),
     "zkg16_diag_msm_tabled": (C.c_int, [ctxp, C.c_int, vp, vp, vp, sz, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]),
+    "zkg16_diag_msm_rounds": (C.c_int, [ctxp, C.c_int, vp, vp, vp, sz, vp, C.c_int, C.c_int, vp, vp, vp]),
+    "zkg16_matrix_stream_bounds": (C.c_int, [sz, C.c_int, C.c_int, vp, C.POINTER(C.c_int)]),
+    "zkg16_diag_matrix_stream": (C.c_int, [ctxp, sz, vp, vp, vp, vp, vp, sz, C.POINTER(C.c_int)]),
     "zkg16_r1cs_check_host": (C.c_int, [C.POINTER(vp * 3), C.POINTER(vp * 3), C.POINTER(vp * 3), sz, sz, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "zkg16_r1cs_check": (C.c_int, [ctxp, H, H, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "zkg16_r1cs_check_batch": (C.c_int, [ctxp, H, vp, sz, vp, vp]),

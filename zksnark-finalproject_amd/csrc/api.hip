@@ -385,6 +385,8 @@ int set_option_one(zkg16_ctx *ctx, const char *name, int64_t v) {
     if (is("acc_lazy")) return set(o.acc_lazy, 0, 1, v);
     // zkg16_prove_matrix: slices of the host sponges the proof is fed in (0 = five growing slices; k = k equal ones; 1 = no overlap: assignment first)
     if (is("matrix_parts")) return set(o.matrix_parts, 0, 8, v);
+    // ... and the fewest permutations a slice may hold: the slice count is lowered until it does (0 restores the default, 512; tests set 1)
+    if (is("matrix_slice_min")) return set(o.matrix_slice_min, 0, 1 << 20, v == 0 ? MATRIX_SLICE_MIN_DEFAULT : v);
     // zkg16_prove_batch / zkg16_prove_matrix_batch: proofs per device pass, 0 = as many as fit (free HBM, 2^31 terms per list)
     if (is("batch_max")) return set(o.batch_max, 0, 65535, v);
     // zkg16_witness_matrix_batch / zkg16_prove_matrix_batch: host threads of the sponge chains, 0 = 8

@@ -750,7 +750,7 @@ int zkg16_prove_matrix(zkg16_ctx *ctx, uint64_t pk_handle, uint64_t r1cs_handle,
     std::unique_ptr<MatrixWitnessStream, void (*)(MatrixWitnessStream *)> ms(nullptr, matrix_stream_free);
     try {
         // the chains start before the ctx is locked: they need neither it nor the device
-        ms.reset(matrix_stream_start(n, a, b, ctx->opt.matrix_parts, ctx->opt.matrix_parts != 1));
+        ms.reset(matrix_stream_start(n, a, b, ctx->opt.matrix_parts, ctx->opt.matrix_slice_min, ctx->opt.matrix_parts != 1));
     } catch (const std::bad_alloc &) {
         return ZKG16_ERR_OOM;
     }

@@ -343,9 +343,74 @@ int diag_msm_tabled(zkg16_ctx *ctx, const uint64_t *bases, const uint8_t *inf, c
     ZK_API_END(ctx)
 }
 
+// zkg16_diag_msm_rounds for one group
+template <class A, class X>
+int diag_msm_rounds(zkg16_ctx *ctx, const uint64_t *bases, const uint8_t *inf, const uint64_t *scalars, size_t n, const uint8_t *part_of, int parts,
+                    int c, uint64_t *out_affine, uint8_t *out_inf, uint32_t *round_entries_out) {
+    using U = typename UOf<A>::T;
+    constexpr bool g2 = sizeof(A) == sizeof(G2Affine);
+    ZK_API_BEGIN(ctx)
+    const size_t digits = (size_t)(254 / c + 1), tb = ((size_t)1 << (c - 1)) * digits;
+    // msm_plan_build's own refusal, before anything is uploaded for it
+    if (n >= ((size_t)1 << 31) || n * digits >= ((size_t)1 << 31))
+        throw HipError{hipErrorInvalidValue, "msm: more than 2^31 (scalar, window) terms", __FILE__, __LINE__};
+    X total = X::inf();
+    std::vector<uint32_t> entries((size_t)parts, 0u);
+    MsmSlot &slot = ctx->slots[0];
+    DevBuf d_bases, d_sc, d_part;
+    StreamDrain drain{ctx};
+    ctx->last_msm_group = 0;      // ws_h and slots[0] are this call's from here on; the state reads as its own once it has succeeded
+    if (n) {
+        d_bases.alloc(n * sizeof(U));
+        d_sc.alloc(n * sizeof(Fr));
+        d_part.alloc(n);
+        upload_points<A>(ctx, d_bases.as<U>(), bases, inf, 0, n);
+        ZK_HIP(hipMemcpyAsync(d_sc.p, scalars, n * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
+        ZK_HIP(hipMemcpyAsync(d_part.p, part_of, n, hipMemcpyHostToDevice, ctx->stream));
+        ZK_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    // prove_device's rounds: per part a plan over the scalars of that part alone, accumulated as round k of the one MSM
+    for (int k = 0; k < parts; k++) {
+        ScalarSrc src{d_sc.as<Fr>(), n, nullptr, 0, false, nullptr};
+        src.part = d_part.as<uint8_t>();
+        src.want_part = k;
+        MsmPlan plan;
+        msm_plan_build(ctx, ctx->ws_h, src, plan, c, /*tabled*/ false);
+        if (plan.c != c || plan.nb * (size_t)plan.nwin != tb) throw HipError{hipErrorInvalidValue, "msm rounds: plan differs from its forecast", __FILE__, __LINE__};
+        if constexpr (g2) msm_g2_enqueue_acc(ctx, ctx->ws_h, plan, d_bases.as<U>(), slot, k);
+        else msm_g1_enqueue_acc(ctx, ctx->ws_h, plan, d_bases.as<U>(), slot, k);
+        // the next round's plan overwrites the list: its length is read on the stream, behind this round's accumulation
+        if (n) ZK_HIP(hipMemcpyAsync(&entries[(size_t)k], ctx->ws_h.offsets.as<uint32_t>() + tb, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    if constexpr (g2) {
+        msm_g2_enqueue_reduce(ctx, slot);
+        total = msm_g2_collect(ctx, slot);
+    } else {
+        msm_g1_enqueue_reduce(ctx, slot);
+        total = msm_g1_collect(ctx, slot);
+    }
+    ZK_HIP(hipStreamSynchronize(ctx->stream));
+    drain.ok = true;
+    ctx->last_msm_group = g2 ? 2 : 1;
+    point_to_abi(xyzz_to_affine(total), out_affine, out_inf);
+    memcpy(round_entries_out, entries.data(), (size_t)parts * sizeof(uint32_t));
+    ZK_API_END(ctx)
+}
+
 }  // namespace
 
 extern "C" {
+
+// One plain-key MSM fed in rounds, as prove_device runs one z-side query of a streamed assignment: per part k a plan from a ScalarSrc
+// with part / want_part = k into ws_h, msm_g?_enqueue_acc(round = k) on slots[0] — round 0 into bucket_sum, later rounds into
+// `buckets`, their fix-ups, then msm_bucket_merge_kernel — and that round's offsets[tb]; then one reduction and one collection.
+int zkg16_diag_msm_rounds(zkg16_ctx *ctx, int group, const uint64_t *bases, const uint8_t *inf, const uint64_t *scalars_canonical, size_t n,
+                          const uint8_t *part_of, int parts, int window_bits, uint64_t *out_affine, uint8_t *out_inf, uint32_t *round_entries_out) {
+    if (!ctx || ((!bases || !scalars_canonical || !part_of) && n) || !out_affine || !out_inf || !round_entries_out) return ZKG16_ERR_BAD_ARG;
+    if (group < 1 || group > 2 || parts < 1 || parts > 255 || window_bits < 2 || window_bits > 20) return ZKG16_ERR_BAD_ARG;
+    if (group == 1) return diag_msm_rounds<G1Affine, G1XYZZ>(ctx, bases, inf, scalars_canonical, n, part_of, parts, window_bits, out_affine, out_inf, round_entries_out);
+    return diag_msm_rounds<G2Affine, G2XYZZ>(ctx, bases, inf, scalars_canonical, n, part_of, parts, window_bits, out_affine, out_inf, round_entries_out);
+}
 
 // One MSM on window tables, as a proof runs one query of a key with tables: msm_tables_build_g?, a tabled msm_plan_build into ws_h, the
 // enqueue on slots[0] (whose last_of_proof it sets for the call) and the collection, one value per vector of a batch; optionally the

@@ -273,6 +273,8 @@ constexpr int PROOF_TIMING_SLOTS = 24, VERIFY_TIMING_SLOTS = 13;
 // profiles/sponge_chains_timing.txt the device wins zkg16_witness_matrix_batch from 3072 chains and zkg16_matrix_hash_batch from 1024 at
 // every measured n, but zkg16_prove_matrix_batch (chain count = a sub-batch's) only at n = 8 — no count wins on every entry
 #define ZKG16_SPONGE_CHAINS_MIN_DEFAULT INT64_MAX
+// zkg16_prove_matrix: fewest permutations a slice of the streamed assignment may hold (witness.hip: matrix_stream_slices)
+#define MATRIX_SLICE_MIN_DEFAULT 512
 
 struct zkg16_ctx {
     int device = 0;
@@ -351,6 +353,7 @@ struct zkg16_ctx {
         int acc_lazy = 1;                             // default G1 / G2 accumulation loops: the mixed addition without the carry passes its results do not need (ec.cuh: xyzz_madd_inline_lc, xyzz_madd_lazy_lc); 0: xyzz_madd_inline / xyzz_madd_lazy
         int g1_inline = 1;                            // G1 accumulation (plain loop): every field product inlined (ec.cuh: xyzz_madd_inline); 0: products as calls
         int matrix_parts = 0;                         // zkg16_prove_matrix: gadget slices the assignment arrives in (0 = five growing slices, k = k equal ones, 1 = no overlap)
+        int matrix_slice_min = MATRIX_SLICE_MIN_DEFAULT;      // zkg16_prove_matrix: the slice count is lowered until a slice holds this many permutations (tests set 1)
         int fuse_pointwise = 1;                       // the point-wise product on the load of the last transform (0: its own pass)
         int wm_transforms = 6;                        // witness map: 6 (default) = C only inverse-transformed, subtracted on the last store; 7 = arkworks' sequence
         int batch_max = 0;                            // zkg16_prove_batch / zkg16_prove_matrix_batch: proofs per device pass (0 = as many as fit)
@@ -533,7 +536,9 @@ void prime_witness_batch_assign(zkg16_ctx *ctx, const Fr *in, size_t k, std::vec
 // witness.hip: the MatrixCircuit's assignment arriving on the device in parts (zkg16_witness_matrix: all at once;
 // zkg16_prove_matrix: while the proof is already running).  slices_wanted gadget slices -> parts = slices + 1.
 struct MatrixWitnessStream;
-MatrixWitnessStream *matrix_stream_start(size_t n, const uint64_t *a, const uint64_t *b, int slices_wanted, bool overlap);   // host chains start here
+// the slice boundaries (permutation indices, bounds[0] = 0 .. bounds[slices] = perms) -> slices; slice_min < 1 = the default
+int matrix_stream_slices(size_t perms, int slices_wanted, int slice_min, uint32_t bounds[9]);
+MatrixWitnessStream *matrix_stream_start(size_t n, const uint64_t *a, const uint64_t *b, int slices_wanted, int slice_min, bool overlap);   // host chains start here
 int matrix_stream_parts(const MatrixWitnessStream *ms);
 size_t matrix_stream_total(const MatrixWitnessStream *ms);
 const uint8_t *matrix_stream_part_of(const MatrixWitnessStream *ms);       // device, total + n_extra bytes (null with one slice)

@@ -529,24 +529,35 @@ struct MatrixWitnessStream {
     explicit MatrixWitnessStream(size_t n) : L(n) {}
 };
 
-MatrixWitnessStream *matrix_stream_start(size_t n, const uint64_t *a, const uint64_t *b, int slices_wanted, bool overlap) {
-    auto *ms = new MatrixWitnessStream(n);
-    ms->a = a; ms->b = b;
-    const size_t perms = (ms->L.nn + POSEIDON_RATE - 1) / POSEIDON_RATE;
-    // slices_wanted = 0: growing slices.  The device needs longer for a slice's terms than the host chain for its states
-    // (128x128: 84 ms of z-side accumulation against 61 ms of chain), so once started it never waits again — what counts is
-    // starting early: a first slice of 6 %, each later one about as long as the device is busy with the one before.
+// The slices a streamed assignment of `perms` permutations per sponge arrives in: bounds[0 .. slices] are permutation indices, 0 first
+// and perms last.  slices_wanted = 0: growing slices.  The device needs longer for a slice's terms than the host chain for its states
+// (128x128: 84 ms of z-side accumulation against 61 ms of chain), so once started it never waits again — what counts is
+// starting early: a first slice of 6 %, each later one about as long as the device is busy with the one before.
+// slice_min (option "matrix_slice_min", default 512): the slice count is lowered until a slice holds at least that many permutations —
+// a slice shorter than ~4 ms of host chain is all fixed cost on the device side.  At least 1, so no slice is ever empty.
+int matrix_stream_slices(size_t perms, int slices_wanted, int slice_min, uint32_t bounds[9]) {
     static const double grow[5] = {0.06, 0.20, 0.45, 0.80, 1.0};
+    if (slice_min < 1) slice_min = MATRIX_SLICE_MIN_DEFAULT;
     int k = slices_wanted == 0 ? 5 : slices_wanted < 1 ? 1 : slices_wanted > 8 ? 8 : slices_wanted;
     const bool growing = slices_wanted == 0 && perms >= 4096;
     if (!growing && slices_wanted == 0) k = 4;
-    while (k > 1 && !growing && perms / k < 512) k--;          // a slice shorter than ~4 ms of host chain is all fixed cost on the device side
-    ms->slices = overlap ? k : 1;
+    while (k > 1 && !growing && perms / k < (size_t)slice_min) k--;
+    for (int i = 0; i <= k; i++)
+        bounds[i] = growing ? (i == 0 ? 0u : (uint32_t)((double)perms * grow[i - 1] + 0.5)) : (uint32_t)(perms * (size_t)i / k);
+    bounds[k] = (uint32_t)perms;
+    return k;
+}
+
+MatrixWitnessStream *matrix_stream_start(size_t n, const uint64_t *a, const uint64_t *b, int slices_wanted, int slice_min, bool overlap) {
+    auto *ms = new MatrixWitnessStream(n);
+    ms->a = a; ms->b = b;
+    const size_t perms = (ms->L.nn + POSEIDON_RATE - 1) / POSEIDON_RATE;
+    uint32_t bounds[9];
+    const int k = matrix_stream_slices(perms, slices_wanted, slice_min, bounds);
+    ms->slices = overlap ? k : 1;           // without overlap the assignment arrives as a whole: one slice, whatever was asked for
     ms->overlap = overlap;
-    ms->bounds.resize(ms->slices + 1);
-    for (int i = 0; i <= ms->slices; i++)
-        ms->bounds[i] = (growing && overlap) ? (i == 0 ? 0u : (uint32_t)((double)perms * grow[i - 1] + 0.5)) : (uint32_t)(perms * (size_t)i / ms->slices);
-    ms->bounds[ms->slices] = (uint32_t)perms;
+    if (overlap) ms->bounds.assign(bounds, bounds + k + 1);
+    else ms->bounds = {0u, (uint32_t)perms};
     try {
         ms->mc.start(n, a, b, !overlap);
     } catch (...) {
@@ -1041,7 +1052,7 @@ int zkg16_witness_matrix(zkg16_ctx *ctx, size_t n, const uint64_t *a, const uint
     // not held up by the host arithmetic
     std::unique_ptr<MatrixWitnessStream, void (*)(MatrixWitnessStream *)> ms(nullptr, matrix_stream_free);
     try {
-        ms.reset(matrix_stream_start(n, a, b, 1, false));
+        ms.reset(matrix_stream_start(n, a, b, 1, 0, false));
         ms->mc.join();
     } catch (const std::bad_alloc &) {
         return ZKG16_ERR_OOM;
@@ -1091,6 +1102,76 @@ int zkg16_witness_matrix(zkg16_ctx *ctx, size_t n, const uint64_t *a, const uint
         (void)hipStreamSynchronize(ctx->stream);
         return ZKG16_ERR_OOM;
     }
+    return ZKG16_OK;
+}
+
+// The slices zkg16_prove_matrix feeds the proof in at size n under options matrix_parts = parts_wanted and matrix_slice_min =
+// slice_min: the choice matrix_stream_start makes (matrix_stream_slices), no ctx, no device.
+int zkg16_matrix_stream_bounds(size_t n, int parts_wanted, int slice_min, uint32_t bounds_out[9], int *slices_out) {
+    if (!bounds_out || !slices_out || n < 2 || n > 1024 || parts_wanted < 0 || parts_wanted > 8 || slice_min < 0 || slice_min > (1 << 20))
+        return ZKG16_ERR_BAD_ARG;
+    uint32_t bounds[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    const int k = matrix_stream_slices((n * n + POSEIDON_RATE - 1) / POSEIDON_RATE, parts_wanted, slice_min, bounds);
+    memcpy(bounds_out, bounds, sizeof bounds);
+    *slices_out = k;
+    return ZKG16_OK;
+}
+
+// The streamed assignment alone, part by part, as zkg16_prove_matrix produces it (diagnostics for tests): the same start / attach /
+// produce(k) calls under the ctx's matrix_parts and matrix_slice_min, on a buffer filled with 0xFF bytes first — an all-ones word is
+// at least r, so no stored Fr equals the fill.  After every part the stream is drained and z read back: first_valid[i] = the first k
+// after which entry i differs from the fill (255: never written).  Nothing runs but the production's own copies and kernels.
+int zkg16_diag_matrix_stream(zkg16_ctx *ctx, size_t n, const uint64_t *a, const uint64_t *b, uint8_t *part_of_out, uint8_t *first_valid_out,
+                             uint64_t *z_out, size_t n_assign, int *parts_out) {
+    if (!ctx || !a || !b || !part_of_out || !first_valid_out || !z_out || !parts_out || n < 2 || n > 1024) return ZKG16_ERR_BAD_ARG;
+    const size_t total = MatrixWitnessLayout(n).total;
+    if (n_assign != total) return ZKG16_ERR_BAD_ARG;
+    if (total >= ((size_t)1 << 32)) return ZKG16_ERR_DOMAIN_TOO_LARGE;
+    std::unique_ptr<MatrixWitnessStream, void (*)(MatrixWitnessStream *)> ms(nullptr, matrix_stream_free);
+    std::vector<uint8_t> part_of, first;
+    std::vector<Fr> z;
+    int parts = 0;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    try {
+        ms.reset(matrix_stream_start(n, a, b, ctx->opt.matrix_parts, ctx->opt.matrix_slice_min, ctx->opt.matrix_parts != 1));
+        part_of.assign(total + 3, 0xFF);            // stays so when no map is built (matrix_parts = 1: the assignment first, then the proof)
+        first.assign(total, 0xFF);
+        z.resize(total);
+        ZK_HIP(hipSetDevice(ctx->device));
+        DevBuf d_z(total * sizeof(Fr));
+        // the stream object's copies and kernels must not outlive it or d_z
+        struct Drain { zkg16_ctx *c; ~Drain() { (void)hipStreamSynchronize(c->stream); } } drain{ctx};
+        ZK_HIP(hipMemsetAsync(d_z.p, 0xFF, total * sizeof(Fr), ctx->stream));
+        matrix_stream_attach(ms.get(), ctx, d_z.as<Fr>(), 3);
+        parts = matrix_stream_parts(ms.get());
+        for (int k = 0; k < parts; k++) {
+            matrix_stream_produce(ms.get(), ctx, k);
+            ZK_HIP(hipMemcpyAsync(z.data(), d_z.p, total * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
+            ZK_HIP(hipStreamSynchronize(ctx->stream));
+            for (size_t i = 0; i < total; i++) {
+                if (first[i] != 0xFF) continue;
+                bool fill = true;
+                for (int l = 0; l < 8; l++) fill = fill && z[i].l[l] == 0xFFFFFFFFu;
+                if (!fill) first[i] = (uint8_t)k;
+            }
+        }
+        if (const uint8_t *d_part = matrix_stream_part_of(ms.get())) {
+            ZK_HIP(hipMemcpyAsync(part_of.data(), d_part, total + 3, hipMemcpyDeviceToHost, ctx->stream));
+            ZK_HIP(hipStreamSynchronize(ctx->stream));
+        }
+    } catch (const HipError &e) {
+        char buf[512];
+        snprintf(buf, sizeof buf, "%s failed: %s (%s:%d)", e.what, hipGetErrorString(e.err), e.file, e.line);
+        ctx->last_error = buf;
+        (void)hipGetLastError();
+        return e.err == hipErrorOutOfMemory ? ZKG16_ERR_OOM : ZKG16_ERR_HIP;
+    } catch (const std::bad_alloc &) {
+        return ZKG16_ERR_OOM;
+    }
+    memcpy(part_of_out, part_of.data(), total + 3);
+    memcpy(first_valid_out, first.data(), total);
+    memcpy(z_out, z.data(), total * sizeof(Fr));
+    *parts_out = parts;
     return ZKG16_OK;
 }
 #endif  // ZKG16_HOST_ONLY

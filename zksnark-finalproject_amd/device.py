@@ -182,6 +182,47 @@ class Device:
                                                    table.ctypes.data if want_table else None, tinf.ctypes.data if want_table else None))
         return (out, oinf, table, tinf) if want_table else (out, oinf)
 
+    def diag_msm_rounds(self, group, bases, scalars, part_of, parts, window_bits, inf=None):
+        """One plain-key MSM fed in `parts` rounds, as a proof on a streamed assignment runs one z-side query (zkg16_diag_msm_rounds).
+        group "g1" | "g2"; bases (n, 12 | 24) with an optional infinity mask; scalars (n, 4) canonical u64 limbs; part_of (n,) the
+        round each scalar takes part in.  -> (point (12 | 24,), inf, round_entries (parts,) uint32: the length of every round's term
+        list).  last_msm_state() reports the last round."""
+        w = 12 if group == "g1" else 24
+        bases = _u64(bases).reshape(-1, w)
+        sc = _u64(scalars).reshape(-1, 4)
+        n = sc.shape[0]
+        part_of = np.ascontiguousarray(part_of, dtype=np.uint8)
+        if bases.shape[0] != n or part_of.shape != (n,):
+            raise ValueError("diag_msm_rounds: one base and one part label per scalar")
+        inf = _opt_u8(inf)
+        if inf is not None and inf.shape != (n,):
+            raise ValueError("diag_msm_rounds: one mask byte per base")
+        out = np.zeros(w, dtype=np.uint64)
+        oinf = np.zeros(1, dtype=np.uint8)
+        entries = np.zeros(max(int(parts), 1), dtype=np.uint32)
+        self._check(self.lib.zkg16_diag_msm_rounds(self.ctx, 1 if group == "g1" else 2, _ptr(bases) if n else None, _ptr(inf), _ptr(sc) if n else None, n,
+                                                   _ptr(part_of) if n else None, int(parts), int(window_bits), out.ctypes.data, oinf.ctypes.data,
+                                                   entries.ctypes.data))
+        return out, int(oinf[0]), entries
+
+    def diag_matrix_stream(self, a, b):
+        """The streamed assignment of prove_matrix(a, b) alone, part by part, under this device's matrix_parts and matrix_slice_min
+        (zkg16_diag_matrix_stream) -> (part_of (total + 3,) uint8: the device's part map, first_valid (total,) uint8: the first part
+        after which each entry had been written (255 = never), z (total, 4): the finished assignment, parts)."""
+        a = np.ascontiguousarray(a, dtype=np.uint64)
+        b = np.ascontiguousarray(b, dtype=np.uint64)
+        n = a.shape[0]
+        if a.shape != (n, n) or b.shape != (n, n):
+            raise ValueError("diag_matrix_stream: a and b must be n x n")
+        total = matrix_variables(n)
+        part_of = np.zeros(total + 3, dtype=np.uint8)
+        first = np.zeros(total, dtype=np.uint8)
+        z = np.zeros((total, 4), dtype=np.uint64)
+        parts = C.c_int(0)
+        self._check(self.lib.zkg16_diag_matrix_stream(self.ctx, n, a.ctypes.data, b.ctypes.data, part_of.ctypes.data, first.ctypes.data,
+                                                      z.ctypes.data, total, C.byref(parts)))
+        return part_of, first, z, parts.value
+
     def circuit_load(self, circuit):
         """circuit: a circuits.CircuitHandle (a synthesized circuit still held by the library) -> (r1cs_handle, witness_handle), loaded
         without exporting its arrays to Python (zkg16_circuit_load)."""
@@ -821,6 +862,22 @@ def table_layout(kind, n, digits, stride_mode=0):
     stride, size = C.c_size_t(0), C.c_uint64(0)
     _check_host(_lib.load().zkg16_table_layout({"g1": 1, "g2": 2}.get(kind, 0), n, digits, stride_mode, C.byref(stride), C.byref(size)))
     return stride.value, size.value
+
+
+def matrix_variables(n):
+    """Variables of the MatrixCircuit of size n: the constant, the three hashes and the witnesses (host-only zkg16_matrix_r1cs_dims)."""
+    nc, nw = C.c_size_t(0), C.c_size_t(0)
+    _check_host(_lib.load().zkg16_matrix_r1cs_dims(n, C.byref(nc), C.byref(nw), None))
+    return 4 + nw.value
+
+
+def matrix_stream_bounds(n, parts_wanted=0, slice_min=0):
+    """The slices prove_matrix feeds a proof of size n in under options matrix_parts = parts_wanted and matrix_slice_min = slice_min
+    (host-only zkg16_matrix_stream_bounds) -> list of slices + 1 permutation indices, from 0 to ceil(n^2 / 2)."""
+    bounds = np.zeros(9, dtype=np.uint32)
+    k = C.c_int(0)
+    _check_host(_lib.load().zkg16_matrix_stream_bounds(n, int(parts_wanted), int(slice_min), bounds.ctypes.data, C.byref(k)))
+    return [int(x) for x in bounds[:k.value + 1]]
 
 
 def shard_plan(n_ranks, m_total, n_h, b_density=0.0, h_ranks=0, z_cost=None, window_tables=False):
