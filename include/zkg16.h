@@ -598,6 +598,52 @@ ZKG16_API int zkg16_witness_fibonacci_batch(zkg16_ctx *ctx, size_t steps, const 
 ZKG16_API int zkg16_prove_fibonacci_batch(zkg16_ctx *ctx, uint64_t pk_handle, uint64_t r1cs_handle, size_t steps, const uint64_t *a,
                                           const uint64_t *b, size_t k, const uint64_t *r, const uint64_t *s, uint64_t *proofs_out /* k x 48 */,
                                           uint8_t *inf_out /* k x 3 */, uint64_t *public_inputs, float *timings_ms);
+/* ---- the linear-equations route (backend/linear_equations.rs:43-106, constraints/linear_equations_constraints.rs:39-61) and K of its
+ * requests on ONE key.  A request is a square system: a = n x n u64 row-major, b = n u64.  The handler's solver (:20-41) starts from
+ * x = 0 and sets x[i] = (b[i] - sum_j a[i][j] x[j]) / a[i][i] for i = 0 .. n-1, so only the terms j < i contribute: x solves L x = b
+ * with L the lower triangle of a, diagonal included.  The circuit claims a x = b, so a request whose a has non-zero entries above the
+ * diagonal is in general UNSATISFIED by the handler's own assignment (failing rows: the equality rows i (n + 1) + n of the i with
+ * (U x)_i != 0, U the strict upper triangle): zkg16_r1cs_check and option "check_satisfied" report it.  a[i][i] == 0, a panic upstream
+ * (inverse().unwrap()), is ZKG16_ERR_UNSUPPORTED here, before any other work.
+ * Layout, with NI = 1 + n (n + 1) instance values first (ark's ConstraintMatrices): a_ij at 1 + i (n + 1) + j, b_i at 1 + i (n + 1) + n;
+ * witness w in column NI + w, NW = n (2 n + 1): per row i the sum's seed 0 at w = i (2 n + 1), the copy of x_j at i (2 n + 1) + 1 + 2 j and
+ * the product a_ij x_j at i (2 n + 1) + 2 + 2 j.  NC = n (n + 1) constraints: row i (n + 1) + j is a_ij * x-copy = product; row i (n + 1) + n
+ * is (-b_i + seed + sum_j product_ij) * 1 = 0.  The matrices depend on n alone, so one key per n serves every request.
+ * n == 0, n > ZKG16_LINEAR_N_MAX, k == 0 or a null pointer: ZKG16_ERR_BAD_ARG in every entry below; every entry is all or nothing — on
+ * any error no handle is registered and no output byte is written.
+ * zkg16_circuit_linear (no ctx, no GPU): the host mirror, for zkg16_circuit_dims / _export / _is_satisfied / _public_inputs / _load.
+ * zkg16_linear_solve_host (no ctx, no GPU): the solver for k requests, x_out[(i n + j) 4 ..] = x_j of request i as Montgomery limbs:
+ * the reference the kernels are tested against.
+ * zkg16_linear_r1cs_dims: the dimensions and non-zero counts (2 n^2 + 2 n, n^2 + n, n^2) with no request in hand (outputs nullable).
+ * zkg16_r1cs_linear: the matrices as an r1cs handle with no request in hand, written on the host from the closed form above and
+ * uploaded once per n — byte for byte the arrays of zkg16_circuit_linear + zkg16_circuit_export for any (a, b).
+ * zkg16_witness_linear_batch: k assignments in ONE upload (8 bytes per input value), two launches whatever k is (the solve: one
+ * 64-lane wave per request; the fill: one lane per element of an assignment) and one synchronisation.  Handle i holds byte for byte
+ * the assignment zkg16_circuit_export gives for request i and is usable wherever a witness handle is.  The assignments share one
+ * allocation, returned when the last handle is freed.  x_out (nullable): k x n x 4 limbs.  timings_ms (nullable, 3): host checks,
+ * device (upload + kernels + read-back), whole call.  A zero diagonal entry in any request: ZKG16_ERR_UNSUPPORTED, zkg16_last_error
+ * names the request and the row. */
+#define ZKG16_LINEAR_N_MAX ((size_t)1024)
+ZKG16_API int zkg16_circuit_linear(size_t n, const uint64_t *a /* n x n */, const uint64_t *b /* n */, zkg16_circuit **out);
+ZKG16_API int zkg16_linear_solve_host(size_t n, const uint64_t *a /* k x n x n */, const uint64_t *b /* k x n */, size_t k,
+                                      uint64_t *x_out /* k x n x 4 */);
+ZKG16_API int zkg16_linear_r1cs_dims(size_t n, size_t *num_instance, size_t *num_witness, size_t *num_constraints, size_t nnz[3]);
+ZKG16_API int zkg16_r1cs_linear(zkg16_ctx *ctx, size_t n, uint64_t *r1cs_handle);
+ZKG16_API int zkg16_witness_linear_batch(zkg16_ctx *ctx, size_t n, const uint64_t *a, const uint64_t *b, size_t k, uint64_t *witness_handles,
+                                         uint64_t *x_out, float *timings_ms);
+/* k requests of the linear handler on one resident key.  Proof i is byte for byte zkg16_prove_resident's on the assignment above with
+ * (r + 4i, s + 4i).  One lane.  The work goes in sub-batches sized as zkg16_prove_batch's with the assignment and its input added per
+ * proof, capped by option "batch_max"; per sub-batch the batched assignment pass, then the batched proof, after which its assignments
+ * are released — no witness handle ever exists.  Option "check_satisfied" applies as to the other batch entries: a batch holding a
+ * request the solver leaves unsatisfied returns ZKG16_ERR_UNSATISFIED, writes nothing, and zkg16_last_check names it.  Checked before
+ * any work, in this order: k == 0, n == 0, n > ZKG16_LINEAR_N_MAX or a null pointer (ZKG16_ERR_BAD_ARG), an unknown handle
+ * (ZKG16_ERR_BAD_HANDLE), a shard key (ZKG16_ERR_UNSUPPORTED), a key that does not fit the r1cs handle or an r1cs handle whose
+ * dimensions are not those of the n-system (ZKG16_ERR_BAD_ARG), a zero diagonal entry in any request (ZKG16_ERR_UNSUPPORTED,
+ * zkg16_last_error names the request and the row).  x_out (nullable): k x n x 4.  timings_ms (nullable, 4): host checks, assignment
+ * passes (device), proving (zkg16_last_timings[9] summed), whole call. */
+ZKG16_API int zkg16_prove_linear_batch(zkg16_ctx *ctx, uint64_t pk_handle, uint64_t r1cs_handle, size_t n, const uint64_t *a, const uint64_t *b,
+                                       size_t k, const uint64_t *r, const uint64_t *s, uint64_t *proofs_out /* k x 48 */,
+                                       uint8_t *inf_out /* k x 3 */, uint64_t *x_out, float *timings_ms);
 /* ---- does an assignment satisfy its R1CS?  (A z)_i * (B z)_i == (C z)_i for every constraint row i < num_constraints, compared as fully
  * reduced residues.  The proving calls prove whatever they are handed: an unsatisfied assignment gives a well-formed proof that no
  * verifier accepts (arkworks' prover debug_asserts cs.is_satisfied(); prime_snark.rs:123-128 asserts it on every request).  The witness

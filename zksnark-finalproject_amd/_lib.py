@@ -149,6 +149,12 @@ SIGNATURES = {
     "zkg16_r1cs_fibonacci": (C.c_int, [ctxp, sz, C.POINTER(H)]),
     "zkg16_witness_fibonacci_batch": (C.c_int, [ctxp, sz, vp, vp, sz, vp, vp, vp]),
     "zkg16_prove_fibonacci_batch": (C.c_int, [ctxp, H, H, sz, vp, vp, sz, vp, vp, vp, vp, vp, vp]),
+    "zkg16_circuit_linear": (C.c_int, [sz, vp, vp, C.POINTER(C.c_void_p)]),
+    "zkg16_linear_solve_host": (C.c_int, [sz, vp, vp, sz, vp]),
+    "zkg16_linear_r1cs_dims": (C.c_int, [sz, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz * 3)]),
+    "zkg16_r1cs_linear": (C.c_int, [ctxp, sz, C.POINTER(H)]),
+    "zkg16_witness_linear_batch": (C.c_int, [ctxp, sz, vp, vp, sz, vp, vp, vp]),
+    "zkg16_prove_linear_batch": (C.c_int, [ctxp, H, H, sz, vp, vp, sz, vp, vp, vp, vp, vp, vp]),
     "zkg16_ntt": (C.c_int, [ctxp, u64p, sz, C.c_int, C.c_int]),
     "zkg16_msm_g1": (C.c_int, [ctxp, vp, vp, vp, sz, u64p, u8p]),
     "zkg16_msm_g2": (C.c_int, [ctxp, vp, vp, vp, sz, u64p, u8p]),

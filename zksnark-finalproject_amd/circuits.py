@@ -1,5 +1,6 @@
-"""Host-side circuit synthesis through the C ABI (csrc/circuits.hip): the reference's MatrixCircuit (+ Poseidon) and
-FibonacciCircuit as R1CS (CSR) + full assignment, ready for Device.r1cs_load / Device.witness_load.  No GPU needed."""
+"""Host-side circuit synthesis through the C ABI (csrc/circuits.hip): the reference's MatrixCircuit (+ Poseidon),
+FibonacciCircuit, PrimeCircuit and LinearEquationCircuit as R1CS (CSR) + full assignment, ready for Device.r1cs_load /
+Device.witness_load.  No GPU needed."""
 import ctypes as C
 
 import numpy as np
@@ -320,6 +321,63 @@ def fibonacci_results_host(steps, a, b):
     if rc:
         raise Zkg16Error(rc, "zkg16_fibonacci_results_host")
     return out
+
+
+def _linear_system(what, a, b):
+    a = np.ascontiguousarray(a, dtype=np.uint64)
+    b = np.ascontiguousarray(b, dtype=np.uint64).reshape(-1)
+    n = b.shape[0]
+    if a.shape != (n, n):
+        raise ValueError(what + ": a must be n x n for the n entries of b")
+    return a, b, n
+
+
+def _linear_raw(a, b):
+    a, b, n = _linear_system("linear_circuit", a, b)
+    h = C.c_void_p()
+    rc = _lib.load().zkg16_circuit_linear(n, a.ctypes.data, b.ctypes.data, C.byref(h))
+    if rc:
+        raise Zkg16Error(rc, "zkg16_circuit_linear")
+    return h
+
+
+def linear_circuit(a, b):
+    """LinearEquationCircuit for the square system a [n, n], b [n] (u64) with the handler's own solution as the witness
+    (zkg16_circuit_linear): x solves the LOWER triangle of a, so the circuit is satisfied exactly when the strict upper triangle
+    times x is zero — `satisfied` says which.  Public inputs: a[0][*], b[0], a[1][*], b[1], ...  A zero diagonal entry: Zkg16Error
+    (ZKG16_ERR_UNSUPPORTED; the reference panics)."""
+    return SynthesizedCircuit(_linear_raw(a, b))
+
+
+def linear_circuit_handle(a, b):
+    """linear_circuit as a CircuitHandle (nothing exported to Python)."""
+    return CircuitHandle(_linear_raw(a, b))
+
+
+def linear_solve_host(a, b):
+    """The linear handler's solver (linear_equations.rs:20-41) for k systems of one size on the host (zkg16_linear_solve_host; no GPU):
+    a [k, n, n], b [k, n] u64 -> x [k, n, 4] Montgomery.  What the kernels of Device.witness_linear_batch are tested against."""
+    a = np.ascontiguousarray(a, dtype=np.uint64)
+    b = np.ascontiguousarray(b, dtype=np.uint64)
+    if a.ndim != 3 or a.shape[1] != a.shape[2] or b.shape != a.shape[:2]:
+        raise ValueError("linear_solve_host: a must be k x n x n and b k x n")
+    k, n = b.shape
+    x = np.zeros((k, n, 4), dtype=np.uint64)
+    rc = _lib.load().zkg16_linear_solve_host(n, a.ctypes.data, b.ctypes.data, k, x.ctypes.data)
+    if rc:
+        raise Zkg16Error(rc, "zkg16_linear_solve_host")
+    return x
+
+
+def linear_r1cs_dims(n):
+    """The linear-equations circuit's dimensions for size n (zkg16_linear_r1cs_dims; the same for every request) ->
+    dict(num_instance, num_witness, num_constraints, nnz)."""
+    ni, nw, nc = C.c_size_t(), C.c_size_t(), C.c_size_t()
+    nnz = (C.c_size_t * 3)()
+    rc = _lib.load().zkg16_linear_r1cs_dims(n, C.byref(ni), C.byref(nw), C.byref(nc), C.byref(nnz))
+    if rc:
+        raise Zkg16Error(rc, "zkg16_linear_r1cs_dims")
+    return dict(num_instance=ni.value, num_witness=nw.value, num_constraints=nc.value, nnz=tuple(nnz))
 
 
 def prime_search(x, i_max):

@@ -599,6 +599,35 @@ int zkg16_r1cs_fibonacci(zkg16_ctx *ctx, size_t steps, uint64_t *r1cs_handle) {
     ZK_API_END(ctx)
 }
 
+// The linear-equations circuit's R1CS of size n with no request in hand: the matrices do not depend on (a, b) and have a closed form
+// (linear_r1cs_build, circuits.hip), written on the host and loaded as zkg16_r1cs_load would — once per n, in front of a setup that
+// costs orders of magnitude more.
+int zkg16_r1cs_linear(zkg16_ctx *ctx, size_t n, uint64_t *r1cs_handle) {
+    if (!ctx || !r1cs_handle || n == 0 || n > ZKG16_LINEAR_N_MAX) return ZKG16_ERR_BAD_ARG;
+    const LinearDims d(n);
+    ZK_API_BEGIN(ctx)
+    std::vector<uint64_t> rp[3];
+    std::vector<uint32_t> col[3];
+    std::vector<Fr> cf[3];
+    uint64_t *prp[3];
+    uint32_t *pcol[3];
+    Fr *pcf[3];
+    for (int m = 0; m < 3; m++) {
+        rp[m].resize(d.nc + 1);
+        col[m].resize(d.nnz[m]);
+        cf[m].resize(d.nnz[m]);
+        prp[m] = rp[m].data(); pcol[m] = col[m].data(); pcf[m] = cf[m].data();
+    }
+    linear_r1cs_build(n, prp, pcol, pcf);
+    const uint64_t *crp[3] = {prp[0], prp[1], prp[2]};
+    const uint64_t *ccf[3] = {reinterpret_cast<const uint64_t *>(pcf[0]), reinterpret_cast<const uint64_t *>(pcf[1]),
+                              reinterpret_cast<const uint64_t *>(pcf[2])};
+    const uint32_t *ccol[3] = {pcol[0], pcol[1], pcol[2]};
+    const int rc = load_r1cs(ctx, crp, ccol, ccf, d.ni, d.nc, d.vars(), r1cs_handle);      // synchronises the stream: the vectors may go
+    if (rc) return rc;
+    ZK_API_END(ctx)
+}
+
 // The PrimeCircuit of candidate (x, j) on the device (prime_device.hip): handles as zkg16_r1cs_load / zkg16_witness_load would return
 // for the arrays of zkg16_circuit_prime + zkg16_circuit_export, without synthesising or uploading them.  The template is uploaded on
 // the first call under ctx->mu (held by every entry here) and stays resident until zkg16_destroy.

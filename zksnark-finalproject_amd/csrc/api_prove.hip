@@ -871,6 +871,55 @@ int zkg16_prove_fibonacci_batch(zkg16_ctx *ctx, uint64_t pk_handle, uint64_t r1c
     ZK_LANE_END(ctx)
 }
 
+// K requests of the linear-equations handler on one resident key and the n-system's resident matrices: per sub-batch the two-launch
+// assignment pass (witness.hip: linear_batch_assign) and prove_batch_device, after which the sub-batch's assignments go back.  No
+// witness handle exists at any time; proofs and solutions are staged and written only when every sub-batch has succeeded.  A zero
+// diagonal entry anywhere ends the call after the handle checks and before any device work.
+int zkg16_prove_linear_batch(zkg16_ctx *ctx, uint64_t pk_handle, uint64_t r1cs_handle, size_t n, const uint64_t *a, const uint64_t *b, size_t k,
+                             const uint64_t *r, const uint64_t *s, uint64_t *proofs_out, uint8_t *inf_out, uint64_t *x_out, float *timings_ms) {
+    if (!a || !b || !r || !s || !proofs_out || !inf_out || k == 0 || n == 0 || n > ZKG16_LINEAR_N_MAX) return ZKG16_ERR_BAD_ARG;
+    const double t_call = now_ms();
+    ZK_LANE_BEGIN(ctx)
+    const LinearDims d(n);
+    ProveHandles h;
+    if (const int st = lookup_handles(root, pk_handle, r1cs_handle, nullptr, 0, Shard::unsupported, 0, h)) return st;
+    if (h.rc->num_variables != d.vars() || h.rc->num_instance != d.ni || h.rc->num_constraints != d.nc)
+        return ZKG16_ERR_BAD_ARG;       // not the linear-equations circuit of this size
+    if (k > SIZE_MAX / (d.vars() * sizeof(Fr))) return ZKG16_ERR_BAD_ARG;
+    const double t_check = now_ms();
+    size_t bad_req = 0, bad_row = 0;
+    if (linear_zero_diagonal(n, a, k, &bad_req, &bad_row)) {
+        char buf[160];
+        snprintf(buf, sizeof buf, "zkg16_prove_linear_batch: request %zu has a zero diagonal entry in row %zu", bad_req, bad_row);
+        ctx->last_error = buf;
+        if (ctx != root) { std::lock_guard<std::mutex> l(root->lane_mu); root->last_error = buf; }
+        return ZKG16_ERR_UNSUPPORTED;
+    }
+    const double check_ms = now_ms() - t_check;
+    const std::vector<Fr> rr = frs_from_abi(r, k), ss = frs_from_abi(s, k);
+    std::vector<uint64_t> xs(4 * k * n);
+    double wit_ms = 0;
+    const float prove_ms = prove_in_passes(ctx, h.pk.get(), h.rc.get(), k, d.vars() * sizeof(Fr) + (n * n + n) * sizeof(uint64_t) + n * sizeof(Fr),
+                                           proofs_out, inf_out, [&](size_t off, size_t nb, uint64_t *proofs, uint8_t *infs) {
+        std::vector<std::shared_ptr<WitnessDev>> wit_refs;
+        float dev_ms = 0;
+        linear_batch_assign(ctx, n, a + off * n * n, b + off * n, nb, wit_refs, xs.data() + 4 * off * n, &dev_ms);
+        wit_ms += dev_ms;
+        std::vector<WitnessDev *> wits(nb);
+        for (size_t i = 0; i < nb; i++) wits[i] = wit_refs[i].get();
+        prove_batch_device(ctx, *h.pk, *h.rc, wits.data(), nb, rr.data() + off, ss.data() + off, proofs, infs);
+    });
+    if (prove_ms < 0) return ZKG16_ERR_UNSATISFIED;
+    if (x_out) memcpy(x_out, xs.data(), xs.size() * sizeof(uint64_t));
+    if (timings_ms) {
+        timings_ms[0] = (float)check_ms;
+        timings_ms[1] = (float)wit_ms;
+        timings_ms[2] = prove_ms;
+        timings_ms[3] = (float)(now_ms() - t_call);
+    }
+    ZK_LANE_END(ctx)
+}
+
 // K prime requests on the template key: every request's inputs first (a refused candidate ends the call before any device work),
 // then per sub-batch the batched assignment (prime_device.hip) and prove_batch_device with the per-proof corrections; the
 // assignments go back after each sub-batch.  Each request's gamma_abc_g1[0] is formed on the host.  Everything is staged and

@@ -787,6 +787,53 @@ void fibonacci_coeffs(size_t steps, Fr &ca, Fr &cb) {
     cb = fibonacci_result(Fr::zero(), Fr::one(), steps);
 }
 
+// ---- the linear-equations route (backend/linear_equations.rs, constraints/linear_equations_constraints.rs; layout in zkg16.h)
+// the first zero diagonal entry of k requests of size n, request-major
+bool linear_zero_diagonal(size_t n, const uint64_t *a, size_t k, size_t *req, size_t *row) {
+    for (size_t q = 0; q < k; q++)
+        for (size_t i = 0; i < n; i++)
+            if (a[q * n * n + i * n + i] == 0) {
+                if (req) *req = q;
+                if (row) *row = i;
+                return true;
+            }
+    return false;
+}
+// solve_linear_equations (linear_equations.rs:20-41): x starts at zero and row i sums a_ij x_j over the whole row, so only j < i
+// contributes (the later x_j are still zero: those products are left out here); x_i = (b_i - sum) / a_ii.  No zero diagonal.
+static void linear_solve(size_t n, const uint64_t *a, const uint64_t *b, Fr *x) {
+    for (size_t i = 0; i < n; i++) {
+        Fr sum = Fr::zero();
+        for (size_t j = 0; j < i; j++) sum = fp_add(sum, fp_mul(fr_from_u64(a[i * n + j]), x[j]));
+        x[i] = fp_mul(fp_sub(fr_from_u64(b[i]), sum), fp_inv(fr_from_u64(a[i * n + i])));
+    }
+}
+// The n-system's matrices from the closed form, as zkg16_circuit_export lays them out: rp[m] n (n + 1) + 1 entries, col / cf
+// 2 n^2 + 2 n, n^2 + n and n^2.  Row i (n + 1) + j: a_ij * x-copy_ij = p_ij.  Row i (n + 1) + n: (-b_i + s_i + sum_j p_ij) * 1 = 0.
+void linear_r1cs_build(size_t n, uint64_t *const rp[3], uint32_t *const col[3], Fr *const cf[3]) {
+    const size_t ni = 1 + n * (n + 1);
+    const Fr one = Fr::one(), minus_one = fp_neg(one);
+    uint64_t at[3] = {0, 0, 0};
+    auto put = [&](int m, size_t c, const Fr &v) { col[m][at[m]] = (uint32_t)c; cf[m][at[m]] = v; at[m]++; };
+    for (size_t i = 0; i < n; i++) {
+        const size_t w0 = ni + i * (2 * n + 1);
+        for (size_t j = 0; j <= n; j++) {
+            for (int m = 0; m < 3; m++) rp[m][i * (n + 1) + j] = at[m];
+            if (j < n) {
+                put(0, 1 + i * (n + 1) + j, one);
+                put(1, w0 + 1 + 2 * j, one);
+                put(2, w0 + 2 + 2 * j, one);
+            } else {
+                put(0, 1 + i * (n + 1) + n, minus_one);
+                put(0, w0, one);
+                for (size_t q = 0; q < n; q++) put(0, w0 + 2 + 2 * q, one);
+                put(1, 0, one);
+            }
+        }
+    }
+    for (int m = 0; m < 3; m++) rp[m][n * (n + 1)] = at[m];
+}
+
 }  // namespace zk
 
 extern "C" {
@@ -855,6 +902,62 @@ int zkg16_fibonacci_results_host(size_t steps, const uint64_t *a, const uint64_t
     } catch (const std::bad_alloc &) {
         return ZKG16_ERR_OOM;
     }
+    return ZKG16_OK;
+}
+
+// LinearEquationCircuit { a, b, x } with x from the handler's solver (linear_equations_constraints.rs:39-61).  Per row i: a witness
+// (the sum's seed, 0), then per j an input a_ij, a witness x_j — allocated again in every row — and their product, then the input
+// b_i and enforce_equal(sum, b_i).  `sum += &product` is Circuit::add of an Lc whose ids ascend with a fresh witness: the term is
+// appended (n^2 merges of up to n terms would rebuild the same vector).
+int zkg16_circuit_linear(size_t n, const uint64_t *a, const uint64_t *b, zkg16_circuit **out) {
+    if (!a || !b || !out || n == 0 || n > ZKG16_LINEAR_N_MAX) return ZKG16_ERR_BAD_ARG;
+    if (linear_zero_diagonal(n, a, 1, nullptr, nullptr)) return ZKG16_ERR_UNSUPPORTED;
+    try {
+        std::vector<Fr> x(n);
+        linear_solve(n, a, b, x.data());
+        std::unique_ptr<zkg16_circuit> c(new zkg16_circuit());
+        Circuit &cs = c->add_segment(0);
+        cs.instance.reserve(1 + n * (n + 1));
+        cs.witness.reserve(n * (2 * n + 1));
+        for (size_t i = 0; i < n; i++) {
+            Lc sum = cs.new_witness(Fr::zero());
+            sum.t.reserve(n + 1);
+            for (size_t j = 0; j < n; j++) {
+                const Lc a_var = cs.new_input(fr_from_u64(a[i * n + j])), x_var = cs.new_witness(x[j]);
+                const Lc product = cs.mul(a_var, x_var);
+                sum.t.push_back(product.t[0]);
+                sum.val = fp_add(sum.val, product.val);
+            }
+            const Lc b_var = cs.new_input(fr_from_u64(b[i]));
+            cs.enforce_equal(sum, b_var);
+        }
+        *out = c.release();
+    } catch (const std::bad_alloc &) {
+        return ZKG16_ERR_OOM;
+    }
+    return ZKG16_OK;
+}
+
+// The solver alone for k requests: what the solve kernel (witness.hip) is tested against.  Staged: nothing is written on an error.
+int zkg16_linear_solve_host(size_t n, const uint64_t *a, const uint64_t *b, size_t k, uint64_t *x_out) {
+    if (!a || !b || !x_out || k == 0 || n == 0 || n > ZKG16_LINEAR_N_MAX || k > SIZE_MAX / (n * n * sizeof(Fr))) return ZKG16_ERR_BAD_ARG;
+    if (linear_zero_diagonal(n, a, k, nullptr, nullptr)) return ZKG16_ERR_UNSUPPORTED;
+    try {
+        std::vector<Fr> x(k * n);
+        for (size_t q = 0; q < k; q++) linear_solve(n, a + q * n * n, b + q * n, x.data() + q * n);
+        memcpy(x_out, x.data(), k * n * sizeof(Fr));
+    } catch (const std::bad_alloc &) {
+        return ZKG16_ERR_OOM;
+    }
+    return ZKG16_OK;
+}
+
+int zkg16_linear_r1cs_dims(size_t n, size_t *num_instance, size_t *num_witness, size_t *num_constraints, size_t nnz[3]) {
+    if (n == 0 || n > ZKG16_LINEAR_N_MAX) return ZKG16_ERR_BAD_ARG;
+    if (num_instance) *num_instance = 1 + n * (n + 1);
+    if (num_witness) *num_witness = n * (2 * n + 1);
+    if (num_constraints) *num_constraints = n * (n + 1);
+    if (nnz) { nnz[0] = 2 * n * n + 2 * n; nnz[1] = n * n + n; nnz[2] = n * n; }
     return ZKG16_OK;
 }
 

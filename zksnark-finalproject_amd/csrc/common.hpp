@@ -583,6 +583,23 @@ void fibonacci_coeffs(size_t steps, Fr &ca, Fr &cb);
 void fibonacci_batch_assign(zkg16_ctx *ctx, const Fr &ca, const Fr &cb, const uint64_t *a, const uint64_t *b, size_t k,
                             std::vector<std::shared_ptr<WitnessDev>> &out, uint64_t *pubs, float *dev_ms);
 
+// K linear-equation requests of one size n in one pass (zkg16_witness_linear_batch, zkg16_prove_linear_batch).  LinearDims: the
+// n-system's dimensions (zkg16.h gives the layout).  linear_zero_diagonal (circuits.hip, host): the first (request, row) whose diagonal
+// entry is zero, which every entry refuses before any other work.  linear_r1cs_build (circuits.hip, host): the three matrices from
+// the closed form into arrays sized by LinearDims.  linear_batch_assign (witness.hip): on ctx->stream (a lane's, or the root's under
+// its mutex) one upload of a | b out of the ctx's pinned staging, the solve launch (one wave per request) and the fill launch, x read
+// back, one synchronisation; the assignments share one allocation (WitnessDev::backing).  x: k x n x 4 limbs, written after the
+// synchronisation.  Throws HipError (the stream drained) / std::bad_alloc.
+struct LinearDims {
+    size_t ni, nw, nc, nnz[3];
+    explicit LinearDims(size_t n) : ni(1 + n * (n + 1)), nw(n * (2 * n + 1)), nc(n * (n + 1)), nnz{2 * n * n + 2 * n, n * n + n, n * n} {}
+    size_t vars() const { return ni + nw; }
+};
+bool linear_zero_diagonal(size_t n, const uint64_t *a, size_t k, size_t *req, size_t *row);
+void linear_r1cs_build(size_t n, uint64_t *const rp[3], uint32_t *const col[3], Fr *const cf[3]);
+void linear_batch_assign(zkg16_ctx *ctx, size_t n, const uint64_t *a, const uint64_t *b, size_t k,
+                         std::vector<std::shared_ptr<WitnessDev>> &out, uint64_t *x, float *dev_ms);
+
 // An assignment that becomes valid in parts while its proof is already running (prove_device): produce(k) blocks until part k
 // can be made, then queues on ctx->stream whatever writes it; part_of[i] = the part variable i (and the trailing r, s, -rs slots)
 // belongs to.

@@ -469,6 +469,56 @@ __global__ void __launch_bounds__(64) wit_fibonacci_batch_kernel(FibBatchArgs g)
     }
 }
 
+// ---- K linear-equation requests of one size (zkg16_witness_linear_batch): the solve, then the fill (linear_dev.cuh holds the
+// arithmetic and its value bounds: every element is fully reduced wherever it is stored).
+// Solve: one 64-lane wave per request — a lone lane on serial Fr work is what DESIGN §2.8.1 measured.  LDS holds one Fr per row: first
+// 1 / a_ii, which lane i mod 64 computes, and from row i's end on y_i = x_i R^2, the form the later rows multiply the u64 entries with.
+// Row i: every lane sums its j < i, the partial sums cross the wave by limb exchanges, lane 0 forms x_i, writes it to `x` and swaps
+// the LDS slot.  The block is one wave, so the barrier after each row is a wave barrier; its trip counts depend on blockIdx alone.
+// n <= ZKG16_LINEAR_N_MAX = 1024: at most 32 KB of LDS.
+#include "linear_dev.cuh"
+struct LinearBatchArgs {
+    const uint64_t *a, *b;          // k x n x n, k x n
+    Fr *x;                          // k x n
+    Fr *z;                          // k x vars: the assignments, one after the other
+    size_t n, k, vars;
+};
+__device__ __forceinline__ Fr linear_xchg(const Fr &v, int off) {
+    Fr o;
+    for (int i = 0; i < 8; i++) o.l[i] = (uint32_t)__shfl_xor((int)v.l[i], off, LINEAR_LANES);
+    return o;
+}
+__global__ void __launch_bounds__(LINEAR_LANES) wit_linear_solve_kernel(LinearBatchArgs g) {
+    extern __shared__ uint4 linear_lds[];
+    Fr *y = reinterpret_cast<Fr *>(linear_lds);
+    const int lane = (int)threadIdx.x;
+    const size_t n = g.n;
+    for (size_t req = blockIdx.x; req < g.k; req += gridDim.x) {
+        const uint64_t *a = g.a + req * n * n, *b = g.b + req * n;
+        Fr *x = g.x + req * n;
+        for (size_t i = (size_t)lane; i < n; i += LINEAR_LANES) y[i] = linear_diag_inv(a[i * n + i]);
+        __syncthreads();
+        for (size_t i = 0; i < n; i++) {
+            Fr v = linear_partial(a + i * n, y, i, lane);
+            for (int off = LINEAR_LANES / 2; off; off >>= 1) v = linear_fold_step(v, linear_xchg(v, off));
+            if (lane == 0) {
+                const Fr xi = linear_finish(b[i], v, y[i]);
+                st32(x + i, xi);
+                y[i] = linear_keep(xi);
+            }
+            __syncthreads();            // y[i] is row i + 1's; the next request's inverses come after the last row's barrier
+        }
+    }
+}
+// Fill: a grid-stride loop over the k x vars elements, one lane per element, so consecutive lanes write consecutive 32-byte elements.
+__global__ void __launch_bounds__(256) wit_linear_fill_kernel(LinearBatchArgs g) {
+    const size_t total = g.k * g.vars;
+    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
+        const size_t req = e / g.vars, t = e % g.vars;
+        st32(g.z + e, linear_fill_value(g.n, g.a + req * g.n * g.n, g.b + req * g.n, g.x + req * g.n, t));
+    }
+}
+
 // part_of[i] = the part of a streamed assignment in which variable i becomes valid: 0 = what needs only a and b (the constant,
 // a, b, the zeros, the products; also the three trailing r / s / -rs slots of the z-side scalar vector), 1 + s = the S-box
 // values of the permutations of slice s of every sponge, the last part also the three hashes.
@@ -889,6 +939,66 @@ void fibonacci_batch_assign(zkg16_ctx *ctx, const Fr &ca, const Fr &cb, const ui
     out = std::move(wits);
 }
 
+// The k assignments of one size on ctx->stream, under ctx's mutex: a | b go up in one copy out of the ctx's pinned staging (8 bytes
+// per input value; the assignments lie one after the other in one allocation, so no address table travels), the solve and the fill
+// launch, the k x n solutions come back, one synchronisation.  `x` (nullable) is written only when all of it succeeded; when this
+// throws the stream has been drained.  No request has a zero diagonal entry: the entries have checked.
+void linear_batch_assign(zkg16_ctx *ctx, size_t n, const uint64_t *a, const uint64_t *b, size_t k,
+                         std::vector<std::shared_ptr<WitnessDev>> &out, uint64_t *x, float *dev_ms) {
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const LinearDims d(n);
+    const size_t vars = d.vars(), a_bytes = k * n * n * sizeof(uint64_t), in_bytes = a_bytes + k * n * sizeof(uint64_t);
+    const size_t x_off = up(in_bytes), x_bytes = k * n * sizeof(Fr);
+    const size_t cap = ctx->opt.matrix_batch_grid > 0 ? (size_t)ctx->opt.matrix_batch_grid : 65535;
+    mbatch_staging_ensure(ctx, x_off + x_bytes);
+    auto backing = std::make_shared<DevBuf>(k * vars * sizeof(Fr));
+    std::vector<std::shared_ptr<WitnessDev>> wits(k);
+    for (size_t i = 0; i < k; i++) {
+        wits[i] = std::make_shared<WitnessDev>();
+        wits[i]->n = vars;
+        wits[i]->backing = backing;
+        wits[i]->z.p = backing->as<Fr>() + i * vars;
+        wits[i]->z.bytes = vars * sizeof(Fr);
+    }
+    uint8_t *hs = static_cast<uint8_t *>(ctx->mbatch_host), *ds = ctx->mbatch_dev.as<uint8_t>();
+    memcpy(hs, a, a_bytes);
+    memcpy(hs + a_bytes, b, in_bytes - a_bytes);
+    hipEvent_t e0, e1;
+    ZK_HIP(hipEventCreate(&e0));
+    struct EvGuard { hipEvent_t e; ~EvGuard() { (void)hipEventDestroy(e); } } g0{e0};
+    ZK_HIP(hipEventCreate(&e1));
+    EvGuard g1{e1};
+    struct Drain { zkg16_ctx *c; bool ok = false; ~Drain() { if (!ok) (void)hipStreamSynchronize(c->stream); } } drain{ctx};
+    ZK_HIP(hipEventRecord(e0, ctx->stream));
+    ZK_HIP(hipMemcpyAsync(ds, hs, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+    LinearBatchArgs g;
+    g.a = reinterpret_cast<const uint64_t *>(ds);
+    g.b = reinterpret_cast<const uint64_t *>(ds + a_bytes);
+    g.x = reinterpret_cast<Fr *>(ds + x_off);
+    g.z = backing->as<Fr>();
+    g.n = n; g.k = k; g.vars = vars;
+    {
+        ScopedKernelTimer kt(ctx, "wit_linear_solve_kernel", (double)k * (double)n * (double)n / 2);
+        hipLaunchKernelGGL(wit_linear_solve_kernel, dim3((unsigned)(k < cap ? k : cap)), dim3(LINEAR_LANES), n * sizeof(Fr), ctx->stream, g);
+        ZK_HIP(hipGetLastError());
+    }
+    {
+        const size_t bx = (k * vars + 255) / 256;
+        ScopedKernelTimer kt(ctx, "wit_linear_fill_kernel", (double)k * (double)vars);
+        hipLaunchKernelGGL(wit_linear_fill_kernel, dim3((unsigned)(bx < cap ? bx : cap)), dim3(256), 0, ctx->stream, g);
+        ZK_HIP(hipGetLastError());
+    }
+    ZK_HIP(hipMemcpyAsync(hs + x_off, ds + x_off, x_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    ZK_HIP(hipEventRecord(e1, ctx->stream));
+    ZK_HIP(hipStreamSynchronize(ctx->stream));      // the staging is free again, and the assignments are whole
+    drain.ok = true;
+    float ms = 0;
+    ZK_HIP(hipEventElapsedTime(&ms, e0, e1));
+    if (dev_ms) *dev_ms = ms;
+    if (x) memcpy(x, hs + x_off, x_bytes);
+    out = std::move(wits);
+}
+
 }  // namespace zk
 #endif  // ZKG16_HOST_ONLY
 
@@ -1024,6 +1134,57 @@ int zkg16_witness_fibonacci_batch(zkg16_ctx *ctx, size_t steps, const uint64_t *
         if (public_inputs) memcpy(public_inputs, pubs.data(), 12 * k * sizeof(uint64_t));
         if (timings_ms) {
             timings_ms[0] = (float)coeff_ms;
+            timings_ms[1] = dev_ms;
+            timings_ms[2] = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
+        }
+    } catch (const HipError &e) {
+        char buf[512];
+        snprintf(buf, sizeof buf, "%s failed: %s (%s:%d)", e.what, hipGetErrorString(e.err), e.file, e.line);
+        ctx->last_error = buf;
+        (void)hipGetLastError();
+        return e.err == hipErrorOutOfMemory ? ZKG16_ERR_OOM : ZKG16_ERR_HIP;
+    } catch (const std::bad_alloc &) {
+        return ZKG16_ERR_OOM;
+    }
+    return ZKG16_OK;
+}
+
+// K linear-equation assignments of one size in one upload, two launches and one synchronisation: handle i carries the bytes
+// zkg16_circuit_export gives for request i.  The diagonals are checked before the ctx is locked; all or nothing: on any error no
+// handle is registered and nothing is written.  timings_ms (nullable, 3): host checks, device, whole call.
+int zkg16_witness_linear_batch(zkg16_ctx *ctx, size_t n, const uint64_t *a, const uint64_t *b, size_t k, uint64_t *witness_handles,
+                               uint64_t *x_out, float *timings_ms) {
+    if (!ctx || !a || !b || !witness_handles || k == 0 || n == 0 || n > ZKG16_LINEAR_N_MAX) return ZKG16_ERR_BAD_ARG;
+    if (k > SIZE_MAX / (LinearDims(n).vars() * sizeof(Fr))) return ZKG16_ERR_BAD_ARG;
+    const auto t_call = std::chrono::steady_clock::now();
+    size_t bad_req = 0, bad_row = 0;
+    const bool zero_diag = linear_zero_diagonal(n, a, k, &bad_req, &bad_row);
+    const double check_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    try {
+        if (zero_diag) {
+            char buf[160];
+            snprintf(buf, sizeof buf, "zkg16_witness_linear_batch: request %zu has a zero diagonal entry in row %zu", bad_req, bad_row);
+            ctx->last_error = buf;
+            return ZKG16_ERR_UNSUPPORTED;
+        }
+        ZK_HIP(hipSetDevice(ctx->device));
+        std::vector<std::shared_ptr<WitnessDev>> wits;
+        std::vector<uint64_t> xs(4 * k * n);
+        float dev_ms = 0;
+        linear_batch_assign(ctx, n, a, b, k, wits, xs.data(), &dev_ms);
+        const uint64_t first = ctx->next_handle.fetch_add(k);
+        size_t put = 0;
+        try {
+            for (; put < k; put++) ctx->wits.put(first + put, std::move(wits[put]));
+        } catch (const std::bad_alloc &) {          // all or nothing: what was registered is taken back
+            for (size_t i = 0; i < put; i++) ctx->wits.erase(first + i);
+            return ZKG16_ERR_OOM;
+        }
+        for (size_t i = 0; i < k; i++) witness_handles[i] = first + i;
+        if (x_out) memcpy(x_out, xs.data(), xs.size() * sizeof(uint64_t));
+        if (timings_ms) {
+            timings_ms[0] = (float)check_ms;
             timings_ms[1] = dev_ms;
             timings_ms[2] = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
         }

@@ -282,6 +282,13 @@ class Device:
         self._check(self.lib.zkg16_r1cs_fibonacci(self.ctx, steps, C.byref(handle)))
         return handle.value
 
+    def r1cs_linear(self, n):
+        """The linear-equations circuit's R1CS of size n, which no request's (a, b) enters (zkg16_r1cs_linear) -> r1cs handle: what the
+        key of prove_linear_batch is set up on."""
+        handle = C.c_uint64()
+        self._check(self.lib.zkg16_r1cs_linear(self.ctx, n, C.byref(handle)))
+        return handle.value
+
     def r1cs_prime(self, x, j):
         """The PrimeCircuit's R1CS for candidate (x, j) from the template resident on the device (zkg16_r1cs_prime) -> r1cs handle."""
         handle = C.c_uint64()
@@ -432,6 +439,25 @@ class Device:
         ms = (C.c_float * 3)()
         self._check(self.lib.zkg16_witness_fibonacci_batch(self.ctx, steps, _ptr(a), _ptr(b), k, _ptr(handles), _ptr(pub), C.addressof(ms)))
         return handles, pub, dict(host_coeffs_ms=float(ms[0]), device_ms=float(ms[1]), call_ms=float(ms[2]))
+
+    @staticmethod
+    def _linear_batch(what, a, b):
+        a, b = _u64(a), _u64(b)
+        if a.ndim != 3 or a.shape[1] != a.shape[2] or b.shape != a.shape[:2]:
+            raise ValueError(what + ": a must be k x n x n and b k x n")
+        return a, b, a.shape[0], a.shape[1]
+
+    def witness_linear_batch(self, a, b):
+        """The linear-equations assignments of k requests of one size, a [k, n, n] and b [k, n] u64, built in one device pass
+        (zkg16_witness_linear_batch: the solve kernel, one wave per request, and the fill kernel) -> (witness handles [k], x [k, n, 4]
+        = the handler's solutions, dict of ms: host checks / device / whole call).  Handle i holds what circuit_load of
+        linear_circuit(a[i], b[i]) would; each is freed on its own."""
+        a, b, k, n = self._linear_batch("witness_linear_batch", a, b)
+        handles = np.zeros(k, dtype=np.uint64)
+        x = np.zeros((k, n, 4), dtype=np.uint64)
+        ms = (C.c_float * 3)()
+        self._check(self.lib.zkg16_witness_linear_batch(self.ctx, n, _ptr(a), _ptr(b), k, _ptr(handles), _ptr(x), C.addressof(ms)))
+        return handles, x, dict(host_check_ms=float(ms[0]), device_ms=float(ms[1]), call_ms=float(ms[2]))
 
     def poseidon_hash_batch(self, elems):
         """k Poseidon hashes in one call (zkg16_poseidon_hash_batch): elems [k, n, 4] Montgomery Fr -> [k, 4], row i the bytes of
@@ -688,6 +714,25 @@ class Device:
         self._check(self.lib.zkg16_prove_fibonacci_batch(self.ctx, pk_h, r1cs_h, steps, _ptr(a), _ptr(b), k, _ptr(rs), _ptr(ss), _ptr(proofs),
                                                          _ptr(inf), _ptr(pub), C.addressof(ms)))
         return proofs, inf, pub, dict(host_coeffs_ms=float(ms[0]), witness_ms=float(ms[1]), prove_ms=float(ms[2]), call_ms=float(ms[3]))
+
+    def prove_linear_batch(self, pk_h, r1cs_h, a, b, rs, ss):
+        """k linear-handler requests of one size on one resident key, a [k, n, n] and b [k, n] u64, rs / ss [k, 4]: assignments and
+        proofs in batched device passes (zkg16_prove_linear_batch) -> (proofs [k, 48], inf [k, 3], x [k, n, 4], dict of ms).  pk_h: a
+        key set up on r1cs_linear(n) = r1cs_h.  Proof i is byte-identical to prove_resident on the circuit_load handles of
+        linear_circuit(a[i], b[i]) with (rs[i], ss[i]) — a proof no verifier accepts when the request's a is not lower-triangular
+        enough for the handler's solver (option "check_satisfied" refuses such a batch instead)."""
+        a, b, k, n = self._linear_batch("prove_linear_batch", a, b)
+        rs = _u64(rs).reshape(-1, 4)
+        ss = _u64(ss).reshape(-1, 4)
+        if rs.shape[0] != k or ss.shape[0] != k:
+            raise ValueError("prove_linear_batch: one r and one s per request")
+        proofs = np.zeros((k, 48), dtype=np.uint64)
+        inf = np.zeros((k, 3), dtype=np.uint8)
+        x = np.zeros((k, n, 4), dtype=np.uint64)
+        ms = (C.c_float * 4)()
+        self._check(self.lib.zkg16_prove_linear_batch(self.ctx, pk_h, r1cs_h, n, _ptr(a), _ptr(b), k, _ptr(rs), _ptr(ss), _ptr(proofs),
+                                                      _ptr(inf), _ptr(x), C.addressof(ms)))
+        return proofs, inf, x, dict(host_check_ms=float(ms[0]), witness_ms=float(ms[1]), prove_ms=float(ms[2]), call_ms=float(ms[3]))
 
     def prove_prime_batch(self, pk_h, r1cs_h, corr, gamma_abc0, xs, js, rs, ss, public_inputs=True):
         """k prime requests (xs[i], js[i]) on the template key in batched device passes (zkg16_prove_prime_batch).  pk_h: the key

@@ -4,6 +4,9 @@
     prove_fibonacci  src/arkworks/backend/fibbonaci_handler.rs:98-145
     prove_fibonaccis / verify_fibonaccis  K Fibonacci requests of one round count under ONE key, in batched device passes (no
                      counterpart upstream)
+    prove_linear_equations  src/arkworks/backend/linear_equations.rs:43-106
+    prove_linear_equations_batch / verify_linear_equations  K linear requests of one size under ONE key, in batched device passes
+                     (no counterpart upstream)
     prove_prime / verify_prime  src/arkworks/backend/prime_snark.rs:49-146, 165-206
     prove_primes     K prime requests under one trapdoor on ONE template key, in batched device passes (no counterpart upstream)
     verify_primes    K such proofs checked together under the ONE extended key of their trapdoor (no counterpart upstream)
@@ -27,7 +30,7 @@ import numpy as np
 
 from . import _lib, device, wire
 from ._lib import Zkg16Error
-from .circuits import (fibonacci_circuit, fibonacci_circuit_handle, matrix_circuit, matrix_hash_batch_host, prime_circuit, prime_dims, prime_key_corrections,
+from .circuits import (fibonacci_circuit, fibonacci_circuit_handle, linear_circuit, linear_circuit_handle, linear_r1cs_dims, matrix_circuit, matrix_hash_batch_host, prime_circuit, prime_dims, prime_key_corrections,
                        prime_public_inputs, prime_search, prime_vk_extend)
 from .workloads import R_MOD, g1_generator, g2_generator
 
@@ -365,6 +368,145 @@ def verify_fibonaccis(vk, claims, proofs_b64, dev=None):
                 raise ValueError("verify_fibonaccis: not a claim")
             pubs.append(np.stack([_fr_mont(a), _fr_mont(b), np.asarray(wire.decode_hash(fib), dtype=np.uint64)]))
         except (ValueError, TypeError):
+            pubs.append(np.zeros((0, 4), dtype=np.uint64))       # the wrong shape: verify_proofs answers invalid for this entry
+    return verify_proofs(vk, pubs, proofs_b64, dev=dev)
+
+
+def _linear_request(what, a, b):
+    """A square system as arrays: a [n, n], b [n] u64.  The reference indexes x by column and divides by a[i][i], which only works
+    for n x n (linear_equations.rs:20-41)."""
+    b = np.asarray(b, dtype=np.uint64).reshape(-1)
+    a = np.asarray(a, dtype=np.uint64)
+    if a.shape != (b.shape[0], b.shape[0]) or b.shape[0] == 0:
+        raise ValueError(what + ": a must be n x n for the n >= 1 entries of b")
+    return a, b
+
+
+def _linear_public_inputs(a, b):
+    """The handler's public input list a[0][*], b[0], a[1][*], b[1], ... (linear_equations.rs:66-72) -> [n (n + 1), 4] Montgomery."""
+    return np.stack([_fr_mont(int(v)) for v in np.concatenate([a, b[:, None]], axis=1).reshape(-1)])
+
+
+def prove_linear_equations(dev, a, b, seed=0, keep_key=False, check_on_device=False):
+    """Mirror of prove_linear_equations (backend/linear_equations.rs:43-106): solve the system with the handler's forward
+    substitution, build LinearEquationCircuit, circuit-specific setup, prove, verify against a[0][*], b[0], a[1][*], b[1], ...
+    The solver is only right for a lower-triangular a: for any other a the circuit is in general unsatisfied, the proof is made all the
+    same (as upstream, whose prover does not check in release builds) and "valid" is False.  A zero diagonal entry, a panic upstream,
+    raises Zkg16Error (ZKG16_ERR_UNSUPPORTED).
+    -> the reference's OutputData fields plus valid, pvk and vk.  Deviations from the reference's record: "proof" and the entries of
+    "public_input" are base64 (of the compressed proof / of the 32 little-endian bytes), as in the other mirrors, where upstream
+    prints Rust Debug strings; "num_constraints" and "num_variables" (the instance count) are the real system's, where upstream
+    reports 0 and 1 from a constraint system it never synthesizes into (:62, :100-101); "proving_time" and "verifying_time" are
+    measured, where upstream returns 0.0; "valid" is the verifier's answer, which upstream computes and drops.
+    check_on_device: "satisfied" is added, the verdict of Device.r1cs_check on the request's handles."""
+    a, b = _linear_request("prove_linear_equations", a, b)
+    if keep_key:
+        circ = linear_circuit(a, b)
+        sources = _from_host(dev, circ)
+    else:
+        circ = linear_circuit_handle(a, b)
+        sources = _from_handle(dev, circ)
+    out = _request(dev, random.Random(seed), circ, *sources, keep_key=keep_key, check_on_device=check_on_device)
+    t0 = time.perf_counter()
+    valid = bool(device.verify(out["vk"], circ.public_inputs, out["proof"], out["inf"]))
+    verifying_time = time.perf_counter() - t0
+    return _with_verdict(dict(proof=wire.encode_proof(out["proof"], out["inf"]), public_input=[wire.encode_hash(x) for x in circ.public_inputs],
+                num_constraints=circ.num_constraints, num_variables=circ.num_instance, proving_time=out["proving_time"],
+                verifying_time=verifying_time, valid=valid, pvk=wire.encode_pvk(out["vk"]), vk=wire.encode_vk(out["vk"]),
+                _detail=out, _circuit=circ), out, check_on_device)
+
+
+def linear_key(dev, n, rng):
+    """The key every linear request of one size shares: the circuit's matrices depend on n alone (Device.r1cs_linear), so
+    prove_linear_equations' draws from rng in its order (trapdoor, generators) and one setup give the key that handler makes for any
+    (a, b) -> dict(ph, rh, vk, setup_time).  The caller frees ph and rh."""
+    trap, g1, g2 = _draw_key(rng)
+    with contextlib.ExitStack() as stack:
+        rh = dev.r1cs_linear(n)
+        stack.callback(dev.r1cs_free, rh)
+        t0 = time.perf_counter()
+        ph, vk = dev.setup_resident(rh, 1 + n * (n + 1), trap, g1, g2)
+        setup_time = time.perf_counter() - t0
+        stack.pop_all()                 # both handles are the caller's from here
+    return dict(ph=ph, rh=rh, vk=vk, setup_time=setup_time)
+
+
+def prove_linear_equations_batch(dev, systems, seed=0, key=None, check_on_device=False):
+    """K requests of the linear handler of one size, systems = [(a, b), ...], under ONE key, assignments and proofs in batched device
+    passes (Device.prove_linear_batch).  The key is set up once from `seed` with prove_linear_equations' draws (then r, s per
+    request), so request 0 is that handler's proof and key for that seed, byte for byte; or it is passed in as key= (linear_key's
+    dict), which stays the caller's.  The key's two encodings are made once, and the K proofs are verified together on the host.
+    -> a list of prove_linear_equations' fields per request; proving_time and verifying_time are the batch's divided by K.
+    check_on_device: the assignments are built as handles (Device.witness_linear_batch), checked together
+    (Device.r1cs_check_batch) and proved with Device.prove_batch — the same proof bytes — and every record gets "satisfied"."""
+    k = len(systems)
+    if k == 0:
+        raise ValueError("prove_linear_equations_batch: no requests")
+    reqs = [_linear_request("prove_linear_equations_batch", a, b) for a, b in systems]
+    n = reqs[0][1].shape[0]
+    if any(q[1].shape[0] != n for q in reqs):
+        raise ValueError("prove_linear_equations_batch: every system of a batch has one size")
+    a, b = np.stack([q[0] for q in reqs]), np.stack([q[1] for q in reqs])
+    rng = random.Random(seed)
+    own = key is None
+    with contextlib.ExitStack() as stack:
+        if own:
+            key = linear_key(dev, n, rng)
+            stack.callback(dev.r1cs_free, key["rh"])
+            stack.callback(dev.pk_free, key["ph"])
+        rs, ss = _draw_rs_batch(rng, k)
+        t0 = time.perf_counter()
+        verdicts, check_time = None, 0.0
+        if check_on_device:
+            whs, xs, ms = dev.witness_linear_batch(a, b)
+            for wh in whs:
+                stack.callback(dev.witness_free, int(wh))
+            tc = time.perf_counter()
+            verdicts = dev.r1cs_check_batch(key["rh"], whs)
+            check_time = time.perf_counter() - tc
+            proofs, inf = dev.prove_batch(key["ph"], key["rh"], whs, rs, ss)
+        else:
+            proofs, inf, xs, ms = dev.prove_linear_batch(key["ph"], key["rh"], a, b, rs, ss)
+        proving_time = time.perf_counter() - t0 - check_time
+    vk = key["vk"]
+    vk_b64, pvk_b64 = wire.encode_vk(vk), wire.encode_pvk(vk)
+    pubs = np.stack([_linear_public_inputs(a[i], b[i]) for i in range(k)])
+    t0 = time.perf_counter()
+    _, each = device.verify_batch_host(device.pvk_prepare(vk), pubs, np.asarray(proofs, dtype=np.uint64), np.asarray(inf, dtype=np.uint8), each=True)
+    verifying_time = time.perf_counter() - t0
+    dims = linear_r1cs_dims(n)
+    out = []
+    for i in range(k):
+        circ = _DeviceCircuit(dims["num_instance"], dims["num_witness"], dims["num_constraints"], pubs[i])
+        rec = dict(proof=wire.encode_proof(proofs[i], inf[i]), public_input=[wire.encode_hash(x) for x in pubs[i]],
+                   num_constraints=circ.num_constraints, num_variables=circ.num_instance, proving_time=proving_time / k,
+                   verifying_time=verifying_time / k, valid=bool(each[i]), pvk=pvk_b64, vk=vk_b64, _circuit=circ,
+                   _detail=dict(proof=proofs[i], inf=inf[i], vk=vk, r=rs[i], s=ss[i], public_inputs=pubs[i], x=xs[i], ms=ms,
+                                setup_time=key["setup_time"] if own else 0.0))
+        if verdicts is not None:
+            rec["satisfied"] = verdicts[i][0] == 0
+        out.append(rec)
+    return out
+
+
+def verify_linear_equations(vk, systems, proofs_b64, dev=None):
+    """The verification the linear handler runs on its own proof (linear_equations.rs:92-94) for K proofs under one key, checked
+    together: systems = [(a, b), ...], each n x n with the n entries of b.  The n^2 + n public inputs a[0][*], b[0], a[1][*], b[1], ...
+    are built per proof and the batch is answered by verify_proofs (with dev: Device.verify_batch_wire and its thresholds)
+    -> {valid: [K bools], verifying_time, decode_time}.  A system that is not square, or holds a value that is no u64, is valid=False
+    for that entry only."""
+    if len(systems) != len(proofs_b64):
+        raise ValueError("verify_linear_equations: one system per proof")
+    pubs = []
+    for a, b in systems:
+        try:
+            rows = [[int(v) for v in row] for row in a]
+            rhs = [int(v) for v in b]
+            if len(rhs) == 0 or len(rows) != len(rhs) or any(len(row) != len(rhs) for row in rows) or \
+                    not all(0 <= v < 1 << 64 for row in rows for v in row) or not all(0 <= v < 1 << 64 for v in rhs):
+                raise ValueError("verify_linear_equations: not a system")
+            pubs.append(_linear_public_inputs(np.array(rows, dtype=np.uint64), np.array(rhs, dtype=np.uint64)))
+        except (ValueError, TypeError, OverflowError):
             pubs.append(np.zeros((0, 4), dtype=np.uint64))       # the wrong shape: verify_proofs answers invalid for this entry
     return verify_proofs(vk, pubs, proofs_b64, dev=dev)
 
