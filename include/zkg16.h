@@ -602,7 +602,8 @@ ZKG16_API int zkg16_prove_fibonacci_batch(zkg16_ctx *ctx, uint64_t pk_handle, ui
  * requests on ONE key.  A request is a square system: a = n x n u64 row-major, b = n u64.  The handler's solver (:20-41) starts from
  * x = 0 and sets x[i] = (b[i] - sum_j a[i][j] x[j]) / a[i][i] for i = 0 .. n-1, so only the terms j < i contribute: x solves L x = b
  * with L the lower triangle of a, diagonal included.  The circuit claims a x = b, so a request whose a has non-zero entries above the
- * diagonal is in general UNSATISFIED by the handler's own assignment (failing rows: the equality rows i (n + 1) + n of the i with
+ * diagonal is in general UNSATISFIED by the handler's own assignment — by design of the reference; option "linear_solver" = 1, below,
+ * solves the system the circuit claims instead — (failing rows: the equality rows i (n + 1) + n of the i with
  * (U x)_i != 0, U the strict upper triangle): zkg16_r1cs_check and option "check_satisfied" report it.  a[i][i] == 0, a panic upstream
  * (inverse().unwrap()), is ZKG16_ERR_UNSUPPORTED here, before any other work.
  * Layout, with NI = 1 + n (n + 1) instance values first (ark's ConstraintMatrices): a_ij at 1 + i (n + 1) + j, b_i at 1 + i (n + 1) + n;
@@ -622,11 +623,29 @@ ZKG16_API int zkg16_prove_fibonacci_batch(zkg16_ctx *ctx, uint64_t pk_handle, ui
  * the assignment zkg16_circuit_export gives for request i and is usable wherever a witness handle is.  The assignments share one
  * allocation, returned when the last handle is freed.  x_out (nullable): k x n x 4 limbs.  timings_ms (nullable, 3): host checks,
  * device (upload + kernels + read-back), whole call.  A zero diagonal entry in any request: ZKG16_ERR_UNSUPPORTED, zkg16_last_error
- * names the request and the row. */
+ * names the request and the row.
+ * Option "linear_solver" (zkg16_set_option; per ctx): 0 (default) is the solver above, the reference's behaviour, and every entry, error
+ * and byte is as described.  1 solves a x = b itself, by Gaussian elimination over Fr with row pivoting (any non-zero entry of the column
+ * among the rows left; division-free row updates p row_i - a_ic row_c, then the n pivots inverted at once, then the back substitution by
+ * columns), so a request with ANY a that is non-singular mod r is satisfied and its proof verifies; for a lower-triangular a with a
+ * non-zero diagonal x and every byte are those of solver 0.  zkg16_witness_linear_batch and zkg16_prove_linear_batch read the option: under 1
+ * the zero-diagonal check is skipped, the solve launch is wit_linear_elim_kernel (one 256-lane workgroup per request; the n x (n + 1)
+ * working matrix in LDS for n <= option "linear_elim_lds_max", 64 by default, else in a global workspace of 32 n (n + 1) bytes per
+ * workgroup, which zkg16_prove_linear_batch's sub-batch sizing counts per request), and its k status words are read back at the call's
+ * (sub-batch's) one synchronisation: 0, or 1 + c with c the smallest column index for which columns 0..c of a are linearly dependent
+ * mod r — a value no pivot order changes.  Any singular request: ZKG16_ERR_UNSUPPORTED, nothing written, no handle registered,
+ * zkg16_last_error names the first such request and c.  The order of the other argument checks is unchanged.
+ * zkg16_linear_solve_general_host (no ctx, no GPU): the same elimination (the kernel's phase functions on one lane) for k requests;
+ * status_out (nullable, k) is written whenever the arguments are good, x_out only when every request was solved, else
+ * ZKG16_ERR_UNSUPPORTED.  zkg16_circuit_linear_general: zkg16_circuit_linear with the eliminated x as the assignment (the same matrices);
+ * a singular a: ZKG16_ERR_UNSUPPORTED. */
 #define ZKG16_LINEAR_N_MAX ((size_t)1024)
 ZKG16_API int zkg16_circuit_linear(size_t n, const uint64_t *a /* n x n */, const uint64_t *b /* n */, zkg16_circuit **out);
 ZKG16_API int zkg16_linear_solve_host(size_t n, const uint64_t *a /* k x n x n */, const uint64_t *b /* k x n */, size_t k,
                                       uint64_t *x_out /* k x n x 4 */);
+ZKG16_API int zkg16_circuit_linear_general(size_t n, const uint64_t *a /* n x n */, const uint64_t *b /* n */, zkg16_circuit **out);
+ZKG16_API int zkg16_linear_solve_general_host(size_t n, const uint64_t *a /* k x n x n */, const uint64_t *b /* k x n */, size_t k,
+                                              uint64_t *x_out /* k x n x 4 */, uint32_t *status_out /* k */);
 ZKG16_API int zkg16_linear_r1cs_dims(size_t n, size_t *num_instance, size_t *num_witness, size_t *num_constraints, size_t nnz[3]);
 ZKG16_API int zkg16_r1cs_linear(zkg16_ctx *ctx, size_t n, uint64_t *r1cs_handle);
 ZKG16_API int zkg16_witness_linear_batch(zkg16_ctx *ctx, size_t n, const uint64_t *a, const uint64_t *b, size_t k, uint64_t *witness_handles,
@@ -855,6 +874,11 @@ ZKG16_API void zkg16_kernel_stats_reset(zkg16_ctx *ctx);
  *   "batch_max"      zkg16_prove_batch / zkg16_prove_matrix_batch: proofs per device pass (0 = as many as fit, else 1..65535)
  *   "matrix_batch_threads" zkg16_witness_matrix_batch / zkg16_prove_matrix_batch: host threads of the sponge chains (0 = 8, else 1..16)
  *   "matrix_batch_grid" cap on either grid dimension of the batched witness kernels (0 = 65535, else 1..65535): beyond it they loop
+ *   "linear_solver"  zkg16_witness_linear_batch / zkg16_prove_linear_batch: 0 (default) = the reference's forward substitution on the lower
+ *                    triangle of a, 1 = Gaussian elimination with row pivoting (see the linear-equations route above).  The default is 0
+ *                    because 0 is what the reference computes, unsatisfied assignments for dense a included
+ *   "linear_elim_lds_max" wit_linear_elim_kernel: the largest n whose working matrix lies in LDS (0 = the default, 64; else 1..64); above it
+ *                    the matrix lies in a global workspace
  *   "sponge_chains_min" zkg16_witness_matrix_batch / zkg16_prove_matrix_batch (3K chains per call or sub-batch) and zkg16_poseidon_hash_batch /
  *                    zkg16_matrix_hash_batch (k chains): calls with at least this many Poseidon sponge chains walk them on the device, one
  *                    GPU lane per chain (the S-box values written as it goes, the hashes read back once; timings_ms[0] = 0); fewer run on

@@ -151,6 +151,8 @@ SIGNATURES = {
     "zkg16_prove_fibonacci_batch": (C.c_int, [ctxp, H, H, sz, vp, vp, sz, vp, vp, vp, vp, vp, vp]),
     "zkg16_circuit_linear": (C.c_int, [sz, vp, vp, C.POINTER(C.c_void_p)]),
     "zkg16_linear_solve_host": (C.c_int, [sz, vp, vp, sz, vp]),
+    "zkg16_circuit_linear_general": (C.c_int, [sz, vp, vp, C.POINTER(C.c_void_p)]),
+    "zkg16_linear_solve_general_host": (C.c_int, [sz, vp, vp, sz, vp, vp]),
     "zkg16_linear_r1cs_dims": (C.c_int, [sz, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz * 3)]),
     "zkg16_r1cs_linear": (C.c_int, [ctxp, sz, C.POINTER(H)]),
     "zkg16_witness_linear_batch": (C.c_int, [ctxp, sz, vp, vp, sz, vp, vp, vp]),

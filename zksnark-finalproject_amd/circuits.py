@@ -332,26 +332,39 @@ def _linear_system(what, a, b):
     return a, b, n
 
 
-def _linear_raw(a, b):
+LINEAR_SOLVERS = {"forward": 0, "elimination": 1}       # option "linear_solver"
+
+
+def linear_solver_id(solver):
+    """"forward" | "elimination" -> the value of option "linear_solver"."""
+    if solver not in LINEAR_SOLVERS:
+        raise ValueError("solver must be 'forward' or 'elimination', not %r" % (solver,))
+    return LINEAR_SOLVERS[solver]
+
+
+def _linear_raw(a, b, solver="forward"):
     a, b, n = _linear_system("linear_circuit", a, b)
+    name = "zkg16_circuit_linear_general" if linear_solver_id(solver) else "zkg16_circuit_linear"
     h = C.c_void_p()
-    rc = _lib.load().zkg16_circuit_linear(n, a.ctypes.data, b.ctypes.data, C.byref(h))
+    rc = getattr(_lib.load(), name)(n, a.ctypes.data, b.ctypes.data, C.byref(h))
     if rc:
-        raise Zkg16Error(rc, "zkg16_circuit_linear")
+        raise Zkg16Error(rc, name)
     return h
 
 
-def linear_circuit(a, b):
+def linear_circuit(a, b, solver="forward"):
     """LinearEquationCircuit for the square system a [n, n], b [n] (u64) with the handler's own solution as the witness
     (zkg16_circuit_linear): x solves the LOWER triangle of a, so the circuit is satisfied exactly when the strict upper triangle
     times x is zero — `satisfied` says which.  Public inputs: a[0][*], b[0], a[1][*], b[1], ...  A zero diagonal entry: Zkg16Error
-    (ZKG16_ERR_UNSUPPORTED; the reference panics)."""
-    return SynthesizedCircuit(_linear_raw(a, b))
+    (ZKG16_ERR_UNSUPPORTED; the reference panics).
+    solver="elimination" (zkg16_circuit_linear_general): the same matrices with x from Gaussian elimination over Fr, satisfied for
+    every a that is non-singular mod r; a singular a: Zkg16Error (ZKG16_ERR_UNSUPPORTED)."""
+    return SynthesizedCircuit(_linear_raw(a, b, solver))
 
 
-def linear_circuit_handle(a, b):
+def linear_circuit_handle(a, b, solver="forward"):
     """linear_circuit as a CircuitHandle (nothing exported to Python)."""
-    return CircuitHandle(_linear_raw(a, b))
+    return CircuitHandle(_linear_raw(a, b, solver))
 
 
 def linear_solve_host(a, b):
@@ -367,6 +380,26 @@ def linear_solve_host(a, b):
     if rc:
         raise Zkg16Error(rc, "zkg16_linear_solve_host")
     return x
+
+
+def linear_solve_general_host(a, b):
+    """Gaussian elimination over Fr with row pivoting for k systems of one size on the host (zkg16_linear_solve_general_host; no GPU;
+    the phase functions of wit_linear_elim_kernel on one lane): a [k, n, n], b [k, n] u64 -> (x [k, n, 4] Montgomery or None, status
+    [k] u32).  status[i] is 0, or 1 + c with c the smallest column index for which columns 0..c of a[i] are linearly dependent mod r;
+    x is None when any request is singular."""
+    a = np.ascontiguousarray(a, dtype=np.uint64)
+    b = np.ascontiguousarray(b, dtype=np.uint64)
+    if a.ndim != 3 or a.shape[1] != a.shape[2] or b.shape != a.shape[:2]:
+        raise ValueError("linear_solve_general_host: a must be k x n x n and b k x n")
+    k, n = b.shape
+    x = np.zeros((k, n, 4), dtype=np.uint64)
+    status = np.zeros(k, dtype=np.uint32)
+    rc = _lib.load().zkg16_linear_solve_general_host(n, a.ctypes.data, b.ctypes.data, k, x.ctypes.data, status.ctypes.data)
+    if rc == 7 and status.any():           # ZKG16_ERR_UNSUPPORTED: some request is singular
+        return None, status
+    if rc:
+        raise Zkg16Error(rc, "zkg16_linear_solve_general_host")
+    return x, status
 
 
 def linear_r1cs_dims(n):

@@ -393,6 +393,10 @@ int set_option_one(zkg16_ctx *ctx, const char *name, int64_t v) {
     if (is("matrix_batch_threads")) return set(o.matrix_batch_threads, 0, 16, v);
     // the batched witness kernels: cap on either grid dimension, 0 = 65535 (tests set 1..3 to run the loops at small K)
     if (is("matrix_batch_grid")) return set(o.matrix_batch_grid, 0, 65535, v);
+    // zkg16_witness_linear_batch / zkg16_prove_linear_batch: 0 (default) = the reference's forward substitution, 1 = Gaussian elimination
+    if (is("linear_solver")) return set(o.linear_solver, 0, 1, v);
+    // wit_linear_elim_kernel: the largest n whose working matrix lies in LDS, 0 = 64 (tests set 1..7 to run the global workspace at small n)
+    if (is("linear_elim_lds_max")) return set(o.linear_elim_lds_max, 0, 64, v);
     // calls with at least this many sponge chains (3K for assignments, k for hashes) walk them on the device (0 restores the default;
     // 1 = always; above 2^32 = never)
     if (is("sponge_chains_min")) {

@@ -874,7 +874,8 @@ int zkg16_prove_fibonacci_batch(zkg16_ctx *ctx, uint64_t pk_handle, uint64_t r1c
 // K requests of the linear-equations handler on one resident key and the n-system's resident matrices: per sub-batch the two-launch
 // assignment pass (witness.hip: linear_batch_assign) and prove_batch_device, after which the sub-batch's assignments go back.  No
 // witness handle exists at any time; proofs and solutions are staged and written only when every sub-batch has succeeded.  A zero
-// diagonal entry anywhere ends the call after the handle checks and before any device work.
+// diagonal entry anywhere ends the call after the handle checks and before any device work (option "linear_solver" = 0); under 1 the
+// assignment pass solves by elimination and a singular request ends the call at that sub-batch's synchronisation.
 int zkg16_prove_linear_batch(zkg16_ctx *ctx, uint64_t pk_handle, uint64_t r1cs_handle, size_t n, const uint64_t *a, const uint64_t *b, size_t k,
                              const uint64_t *r, const uint64_t *s, uint64_t *proofs_out, uint8_t *inf_out, uint64_t *x_out, float *timings_ms) {
     if (!a || !b || !r || !s || !proofs_out || !inf_out || k == 0 || n == 0 || n > ZKG16_LINEAR_N_MAX) return ZKG16_ERR_BAD_ARG;
@@ -888,7 +889,8 @@ int zkg16_prove_linear_batch(zkg16_ctx *ctx, uint64_t pk_handle, uint64_t r1cs_h
     if (k > SIZE_MAX / (d.vars() * sizeof(Fr))) return ZKG16_ERR_BAD_ARG;
     const double t_check = now_ms();
     size_t bad_req = 0, bad_row = 0;
-    if (linear_zero_diagonal(n, a, k, &bad_req, &bad_row)) {
+    const bool elim = ctx->opt.linear_solver == 1;      // elimination: a zero diagonal entry may be solvable, the kernel's status words decide
+    if (!elim && linear_zero_diagonal(n, a, k, &bad_req, &bad_row)) {
         char buf[160];
         snprintf(buf, sizeof buf, "zkg16_prove_linear_batch: request %zu has a zero diagonal entry in row %zu", bad_req, bad_row);
         ctx->last_error = buf;
@@ -899,16 +901,31 @@ int zkg16_prove_linear_batch(zkg16_ctx *ctx, uint64_t pk_handle, uint64_t r1cs_h
     const std::vector<Fr> rr = frs_from_abi(r, k), ss = frs_from_abi(s, k);
     std::vector<uint64_t> xs(4 * k * n);
     double wit_ms = 0;
-    const float prove_ms = prove_in_passes(ctx, h.pk.get(), h.rc.get(), k, d.vars() * sizeof(Fr) + (n * n + n) * sizeof(uint64_t) + n * sizeof(Fr),
-                                           proofs_out, inf_out, [&](size_t off, size_t nb, uint64_t *proofs, uint8_t *infs) {
-        std::vector<std::shared_ptr<WitnessDev>> wit_refs;
-        float dev_ms = 0;
-        linear_batch_assign(ctx, n, a + off * n * n, b + off * n, nb, wit_refs, xs.data() + 4 * off * n, &dev_ms);
-        wit_ms += dev_ms;
-        std::vector<WitnessDev *> wits(nb);
-        for (size_t i = 0; i < nb; i++) wits[i] = wit_refs[i].get();
-        prove_batch_device(ctx, *h.pk, *h.rc, wits.data(), nb, rr.data() + off, ss.data() + off, proofs, infs);
-    });
+    // per proof: the assignment, its input and x; the elimination's global workspace where it is used (one per workgroup, at most one per request)
+    const size_t elim_extra = elim && !linear_elim_in_lds(ctx, n) ? n * (n + 1) * sizeof(Fr) + sizeof(uint32_t) : 0;
+    float prove_ms = 0;
+    try {
+        prove_ms = prove_in_passes(ctx, h.pk.get(), h.rc.get(), k, d.vars() * sizeof(Fr) + (n * n + n) * sizeof(uint64_t) + n * sizeof(Fr) + elim_extra,
+                                   proofs_out, inf_out, [&](size_t off, size_t nb, uint64_t *proofs, uint8_t *infs) {
+            std::vector<std::shared_ptr<WitnessDev>> wit_refs;
+            float dev_ms = 0;
+            try {
+                linear_batch_assign(ctx, n, a + off * n * n, b + off * n, nb, wit_refs, xs.data() + 4 * off * n, &dev_ms);
+            } catch (const LinearSingular &e) {
+                throw LinearSingular{off + e.req, e.col};       // the request's index in the call
+            }
+            wit_ms += dev_ms;
+            std::vector<WitnessDev *> wits(nb);
+            for (size_t i = 0; i < nb; i++) wits[i] = wit_refs[i].get();
+            prove_batch_device(ctx, *h.pk, *h.rc, wits.data(), nb, rr.data() + off, ss.data() + off, proofs, infs);
+        });
+    } catch (const LinearSingular &e) {         // nothing was written: proofs and solutions are staged
+        char buf[200];
+        snprintf(buf, sizeof buf, "zkg16_prove_linear_batch: request %zu is singular: columns 0..%zu of a are linearly dependent (column %zu)", e.req, e.col, e.col);
+        ctx->last_error = buf;
+        if (ctx != root) { std::lock_guard<std::mutex> l(root->lane_mu); root->last_error = buf; }
+        return ZKG16_ERR_UNSUPPORTED;
+    }
     if (prove_ms < 0) return ZKG16_ERR_UNSATISFIED;
     if (x_out) memcpy(x_out, xs.data(), xs.size() * sizeof(uint64_t));
     if (timings_ms) {

@@ -808,6 +808,14 @@ static void linear_solve(size_t n, const uint64_t *a, const uint64_t *b, Fr *x) 
         x[i] = fp_mul(fp_sub(fr_from_u64(b[i]), sum), fp_inv(fr_from_u64(a[i * n + i])));
     }
 }
+// The second solver (option "linear_solver" = 1): the elimination kernel's own phases on one lane (linear_elim_dev.cuh).
+#include "linear_dev.cuh"
+#include "linear_elim_dev.cuh"
+uint32_t linear_solve_general(size_t n, const uint64_t *a, const uint64_t *b, Fr *x) {
+    std::vector<Fr> m(n * (n + 1) + n);
+    std::vector<uint32_t> order(n);
+    return linear_elim_solve_host(n, a, b, m.data(), m.data() + n * (n + 1), order.data(), x);
+}
 // The n-system's matrices from the closed form, as zkg16_circuit_export lays them out: rp[m] n (n + 1) + 1 entries, col / cf
 // 2 n^2 + 2 n, n^2 + n and n^2.  Row i (n + 1) + j: a_ij * x-copy_ij = p_ij.  Row i (n + 1) + n: (-b_i + s_i + sum_j p_ij) * 1 = 0.
 void linear_r1cs_build(size_t n, uint64_t *const rp[3], uint32_t *const col[3], Fr *const cf[3]) {
@@ -909,12 +917,13 @@ int zkg16_fibonacci_results_host(size_t steps, const uint64_t *a, const uint64_t
 // (the sum's seed, 0), then per j an input a_ij, a witness x_j — allocated again in every row — and their product, then the input
 // b_i and enforce_equal(sum, b_i).  `sum += &product` is Circuit::add of an Lc whose ids ascend with a fresh witness: the term is
 // appended (n^2 merges of up to n terms would rebuild the same vector).
-int zkg16_circuit_linear(size_t n, const uint64_t *a, const uint64_t *b, zkg16_circuit **out) {
+static int linear_circuit_build(size_t n, const uint64_t *a, const uint64_t *b, bool general, zkg16_circuit **out) {
     if (!a || !b || !out || n == 0 || n > ZKG16_LINEAR_N_MAX) return ZKG16_ERR_BAD_ARG;
-    if (linear_zero_diagonal(n, a, 1, nullptr, nullptr)) return ZKG16_ERR_UNSUPPORTED;
+    if (!general && linear_zero_diagonal(n, a, 1, nullptr, nullptr)) return ZKG16_ERR_UNSUPPORTED;
     try {
         std::vector<Fr> x(n);
-        linear_solve(n, a, b, x.data());
+        if (!general) linear_solve(n, a, b, x.data());
+        else if (linear_solve_general(n, a, b, x.data())) return ZKG16_ERR_UNSUPPORTED;
         std::unique_ptr<zkg16_circuit> c(new zkg16_circuit());
         Circuit &cs = c->add_segment(0);
         cs.instance.reserve(1 + n * (n + 1));
@@ -938,6 +947,10 @@ int zkg16_circuit_linear(size_t n, const uint64_t *a, const uint64_t *b, zkg16_c
     return ZKG16_OK;
 }
 
+int zkg16_circuit_linear(size_t n, const uint64_t *a, const uint64_t *b, zkg16_circuit **out) { return linear_circuit_build(n, a, b, false, out); }
+// The same circuit with x from the elimination: satisfied whenever a is non-singular mod r; a singular a: ZKG16_ERR_UNSUPPORTED.
+int zkg16_circuit_linear_general(size_t n, const uint64_t *a, const uint64_t *b, zkg16_circuit **out) { return linear_circuit_build(n, a, b, true, out); }
+
 // The solver alone for k requests: what the solve kernel (witness.hip) is tested against.  Staged: nothing is written on an error.
 int zkg16_linear_solve_host(size_t n, const uint64_t *a, const uint64_t *b, size_t k, uint64_t *x_out) {
     if (!a || !b || !x_out || k == 0 || n == 0 || n > ZKG16_LINEAR_N_MAX || k > SIZE_MAX / (n * n * sizeof(Fr))) return ZKG16_ERR_BAD_ARG;
@@ -945,6 +958,28 @@ int zkg16_linear_solve_host(size_t n, const uint64_t *a, const uint64_t *b, size
     try {
         std::vector<Fr> x(k * n);
         for (size_t q = 0; q < k; q++) linear_solve(n, a + q * n * n, b + q * n, x.data() + q * n);
+        memcpy(x_out, x.data(), k * n * sizeof(Fr));
+    } catch (const std::bad_alloc &) {
+        return ZKG16_ERR_OOM;
+    }
+    return ZKG16_OK;
+}
+
+// The elimination for k requests: what wit_linear_elim_kernel is tested against.  status_out (nullable, k): 0, or 1 + the smallest c
+// for which columns 0..c of the request's a are linearly dependent — written whenever the arguments are good.  x_out is staged and
+// written only when every request was solved; else ZKG16_ERR_UNSUPPORTED.
+int zkg16_linear_solve_general_host(size_t n, const uint64_t *a, const uint64_t *b, size_t k, uint64_t *x_out, uint32_t *status_out) {
+    if (!a || !b || !x_out || k == 0 || n == 0 || n > ZKG16_LINEAR_N_MAX || k > SIZE_MAX / (n * n * sizeof(Fr))) return ZKG16_ERR_BAD_ARG;
+    try {
+        std::vector<Fr> x(k * n);
+        std::vector<uint32_t> st(k);
+        bool singular = false;
+        for (size_t q = 0; q < k; q++) {
+            st[q] = linear_solve_general(n, a + q * n * n, b + q * n, x.data() + q * n);
+            singular |= st[q] != 0;
+        }
+        if (status_out) memcpy(status_out, st.data(), k * sizeof(uint32_t));
+        if (singular) return ZKG16_ERR_UNSUPPORTED;
         memcpy(x_out, x.data(), k * n * sizeof(Fr));
     } catch (const std::bad_alloc &) {
         return ZKG16_ERR_OOM;

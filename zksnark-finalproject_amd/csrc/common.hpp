@@ -359,6 +359,8 @@ struct zkg16_ctx {
         int batch_max = 0;                            // zkg16_prove_batch / zkg16_prove_matrix_batch: proofs per device pass (0 = as many as fit)
         int matrix_batch_threads = 0;                 // zkg16_witness_matrix_batch / zkg16_prove_matrix_batch: host threads of the sponge chains (0 = 8)
         int matrix_batch_grid = 0;                    // cap on either grid dimension of the batched witness kernels (0 = 65535): beyond it they loop
+        int linear_solver = 0;                        // the linear route's solver: 0 = the reference's forward substitution on the lower triangle, 1 = Gaussian elimination (linear_elim_dev.cuh)
+        int linear_elim_lds_max = 0;                  // wit_linear_elim_kernel: the largest n whose working matrix lies in LDS (0 = 64); above it a global workspace
         int64_t sponge_chains_min = ZKG16_SPONGE_CHAINS_MIN_DEFAULT;             // calls with at least this many sponge chains walk them on the device; above 2^32: never
         int sponge_chain_segment = 0;                 // permutations of a chain per launch of wit_chain_batch_kernel (0 = 256)
         int verify_batch_min = ZKG16_VERIFY_BATCH_MIN_DEFAULT;                   // zkg16_verify_batch: shorter batches are answered by the host form (the measured crossover)
@@ -372,7 +374,7 @@ struct zkg16_ctx {
     size_t circuit_stage_bytes = 0;
     float vb_timings[zk::VERIFY_TIMING_SLOTS] = {0};                    // zkg16_verify_batch_timings (root: the last batch verified on any lane)
     int num_cus = 256;
-    bool lds_attr_fixup[2] = {false, false}, lds_attr_ntt = false;      // hipFuncSetAttribute(max dynamic LDS) done on this device
+    bool lds_attr_fixup[2] = {false, false}, lds_attr_ntt = false, lds_attr_linear_elim = false;      // hipFuncSetAttribute(max dynamic LDS) done on this device
     zk::FixedBaseCache fb_g1, fb_g2;
     zk::DevBuf poseidon_dev;                          // Poseidon MDS + round constants, Montgomery form (witness.hip), uploaded on first use
     std::shared_ptr<zk::PrimeDev> prime_dev;          // PrimeCircuit template + witness program (prime_device.hip), root only, uploaded on first use
@@ -595,6 +597,14 @@ struct LinearDims {
     explicit LinearDims(size_t n) : ni(1 + n * (n + 1)), nw(n * (2 * n + 1)), nc(n * (n + 1)), nnz{2 * n * n + 2 * n, n * n + n, n * n} {}
     size_t vars() const { return ni + nw; }
 };
+// Option "linear_solver" = 1 (Gaussian elimination, linear_elim_dev.cuh): linear_batch_assign launches wit_linear_elim_kernel in the
+// solve kernel's place and throws LinearSingular {first singular request of the call's k, the smallest c for which columns 0..c of a
+// are linearly dependent} after the synchronisation.  linear_elim_in_lds: whether a request's working matrix stays in LDS (else
+// n (n + 1) Fr of global workspace per workgroup).  linear_solve_general (circuits.hip, host): the same elimination for one request
+// -> the status word, 0 or 1 + c; x is written only for 0.
+struct LinearSingular { size_t req, col; };
+bool linear_elim_in_lds(const zkg16_ctx *ctx, size_t n);
+uint32_t linear_solve_general(size_t n, const uint64_t *a, const uint64_t *b, Fr *x);
 bool linear_zero_diagonal(size_t n, const uint64_t *a, size_t k, size_t *req, size_t *row);
 void linear_r1cs_build(size_t n, uint64_t *const rp[3], uint32_t *const col[3], Fr *const cf[3]);
 void linear_batch_assign(zkg16_ctx *ctx, size_t n, const uint64_t *a, const uint64_t *b, size_t k,

@@ -519,6 +519,63 @@ __global__ void __launch_bounds__(256) wit_linear_fill_kernel(LinearBatchArgs g)
     }
 }
 
+// ---- the solve by elimination (option "linear_solver" = 1; linear_elim_dev.cuh holds the phases, their value bounds and the status
+// rule).  One workgroup of 256 lanes per request, a grid-stride loop over the requests.  LDS: inv[n] | pick[2], status | order[n], and
+// behind them the working matrix M when n <= the LDS bound (option "linear_elim_lds_max", 64 by default: 133,120 + 2,336 bytes of 160 KiB);
+// above it M is the workgroup's slice of a workspace in global memory (g.work), which __syncthreads orders like the LDS.
+// Per request 4 n + 2 barriers whatever the data: one after the load, three per column (offers in | pivot placed | rows reduced), one
+// after the inversions, one per column of the back substitution.  The offers of column c meet in pick[c & 1]; lane 0 resets the
+// other word while it places the pivot, which nobody reads between those two barriers.  A singular request gets x = 0.
+#include "linear_elim_dev.cuh"
+struct LinearElimArgs {
+    const uint64_t *a, *b;          // k x n x n, k x n
+    Fr *x;                          // k x n
+    uint32_t *status;               // k: 0, or 1 + the column without a pivot
+    Fr *work;                       // gridDim.x x n (n + 1); unused by the LDS form
+    size_t n, k;
+};
+template <bool IN_LDS>
+__global__ void __launch_bounds__(LINEAR_ELIM_LANES) wit_linear_elim_kernel(LinearElimArgs g) {
+    extern __shared__ uint4 linear_lds[];           // all of it dynamic: a static word would come off the 160 KiB the launch may ask for
+    const int lane = (int)threadIdx.x;
+    const size_t n = g.n;
+    Fr *inv = reinterpret_cast<Fr *>(linear_lds);
+    uint32_t *pick = reinterpret_cast<uint32_t *>(inv + n), &status = pick[2], *order = pick + 8;
+    Fr *M = IN_LDS ? inv + n + 1 + (n + 7) / 8 : g.work + (size_t)blockIdx.x * n * (n + 1);
+    for (size_t req = blockIdx.x; req < g.k; req += gridDim.x) {
+        Fr *x = g.x + req * n;
+        linear_elim_load(n, g.a + req * n * n, g.b + req * n, M, order, lane, LINEAR_ELIM_LANES);
+        if (lane == 0) { pick[0] = pick[1] = (uint32_t)n; status = 0; }
+        __syncthreads();
+        for (size_t c = 0; c < n; c++) {
+            const uint32_t offer = linear_elim_offer(n, M, order, c, lane, LINEAR_ELIM_LANES);
+            if (offer < n) atomicMin(&pick[c & 1], offer);
+            __syncthreads();
+            if (lane == 0) {
+                const uint32_t k = pick[c & 1];
+                if (k < n) linear_elim_swap(order, c, k);
+                else if (status == 0) status = (uint32_t)(1 + c);
+                pick[(c + 1) & 1] = (uint32_t)n;
+            }
+            __syncthreads();
+            if (status == 0) linear_elim_reduce(n, M, order, c, lane, LINEAR_ELIM_LANES);
+            __syncthreads();
+        }
+        const bool ok = status == 0;
+        if (ok) linear_elim_invert(n, M, order, inv, lane, LINEAR_ELIM_LANES);
+        else for (size_t i = (size_t)lane; i < n; i += LINEAR_ELIM_LANES) st32(x + i, Fr::zero());
+        __syncthreads();
+        for (size_t c = n; c-- > 0;) {
+            if (ok) {
+                const Fr xc = linear_elim_back(n, M, order, inv, c, lane, LINEAR_ELIM_LANES);
+                if (lane == 0) st32(x + c, xc);
+            }
+            __syncthreads();
+        }
+        if (lane == 0) g.status[req] = status;      // the next request's reset of `status` is this lane's too
+    }
+}
+
 // part_of[i] = the part of a streamed assignment in which variable i becomes valid: 0 = what needs only a and b (the constant,
 // a, b, the zeros, the products; also the three trailing r / s / -rs slots of the z-side scalar vector), 1 + s = the S-box
 // values of the permutations of slice s of every sponge, the last part also the three hashes.
@@ -939,10 +996,17 @@ void fibonacci_batch_assign(zkg16_ctx *ctx, const Fr &ca, const Fr &cb, const ui
     out = std::move(wits);
 }
 
+// whether the elimination keeps a request's working matrix in LDS: n up to option "linear_elim_lds_max" (0 = LINEAR_ELIM_LDS_N)
+bool linear_elim_in_lds(const zkg16_ctx *ctx, size_t n) {
+    return n <= (size_t)(ctx->opt.linear_elim_lds_max > 0 ? ctx->opt.linear_elim_lds_max : LINEAR_ELIM_LDS_N);
+}
+
 // The k assignments of one size on ctx->stream, under ctx's mutex: a | b go up in one copy out of the ctx's pinned staging (8 bytes
 // per input value; the assignments lie one after the other in one allocation, so no address table travels), the solve and the fill
 // launch, the k x n solutions come back, one synchronisation.  `x` (nullable) is written only when all of it succeeded; when this
-// throws the stream has been drained.  No request has a zero diagonal entry: the entries have checked.
+// throws the stream has been drained.  Option "linear_solver" = 0: no request has a zero diagonal entry, the entries have checked.
+// 1: the elimination kernel takes the solve kernel's place and the k status words come back with x; a singular request throws
+// LinearSingular after the synchronisation, nothing written.
 void linear_batch_assign(zkg16_ctx *ctx, size_t n, const uint64_t *a, const uint64_t *b, size_t k,
                          std::vector<std::shared_ptr<WitnessDev>> &out, uint64_t *x, float *dev_ms) {
     auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
@@ -950,7 +1014,9 @@ void linear_batch_assign(zkg16_ctx *ctx, size_t n, const uint64_t *a, const uint
     const size_t vars = d.vars(), a_bytes = k * n * n * sizeof(uint64_t), in_bytes = a_bytes + k * n * sizeof(uint64_t);
     const size_t x_off = up(in_bytes), x_bytes = k * n * sizeof(Fr);
     const size_t cap = ctx->opt.matrix_batch_grid > 0 ? (size_t)ctx->opt.matrix_batch_grid : 65535;
-    mbatch_staging_ensure(ctx, x_off + x_bytes);
+    const bool elim = ctx->opt.linear_solver == 1, elim_lds = linear_elim_in_lds(ctx, n);
+    const size_t st_bytes = elim ? k * sizeof(uint32_t) : 0;        // the status words lie behind x: one copy brings both back
+    mbatch_staging_ensure(ctx, x_off + x_bytes + st_bytes);
     auto backing = std::make_shared<DevBuf>(k * vars * sizeof(Fr));
     std::vector<std::shared_ptr<WitnessDev>> wits(k);
     for (size_t i = 0; i < k; i++) {
@@ -977,7 +1043,27 @@ void linear_batch_assign(zkg16_ctx *ctx, size_t n, const uint64_t *a, const uint
     g.x = reinterpret_cast<Fr *>(ds + x_off);
     g.z = backing->as<Fr>();
     g.n = n; g.k = k; g.vars = vars;
-    {
+    DevBuf elim_work;
+    if (elim) {
+        const unsigned blocks = (unsigned)(k < cap ? k : cap);
+        const size_t small = (n + 1 + (n + 7) / 8) * sizeof(Fr), m_bytes = n * (n + 1) * sizeof(Fr), lds = small + (elim_lds ? m_bytes : 0);
+        LinearElimArgs e;
+        e.a = g.a; e.b = g.b; e.x = g.x;
+        e.status = reinterpret_cast<uint32_t *>(ds + x_off + x_bytes);
+        e.work = nullptr;
+        e.n = n; e.k = k;
+        if (!elim_lds) {
+            elim_work.alloc(blocks * m_bytes);
+            e.work = elim_work.as<Fr>();
+        } else if (lds > 64 * 1024 && !ctx->lds_attr_linear_elim) {      // above the 64 KiB default dynamic-LDS cap
+            ZK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(wit_linear_elim_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            ctx->lds_attr_linear_elim = true;
+        }
+        ScopedKernelTimer kt(ctx, "wit_linear_elim_kernel", (double)k * (double)n * (double)n * (double)n / 3);
+        if (elim_lds) hipLaunchKernelGGL(wit_linear_elim_kernel<true>, dim3(blocks), dim3(LINEAR_ELIM_LANES), lds, ctx->stream, e);
+        else hipLaunchKernelGGL(wit_linear_elim_kernel<false>, dim3(blocks), dim3(LINEAR_ELIM_LANES), lds, ctx->stream, e);
+        ZK_HIP(hipGetLastError());
+    } else {
         ScopedKernelTimer kt(ctx, "wit_linear_solve_kernel", (double)k * (double)n * (double)n / 2);
         hipLaunchKernelGGL(wit_linear_solve_kernel, dim3((unsigned)(k < cap ? k : cap)), dim3(LINEAR_LANES), n * sizeof(Fr), ctx->stream, g);
         ZK_HIP(hipGetLastError());
@@ -988,10 +1074,15 @@ void linear_batch_assign(zkg16_ctx *ctx, size_t n, const uint64_t *a, const uint
         hipLaunchKernelGGL(wit_linear_fill_kernel, dim3((unsigned)(bx < cap ? bx : cap)), dim3(256), 0, ctx->stream, g);
         ZK_HIP(hipGetLastError());
     }
-    ZK_HIP(hipMemcpyAsync(hs + x_off, ds + x_off, x_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    ZK_HIP(hipMemcpyAsync(hs + x_off, ds + x_off, x_bytes + st_bytes, hipMemcpyDeviceToHost, ctx->stream));
     ZK_HIP(hipEventRecord(e1, ctx->stream));
     ZK_HIP(hipStreamSynchronize(ctx->stream));      // the staging is free again, and the assignments are whole
     drain.ok = true;
+    if (elim) {
+        const uint32_t *st = reinterpret_cast<const uint32_t *>(hs + x_off + x_bytes);
+        for (size_t i = 0; i < k; i++)
+            if (st[i]) throw LinearSingular{i, (size_t)st[i] - 1};
+    }
     float ms = 0;
     ZK_HIP(hipEventElapsedTime(&ms, e0, e1));
     if (dev_ms) *dev_ms = ms;
@@ -1162,7 +1253,7 @@ int zkg16_witness_linear_batch(zkg16_ctx *ctx, size_t n, const uint64_t *a, cons
     const double check_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
     std::lock_guard<std::mutex> lk(ctx->mu);
     try {
-        if (zero_diag) {
+        if (zero_diag && ctx->opt.linear_solver == 0) {
             char buf[160];
             snprintf(buf, sizeof buf, "zkg16_witness_linear_batch: request %zu has a zero diagonal entry in row %zu", bad_req, bad_row);
             ctx->last_error = buf;
@@ -1188,6 +1279,11 @@ int zkg16_witness_linear_batch(zkg16_ctx *ctx, size_t n, const uint64_t *a, cons
             timings_ms[1] = dev_ms;
             timings_ms[2] = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
         }
+    } catch (const LinearSingular &e) {
+        char buf[200];
+        snprintf(buf, sizeof buf, "zkg16_witness_linear_batch: request %zu is singular: columns 0..%zu of a are linearly dependent (column %zu)", e.req, e.col, e.col);
+        ctx->last_error = buf;
+        return ZKG16_ERR_UNSUPPORTED;
     } catch (const HipError &e) {
         char buf[512];
         snprintf(buf, sizeof buf, "%s failed: %s (%s:%d)", e.what, hipGetErrorString(e.err), e.file, e.line);

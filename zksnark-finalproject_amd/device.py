@@ -1,4 +1,5 @@
 """Thin object layer over the C ABI: one `Device` == one zkg16_ctx == one MI355X."""
+import contextlib
 import ctypes as C
 import threading
 
@@ -31,6 +32,7 @@ class Device:
         # MatrixCircuit shapes resident on this device, by size (handlers._matrix_shape); entries have .rh
         self._matrix_shapes = {}
         self._matrix_shapes_lock = threading.Lock()
+        self._options = {}              # what set_option was last given, by name (the ABI has no getter)
         self.lib = _lib.load()
         self.ctx = C.c_void_p()
         ids = (C.c_int * 1)(device_id)
@@ -447,16 +449,36 @@ class Device:
             raise ValueError(what + ": a must be k x n x n and b k x n")
         return a, b, a.shape[0], a.shape[1]
 
-    def witness_linear_batch(self, a, b):
+    @contextlib.contextmanager
+    def _linear_solver(self, solver):
+        """Option "linear_solver" set to `solver` ("forward" | "elimination") for the body and put back to what set_option last gave
+        it (0 if never set).  None: the option stays as it is."""
+        if solver is None:
+            yield
+            return
+        from .circuits import linear_solver_id
+        before = self._options.get("linear_solver", 0)
+        self.set_option("linear_solver", linear_solver_id(solver))
+        try:
+            yield
+        finally:
+            self.set_option("linear_solver", before)
+
+    def witness_linear_batch(self, a, b, solver=None):
         """The linear-equations assignments of k requests of one size, a [k, n, n] and b [k, n] u64, built in one device pass
         (zkg16_witness_linear_batch: the solve kernel, one wave per request, and the fill kernel) -> (witness handles [k], x [k, n, 4]
         = the handler's solutions, dict of ms: host checks / device / whole call).  Handle i holds what circuit_load of
-        linear_circuit(a[i], b[i]) would; each is freed on its own."""
+        linear_circuit(a[i], b[i]) would; each is freed on its own.
+        solver: "forward" (the reference's substitution on the lower triangle) or "elimination" (Gaussian elimination over Fr, the
+        elimination kernel in the solve kernel's place: handle i holds what linear_circuit(a[i], b[i], solver="elimination") exports;
+        a singular request fails the whole call with status 7) — option "linear_solver" is set for this call and restored; None
+        (default): the option as the ctx has it, "forward" unless set."""
         a, b, k, n = self._linear_batch("witness_linear_batch", a, b)
         handles = np.zeros(k, dtype=np.uint64)
         x = np.zeros((k, n, 4), dtype=np.uint64)
         ms = (C.c_float * 3)()
-        self._check(self.lib.zkg16_witness_linear_batch(self.ctx, n, _ptr(a), _ptr(b), k, _ptr(handles), _ptr(x), C.addressof(ms)))
+        with self._linear_solver(solver):
+            self._check(self.lib.zkg16_witness_linear_batch(self.ctx, n, _ptr(a), _ptr(b), k, _ptr(handles), _ptr(x), C.addressof(ms)))
         return handles, x, dict(host_check_ms=float(ms[0]), device_ms=float(ms[1]), call_ms=float(ms[2]))
 
     def poseidon_hash_batch(self, elems):
@@ -715,12 +737,14 @@ class Device:
                                                          _ptr(inf), _ptr(pub), C.addressof(ms)))
         return proofs, inf, pub, dict(host_coeffs_ms=float(ms[0]), witness_ms=float(ms[1]), prove_ms=float(ms[2]), call_ms=float(ms[3]))
 
-    def prove_linear_batch(self, pk_h, r1cs_h, a, b, rs, ss):
+    def prove_linear_batch(self, pk_h, r1cs_h, a, b, rs, ss, solver=None):
         """k linear-handler requests of one size on one resident key, a [k, n, n] and b [k, n] u64, rs / ss [k, 4]: assignments and
         proofs in batched device passes (zkg16_prove_linear_batch) -> (proofs [k, 48], inf [k, 3], x [k, n, 4], dict of ms).  pk_h: a
         key set up on r1cs_linear(n) = r1cs_h.  Proof i is byte-identical to prove_resident on the circuit_load handles of
         linear_circuit(a[i], b[i]) with (rs[i], ss[i]) — a proof no verifier accepts when the request's a is not lower-triangular
-        enough for the handler's solver (option "check_satisfied" refuses such a batch instead)."""
+        enough for the handler's solver (option "check_satisfied" refuses such a batch instead).  solver: as witness_linear_batch's;
+        with "elimination" proof i is prove_resident's on linear_circuit(a[i], b[i], solver="elimination") and verifies for every
+        non-singular a[i]."""
         a, b, k, n = self._linear_batch("prove_linear_batch", a, b)
         rs = _u64(rs).reshape(-1, 4)
         ss = _u64(ss).reshape(-1, 4)
@@ -730,8 +754,9 @@ class Device:
         inf = np.zeros((k, 3), dtype=np.uint8)
         x = np.zeros((k, n, 4), dtype=np.uint64)
         ms = (C.c_float * 4)()
-        self._check(self.lib.zkg16_prove_linear_batch(self.ctx, pk_h, r1cs_h, n, _ptr(a), _ptr(b), k, _ptr(rs), _ptr(ss), _ptr(proofs),
-                                                      _ptr(inf), _ptr(x), C.addressof(ms)))
+        with self._linear_solver(solver):
+            self._check(self.lib.zkg16_prove_linear_batch(self.ctx, pk_h, r1cs_h, n, _ptr(a), _ptr(b), k, _ptr(rs), _ptr(ss), _ptr(proofs),
+                                                          _ptr(inf), _ptr(x), C.addressof(ms)))
         return proofs, inf, x, dict(host_check_ms=float(ms[0]), witness_ms=float(ms[1]), prove_ms=float(ms[2]), call_ms=float(ms[3]))
 
     def prove_prime_batch(self, pk_h, r1cs_h, corr, gamma_abc0, xs, js, rs, ss, public_inputs=True):
@@ -878,6 +903,7 @@ class Device:
 
     def set_option(self, name, value):
         self._check(self.lib.zkg16_set_option(self.ctx, name.encode(), int(value)))
+        self._options[name] = int(value)
 
 
 def z_costs(r1cs, z_mont, num_instance):

@@ -30,7 +30,7 @@ import numpy as np
 
 from . import _lib, device, wire
 from ._lib import Zkg16Error
-from .circuits import (fibonacci_circuit, fibonacci_circuit_handle, linear_circuit, linear_circuit_handle, linear_r1cs_dims, matrix_circuit, matrix_hash_batch_host, prime_circuit, prime_dims, prime_key_corrections,
+from .circuits import (fibonacci_circuit, fibonacci_circuit_handle, linear_circuit, linear_circuit_handle, linear_r1cs_dims, linear_solver_id, matrix_circuit, matrix_hash_batch_host, prime_circuit, prime_dims, prime_key_corrections,
                        prime_public_inputs, prime_search, prime_vk_extend)
 from .workloads import R_MOD, g1_generator, g2_generator
 
@@ -387,7 +387,7 @@ def _linear_public_inputs(a, b):
     return np.stack([_fr_mont(int(v)) for v in np.concatenate([a, b[:, None]], axis=1).reshape(-1)])
 
 
-def prove_linear_equations(dev, a, b, seed=0, keep_key=False, check_on_device=False):
+def prove_linear_equations(dev, a, b, seed=0, keep_key=False, check_on_device=False, solver="forward"):
     """Mirror of prove_linear_equations (backend/linear_equations.rs:43-106): solve the system with the handler's forward
     substitution, build LinearEquationCircuit, circuit-specific setup, prove, verify against a[0][*], b[0], a[1][*], b[1], ...
     The solver is only right for a lower-triangular a: for any other a the circuit is in general unsatisfied, the proof is made all the
@@ -398,13 +398,16 @@ def prove_linear_equations(dev, a, b, seed=0, keep_key=False, check_on_device=Fa
     prints Rust Debug strings; "num_constraints" and "num_variables" (the instance count) are the real system's, where upstream
     reports 0 and 1 from a constraint system it never synthesizes into (:62, :100-101); "proving_time" and "verifying_time" are
     measured, where upstream returns 0.0; "valid" is the verifier's answer, which upstream computes and drops.
-    check_on_device: "satisfied" is added, the verdict of Device.r1cs_check on the request's handles."""
+    check_on_device: "satisfied" is added, the verdict of Device.r1cs_check on the request's handles.
+    solver: "forward" is the above; "elimination" solves a x = b by Gaussian elimination over Fr (circuits.linear_circuit's
+    solver=), so "valid" (and "satisfied") is True for every a that is non-singular mod r, and a singular a raises Zkg16Error
+    (ZKG16_ERR_UNSUPPORTED) as a zero diagonal does.  Key, matrices and public inputs do not depend on the solver."""
     a, b = _linear_request("prove_linear_equations", a, b)
     if keep_key:
-        circ = linear_circuit(a, b)
+        circ = linear_circuit(a, b, solver=solver)
         sources = _from_host(dev, circ)
     else:
-        circ = linear_circuit_handle(a, b)
+        circ = linear_circuit_handle(a, b, solver=solver)
         sources = _from_handle(dev, circ)
     out = _request(dev, random.Random(seed), circ, *sources, keep_key=keep_key, check_on_device=check_on_device)
     t0 = time.perf_counter()
@@ -431,15 +434,18 @@ def linear_key(dev, n, rng):
     return dict(ph=ph, rh=rh, vk=vk, setup_time=setup_time)
 
 
-def prove_linear_equations_batch(dev, systems, seed=0, key=None, check_on_device=False):
+def prove_linear_equations_batch(dev, systems, seed=0, key=None, check_on_device=False, solver="forward"):
     """K requests of the linear handler of one size, systems = [(a, b), ...], under ONE key, assignments and proofs in batched device
     passes (Device.prove_linear_batch).  The key is set up once from `seed` with prove_linear_equations' draws (then r, s per
     request), so request 0 is that handler's proof and key for that seed, byte for byte; or it is passed in as key= (linear_key's
     dict), which stays the caller's.  The key's two encodings are made once, and the K proofs are verified together on the host.
     -> a list of prove_linear_equations' fields per request; proving_time and verifying_time are the batch's divided by K.
     check_on_device: the assignments are built as handles (Device.witness_linear_batch), checked together
-    (Device.r1cs_check_batch) and proved with Device.prove_batch — the same proof bytes — and every record gets "satisfied"."""
+    (Device.r1cs_check_batch) and proved with Device.prove_batch — the same proof bytes — and every record gets "satisfied".
+    solver: "forward", or "elimination" (the device passes run under option "linear_solver" = 1): every non-singular request's
+    record has valid True, and a singular request raises Zkg16Error (ZKG16_ERR_UNSUPPORTED) for the whole batch."""
     k = len(systems)
+    how = {} if linear_solver_id(solver) == 0 else dict(solver=solver)        # "forward": the Device calls as they always were
     if k == 0:
         raise ValueError("prove_linear_equations_batch: no requests")
     reqs = [_linear_request("prove_linear_equations_batch", a, b) for a, b in systems]
@@ -458,7 +464,7 @@ def prove_linear_equations_batch(dev, systems, seed=0, key=None, check_on_device
         t0 = time.perf_counter()
         verdicts, check_time = None, 0.0
         if check_on_device:
-            whs, xs, ms = dev.witness_linear_batch(a, b)
+            whs, xs, ms = dev.witness_linear_batch(a, b, **how)
             for wh in whs:
                 stack.callback(dev.witness_free, int(wh))
             tc = time.perf_counter()
@@ -466,7 +472,7 @@ def prove_linear_equations_batch(dev, systems, seed=0, key=None, check_on_device
             check_time = time.perf_counter() - tc
             proofs, inf = dev.prove_batch(key["ph"], key["rh"], whs, rs, ss)
         else:
-            proofs, inf, xs, ms = dev.prove_linear_batch(key["ph"], key["rh"], a, b, rs, ss)
+            proofs, inf, xs, ms = dev.prove_linear_batch(key["ph"], key["rh"], a, b, rs, ss, **how)
         proving_time = time.perf_counter() - t0 - check_time
     vk = key["vk"]
     vk_b64, pvk_b64 = wire.encode_vk(vk), wire.encode_pvk(vk)
