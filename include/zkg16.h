@@ -359,7 +359,9 @@ ZKG16_API int zkg16_final_exp_batch(zkg16_ctx *ctx, const uint64_t *f /* n x 72 
  * [8] zkg16_verify_batch_wire only: the decompress kernels (device events; the host decode's wall time when the host form answered);
  * [9] the per-proof pass that took over from bisecting (device events; 0 when it did not run; its time is part of [5] too),
  * [10] the number of range tests bisecting made; [11] zkg16_verify_prime_batch[_wire] only: the inputs kernel, [12] the sums
- * kernels (device events; both 0 when the host form answered or the call was not a prime call).
+ * kernels (device events; both 0 when the host form answered or the call was not a prime call); [13] zkg16_verify_batch_u64[_wire]
+ * only: the sums kernels, [14] the X kernel of its per-proof pass (device events; 0 when the host form answered, the call was not
+ * a u64 call or, for [14], the per-proof pass did not run); in those calls [10] counts the test of the whole batch too.
  * Returns the number of entries written (at most cap). */
 ZKG16_API int zkg16_verify_batch_timings(zkg16_ctx *ctx, float *ms, int cap);
 
@@ -404,6 +406,54 @@ ZKG16_API int zkg16_prime_inputs_batch(zkg16_ctx *ctx, const uint64_t *xs, const
                              uint64_t *public_inputs);
 ZKG16_API int zkg16_prime_rho_sums(zkg16_ctx *ctx, const uint64_t *xs, const uint64_t *js, const uint64_t *rho, const uint8_t *live, size_t k,
                          uint64_t *sums);
+
+/* ---- the u64 form: K proofs under one key whose public inputs are all plain 64-bit values (the linear-equations route: its
+ * n^2 + n inputs a[0][*], b[0], a[1][*], b[1], ... are the row-major matrix [a | b]).  values = k x (num_instance - 1) u64,
+ * row-major: 8 bytes per input where zkg16_verify_batch takes 32, and nothing is converted on the host unless bisecting runs.
+ * zkg16_verify_batch_u64_host: the values expanded to Montgomery limbs, then zkg16_verify_batch_host; no ctx, no GPU.  It is the
+ * reference for every verdict of the calls below.
+ * zkg16_verify_batch_u64 / zkg16_verify_batch_u64_wire: zkg16_verify_batch / _wire with the inputs' share of the work on the device.
+ * The values go up once; the num_instance multiplier sums s_0 = sum rho_k, s_{1+c} = sum_k rho_k values[k][c] of the member proofs
+ * are taken in a kernel as plain integers (rho < 2^128, values < 2^64, k < 2^32: every sum stays below 2^224 < r, nothing is
+ * reduced on the device); sum_i s_i gamma_abc_g1[i] is one G1 MSM of the ctx over the key's points with those sums as scalars,
+ * and the test of the whole batch takes that point — the host walks neither K x (num_instance - 1) inputs nor num_instance scalar
+ * multiplications.  The host cross-checks s_0 against its own sum of the multipliers; on a mismatch the device sums are refused,
+ * the verdicts come from host-expanded inputs and the call reports ZKG16_ERR_HIP.  Narrower ranges (bisecting) are computed on
+ * the host from inputs expanded on demand.
+ * The per-proof pass (zkg16_verify_each_u64, and the take-over from bisecting) makes X_k = gamma_abc[0] + sum_c values[k][c]
+ * gamma_abc[1 + c] with each proof spread over L lanes (the smallest power of two >= min(num_instance - 1, 64)), one shared
+ * doubling chain of 64 steps per lane; the Miller and final-exponentiation kernels of zkg16_verify_each follow unchanged.
+ * In these entries the test of the whole batch counts as the first range test and an UNSET option "verify_each_after" means 1: the
+ * per-proof pass decides every member proof right after that test fails (each further range test costs num_instance host scalar
+ * multiplications here; the default of 32 was derived at num_instance = 4).  A value the caller set is honoured (a value above
+ * 2k bisects to the end).  Below "verify_batch_min" / "verify_wire_min" the host form answers; those thresholds were measured
+ * for zkg16_verify_batch / _wire at num_instance = 4 and are reused here, this form's own crossover is not measured.
+ * num_instance < 2, null values and k >= 2^32: ZKG16_ERR_BAD_ARG before any work, outputs untouched; every other argument check,
+ * undecodable proofs, membership failures, ok_each, decode_status and passes of 65,536 proofs as zkg16_verify_batch / _wire / _each. */
+ZKG16_API int zkg16_verify_batch_u64_host(const uint64_t *gamma_abc_g1, size_t num_instance, const uint64_t alpha_beta[72],
+                                const uint64_t *gamma_neg_coeffs, const uint64_t *delta_neg_coeffs, size_t n_coeffs,
+                                const uint64_t *values /* k x (num_instance - 1) */, const uint64_t *proofs, const uint8_t *inf,
+                                const uint64_t *rho, size_t k, int threads, int *ok, uint8_t *ok_each);
+ZKG16_API int zkg16_verify_batch_u64(zkg16_ctx *ctx, const uint64_t *gamma_abc_g1, size_t num_instance, const uint64_t alpha_beta[72],
+                           const uint64_t *gamma_neg_coeffs, const uint64_t *delta_neg_coeffs, size_t n_coeffs,
+                           const uint64_t *values, const uint64_t *proofs, const uint8_t *inf, const uint64_t *rho, size_t k,
+                           int *ok, uint8_t *ok_each);
+ZKG16_API int zkg16_verify_batch_u64_wire(zkg16_ctx *ctx, const uint64_t *gamma_abc_g1, size_t num_instance, const uint64_t alpha_beta[72],
+                                const uint64_t *gamma_neg_coeffs, const uint64_t *delta_neg_coeffs, size_t n_coeffs,
+                                const uint64_t *values, const uint8_t *proof_bytes /* k x 192 */, const uint64_t *rho, size_t k,
+                                int *ok, uint8_t *ok_each, uint8_t *decode_status);
+ZKG16_API int zkg16_verify_each_u64(zkg16_ctx *ctx, const uint64_t *gamma_abc_g1, size_t num_instance, const uint64_t alpha_beta[72],
+                          const uint64_t *gamma_neg_coeffs, const uint64_t *delta_neg_coeffs, size_t n_coeffs,
+                          const uint64_t *values, const uint64_t *proofs, const uint8_t *inf, size_t k, uint8_t *ok_each);
+/* Stage entries (tests / tools).  zkg16_u64_rho_sums: sums ((m + 1) x 4 u64, plain integers, unreduced) = sum_k rho_k
+ * (1, values[k][0 .. m)) over the proofs with live[k] != 0 (live null: all); m >= 1, k < 2^32; k == 0: ZKG16_OK, nothing written.
+ * zkg16_u64_prepared_inputs: x_out[j] (12 u64, affine Montgomery limbs; zeros with inf_out[j] = 1 for the point at infinity) =
+ * gamma_abc_g1[0] + sum_c values[idx[j]][c] gamma_abc_g1[1 + c], j < n (idx null: row j; idx entries index rows of values, which
+ * must hold them all); gamma_abc_g1 with all-zero limbs = the point at infinity; n == 0: ZKG16_OK, nothing written. */
+ZKG16_API int zkg16_u64_rho_sums(zkg16_ctx *ctx, const uint64_t *values, size_t m, const uint64_t *rho, const uint8_t *live, size_t k,
+                       uint64_t *sums /* (m + 1) x 4 */);
+ZKG16_API int zkg16_u64_prepared_inputs(zkg16_ctx *ctx, const uint64_t *gamma_abc_g1, size_t num_instance, const uint64_t *values,
+                              const uint32_t *idx, size_t n, uint64_t *x_out /* n x 12 */, uint8_t *inf_out /* n */);
 
 /* prod_i e(P_i, Q_i) == 1 ?  Host-only (no ctx, no GPU).  g1: n x 12 limbs, g2: n x 24 limbs, flag bytes nullable.
  * flags: ZKG16_PAIRING_PLAIN_FINAL_EXP = final exponentiation as one plain power by (q^12-1)/r (slow cross-check of the

@@ -1,0 +1,335 @@
+"""The u64 form of batched verification on the device (zkg16_verify_batch_u64, zkg16_verify_batch_u64_wire, zkg16_verify_each_u64, the
+stage entries zkg16_u64_rho_sums / zkg16_u64_prepared_inputs, handlers.verify_linear_equations(dev=dev)): the kernels against Python
+integers and the oracle's points limb for limb, real proofs of prove_linear_batch, simulated statements whose verdicts are known by
+construction (tests/u64_verify_cases.py), and the existing batch entries on an ordinary batch.
+
+The X-kernel slot of the timings (u64_x_ms) is asserted > 0 where the per-proof pass runs, on the batches with negatives; a valid
+batch never runs that pass, so there the slot is asserted to be 0."""
+import base64
+import ctypes as C
+import random
+
+import numpy as np
+import pytest
+
+import linear_cases as LC
+import pyref as P
+import sim_proofs as S
+import u64_verify_cases as U
+import verify_batch_cases as VB
+from helpers import *
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def dev():
+    from zksnark_finalproject_amd import Device
+    d = Device(0)
+    d.set_option("verify_batch_min", 1)         # every batch of this module runs the kernels unless a test says otherwise
+    d.set_option("verify_wire_min", 1)
+    yield d
+    d.close()
+
+
+def thresholds(dev, batch_min, wire_min):
+    dev.set_option("verify_batch_min", batch_min)
+    dev.set_option("verify_wire_min", wire_min)
+
+
+# ------------------------------------------------------------------------------------------------ the stage entries
+@pytest.mark.parametrize("case_", list(U.sum_cases()), ids=lambda c: c[0])
+def test_u64_rho_sums_equal_python_integers(dev, case_):
+    name, vals, rhos, live = case_
+    assert dev.u64_rho_sums(vals, S.rho_rows(rhos), live) == U.sums_want(name, vals, rhos, live)
+
+
+def test_u64_rho_sums_across_a_launch_boundary(dev):
+    vals, rhos, live = U.boundary_case()
+    assert dev.u64_rho_sums(vals, S.rho_rows(rhos), live) == U.py_sums(vals, rhos, live)
+    # k == 0: fine, nothing written
+    sums = np.full((3, 4), 0x5A, dtype=np.uint64)
+    assert dev.lib.zkg16_u64_rho_sums(dev.ctx, None, 2, None, None, 0, sums.ctypes.data) == 0 and (sums == 0x5A).all()
+    assert dev.lib.zkg16_u64_rho_sums(dev.ctx, vals.ctypes.data, 0, vals.ctypes.data, None, 1, sums.ctypes.data) == 1 and (sums == 0x5A).all()
+
+
+X_ROWS = 130
+
+
+@pytest.mark.parametrize("family", U.X_FAMILIES)
+@pytest.mark.parametrize("m", U.X_MS)
+def test_u64_prepared_inputs_equal_the_oracle(dev, oracle, family, m):
+    xc = U.x_case(oracle, family, m, X_ROWS)
+    for n in (1, 63, 65, 130):
+        got, inf = dev.u64_prepared_inputs(xc.gabc, xc.values[:n])
+        assert np.array_equal(inf, xc.want_inf[:n]) and np.array_equal(got, xc.want[:n]), (family, m, n)
+    # a list of rows: a permutation with repeats, the rows at infinity and the all-zero row among them
+    rng = random.Random(m)
+    idx = np.array([0, 1, 2, 129, 129, 0] + [rng.randrange(X_ROWS) for _ in range(64)], dtype=np.uint32)
+    got, inf = dev.u64_prepared_inputs(xc.gabc, xc.values, idx)
+    assert np.array_equal(inf, xc.want_inf[idx]) and np.array_equal(got, xc.want[idx]), (family, m)
+
+
+def test_u64_prepared_inputs_arguments(dev, oracle):
+    xc = U.x_case(oracle, "random", 3, X_ROWS)
+    out, inf = np.full((2, 12), 0x5A, dtype=np.uint64), np.full(2, 9, dtype=np.uint8)
+    call = lambda g, ni, v, n: dev.lib.zkg16_u64_prepared_inputs(dev.ctx, g, ni, v, None, n, out.ctypes.data, inf.ctypes.data)
+    vals = np.ascontiguousarray(xc.values[:2])
+    assert call(None, 4, vals.ctypes.data, 2) == 1 and call(xc.gabc.ctypes.data, 1, vals.ctypes.data, 2) == 1 and call(xc.gabc.ctypes.data, 4, None, 2) == 1
+    assert call(xc.gabc.ctypes.data, 4, vals.ctypes.data, 0) == 0
+    assert (out == 0x5A).all() and (inf == 9).all()
+
+
+# ------------------------------------------------------------------------------------------------ real proofs
+N_LIN, K_LIN = 3, 4
+
+
+@pytest.fixture(scope="module")
+def proved(dev):
+    """one linear_key at n = 3 and 4 proofs of lower-triangular systems from prove_linear_batch -> dict(pvk, a, b, values, proofs, inf)"""
+    from zksnark_finalproject_amd import handlers
+    from zksnark_finalproject_amd.device import pvk_prepare
+    rng = random.Random(0x6401)
+    key = handlers.linear_key(dev, N_LIN, rng)
+    try:
+        a, b = LC.lower_requests(N_LIN, K_LIN, seed=40)
+        rs, ss = handlers._draw_rs_batch(rng, K_LIN)
+        proofs, inf, _, _ = dev.prove_linear_batch(key["ph"], key["rh"], a, b, rs, ss)
+    finally:
+        dev.pk_free(key["ph"])
+        dev.r1cs_free(key["rh"])
+    values = np.ascontiguousarray(np.concatenate([a, b[:, :, None]], axis=2).reshape(K_LIN, N_LIN * (N_LIN + 1)))
+    return dict(vk=key["vk"], pvk=pvk_prepare(key["vk"]), a=a, b=b, values=values, proofs=np.asarray(proofs, dtype=np.uint64), inf=np.asarray(inf, dtype=np.uint8))
+
+
+def _wire(proofs, inf):
+    return VB.to_wire(VB.Batch(None, None, proofs, inf))
+
+
+def _loop(pvk, values, proofs, inf):
+    from zksnark_finalproject_amd.device import verify_prepared
+    pubs = U.expand(values)
+    return np.array([verify_prepared(pvk, pubs[i], proofs[i], inf[i]) for i in range(len(proofs))], dtype=bool)
+
+
+def test_real_proofs_verify(dev, proved):
+    from zksnark_finalproject_amd.handlers import _linear_public_inputs
+    pvk, values, proofs, inf = proved["pvk"], proved["values"], proved["proofs"], proved["inf"]
+    assert np.array_equal(U.expand(values[0]), _linear_public_inputs(proved["a"][0], proved["b"][0]))      # the handler's input order
+    assert _loop(pvk, values, proofs, inf).all()
+    rho = VB.draw_rho(random.Random(1), K_LIN)
+    ok, each = dev.verify_batch_u64(pvk, values, proofs, inf, rho=rho, each=True)
+    assert ok is True and each.all()
+    tm = dev.verify_batch_timings(u64=True)
+    # the whole-batch test is the one range test; a valid batch never runs the per-proof pass, so its X kernel has no time
+    assert tm["u64_sums_ms"] > 0 and tm["host_form"] == 0 and tm["range_tests"] == 1 and tm["u64_x_ms"] == 0 and tm["each_ms"] == 0
+    assert tm["prime_inputs_ms"] == 0 and tm["prime_sums_ms"] == 0
+    assert list(tm)[:13] == list(dev.verify_batch_timings(prime=True)) and len(tm) == 15 and list(tm)[13:] == ["u64_sums_ms", "u64_x_ms"]
+    ok, each = dev.verify_batch_u64_wire(pvk, values, _wire(proofs, inf), each=True)          # rho from `secrets`
+    assert ok is True and each.all()
+    tm = dev.verify_batch_timings(u64=True)
+    assert tm["u64_sums_ms"] > 0 and tm["host_form"] == 0 and tm["range_tests"] == 1 and tm["decode_ms"] > 0
+    assert dev.verify_each_u64(pvk, values, proofs, inf).all()
+    assert dev.verify_batch_u64(pvk, values[:1], proofs[:1], inf[:1]) is True                 # K = 1
+    # an ordinary call afterwards: the two u64 slots are zero again and the whole-batch test is not counted
+    assert dev.verify_batch(pvk, U.expand(values), proofs, inf, rho=rho) is True
+    tm = dev.verify_batch_timings(u64=True)
+    assert tm["u64_sums_ms"] == 0 and tm["u64_x_ms"] == 0 and tm["range_tests"] == 0
+
+
+def _tampered(proved):
+    """a swapped system (0 and 1), a changed b entry (2), a dropped C (3) -> (values, proofs, inf)"""
+    values, proofs, inf = proved["values"].copy(), proved["proofs"].copy(), proved["inf"].copy()
+    values[[0, 1]] = values[[1, 0]]
+    values[2, N_LIN] ^= np.uint64(1)            # b[0] of request 2
+    proofs[3, 36:48] = 0
+    inf[3, 2] = 1
+    return values, proofs, inf
+
+
+def test_real_proofs_with_negatives(dev, proved):
+    pvk = proved["pvk"]
+    values, proofs, inf = _tampered(proved)
+    want = _loop(pvk, values, proofs, inf)
+    assert not want.any()
+    # one good proof among them
+    values = np.concatenate([values, proved["values"][:1]])
+    proofs, inf = np.concatenate([proofs, proved["proofs"][:1]]), np.concatenate([inf, proved["inf"][:1]])
+    want = np.append(want, True)
+    k = len(want)
+    rho = VB.draw_rho(random.Random(2), k)
+    # the option unset: the per-proof pass right after the whole-batch test
+    ok, each = dev.verify_batch_u64(pvk, values, proofs, inf, rho=rho, each=True)
+    tm = dev.verify_batch_timings(u64=True)
+    assert ok is False and np.array_equal(each, want)
+    assert tm["each_ms"] > 0 and tm["range_tests"] == 1 and tm["u64_sums_ms"] > 0 and tm["u64_x_ms"] > 0 and tm["host_form"] == 0
+    assert tm["u64_x_ms"] <= tm["each_ms"]
+    by = _wire(proofs, inf)
+    ok, each, st = dev.verify_batch_u64_wire(pvk, values, by, rho=rho, each=True, status=True)
+    tm = dev.verify_batch_timings(u64=True)
+    assert ok is False and np.array_equal(each, want) and not st.any() and tm["each_ms"] > 0 and tm["range_tests"] == 1
+    # a value the caller set: bisecting to the end on inputs the host expanded
+    dev.set_option("verify_each_after", 64)
+    try:
+        ok, each = dev.verify_batch_u64(pvk, values, proofs, inf, rho=rho, each=True)
+        tm = dev.verify_batch_timings(u64=True)
+        assert ok is False and np.array_equal(each, want) and tm["each_ms"] == 0 and tm["u64_x_ms"] == 0 and tm["range_tests"] > 1
+        ok, each = dev.verify_batch_u64_wire(pvk, values, by, rho=rho, each=True)
+        assert ok is False and np.array_equal(each, want) and dev.verify_batch_timings()["each_ms"] == 0
+        dev.set_option("verify_each_after", 32)         # set to the other entries' default: set all the same
+        ok, each = dev.verify_batch_u64(pvk, values, proofs, inf, rho=rho, each=True)
+        assert np.array_equal(each, want) and dev.verify_batch_timings()["each_ms"] == 0
+    finally:
+        dev.set_option("verify_each_after", 0)
+    ok, each = dev.verify_batch_u64(pvk, values, proofs, inf, rho=rho, each=True)             # unset again
+    assert np.array_equal(each, want) and dev.verify_batch_timings()["each_ms"] > 0
+    # an undecodable A: its status, the others' verdicts untouched
+    by[4, 0] &= 0x7F
+    ok, each, st = dev.verify_batch_u64_wire(pvk, values, by, rho=rho, each=True, status=True)
+    assert ok is False and not each.any() and st[4, 0] == 1 and not np.delete(st, 4, axis=0).any() and not st[4, 1:].any()
+    assert np.array_equal(dev.verify_each_u64(pvk, values, proofs, inf), want)
+
+
+def test_host_form_below_the_default_thresholds(dev, proved):
+    """5 proofs are far below both defaults: the host form answers, with the same verdicts"""
+    from zksnark_finalproject_amd.device import verify_batch_u64_host
+    pvk = proved["pvk"]
+    values, proofs, inf = _tampered(proved)
+    values[1], proofs[1], inf[1] = proved["values"][1], proved["proofs"][1], proved["inf"][1]
+    want = _loop(pvk, values, proofs, inf)
+    assert list(want) == [False, True, False, False]
+    rho = VB.draw_rho(random.Random(6), len(want))
+    assert np.array_equal(verify_batch_u64_host(pvk, values, proofs, inf, rho=rho, each=True)[1], want)
+    thresholds(dev, 0, 0)                           # 0 restores the defaults
+    try:
+        ok, each = dev.verify_batch_u64(pvk, values, proofs, inf, rho=rho, each=True)
+        tm = dev.verify_batch_timings(u64=True)
+        assert ok is False and np.array_equal(each, want)
+        assert tm["host_form"] == 1 and tm["u64_sums_ms"] == 0 and tm["u64_x_ms"] == 0
+        ok, each = dev.verify_batch_u64_wire(pvk, values, _wire(proofs, inf), rho=rho, each=True)
+        assert ok is False and np.array_equal(each, want) and dev.verify_batch_timings()["host_form"] == 1
+    finally:
+        thresholds(dev, 1, 1)
+
+
+def test_arguments_are_checked_before_any_work(dev, proved):
+    from zksnark_finalproject_amd.device import _verify_u64_args
+    pvk, values, proofs, inf = proved["pvk"], proved["values"], proved["proofs"], proved["inf"]
+    rho = VB.draw_rho(random.Random(9), K_LIN)
+    args, k = _verify_u64_args(pvk, values, proofs, inf, rho)
+    ok, each = C.c_int(7), np.full(k, 9, dtype=np.uint8)
+    call = lambda a: dev.lib.zkg16_verify_batch_u64(dev.ctx, *a, C.byref(ok), each.ctypes.data)
+    by = _wire(proofs, inf)
+    wire_call = lambda a, raw=by.ctypes.data: dev.lib.zkg16_verify_batch_u64_wire(dev.ctx, *a[:7], raw, a[9], a[10], C.byref(ok), each.ctypes.data, None)
+    each_call = lambda a: dev.lib.zkg16_verify_each_u64(dev.ctx, *a[:9], a[10], each.ctypes.data)
+    for c in (call, wire_call, each_call):
+        assert c(args[:1] + (1,) + args[2:]) == 1                                                     # num_instance < 2
+        assert c(args[:6] + (None,) + args[7:]) == 1                                                  # no values
+        assert c(args[:10] + (1 << 32,)) == 1 and c(args[:10] + (0,)) == 1                            # k >= 2^32, k == 0
+        assert c(args[:5] + (67,) + args[6:]) == 1 and c((None,) + args[1:]) == 1
+    for c in (call, wire_call):
+        zero = rho.copy()
+        zero[2] = 0
+        assert c(args[:9] + (zero.ctypes.data,) + args[10:]) == 1
+    assert wire_call(tuple(args), raw=None) == 1
+    assert dev.lib.zkg16_verify_batch_u64(None, *args, C.byref(ok), each.ctypes.data) == 1
+    assert ok.value == 7 and (each == 9).all()
+    assert call(tuple(args)) == 0 and ok.value == 1 and (each == 1).all()
+
+
+# ------------------------------------------------------------------------------------------------ simulated statements
+@pytest.fixture(scope="module")
+def sims(oracle):
+    """{(m, k): (U64Sim, rho, the host form's (ok, each))}: made once, shared by the entries"""
+    from zksnark_finalproject_amd.device import verify_batch_u64_host
+    out = {}
+    for m in (72, 129):
+        for k in (130, 1):
+            sim = U.U64Sim(oracle, m, k, S.spread(k), 100 * m + k)
+            rho = VB.draw_rho(random.Random(m + k), k)
+            b = sim.batch
+            out[(m, k)] = (sim, rho, verify_batch_u64_host(b.pvk, sim.values, b.proofs, b.infs, rho=rho, each=True))
+    return out
+
+
+@pytest.mark.parametrize("k", [130, 1])
+@pytest.mark.parametrize("m", [72, 129])
+def test_simulated_statements(dev, sims, m, k):
+    """K = 130: two waves and a partial third of the Miller kernels, 130 blocks of the X kernel, negatives spread over them; K = 1:
+    a negative alone.  m = 72 and 129: two and three columns a lane."""
+    sim, rho, host = sims[(m, k)]
+    b, want = sim.batch, sim.want
+    assert not want.all() and (k == 1 or want.any())
+    assert host[0] is False and np.array_equal(host[1], want)
+    ok, each = dev.verify_batch_u64(b.pvk, sim.values, b.proofs, b.infs, rho=rho, each=True)
+    tm = dev.verify_batch_timings(u64=True)
+    assert tm["host_form"] == 0 and tm["range_tests"] == 1 and (k == 1 or tm["u64_x_ms"] > 0)
+    assert ok is False and np.array_equal(each, want), [(s.name, g, w) for s, g, w in zip(sim.stmts, each, want) if g != w]
+    ok, each = dev.verify_batch_u64_wire(b.pvk, sim.values, VB.to_wire(b), rho=rho, each=True)
+    assert ok is False and np.array_equal(each, want)
+    assert np.array_equal(dev.verify_each_u64(b.pvk, sim.values, b.proofs, b.infs), want)
+    good = np.flatnonzero(want)
+    if len(good):
+        assert dev.verify_batch_u64(b.pvk, sim.values[good], b.proofs[good], b.infs[good], rho=rho[good]) is True
+        assert dev.verify_batch_timings(u64=True)["u64_x_ms"] == 0
+
+
+# ------------------------------------------------------------------------------------------------ the handler
+def test_handler_with_device_answers_as_without(dev, proved):
+    from zksnark_finalproject_amd import handlers, wire
+    systems = [(proved["a"][i], proved["b"][i]) for i in range(K_LIN)]
+    sent = [wire.encode_proof(proved["proofs"][i], proved["inf"][i]) for i in range(K_LIN)]
+    vk = proved["vk"]
+    cases = {
+        "good": (systems, sent),
+        "swapped": ([systems[1], systems[0]] + systems[2:], sent),
+        "as_lists": ([(a.tolist(), b.tolist()) for a, b in systems], sent),
+        "malformed": ([systems[0], (systems[1][0][:2], systems[1][1]), ([[1, -2, 3]] * 3, [1, 2, 3]), ([[2**64, 0, 0]] * 3, [1, 2, 3])], sent),
+        "bad_proofs": (systems, [sent[0], "not base64 !", base64.standard_b64encode(b"\x00" * 191).decode(), sent[3]]),
+        "other_size": ([LC.system(2, "lower", 1)] + systems[1:], sent),
+    }
+    for name, (sy, pr) in cases.items():
+        want = handlers.verify_linear_equations(vk, sy, pr)
+        got = handlers.verify_linear_equations(vk, sy, pr, dev=dev)
+        assert got["valid"] == want["valid"] and set(got) == {"valid", "verifying_time", "decode_time"}, name
+    assert handlers.verify_linear_equations(vk, systems, sent, dev=dev)["valid"] == [True] * K_LIN
+    tm = dev.verify_batch_timings(u64=True)
+    assert tm["u64_sums_ms"] > 0 and tm["host_form"] == 0 and tm["decode_ms"] > 0            # the new route ran, on the device
+    assert handlers.verify_linear_equations(vk, cases["swapped"][0], sent, dev=dev)["valid"] == [False, False, True, True]
+    assert dev.verify_batch_timings(u64=True)["u64_x_ms"] > 0
+    # the key as it travels, prepared, and one that does not decode
+    assert handlers.verify_linear_equations(wire.encode_vk(vk), systems, sent, dev=dev)["valid"] == [True] * K_LIN
+    assert handlers.verify_linear_equations(wire.encode_pvk(vk), systems, sent, dev=dev)["valid"] == [True] * K_LIN
+    assert handlers.verify_linear_equations("AAAA", systems, sent, dev=dev)["valid"] == [False] * K_LIN
+    with pytest.raises(ValueError):
+        handlers.verify_linear_equations(vk, systems, sent[:2], dev=dev)
+
+
+# ------------------------------------------------------------------------------------------------ the existing entries
+def test_existing_entries_answer_as_before(dev, oracle):
+    """vb_decide and the per-proof pass gained a third source of inputs and the option store a flag: an ordinary batch still gets the
+    host form's verdicts through zkg16_verify_batch, zkg16_verify_batch_wire and zkg16_verify_each, with the same range-test counts"""
+    from zksnark_finalproject_amd.device import verify_batch_host
+    k = 6
+    base = VB.make_batch(oracle, k)
+    b = VB.tamper(oracle, VB.tamper(oracle, base, "public_input", (1,)), "c_plus_g", (4,))
+    want = b.loop()
+    assert list(want) == [True, False, True, True, False, True]
+    rho = VB.draw_rho(random.Random(5), k)
+    assert verify_batch_host(b.pvk, b.pubs, b.proofs, b.infs, rho=rho, each=True)[1].tolist() == want.tolist()
+    for after in (0, 1):
+        dev.set_option("verify_each_after", after)
+        try:
+            ok, each = dev.verify_batch(b.pvk, b.pubs, b.proofs, b.infs, rho=rho, each=True)
+            tm = dev.verify_batch_timings()
+            assert ok is False and np.array_equal(each, want) and tm["host_form"] == 0
+            # unset: the default of 32 holds here, bisecting runs to the end; 1: one range test of bisecting, then the pass
+            assert (tm["each_ms"] > 0 and tm["range_tests"] == 1) if after == 1 else (tm["each_ms"] == 0 and tm["range_tests"] > 1)
+            ok, each = dev.verify_batch_wire(b.pvk, b.pubs, VB.to_wire(b), rho=rho, each=True)
+            assert ok is False and np.array_equal(each, want)
+        finally:
+            dev.set_option("verify_each_after", 0)
+    assert np.array_equal(dev.verify_each(b.pvk, b.pubs, b.proofs, b.infs), want)
+    assert dev.verify_batch(base.pvk, base.pubs, base.proofs, base.infs, rho=rho) is True
+    assert dev.verify_batch_timings()["range_tests"] == 0
+    assert len(dev.verify_batch_timings()) == 11 and len(dev.verify_batch_timings(prime=True)) == 13

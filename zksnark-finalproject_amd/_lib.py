@@ -94,7 +94,13 @@ SIGNATURES = {
     "zkg16_verify_prime_batch_wire": (C.c_int, [ctxp, vp, sz, vp, vp, vp, sz, vp, vp, vp, vp, sz, C.POINTER(C.c_int), vp, vp]),
     "zkg16_prime_inputs_batch": (C.c_int, [ctxp, vp, vp, sz, vp, vp, vp]),
     "zkg16_prime_rho_sums": (C.c_int, [ctxp, vp, vp, vp, vp, sz, vp]),
-    "zkg16_points_decompress_batch": (C.c_int, [ctxp, C.c_int, vp, sz, vp, vp, C.c_int, C.POINTER(C.c_int)]),
+    "zkg16_verify_batch_u64_host": (C.c_int, [vp, sz, vp, vp, vp, sz, vp, vp, vp, vp, sz, C.c_int, C.POINTER(C.c_int), vp]),
+    "zkg16_verify_batch_u64": (C.c_int, [ctxp, vp, sz, vp, vp, vp, sz, vp, vp, vp, vp, sz, C.POINTER(C.c_int), vp]),
+    "zkg16_verify_batch_u64_wire": (C.c_int, [ctxp, vp, sz, vp, vp, vp, sz, vp, vp, vp, sz, C.POINTER(C.c_int), vp, vp]),
+    "zkg16_verify_each_u64": (C.c_int, [ctxp, vp, sz, vp, vp, vp, sz, vp, vp, vp, sz, vp]),
+    "zkg16_u64_rho_sums": (C.c_int, [ctxp, vp, sz, vp, vp, sz, vp]),
+    "zkg16_u64_prepared_inputs": (C.c_int, [ctxp, vp, sz, vp, vp, sz, vp, vp]),
+    "zkg16_points_decompress_batch":(C.c_int, [ctxp, C.c_int, vp, sz, vp, vp, C.c_int, C.POINTER(C.c_int)]),
     "zkg16_miller_loop_batch": (C.c_int, [ctxp, vp, vp, vp, vp, sz, vp]),
     "zkg16_point_check_batch": (C.c_int, [ctxp, C.c_int, vp, vp, sz, vp]),
     "zkg16_final_exp": (C.c_int, [u64p, u64p]),

@@ -412,7 +412,11 @@ int set_option_one(zkg16_ctx *ctx, const char *name, int64_t v) {
     if (is("verify_wire_min")) return set(o.verify_wire_min, 0, 1 << 30, v == 0 ? ZKG16_VERIFY_WIRE_MIN_DEFAULT : v);
     // zkg16_verify_batch[_wire] with ok_each: range tests bisecting may make before the per-proof pass decides what is left
     // (0 restores the default; 1 = after the first; above 2K = never)
-    if (is("verify_each_after")) return set(o.verify_each_after, 0, 1 << 30, v == 0 ? ZKG16_VERIFY_EACH_AFTER_DEFAULT : v);
+    if (is("verify_each_after")) {
+        const int rc = set(o.verify_each_after, 0, 1 << 30, v == 0 ? ZKG16_VERIFY_EACH_AFTER_DEFAULT : v);
+        if (rc == ZKG16_OK) o.verify_each_after_set = v != 0;      // the u64 entries have a default of their own (zkg16_verify_batch_u64)
+        return rc;
+    }
     // 0 (default): the proving calls prove whatever they are handed; 1: they check (A z)(B z) == C z after the SpMV and refuse with ZKG16_ERR_UNSATISFIED
     if (is("check_satisfied")) return set(o.check_satisfied, 0, 1, v);
     if (is("reduce_chunk")) return set(o.reduce_chunk, 0, 64, v, (v & (v - 1)) == 0);      // 0 = default, else a power of two up to 64

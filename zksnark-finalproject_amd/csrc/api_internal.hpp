@@ -44,7 +44,9 @@ enum VerifyTiming : int {
     V_RANGE_TESTS = 10,    // range tests bisecting made
     V_PRIME_INPUTS = 11,   // the prime form: the inputs kernel (device events; 0 when the host form answered or the call was not a prime call)
     V_PRIME_SUMS = 12,     // ... and the sums kernels
-    V_COUNT = 13
+    V_U64_SUMS = 13,       // the u64 form: the sums kernels (device events; 0 when the host form answered or the call was not a u64 call)
+    V_U64_X = 14,          // ... and the X kernel of its per-proof pass (0 when that pass did not run)
+    V_COUNT = 15
 };
 static_assert(T_COUNT <= PROOF_TIMING_SLOTS && V_COUNT == VERIFY_TIMING_SLOTS, "timing slots");
 

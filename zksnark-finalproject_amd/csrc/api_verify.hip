@@ -12,6 +12,9 @@ using namespace zk;
 // stream beside A and C on two others; everything after reads that array as if the host had uploaded it.
 // The prime form (zkg16_verify_prime_batch[_wire]) has no public inputs on the host: (x, j) go up, the inputs kernel runs in front
 // of the membership kernels of the main stream, and the 260 multiplier sums are taken there once the member mask is known.
+// The u64 form (zkg16_verify_batch_u64[_wire]) sends its k x (num_instance - 1) 64-bit values up as they are: the sums kernels run
+// where the prime form's do, a second G1 MSM over the key's points turns the device sums into sum_i s_i gamma_abc[i], and the
+// per-proof pass makes X_k from the rows on the device (u64_x_kernel in the place of each_x_kernel).
 namespace {
 const size_t VB_PASS = 65536;          // pairs / points per launch: one wave per SIMD of a 256-CU device
 struct VbEvents {
@@ -77,35 +80,69 @@ struct VbPrime {
     const uint32_t *d_dig = nullptr;
 };
 
+// The u64 form (verify_batch.hpp): the batch's values on the host (k x (num_instance - 1), row-major), and once they are uploaded,
+// the device copy the sums kernels and the per-proof pass read
+struct VbU64 {
+    const uint64_t *values;
+    const uint64_t *d_values = nullptr;
+};
+// which gamma_abc points are the point at infinity: all-zero limbs (load_pt's rule)
+std::vector<uint8_t> vb_zero_points(const uint64_t *pts, size_t n) {
+    std::vector<uint8_t> fl(n);
+    for (size_t i = 0; i < n; i++) {
+        uint64_t any = 0;
+        for (size_t t = 0; t < 12; t++) any |= pts[12 * i + t];
+        fl[i] = any ? 0 : 1;
+    }
+    return fl;
+}
+
 // The per-proof pass on the lane's main stream: the proofs idx[0 .. n) (null: 0 .. n - 1) of the k x 48 limbs / k x 3 flags already on
 // the device, each with its public inputs (pub(j): the (num_instance - 1) x 4 Montgomery limbs of the proof at position j), in
 // launches of VB_PASS.  The key is converted and uploaded once per call.  prime (nullable): the prime form — pub is not asked; the
 // inputs of the listed proofs are written on the device from its (x, j) and digests, so nothing travels per proof but its index.
+// u64 (nullable): the u64 form — pub is not asked either; X_k of every listed proof is made from its row of values on the device
+// (all the X launches first, between two events of their own: *x_ms, when asked), then the Miller and final-exponentiation launches.
 // Returns the kernels' time in ms (device events)
 float vb_each_pass(zkg16_ctx *ctx, const VbKey &key, const uint64_t *d_proofs, const uint8_t *d_inf, const uint32_t *idx, size_t n,
-                   const std::function<const uint64_t *(size_t)> &pub, uint8_t *verdict, const VbPrime *prime = nullptr) {
+                   const std::function<const uint64_t *(size_t)> &pub, uint8_t *verdict, const VbPrime *prime = nullptr, const VbU64 *u64 = nullptr,
+                   float *x_ms = nullptr) {
     if (!n) return 0;
     hipStream_t st = ctx->stream;
     const size_t ni = key.num_instance, per = 4 * (ni - 1), pass = std::min(n, VB_PASS);
     std::vector<uint32_t> words(vb_each_key_count(ni));
     vb_each_key_words(key, words.data());
-    std::vector<uint64_t> z(prime ? 1 : std::max<size_t>(n * per, 1));
-    for (size_t j = 0; j < n && per && !prime; j++) vb_scalars_canonical(pub(j), ni - 1, z.data() + per * j);
-    DevBuf d_key(words.size() * 4), d_z(prime ? n * per * 8 : z.size() * 8), d_idx(idx ? n * 4 : 0), d_scratch(vb_each_scratch_bytes(pass)), d_verdict(n);
+    const bool made_here = prime || u64;      // the inputs are made on the device
+    std::vector<uint64_t> z(made_here ? 1 : std::max<size_t>(n * per, 1));
+    for (size_t j = 0; j < n && per && !made_here; j++) vb_scalars_canonical(pub(j), ni - 1, z.data() + per * j);
+    DevBuf d_key(words.size() * 4), d_z(prime ? n * per * 8 : u64 ? 0 : z.size() * 8), d_idx(idx ? n * 4 : 0), d_scratch(vb_each_scratch_bytes(pass)), d_verdict(n);
+    DevBuf d_xk(u64 ? vb_each_x_bytes(n) : 0), d_have(u64 ? n : 0);
     VbEvents evs;
     ZK_HIP(hipMemcpyAsync(d_key.p, words.data(), words.size() * 4, hipMemcpyHostToDevice, st));
-    if (!prime) ZK_HIP(hipMemcpyAsync(d_z.p, z.data(), z.size() * 8, hipMemcpyHostToDevice, st));
+    if (!made_here) ZK_HIP(hipMemcpyAsync(d_z.p, z.data(), z.size() * 8, hipMemcpyHostToDevice, st));
     if (idx) ZK_HIP(hipMemcpyAsync(d_idx.p, idx, n * 4, hipMemcpyHostToDevice, st));
     ZK_HIP(hipEventRecord(evs.ev[0], st));
+    if (u64) {
+        const uint32_t *pts = d_key.as<uint32_t>() + vb_each_key_points_at();
+        for (size_t off = 0; off < n; off += VB_PASS)
+            vb_u64_x_launch(st, pts, ni, idx ? u64->d_values : u64->d_values + (ni - 1) * off, idx ? d_idx.as<uint32_t>() + off : nullptr, std::min(VB_PASS, n - off),
+                            d_xk.as<uint8_t>() + vb_each_x_bytes(off), d_have.as<uint8_t>() + off);
+        ZK_HIP(hipEventRecord(evs.ev[2], st));
+        for (size_t off = 0; off < n; off += VB_PASS)
+            vb_each_tail_launch(st, d_key.as<uint32_t>(), idx ? d_idx.as<uint32_t>() + off : nullptr, std::min(VB_PASS, n - off), idx ? d_proofs : d_proofs + 48 * off,
+                                idx ? d_inf : d_inf + 3 * off, d_xk.as<uint8_t>() + vb_each_x_bytes(off), d_have.as<uint8_t>() + off, d_scratch.p,
+                                d_verdict.as<uint8_t>() + off);
+    }
     for (size_t off = 0; off < n && prime; off += VB_PASS)
         vb_prime_z_launch(st, idx ? d_idx.as<uint32_t>() + off : nullptr, std::min(VB_PASS, n - off), idx ? prime->d_xs : prime->d_xs + off,
                           idx ? prime->d_js : prime->d_js + off, idx ? prime->d_dig : prime->d_dig + 8 * off, d_z.as<uint64_t>() + per * off);
-    for (size_t off = 0; off < n; off += VB_PASS)
+    for (size_t off = 0; off < n && !u64; off += VB_PASS)
         vb_each_launch(st, d_key.as<uint32_t>(), ni, idx ? d_idx.as<uint32_t>() + off : nullptr, std::min(VB_PASS, n - off), idx ? d_proofs : d_proofs + 48 * off,
                        idx ? d_inf : d_inf + 3 * off, d_z.as<uint64_t>() + per * off, d_scratch.p, d_verdict.as<uint8_t>() + off);
     ZK_HIP(hipEventRecord(evs.ev[1], st));
     ZK_HIP(hipMemcpyAsync(verdict, d_verdict.p, n, hipMemcpyDeviceToHost, st));
     ZK_HIP(hipStreamSynchronize(st));
+    if (u64 && x_ms) *x_ms += vb_elapsed(evs.ev[0], evs.ev[2]);
     return vb_elapsed(evs.ev[0], evs.ev[1]);
 }
 
@@ -116,8 +153,11 @@ float vb_each_pass(zkg16_ctx *ctx, const VbKey &key, const uint64_t *d_proofs, c
 // prime (nullable): the prime form — b.public_inputs is null; the inputs kernel runs beside the membership kernels, the 260 sums of
 // the member proofs are taken on the device once the membership verdicts are back, and the host expands inputs (from the 32-byte
 // digests it then downloads) only when bisecting asks for them.
+// u64 (nullable): the u64 form — b.public_inputs is null as well; the values go up beside the proofs, the num_instance sums of the
+// member proofs are taken where the prime form's are, sum_i s_i gamma_abc[i] is a second MSM of the ctx on those device sums, and
+// the host expands values to Montgomery limbs only when bisecting asks for them.
 int vb_device(zkg16_ctx *ctx, const VbKey &key, VbBatch b, const uint8_t *wire, int *ok, uint8_t *ok_each, uint8_t *decode_status, double t_all,
-              VbPrime *prime = nullptr) {
+              VbPrime *prime = nullptr, VbU64 *u64 = nullptr) {
     const size_t k = b.k;
     float tm[V_COUNT] = {0};
     ZK_LANE_BEGIN(ctx)
@@ -130,7 +170,9 @@ int vb_device(zkg16_ctx *ctx, const VbKey &key, VbBatch b, const uint8_t *wire, 
     DevBuf d_wire(wire ? k * 192 : 0), d_st(wire ? 3 * k : 0);
     const size_t sum_blocks = prime ? vb_prime_sums_blocks(k) : 0;
     DevBuf d_xs(prime ? k * 8 : 0), d_js(prime ? k * 8 : 0), d_dig(prime ? k * 32 : 0), d_part(sum_blocks * 260 * 32), d_sums(prime ? 260 * 32 : 0);
-    std::vector<uint64_t> sums(prime ? 260 * 4 : 0), expanded;
+    const size_t ni = key.num_instance, um = ni - 1;
+    DevBuf d_values(u64 ? k * um * 8 : 0), d_upart(u64 ? vb_u64_sums_partial_words(k, um) * 8 : 0), d_usums(u64 ? ni * 32 : 0);
+    std::vector<uint64_t> sums(prime ? 260 * 4 : u64 ? ni * 4 : 0), expanded;
     std::vector<uint32_t> digests;
     const VbEndo en = vb_endo();
     std::vector<uint64_t> dec_proofs;
@@ -168,6 +210,10 @@ int vb_device(zkg16_ctx *ctx, const VbKey &key, VbBatch b, const uint8_t *wire, 
         upload_h2d(ctx, d_proofs.p, b.proofs, k * 48 * 8);
         ZK_HIP(hipMemcpyAsync(d_inf.p, b.inf, 3 * k, hipMemcpyHostToDevice, s_main));
         ZK_HIP(hipMemcpyAsync(d_rho.p, b.rho, k * 16, hipMemcpyHostToDevice, s_main));
+    }
+    if (u64) {
+        upload_h2d(ctx, d_values.p, u64->values, k * um * 8);
+        u64->d_values = d_values.as<uint64_t>();
     }
     ZK_HIP(hipEventRecord(e_up, s_main));
     for (hipStream_t st : {s_mil, s_c, s_b}) ZK_HIP(hipStreamWaitEvent(st, e_up, 0));
@@ -256,6 +302,25 @@ int vb_device(zkg16_ctx *ctx, const VbKey &key, VbBatch b, const uint8_t *wire, 
         ZK_HIP(hipEventRecord(e_s1, s_main));
         ZK_HIP(hipMemcpyAsync(sums.data(), d_sums.p, 260 * 32, hipMemcpyDeviceToHost, s_main));
     }
+    uint64_t sum_x[12] = {0};
+    uint8_t sum_x_inf = 1;
+    if (u64) {
+        ZK_HIP(hipEventRecord(e_s0, s_main));
+        vb_u64_sums_launch(s_main, u64->d_values, um, d_rho.as<uint64_t>(), d_live.as<uint8_t>(), k, d_upart.as<uint64_t>(), d_usums.as<uint64_t>());
+        ZK_HIP(hipEventRecord(e_s1, s_main));
+        ZK_HIP(hipMemcpyAsync(sums.data(), d_usums.p, ni * 32, hipMemcpyDeviceToHost, s_main));
+        if (n_live) {
+            // sum_i s_i gamma_abc[i]: the sums stay where they are — below 2^224 < r, they are canonical scalars as they lie
+            const std::vector<uint8_t> ginf = vb_zero_points(key.gamma_abc_g1, ni);
+            DevBuf d_gbases(ni * sizeof(G1AffineU));
+            upload_points<G1Affine>(ctx, d_gbases.as<G1AffineU>(), key.gamma_abc_g1, ginf.data(), 0, ni);
+            ZK_HIP(hipStreamSynchronize(s_main));
+            MsmPlan plan;
+            msm_plan_build(ctx, ctx->ws_h, d_usums.as<Fr>(), ni, plan);
+            const G1XYZZ total = msm_g1_exec(ctx, ctx->ws_h, plan, d_gbases.as<G1AffineU>(), "verify_batch_u64_msm");
+            point_to_abi(xyzz_to_affine(total), sum_x, &sum_x_inf);
+        }
+    }
     ZK_HIP(hipStreamWaitEvent(s_main, e_mil, 0));
     ZK_HIP(hipEventRecord(e_p0, s_main));
     const uint64_t *d_prod = vb_product_launch(s_main, d_f.as<uint64_t>(), d_live.as<uint8_t>(), k, d_tmp.as<uint64_t>());
@@ -269,15 +334,22 @@ int vb_device(zkg16_ctx *ctx, const VbKey &key, VbBatch b, const uint8_t *wire, 
         tm[V_PRIME_INPUTS] = vb_elapsed(e_i0, e_i1);
         tm[V_PRIME_SUMS] = vb_elapsed(e_s0, e_s1);
     }
+    if (u64) tm[V_U64_SUMS] = vb_elapsed(e_s0, e_s1);
     // the K Miller values leave the device only when the batch equation failed and the caller wants to know where
     std::vector<uint64_t> miller;
     // ... and when bisecting has used its budget of range tests, the proofs it left undecided stay here for the per-proof pass
     VbEach each;
     each.after = (size_t)ctx->opt.verify_each_after;
+    if (u64) {
+        // every further range test costs num_instance host scalar multiplications here, the per-proof pass a fixed number of launches:
+        // unless the caller set the option, that pass decides every member proof right after the test of the whole batch
+        each.count_whole = true;
+        if (!ctx->opt.verify_each_after_set) each.after = 1;
+    }
     each.decide = [&](const uint32_t *idx, size_t n, uint8_t *verdict) {
         const size_t per = 4 * (key.num_instance - 1);
         tm[V_EACH] += vb_each_pass(ctx, key, d_proofs.as<uint64_t>(), d_inf.as<uint8_t>(), idx, n, [&](size_t j) { return b.public_inputs + per * idx[j]; }, verdict,
-                                   prime);
+                                   prime, u64, tm + V_U64_X);
     };
     VbInputs inputs;
     if (prime) {
@@ -290,13 +362,25 @@ int vb_device(zkg16_ctx *ctx, const VbKey &key, VbBatch b, const uint8_t *wire, 
             return expanded.data();
         };
     }
+    if (u64) {
+        inputs.sums = sums.data();
+        inputs.sum_x = sum_x;
+        inputs.sum_x_inf = &sum_x_inf;
+        inputs.expand = [&]() -> const uint64_t * {
+            expanded.resize(4 * um * k);
+            vb_u64_expand(u64->values, um * k, expanded.data());
+            return expanded.data();
+        };
+    }
     vb_decide(key, b, member.data(), [&]() -> const uint64_t * {
         miller.resize(72 * k);
         ZK_HIP(hipMemcpy(miller.data(), d_f.p, k * 72 * 8, hipMemcpyDeviceToHost));
         return miller.data();
-    }, prod, sum_c, &sum_c_inf, 0, ok, ok_each, tm + V_HOST, &each, prime ? &inputs : nullptr);
+    }, prod, sum_c, &sum_c_inf, 0, ok, ok_each, tm + V_HOST, &each, prime || u64 ? &inputs : nullptr);
     // the verdicts above came from host-expanded inputs then, and are right; a device whose sums are wrong is reported all the same
-    if (inputs.sums_refused) throw HipError{hipErrorUnknown, "prime_rho_sums_kernel: s_0 differs from the host's sum of the multipliers", __FILE__, __LINE__};
+    if (inputs.sums_refused)
+        throw HipError{hipErrorUnknown, u64 ? "u64_rho_sums_kernel: s_0 differs from the host's sum of the multipliers"
+                                            : "prime_rho_sums_kernel: s_0 differs from the host's sum of the multipliers", __FILE__, __LINE__};
     tm[V_RANGE_TESTS] = (float)each.range_tests;
     tm[V_TOTAL] = (float)(now_ms() - t_all);
     vb_publish(root, tm);
@@ -487,6 +571,155 @@ int zkg16_prime_rho_sums(zkg16_ctx *ctx, const uint64_t *xs, const uint64_t *js,
                          d_part.as<uint64_t>(), d_sums.as<uint64_t>());
     ZK_HIP(hipMemcpyAsync(sums, d_sums.p, 260 * 32, hipMemcpyDeviceToHost, st));
     ZK_HIP(hipStreamSynchronize(st));
+    ZK_LANE_END(ctx)
+}
+
+// ---- the u64 form: a key whose public inputs are plain 64-bit values, values = k x (num_instance - 1) u64
+static int vu_check(zkg16_ctx *ctx, const VbKey &key, const uint64_t *values, const void *proofs, const uint8_t *inf, const uint64_t *rho, size_t k, const int *ok) {
+    if (!ctx || key.num_instance < 2 || !values || k >> 32) return ZKG16_ERR_BAD_ARG;
+    // the checks of zkg16_verify_batch: the values stand in for the inputs that do not exist yet
+    return vb_check_args(key, VbBatch{values, static_cast<const uint64_t *>(proofs), inf, rho, k}, ok);
+}
+static std::vector<uint64_t> vu_inputs_host(const VbKey &key, const uint64_t *values, size_t k) {
+    std::vector<uint64_t> pub(4 * (key.num_instance - 1) * k);
+    vb_u64_expand(values, (key.num_instance - 1) * k, pub.data());
+    return pub;
+}
+
+int zkg16_verify_batch_u64(zkg16_ctx *ctx, const uint64_t *gamma_abc_g1, size_t num_instance, const uint64_t alpha_beta[72], const uint64_t *gamma_neg_coeffs,
+                           const uint64_t *delta_neg_coeffs, size_t n_coeffs, const uint64_t *values, const uint64_t *proofs, const uint8_t *inf, const uint64_t *rho,
+                           size_t k, int *ok, uint8_t *ok_each) {
+    const VbKey key{gamma_abc_g1, num_instance, alpha_beta, gamma_neg_coeffs, delta_neg_coeffs, n_coeffs};
+    const int rc = vu_check(ctx, key, values, proofs, inf, rho, k, ok);
+    if (rc != ZKG16_OK) return rc;
+    const double t_all = now_ms();
+    if (k < (size_t)ctx->opt.verify_batch_min)
+        return vb_answer_on_host(ctx, t_all, [&](float *) {
+            const std::vector<uint64_t> pub = vu_inputs_host(key, values, k);
+            vb_host(key, VbBatch{pub.data(), proofs, inf, rho, k}, 0, ok, ok_each);
+        });
+    VbU64 u64{values};
+    return vb_device(ctx, key, VbBatch{nullptr, proofs, inf, rho, k}, nullptr, ok, ok_each, nullptr, t_all, nullptr, &u64);
+}
+
+int zkg16_verify_batch_u64_wire(zkg16_ctx *ctx, const uint64_t *gamma_abc_g1, size_t num_instance, const uint64_t alpha_beta[72], const uint64_t *gamma_neg_coeffs,
+                                const uint64_t *delta_neg_coeffs, size_t n_coeffs, const uint64_t *values, const uint8_t *proof_bytes, const uint64_t *rho,
+                                size_t k, int *ok, uint8_t *ok_each, uint8_t *decode_status) {
+    const VbKey key{gamma_abc_g1, num_instance, alpha_beta, gamma_neg_coeffs, delta_neg_coeffs, n_coeffs};
+    if (!proof_bytes) return ZKG16_ERR_BAD_ARG;
+    const int rc = vu_check(ctx, key, values, proof_bytes, proof_bytes, rho, k, ok);
+    if (rc != ZKG16_OK) return rc;
+    const double t_all = now_ms();
+    if (k < (size_t)ctx->opt.verify_wire_min)
+        return vb_answer_on_host(ctx, t_all, [&](float *tm) {
+            std::vector<uint64_t> proofs(48 * k);
+            std::vector<uint8_t> inf(3 * k), st(3 * k);
+            vb_wire_decode_host(proof_bytes, k, decode_status ? 1 : 0, 0, proofs.data(), inf.data(), st.data());
+            tm[V_DECODE] = (float)(now_ms() - t_all);
+            std::vector<uint8_t> dead(k);
+            for (size_t i = 0; i < k; i++) dead[i] = st[3 * i] || st[3 * i + 1] || st[3 * i + 2] ? 1 : 0;
+            const std::vector<uint64_t> pub = vu_inputs_host(key, values, k);
+            vb_host(key, VbBatch{pub.data(), proofs.data(), inf.data(), rho, k}, 0, ok, ok_each, dead.data());
+            if (decode_status) memcpy(decode_status, st.data(), 3 * k);
+        });
+    VbU64 u64{values};
+    return vb_device(ctx, key, VbBatch{nullptr, nullptr, nullptr, rho, k}, proof_bytes, ok, ok_each, decode_status, t_all, nullptr, &u64);
+}
+
+int zkg16_verify_each_u64(zkg16_ctx *ctx, const uint64_t *gamma_abc_g1, size_t num_instance, const uint64_t alpha_beta[72], const uint64_t *gamma_neg_coeffs,
+                          const uint64_t *delta_neg_coeffs, size_t n_coeffs, const uint64_t *values, const uint64_t *proofs, const uint8_t *inf, size_t k,
+                          uint8_t *ok_each) {
+    if (!ctx || !ok_each || k == 0) return ZKG16_ERR_BAD_ARG;
+    const VbKey key{gamma_abc_g1, num_instance, alpha_beta, gamma_neg_coeffs, delta_neg_coeffs, n_coeffs};
+    {
+        // the checks of zkg16_verify_each: there are no multipliers, so one non-zero pair stands in for them
+        const uint64_t some_rho[2] = {1, 0};
+        int ok_probe = 0;
+        if (num_instance < 2 || !values || k >> 32) return ZKG16_ERR_BAD_ARG;
+        const int rc = vb_check_args(key, VbBatch{values, proofs, inf, some_rho, 1}, &ok_probe);
+        if (rc != ZKG16_OK) return rc;
+    }
+    ZK_LANE_BEGIN(ctx)
+    hipStream_t s_main = ctx->stream, s_c = ctx->slots[1].stream, s_b = ctx->slots[2].stream;
+    const std::vector<uint8_t> fl = vb_flags(proofs, inf, k);
+    const size_t m = num_instance - 1;
+    VbEvents evs;
+    DevBuf d_proofs(k * 48 * 8), d_inf(3 * k), d_mem3(3 * k), d_values(k * m * 8);
+    const VbEndo en = vb_endo();
+    upload_h2d(ctx, d_proofs.p, proofs, k * 48 * 8);
+    upload_h2d(ctx, d_values.p, values, k * m * 8);
+    ZK_HIP(hipMemcpyAsync(d_inf.p, fl.data(), 3 * k, hipMemcpyHostToDevice, s_main));
+    ZK_HIP(hipEventRecord(evs.ev[0], s_main));
+    for (hipStream_t st : {s_c, s_b}) ZK_HIP(hipStreamWaitEvent(st, evs.ev[0], 0));
+    for (size_t off = 0; off < k; off += VB_PASS)
+        vb_membership_chunk(s_main, s_c, s_b, d_proofs.as<uint64_t>() + 48 * off, d_inf.as<uint8_t>() + 3 * off, std::min(VB_PASS, k - off), en,
+                            d_mem3.as<uint8_t>() + 3 * off);
+    ZK_HIP(hipEventRecord(evs.ev[1], s_c));
+    ZK_HIP(hipEventRecord(evs.ev[2], s_b));
+    ZK_HIP(hipStreamWaitEvent(s_main, evs.ev[1], 0));
+    ZK_HIP(hipStreamWaitEvent(s_main, evs.ev[2], 0));
+    std::vector<uint8_t> mem3(3 * k);
+    ZK_HIP(hipMemcpyAsync(mem3.data(), d_mem3.p, 3 * k, hipMemcpyDeviceToHost, s_main));
+    ZK_HIP(hipStreamSynchronize(s_main));
+    // proofs that failed membership are never listed
+    std::vector<uint32_t> idx;
+    for (size_t i = 0; i < k; i++)
+        if (mem3[3 * i] && mem3[3 * i + 1] && mem3[3 * i + 2]) idx.push_back((uint32_t)i);
+    std::vector<uint8_t> verdict(idx.size());
+    const VbU64 u64{values, d_values.as<uint64_t>()};
+    (void)vb_each_pass(ctx, key, d_proofs.as<uint64_t>(), d_inf.as<uint8_t>(), idx.size() == k ? nullptr : idx.data(), idx.size(),
+                       [](size_t) -> const uint64_t * { return nullptr; }, verdict.data(), nullptr, &u64);
+    memset(ok_each, 0, k);
+    for (size_t j = 0; j < idx.size(); j++) ok_each[idx[j]] = verdict[j] ? 1 : 0;
+    ZK_LANE_END(ctx)
+}
+
+// Stage entries: the sums kernels and the X kernel by themselves
+int zkg16_u64_rho_sums(zkg16_ctx *ctx, const uint64_t *values, size_t m, const uint64_t *rho, const uint8_t *live, size_t k, uint64_t *sums) {
+    if (!ctx || m == 0 || ((!values || !rho || !sums) && k) || k >> 32) return ZKG16_ERR_BAD_ARG;
+    if (!k) return ZKG16_OK;
+    ZK_LANE_BEGIN(ctx)
+    hipStream_t st = ctx->stream;
+    DevBuf d_values(k * m * 8), d_rho(k * 16), d_live(live ? k : 0), d_part(vb_u64_sums_partial_words(k, m) * 8), d_sums((m + 1) * 32);
+    upload_h2d(ctx, d_values.p, values, k * m * 8);
+    ZK_HIP(hipMemcpyAsync(d_rho.p, rho, k * 16, hipMemcpyHostToDevice, st));
+    if (live) ZK_HIP(hipMemcpyAsync(d_live.p, live, k, hipMemcpyHostToDevice, st));
+    vb_u64_sums_launch(st, d_values.as<uint64_t>(), m, d_rho.as<uint64_t>(), live ? d_live.as<uint8_t>() : nullptr, k, d_part.as<uint64_t>(), d_sums.as<uint64_t>());
+    ZK_HIP(hipMemcpyAsync(sums, d_sums.p, (m + 1) * 32, hipMemcpyDeviceToHost, st));
+    ZK_HIP(hipStreamSynchronize(st));
+    ZK_LANE_END(ctx)
+}
+
+int zkg16_u64_prepared_inputs(zkg16_ctx *ctx, const uint64_t *gamma_abc_g1, size_t num_instance, const uint64_t *values, const uint32_t *idx, size_t n,
+                              uint64_t *x_out, uint8_t *inf_out) {
+    if (!ctx || !gamma_abc_g1 || num_instance < 2 || ((!values || !x_out || !inf_out) && n) || n >> 32) return ZKG16_ERR_BAD_ARG;
+    if (!n) return ZKG16_OK;
+    ZK_LANE_BEGIN(ctx)
+    hipStream_t st = ctx->stream;
+    const size_t m = num_instance - 1;
+    size_t rows = n;
+    if (idx) {
+        rows = 0;
+        for (size_t j = 0; j < n; j++) rows = std::max<size_t>(rows, (size_t)idx[j] + 1);
+    }
+    std::vector<uint32_t> words(vb_points_count(num_instance));
+    vb_points_words(gamma_abc_g1, num_instance, words.data());
+    DevBuf d_pts(words.size() * 4), d_values(rows * m * 8), d_idx(idx ? n * 4 : 0), d_xk(vb_each_x_bytes(n)), d_have(n);
+    ZK_HIP(hipMemcpyAsync(d_pts.p, words.data(), words.size() * 4, hipMemcpyHostToDevice, st));
+    upload_h2d(ctx, d_values.p, values, rows * m * 8);
+    if (idx) ZK_HIP(hipMemcpyAsync(d_idx.p, idx, n * 4, hipMemcpyHostToDevice, st));
+    for (size_t off = 0; off < n; off += VB_PASS)
+        vb_u64_x_launch(st, d_pts.as<uint32_t>(), num_instance, idx ? d_values.as<uint64_t>() : d_values.as<uint64_t>() + m * off,
+                        idx ? d_idx.as<uint32_t>() + off : nullptr, std::min(VB_PASS, n - off), d_xk.as<uint8_t>() + vb_each_x_bytes(off), d_have.as<uint8_t>() + off);
+    std::vector<uint8_t> xk(vb_each_x_bytes(n)), have(n);
+    ZK_HIP(hipMemcpyAsync(xk.data(), d_xk.p, xk.size(), hipMemcpyDeviceToHost, st));
+    ZK_HIP(hipMemcpyAsync(have.data(), d_have.p, n, hipMemcpyDeviceToHost, st));
+    ZK_HIP(hipStreamSynchronize(st));
+    for (size_t j = 0; j < n; j++) {
+        inf_out[j] = have[j] ? 0 : 1;
+        if (have[j]) vb_point_limbs(xk.data() + vb_each_x_bytes(j), x_out + 12 * j);
+        else memset(x_out + 12 * j, 0, 96);
+    }
     ZK_LANE_END(ctx)
 }
 

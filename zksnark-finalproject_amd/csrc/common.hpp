@@ -254,7 +254,7 @@ struct MsmWorkspace {       // grown on demand, reused across proofs
 };
 
 // sizes of zkg16_ctx::timings (22 slots in use, declared with two to spare) and ::vb_timings
-constexpr int PROOF_TIMING_SLOTS = 24, VERIFY_TIMING_SLOTS = 13;
+constexpr int PROOF_TIMING_SLOTS = 24, VERIFY_TIMING_SLOTS = 15;
 
 }  // namespace zk
 
@@ -367,6 +367,7 @@ struct zkg16_ctx {
         int verify_wire_min = ZKG16_VERIFY_WIRE_MIN_DEFAULT;                     // zkg16_verify_batch_wire: shorter batches are decoded and answered on the host (the measured crossover)
         int check_satisfied = 0;                      // 1: the proving calls check their assignments after the SpMV (r1cs_check_kernel) and refuse unsatisfied ones
         int verify_each_after = ZKG16_VERIFY_EACH_AFTER_DEFAULT;                 // zkg16_verify_batch[_wire] with ok_each: range tests before the per-proof pass takes over
+        int verify_each_after_set = 0;                // 1: the caller set "verify_each_after" (the u64 entries read an unset option as 1; the stored value cannot tell unset from 32)
     } opt;
     std::map<std::string, zk::KernelStat> kstats;
     std::vector<zk::PendingEvent> pending_events;

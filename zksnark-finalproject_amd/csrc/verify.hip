@@ -977,9 +977,11 @@ struct VbDecider {
             if (!prod) f = pf::mul(f, fpart[t]);
             if (!sum_c) c = pf::pt_add(c, cpart[t]);
         }
+        // the u64 form: sum_i s_i gamma_abc[i] came with the sums, and only s_0 is looked at
+        const bool have_x = sums && inputs->sum_x;
         if (sums) {
             // plain integers below r (verify_batch.hpp: VbInputs): to Montgomery, nothing to reduce
-            for (size_t i = 0; i < ni; i++) {
+            for (size_t i = 0; i < (have_x ? 1 : ni); i++) {
                 Fr c;
                 memcpy(c.l, sums + 4 * i, sizeof c.l);
                 const Fr m = fp_to_mont(c);
@@ -991,8 +993,8 @@ struct VbDecider {
             }
         }
         // sum_k rho_k X_k = sum_i s_i gamma_abc[i]
-        HPt x = pf::pt_inf<pf::Fq64>();
-        for (size_t i = 0; i < ni; i++) {
+        HPt x = have_x ? vb_g1(inputs->sum_x, inputs->sum_x_inf && *inputs->sum_x_inf) : pf::pt_inf<pf::Fq64>();
+        for (size_t i = 0; i < ni && !have_x; i++) {
             const Fr sc = fp_from_mont(s[i]);
             uint64_t e[4];
             memcpy(e, sc.l, sizeof e);
@@ -1090,7 +1092,7 @@ void vb_decide(const VbKey &key, const VbBatch &b, const uint8_t *member, const 
     VbDecider dc(key, b, threads);
     dc.each = each;
     dc.inputs = inputs;
-    if (each) each->range_tests = 0;
+    if (each) each->range_tests = each->count_whole ? 1 : 0;
     for (size_t k = 0; k < b.k; k++)
         if (member[k]) dc.live.push_back((uint32_t)k);
     if (!prod) dc.miller = fetch_miller();
@@ -1128,6 +1130,16 @@ void vb_prime_expand(const uint64_t *xs, const uint64_t *js, const uint32_t *dig
         for (unsigned t = 0; t < 256; t++) o[1 + t] = ((d[t >> 5] >> (t & 31)) & 1) ? one : zero;
         o[257] = mont(d[0] & 0xFFFFFu);
         o[258] = mont(js[i]);
+    }
+}
+
+void vb_u64_expand(const uint64_t *values, size_t n, uint64_t *out) {
+    for (size_t i = 0; i < n; i++) {
+        Fr c = Fr::zero();
+        c.l[0] = (uint32_t)values[i];
+        c.l[1] = (uint32_t)(values[i] >> 32);
+        const Fr m = fp_to_mont(c);
+        memcpy(out + 4 * i, m.l, 32);
     }
 }
 
@@ -1243,6 +1255,26 @@ int zkg16_verify_prime_batch_host(const uint64_t *gamma_abc_g1, size_t num_insta
     try {
         std::vector<uint64_t> pub(4 * 259 * k);
         for (size_t i = 0; i < k; i++) (void)zkg16_prime_ext_inputs(xs[i], js[i], pub.data() + 4 * 259 * i);      // fails on a null pointer only
+        zk::vb_host(key, zk::VbBatch{pub.data(), proofs, inf, rho, k}, threads, ok, ok_each);
+    } catch (const std::bad_alloc &) {
+        return ZKG16_ERR_OOM;
+    }
+    return ZKG16_OK;
+}
+
+// ---- the u64 form (verify_batch.hpp): public inputs that are plain 64-bit values, expanded here
+int zkg16_verify_batch_u64_host(const uint64_t *gamma_abc_g1, size_t num_instance, const uint64_t alpha_beta[72], const uint64_t *gamma_neg_coeffs,
+                                const uint64_t *delta_neg_coeffs, size_t n_coeffs, const uint64_t *values, const uint64_t *proofs, const uint8_t *inf,
+                                const uint64_t *rho, size_t k, int threads, int *ok, uint8_t *ok_each) {
+    if (num_instance < 2 || !values || threads < 0 || k >> 32) return ZKG16_ERR_BAD_ARG;
+    const zk::VbKey key{gamma_abc_g1, num_instance, alpha_beta, gamma_neg_coeffs, delta_neg_coeffs, n_coeffs};
+    {
+        const int rc = zk::vb_check_args(key, zk::VbBatch{values, proofs, inf, rho, k}, ok);      // values stand in for the inputs made below
+        if (rc != ZKG16_OK) return rc;
+    }
+    try {
+        std::vector<uint64_t> pub(4 * (num_instance - 1) * k);
+        zk::vb_u64_expand(values, (num_instance - 1) * k, pub.data());
         zk::vb_host(key, zk::VbBatch{pub.data(), proofs, inf, rho, k}, threads, ok, ok_each);
     } catch (const std::bad_alloc &) {
         return ZKG16_ERR_OOM;

@@ -14,6 +14,11 @@
 //                         lane t owning digest bit t (rho and the digest word are the same address for a whole wave), then
 //   prime_sums_reduce_kernel  the blocks' partial sums added up, one lane per column — integer sums, so any order gives the same
 //   prime_z_expand_kernel the 259 canonical scalars of each listed request, for each_x_kernel
+//   u64_rho_sums_kernel   the u64 form's front (u64_inputs_dev.cuh): the multiplier sums of a slice of proofs, a 256-lane block per
+//                         (256 columns, slice), lane t owning a column (a row's values are contiguous across the wave), then
+//   u64_sums_reduce_kernel    the slices' partial sums added up, one lane per column
+//   u64_x_kernel          the prepared input X of each listed proof from its row of 64-bit values: a proof spread over L lanes,
+//                         each walking one shared-doubling chain over its columns, the L partial sums met through LDS
 //
 // Registers: a Miller lane's state is f (12 Fq = 168 dwords), T (84), Q and P (84) and the operation at hand; every Fq product is a
 // call (ffu.cuh: fqu_mul_call), so what is live across it sits in the callee-saved registers or in scratch: 4,272 B of scratch
@@ -28,6 +33,7 @@
 #include "pairing_dev.cuh"
 #include "pairing_each_dev.cuh"
 #include "prime_inputs_dev.cuh"
+#include "u64_inputs_dev.cuh"
 
 namespace zk {
 namespace {
@@ -221,6 +227,60 @@ __global__ __launch_bounds__(256) void prime_z_expand_kernel(const uint32_t *idx
     *o = make_ulonglong4(pi::ext_scalar(c, xs[i], js[i], dig + 8 * i), 0, 0, 0);
 }
 
+// ---- the u64 form's front (u64_inputs_dev.cuh)
+// block (x, y): the columns [256 x, 256 x + 256) (column 0: sum rho; the last tile may be partial) over the proofs of slice y,
+// [y * per, min(k, (y + 1) * per)) -> partial + (y * (m + 1) + column) * 4; every column of every slice is written
+__global__ __launch_bounds__(256) void u64_rho_sums_kernel(const uint64_t *values, size_t m, const uint64_t *rho, const uint8_t *live, size_t k, size_t per,
+                                                           uint64_t *partial) {
+    const size_t col = (size_t)blockIdx.x * u6::SUM_LANES + threadIdx.x;
+    if (col > m) return;
+    const size_t start = (size_t)blockIdx.y * per, lo = start < k ? start : k, hi = lo + per < k ? lo + per : k;
+    uint64_t acc[4];
+    u6::column_sum(col, values, m, rho, live, lo, hi, acc);
+    uint64_t *o = partial + ((size_t)blockIdx.y * (m + 1) + col) * 4;
+#pragma unroll
+    for (int i = 0; i < 4; i++) o[i] = acc[i];
+}
+
+// sums[c] = sum over the slices of partial[y][c], c <= m
+__global__ __launch_bounds__(64) void u64_sums_reduce_kernel(const uint64_t *partial, size_t slices, size_t m, uint64_t *sums) {
+    const size_t c = (size_t)blockIdx.x * 64 + threadIdx.x;
+    if (c > m) return;
+    uint64_t acc[4] = {0, 0, 0, 0};
+    for (size_t y = 0; y < slices; y++) pi::add256(acc, partial + (y * (m + 1) + c) * 4);
+#pragma unroll
+    for (int i = 0; i < 4; i++) sums[4 * c + i] = acc[i];
+}
+
+// X of the proof at list position j (row idx[j] of values; idx null: row j), written as each_x_kernel writes it.  One wave per
+// block; L (a power of two <= 64) lanes share a proof, 64 / L proofs a wave.  Lanes past the list keep the point at infinity and
+// take part in the rounds (the barriers are the block's)
+const unsigned X_POINT_WORDS = 56;
+static_assert(sizeof(XYZZ<FqU>) == X_POINT_WORDS * 4, "a partial sum in LDS");
+__global__ __launch_bounds__(64) void u64_x_kernel(const Affine<FqU> *gamma_abc, size_t m, const uint64_t *values, const uint32_t *idx, size_t n, unsigned L, FqU *xk,
+                                                   uint8_t *have) {
+    __shared__ uint32_t part_words[64 * X_POINT_WORDS];
+    XYZZ<FqU> *part = reinterpret_cast<XYZZ<FqU> *>(part_words);
+    const unsigned t = threadIdx.x, lane = t & (L - 1), per = 64 / L;
+    const size_t j = (size_t)blockIdx.x * per + t / L;
+    const bool active = j < n;
+    XYZZ<FqU> acc = XYZZ<FqU>::inf();
+    if (active) acc = u6::ladder(gamma_abc, m, values + m * (idx ? (size_t)idx[j] : j), lane, L);
+    for (unsigned s = L >> 1; s; s >>= 1) {
+        if (lane >= s && lane < 2 * s) part[t] = acc;
+        __syncthreads();
+        if (lane < s) xyzz_add(acc, part[t + s]);
+        __syncthreads();
+    }
+    if (active && lane == 0) {
+        FqU x = FqU::zero(), y = FqU::zero();
+        const bool h = u6::finish(acc, gamma_abc[0], x, y);
+        xk[2 * j] = x;
+        xk[2 * j + 1] = y;
+        have[j] = h ? 1 : 0;
+    }
+}
+
 unsigned blocks_of(size_t n) { return (unsigned)((n + 63) / 64); }
 
 }  // namespace
@@ -268,6 +328,59 @@ void vb_each_launch(hipStream_t st, const uint32_t *key_words, size_t num_instan
     ZK_HIP(hipGetLastError());
     hipLaunchKernelGGL(final_exp_kernel, dim3(blocks_of(n)), dim3(64), 0, st, (const uint64_t *)f, n, vb_frob(), (uint64_t *)nullptr,
                        reinterpret_cast<const uint64_t *>(key_words), verdict);
+    ZK_HIP(hipGetLastError());
+}
+
+size_t vb_each_x_bytes(size_t n) { return n * 2 * sizeof(FqU); }
+size_t vb_each_key_points_at() { return EACH_AB_WORDS + EACH_COEFF_WORDS; }
+
+void vb_each_tail_launch(hipStream_t st, const uint32_t *key_words, const uint32_t *idx, size_t n, const uint64_t *proofs, const uint8_t *inf, const void *xk,
+                         const uint8_t *have, void *scratch, uint8_t *verdict) {
+    if (!n) return;
+    uint64_t *f = static_cast<uint64_t *>(scratch);
+    const pd::Ell *ell = reinterpret_cast<const pd::Ell *>(key_words + EACH_AB_WORDS);
+    hipLaunchKernelGGL(each_miller_kernel, dim3(blocks_of(n)), dim3(64), 0, st, idx, n, proofs, inf, static_cast<const FqU *>(xk), have, ell, ell + 68, f);
+    ZK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(final_exp_kernel, dim3(blocks_of(n)), dim3(64), 0, st, (const uint64_t *)f, n, vb_frob(), (uint64_t *)nullptr,
+                       reinterpret_cast<const uint64_t *>(key_words), verdict);
+    ZK_HIP(hipGetLastError());
+}
+
+size_t vb_points_count(size_t n) { return EACH_POINT_WORDS * n; }
+void vb_points_words(const uint64_t *pts, size_t n, uint32_t *out) {
+    Affine<FqU> *o = reinterpret_cast<Affine<FqU> *>(out);
+    for (size_t i = 0; i < n; i++) {
+        G1Affine p;
+        memcpy(&p, pts + 12 * i, sizeof p);
+        o[i] = Affine<FqU>{fqu_from_sat(p.x), fqu_from_sat(p.y)};       // exact zeros stay exact: the point at infinity
+    }
+}
+void vb_point_limbs(const void *xk, uint64_t out[12]) {
+    const FqU *c = static_cast<const FqU *>(xk);
+    const G1Affine p{fqu_to_sat(c[0]), fqu_to_sat(c[1])};
+    memcpy(out, &p, sizeof p);
+}
+
+size_t vb_u64_sums_partial_words(size_t k, size_t m) { return u6::sum_slices(k) * (m + 1) * 4; }
+
+void vb_u64_sums_launch(hipStream_t st, const uint64_t *values, size_t m, const uint64_t *rho, const uint8_t *live, size_t k, uint64_t *partial, uint64_t *sums) {
+    const size_t slices = u6::sum_slices(k);
+    if (slices) {
+        const dim3 grid((unsigned)((m + 1 + u6::SUM_LANES - 1) / u6::SUM_LANES), (unsigned)slices);
+        hipLaunchKernelGGL(u64_rho_sums_kernel, grid, dim3(u6::SUM_LANES), 0, st, values, m, rho, live, k, u6::slice_len(k), partial);
+        ZK_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(u64_sums_reduce_kernel, dim3(blocks_of(m + 1)), dim3(64), 0, st, (const uint64_t *)partial, slices, m, sums);
+    ZK_HIP(hipGetLastError());
+}
+
+void vb_u64_x_launch(hipStream_t st, const uint32_t *gamma_abc_words, size_t num_instance, const uint64_t *values, const uint32_t *idx, size_t n, void *xk,
+                     uint8_t *have) {
+    if (!n) return;
+    const size_t m = num_instance - 1;
+    const unsigned L = u6::group_lanes(m), per = 64 / L;
+    hipLaunchKernelGGL(u64_x_kernel, dim3((unsigned)((n + per - 1) / per)), dim3(64), 0, st, reinterpret_cast<const Affine<FqU> *>(gamma_abc_words), m, values, idx, n, L,
+                       static_cast<FqU *>(xk), have);
     ZK_HIP(hipGetLastError());
 }
 

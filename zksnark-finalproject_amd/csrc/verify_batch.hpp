@@ -46,20 +46,28 @@ int vb_check_args(const VbKey &key, const VbBatch &b, const int *ok);
 // proofs are still not all named, every proof of a range that is still open goes to decide() in ONE call — verdict[j] != 0 iff
 // proof idx[j] holds by itself (what zkg16_verify_prepared says of it) — and no further range test is made.  decide empty: bisect
 // to the end, as the host form does.  range_tests: how many find_bad made (out).
+// count_whole (the u64 entries): the test of the whole batch counts as the first range test, so after = 1 hands every member proof
+// of a failed batch to decide() with no range test of bisecting made.
 struct VbEach {
     std::function<void(const uint32_t *idx, size_t n, uint8_t *verdict)> decide;
     size_t after = 0;
     size_t range_tests = 0;
+    bool count_whole = false;
 };
 // Where the public inputs come from when b.public_inputs is null (the prime form; num_instance = 260).  sums (nullable): the
 // num_instance multiplier sums s_i = sum_k rho_k z_{k,i} (z_{k,0} = 1) over the member proofs as plain integers below r, 4 u64 each
 // (vb_prime_sums_launch): the whole-batch test takes them instead of walking K x 259 inputs; s_0 is also summed here, and when the
 // two differ the sums are not used and sums_refused is set (out).  expand(): the k x (num_instance - 1) x 4 Montgomery inputs,
 // called at most once and only when a range test needs them (bisecting, or no sums).
+// sum_x (nullable; the u64 form, any num_instance): sum_i s_i gamma_abc[i] of those very sums, taken by the ctx's G1 MSM with the
+// device sums as scalars (12 u64 affine; *sum_x_inf != 0: the point at infinity).  The range that covers every member proof then
+// walks neither the inputs nor num_instance scalar multiplications; s_0 is cross-checked all the same, and a refusal drops sum_x too.
 struct VbInputs {
     const uint64_t *sums = nullptr;
     std::function<const uint64_t *()> expand;
     bool sums_refused = false;
+    const uint64_t *sum_x = nullptr;
+    const uint8_t *sum_x_inf = nullptr;
 };
 void vb_decide(const VbKey &key, const VbBatch &b, const uint8_t *member, const std::function<const uint64_t *()> &fetch_miller, const uint64_t *prod,
                const uint64_t *sum_c, const uint8_t *sum_c_inf, int threads, int *ok, uint8_t *ok_each, float ms[2], VbEach *each = nullptr,
@@ -67,6 +75,8 @@ void vb_decide(const VbKey &key, const VbBatch &b, const uint8_t *member, const 
 // the prime form's inputs on the host: digests (k x 8 words as the inputs kernel writes them = k x 32 digest bytes) ->
 // out (k x 259 x 4, Montgomery): x, the 256 digest bits, n = the digest mod 2^20, j
 void vb_prime_expand(const uint64_t *xs, const uint64_t *js, const uint32_t *digests, size_t k, uint64_t *out);
+// the u64 form's inputs on the host: n plain 64-bit values -> out (n x 4, Montgomery)
+void vb_u64_expand(const uint64_t *values, size_t n, uint64_t *out);
 // everything on host threads (zkg16_verify_batch_host).  dead (nullable, k bytes): proofs counted as failing membership whatever
 // their limbs say (zkg16_verify_batch_wire: a proof with a point that did not decode; its zero limbs would read as infinity)
 void vb_host(const VbKey &key, const VbBatch &b, int threads, int *ok, uint8_t *ok_each, const uint8_t *dead = nullptr);
@@ -122,6 +132,13 @@ size_t vb_each_scratch_bytes(size_t n);
 // Three kernels: X_k, the three-pair Miller loop (one squaring per bit), the final exponentiation with the comparison
 void vb_each_launch(hipStream_t st, const uint32_t *key_words, size_t num_instance, const uint32_t *idx, size_t n, const uint64_t *proofs, const uint8_t *inf,
                     const uint64_t *z, void *scratch, uint8_t *verdict);
+// the last two of those kernels alone, on X_k made elsewhere: xk (2 n U-form coordinates, 14 words each) and have (n flags) by
+// position j, as each_x_kernel and vb_u64_x_launch write them; scratch: room for vb_each_scratch_bytes(n)
+void vb_each_tail_launch(hipStream_t st, const uint32_t *key_words, const uint32_t *idx, size_t n, const uint64_t *proofs, const uint8_t *inf, const void *xk,
+                         const uint8_t *have, void *scratch, uint8_t *verdict);
+size_t vb_each_x_bytes(size_t n);       // room for xk of n proofs (their flags lie elsewhere)
+// where gamma_abc lies in a key block (u32 words from its start)
+size_t vb_each_key_points_at();
 
 // ---- the prime form's front (prime_inputs_dev.cuh): K prime requests of one trapdoor under the extended key of 260 points
 // (zkg16_prime_vk_extend), whose 259 public inputs x, bit_0 .. bit_255, n, j all follow from the 16 bytes (x, j).  Device pointers
@@ -135,5 +152,24 @@ void vb_prime_sums_launch(hipStream_t st, const uint64_t *xs, const uint64_t *js
                           uint64_t *partial, uint64_t *sums);
 // z (n x 259 x 4 canonical limbs, what vb_each_launch reads) of the requests idx[0 .. n) (idx null: requests 0 .. n - 1)
 void vb_prime_z_launch(hipStream_t st, const uint32_t *idx, size_t n, const uint64_t *xs, const uint64_t *js, const uint32_t *dig, uint64_t *z);
+
+// ---- the u64 form's front (u64_inputs_dev.cuh): a key of any num_instance >= 2 whose m = num_instance - 1 public inputs are
+// plain 64-bit values, values = k x m u64 row-major on the device
+// sums ((m + 1) x 4 u64, plain integers, unreduced) = sum_k rho_k (1, values[k][0], .., values[k][m - 1]) over the proofs with
+// live[k] != 0 (live null: all k of them); partial: room for vb_u64_sums_partial_words(k, m) u64.  k < 2^32.  Two kernels: a
+// 256-lane block per (256 columns, slice of proofs), then one lane per column adding the slices
+size_t vb_u64_sums_partial_words(size_t k, size_t m);
+void vb_u64_sums_launch(hipStream_t st, const uint64_t *values, size_t m, const uint64_t *rho, const uint8_t *live, size_t k, uint64_t *partial, uint64_t *sums);
+// X_k = gamma_abc[0] + sum_c values[idx[j]][c] gamma_abc[1 + c] of the proofs idx[0 .. n) (idx null: rows 0 .. n - 1), written
+// as each_x_kernel writes it: xk[2 j], xk[2 j + 1] affine in the U-form, have[j] = 0 for the point at infinity.  gamma_abc:
+// num_instance affine U-form points as they lie in a key block (vb_each_key_words).  A proof is spread over
+// L = u6::group_lanes(m) lanes, 64 / L proofs per wave
+// n affine points (12 u64 each, saturated Montgomery limbs; all-zero = the point at infinity) as the kernel reads them, without the
+// rest of a key block: vb_points_count(n) words.  vb_point_limbs: one X as the kernel wrote it (two U-form coordinates) -> 12 limbs
+size_t vb_points_count(size_t n);
+void vb_points_words(const uint64_t *pts, size_t n, uint32_t *out);
+void vb_point_limbs(const void *xk, uint64_t out[12]);
+void vb_u64_x_launch(hipStream_t st, const uint32_t *gamma_abc_words, size_t num_instance, const uint64_t *values, const uint32_t *idx, size_t n, void *xk,
+                     uint8_t *have);
 
 }  // namespace zk

@@ -626,6 +626,72 @@ class Device:
                                                   _ptr(live) if k else None, k, _ptr(sums)))
         return [sum(int(v) << (64 * i) for i, v in enumerate(row)) for row in sums]
 
+    # ---- the u64 form: keys whose public inputs are plain 64-bit values (the linear-equations route)
+    def verify_batch_u64(self, pvk, values, proofs, infs, rho=None, each=False):
+        """verify_batch for a key whose public inputs are all plain u64 (zkg16_verify_batch_u64): values [k, num_instance - 1]
+        uint64 in the place of the Montgomery limbs; the multiplier sums, sum_i s_i gamma_abc[i] and, when the per-proof pass runs,
+        each proof's prepared input are made on the device from them.  With the option "verify_each_after" unset that pass decides
+        every proof right after a failed test of the whole batch.  Everything else as verify_batch."""
+        args, k = _verify_u64_args(pvk, values, proofs, infs, rho)
+        ok = C.c_int(0)
+        ok_each = np.zeros(k, dtype=np.uint8) if each else None
+        self._check(self.lib.zkg16_verify_batch_u64(self.ctx, *args, C.byref(ok), _ptr(ok_each)))
+        return (bool(ok.value), ok_each.astype(bool)) if each else bool(ok.value)
+
+    def verify_batch_u64_wire(self, pvk, values, proof_bytes, rho=None, each=False, status=False):
+        """verify_batch_wire for the u64 form (zkg16_verify_batch_u64_wire): proof_bytes = k x 192 compressed bytes; rho is drawn
+        from `secrets` when None.  Returns as verify_batch_wire."""
+        raw = np.ascontiguousarray(np.frombuffer(proof_bytes, dtype=np.uint8) if isinstance(proof_bytes, (bytes, bytearray, memoryview))
+                                   else np.asarray(proof_bytes, dtype=np.uint8)).reshape(-1)
+        if raw.size % 192:
+            raise ValueError("verify_batch_u64_wire: a compressed proof is 192 bytes")
+        k = raw.size // 192
+        args, _ = _verify_u64_args(pvk, values, None, None, rho, k=k)
+        ok = C.c_int(0)
+        ok_each = np.zeros(k, dtype=np.uint8) if each else None
+        st = np.zeros((k, 3), dtype=np.uint8) if status else None
+        self._check(self.lib.zkg16_verify_batch_u64_wire(self.ctx, *args[:7], _ptr(raw) if k else None, args[9], k, C.byref(ok), _ptr(ok_each), _ptr(st)))
+        out = (bool(ok.value),) + ((ok_each.astype(bool),) if each else ()) + ((st,) if status else ())
+        return out if len(out) > 1 else out[0]
+
+    def verify_each_u64(self, pvk, values, proofs, infs):
+        """verify_each for the u64 form (zkg16_verify_each_u64) -> bool array [k]."""
+        args, k = _verify_u64_args(pvk, values, proofs, infs, np.ones((_u64(proofs).reshape(-1, 48).shape[0], 2), dtype=np.uint64))
+        ok_each = np.zeros(k, dtype=np.uint8)
+        self._check(self.lib.zkg16_verify_each_u64(self.ctx, *args[:9], k, _ptr(ok_each)))
+        return ok_each.astype(bool)
+
+    def u64_rho_sums(self, values, rho, live=None):
+        """The u64 form's sums kernels by themselves (zkg16_u64_rho_sums): values [k, m] uint64, rho [k, 2], live [k] bytes or None
+        (all) -> the m + 1 sums sum_k rho_k (1, values[k][0], .., values[k][m - 1]) as Python integers (unreduced)."""
+        values, rho = _u64(values), _u64(rho).reshape(-1, 2)
+        if values.ndim != 2 or values.shape[1] == 0:
+            raise ValueError("u64_rho_sums: values is [k, m] with m >= 1")
+        k, m = values.shape
+        live = None if live is None else np.ascontiguousarray(live, dtype=np.uint8).reshape(-1)
+        if rho.shape[0] != k or (live is not None and live.shape[0] != k):
+            raise ValueError("u64_rho_sums: one multiplier and one live byte per row")
+        sums = np.zeros((m + 1, 4), dtype=np.uint64)
+        self._check(self.lib.zkg16_u64_rho_sums(self.ctx, _ptr(values) if k else None, m, _ptr(rho) if k else None, _ptr(live) if k else None, k, _ptr(sums)))
+        return [sum(int(v) << (64 * i) for i, v in enumerate(row)) for row in sums]
+
+    def u64_prepared_inputs(self, gamma_abc_g1, values, idx=None):
+        """The u64 form's X kernel by itself (zkg16_u64_prepared_inputs): gamma_abc_g1 [num_instance, 12] (all-zero limbs: the
+        point at infinity), values [rows, num_instance - 1] uint64, idx (None: every row in order) the rows wanted, repeats allowed
+        -> (points [n, 12] affine Montgomery limbs, infinity flags [n]): gamma_abc[0] + sum_c values[row][c] gamma_abc[1 + c]."""
+        gabc, values = _u64(gamma_abc_g1).reshape(-1, 12), _u64(values)
+        if values.ndim != 2 or values.shape[1] != gabc.shape[0] - 1:
+            raise ValueError("u64_prepared_inputs: values is [rows, num_instance - 1]")
+        idx = None if idx is None else np.ascontiguousarray(idx, dtype=np.uint32).reshape(-1)
+        if idx is not None and idx.size and int(idx.max()) >= values.shape[0]:
+            raise ValueError("u64_prepared_inputs: idx names a row that is not there")
+        n = values.shape[0] if idx is None else idx.shape[0]
+        out = np.zeros((n, 12), dtype=np.uint64)
+        inf = np.zeros(n, dtype=np.uint8)
+        self._check(self.lib.zkg16_u64_prepared_inputs(self.ctx, _ptr(gabc), gabc.shape[0], _ptr(values) if n else None, _ptr(idx) if n else None, n,
+                                                       _ptr(out) if n else None, _ptr(inf) if n else None))
+        return out, inf
+
     def final_exp_batch(self, f):
         """The verifier's final exponentiation of n Fq12 values on the device (zkg16_final_exp_batch): [n, 72] -> [n, 72], each row
         bit-equal to final_exp() of that row."""
@@ -653,15 +719,18 @@ class Device:
             self._check(rc)
         return out, inf, status[:n].copy()
 
-    def verify_batch_timings(self, prime=False):
+    def verify_batch_timings(self, prime=False, u64=False):
         """ms of the last verify_batch / verify_batch_wire: membership, scaling + Miller, product tree, MSM, host equation, bisecting,
         total wall, whether the host form answered, the decode kernels (verify_batch_wire only), the per-proof pass that took over
         from bisecting (0 when it did not run) and the number of range tests bisecting made.  prime=True (after verify_prime_batch /
         verify_prime_batch_wire) adds prime_inputs_ms and prime_sums_ms, the two kernels of the prime form's front (0 when the host
-        form answered or the last call was not a prime call)."""
+        form answered or the last call was not a prime call).  u64=True (after verify_batch_u64 / verify_batch_u64_wire) adds those
+        and u64_sums_ms and u64_x_ms, the sums kernels and the X kernel of the u64 form's per-proof pass (0 when the host form
+        answered, the last call was not a u64 call or that pass did not run); after those calls range_tests counts the test of the
+        whole batch too."""
         names = ("membership_ms", "miller_ms", "product_ms", "msm_ms", "host_ms", "bisect_ms", "total_ms", "host_form", "decode_ms", "each_ms", "range_tests",
-                 "prime_inputs_ms", "prime_sums_ms")
-        cap = 13 if prime else 11
+                 "prime_inputs_ms", "prime_sums_ms", "u64_sums_ms", "u64_x_ms")
+        cap = 15 if u64 else 13 if prime else 11
         ms = (C.c_float * cap)()
         n = self.lib.zkg16_verify_batch_timings(self.ctx, ms, cap)
         return {names[i]: float(ms[i]) for i in range(n)}
@@ -1151,6 +1220,38 @@ def _verify_prime_args(pvk, xs, js, proofs, infs, rho, k=None):
     keep = (gabc, ab, g, d, xs, js, proofs, infs, rho)
     return _KeepAlive((_ptr(gabc), gabc.shape[0], _ptr(ab), _ptr(g), _ptr(d), g.shape[0], _ptr(xs) if k else None, _ptr(js) if k else None, _ptr(proofs),
                        _ptr(infs), _ptr(rho), k), keep), k
+
+
+def _verify_u64_args(pvk, values, proofs, infs, rho, k=None):
+    """_verify_batch_args for the u64 form: values [k, num_instance - 1] uint64 in the place of the public inputs"""
+    gabc = _u64(pvk["gamma_abc_g1"]).reshape(-1, 12)
+    proofs = _u64(proofs).reshape(-1, 48) if proofs is not None else None
+    k = proofs.shape[0] if proofs is not None else k
+    infs = np.ascontiguousarray(infs, dtype=np.uint8).reshape(-1, 3) if proofs is not None else None
+    values = _u64(values)
+    if gabc.shape[0] < 2 or values.shape != (k, gabc.shape[0] - 1):
+        raise ValueError("verify_batch_u64: values is [k, num_instance - 1] for a key with at least two instance variables")
+    if infs is not None and infs.shape[0] != k:
+        raise ValueError("verify_batch_u64: one flag triple per proof")
+    rho = draw_rho(k) if rho is None else _u64(rho).reshape(-1, 2)
+    if rho.shape[0] != k:
+        raise ValueError("verify_batch_u64: one multiplier per proof")
+    g, d = _u64(pvk["gamma_neg_pc"]).reshape(-1, 36), _u64(pvk["delta_neg_pc"]).reshape(-1, 36)
+    ab = _u64(pvk["alpha_beta"])
+    keep = (gabc, ab, g, d, values, proofs, infs, rho)
+    return _KeepAlive((_ptr(gabc), gabc.shape[0], _ptr(ab), _ptr(g), _ptr(d), g.shape[0], _ptr(values) if k else None, _ptr(proofs), _ptr(infs), _ptr(rho), k),
+                      keep), k
+
+
+def verify_batch_u64_host(pvk, values, proofs, infs, rho=None, each=False, threads=0):
+    """Device.verify_batch_u64's verdicts on host threads alone (zkg16_verify_batch_u64_host; threads 0 = 8; no GPU): the values are
+    expanded to Montgomery limbs and verify_batch_host answers."""
+    lib = _lib.load()
+    args, k = _verify_u64_args(pvk, values, proofs, infs, rho)
+    ok = C.c_int(0)
+    ok_each = np.zeros(k, dtype=np.uint8) if each else None
+    _check_host(lib.zkg16_verify_batch_u64_host(*args, threads, C.byref(ok), _ptr(ok_each)))
+    return (bool(ok.value), ok_each.astype(bool)) if each else bool(ok.value)
 
 
 def verify_prime_batch_host(pvk, xs, js, proofs, infs, rho=None, each=False, threads=0):

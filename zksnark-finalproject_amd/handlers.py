@@ -498,11 +498,14 @@ def prove_linear_equations_batch(dev, systems, seed=0, key=None, check_on_device
 def verify_linear_equations(vk, systems, proofs_b64, dev=None):
     """The verification the linear handler runs on its own proof (linear_equations.rs:92-94) for K proofs under one key, checked
     together: systems = [(a, b), ...], each n x n with the n entries of b.  The n^2 + n public inputs a[0][*], b[0], a[1][*], b[1], ...
-    are built per proof and the batch is answered by verify_proofs (with dev: Device.verify_batch_wire and its thresholds)
+    are built per proof and the batch is answered by verify_proofs; with dev they stay 64-bit values, one uint64 array for the batch,
+    and Device.verify_batch_u64_wire answers (its thresholds and its per-proof take-over)
     -> {valid: [K bools], verifying_time, decode_time}.  A system that is not square, or holds a value that is no u64, is valid=False
     for that entry only."""
     if len(systems) != len(proofs_b64):
         raise ValueError("verify_linear_equations: one system per proof")
+    if dev is not None:
+        return _verify_linear_equations_u64(dev, vk, systems, proofs_b64)
     pubs = []
     for a, b in systems:
         try:
@@ -515,6 +518,64 @@ def verify_linear_equations(vk, systems, proofs_b64, dev=None):
         except (ValueError, TypeError, OverflowError):
             pubs.append(np.zeros((0, 4), dtype=np.uint64))       # the wrong shape: verify_proofs answers invalid for this entry
     return verify_proofs(vk, pubs, proofs_b64, dev=dev)
+
+
+def _linear_u64_row(a, b):
+    """A request's n (n + 1) public inputs a[0][*], b[0], a[1][*], b[1], ... = the row-major matrix [a | b] as one uint64 vector, or
+    None for what verify_linear_equations calls no system.  Integer arrays (and lists numpy reads as such) are checked and laid out
+    by numpy, no Python integer per value; anything else (objects, floats, strings) goes value by value through int(), exactly as
+    without a device."""
+    try:
+        am, bv = np.asarray(a), np.asarray(b)
+        if am.dtype.kind not in "ui" or bv.dtype.kind not in "ui":
+            rows = [[int(v) for v in row] for row in a]
+            rhs = [int(v) for v in b]
+            if any(len(row) != len(rhs) for row in rows) or not all(0 <= v < 1 << 64 for row in rows for v in row) or \
+                    not all(0 <= v < 1 << 64 for v in rhs):
+                return None
+            am, bv = np.array(rows, dtype=np.uint64).reshape(len(rows), -1), np.array(rhs, dtype=np.uint64)
+        n = bv.shape[0] if bv.ndim == 1 else 0
+        if n == 0 or am.shape != (n, n) or (am.dtype.kind == "i" and am.min() < 0) or (bv.dtype.kind == "i" and bv.min() < 0):
+            return None
+        return np.concatenate([am.astype(np.uint64), bv.astype(np.uint64)[:, None]], axis=1).reshape(-1)
+    except (ValueError, TypeError, OverflowError):
+        return None
+
+
+def _verify_linear_equations_u64(dev, vk, systems, proofs_b64):
+    """verify_linear_equations with a device: every public input of the route is a plain u64, so the K' well-formed requests
+    travel as one [K', n (n + 1)] uint64 array and 192 proof bytes each into Device.verify_batch_u64_wire — 8 bytes per input, no
+    Montgomery conversion on the host, the multiplier sums and the prepared inputs taken on the device.  Entries that are malformed
+    never reach the device; the answers are verify_proofs'."""
+    t0 = time.perf_counter()
+    k = len(proofs_b64)
+    valid = [False] * k
+    try:
+        vk = _decode_key(vk)
+        pvk = vk if "alpha_beta" in vk else device.pvk_prepare(vk)
+        ni = np.asarray(pvk["gamma_abc_g1"]).reshape(-1, 12).shape[0]
+    except (ValueError, IndexError, Zkg16Error) as e:
+        if not _answers_invalid(e):
+            raise
+        return dict(valid=valid, verifying_time=0.0, decode_time=time.perf_counter() - t0)
+    idx, proofs, rows = [], [], []
+    for i, ((a, b), pb) in enumerate(zip(systems, proofs_b64)):
+        try:
+            proof = base64.standard_b64decode(pb)
+        except (ValueError, TypeError):
+            continue
+        row = _linear_u64_row(a, b)
+        if row is None or row.shape[0] != ni - 1 or ni < 2 or len(proof) != 192:
+            continue
+        idx.append(i)
+        proofs.append(proof)
+        rows.append(row)
+    t1 = time.perf_counter()
+    if idx:
+        _, each = dev.verify_batch_u64_wire(pvk, np.stack(rows), b"".join(proofs), each=True)
+        for i, ok in zip(idx, each):
+            valid[i] = bool(ok)
+    return dict(valid=valid, verifying_time=time.perf_counter() - t1, decode_time=t1 - t0)
 
 
 def prove_prime(dev, x, i, seed=7, keep_key=False, check_satisfied=False, check_on_device=False):
