@@ -55,7 +55,7 @@ typedef struct zkg16_ctx zkg16_ctx;
 ZKG16_API int zkg16_init(const int *device_ids, int n_devices, zkg16_ctx **out);
 ZKG16_API void zkg16_destroy(zkg16_ctx *ctx);
 ZKG16_API const char *zkg16_strerror(int status);
-ZKG16_API const char *zkg16_last_error(zkg16_ctx *ctx); /* text of the last HIP failure on this ctx */
+ZKG16_API const char *zkg16_last_error(zkg16_ctx *ctx); /* text of the last HIP failure on this ctx; ctx NULL: the last refusal of a host-only entry on this thread */
 ZKG16_API const char *zkg16_version(void);
 
 /* ---- proving key residency  (replaces holding `ProvingKey<Bls12_381>` on the host: matrix_proof.rs:129-140).
@@ -364,6 +364,45 @@ ZKG16_API int zkg16_final_exp_batch(zkg16_ctx *ctx, const uint64_t *f /* n x 72 
  * a u64 call or, for [14], the per-proof pass did not run); in those calls [10] counts the test of the whole batch too.
  * Returns the number of entries written (at most cap). */
 ZKG16_API int zkg16_verify_batch_timings(zkg16_ctx *ctx, float *ms, int cap);
+
+/* ---- re-randomising proofs (ark-groth16 0.4 Groth16::rerandomize_proof): for non-zero r1, r2 in Fr and the key's delta_g2
+ *
+ *     A' = r1^-1 A        B' = r1 B + (r1 r2) delta        C' = C + r2 A
+ *
+ * (A', B', C') verifies for exactly the public inputs (A, B, C) verifies for, and a proof that does not verify still does not:
+ * both sides of the pairing equation gain e(A, delta)^r2.  Nothing is drawn here: r1, r2 are the caller's, k x 4 Montgomery limbs
+ * each, as r and s of zkg16_prove_batch.  proofs k x 48 limbs (A 12 | B 24 | C 12), inf k x 3 flags (nullable: none set).
+ * A point is the point at infinity when its flag is set or all its limbs are zero (zkg16_verify_prepared's rule); an output at
+ * infinity is zero limbs with its flag set (0xC0 and zeros on the wire).  A = O gives A' = O and C' = C; B = O gives
+ * B' = (r1 r2) delta; C = O gives C' = r2 A.  The limb forms do not test membership, like zkg16_verify_prepared's key points: what
+ * they return for a point that is on no curve, or for limbs that are not below q, is unspecified (nothing traps).
+ * ZKG16_ERR_BAD_ARG before any work, outputs untouched: k == 0, a null pointer (inf excepted), a delta_g2 of all-zero limbs, any
+ * r1 or r2 that is zero or whose limbs are not below r — zkg16_last_error (of the ctx; of NULL for the host form, per thread)
+ * names the proof index and which multiplier.
+ *
+ * zkg16_rerandomize_batch_host: no ctx and no GPU, on up to `threads` host threads (0 = 8), by the kernels' own arithmetic compiled
+ * for the host: the reference for every byte the device produces.
+ * zkg16_rerandomize_batch: on a lane of the ctx, one GPU lane per (proof, group), in passes of at most 65,536 proofs (option
+ * "rerandomize_pass" lowers that); byte for byte the host form's output.  Batches shorter than option "rerandomize_min" are
+ * answered by the host form (default 256, the measured crossover: see zkg16_set_option).
+ * zkg16_rerandomize_batch_wire: proof_bytes k x 192 compressed bytes in, bytes_out k x 192 out, nothing but bytes crossing the
+ * bus: decoded by the decompress kernels, every decoded point tested by the membership kernels, re-randomised, encoded by the
+ * compress kernel.  A proof with a point that does not decode or is not in the subgroup gets the validating host decoder's status
+ * (1 to 5, as decode_status of zkg16_verify_batch_wire) in status (k x 3, nullable) and 192 zero bytes out; the other proofs are
+ * unaffected, and the return code is ZKG16_OK.  With status null and any such proof: ZKG16_ERR_BAD_ARG (bytes_out is written). */
+ZKG16_API int zkg16_rerandomize_batch_host(const uint64_t delta_g2[24], const uint64_t *proofs, const uint8_t *inf, const uint64_t *r1, const uint64_t *r2,
+                                           size_t k, int threads, uint64_t *proofs_out, uint8_t *inf_out);
+ZKG16_API int zkg16_rerandomize_batch(zkg16_ctx *ctx, const uint64_t delta_g2[24], const uint64_t *proofs, const uint8_t *inf, const uint64_t *r1,
+                                      const uint64_t *r2, size_t k, uint64_t *proofs_out, uint8_t *inf_out);
+ZKG16_API int zkg16_rerandomize_batch_wire(zkg16_ctx *ctx, const uint64_t delta_g2[24], const uint8_t *proof_bytes, const uint64_t *r1, const uint64_t *r2,
+                                           size_t k, uint8_t *bytes_out, uint8_t *status);
+/* Stage entry: the device form of zkg16_points_compress, byte for byte (the flag alone says infinity; inf nullable).  n == 0: ZKG16_OK. */
+ZKG16_API int zkg16_points_compress_batch(zkg16_ctx *ctx, int group, const uint64_t *points, const uint8_t *inf, size_t n, uint8_t *out);
+/* The last zkg16_rerandomize_batch / zkg16_rerandomize_batch_wire on this ctx, in ms (device events unless said): [0] upload,
+ * [1] decompress + membership kernels (wire only), [2] the G1 kernel, [3] the G2 kernel (the two run side by side), [4] the compress
+ * kernel (wire only), [5] read-back, [6] total wall (host clock); [7] = 1 when the host form answered (then only [6] is set).  A
+ * refused call leaves the entries as they were.  Returns the number of entries written (at most cap). */
+ZKG16_API int zkg16_rerandomize_timings(zkg16_ctx *ctx, float *ms, int cap);
 
 /* ---- the prime form: K proofs of the prime handler made under ONE trapdoor (zkg16_prove_prime_batch), verified together.
  * Request i's own key is the template's with gamma_abc_g1[0] + n_i V_n - j_i V_j in front, so no two requests share a key — but
@@ -942,6 +981,12 @@ ZKG16_API void zkg16_kernel_stats_reset(zkg16_ctx *ctx);
  *                    and return ZKG16_ERR_UNSATISFIED, writing nothing, when one fails (zkg16_r1cs_check above; zkg16_last_check); any
  *                    other value: ZKG16_ERR_BAD_ARG.  The one option that can change what a call returns — for assignments no verifier accepts
  *   "sponge_chain_segment" permutations of a chain per launch of the chain kernel (0 = 256, else 1..65535): the state is carried between launches
+ *   "rerandomize_min" zkg16_rerandomize_batch[_wire]: shorter batches are answered by the host form (1 = always the device, 0 restores
+ *                    the default).  Default 256: the smallest measured K at which both device forms beat the host form on eight
+ *                    threads in every round, 0.092 (limbs) and 0.109 (wire) against 0.163 ms per proof; at K = 64 they lost, 0.367 and
+ *                    0.432 against 0.168: a device call costs 24 to 28 ms whatever K is (profiles/rerandomize_timing.txt)
+ *   "rerandomize_pass" zkg16_rerandomize_batch[_wire]: proofs per kernel launch (0 = 65,536, else 1..65,536; tests lower it to run
+ *                    several passes at small k)
  * Unknown names return ZKG16_ERR_UNSUPPORTED. */
 ZKG16_API int zkg16_set_option(zkg16_ctx *ctx, const char *name, int64_t value);
 

@@ -107,6 +107,11 @@ SIGNATURES = {
     "zkg16_verify_each": (C.c_int, [ctxp, vp, sz, vp, vp, vp, sz, vp, vp, vp, sz, vp]),
     "zkg16_final_exp_batch": (C.c_int, [ctxp, vp, sz, vp]),
     "zkg16_verify_batch_timings": (C.c_int, [ctxp, C.POINTER(C.c_float), C.c_int]),
+    "zkg16_rerandomize_batch_host": (C.c_int, [vp, vp, vp, vp, vp, sz, C.c_int, vp, vp]),
+    "zkg16_rerandomize_batch": (C.c_int, [ctxp, vp, vp, vp, vp, vp, sz, vp, vp]),
+    "zkg16_rerandomize_batch_wire": (C.c_int, [ctxp, vp, vp, vp, vp, sz, vp, vp]),
+    "zkg16_points_compress_batch": (C.c_int, [ctxp, C.c_int, vp, vp, sz, vp]),
+    "zkg16_rerandomize_timings": (C.c_int, [ctxp, C.POINTER(C.c_float), C.c_int]),
     "zkg16_g1_decompress": (C.c_int, [vp, sz, vp, vp, C.c_int, C.POINTER(C.c_int)]),
     "zkg16_g2_decompress": (C.c_int, [vp, sz, vp, vp, C.c_int, C.POINTER(C.c_int)]),
     "zkg16_points_compress": (C.c_int, [C.c_int, vp, vp, sz, vp]),

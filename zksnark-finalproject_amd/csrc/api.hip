@@ -112,6 +112,11 @@ int fail(zkg16_ctx *ctx, const HipError &e) {
     return ZKG16_ERR_HIP;
 }
 
+std::string &host_last_error() {
+    static thread_local std::string text;
+    return text;
+}
+
 LaneLease::LaneLease(zkg16_ctx *r) : root(r) {
     {
         std::unique_lock<std::mutex> lk(root->lane_mu);
@@ -274,7 +279,8 @@ const char *zkg16_strerror(int status) {
     }
 }
 
-const char *zkg16_last_error(zkg16_ctx *ctx) { return ctx ? ctx->last_error.c_str() : ""; }
+// without a ctx: the last refusal of a host-only entry point on the calling thread (empty until one has refused)
+const char *zkg16_last_error(zkg16_ctx *ctx) { return ctx ? ctx->last_error.c_str() : zk::host_last_error().c_str(); }
 
 int zkg16_init(const int *device_ids, int n_devices, zkg16_ctx **out) {
     if (!out) return ZKG16_ERR_BAD_ARG;
@@ -417,6 +423,10 @@ int set_option_one(zkg16_ctx *ctx, const char *name, int64_t v) {
         if (rc == ZKG16_OK) o.verify_each_after_set = v != 0;      // the u64 entries have a default of their own (zkg16_verify_batch_u64)
         return rc;
     }
+    // zkg16_rerandomize_batch[_wire]: batches shorter than this go to the host form (0 restores the default; 1 = always the device)
+    if (is("rerandomize_min")) return set(o.rerandomize_min, 0, 1 << 30, v == 0 ? ZKG16_RERANDOMIZE_MIN_DEFAULT : v);
+    // ... and proofs per launch (0 = 65,536)
+    if (is("rerandomize_pass")) return set(o.rerandomize_pass, 0, 65536, v);
     // 0 (default): the proving calls prove whatever they are handed; 1: they check (A z)(B z) == C z after the SpMV and refuse with ZKG16_ERR_UNSATISFIED
     if (is("check_satisfied")) return set(o.check_satisfied, 0, 1, v);
     if (is("reduce_chunk")) return set(o.reduce_chunk, 0, 64, v, (v & (v - 1)) == 0);      // 0 = default, else a power of two up to 64

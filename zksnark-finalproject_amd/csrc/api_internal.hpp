@@ -48,7 +48,21 @@ enum VerifyTiming : int {
     V_U64_X = 14,          // ... and the X kernel of its per-proof pass (0 when that pass did not run)
     V_COUNT = 15
 };
-static_assert(T_COUNT <= PROOF_TIMING_SLOTS && V_COUNT == VERIFY_TIMING_SLOTS, "timing slots");
+// ---- zkg16_ctx::rr_timings (zkg16_rerandomize_timings), ABI as well
+enum RerandomizeTiming : int {
+    R_UPLOAD = 0,          // proofs (limbs or wire bytes), multipliers and delta to the device (device events, as the next five)
+    R_DECODE = 1,          // the decompress and membership kernels (zkg16_rerandomize_batch_wire only)
+    R_G1 = 2,              // the G1 kernel: A' and C'
+    R_G2 = 3,              // the G2 kernel: B' (it runs beside the G1 kernel, so the two sum to more than the call)
+    R_COMPRESS = 4,        // the compress kernel (zkg16_rerandomize_batch_wire only)
+    R_READBACK = 5,        // results to the host
+    R_TOTAL = 6,           // wall time of the call
+    R_HOST_FORM = 7,       // 1 when the host form answered
+    R_COUNT = 8
+};
+static_assert(T_COUNT <= PROOF_TIMING_SLOTS && V_COUNT == VERIFY_TIMING_SLOTS && R_COUNT == RERANDOMIZE_TIMING_SLOTS, "timing slots");
+// the last refusal of a host-only entry point on this thread (zkg16_last_error(NULL)); api.hip
+std::string &host_last_error();
 
 int fail(zkg16_ctx *ctx, const HipError &e);      // api.hip: the error's text into ctx->last_error -> its status
 

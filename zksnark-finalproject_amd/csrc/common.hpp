@@ -254,7 +254,7 @@ struct MsmWorkspace {       // grown on demand, reused across proofs
 };
 
 // sizes of zkg16_ctx::timings (22 slots in use, declared with two to spare) and ::vb_timings
-constexpr int PROOF_TIMING_SLOTS = 24, VERIFY_TIMING_SLOTS = 15;
+constexpr int PROOF_TIMING_SLOTS = 24, VERIFY_TIMING_SLOTS = 15, RERANDOMIZE_TIMING_SLOTS = 8;
 
 }  // namespace zk
 
@@ -273,6 +273,11 @@ constexpr int PROOF_TIMING_SLOTS = 24, VERIFY_TIMING_SLOTS = 15;
 // profiles/sponge_chains_timing.txt the device wins zkg16_witness_matrix_batch from 3072 chains and zkg16_matrix_hash_batch from 1024 at
 // every measured n, but zkg16_prove_matrix_batch (chain count = a sub-batch's) only at n = 8 — no count wins on every entry
 #define ZKG16_SPONGE_CHAINS_MIN_DEFAULT INT64_MAX
+// zkg16_rerandomize_batch[_wire] answer batches shorter than this through the host form: the smallest measured K at which both device
+// forms beat zkg16_rerandomize_batch_host on eight threads in all three rounds, 0.092 (limbs) and 0.109 (wire) against 0.163 ms per
+// proof; at K = 64 they lost, 0.367 and 0.432 against 0.168 — a device call costs 24 to 28 ms whatever K is
+// (profiles/rerandomize_timing.txt)
+#define ZKG16_RERANDOMIZE_MIN_DEFAULT 256
 // zkg16_prove_matrix: fewest permutations a slice of the streamed assignment may hold (witness.hip: matrix_stream_slices)
 #define MATRIX_SLICE_MIN_DEFAULT 512
 
@@ -367,6 +372,8 @@ struct zkg16_ctx {
         int verify_wire_min = ZKG16_VERIFY_WIRE_MIN_DEFAULT;                     // zkg16_verify_batch_wire: shorter batches are decoded and answered on the host (the measured crossover)
         int check_satisfied = 0;                      // 1: the proving calls check their assignments after the SpMV (r1cs_check_kernel) and refuse unsatisfied ones
         int verify_each_after = ZKG16_VERIFY_EACH_AFTER_DEFAULT;                 // zkg16_verify_batch[_wire] with ok_each: range tests before the per-proof pass takes over
+        int rerandomize_min = ZKG16_RERANDOMIZE_MIN_DEFAULT;                     // zkg16_rerandomize_batch[_wire]: shorter batches are answered by the host form
+        int rerandomize_pass = 0;                     // zkg16_rerandomize_batch[_wire]: proofs per launch (0 = 65,536; tests lower it to reach several passes at small k)
         int verify_each_after_set = 0;                // 1: the caller set "verify_each_after" (the u64 entries read an unset option as 1; the stored value cannot tell unset from 32)
     } opt;
     std::map<std::string, zk::KernelStat> kstats;
@@ -374,6 +381,7 @@ struct zkg16_ctx {
     void *circuit_stage = nullptr;                    // pinned staging block of zkg16_circuit_load (root ctx; grown on demand)
     size_t circuit_stage_bytes = 0;
     float vb_timings[zk::VERIFY_TIMING_SLOTS] = {0};                    // zkg16_verify_batch_timings (root: the last batch verified on any lane)
+    float rr_timings[zk::RERANDOMIZE_TIMING_SLOTS] = {0};               // zkg16_rerandomize_timings (root: the last batch re-randomised on any lane)
     int num_cus = 256;
     bool lds_attr_fixup[2] = {false, false}, lds_attr_ntt = false, lds_attr_linear_elim = false;      // hipFuncSetAttribute(max dynamic LDS) done on this device
     zk::FixedBaseCache fb_g1, fb_g2;

@@ -19,6 +19,10 @@
 //   u64_sums_reduce_kernel    the slices' partial sums added up, one lane per column
 //   u64_x_kernel          the prepared input X of each listed proof from its row of 64-bit values: a proof spread over L lanes,
 //                         each walking one shared-doubling chain over its columns, the L partial sums met through LDS
+//   rerandomize_g1_kernel A' = r1^-1 A and C' = C + r2 A of each proof (rerandomize_dev.cuh, as the two below): one doubling chain, two
+//                         accumulators, one inversion for both results
+//   rerandomize_g2_kernel B' = r1 B + (r1 r2) delta of each proof: one interleaved ladder over {B, delta, B + delta}
+//   compress_kernel       n affine points of one group to their 48 / 96 wire bytes
 //
 // Registers: a Miller lane's state is f (12 Fq = 168 dwords), T (84), Q and P (84) and the operation at hand; every Fq product is a
 // call (ffu.cuh: fqu_mul_call), so what is live across it sits in the callee-saved registers or in scratch: 4,272 B of scratch
@@ -33,6 +37,7 @@
 #include "pairing_dev.cuh"
 #include "pairing_each_dev.cuh"
 #include "prime_inputs_dev.cuh"
+#include "rerandomize_dev.cuh"
 #include "u64_inputs_dev.cuh"
 
 namespace zk {
@@ -281,6 +286,57 @@ __global__ __launch_bounds__(64) void u64_x_kernel(const Affine<FqU> *gamma_abc,
     }
 }
 
+// ---- re-randomising (rerandomize_dev.cuh).  st3 / mem3 (nullable, 3 bytes a proof: the decode statuses and membership verdicts of
+// the wire form): a proof with a status that is not zero or a verdict that is zero is left out; its outputs are zero
+ZK_HD bool rr_left_out(const uint8_t *st3, const uint8_t *mem3, size_t i) {
+    bool out = false;
+    if (st3) out = out || st3[3 * i] || st3[3 * i + 1] || st3[3 * i + 2];
+    if (mem3) out = out || !mem3[3 * i] || !mem3[3 * i + 1] || !mem3[3 * i + 2];
+    return out;
+}
+// proof i: A', C' -> out + 48 i (+ 0, + 36), their flags -> out_inf + 3 i (+ 0, + 2)
+__global__ __launch_bounds__(64) void rerandomize_g1_kernel(const uint64_t *proofs, const uint8_t *inf, const uint64_t *r1, const uint64_t *r2, const uint8_t *st3,
+                                                            const uint8_t *mem3, size_t n, uint64_t *out, uint8_t *out_inf) {
+    const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    if (rr_left_out(st3, mem3, i)) {
+        for (int t = 0; t < 12; t++) out[48 * i + t] = out[48 * i + 36 + t] = 0;
+        out_inf[3 * i] = out_inf[3 * i + 2] = 0;
+        return;
+    }
+    rr::proof_g1(proofs + 48 * i, inf + 3 * i, r1 + 4 * i, r2 + 4 * i, out + 48 * i, out_inf + 3 * i);
+}
+// proof i: B' -> out + 48 i + 12, its flag -> out_inf + 3 i + 1; delta: 24 u64 on the device
+__global__ __launch_bounds__(64) void rerandomize_g2_kernel(const uint64_t *proofs, const uint8_t *inf, const uint64_t *delta, const uint64_t *r1, const uint64_t *r2,
+                                                            const uint8_t *st3, const uint8_t *mem3, size_t n, uint64_t *out, uint8_t *out_inf) {
+    const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    if (rr_left_out(st3, mem3, i)) {
+        for (int t = 0; t < 24; t++) out[48 * i + 12 + t] = 0;
+        out_inf[3 * i + 1] = 0;
+        return;
+    }
+    rr::proof_g2(proofs + 48 * i, inf + 3 * i, *reinterpret_cast<const G2Affine *>(delta), r1 + 4 * i, r2 + 4 * i, out + 48 * i, out_inf + 3 * i);
+}
+// point i: pts + i * stride (u64 units), inf[i * inf_stride] (inf null: none at infinity) -> out + i * byte_stride (48 / 96 bytes);
+// with st3 / mem3, point i belongs to proof i and a proof left out gets zero bytes
+__global__ __launch_bounds__(64) void compress_kernel(int group, const uint64_t *pts, size_t stride, const uint8_t *inf, size_t inf_stride, size_t n,
+                                                      const uint8_t *st3, const uint8_t *mem3, uint8_t *out, size_t byte_stride) {
+    const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    uint8_t b[96];
+    const int nb = group == 1 ? 48 : 96;
+    if (rr_left_out(st3, mem3, i)) {
+        for (int t = 0; t < nb; t++) b[t] = 0;
+    } else {
+        const bool at_inf = inf && inf[i * inf_stride];
+        if (group == 1) rr::g1_compress(pts + i * stride, at_inf, b);
+        else rr::g2_compress(pts + i * stride, at_inf, b);
+    }
+    uint8_t *o = out + i * byte_stride;
+    for (int t = 0; t < nb; t++) o[t] = b[t];
+}
+
 unsigned blocks_of(size_t n) { return (unsigned)((n + 63) / 64); }
 
 }  // namespace
@@ -429,6 +485,33 @@ void vb_decompress_launch(hipStream_t st, int group, const uint8_t *bytes, size_
     hipLaunchKernelGGL(decompress_kernel, dim3(blocks_of(n)), dim3(64), 0, st, group, bytes, byte_stride, n, validate, en, out, stride, inf, inf_stride, status,
                        status_stride);
     ZK_HIP(hipGetLastError());
+}
+
+void vb_rerandomize_launch(hipStream_t st_g1, hipStream_t st_g2, const uint64_t *proofs, const uint8_t *inf, const uint64_t *delta, const uint64_t *r1,
+                           const uint64_t *r2, const uint8_t *st3, const uint8_t *mem3, size_t n, uint64_t *out, uint8_t *out_inf) {
+    if (!n) return;
+    // the long kernel first
+    hipLaunchKernelGGL(rerandomize_g2_kernel, dim3(blocks_of(n)), dim3(64), 0, st_g2, proofs, inf, delta, r1, r2, st3, mem3, n, out, out_inf);
+    ZK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(rerandomize_g1_kernel, dim3(blocks_of(n)), dim3(64), 0, st_g1, proofs, inf, r1, r2, st3, mem3, n, out, out_inf);
+    ZK_HIP(hipGetLastError());
+}
+
+void vb_compress_launch(hipStream_t st, int group, const uint64_t *pts, size_t stride, const uint8_t *inf, size_t inf_stride, size_t n, const uint8_t *st3,
+                        const uint8_t *mem3, uint8_t *out, size_t byte_stride) {
+    if (!n) return;
+    hipLaunchKernelGGL(compress_kernel, dim3(blocks_of(n)), dim3(64), 0, st, group, pts, stride, inf, inf_stride, n, st3, mem3, out, byte_stride);
+    ZK_HIP(hipGetLastError());
+}
+
+void vb_rerandomize_host_range(const uint64_t *proofs, const uint8_t *inf, const uint64_t *delta, const uint64_t *r1, const uint64_t *r2, size_t lo, size_t hi,
+                               uint64_t *out, uint8_t *out_inf) {
+    G2Affine d;
+    memcpy(&d, delta, sizeof d);
+    for (size_t i = lo; i < hi; i++) {
+        rr::proof_g1(proofs + 48 * i, inf ? inf + 3 * i : nullptr, r1 + 4 * i, r2 + 4 * i, out + 48 * i, out_inf + 3 * i);
+        rr::proof_g2(proofs + 48 * i, inf ? inf + 3 * i : nullptr, d, r1 + 4 * i, r2 + 4 * i, out + 48 * i, out_inf + 3 * i);
+    }
 }
 
 const uint64_t *vb_product_launch(hipStream_t st, const uint64_t *f, const uint8_t *live, size_t n, uint64_t *tmp) {

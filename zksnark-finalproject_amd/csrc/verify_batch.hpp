@@ -172,4 +172,19 @@ void vb_point_limbs(const void *xk, uint64_t out[12]);
 void vb_u64_x_launch(hipStream_t st, const uint32_t *gamma_abc_words, size_t num_instance, const uint64_t *values, const uint32_t *idx, size_t n, void *xk,
                      uint8_t *have);
 
+// ---- re-randomising (rerandomize_dev.cuh): A' = r1^-1 A, B' = r1 B + (r1 r2) delta, C' = C + r2 A
+// n proofs on the device (48 limbs and 3 flags each, the flags as vb_flags leaves them or as the decode kernel wrote them), r1 / r2
+// n x 4 Montgomery limbs, delta 24 limbs: the G2 kernel on st_g2 and the G1 kernel on st_g1 -> out (n x 48), out_inf (n x 3).
+// st3 / mem3 (nullable, n x 3 each): decode statuses and membership verdicts; a proof with a bad one is left out (zero outputs)
+void vb_rerandomize_launch(hipStream_t st_g1, hipStream_t st_g2, const uint64_t *proofs, const uint8_t *inf, const uint64_t *delta, const uint64_t *r1,
+                           const uint64_t *r2, const uint8_t *st3, const uint8_t *mem3, size_t n, uint64_t *out, uint8_t *out_inf);
+// n affine points of one group at pts + i * stride (u64 units), flags at inf + i * inf_stride (null: none at infinity) -> the
+// bytes of zkg16_points_compress at out + i * byte_stride.  st3 / mem3 (nullable): as above, point i belonging to proof i; a proof
+// left out gets zero bytes
+void vb_compress_launch(hipStream_t st, int group, const uint64_t *pts, size_t stride, const uint8_t *inf, size_t inf_stride, size_t n, const uint8_t *st3,
+                        const uint8_t *mem3, uint8_t *out, size_t byte_stride);
+// the proofs [lo, hi) on the calling host thread, by the kernels' own arithmetic (inf nullable: no flag set)
+void vb_rerandomize_host_range(const uint64_t *proofs, const uint8_t *inf, const uint64_t *delta, const uint64_t *r1, const uint64_t *r2, size_t lo, size_t hi,
+                               uint64_t *out, uint8_t *out_inf);
+
 }  // namespace zk

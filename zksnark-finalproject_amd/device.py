@@ -719,6 +719,56 @@ class Device:
             self._check(rc)
         return out, inf, status[:n].copy()
 
+    # ---- re-randomising
+    def rerandomize_batch(self, vk_or_delta, proofs, inf=None, r1=None, r2=None):
+        """rerandomize_batch_host with one GPU lane per (proof, group) (zkg16_rerandomize_batch): byte for byte the host form's
+        output.  Batches shorter than the option "rerandomize_min" are answered by the host form."""
+        proofs, inf, k = _rerandomize_limbs(proofs, inf)
+        delta, r1, r2 = _rerandomize_args(vk_or_delta, k, r1, r2)
+        out = np.zeros((k, 48), dtype=np.uint64)
+        oinf = np.zeros((k, 3), dtype=np.uint8)
+        self._check(self.lib.zkg16_rerandomize_batch(self.ctx, _ptr(delta), _ptr(proofs) if k else None, _ptr(inf), _ptr(r1) if k else None,
+                                                     _ptr(r2) if k else None, k, _ptr(out), _ptr(oinf)))
+        return out, oinf
+
+    def rerandomize_batch_wire(self, vk_or_delta, proof_bytes, r1=None, r2=None, status=True):
+        """K compressed proofs (k x 192 bytes: bytes or a uint8 array) re-randomised without leaving the device between decoding
+        and encoding (zkg16_rerandomize_batch_wire) -> (bytes [k, 192] uint8, statuses [k, 3]).  A proof with a point that does not
+        decode or is not in the subgroup has its status set (1 .. 5, as verify_batch_wire's) and 192 zero bytes; the others are
+        unaffected.  status=False: only the bytes, and such a proof raises."""
+        raw = np.ascontiguousarray(np.frombuffer(proof_bytes, dtype=np.uint8) if isinstance(proof_bytes, (bytes, bytearray, memoryview))
+                                   else np.asarray(proof_bytes, dtype=np.uint8)).reshape(-1)
+        if raw.size % 192:
+            raise ValueError("rerandomize_batch_wire: a compressed proof is 192 bytes")
+        k = raw.size // 192
+        delta, r1, r2 = _rerandomize_args(vk_or_delta, k, r1, r2)
+        out = np.zeros((k, 192), dtype=np.uint8)
+        st = np.zeros((k, 3), dtype=np.uint8) if status else None
+        self._check(self.lib.zkg16_rerandomize_batch_wire(self.ctx, _ptr(delta), _ptr(raw) if k else None, _ptr(r1) if k else None, _ptr(r2) if k else None, k,
+                                                          _ptr(out), _ptr(st)))
+        return (out, st) if status else out
+
+    def points_compress_batch(self, group, points, inf=None):
+        """wire.points_compress on the device (zkg16_points_compress_batch): [n, 12 | 24] Montgomery limbs, optional flags -> bytes."""
+        w, nb = (12, 48) if group == "g1" else (24, 96)
+        pts = _u64(points).reshape(-1, w)
+        n = pts.shape[0]
+        inf = None if inf is None else np.ascontiguousarray(inf, dtype=np.uint8).reshape(-1)
+        if inf is not None and inf.shape[0] != n:
+            raise ValueError("points_compress_batch: one infinity flag per point")
+        out = np.zeros(n * nb, dtype=np.uint8)
+        self._check(self.lib.zkg16_points_compress_batch(self.ctx, 1 if group == "g1" else 2, _ptr(pts) if n else None, _ptr(inf) if n else None, n,
+                                                         _ptr(out) if n else None))
+        return out.tobytes()
+
+    def rerandomize_timings(self):
+        """ms of the last rerandomize_batch / rerandomize_batch_wire: upload, decode + membership kernels (wire), the G1 kernel, the
+        G2 kernel (side by side), the compress kernel (wire), read-back, total wall, and whether the host form answered."""
+        names = ("upload_ms", "decode_ms", "g1_ms", "g2_ms", "compress_ms", "readback_ms", "total_ms", "host_form")
+        ms = (C.c_float * 8)()
+        n = self.lib.zkg16_rerandomize_timings(self.ctx, ms, 8)
+        return {names[i]: float(ms[i]) for i in range(n)}
+
     def verify_batch_timings(self, prime=False, u64=False):
         """ms of the last verify_batch / verify_batch_wire: membership, scaling + Miller, product tree, MSM, host equation, bisecting,
         total wall, whether the host form answered, the decode kernels (verify_batch_wire only), the per-proof pass that took over
@@ -1176,6 +1226,61 @@ def draw_rho(k):
             v = secrets.randbits(128)
         out[i, 0], out[i, 1] = v & ((1 << 64) - 1), v >> 64
     return out
+
+
+_FR_MOD = 0x73eda753299d7d483339d80809a1d80553bda402fffe5bfeffffffff00000001
+
+
+def draw_rerandomizers(k):
+    """k non-zero elements of Fr from the operating system's generator, a zero redrawn as ark-groth16's rerandomize_proof redraws it
+    -> [k, 4] u64 Montgomery limbs."""
+    import secrets
+    out = np.zeros((k, 4), dtype=np.uint64)
+    for i in range(k):
+        v = 0
+        while v == 0:
+            v = secrets.randbelow(_FR_MOD)
+        m = (v << 256) % _FR_MOD
+        out[i] = [(m >> (64 * t)) & ((1 << 64) - 1) for t in range(4)]
+    return out
+
+
+def _rerandomize_args(vk_or_delta, k, r1, r2):
+    """(delta_g2 [24], r1 [k, 4], r2 [k, 4]) of the three re-randomising entries; vk_or_delta: a key dict or the 24 limbs"""
+    delta = _u64(vk_or_delta["delta_g2"] if isinstance(vk_or_delta, dict) else vk_or_delta).reshape(-1)
+    if delta.shape[0] != 24:
+        raise ValueError("rerandomize: delta_g2 is 24 limbs")
+    r1 = draw_rerandomizers(k) if r1 is None else _u64(r1).reshape(-1, 4)
+    r2 = draw_rerandomizers(k) if r2 is None else _u64(r2).reshape(-1, 4)
+    if r1.shape[0] != k or r2.shape[0] != k:
+        raise ValueError("rerandomize: one r1 and one r2 per proof")
+    return delta, r1, r2
+
+
+def _rerandomize_limbs(proofs, inf):
+    proofs = _u64(proofs).reshape(-1, 48)
+    k = proofs.shape[0]
+    inf = None if inf is None else np.ascontiguousarray(inf, dtype=np.uint8).reshape(-1, 3)
+    if inf is not None and inf.shape[0] != k:
+        raise ValueError("rerandomize: three infinity flags per proof")
+    return proofs, inf, k
+
+
+def rerandomize_batch_host(vk_or_delta, proofs, inf=None, r1=None, r2=None, threads=0):
+    """K proofs of one key re-randomised on host threads (zkg16_rerandomize_batch_host; no GPU): A' = r1^-1 A, B' = r1 B + r1 r2 delta,
+    C' = C + r2 A.  proofs [k, 48], inf [k, 3] or None, r1 / r2 [k, 4] Montgomery and non-zero (None: drawn from `secrets`)
+    -> (proofs [k, 48], inf [k, 3]).  The new proofs verify for exactly the inputs the old ones verify for."""
+    proofs, inf, k = _rerandomize_limbs(proofs, inf)
+    delta, r1, r2 = _rerandomize_args(vk_or_delta, k, r1, r2)
+    out = np.zeros((k, 48), dtype=np.uint64)
+    oinf = np.zeros((k, 3), dtype=np.uint8)
+    lib = _lib.load()
+    rc = lib.zkg16_rerandomize_batch_host(_ptr(delta), _ptr(proofs) if k else None, _ptr(inf), _ptr(r1) if k else None, _ptr(r2) if k else None, k, threads,
+                                          _ptr(out), _ptr(oinf))
+    if rc != 0:
+        detail = lib.zkg16_last_error(None).decode()
+        raise Zkg16Error(rc, lib.zkg16_strerror(rc).decode() + (" — " + detail if detail else ""))
+    return out, oinf
 
 
 def _verify_batch_args(pvk, public_inputs, proofs, infs, rho, k=None):

@@ -10,6 +10,7 @@
     prove_prime / verify_prime  src/arkworks/backend/prime_snark.rs:49-146, 165-206
     prove_primes     K prime requests under one trapdoor on ONE template key, in batched device passes (no counterpart upstream)
     verify_primes    K such proofs checked together under the ONE extended key of their trapdoor (no counterpart upstream)
+    rerandomize_proofs  K proofs of one key re-randomised (ark-groth16 rerandomize_proof; no handler upstream calls it)
 Same steps, same response fields: the circuit's R1CS and assignment (built on the device for matrix and prime requests,
 synthesized inside the library and loaded unexported for Fibonacci; the host C++ mirror's arrays only where a test wants them),
 per-request Groth16 setup (on the device, zkg16_setup_resident), prove (zkg16_prove_resident), encode (wire.py): one sequence for
@@ -761,6 +762,43 @@ def verify_proofs(vk, public_inputs_list, proofs_b64, dev=None):
         for i, ok in zip(idx, each):
             valid[i] = bool(ok)
     return dict(valid=valid, verifying_time=time.perf_counter() - t1, decode_time=t1 - t0)
+
+
+def rerandomize_proofs(vk, proofs_b64, dev=None):
+    """K base64 compressed proofs of one key re-randomised (ark-groth16's rerandomize_proof, with r1, r2 of each proof drawn from
+    `secrets`): the results verify for exactly the inputs the originals verify for and cannot be linked to them.  vk: a key dict or
+    the base64 the prove mirrors return (its delta_g2 is all that is read).  With dev the proofs stay bytes from end to end
+    (Device.rerandomize_batch_wire); without, host decoding, device.rerandomize_batch_host and encoding.  -> a list of base64
+    proofs, "" for a proof that did not decode (wrong length, bad base64, a point off the curve or outside the subgroup); the other
+    entries are unaffected.  Anything else that goes wrong — the key included — is raised."""
+    vk = _decode_key(vk)
+    k = len(proofs_b64)
+    out = [""] * k
+    keep_bytes = dev is not None
+    idx, proofs = [], []
+    for i, pb in enumerate(proofs_b64):
+        try:
+            proof = base64.standard_b64decode(pb)
+            if len(proof) != 192:
+                continue
+            if not keep_bytes:
+                proof = wire.proof_deserialize_compressed(proof)
+        except (ValueError, IndexError, TypeError):          # binascii.Error is a ValueError
+            continue
+        idx.append(i)
+        proofs.append(proof)
+    if not idx:
+        return out
+    if keep_bytes:
+        new, st = dev.rerandomize_batch_wire(vk, b"".join(proofs))
+        for j, i in enumerate(idx):
+            if not st[j].any():
+                out[i] = base64.standard_b64encode(new[j].tobytes()).decode()
+    else:
+        new, inf = device.rerandomize_batch_host(vk, np.array([p for p, _ in proofs], dtype=np.uint64), np.array([f for _, f in proofs], dtype=np.uint8))
+        for j, i in enumerate(idx):
+            out[i] = wire.encode_proof(new[j], inf[j])
+    return out
 
 
 def verify_primes(ext_vk, requests, dev=None):
