@@ -46,7 +46,7 @@ typedef enum {
     ZKG16_ERR_NO_DEVICE = 5,        /* no gfx950 device visible: the product has NO CPU fallback */
     ZKG16_ERR_BAD_HANDLE = 6,
     ZKG16_ERR_UNSUPPORTED = 7,
-    ZKG16_ERR_UNSATISFIED = 8       /* option "check_satisfied": an assignment of the call does not satisfy its R1CS; nothing was written */
+    ZKG16_ERR_UNSATISFIED = 8       /* option "check_satisfied" or a zkg16_prove_trapdoor* call: an assignment of the call does not satisfy its R1CS; nothing was written */
 } zkg16_status;
 
 typedef struct zkg16_ctx zkg16_ctx;
@@ -793,6 +793,55 @@ ZKG16_API int zkg16_r1cs_check_batch(zkg16_ctx *ctx, uint64_t r1cs_handle, const
 ZKG16_API int zkg16_prime_check_batch(zkg16_ctx *ctx, uint64_t r1cs_template_handle, const uint64_t *xs, const uint64_t *js, size_t k,
                             uint64_t *n_bad /* k */, uint64_t *first_bad /* nullable, k */);
 ZKG16_API int zkg16_last_check(zkg16_ctx *ctx, uint64_t *n_bad, uint64_t *first_bad, size_t cap, size_t *k_out);
+
+/* ---- The trapdoor route: setup-and-prove requests answered without the proving key.
+ * THIS IS NOT A WAY TO PROVE UNDER SOMEONE ELSE'S KEY.  It is for callers that drew the trapdoor themselves — every handler of the
+ * reference does, proves once and drops the key — and who could therefore forge a proof of any statement anyway.  What it saves is
+ * building and consuming a proving key nobody else ever reads.  With u_k, v_k, w_k the QAP column values at tau and
+ * lg_k = (beta u_k + alpha v_k + w_k) / delta, a SATISFIED assignment z has
+ *   S_u = sum z_k u_k   S_v = sum z_k v_k   S_w = sum z_k w_k   S_l = sum_{k >= num_instance} z_k lg_k
+ *   a = alpha + S_u + r delta     b = beta + S_v + s delta     c = S_l + (S_u S_v - S_w) / delta + s a + r b - r s delta
+ *   A = a G1   B = b G2   C = c G1
+ * (h(tau) Z(tau) = S_u S_v - S_w because h Z = a b - c as polynomials).  These are the group elements the key route computes, and
+ * affine coordinates are unique: proof i is byte for byte
+ *   zkg16_prove_resident(zkg16_setup_resident(r1cs, trapdoor, g1_gen, g2_gen), r1cs, witness_handles[i], r + 4 i, s + 4 i)
+ * and alpha_g1, beta_g2, gamma_g2, delta_g2, gamma_abc_g1 are zkg16_setup_resident's.  A log of 0 is the point at infinity (limbs 0,
+ * flag 1), as zkg16_prove_resident writes one.
+ * The identity needs a satisfied z (arkworks' h is not the quotient otherwise), so satisfaction is ALWAYS checked (one sparse product
+ * and zkg16_r1cs_check's kernel over the k assignments): if any assignment fails the call returns ZKG16_ERR_UNSATISFIED, writes
+ * nothing, and zkg16_last_check names the requests — where the key route would emit a proof no verifier accepts.
+ * One trapdoor per call: the batch form is k assignments of one system under one key, the single form is the batch form with k = 1.
+ * Per call: the QAP evaluation once (zkg16_setup's first stage), per pass of at most 65,535 requests (option "trapdoor_pass") the
+ * check and one kernel for the four dot products, then the O(1) tail per request on the host and num_instance + 3 k + 7 fixed-base
+ * points (one G1 and one G2 pass).  Outputs are written only when every pass has succeeded.  The call takes one lane.
+ * timings_ms (nullable, 5): QAP evaluation, sparse product + check, dot kernel, fixed-base passes (device events), whole call (host).
+ * Checked before any device work, outputs untouched: null pointers or k == 0 (ZKG16_ERR_BAD_ARG), unknown handles
+ * (ZKG16_ERR_BAD_HANDLE), a prime template handle (ZKG16_ERR_UNSUPPORTED: no request's system, as in zkg16_r1cs_check), a witness
+ * whose length is not the system's num_variables, a zero trapdoor entry (zkg16_setup refuses those too) or a tau with tau^N = 1
+ * (ZKG16_ERR_BAD_ARG; zkg16_last_error says which entry).
+ * zkg16_prove_trapdoor_host: no ctx, no GPU, up to `threads` host threads (0 = 8) — the reference for every byte of the device
+ * forms.  Arrays as for zkg16_r1cs_check_host, z: k x num_variables x 4.  L_j(tau) = (Z(tau) / N) omega^j / (tau - omega^j) with a
+ * batch inversion, column sums by a plain loop, the check is zkg16_r1cs_check_host's, points by the host scalar multiplication.  Its
+ * refusals' text: zkg16_last_error(NULL). */
+ZKG16_API int zkg16_prove_trapdoor(zkg16_ctx *ctx, uint64_t r1cs_handle, uint64_t witness_handle, const uint64_t trapdoor[20],
+                         const uint64_t g1_gen[12], const uint64_t g2_gen[24], const uint64_t r[4], const uint64_t s[4],
+                         uint64_t proof_out[48], uint8_t inf_out[3],
+                         uint64_t alpha_g1[12], uint64_t beta_g2[24], uint64_t gamma_g2[24], uint64_t delta_g2[24],
+                         uint64_t *gamma_abc_g1 /* num_instance x 12 */, float *timings_ms /* nullable, 5 */);
+ZKG16_API int zkg16_prove_trapdoor_batch(zkg16_ctx *ctx, uint64_t r1cs_handle, const uint64_t *witness_handles, size_t k,
+                               const uint64_t trapdoor[20], const uint64_t g1_gen[12], const uint64_t g2_gen[24],
+                               const uint64_t *r /* k x 4 */, const uint64_t *s /* k x 4 */,
+                               uint64_t *proofs_out /* k x 48 */, uint8_t *inf_out /* k x 3 */,
+                               uint64_t alpha_g1[12], uint64_t beta_g2[24], uint64_t gamma_g2[24], uint64_t delta_g2[24],
+                               uint64_t *gamma_abc_g1 /* num_instance x 12 */, float *timings_ms /* nullable, 5 */);
+ZKG16_API int zkg16_prove_trapdoor_host(const uint64_t *const row_ptr[3], const uint32_t *const col[3], const uint64_t *const coeff[3],
+                              size_t num_instance, size_t num_constraints, size_t num_variables,
+                              const uint64_t *z /* k x num_variables x 4 */, size_t k,
+                              const uint64_t trapdoor[20], const uint64_t g1_gen[12], const uint64_t g2_gen[24],
+                              const uint64_t *r /* k x 4 */, const uint64_t *s /* k x 4 */, int threads,
+                              uint64_t *proofs_out /* k x 48 */, uint8_t *inf_out /* k x 3 */,
+                              uint64_t alpha_g1[12], uint64_t beta_g2[24], uint64_t gamma_g2[24], uint64_t delta_g2[24],
+                              uint64_t *gamma_abc_g1 /* num_instance x 12 */);
 /* native Poseidon sponge hash of n Fr elements (Montgomery) — the public inputs hash_a/b/c of the matrix handler */
 ZKG16_API int zkg16_poseidon_hash(const uint64_t *elems, size_t n, uint64_t out[4]);
 /* k hashes in one call.  elems: k vectors of n Fr each (Montgomery), back to back; out[4 i ..] is byte for byte
@@ -987,6 +1036,8 @@ ZKG16_API void zkg16_kernel_stats_reset(zkg16_ctx *ctx);
  *                    0.432 against 0.168: a device call costs 24 to 28 ms whatever K is (profiles/rerandomize_timing.txt)
  *   "rerandomize_pass" zkg16_rerandomize_batch[_wire]: proofs per kernel launch (0 = 65,536, else 1..65,536; tests lower it to run
  *                    several passes at small k)
+ *   "trapdoor_pass"  zkg16_prove_trapdoor_batch: requests per device pass (0 = 65,535, else 1..65,535; tests lower it to run several
+ *                    passes at small k)
  * Unknown names return ZKG16_ERR_UNSUPPORTED. */
 ZKG16_API int zkg16_set_option(zkg16_ctx *ctx, const char *name, int64_t value);
 

@@ -52,6 +52,10 @@ SIGNATURES = {
     "zkg16_r1cs_check_batch": (C.c_int, [ctxp, H, vp, sz, vp, vp]),
     "zkg16_prime_check_batch": (C.c_int, [ctxp, H, vp, vp, sz, vp, vp]),
     "zkg16_last_check": (C.c_int, [ctxp, vp, vp, sz, C.POINTER(sz)]),
+    "zkg16_prove_trapdoor": (C.c_int, [ctxp, H, H, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "zkg16_prove_trapdoor_batch": (C.c_int, [ctxp, H, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "zkg16_prove_trapdoor_host": (C.c_int, [C.POINTER(vp * 3), C.POINTER(vp * 3), C.POINTER(vp * 3), sz, sz, sz, vp, sz, vp, vp, vp, vp, vp, C.c_int,
+                                            vp, vp, vp, vp, vp, vp, vp]),
     "zkg16_group_create": (C.c_int, [vp, C.c_int, C.POINTER(vp)]),
     "zkg16_group_destroy": (None, [vp]),
     "zkg16_group_last_error": (C.c_char_p, [vp]),
@@ -185,6 +189,9 @@ SIGNATURES = {
 }
 
 _lib = None
+
+
+ZKG16_ERR_BAD_ARG, ZKG16_ERR_UNSATISFIED = 1, 8      # include/zkg16.h: zkg16_status, the two that callers in this package branch on
 
 
 class Zkg16Error(RuntimeError):

@@ -172,6 +172,15 @@ struct EventSet {
     EventSet &operator=(const EventSet &) = delete;
 };
 
+// Every launch helper targets ctx->stream: while this guard lives the ctx's second stream takes its place, on every way out
+struct StreamSwap {
+    zkg16_ctx *c;
+    explicit StreamSwap(zkg16_ctx *ctx) : c(ctx) { std::swap(c->stream, c->wm_stream); }
+    ~StreamSwap() { std::swap(c->stream, c->wm_stream); }
+    StreamSwap(const StreamSwap &) = delete;
+    StreamSwap &operator=(const StreamSwap &) = delete;
+};
+
 // ---- the prove pipeline (api_prove.hip), as far as the device groups need it
 struct GroupRank;      // group.hpp
 struct Partials {

@@ -374,6 +374,7 @@ struct zkg16_ctx {
         int verify_each_after = ZKG16_VERIFY_EACH_AFTER_DEFAULT;                 // zkg16_verify_batch[_wire] with ok_each: range tests before the per-proof pass takes over
         int rerandomize_min = ZKG16_RERANDOMIZE_MIN_DEFAULT;                     // zkg16_rerandomize_batch[_wire]: shorter batches are answered by the host form
         int rerandomize_pass = 0;                     // zkg16_rerandomize_batch[_wire]: proofs per launch (0 = 65,536; tests lower it to reach several passes at small k)
+        int trapdoor_pass = 0;                        // zkg16_prove_trapdoor_batch: requests per device pass (0 = 65,535; tests lower it to reach several passes at small k)
         int verify_each_after_set = 0;                // 1: the caller set "verify_each_after" (the u64 entries read an unset option as 1; the stored value cannot tell unset from 32)
     } opt;
     std::map<std::string, zk::KernelStat> kstats;
@@ -496,6 +497,13 @@ struct SetupOut {
     uint8_t *a_inf, *b_g1_inf, *b_g2_inf, *l_inf;
     uint64_t *alpha_g1, *beta_g1, *beta_g2, *delta_g1, *delta_g2, *gamma_g2;
 };
+// the QAP at tau (qap_eval_run): u, v, w [num_variables], lg = (beta u + alpha v + w) / (gamma for the instance columns, delta for the
+// others), L = the Lagrange values L_j(tau), j < N, and the host values Z(tau), 1 / delta, 1 / gamma
+struct QapEval {
+    DevBuf uvw[3], lg, L, scratch[8];
+    Fr zt, dinv, ginv;
+};
+void qap_eval_run(zkg16_ctx *ctx, const R1csDev &m, const Fr trap[5], QapEval &q);      // throws when tau^N = 1
 void setup_run(zkg16_ctx *ctx, const R1csDev &m, const Fr trap[5], const G1Affine &g1, const G2Affine &g2, const SetupOut &out, PkDev *resident = nullptr);
 void fr_powers_run(zkg16_ctx *ctx, Fr *out, const Fr &base, const Fr &scale, size_t n);
 // Bases side: window sums -> host; returns the MSM value (XYZZ) after the host Horner.

@@ -129,7 +129,10 @@ __global__ void __launch_bounds__(256) setup_lg_kernel(const Fr *u, const Fr *v,
     st_fr(lg + k, fp_mul(x, k < num_instance ? ginv : dinv));
 }
 
-void setup_run(zkg16_ctx *ctx, const R1csDev &m, const Fr trap[5], const G1Affine &g1, const G2Affine &g2, const SetupOut &out, PkDev *res) {
+// The QAP evaluated at tau, on ctx->stream (nothing is synchronised): L = ifft((tau^j)_j), the three column-sum passes into u, v, w
+// (heavy-column queue and the add_inputs rows included) and setup_lg_kernel.  Both the key route (setup_run) and the trapdoor route
+// (api_trapdoor.hip) start here.
+void qap_eval_run(zkg16_ctx *ctx, const R1csDev &m, const Fr trap[5], QapEval &q) {
     const Fr &tau = trap[0], &alpha = trap[1], &beta = trap[2], &gamma = trap[3], &delta = trap[4];
     const size_t N = (size_t)1 << m.log_n, nc = m.num_constraints, ni = m.num_instance, nv = m.num_variables;
     Fr zt = tau;
@@ -137,16 +140,23 @@ void setup_run(zkg16_ctx *ctx, const R1csDev &m, const Fr trap[5], const G1Affin
     zt = fp_sub(zt, Fr::one());                                  // Z(tau) = tau^N - 1
     if (zt.is_zero()) throw HipError{hipErrorInvalidValue, "setup: tau lies in the evaluation domain", __FILE__, __LINE__};
     const Fr dinv = fp_inv(delta), ginv = fp_inv(gamma);
+    q.zt = zt; q.dinv = dinv; q.ginv = ginv;
 
     // L = ifft((tau^j)_j)
-    DevBuf Lsrc(N * sizeof(Fr)), L(N * sizeof(Fr));
+    // (the scratch buffers live in q as well: releasing one synchronises the device, so they go when the caller is done with q)
+    DevBuf &Lsrc = q.scratch[0], &L = q.L;
+    Lsrc.alloc(N * sizeof(Fr));
+    L.alloc(N * sizeof(Fr));
     fr_powers_run(ctx, Lsrc.as<Fr>(), tau, Fr::one(), N);
     ntt_run(ctx, Lsrc.as<Fr>(), L.as<Fr>(), m.log_n, true, false);      // out of place: the transform ends in L
 
     // u, v, w: per-matrix column sums
-    DevBuf uvw[3];
+    DevBuf *uvw = q.uvw;
     const size_t queue_slots = col_queue_slots(std::max(m.nnz[0], std::max(m.nnz[1], m.nnz[2])));
-    DevBuf keys, sorted, rowid, coloff, sort_temp, heavy((1 + 3 * queue_slots) * sizeof(uint32_t)), partial(queue_slots * sizeof(Fr));
+    DevBuf &keys = q.scratch[1], &sorted = q.scratch[2], &rowid = q.scratch[3], &coloff = q.scratch[4], &sort_temp = q.scratch[5],
+           &heavy = q.scratch[6], &partial = q.scratch[7];
+    heavy.alloc((1 + 3 * queue_slots) * sizeof(uint32_t));
+    partial.alloc(queue_slots * sizeof(Fr));
     unsigned key_bits = 1;
     while (((size_t)1 << key_bits) <= nv) key_bits++;
     for (int k = 0; k < 3; k++) {
@@ -173,10 +183,20 @@ void setup_run(zkg16_ctx *ctx, const R1csDev &m, const Fr trap[5], const G1Affin
                            k == 0 ? 1 : 0, uvw[k].as<Fr>());
         ZK_HIP(hipGetLastError());
     }
-    DevBuf lg(nv * sizeof(Fr));
+    DevBuf &lg = q.lg;
+    lg.alloc(nv * sizeof(Fr));
     hipLaunchKernelGGL(setup_lg_kernel, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, ctx->stream, uvw[0].as<Fr>(), uvw[1].as<Fr>(),
                        uvw[2].as<Fr>(), alpha, beta, ginv, dinv, nv, ni, lg.as<Fr>());
     ZK_HIP(hipGetLastError());
+}
+
+void setup_run(zkg16_ctx *ctx, const R1csDev &m, const Fr trap[5], const G1Affine &g1, const G2Affine &g2, const SetupOut &out, PkDev *res) {
+    const Fr &tau = trap[0], &alpha = trap[1], &beta = trap[2], &gamma = trap[3], &delta = trap[4];
+    const size_t N = (size_t)1 << m.log_n, ni = m.num_instance, nv = m.num_variables;
+    QapEval q;
+    qap_eval_run(ctx, m, trap, q);
+    DevBuf *uvw = q.uvw, &lg = q.lg, &L = q.L;
+    const Fr &zt = q.zt, &dinv = q.dinv;
     // h_i = tau^i * Z(tau) / delta, i < N - 1   (reuses L's storage)
     fr_powers_run(ctx, L.as<Fr>(), tau, fp_mul(zt, dinv), N - 1);
 

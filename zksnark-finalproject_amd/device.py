@@ -531,6 +531,40 @@ class Device:
         self._check(self.lib.zkg16_prove_batch(self.ctx, pk_h, r1cs_h, hs, k, rs, ss, proofs, inf))
         return proofs, inf
 
+    # ---- the trapdoor route: setup-and-prove without the key (zkg16_prove_trapdoor*)
+    def prove_trapdoor(self, r1cs_h, wit_h, num_instance, trapdoor_mont, g1_gen, g2_gen, r, s):
+        """One setup-and-prove request answered from the trapdoor, no proving key built (zkg16_prove_trapdoor) -> (proof [48], inf [3],
+        vk dict shaped as setup_resident's).  Byte for byte prove_resident on setup_resident's key for the same arguments.  Only for
+        callers that drew the trapdoor themselves.  An unsatisfied assignment raises Zkg16Error with status 8 (last_check names it)."""
+        proofs, inf, vk = self.prove_trapdoor_batch(r1cs_h, [wit_h], num_instance, trapdoor_mont, g1_gen, g2_gen,
+                                                    _u64(r).reshape(1, 4), _u64(s).reshape(1, 4), _single=True)
+        return proofs[0], inf[0], vk
+
+    def prove_trapdoor_batch(self, r1cs_h, witness_handles, num_instance, trapdoor_mont, g1_gen, g2_gen, rs, ss, _single=False):
+        """k assignments of one system under the one key of the trapdoor (zkg16_prove_trapdoor_batch): rs / ss [k, 4] Montgomery ->
+        (proofs [k, 48], inf [k, 3], vk dict); proof i is prove_trapdoor's for (witness_handles[i], rs[i], ss[i]).  The call's five
+        times (ms: QAP evaluation, sparse product + check, dot kernel, fixed-base passes, whole call) are kept in last_trapdoor_ms."""
+        hs = np.ascontiguousarray(witness_handles, dtype=np.uint64).reshape(-1)
+        k = hs.shape[0]
+        rs, ss = _u64(rs).reshape(-1, 4), _u64(ss).reshape(-1, 4)
+        if rs.shape[0] != k or ss.shape[0] != k:
+            raise ValueError("prove_trapdoor_batch: one r and one s per witness handle")
+        proofs = np.zeros((k, 48), dtype=np.uint64)
+        inf = np.zeros((k, 3), dtype=np.uint8)
+        vk = dict(alpha_g1=np.zeros(12, np.uint64), beta_g2=np.zeros(24, np.uint64), gamma_g2=np.zeros(24, np.uint64),
+                  delta_g2=np.zeros(24, np.uint64), gamma_abc_g1=np.zeros((num_instance, 12), np.uint64))
+        ms = (C.c_float * 5)()
+        trap, g1, g2 = _u64(trapdoor_mont).reshape(-1), _u64(g1_gen), _u64(g2_gen)
+        tail = (_ptr(proofs), _ptr(inf), _ptr(vk["alpha_g1"]), _ptr(vk["beta_g2"]), _ptr(vk["gamma_g2"]), _ptr(vk["delta_g2"]),
+                _ptr(vk["gamma_abc_g1"]), C.addressof(ms))
+        if _single:
+            rc = self.lib.zkg16_prove_trapdoor(self.ctx, r1cs_h, int(hs[0]), _ptr(trap), _ptr(g1), _ptr(g2), _ptr(rs), _ptr(ss), *tail)
+        else:
+            rc = self.lib.zkg16_prove_trapdoor_batch(self.ctx, r1cs_h, _ptr(hs) if k else None, k, _ptr(trap), _ptr(g1), _ptr(g2), _ptr(rs), _ptr(ss), *tail)
+        self._check(rc)
+        self.last_trapdoor_ms = dict(zip(("qap_ms", "check_ms", "dot_ms", "points_ms", "call_ms"), (float(x) for x in ms)))
+        return proofs, inf, vk
+
     # ---- batched verification
     def verify_batch(self, pvk, public_inputs, proofs, infs, rho=None, each=False):
         """K proofs under one prepared key checked together, the per-proof work in kernels (zkg16_verify_batch): public_inputs
@@ -1150,6 +1184,36 @@ def _setup_resident(self, r1cs_h, num_instance, trapdoor_mont, g1_gen, g2_gen):
 
 
 Device.setup_resident = _setup_resident
+
+
+def prove_trapdoor_host(r1cs, z, trapdoor_mont, g1_gen, g2_gen, rs, ss, threads=0):
+    """The trapdoor route without a device (zkg16_prove_trapdoor_host): r1cs = the dict r1cs_load takes, z [k, num_variables, 4] (or
+    [num_variables, 4] for one request), rs / ss [k, 4] -> (proofs [k, 48], inf [k, 3], vk dict shaped as setup_resident's).  The
+    reference for every byte of Device.prove_trapdoor[_batch]."""
+    lib = _lib.load()
+    z = _u64(z)
+    z = z.reshape((1,) + z.shape) if z.ndim == 2 else z
+    k, nv = z.shape[0], z.shape[1]
+    rs, ss = _u64(rs).reshape(-1, 4), _u64(ss).reshape(-1, 4)
+    if rs.shape[0] != k or ss.shape[0] != k:
+        raise ValueError("prove_trapdoor_host: one r and one s per assignment")
+    ni = int(r1cs["num_inputs"])
+    keep, tabs = [], []
+    for i, dt in ((0, np.uint64), (1, np.uint32), (2, np.uint64)):
+        arrs = [np.ascontiguousarray(r1cs[m][i], dtype=dt) for m in "abc"]
+        keep += arrs
+        tabs.append((C.c_void_p * 3)(*[x.ctypes.data if x.size else None for x in arrs]))
+    if any(x.shape[0] != r1cs["num_constraints"] + 1 for x in keep[:3]):
+        raise ValueError("prove_trapdoor_host: every row pointer has num_constraints + 1 entries")
+    proofs = np.zeros((k, 48), dtype=np.uint64)
+    inf = np.zeros((k, 3), dtype=np.uint8)
+    vk = dict(alpha_g1=np.zeros(12, np.uint64), beta_g2=np.zeros(24, np.uint64), gamma_g2=np.zeros(24, np.uint64),
+              delta_g2=np.zeros(24, np.uint64), gamma_abc_g1=np.zeros((ni, 12), np.uint64))
+    trap, g1, g2 = _u64(trapdoor_mont).reshape(-1), _u64(g1_gen), _u64(g2_gen)
+    _check_host(lib.zkg16_prove_trapdoor_host(C.byref(tabs[0]), C.byref(tabs[1]), C.byref(tabs[2]), ni, r1cs["num_constraints"], nv, _ptr(z), k, _ptr(trap), _ptr(g1), _ptr(g2), _ptr(rs), _ptr(ss),
+                                              int(threads), _ptr(proofs), _ptr(inf), _ptr(vk["alpha_g1"]), _ptr(vk["beta_g2"]), _ptr(vk["gamma_g2"]),
+                                              _ptr(vk["delta_g2"]), _ptr(vk["gamma_abc_g1"])))
+    return proofs, inf, vk
 
 
 def pairing_check(g1_points, g2_points, g1_inf=None, g2_inf=None, plain_final_exp=False):

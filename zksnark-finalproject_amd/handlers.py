@@ -30,12 +30,10 @@ import time
 import numpy as np
 
 from . import _lib, device, wire
-from ._lib import Zkg16Error
+from ._lib import ZKG16_ERR_BAD_ARG, ZKG16_ERR_UNSATISFIED, Zkg16Error
 from .circuits import (fibonacci_circuit, fibonacci_circuit_handle, linear_circuit, linear_circuit_handle, linear_r1cs_dims, linear_solver_id, matrix_circuit, matrix_hash_batch_host, prime_circuit, prime_dims, prime_key_corrections,
                        prime_public_inputs, prime_search, prime_vk_extend)
 from .workloads import R_MOD, g1_generator, g2_generator
-
-ZKG16_ERR_BAD_ARG = 1      # include/zkg16.h
 
 
 def _fr_mont(x):
@@ -93,7 +91,16 @@ class _DeviceCircuit:
         self.public_inputs = public_inputs
 
 
-def _request(dev, rng, circ, r1cs, assignment, keep_key=False, overlap=False, check_on_device=False):
+ROUTES = ("key", "trapdoor")
+
+
+def _route(route):
+    if route not in ROUTES:
+        raise ValueError("route: 'key' or 'trapdoor'")
+    return route
+
+
+def _request(dev, rng, circ, r1cs, assignment, keep_key=False, overlap=False, check_on_device=False, route="key"):
     """One request of any handler: draw the key, obtain the R1CS and the assignment, set the key up, draw r and s, prove, release.
     circ gives the dimensions.  r1cs(own) -> R1CS handle and assignment(own) -> (witness handle, public inputs or None) say how
     this kind of circuit reaches the device; each passes a handle the request owns through own(free, handle) the moment it has it,
@@ -104,7 +111,14 @@ def _request(dev, rng, circ, r1cs, assignment, keep_key=False, overlap=False, ch
     on a thread beside the setup's kernels (zkg16_witness_matrix takes the ctx only for its ~1 ms of kernels): at 128x128 the 61 ms
     of chains disappear under the 0.2 s setup.
     check_on_device: before proving, Device.r1cs_check on the two handles the request holds -> "satisfied" (else None) and
-    "check_time", which is not part of proving_time; the proof is made either way."""
+    "check_time", which is not part of proving_time; the proof is made either way.
+    route: "key" (default) is the above.  "trapdoor" (ignored with keep_key): the request drew the trapdoor itself, so one
+    Device.prove_trapdoor call takes the place of setup_resident + prove_resident and no proving key is built — the same draws in the
+    same order (trapdoor, generators, then r, s), the same proof and vk bytes for a seed.  setup_time is then reported as 0.0 and
+    proving_time is the whole call (the QAP evaluation, the check and the points included); with check_on_device "satisfied" comes
+    from the call's own check and check_time is 0.0.  The call refuses an unsatisfied assignment (ZKG16_ERR_UNSATISFIED): the request
+    then falls back to the key route and its record is what it is today.  "route" in the result says which route answered."""
+    _route(route)
     trap, g1, g2 = _draw_key(rng)
     with contextlib.ExitStack() as stack:
         def own(free, h):
@@ -130,6 +144,30 @@ def _request(dev, rng, circ, r1cs, assignment, keep_key=False, overlap=False, ch
             stack.callback(finish)
         else:
             wh, pub = assignment(own)
+
+        def joined():
+            thread.join()
+            if "err" in early:
+                raise early["err"]
+            return early["out"]
+        answered, rs_drawn = "key", None
+        if route == "trapdoor" and not keep_key:
+            rs_drawn = r, s = _draw_rs(rng)
+            t0 = time.perf_counter()
+            if overlap:
+                wh, pub = joined()
+            try:
+                proof, inf, vk = dev.prove_trapdoor(rh, wh, circ.num_instance, trap, g1, g2, r, s)
+                answered = "trapdoor"
+            except Zkg16Error as e:
+                if e.status != ZKG16_ERR_UNSATISFIED:
+                    raise
+            proving_time = time.perf_counter() - t0
+        if answered == "trapdoor":
+            if pub is not None:
+                circ.public_inputs = pub
+            return dict(proof=proof, inf=inf, vk=vk, pk=None, setup_time=0.0, proving_time=proving_time, r=r, s=s,
+                        satisfied=True if check_on_device else None, check_time=0.0, route="trapdoor")
         t0 = time.perf_counter()
         if keep_key:        # tests want the key on the host as well
             pk, vk = dev.setup(rh, circ.num_instance, circ.num_vars, circ.domain, trap, g1, g2)
@@ -139,13 +177,10 @@ def _request(dev, rng, circ, r1cs, assignment, keep_key=False, overlap=False, ch
             ph, vk = dev.setup_resident(rh, circ.num_instance, trap, g1, g2)
             own(dev.pk_free, ph)
         setup_time = time.perf_counter() - t0
-        r, s = _draw_rs(rng)
+        r, s = rs_drawn or _draw_rs(rng)
         t0 = time.perf_counter()
         if overlap:
-            thread.join()
-            if "err" in early:
-                raise early["err"]
-            wh, pub = early["out"]
+            wh, pub = joined()
         satisfied, check_time = None, 0.0
         if check_on_device:
             tc = time.perf_counter()
@@ -156,7 +191,26 @@ def _request(dev, rng, circ, r1cs, assignment, keep_key=False, overlap=False, ch
     if pub is not None:
         circ.public_inputs = pub
     return dict(proof=proof, inf=inf, vk=vk, pk=pk, setup_time=setup_time, proving_time=proving_time, r=r, s=s, satisfied=satisfied,
-                check_time=check_time)
+                check_time=check_time, route="key")
+
+
+def _trapdoor_batch(dev, stack, rh, whs, num_instance, trap, g1, g2, rs, ss):
+    """The batch handlers' trapdoor route: the witness handles become the stack's to free, then one Device.prove_trapdoor_batch call
+    -> (proofs, inf, vk), or None when the call refused an unsatisfied assignment (the caller redoes the batch on the key route)."""
+    for wh in whs:
+        stack.callback(dev.witness_free, int(wh))
+    try:
+        return dev.prove_trapdoor_batch(rh, whs, num_instance, trap, g1, g2, rs, ss)
+    except Zkg16Error as e:
+        if e.status != ZKG16_ERR_UNSATISFIED:
+            raise
+        return None
+
+
+def _trapdoor_only_own_key(what, route, key):
+    if _route(route) == "trapdoor" and key is not None:
+        raise ValueError(what + ": route='trapdoor' draws its own key (key must be None)")
+    return route == "trapdoor"
 
 
 def _from_host(dev, circ):
@@ -201,14 +255,15 @@ def _with_verdict(record, out, check_on_device):
     return record
 
 
-def prove_matrix(dev, size, matrix_a, matrix_b, seed=0, keep_key=False, check_on_device=False):
+def prove_matrix(dev, size, matrix_a, matrix_b, seed=0, keep_key=False, check_on_device=False, route="key"):
     """-> the reference's ProveOutput fields (matrix_proof.rs:80-91).  check_on_device: "satisfied" is added, the verdict of
-    Device.r1cs_check on the request's handles (the reference's matrix handler does not check)."""
+    Device.r1cs_check on the request's handles (the reference's matrix handler does not check).  route: _request's ("trapdoor": no
+    proving key is built; setup_time 0.0, proving_time the whole call)."""
     a = np.asarray(matrix_a, dtype=np.uint64).reshape(size, size)
     b = np.asarray(matrix_b, dtype=np.uint64).reshape(size, size)
     if keep_key or size < 2:            # tests want the host copy of everything
         circ = matrix_circuit(a, b)
-        out = _request(dev, random.Random(seed), circ, *_from_host(dev, circ), keep_key=keep_key, check_on_device=check_on_device)
+        out = _request(dev, random.Random(seed), circ, *_from_host(dev, circ), keep_key=keep_key, check_on_device=check_on_device, route=route)
     else:                               # the request path: resident matrices, the assignment built on the device beside the setup
         shape = _matrix_shape(dev, size)
         circ = _DeviceCircuit(shape.num_instance, shape.num_witness, shape.num_constraints)      # hash_a, hash_b, hash_c come with the assignment
@@ -216,7 +271,7 @@ def prove_matrix(dev, size, matrix_a, matrix_b, seed=0, keep_key=False, check_on
         def assignment(own):
             wh, pub, _ = dev.witness_matrix(a, b)
             return own(dev.witness_free, wh), pub
-        out = _request(dev, random.Random(seed), circ, lambda own: shape.rh, assignment, overlap=True, check_on_device=check_on_device)
+        out = _request(dev, random.Random(seed), circ, lambda own: shape.rh, assignment, overlap=True, check_on_device=check_on_device, route=route)
     ha, hb, hc = circ.public_inputs
     return _with_verdict(dict(hash_a=wire.encode_hash(ha), hash_b=wire.encode_hash(hb), hash_c=wire.encode_hash(hc),
                 setup_time=out["setup_time"], proving_time=out["proving_time"],
@@ -227,14 +282,19 @@ def prove_matrix(dev, size, matrix_a, matrix_b, seed=0, keep_key=False, check_on
                 pvk=wire.encode_pvk(out["vk"]), vk=wire.encode_vk(out["vk"]), _detail=out, _circuit=circ), out, check_on_device)
 
 
-def prove_matrices(dev, size, pairs, seed=0, key=None, check_on_device=False):
+def prove_matrices(dev, size, pairs, seed=0, key=None, check_on_device=False, route="key"):
     """K requests of one size under ONE key, assignments and proofs in batched device passes (Device.prove_matrix_batch).  pairs: K
     (matrix_a, matrix_b).  The key is set up once on the device from `seed` (the draws of prove_matrix, then r, s per request, so
     request 0 is prove_matrix's proof for that seed), or passed in as key=(pk handle, vk dict), which stays the caller's.  The
     matrices come from the shape cache.  -> the shared vk / pvk and, per request, prove_matrix's hash_a / hash_b / hash_c / proof.
     check_on_device: the assignments are built as handles (Device.witness_matrix_batch), checked together (Device.r1cs_check_batch)
-    and proved with Device.prove_batch — the same proof bytes — and every request's record gets "satisfied"."""
+    and proved with Device.prove_batch — the same proof bytes — and every request's record gets "satisfied".
+    route: "trapdoor" (only with key=None): the key is drawn as above but never built — the assignments are made as handles
+    (Device.witness_matrix_batch) and one Device.prove_trapdoor_batch call gives the same proofs and vk; setup_time is 0.0 and
+    proving_time the whole pass.  If the call refuses an unsatisfied assignment the whole batch is redone on the key route.
+    _detail["route"] says which route answered."""
     k = len(pairs)
+    trapdoor = _trapdoor_only_own_key("prove_matrices", route, key)
     if k == 0:
         raise ValueError("prove_matrices: no requests")
     a = np.stack([np.asarray(p[0], dtype=np.uint64).reshape(size, size) for p in pairs])
@@ -242,19 +302,30 @@ def prove_matrices(dev, size, pairs, seed=0, key=None, check_on_device=False):
     shape = _matrix_shape(dev, size)
     rng = random.Random(seed)
     with contextlib.ExitStack() as stack:
-        setup_time = 0.0
+        setup_time, answered, got = 0.0, "key", None
         if key is None:
             trap, g1, g2 = _draw_key(rng)
-            t0 = time.perf_counter()
-            ph, vk = dev.setup_resident(shape.rh, shape.num_instance, trap, g1, g2)
-            stack.callback(dev.pk_free, ph)
-            setup_time = time.perf_counter() - t0
+            if trapdoor:
+                rs, ss = _draw_rs_batch(rng, k)
+                t0 = time.perf_counter()
+                whs, pubs, ms = dev.witness_matrix_batch(a, b)
+                got = _trapdoor_batch(dev, stack, shape.rh, whs, shape.num_instance, trap, g1, g2, rs, ss)
+            if got is None:
+                t0 = time.perf_counter()
+                ph, vk = dev.setup_resident(shape.rh, shape.num_instance, trap, g1, g2)
+                stack.callback(dev.pk_free, ph)
+                setup_time = time.perf_counter() - t0
         else:
             ph, vk = key
-        rs, ss = _draw_rs_batch(rng, k)
-        t0 = time.perf_counter()
+        if not trapdoor:
+            rs, ss = _draw_rs_batch(rng, k)
+        if got is None:
+            t0 = time.perf_counter()
         verdicts = None
-        if check_on_device:
+        if got is not None:
+            (proofs, inf, vk), answered = got, "trapdoor"
+            verdicts = [(0, None)] * k if check_on_device else None
+        elif check_on_device:
             whs, pubs, ms = dev.witness_matrix_batch(a, b)
             for wh in whs:
                 stack.callback(dev.witness_free, int(wh))
@@ -270,19 +341,19 @@ def prove_matrices(dev, size, pairs, seed=0, key=None, check_on_device=False):
             q["satisfied"] = n_bad == 0
     return dict(vk=wire.encode_vk(vk), pvk=wire.encode_pvk(vk), setup_time=setup_time, proving_time=proving_time,
                 num_constraints_circuit=shape.num_constraints, num_variables=shape.num_instance, requests=requests,
-                _detail=dict(proofs=proofs, inf=inf, public_inputs=pubs, vk=vk, rs=rs, ss=ss, ms=ms))
+                _detail=dict(proofs=proofs, inf=inf, public_inputs=pubs, vk=vk, rs=rs, ss=ss, ms=ms, route=answered))
 
 
-def prove_fibonacci(dev, a, b, num_of_rounds, seed=42, keep_key=False, check_on_device=False):
+def prove_fibonacci(dev, a, b, num_of_rounds, seed=42, keep_key=False, check_on_device=False, route="key"):
     """-> the reference's OutputDataFib-like fields (fibbonaci_handler.rs:84-90).  check_on_device: "satisfied" is added, the verdict
-    of Device.r1cs_check on the request's handles."""
+    of Device.r1cs_check on the request's handles.  route: _request's."""
     if keep_key:
         circ = fibonacci_circuit(a, b, num_of_rounds)
         sources = _from_host(dev, circ)
     else:
         circ = fibonacci_circuit_handle(a, b, num_of_rounds)
         sources = _from_handle(dev, circ)
-    out = _request(dev, random.Random(seed), circ, *sources, keep_key=keep_key, check_on_device=check_on_device)
+    out = _request(dev, random.Random(seed), circ, *sources, keep_key=keep_key, check_on_device=check_on_device, route=route)
     return _with_verdict(dict(proof=wire.encode_proof(out["proof"], out["inf"]), proving_time=out["proving_time"], setup_time=out["setup_time"],
                 num_constraints=circ.num_constraints, num_variables=circ.num_instance,
                 fib_number=[wire.encode_hash(x) for x in circ.public_inputs][-1], pvk=wire.encode_pvk(out["vk"]), vk=wire.encode_vk(out["vk"]),
@@ -304,15 +375,18 @@ def fibonacci_key(dev, num_of_rounds, rng):
     return dict(ph=ph, rh=rh, vk=vk, setup_time=setup_time)
 
 
-def prove_fibonaccis(dev, requests, num_of_rounds, seed=42, key=None, check_on_device=False):
+def prove_fibonaccis(dev, requests, num_of_rounds, seed=42, key=None, check_on_device=False, route="key"):
     """K requests of the Fibonacci handler of one round count, requests = [(a, b), ...], under ONE key, assignments and proofs in
     batched device passes (Device.prove_fibonacci_batch).  The key is set up once from `seed` with prove_fibonacci's draws (then r,
     s per request), so request 0 is prove_fibonacci's proof and key for that seed, byte for byte; or it is passed in as key=
     (fibonacci_key's dict), which stays the caller's.  The key's two encodings are made once.
     -> a list of prove_fibonacci's fields per request; proving_time is the batch's divided by K.
     check_on_device: the assignments are built as handles (Device.witness_fibonacci_batch), checked together
-    (Device.r1cs_check_batch) and proved with Device.prove_batch — the same proof bytes — and every record gets "satisfied"."""
+    (Device.r1cs_check_batch) and proved with Device.prove_batch — the same proof bytes — and every record gets "satisfied".
+    route: "trapdoor" (only with key=None): prove_matrices' — Device.witness_fibonacci_batch, then one Device.prove_trapdoor_batch
+    call; setup_time 0.0; a refused batch is redone on the key route; _detail["route"] says which route answered."""
     k = len(requests)
+    trapdoor = _trapdoor_only_own_key("prove_fibonaccis", route, key)
     if k == 0:
         raise ValueError("prove_fibonaccis: no requests")
     a = np.array([int(q[0]) for q in requests], dtype=np.uint64)
@@ -320,14 +394,34 @@ def prove_fibonaccis(dev, requests, num_of_rounds, seed=42, key=None, check_on_d
     rng = random.Random(seed)
     own = key is None
     with contextlib.ExitStack() as stack:
-        if own:
+        answered, got = "key", None
+        if trapdoor:
+            trap, g1, g2 = _draw_key(rng)
+            rh = dev.r1cs_fibonacci(num_of_rounds)
+            stack.callback(dev.r1cs_free, rh)
+            rs, ss = _draw_rs_batch(rng, k)
+            t0 = time.perf_counter()
+            whs, pubs, ms = dev.witness_fibonacci_batch(num_of_rounds, a, b)
+            got = _trapdoor_batch(dev, stack, rh, whs, 4, trap, g1, g2, rs, ss)
+            if got is None:
+                t0 = time.perf_counter()
+                ph, vk = dev.setup_resident(rh, 4, trap, g1, g2)
+                stack.callback(dev.pk_free, ph)
+                key = dict(ph=ph, rh=rh, vk=vk, setup_time=time.perf_counter() - t0)
+        elif own:
             key = fibonacci_key(dev, num_of_rounds, rng)
             stack.callback(dev.r1cs_free, key["rh"])
             stack.callback(dev.pk_free, key["ph"])
-        rs, ss = _draw_rs_batch(rng, k)
-        t0 = time.perf_counter()
+        if not trapdoor:
+            rs, ss = _draw_rs_batch(rng, k)
+        if got is None:
+            t0 = time.perf_counter()
         verdicts, check_time = None, 0.0
-        if check_on_device:
+        if got is not None:
+            (proofs, inf, vk), answered = got, "trapdoor"
+            key = dict(vk=vk, setup_time=0.0)
+            verdicts = [(0, None)] * k if check_on_device else None
+        elif check_on_device:
             whs, pubs, ms = dev.witness_fibonacci_batch(num_of_rounds, a, b)
             for wh in whs:
                 stack.callback(dev.witness_free, int(wh))
@@ -346,7 +440,7 @@ def prove_fibonaccis(dev, requests, num_of_rounds, seed=42, key=None, check_on_d
         rec = dict(proof=wire.encode_proof(proofs[i], inf[i]), proving_time=proving_time / k, setup_time=key["setup_time"] if own else 0.0,
                    num_constraints=circ.num_constraints, num_variables=circ.num_instance, fib_number=wire.encode_hash(pubs[i][2]),
                    pvk=pvk_b64, vk=vk_b64, _circuit=circ,
-                   _detail=dict(proof=proofs[i], inf=inf[i], vk=vk, r=rs[i], s=ss[i], public_inputs=pubs[i], ms=ms))
+                   _detail=dict(proof=proofs[i], inf=inf[i], vk=vk, r=rs[i], s=ss[i], public_inputs=pubs[i], ms=ms, route=answered))
         if verdicts is not None:
             rec["satisfied"] = verdicts[i][0] == 0
         out.append(rec)
@@ -388,7 +482,7 @@ def _linear_public_inputs(a, b):
     return np.stack([_fr_mont(int(v)) for v in np.concatenate([a, b[:, None]], axis=1).reshape(-1)])
 
 
-def prove_linear_equations(dev, a, b, seed=0, keep_key=False, check_on_device=False, solver="forward"):
+def prove_linear_equations(dev, a, b, seed=0, keep_key=False, check_on_device=False, solver="forward", route="key"):
     """Mirror of prove_linear_equations (backend/linear_equations.rs:43-106): solve the system with the handler's forward
     substitution, build LinearEquationCircuit, circuit-specific setup, prove, verify against a[0][*], b[0], a[1][*], b[1], ...
     The solver is only right for a lower-triangular a: for any other a the circuit is in general unsatisfied, the proof is made all the
@@ -402,7 +496,8 @@ def prove_linear_equations(dev, a, b, seed=0, keep_key=False, check_on_device=Fa
     check_on_device: "satisfied" is added, the verdict of Device.r1cs_check on the request's handles.
     solver: "forward" is the above; "elimination" solves a x = b by Gaussian elimination over Fr (circuits.linear_circuit's
     solver=), so "valid" (and "satisfied") is True for every a that is non-singular mod r, and a singular a raises Zkg16Error
-    (ZKG16_ERR_UNSUPPORTED) as a zero diagonal does.  Key, matrices and public inputs do not depend on the solver."""
+    (ZKG16_ERR_UNSUPPORTED) as a zero diagonal does.  Key, matrices and public inputs do not depend on the solver.
+    route: _request's; a system the solver leaves unsatisfied (a dense a under "forward") is answered by the key route."""
     a, b = _linear_request("prove_linear_equations", a, b)
     if keep_key:
         circ = linear_circuit(a, b, solver=solver)
@@ -410,7 +505,7 @@ def prove_linear_equations(dev, a, b, seed=0, keep_key=False, check_on_device=Fa
     else:
         circ = linear_circuit_handle(a, b, solver=solver)
         sources = _from_handle(dev, circ)
-    out = _request(dev, random.Random(seed), circ, *sources, keep_key=keep_key, check_on_device=check_on_device)
+    out = _request(dev, random.Random(seed), circ, *sources, keep_key=keep_key, check_on_device=check_on_device, route=route)
     t0 = time.perf_counter()
     valid = bool(device.verify(out["vk"], circ.public_inputs, out["proof"], out["inf"]))
     verifying_time = time.perf_counter() - t0
@@ -435,7 +530,7 @@ def linear_key(dev, n, rng):
     return dict(ph=ph, rh=rh, vk=vk, setup_time=setup_time)
 
 
-def prove_linear_equations_batch(dev, systems, seed=0, key=None, check_on_device=False, solver="forward"):
+def prove_linear_equations_batch(dev, systems, seed=0, key=None, check_on_device=False, solver="forward", route="key"):
     """K requests of the linear handler of one size, systems = [(a, b), ...], under ONE key, assignments and proofs in batched device
     passes (Device.prove_linear_batch).  The key is set up once from `seed` with prove_linear_equations' draws (then r, s per
     request), so request 0 is that handler's proof and key for that seed, byte for byte; or it is passed in as key= (linear_key's
@@ -444,8 +539,12 @@ def prove_linear_equations_batch(dev, systems, seed=0, key=None, check_on_device
     check_on_device: the assignments are built as handles (Device.witness_linear_batch), checked together
     (Device.r1cs_check_batch) and proved with Device.prove_batch — the same proof bytes — and every record gets "satisfied".
     solver: "forward", or "elimination" (the device passes run under option "linear_solver" = 1): every non-singular request's
-    record has valid True, and a singular request raises Zkg16Error (ZKG16_ERR_UNSUPPORTED) for the whole batch."""
+    record has valid True, and a singular request raises Zkg16Error (ZKG16_ERR_UNSUPPORTED) for the whole batch.
+    route: "trapdoor" (only with key=None): prove_matrices' — Device.witness_linear_batch, then one Device.prove_trapdoor_batch
+    call; setup_time 0.0; a batch holding a request its solver leaves unsatisfied is redone on the key route; _detail["route"] says
+    which route answered."""
     k = len(systems)
+    trapdoor = _trapdoor_only_own_key("prove_linear_equations_batch", route, key)
     how = {} if linear_solver_id(solver) == 0 else dict(solver=solver)        # "forward": the Device calls as they always were
     if k == 0:
         raise ValueError("prove_linear_equations_batch: no requests")
@@ -457,14 +556,34 @@ def prove_linear_equations_batch(dev, systems, seed=0, key=None, check_on_device
     rng = random.Random(seed)
     own = key is None
     with contextlib.ExitStack() as stack:
-        if own:
+        answered, got = "key", None
+        if trapdoor:
+            trap, g1, g2 = _draw_key(rng)
+            rh = dev.r1cs_linear(n)
+            stack.callback(dev.r1cs_free, rh)
+            rs, ss = _draw_rs_batch(rng, k)
+            t0 = time.perf_counter()
+            whs, xs, ms = dev.witness_linear_batch(a, b, **how)
+            got = _trapdoor_batch(dev, stack, rh, whs, 1 + n * (n + 1), trap, g1, g2, rs, ss)
+            if got is None:
+                t0 = time.perf_counter()
+                ph, vk = dev.setup_resident(rh, 1 + n * (n + 1), trap, g1, g2)
+                stack.callback(dev.pk_free, ph)
+                key = dict(ph=ph, rh=rh, vk=vk, setup_time=time.perf_counter() - t0)
+        elif own:
             key = linear_key(dev, n, rng)
             stack.callback(dev.r1cs_free, key["rh"])
             stack.callback(dev.pk_free, key["ph"])
-        rs, ss = _draw_rs_batch(rng, k)
-        t0 = time.perf_counter()
+        if not trapdoor:
+            rs, ss = _draw_rs_batch(rng, k)
+        if got is None:
+            t0 = time.perf_counter()
         verdicts, check_time = None, 0.0
-        if check_on_device:
+        if got is not None:
+            (proofs, inf, vk), answered = got, "trapdoor"
+            key = dict(vk=vk, setup_time=0.0)
+            verdicts = [(0, None)] * k if check_on_device else None
+        elif check_on_device:
             whs, xs, ms = dev.witness_linear_batch(a, b, **how)
             for wh in whs:
                 stack.callback(dev.witness_free, int(wh))
@@ -489,7 +608,7 @@ def prove_linear_equations_batch(dev, systems, seed=0, key=None, check_on_device
                    num_constraints=circ.num_constraints, num_variables=circ.num_instance, proving_time=proving_time / k,
                    verifying_time=verifying_time / k, valid=bool(each[i]), pvk=pvk_b64, vk=vk_b64, _circuit=circ,
                    _detail=dict(proof=proofs[i], inf=inf[i], vk=vk, r=rs[i], s=ss[i], public_inputs=pubs[i], x=xs[i], ms=ms,
-                                setup_time=key["setup_time"] if own else 0.0))
+                                setup_time=key["setup_time"] if own else 0.0, route=answered))
         if verdicts is not None:
             rec["satisfied"] = verdicts[i][0] == 0
         out.append(rec)
@@ -579,12 +698,13 @@ def _verify_linear_equations_u64(dev, vk, systems, proofs_b64):
     return dict(valid=valid, verifying_time=time.perf_counter() - t1, decode_time=t1 - t0)
 
 
-def prove_prime(dev, x, i, seed=7, keep_key=False, check_satisfied=False, check_on_device=False):
+def prove_prime(dev, x, i, seed=7, keep_key=False, check_satisfied=False, check_on_device=False, route="key"):
     """-> the reference's ProveOutput fields of the prime handler (prime_snark.rs:36-47): search j in 0..=i for the first
     hash(x + j) mod 2^20 that passes the Fermat test, build PrimeCircuit for it, circuit-specific setup, prove.
     "satisfied": None, or with check_satisfied the host synthesis' verdict (which leaves the device path for the host synthesis),
     or with check_on_device Device.r1cs_check's on the handles of whichever path the request took — what the reference's
-    assert!(cs.is_satisfied()) (prime_snark.rs:123-128) looks at.  The proof is returned either way."""
+    assert!(cs.is_satisfied()) (prime_snark.rs:123-128) looks at.  The proof is returned either way.  route: _request's; a
+    candidate whose circuit is not satisfied is answered by the key route."""
     found = prime_search(x, i)
     if not found["found"]:
         return dict(_PRIME_NOT_FOUND)
@@ -596,7 +716,7 @@ def prove_prime(dev, x, i, seed=7, keep_key=False, check_satisfied=False, check_
         circ = _DeviceCircuit(dims["num_instance"], dims["num_witness"], dims["num_constraints"], prime_public_inputs(x, j))
         circ.j = j
         sources = (lambda own: own(dev.r1cs_free, dev.r1cs_prime(x, j)), lambda own: (own(dev.witness_free, dev.witness_prime(x, j)), None))
-    out = _request(dev, random.Random(seed), circ, *sources, keep_key=keep_key, check_on_device=check_on_device)
+    out = _request(dev, random.Random(seed), circ, *sources, keep_key=keep_key, check_on_device=check_on_device, route=route)
     return dict(proof=wire.encode_proof(out["proof"], out["inf"]), j=found["j"], num_constraints=circ.num_constraints,
                 num_variables=circ.num_vars, setup_time=out["setup_time"], proving_time=out["proving_time"], found_prime=True,
                 prime_num=str(found["prime"]), pvk=wire.encode_pvk(out["vk"]), vk=wire.encode_vk(out["vk"]),
