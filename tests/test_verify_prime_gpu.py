@@ -216,11 +216,11 @@ def test_host_form_below_the_default_thresholds(dev, proved):
 
 def test_arguments_are_checked_before_any_work(dev, proved):
     import ctypes as C
-    from zksnark_finalproject_amd.device import _verify_prime_args
+    from zksnark_finalproject_amd.device import _verify_args
     pvk, proofs, inf = proved["pvk"], proved["proofs"], proved["inf"]
     xs, js = PV.u64s(x for x, _ in PROVED), PV.u64s(j for _, j in PROVED)
     rho = VB.draw_rho(random.Random(9), len(PROVED))
-    args, k = _verify_prime_args(pvk, xs, js, proofs, inf, rho)
+    args, k = _verify_args(pvk, "prime", (xs, js), proofs, inf, rho)
     ok, each = C.c_int(7), np.full(k, 9, dtype=np.uint8)
     call = lambda a: dev.lib.zkg16_verify_prime_batch(dev.ctx, *a, C.byref(ok), each.ctypes.data)
     by = _wire(proofs, inf)
@@ -295,3 +295,11 @@ def test_existing_entries_answer_as_before(dev, oracle):
     assert np.array_equal(dev.verify_each(b.pvk, b.pubs, b.proofs, b.infs), want)
     assert dev.verify_batch(base.pvk, base.pubs, base.proofs, base.infs, rho=rho) is True
     assert len(dev.verify_batch_timings()) == 11
+
+
+def test_verify_prime_batch_wire_refuses_a_payload_of_no_whole_proofs(dev):
+    """bytes or a uint8 array whose length is no multiple of 192: refused before the key or (x, j) are looked at"""
+    for raw in (bytes(191), np.zeros(193, dtype=np.uint8)):
+        with pytest.raises(ValueError) as e:
+            dev.verify_prime_batch_wire(None, None, None, raw)
+        assert str(e.value) == "verify_prime_batch_wire: a compressed proof is 192 bytes"

@@ -152,11 +152,11 @@ def test_verify_prime_batch_host(case):
 
 def test_verify_prime_batch_host_checks_arguments(sim, case):
     from zksnark_finalproject_amd import _lib
-    from zksnark_finalproject_amd.device import _verify_prime_args
+    from zksnark_finalproject_amd.device import _verify_args
     claims, b, xs, js, want = case
     lib = _lib.load()
     rho = VB.draw_rho(random.Random(4), K)
-    args, k = _verify_prime_args(b.pvk, xs, js, b.proofs, b.infs, rho)
+    args, k = _verify_args(b.pvk, "prime", (xs, js), b.proofs, b.infs, rho)
     ok, each = C.c_int(7), np.full(K, 9, dtype=np.uint8)
 
     def call(a):

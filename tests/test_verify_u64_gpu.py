@@ -213,10 +213,10 @@ def test_host_form_below_the_default_thresholds(dev, proved):
 
 
 def test_arguments_are_checked_before_any_work(dev, proved):
-    from zksnark_finalproject_amd.device import _verify_u64_args
+    from zksnark_finalproject_amd.device import _verify_args
     pvk, values, proofs, inf = proved["pvk"], proved["values"], proved["proofs"], proved["inf"]
     rho = VB.draw_rho(random.Random(9), K_LIN)
-    args, k = _verify_u64_args(pvk, values, proofs, inf, rho)
+    args, k = _verify_args(pvk, "u64", (values,), proofs, inf, rho)
     ok, each = C.c_int(7), np.full(k, 9, dtype=np.uint8)
     call = lambda a: dev.lib.zkg16_verify_batch_u64(dev.ctx, *a, C.byref(ok), each.ctypes.data)
     by = _wire(proofs, inf)
@@ -333,3 +333,11 @@ def test_existing_entries_answer_as_before(dev, oracle):
     assert dev.verify_batch(base.pvk, base.pubs, base.proofs, base.infs, rho=rho) is True
     assert dev.verify_batch_timings()["range_tests"] == 0
     assert len(dev.verify_batch_timings()) == 11 and len(dev.verify_batch_timings(prime=True)) == 13
+
+
+def test_verify_batch_u64_wire_refuses_a_payload_of_no_whole_proofs(dev):
+    """bytes or a uint8 array whose length is no multiple of 192: refused before the key or the values are looked at"""
+    for raw in (bytes(191), np.zeros(193, dtype=np.uint8)):
+        with pytest.raises(ValueError) as e:
+            dev.verify_batch_u64_wire(None, None, raw)
+        assert str(e.value) == "verify_batch_u64_wire: a compressed proof is 192 bytes"

@@ -101,11 +101,11 @@ def test_verify_batch_u64_host(sim):
 
 def test_verify_batch_u64_host_checks_arguments(sim):
     from zksnark_finalproject_amd import _lib
-    from zksnark_finalproject_amd.device import _verify_u64_args
+    from zksnark_finalproject_amd.device import _verify_args
     b = sim.batch
     lib = _lib.load()
     rho = VB.draw_rho(random.Random(4), K)
-    args, k = _verify_u64_args(b.pvk, sim.values, b.proofs, b.infs, rho)
+    args, k = _verify_args(b.pvk, "u64", (sim.values,), b.proofs, b.infs, rho)
     ok, each = C.c_int(7), np.full(K, 9, dtype=np.uint8)
 
     def call(a, threads=0):

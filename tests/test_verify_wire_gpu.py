@@ -300,3 +300,11 @@ def test_handler_verify_proofs_same_with_and_without_device(dev, oracle, batch10
     without = handlers.verify_proofs(b.pvk, pubs, enc, dev=None)
     want = [i not in (1, 3, 4, 6, 8) for i in range(k)]
     assert with_dev["valid"] == without["valid"] == want
+
+
+def test_verify_batch_wire_refuses_a_payload_of_no_whole_proofs(dev):
+    """bytes or a uint8 array whose length is no multiple of 192: refused before the key or the inputs are looked at"""
+    for raw in (bytes(191), np.zeros(193, dtype=np.uint8)):
+        with pytest.raises(ValueError) as e:
+            dev.verify_batch_wire(None, None, raw)
+        assert str(e.value) == "verify_batch_wire: a compressed proof is 192 bytes"

@@ -1,7 +1,8 @@
-// libzkg16 C ABI (include/zkg16.h), part 1 of 6: the ctx itself — kernel timer, streams, lanes, the device allocation cache,
+// libzkg16 C ABI (include/zkg16.h), part 1 of 8: the ctx itself — kernel timer, streams, lanes, the device allocation cache,
 // zkg16_init / zkg16_destroy, options and instrumentation.  The other parts: api_keys.hip (key / R1CS / witness residency),
 // api_prove.hip (the prove pipeline and its O(1) host tail), api_stages.hip (setup and the stage entry points), api_group.hip (device
-// groups), api_verify.hip (batched verification); api_internal.hpp is what they share.
+// groups), api_verify.hip (batched verification), api_rerandomize.hip (re-randomising), api_trapdoor.hip (setup-and-prove requests);
+// api_internal.hpp is what they share.
 //
 // There is NO CPU fallback: without a HIP device zkg16_init fails with ZKG16_ERR_NO_DEVICE.
 #include "api_internal.hpp"

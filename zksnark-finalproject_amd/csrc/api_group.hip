@@ -1,4 +1,4 @@
-// libzkg16 C ABI, part 5 of 6 (api.hip): device groups.
+// libzkg16 C ABI, part 5 of 8 (api.hip): device groups.
 #include "api_internal.hpp"
 #include "group.hpp"
 

@@ -1,11 +1,13 @@
 // What the files behind the C ABI (include/zkg16.h) share: api.hip (ctx, lanes, options, instrumentation), api_keys.hip (key /
 // R1CS / assignment residency), api_prove.hip (the prove pipeline and its host tail), api_stages.hip (setup and the stage entry
-// points), api_group.hip (device groups) and api_verify.hip (batched verification).  None of them holds a kernel.
+// points), api_group.hip (device groups), api_verify.hip (batched verification), api_rerandomize.hip (re-randomising) and
+// api_trapdoor.hip (setup-and-prove requests).  None of them holds a kernel.
 #pragma once
 #include <chrono>
 #include <exception>
 
 #include "common.hpp"
+#include "verify_batch.hpp"
 
 namespace zk {
 
@@ -180,6 +182,51 @@ struct StreamSwap {
     StreamSwap(const StreamSwap &) = delete;
     StreamSwap &operator=(const StreamSwap &) = delete;
 };
+
+// ---- batched verification and re-randomising on a lane (api_verify.hip defines what is declared here; api_rerandomize.hip)
+const size_t VB_PASS = 65536;          // pairs / points per launch: one wave per SIMD of a 256-CU device
+struct VbEvents {
+    hipEvent_t ev[14] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    VbEvents() { for (auto &e : ev) ZK_HIP(hipEventCreate(&e)); }
+    ~VbEvents() { for (auto &e : ev) if (e) (void)hipEventDestroy(e); }
+    VbEvents(const VbEvents &) = delete;
+    VbEvents &operator=(const VbEvents &) = delete;
+};
+inline float vb_elapsed(hipEvent_t a, hipEvent_t b) {
+    float ms = 0;
+    ZK_HIP(hipEventElapsedTime(&ms, a, b));
+    return ms;
+}
+// The flags the kernels read: zkg16_verify_prepared and the host form read all-zero limbs as the point at infinity whatever the flag
+// says, the kernels go by the flag alone (all-zero limbs are on no curve and would fail membership), so the flag is set for them
+std::vector<uint8_t> vb_flags(const uint64_t *proofs, const uint8_t *inf, size_t k);
+// The lane's main stream and the two beside it that the per-point kernels of A, B and C spread over
+struct VbStreams {
+    hipStream_t main, c, b;
+};
+inline VbStreams vb_streams(zkg16_ctx *ctx) { return VbStreams{ctx->stream, ctx->slots[1].stream, ctx->slots[2].stream}; }
+// fork: e is recorded on the main stream, and `also` (if any), c and b wait for it, in that order
+inline void vb_fork(const VbStreams &s, hipEvent_t e, hipStream_t also = nullptr) {
+    ZK_HIP(hipEventRecord(e, s.main));
+    if (also) ZK_HIP(hipStreamWaitEvent(also, e, 0));
+    for (hipStream_t st : {s.c, s.b}) ZK_HIP(hipStreamWaitEvent(st, e, 0));
+}
+// join: the main stream waits for what c and b hold now (e_c, e_b recorded there); e_also (if any) is recorded on `also` in between
+inline void vb_join(const VbStreams &s, hipEvent_t e_c, hipEvent_t e_b, hipEvent_t e_also = nullptr, hipStream_t also = nullptr) {
+    ZK_HIP(hipEventRecord(e_c, s.c));
+    ZK_HIP(hipEventRecord(e_b, s.b));
+    if (e_also) ZK_HIP(hipEventRecord(e_also, also));
+    ZK_HIP(hipStreamWaitEvent(s.main, e_c, 0));
+    ZK_HIP(hipStreamWaitEvent(s.main, e_b, 0));
+}
+// The three membership launches of one chunk of n proofs (48 limbs and 3 flags each; verdicts m3, 3 a proof): A on the main
+// stream, C and B beside it.
+void vb_membership_chunk(const VbStreams &s, const uint64_t *pts, const uint8_t *fl, size_t n, const VbEndo &en, uint8_t *m3);
+// The wire decode of k proofs (192 bytes each, on the device) in launches of `pass`, unvalidated: B (two powers and an inversion) on
+// the main stream, A and C (one power each) beside it, then the join (e_c, e_b).  The side streams already wait for the bytes.
+// Limbs (k x 48), flags and statuses (k x 3 each) land where the membership launches read them
+void vb_wire_decode(const VbStreams &s, hipEvent_t e_c, hipEvent_t e_b, const uint8_t *d_wire, size_t k, size_t pass, const VbEndo &en, uint64_t *d_proofs,
+                    uint8_t *d_inf, uint8_t *d_st);
 
 // ---- the prove pipeline (api_prove.hip), as far as the device groups need it
 struct GroupRank;      // group.hpp

@@ -1,4 +1,4 @@
-// libzkg16 C ABI, part 2 of 6 (api.hip): residency — proving keys and their shards (load, slice, shard plans, window tables), R1CS
+// libzkg16 C ABI, part 2 of 8 (api.hip): residency — proving keys and their shards (load, slice, shard plans, window tables), R1CS
 // matrices, synthesized circuits and assignments; the host -> device upload helpers the other parts share.
 #include "api_internal.hpp"
 

@@ -1,4 +1,4 @@
-// libzkg16 C ABI, part 3 of 6 (api.hip): the prove pipeline and its O(1) host tail.  Mirrors ark-groth16 0.4
+// libzkg16 C ABI, part 3 of 8 (api.hip): the prove pipeline and its O(1) host tail.  Mirrors ark-groth16 0.4
 // `create_proof_with_reduction_and_matrices` + `create_proof_with_assignment` (src/prover.rs) as the reference
 // reaches them from src/arkworks/backend/matrix_proof.rs:139-140.
 //

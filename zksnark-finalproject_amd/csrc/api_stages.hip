@@ -1,4 +1,4 @@
-// libzkg16 C ABI, part 4 of 6 (api.hip): key generation from a known trapdoor and the stage entry points (NTT, MSM, witness map,
+// libzkg16 C ABI, part 4 of 8 (api.hip): key generation from a known trapdoor and the stage entry points (NTT, MSM, witness map,
 // fixed-base batches) with their stand-alone benchmarks.
 #include "api_internal.hpp"
 #include "r1cs_check_dev.cuh"

@@ -1,4 +1,4 @@
-// libzkg16 C ABI (api.hip): the trapdoor route — setup-and-prove requests answered without the proving key.
+// libzkg16 C ABI, part 8 of 8 (api.hip): the trapdoor route — setup-and-prove requests answered without the proving key.
 // Every handler of the reference draws a trapdoor, runs circuit_specific_setup, proves once and drops the key
 // (matrix_proof.rs:129-140, prime_snark.rs:112-119, fibbonaci_handler.rs:107-110, linear_equations.rs).  Whoever holds the trapdoor
 // knows the discrete logs of every key point, so for a SATISFIED assignment z the proof's three logs are four dot products over the

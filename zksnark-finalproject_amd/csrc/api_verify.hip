@@ -1,10 +1,5 @@
-// libzkg16 C ABI, part 6 of 6 (api.hip): batched verification.
-#include <string>
-#include <system_error>
-#include <thread>
-
+// libzkg16 C ABI, part 6 of 8 (api.hip): batched verification.
 #include "api_internal.hpp"
-#include "verify_batch.hpp"
 
 using namespace zk;
 
@@ -14,46 +9,13 @@ using namespace zk;
 // which C_k enter the MSM), so the MSM of sum rho_k C_k runs on the lane's main stream while the Miller kernel is still busy.
 // From wire bytes (zkg16_verify_batch_wire) the three decompress launches of a pass fill the device proof array first, B on the main
 // stream beside A and C on two others; everything after reads that array as if the host had uploaded it.
-// The prime form (zkg16_verify_prime_batch[_wire]) has no public inputs on the host: (x, j) go up, the inputs kernel runs in front
-// of the membership kernels of the main stream, and the 260 multiplier sums are taken there once the member mask is known.
-// The u64 form (zkg16_verify_batch_u64[_wire]) sends its k x (num_instance - 1) 64-bit values up as they are: the sums kernels run
-// where the prime form's do, a second G1 MSM over the key's points turns the device sums into sum_i s_i gamma_abc[i], and the
-// per-proof pass makes X_k from the rows on the device (u64_x_kernel in the place of each_x_kernel).
-namespace {
-const size_t VB_PASS = 65536;          // pairs / points per launch: one wave per SIMD of a 256-CU device
-struct VbEvents {
-    hipEvent_t ev[14] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    VbEvents() { for (auto &e : ev) ZK_HIP(hipEventCreate(&e)); }
-    ~VbEvents() { for (auto &e : ev) if (e) (void)hipEventDestroy(e); }
-    VbEvents(const VbEvents &) = delete;
-    VbEvents &operator=(const VbEvents &) = delete;
-};
-float vb_elapsed(hipEvent_t a, hipEvent_t b) {
-    float ms = 0;
-    ZK_HIP(hipEventElapsedTime(&ms, a, b));
-    return ms;
-}
-void vb_publish(zkg16_ctx *root, const float tm[V_COUNT]) {
-    std::lock_guard<std::mutex> lk(root->lane_mu);
-    memcpy(root->vb_timings, tm, sizeof root->vb_timings);
-}
-// A batch below the entry point's threshold: form(tm) answers it on the host (vb_host, after decoding if need be); its wall time
-// since t_all and the host-form mark are published with whatever slots form filled in.
-template <class Form>
-int vb_answer_on_host(zkg16_ctx *ctx, double t_all, Form &&form) {
-    float tm[V_COUNT] = {0};
-    try {
-        form(tm);
-    } catch (const std::bad_alloc &) {
-        return ZKG16_ERR_OOM;
-    }
-    tm[V_TOTAL] = (float)(now_ms() - t_all);
-    tm[V_HOST_FORM] = 1;
-    vb_publish(ctx, tm);
-    return ZKG16_OK;
-}
-// The flags the kernels read: zkg16_verify_prepared and the host form read all-zero limbs as the point at infinity whatever the flag
-// says, the kernels go by the flag alone (all-zero limbs are on no curve and would fail membership), so the flag is set for them
+// Where the public inputs come from is a VbForm (verify_batch.hpp).  The prime form (zkg16_verify_prime_batch[_wire]) has none on
+// the host: (x, j) go up, the inputs kernel runs in front of the membership kernels of the main stream, and the 260 multiplier sums
+// are taken there once the member mask is known.  The u64 form (zkg16_verify_batch_u64[_wire]) sends its k x (num_instance - 1)
+// 64-bit values up as they are: the sums kernels run where the prime form's do, a second G1 MSM over the key's points turns the
+// device sums into sum_i s_i gamma_abc[i], and the per-proof pass makes X_k from the rows on the device (u64_x_kernel in the place
+// of each_x_kernel).
+namespace zk {
 std::vector<uint8_t> vb_flags(const uint64_t *proofs, const uint8_t *inf, size_t k) {
     std::vector<uint8_t> fl(3 * k);
     for (size_t i = 0; i < k; i++) {
@@ -67,29 +29,31 @@ std::vector<uint8_t> vb_flags(const uint64_t *proofs, const uint8_t *inf, size_t
     }
     return fl;
 }
-// The three membership launches of one chunk of n proofs (48 limbs and 3 flags each; verdicts m3, 3 a proof): A on the main
-// stream, C and B beside it.
-void vb_membership_chunk(hipStream_t s_main, hipStream_t s_c, hipStream_t s_b, const uint64_t *pts, const uint8_t *fl, size_t n, const VbEndo &en,
-                         uint8_t *m3) {
-    vb_membership_launch(s_main, 1, pts, 48, fl, 3, n, en, m3, 3);
-    vb_membership_launch(s_c, 1, pts + 36, 48, fl + 2, 3, n, en, m3 + 2, 3);
-    vb_membership_launch(s_b, 2, pts + 12, 48, fl + 1, 3, n, en, m3 + 1, 3);
+void vb_membership_chunk(const VbStreams &s, const uint64_t *pts, const uint8_t *fl, size_t n, const VbEndo &en, uint8_t *m3) {
+    vb_membership_launch(s.main, 1, pts, 48, fl, 3, n, en, m3, 3);
+    vb_membership_launch(s.c, 1, pts + 36, 48, fl + 2, 3, n, en, m3 + 2, 3);
+    vb_membership_launch(s.b, 2, pts + 12, 48, fl + 1, 3, n, en, m3 + 1, 3);
 }
+void vb_wire_decode(const VbStreams &s, hipEvent_t e_c, hipEvent_t e_b, const uint8_t *d_wire, size_t k, size_t pass, const VbEndo &en, uint64_t *d_proofs,
+                    uint8_t *d_inf, uint8_t *d_st) {
+    for (size_t off = 0; off < k; off += pass) {
+        const size_t n = std::min(pass, k - off);
+        const uint8_t *by = d_wire + 192 * off;
+        uint64_t *pts = d_proofs + 48 * off;
+        uint8_t *fl = d_inf + 3 * off, *st3 = d_st + 3 * off;
+        vb_decompress_launch(s.main, 2, by + 48, 192, n, 0, en, pts + 12, 48, fl + 1, 3, st3 + 1, 3);
+        vb_decompress_launch(s.c, 1, by, 192, n, 0, en, pts, 48, fl, 3, st3, 3);
+        vb_decompress_launch(s.b, 1, by + 144, 192, n, 0, en, pts + 36, 48, fl + 2, 3, st3 + 2, 3);
+    }
+    vb_join(s, e_c, e_b);
+}
+}  // namespace zk
 
-// The prime form (verify_batch.hpp): the batch's (x, j) on the host, and once vb_device has run the inputs kernel, the device
-// copies and digests the later stages read
-struct VbPrime {
-    const uint64_t *xs, *js;
-    const uint64_t *d_xs = nullptr, *d_js = nullptr;
-    const uint32_t *d_dig = nullptr;
-};
-
-// The u64 form (verify_batch.hpp): the batch's values on the host (k x (num_instance - 1), row-major), and once they are uploaded,
-// the device copy the sums kernels and the per-proof pass read
-struct VbU64 {
-    const uint64_t *values;
-    const uint64_t *d_values = nullptr;
-};
+namespace {
+void vb_publish(zkg16_ctx *root, const float tm[V_COUNT]) {
+    std::lock_guard<std::mutex> lk(root->lane_mu);
+    memcpy(root->vb_timings, tm, sizeof root->vb_timings);
+}
 // which gamma_abc points are the point at infinity: all-zero limbs (load_pt's rule)
 std::vector<uint8_t> vb_zero_points(const uint64_t *pts, size_t n) {
     std::vector<uint8_t> fl(n);
@@ -102,34 +66,32 @@ std::vector<uint8_t> vb_zero_points(const uint64_t *pts, size_t n) {
 }
 
 // The per-proof pass on the lane's main stream: the proofs idx[0 .. n) (null: 0 .. n - 1) of the k x 48 limbs / k x 3 flags already on
-// the device, each with its public inputs (pub(j): the (num_instance - 1) x 4 Montgomery limbs of the proof at position j), in
-// launches of VB_PASS.  The key is converted and uploaded once per call.  prime (nullable): the prime form — pub is not asked; the
-// inputs of the listed proofs are written on the device from its (x, j) and digests, so nothing travels per proof but its index.
-// u64 (nullable): the u64 form — pub is not asked either; X_k of every listed proof is made from its row of values on the device
+// the device, each with its public inputs, in launches of VB_PASS.  The key is converted and uploaded once per call.  By the form:
+// Limbs — the inputs of the listed proofs go up as canonical limbs.  Prime — they are written on the device from its (x, j) and
+// digests, so nothing travels per proof but its index.  U64 — X_k of every listed proof is made from its row of values on the device
 // (all the X launches first, between two events of their own: *x_ms, when asked), then the Miller and final-exponentiation launches.
 // Returns the kernels' time in ms (device events)
-float vb_each_pass(zkg16_ctx *ctx, const VbKey &key, const uint64_t *d_proofs, const uint8_t *d_inf, const uint32_t *idx, size_t n,
-                   const std::function<const uint64_t *(size_t)> &pub, uint8_t *verdict, const VbPrime *prime = nullptr, const VbU64 *u64 = nullptr,
-                   float *x_ms = nullptr) {
+float vb_each_pass(zkg16_ctx *ctx, const VbKey &key, const VbForm &form, const uint64_t *d_proofs, const uint8_t *d_inf, const uint32_t *idx, size_t n,
+                   uint8_t *verdict, float *x_ms = nullptr) {
     if (!n) return 0;
     hipStream_t st = ctx->stream;
+    const bool limbs = form.kind == VbKind::Limbs, prime = form.kind == VbKind::Prime, u64 = form.kind == VbKind::U64;
     const size_t ni = key.num_instance, per = 4 * (ni - 1), pass = std::min(n, VB_PASS);
     std::vector<uint32_t> words(vb_each_key_count(ni));
     vb_each_key_words(key, words.data());
-    const bool made_here = prime || u64;      // the inputs are made on the device
-    std::vector<uint64_t> z(made_here ? 1 : std::max<size_t>(n * per, 1));
-    for (size_t j = 0; j < n && per && !made_here; j++) vb_scalars_canonical(pub(j), ni - 1, z.data() + per * j);
+    std::vector<uint64_t> z(limbs ? std::max<size_t>(n * per, 1) : 1);
+    for (size_t j = 0; j < n && per && limbs; j++) vb_scalars_canonical(form.public_inputs + per * (idx ? idx[j] : j), ni - 1, z.data() + per * j);
     DevBuf d_key(words.size() * 4), d_z(prime ? n * per * 8 : u64 ? 0 : z.size() * 8), d_idx(idx ? n * 4 : 0), d_scratch(vb_each_scratch_bytes(pass)), d_verdict(n);
     DevBuf d_xk(u64 ? vb_each_x_bytes(n) : 0), d_have(u64 ? n : 0);
     VbEvents evs;
     ZK_HIP(hipMemcpyAsync(d_key.p, words.data(), words.size() * 4, hipMemcpyHostToDevice, st));
-    if (!made_here) ZK_HIP(hipMemcpyAsync(d_z.p, z.data(), z.size() * 8, hipMemcpyHostToDevice, st));
+    if (limbs) ZK_HIP(hipMemcpyAsync(d_z.p, z.data(), z.size() * 8, hipMemcpyHostToDevice, st));
     if (idx) ZK_HIP(hipMemcpyAsync(d_idx.p, idx, n * 4, hipMemcpyHostToDevice, st));
     ZK_HIP(hipEventRecord(evs.ev[0], st));
     if (u64) {
         const uint32_t *pts = d_key.as<uint32_t>() + vb_each_key_points_at();
         for (size_t off = 0; off < n; off += VB_PASS)
-            vb_u64_x_launch(st, pts, ni, idx ? u64->d_values : u64->d_values + (ni - 1) * off, idx ? d_idx.as<uint32_t>() + off : nullptr, std::min(VB_PASS, n - off),
+            vb_u64_x_launch(st, pts, ni, idx ? form.d_values : form.d_values + (ni - 1) * off, idx ? d_idx.as<uint32_t>() + off : nullptr, std::min(VB_PASS, n - off),
                             d_xk.as<uint8_t>() + vb_each_x_bytes(off), d_have.as<uint8_t>() + off);
         ZK_HIP(hipEventRecord(evs.ev[2], st));
         for (size_t off = 0; off < n; off += VB_PASS)
@@ -138,8 +100,8 @@ float vb_each_pass(zkg16_ctx *ctx, const VbKey &key, const uint64_t *d_proofs, c
                                 d_verdict.as<uint8_t>() + off);
     }
     for (size_t off = 0; off < n && prime; off += VB_PASS)
-        vb_prime_z_launch(st, idx ? d_idx.as<uint32_t>() + off : nullptr, std::min(VB_PASS, n - off), idx ? prime->d_xs : prime->d_xs + off,
-                          idx ? prime->d_js : prime->d_js + off, idx ? prime->d_dig : prime->d_dig + 8 * off, d_z.as<uint64_t>() + per * off);
+        vb_prime_z_launch(st, idx ? d_idx.as<uint32_t>() + off : nullptr, std::min(VB_PASS, n - off), idx ? form.d_xs : form.d_xs + off,
+                          idx ? form.d_js : form.d_js + off, idx ? form.d_dig : form.d_dig + 8 * off, d_z.as<uint64_t>() + per * off);
     for (size_t off = 0; off < n && !u64; off += VB_PASS)
         vb_each_launch(st, d_key.as<uint32_t>(), ni, idx ? d_idx.as<uint32_t>() + off : nullptr, std::min(VB_PASS, n - off), idx ? d_proofs : d_proofs + 48 * off,
                        idx ? d_inf : d_inf + 3 * off, d_z.as<uint64_t>() + per * off, d_scratch.p, d_verdict.as<uint8_t>() + off);
@@ -150,33 +112,33 @@ float vb_each_pass(zkg16_ctx *ctx, const VbKey &key, const uint64_t *d_proofs, c
     return vb_elapsed(evs.ev[0], evs.ev[1]);
 }
 
-// The device form of both entry points.  wire == null: b.proofs / b.inf are the caller's limbs and flags.  wire != null (k x 192
+// The device form of every batch entry point.  wire == null: b.proofs / b.inf are the caller's limbs and flags.  wire != null (k x 192
 // bytes): b.proofs / b.inf are null; the proofs are decoded on the device, unvalidated, and the decoded limbs and flags come back
 // once for the MSM's bases and vb_decide.  A proof with a point that did not decode is left out like one that fails membership;
 // decode_status (nullable, k x 3): the decode kernel's statuses, 5 where a decoded point failed membership.
-// prime (nullable): the prime form — b.public_inputs is null; the inputs kernel runs beside the membership kernels, the 260 sums of
-// the member proofs are taken on the device once the membership verdicts are back, and the host expands inputs (from the 32-byte
-// digests it then downloads) only when bisecting asks for them.
-// u64 (nullable): the u64 form — b.public_inputs is null as well; the values go up beside the proofs, the num_instance sums of the
-// member proofs are taken where the prime form's are, sum_i s_i gamma_abc[i] is a second MSM of the ctx on those device sums, and
-// the host expands values to Montgomery limbs only when bisecting asks for them.
-int vb_device(zkg16_ctx *ctx, const VbKey &key, VbBatch b, const uint8_t *wire, int *ok, uint8_t *ok_each, uint8_t *decode_status, double t_all,
-              VbPrime *prime = nullptr, VbU64 *u64 = nullptr) {
+// form: Limbs — b.public_inputs are the inputs.  Prime — b.public_inputs is null; the inputs kernel runs beside the membership
+// kernels, the 260 sums of the member proofs are taken on the device once the membership verdicts are back, and the host expands
+// inputs (from the 32-byte digests it then downloads) only when bisecting asks for them.  U64 — b.public_inputs is null as well;
+// the values go up beside the proofs, the num_instance sums of the member proofs are taken where the prime form's are,
+// sum_i s_i gamma_abc[i] is a second MSM of the ctx on those device sums, and the host expands values to Montgomery limbs only when
+// bisecting asks for them.  The form's device pointers are filled in here.
+int vb_device(zkg16_ctx *ctx, const VbKey &key, VbForm &form, VbBatch b, const uint8_t *wire, int *ok, uint8_t *ok_each, uint8_t *decode_status, double t_all) {
     const size_t k = b.k;
+    const bool prime = form.kind == VbKind::Prime, u64 = form.kind == VbKind::U64;
     float tm[V_COUNT] = {0};
     ZK_LANE_BEGIN(ctx)
-    hipStream_t s_main = ctx->stream, s_mil = ctx->wm_stream, s_c = ctx->slots[1].stream, s_b = ctx->slots[2].stream;
+    const VbStreams s = vb_streams(ctx);
+    hipStream_t s_main = s.main, s_mil = ctx->wm_stream;
     VbEvents evs;
     hipEvent_t e_up = evs.ev[0], e_a = evs.ev[1], e_c = evs.ev[2], e_b = evs.ev[3], e_mil = evs.ev[4], e_p0 = evs.ev[5], e_p1 = evs.ev[6], e_m0 = evs.ev[7],
                e_d0 = evs.ev[8], e_d1 = evs.ev[9], e_i0 = evs.ev[10], e_i1 = evs.ev[11], e_s0 = evs.ev[12], e_s1 = evs.ev[13];
     const size_t half = (k + 1) / 2;
     DevBuf d_proofs(k * 48 * 8), d_inf(3 * k), d_rho(k * 16), d_mem3(3 * k), d_live(k), d_f(k * 72 * 8), d_tmp(2 * half * 72 * 8);
     DevBuf d_wire(wire ? k * 192 : 0), d_st(wire ? 3 * k : 0);
-    const size_t sum_blocks = prime ? vb_prime_sums_blocks(k) : 0;
-    DevBuf d_xs(prime ? k * 8 : 0), d_js(prime ? k * 8 : 0), d_dig(prime ? k * 32 : 0), d_part(sum_blocks * 260 * 32), d_sums(prime ? 260 * 32 : 0);
-    const size_t ni = key.num_instance, um = ni - 1;
-    DevBuf d_values(u64 ? k * um * 8 : 0), d_upart(u64 ? vb_u64_sums_partial_words(k, um) * 8 : 0), d_usums(u64 ? ni * 32 : 0);
-    std::vector<uint64_t> sums(prime ? 260 * 4 : u64 ? ni * 4 : 0), expanded;
+    const size_t ni = key.num_instance, um = ni - 1;      // the prime form's key has 260 points: ni sums in both forms that take them
+    DevBuf d_xs(prime ? k * 8 : 0), d_js(prime ? k * 8 : 0), d_dig(prime ? k * 32 : 0), d_values(u64 ? k * um * 8 : 0);
+    DevBuf d_part(prime ? vb_prime_sums_blocks(k) * 260 * 32 : u64 ? vb_u64_sums_partial_words(k, um) * 8 : 0), d_sums(prime || u64 ? ni * 32 : 0);
+    std::vector<uint64_t> sums(prime || u64 ? ni * 4 : 0), expanded;
     std::vector<uint32_t> digests;
     const VbEndo en = vb_endo();
     std::vector<uint64_t> dec_proofs;
@@ -184,22 +146,8 @@ int vb_device(zkg16_ctx *ctx, const VbKey &key, VbBatch b, const uint8_t *wire, 
     if (wire) {
         upload_h2d(ctx, d_wire.p, wire, k * 192);
         ZK_HIP(hipMemcpyAsync(d_rho.p, b.rho, k * 16, hipMemcpyHostToDevice, s_main));
-        ZK_HIP(hipEventRecord(e_d0, s_main));
-        for (hipStream_t st : {s_c, s_b}) ZK_HIP(hipStreamWaitEvent(st, e_d0, 0));
-        for (size_t off = 0; off < k; off += VB_PASS) {
-            const size_t n = std::min(VB_PASS, k - off);
-            const uint8_t *by = d_wire.as<uint8_t>() + 192 * off;
-            uint64_t *pts = d_proofs.as<uint64_t>() + 48 * off;
-            uint8_t *fl = d_inf.as<uint8_t>() + 3 * off, *st3 = d_st.as<uint8_t>() + 3 * off;
-            // B (two powers and an inversion) on the main stream, A and C (one power each) beside it
-            vb_decompress_launch(s_main, 2, by + 48, 192, n, 0, en, pts + 12, 48, fl + 1, 3, st3 + 1, 3);
-            vb_decompress_launch(s_c, 1, by, 192, n, 0, en, pts, 48, fl, 3, st3, 3);
-            vb_decompress_launch(s_b, 1, by + 144, 192, n, 0, en, pts + 36, 48, fl + 2, 3, st3 + 2, 3);
-        }
-        ZK_HIP(hipEventRecord(e_c, s_c));
-        ZK_HIP(hipEventRecord(e_b, s_b));
-        ZK_HIP(hipStreamWaitEvent(s_main, e_c, 0));
-        ZK_HIP(hipStreamWaitEvent(s_main, e_b, 0));
+        vb_fork(s, e_d0);
+        vb_wire_decode(s, e_c, e_b, d_wire.as<uint8_t>(), k, VB_PASS, en, d_proofs.as<uint64_t>(), d_inf.as<uint8_t>(), d_st.as<uint8_t>());
         ZK_HIP(hipEventRecord(e_d1, s_main));
         // the decoded proofs travel to the host behind the kernels below; they are first read after the membership verdicts
         dec_proofs.resize(48 * k);
@@ -216,24 +164,23 @@ int vb_device(zkg16_ctx *ctx, const VbKey &key, VbBatch b, const uint8_t *wire, 
         ZK_HIP(hipMemcpyAsync(d_rho.p, b.rho, k * 16, hipMemcpyHostToDevice, s_main));
     }
     if (u64) {
-        upload_h2d(ctx, d_values.p, u64->values, k * um * 8);
-        u64->d_values = d_values.as<uint64_t>();
+        upload_h2d(ctx, d_values.p, form.values, k * um * 8);
+        form.d_values = d_values.as<uint64_t>();
     }
-    ZK_HIP(hipEventRecord(e_up, s_main));
-    for (hipStream_t st : {s_mil, s_c, s_b}) ZK_HIP(hipStreamWaitEvent(st, e_up, 0));
+    vb_fork(s, e_up, s_mil);
     ZK_HIP(hipEventRecord(e_m0, s_mil));
     if (prime) {
         // 16 bytes per proof up, one SHA-256 block per lane: in front of the membership kernels of the main stream
-        ZK_HIP(hipMemcpyAsync(d_xs.p, prime->xs, k * 8, hipMemcpyHostToDevice, s_main));
-        ZK_HIP(hipMemcpyAsync(d_js.p, prime->js, k * 8, hipMemcpyHostToDevice, s_main));
+        ZK_HIP(hipMemcpyAsync(d_xs.p, form.xs, k * 8, hipMemcpyHostToDevice, s_main));
+        ZK_HIP(hipMemcpyAsync(d_js.p, form.js, k * 8, hipMemcpyHostToDevice, s_main));
         ZK_HIP(hipEventRecord(e_i0, s_main));
         for (size_t off = 0; off < k; off += VB_PASS)
             vb_prime_inputs_launch(s_main, d_xs.as<uint64_t>() + off, d_js.as<uint64_t>() + off, std::min(VB_PASS, k - off), d_dig.as<uint32_t>() + 8 * off, nullptr,
                                    nullptr);
         ZK_HIP(hipEventRecord(e_i1, s_main));
-        prime->d_xs = d_xs.as<uint64_t>();
-        prime->d_js = d_js.as<uint64_t>();
-        prime->d_dig = d_dig.as<uint32_t>();
+        form.d_xs = d_xs.as<uint64_t>();
+        form.d_js = d_js.as<uint64_t>();
+        form.d_dig = d_dig.as<uint32_t>();
     }
     for (size_t off = 0; off < k; off += VB_PASS) {
         const size_t n = std::min(VB_PASS, k - off);
@@ -241,16 +188,12 @@ int vb_device(zkg16_ctx *ctx, const VbKey &key, VbBatch b, const uint8_t *wire, 
         const uint8_t *fl = d_inf.as<uint8_t>() + 3 * off;
         uint8_t *m3 = d_mem3.as<uint8_t>() + 3 * off;
         // membership first: where two of these streams share a hardware queue, the short kernels must not sit behind the long one
-        vb_membership_chunk(s_main, s_c, s_b, pts, fl, n, en, m3);
+        vb_membership_chunk(s, pts, fl, n, en, m3);
         vb_miller_launch(s_mil, pts, 48, fl, pts + 12, 48, fl + 1, 3, d_rho.as<uint64_t>() + 2 * off, n, d_f.as<uint64_t>() + 72 * off);
     }
     const double t_launched = now_ms();
     ZK_HIP(hipEventRecord(e_a, s_main));
-    ZK_HIP(hipEventRecord(e_c, s_c));
-    ZK_HIP(hipEventRecord(e_b, s_b));
-    ZK_HIP(hipEventRecord(e_mil, s_mil));
-    ZK_HIP(hipStreamWaitEvent(s_main, e_c, 0));
-    ZK_HIP(hipStreamWaitEvent(s_main, e_b, 0));
+    vb_join(s, e_c, e_b, e_mil, s_mil);
     std::vector<uint8_t> mem3(3 * k), member(k);
     ZK_HIP(hipMemcpyAsync(mem3.data(), d_mem3.p, 3 * k, hipMemcpyDeviceToHost, s_main));
     if (wire) {
@@ -298,32 +241,28 @@ int vb_device(zkg16_ctx *ctx, const VbKey &key, VbBatch b, const uint8_t *wire, 
     }
     // the product of the member proofs' Miller values
     ZK_HIP(hipMemcpyAsync(d_live.p, member.data(), k, hipMemcpyHostToDevice, s_main));
-    if (prime) {
-        // s_i = sum rho_k z_{k,i} over the member proofs, while the Miller kernel is still busy
-        ZK_HIP(hipEventRecord(e_s0, s_main));
-        vb_prime_sums_launch(s_main, prime->d_xs, prime->d_js, prime->d_dig, d_rho.as<uint64_t>(), d_live.as<uint8_t>(), k, d_part.as<uint64_t>(),
-                             d_sums.as<uint64_t>());
-        ZK_HIP(hipEventRecord(e_s1, s_main));
-        ZK_HIP(hipMemcpyAsync(sums.data(), d_sums.p, 260 * 32, hipMemcpyDeviceToHost, s_main));
-    }
     uint64_t sum_x[12] = {0};
     uint8_t sum_x_inf = 1;
-    if (u64) {
+    if (prime || u64) {
+        // s_i = sum rho_k z_{k,i} over the member proofs, while the Miller kernel is still busy
         ZK_HIP(hipEventRecord(e_s0, s_main));
-        vb_u64_sums_launch(s_main, u64->d_values, um, d_rho.as<uint64_t>(), d_live.as<uint8_t>(), k, d_upart.as<uint64_t>(), d_usums.as<uint64_t>());
+        if (prime)
+            vb_prime_sums_launch(s_main, form.d_xs, form.d_js, form.d_dig, d_rho.as<uint64_t>(), d_live.as<uint8_t>(), k, d_part.as<uint64_t>(), d_sums.as<uint64_t>());
+        else
+            vb_u64_sums_launch(s_main, form.d_values, um, d_rho.as<uint64_t>(), d_live.as<uint8_t>(), k, d_part.as<uint64_t>(), d_sums.as<uint64_t>());
         ZK_HIP(hipEventRecord(e_s1, s_main));
-        ZK_HIP(hipMemcpyAsync(sums.data(), d_usums.p, ni * 32, hipMemcpyDeviceToHost, s_main));
-        if (n_live) {
-            // sum_i s_i gamma_abc[i]: the sums stay where they are — below 2^224 < r, they are canonical scalars as they lie
-            const std::vector<uint8_t> ginf = vb_zero_points(key.gamma_abc_g1, ni);
-            DevBuf d_gbases(ni * sizeof(G1AffineU));
-            upload_points<G1Affine>(ctx, d_gbases.as<G1AffineU>(), key.gamma_abc_g1, ginf.data(), 0, ni);
-            ZK_HIP(hipStreamSynchronize(s_main));
-            MsmPlan plan;
-            msm_plan_build(ctx, ctx->ws_h, d_usums.as<Fr>(), ni, plan);
-            const G1XYZZ total = msm_g1_exec(ctx, ctx->ws_h, plan, d_gbases.as<G1AffineU>(), "verify_batch_u64_msm");
-            point_to_abi(xyzz_to_affine(total), sum_x, &sum_x_inf);
-        }
+        ZK_HIP(hipMemcpyAsync(sums.data(), d_sums.p, ni * 32, hipMemcpyDeviceToHost, s_main));
+    }
+    if (u64 && n_live) {
+        // sum_i s_i gamma_abc[i]: the sums stay where they are — below 2^224 < r, they are canonical scalars as they lie
+        const std::vector<uint8_t> ginf = vb_zero_points(key.gamma_abc_g1, ni);
+        DevBuf d_gbases(ni * sizeof(G1AffineU));
+        upload_points<G1Affine>(ctx, d_gbases.as<G1AffineU>(), key.gamma_abc_g1, ginf.data(), 0, ni);
+        ZK_HIP(hipStreamSynchronize(s_main));
+        MsmPlan plan;
+        msm_plan_build(ctx, ctx->ws_h, d_sums.as<Fr>(), ni, plan);
+        const G1XYZZ total = msm_g1_exec(ctx, ctx->ws_h, plan, d_gbases.as<G1AffineU>(), "verify_batch_u64_msm");
+        point_to_abi(xyzz_to_affine(total), sum_x, &sum_x_inf);
     }
     ZK_HIP(hipStreamWaitEvent(s_main, e_mil, 0));
     ZK_HIP(hipEventRecord(e_p0, s_main));
@@ -351,29 +290,21 @@ int vb_device(zkg16_ctx *ctx, const VbKey &key, VbBatch b, const uint8_t *wire, 
         if (!ctx->opt.verify_each_after_set) each.after = 1;
     }
     each.decide = [&](const uint32_t *idx, size_t n, uint8_t *verdict) {
-        const size_t per = 4 * (key.num_instance - 1);
-        tm[V_EACH] += vb_each_pass(ctx, key, d_proofs.as<uint64_t>(), d_inf.as<uint8_t>(), idx, n, [&](size_t j) { return b.public_inputs + per * idx[j]; }, verdict,
-                                   prime, u64, tm + V_U64_X);
+        tm[V_EACH] += vb_each_pass(ctx, key, form, d_proofs.as<uint64_t>(), d_inf.as<uint8_t>(), idx, n, verdict, tm + V_U64_X);
     };
     VbInputs inputs;
-    if (prime) {
+    if (prime || u64) {
         inputs.sums = sums.data();
+        if (u64) {
+            inputs.sum_x = sum_x;
+            inputs.sum_x_inf = &sum_x_inf;
+        }
         inputs.expand = [&]() -> const uint64_t * {
-            digests.resize(8 * k);
-            ZK_HIP(hipMemcpy(digests.data(), d_dig.p, k * 32, hipMemcpyDeviceToHost));
-            expanded.resize(4 * 259 * k);
-            vb_prime_expand(prime->xs, prime->js, digests.data(), k, expanded.data());
-            return expanded.data();
-        };
-    }
-    if (u64) {
-        inputs.sums = sums.data();
-        inputs.sum_x = sum_x;
-        inputs.sum_x_inf = &sum_x_inf;
-        inputs.expand = [&]() -> const uint64_t * {
-            expanded.resize(4 * um * k);
-            vb_u64_expand(u64->values, um * k, expanded.data());
-            return expanded.data();
+            if (prime) {
+                digests.resize(8 * k);
+                ZK_HIP(hipMemcpy(digests.data(), d_dig.p, k * 32, hipMemcpyDeviceToHost));
+            }
+            return vb_form_expand(key, form, k, prime ? digests.data() : nullptr, expanded);
         };
     }
     vb_decide(key, b, member.data(), [&]() -> const uint64_t * {
@@ -390,6 +321,82 @@ int vb_device(zkg16_ctx *ctx, const VbKey &key, VbBatch b, const uint8_t *wire, 
     vb_publish(root, tm);
     ZK_LANE_END(ctx)
 }
+
+// Every batch entry point: the checks, the host form below the entry's threshold, vb_device above it.  from_wire: proof_bytes
+// (k x 192) are the proofs, and proofs / inf are null; else proofs / inf are the limbs and flags, and proof_bytes / decode_status null
+int vb_entry(zkg16_ctx *ctx, const VbKey &key, VbForm form, const uint64_t *proofs, const uint8_t *inf, bool from_wire, const uint8_t *proof_bytes,
+             const uint64_t *rho, size_t k, int *ok, uint8_t *ok_each, uint8_t *decode_status) {
+    if (!ctx || !ok || (from_wire ? !proof_bytes : !proofs || !inf)) return ZKG16_ERR_BAD_ARG;
+    int rc = vb_check_batch(key, form, k);
+    if (rc == ZKG16_OK) rc = vb_check_rho(rho, k);
+    if (rc != ZKG16_OK) return rc;
+    const double t_all = now_ms();
+    VbBatch b{form.public_inputs, proofs, inf, rho, k};
+    if (k >= (size_t)(from_wire ? ctx->opt.verify_wire_min : ctx->opt.verify_batch_min)) return vb_device(ctx, key, form, b, proof_bytes, ok, ok_each, decode_status, t_all);
+    float tm[V_COUNT] = {0};
+    try {
+        std::vector<uint64_t> made, dec_proofs;
+        std::vector<uint8_t> dec_inf, st, dead;
+        if (from_wire) {
+            // status 5 costs the subgroup tests a second time (vb_host makes its own): only for a caller who asks for the statuses
+            dec_proofs.resize(48 * k);
+            dec_inf.resize(3 * k);
+            st.resize(3 * k);
+            dead.resize(k);
+            vb_wire_decode_host(proof_bytes, k, decode_status ? 1 : 0, 0, dec_proofs.data(), dec_inf.data(), st.data());
+            tm[V_DECODE] = (float)(now_ms() - t_all);
+            for (size_t i = 0; i < k; i++) dead[i] = st[3 * i] || st[3 * i + 1] || st[3 * i + 2] ? 1 : 0;
+            b.proofs = dec_proofs.data();
+            b.inf = dec_inf.data();
+        }
+        b.public_inputs = vb_form_expand(key, form, k, nullptr, made);
+        vb_host(key, b, 0, ok, ok_each, from_wire ? dead.data() : nullptr);
+        if (from_wire && decode_status) memcpy(decode_status, st.data(), 3 * k);
+    } catch (const std::bad_alloc &) {
+        return ZKG16_ERR_OOM;
+    }
+    tm[V_TOTAL] = (float)(now_ms() - t_all);
+    tm[V_HOST_FORM] = 1;
+    vb_publish(ctx, tm);
+    return ZKG16_OK;
+}
+
+// Both per-proof entry points: membership of every proof, then the per-proof pass over the ones that passed
+int vb_each_entry(zkg16_ctx *ctx, const VbKey &key, VbForm form, const uint64_t *proofs, const uint8_t *inf, size_t k, uint8_t *ok_each) {
+    if (!ctx || !ok_each || !proofs || !inf) return ZKG16_ERR_BAD_ARG;
+    const int rc = vb_check_batch(key, form, k);
+    if (rc != ZKG16_OK) return rc;
+    ZK_LANE_BEGIN(ctx)
+    const VbStreams s = vb_streams(ctx);
+    // zkg16_verify_prepared reads all-zero limbs as the point at infinity whatever the flag says: the same here
+    const std::vector<uint8_t> fl = vb_flags(proofs, inf, k);
+    const size_t values_bytes = form.kind == VbKind::U64 ? k * (key.num_instance - 1) * 8 : 0;
+    VbEvents evs;
+    DevBuf d_proofs(k * 48 * 8), d_inf(3 * k), d_mem3(3 * k), d_values(values_bytes);
+    const VbEndo en = vb_endo();
+    upload_h2d(ctx, d_proofs.p, proofs, k * 48 * 8);
+    if (form.kind == VbKind::U64) {
+        upload_h2d(ctx, d_values.p, form.values, values_bytes);
+        form.d_values = d_values.as<uint64_t>();
+    }
+    ZK_HIP(hipMemcpyAsync(d_inf.p, fl.data(), 3 * k, hipMemcpyHostToDevice, s.main));
+    vb_fork(s, evs.ev[0]);
+    for (size_t off = 0; off < k; off += VB_PASS)
+        vb_membership_chunk(s, d_proofs.as<uint64_t>() + 48 * off, d_inf.as<uint8_t>() + 3 * off, std::min(VB_PASS, k - off), en, d_mem3.as<uint8_t>() + 3 * off);
+    vb_join(s, evs.ev[1], evs.ev[2]);
+    std::vector<uint8_t> mem3(3 * k);
+    ZK_HIP(hipMemcpyAsync(mem3.data(), d_mem3.p, 3 * k, hipMemcpyDeviceToHost, s.main));
+    ZK_HIP(hipStreamSynchronize(s.main));
+    // proofs that failed membership are never listed
+    std::vector<uint32_t> idx;
+    for (size_t i = 0; i < k; i++)
+        if (mem3[3 * i] && mem3[3 * i + 1] && mem3[3 * i + 2]) idx.push_back((uint32_t)i);
+    std::vector<uint8_t> verdict(idx.size());
+    (void)vb_each_pass(ctx, key, form, d_proofs.as<uint64_t>(), d_inf.as<uint8_t>(), idx.size() == k ? nullptr : idx.data(), idx.size(), verdict.data());
+    memset(ok_each, 0, k);
+    for (size_t j = 0; j < idx.size(); j++) ok_each[idx[j]] = verdict[j] ? 1 : 0;
+    ZK_LANE_END(ctx)
+}
 }  // namespace
 
 extern "C" {
@@ -397,147 +404,37 @@ extern "C" {
 int zkg16_verify_batch(zkg16_ctx *ctx, const uint64_t *gamma_abc_g1, size_t num_instance, const uint64_t alpha_beta[72], const uint64_t *gamma_neg_coeffs,
                        const uint64_t *delta_neg_coeffs, size_t n_coeffs, const uint64_t *public_inputs, const uint64_t *proofs, const uint8_t *inf,
                        const uint64_t *rho, size_t k, int *ok, uint8_t *ok_each) {
-    if (!ctx) return ZKG16_ERR_BAD_ARG;
     const VbKey key{gamma_abc_g1, num_instance, alpha_beta, gamma_neg_coeffs, delta_neg_coeffs, n_coeffs};
-    const VbBatch b{public_inputs, proofs, inf, rho, k};
-    const int rc = vb_check_args(key, b, ok);
-    if (rc != ZKG16_OK) return rc;
-    const double t_all = now_ms();
-    if (k < (size_t)ctx->opt.verify_batch_min) return vb_answer_on_host(ctx, t_all, [&](float *) { vb_host(key, b, 0, ok, ok_each); });
-    return vb_device(ctx, key, b, nullptr, ok, ok_each, nullptr, t_all);
+    return vb_entry(ctx, key, vb_limbs(public_inputs), proofs, inf, false, nullptr, rho, k, ok, ok_each, nullptr);
 }
 
 int zkg16_verify_batch_wire(zkg16_ctx *ctx, const uint64_t *gamma_abc_g1, size_t num_instance, const uint64_t alpha_beta[72], const uint64_t *gamma_neg_coeffs,
                             const uint64_t *delta_neg_coeffs, size_t n_coeffs, const uint64_t *public_inputs, const uint8_t *proof_bytes,
                             const uint64_t *rho, size_t k, int *ok, uint8_t *ok_each, uint8_t *decode_status) {
-    if (!ctx || !proof_bytes) return ZKG16_ERR_BAD_ARG;
     const VbKey key{gamma_abc_g1, num_instance, alpha_beta, gamma_neg_coeffs, delta_neg_coeffs, n_coeffs};
-    {
-        // the checks of zkg16_verify_batch: the bytes stand in for the limbs and flags that do not exist yet
-        const VbBatch probe{public_inputs, reinterpret_cast<const uint64_t *>(proof_bytes), proof_bytes, rho, k};
-        const int rc = vb_check_args(key, probe, ok);
-        if (rc != ZKG16_OK) return rc;
-    }
-    const double t_all = now_ms();
-    if (k < (size_t)ctx->opt.verify_wire_min)
-        return vb_answer_on_host(ctx, t_all, [&](float *tm) {
-            // status 5 costs the subgroup tests a second time (vb_host makes its own): only for a caller who asks for the statuses
-            std::vector<uint64_t> proofs(48 * k);
-            std::vector<uint8_t> inf(3 * k), st(3 * k);
-            vb_wire_decode_host(proof_bytes, k, decode_status ? 1 : 0, 0, proofs.data(), inf.data(), st.data());
-            tm[V_DECODE] = (float)(now_ms() - t_all);
-            std::vector<uint8_t> dead(k);
-            for (size_t i = 0; i < k; i++) dead[i] = st[3 * i] || st[3 * i + 1] || st[3 * i + 2] ? 1 : 0;
-            const VbBatch b{public_inputs, proofs.data(), inf.data(), rho, k};
-            vb_host(key, b, 0, ok, ok_each, dead.data());
-            if (decode_status) memcpy(decode_status, st.data(), 3 * k);
-        });
-    return vb_device(ctx, key, VbBatch{public_inputs, nullptr, nullptr, rho, k}, proof_bytes, ok, ok_each, decode_status, t_all);
+    return vb_entry(ctx, key, vb_limbs(public_inputs), nullptr, nullptr, true, proof_bytes, rho, k, ok, ok_each, decode_status);
 }
 
 int zkg16_verify_each(zkg16_ctx *ctx, const uint64_t *gamma_abc_g1, size_t num_instance, const uint64_t alpha_beta[72], const uint64_t *gamma_neg_coeffs,
                       const uint64_t *delta_neg_coeffs, size_t n_coeffs, const uint64_t *public_inputs, const uint64_t *proofs, const uint8_t *inf, size_t k,
                       uint8_t *ok_each) {
-    if (!ctx || !ok_each) return ZKG16_ERR_BAD_ARG;
     const VbKey key{gamma_abc_g1, num_instance, alpha_beta, gamma_neg_coeffs, delta_neg_coeffs, n_coeffs};
-    {
-        // the checks of zkg16_verify_batch; there are no multipliers, so one non-zero pair stands in for them
-        const uint64_t some_rho[2] = {1, 0};
-        int ok_probe = 0;
-        const VbBatch probe{public_inputs, proofs, inf, some_rho, 1};
-        if (k == 0) return ZKG16_ERR_BAD_ARG;
-        const int rc = vb_check_args(key, probe, &ok_probe);
-        if (rc != ZKG16_OK) return rc;
-    }
-    ZK_LANE_BEGIN(ctx)
-    hipStream_t s_main = ctx->stream, s_c = ctx->slots[1].stream, s_b = ctx->slots[2].stream;
-    // zkg16_verify_prepared reads all-zero limbs as the point at infinity whatever the flag says: the same here
-    const std::vector<uint8_t> fl = vb_flags(proofs, inf, k);
-    VbEvents evs;
-    DevBuf d_proofs(k * 48 * 8), d_inf(3 * k), d_mem3(3 * k);
-    const VbEndo en = vb_endo();
-    upload_h2d(ctx, d_proofs.p, proofs, k * 48 * 8);
-    ZK_HIP(hipMemcpyAsync(d_inf.p, fl.data(), 3 * k, hipMemcpyHostToDevice, s_main));
-    ZK_HIP(hipEventRecord(evs.ev[0], s_main));
-    for (hipStream_t st : {s_c, s_b}) ZK_HIP(hipStreamWaitEvent(st, evs.ev[0], 0));
-    for (size_t off = 0; off < k; off += VB_PASS) {
-        const size_t n = std::min(VB_PASS, k - off);
-        const uint64_t *pts = d_proofs.as<uint64_t>() + 48 * off;
-        const uint8_t *f3 = d_inf.as<uint8_t>() + 3 * off;
-        uint8_t *m3 = d_mem3.as<uint8_t>() + 3 * off;
-        vb_membership_chunk(s_main, s_c, s_b, pts, f3, n, en, m3);
-    }
-    ZK_HIP(hipEventRecord(evs.ev[1], s_c));
-    ZK_HIP(hipEventRecord(evs.ev[2], s_b));
-    ZK_HIP(hipStreamWaitEvent(s_main, evs.ev[1], 0));
-    ZK_HIP(hipStreamWaitEvent(s_main, evs.ev[2], 0));
-    std::vector<uint8_t> mem3(3 * k);
-    ZK_HIP(hipMemcpyAsync(mem3.data(), d_mem3.p, 3 * k, hipMemcpyDeviceToHost, s_main));
-    ZK_HIP(hipStreamSynchronize(s_main));
-    // proofs that failed membership are never listed
-    std::vector<uint32_t> idx;
-    for (size_t i = 0; i < k; i++)
-        if (mem3[3 * i] && mem3[3 * i + 1] && mem3[3 * i + 2]) idx.push_back((uint32_t)i);
-    std::vector<uint8_t> verdict(idx.size());
-    const size_t per = 4 * (num_instance - 1);
-    (void)vb_each_pass(ctx, key, d_proofs.as<uint64_t>(), d_inf.as<uint8_t>(), idx.size() == k ? nullptr : idx.data(), idx.size(),
-                       [&](size_t j) { return public_inputs + per * idx[j]; }, verdict.data());
-    memset(ok_each, 0, k);
-    for (size_t j = 0; j < idx.size(); j++) ok_each[idx[j]] = verdict[j] ? 1 : 0;
-    ZK_LANE_END(ctx)
+    return vb_each_entry(ctx, key, vb_limbs(public_inputs), proofs, inf, k, ok_each);
 }
 
 // ---- the prime form: K requests of one trapdoor under the extended key (zkg16_prime_vk_extend), their inputs made on the device
-static int vp_check(zkg16_ctx *ctx, const VbKey &key, const uint64_t *xs, const uint64_t *js, const void *proofs, const uint8_t *inf, const uint64_t *rho, size_t k,
-                    const int *ok) {
-    if (!ctx || key.num_instance != 260 || !xs || !js || k >> 32) return ZKG16_ERR_BAD_ARG;
-    // the checks of zkg16_verify_batch: xs stands in for the inputs that do not exist yet
-    return vb_check_args(key, VbBatch{xs, static_cast<const uint64_t *>(proofs), inf, rho, k}, ok);
-}
-static std::vector<uint64_t> vp_inputs_host(const uint64_t *xs, const uint64_t *js, size_t k) {
-    std::vector<uint64_t> pub(4 * 259 * k);
-    for (size_t i = 0; i < k; i++) (void)zkg16_prime_ext_inputs(xs[i], js[i], pub.data() + 4 * 259 * i);      // fails on a null pointer only
-    return pub;
-}
-
 int zkg16_verify_prime_batch(zkg16_ctx *ctx, const uint64_t *gamma_abc_g1, size_t num_instance, const uint64_t alpha_beta[72], const uint64_t *gamma_neg_coeffs,
                              const uint64_t *delta_neg_coeffs, size_t n_coeffs, const uint64_t *xs, const uint64_t *js, const uint64_t *proofs, const uint8_t *inf,
                              const uint64_t *rho, size_t k, int *ok, uint8_t *ok_each) {
     const VbKey key{gamma_abc_g1, num_instance, alpha_beta, gamma_neg_coeffs, delta_neg_coeffs, n_coeffs};
-    const int rc = vp_check(ctx, key, xs, js, proofs, inf, rho, k, ok);
-    if (rc != ZKG16_OK) return rc;
-    const double t_all = now_ms();
-    if (k < (size_t)ctx->opt.verify_batch_min)
-        return vb_answer_on_host(ctx, t_all, [&](float *) {
-            const std::vector<uint64_t> pub = vp_inputs_host(xs, js, k);
-            vb_host(key, VbBatch{pub.data(), proofs, inf, rho, k}, 0, ok, ok_each);
-        });
-    VbPrime prime{xs, js};
-    return vb_device(ctx, key, VbBatch{nullptr, proofs, inf, rho, k}, nullptr, ok, ok_each, nullptr, t_all, &prime);
+    return vb_entry(ctx, key, vb_prime(xs, js), proofs, inf, false, nullptr, rho, k, ok, ok_each, nullptr);
 }
 
 int zkg16_verify_prime_batch_wire(zkg16_ctx *ctx, const uint64_t *gamma_abc_g1, size_t num_instance, const uint64_t alpha_beta[72], const uint64_t *gamma_neg_coeffs,
                                   const uint64_t *delta_neg_coeffs, size_t n_coeffs, const uint64_t *xs, const uint64_t *js, const uint8_t *proof_bytes,
                                   const uint64_t *rho, size_t k, int *ok, uint8_t *ok_each, uint8_t *decode_status) {
     const VbKey key{gamma_abc_g1, num_instance, alpha_beta, gamma_neg_coeffs, delta_neg_coeffs, n_coeffs};
-    if (!proof_bytes) return ZKG16_ERR_BAD_ARG;
-    const int rc = vp_check(ctx, key, xs, js, proof_bytes, proof_bytes, rho, k, ok);
-    if (rc != ZKG16_OK) return rc;
-    const double t_all = now_ms();
-    if (k < (size_t)ctx->opt.verify_wire_min)
-        return vb_answer_on_host(ctx, t_all, [&](float *tm) {
-            std::vector<uint64_t> proofs(48 * k);
-            std::vector<uint8_t> inf(3 * k), st(3 * k);
-            vb_wire_decode_host(proof_bytes, k, decode_status ? 1 : 0, 0, proofs.data(), inf.data(), st.data());
-            tm[V_DECODE] = (float)(now_ms() - t_all);
-            std::vector<uint8_t> dead(k);
-            for (size_t i = 0; i < k; i++) dead[i] = st[3 * i] || st[3 * i + 1] || st[3 * i + 2] ? 1 : 0;
-            const std::vector<uint64_t> pub = vp_inputs_host(xs, js, k);
-            vb_host(key, VbBatch{pub.data(), proofs.data(), inf.data(), rho, k}, 0, ok, ok_each, dead.data());
-            if (decode_status) memcpy(decode_status, st.data(), 3 * k);
-        });
-    VbPrime prime{xs, js};
-    return vb_device(ctx, key, VbBatch{nullptr, nullptr, nullptr, rho, k}, proof_bytes, ok, ok_each, decode_status, t_all, &prime);
+    return vb_entry(ctx, key, vb_prime(xs, js), nullptr, nullptr, true, proof_bytes, rho, k, ok, ok_each, decode_status);
 }
 
 // Stage entries: the inputs kernel and the sums kernels by themselves
@@ -579,103 +476,25 @@ int zkg16_prime_rho_sums(zkg16_ctx *ctx, const uint64_t *xs, const uint64_t *js,
 }
 
 // ---- the u64 form: a key whose public inputs are plain 64-bit values, values = k x (num_instance - 1) u64
-static int vu_check(zkg16_ctx *ctx, const VbKey &key, const uint64_t *values, const void *proofs, const uint8_t *inf, const uint64_t *rho, size_t k, const int *ok) {
-    if (!ctx || key.num_instance < 2 || !values || k >> 32) return ZKG16_ERR_BAD_ARG;
-    // the checks of zkg16_verify_batch: the values stand in for the inputs that do not exist yet
-    return vb_check_args(key, VbBatch{values, static_cast<const uint64_t *>(proofs), inf, rho, k}, ok);
-}
-static std::vector<uint64_t> vu_inputs_host(const VbKey &key, const uint64_t *values, size_t k) {
-    std::vector<uint64_t> pub(4 * (key.num_instance - 1) * k);
-    vb_u64_expand(values, (key.num_instance - 1) * k, pub.data());
-    return pub;
-}
-
 int zkg16_verify_batch_u64(zkg16_ctx *ctx, const uint64_t *gamma_abc_g1, size_t num_instance, const uint64_t alpha_beta[72], const uint64_t *gamma_neg_coeffs,
                            const uint64_t *delta_neg_coeffs, size_t n_coeffs, const uint64_t *values, const uint64_t *proofs, const uint8_t *inf, const uint64_t *rho,
                            size_t k, int *ok, uint8_t *ok_each) {
     const VbKey key{gamma_abc_g1, num_instance, alpha_beta, gamma_neg_coeffs, delta_neg_coeffs, n_coeffs};
-    const int rc = vu_check(ctx, key, values, proofs, inf, rho, k, ok);
-    if (rc != ZKG16_OK) return rc;
-    const double t_all = now_ms();
-    if (k < (size_t)ctx->opt.verify_batch_min)
-        return vb_answer_on_host(ctx, t_all, [&](float *) {
-            const std::vector<uint64_t> pub = vu_inputs_host(key, values, k);
-            vb_host(key, VbBatch{pub.data(), proofs, inf, rho, k}, 0, ok, ok_each);
-        });
-    VbU64 u64{values};
-    return vb_device(ctx, key, VbBatch{nullptr, proofs, inf, rho, k}, nullptr, ok, ok_each, nullptr, t_all, nullptr, &u64);
+    return vb_entry(ctx, key, vb_u64(values), proofs, inf, false, nullptr, rho, k, ok, ok_each, nullptr);
 }
 
 int zkg16_verify_batch_u64_wire(zkg16_ctx *ctx, const uint64_t *gamma_abc_g1, size_t num_instance, const uint64_t alpha_beta[72], const uint64_t *gamma_neg_coeffs,
                                 const uint64_t *delta_neg_coeffs, size_t n_coeffs, const uint64_t *values, const uint8_t *proof_bytes, const uint64_t *rho,
                                 size_t k, int *ok, uint8_t *ok_each, uint8_t *decode_status) {
     const VbKey key{gamma_abc_g1, num_instance, alpha_beta, gamma_neg_coeffs, delta_neg_coeffs, n_coeffs};
-    if (!proof_bytes) return ZKG16_ERR_BAD_ARG;
-    const int rc = vu_check(ctx, key, values, proof_bytes, proof_bytes, rho, k, ok);
-    if (rc != ZKG16_OK) return rc;
-    const double t_all = now_ms();
-    if (k < (size_t)ctx->opt.verify_wire_min)
-        return vb_answer_on_host(ctx, t_all, [&](float *tm) {
-            std::vector<uint64_t> proofs(48 * k);
-            std::vector<uint8_t> inf(3 * k), st(3 * k);
-            vb_wire_decode_host(proof_bytes, k, decode_status ? 1 : 0, 0, proofs.data(), inf.data(), st.data());
-            tm[V_DECODE] = (float)(now_ms() - t_all);
-            std::vector<uint8_t> dead(k);
-            for (size_t i = 0; i < k; i++) dead[i] = st[3 * i] || st[3 * i + 1] || st[3 * i + 2] ? 1 : 0;
-            const std::vector<uint64_t> pub = vu_inputs_host(key, values, k);
-            vb_host(key, VbBatch{pub.data(), proofs.data(), inf.data(), rho, k}, 0, ok, ok_each, dead.data());
-            if (decode_status) memcpy(decode_status, st.data(), 3 * k);
-        });
-    VbU64 u64{values};
-    return vb_device(ctx, key, VbBatch{nullptr, nullptr, nullptr, rho, k}, proof_bytes, ok, ok_each, decode_status, t_all, nullptr, &u64);
+    return vb_entry(ctx, key, vb_u64(values), nullptr, nullptr, true, proof_bytes, rho, k, ok, ok_each, decode_status);
 }
 
 int zkg16_verify_each_u64(zkg16_ctx *ctx, const uint64_t *gamma_abc_g1, size_t num_instance, const uint64_t alpha_beta[72], const uint64_t *gamma_neg_coeffs,
                           const uint64_t *delta_neg_coeffs, size_t n_coeffs, const uint64_t *values, const uint64_t *proofs, const uint8_t *inf, size_t k,
                           uint8_t *ok_each) {
-    if (!ctx || !ok_each || k == 0) return ZKG16_ERR_BAD_ARG;
     const VbKey key{gamma_abc_g1, num_instance, alpha_beta, gamma_neg_coeffs, delta_neg_coeffs, n_coeffs};
-    {
-        // the checks of zkg16_verify_each: there are no multipliers, so one non-zero pair stands in for them
-        const uint64_t some_rho[2] = {1, 0};
-        int ok_probe = 0;
-        if (num_instance < 2 || !values || k >> 32) return ZKG16_ERR_BAD_ARG;
-        const int rc = vb_check_args(key, VbBatch{values, proofs, inf, some_rho, 1}, &ok_probe);
-        if (rc != ZKG16_OK) return rc;
-    }
-    ZK_LANE_BEGIN(ctx)
-    hipStream_t s_main = ctx->stream, s_c = ctx->slots[1].stream, s_b = ctx->slots[2].stream;
-    const std::vector<uint8_t> fl = vb_flags(proofs, inf, k);
-    const size_t m = num_instance - 1;
-    VbEvents evs;
-    DevBuf d_proofs(k * 48 * 8), d_inf(3 * k), d_mem3(3 * k), d_values(k * m * 8);
-    const VbEndo en = vb_endo();
-    upload_h2d(ctx, d_proofs.p, proofs, k * 48 * 8);
-    upload_h2d(ctx, d_values.p, values, k * m * 8);
-    ZK_HIP(hipMemcpyAsync(d_inf.p, fl.data(), 3 * k, hipMemcpyHostToDevice, s_main));
-    ZK_HIP(hipEventRecord(evs.ev[0], s_main));
-    for (hipStream_t st : {s_c, s_b}) ZK_HIP(hipStreamWaitEvent(st, evs.ev[0], 0));
-    for (size_t off = 0; off < k; off += VB_PASS)
-        vb_membership_chunk(s_main, s_c, s_b, d_proofs.as<uint64_t>() + 48 * off, d_inf.as<uint8_t>() + 3 * off, std::min(VB_PASS, k - off), en,
-                            d_mem3.as<uint8_t>() + 3 * off);
-    ZK_HIP(hipEventRecord(evs.ev[1], s_c));
-    ZK_HIP(hipEventRecord(evs.ev[2], s_b));
-    ZK_HIP(hipStreamWaitEvent(s_main, evs.ev[1], 0));
-    ZK_HIP(hipStreamWaitEvent(s_main, evs.ev[2], 0));
-    std::vector<uint8_t> mem3(3 * k);
-    ZK_HIP(hipMemcpyAsync(mem3.data(), d_mem3.p, 3 * k, hipMemcpyDeviceToHost, s_main));
-    ZK_HIP(hipStreamSynchronize(s_main));
-    // proofs that failed membership are never listed
-    std::vector<uint32_t> idx;
-    for (size_t i = 0; i < k; i++)
-        if (mem3[3 * i] && mem3[3 * i + 1] && mem3[3 * i + 2]) idx.push_back((uint32_t)i);
-    std::vector<uint8_t> verdict(idx.size());
-    const VbU64 u64{values, d_values.as<uint64_t>()};
-    (void)vb_each_pass(ctx, key, d_proofs.as<uint64_t>(), d_inf.as<uint8_t>(), idx.size() == k ? nullptr : idx.data(), idx.size(),
-                       [](size_t) -> const uint64_t * { return nullptr; }, verdict.data(), nullptr, &u64);
-    memset(ok_each, 0, k);
-    for (size_t j = 0; j < idx.size(); j++) ok_each[idx[j]] = verdict[j] ? 1 : 0;
-    ZK_LANE_END(ctx)
+    return vb_each_entry(ctx, key, vb_u64(values), proofs, inf, k, ok_each);
 }
 
 // Stage entries: the sums kernels and the X kernel by themselves
@@ -798,289 +617,6 @@ int zkg16_point_check_batch(zkg16_ctx *ctx, int group, const uint64_t *points, c
     ZK_HIP(hipStreamSynchronize(ctx->stream));
     ZK_LANE_END(ctx)
 }
-
-}  // extern "C"
-
-// ------------------------------------------------------------------------------------------------ re-randomising
-// (rerandomize_dev.cuh.)  A' = r1^-1 A, B' = r1 B + (r1 r2) delta, C' = C + r2 A for k proofs of one key: the G2 kernel on the lane's
-// main stream, the G1 kernel beside it on a second one.  From wire bytes the decompress and membership kernels run in front as they
-// do for zkg16_verify_batch_wire, nothing comes back in between (the kernels read the statuses and verdicts where they lie), and the
-// compress kernel turns the results into the bytes that travel back.
-namespace {
-// why a call is refused, or null; *text names the proof and the multiplier
-const char *rr_refusal(const uint64_t *delta, const void *proofs, const uint64_t *r1, const uint64_t *r2, size_t k, const void *out, const void *out2, std::string *text) {
-    if (k == 0) return "no proofs";
-    if (!delta || !proofs || !r1 || !r2 || !out || !out2) return "a null pointer";
-    uint64_t any = 0;
-    for (int t = 0; t < 24; t++) any |= delta[t];
-    if (!any) return "delta_g2 is all-zero limbs";
-    uint64_t mod[4];
-    for (int i = 0; i < 4; i++) mod[i] = (uint64_t)FrP::mod(2 * i) | (uint64_t)FrP::mod(2 * i + 1) << 32;
-    for (size_t i = 0; i < k; i++)
-        for (int which = 0; which < 2; which++) {
-            const uint64_t *v = (which ? r2 : r1) + 4 * i;
-            bool less = false;
-            for (int t = 0; t < 4; t++) less = v[t] < mod[t] || (v[t] == mod[t] && less);
-            const bool zero = !(v[0] | v[1] | v[2] | v[3]);
-            if (zero || !less) {
-                char buf[96];
-                snprintf(buf, sizeof buf, "r%d of proof %zu is %s", which + 1, i, zero ? "zero" : "not below r");
-                *text = buf;
-                return text->c_str();
-            }
-        }
-    return nullptr;
-}
-int rr_refuse(zkg16_ctx *ctx, const char *entry, const char *why) {
-    const std::string text = std::string(entry) + ": " + why;
-    if (ctx) {
-        std::lock_guard<std::mutex> lk(ctx->lane_mu);
-        ctx->last_error = text;
-    } else {
-        host_last_error() = text;
-    }
-    return ZKG16_ERR_BAD_ARG;
-}
-// fn(lo, hi) over [0, n) on up to `threads` host threads (0 = 8); a thread that cannot be started runs inline
-template <class Fn>
-void rr_parallel(size_t n, int threads, Fn fn) {
-    const size_t nt = std::min<size_t>(threads <= 0 ? 8 : (size_t)threads, n);
-    if (nt <= 1) { if (n) fn((size_t)0, n); return; }
-    struct Joiner {
-        std::vector<std::thread> th;
-        ~Joiner() { for (auto &t : th) if (t.joinable()) t.join(); }
-    } tg;
-    const size_t per = (n + nt - 1) / nt;
-    for (size_t t = 0; t < nt; t++) {
-        const size_t lo = t * per, hi = std::min(n, lo + per);
-        if (lo >= hi) break;
-        auto job = [lo, hi, &fn] { fn(lo, hi); };
-        try {
-            tg.th.emplace_back(job);
-        } catch (const std::system_error &) {
-            job();
-        }
-    }
-}
-void rr_host(const uint64_t *delta, const uint64_t *proofs, const uint8_t *inf, const uint64_t *r1, const uint64_t *r2, size_t k, int threads, uint64_t *out,
-             uint8_t *out_inf) {
-    rr_parallel(k, threads, [&](size_t lo, size_t hi) { vb_rerandomize_host_range(proofs, inf, delta, r1, r2, lo, hi, out, out_inf); });
-}
-// the wire form on the host: decode (validating), the host form, encode; a proof that did not decode gets zero bytes
-void rr_host_wire(const uint64_t *delta, const uint8_t *bytes, const uint64_t *r1, const uint64_t *r2, size_t k, uint8_t *bytes_out, uint8_t *st) {
-    std::vector<uint64_t> proofs(48 * k), out(48 * k);
-    std::vector<uint8_t> inf(3 * k), out_inf(3 * k);
-    vb_wire_decode_host(bytes, k, 1, 0, proofs.data(), inf.data(), st);
-    rr_host(delta, proofs.data(), inf.data(), r1, r2, k, 0, out.data(), out_inf.data());
-    for (size_t i = 0; i < k; i++) {
-        uint8_t *b = bytes_out + 192 * i;
-        if (st[3 * i] || st[3 * i + 1] || st[3 * i + 2]) {
-            memset(b, 0, 192);
-            continue;
-        }
-        (void)zkg16_points_compress(1, out.data() + 48 * i, out_inf.data() + 3 * i, 1, b);
-        (void)zkg16_points_compress(2, out.data() + 48 * i + 12, out_inf.data() + 3 * i + 1, 1, b + 48);
-        (void)zkg16_points_compress(1, out.data() + 48 * i + 36, out_inf.data() + 3 * i + 2, 1, b + 144);
-    }
-}
-void rr_publish(zkg16_ctx *root, const float tm[R_COUNT]) {
-    std::lock_guard<std::mutex> lk(root->lane_mu);
-    memcpy(root->rr_timings, tm, sizeof root->rr_timings);
-}
-bool rr_any_failed(const uint8_t *st, size_t k) {
-    bool any = false;
-    for (size_t j = 0; j < 3 * k; j++) any = any || st[j];
-    return any;
-}
-
-// The device form.  wire == null: proofs / inf are the caller's limbs and flags, and proofs_out / inf_out take the results.
-// wire != null (k x 192 bytes): bytes_out takes k x 192 bytes and st (k x 3) the statuses of the validating host decoder
-int rr_device(zkg16_ctx *ctx, const uint64_t *delta, const uint64_t *proofs, const uint8_t *inf, const uint8_t *wire, const uint64_t *r1, const uint64_t *r2, size_t k,
-              uint64_t *proofs_out, uint8_t *inf_out, uint8_t *bytes_out, uint8_t *st, double t_all) {
-    float tm[R_COUNT] = {0};
-    ZK_LANE_BEGIN(ctx)
-    hipStream_t s_main = ctx->stream, s_c = ctx->slots[1].stream, s_b = ctx->slots[2].stream;
-    const size_t pass = ctx->opt.rerandomize_pass > 0 ? (size_t)ctx->opt.rerandomize_pass : VB_PASS;
-    VbEvents evs;
-    hipEvent_t e_0 = evs.ev[0], e_up = evs.ev[1], e_c = evs.ev[2], e_b = evs.ev[3], e_dec = evs.ev[4], e_c2 = evs.ev[5], e_b2 = evs.ev[6], e_mem = evs.ev[7],
-               e_g1a = evs.ev[8], e_g1b = evs.ev[9], e_g2b = evs.ev[10], e_cmp = evs.ev[11], e_rb = evs.ev[12];
-    DevBuf d_proofs(k * 48 * 8), d_inf(3 * k), d_r1(k * 32), d_r2(k * 32), d_delta(24 * 8), d_out(k * 48 * 8), d_oinf(3 * k);
-    DevBuf d_wire(wire ? k * 192 : 0), d_st(wire ? 3 * k : 0), d_mem3(wire ? 3 * k : 0), d_bytes(wire ? k * 192 : 0);
-    std::vector<uint8_t> flags;
-    ZK_HIP(hipEventRecord(e_0, s_main));
-    if (wire) {
-        upload_h2d(ctx, d_wire.p, wire, k * 192);
-    } else {
-        // load_pt's rule on the flags, as the verifiers apply it; the kernels look at the limbs as well
-        std::vector<uint8_t> none;
-        if (!inf) none.assign(3 * k, 0);
-        flags = vb_flags(proofs, inf ? inf : none.data(), k);
-        upload_h2d(ctx, d_proofs.p, proofs, k * 48 * 8);
-        upload_h2d(ctx, d_inf.p, flags.data(), 3 * k);
-    }
-    upload_h2d(ctx, d_r1.p, r1, k * 32);
-    upload_h2d(ctx, d_r2.p, r2, k * 32);
-    upload_h2d(ctx, d_delta.p, delta, 24 * 8);
-    ZK_HIP(hipEventRecord(e_up, s_main));
-    for (hipStream_t s : {s_c, s_b}) ZK_HIP(hipStreamWaitEvent(s, e_up, 0));
-    const uint8_t *st3 = nullptr, *mem3 = nullptr;
-    if (wire) {
-        const VbEndo en = vb_endo();
-        for (size_t off = 0; off < k; off += pass) {
-            const size_t n = std::min(pass, k - off);
-            const uint8_t *by = d_wire.as<uint8_t>() + 192 * off;
-            uint64_t *pts = d_proofs.as<uint64_t>() + 48 * off;
-            uint8_t *fl = d_inf.as<uint8_t>() + 3 * off, *s3 = d_st.as<uint8_t>() + 3 * off;
-            vb_decompress_launch(s_main, 2, by + 48, 192, n, 0, en, pts + 12, 48, fl + 1, 3, s3 + 1, 3);
-            vb_decompress_launch(s_c, 1, by, 192, n, 0, en, pts, 48, fl, 3, s3, 3);
-            vb_decompress_launch(s_b, 1, by + 144, 192, n, 0, en, pts + 36, 48, fl + 2, 3, s3 + 2, 3);
-        }
-        ZK_HIP(hipEventRecord(e_c, s_c));
-        ZK_HIP(hipEventRecord(e_b, s_b));
-        ZK_HIP(hipStreamWaitEvent(s_main, e_c, 0));
-        ZK_HIP(hipStreamWaitEvent(s_main, e_b, 0));
-        ZK_HIP(hipEventRecord(e_dec, s_main));
-        for (hipStream_t s : {s_c, s_b}) ZK_HIP(hipStreamWaitEvent(s, e_dec, 0));
-        for (size_t off = 0; off < k; off += pass)
-            vb_membership_chunk(s_main, s_c, s_b, d_proofs.as<uint64_t>() + 48 * off, d_inf.as<uint8_t>() + 3 * off, std::min(pass, k - off), en,
-                                d_mem3.as<uint8_t>() + 3 * off);
-        ZK_HIP(hipEventRecord(e_c2, s_c));
-        ZK_HIP(hipEventRecord(e_b2, s_b));
-        ZK_HIP(hipStreamWaitEvent(s_main, e_c2, 0));
-        ZK_HIP(hipStreamWaitEvent(s_main, e_b2, 0));
-        st3 = d_st.as<uint8_t>();
-        mem3 = d_mem3.as<uint8_t>();
-    }
-    ZK_HIP(hipEventRecord(e_mem, s_main));
-    ZK_HIP(hipStreamWaitEvent(s_c, e_mem, 0));
-    ZK_HIP(hipEventRecord(e_g1a, s_c));
-    for (size_t off = 0; off < k; off += pass)
-        vb_rerandomize_launch(s_c, s_main, d_proofs.as<uint64_t>() + 48 * off, d_inf.as<uint8_t>() + 3 * off, d_delta.as<uint64_t>(), d_r1.as<uint64_t>() + 4 * off,
-                              d_r2.as<uint64_t>() + 4 * off, st3 ? st3 + 3 * off : nullptr, mem3 ? mem3 + 3 * off : nullptr, std::min(pass, k - off),
-                              d_out.as<uint64_t>() + 48 * off, d_oinf.as<uint8_t>() + 3 * off);
-    ZK_HIP(hipEventRecord(e_g1b, s_c));
-    ZK_HIP(hipEventRecord(e_g2b, s_main));
-    ZK_HIP(hipStreamWaitEvent(s_main, e_g1b, 0));
-    std::vector<uint8_t> dec_st, mem;
-    if (wire) {
-        for (size_t off = 0; off < k; off += pass) {
-            const size_t n = std::min(pass, k - off);
-            const uint64_t *pts = d_out.as<uint64_t>() + 48 * off;
-            const uint8_t *fl = d_oinf.as<uint8_t>() + 3 * off;
-            uint8_t *by = d_bytes.as<uint8_t>() + 192 * off;
-            vb_compress_launch(s_main, 1, pts, 48, fl, 3, n, st3 + 3 * off, mem3 + 3 * off, by, 192);
-            vb_compress_launch(s_main, 2, pts + 12, 48, fl + 1, 3, n, st3 + 3 * off, mem3 + 3 * off, by + 48, 192);
-            vb_compress_launch(s_main, 1, pts + 36, 48, fl + 2, 3, n, st3 + 3 * off, mem3 + 3 * off, by + 144, 192);
-        }
-        ZK_HIP(hipEventRecord(e_cmp, s_main));
-        dec_st.resize(3 * k);
-        mem.resize(3 * k);
-        ZK_HIP(hipMemcpyAsync(bytes_out, d_bytes.p, k * 192, hipMemcpyDeviceToHost, s_main));
-        ZK_HIP(hipMemcpyAsync(dec_st.data(), d_st.p, 3 * k, hipMemcpyDeviceToHost, s_main));
-        ZK_HIP(hipMemcpyAsync(mem.data(), d_mem3.p, 3 * k, hipMemcpyDeviceToHost, s_main));
-    } else {
-        ZK_HIP(hipEventRecord(e_cmp, s_main));
-        ZK_HIP(hipMemcpyAsync(proofs_out, d_out.p, k * 48 * 8, hipMemcpyDeviceToHost, s_main));
-        ZK_HIP(hipMemcpyAsync(inf_out, d_oinf.p, 3 * k, hipMemcpyDeviceToHost, s_main));
-    }
-    ZK_HIP(hipEventRecord(e_rb, s_main));
-    ZK_HIP(hipStreamSynchronize(s_main));
-    if (wire)
-        for (size_t j = 0; j < 3 * k; j++) st[j] = dec_st[j] ? dec_st[j] : (mem[j] ? 0 : 5);
-    tm[R_UPLOAD] = vb_elapsed(e_0, e_up);
-    if (wire) tm[R_DECODE] = vb_elapsed(e_up, e_mem);
-    tm[R_G1] = vb_elapsed(e_g1a, e_g1b);
-    tm[R_G2] = vb_elapsed(e_mem, e_g2b);
-    if (wire) tm[R_COMPRESS] = vb_elapsed(e_g2b, e_cmp);      // from the end of the G2 kernel: the wait for the G1 kernel, if any, is in it
-    tm[R_READBACK] = vb_elapsed(e_cmp, e_rb);
-    tm[R_TOTAL] = (float)(now_ms() - t_all);
-    rr_publish(root, tm);
-    ZK_LANE_END(ctx)
-}
-template <class Form>
-int rr_answer_on_host(zkg16_ctx *ctx, double t_all, Form &&form) {
-    float tm[R_COUNT] = {0};
-    try {
-        form();
-    } catch (const std::bad_alloc &) {
-        return ZKG16_ERR_OOM;
-    }
-    tm[R_TOTAL] = (float)(now_ms() - t_all);
-    tm[R_HOST_FORM] = 1;
-    rr_publish(ctx, tm);
-    return ZKG16_OK;
-}
-}  // namespace
-
-extern "C" {
-
-int zkg16_rerandomize_batch_host(const uint64_t delta_g2[24], const uint64_t *proofs, const uint8_t *inf, const uint64_t *r1, const uint64_t *r2, size_t k, int threads,
-                                 uint64_t *proofs_out, uint8_t *inf_out) {
-    std::string text;
-    if (const char *why = rr_refusal(delta_g2, proofs, r1, r2, k, proofs_out, inf_out, &text)) return rr_refuse(nullptr, "zkg16_rerandomize_batch_host", why);
-    try {
-        rr_host(delta_g2, proofs, inf, r1, r2, k, threads, proofs_out, inf_out);
-    } catch (const std::bad_alloc &) {
-        return ZKG16_ERR_OOM;
-    }
-    return ZKG16_OK;
-}
-
-int zkg16_rerandomize_batch(zkg16_ctx *ctx, const uint64_t delta_g2[24], const uint64_t *proofs, const uint8_t *inf, const uint64_t *r1, const uint64_t *r2, size_t k,
-                            uint64_t *proofs_out, uint8_t *inf_out) {
-    if (!ctx) return ZKG16_ERR_BAD_ARG;
-    std::string text;
-    if (const char *why = rr_refusal(delta_g2, proofs, r1, r2, k, proofs_out, inf_out, &text)) return rr_refuse(ctx, "zkg16_rerandomize_batch", why);
-    const double t_all = now_ms();
-    if (k < (size_t)ctx->opt.rerandomize_min) return rr_answer_on_host(ctx, t_all, [&] { rr_host(delta_g2, proofs, inf, r1, r2, k, 0, proofs_out, inf_out); });
-    return rr_device(ctx, delta_g2, proofs, inf, nullptr, r1, r2, k, proofs_out, inf_out, nullptr, nullptr, t_all);
-}
-
-int zkg16_rerandomize_batch_wire(zkg16_ctx *ctx, const uint64_t delta_g2[24], const uint8_t *proof_bytes, const uint64_t *r1, const uint64_t *r2, size_t k,
-                                 uint8_t *bytes_out, uint8_t *status) {
-    if (!ctx) return ZKG16_ERR_BAD_ARG;
-    std::string text;
-    if (const char *why = rr_refusal(delta_g2, proof_bytes, r1, r2, k, bytes_out, bytes_out, &text)) return rr_refuse(ctx, "zkg16_rerandomize_batch_wire", why);
-    const double t_all = now_ms();
-    std::vector<uint8_t> st;
-    try {
-        st.resize(3 * k);
-    } catch (const std::bad_alloc &) {
-        return ZKG16_ERR_OOM;
-    }
-    const int rc = k < (size_t)ctx->opt.rerandomize_min
-                       ? rr_answer_on_host(ctx, t_all, [&] { rr_host_wire(delta_g2, proof_bytes, r1, r2, k, bytes_out, st.data()); })
-                       : rr_device(ctx, delta_g2, nullptr, nullptr, proof_bytes, r1, r2, k, nullptr, nullptr, bytes_out, st.data(), t_all);
-    if (rc != ZKG16_OK) return rc;
-    if (status) memcpy(status, st.data(), 3 * k);
-    else if (rr_any_failed(st.data(), k)) return rr_refuse(ctx, "zkg16_rerandomize_batch_wire", "a proof did not decode and status is null");
-    return ZKG16_OK;
-}
-
-int zkg16_points_compress_batch(zkg16_ctx *ctx, int group, const uint64_t *points, const uint8_t *inf, size_t n, uint8_t *out) {
-    if (!ctx || (group != 1 && group != 2) || ((!points || !out) && n)) return ZKG16_ERR_BAD_ARG;
-    if (!n) return ZKG16_OK;
-    ZK_LANE_BEGIN(ctx)
-    const size_t w = group == 1 ? 12 : 24, nb = group == 1 ? 48 : 96;
-    DevBuf d_p(n * w * 8), d_i(inf ? n : 0), d_b(n * nb);
-    upload_h2d(ctx, d_p.p, points, n * w * 8);
-    if (inf) ZK_HIP(hipMemcpyAsync(d_i.p, inf, n, hipMemcpyHostToDevice, ctx->stream));
-    for (size_t off = 0; off < n; off += VB_PASS)
-        vb_compress_launch(ctx->stream, group, d_p.as<uint64_t>() + w * off, w, inf ? d_i.as<uint8_t>() + off : nullptr, 1, std::min(VB_PASS, n - off), nullptr, nullptr,
-                           d_b.as<uint8_t>() + nb * off, nb);
-    ZK_HIP(hipMemcpyAsync(out, d_b.p, n * nb, hipMemcpyDeviceToHost, ctx->stream));
-    ZK_HIP(hipStreamSynchronize(ctx->stream));
-    ZK_LANE_END(ctx)
-}
-
-int zkg16_rerandomize_timings(zkg16_ctx *ctx, float *ms, int cap) {
-    if (!ctx || !ms || cap < 0) return ZKG16_ERR_BAD_ARG;
-    std::lock_guard<std::mutex> lk(ctx->lane_mu);
-    const int n = cap < R_COUNT ? cap : R_COUNT;
-    memcpy(ms, ctx->rr_timings, n * sizeof(float));
-    return n;
-}
-
 int zkg16_verify_batch_timings(zkg16_ctx *ctx, float *ms, int cap) {
     if (!ctx || !ms || cap < 0) return ZKG16_ERR_BAD_ARG;
     std::lock_guard<std::mutex> lk(ctx->lane_mu);

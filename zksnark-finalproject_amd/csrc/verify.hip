@@ -865,28 +865,6 @@ using HPt = pf::Pt<pf::Fq64>;
 
 double vb_now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
-// fn(lo, hi) over [0, n) on up to `threads` threads (0 = 8), at least min_per items each; a thread that cannot be started runs inline
-template <class Fn>
-void vb_parallel(size_t n, int threads, size_t min_per, Fn fn) {
-    size_t nt = threads <= 0 ? 8 : (size_t)threads;
-    if (min_per && n / min_per < nt) nt = n / min_per;
-    if (nt <= 1) { if (n) fn((size_t)0, n); return; }
-    struct Joiner {
-        std::vector<std::thread> th;
-        ~Joiner() { for (auto &t : th) if (t.joinable()) t.join(); }
-    } tg;
-    const size_t per = (n + nt - 1) / nt;
-    for (size_t t = 0; t < nt; t++) {
-        const size_t lo = t * per, hi = std::min(n, lo + per);
-        if (lo >= hi) break;
-        auto job = [lo, hi, &fn] { fn(lo, hi); };
-        try {
-            tg.th.emplace_back(job);
-        } catch (const std::system_error &) {
-            job();
-        }
-    }
-}
 Fr vb_rho_mont(const uint64_t *rho) {
     Fr c = Fr::zero();
     memcpy(c.l, rho, 16);
@@ -1050,12 +1028,22 @@ struct VbDecider {
 
 namespace zk {
 
-int vb_check_args(const VbKey &key, const VbBatch &b, const int *ok) {
-    if (!key.gamma_abc_g1 || key.num_instance == 0 || !key.alpha_beta || !key.gamma_neg_coeffs || !key.delta_neg_coeffs || key.n_coeffs != ELL_COUNT)
+int vb_check_batch(const VbKey &key, const VbForm &form, size_t k) {
+    if (!key.gamma_abc_g1 || key.num_instance == 0 || !key.alpha_beta || !key.gamma_neg_coeffs || !key.delta_neg_coeffs || key.n_coeffs != ELL_COUNT || k == 0)
         return ZKG16_ERR_BAD_ARG;
-    if (b.k == 0 || !b.proofs || !b.inf || !b.rho || (!b.public_inputs && key.num_instance > 1) || !ok) return ZKG16_ERR_BAD_ARG;
-    for (size_t k = 0; k < b.k; k++)
-        if (!(b.rho[2 * k] | b.rho[2 * k + 1])) return ZKG16_ERR_BAD_ARG;       // a zero multiplier would wave proof k through
+    bool fits = false;
+    switch (form.kind) {
+    case VbKind::Limbs: fits = form.public_inputs || key.num_instance == 1; break;
+    case VbKind::Prime: fits = key.num_instance == 260 && form.xs && form.js && !(k >> 32); break;
+    case VbKind::U64: fits = key.num_instance >= 2 && form.values && !(k >> 32); break;
+    }
+    return fits ? ZKG16_OK : ZKG16_ERR_BAD_ARG;
+}
+
+int vb_check_rho(const uint64_t *rho, size_t k) {
+    if (!rho) return ZKG16_ERR_BAD_ARG;
+    for (size_t i = 0; i < k; i++)
+        if (!(rho[2 * i] | rho[2 * i + 1])) return ZKG16_ERR_BAD_ARG;       // a zero multiplier would wave proof i through
     return ZKG16_OK;
 }
 
@@ -1143,6 +1131,17 @@ void vb_u64_expand(const uint64_t *values, size_t n, uint64_t *out) {
     }
 }
 
+const uint64_t *vb_form_expand(const VbKey &key, const VbForm &form, size_t k, const uint32_t *digests, std::vector<uint64_t> &made) {
+    if (form.kind == VbKind::Limbs) return form.public_inputs;
+    const size_t m = key.num_instance - 1;
+    made.resize(4 * m * k);
+    if (form.kind == VbKind::U64) vb_u64_expand(form.values, m * k, made.data());
+    else if (digests) vb_prime_expand(form.xs, form.js, digests, k, made.data());
+    else
+        for (size_t i = 0; i < k; i++) (void)zkg16_prime_ext_inputs(form.xs[i], form.js[i], made.data() + 4 * m * i);      // fails on a null pointer only
+    return made.data();
+}
+
 void vb_host(const VbKey &key, const VbBatch &b, int threads, int *ok, uint8_t *ok_each, const uint8_t *dead) {
     (void)pf::endo();                // the function-local statics exist before any helper thread asks for them
     (void)pf::consts();
@@ -1196,20 +1195,27 @@ void vb_wire_decode_host(const uint8_t *proof_bytes, size_t k, int validate, int
 
 extern "C" {
 
-int zkg16_verify_batch_host(const uint64_t *gamma_abc_g1, size_t num_instance, const uint64_t alpha_beta[72], const uint64_t *gamma_neg_coeffs,
-                            const uint64_t *delta_neg_coeffs, size_t n_coeffs, const uint64_t *public_inputs, const uint64_t *proofs, const uint8_t *inf,
-                            const uint64_t *rho, size_t k, int threads, int *ok, uint8_t *ok_each) {
-    const zk::VbKey key{gamma_abc_g1, num_instance, alpha_beta, gamma_neg_coeffs, delta_neg_coeffs, n_coeffs};
-    const zk::VbBatch b{public_inputs, proofs, inf, rho, k};
-    if (threads < 0) return ZKG16_ERR_BAD_ARG;
-    const int rc = zk::vb_check_args(key, b, ok);
+// The three host forms: the checks, the form's inputs expanded to Montgomery limbs, vb_host
+static int vb_host_entry(const zk::VbKey &key, const zk::VbForm &form, const uint64_t *proofs, const uint8_t *inf, const uint64_t *rho, size_t k, int threads, int *ok,
+                         uint8_t *ok_each) {
+    if (threads < 0 || !proofs || !inf || !ok) return ZKG16_ERR_BAD_ARG;
+    int rc = zk::vb_check_batch(key, form, k);
+    if (rc == ZKG16_OK) rc = zk::vb_check_rho(rho, k);
     if (rc != ZKG16_OK) return rc;
     try {
-        zk::vb_host(key, b, threads, ok, ok_each);
+        std::vector<uint64_t> made;
+        zk::vb_host(key, zk::VbBatch{zk::vb_form_expand(key, form, k, nullptr, made), proofs, inf, rho, k}, threads, ok, ok_each);
     } catch (const std::bad_alloc &) {
         return ZKG16_ERR_OOM;
     }
     return ZKG16_OK;
+}
+
+int zkg16_verify_batch_host(const uint64_t *gamma_abc_g1, size_t num_instance, const uint64_t alpha_beta[72], const uint64_t *gamma_neg_coeffs,
+                            const uint64_t *delta_neg_coeffs, size_t n_coeffs, const uint64_t *public_inputs, const uint64_t *proofs, const uint8_t *inf,
+                            const uint64_t *rho, size_t k, int threads, int *ok, uint8_t *ok_each) {
+    const zk::VbKey key{gamma_abc_g1, num_instance, alpha_beta, gamma_neg_coeffs, delta_neg_coeffs, n_coeffs};
+    return vb_host_entry(key, zk::vb_limbs(public_inputs), proofs, inf, rho, k, threads, ok, ok_each);
 }
 
 // ---- the prime form (verify_batch.hpp): one extended key for every request of a trapdoor
@@ -1246,40 +1252,16 @@ int zkg16_prime_ext_inputs(uint64_t x, uint64_t j, uint64_t *out) {
 int zkg16_verify_prime_batch_host(const uint64_t *gamma_abc_g1, size_t num_instance, const uint64_t alpha_beta[72], const uint64_t *gamma_neg_coeffs,
                                   const uint64_t *delta_neg_coeffs, size_t n_coeffs, const uint64_t *xs, const uint64_t *js, const uint64_t *proofs,
                                   const uint8_t *inf, const uint64_t *rho, size_t k, int threads, int *ok, uint8_t *ok_each) {
-    if (num_instance != 260 || !xs || !js || threads < 0 || k >> 32) return ZKG16_ERR_BAD_ARG;
     const zk::VbKey key{gamma_abc_g1, num_instance, alpha_beta, gamma_neg_coeffs, delta_neg_coeffs, n_coeffs};
-    {
-        const int rc = zk::vb_check_args(key, zk::VbBatch{xs, proofs, inf, rho, k}, ok);      // xs stands in for the inputs made below
-        if (rc != ZKG16_OK) return rc;
-    }
-    try {
-        std::vector<uint64_t> pub(4 * 259 * k);
-        for (size_t i = 0; i < k; i++) (void)zkg16_prime_ext_inputs(xs[i], js[i], pub.data() + 4 * 259 * i);      // fails on a null pointer only
-        zk::vb_host(key, zk::VbBatch{pub.data(), proofs, inf, rho, k}, threads, ok, ok_each);
-    } catch (const std::bad_alloc &) {
-        return ZKG16_ERR_OOM;
-    }
-    return ZKG16_OK;
+    return vb_host_entry(key, zk::vb_prime(xs, js), proofs, inf, rho, k, threads, ok, ok_each);
 }
 
-// ---- the u64 form (verify_batch.hpp): public inputs that are plain 64-bit values, expanded here
+// ---- the u64 form (verify_batch.hpp): public inputs that are plain 64-bit values
 int zkg16_verify_batch_u64_host(const uint64_t *gamma_abc_g1, size_t num_instance, const uint64_t alpha_beta[72], const uint64_t *gamma_neg_coeffs,
                                 const uint64_t *delta_neg_coeffs, size_t n_coeffs, const uint64_t *values, const uint64_t *proofs, const uint8_t *inf,
                                 const uint64_t *rho, size_t k, int threads, int *ok, uint8_t *ok_each) {
-    if (num_instance < 2 || !values || threads < 0 || k >> 32) return ZKG16_ERR_BAD_ARG;
     const zk::VbKey key{gamma_abc_g1, num_instance, alpha_beta, gamma_neg_coeffs, delta_neg_coeffs, n_coeffs};
-    {
-        const int rc = zk::vb_check_args(key, zk::VbBatch{values, proofs, inf, rho, k}, ok);      // values stand in for the inputs made below
-        if (rc != ZKG16_OK) return rc;
-    }
-    try {
-        std::vector<uint64_t> pub(4 * (num_instance - 1) * k);
-        zk::vb_u64_expand(values, (num_instance - 1) * k, pub.data());
-        zk::vb_host(key, zk::VbBatch{pub.data(), proofs, inf, rho, k}, threads, ok, ok_each);
-    } catch (const std::bad_alloc &) {
-        return ZKG16_ERR_OOM;
-    }
-    return ZKG16_OK;
+    return vb_host_entry(key, zk::vb_u64(values), proofs, inf, rho, k, threads, ok, ok_each);
 }
 
 // the final exponentiation of the verifier (f^(3 (q^12 - 1)/r), pairing_fast.inc) of one Fq12 value in the ABI's tower order

@@ -1,5 +1,5 @@
-// Batched Groth16 verification: what verify.hip (host arithmetic), verify_batch.hip (kernels) and api_verify.hip (entry points on a lane of
-// the ctx) share.  K proofs under one prepared key hold iff, for multipliers rho_k nobody could predict (error 2^-128),
+// Batched Groth16 verification: what verify.hip (host arithmetic), verify_batch.hip (kernels), api_verify.hip and api_rerandomize.hip
+// (entry points on a lane of the ctx) share.  K proofs under one prepared key hold iff, for multipliers rho_k nobody could predict (error 2^-128),
 //
 //     FE( prod_k ML(rho_k A_k, B_k) * ML(sum_k rho_k X_k, -gamma) * ML(sum_k rho_k C_k, -delta) ) == e(alpha, beta)^(sum_k rho_k)
 //
@@ -10,7 +10,11 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <functional>
+#include <system_error>
+#include <thread>
+#include <vector>
 
 #include <hip/hip_runtime.h>
 
@@ -31,8 +35,55 @@ struct VbBatch {
     const uint64_t *rho;                // k x 2
     size_t k;
 };
-// the argument checks every batch entry point makes before any work
-int vb_check_args(const VbKey &key, const VbBatch &b, const int *ok);
+// Where the public inputs of a batch come from: the kind, the host pointers of that kind, and the device copies the later stages
+// read, filled in once they are uploaded.
+//   Limbs: public_inputs as in VbBatch (nullable when num_instance == 1).
+//   Prime: K requests of one trapdoor under the extended key of 260 points (zkg16_prime_vk_extend); xs, js [k], and d_dig the
+//          digests the inputs kernel made of them.
+//   U64:   a key of num_instance >= 2 whose inputs are plain 64-bit values; values k x (num_instance - 1), row-major.
+enum class VbKind { Limbs, Prime, U64 };
+struct VbForm {
+    VbKind kind = VbKind::Limbs;
+    const uint64_t *public_inputs = nullptr;
+    const uint64_t *xs = nullptr, *js = nullptr;
+    const uint64_t *values = nullptr;
+    const uint64_t *d_xs = nullptr, *d_js = nullptr, *d_values = nullptr;
+    const uint32_t *d_dig = nullptr;
+};
+inline VbForm vb_limbs(const uint64_t *public_inputs) { return VbForm{VbKind::Limbs, public_inputs}; }
+inline VbForm vb_prime(const uint64_t *xs, const uint64_t *js) { return VbForm{VbKind::Prime, nullptr, xs, js}; }
+inline VbForm vb_u64(const uint64_t *values) { return VbForm{VbKind::U64, nullptr, nullptr, nullptr, values}; }
+// The argument checks every entry point makes before any work, each caller naming what it has: the key and the form's inputs for
+// k proofs (k == 0, a key the form does not fit and k >= 2^32 where the kernels index by 32 bits are refused here) ...
+int vb_check_batch(const VbKey &key, const VbForm &form, size_t k);
+// ... and k multipliers, for the entry points that take them; vb_check_batch comes first (it bounds k)
+int vb_check_rho(const uint64_t *rho, size_t k);
+// The form's inputs as k x (num_instance - 1) x 4 Montgomery limbs: the caller's own for Limbs, else made in `made`.  digests
+// (Prime, nullable): k x 8 words as the inputs kernel writes them; null: hashed here (zkg16_prime_ext_inputs)
+const uint64_t *vb_form_expand(const VbKey &key, const VbForm &form, size_t k, const uint32_t *digests, std::vector<uint64_t> &made);
+
+// fn(lo, hi) over [0, n) on up to `threads` host threads (0 = 8), at least min_per items each; a thread that cannot be started runs inline
+template <class Fn>
+void vb_parallel(size_t n, int threads, size_t min_per, Fn fn) {
+    size_t nt = threads <= 0 ? 8 : (size_t)threads;
+    if (min_per && n / min_per < nt) nt = n / min_per;
+    if (nt <= 1) { if (n) fn((size_t)0, n); return; }
+    struct Joiner {
+        std::vector<std::thread> th;
+        ~Joiner() { for (auto &t : th) if (t.joinable()) t.join(); }
+    } tg;
+    const size_t per = (n + nt - 1) / nt;
+    for (size_t t = 0; t < nt; t++) {
+        const size_t lo = t * per, hi = std::min(n, lo + per);
+        if (lo >= hi) break;
+        auto job = [lo, hi, &fn] { fn(lo, hi); };
+        try {
+            tg.th.emplace_back(job);
+        } catch (const std::system_error &) {
+            job();
+        }
+    }
+}
 
 // ---- verify.hip
 // The batch's verdicts from its per-proof parts: member[k] != 0 iff A_k, B_k, C_k passed membership; prod (nullable, 72 u64): the

@@ -565,17 +565,36 @@ class Device:
         self.last_trapdoor_ms = dict(zip(("qap_ms", "check_ms", "dot_ms", "points_ms", "call_ms"), (float(x) for x in ms)))
         return proofs, inf, vk
 
-    # ---- batched verification
+    # ---- batched verification: one body per shape of entry point, whatever the form of the public inputs (_verify_args)
+    def _verify_limbs(self, entry, pvk, kind, inputs, proofs, infs, rho, each):
+        args, k = _verify_args(pvk, kind, inputs, proofs, infs, rho)
+        ok = C.c_int(0)
+        ok_each = np.zeros(k, dtype=np.uint8) if each else None
+        self._check(getattr(self.lib, "zkg16_" + entry)(self.ctx, *args, C.byref(ok), _ptr(ok_each)))
+        return _verify_result(ok, ok_each)
+
+    def _verify_wire(self, entry, pvk, kind, inputs, proof_bytes, rho, each, status):
+        raw, k = _wire_bytes(entry, proof_bytes)
+        args, _ = _verify_args(pvk, kind, inputs, None, None, rho, k=k)
+        ok = C.c_int(0)
+        ok_each = np.zeros(k, dtype=np.uint8) if each else None
+        st = np.zeros((k, 3), dtype=np.uint8) if status else None
+        # the bytes in the place of the limbs and flags
+        self._check(getattr(self.lib, "zkg16_" + entry)(self.ctx, *args[:-4], _ptr(raw) if k else None, args[-2], k, C.byref(ok), _ptr(ok_each), _ptr(st)))
+        return _verify_result(ok, ok_each, st)
+
+    def _verify_each(self, entry, pvk, kind, inputs, proofs, infs):
+        args, k = _verify_args(pvk, kind, inputs, proofs, infs, np.ones((_u64(proofs).reshape(-1, 48).shape[0], 2), dtype=np.uint64))
+        ok_each = np.zeros(k, dtype=np.uint8)
+        self._check(getattr(self.lib, "zkg16_" + entry)(self.ctx, *args[:-2], k, _ptr(ok_each)))      # no multipliers
+        return ok_each.astype(bool)
+
     def verify_batch(self, pvk, public_inputs, proofs, infs, rho=None, each=False):
         """K proofs under one prepared key checked together, the per-proof work in kernels (zkg16_verify_batch): public_inputs
         [k, num_instance - 1, 4] Montgomery, proofs [k, 48], infs [k, 3]; rho [k, 2]: 128-bit non-zero multipliers that whoever
         made the proofs could not predict (None: drawn from `secrets`).  -> all_valid, or (all_valid, per-proof bool array) with
         each=True.  Batches shorter than the option "verify_batch_min" are answered by the host form."""
-        args, k = _verify_batch_args(pvk, public_inputs, proofs, infs, rho)
-        ok = C.c_int(0)
-        ok_each = np.zeros(k, dtype=np.uint8) if each else None
-        self._check(self.lib.zkg16_verify_batch(self.ctx, *args, C.byref(ok), _ptr(ok_each)))
-        return (bool(ok.value), ok_each.astype(bool)) if each else bool(ok.value)
+        return self._verify_limbs("verify_batch", pvk, "limbs", (public_inputs,), proofs, infs, rho, each)
 
     def verify_batch_wire(self, pvk, public_inputs, proof_bytes, rho=None, each=False, status=False):
         """verify_batch from the proofs as they travel (zkg16_verify_batch_wire): proof_bytes = k x 192 compressed bytes (bytes, or
@@ -583,55 +602,24 @@ class Device:
         -> all_valid, followed by the per-proof bool array with each=True and by the [k, 3] decode statuses (A, B, C: 0 ok ... 5
         not in the subgroup, as the validating host decoder reports them) with status=True.  Batches shorter than the option
         "verify_wire_min" are decoded and answered on the host."""
-        raw = np.ascontiguousarray(np.frombuffer(proof_bytes, dtype=np.uint8) if isinstance(proof_bytes, (bytes, bytearray, memoryview))
-                                   else np.asarray(proof_bytes, dtype=np.uint8)).reshape(-1)
-        if raw.size % 192:
-            raise ValueError("verify_batch_wire: a compressed proof is 192 bytes")
-        k = raw.size // 192
-        args, _ = _verify_batch_args(pvk, public_inputs, None, None, rho, k=k)
-        ok = C.c_int(0)
-        ok_each = np.zeros(k, dtype=np.uint8) if each else None
-        st = np.zeros((k, 3), dtype=np.uint8) if status else None
-        self._check(self.lib.zkg16_verify_batch_wire(self.ctx, *args[:7], _ptr(raw) if k else None, args[9], k, C.byref(ok), _ptr(ok_each), _ptr(st)))
-        out = (bool(ok.value),) + ((ok_each.astype(bool),) if each else ()) + ((st,) if status else ())
-        return out if len(out) > 1 else out[0]
+        return self._verify_wire("verify_batch_wire", pvk, "limbs", (public_inputs,), proof_bytes, rho, each, status)
 
     def verify_each(self, pvk, public_inputs, proofs, infs):
         """What verify_prepared says of each of K proofs under one prepared key, in one device pass (zkg16_verify_each; arguments as
         verify_batch, no multipliers) -> bool array [k].  The cost does not depend on how many of the proofs are bad."""
-        args, k = _verify_batch_args(pvk, public_inputs, proofs, infs, np.ones((_u64(proofs).reshape(-1, 48).shape[0], 2), dtype=np.uint64))
-        ok_each = np.zeros(k, dtype=np.uint8)
-        self._check(self.lib.zkg16_verify_each(self.ctx, *args[:9], k, _ptr(ok_each)))
-        return ok_each.astype(bool)
+        return self._verify_each("verify_each", pvk, "limbs", (public_inputs,), proofs, infs)
 
     # ---- the prime form: K prime requests of one trapdoor under the extended key (circuits.prime_vk_extend)
     def verify_prime_batch(self, pvk, xs, js, proofs, infs, rho=None, each=False):
         """verify_batch for K proofs of the prime handler made under one trapdoor (zkg16_verify_prime_batch): pvk = the prepared
         extended key (260 gamma_abc_g1 points), xs / js [k] u64; the 259 public inputs of each proof and the multiplier sums of the
         batch equation are made on the device from those 16 bytes.  Everything else as verify_batch."""
-        xs, js = _u64(xs).reshape(-1), _u64(js).reshape(-1)
-        args, k = _verify_prime_args(pvk, xs, js, proofs, infs, rho)
-        ok = C.c_int(0)
-        ok_each = np.zeros(k, dtype=np.uint8) if each else None
-        self._check(self.lib.zkg16_verify_prime_batch(self.ctx, *args, C.byref(ok), _ptr(ok_each)))
-        return (bool(ok.value), ok_each.astype(bool)) if each else bool(ok.value)
+        return self._verify_limbs("verify_prime_batch", pvk, "prime", (xs, js), proofs, infs, rho, each)
 
     def verify_prime_batch_wire(self, pvk, xs, js, proof_bytes, rho=None, each=False, status=False):
         """verify_batch_wire for the prime form (zkg16_verify_prime_batch_wire): proof_bytes = k x 192 compressed bytes; rho is
         drawn from `secrets` when None.  Returns as verify_batch_wire."""
-        raw = np.ascontiguousarray(np.frombuffer(proof_bytes, dtype=np.uint8) if isinstance(proof_bytes, (bytes, bytearray, memoryview))
-                                   else np.asarray(proof_bytes, dtype=np.uint8)).reshape(-1)
-        if raw.size % 192:
-            raise ValueError("verify_prime_batch_wire: a compressed proof is 192 bytes")
-        k = raw.size // 192
-        xs, js = _u64(xs).reshape(-1), _u64(js).reshape(-1)
-        args, _ = _verify_prime_args(pvk, xs, js, None, None, rho, k=k)
-        ok = C.c_int(0)
-        ok_each = np.zeros(k, dtype=np.uint8) if each else None
-        st = np.zeros((k, 3), dtype=np.uint8) if status else None
-        self._check(self.lib.zkg16_verify_prime_batch_wire(self.ctx, *args[:8], _ptr(raw) if k else None, args[10], k, C.byref(ok), _ptr(ok_each), _ptr(st)))
-        out = (bool(ok.value),) + ((ok_each.astype(bool),) if each else ()) + ((st,) if status else ())
-        return out if len(out) > 1 else out[0]
+        return self._verify_wire("verify_prime_batch_wire", pvk, "prime", (xs, js), proof_bytes, rho, each, status)
 
     def prime_inputs_batch(self, xs, js, public_inputs=False):
         """The inputs kernel by itself (zkg16_prime_inputs_batch) -> (digests [k, 32] u8, n [k] u32), followed by the
@@ -666,34 +654,16 @@ class Device:
         uint64 in the place of the Montgomery limbs; the multiplier sums, sum_i s_i gamma_abc[i] and, when the per-proof pass runs,
         each proof's prepared input are made on the device from them.  With the option "verify_each_after" unset that pass decides
         every proof right after a failed test of the whole batch.  Everything else as verify_batch."""
-        args, k = _verify_u64_args(pvk, values, proofs, infs, rho)
-        ok = C.c_int(0)
-        ok_each = np.zeros(k, dtype=np.uint8) if each else None
-        self._check(self.lib.zkg16_verify_batch_u64(self.ctx, *args, C.byref(ok), _ptr(ok_each)))
-        return (bool(ok.value), ok_each.astype(bool)) if each else bool(ok.value)
+        return self._verify_limbs("verify_batch_u64", pvk, "u64", (values,), proofs, infs, rho, each)
 
     def verify_batch_u64_wire(self, pvk, values, proof_bytes, rho=None, each=False, status=False):
         """verify_batch_wire for the u64 form (zkg16_verify_batch_u64_wire): proof_bytes = k x 192 compressed bytes; rho is drawn
         from `secrets` when None.  Returns as verify_batch_wire."""
-        raw = np.ascontiguousarray(np.frombuffer(proof_bytes, dtype=np.uint8) if isinstance(proof_bytes, (bytes, bytearray, memoryview))
-                                   else np.asarray(proof_bytes, dtype=np.uint8)).reshape(-1)
-        if raw.size % 192:
-            raise ValueError("verify_batch_u64_wire: a compressed proof is 192 bytes")
-        k = raw.size // 192
-        args, _ = _verify_u64_args(pvk, values, None, None, rho, k=k)
-        ok = C.c_int(0)
-        ok_each = np.zeros(k, dtype=np.uint8) if each else None
-        st = np.zeros((k, 3), dtype=np.uint8) if status else None
-        self._check(self.lib.zkg16_verify_batch_u64_wire(self.ctx, *args[:7], _ptr(raw) if k else None, args[9], k, C.byref(ok), _ptr(ok_each), _ptr(st)))
-        out = (bool(ok.value),) + ((ok_each.astype(bool),) if each else ()) + ((st,) if status else ())
-        return out if len(out) > 1 else out[0]
+        return self._verify_wire("verify_batch_u64_wire", pvk, "u64", (values,), proof_bytes, rho, each, status)
 
     def verify_each_u64(self, pvk, values, proofs, infs):
         """verify_each for the u64 form (zkg16_verify_each_u64) -> bool array [k]."""
-        args, k = _verify_u64_args(pvk, values, proofs, infs, np.ones((_u64(proofs).reshape(-1, 48).shape[0], 2), dtype=np.uint64))
-        ok_each = np.zeros(k, dtype=np.uint8)
-        self._check(self.lib.zkg16_verify_each_u64(self.ctx, *args[:9], k, _ptr(ok_each)))
-        return ok_each.astype(bool)
+        return self._verify_each("verify_each_u64", pvk, "u64", (values,), proofs, infs)
 
     def u64_rho_sums(self, values, rho, live=None):
         """The u64 form's sums kernels by themselves (zkg16_u64_rho_sums): values [k, m] uint64, rho [k, 2], live [k] bytes or None
@@ -770,11 +740,7 @@ class Device:
         and encoding (zkg16_rerandomize_batch_wire) -> (bytes [k, 192] uint8, statuses [k, 3]).  A proof with a point that does not
         decode or is not in the subgroup has its status set (1 .. 5, as verify_batch_wire's) and 192 zero bytes; the others are
         unaffected.  status=False: only the bytes, and such a proof raises."""
-        raw = np.ascontiguousarray(np.frombuffer(proof_bytes, dtype=np.uint8) if isinstance(proof_bytes, (bytes, bytearray, memoryview))
-                                   else np.asarray(proof_bytes, dtype=np.uint8)).reshape(-1)
-        if raw.size % 192:
-            raise ValueError("rerandomize_batch_wire: a compressed proof is 192 bytes")
-        k = raw.size // 192
+        raw, k = _wire_bytes("rerandomize_batch_wire", proof_bytes)
         delta, r1, r2 = _rerandomize_args(vk_or_delta, k, r1, r2)
         out = np.zeros((k, 192), dtype=np.uint8)
         st = np.zeros((k, 3), dtype=np.uint8) if status else None
@@ -1347,93 +1313,6 @@ def rerandomize_batch_host(vk_or_delta, proofs, inf=None, r1=None, r2=None, thre
     return out, oinf
 
 
-def _verify_batch_args(pvk, public_inputs, proofs, infs, rho, k=None):
-    """the argument tuple the batch entry points share; proofs = infs = None with k given: the wire form, which has no limbs yet"""
-    gabc = _u64(pvk["gamma_abc_g1"]).reshape(-1, 12)
-    proofs = _u64(proofs).reshape(-1, 48) if proofs is not None else None
-    k = proofs.shape[0] if proofs is not None else k
-    infs = np.ascontiguousarray(infs, dtype=np.uint8).reshape(-1, 3) if proofs is not None else None
-    pub = _u64(public_inputs)
-    # (k, -1, 4) cannot be inferred for an empty array: no proofs, or a key with one instance variable and so no inputs
-    pub = pub.reshape(k, -1, 4) if pub.size else pub.reshape(k, 0 if k else gabc.shape[0] - 1, 4)
-    if pub.shape[1] != gabc.shape[0] - 1:
-        raise ValueError("verify_batch: %d public inputs per proof for a key with %d instance variables" % (pub.shape[1], gabc.shape[0]))
-    if infs is not None and infs.shape[0] != k:
-        raise ValueError("verify_batch: one flag triple per proof")
-    rho = draw_rho(k) if rho is None else _u64(rho).reshape(-1, 2)
-    if rho.shape[0] != k:
-        raise ValueError("verify_batch: one multiplier per proof")
-    g, d = _u64(pvk["gamma_neg_pc"]).reshape(-1, 36), _u64(pvk["delta_neg_pc"]).reshape(-1, 36)
-    ab = _u64(pvk["alpha_beta"])
-    # the arrays must outlive the call: they travel in the tuple
-    keep = (gabc, ab, g, d, pub, proofs, infs, rho)
-    return _KeepAlive((_ptr(gabc), gabc.shape[0], _ptr(ab), _ptr(g), _ptr(d), g.shape[0], _ptr(pub) if pub.size else None, _ptr(proofs), _ptr(infs),
-                       _ptr(rho), k), keep), k
-
-
-def _verify_prime_args(pvk, xs, js, proofs, infs, rho, k=None):
-    """_verify_batch_args for the prime form: xs, js [k] in the place of the public inputs"""
-    gabc = _u64(pvk["gamma_abc_g1"]).reshape(-1, 12)
-    proofs = _u64(proofs).reshape(-1, 48) if proofs is not None else None
-    k = proofs.shape[0] if proofs is not None else k
-    infs = np.ascontiguousarray(infs, dtype=np.uint8).reshape(-1, 3) if proofs is not None else None
-    if xs.shape[0] != k or js.shape[0] != k:
-        raise ValueError("verify_prime_batch: one x and one j per proof")
-    if infs is not None and infs.shape[0] != k:
-        raise ValueError("verify_prime_batch: one flag triple per proof")
-    rho = draw_rho(k) if rho is None else _u64(rho).reshape(-1, 2)
-    if rho.shape[0] != k:
-        raise ValueError("verify_prime_batch: one multiplier per proof")
-    g, d = _u64(pvk["gamma_neg_pc"]).reshape(-1, 36), _u64(pvk["delta_neg_pc"]).reshape(-1, 36)
-    ab = _u64(pvk["alpha_beta"])
-    keep = (gabc, ab, g, d, xs, js, proofs, infs, rho)
-    return _KeepAlive((_ptr(gabc), gabc.shape[0], _ptr(ab), _ptr(g), _ptr(d), g.shape[0], _ptr(xs) if k else None, _ptr(js) if k else None, _ptr(proofs),
-                       _ptr(infs), _ptr(rho), k), keep), k
-
-
-def _verify_u64_args(pvk, values, proofs, infs, rho, k=None):
-    """_verify_batch_args for the u64 form: values [k, num_instance - 1] uint64 in the place of the public inputs"""
-    gabc = _u64(pvk["gamma_abc_g1"]).reshape(-1, 12)
-    proofs = _u64(proofs).reshape(-1, 48) if proofs is not None else None
-    k = proofs.shape[0] if proofs is not None else k
-    infs = np.ascontiguousarray(infs, dtype=np.uint8).reshape(-1, 3) if proofs is not None else None
-    values = _u64(values)
-    if gabc.shape[0] < 2 or values.shape != (k, gabc.shape[0] - 1):
-        raise ValueError("verify_batch_u64: values is [k, num_instance - 1] for a key with at least two instance variables")
-    if infs is not None and infs.shape[0] != k:
-        raise ValueError("verify_batch_u64: one flag triple per proof")
-    rho = draw_rho(k) if rho is None else _u64(rho).reshape(-1, 2)
-    if rho.shape[0] != k:
-        raise ValueError("verify_batch_u64: one multiplier per proof")
-    g, d = _u64(pvk["gamma_neg_pc"]).reshape(-1, 36), _u64(pvk["delta_neg_pc"]).reshape(-1, 36)
-    ab = _u64(pvk["alpha_beta"])
-    keep = (gabc, ab, g, d, values, proofs, infs, rho)
-    return _KeepAlive((_ptr(gabc), gabc.shape[0], _ptr(ab), _ptr(g), _ptr(d), g.shape[0], _ptr(values) if k else None, _ptr(proofs), _ptr(infs), _ptr(rho), k),
-                      keep), k
-
-
-def verify_batch_u64_host(pvk, values, proofs, infs, rho=None, each=False, threads=0):
-    """Device.verify_batch_u64's verdicts on host threads alone (zkg16_verify_batch_u64_host; threads 0 = 8; no GPU): the values are
-    expanded to Montgomery limbs and verify_batch_host answers."""
-    lib = _lib.load()
-    args, k = _verify_u64_args(pvk, values, proofs, infs, rho)
-    ok = C.c_int(0)
-    ok_each = np.zeros(k, dtype=np.uint8) if each else None
-    _check_host(lib.zkg16_verify_batch_u64_host(*args, threads, C.byref(ok), _ptr(ok_each)))
-    return (bool(ok.value), ok_each.astype(bool)) if each else bool(ok.value)
-
-
-def verify_prime_batch_host(pvk, xs, js, proofs, infs, rho=None, each=False, threads=0):
-    """Device.verify_prime_batch's verdicts on host threads alone (zkg16_verify_prime_batch_host; threads 0 = 8; no GPU)."""
-    lib = _lib.load()
-    xs, js = _u64(xs).reshape(-1), _u64(js).reshape(-1)
-    args, k = _verify_prime_args(pvk, xs, js, proofs, infs, rho)
-    ok = C.c_int(0)
-    ok_each = np.zeros(k, dtype=np.uint8) if each else None
-    _check_host(lib.zkg16_verify_prime_batch_host(*args, threads, C.byref(ok), _ptr(ok_each)))
-    return (bool(ok.value), ok_each.astype(bool)) if each else bool(ok.value)
-
-
 class _KeepAlive(tuple):
     def __new__(cls, items, keep):
         self = super().__new__(cls, items)
@@ -1441,14 +1320,86 @@ class _KeepAlive(tuple):
         return self
 
 
-def verify_batch_host(pvk, public_inputs, proofs, infs, rho=None, each=False, threads=0):
-    """Device.verify_batch's verdicts on host threads alone (zkg16_verify_batch_host; threads 0 = 8; no GPU)."""
+_VERIFY_FORMS = {"limbs": "verify_batch", "prime": "verify_prime_batch", "u64": "verify_batch_u64"}
+
+
+def _verify_args(pvk, kind, inputs, proofs, infs, rho, k=None):
+    """The argument tuple the verification entry points share: the key (6), the form's inputs, proofs, infs, rho, k.  kind / inputs:
+    "limbs" / (public_inputs [k, num_instance - 1, 4],), "prime" / (xs [k], js [k]) or "u64" / (values [k, num_instance - 1],).
+    proofs = infs = None with k given: the wire form, which has no limbs yet"""
+    who = _VERIFY_FORMS[kind]
+    gabc = _u64(pvk["gamma_abc_g1"]).reshape(-1, 12)
+    proofs = _u64(proofs).reshape(-1, 48) if proofs is not None else None
+    k = proofs.shape[0] if proofs is not None else k
+    infs = np.ascontiguousarray(infs, dtype=np.uint8).reshape(-1, 3) if proofs is not None else None
+    if kind == "limbs":
+        pub = _u64(inputs[0])
+        # (k, -1, 4) cannot be inferred for an empty array: no proofs, or a key with one instance variable and so no inputs
+        pub = pub.reshape(k, -1, 4) if pub.size else pub.reshape(k, 0 if k else gabc.shape[0] - 1, 4)
+        if pub.shape[1] != gabc.shape[0] - 1:
+            raise ValueError("verify_batch: %d public inputs per proof for a key with %d instance variables" % (pub.shape[1], gabc.shape[0]))
+        inputs, there = (pub,), pub.size
+    elif kind == "prime":
+        inputs = tuple(_u64(a).reshape(-1) for a in inputs)
+        if inputs[0].shape[0] != k or inputs[1].shape[0] != k:
+            raise ValueError("verify_prime_batch: one x and one j per proof")
+        there = k
+    else:
+        inputs = (_u64(inputs[0]),)
+        if gabc.shape[0] < 2 or inputs[0].shape != (k, gabc.shape[0] - 1):
+            raise ValueError("verify_batch_u64: values is [k, num_instance - 1] for a key with at least two instance variables")
+        there = k
+    if infs is not None and infs.shape[0] != k:
+        raise ValueError("%s: one flag triple per proof" % who)
+    rho = draw_rho(k) if rho is None else _u64(rho).reshape(-1, 2)
+    if rho.shape[0] != k:
+        raise ValueError("%s: one multiplier per proof" % who)
+    g, d = _u64(pvk["gamma_neg_pc"]).reshape(-1, 36), _u64(pvk["delta_neg_pc"]).reshape(-1, 36)
+    ab = _u64(pvk["alpha_beta"])
+    # the arrays must outlive the call: they travel in the tuple
+    keep = (gabc, ab, g, d) + inputs + (proofs, infs, rho)
+    return _KeepAlive((_ptr(gabc), gabc.shape[0], _ptr(ab), _ptr(g), _ptr(d), g.shape[0]) + tuple(_ptr(a) if there else None for a in inputs)
+                      + (_ptr(proofs), _ptr(infs), _ptr(rho), k), keep), k
+
+
+def _wire_bytes(who, proof_bytes):
+    """k x 192 compressed proof bytes (bytes, bytearray, memoryview or a uint8 array) -> (the bytes as a flat uint8 array, k)"""
+    raw = np.ascontiguousarray(np.frombuffer(proof_bytes, dtype=np.uint8) if isinstance(proof_bytes, (bytes, bytearray, memoryview))
+                               else np.asarray(proof_bytes, dtype=np.uint8)).reshape(-1)
+    if raw.size % 192:
+        raise ValueError("%s: a compressed proof is 192 bytes" % who)
+    return raw, raw.size // 192
+
+
+def _verify_result(ok, ok_each=None, status=None):
+    """all_valid, followed by the per-proof bool array and the decode statuses where the caller asked for them"""
+    out = (bool(ok.value),) + (() if ok_each is None else (ok_each.astype(bool),)) + (() if status is None else (status,))
+    return out if len(out) > 1 else out[0]
+
+
+def _verify_host(entry, pvk, kind, inputs, proofs, infs, rho, each, threads):
     lib = _lib.load()
-    args, k = _verify_batch_args(pvk, public_inputs, proofs, infs, rho)
+    args, k = _verify_args(pvk, kind, inputs, proofs, infs, rho)
     ok = C.c_int(0)
     ok_each = np.zeros(k, dtype=np.uint8) if each else None
-    _check_host(lib.zkg16_verify_batch_host(*args, threads, C.byref(ok), _ptr(ok_each)))
-    return (bool(ok.value), ok_each.astype(bool)) if each else bool(ok.value)
+    _check_host(getattr(lib, entry)(*args, threads, C.byref(ok), _ptr(ok_each)))
+    return _verify_result(ok, ok_each)
+
+
+def verify_batch_u64_host(pvk, values, proofs, infs, rho=None, each=False, threads=0):
+    """Device.verify_batch_u64's verdicts on host threads alone (zkg16_verify_batch_u64_host; threads 0 = 8; no GPU): the values are
+    expanded to Montgomery limbs and verify_batch_host answers."""
+    return _verify_host("zkg16_verify_batch_u64_host", pvk, "u64", (values,), proofs, infs, rho, each, threads)
+
+
+def verify_prime_batch_host(pvk, xs, js, proofs, infs, rho=None, each=False, threads=0):
+    """Device.verify_prime_batch's verdicts on host threads alone (zkg16_verify_prime_batch_host; threads 0 = 8; no GPU)."""
+    return _verify_host("zkg16_verify_prime_batch_host", pvk, "prime", (xs, js), proofs, infs, rho, each, threads)
+
+
+def verify_batch_host(pvk, public_inputs, proofs, infs, rho=None, each=False, threads=0):
+    """Device.verify_batch's verdicts on host threads alone (zkg16_verify_batch_host; threads 0 = 8; no GPU)."""
+    return _verify_host("zkg16_verify_batch_host", pvk, "limbs", (public_inputs,), proofs, infs, rho, each, threads)
 
 
 def final_exp(f):
