@@ -1,7 +1,9 @@
 """The request path of handlers.py on a fake Device (no GPU, only the library's host entry points): every device handle a
 request obtains is released on every way out, the assignment thread never outlives its request, the draws from the PRNG keep their
 order, the assignment of a cached shape still starts beside the setup, two first requests of one size make one R1CS, and the
-verify handlers answer invalid for what cannot be decoded but raise for what is the service's trouble."""
+verify handlers answer invalid for what cannot be decoded but raise for what is the service's trouble.  The batch handlers are pinned
+on every path they have: their own key, a caller's key, check_on_device, the trapdoor route, and a refused trapdoor batch redone on
+the key route."""
 import base64
 import random
 import threading
@@ -12,6 +14,7 @@ import pytest
 
 from helpers import fr_mont
 from zksnark_finalproject_amd import Zkg16Error, device, handlers, wire
+from zksnark_finalproject_amd._lib import ZKG16_ERR_UNSATISFIED
 from zksnark_finalproject_amd.workloads import R_MOD, g1_generator, g2_generator
 
 _G1, _G2 = g1_generator(), g2_generator()
@@ -34,9 +37,11 @@ def fake_vk(num_instance):
 class FakeDevice:
     """The Device methods the handlers call.  Hands out fresh handle numbers and keeps the set of live ones; records every call
     with its arguments; raises `exc` at the fail_at-th call since arm().  The *_free calls are recorded but neither counted nor
-    failed: on the real Device they return nothing.  A free of a handle that is not live, or a proof on one, is an AssertionError."""
+    failed: on the real Device they return nothing.  A free of a handle that is not live, or a proof on one, is an AssertionError.
+    refuse_trapdoor: prove_trapdoor_batch answers as the library does for an unsatisfied assignment (Zkg16Error, status 8)."""
 
-    def __init__(self, wait_for_assignment=False, r1cs_matrix_sleep=0.0):
+    def __init__(self, wait_for_assignment=False, r1cs_matrix_sleep=0.0, refuse_trapdoor=False):
+        self.refuse_trapdoor = refuse_trapdoor
         self._matrix_shapes = {}
         self._matrix_shapes_lock = threading.Lock()
         self._mu = threading.Lock()
@@ -87,6 +92,14 @@ class FakeDevice:
         time.sleep(self.r1cs_matrix_sleep)
         return self._new("r1cs")
 
+    def r1cs_fibonacci(self, steps):
+        self._call("r1cs_fibonacci", steps)
+        return self._new("r1cs")
+
+    def r1cs_linear(self, n):
+        self._call("r1cs_linear", n)
+        return self._new("r1cs")
+
     def r1cs_prime(self, x, j):
         self._call("r1cs_prime", x, j)
         return self._new("r1cs")
@@ -113,8 +126,35 @@ class FakeDevice:
         self._call("witness_prime", x, j)
         return self._new("witness")
 
+    def _witness_batch(self, name, args, side):
+        """A failed call registers nothing, as the library's all-or-nothing entries."""
+        self._call(name, *args)
+        return np.array([self._new("witness") for _ in range(side.shape[0])], dtype=np.uint64), side, {}
+
+    def witness_matrix_batch(self, a, b):
+        return self._witness_batch("witness_matrix_batch", (a, b), np.zeros((a.shape[0], 3, 4), dtype=np.uint64))
+
+    def witness_fibonacci_batch(self, steps, a, b):
+        return self._witness_batch("witness_fibonacci_batch", (steps, a, b), np.zeros((a.shape[0], 3, 4), dtype=np.uint64))
+
+    def witness_linear_batch(self, a, b, solver=None):
+        return self._witness_batch("witness_linear_batch", (a, b), np.zeros(b.shape + (4,), dtype=np.uint64))
+
     def witness_free(self, h):
         self._free("witness_free", "witness", h)
+
+    # satisfaction: every assignment satisfied
+    def r1cs_check_batch(self, r1cs_h, witness_handles):
+        self._call("r1cs_check_batch", r1cs_h, witness_handles)
+        self._is("r1cs", r1cs_h)
+        for wh in witness_handles:
+            self._is("witness", int(wh))
+        return [(0, 2 ** 64 - 1)] * len(witness_handles)
+
+    def prime_check_batch(self, r1cs_h, xs, js):
+        self._call("prime_check_batch", r1cs_h, xs, js)
+        self._is("r1cs", r1cs_h)
+        return [(0, 2 ** 64 - 1)] * len(xs)
 
     def circuit_load(self, circuit):
         self._call("circuit_load", circuit)
@@ -152,6 +192,36 @@ class FakeDevice:
         k = a.shape[0]
         return np.tile(_PROOF, (k, 1)), np.zeros((k, 3), dtype=np.uint8), np.zeros((k, 3, 4), dtype=np.uint64), {}
 
+    @staticmethod
+    def _proofs(k):
+        return np.tile(_PROOF, (k, 1)), np.zeros((k, 3), dtype=np.uint8)
+
+    def prove_batch(self, pk_h, r1cs_h, witness_handles, rs, ss):
+        self._call("prove_batch", pk_h, r1cs_h, witness_handles, rs, ss)
+        self._is("pk", pk_h), self._is("r1cs", r1cs_h)
+        for wh in witness_handles:
+            self._is("witness", int(wh))
+        return self._proofs(len(witness_handles))
+
+    def prove_fibonacci_batch(self, pk_h, r1cs_h, steps, a, b, rs, ss):
+        self._call("prove_fibonacci_batch", pk_h, r1cs_h, steps, a, b, rs, ss)
+        self._is("pk", pk_h), self._is("r1cs", r1cs_h)
+        return self._proofs(len(a)) + (np.zeros((len(a), 3, 4), dtype=np.uint64), {})
+
+    def prove_linear_batch(self, pk_h, r1cs_h, a, b, rs, ss, solver=None):
+        self._call("prove_linear_batch", pk_h, r1cs_h, a, b, rs, ss)
+        self._is("pk", pk_h), self._is("r1cs", r1cs_h)
+        return self._proofs(len(a)) + (np.zeros(b.shape + (4,), dtype=np.uint64), {})
+
+    def prove_trapdoor_batch(self, r1cs_h, witness_handles, num_instance, trap, g1, g2, rs, ss):
+        self._call("prove_trapdoor_batch", r1cs_h, witness_handles, num_instance, trap, g1, g2, rs, ss)
+        self._is("r1cs", r1cs_h)
+        for wh in witness_handles:
+            self._is("witness", int(wh))
+        if self.refuse_trapdoor:
+            raise Zkg16Error(ZKG16_ERR_UNSATISFIED, "prove_trapdoor_batch: refused")
+        return self._proofs(len(witness_handles)) + (fake_vk(num_instance),)
+
     def prove_prime_batch(self, pk_h, r1cs_h, corr, gamma_abc0, xs, js, rs, ss):
         self._call("prove_prime_batch", pk_h, r1cs_h, corr, gamma_abc0, xs, js, rs, ss)
         self._is("pk", pk_h), self._is("r1cs", r1cs_h)
@@ -167,6 +237,9 @@ _A2 = np.array([[1, 2], [3, 4]], dtype=np.uint64)
 _B2 = np.array([[5, 6], [7, 8]], dtype=np.uint64)
 _PAIRS = [(_A2, _B2), (_B2, _A2)]
 _PRIMES = [(12345, 32), (12346, 32)]
+_FIBS = [(0, 1), (2, 3)]
+_SYSTEMS = [(np.array([[1, 0], [2, 3]], dtype=np.uint64), np.array([4, 5], dtype=np.uint64)),
+            (np.array([[2, 0], [1, 1]], dtype=np.uint64), np.array([6, 7], dtype=np.uint64))]
 
 
 def _matrices_key(dev):
@@ -182,6 +255,41 @@ def _primes_key(dev):
     return handlers.prime_template_key(dev, random.Random(1))
 
 
+def _fibonaccis_key(dev):
+    return handlers.fibonacci_key(dev, 3, random.Random(1))
+
+
+def _linears_key(dev):
+    return handlers.linear_key(dev, 2, random.Random(1))
+
+
+# The batch handlers: name -> (the request with the path's keywords, what makes a caller's key, the R1CS call of a first request, the
+# witness-batch call, the fused proving call).  Each is pinned on six paths (_BATCH_PATHS); "refused" in a name arms the fake's
+# prove_trapdoor_batch to refuse.
+_BATCH_HANDLERS = {
+    "matrices": (lambda dev, **kw: handlers.prove_matrices(dev, 2, _PAIRS, seed=3, **kw), _matrices_key,
+                 "r1cs_matrix", "witness_matrix_batch", "prove_matrix_batch"),
+    "fibonaccis": (lambda dev, **kw: handlers.prove_fibonaccis(dev, _FIBS, 3, seed=3, **kw), _fibonaccis_key,
+                   "r1cs_fibonacci", "witness_fibonacci_batch", "prove_fibonacci_batch"),
+    "linears": (lambda dev, **kw: handlers.prove_linear_equations_batch(dev, _SYSTEMS, seed=3, **kw), _linears_key,
+                "r1cs_linear", "witness_linear_batch", "prove_linear_batch"),
+}
+# path -> (the handler's keywords, the calls after the R1CS call as (r1cs, witness, fused) -> names)
+_BATCH_PATHS = {
+    "": (dict(), lambda r, w, f: [r, "setup_resident", f]),
+    "_key": (dict(), lambda r, w, f: [f]),
+    "_check": (dict(check_on_device=True), lambda r, w, f: [r, "setup_resident", w, "r1cs_check_batch", "prove_batch"]),
+    "_trapdoor": (dict(route="trapdoor"), lambda r, w, f: [r, w, "prove_trapdoor_batch"]),
+    "_trapdoor_refused": (dict(route="trapdoor"), lambda r, w, f: [r, w, "prove_trapdoor_batch", "setup_resident", f]),
+    "_trapdoor_refused_check": (dict(route="trapdoor", check_on_device=True),
+                                lambda r, w, f: [r, w, "prove_trapdoor_batch", "setup_resident", w, "r1cs_check_batch", "prove_batch"]),
+}
+
+
+def _batch_request(call, kw, with_key):
+    return (lambda dev, key: call(dev, key=key, **kw)) if with_key else (lambda dev, key: call(dev, **kw))
+
+
 # name -> (request(dev, key), what runs on dev before the request: it may return a key, which stays the caller's)
 REQUESTS = {
     "matrix_first": (lambda dev, key: handlers.prove_matrix(dev, 2, _A2, _B2, seed=3), None),
@@ -191,10 +299,9 @@ REQUESTS = {
     "fibonacci": (lambda dev, key: handlers.prove_fibonacci(dev, 0, 1, 3, seed=3), None),
     "fibonacci_keep_key": (lambda dev, key: handlers.prove_fibonacci(dev, 0, 1, 3, seed=3, keep_key=True), None),
     "prime": (lambda dev, key: handlers.prove_prime(dev, 12345, 32, seed=3), None),
-    "matrices": (lambda dev, key: handlers.prove_matrices(dev, 2, _PAIRS, seed=3), None),
-    "matrices_key": (lambda dev, key: handlers.prove_matrices(dev, 2, _PAIRS, seed=3, key=key), _matrices_key),
     "primes": (lambda dev, key: handlers.prove_primes(dev, _PRIMES, seed=3), None),
     "primes_key": (lambda dev, key: handlers.prove_primes(dev, _PRIMES, seed=3, key=key), _primes_key),
+    "primes_check": (lambda dev, key: handlers.prove_primes(dev, _PRIMES, seed=3, check_on_device=True), None),
 }
 EXPECTED_CALLS = {
     "matrix_first": ["r1cs_matrix", "witness_matrix", "setup_resident", "prove_resident"],
@@ -204,17 +311,21 @@ EXPECTED_CALLS = {
     "fibonacci": ["circuit_load", "setup_resident", "prove_resident"],
     "fibonacci_keep_key": ["r1cs_load", "witness_load", "setup", "pk_load", "prove_resident"],
     "prime": ["r1cs_prime", "witness_prime", "setup_resident", "prove_resident"],
-    "matrices": ["r1cs_matrix", "setup_resident", "prove_matrix_batch"],
-    "matrices_key": ["prove_matrix_batch"],
     "primes": ["r1cs_prime_template", "setup_resident", "prove_prime_batch"],
     "primes_key": ["prove_prime_batch"],
+    "primes_check": ["r1cs_prime_template", "setup_resident", "prime_check_batch", "prove_prime_batch"],
 }
+for _h, (_call, _key, _r, _w, _f) in _BATCH_HANDLERS.items():
+    for _p, (_kw, _calls) in _BATCH_PATHS.items():
+        REQUESTS[_h + _p] = (_batch_request(_call, _kw, _p == "_key"), _key if _p == "_key" else None)
+        EXPECTED_CALLS[_h + _p] = _calls(_r, _w, _f)
+_PROVING_BATCH_CALLS = ("prove_matrix_batch", "prove_fibonacci_batch", "prove_linear_batch", "prove_prime_batch", "prove_batch", "prove_trapdoor_batch")
 
 
 def _run(name, fail_at=None):
     """The request on a fresh fake -> (dev, handles that may stay live, what came out: the result or the exception)."""
     request, before = REQUESTS[name]
-    dev = FakeDevice(wait_for_assignment=name in ("matrix_first", "matrix_cached"))
+    dev = FakeDevice(wait_for_assignment=name in ("matrix_first", "matrix_cached"), refuse_trapdoor="refused" in name)
     key = before(dev) if before else None
     borrowed = set() if key is None else {key[0]} if isinstance(key, tuple) else {key["ph"], key["rh"]}
     exc = Boom(name)
@@ -267,24 +378,30 @@ def _expected_draws(seed, proofs):
 def test_draw_order(name):
     dev, out = _run(name)
     calls = dict(dev.calls)
-    batch = calls.get("prove_matrix_batch") or calls.get("prove_prime_batch")
-    proofs = len(batch[-1]) if batch else 1
+    batches = [args for call, args in dev.calls if call in _PROVING_BATCH_CALLS]
+    proofs = len(batches[0][-1]) if batches else 1
     trap, g1, g2, rs = _expected_draws(3, proofs)
-    setup = calls.get("setup") or calls.get("setup_resident")
-    assert np.array_equal(setup[-3], trap) and np.array_equal(setup[-2], g1) and np.array_equal(setup[-1], g2)
-    if batch:
-        assert proofs == (2 if name == "matrices" else sum(1 for q in out if q["found_prime"]))
-        assert np.array_equal(batch[-2], np.stack([r for r, _ in rs])) and np.array_equal(batch[-1], np.stack([s for _, s in rs]))
+    # the key's draws reach the setup, or the trapdoor call in front of r and s; a refused trapdoor batch shows them to both
+    keyed = [args[-3:] for call, args in dev.calls if call in ("setup", "setup_resident")]
+    keyed += [args[-5:-2] for call, args in dev.calls if call == "prove_trapdoor_batch"]
+    assert len(keyed) == (2 if "refused" in name else 1)
+    for got in keyed:
+        assert np.array_equal(got[0], trap) and np.array_equal(got[1], g1) and np.array_equal(got[2], g2)
+    if batches:
+        assert len(batches) == (2 if "refused" in name else 1)
+        assert proofs == (sum(1 for q in out if q["found_prime"]) if name.startswith("primes") else 2)
+        for batch in batches:
+            assert np.array_equal(batch[-2], np.stack([r for r, _ in rs])) and np.array_equal(batch[-1], np.stack([s for _, s in rs]))
     else:
         assert np.array_equal(calls["prove_resident"][-2], rs[0][0]) and np.array_equal(calls["prove_resident"][-1], rs[0][1])
         assert np.array_equal(out["_detail"]["r"], rs[0][0]) and np.array_equal(out["_detail"]["s"], rs[0][1])
 
 
-@pytest.mark.parametrize("name", ["matrices_key", "primes_key"])
+@pytest.mark.parametrize("name", ["matrices_key", "fibonaccis_key", "linears_key", "primes_key"])
 def test_draw_order_with_a_callers_key(name):
     """key=: no trapdoor is drawn, the first draws are r and s of the first proof."""
     dev, out = _run(name)
-    batch = dict(dev.calls).get("prove_matrix_batch") or dict(dev.calls).get("prove_prime_batch")
+    (batch,) = [args for call, args in dev.calls if call in _PROVING_BATCH_CALLS]
     rng = random.Random(3)
     rs = [(fr_mont(rng.randrange(R_MOD)), fr_mont(rng.randrange(R_MOD))) for _ in range(len(batch[-1]))]
     assert np.array_equal(batch[-2], np.stack([r for r, _ in rs])) and np.array_equal(batch[-1], np.stack([s for _, s in rs]))
@@ -305,6 +422,56 @@ def test_circuit_record_and_response_fields():
         assert (out["_detail"]["pk"] is not None) == name.endswith("keep_key")
     _, out = _run("matrix_cached")
     assert out["num_constraints"] == out["num_constraints_circuit"] + 2 * 2 ** 3 and out["num_variables"] == 4
+
+
+_BATCH_RECORD_FIELDS = {       # handler -> (a request's record, its "_detail"); prove_matrices: (the response, a request, "_detail")
+    "matrices": ({"vk", "pvk", "setup_time", "proving_time", "num_constraints_circuit", "num_variables", "requests", "_detail"},
+                 {"hash_a", "hash_b", "hash_c", "proof"}, {"proofs", "inf", "public_inputs", "vk", "rs", "ss", "ms", "route"}),
+    "fibonaccis": ({"proof", "proving_time", "setup_time", "num_constraints", "num_variables", "fib_number", "pvk", "vk", "_circuit", "_detail"},
+                   {"proof", "inf", "vk", "r", "s", "public_inputs", "ms", "route"}),
+    "linears": ({"proof", "public_input", "num_constraints", "num_variables", "proving_time", "verifying_time", "valid", "pvk", "vk", "_circuit",
+                 "_detail"}, {"proof", "inf", "vk", "r", "s", "public_inputs", "x", "ms", "setup_time", "route"}),
+    "primes": ({"proof", "j", "num_constraints", "num_variables", "setup_time", "proving_time", "found_prime", "prime_num", "pvk", "vk",
+                "satisfied", "_detail"}, {"proof", "inf", "vk", "r", "s", "public_inputs", "ms"}),
+}
+
+
+@pytest.mark.parametrize("name", sorted(n for n in REQUESTS if n.split("_")[0] in _BATCH_RECORD_FIELDS))
+def test_batch_record_fields(name):
+    """The fields of a batch handler's records, keys only, on every path: "satisfied" joins a record only with check_on_device (a
+    prime record always has it); "route" names the route that answered; setup_time is 0.0 with a caller's key and when the trapdoor
+    route answered."""
+    handler = name.split("_")[0]
+    _, out = _run(name)
+    checked = {"satisfied"} if name.endswith("_check") else set()
+    if handler == "matrices":
+        top, request, detail = _BATCH_RECORD_FIELDS[handler]
+        assert set(out) == top and set(out["_detail"]) == detail and len(out["requests"]) == 2
+        assert all(set(q) == request | checked for q in out["requests"])
+        details, setup_times = [out["_detail"]], [out["setup_time"]]
+    else:
+        record, detail = _BATCH_RECORD_FIELDS[handler]
+        assert len(out) == 2 and all(set(q) == record | checked and set(q["_detail"]) == detail for q in out)
+        details = [q["_detail"] for q in out]
+        setup_times = [q["_detail"]["setup_time"] if handler == "linears" else q["setup_time"] for q in out]
+    answered = "trapdoor" if name.endswith("_trapdoor") else "key"
+    assert handler == "primes" or all(d["route"] == answered for d in details)
+    if name.endswith("_key") or answered == "trapdoor":
+        assert setup_times == [0.0] * len(setup_times)
+    else:
+        assert all(t > 0.0 for t in setup_times)
+
+
+@pytest.mark.parametrize("name", sorted(_BATCH_HANDLERS))
+def test_trapdoor_route_takes_no_key(name):
+    """route="trapdoor" draws its own key: with key= the handler raises before any device call."""
+    call, make_key = _BATCH_HANDLERS[name][:2]
+    dev = FakeDevice()
+    key = make_key(dev)
+    dev.arm()
+    with pytest.raises(ValueError):
+        call(dev, key=key, route="trapdoor")
+    assert dev.calls == []
 
 
 def test_two_first_requests_make_one_r1cs():

@@ -247,6 +247,30 @@ def test_a_singular_request_in_a_later_sub_batch(dev, keys):
         dev.set_option("batch_max", 0)
 
 
+def test_a_singular_request_in_the_second_sub_batch_writes_nothing(dev, keys):
+    """batch_max = 2, request 2 of 3 singular: the second pass holds that request alone, so its index in the pass (0) is not its index
+    in the call.  Status 7 at the C entry, zkg16_last_error names request 2, and proofs, flags and solutions still hold the sentinel
+    although the first pass has proved."""
+    n = 3
+    st = keys(n)
+    _, sa, sb, c = LG.singular(n)[-1]
+    a = np.ascontiguousarray(np.stack([st["a"][0], st["a"][1], sa]))
+    b = np.ascontiguousarray(np.stack([st["b"][0], st["b"][1], sb]))
+    proofs, inf = np.full((3, 48), SENTINEL, dtype=np.uint64), np.full((3, 3), 0x5A, dtype=np.uint8)
+    x = np.full((3, n, 4), SENTINEL, dtype=np.uint64)
+    rs, ss = np.ascontiguousarray(st["rs"][:3]), np.ascontiguousarray(st["ss"][:3])
+    dev.set_option("linear_solver", 1)
+    dev.set_option("batch_max", 2)
+    try:
+        rc = dev.lib.zkg16_prove_linear_batch(dev.ctx, st["ph"], st["rh"], n, _vp(a), _vp(b), 3, _vp(rs), _vp(ss), _vp(proofs), _vp(inf), _vp(x), None)
+        text = dev.lib.zkg16_last_error(dev.ctx)
+    finally:
+        dev.set_option("batch_max", 0)
+        dev.set_option("linear_solver", 0)
+    assert rc == UNSUPPORTED == 7 and (proofs == SENTINEL).all() and (inf == 0x5A).all() and (x == SENTINEL).all()
+    assert b"zkg16_prove_linear_batch: request 2 " in text and b"column %d)" % c in text, text
+
+
 # ---------------------------------------------------------------------------------------------- the option
 def test_the_solver_is_set_for_one_call_only(dev, expected):
     """solver= sets option "linear_solver" for the call and restores it: a following call with the default solver still refuses a zero

@@ -675,15 +675,7 @@ int zkg16_witness_prime_batch(zkg16_ctx *ctx, const uint64_t *xs, const uint64_t
     ZK_API_BEGIN(ctx)
     std::vector<std::shared_ptr<WitnessDev>> wits;
     prime_witness_batch_assign(ctx, in.data(), k, wits, nullptr);
-    const uint64_t first = ctx->next_handle.fetch_add(k);
-    size_t put = 0;
-    try {
-        for (; put < k; put++) ctx->wits.put(first + put, std::move(wits[put]));
-    } catch (const std::bad_alloc &) {          // all or nothing: what was registered is taken back
-        for (size_t i = 0; i < put; i++) ctx->wits.erase(first + i);
-        return ZKG16_ERR_OOM;
-    }
-    for (size_t i = 0; i < k; i++) witness_handles[i] = first + i;
+    if (const int st = witness_batch_register(ctx, wits, witness_handles)) return st;
     ZK_API_END(ctx)
 }
 

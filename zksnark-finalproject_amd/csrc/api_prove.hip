@@ -663,6 +663,41 @@ std::vector<Fr> frs_from_abi(const uint64_t *l, size_t k) {
     return v;
 }
 
+// ---- the spine of the four zkg16_prove_*_batch entries that build their own assignments (no witness handle exists at any time):
+// per sub-batch (prove_in_passes) assign(off, nb, wit_refs, &dev_ms) makes the assignments of requests [off, off + nb) — the entry
+// offsets its inputs and staged side outputs there — and prove_batch_device proves them under r, s of those requests, after which the
+// sub-batch's assignments go back.  pc: the prime entry's corrections; its assign step points n and j at the sub-batch.  What assign
+// throws passes through.  -> the assign steps' summed device time and prove_in_passes' answer (negative: unsatisfied, nothing written).
+struct BatchTimes {
+    double wit_ms = 0;
+    float prove_ms = 0;
+};
+template <class Assign>
+BatchTimes prove_assigned_batch(zkg16_ctx *ctx, const ProveHandles &h, size_t k, const uint64_t *r, const uint64_t *s, size_t extra_per_proof,
+                                uint64_t *proofs_out, uint8_t *inf_out, Assign &&assign, const PrimeCorr *pc = nullptr) {
+    const std::vector<Fr> rr = frs_from_abi(r, k), ss = frs_from_abi(s, k);
+    BatchTimes t;
+    t.prove_ms = prove_in_passes(ctx, h.pk.get(), h.rc.get(), k, extra_per_proof, proofs_out, inf_out,
+                                 [&](size_t off, size_t nb, uint64_t *proofs, uint8_t *infs) {
+        std::vector<std::shared_ptr<WitnessDev>> wit_refs;
+        float dev_ms = 0;
+        assign(off, nb, wit_refs, &dev_ms);
+        t.wit_ms += dev_ms;
+        std::vector<WitnessDev *> wits(nb);
+        for (size_t i = 0; i < nb; i++) wits[i] = wit_refs[i].get();
+        prove_batch_device(ctx, *h.pk, *h.rc, wits.data(), nb, rr.data() + off, ss.data() + off, proofs, infs, pc);
+    });
+    return t;
+}
+// their timings_ms (nullable, 4): the entry's host pre-work, the assign steps, proving, the whole call
+void batch_times_out(float *timings_ms, double host_ms, const BatchTimes &t, double t_call) {
+    if (!timings_ms) return;
+    timings_ms[0] = (float)host_ms;
+    timings_ms[1] = (float)t.wit_ms;
+    timings_ms[2] = t.prove_ms;
+    timings_ms[3] = (float)(now_ms() - t_call);
+}
+
 }  // namespace
 
 extern "C" {
@@ -799,32 +834,20 @@ int zkg16_prove_matrix_batch(zkg16_ctx *ctx, uint64_t pk_handle, uint64_t r1cs_h
     ProveHandles h;
     if (const int st = lookup_handles(root, pk_handle, r1cs_handle, nullptr, 0, Shard::unsupported, total, h)) return st;
     if (k > SIZE_MAX / (total * sizeof(Fr))) return ZKG16_ERR_BAD_ARG;
-    const std::vector<Fr> rr = frs_from_abi(r, k), ss = frs_from_abi(s, k);
     std::vector<uint64_t> pubs(12 * k);
-    double chain_ms = 0, wit_ms = 0;
-    const float prove_ms = prove_in_passes(ctx, h.pk.get(), h.rc.get(), k, total * sizeof(Fr), proofs_out, inf_out,
-                                           [&](size_t off, size_t nb, uint64_t *proofs, uint8_t *infs) {
+    double chain_ms = 0;
+    const BatchTimes t = prove_assigned_batch(ctx, h, k, r, s, total * sizeof(Fr), proofs_out, inf_out,
+                                              [&](size_t off, size_t nb, std::vector<std::shared_ptr<WitnessDev>> &wit_refs, float *dev_ms) {
         const uint64_t *ao = a + off * nn, *bo = b + off * nn;
         MatrixBatchChains mc;
         if (sponge_chains_on_device(ctx, 3 * nb)) matrix_batch_chains_device(mc, n, nb, pubs.data() + 12 * off);
         else matrix_batch_chains(mc, n, ao, bo, nb, ctx->opt.matrix_batch_threads, pubs.data() + 12 * off);
         chain_ms += mc.ms;
-        std::vector<std::shared_ptr<WitnessDev>> wit_refs;
-        float dev_ms = 0;
-        matrix_batch_assign(ctx, mc, ao, bo, wit_refs, &dev_ms);
-        wit_ms += dev_ms;
-        std::vector<WitnessDev *> wits(nb);
-        for (size_t i = 0; i < nb; i++) wits[i] = wit_refs[i].get();
-        prove_batch_device(ctx, *h.pk, *h.rc, wits.data(), nb, rr.data() + off, ss.data() + off, proofs, infs);
+        matrix_batch_assign(ctx, mc, ao, bo, wit_refs, dev_ms);
     });
-    if (prove_ms < 0) return ZKG16_ERR_UNSATISFIED;
+    if (t.prove_ms < 0) return ZKG16_ERR_UNSATISFIED;
     if (public_inputs) memcpy(public_inputs, pubs.data(), pubs.size() * sizeof(uint64_t));
-    if (timings_ms) {
-        timings_ms[0] = (float)chain_ms;
-        timings_ms[1] = (float)wit_ms;
-        timings_ms[2] = prove_ms;
-        timings_ms[3] = (float)(now_ms() - t_call);
-    }
+    batch_times_out(timings_ms, chain_ms, t, t_call);
     ZK_LANE_END(ctx)
 }
 
@@ -847,27 +870,14 @@ int zkg16_prove_fibonacci_batch(zkg16_ctx *ctx, uint64_t pk_handle, uint64_t r1c
     Fr ca, cb;
     fibonacci_coeffs(steps, ca, cb);
     const double coeff_ms = now_ms() - t_coeff;
-    const std::vector<Fr> rr = frs_from_abi(r, k), ss = frs_from_abi(s, k);
     std::vector<uint64_t> pubs(12 * k);
-    double wit_ms = 0;
-    const float prove_ms = prove_in_passes(ctx, h.pk.get(), h.rc.get(), k, FIBONACCI_VARS * sizeof(Fr), proofs_out, inf_out,
-                                           [&](size_t off, size_t nb, uint64_t *proofs, uint8_t *infs) {
-        std::vector<std::shared_ptr<WitnessDev>> wit_refs;
-        float dev_ms = 0;
-        fibonacci_batch_assign(ctx, ca, cb, a + off, b + off, nb, wit_refs, pubs.data() + 12 * off, &dev_ms);
-        wit_ms += dev_ms;
-        std::vector<WitnessDev *> wits(nb);
-        for (size_t i = 0; i < nb; i++) wits[i] = wit_refs[i].get();
-        prove_batch_device(ctx, *h.pk, *h.rc, wits.data(), nb, rr.data() + off, ss.data() + off, proofs, infs);
+    const BatchTimes t = prove_assigned_batch(ctx, h, k, r, s, FIBONACCI_VARS * sizeof(Fr), proofs_out, inf_out,
+                                              [&](size_t off, size_t nb, std::vector<std::shared_ptr<WitnessDev>> &wit_refs, float *dev_ms) {
+        fibonacci_batch_assign(ctx, ca, cb, a + off, b + off, nb, wit_refs, pubs.data() + 12 * off, dev_ms);
     });
-    if (prove_ms < 0) return ZKG16_ERR_UNSATISFIED;
+    if (t.prove_ms < 0) return ZKG16_ERR_UNSATISFIED;
     if (public_inputs) memcpy(public_inputs, pubs.data(), pubs.size() * sizeof(uint64_t));
-    if (timings_ms) {
-        timings_ms[0] = (float)coeff_ms;
-        timings_ms[1] = (float)wit_ms;
-        timings_ms[2] = prove_ms;
-        timings_ms[3] = (float)(now_ms() - t_call);
-    }
+    batch_times_out(timings_ms, coeff_ms, t, t_call);
     ZK_LANE_END(ctx)
 }
 
@@ -898,26 +908,18 @@ int zkg16_prove_linear_batch(zkg16_ctx *ctx, uint64_t pk_handle, uint64_t r1cs_h
         return ZKG16_ERR_UNSUPPORTED;
     }
     const double check_ms = now_ms() - t_check;
-    const std::vector<Fr> rr = frs_from_abi(r, k), ss = frs_from_abi(s, k);
     std::vector<uint64_t> xs(4 * k * n);
-    double wit_ms = 0;
     // per proof: the assignment, its input and x; the elimination's global workspace where it is used (one per workgroup, at most one per request)
     const size_t elim_extra = elim && !linear_elim_in_lds(ctx, n) ? n * (n + 1) * sizeof(Fr) + sizeof(uint32_t) : 0;
-    float prove_ms = 0;
+    BatchTimes t;
     try {
-        prove_ms = prove_in_passes(ctx, h.pk.get(), h.rc.get(), k, d.vars() * sizeof(Fr) + (n * n + n) * sizeof(uint64_t) + n * sizeof(Fr) + elim_extra,
-                                   proofs_out, inf_out, [&](size_t off, size_t nb, uint64_t *proofs, uint8_t *infs) {
-            std::vector<std::shared_ptr<WitnessDev>> wit_refs;
-            float dev_ms = 0;
+        t = prove_assigned_batch(ctx, h, k, r, s, d.vars() * sizeof(Fr) + (n * n + n) * sizeof(uint64_t) + n * sizeof(Fr) + elim_extra, proofs_out, inf_out,
+                                 [&](size_t off, size_t nb, std::vector<std::shared_ptr<WitnessDev>> &wit_refs, float *dev_ms) {
             try {
-                linear_batch_assign(ctx, n, a + off * n * n, b + off * n, nb, wit_refs, xs.data() + 4 * off * n, &dev_ms);
+                linear_batch_assign(ctx, n, a + off * n * n, b + off * n, nb, wit_refs, xs.data() + 4 * off * n, dev_ms);
             } catch (const LinearSingular &e) {
                 throw LinearSingular{off + e.req, e.col};       // the request's index in the call
             }
-            wit_ms += dev_ms;
-            std::vector<WitnessDev *> wits(nb);
-            for (size_t i = 0; i < nb; i++) wits[i] = wit_refs[i].get();
-            prove_batch_device(ctx, *h.pk, *h.rc, wits.data(), nb, rr.data() + off, ss.data() + off, proofs, infs);
         });
     } catch (const LinearSingular &e) {         // nothing was written: proofs and solutions are staged
         char buf[200];
@@ -926,14 +928,9 @@ int zkg16_prove_linear_batch(zkg16_ctx *ctx, uint64_t pk_handle, uint64_t r1cs_h
         if (ctx != root) { std::lock_guard<std::mutex> l(root->lane_mu); root->last_error = buf; }
         return ZKG16_ERR_UNSUPPORTED;
     }
-    if (prove_ms < 0) return ZKG16_ERR_UNSATISFIED;
+    if (t.prove_ms < 0) return ZKG16_ERR_UNSATISFIED;
     if (x_out) memcpy(x_out, xs.data(), xs.size() * sizeof(uint64_t));
-    if (timings_ms) {
-        timings_ms[0] = (float)check_ms;
-        timings_ms[1] = (float)wit_ms;
-        timings_ms[2] = prove_ms;
-        timings_ms[3] = (float)(now_ms() - t_call);
-    }
+    batch_times_out(timings_ms, check_ms, t, t_call);
     ZK_LANE_END(ctx)
 }
 
@@ -961,22 +958,14 @@ int zkg16_prove_prime_batch(zkg16_ctx *ctx, uint64_t pk_handle, uint64_t r1cs_ha
     pc.U = g1_from_abi(corr, 0);
     memcpy(pc.rows, h.rc->patch_rows, sizeof pc.rows);
     const G1Affine v_n = g1_from_abi(corr + 12, 0), v_j = g1_from_abi(corr + 24, 0), g0 = g1_from_abi(gamma_abc0_template, 0);
-    const std::vector<Fr> rr = frs_from_abi(r, k), ss = frs_from_abi(s, k);
     std::vector<uint64_t> gammas(12 * k), pubs(public_inputs ? 257 * 4 * k : 0);
-    double wit_ms = 0;
-    const float prove_ms = prove_in_passes(ctx, h.pk.get(), h.rc.get(), k, h.rc->num_variables * sizeof(Fr), proofs_out, inf_out,
-                                           [&](size_t off, size_t nb, uint64_t *proofs, uint8_t *infs) {
-        std::vector<std::shared_ptr<WitnessDev>> wit_refs;
-        float dev_ms = 0;
-        prime_witness_batch_assign(ctx, in.data() + off * stride, nb, wit_refs, &dev_ms);
-        wit_ms += dev_ms;
-        std::vector<WitnessDev *> wits(nb);
-        for (size_t i = 0; i < nb; i++) wits[i] = wit_refs[i].get();
+    const BatchTimes t = prove_assigned_batch(ctx, h, k, r, s, h.rc->num_variables * sizeof(Fr), proofs_out, inf_out,
+                                              [&](size_t off, size_t nb, std::vector<std::shared_ptr<WitnessDev>> &wit_refs, float *dev_ms) {
+        prime_witness_batch_assign(ctx, in.data() + off * stride, nb, wit_refs, dev_ms);
         pc.n = ns.data() + off;
         pc.j = js + off;
-        prove_batch_device(ctx, *h.pk, *h.rc, wits.data(), nb, rr.data() + off, ss.data() + off, proofs, infs, &pc);
-    });
-    if (prove_ms < 0) return ZKG16_ERR_UNSATISFIED;
+    }, &pc);
+    if (t.prove_ms < 0) return ZKG16_ERR_UNSATISFIED;
     for (size_t i = 0; i < k; i++) {      // gamma_abc_g1[0] = the template's + n V_n - j V_j
         G1XYZZ g = G1XYZZ::from_affine(g0);
         xyzz_add(g, g1_mul_u64(v_n, ns[i]));
@@ -986,12 +975,7 @@ int zkg16_prove_prime_batch(zkg16_ctx *ctx, uint64_t pk_handle, uint64_t r1cs_ha
     }
     memcpy(gamma_abc0_out, gammas.data(), gammas.size() * sizeof(uint64_t));
     if (public_inputs) memcpy(public_inputs, pubs.data(), pubs.size() * sizeof(uint64_t));
-    if (timings_ms) {
-        timings_ms[0] = (float)in_ms;
-        timings_ms[1] = (float)wit_ms;
-        timings_ms[2] = prove_ms;
-        timings_ms[3] = (float)(now_ms() - t_call);
-    }
+    batch_times_out(timings_ms, in_ms, t, t_call);
     ZK_LANE_END(ctx)
 }
 

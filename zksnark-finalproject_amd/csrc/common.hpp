@@ -567,6 +567,10 @@ double matrix_stream_chain_ms(const MatrixWitnessStream *ms);
 void matrix_stream_hashes(const MatrixWitnessStream *ms, uint64_t out[12]);
 void matrix_stream_free(MatrixWitnessStream *ms);
 
+// The assignments of a *_batch_assign become witness handles of ctx (under its mutex), all or nothing (witness.hip): wits.size()
+// consecutive handles written to handles_out -> ZKG16_OK, or none registered, nothing written -> ZKG16_ERR_OOM.
+int witness_batch_register(zkg16_ctx *ctx, std::vector<std::shared_ptr<WitnessDev>> &wits, uint64_t *handles_out);
+
 // K requests of one size in one pass (zkg16_witness_matrix_batch, zkg16_prove_matrix_batch).  matrix_batch_chains: the 3k host chains
 // on `threads` threads (0 = 8), no ctx; the 12 k hash limbs go to `hashes`, which must stay valid for matrix_batch_assign.  That
 // one queues the uploads and the two batched launches on ctx->stream (under ctx's mutex) and synchronises it: k assignments in one

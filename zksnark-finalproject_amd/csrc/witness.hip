@@ -1090,6 +1090,36 @@ void linear_batch_assign(zkg16_ctx *ctx, size_t n, const uint64_t *a, const uint
     out = std::move(wits);
 }
 
+int witness_batch_register(zkg16_ctx *ctx, std::vector<std::shared_ptr<WitnessDev>> &wits, uint64_t *handles_out) {
+    const size_t k = wits.size();
+    const uint64_t first = ctx->next_handle.fetch_add(k);
+    size_t put = 0;
+    try {
+        for (; put < k; put++) ctx->wits.put(first + put, std::move(wits[put]));
+    } catch (const std::bad_alloc &) {          // all or nothing: what was registered is taken back
+        for (size_t i = 0; i < put; i++) ctx->wits.erase(first + i);
+        return ZKG16_ERR_OOM;
+    }
+    for (size_t i = 0; i < k; i++) handles_out[i] = first + i;
+    return ZKG16_OK;
+}
+
+// The catch tail of the three zkg16_witness_*_batch entries below, called from their catch (...): the exception in flight -> its
+// status, a HipError's text into ctx->last_error.  Anything else goes on as it would have.
+static int witness_batch_status(zkg16_ctx *ctx) {
+    try {
+        throw;
+    } catch (const HipError &e) {
+        char buf[512];
+        snprintf(buf, sizeof buf, "%s failed: %s (%s:%d)", e.what, hipGetErrorString(e.err), e.file, e.line);
+        ctx->last_error = buf;
+        (void)hipGetLastError();
+        return e.err == hipErrorOutOfMemory ? ZKG16_ERR_OOM : ZKG16_ERR_HIP;
+    } catch (const std::bad_alloc &) {
+        return ZKG16_ERR_OOM;
+    }
+}
+
 }  // namespace zk
 #endif  // ZKG16_HOST_ONLY
 
@@ -1168,29 +1198,15 @@ int zkg16_witness_matrix_batch(zkg16_ctx *ctx, size_t n, const uint64_t *a, cons
         std::vector<std::shared_ptr<WitnessDev>> wits;
         float dev_ms = 0;
         matrix_batch_assign(ctx, mc, a, b, wits, &dev_ms);
-        const uint64_t first = ctx->next_handle.fetch_add(k);
-        size_t put = 0;
-        try {
-            for (; put < k; put++) ctx->wits.put(first + put, std::move(wits[put]));
-        } catch (const std::bad_alloc &) {          // all or nothing: what was registered is taken back
-            for (size_t i = 0; i < put; i++) ctx->wits.erase(first + i);
-            return ZKG16_ERR_OOM;
-        }
-        for (size_t i = 0; i < k; i++) witness_handles[i] = first + i;
+        if (const int st = witness_batch_register(ctx, wits, witness_handles)) return st;
         if (public_inputs) memcpy(public_inputs, hashes.data(), 12 * k * sizeof(uint64_t));
         if (timings_ms) {
             timings_ms[0] = (float)mc.ms;
             timings_ms[1] = dev_ms;
             timings_ms[2] = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
         }
-    } catch (const HipError &e) {
-        char buf[512];
-        snprintf(buf, sizeof buf, "%s failed: %s (%s:%d)", e.what, hipGetErrorString(e.err), e.file, e.line);
-        ctx->last_error = buf;
-        (void)hipGetLastError();
-        return e.err == hipErrorOutOfMemory ? ZKG16_ERR_OOM : ZKG16_ERR_HIP;
-    } catch (const std::bad_alloc &) {
-        return ZKG16_ERR_OOM;
+    } catch (...) {
+        return witness_batch_status(ctx);
     }
     return ZKG16_OK;
 }
@@ -1213,29 +1229,15 @@ int zkg16_witness_fibonacci_batch(zkg16_ctx *ctx, size_t steps, const uint64_t *
         std::vector<uint64_t> pubs(12 * k);
         float dev_ms = 0;
         fibonacci_batch_assign(ctx, ca, cb, a, b, k, wits, pubs.data(), &dev_ms);
-        const uint64_t first = ctx->next_handle.fetch_add(k);
-        size_t put = 0;
-        try {
-            for (; put < k; put++) ctx->wits.put(first + put, std::move(wits[put]));
-        } catch (const std::bad_alloc &) {          // all or nothing: what was registered is taken back
-            for (size_t i = 0; i < put; i++) ctx->wits.erase(first + i);
-            return ZKG16_ERR_OOM;
-        }
-        for (size_t i = 0; i < k; i++) witness_handles[i] = first + i;
+        if (const int st = witness_batch_register(ctx, wits, witness_handles)) return st;
         if (public_inputs) memcpy(public_inputs, pubs.data(), 12 * k * sizeof(uint64_t));
         if (timings_ms) {
             timings_ms[0] = (float)coeff_ms;
             timings_ms[1] = dev_ms;
             timings_ms[2] = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
         }
-    } catch (const HipError &e) {
-        char buf[512];
-        snprintf(buf, sizeof buf, "%s failed: %s (%s:%d)", e.what, hipGetErrorString(e.err), e.file, e.line);
-        ctx->last_error = buf;
-        (void)hipGetLastError();
-        return e.err == hipErrorOutOfMemory ? ZKG16_ERR_OOM : ZKG16_ERR_HIP;
-    } catch (const std::bad_alloc &) {
-        return ZKG16_ERR_OOM;
+    } catch (...) {
+        return witness_batch_status(ctx);
     }
     return ZKG16_OK;
 }
@@ -1264,15 +1266,7 @@ int zkg16_witness_linear_batch(zkg16_ctx *ctx, size_t n, const uint64_t *a, cons
         std::vector<uint64_t> xs(4 * k * n);
         float dev_ms = 0;
         linear_batch_assign(ctx, n, a, b, k, wits, xs.data(), &dev_ms);
-        const uint64_t first = ctx->next_handle.fetch_add(k);
-        size_t put = 0;
-        try {
-            for (; put < k; put++) ctx->wits.put(first + put, std::move(wits[put]));
-        } catch (const std::bad_alloc &) {          // all or nothing: what was registered is taken back
-            for (size_t i = 0; i < put; i++) ctx->wits.erase(first + i);
-            return ZKG16_ERR_OOM;
-        }
-        for (size_t i = 0; i < k; i++) witness_handles[i] = first + i;
+        if (const int st = witness_batch_register(ctx, wits, witness_handles)) return st;
         if (x_out) memcpy(x_out, xs.data(), xs.size() * sizeof(uint64_t));
         if (timings_ms) {
             timings_ms[0] = (float)check_ms;
@@ -1284,14 +1278,8 @@ int zkg16_witness_linear_batch(zkg16_ctx *ctx, size_t n, const uint64_t *a, cons
         snprintf(buf, sizeof buf, "zkg16_witness_linear_batch: request %zu is singular: columns 0..%zu of a are linearly dependent (column %zu)", e.req, e.col, e.col);
         ctx->last_error = buf;
         return ZKG16_ERR_UNSUPPORTED;
-    } catch (const HipError &e) {
-        char buf[512];
-        snprintf(buf, sizeof buf, "%s failed: %s (%s:%d)", e.what, hipGetErrorString(e.err), e.file, e.line);
-        ctx->last_error = buf;
-        (void)hipGetLastError();
-        return e.err == hipErrorOutOfMemory ? ZKG16_ERR_OOM : ZKG16_ERR_HIP;
-    } catch (const std::bad_alloc &) {
-        return ZKG16_ERR_OOM;
+    } catch (...) {
+        return witness_batch_status(ctx);
     }
     return ZKG16_OK;
 }

@@ -27,6 +27,25 @@ def _check_host(rc):
         raise Zkg16Error(rc, _lib.load().zkg16_strerror(rc).decode())
 
 
+# ---- what the batch proving methods share
+def _rs_ss(who, rs, ss, k, each="one r and one s per request"):
+    """The blinding pairs of a batch of k -> (rs [k, 4], ss [k, 4]) u64."""
+    rs, ss = _u64(rs).reshape(-1, 4), _u64(ss).reshape(-1, 4)
+    if rs.shape[0] != k or ss.shape[0] != k:
+        raise ValueError(who + ": " + each)
+    return rs, ss
+
+
+def _proof_outputs(k):
+    """-> (proofs [k, 48], inf [k, 3]) for an entry point to fill."""
+    return np.zeros((k, 48), dtype=np.uint64), np.zeros((k, 3), dtype=np.uint8)
+
+
+def _ms(times, *names):
+    """An entry point's c_float times under their names."""
+    return {name: float(t) for name, t in zip(names, times)}
+
+
 class Device:
     def __init__(self, device_id=0):
         # MatrixCircuit shapes resident on this device, by size (handlers._matrix_shape); entries have .rh
@@ -422,7 +441,7 @@ class Device:
         pub = np.zeros((k, 3, 4), dtype=np.uint64)
         ms = (C.c_float * 3)()
         self._check(self.lib.zkg16_witness_matrix_batch(self.ctx, n, _ptr(a), _ptr(b), k, _ptr(handles), _ptr(pub), C.addressof(ms)))
-        return handles, pub, dict(host_sponges_ms=float(ms[0]), device_ms=float(ms[1]), call_ms=float(ms[2]))
+        return handles, pub, _ms(ms, "host_sponges_ms", "device_ms", "call_ms")
 
     @staticmethod
     def _fibonacci_batch(what, a, b):
@@ -440,7 +459,7 @@ class Device:
         pub = np.zeros((k, 3, 4), dtype=np.uint64)
         ms = (C.c_float * 3)()
         self._check(self.lib.zkg16_witness_fibonacci_batch(self.ctx, steps, _ptr(a), _ptr(b), k, _ptr(handles), _ptr(pub), C.addressof(ms)))
-        return handles, pub, dict(host_coeffs_ms=float(ms[0]), device_ms=float(ms[1]), call_ms=float(ms[2]))
+        return handles, pub, _ms(ms, "host_coeffs_ms", "device_ms", "call_ms")
 
     @staticmethod
     def _linear_batch(what, a, b):
@@ -479,7 +498,7 @@ class Device:
         ms = (C.c_float * 3)()
         with self._linear_solver(solver):
             self._check(self.lib.zkg16_witness_linear_batch(self.ctx, n, _ptr(a), _ptr(b), k, _ptr(handles), _ptr(x), C.addressof(ms)))
-        return handles, x, dict(host_check_ms=float(ms[0]), device_ms=float(ms[1]), call_ms=float(ms[2]))
+        return handles, x, _ms(ms, "host_check_ms", "device_ms", "call_ms")
 
     def poseidon_hash_batch(self, elems):
         """k Poseidon hashes in one call (zkg16_poseidon_hash_batch): elems [k, n, 4] Montgomery Fr -> [k, 4], row i the bytes of
@@ -522,12 +541,8 @@ class Device:
         rs[k], ss[k])."""
         hs = np.ascontiguousarray(witness_handles, dtype=np.uint64).reshape(-1)
         k = hs.shape[0]
-        rs = _u64(rs).reshape(-1, 4)
-        ss = _u64(ss).reshape(-1, 4)
-        if rs.shape[0] != k or ss.shape[0] != k:
-            raise ValueError("prove_batch: one r and one s per witness handle")
-        proofs = np.zeros((k, 48), dtype=np.uint64)
-        inf = np.zeros((k, 3), dtype=np.uint8)
+        rs, ss = _rs_ss("prove_batch", rs, ss, k, "one r and one s per witness handle")
+        proofs, inf = _proof_outputs(k)
         self._check(self.lib.zkg16_prove_batch(self.ctx, pk_h, r1cs_h, hs, k, rs, ss, proofs, inf))
         return proofs, inf
 
@@ -546,11 +561,8 @@ class Device:
         times (ms: QAP evaluation, sparse product + check, dot kernel, fixed-base passes, whole call) are kept in last_trapdoor_ms."""
         hs = np.ascontiguousarray(witness_handles, dtype=np.uint64).reshape(-1)
         k = hs.shape[0]
-        rs, ss = _u64(rs).reshape(-1, 4), _u64(ss).reshape(-1, 4)
-        if rs.shape[0] != k or ss.shape[0] != k:
-            raise ValueError("prove_trapdoor_batch: one r and one s per witness handle")
-        proofs = np.zeros((k, 48), dtype=np.uint64)
-        inf = np.zeros((k, 3), dtype=np.uint8)
+        rs, ss = _rs_ss("prove_trapdoor_batch", rs, ss, k, "one r and one s per witness handle")
+        proofs, inf = _proof_outputs(k)
         vk = dict(alpha_g1=np.zeros(12, np.uint64), beta_g2=np.zeros(24, np.uint64), gamma_g2=np.zeros(24, np.uint64),
                   delta_g2=np.zeros(24, np.uint64), gamma_abc_g1=np.zeros((num_instance, 12), np.uint64))
         ms = (C.c_float * 5)()
@@ -562,7 +574,7 @@ class Device:
         else:
             rc = self.lib.zkg16_prove_trapdoor_batch(self.ctx, r1cs_h, _ptr(hs) if k else None, k, _ptr(trap), _ptr(g1), _ptr(g2), _ptr(rs), _ptr(ss), *tail)
         self._check(rc)
-        self.last_trapdoor_ms = dict(zip(("qap_ms", "check_ms", "dot_ms", "points_ms", "call_ms"), (float(x) for x in ms)))
+        self.last_trapdoor_ms = _ms(ms, "qap_ms", "check_ms", "dot_ms", "points_ms", "call_ms")
         return proofs, inf, vk
 
     # ---- batched verification: one body per shape of entry point, whatever the form of the public inputs (_verify_args)
@@ -826,17 +838,13 @@ class Device:
         batched device passes (zkg16_prove_matrix_batch) -> (proofs [k, 48], inf [k, 3], public inputs [k, 3, 4], dict of ms).  Proof i
         is byte-identical to prove_resident on witness_matrix(a[i], b[i]) with (rs[i], ss[i])."""
         a, b, k, n = self._matrix_batch("prove_matrix_batch", a, b)
-        rs = _u64(rs).reshape(-1, 4)
-        ss = _u64(ss).reshape(-1, 4)
-        if rs.shape[0] != k or ss.shape[0] != k:
-            raise ValueError("prove_matrix_batch: one r and one s per request")
-        proofs = np.zeros((k, 48), dtype=np.uint64)
-        inf = np.zeros((k, 3), dtype=np.uint8)
+        rs, ss = _rs_ss("prove_matrix_batch", rs, ss, k)
+        proofs, inf = _proof_outputs(k)
         pub = np.zeros((k, 3, 4), dtype=np.uint64)
         ms = (C.c_float * 4)()
         self._check(self.lib.zkg16_prove_matrix_batch(self.ctx, pk_h, r1cs_h, n, _ptr(a), _ptr(b), k, _ptr(rs), _ptr(ss), _ptr(proofs), _ptr(inf),
                                                       _ptr(pub), C.addressof(ms)))
-        return proofs, inf, pub, dict(host_sponges_ms=float(ms[0]), witness_ms=float(ms[1]), prove_ms=float(ms[2]), call_ms=float(ms[3]))
+        return proofs, inf, pub, _ms(ms, "host_sponges_ms", "witness_ms", "prove_ms", "call_ms")
 
     def prove_fibonacci_batch(self, pk_h, r1cs_h, steps, a, b, rs, ss):
         """k Fibonacci-handler requests of one round count on one resident key, a and b [k] u64, rs / ss [k, 4]: assignments and proofs
@@ -844,17 +852,13 @@ class Device:
         dict of ms).  pk_h: a key set up on r1cs_fibonacci(steps) = r1cs_h.  Proof i is byte-identical to prove_resident on the
         circuit_load handles of fibonacci_circuit(a[i], b[i], steps) with (rs[i], ss[i])."""
         a, b, k = self._fibonacci_batch("prove_fibonacci_batch", a, b)
-        rs = _u64(rs).reshape(-1, 4)
-        ss = _u64(ss).reshape(-1, 4)
-        if rs.shape[0] != k or ss.shape[0] != k:
-            raise ValueError("prove_fibonacci_batch: one r and one s per request")
-        proofs = np.zeros((k, 48), dtype=np.uint64)
-        inf = np.zeros((k, 3), dtype=np.uint8)
+        rs, ss = _rs_ss("prove_fibonacci_batch", rs, ss, k)
+        proofs, inf = _proof_outputs(k)
         pub = np.zeros((k, 3, 4), dtype=np.uint64)
         ms = (C.c_float * 4)()
         self._check(self.lib.zkg16_prove_fibonacci_batch(self.ctx, pk_h, r1cs_h, steps, _ptr(a), _ptr(b), k, _ptr(rs), _ptr(ss), _ptr(proofs),
                                                          _ptr(inf), _ptr(pub), C.addressof(ms)))
-        return proofs, inf, pub, dict(host_coeffs_ms=float(ms[0]), witness_ms=float(ms[1]), prove_ms=float(ms[2]), call_ms=float(ms[3]))
+        return proofs, inf, pub, _ms(ms, "host_coeffs_ms", "witness_ms", "prove_ms", "call_ms")
 
     def prove_linear_batch(self, pk_h, r1cs_h, a, b, rs, ss, solver=None):
         """k linear-handler requests of one size on one resident key, a [k, n, n] and b [k, n] u64, rs / ss [k, 4]: assignments and
@@ -865,18 +869,14 @@ class Device:
         with "elimination" proof i is prove_resident's on linear_circuit(a[i], b[i], solver="elimination") and verifies for every
         non-singular a[i]."""
         a, b, k, n = self._linear_batch("prove_linear_batch", a, b)
-        rs = _u64(rs).reshape(-1, 4)
-        ss = _u64(ss).reshape(-1, 4)
-        if rs.shape[0] != k or ss.shape[0] != k:
-            raise ValueError("prove_linear_batch: one r and one s per request")
-        proofs = np.zeros((k, 48), dtype=np.uint64)
-        inf = np.zeros((k, 3), dtype=np.uint8)
+        rs, ss = _rs_ss("prove_linear_batch", rs, ss, k)
+        proofs, inf = _proof_outputs(k)
         x = np.zeros((k, n, 4), dtype=np.uint64)
         ms = (C.c_float * 4)()
         with self._linear_solver(solver):
             self._check(self.lib.zkg16_prove_linear_batch(self.ctx, pk_h, r1cs_h, n, _ptr(a), _ptr(b), k, _ptr(rs), _ptr(ss), _ptr(proofs),
                                                           _ptr(inf), _ptr(x), C.addressof(ms)))
-        return proofs, inf, x, dict(host_check_ms=float(ms[0]), witness_ms=float(ms[1]), prove_ms=float(ms[2]), call_ms=float(ms[3]))
+        return proofs, inf, x, _ms(ms, "host_check_ms", "witness_ms", "prove_ms", "call_ms")
 
     def prove_prime_batch(self, pk_h, r1cs_h, corr, gamma_abc0, xs, js, rs, ss, public_inputs=True):
         """k prime requests (xs[i], js[i]) on the template key in batched device passes (zkg16_prove_prime_batch).  pk_h: the key
@@ -885,20 +885,19 @@ class Device:
         inputs [k, 257, 4] or None, dict of ms).  Proof and key are byte for byte those of the per-request path."""
         xs, js = _u64(xs).reshape(-1), _u64(js).reshape(-1)
         k = xs.shape[0]
-        rs, ss = _u64(rs).reshape(-1, 4), _u64(ss).reshape(-1, 4)
-        if js.shape[0] != k or rs.shape[0] != k or ss.shape[0] != k:
+        rs, ss = _rs_ss("prove_prime_batch", rs, ss, k, "one j, r and s per request")
+        if js.shape[0] != k:
             raise ValueError("prove_prime_batch: one j, r and s per request")
         corr, gamma_abc0 = _u64(corr).reshape(-1), _u64(gamma_abc0).reshape(-1)
         if corr.size != 36 or gamma_abc0.size != 12:
             raise ValueError("prove_prime_batch: corr 3 x 12 limbs, gamma_abc0 12 limbs")
-        proofs = np.zeros((k, 48), dtype=np.uint64)
-        inf = np.zeros((k, 3), dtype=np.uint8)
+        proofs, inf = _proof_outputs(k)
         g0 = np.zeros((k, 12), dtype=np.uint64)
         pub = np.zeros((k, 257, 4), dtype=np.uint64) if public_inputs else None
         ms = (C.c_float * 4)()
         self._check(self.lib.zkg16_prove_prime_batch(self.ctx, pk_h, r1cs_h, _ptr(corr), _ptr(gamma_abc0), _ptr(xs), _ptr(js), k, _ptr(rs), _ptr(ss),
                                                      _ptr(proofs), _ptr(inf), _ptr(g0), _ptr(pub), C.addressof(ms)))
-        return proofs, inf, g0, pub, dict(host_inputs_ms=float(ms[0]), witness_ms=float(ms[1]), prove_ms=float(ms[2]), call_ms=float(ms[3]))
+        return proofs, inf, g0, pub, _ms(ms, "host_inputs_ms", "witness_ms", "prove_ms", "call_ms")
 
     def prove(self, pk_h, r, s, r1cs, z):
         args, keep = self._csr(r1cs)

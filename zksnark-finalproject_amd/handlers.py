@@ -194,23 +194,94 @@ def _request(dev, rng, circ, r1cs, assignment, keep_key=False, overlap=False, ch
                 check_time=check_time, route="key")
 
 
-def _trapdoor_batch(dev, stack, rh, whs, num_instance, trap, g1, g2, rs, ss):
-    """The batch handlers' trapdoor route: the witness handles become the stack's to free, then one Device.prove_trapdoor_batch call
-    -> (proofs, inf, vk), or None when the call refused an unsatisfied assignment (the caller redoes the batch on the key route)."""
-    for wh in whs:
-        stack.callback(dev.witness_free, int(wh))
-    try:
-        return dev.prove_trapdoor_batch(rh, whs, num_instance, trap, g1, g2, rs, ss)
-    except Zkg16Error as e:
-        if e.status != ZKG16_ERR_UNSATISFIED:
-            raise
-        return None
+_Batch = collections.namedtuple("_Batch", "proofs inf side ms vk rs ss verdicts setup_time proving_time route")
 
 
-def _trapdoor_only_own_key(what, route, key):
+def _batch_checks(what, k, route, key):
+    """What a batch handler refuses before it shapes its input: an unknown route, route="trapdoor" with a caller's key, no requests."""
     if _route(route) == "trapdoor" and key is not None:
         raise ValueError(what + ": route='trapdoor' draws its own key (key must be None)")
-    return route == "trapdoor"
+    if k == 0:
+        raise ValueError(what + ": no requests")
+
+
+def _batch_request(dev, rng, k, key, route, r1cs, num_instance, witness_batch, prove_fused, check_on_device, check_apart):
+    """K requests of one batch handler under one key (after _batch_checks): draw the key, draw r and s per request, prove, release.
+    key: None, or the caller's (ph, rh, vk), which stays the caller's.  With None the key is drawn (_request's draws) and set up on
+    rh = r1cs(own), which passes a handle the request owns through own(free, handle) and a borrowed one (a cached shape's) not.
+    witness_batch() -> (witness handles, side output, ms) and prove_fused(ph, rh, rs, ss) -> (proofs, inf, side output, ms) are the
+    handler's two Device calls.  One of three ways to the proofs:
+      route "trapdoor" (key must be None): r and s are drawn before any device work, the assignments are made as handles and one
+        Device.prove_trapdoor_batch call answers without a key; setup_time stays 0.0.  If it refuses an unsatisfied assignment the
+        key is set up after all and the batch is redone below (with check_on_device on a second set of handles);
+      check_on_device: handles, Device.r1cs_check_batch, Device.prove_batch; check_apart takes the check out of proving_time;
+      else prove_fused.
+    -> _Batch; verdicts: None, or with check_on_device [(n_bad, first_bad)] * k ((0, None) when the trapdoor route answered, which
+    checks for itself); route: the one that answered."""
+    trapdoor = route == "trapdoor"
+    with contextlib.ExitStack() as stack:
+        def own(free, h):
+            stack.callback(free, h)
+            return h
+
+        def handles():
+            whs, side, ms = witness_batch()
+            for wh in whs:
+                own(dev.witness_free, int(wh))
+            return whs, side, ms
+        setup_time, got = 0.0, None
+        if key is None:
+            trap, g1, g2 = _draw_key(rng)
+            rh = r1cs(own)
+            if trapdoor:
+                rs, ss = _draw_rs_batch(rng, k)
+                t0 = time.perf_counter()
+                whs, side, ms = handles()
+                try:
+                    got = dev.prove_trapdoor_batch(rh, whs, num_instance, trap, g1, g2, rs, ss)
+                except Zkg16Error as e:
+                    if e.status != ZKG16_ERR_UNSATISFIED:
+                        raise
+            if got is None:
+                t0 = time.perf_counter()
+                ph, vk = dev.setup_resident(rh, num_instance, trap, g1, g2)
+                own(dev.pk_free, ph)
+                setup_time = time.perf_counter() - t0
+        else:
+            ph, rh, vk = key
+        if not trapdoor:
+            rs, ss = _draw_rs_batch(rng, k)
+        if got is None:
+            t0 = time.perf_counter()
+        verdicts, check_time = None, 0.0
+        if got is not None:
+            proofs, inf, vk = got
+            verdicts = [(0, None)] * k if check_on_device else None
+        elif check_on_device:
+            whs, side, ms = handles()
+            tc = time.perf_counter()
+            verdicts = dev.r1cs_check_batch(rh, whs)
+            if check_apart:
+                check_time = time.perf_counter() - tc
+            proofs, inf = dev.prove_batch(ph, rh, whs, rs, ss)
+        else:
+            proofs, inf, side, ms = prove_fused(ph, rh, rs, ss)
+        proving_time = time.perf_counter() - t0 - check_time
+    return _Batch(proofs, inf, side, ms, vk, rs, ss, verdicts, setup_time, proving_time, "key" if got is None else "trapdoor")
+
+
+def _batch_records(out, fields, detail):
+    """A batch's per-request records: fields(i) and detail(i) give what only the handler knows; the proof, the key's two encodings
+    (made once), "satisfied" (only when the device check ran) and the core of "_detail" are the same for every handler."""
+    vk_b64, pvk_b64 = wire.encode_vk(out.vk), wire.encode_pvk(out.vk)
+    records = []
+    for i in range(len(out.proofs)):
+        rec = dict(fields(i), proof=wire.encode_proof(out.proofs[i], out.inf[i]), pvk=pvk_b64, vk=vk_b64,
+                   _detail=dict(detail(i), proof=out.proofs[i], inf=out.inf[i], vk=out.vk, r=out.rs[i], s=out.ss[i], ms=out.ms, route=out.route))
+        if out.verdicts is not None:
+            rec["satisfied"] = out.verdicts[i][0] == 0
+        records.append(rec)
+    return records
 
 
 def _from_host(dev, circ):
@@ -294,54 +365,22 @@ def prove_matrices(dev, size, pairs, seed=0, key=None, check_on_device=False, ro
     proving_time the whole pass.  If the call refuses an unsatisfied assignment the whole batch is redone on the key route.
     _detail["route"] says which route answered."""
     k = len(pairs)
-    trapdoor = _trapdoor_only_own_key("prove_matrices", route, key)
-    if k == 0:
-        raise ValueError("prove_matrices: no requests")
+    _batch_checks("prove_matrices", k, route, key)
     a = np.stack([np.asarray(p[0], dtype=np.uint64).reshape(size, size) for p in pairs])
     b = np.stack([np.asarray(p[1], dtype=np.uint64).reshape(size, size) for p in pairs])
-    shape = _matrix_shape(dev, size)
-    rng = random.Random(seed)
-    with contextlib.ExitStack() as stack:
-        setup_time, answered, got = 0.0, "key", None
-        if key is None:
-            trap, g1, g2 = _draw_key(rng)
-            if trapdoor:
-                rs, ss = _draw_rs_batch(rng, k)
-                t0 = time.perf_counter()
-                whs, pubs, ms = dev.witness_matrix_batch(a, b)
-                got = _trapdoor_batch(dev, stack, shape.rh, whs, shape.num_instance, trap, g1, g2, rs, ss)
-            if got is None:
-                t0 = time.perf_counter()
-                ph, vk = dev.setup_resident(shape.rh, shape.num_instance, trap, g1, g2)
-                stack.callback(dev.pk_free, ph)
-                setup_time = time.perf_counter() - t0
-        else:
-            ph, vk = key
-        if not trapdoor:
-            rs, ss = _draw_rs_batch(rng, k)
-        if got is None:
-            t0 = time.perf_counter()
-        verdicts = None
-        if got is not None:
-            (proofs, inf, vk), answered = got, "trapdoor"
-            verdicts = [(0, None)] * k if check_on_device else None
-        elif check_on_device:
-            whs, pubs, ms = dev.witness_matrix_batch(a, b)
-            for wh in whs:
-                stack.callback(dev.witness_free, int(wh))
-            verdicts = dev.r1cs_check_batch(shape.rh, whs)
-            proofs, inf = dev.prove_batch(ph, shape.rh, whs, rs, ss)
-        else:
-            proofs, inf, pubs, ms = dev.prove_matrix_batch(ph, shape.rh, a, b, rs, ss)
-        proving_time = time.perf_counter() - t0
+    shape = _matrix_shape(dev, size)         # its rh is borrowed, with either key
+    out = _batch_request(dev, random.Random(seed), k, None if key is None else (key[0], shape.rh, key[1]), route,
+                         lambda own: shape.rh, shape.num_instance, lambda: dev.witness_matrix_batch(a, b),
+                         lambda ph, rh, rs, ss: dev.prove_matrix_batch(ph, rh, a, b, rs, ss), check_on_device, check_apart=False)
+    pubs = out.side
     requests = [dict(hash_a=wire.encode_hash(pubs[i][0]), hash_b=wire.encode_hash(pubs[i][1]), hash_c=wire.encode_hash(pubs[i][2]),
-                     proof=wire.encode_proof(proofs[i], inf[i])) for i in range(k)]
-    if verdicts is not None:
-        for q, (n_bad, _) in zip(requests, verdicts):
+                     proof=wire.encode_proof(out.proofs[i], out.inf[i])) for i in range(k)]
+    if out.verdicts is not None:
+        for q, (n_bad, _) in zip(requests, out.verdicts):
             q["satisfied"] = n_bad == 0
-    return dict(vk=wire.encode_vk(vk), pvk=wire.encode_pvk(vk), setup_time=setup_time, proving_time=proving_time,
+    return dict(vk=wire.encode_vk(out.vk), pvk=wire.encode_pvk(out.vk), setup_time=out.setup_time, proving_time=out.proving_time,
                 num_constraints_circuit=shape.num_constraints, num_variables=shape.num_instance, requests=requests,
-                _detail=dict(proofs=proofs, inf=inf, public_inputs=pubs, vk=vk, rs=rs, ss=ss, ms=ms, route=answered))
+                _detail=dict(proofs=out.proofs, inf=out.inf, public_inputs=pubs, vk=out.vk, rs=out.rs, ss=out.ss, ms=out.ms, route=out.route))
 
 
 def prove_fibonacci(dev, a, b, num_of_rounds, seed=42, keep_key=False, check_on_device=False, route="key"):
@@ -386,65 +425,20 @@ def prove_fibonaccis(dev, requests, num_of_rounds, seed=42, key=None, check_on_d
     route: "trapdoor" (only with key=None): prove_matrices' — Device.witness_fibonacci_batch, then one Device.prove_trapdoor_batch
     call; setup_time 0.0; a refused batch is redone on the key route; _detail["route"] says which route answered."""
     k = len(requests)
-    trapdoor = _trapdoor_only_own_key("prove_fibonaccis", route, key)
-    if k == 0:
-        raise ValueError("prove_fibonaccis: no requests")
+    _batch_checks("prove_fibonaccis", k, route, key)
     a = np.array([int(q[0]) for q in requests], dtype=np.uint64)
     b = np.array([int(q[1]) for q in requests], dtype=np.uint64)
-    rng = random.Random(seed)
-    own = key is None
-    with contextlib.ExitStack() as stack:
-        answered, got = "key", None
-        if trapdoor:
-            trap, g1, g2 = _draw_key(rng)
-            rh = dev.r1cs_fibonacci(num_of_rounds)
-            stack.callback(dev.r1cs_free, rh)
-            rs, ss = _draw_rs_batch(rng, k)
-            t0 = time.perf_counter()
-            whs, pubs, ms = dev.witness_fibonacci_batch(num_of_rounds, a, b)
-            got = _trapdoor_batch(dev, stack, rh, whs, 4, trap, g1, g2, rs, ss)
-            if got is None:
-                t0 = time.perf_counter()
-                ph, vk = dev.setup_resident(rh, 4, trap, g1, g2)
-                stack.callback(dev.pk_free, ph)
-                key = dict(ph=ph, rh=rh, vk=vk, setup_time=time.perf_counter() - t0)
-        elif own:
-            key = fibonacci_key(dev, num_of_rounds, rng)
-            stack.callback(dev.r1cs_free, key["rh"])
-            stack.callback(dev.pk_free, key["ph"])
-        if not trapdoor:
-            rs, ss = _draw_rs_batch(rng, k)
-        if got is None:
-            t0 = time.perf_counter()
-        verdicts, check_time = None, 0.0
-        if got is not None:
-            (proofs, inf, vk), answered = got, "trapdoor"
-            key = dict(vk=vk, setup_time=0.0)
-            verdicts = [(0, None)] * k if check_on_device else None
-        elif check_on_device:
-            whs, pubs, ms = dev.witness_fibonacci_batch(num_of_rounds, a, b)
-            for wh in whs:
-                stack.callback(dev.witness_free, int(wh))
-            tc = time.perf_counter()
-            verdicts = dev.r1cs_check_batch(key["rh"], whs)
-            check_time = time.perf_counter() - tc
-            proofs, inf = dev.prove_batch(key["ph"], key["rh"], whs, rs, ss)
-        else:
-            proofs, inf, pubs, ms = dev.prove_fibonacci_batch(key["ph"], key["rh"], num_of_rounds, a, b, rs, ss)
-        proving_time = time.perf_counter() - t0 - check_time
-    vk = key["vk"]
-    vk_b64, pvk_b64 = wire.encode_vk(vk), wire.encode_pvk(vk)
-    out = []
-    for i in range(k):
+    out = _batch_request(dev, random.Random(seed), k, None if key is None else (key["ph"], key["rh"], key["vk"]), route,
+                         lambda own: own(dev.r1cs_free, dev.r1cs_fibonacci(num_of_rounds)), 4,
+                         lambda: dev.witness_fibonacci_batch(num_of_rounds, a, b),
+                         lambda ph, rh, rs, ss: dev.prove_fibonacci_batch(ph, rh, num_of_rounds, a, b, rs, ss), check_on_device, check_apart=True)
+    pubs = out.side
+
+    def fields(i):
         circ = _DeviceCircuit(4, 1, num_of_rounds + 1, pubs[i])
-        rec = dict(proof=wire.encode_proof(proofs[i], inf[i]), proving_time=proving_time / k, setup_time=key["setup_time"] if own else 0.0,
-                   num_constraints=circ.num_constraints, num_variables=circ.num_instance, fib_number=wire.encode_hash(pubs[i][2]),
-                   pvk=pvk_b64, vk=vk_b64, _circuit=circ,
-                   _detail=dict(proof=proofs[i], inf=inf[i], vk=vk, r=rs[i], s=ss[i], public_inputs=pubs[i], ms=ms, route=answered))
-        if verdicts is not None:
-            rec["satisfied"] = verdicts[i][0] == 0
-        out.append(rec)
-    return out
+        return dict(proving_time=out.proving_time / k, setup_time=out.setup_time, num_constraints=circ.num_constraints,
+                    num_variables=circ.num_instance, fib_number=wire.encode_hash(pubs[i][2]), _circuit=circ)
+    return _batch_records(out, fields, lambda i: dict(public_inputs=pubs[i]))
 
 
 def verify_fibonaccis(vk, claims, proofs_b64, dev=None):
@@ -544,75 +538,29 @@ def prove_linear_equations_batch(dev, systems, seed=0, key=None, check_on_device
     call; setup_time 0.0; a batch holding a request its solver leaves unsatisfied is redone on the key route; _detail["route"] says
     which route answered."""
     k = len(systems)
-    trapdoor = _trapdoor_only_own_key("prove_linear_equations_batch", route, key)
+    _batch_checks("prove_linear_equations_batch", k, route, key)
     how = {} if linear_solver_id(solver) == 0 else dict(solver=solver)        # "forward": the Device calls as they always were
-    if k == 0:
-        raise ValueError("prove_linear_equations_batch: no requests")
     reqs = [_linear_request("prove_linear_equations_batch", a, b) for a, b in systems]
     n = reqs[0][1].shape[0]
     if any(q[1].shape[0] != n for q in reqs):
         raise ValueError("prove_linear_equations_batch: every system of a batch has one size")
     a, b = np.stack([q[0] for q in reqs]), np.stack([q[1] for q in reqs])
-    rng = random.Random(seed)
-    own = key is None
-    with contextlib.ExitStack() as stack:
-        answered, got = "key", None
-        if trapdoor:
-            trap, g1, g2 = _draw_key(rng)
-            rh = dev.r1cs_linear(n)
-            stack.callback(dev.r1cs_free, rh)
-            rs, ss = _draw_rs_batch(rng, k)
-            t0 = time.perf_counter()
-            whs, xs, ms = dev.witness_linear_batch(a, b, **how)
-            got = _trapdoor_batch(dev, stack, rh, whs, 1 + n * (n + 1), trap, g1, g2, rs, ss)
-            if got is None:
-                t0 = time.perf_counter()
-                ph, vk = dev.setup_resident(rh, 1 + n * (n + 1), trap, g1, g2)
-                stack.callback(dev.pk_free, ph)
-                key = dict(ph=ph, rh=rh, vk=vk, setup_time=time.perf_counter() - t0)
-        elif own:
-            key = linear_key(dev, n, rng)
-            stack.callback(dev.r1cs_free, key["rh"])
-            stack.callback(dev.pk_free, key["ph"])
-        if not trapdoor:
-            rs, ss = _draw_rs_batch(rng, k)
-        if got is None:
-            t0 = time.perf_counter()
-        verdicts, check_time = None, 0.0
-        if got is not None:
-            (proofs, inf, vk), answered = got, "trapdoor"
-            key = dict(vk=vk, setup_time=0.0)
-            verdicts = [(0, None)] * k if check_on_device else None
-        elif check_on_device:
-            whs, xs, ms = dev.witness_linear_batch(a, b, **how)
-            for wh in whs:
-                stack.callback(dev.witness_free, int(wh))
-            tc = time.perf_counter()
-            verdicts = dev.r1cs_check_batch(key["rh"], whs)
-            check_time = time.perf_counter() - tc
-            proofs, inf = dev.prove_batch(key["ph"], key["rh"], whs, rs, ss)
-        else:
-            proofs, inf, xs, ms = dev.prove_linear_batch(key["ph"], key["rh"], a, b, rs, ss, **how)
-        proving_time = time.perf_counter() - t0 - check_time
-    vk = key["vk"]
-    vk_b64, pvk_b64 = wire.encode_vk(vk), wire.encode_pvk(vk)
+    out = _batch_request(dev, random.Random(seed), k, None if key is None else (key["ph"], key["rh"], key["vk"]), route,
+                         lambda own: own(dev.r1cs_free, dev.r1cs_linear(n)), 1 + n * (n + 1), lambda: dev.witness_linear_batch(a, b, **how),
+                         lambda ph, rh, rs, ss: dev.prove_linear_batch(ph, rh, a, b, rs, ss, **how), check_on_device, check_apart=True)
     pubs = np.stack([_linear_public_inputs(a[i], b[i]) for i in range(k)])
     t0 = time.perf_counter()
-    _, each = device.verify_batch_host(device.pvk_prepare(vk), pubs, np.asarray(proofs, dtype=np.uint64), np.asarray(inf, dtype=np.uint8), each=True)
+    _, each = device.verify_batch_host(device.pvk_prepare(out.vk), pubs, np.asarray(out.proofs, dtype=np.uint64), np.asarray(out.inf, dtype=np.uint8),
+                                       each=True)
     verifying_time = time.perf_counter() - t0
     dims = linear_r1cs_dims(n)
-    out = []
-    for i in range(k):
+
+    def fields(i):
         circ = _DeviceCircuit(dims["num_instance"], dims["num_witness"], dims["num_constraints"], pubs[i])
-        rec = dict(proof=wire.encode_proof(proofs[i], inf[i]), public_input=[wire.encode_hash(x) for x in pubs[i]],
-                   num_constraints=circ.num_constraints, num_variables=circ.num_instance, proving_time=proving_time / k,
-                   verifying_time=verifying_time / k, valid=bool(each[i]), pvk=pvk_b64, vk=vk_b64, _circuit=circ,
-                   _detail=dict(proof=proofs[i], inf=inf[i], vk=vk, r=rs[i], s=ss[i], public_inputs=pubs[i], x=xs[i], ms=ms,
-                                setup_time=key["setup_time"] if own else 0.0, route=answered))
-        if verdicts is not None:
-            rec["satisfied"] = verdicts[i][0] == 0
-        out.append(rec)
-    return out
+        return dict(public_input=[wire.encode_hash(x) for x in pubs[i]], num_constraints=circ.num_constraints,
+                    num_variables=circ.num_instance, proving_time=out.proving_time / k, verifying_time=verifying_time / k,
+                    valid=bool(each[i]), _circuit=circ)
+    return _batch_records(out, fields, lambda i: dict(public_inputs=pubs[i], x=out.side[i], setup_time=out.setup_time))
 
 
 def verify_linear_equations(vk, systems, proofs_b64, dev=None):
