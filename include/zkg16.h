@@ -1000,6 +1000,9 @@ ZKG16_API void zkg16_kernel_stats_reset(zkg16_ctx *ctx);
  *   "collect_threads" host combination of the z-side MSMs' window sums: 0 = own threads for plain keys, 1 = always, 2 = never
  *   "fixed_base_bits" window width of the setup's fixed-base multiplications (0 = by batch size; 16 / 18 / 20 = two-level tables)
  *   "g2_lazy"        G2 accumulation's Fq2 products: 0 / 1 (default) two fused two-product reductions with operands parked in LDS, 2 = Karatsuba
+ *   "g2_split"       G2 accumulation: 1 (default) = every Fq2 value split over a pair of lanes, two waves per SIMD; 0 = one lane per point
+ *                    (same proofs byte for byte; "acc_pipeline" bit 1, "g2_lazy" = 2 and "acc_debug" keep their one-lane loops)
+ *   "g2_split_form"  the split loop's field products: 0 / 2 (default) = inlined, 1 = device-function calls
  *   "g1_inline"      G1 accumulation (plain loop): 0 / 1 (default) every field product inlined, no call; 2 = products as device-function calls
  *   "acc_lazy"       the default G1 / G2 accumulation loops: 1 (default) = mixed additions without the carry passes their results do not
  *                    need, 0 = the earlier additions (same sums; for A/B runs)

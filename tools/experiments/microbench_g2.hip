@@ -1,4 +1,5 @@
-// G2 mixed addition, one lane per point (Karatsuba and one-reduction forms) against the pair-split form (g2split.cuh): the split
+// G2 mixed addition, one lane per point (Karatsuba and one-reduction forms) against the pair-split form (csrc/g2split.cuh, the header
+// the product's split accumulation kernel uses; products as calls, the earlier addition: h2_madd<false> over H2Lane<false>): the split
 // form's results are checked against the one-lane form (as group elements), then the bare loops are timed.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -I zksnark-finalproject_amd/csrc tools/experiments/microbench_g2.hip -o tools/bin/microbench_g2
 #include <hip/hip_runtime.h>
@@ -8,6 +9,7 @@
 #include <vector>
 #include "g2split.cuh"
 using namespace zk;
+using SplitLane = H2Lane<false>;
 #define CHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP error %s at %s:%d\n", hipGetErrorString(e_), __FILE__, __LINE__); return 1; } } while (0)
 constexpr int ITERS = 64;
 
@@ -33,13 +35,13 @@ __global__ void __launch_bounds__(64, 1) k_check_one(XYZZ<Fq2U> *out, int steps)
 }
 __global__ void __launch_bounds__(64, 2) k_check_split(XYZZ<Fq2U> *out, int steps) {
     const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x, s = tid >> 1;
-    const int h = tid & 1;
-    H2XYZZ acc = h2_inf();
+    const SplitLane m{(int)(tid & 1)};
+    H2XYZZ<SplitLane> acc = h2_inf(m);
     for (int t = 0; t < steps; t++) {
         const Affine<Fq2U> p = rnd_pt(pt_seed(s, t));
-        h2_madd(acc, H2Affine{h ? p.x.c1 : p.x.c0, h ? p.y.c1 : p.y.c0}, pt_neg(t), h);
+        h2_madd<false>(m, acc, H2Affine<SplitLane>{m.h ? p.x.c1 : p.x.c0, m.h ? p.y.c1 : p.y.c0}, pt_neg(t));
     }
-    h2_st_xyzz(out + s, acc, h);
+    h2_st_xyzz(m, out + s, acc);
 }
 template <bool LAZY>
 __global__ void __launch_bounds__(64, 1) k_madd_one(uint32_t *out, uint32_t seed) {
@@ -50,11 +52,11 @@ __global__ void __launch_bounds__(64, 1) k_madd_one(uint32_t *out, uint32_t seed
 }
 template <int MINB>
 __global__ void __launch_bounds__(64, MINB) k_madd_split(uint32_t *out, uint32_t seed) {
-    const int h = threadIdx.x & 1;
+    const SplitLane m{(int)(threadIdx.x & 1)};
     const Affine<Fq2U> p = rnd_pt(seed);
-    H2XYZZ acc{FqU::one(), FqU::one(), h2_one(h), h2_one(h)};
-    const H2Affine q{h ? p.x.c1 : p.x.c0, h ? p.y.c1 : p.y.c0};
-    for (int it = 0; it < ITERS; it++) h2_madd(acc, q, (it & 1) != 0, h);
+    H2XYZZ<SplitLane> acc{FqU::one(), FqU::one(), m.one(), m.one()};
+    const H2Affine<SplitLane> q{m.h ? p.x.c1 : p.x.c0, m.h ? p.y.c1 : p.y.c0};
+    for (int it = 0; it < ITERS; it++) h2_madd<false>(m, acc, q, (it & 1) != 0);
     out[blockIdx.x * blockDim.x + threadIdx.x] = acc.x.l[0] ^ seed;
 }
 

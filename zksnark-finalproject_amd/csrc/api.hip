@@ -387,6 +387,11 @@ int set_option_one(zkg16_ctx *ctx, const char *name, int64_t v) {
     if (is("g2_lazy")) return set(o.g2_lazy, 0, 2, v == 2 ? 0 : 1);
     // G1 bucket accumulation (plain loop): 0 / 1 (default) = every field product inlined, 2 = products as device-function calls (the earlier loop)
     if (is("g1_inline")) return set(o.g1_inline, 0, 2, v == 2 ? 0 : 1);
+    // G2 bucket accumulation: 1 (default) = every Fq2 value split over a pair of lanes (component 0 on the even lane, 1 on the odd one),
+    // two waves per SIMD; 0 = one lane per point.  Proofs are byte-identical; stored bucket representatives may differ within their bounds
+    if (is("g2_split")) return set(o.g2_split, 0, 1, v);
+    // ... and the products of its loop: 0 / 2 (default) = inlined, 1 = device-function calls
+    if (is("g2_split_form")) return set(o.g2_split_form, 0, 2, v == 2 ? 0 : v);
     // default G1 / G2 bucket accumulation loops: 1 (default) = mixed additions without the carry passes their results do not need,
     // 0 = the earlier additions (xyzz_madd_inline, xyzz_madd_lazy)
     if (is("acc_lazy")) return set(o.acc_lazy, 0, 1, v);

@@ -356,6 +356,8 @@ struct zkg16_ctx {
         int fixed_base_bits = 0;                      // setup's fixed-base window width (0 = by batch size; even widths >= 16 are built in two levels)
         int g2_lazy = 1;                              // G2 accumulation: Fq2 products with one reduction per component, operands parked in LDS (ffu.cuh: fq2u_mul_lazy)
         int acc_lazy = 1;                             // default G1 / G2 accumulation loops: the mixed addition without the carry passes its results do not need (ec.cuh: xyzz_madd_inline_lc, xyzz_madd_lazy_lc); 0: xyzz_madd_inline / xyzz_madd_lazy
+        int g2_split = 1;                             // G2 accumulation with every Fq2 value split over a lane pair, two waves per SIMD (g2split.cuh; msm.hip: msm_accumulate_split_kernel); acc_lazy selects its addition; acc_pipeline bit 1 and g2_lazy = 2 keep their one-lane loops; 0: the one-lane loop
+        int g2_split_form = 0;                        // the split loop's products: 0 / 2 = inlined (default), 1 = device-function calls (msm.hip: g2_split_form)
         int g1_inline = 1;                            // G1 accumulation (plain loop): every field product inlined (ec.cuh: xyzz_madd_inline); 0: products as calls
         int matrix_parts = 0;                         // zkg16_prove_matrix: gadget slices the assignment arrives in (0 = five growing slices, k = k equal ones, 1 = no overlap)
         int matrix_slice_min = MATRIX_SLICE_MIN_DEFAULT;      // zkg16_prove_matrix: the slice count is lowered until a slice holds this many permutations (tests set 1)
@@ -462,7 +464,7 @@ struct MsmPlan {
     bool tabled = false;     // the bases are a window table [nwin_digits][n] (msm_tables_build): every digit lands in ONE bucket set
     size_t nb = 0;           // buckets per window = 2^(c-1)
     size_t total_entries = 0;            // upper bound n * windows (the exact count lives on the device)
-    uint32_t lanes_g1 = 0, lanes_g2 = 0; // lanes of one resident round of accumulation waves (2 / 1 waves per SIMD)
+    uint32_t lanes_g1 = 0, lanes_g2 = 0; // lanes of one resident round of accumulation waves (2 waves per SIMD; G2: one wave of 64 one-lane segments or two waves of 32 lane pairs)
     int batch = 1;           // scalar vectors (zkg16_prove_batch): nwin = batch x the windows of one
 };
 void msm_plan_build(zkg16_ctx *ctx, MsmWorkspace &ws, const Fr *scalars_canonical, size_t n, MsmPlan &plan, int window_bits = 0);

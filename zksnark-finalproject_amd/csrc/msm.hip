@@ -23,6 +23,7 @@
 #include <chrono>
 
 #include "common.hpp"
+#include "g2split.cuh"
 
 namespace zk {
 
@@ -365,6 +366,74 @@ __global__ void __launch_bounds__(64, FieldTraits<F>::g2 ? 1 : 2) msm_accumulate
     }
     a.seg_meta[2 * t] = head_b;
     a.seg_meta[2 * t + 1] = tail_b;
+}
+
+// ---- G2 with every Fq2 value split over a lane pair (g2split.cuh; option "g2_split"): lane 2t holds component 0 and lane 2t + 1
+// component 1 of segment t's running sum and base, so per-lane state is G1-sized and two waves fit on a SIMD.  Segments, their
+// partial sums, seg_meta and everything downstream are those of msm_accumulate_kernel<Fq2U>: twice the lanes at half the width make
+// the same number of segments (num_cus * 4 SIMDs * 2 waves * 32 pairs = plan.lanes_g2).  Every branch is taken by both lanes of a
+// pair together: the segment bounds, the entry and its sign are the pair's, and the tests on field values go through H2Lane::both.
+// Both lanes read the same entry; lane h loads and stores component h of each coordinate (8-byte accesses: component 1 starts at a
+// multiple of 8 bytes); seg_meta is written by the even lane.  The timing probes of AccArgs::debug are not implemented here
+// (msm_launch_accumulate: a ctx with "acc_debug" set runs the one-lane kernel).
+// LC: the addition without the carry passes its results do not need (h2_madd<true>); INL: products inlined instead of called.
+// Gathering the next base one addition ahead, as G1's inlined loop does, was tried on the inlined form and changed nothing (32.76
+// against 32.73 ms per launch at 128x128, profiles/g2_split_ab.txt: the second wave already covers the gather), so it is not kept.
+template <class F> __device__ __forceinline__ const Affine<F> *base_ptr(const Affine<F> *b, uint32_t i) { return b + i; }
+template <class F> __device__ __forceinline__ const Affine<F> *base_ptr(const PadAffine<F> *b, uint32_t i) { return &b[i].p; }
+
+template <class BASE, bool LC, bool INL>
+__global__ void __launch_bounds__(64, 2) msm_accumulate_split_kernel(AccArgs<Fq2U> a) {
+    using M = H2Lane<INL>;
+    const BASE *const bases = static_cast<const BASE *>(a.bases);
+    const uint32_t t = (blockIdx.x * 64u + threadIdx.x) >> 1;
+    const M m{(int)(threadIdx.x & 1u)};
+    const uint32_t total = *a.total_ptr;
+    const uint32_t seg_len = *a.seg_len_ptr;
+    const uint32_t start = t * seg_len;
+    if (start >= total) return;
+    const uint32_t end = start + seg_len < total ? start + seg_len : total;
+    uint2 en = a.entries[start];
+    const uint32_t g_first = en.y;
+    const bool head_open = start > 0 && a.entries[start - 1].y == g_first;
+    const uint32_t g_after = end < total ? a.entries[end].y : 0xffffffffu;
+    int32_t head_b = -1, tail_b = -1;
+    H2XYZZ<M> acc = h2_inf(m);
+    uint32_t cur = g_first;
+    // the round-1 loop: the base is gathered right before its addition; the second wave of the SIMD runs meanwhile
+    uint32_t e = en.x, gb = en.y;
+    for (uint32_t p = start; p < end; p++) {
+        if (p + 1 < end) en = a.entries[p + 1];
+        const uint32_t e_n = en.x, g_n = en.y;
+        if (gb != cur) {
+            if (cur == g_first && head_open) {
+                head_b = (int32_t)cur;
+                h2_st_xyzz(m, a.seg_head + t, acc);
+            } else if (!h2_is_inf(m, acc)) {
+                h2_st_xyzz(m, a.buckets + cur, acc);
+            }
+            acc = h2_inf(m);
+            cur = gb;
+        }
+        const H2Affine<M> b = h2_ld_affine(m, base_ptr(bases, e >> 1));
+        // P = Q: the base is fetched again for the doubling, so it is not live across the addition's products
+        if (!h2_madd_nd<LC>(m, acc, b, (e & 1u) != 0)) acc = h2_dbl_term(m, h2_ld_affine(m, base_ptr(bases, e >> 1)), (e & 1u) != 0);
+        e = e_n;
+        gb = g_n;
+    }
+    if (cur == g_first && head_open) {
+        head_b = (int32_t)cur;
+        h2_st_xyzz(m, a.seg_head + t, acc);
+    } else if (cur == g_after) {
+        tail_b = (int32_t)cur;
+        h2_st_xyzz(m, a.seg_tail + t, acc);
+    } else if (!h2_is_inf(m, acc)) {
+        h2_st_xyzz(m, a.buckets + cur, acc);
+    }
+    if (m.h == 0) {
+        a.seg_meta[2 * t] = head_b;
+        a.seg_meta[2 * t + 1] = tail_b;
+    }
 }
 
 // One lane per segment whose last bucket spills over: add the head partials of the following segments.
@@ -846,6 +915,8 @@ void msm_plan_build(zkg16_ctx *ctx, MsmWorkspace &ws, const ScalarSrc &src, MsmP
     // G1: two waves per SIMD, four from 2^25 terms on (124 registers: four fit; the extra waves hide what is left of the gather
     // latency — 128x128: 163.0 -> 160.8 ms; no change at 32x32, where a lane would get ~25 terms)
     plan.lanes_g1 = (uint32_t)ctx->num_cus * 4u * (uint32_t)(ctx->opt.g1_waves > 0 ? ctx->opt.g1_waves : tot >= ((size_t)1 << 25) ? 4 : 2) * 64u;
+    // G2 segments of one resident round: one wave of 64 one-lane segments per SIMD, or two waves of 32 lane pairs (g2_split; its
+    // __launch_bounds__(64, 2) is the occupancy msm_acc_resident_waves reports): the same count, so the plan does not depend on the option
     plan.lanes_g2 = (uint32_t)ctx->num_cus * 4u * 1u * 64u;
     ws.last_lanes_g1 = plan.lanes_g1;
     ws.seg_params.ensure(2 * sizeof(uint32_t));
@@ -1047,11 +1118,34 @@ __global__ void __launch_bounds__(64, FieldTraits<F>::g2 ? 1 : 2) msm_bucket_mer
     stv(sum + i, a);
 }
 
+// The split G2 loop the options select (instantiations of msm_accumulate_split_kernel<BASE, LC, INL>):
+//   0  products as calls, the earlier addition (acc_lazy = 0 always runs this one)
+//   1  products as calls, the addition without its spare carry passes ("g2_split_form" = 1)
+//   2  products inlined, the addition without its spare carry passes ("g2_split_form" = 2, and 0: it measured fastest,
+//      profiles/g2_split_ab.txt)
+// The loops asked for by name keep their one-lane kernels: acc_pipeline bit 1 and g2_lazy = 2 (Karatsuba).
+// The timing probes of "acc_debug" exist in the one-lane kernels only, so a ctx that sets them runs those.
+static bool g2_split_on(const zkg16_ctx *ctx) { return ctx->opt.g2_split && ctx->opt.g2_lazy && !(ctx->opt.acc_pipeline & 2) && !ctx->opt.acc_debug; }
+static int g2_split_form(const zkg16_ctx *ctx) {
+    if (!ctx->opt.acc_lazy) return 0;
+    return ctx->opt.g2_split_form == 1 ? 1 : 2;
+}
+
 // the accumulation variant the options select, for entries of type BASE
 template <class F, class BASE>
 static void msm_launch_accumulate(zkg16_ctx *ctx, unsigned grid, const AccArgs<F> &a) {
     const bool pipe = (ctx->opt.acc_pipeline >> (FieldTraits<F>::g2 ? 1 : 0)) & 1;
     const bool lc = ctx->opt.acc_lazy != 0;      // only the default loops have the form without the spare carry passes
+    if constexpr (FieldTraits<F>::g2) {
+        if (g2_split_on(ctx)) {      // one pair of lanes per segment: twice the blocks for the same segments
+            switch (g2_split_form(ctx)) {
+                case 0: hipLaunchKernelGGL((msm_accumulate_split_kernel<BASE, false, false>), dim3(2 * grid), dim3(64), 0, ctx->stream, a); break;
+                case 1: hipLaunchKernelGGL((msm_accumulate_split_kernel<BASE, true, false>), dim3(2 * grid), dim3(64), 0, ctx->stream, a); break;
+                default: hipLaunchKernelGGL((msm_accumulate_split_kernel<BASE, true, true>), dim3(2 * grid), dim3(64), 0, ctx->stream, a); break;
+            }
+            return;
+        }
+    }
     if (pipe) {
         hipLaunchKernelGGL((msm_accumulate_kernel<F, BASE, true>), dim3(grid), dim3(64), 0, ctx->stream, a);
     } else if constexpr (FieldTraits<F>::g2) {
@@ -1330,13 +1424,20 @@ void msm_slot_wait(MsmSlot &slot) {
     if (slot.active) ZK_HIP(hipEventSynchronize(slot.red_done));
 }
 
-// Waves of the shipped accumulation kernels one SIMD can hold at once (registers: 255 for G1, 478 for G2 in this build): what the
+// Waves of the shipped accumulation kernels one SIMD can hold at once (registers: 255 for G1; G2: 218 per lane of the split kernel, two
+// waves, 478 for the one-lane kernel, one wave): what the
 // bare-loop comparison of bench.py has to be read against, beside the waves per SIMD the grid is sized for (zkg16_last_acc_waves).
 int msm_acc_resident_waves(zkg16_ctx *ctx, bool g2) {
     int blocks = 0;
     const bool pipe = (ctx->opt.acc_pipeline >> (g2 ? 1 : 0)) & 1;
     hipError_t e;
-    if (g2) {
+    if (g2 && g2_split_on(ctx)) {
+        switch (g2_split_form(ctx)) {
+            case 0: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, msm_accumulate_split_kernel<Affine<Fq2U>, false, false>, 64, 0); break;
+            case 1: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, msm_accumulate_split_kernel<Affine<Fq2U>, true, false>, 64, 0); break;
+            default: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, msm_accumulate_split_kernel<Affine<Fq2U>, true, true>, 64, 0); break;
+        }
+    } else if (g2) {
         if (pipe) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, msm_accumulate_kernel<Fq2U, Affine<Fq2U>, true>, 64, 0);
         else if (ctx->opt.g2_lazy && ctx->opt.acc_lazy) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, msm_accumulate_kernel<Fq2U, Affine<Fq2U>, false, true, false, true>, 64, 0);
         else if (ctx->opt.g2_lazy) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, msm_accumulate_kernel<Fq2U, Affine<Fq2U>, false, true>, 64, 0);
