@@ -129,6 +129,28 @@ ZKG16_API int zkg16_shard_plan(int n_ranks, size_t m_total, size_t n_h, double b
 /* The same plan with the cost factors of shards that carry window tables (window_tables != 0; zkg16_pk_precompute on every shard). */
 ZKG16_API int zkg16_shard_plan_tables(int n_ranks, size_t m_total, size_t n_h, double b_density, int h_ranks, const float *z_cost,
                             int window_tables, uint64_t *ranges, uint8_t *blinding, int *h_ranks_out);
+/* Is every element of a resident key a point of its group?  What ark's ProvingKey::deserialize_compressed answers with Validate::Yes:
+ * each point of the five queries satisfies the curve equation and lies in the prime-order subgroup (zkg16_point_check's rule; the
+ * point at infinity passes), tested on the device where the key lies, one GPU lane per point.  Any handle: a whole key, a shard of
+ * zkg16_pk_load_range / zkg16_pk_slice (the ranges it holds), with or without window tables at either entry stride.
+ * Queries in the order a, b_g1, b_g2, h, l: n_bad[q] = points of query q that failed, first_bad[q] = the smallest index of one in the
+ * whole key's numbering (UINT64_MAX where n_bad[q] is 0).  The three trailing blinding slots are copies of the single points and are
+ * not counted.  single_mask: bit 0..4 set when alpha_g1, beta_g1, beta_g2, delta_g1, delta_g2 is at infinity or fails
+ * zkg16_point_check (host).  *ok = 1 iff nothing failed.  A bad key is an answer: ZKG16_OK with *ok = 0.
+ * NOT answered: whether it is the right key (the queries against an R1CS or a verifying key, pairing relations between b_g1 and
+ * b_g2 or among alpha, beta, delta).  Option "pk_validate" runs this inside zkg16_pk_load / zkg16_pk_load_range. */
+ZKG16_API int zkg16_pk_check(zkg16_ctx *ctx, uint64_t pk_handle, uint64_t n_bad[5], uint64_t first_bad[5], uint32_t *single_mask, int *ok);
+/* Stage entry (tests / tools) of the same kernels: n host points of one group (1 = G1, 12 u64 each; 2 = G2, 24 u64) in the limbs of
+ * zkg16_point_check_batch, inf nullable; uploaded and converted as a key's queries are.  *n_bad = points that fail
+ * zkg16_point_check, *first_bad = the smallest index of one (UINT64_MAX: none).  n == 0 is ZKG16_OK with (0, UINT64_MAX). */
+ZKG16_API int zkg16_points_check_bulk(zkg16_ctx *ctx, int group, const uint64_t *points, const uint8_t *inf, size_t n, uint64_t *n_bad,
+                            uint64_t *first_bad);
+/* The last key check on this ctx (zkg16_pk_check, or a load under option "pk_validate") and the last zkg16_points_check_bulk, in ms:
+ * [0..4] the kernels of a, b_g1, b_g2, h, l (device events on the streams they ran on: they overlap, so they sum to more than the
+ * call; 0 for an empty range), [5] total wall of the check with its one synchronisation (host clock); [6] the kernel of the last
+ * zkg16_points_check_bulk (device events), [7] the upload and conversion in front of it (host clock).  Returns the number of
+ * entries written (at most cap). */
+ZKG16_API int zkg16_pk_check_timings(zkg16_ctx *ctx, float *ms, int cap);
 ZKG16_API void zkg16_pk_free(zkg16_ctx *ctx, uint64_t pk_handle);
 
 /* ---- device groups: several ctxs of ONE process (one per GPU; several may share a GPU) proving one proof together.
@@ -1032,6 +1054,10 @@ ZKG16_API void zkg16_kernel_stats_reset(zkg16_ctx *ctx);
  *   "check_satisfied" 0 (default) = the proving calls prove whatever they are handed; 1 = they check their assignments on the device
  *                    and return ZKG16_ERR_UNSATISFIED, writing nothing, when one fails (zkg16_r1cs_check above; zkg16_last_check); any
  *                    other value: ZKG16_ERR_BAD_ARG.  The one option that can change what a call returns — for assignments no verifier accepts
+ *   "pk_validate"    0 (default) = zkg16_pk_load / zkg16_pk_load_range copy the key they are handed; 1 = they run zkg16_pk_check on the
+ *                    uploaded key before the handle exists: a key with a bad point returns ZKG16_ERR_BAD_ARG, *pk_handle is not
+ *                    written, the key's device buffers are released and zkg16_last_error names the query and the index
+ *                    (e.g. "h_query[63]") or the single point; any other value: ZKG16_ERR_BAD_ARG
  *   "sponge_chain_segment" permutations of a chain per launch of the chain kernel (0 = 256, else 1..65535): the state is carried between launches
  *   "rerandomize_min" zkg16_rerandomize_batch[_wire]: shorter batches are answered by the host form (1 = always the device, 0 restores
  *                    the default).  Default 256: the smallest measured K at which both device forms beat the host form on eight

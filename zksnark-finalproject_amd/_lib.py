@@ -107,6 +107,9 @@ SIGNATURES = {
     "zkg16_points_decompress_batch":(C.c_int, [ctxp, C.c_int, vp, sz, vp, vp, C.c_int, C.POINTER(C.c_int)]),
     "zkg16_miller_loop_batch": (C.c_int, [ctxp, vp, vp, vp, vp, sz, vp]),
     "zkg16_point_check_batch": (C.c_int, [ctxp, C.c_int, vp, vp, sz, vp]),
+    "zkg16_pk_check": (C.c_int, [ctxp, C.c_uint64, vp, vp, C.POINTER(C.c_uint32), C.POINTER(C.c_int)]),
+    "zkg16_pk_check_timings": (C.c_int, [ctxp, C.POINTER(C.c_float), C.c_int]),
+    "zkg16_points_check_bulk": (C.c_int, [ctxp, C.c_int, vp, vp, sz, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "zkg16_final_exp": (C.c_int, [u64p, u64p]),
     "zkg16_verify_each": (C.c_int, [ctxp, vp, sz, vp, vp, vp, sz, vp, vp, vp, sz, vp]),
     "zkg16_final_exp_batch": (C.c_int, [ctxp, vp, sz, vp]),

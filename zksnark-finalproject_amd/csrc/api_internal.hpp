@@ -62,6 +62,15 @@ enum RerandomizeTiming : int {
     R_HOST_FORM = 7,       // 1 when the host form answered
     R_COUNT = 8
 };
+// ---- zkg16_ctx::pkc_timings (zkg16_pk_check_timings), ABI as well
+enum PkCheckTiming : int {
+    K_A = 0, K_B1 = 1, K_B2 = 2, K_H = 3, K_L = 4,      // the kernel of each query of the last key check (device events on the streams they ran on: they overlap)
+    K_TOTAL = 5,           // wall time of that check, its one synchronisation included
+    K_BULK_KERNEL = 6,     // the last zkg16_points_check_bulk: its kernel (device events)
+    K_BULK_UPLOAD = 7,     // ... and the upload and conversion in front of it (host clock)
+    K_COUNT = 8
+};
+static_assert(K_COUNT == PK_CHECK_TIMING_SLOTS, "timing slots");
 static_assert(T_COUNT <= PROOF_TIMING_SLOTS && V_COUNT == VERIFY_TIMING_SLOTS && R_COUNT == RERANDOMIZE_TIMING_SLOTS, "timing slots");
 // the last refusal of a host-only entry point on this thread (zkg16_last_error(NULL)); api.hip
 std::string &host_last_error();
@@ -164,6 +173,20 @@ void upload_h2d(zkg16_ctx *ctx, void *dst, const void *src, size_t bytes);
 int r1cs_create(const uint64_t *const rp[3], const uint32_t *const col[3], const uint64_t *const cf[3], size_t num_instance,
                 size_t num_constraints, size_t num_variables, std::unique_ptr<R1csDev> &out);
 void r1cs_copy(zkg16_ctx *ctx, R1csDev &r, const uint64_t *const rp[3], const uint32_t *const col[3], const uint64_t *const cf[3]);
+
+// ---- membership of resident points (pk_check.hip; kernels: pk_check_dev.cuh).  Launches on `st`, nothing synchronises.
+// res: two device words per array, {number of bad points, smallest bad index}; pk_check_init_launch writes {0, UINT64_MAX} into
+// `slots` of them, pk_check_launch folds the verdicts of n U-form affine entries at base + i * stride (bytes) into one
+void pk_check_init_launch(hipStream_t st, uint64_t *res, int slots);
+void pk_check_launch(hipStream_t st, int group, const void *base, size_t stride, size_t n, const VbEndo &en, uint64_t *res);
+// The five queries of a resident key or shard (a, b_g1, b_g2, h, l) and its five single points (api_keys.hip): what zkg16_pk_check
+// returns.  One synchronisation
+struct PkCheckResult {
+    uint64_t n_bad[5], first_bad[5];
+    uint32_t single_mask;
+    bool ok() const { return !single_mask && !(n_bad[0] | n_bad[1] | n_bad[2] | n_bad[3] | n_bad[4]); }
+};
+void pk_check_run(zkg16_ctx *ctx, const PkDev &pk, PkCheckResult &out);
 
 // events of one proof, destroyed on every exit path
 struct EventSet {

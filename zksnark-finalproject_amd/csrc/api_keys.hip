@@ -133,6 +133,71 @@ void r1cs_copy(zkg16_ctx *ctx, R1csDev &r, const uint64_t *const rp[3], const ui
         }
     }
 }
+
+// ---- zkg16_pk_check: every point of a resident key or shard against zkg16_point_check's rule, where the key lies
+static const char *const PK_QUERY_NAMES[5] = {"a_query", "b_g1_query", "b_g2_query", "h_query", "l_query"};
+static const char *const PK_SINGLE_NAMES[5] = {"alpha_g1", "beta_g1", "beta_g2", "delta_g1", "delta_g2"};
+template <class A>
+static bool single_good(const A &p, int group) {
+    if (p.is_inf()) return false;      // a key's single points are generators' multiples by non-zero trapdoors: infinity is a broken key
+    uint64_t limbs[sizeof(A) / 8];
+    memcpy(limbs, &p, sizeof p);
+    int ok = 0;
+    return zkg16_point_check(group, limbs, &ok) == ZKG16_OK && ok;
+}
+void pk_check_run(zkg16_ctx *ctx, const PkDev &pk, PkCheckResult &out) {
+    const size_t nz = pk.z_hi - pk.z_lo, nh = pk.h_hi - pk.h_lo;
+    // level 0 of a window table is the query itself, at the table's entry stride; the three trailing blinding slots are copies of
+    // delta (checked below from the host copies) and are left out
+    const size_t s1z = pk.pad_z_g1 ? (size_t)ZKG16_TABLE_STRIDE_PADDED_G1 : sizeof(G1AffineU), s2z = pk.pad_z_g2 ? (size_t)ZKG16_TABLE_STRIDE_PADDED_G2 : sizeof(G2AffineU);
+    const size_t s1h = pk.pad_h ? (size_t)ZKG16_TABLE_STRIDE_PADDED_G1 : sizeof(G1AffineU);
+    // l_query[j] lies at the index of z[num_instance + j]; the entries below it are infinity by construction
+    const size_t l_lo = pk.z_lo > pk.num_instance ? pk.z_lo : pk.num_instance, nl = pk.z_hi > l_lo ? pk.z_hi - l_lo : 0;
+    struct Arr { int group; const void *base; size_t stride, n, first; hipStream_t st; };
+    const Arr arr[5] = {
+        {1, pk.a.p, s1z, nz, pk.z_lo, ctx->slots[1].stream},
+        {1, pk.b1.p, s1z, nz, pk.z_lo, ctx->slots[2].stream},
+        {2, pk.b2.p, s2z, nz, pk.z_lo, ctx->slots[0].stream},
+        {1, pk.h.p, s1h, nh, pk.h_lo, ctx->stream},
+        {1, static_cast<const unsigned char *>(pk.l.p) + (l_lo - pk.z_lo) * s1z, s1z, nl, l_lo - pk.num_instance, ctx->slots[3].stream},
+    };
+    const VbEndo en = vb_endo();
+    DevBuf res(10 * sizeof(uint64_t));
+    VbEvents ev;           // [0] the fork; [1 + 2q], [2 + 2q] around the kernel of query q
+    const double t0 = now_ms();
+    // the slot is written on the main stream; the four small queries run beside h_query on streams of their own and are joined again
+    pk_check_init_launch(ctx->stream, res.as<uint64_t>(), 5);
+    ZK_HIP(hipEventRecord(ev.ev[0], ctx->stream));
+    for (int q = 0; q < 5; q++) {
+        if (arr[q].st != ctx->stream) ZK_HIP(hipStreamWaitEvent(arr[q].st, ev.ev[0], 0));
+        ZK_HIP(hipEventRecord(ev.ev[1 + 2 * q], arr[q].st));
+        pk_check_launch(arr[q].st, arr[q].group, arr[q].base, arr[q].stride, arr[q].n, en, res.as<uint64_t>() + 2 * q);
+        ZK_HIP(hipEventRecord(ev.ev[2 + 2 * q], arr[q].st));
+    }
+    for (int q = 0; q < 5; q++)
+        if (arr[q].st != ctx->stream) ZK_HIP(hipStreamWaitEvent(ctx->stream, ev.ev[2 + 2 * q], 0));
+    uint64_t host[10];
+    ZK_HIP(hipMemcpyAsync(host, res.p, sizeof host, hipMemcpyDeviceToHost, ctx->stream));
+    // the single points on the host meanwhile, from the key's own copies
+    out.single_mask = (single_good(pk.alpha_g1, 1) ? 0u : 1u) | (single_good(pk.beta_g1, 1) ? 0u : 2u) | (single_good(pk.beta_g2, 2) ? 0u : 4u) |
+                      (single_good(pk.delta_g1, 1) ? 0u : 8u) | (single_good(pk.delta_g2, 2) ? 0u : 16u);
+    ZK_HIP(hipStreamSynchronize(ctx->stream));
+    for (int q = 0; q < 5; q++) {
+        out.n_bad[q] = host[2 * q];
+        out.first_bad[q] = host[2 * q] ? host[2 * q + 1] + arr[q].first : UINT64_MAX;      // the whole key's numbering
+        ctx->pkc_timings[K_A + q] = arr[q].n ? vb_elapsed(ev.ev[1 + 2 * q], ev.ev[2 + 2 * q]) : 0.0f;
+    }
+    ctx->pkc_timings[K_TOTAL] = (float)(now_ms() - t0);
+}
+// option "pk_validate": the text zkg16_last_error gives for a key zkg16_pk_load refused
+static std::string pk_check_text(const PkCheckResult &r) {
+    std::string s = "pk_validate: not a point of the group:";
+    for (int q = 0; q < 5; q++)
+        if (r.n_bad[q]) s += std::string(" ") + PK_QUERY_NAMES[q] + "[" + std::to_string(r.first_bad[q]) + "] (" + std::to_string(r.n_bad[q]) + " in all)";
+    for (int b = 0; b < 5; b++)
+        if (r.single_mask & (1u << b)) s += std::string(" ") + PK_SINGLE_NAMES[b];
+    return s;
+}
 }  // namespace zk
 
 namespace {
@@ -207,6 +272,14 @@ int zkg16_pk_load_range(zkg16_ctx *ctx,
     upload_one<G1Affine>(ctx, pk->l.as<G1AffineU>() + nz + 2, pk->delta_g1);
     pk->b_mask.alloc(nz + 3);
     pk->b_skipped = b_density_mask_run(ctx, pk->b1.as<G1AffineU>(), pk->b2.as<G2AffineU>(), nz + 3, pk->b_mask.as<uint8_t>());
+    if (ctx->opt.pk_validate) {      // before the handle exists: a refused key leaves nothing behind (its buffers go with `pk`)
+        PkCheckResult chk;
+        pk_check_run(ctx, *pk, chk);
+        if (!chk.ok()) {
+            ctx->last_error = pk_check_text(chk);
+            return ZKG16_ERR_BAD_ARG;
+        }
+    }
     *pk_handle = ctx->next_handle++;
     ctx->pks.put(*pk_handle, std::move(pk));
     ZK_API_END(ctx)
@@ -484,6 +557,59 @@ int zkg16_pk_table_bits(zkg16_ctx *ctx, uint64_t pk_handle, int *window_bits_z, 
     if (window_bits_z) *window_bits_z = pk->tab_c_z;
     if (window_bits_h) *window_bits_h = pk->tab_c_h;
     ZK_API_END(ctx)
+}
+
+// Is every element of a resident key a point of its group (ark: ProvingKey::deserialize_compressed with Validate::Yes)?  Any handle:
+// a whole key or a shard, with or without window tables.  A bad key is an answer, not an error.
+int zkg16_pk_check(zkg16_ctx *ctx, uint64_t pk_handle, uint64_t n_bad[5], uint64_t first_bad[5], uint32_t *single_mask, int *ok) {
+    if (!n_bad || !first_bad || !single_mask || !ok) return ZKG16_ERR_BAD_ARG;
+    ZK_API_BEGIN(ctx)
+    std::shared_lock<std::shared_mutex> keys(ctx->key_rw);      // zkg16_pk_precompute replaces the buffers under the exclusive lock
+    auto pk_ref = ctx->pks.get(pk_handle); PkDev *pk = pk_ref.get();
+    if (!pk) return ZKG16_ERR_BAD_HANDLE;
+    PkCheckResult r;
+    pk_check_run(ctx, *pk, r);
+    memcpy(n_bad, r.n_bad, sizeof r.n_bad);
+    memcpy(first_bad, r.first_bad, sizeof r.first_bad);
+    *single_mask = r.single_mask;
+    *ok = r.ok() ? 1 : 0;
+    ZK_API_END(ctx)
+}
+
+// The stage entry of the same kernels: n host points in the limbs of zkg16_point_check_batch, uploaded and converted as a key's
+// queries are.  No points (n == 0) is accepted, as there: nothing runs, and the answer is that of an array without a bad point.
+int zkg16_points_check_bulk(zkg16_ctx *ctx, int group, const uint64_t *points, const uint8_t *inf, size_t n, uint64_t *n_bad, uint64_t *first_bad) {
+    if (!ctx || (group != 1 && group != 2) || (!points && n) || !n_bad || !first_bad || n >= ((size_t)1 << 36)) return ZKG16_ERR_BAD_ARG;
+    *n_bad = 0;
+    *first_bad = UINT64_MAX;
+    if (!n) return ZKG16_OK;
+    ZK_API_BEGIN(ctx)
+    DevBuf pts(n * (group == 1 ? sizeof(G1AffineU) : sizeof(G2AffineU))), res(2 * sizeof(uint64_t));
+    EventSet ev;
+    const double t0 = now_ms();
+    if (group == 1) upload_points<G1Affine>(ctx, pts.as<G1AffineU>(), points, inf, 0, n);
+    else upload_points<G2Affine>(ctx, pts.as<G2AffineU>(), points, inf, 0, n);
+    const double t1 = now_ms();
+    pk_check_init_launch(ctx->stream, res.as<uint64_t>(), 1);
+    ZK_HIP(hipEventRecord(ev.ev[0], ctx->stream));
+    pk_check_launch(ctx->stream, group, pts.p, group == 1 ? sizeof(G1AffineU) : sizeof(G2AffineU), n, vb_endo(), res.as<uint64_t>());
+    ZK_HIP(hipEventRecord(ev.ev[1], ctx->stream));
+    uint64_t host[2];
+    ZK_HIP(hipMemcpyAsync(host, res.p, sizeof host, hipMemcpyDeviceToHost, ctx->stream));
+    ZK_HIP(hipStreamSynchronize(ctx->stream));
+    ctx->pkc_timings[K_BULK_KERNEL] = vb_elapsed(ev.ev[0], ev.ev[1]);
+    ctx->pkc_timings[K_BULK_UPLOAD] = (float)(t1 - t0);
+    *n_bad = host[0];
+    *first_bad = host[0] ? host[1] : UINT64_MAX;
+    ZK_API_END(ctx)
+}
+
+int zkg16_pk_check_timings(zkg16_ctx *ctx, float *ms, int cap) {
+    if (!ctx || !ms || cap < 0) return ZKG16_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    const int n = cap < K_COUNT ? cap : K_COUNT;
+    memcpy(ms, ctx->pkc_timings, n * sizeof(float));
+    return n;
 }
 
 void zkg16_pk_free(zkg16_ctx *ctx, uint64_t h) {

@@ -46,6 +46,10 @@ def _ms(times, *names):
     return {name: float(t) for name, t in zip(names, times)}
 
 
+PK_QUERIES = ("a_query", "b_g1_query", "b_g2_query", "h_query", "l_query")          # the order of zkg16_pk_check's arrays
+PK_SINGLES = ("alpha_g1", "beta_g1", "beta_g2", "delta_g1", "delta_g2")               # ... and of its single_mask bits
+
+
 class Device:
     def __init__(self, device_id=0):
         # MatrixCircuit shapes resident on this device, by size (handlers._matrix_shape); entries have .rh
@@ -106,6 +110,25 @@ class Device:
             _u64(pk["alpha_g1"]), _u64(pk["beta_g1"]), _u64(pk["beta_g2"]), _u64(pk["delta_g1"]), _u64(pk["delta_g2"]),
             num_instance, z_lo, z_hi, h_lo, h_hi, int(bool(blinding)), C.byref(handle)))
         return handle.value
+
+    def pk_check(self, pk_h):
+        """Is every element of a resident key or shard a point of its group (zkg16_pk_check: curve and prime-order subgroup, on the
+        device where the key lies)?  -> dict(ok, n_bad, first_bad, singles): n_bad / first_bad keyed by query name (first_bad in the
+        whole key's numbering, None where nothing failed), singles keyed by point name (True = at infinity or not in the group)."""
+        n_bad, first_bad = np.zeros(5, dtype=np.uint64), np.zeros(5, dtype=np.uint64)
+        mask, ok = C.c_uint32(0), C.c_int(0)
+        self._check(self.lib.zkg16_pk_check(self.ctx, pk_h, _ptr(n_bad), _ptr(first_bad), C.byref(mask), C.byref(ok)))
+        return dict(ok=bool(ok.value),
+                    n_bad={q: int(n_bad[i]) for i, q in enumerate(PK_QUERIES)},
+                    first_bad={q: (int(first_bad[i]) if n_bad[i] else None) for i, q in enumerate(PK_QUERIES)},
+                    singles={q: bool(mask.value >> i & 1) for i, q in enumerate(PK_SINGLES)})
+
+    def pk_check_timings(self):
+        """ms of the last pk_check (or validated load) and the last points_check_bulk (zkg16_pk_check_timings): the kernel of each
+        query by name (device events; they run side by side), total_ms (wall), and the stage entry's bulk_kernel_ms / bulk_upload_ms."""
+        ms = (C.c_float * 8)()
+        n = self.lib.zkg16_pk_check_timings(self.ctx, ms, 8)
+        return {name: float(ms[i]) for i, name in enumerate((PK_QUERIES + ("total_ms", "bulk_kernel_ms", "bulk_upload_ms"))[:n])}
 
     def pk_precompute(self, pk_h, window_bits_z=0, window_bits_h=0):
         """Window tables for a key that stays resident (zkg16_pk_precompute): same proofs, fewer bucket additions.
@@ -816,6 +839,16 @@ class Device:
         out = np.zeros(pts.shape[0], dtype=np.uint8)
         self._check(self.lib.zkg16_point_check_batch(self.ctx, 1 if group == "g1" else 2, _ptr(pts), _ptr(fl), pts.shape[0], _ptr(out)))
         return out.astype(bool)
+
+    def points_check_bulk(self, group, points, inf=None):
+        """How many of n affine points fail point_check, and the smallest index of one, on the device by the kernels of pk_check
+        (zkg16_points_check_bulk) -> (n_bad, first_bad); first_bad is 2^64 - 1 when none failed."""
+        pts = _u64(points).reshape(-1, 12 if group == "g1" else 24)
+        fl = _opt_u8(inf)
+        n_bad, first_bad = C.c_uint64(0), C.c_uint64(0)
+        self._check(self.lib.zkg16_points_check_bulk(self.ctx, 1 if group == "g1" else 2, _ptr(pts) if pts.shape[0] else None, _ptr(fl), pts.shape[0],
+                                                     C.byref(n_bad), C.byref(first_bad)))
+        return int(n_bad.value), int(first_bad.value)
 
     def prove_matrix(self, pk_h, r1cs_h, a, b, r, s):
         """One matrix-handler request on resident matrices: assignment built on the device while the proof already runs

@@ -399,10 +399,20 @@ def prove_fibonacci(dev, a, b, num_of_rounds, seed=42, keep_key=False, check_on_
                 _detail=out, _circuit=circ), out, check_on_device)
 
 
-def fibonacci_key(dev, num_of_rounds, rng):
+def _key_checked(dev, stack, ph, check_key):
+    """-> the fields check_key adds to a kept key's record: key_ok = Device.pk_check's verdict on the resident key.  The key handle
+    joins the stack first, so a failing check frees it with the rest."""
+    if not check_key:
+        return {}
+    stack.callback(dev.pk_free, ph)
+    return dict(key_ok=dev.pk_check(ph)["ok"])
+
+
+def fibonacci_key(dev, num_of_rounds, rng, check_key=False):
     """The key every Fibonacci request of one round count shares: the circuit's matrices depend on the round count alone
     (Device.r1cs_fibonacci), so prove_fibonacci's draws from rng in its order (trapdoor, generators) and one setup give the key
-    prove_fibonacci makes for any (a, b) -> dict(ph, rh, vk, setup_time).  The caller frees ph and rh."""
+    prove_fibonacci makes for any (a, b) -> dict(ph, rh, vk, setup_time).  The caller frees ph and rh.
+    check_key: the record also carries key_ok, what Device.pk_check says of the resident key (every element a point of its group)."""
     trap, g1, g2 = _draw_key(rng)
     with contextlib.ExitStack() as stack:
         rh = dev.r1cs_fibonacci(num_of_rounds)
@@ -410,8 +420,9 @@ def fibonacci_key(dev, num_of_rounds, rng):
         t0 = time.perf_counter()
         ph, vk = dev.setup_resident(rh, 4, trap, g1, g2)
         setup_time = time.perf_counter() - t0
+        checked = _key_checked(dev, stack, ph, check_key)
         stack.pop_all()                 # both handles are the caller's from here
-    return dict(ph=ph, rh=rh, vk=vk, setup_time=setup_time)
+    return dict(ph=ph, rh=rh, vk=vk, setup_time=setup_time, **checked)
 
 
 def prove_fibonaccis(dev, requests, num_of_rounds, seed=42, key=None, check_on_device=False, route="key"):
@@ -509,10 +520,10 @@ def prove_linear_equations(dev, a, b, seed=0, keep_key=False, check_on_device=Fa
                 _detail=out, _circuit=circ), out, check_on_device)
 
 
-def linear_key(dev, n, rng):
+def linear_key(dev, n, rng, check_key=False):
     """The key every linear request of one size shares: the circuit's matrices depend on n alone (Device.r1cs_linear), so
     prove_linear_equations' draws from rng in its order (trapdoor, generators) and one setup give the key that handler makes for any
-    (a, b) -> dict(ph, rh, vk, setup_time).  The caller frees ph and rh."""
+    (a, b) -> dict(ph, rh, vk, setup_time).  The caller frees ph and rh.  check_key: as fibonacci_key."""
     trap, g1, g2 = _draw_key(rng)
     with contextlib.ExitStack() as stack:
         rh = dev.r1cs_linear(n)
@@ -520,8 +531,9 @@ def linear_key(dev, n, rng):
         t0 = time.perf_counter()
         ph, vk = dev.setup_resident(rh, 1 + n * (n + 1), trap, g1, g2)
         setup_time = time.perf_counter() - t0
+        checked = _key_checked(dev, stack, ph, check_key)
         stack.pop_all()                 # both handles are the caller's from here
-    return dict(ph=ph, rh=rh, vk=vk, setup_time=setup_time)
+    return dict(ph=ph, rh=rh, vk=vk, setup_time=setup_time, **checked)
 
 
 def prove_linear_equations_batch(dev, systems, seed=0, key=None, check_on_device=False, solver="forward", route="key"):
@@ -674,12 +686,12 @@ def prove_prime(dev, x, i, seed=7, keep_key=False, check_satisfied=False, check_
 _PRIME_NOT_FOUND = dict(proof="", j=0, num_constraints=0, num_variables=0, setup_time=0.0, proving_time=0.0, found_prime=False, prime_num="", vk="")
 
 
-def prime_template_key(dev, rng):
+def prime_template_key(dev, rng, check_key=False):
     """The key every prime request of one trapdoor shares: prove_prime's draws from rng in its order (trapdoor, generators), one
     setup on the template (Device.r1cs_prime_template) -> dict(ph, rh, vk, corr, ext_vk, setup_time).  The trapdoor itself is not
     kept: corr (circuits.prime_key_corrections) is all a request needs of it.  ext_vk: the template vk with the 260 gamma_abc_g1
     points of circuits.prime_vk_extend, the ONE key verify_primes checks every request of this trapdoor under (it serialises
-    through wire.vk_serialize_compressed like any vk).  The caller frees ph and rh."""
+    through wire.vk_serialize_compressed like any vk).  The caller frees ph and rh.  check_key: as fibonacci_key."""
     trap, g1, g2 = _draw_key(rng)
     corr, inf = prime_key_corrections(trap, g1)
     if inf.any():
@@ -690,9 +702,10 @@ def prime_template_key(dev, rng):
         t0 = time.perf_counter()
         ph, vk = dev.setup_resident(rh, prime_dims(1)["num_instance"], trap, g1, g2)
         setup_time = time.perf_counter() - t0
+        checked = _key_checked(dev, stack, ph, check_key)
         stack.pop_all()                 # both handles are the caller's from here
     ext_vk = dict(vk, gamma_abc_g1=prime_vk_extend(vk["gamma_abc_g1"], corr))
-    return dict(ph=ph, rh=rh, vk=vk, corr=corr, ext_vk=ext_vk, setup_time=setup_time)
+    return dict(ph=ph, rh=rh, vk=vk, corr=corr, ext_vk=ext_vk, setup_time=setup_time, **checked)
 
 
 def prove_primes(dev, requests, seed=7, key=None, check_on_device=False):
