@@ -151,6 +151,75 @@ ZKG16_API int zkg16_points_check_bulk(zkg16_ctx *ctx, int group, const uint64_t 
  * zkg16_points_check_bulk (device events), [7] the upload and conversion in front of it (host clock).  Returns the number of
  * entries written (at most cap). */
 ZKG16_API int zkg16_pk_check_timings(zkg16_ctx *ctx, float *ms, int cap);
+
+/* ---- a proving key as bytes: ark-groth16 0.4's ProvingKey<Bls12_381>::serialize_compressed, the one object of the flow that did
+ * not yet travel in arkworks' encoding (proofs and verifying keys: zkg16_points_compress and the decoders below).  Fields in
+ * declaration order, a Vec as a u64 little-endian count and its items, points as zkg16_g1_decompress / zkg16_g2_decompress read them:
+ *
+ *   vk:  alpha_g1 48 | beta_g2 96 | gamma_g2 96 | delta_g2 96 | count 8 | gamma_abc_g1 48 x ni
+ *   beta_g1 48 | delta_g1 48
+ *   a_query 8 + 48 m | b_g1_query 8 + 48 m | b_g2_query 8 + 96 m | h_query 8 + 48 n_h | l_query 8 + 48 (m - ni)
+ *
+ * A restatement of the upstream layout, as the other mirrors: parity with bytes written by a real arkworks build is UNPINNED (the
+ * crates are not vendored); what is pinned is that the host and the device forms here agree byte for byte and status for status.
+ * The uncompressed encoding is not offered.  Every call is all or nothing: a refusal writes no output and leaves no handle.
+ *
+ * zkg16_pk_bytes_dims (host only): walks the five length prefixes and nothing else.  Each count is compared with the bytes that
+ * remain before it is multiplied, so no prefix (2^63, 2^64 - 1) can overflow.  ZKG16_ERR_BAD_ARG, nothing written, zkg16_last_error(NULL)
+ * naming the field: len is not exactly what the counts imply (truncated, trailing bytes), ni == 0 or ni > m, the three z-side counts
+ * differ, n_l != m - ni.  zkg16_pk_bytes_size (host only): the inverse; ZKG16_ERR_BAD_ARG for ni outside 1 .. m or a size beyond size_t. */
+ZKG16_API int zkg16_pk_bytes_dims(const uint8_t *bytes, size_t len, size_t *num_instance, size_t *m, size_t *n_h, size_t *n_l);
+ZKG16_API int zkg16_pk_bytes_size(size_t num_instance, size_t m, size_t n_h, size_t *bytes);
+/* The host forms (no ctx, up to `threads` host threads, 0 = 8), built on zkg16_points_compress and the host decoders: THE REFERENCE
+ * for every byte and every status of the device forms below.  Arrays as zkg16_pk_load's (a / b_g1 / b_g2: m points, h: n_h,
+ * l: m - num_instance; *_inf nullable when serialising) plus gamma_g2 and gamma_abc_g1 (num_instance points).
+ * zkg16_pk_serialize_host: cap below zkg16_pk_bytes_size or a null pointer: ZKG16_ERR_BAD_ARG, out untouched.
+ * zkg16_pk_deserialize_host: outputs sized by zkg16_pk_bytes_dims.  What zkg16_pk_bytes_dims refuses is refused; a point whose
+ * decoder status is not 0 (1 - 4, and 5 with validate) or a single point at infinity: ZKG16_ERR_BAD_ARG, no output written, and
+ * zkg16_last_error(NULL) names the entry and the status, e.g. "b_g2_query[17]: status 4": the smallest index of the first failing
+ * field in file order. */
+ZKG16_API int zkg16_pk_serialize_host(const uint64_t *a_query, const uint8_t *a_inf, const uint64_t *b_g1_query, const uint8_t *b_g1_inf,
+                            const uint64_t *b_g2_query, const uint8_t *b_g2_inf, const uint64_t *h_query, const uint8_t *h_inf,
+                            const uint64_t *l_query, const uint8_t *l_inf,
+                            const uint64_t alpha_g1[12], const uint64_t beta_g1[12], const uint64_t beta_g2[24],
+                            const uint64_t delta_g1[12], const uint64_t delta_g2[24], const uint64_t gamma_g2[24],
+                            const uint64_t *gamma_abc_g1, size_t num_instance, size_t m, size_t n_h, int threads,
+                            uint8_t *out, size_t cap, size_t *written);
+ZKG16_API int zkg16_pk_deserialize_host(const uint8_t *bytes, size_t len, int validate, int threads,
+                            uint64_t *a_query, uint8_t *a_inf, uint64_t *b_g1_query, uint8_t *b_g1_inf,
+                            uint64_t *b_g2_query, uint8_t *b_g2_inf, uint64_t *h_query, uint8_t *h_inf,
+                            uint64_t *l_query, uint8_t *l_inf,
+                            uint64_t alpha_g1[12], uint64_t beta_g1[12], uint64_t beta_g2[24],
+                            uint64_t delta_g1[12], uint64_t delta_g2[24], uint64_t gamma_g2[24], uint64_t *gamma_abc_g1);
+/* A whole resident key copied back as zkg16_pk_load's arrays (limbs and infinity flags): level 0 of each query where it lies, at
+ * either entry stride of a window table, without the three blinding slots, l_query in its own numbering.  With every array and
+ * single point null only the dimensions are written (each nullable).  A shard: ZKG16_ERR_UNSUPPORTED. */
+ZKG16_API int zkg16_pk_read(zkg16_ctx *ctx, uint64_t pk_handle, uint64_t *a_query, uint8_t *a_inf, uint64_t *b_g1_query, uint8_t *b_g1_inf,
+                  uint64_t *b_g2_query, uint8_t *b_g2_inf, uint64_t *h_query, uint8_t *h_inf, uint64_t *l_query, uint8_t *l_inf,
+                  uint64_t alpha_g1[12], uint64_t beta_g1[12], uint64_t beta_g2[24], uint64_t delta_g1[12], uint64_t delta_g2[24],
+                  size_t *num_instance, size_t *m, size_t *n_h);
+/* zkg16_pk_serialize_host of zkg16_pk_read's arrays, byte for byte, encoded on the device where the key lies (one lane per point,
+ * 0xC0 and zeros for a point at infinity anywhere) and brought back in pieces through the ctx's pinned staging ring.  The handle
+ * holds neither gamma_g2 nor gamma_abc_g1 (num_instance points): the caller passes them.  Window tables are not saved
+ * (zkg16_pk_precompute rebuilds them).  Before any device work, out untouched: cap below the key's size or a null pointer
+ * (ZKG16_ERR_BAD_ARG), an unknown handle (ZKG16_ERR_BAD_HANDLE), a shard (ZKG16_ERR_UNSUPPORTED). */
+ZKG16_API int zkg16_pk_save(zkg16_ctx *ctx, uint64_t pk_handle, const uint64_t gamma_g2[24], const uint64_t *gamma_abc_g1,
+                  uint8_t *out, size_t cap, size_t *written);
+/* A whole key from its bytes, decoded on the device (one lane per point; the G2 square root without an inversion) straight into the
+ * key's arrays: the handle zkg16_pk_load returns for zkg16_pk_deserialize_host's arrays, word for word — blinding slots, l_query at
+ * the index of its scalar, the B-side mask — usable by every call that takes a whole key.  The verifying key comes back with it
+ * (gamma_abc_g1: cap_abc points of room, at least num_instance).  What zkg16_pk_bytes_dims refuses, a point of status 1 - 4
+ * anywhere or a single point at infinity: ZKG16_ERR_BAD_ARG, no handle, every buffer released, no output written, zkg16_last_error
+ * (of the ctx) as the host form's.  validate != 0 or option "pk_validate": zkg16_pk_check's test on the decoded key before the
+ * handle exists, exactly as in zkg16_pk_load (status 5; the text is that call's), gamma_g2 and gamma_abc_g1 by zkg16_point_check. */
+ZKG16_API int zkg16_pk_load_bytes(zkg16_ctx *ctx, const uint8_t *bytes, size_t len, int validate, uint64_t *pk_handle,
+                        uint64_t alpha_g1[12], uint64_t beta_g2[24], uint64_t gamma_g2[24], uint64_t delta_g2[24],
+                        uint64_t *gamma_abc_g1, size_t cap_abc);
+/* The last zkg16_pk_load_bytes / zkg16_pk_save / zkg16_pk_read on this ctx, in ms: [0] host time in the staging ring (copies into or
+ * out of its pinned halves and waits for their transfers), [1..5] the decode / encode / read kernels of a, b_g1, b_g2, h, l from the
+ * first piece to the last (device events; later pieces' copies overlap them), [6] gamma_abc_g1 and the single points, [7] the key
+ * check of a validated load, [8] total wall time.  Returns the number of entries written (at most cap). */
+ZKG16_API int zkg16_pk_bytes_timings(zkg16_ctx *ctx, float *ms, int cap);
 ZKG16_API void zkg16_pk_free(zkg16_ctx *ctx, uint64_t pk_handle);
 
 /* ---- device groups: several ctxs of ONE process (one per GPU; several may share a GPU) proving one proof together.
@@ -1067,6 +1136,9 @@ ZKG16_API void zkg16_kernel_stats_reset(zkg16_ctx *ctx);
  *                    several passes at small k)
  *   "trapdoor_pass"  zkg16_prove_trapdoor_batch: requests per device pass (0 = 65,535, else 1..65,535; tests lower it to run several
  *                    passes at small k)
+ *   "pk_bytes_piece" zkg16_pk_load_bytes / zkg16_pk_save / zkg16_pk_read: points per piece of a query (0 = 524,288, else 1..524,288).
+ *                    Each query is cut into pieces on its own; two pieces are in flight, so the default keeps the staging beside
+ *                    the key at 96 MiB of HBM (two pieces of G2 bytes), under 256 MiB.  Tests lower it to reach several pieces at small keys
  * Unknown names return ZKG16_ERR_UNSUPPORTED. */
 ZKG16_API int zkg16_set_option(zkg16_ctx *ctx, const char *name, int64_t value);
 

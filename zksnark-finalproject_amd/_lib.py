@@ -110,6 +110,14 @@ SIGNATURES = {
     "zkg16_pk_check": (C.c_int, [ctxp, C.c_uint64, vp, vp, C.POINTER(C.c_uint32), C.POINTER(C.c_int)]),
     "zkg16_pk_check_timings": (C.c_int, [ctxp, C.POINTER(C.c_float), C.c_int]),
     "zkg16_points_check_bulk": (C.c_int, [ctxp, C.c_int, vp, vp, sz, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "zkg16_pk_bytes_dims": (C.c_int, [vp, sz, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]),
+    "zkg16_pk_bytes_size": (C.c_int, [sz, sz, sz, C.POINTER(sz)]),
+    "zkg16_pk_serialize_host": (C.c_int, [vp] * 17 + [sz, sz, sz, C.c_int, vp, sz, C.POINTER(sz)]),
+    "zkg16_pk_deserialize_host": (C.c_int, [vp, sz, C.c_int, C.c_int] + [vp] * 17),
+    "zkg16_pk_read": (C.c_int, [ctxp, H] + [vp] * 15 + [C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]),
+    "zkg16_pk_save": (C.c_int, [ctxp, H, vp, vp, vp, sz, C.POINTER(sz)]),
+    "zkg16_pk_load_bytes": (C.c_int, [ctxp, vp, sz, C.c_int, C.POINTER(H), vp, vp, vp, vp, vp, sz]),
+    "zkg16_pk_bytes_timings": (C.c_int, [ctxp, C.POINTER(C.c_float), C.c_int]),
     "zkg16_final_exp": (C.c_int, [u64p, u64p]),
     "zkg16_verify_each": (C.c_int, [ctxp, vp, sz, vp, vp, vp, sz, vp, vp, vp, sz, vp]),
     "zkg16_final_exp_batch": (C.c_int, [ctxp, vp, sz, vp]),

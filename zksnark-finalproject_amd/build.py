@@ -13,8 +13,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libzkg16.so")
-SOURCES = ["api.hip", "api_keys.hip", "api_prove.hip", "api_stages.hip", "api_group.hip", "api_verify.hip", "api_rerandomize.hip", "api_trapdoor.hip", "ntt.hip", "poly.hip", "msm.hip", "sort.hip", "bucket_sort.hip", "setup.hip", "circuits.hip", "verify.hip", "witness.hip", "matrix_r1cs.hip", "prime_device.hip", "group.hip", "verify_batch.hip", "pk_check.hip"]
-HEADERS = ["ff.cuh", "ffu.cuh", "fru.cuh", "ec.cuh", "g2split.cuh", "common.hpp", "api_internal.hpp", "hostff.hpp", "matrix_plan.hpp", "prime_program.hpp", "group.hpp", "verify_batch.hpp", "pairing_dev.cuh", "pairing_each_dev.cuh", "decompress_dev.cuh", "sponge_chain_dev.cuh", "linear_dev.cuh", "linear_elim_dev.cuh", "prime_inputs_dev.cuh", "u64_inputs_dev.cuh", "rerandomize_dev.cuh", "r1cs_check_dev.cuh", "trapdoor_dev.cuh", "pk_check_dev.cuh", "pairing_fast.inc", "poseidon_h64.inc", "poseidon_params.inc", "prime_circuit.inc", "final_exp.inc", os.path.join("..", "..", "include", "zkg16.h")]
+SOURCES = ["api.hip", "api_keys.hip", "api_prove.hip", "api_stages.hip", "api_group.hip", "api_verify.hip", "api_rerandomize.hip", "api_trapdoor.hip", "ntt.hip", "poly.hip", "msm.hip", "sort.hip", "bucket_sort.hip", "setup.hip", "circuits.hip", "verify.hip", "witness.hip", "matrix_r1cs.hip", "prime_device.hip", "group.hip", "verify_batch.hip", "pk_check.hip", "pk_bytes.hip"]
+HEADERS = ["ff.cuh", "ffu.cuh", "fru.cuh", "ec.cuh", "g2split.cuh", "common.hpp", "api_internal.hpp", "hostff.hpp", "matrix_plan.hpp", "prime_program.hpp", "group.hpp", "verify_batch.hpp", "pairing_dev.cuh", "pairing_each_dev.cuh", "decompress_dev.cuh", "sponge_chain_dev.cuh", "linear_dev.cuh", "linear_elim_dev.cuh", "prime_inputs_dev.cuh", "u64_inputs_dev.cuh", "rerandomize_dev.cuh", "r1cs_check_dev.cuh", "trapdoor_dev.cuh", "pk_check_dev.cuh", "pk_bytes_dev.cuh", "pairing_fast.inc", "poseidon_h64.inc", "poseidon_params.inc", "prime_circuit.inc", "final_exp.inc", os.path.join("..", "..", "include", "zkg16.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wall", "-Wno-unused-function"]
 
 

@@ -437,6 +437,8 @@ int set_option_one(zkg16_ctx *ctx, const char *name, int64_t v) {
     if (is("check_satisfied")) return set(o.check_satisfied, 0, 1, v);
     // 0 (default): zkg16_pk_load / zkg16_pk_load_range copy what they are handed; 1: they run zkg16_pk_check on the uploaded key and refuse a bad one
     if (is("pk_validate")) return set(o.pk_validate, 0, 1, v);
+    // zkg16_pk_load_bytes / zkg16_pk_save / zkg16_pk_read: points per piece of a query (0 = 524,288)
+    if (is("pk_bytes_piece")) return set(o.pk_bytes_piece, 0, 1 << 19, v);
     // zkg16_prove_trapdoor_batch: requests per device pass (0 = 65,535)
     if (is("trapdoor_pass")) return set(o.trapdoor_pass, 0, 65535, v);
     if (is("reduce_chunk")) return set(o.reduce_chunk, 0, 64, v, (v & (v - 1)) == 0);      // 0 = default, else a power of two up to 64

@@ -71,6 +71,16 @@ enum PkCheckTiming : int {
     K_COUNT = 8
 };
 static_assert(K_COUNT == PK_CHECK_TIMING_SLOTS, "timing slots");
+// ---- zkg16_ctx::pkb_timings (zkg16_pk_bytes_timings), ABI as well
+enum PkBytesTiming : int {
+    B_COPY = 0,            // host time in the staging ring: bytes copied into / out of its pinned halves and the waits for their transfers (host clock)
+    B_A = 1, B_B1 = 2, B_B2 = 3, B_H = 4, B_L = 5,      // the decode / encode / read kernels of each query, first piece to last (device events; the copies of later pieces overlap them)
+    B_VK = 6,              // gamma_abc_g1 on the device and the single points on the host (host clock)
+    B_CHECK = 7,           // the key check of a validated load (K_TOTAL of that check; 0 otherwise)
+    B_TOTAL = 8,           // wall time of the call
+    B_COUNT = 9
+};
+static_assert(B_COUNT == PK_BYTES_TIMING_SLOTS, "timing slots");
 static_assert(T_COUNT <= PROOF_TIMING_SLOTS && V_COUNT == VERIFY_TIMING_SLOTS && R_COUNT == RERANDOMIZE_TIMING_SLOTS, "timing slots");
 // the last refusal of a host-only entry point on this thread (zkg16_last_error(NULL)); api.hip
 std::string &host_last_error();
@@ -187,6 +197,17 @@ struct PkCheckResult {
     bool ok() const { return !single_mask && !(n_bad[0] | n_bad[1] | n_bad[2] | n_bad[3] | n_bad[4]); }
 };
 void pk_check_run(zkg16_ctx *ctx, const PkDev &pk, PkCheckResult &out);
+
+// ---- a key's points between wire bytes and the resident form (pk_bytes.hip; kernels: pk_bytes_dev.cuh).  Launches on `st`, nothing
+// synchronises.  res: two device words per array, {points with a decode status, smallest (index << 3 | status)};
+// pk_bytes_init_launch writes {0, UINT64_MAX} into `slots` of them
+void pk_bytes_init_launch(hipStream_t st, uint64_t *res, int slots);
+// n encodings of one group back to back (48 / 96 bytes, device) -> U-form affine entries at out + i * stride (bytes), (0, 0) for the
+// point at infinity and for a refused encoding; `first` is added to the index a failure reports
+void pk_bytes_decode_launch(hipStream_t st, int group, const uint8_t *bytes, size_t n, void *out, size_t stride, size_t first, uint64_t *res);
+// n U-form entries at base + i * stride -> the bytes of zkg16_points_compress, back to back / the limbs and flags of zkg16_pk_load
+void pk_bytes_encode_launch(hipStream_t st, int group, const void *base, size_t stride, size_t n, uint8_t *out);
+void pk_bytes_read_launch(hipStream_t st, int group, const void *base, size_t stride, size_t n, uint64_t *limbs, uint8_t *inf);
 
 // events of one proof, destroyed on every exit path
 struct EventSet {

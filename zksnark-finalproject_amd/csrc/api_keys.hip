@@ -1,5 +1,6 @@
 // libzkg16 C ABI, part 2 of 8 (api.hip): residency — proving keys and their shards (load, slice, shard plans, window tables), R1CS
-// matrices, synthesized circuits and assignments; the host -> device upload helpers the other parts share.
+// matrices, synthesized circuits and assignments; the host -> device upload helpers the other parts share; a key to and from arkworks'
+// ProvingKey bytes (at the end of the file).
 #include "api_internal.hpp"
 
 using namespace zk;
@@ -863,6 +864,595 @@ void zkg16_witness_free(zkg16_ctx *ctx, uint64_t h) {
     std::lock_guard<std::mutex> lk(ctx->mu);
     (void)hipSetDevice(ctx->device);
     ctx->wits.erase(h);
+}
+
+}  // extern "C"
+
+// ---- a proving key as the bytes of ark-groth16 0.4's ProvingKey<Bls12_381>::serialize_compressed (include/zkg16.h has the layout):
+// zkg16_pk_bytes_dims / _size and the host forms (no ctx), zkg16_pk_read / _save / _load_bytes on the device where the key lies
+namespace {
+constexpr size_t PKB_HEAD = 48 + 3 * 96;      // alpha_g1 | beta_g2 | gamma_g2 | delta_g2
+constexpr size_t PKB_QSIZE[5] = {48, 48, 96, 48, 48};
+constexpr int PKB_QGROUP[5] = {1, 1, 2, 1, 1};
+constexpr size_t PKB_PIECE_DEFAULT = (size_t)1 << 19;      // 48 MiB of G2 bytes: one half of the staging ring holds a piece
+struct PkbLayout {
+    size_t ni = 0, m = 0, n_h = 0, n_l = 0;
+    size_t at_abc = 0, at_beta_g1 = 0, at_delta_g1 = 0, at_q[5] = {0, 0, 0, 0, 0};
+    size_t n_q(int q) const { return q == 3 ? n_h : q == 4 ? n_l : m; }
+};
+uint64_t le64(const uint8_t *b) {
+    uint64_t v = 0;
+    for (int i = 0; i < 8; i++) v |= (uint64_t)b[i] << (8 * i);
+    return v;
+}
+void put_le64(uint8_t *b, uint64_t v) {
+    for (int i = 0; i < 8; i++) b[i] = (uint8_t)(v >> (8 * i));
+}
+// The five length prefixes and nothing else.  A count is compared with the bytes that remain BEFORE it is multiplied: no product of
+// a hostile prefix is ever formed.  false: err names the field
+bool pkb_walk(const uint8_t *b, size_t len, PkbLayout &L, std::string &err) {
+    size_t pos = 0;
+    auto need = [&](size_t k, const char *what) {
+        if (len - pos >= k) return true;
+        err = std::string("pk bytes: truncated in ") + what;
+        return false;
+    };
+    auto count = [&](size_t item, const char *what, size_t &out) {
+        if (!need(8, what)) return false;
+        const uint64_t c = le64(b + pos);
+        pos += 8;
+        if (c > (uint64_t)((len - pos) / item)) {
+            err = std::string("pk bytes: ") + what + ": count " + std::to_string(c) + " exceeds the bytes that remain";
+            return false;
+        }
+        out = (size_t)c;
+        return true;
+    };
+    if (!need(PKB_HEAD, "vk")) return false;
+    pos = PKB_HEAD;
+    if (!count(48, "gamma_abc_g1", L.ni)) return false;
+    L.at_abc = pos;
+    pos += 48 * L.ni;
+    if (!need(96, "beta_g1 / delta_g1")) return false;
+    L.at_beta_g1 = pos;
+    L.at_delta_g1 = pos + 48;
+    pos += 96;
+    size_t cnt[5];
+    for (int q = 0; q < 5; q++) {
+        if (!count(PKB_QSIZE[q], PK_QUERY_NAMES[q], cnt[q])) return false;
+        L.at_q[q] = pos;
+        pos += PKB_QSIZE[q] * cnt[q];
+    }
+    if (pos != len) { err = "pk bytes: " + std::to_string(len - pos) + " trailing bytes"; return false; }
+    L.m = cnt[0]; L.n_h = cnt[3]; L.n_l = cnt[4];
+    if (L.ni == 0 || L.ni > L.m) { err = "pk bytes: gamma_abc_g1: count " + std::to_string(L.ni) + " is not in 1 .. a_query's " + std::to_string(L.m); return false; }
+    for (int q = 1; q < 3; q++)
+        if (cnt[q] != L.m) { err = std::string("pk bytes: ") + PK_QUERY_NAMES[q] + ": count " + std::to_string(cnt[q]) + " differs from a_query's " + std::to_string(L.m); return false; }
+    if (L.n_l != L.m - L.ni) { err = "pk bytes: l_query: count " + std::to_string(L.n_l) + " is not a_query's less gamma_abc_g1's"; return false; }
+    return true;
+}
+bool pkb_size(size_t ni, size_t m, size_t n_h, size_t &bytes) {
+    if (ni == 0 || ni > m) return false;
+    unsigned __int128 t = PKB_HEAD + 8 + 96 + 5 * 8;
+    t += (unsigned __int128)48 * ni + (unsigned __int128)(48 + 48 + 96) * m + (unsigned __int128)48 * n_h + (unsigned __int128)48 * (m - ni);
+    if (t > (unsigned __int128)SIZE_MAX) return false;
+    bytes = (size_t)t;
+    return true;
+}
+// n points of one group through the host decoders on up to `threads` threads: the smallest index with a status and that status
+// (0: none).  out / inf: n x 12 | 24 limbs and n flags
+int pkb_decode_host(int group, const uint8_t *src, size_t n, int validate, int threads, uint64_t *out, uint8_t *inf, size_t &bad_at) {
+    const size_t sz = group == 1 ? 48 : 96, w = group == 1 ? 12 : 24;
+    std::vector<int> st(n ? n : 1, 0);
+    vb_parallel(n, threads, 64, [&](size_t lo, size_t hi) {
+        if (group == 1) (void)zkg16_g1_decompress(src + sz * lo, hi - lo, out + w * lo, inf + lo, validate, st.data() + lo);
+        else (void)zkg16_g2_decompress(src + sz * lo, hi - lo, out + w * lo, inf + lo, validate, st.data() + lo);
+    });
+    for (size_t i = 0; i < n; i++)
+        if (st[i]) { bad_at = i; return st[i]; }
+    return 0;
+}
+void pkb_compress_host(int group, const uint64_t *pts, const uint8_t *inf, size_t n, int threads, uint8_t *out) {
+    const size_t sz = group == 1 ? 48 : 96, w = group == 1 ? 12 : 24;
+    vb_parallel(n, threads, 256, [&](size_t lo, size_t hi) { (void)zkg16_points_compress(group, pts + w * lo, inf ? inf + lo : nullptr, hi - lo, out + sz * lo); });
+}
+// the six single points in file order: name, group, offset, whether the key (PkDev) holds it
+struct PkbSingle { const char *name; int group; size_t at; };
+void pkb_singles(const PkbLayout &L, PkbSingle s[6]) {
+    s[0] = {"alpha_g1", 1, 0}; s[1] = {"beta_g2", 2, 48}; s[2] = {"gamma_g2", 2, 144}; s[3] = {"delta_g2", 2, 240};
+    s[4] = {"beta_g1", 1, L.at_beta_g1}; s[5] = {"delta_g1", 1, L.at_delta_g1};
+}
+std::string pkb_status_text(const char *name, bool indexed, size_t i, int status) {
+    return std::string(name) + (indexed ? "[" + std::to_string(i) + "]" : std::string()) + ": status " + std::to_string(status);
+}
+// one single point by the host decoder; a point at infinity is refused as zkg16_pk_check refuses it.  "" = good
+std::string pkb_single_host(const PkbSingle &sp, const uint8_t *bytes, int validate, uint64_t out[24]) {
+    uint8_t inf = 0;
+    int st = 0;
+    if (sp.group == 1) (void)zkg16_g1_decompress(bytes + sp.at, 1, out, &inf, validate, &st);
+    else (void)zkg16_g2_decompress(bytes + sp.at, 1, out, &inf, validate, &st);
+    if (st) return pkb_status_text(sp.name, false, 0, st);
+    if (inf) return std::string(sp.name) + ": the point at infinity";
+    return std::string();
+}
+void par_memcpy(void *dst, const void *src, size_t len) {
+    if (len < ((size_t)8 << 20)) { memcpy(dst, src, len); return; }
+    constexpr int T = 4;
+    const size_t part = (len / T + 4095) & ~(size_t)4095;
+    unsigned char *d = static_cast<unsigned char *>(dst);
+    const unsigned char *s = static_cast<const unsigned char *>(src);
+    ThreadGroup tg;
+    for (int t = 1; t < T; t++) {
+        const size_t lo = part * t < len ? part * t : len, hi = part * (t + 1) < len ? part * (t + 1) : len;
+        tg.run([=]() { if (hi > lo) memcpy(d + lo, s + lo, hi - lo); });
+    }
+    memcpy(d, s, part < len ? part : len);
+}
+// Pieces between host memory and the kernels through the ctx's pinned ring (two halves of STAGE_BYTES) and two device buffers:
+// copies run on the ctx's second stream, kernels on its first, so the copy of piece i + 1 overlaps the kernel of piece i.
+// stage_done[s]: the last transfer through pinned half s; krn[s]: the last kernel on device buffer s.
+struct PkbPipe {
+    zkg16_ctx *ctx;
+    hipStream_t copy;
+    DevBuf dev[2];
+    VbEvents ev;            // [2q], [2q + 1]: around the kernels of query q (q < 5); [10 + s]: krn[s]
+    size_t turn = 0;
+    double host_ms = 0;
+    struct Pending { void *dst = nullptr; size_t bytes = 0; } pending[2];
+    PkbPipe(zkg16_ctx *c, size_t dev_bytes) : ctx(c), copy(c->wm_stream) {
+        for (int i = 0; i < 2; i++) {
+            dev[i].alloc(dev_bytes);
+            if (!ctx->stage_host[i]) {
+                ZK_HIP(hipHostMalloc(&ctx->stage_host[i], STAGE_BYTES, hipHostMallocDefault));
+                ZK_HIP(hipEventCreateWithFlags(&ctx->stage_done[i], hipEventDisableTiming));
+            }
+        }
+    }
+    unsigned char *pinned(int s) const { return static_cast<unsigned char *>(ctx->stage_host[s]); }
+    // host bytes -> device buffer of the next slot, queued; the caller launches its kernel on ctx->stream and calls kernel_done
+    int upload(const void *src, size_t bytes) {
+        const int s = (int)(turn++ & 1);
+        const double t0 = now_ms();
+        ZK_HIP(hipEventSynchronize(ctx->stage_done[s]));            // the transfer that last read this half has left it (a fresh event is complete)
+        par_memcpy(pinned(s), src, bytes);
+        host_ms += now_ms() - t0;
+        ZK_HIP(hipStreamWaitEvent(copy, ev.ev[10 + s], 0));         // the kernel that last read this device buffer is done
+        ZK_HIP(hipMemcpyAsync(dev[s].p, pinned(s), bytes, hipMemcpyHostToDevice, copy));
+        ZK_HIP(hipEventRecord(ctx->stage_done[s], copy));
+        ZK_HIP(hipStreamWaitEvent(ctx->stream, ctx->stage_done[s], 0));
+        return s;
+    }
+    void kernel_done(int s) { ZK_HIP(hipEventRecord(ev.ev[10 + s], ctx->stream)); }
+    // the next slot for a kernel that writes dev[s]; what the slot still holds for the host is delivered first
+    int claim() {
+        const int s = (int)(turn++ & 1);
+        flush(s);
+        return s;
+    }
+    // device buffer s (written by the kernel just launched on ctx->stream) -> dst on the host, delivered by a later flush
+    void download(int s, void *dst, size_t bytes) {
+        kernel_done(s);
+        ZK_HIP(hipStreamWaitEvent(copy, ev.ev[10 + s], 0));
+        ZK_HIP(hipMemcpyAsync(pinned(s), dev[s].p, bytes, hipMemcpyDeviceToHost, copy));
+        ZK_HIP(hipEventRecord(ctx->stage_done[s], copy));
+        pending[s].dst = dst;
+        pending[s].bytes = bytes;
+    }
+    void flush(int s) {
+        if (!pending[s].bytes) return;
+        const double t0 = now_ms();
+        ZK_HIP(hipEventSynchronize(ctx->stage_done[s]));
+        par_memcpy(pending[s].dst, pinned(s), pending[s].bytes);
+        host_ms += now_ms() - t0;
+        pending[s].bytes = 0;
+    }
+    void flush_all() { flush((int)(turn & 1)); flush((int)((turn + 1) & 1)); }      // the older piece first
+};
+size_t pkb_piece(const zkg16_ctx *ctx, size_t per_point) {
+    size_t p = ctx->opt.pk_bytes_piece > 0 ? (size_t)ctx->opt.pk_bytes_piece : PKB_PIECE_DEFAULT;
+    if (p * per_point > STAGE_BYTES) p = STAGE_BYTES / per_point;
+    return p;
+}
+// level 0 of a whole key's five queries where they lie: base, entry stride, length (l_query in its own numbering)
+struct PkbArr { int group; const unsigned char *base; size_t stride, n; };
+void pkb_arrays(const PkDev &pk, PkbArr arr[5]) {
+    const size_t s1z = pk.pad_z_g1 ? (size_t)ZKG16_TABLE_STRIDE_PADDED_G1 : sizeof(G1AffineU), s2z = pk.pad_z_g2 ? (size_t)ZKG16_TABLE_STRIDE_PADDED_G2 : sizeof(G2AffineU);
+    const size_t s1h = pk.pad_h ? (size_t)ZKG16_TABLE_STRIDE_PADDED_G1 : sizeof(G1AffineU);
+    arr[0] = {1, pk.a.as<unsigned char>(), s1z, pk.m_total};
+    arr[1] = {1, pk.b1.as<unsigned char>(), s1z, pk.m_total};
+    arr[2] = {2, pk.b2.as<unsigned char>(), s2z, pk.m_total};
+    arr[3] = {1, pk.h.as<unsigned char>(), s1h, pk.n_h_total};
+    arr[4] = {1, pk.l.as<unsigned char>() + pk.num_instance * s1z, s1z, pk.m_total - pk.num_instance};
+}
+void pkb_query_times(zkg16_ctx *ctx, PkbPipe &pipe, const size_t n[5]) {
+    for (int q = 0; q < 5; q++) ctx->pkb_timings[B_A + q] = n[q] ? vb_elapsed(pipe.ev.ev[2 * q], pipe.ev.ev[2 * q + 1]) : 0.0f;
+}
+}  // namespace
+
+extern "C" {
+
+int zkg16_pk_bytes_dims(const uint8_t *bytes, size_t len, size_t *num_instance, size_t *m, size_t *n_h, size_t *n_l) {
+    if (!bytes || !num_instance || !m || !n_h || !n_l) { host_last_error() = "zkg16_pk_bytes_dims: null pointer"; return ZKG16_ERR_BAD_ARG; }
+    PkbLayout L;
+    std::string err;
+    try {
+        if (!pkb_walk(bytes, len, L, err)) { host_last_error() = err; return ZKG16_ERR_BAD_ARG; }
+    } catch (const std::bad_alloc &) {
+        return ZKG16_ERR_OOM;
+    }
+    *num_instance = L.ni; *m = L.m; *n_h = L.n_h; *n_l = L.n_l;
+    return ZKG16_OK;
+}
+
+int zkg16_pk_bytes_size(size_t num_instance, size_t m, size_t n_h, size_t *bytes) {
+    size_t b = 0;
+    if (!bytes || !pkb_size(num_instance, m, n_h, b)) { host_last_error() = "zkg16_pk_bytes_size: null pointer, num_instance outside 1 .. m, or a size beyond size_t"; return ZKG16_ERR_BAD_ARG; }
+    *bytes = b;
+    return ZKG16_OK;
+}
+
+int zkg16_pk_serialize_host(const uint64_t *a_query, const uint8_t *a_inf, const uint64_t *b_g1_query, const uint8_t *b_g1_inf, const uint64_t *b_g2_query,
+                            const uint8_t *b_g2_inf, const uint64_t *h_query, const uint8_t *h_inf, const uint64_t *l_query, const uint8_t *l_inf,
+                            const uint64_t alpha_g1[12], const uint64_t beta_g1[12], const uint64_t beta_g2[24], const uint64_t delta_g1[12],
+                            const uint64_t delta_g2[24], const uint64_t gamma_g2[24], const uint64_t *gamma_abc_g1, size_t num_instance, size_t m, size_t n_h,
+                            int threads, uint8_t *out, size_t cap, size_t *written) {
+    size_t total = 0;
+    if (!a_query || !b_g1_query || !b_g2_query || (!h_query && n_h) || (!l_query && m != num_instance) || !alpha_g1 || !beta_g1 || !beta_g2 || !delta_g1 ||
+        !delta_g2 || !gamma_g2 || !gamma_abc_g1 || !out || !written || threads < 0 || !pkb_size(num_instance, m, n_h, total) || cap < total) {
+        host_last_error() = "zkg16_pk_serialize_host: null pointer, num_instance outside 1 .. m, or cap below zkg16_pk_bytes_size";
+        return ZKG16_ERR_BAD_ARG;
+    }
+    try {
+        uint8_t *p = out;
+        (void)zkg16_points_compress(1, alpha_g1, nullptr, 1, p); p += 48;
+        (void)zkg16_points_compress(2, beta_g2, nullptr, 1, p); p += 96;
+        (void)zkg16_points_compress(2, gamma_g2, nullptr, 1, p); p += 96;
+        (void)zkg16_points_compress(2, delta_g2, nullptr, 1, p); p += 96;
+        put_le64(p, num_instance); p += 8;
+        pkb_compress_host(1, gamma_abc_g1, nullptr, num_instance, threads, p); p += 48 * num_instance;
+        (void)zkg16_points_compress(1, beta_g1, nullptr, 1, p); p += 48;
+        (void)zkg16_points_compress(1, delta_g1, nullptr, 1, p); p += 48;
+        const uint64_t *pts[5] = {a_query, b_g1_query, b_g2_query, h_query, l_query};
+        const uint8_t *inf[5] = {a_inf, b_g1_inf, b_g2_inf, h_inf, l_inf};
+        const size_t n[5] = {m, m, m, n_h, m - num_instance};
+        for (int q = 0; q < 5; q++) {
+            put_le64(p, n[q]); p += 8;
+            pkb_compress_host(PKB_QGROUP[q], pts[q], inf[q], n[q], threads, p); p += PKB_QSIZE[q] * n[q];
+        }
+        *written = (size_t)(p - out);
+    } catch (const std::bad_alloc &) {
+        return ZKG16_ERR_OOM;
+    }
+    return ZKG16_OK;
+}
+
+int zkg16_pk_deserialize_host(const uint8_t *bytes, size_t len, int validate, int threads, uint64_t *a_query, uint8_t *a_inf, uint64_t *b_g1_query, uint8_t *b_g1_inf,
+                              uint64_t *b_g2_query, uint8_t *b_g2_inf, uint64_t *h_query, uint8_t *h_inf, uint64_t *l_query, uint8_t *l_inf, uint64_t alpha_g1[12],
+                              uint64_t beta_g1[12], uint64_t beta_g2[24], uint64_t delta_g1[12], uint64_t delta_g2[24], uint64_t gamma_g2[24],
+                              uint64_t *gamma_abc_g1) {
+    if (!bytes || !a_query || !a_inf || !b_g1_query || !b_g1_inf || !b_g2_query || !b_g2_inf || !alpha_g1 || !beta_g1 || !beta_g2 || !delta_g1 || !delta_g2 ||
+        !gamma_g2 || !gamma_abc_g1 || threads < 0) {
+        host_last_error() = "zkg16_pk_deserialize_host: null pointer";
+        return ZKG16_ERR_BAD_ARG;
+    }
+    try {
+        PkbLayout L;
+        std::string err;
+        if (!pkb_walk(bytes, len, L, err)) { host_last_error() = err; return ZKG16_ERR_BAD_ARG; }
+        if ((L.n_h && (!h_query || !h_inf)) || (L.n_l && (!l_query || !l_inf))) { host_last_error() = "zkg16_pk_deserialize_host: null pointer"; return ZKG16_ERR_BAD_ARG; }
+        // everything into buffers of the call first: a refusal writes no output
+        PkbSingle sp[6];
+        pkb_singles(L, sp);
+        uint64_t single[6][24];
+        std::vector<uint64_t> abc(12 * L.ni), qv[5];
+        std::vector<uint8_t> abc_inf(L.ni), qi[5];
+        auto refuse = [&](const std::string &text) { host_last_error() = text; return ZKG16_ERR_BAD_ARG; };
+        auto abc_run = [&]() {
+            size_t at = 0;
+            const int st = pkb_decode_host(1, bytes + L.at_abc, L.ni, validate, threads, abc.data(), abc_inf.data(), at);
+            return st ? pkb_status_text("gamma_abc_g1", true, at, st) : std::string();
+        };
+        for (int i = 0; i < 6; i++) {
+            if (i == 4) { const std::string t = abc_run(); if (!t.empty()) return refuse(t); }       // file order
+            const std::string t = pkb_single_host(sp[i], bytes, validate, single[i]);
+            if (!t.empty()) return refuse(t);
+        }
+        for (int q = 0; q < 5; q++) {
+            const size_t n = L.n_q(q);
+            qv[q].resize((PKB_QGROUP[q] == 1 ? 12 : 24) * (n ? n : 1));
+            qi[q].resize(n ? n : 1);
+            size_t at = 0;
+            const int st = pkb_decode_host(PKB_QGROUP[q], bytes + L.at_q[q], n, validate, threads, qv[q].data(), qi[q].data(), at);
+            if (st) return refuse(pkb_status_text(PK_QUERY_NAMES[q], true, at, st));
+        }
+        uint64_t *single_out[6] = {alpha_g1, beta_g2, gamma_g2, delta_g2, beta_g1, delta_g1};
+        for (int i = 0; i < 6; i++) memcpy(single_out[i], single[i], (sp[i].group == 1 ? 12 : 24) * sizeof(uint64_t));
+        memcpy(gamma_abc_g1, abc.data(), 12 * L.ni * sizeof(uint64_t));
+        uint64_t *q_out[5] = {a_query, b_g1_query, b_g2_query, h_query, l_query};
+        uint8_t *i_out[5] = {a_inf, b_g1_inf, b_g2_inf, h_inf, l_inf};
+        for (int q = 0; q < 5; q++) {
+            const size_t n = L.n_q(q);
+            if (!n) continue;
+            memcpy(q_out[q], qv[q].data(), (PKB_QGROUP[q] == 1 ? 12 : 24) * n * sizeof(uint64_t));
+            memcpy(i_out[q], qi[q].data(), n);
+        }
+    } catch (const std::bad_alloc &) {
+        return ZKG16_ERR_OOM;
+    }
+    return ZKG16_OK;
+}
+
+// A whole resident key back as zkg16_pk_load's arrays: level 0 of each query where it lies (a window table's first level at the
+// table's entry stride), without the three blinding slots, l_query in its own numbering.  Null arrays: the dimensions alone.
+int zkg16_pk_read(zkg16_ctx *ctx, uint64_t pk_handle, uint64_t *a_query, uint8_t *a_inf, uint64_t *b_g1_query, uint8_t *b_g1_inf, uint64_t *b_g2_query,
+                  uint8_t *b_g2_inf, uint64_t *h_query, uint8_t *h_inf, uint64_t *l_query, uint8_t *l_inf, uint64_t alpha_g1[12], uint64_t beta_g1[12],
+                  uint64_t beta_g2[24], uint64_t delta_g1[12], uint64_t delta_g2[24], size_t *num_instance, size_t *m, size_t *n_h) {
+    ZK_API_BEGIN(ctx)
+    std::shared_lock<std::shared_mutex> keys(ctx->key_rw);
+    auto pk_ref = ctx->pks.get(pk_handle); PkDev *pk = pk_ref.get();
+    if (!pk) return ZKG16_ERR_BAD_HANDLE;
+    if (!pk->full) return ZKG16_ERR_UNSUPPORTED;
+    if (num_instance) *num_instance = pk->num_instance;
+    if (m) *m = pk->m_total;
+    if (n_h) *n_h = pk->n_h_total;
+    uint64_t *q_out[5] = {a_query, b_g1_query, b_g2_query, h_query, l_query};
+    uint8_t *i_out[5] = {a_inf, b_g1_inf, b_g2_inf, h_inf, l_inf};
+    PkbArr arr[5];
+    pkb_arrays(*pk, arr);
+    bool any = false, all = true;
+    for (int q = 0; q < 5; q++) {
+        const bool have = q_out[q] && i_out[q];
+        any = any || q_out[q] || i_out[q];
+        all = all && (have || !arr[q].n);
+    }
+    if (!any && !alpha_g1 && !beta_g1 && !beta_g2 && !delta_g1 && !delta_g2) return ZKG16_OK;      // the dimensions alone
+    if (!all || !alpha_g1 || !beta_g1 || !beta_g2 || !delta_g1 || !delta_g2) return ZKG16_ERR_BAD_ARG;
+    const double t0 = now_ms();
+    memset(ctx->pkb_timings, 0, sizeof ctx->pkb_timings);
+    const size_t piece = pkb_piece(ctx, sizeof(G2Affine) + 1);
+    PkbPipe pipe(ctx, piece * (sizeof(G2Affine) + 1));
+    size_t n5[5];
+    // a piece travels as its limbs followed by its flags; the host puts the two where they belong
+    struct Split { uint64_t *limbs; uint8_t *inf; size_t cnt, w; };
+    std::vector<unsigned char> bounce[2];
+    Split split[2] = {};
+    auto deliver = [&](int s) {
+        pipe.flush(s);
+        if (!split[s].cnt) return;
+        memcpy(split[s].limbs, bounce[s].data(), split[s].cnt * split[s].w);
+        memcpy(split[s].inf, bounce[s].data() + split[s].cnt * split[s].w, split[s].cnt);
+        split[s].cnt = 0;
+    };
+    for (int q = 0; q < 5; q++) {
+        n5[q] = arr[q].n;
+        const size_t w = arr[q].group == 1 ? sizeof(G1Affine) : sizeof(G2Affine);
+        for (size_t off = 0; off < arr[q].n; off += piece) {
+            const size_t cnt = arr[q].n - off < piece ? arr[q].n - off : piece;
+            const int s = (int)(pipe.turn & 1);
+            deliver(s);
+            (void)pipe.claim();
+            if (off == 0) ZK_HIP(hipEventRecord(pipe.ev.ev[2 * q], ctx->stream));
+            pk_bytes_read_launch(ctx->stream, arr[q].group, arr[q].base + off * arr[q].stride, arr[q].stride, cnt, pipe.dev[s].as<uint64_t>(),
+                                 pipe.dev[s].as<uint8_t>() + cnt * w);
+            bounce[s].resize(piece * (sizeof(G2Affine) + 1));
+            pipe.download(s, bounce[s].data(), cnt * (w + 1));
+            split[s] = Split{q_out[q] + off * (w / 8), i_out[q] + off, cnt, w};
+        }
+        if (arr[q].n) ZK_HIP(hipEventRecord(pipe.ev.ev[2 * q + 1], ctx->stream));
+    }
+    deliver((int)(pipe.turn & 1));
+    deliver((int)((pipe.turn + 1) & 1));
+    ZK_HIP(hipStreamSynchronize(ctx->stream));
+    point_to_abi(pk->alpha_g1, alpha_g1, nullptr);
+    point_to_abi(pk->beta_g1, beta_g1, nullptr);
+    point_to_abi(pk->beta_g2, beta_g2, nullptr);
+    point_to_abi(pk->delta_g1, delta_g1, nullptr);
+    point_to_abi(pk->delta_g2, delta_g2, nullptr);
+    pkb_query_times(ctx, pipe, n5);
+    ctx->pkb_timings[B_COPY] = (float)pipe.host_ms;
+    ctx->pkb_timings[B_TOTAL] = (float)(now_ms() - t0);
+    ZK_API_END(ctx)
+}
+
+// The bytes of zkg16_pk_serialize_host for zkg16_pk_read's arrays, encoded on the device where the key lies and brought back in
+// pieces through the pinned ring.  The handle holds neither gamma_g2 nor gamma_abc_g1: the caller passes them.
+int zkg16_pk_save(zkg16_ctx *ctx, uint64_t pk_handle, const uint64_t gamma_g2[24], const uint64_t *gamma_abc_g1, uint8_t *out, size_t cap, size_t *written) {
+    if (!gamma_g2 || !gamma_abc_g1 || !out || !written) return ZKG16_ERR_BAD_ARG;
+    ZK_API_BEGIN(ctx)
+    std::shared_lock<std::shared_mutex> keys(ctx->key_rw);
+    auto pk_ref = ctx->pks.get(pk_handle); PkDev *pk = pk_ref.get();
+    if (!pk) return ZKG16_ERR_BAD_HANDLE;
+    if (!pk->full) return ZKG16_ERR_UNSUPPORTED;
+    size_t total = 0;
+    if (!pkb_size(pk->num_instance, pk->m_total, pk->n_h_total, total) || cap < total) {
+        ctx->last_error = "zkg16_pk_save: cap " + std::to_string(cap) + " is below the key's " + std::to_string(total) + " bytes";
+        return ZKG16_ERR_BAD_ARG;
+    }
+    const double t0 = now_ms();
+    memset(ctx->pkb_timings, 0, sizeof ctx->pkb_timings);
+    const size_t piece = pkb_piece(ctx, 96);
+    PkbPipe pipe(ctx, piece * 96);
+    PkbArr arr[5];
+    pkb_arrays(*pk, arr);
+    // where each section goes
+    uint8_t *p = out + PKB_HEAD + 8 + 48 * pk->num_instance + 96;
+    uint8_t *q_at[5];
+    size_t n5[5];
+    for (int q = 0; q < 5; q++) {
+        n5[q] = arr[q].n;
+        q_at[q] = p + 8;
+        p += 8 + PKB_QSIZE[q] * arr[q].n;
+    }
+    for (int q = 0; q < 5; q++) {
+        for (size_t off = 0; off < arr[q].n; off += piece) {
+            const size_t cnt = arr[q].n - off < piece ? arr[q].n - off : piece;
+            const int s = pipe.claim();
+            if (off == 0) ZK_HIP(hipEventRecord(pipe.ev.ev[2 * q], ctx->stream));
+            pk_bytes_encode_launch(ctx->stream, arr[q].group, arr[q].base + off * arr[q].stride, arr[q].stride, cnt, pipe.dev[s].as<uint8_t>());
+            pipe.download(s, q_at[q] + off * PKB_QSIZE[q], cnt * PKB_QSIZE[q]);
+        }
+        if (arr[q].n) ZK_HIP(hipEventRecord(pipe.ev.ev[2 * q + 1], ctx->stream));
+    }
+    // the verifying key and the single points on the host meanwhile
+    const double tv = now_ms();
+    {
+        uint64_t limbs[24];
+        uint8_t *v = out;
+        point_to_abi(pk->alpha_g1, limbs, nullptr); (void)zkg16_points_compress(1, limbs, nullptr, 1, v); v += 48;
+        point_to_abi(pk->beta_g2, limbs, nullptr); (void)zkg16_points_compress(2, limbs, nullptr, 1, v); v += 96;
+        (void)zkg16_points_compress(2, gamma_g2, nullptr, 1, v); v += 96;
+        point_to_abi(pk->delta_g2, limbs, nullptr); (void)zkg16_points_compress(2, limbs, nullptr, 1, v); v += 96;
+        put_le64(v, pk->num_instance); v += 8;
+        pkb_compress_host(1, gamma_abc_g1, nullptr, pk->num_instance, 0, v); v += 48 * pk->num_instance;
+        point_to_abi(pk->beta_g1, limbs, nullptr); (void)zkg16_points_compress(1, limbs, nullptr, 1, v); v += 48;
+        point_to_abi(pk->delta_g1, limbs, nullptr); (void)zkg16_points_compress(1, limbs, nullptr, 1, v);
+        for (int q = 0; q < 5; q++) put_le64(q_at[q] - 8, arr[q].n);
+    }
+    ctx->pkb_timings[B_VK] = (float)(now_ms() - tv);
+    pipe.flush_all();
+    ZK_HIP(hipStreamSynchronize(ctx->stream));
+    *written = total;
+    pkb_query_times(ctx, pipe, n5);
+    ctx->pkb_timings[B_COPY] = (float)pipe.host_ms;
+    ctx->pkb_timings[B_TOTAL] = (float)(now_ms() - t0);
+    ZK_API_END(ctx)
+}
+
+// A whole key from its bytes, decoded on the device straight into the key's arrays: the handle zkg16_pk_load makes from
+// zkg16_pk_deserialize_host's arrays.  All or nothing.
+int zkg16_pk_load_bytes(zkg16_ctx *ctx, const uint8_t *bytes, size_t len, int validate, uint64_t *pk_handle, uint64_t alpha_g1[12], uint64_t beta_g2[24],
+                        uint64_t gamma_g2[24], uint64_t delta_g2[24], uint64_t *gamma_abc_g1, size_t cap_abc) {
+    if (!bytes || !pk_handle || !alpha_g1 || !beta_g2 || !gamma_g2 || !delta_g2 || !gamma_abc_g1) return ZKG16_ERR_BAD_ARG;
+    ZK_API_BEGIN(ctx)
+    auto refuse = [&](const std::string &text) { ctx->last_error = text; return ZKG16_ERR_BAD_ARG; };
+    PkbLayout L;
+    {
+        std::string err;
+        if (!pkb_walk(bytes, len, L, err)) return refuse(err);
+    }
+    if (cap_abc < L.ni) return refuse("zkg16_pk_load_bytes: cap_abc " + std::to_string(cap_abc) + " is below num_instance " + std::to_string(L.ni));
+    if (L.m + 3 >= ((size_t)1 << 32) || L.n_h >= ((size_t)1 << 32)) return refuse("zkg16_pk_load_bytes: a query of 2^32 points or more");
+    const double t0 = now_ms();
+    memset(ctx->pkb_timings, 0, sizeof ctx->pkb_timings);
+    // the six single points on the host, in file order; gamma_abc_g1 lies between the fourth and the fifth, so a failure of the
+    // last two is reported only when gamma_abc_g1 (decoded on the host for that rare answer) has none
+    PkbSingle sp[6];
+    pkb_singles(L, sp);
+    uint64_t single[6][24];
+    for (int i = 0; i < 6; i++) {
+        const std::string t = pkb_single_host(sp[i], bytes, 0, single[i]);
+        if (t.empty()) continue;
+        if (i >= 4) {
+            std::vector<uint64_t> abc(12 * L.ni);
+            std::vector<uint8_t> abc_inf(L.ni);
+            size_t at = 0;
+            if (const int st = pkb_decode_host(1, bytes + L.at_abc, L.ni, 0, 0, abc.data(), abc_inf.data(), at)) return refuse(pkb_status_text("gamma_abc_g1", true, at, st));
+        }
+        return refuse(t);
+    }
+    auto pk = std::make_unique<PkDev>();
+    pk->num_instance = L.ni;
+    pk->m_total = L.m;
+    pk->n_h_total = L.n_h;
+    pk->z_lo = 0; pk->z_hi = L.m; pk->h_lo = 0; pk->h_hi = L.n_h;
+    pk->blinding = true;
+    pk->full = true;
+    const size_t nz = L.m;
+    pk->a.alloc((nz + 3) * sizeof(G1AffineU));
+    pk->b1.alloc((nz + 3) * sizeof(G1AffineU));
+    pk->l.alloc((nz + 3) * sizeof(G1AffineU));
+    pk->b2.alloc((nz + 3) * sizeof(G2AffineU));
+    pk->h.alloc((L.n_h ? L.n_h : 1) * sizeof(G1AffineU));
+    ZK_HIP(hipMemsetAsync(pk->a.p, 0, pk->a.bytes, ctx->stream));      // (0,0) = infinity everywhere by default
+    ZK_HIP(hipMemsetAsync(pk->b1.p, 0, pk->b1.bytes, ctx->stream));
+    ZK_HIP(hipMemsetAsync(pk->l.p, 0, pk->l.bytes, ctx->stream));
+    ZK_HIP(hipMemsetAsync(pk->b2.p, 0, pk->b2.bytes, ctx->stream));
+    const size_t piece = pkb_piece(ctx, 96);
+    PkbPipe pipe(ctx, piece * 96);
+    DevBuf res(12 * sizeof(uint64_t)), abc_u(L.ni * sizeof(G1AffineU)), abc_sat(L.ni * (sizeof(G1Affine) + 1));
+    pk_bytes_init_launch(ctx->stream, res.as<uint64_t>(), 6);
+    struct Dst { int group; unsigned char *base; size_t stride, n; const uint8_t *src; };
+    const Dst dst[6] = {
+        {1, pk->a.as<unsigned char>(), sizeof(G1AffineU), L.m, bytes + L.at_q[0]},
+        {1, pk->b1.as<unsigned char>(), sizeof(G1AffineU), L.m, bytes + L.at_q[1]},
+        {2, pk->b2.as<unsigned char>(), sizeof(G2AffineU), L.m, bytes + L.at_q[2]},
+        {1, pk->h.as<unsigned char>(), sizeof(G1AffineU), L.n_h, bytes + L.at_q[3]},
+        {1, pk->l.as<unsigned char>() + L.ni * sizeof(G1AffineU), sizeof(G1AffineU), L.n_l, bytes + L.at_q[4]},      // l_query[j] at the index of its scalar
+        {1, abc_u.as<unsigned char>(), sizeof(G1AffineU), L.ni, bytes + L.at_abc},
+    };
+    const double tv = now_ms();
+    for (int qq = 0; qq < 6; qq++) {
+        const int q = (qq + 5) % 6;      // gamma_abc_g1 first, then the queries in file order
+        const size_t sz = dst[q].group == 1 ? 48 : 96;
+        for (size_t off = 0; off < dst[q].n; off += piece) {
+            const size_t cnt = dst[q].n - off < piece ? dst[q].n - off : piece;
+            const int s = pipe.upload(dst[q].src + off * sz, cnt * sz);
+            if (off == 0 && q < 5) ZK_HIP(hipEventRecord(pipe.ev.ev[2 * q], ctx->stream));
+            pk_bytes_decode_launch(ctx->stream, dst[q].group, pipe.dev[s].as<uint8_t>(), cnt, dst[q].base + off * dst[q].stride, dst[q].stride, off, res.as<uint64_t>() + 2 * q);
+            pipe.kernel_done(s);
+        }
+        if (dst[q].n && q < 5) ZK_HIP(hipEventRecord(pipe.ev.ev[2 * q + 1], ctx->stream));
+        if (q == 5) {      // gamma_abc_g1 back as limbs
+            pk_bytes_read_launch(ctx->stream, 1, abc_u.p, sizeof(G1AffineU), L.ni, abc_sat.as<uint64_t>(), abc_sat.as<uint8_t>() + L.ni * sizeof(G1Affine));
+            ctx->pkb_timings[B_VK] = (float)(now_ms() - tv);
+        }
+    }
+    uint64_t host[12];
+    std::vector<uint64_t> abc(12 * L.ni);
+    ZK_HIP(hipMemcpyAsync(host, res.p, sizeof host, hipMemcpyDeviceToHost, ctx->stream));      // the failures of the whole call, once
+    ZK_HIP(hipMemcpyAsync(abc.data(), abc_sat.p, L.ni * sizeof(G1Affine), hipMemcpyDeviceToHost, ctx->stream));
+    ZK_HIP(hipStreamSynchronize(ctx->stream));
+    for (int qq = 0; qq < 6; qq++) {
+        const int q = (qq + 5) % 6;
+        if (host[2 * q]) return refuse(pkb_status_text(q == 5 ? "gamma_abc_g1" : PK_QUERY_NAMES[q], true, (size_t)(host[2 * q + 1] >> 3), (int)(host[2 * q + 1] & 7)));
+    }
+    pk->alpha_g1 = g1_from_abi(single[0], 0);
+    pk->beta_g2 = g2_from_abi(single[1], 0);
+    pk->delta_g2 = g2_from_abi(single[3], 0);
+    pk->beta_g1 = g1_from_abi(single[4], 0);
+    pk->delta_g1 = g1_from_abi(single[5], 0);
+    // the blinding slots and the B-side mask, as zkg16_pk_load_range
+    upload_one<G1Affine>(ctx, pk->a.as<G1AffineU>() + nz + 0, pk->delta_g1);
+    upload_one<G1Affine>(ctx, pk->b1.as<G1AffineU>() + nz + 1, pk->delta_g1);
+    upload_one<G2Affine>(ctx, pk->b2.as<G2AffineU>() + nz + 1, pk->delta_g2);
+    upload_one<G1Affine>(ctx, pk->l.as<G1AffineU>() + nz + 2, pk->delta_g1);
+    pk->b_mask.alloc(nz + 3);
+    pk->b_skipped = b_density_mask_run(ctx, pk->b1.as<G1AffineU>(), pk->b2.as<G2AffineU>(), nz + 3, pk->b_mask.as<uint8_t>());
+    if (validate || ctx->opt.pk_validate) {      // before the handle exists, as zkg16_pk_load_range; the verifying key's own points on the host
+        PkCheckResult chk;
+        pk_check_run(ctx, *pk, chk);
+        ctx->pkb_timings[B_CHECK] = ctx->pkc_timings[K_TOTAL];
+        if (!chk.ok()) return refuse(pk_check_text(chk));
+        int ok = 0;
+        if (zkg16_point_check(2, single[2], &ok) != ZKG16_OK || !ok) return refuse("pk_validate: not a point of the group: gamma_g2");
+        for (size_t i = 0; i < L.ni; i++) {
+            bool zero = true;
+            for (int k = 0; k < 12; k++) zero = zero && abc[12 * i + k] == 0;
+            if (zero) continue;      // the point at infinity passes, as in the queries
+            if (zkg16_point_check(1, abc.data() + 12 * i, &ok) != ZKG16_OK || !ok) return refuse("pk_validate: not a point of the group: gamma_abc_g1[" + std::to_string(i) + "]");
+        }
+    }
+    size_t n5[5];
+    for (int q = 0; q < 5; q++) n5[q] = dst[q].n;
+    pkb_query_times(ctx, pipe, n5);
+    ctx->pkb_timings[B_COPY] = (float)pipe.host_ms;
+    memcpy(alpha_g1, single[0], 12 * sizeof(uint64_t));
+    memcpy(beta_g2, single[1], 24 * sizeof(uint64_t));
+    memcpy(gamma_g2, single[2], 24 * sizeof(uint64_t));
+    memcpy(delta_g2, single[3], 24 * sizeof(uint64_t));
+    memcpy(gamma_abc_g1, abc.data(), 12 * L.ni * sizeof(uint64_t));
+    *pk_handle = ctx->next_handle++;
+    ctx->pks.put(*pk_handle, std::move(pk));
+    ctx->pkb_timings[B_TOTAL] = (float)(now_ms() - t0);
+    ZK_API_END(ctx)
+}
+
+int zkg16_pk_bytes_timings(zkg16_ctx *ctx, float *ms, int cap) {
+    if (!ctx || !ms || cap < 0) return ZKG16_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    const int n = cap < B_COUNT ? cap : B_COUNT;
+    memcpy(ms, ctx->pkb_timings, n * sizeof(float));
+    return n;
 }
 
 }  // extern "C"

@@ -254,7 +254,7 @@ struct MsmWorkspace {       // grown on demand, reused across proofs
 };
 
 // sizes of zkg16_ctx::timings (22 slots in use, declared with two to spare) and ::vb_timings
-constexpr int PROOF_TIMING_SLOTS = 24, VERIFY_TIMING_SLOTS = 15, RERANDOMIZE_TIMING_SLOTS = 8, PK_CHECK_TIMING_SLOTS = 8;
+constexpr int PROOF_TIMING_SLOTS = 24, VERIFY_TIMING_SLOTS = 15, RERANDOMIZE_TIMING_SLOTS = 8, PK_CHECK_TIMING_SLOTS = 8, PK_BYTES_TIMING_SLOTS = 9;
 
 }  // namespace zk
 
@@ -378,6 +378,7 @@ struct zkg16_ctx {
         int rerandomize_pass = 0;                     // zkg16_rerandomize_batch[_wire]: proofs per launch (0 = 65,536; tests lower it to reach several passes at small k)
         int trapdoor_pass = 0;                        // zkg16_prove_trapdoor_batch: requests per device pass (0 = 65,535; tests lower it to reach several passes at small k)
         int pk_validate = 0;                          // 1: zkg16_pk_load / zkg16_pk_load_range check every point of the key on the device (zkg16_pk_check) before the handle exists and refuse a bad key
+        int pk_bytes_piece = 0;                       // zkg16_pk_load_bytes / zkg16_pk_save / zkg16_pk_read: points per piece of a query (0 = 524,288: two pieces of G2 bytes in flight are 96 MiB of HBM beside the key; tests lower it to reach several pieces at small keys)
         int verify_each_after_set = 0;                // 1: the caller set "verify_each_after" (the u64 entries read an unset option as 1; the stored value cannot tell unset from 32)
     } opt;
     std::map<std::string, zk::KernelStat> kstats;
@@ -386,6 +387,7 @@ struct zkg16_ctx {
     size_t circuit_stage_bytes = 0;
     float vb_timings[zk::VERIFY_TIMING_SLOTS] = {0};                    // zkg16_verify_batch_timings (root: the last batch verified on any lane)
     float pkc_timings[zk::PK_CHECK_TIMING_SLOTS] = {0};                 // zkg16_pk_check_timings (under mu: the last zkg16_pk_check / zkg16_points_check_bulk / validated load)
+    float pkb_timings[zk::PK_BYTES_TIMING_SLOTS] = {0};                 // zkg16_pk_bytes_timings (under mu: the last zkg16_pk_load_bytes / zkg16_pk_save / zkg16_pk_read)
     float rr_timings[zk::RERANDOMIZE_TIMING_SLOTS] = {0};               // zkg16_rerandomize_timings (root: the last batch re-randomised on any lane)
     int num_cus = 256;
     bool lds_attr_fixup[2] = {false, false}, lds_attr_ntt = false, lds_attr_linear_elim = false;      // hipFuncSetAttribute(max dynamic LDS) done on this device

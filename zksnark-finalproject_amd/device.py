@@ -130,6 +130,55 @@ class Device:
         n = self.lib.zkg16_pk_check_timings(self.ctx, ms, 8)
         return {name: float(ms[i]) for i, name in enumerate((PK_QUERIES + ("total_ms", "bulk_kernel_ms", "bulk_upload_ms"))[:n])}
 
+    # ---- a resident key as arkworks' ProvingKey bytes (wire.pk_serialize_compressed / pk_deserialize_compressed are the host forms)
+    def pk_read(self, pk_h):
+        """A whole resident key copied back as the dict pk_load takes, flags included (zkg16_pk_read): level 0 of a window table at
+        either stride, without the blinding slots.  A shard: Zkg16Error, status 7."""
+        from . import wire
+        d = [C.c_size_t() for _ in range(3)]
+        self._check(self.lib.zkg16_pk_read(self.ctx, pk_h, *([None] * 15), *[C.byref(x) for x in d]))
+        ni, m, n_h = (int(x.value) for x in d)
+        pk, _, ptrs = wire._pk_arrays(ni, m, n_h)
+        self._check(self.lib.zkg16_pk_read(self.ctx, pk_h, *ptrs, None, None, None))
+        pk["num_instance"] = ni
+        return pk
+
+    def pk_save(self, pk_h, vk):
+        """A whole resident key -> ProvingKey::serialize_compressed bytes, encoded on the device (zkg16_pk_save): byte for byte
+        wire.pk_serialize_compressed(self.pk_read(pk_h), vk).  vk: gamma_g2 and gamma_abc_g1 are read (the handle holds neither)."""
+        from . import wire
+        d = [C.c_size_t() for _ in range(3)]
+        self._check(self.lib.zkg16_pk_read(self.ctx, pk_h, *([None] * 15), *[C.byref(x) for x in d]))
+        ni, m, n_h = (int(x.value) for x in d)
+        gabc = _u64(vk["gamma_abc_g1"]).reshape(-1, 12)
+        if gabc.shape[0] != ni:
+            raise ValueError("pk_save: %d gamma_abc_g1 points for a key with %d instance variables" % (gabc.shape[0], ni))
+        out = np.zeros(wire.pk_bytes_size(ni, m, n_h), dtype=np.uint8)
+        written = C.c_size_t()
+        self._check(self.lib.zkg16_pk_save(self.ctx, pk_h, _ptr(_u64(vk["gamma_g2"]).reshape(24)), _ptr(gabc), _ptr(out), out.size, C.byref(written)))
+        return out[:written.value].tobytes()
+
+    def pk_load_bytes(self, raw, validate=False):
+        """ProvingKey bytes (bytes or a uint8 array: np.fromfile, np.memmap) -> (pk handle, vk dict), decoded on the device
+        (zkg16_pk_load_bytes): the handle pk_load gives for wire.pk_deserialize_compressed(raw).  validate: pk_check's test before
+        the handle exists.  A refusal (Zkg16Error, status 1) names the entry and its decoder status and leaves nothing behind."""
+        from . import wire
+        b = wire._raw_u8(raw)
+        ni = wire.pk_bytes_dims(b)[0]
+        vk = dict(alpha_g1=np.zeros(12, np.uint64), beta_g2=np.zeros(24, np.uint64), gamma_g2=np.zeros(24, np.uint64),
+                  delta_g2=np.zeros(24, np.uint64), gamma_abc_g1=np.zeros((ni, 12), np.uint64))
+        h = C.c_uint64()
+        self._check(self.lib.zkg16_pk_load_bytes(self.ctx, _ptr(b), b.size, 1 if validate else 0, C.byref(h), _ptr(vk["alpha_g1"]), _ptr(vk["beta_g2"]),
+                                                 _ptr(vk["gamma_g2"]), _ptr(vk["delta_g2"]), _ptr(vk["gamma_abc_g1"]), ni))
+        return h.value, vk
+
+    def pk_bytes_timings(self):
+        """ms of the last pk_load_bytes / pk_save / pk_read (zkg16_pk_bytes_timings): copy_ms (host time in the staging ring), the
+        kernels of each query by name (device events, first piece to last), vk_ms, check_ms, total_ms (wall)."""
+        ms = (C.c_float * 9)()
+        n = self.lib.zkg16_pk_bytes_timings(self.ctx, ms, 9)
+        return {name: float(ms[i]) for i, name in enumerate((("copy_ms",) + PK_QUERIES + ("vk_ms", "check_ms", "total_ms"))[:n])}
+
     def pk_precompute(self, pk_h, window_bits_z=0, window_bits_h=0):
         """Window tables for a key that stays resident (zkg16_pk_precompute): same proofs, fewer bucket additions.
         0 = width chosen from the query length, < 0 = leave that side without a table.  The entries are laid out as option

@@ -408,6 +408,28 @@ def _key_checked(dev, stack, ph, check_key):
     return dict(key_ok=dev.pk_check(ph)["ok"])
 
 
+def key_to_bytes(dev, key):
+    """A kept key (fibonacci_key's, linear_key's, prime_template_key's or a matrix key's dict: ph and vk are read) -> its proving key
+    as ark-groth16's ProvingKey::serialize_compressed bytes, encoded on the device where it lies (Device.pk_save).  The bytes hold
+    the verifying key too.  They do not hold the R1CS handle (a circuit's matrices are rebuilt from its size: Device.r1cs_fibonacci,
+    r1cs_linear, r1cs_matrix, r1cs_prime_template), window tables (Device.pk_precompute rebuilds them) or the prime template's
+    `corr`: three G1 points outside ark's struct, which stay the caller's to keep, through wire.points_compress."""
+    return dev.pk_save(key["ph"], key["vk"])
+
+
+def key_from_bytes(dev, raw, rh, check_key=False):
+    """key_to_bytes' inverse: ProvingKey bytes (bytes or a uint8 array) decoded on the device (Device.pk_load_bytes) -> dict(ph, rh,
+    vk), the shape prove_fibonaccis, prove_linear_equations_batch and prove_matrices take as key=; rh is the caller's R1CS handle of
+    the key's circuit and is passed through.  The caller frees ph and rh.  Bytes that do not decode raise (Zkg16Error, status 1,
+    naming the entry) and leave nothing resident.  check_key: as fibonacci_key — key_ok = Device.pk_check's verdict.  The prime
+    template's `corr` is not part of the bytes: a caller that kept it (wire.points_compress) adds it to the dict itself."""
+    with contextlib.ExitStack() as stack:
+        ph, vk = dev.pk_load_bytes(raw)
+        checked = _key_checked(dev, stack, ph, check_key)
+        stack.pop_all()
+    return dict(ph=ph, rh=rh, vk=vk, setup_time=0.0, **checked)
+
+
 def fibonacci_key(dev, num_of_rounds, rng, check_key=False):
     """The key every Fibonacci request of one round count shares: the circuit's matrices depend on the round count alone
     (Device.r1cs_fibonacci), so prove_fibonacci's draws from rng in its order (trapdoor, generators) and one setup give the key

@@ -347,3 +347,105 @@ def encode_pvk(vk):
 
 def decode_pvk(s):
     return pvk_deserialize_compressed(base64.standard_b64decode(s))
+
+
+# ---- ProvingKey (ark-groth16 0.4 data_structures.rs: ProvingKey { vk, beta_g1, delta_g1, a_query, b_g1_query, b_g2_query, h_query,
+# l_query }, derived CanonicalSerialize = the fields in order, a Vec as a u64 LE count and its items).  The host forms of the library
+# (zkg16_pk_serialize_host / zkg16_pk_deserialize_host); Device.pk_save / Device.pk_load_bytes are the same bytes made and read on the
+# device.  The layout is the published one; parity with bytes from a real arkworks build is unpinned, as for the prepared key above.
+_PK_QUERIES = (("a_query", "a_inf", 12), ("b_g1_query", "b_g1_inf", 12), ("b_g2_query", "b_g2_inf", 24), ("h_query", "h_inf", 12), ("l_query", "l_inf", 12))
+_PK_SINGLES = (("alpha_g1", 12), ("beta_g1", 12), ("beta_g2", 24), ("delta_g1", 12), ("delta_g2", 24))
+
+
+def _raw_u8(b):
+    """bytes, bytearray, memoryview or a uint8 array (np.fromfile, np.memmap) -> a contiguous uint8 array, without a copy where possible"""
+    if isinstance(b, np.ndarray):
+        return np.ascontiguousarray(b, dtype=np.uint8).reshape(-1)
+    return np.frombuffer(b, dtype=np.uint8)
+
+
+def _host_refusal(what):
+    from . import _lib
+    return ValueError("%s: %s" % (what, _lib.load().zkg16_last_error(None).decode()))
+
+
+def pk_bytes_dims(b):
+    """The dimensions a serialized proving key states -> (num_instance, m, n_h, n_l); only its five length prefixes are read, each
+    checked against the bytes that remain (zkg16_pk_bytes_dims).  ValueError names the field that does not fit."""
+    import ctypes as C
+    from . import _lib
+    raw = _raw_u8(b)
+    d = [C.c_size_t() for _ in range(4)]
+    if _lib.load().zkg16_pk_bytes_dims(raw.ctypes.data_as(C.c_void_p), raw.size, *[C.byref(x) for x in d]):
+        raise _host_refusal("proving key")
+    return tuple(int(x.value) for x in d)
+
+
+def pk_bytes_size(num_instance, m, n_h):
+    """The length of a serialized proving key of these dimensions (zkg16_pk_bytes_size)."""
+    import ctypes as C
+    from . import _lib
+    out = C.c_size_t()
+    if _lib.load().zkg16_pk_bytes_size(num_instance, m, n_h, C.byref(out)):
+        raise _host_refusal("proving key")
+    return int(out.value)
+
+
+def pk_serialize_compressed(pk, vk, threads=0):
+    """(pk dict as Device.pk_load takes, vk dict with gamma_g2 and gamma_abc_g1) -> ProvingKey::serialize_compressed bytes, on host
+    threads (zkg16_pk_serialize_host)."""
+    import ctypes as C
+    from . import _lib
+    keep, args = [], []
+    for name, flag, w in _PK_QUERIES:
+        pts = np.ascontiguousarray(pk[name], dtype=np.uint64).reshape(-1, w)
+        inf = None if pk.get(flag) is None else np.ascontiguousarray(pk[flag], dtype=np.uint8).reshape(-1)
+        if inf is not None and inf.shape[0] != pts.shape[0]:
+            raise ValueError("%s has %d flags for %d points" % (flag, inf.shape[0], pts.shape[0]))
+        keep += [pts, inf]
+        args += [pts.ctypes.data_as(C.c_void_p), None if inf is None else inf.ctypes.data_as(C.c_void_p)]
+    for name, w in _PK_SINGLES:
+        keep.append(np.ascontiguousarray(pk[name], dtype=np.uint64).reshape(w))
+        args.append(keep[-1].ctypes.data_as(C.c_void_p))
+    g2 = np.ascontiguousarray(vk["gamma_g2"], dtype=np.uint64).reshape(24)
+    gabc = np.ascontiguousarray(vk["gamma_abc_g1"], dtype=np.uint64).reshape(-1, 12)
+    m, n_h, ni = keep[0].shape[0], keep[6].shape[0], gabc.shape[0]
+    if keep[2].shape[0] != m or keep[4].shape[0] != m or keep[8].shape[0] != m - ni:
+        raise ValueError("query lengths do not fit one key")
+    out = np.zeros(pk_bytes_size(ni, m, n_h), dtype=np.uint8)
+    written = C.c_size_t()
+    if _lib.load().zkg16_pk_serialize_host(*args, g2.ctypes.data_as(C.c_void_p), gabc.ctypes.data_as(C.c_void_p), ni, m, n_h, threads,
+                                           out.ctypes.data_as(C.c_void_p), out.size, C.byref(written)):
+        raise _host_refusal("proving key")
+    assert written.value == out.size
+    return out.tobytes()
+
+
+def _pk_arrays(ni, m, n_h):
+    """empty arrays of a key of these dimensions -> (pk dict, vk dict, the pointers in the C entries' order)"""
+    import ctypes as C
+    n = dict(a_query=m, b_g1_query=m, b_g2_query=m, h_query=n_h, l_query=m - ni)
+    pk, ptrs = {}, []
+    for name, flag, w in _PK_QUERIES:
+        pk[name], pk[flag] = np.zeros((n[name], w), dtype=np.uint64), np.zeros(n[name], dtype=np.uint8)
+        ptrs += [pk[name].ctypes.data_as(C.c_void_p), pk[flag].ctypes.data_as(C.c_void_p)]
+    for name, w in _PK_SINGLES:
+        pk[name] = np.zeros(w, dtype=np.uint64)
+        ptrs.append(pk[name].ctypes.data_as(C.c_void_p))
+    vk = dict(gamma_g2=np.zeros(24, dtype=np.uint64), gamma_abc_g1=np.zeros((ni, 12), dtype=np.uint64))
+    return pk, vk, ptrs
+
+
+def pk_deserialize_compressed(b, validate=True, threads=0):
+    """ProvingKey::deserialize_compressed on host threads (zkg16_pk_deserialize_host) -> (pk dict for Device.pk_load, vk dict).
+    ValueError names the first entry in file order that does not decode and its decoder status, e.g. "b_g2_query[17]: status 4"."""
+    import ctypes as C
+    from . import _lib
+    raw = _raw_u8(b)
+    ni, m, n_h, _ = pk_bytes_dims(raw)
+    pk, vk, ptrs = _pk_arrays(ni, m, n_h)
+    if _lib.load().zkg16_pk_deserialize_host(raw.ctypes.data_as(C.c_void_p), raw.size, 1 if validate else 0, threads, *ptrs,
+                                             vk["gamma_g2"].ctypes.data_as(C.c_void_p), vk["gamma_abc_g1"].ctypes.data_as(C.c_void_p)):
+        raise _host_refusal("proving key")
+    vk.update(alpha_g1=pk["alpha_g1"], beta_g2=pk["beta_g2"], delta_g2=pk["delta_g2"])
+    return pk, vk
